@@ -17,7 +17,8 @@ configs[3], 64 mixed-size pages for the whole job, cost-sharded (LPT) over the r
 filled (reference demo/demo_vllm_svg.py:28), 4096 new tokens, GREEDY (the reference samples this task at T = 0.9), fp8 (e4m3,
 per-output-channel scale) weights; B = 1.  --fp8 0/1 overrides the weight format of any workload.
 
-Prints ONE JSON line on rank 0 (see README/DESIGN for the field contract).
+Prints ONE JSON line on rank 0 (see README/DESIGN for the field contract).  --dump-outputs DIR also writes the last timed step's
+token ids as DIR/*.npy (inputs and weights are seeded: the same arguments give the same inputs on every run).
 """
 from __future__ import annotations
 
@@ -75,7 +76,13 @@ def parse():
                     help="a4 / highres / svg: distinct page sets the steps rotate through (default 2 with the pipelined step, else 1): step k processes set k mod n, "
                          "all sets resident in HBM, each set's tokens checked against its own sequential batch")
     ap.add_argument("--seed", type=int, default=0)
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned (every page's generated token ids, gathered over the ranks) "
+                         "as DIR/<name>.npy in float32, for comparing two builds output for output")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def respawn_under_torchrun(a):
@@ -211,6 +218,32 @@ def other_config_legs():
             out[name] = {"failed": True, "error": repr(e)[:300]}
         out[name]["leg_wall_s"] = time.perf_counter() - t0
     return out
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(d, gathered, max_new_tokens):
+    """--dump-outputs: the job's result of the last timed step — (page index, generated token ids) per page, as dp.gather_token_ids returns
+    it — as float32 arrays (token ids are below 2**24, so exact): token_ids [pages, max_new_tokens] padded with -1, token_lengths [pages],
+    page_index [pages].  Above DUMP_MAX_BYTES the rows are a fixed seeded sample of the pages, in page order."""
+    n = len(gathered)
+    row_bytes = 4 * (max_new_tokens + 2)
+    rows = np.arange(n)
+    if n * row_bytes > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_BYTES // row_bytes, replace=False))
+    ids = np.full((len(rows), max_new_tokens), -1, np.float32)
+    lens = np.zeros(len(rows), np.float32)
+    for r, i in enumerate(rows):
+        toks = np.asarray(gathered[i][1], np.int64)
+        assert len(toks) <= max_new_tokens and (toks.size == 0 or int(toks.max()) < 2 ** 24)
+        ids[r, :len(toks)], lens[r] = toks, len(toks)
+    out = {"token_ids": ids, "token_lengths": lens, "page_index": np.asarray([gathered[i][0] for i in rows], np.float32)}
+    d = Path(d)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, arr in out.items():
+        np.save(d / f"{name}.npy", arr)
+    return {"dir": str(d), "files": sorted(f"{name}.npy" for name in out), "pages": int(len(rows)), "pages_in_job": n}
 
 
 def mixed_pages(n_total, seed=2025):
@@ -719,6 +752,8 @@ def main():
         }
         if parity:
             res.update(parity)
+        if a.dump_outputs:
+            res["dump_outputs"] = dump_outputs(a.dump_outputs, gathered, a.max_new_tokens)
         if per_rank:
             res["per_rank"] = per_rank
         if mixed:
