@@ -11,6 +11,14 @@
 //                -> chunk (slab,dg), lane (g,i) = V^T[16dg+i][keys 32slab + {4g..4g+3, 16+4g..16+4g+3}]
 //                   which is exactly the key order in which a lane holds P^T after the S^T MFMAs
 //                   (A of O^T = V^T.P^T).
+// fp8 KV cache (DotsConfig.kv_cache_dtype = 1, opt-in): OCP e4m3fn, one fp32 scale s per (layer, kv head, K|V) (kv_scales [layers][Hkv][2]),
+// stored = e4m3fn(clamp(x / s, -448, 448)) rounded to nearest even, x = the bf16 value the bf16 pool would hold; dequantised = float(stored) * s.
+//   pool8[layer][page][kv_head][0 = K | 1 = V][8192 B]             (K 8 KiB + V 8 KiB per (page, kv head), 64 tokens as before)
+//   the same chunks and lanes as above, one byte per element, CHUNK PAIRS interleaved:
+//   element (chunk c, lane l, j)  ->  byte (c >> 1) * 1024 + l * 16 + (c & 1) * 8 + j         (decode_layout.h kv8_byte / k8_off / v8_off)
+//   so a lane's 16-byte load at (c2 * 64 + l) * 16 is its fragment of chunks 2 c2 and 2 c2 + 1: 8 x 1 KiB loads for K, 8 for V, each
+//   converted in registers (v_cvt_scalef32_pk_bf16_fp8, scale 1, exact) to exactly the two bf16x8 A operands the bf16 page gives.
+//   The attention kernel folds s_K into its softmax scale and multiplies its partial O by s_V; m, l and the combine kernel are unchanged.
 //
 // Dense layers at M = B <= 16 rows (decode_fused.hip): skinny GEMM on MFMA with the weight tile as the A operand,
 // weights streamed straight to VGPRs (guide: "GEMV / M<=16: neither LDS nor glds"), split-K only across the waves of
@@ -27,14 +35,24 @@ TRACE_DECL
 
 // ------------------------------------------------------------------------------------------------
 // prefill -> pages.  grid (tiles, Hkv, 2); K from the rope'd head-major buffer, V from the qkv buffer.
+// KVT = uint8_t: an fp8 pool, every 16-byte bf16 chunk row is quantised with kv_scales[h][which] and stored as 8 bytes (decode_layout.h kv8_byte).
+template <typename KVT>
 __global__ __launch_bounds__(256) void kv_to_pages_kernel(const bf16_t* __restrict__ k, const bf16_t* __restrict__ qkv,
                                                           const Tile64* __restrict__ tiles, const int32_t* __restrict__ block_table,
-                                                          int max_pages, bf16_t* __restrict__ pool, int64_t T, int Hq, int Hkv) {
+                                                          int max_pages, KVT* __restrict__ pool, int64_t T, int Hq, int Hkv,
+                                                          const float* __restrict__ kv_scales) {
+    constexpr bool KV8 = sizeof(KVT) == 1;
     __shared__ __attribute__((aligned(16))) bf16_t lds[64 * 136];
     const Tile64 tl = tiles[blockIdx.x];
     const int h = blockIdx.y, which = blockIdx.z, tid = threadIdx.x;
     const int page = block_table[tl.seq * max_pages + tl.page];
-    bf16_t* dst = pool + ((size_t)(page * Hkv + h) * 2 + which) * PAGE_ELEMS;
+    KVT* dst = pool + ((size_t)(page * Hkv + h) * 2 + which) * PAGE_ELEMS;
+    float kvs = 1.0f;
+    if constexpr (KV8) kvs = kv_scales[h * 2 + which];
+    auto put = [&](int ci, u32x4 v) {          // chunk row ci (8 elements)
+        if constexpr (KV8) *reinterpret_cast<u32x2*>(dst + kv8_byte(ci * 8)) = kv8_pack8(v, kvs);
+        else *reinterpret_cast<u32x4*>(dst + (size_t)ci * 8) = v;
+    };
     if (which == 0) {
 #pragma unroll
         for (int it = 0; it < 4; ++it) {
@@ -43,7 +61,7 @@ __global__ __launch_bounds__(256) void kv_to_pages_kernel(const bf16_t* __restri
             const int key = kg * 16 + i;
             u32x4 v = {0, 0, 0, 0};
             if (key < tl.n) v = *reinterpret_cast<const u32x4*>(k + ((size_t)h * T + tl.tok0 + key) * 128 + kk * 32 + g * 8);
-            *reinterpret_cast<u32x4*>(dst + (size_t)ci * 8) = v;
+            put(ci, v);
         }
     } else {
         const int ld = (Hq + 2 * Hkv) * 128;
@@ -69,7 +87,7 @@ __global__ __launch_bounds__(256) void kv_to_pages_kernel(const bf16_t* __restri
                 const int key1 = slab * 32 + (e1 >> 2) * 16 + g * 4 + (e1 & 3);
                 o[e2] = (uint32_t)lds[key0 * 136 + d] | ((uint32_t)lds[key1 * 136 + d] << 16);
             }
-            *reinterpret_cast<u32x4*>(dst + (size_t)ci * 8) = o;
+            put(ci, o);
         }
     }
 }
@@ -125,11 +143,14 @@ __global__ __launch_bounds__(256) void convert_x_kernel(const bf16_t* __restrict
 //    1.9 us between "pages done" and the barrier behind these writes).
 constexpr int AT_LD = 132;
 
-template <int NW, bool ONE>
-__global__ __launch_bounds__(NW * 64, ONE && NW <= 4 ? 3 : 2) void decode_attn_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ pool,
+// KVT = uint8_t: the fp8 pool (layout in the header): a page is 8 + 8 sixteen-byte loads per lane, converted to the bf16 fragments of the bf16 pool
+// in registers; s_K = kv_scales[hkv][0] is folded into scale_log2e, the partial O is multiplied by s_V = kv_scales[hkv][1] as it is written.
+template <int NW, bool ONE, typename KVT = bf16_t>
+__global__ __launch_bounds__(NW * 64, ONE && NW <= 4 ? 3 : 2) void decode_attn_kernel(const bf16_t* __restrict__ q, const KVT* __restrict__ pool,
                                                           const int32_t* __restrict__ ctx_len, const int32_t* __restrict__ block_table,
                                                           int max_pages, float* __restrict__ part_o, float* __restrict__ part_ml,
-                                                          int Hq, int Hkv, int n_splits, float scale_log2e) {
+                                                          int Hq, int Hkv, int n_splits, float scale_log2e, const float* __restrict__ kv_scales) {
+    constexpr bool KV8 = sizeof(KVT) == 1;
     extern __shared__ __attribute__((aligned(16))) char at_smem[];
     const int split = blockIdx.x, hkv = blockIdx.y, b = blockIdx.z;
     const int group = Hq / Hkv;
@@ -141,6 +162,11 @@ __global__ __launch_bounds__(NW * 64, ONE && NW <= 4 ? 3 : 2) void decode_attn_k
     TRACE(0);
     const int ctx = ctx_len[b] + 1;                       // includes the token appended this step
     int page = block_table[b * max_pages + min(p0, max_pages - 1)];
+    float s_v = 1.0f;
+    if constexpr (KV8) {
+        scale_log2e *= kv_scales[hkv * 2];
+        s_v = kv_scales[hkv * 2 + 1];
+    }
     // Q fragments (B operand): lane (j = i, g) holds Q[hkv*group + j][32kk + 8g .. +7]; zero rows j >= group
     u32x4 qraw[4];
 #pragma unroll
@@ -157,15 +183,28 @@ __global__ __launch_bounds__(NW * 64, ONE && NW <= 4 ? 3 : 2) void decode_attn_k
     // one page: S^T = K.Q^T -> online softmax -> O^T += V^T.P^T.  The load / MFMA order is pinned (sched_barrier): K and V slab 0
     // first, V slab 1 only once the K registers are free.
     auto page_step = [&](int p, int pg, bool first) {
-        const bf16_t* kp = pool + ((size_t)(pg * Hkv + hkv) * 2) * PAGE_ELEMS;
-        const bf16_t* vp = kp + PAGE_ELEMS;
+        const KVT* kp = pool + ((size_t)(pg * Hkv + hkv) * 2) * PAGE_ELEMS;
+        const KVT* vp = kp + PAGE_ELEMS;
         bf16x8 kf[16], va[8], vb[8];
+        u32x4 va8[4], vb8[4];                                // fp8: the raw V loads, converted where their MFMAs issue
+        if constexpr (KV8) {
+            u32x4 k8[8];
+#pragma unroll
+            for (int c2 = 0; c2 < 8; ++c2) k8[c2] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(kp + (size_t)(c2 * 64 + l) * 16));
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int c2 = 0; c2 < 4; ++c2) va8[c2] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(vp + (size_t)(c2 * 64 + l) * 16));
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int c = 0; c < 16; ++c) kf[c] = kv8_frag(k8[c >> 1], c & 1);
+        } else {
 #pragma unroll
         for (int c = 0; c < 16; ++c) kf[c] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(kp + (size_t)(c * 64 + l) * 8));
         __builtin_amdgcn_sched_barrier(0);                   // K before V: S^T waits for K only (a wave's loads return in order)
 #pragma unroll
         for (int c = 0; c < 8; ++c) va[c] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(vp + (size_t)(c * 64 + l) * 8));
         __builtin_amdgcn_sched_barrier(0);
+        }
         bf16x8 qf[4];
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
@@ -181,8 +220,13 @@ __global__ __launch_bounds__(NW * 64, ONE && NW <= 4 ? 3 : 2) void decode_attn_k
             for (int kk = 0; kk < 4; ++kk) s[kg] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[kg * 4 + kk], qf[kk], s[kg], 0, 0, 0);
         }
         __builtin_amdgcn_sched_barrier(0);
+        if constexpr (KV8) {
+#pragma unroll
+            for (int c2 = 0; c2 < 4; ++c2) vb8[c2] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(vp + (size_t)((c2 + 4) * 64 + l) * 16));
+        } else {
 #pragma unroll
         for (int c = 0; c < 8; ++c) vb[c] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(vp + (size_t)((c + 8) * 64 + l) * 8));
+        }
         __builtin_amdgcn_sched_barrier(0);
         const int key0 = p * PAGE;
         float mx = -INFINITY;
@@ -225,10 +269,17 @@ __global__ __launch_bounds__(NW * 64, ONE && NW <= 4 ? 3 : 2) void decode_attn_k
                 for (int r = 0; r < 4; ++r) o[dg][r] *= alpha;
         }
         // V chunks arrive in order (slab 0: dg 0..7, then slab 1): consume them in that order
+        if constexpr (KV8) {
+#pragma unroll
+            for (int dg = 0; dg < 8; ++dg) o[dg] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kv8_frag(va8[dg >> 1], dg & 1), pf[0], o[dg], 0, 0, 0);
+#pragma unroll
+            for (int dg = 0; dg < 8; ++dg) o[dg] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kv8_frag(vb8[dg >> 1], dg & 1), pf[1], o[dg], 0, 0, 0);
+        } else {
 #pragma unroll
         for (int dg = 0; dg < 8; ++dg) o[dg] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(va[dg], pf[0], o[dg], 0, 0, 0);
 #pragma unroll
         for (int dg = 0; dg < 8; ++dg) o[dg] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vb[dg], pf[1], o[dg], 0, 0, 0);
+        }
     };
     if constexpr (ONE) {
         if (p0 < n_pages) page_step(p0, page, true);
@@ -263,7 +314,8 @@ __global__ __launch_bounds__(NW * 64, ONE && NW <= 4 ? 3 : 2) void decode_attn_k
             lsum += lds_l[ww * 16 + j] * f;
         }
         const size_t base = (((size_t)b * Hkv + hkv) * n_splits + split) * group + j;
-        part_o[base * 128 + d] = acc;
+        if constexpr (KV8) part_o[base * 128 + d] = acc * s_v;
+        else part_o[base * 128 + d] = acc;
         if (d == 0) { part_ml[base * 2] = m; part_ml[base * 2 + 1] = lsum; }
     }
     TRACE(4);
@@ -667,10 +719,14 @@ void dots_trace_set_decode(unsigned long long* buf) { (void)hipMemcpyToSymbol(HI
 #endif
 
 hipError_t launch_kv_to_pages(hipStream_t s, const bf16_t* k, const bf16_t* qkv, const Tile64* tiles, int n_tiles,
-                              const int32_t* block_table, int max_pages, bf16_t* pool_layer, int64_t T, int Hq, int Hkv) {
+                              const int32_t* block_table, int max_pages, void* pool_layer, int64_t T, int Hq, int Hkv, const float* kv_scales) {
     if (n_tiles <= 0) return hipSuccess;
-    hipLaunchKernelGGL(kv_to_pages_kernel, dim3(n_tiles, Hkv, 2), dim3(256), 0, s, k, qkv, tiles, block_table, max_pages,
-                       pool_layer, T, Hq, Hkv);
+    if (kv_scales)
+        hipLaunchKernelGGL(kv_to_pages_kernel<uint8_t>, dim3(n_tiles, Hkv, 2), dim3(256), 0, s, k, qkv, tiles, block_table, max_pages,
+                           (uint8_t*)pool_layer, T, Hq, Hkv, kv_scales);
+    else
+        hipLaunchKernelGGL(kv_to_pages_kernel<bf16_t>, dim3(n_tiles, Hkv, 2), dim3(256), 0, s, k, qkv, tiles, block_table, max_pages,
+                           (bf16_t*)pool_layer, T, Hq, Hkv, nullptr);
     return hipGetLastError();
 }
 
@@ -725,11 +781,12 @@ int decode_attn_splits(int max_seq_len) {
 // costs; requesting the K half early or allocating DMA changed nothing.  It therefore never runs by default: opt-in only.
 // part_cus > 0: the stream is CU-masked to that many CUs.  stream_mode: 1 = the streaming kernel wherever it is legal, 0 = never, -1 = the
 // process default (DOTS_OCR_ATTN_STREAM=1: wherever legal; DOTS_OCR_ATTN_STREAM_MIN=n: from n items per CU; unset: never).
-int decode_attn_stream_wgs(int B, int Hkv, int n_splits, int max_pages, int part_cus, int stream_mode) {
+// The streaming kernel reads bf16 pages only: 0 for an fp8 pool (kv8), whatever the mode.
+int decode_attn_stream_wgs(int B, int Hkv, int n_splits, int max_pages, int part_cus, int stream_mode, bool kv8) {
     static const int env_mode = [] { const char* e = getenv("DOTS_OCR_ATTN_STREAM"); return e ? (atoi(e) != 0 ? 1 : 0) : -1; }();
     static const int min_items = [] { const char* e = getenv("DOTS_OCR_ATTN_STREAM_MIN"); return e ? std::max(1, atoi(e)) : 0; }();
     const int mode = stream_mode >= 0 ? stream_mode : (env_mode >= 0 ? env_mode : (min_items > 0 ? -1 : 0));
-    if (mode == 0 || decode_attn_waves() != ST_NW || (int64_t)n_splits * ST_NW < max_pages || B > MAX_DECODE_ROWS) return 0;
+    if (kv8 || mode == 0 || decode_attn_waves() != ST_NW || (int64_t)n_splits * ST_NW < max_pages || B > MAX_DECODE_ROWS) return 0;
     static int n_cus = 0;
     if (n_cus == 0) {
         int dev = 0, v = 0;
@@ -741,13 +798,13 @@ int decode_attn_stream_wgs(int B, int Hkv, int n_splits, int max_pages, int part
     return items >= min_items * cus ? cus : 0;
 }
 
-hipError_t launch_decode_attn(hipStream_t s, const bf16_t* q, const bf16_t* pool_layer, const int32_t* ctx_len,
+hipError_t launch_decode_attn(hipStream_t s, const bf16_t* q, const void* pool_layer, const int32_t* ctx_len,
                               const int32_t* block_table, int max_pages, float* part_o, float* part_ml,
-                              int B, int Hq, int Hkv, int n_splits, float scale, int part_cus, int stream_mode) {
+                              int B, int Hq, int Hkv, int n_splits, float scale, int part_cus, int stream_mode, const float* kv_scales) {
     if (Hq % Hkv != 0 || Hq / Hkv > 16) return hipErrorInvalidValue;
     const float sl = scale * 1.44269504088896340736f;
     const int nw = decode_attn_waves(), group = Hq / Hkv;
-    if (const int wgs = decode_attn_stream_wgs(B, Hkv, n_splits, max_pages, part_cus, stream_mode)) {
+    if (const int wgs = decode_attn_stream_wgs(B, Hkv, n_splits, max_pages, part_cus, stream_mode, kv_scales != nullptr)) {
         static uint32_t attr = 0;
         const size_t lds_s = (size_t)ST_NW * ST_PAGE_BYTES + ((size_t)ST_NW * group * AT_LD + 2 * ST_NW * 16) * sizeof(float) + 2 * MAX_DECODE_ROWS * sizeof(int);
         int dev = 0;
@@ -759,14 +816,22 @@ hipError_t launch_decode_attn(hipStream_t s, const bf16_t* q, const bf16_t* pool
             if (e != hipSuccess) return e;
             __atomic_fetch_or(&attr, bit, __ATOMIC_RELEASE);
         }
-        hipLaunchKernelGGL(decode_attn_stream_kernel, dim3(wgs), dim3(ST_NW * 64), lds_s, s, q, pool_layer, ctx_len, block_table, max_pages, part_o, part_ml,
+        hipLaunchKernelGGL(decode_attn_stream_kernel, dim3(wgs), dim3(ST_NW * 64), lds_s, s, q, (const bf16_t*)pool_layer, ctx_len, block_table, max_pages, part_o, part_ml,
                            B, Hq, Hkv, n_splits, sl);
         return hipGetLastError();
     }
     const dim3 grid(n_splits, Hkv, B);
     const size_t lds = ((size_t)nw * group * AT_LD + 2 * nw * 16) * sizeof(float);
     const bool one = (int64_t)n_splits * nw >= max_pages;        // every wave owns at most one page: the light-weight instantiation
-#define ATTN_GO(NWV, ONEV) hipLaunchKernelGGL((decode_attn_kernel<NWV, ONEV>), grid, dim3(NWV * 64), lds, s, q, pool_layer, ctx_len, block_table, max_pages, part_o, part_ml, Hq, Hkv, n_splits, sl)
+#define ATTN_GO(NWV, ONEV)                                                                                                                    \
+    do {                                                                                                                                      \
+        if (kv_scales)                                                                                                                        \
+            hipLaunchKernelGGL((decode_attn_kernel<NWV, ONEV, uint8_t>), grid, dim3(NWV * 64), lds, s, q, (const uint8_t*)pool_layer, ctx_len, \
+                               block_table, max_pages, part_o, part_ml, Hq, Hkv, n_splits, sl, kv_scales);                                    \
+        else                                                                                                                                  \
+            hipLaunchKernelGGL((decode_attn_kernel<NWV, ONEV>), grid, dim3(NWV * 64), lds, s, q, (const bf16_t*)pool_layer, ctx_len,           \
+                               block_table, max_pages, part_o, part_ml, Hq, Hkv, n_splits, sl, nullptr);                                      \
+    } while (0)
     switch (nw) {
         case 1: if (one) ATTN_GO(1, true); else ATTN_GO(1, false); break;
         case 2: if (one) ATTN_GO(2, true); else ATTN_GO(2, false); break;

@@ -56,9 +56,12 @@ __global__ __launch_bounds__(256) void dec_embed_kernel(const int32_t* __restric
 // tensor, RoPE, q store / K, V page append.  f0 = the lane's first feature (q / k heads: rows = features (f0, f0 + 64, f0 + 1, f0 + 65); v
 // heads: f0 .. f0 + 3), row = the batch row, pos / page = its position and the page that holds it.  Shared by dec_qkv_kernel and
 // dec_qkv_wide_kernel: one definition, the same bits.
-template <typename WT>
+// KVT = the page pool's element type: bf16_t, or uint8_t for an fp8 (e4m3fn) pool, whose K / V rows are the bf16 values above quantised with
+// kvs = this kv head's K or V scale (kv8_pack2, decode_layout.h): 16-bit stores of two e4m3 values where the bf16 pool takes a bf16 pair.
+template <typename WT, typename KVT = bf16_t>
 DEVI void qkv_epilogue(f32x4 x, bool rot, int head, int Hq, int Hkv, int f0, bool has_bias, uint32_t bia0, uint32_t bia1, f32x2 sc0, f32x2 sc1,
-                       const float (&rc)[2], const float (&rs)[2], int pos, int page, int row, bf16_t* __restrict__ pool, bf16_t* __restrict__ q_out) {
+                       const float (&rc)[2], const float (&rs)[2], int pos, int page, int row, KVT* __restrict__ pool, bf16_t* __restrict__ q_out,
+                       float kvs = 1.0f) {
 #pragma clang fp contract(off)      // every fused multiply-add below is written out: the bits must not depend on the kernel this is inlined into
     const int key = pos & 63;
     // bias of rows r = 0..3: rot (lo(bia0), lo(bia1), hi(bia0), hi(bia1)), else (lo(bia0), hi(bia0), lo(bia1), hi(bia1))
@@ -77,16 +80,36 @@ DEVI void qkv_epilogue(f32x4 x, bool rot, int head, int Hq, int Hkv, int f0, boo
             bf16_t* qp = q_out + ((size_t)row * Hq + head) * 128;
             *reinterpret_cast<uint32_t*>(qp + d) = lo;
             *reinterpret_cast<uint32_t*>(qp + d + 64) = hi;
+        } else if constexpr (sizeof(KVT) == 1) {
+            uint8_t* kp = pool + ((size_t)(page * Hkv + (head - Hq)) * 2) * PAGE_BYTES8;
+            *reinterpret_cast<uint16_t*>(kp + k8_off(key, d)) = (uint16_t)kv8_pack2(lo_bf(lo), hi_bf(lo), kvs);
+            *reinterpret_cast<uint16_t*>(kp + k8_off(key, d + 64)) = (uint16_t)kv8_pack2(lo_bf(hi), hi_bf(hi), kvs);
         } else {
             bf16_t* kp = pool + ((size_t)(page * Hkv + (head - Hq)) * 2) * PAGE_ELEMS;
             *reinterpret_cast<uint32_t*>(kp + k_chunk(key, d) * 8 + (d & 7)) = lo;
             *reinterpret_cast<uint32_t*>(kp + k_chunk(key, d + 64) * 8 + (d & 7)) = hi;
         }
+    } else if constexpr (sizeof(KVT) == 1) {
+        uint8_t* vp = pool + ((size_t)(page * Hkv + (head - Hq - Hkv)) * 2 + 1) * PAGE_BYTES8;
+        const uint32_t v01 = kv8_pack2(y[0], y[1], kvs), v23 = kv8_pack2(y[2], y[3], kvs);
+        vp[v8_off(key, f0)] = (uint8_t)v01;
+        vp[v8_off(key, f0 + 1)] = (uint8_t)(v01 >> 8);
+        vp[v8_off(key, f0 + 2)] = (uint8_t)v23;
+        vp[v8_off(key, f0 + 3)] = (uint8_t)(v23 >> 8);
     } else {
         bf16_t* vp = pool + ((size_t)(page * Hkv + (head - Hq - Hkv)) * 2 + 1) * PAGE_ELEMS;
 #pragma unroll
         for (int r = 0; r < 4; ++r) vp[v_off(key, f0 + r)] = f2bf(y[r]);
     }
+}
+
+// fp32 scale of the K (rot) or V row a qkv head appends to an fp8 pool: kv_scales [Hkv][K | V]; 1 for q heads and for a bf16 pool (not read)
+template <typename KVT>
+DEVI float kv_head_scale(const float* __restrict__ kv_scales, bool rot, int head, int Hq, int Hkv) {
+    if constexpr (sizeof(KVT) == 1) {
+        if (head >= Hq) return rot ? kv_scales[(head - Hq) * 2] : kv_scales[(head - Hq - Hkv) * 2 + 1];
+    }
+    return 1.0f;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -98,13 +121,14 @@ DEVI void qkv_epilogue(f32x4 x, bool rot, int head, int Hq, int Hkv, int f0, boo
 // k-steps per wave = H / 32 / 16 <= NC (the same bound as the row chunks: H <= 512 NC).
 // FULL: one whole 16-row tile per workgroup (half as many workgroups: (Hq + 2 Hkv) * 8) — for a stream that is CU-masked to half the chip
 // (the decode partition of the pipelined step, engine.hip), where 256 workgroups of 1024 threads would need two rounds.  Same arithmetic per element.
-template <int NC, typename WT, bool FULL>
+// KVT: the page pool's element type (qkv_epilogue); kv_scales [Hkv][2] is read by the fp8 instantiations only.
+template <int NC, typename WT, bool FULL, typename KVT = bf16_t>
 __global__ __launch_bounds__(1024) void dec_qkv_kernel(const bf16_t* __restrict__ h, const bf16_t* __restrict__ ln_w,
                                                        const WT* __restrict__ Wd, const float* __restrict__ wscale, const bf16_t* __restrict__ bias,
                                                        const float* __restrict__ inv_freq, const int32_t* __restrict__ ctx_len,
                                                        const int32_t* __restrict__ block_table, int max_pages,
-                                                       bf16_t* __restrict__ pool, bf16_t* __restrict__ q_out,
-                                                       int B, int H, int Hq, int Hkv, float eps, int XR) {
+                                                       KVT* __restrict__ pool, bf16_t* __restrict__ q_out,
+                                                       int B, int H, int Hq, int Hkv, float eps, int XR, const float* __restrict__ kv_scales) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     {   // this workgroup's 16-row batch tile
         const int t0 = 16 * blockIdx.x;
@@ -138,6 +162,7 @@ __global__ __launch_bounds__(1024) void dec_qkv_kernel(const bf16_t* __restrict_
         sc0 = *reinterpret_cast<const f32x2*>(wscale + head * 128 + f0);
         sc1 = *reinterpret_cast<const f32x2*>(wscale + head * 128 + f1);
     }
+    const float kvs = kv_head_scale<KVT>(kv_scales, rot, head, Hq, Hkv);
     __builtin_amdgcn_sched_barrier(0);
     // ---- 2. weight slice: lane (g, i) reads row (i & 7) + 8 half of the chunk; rows of the other half are duplicates
     const WT* wp = Wd + ((size_t)tile * KS) * 64 + lane_slot<WT>(g, FULL ? m : (m & 7) + 8 * half);
@@ -150,6 +175,7 @@ __global__ __launch_bounds__(1024) void dec_qkv_kernel(const bf16_t* __restrict_
     pin_rows<1, NC>(R);
     PIN(fr0); PIN(fr1); PIN(bia0); PIN(bia1);
     if constexpr (is_fp8<WT>::value) { PIN(sc0); PIN(sc1); }
+    if constexpr (sizeof(KVT) == 1) PIN(kvs);
     TRACE(1);
     float rc[2] = {1.f, 1.f}, rs[2] = {0.f, 0.f};
     if (wv == 15 && rot) {      // precise sincosf (the fast path up to |x| < 2^17); runs beside the other waves' norm
@@ -170,7 +196,7 @@ __global__ __launch_bounds__(1024) void dec_qkv_kernel(const bf16_t* __restrict_
     f32x4 x = {0, 0, 0, 0};
 #pragma unroll
     for (int sl = 0; sl < 16; ++sl) x += red[sl * 64 + lane];
-    qkv_epilogue<WT>(x, rot, head, Hq, Hkv, f0, bias != nullptr, bia0, bia1, sc0, sc1, rc, rs, pos, page, m, pool, q_out);
+    qkv_epilogue<WT, KVT>(x, rot, head, Hq, Hkv, f0, bias != nullptr, bia0, bia1, sc0, sc1, rc, rs, pos, page, m, pool, q_out, kvs);
     TRACE(6);
 }
 
@@ -497,13 +523,13 @@ __global__ __launch_bounds__(1024) void dec_proj_wide_kernel(const bf16_t* __res
 // grid.y = ceil(n_out / NM) workgroups, n_out = (Hq + 2 Hkv) * 8 whole 16-row tiles of the (permuted, launch_pack_frag_qkv) qkv weight.
 // XIMG (round 6, batches above 32 rows): h is the NORMALISED X image of the rows (dec_norm_ximg_kernel, decode_b64.hip: the same row_rstd / norm8,
 // so the same bits) — no statistics, no in-register normalisation, no first barrier: a wave's fragments of its K slice are requested with its weights.
-template <int NM, int TT, int NC, typename WT, bool XIMG = false>
+template <int NM, int TT, int NC, typename WT, bool XIMG = false, typename KVT = bf16_t>
 __global__ __launch_bounds__(1024) void dec_qkv_wide_kernel(const bf16_t* __restrict__ h, const bf16_t* __restrict__ ln_w,
                                                             const WT* __restrict__ Wd, const float* __restrict__ wscale, const bf16_t* __restrict__ bias,
                                                             const float* __restrict__ inv_freq, const int32_t* __restrict__ ctx_len,
                                                             const int32_t* __restrict__ block_table, int max_pages,
-                                                            bf16_t* __restrict__ pool, bf16_t* __restrict__ q_out,
-                                                            int B, int H, int Hq, int Hkv, float eps) {
+                                                            KVT* __restrict__ pool, bf16_t* __restrict__ q_out,
+                                                            int B, int H, int Hq, int Hkv, float eps, const float* __restrict__ kv_scales) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     f32x4* red = reinterpret_cast<f32x4*>(smem);                                  // [16][NM][TT][64]
     float* rstd_s = reinterpret_cast<float*>(smem + (size_t)16 * NM * TT * 64 * sizeof(f32x4));     // [16 TT]
@@ -555,6 +581,7 @@ __global__ __launch_bounds__(1024) void dec_qkv_wide_kernel(const bf16_t* __rest
         sc0 = *reinterpret_cast<const f32x2*>(wscale + head * 128 + f0);
         sc1 = *reinterpret_cast<const f32x2*>(wscale + head * 128 + f1);
     }
+    const float kvs = kv_head_scale<KVT>(kv_scales, rot, head, Hq, Hkv);
     __builtin_amdgcn_sched_barrier(0);
     const WT* zc = reinterpret_cast<const WT*>(g_zero_chunk) + lane;
     WT a[NM][NC];
@@ -646,13 +673,14 @@ __global__ __launch_bounds__(1024) void dec_qkv_wide_kernel(const bf16_t* __rest
     TRACE(4);
     PIN(page); PIN(fr0); PIN(fr1); PIN(bia0); PIN(bia1);
     if constexpr (is_fp8<WT>::value) { PIN(sc0); PIN(sc1); }
+    if constexpr (sizeof(KVT) == 1) PIN(kvs);
     __syncthreads();
     TRACE(5);
     if (!epi) return;
     f32x4 x = {0, 0, 0, 0};
 #pragma unroll
     for (int sl = 0; sl < 16; ++sl) x += red[((size_t)((sl * NM + je) * TT + te)) * 64 + lane];
-    qkv_epilogue<WT>(x, rot, head, Hq, Hkv, f0, bias != nullptr, bia0, bia1, sc0, sc1, rc, rs, pos, page, row, pool, q_out);
+    qkv_epilogue<WT, KVT>(x, rot, head, Hq, Hkv, f0, bias != nullptr, bia0, bia1, sc0, sc1, rc, rs, pos, page, row, pool, q_out, kvs);
     TRACE(6);
 }
 
@@ -990,10 +1018,11 @@ static bool wide_on() {
 
 // part_cus > 0: the stream is CU-masked to that many CUs (the decode partition of the pipelined step): whole 16-row weight tiles per workgroup
 // (half as many workgroups) at B <= 16, as many features per workgroup as one round on those CUs needs above.
-hipError_t launch_dec_qkv(hipStream_t s, const bf16_t* h, const bf16_t* ln_w, const void* Wd, const float* wscale, const bf16_t* bias,
+template <typename KVT>
+static hipError_t dec_qkv_launch(hipStream_t s, const bf16_t* h, const bf16_t* ln_w, const void* Wd, const float* wscale, const bf16_t* bias,
                           const float* inv_freq, const int32_t* ctx_len, const int32_t* block_table, int max_pages,
-                          bf16_t* pool_layer, bf16_t* q_out, int B, int H, int Hq, int Hkv, float eps, int part_cus, bf16_t* xn,
-                          const float* pend, const float* pend_scale) {
+                          KVT* pool_layer, bf16_t* q_out, int B, int H, int Hq, int Hkv, float eps, int part_cus, bf16_t* xn,
+                          const float* pend, const float* pend_scale, const float* kv_scales) {
     if (H % 32 || H > 512 * NC_MAX || B < 1 || B > MAX_DECODE_ROWS) return hipErrorInvalidValue;
     const int full_tiles = part_cus > 0;
     {   // a pending K-split residual update that the X-image path below will not fuse into its norm launch gets a launch of its own
@@ -1016,22 +1045,22 @@ hipError_t launch_dec_qkv(hipStream_t s, const bf16_t* h, const bf16_t* ln_w, co
         auto go = [&](auto kern, auto wd, uint32_t* done) -> hipError_t {
             hipError_t e = ensure_lds(kern, lds_w, done);
             if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(kern, grid_w, dim3(1024), lds_w, s, h, ln_w, wd, wscale, bias, inv_freq, ctx_len, block_table, max_pages, pool_layer, q_out, B, H, Hq, Hkv, eps);
+            hipLaunchKernelGGL(kern, grid_w, dim3(1024), lds_w, s, h, ln_w, wd, wscale, bias, inv_freq, ctx_len, block_table, max_pages, pool_layer, q_out, B, H, Hq, Hkv, eps, kv_scales);
             return hipGetLastError();
         };
 #define QKV_WIDE(NMV, TTV, IDX)                                                                                                     \
-        return wscale ? go(dec_qkv_wide_kernel<NMV, TTV, NC_MAX, u32x2>, (const u32x2*)Wd, &attr_w[IDX])                              \
-                      : go(dec_qkv_wide_kernel<NMV, TTV, NC_MAX, bf16x8>, (const bf16x8*)Wd, &attr_w[IDX + 1])
+        return wscale ? go(dec_qkv_wide_kernel<NMV, TTV, NC_MAX, u32x2, false, KVT>, (const u32x2*)Wd, &attr_w[IDX])                  \
+                      : go(dec_qkv_wide_kernel<NMV, TTV, NC_MAX, bf16x8, false, KVT>, (const bf16x8*)Wd, &attr_w[IDX + 1])
         if (ximg) {          // tt == 4
             const bf16_t* hx = xn;
             auto gox = [&](auto kern, auto wd, uint32_t* done) -> hipError_t {
                 hipError_t e = ensure_lds(kern, lds_w, done);
                 if (e != hipSuccess) return e;
-                hipLaunchKernelGGL(kern, grid_w, dim3(1024), lds_w, s, hx, ln_w, wd, wscale, bias, inv_freq, ctx_len, block_table, max_pages, pool_layer, q_out, B, H, Hq, Hkv, eps);
+                hipLaunchKernelGGL(kern, grid_w, dim3(1024), lds_w, s, hx, ln_w, wd, wscale, bias, inv_freq, ctx_len, block_table, max_pages, pool_layer, q_out, B, H, Hq, Hkv, eps, kv_scales);
                 return hipGetLastError();
             };
-            if (nm == 1) return wscale ? gox(dec_qkv_wide_kernel<1, 4, NC_MAX, u32x2, true>, (const u32x2*)Wd, &attr_w[8]) : gox(dec_qkv_wide_kernel<1, 4, NC_MAX, bf16x8, true>, (const bf16x8*)Wd, &attr_w[9]);
-            return wscale ? gox(dec_qkv_wide_kernel<2, 4, NC_MAX, u32x2, true>, (const u32x2*)Wd, &attr_w[10]) : gox(dec_qkv_wide_kernel<2, 4, NC_MAX, bf16x8, true>, (const bf16x8*)Wd, &attr_w[11]);
+            if (nm == 1) return wscale ? gox(dec_qkv_wide_kernel<1, 4, NC_MAX, u32x2, true, KVT>, (const u32x2*)Wd, &attr_w[8]) : gox(dec_qkv_wide_kernel<1, 4, NC_MAX, bf16x8, true, KVT>, (const bf16x8*)Wd, &attr_w[9]);
+            return wscale ? gox(dec_qkv_wide_kernel<2, 4, NC_MAX, u32x2, true, KVT>, (const u32x2*)Wd, &attr_w[10]) : gox(dec_qkv_wide_kernel<2, 4, NC_MAX, bf16x8, true, KVT>, (const bf16x8*)Wd, &attr_w[11]);
         }
         if (nm == 1 && tt == 2) { QKV_WIDE(1, 2, 0); }
         if (nm == 1) { QKV_WIDE(1, 4, 2); }
@@ -1046,11 +1075,23 @@ hipError_t launch_dec_qkv(hipStream_t s, const bf16_t* h, const bf16_t* ln_w, co
     auto go = [&](auto kern, auto wd, uint32_t* done) -> hipError_t {
         hipError_t e = ensure_lds(kern, lds_max, done);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, grid, dim3(1024), lds, s, h, ln_w, wd, wscale, bias, inv_freq, ctx_len, block_table, max_pages, pool_layer, q_out, B, H, Hq, Hkv, eps, XR);
+        hipLaunchKernelGGL(kern, grid, dim3(1024), lds, s, h, ln_w, wd, wscale, bias, inv_freq, ctx_len, block_table, max_pages, pool_layer, q_out, B, H, Hq, Hkv, eps, XR, kv_scales);
         return hipGetLastError();
     };
-    if (wscale) return full_tiles ? go(dec_qkv_kernel<NC_MAX, u32x2, true>, (const u32x2*)Wd, &attr[3]) : go(dec_qkv_kernel<NC_MAX, u32x2, false>, (const u32x2*)Wd, &attr[1]);
-    return full_tiles ? go(dec_qkv_kernel<NC_MAX, bf16x8, true>, (const bf16x8*)Wd, &attr[2]) : go(dec_qkv_kernel<NC_MAX, bf16x8, false>, (const bf16x8*)Wd, &attr[0]);
+    if (wscale) return full_tiles ? go(dec_qkv_kernel<NC_MAX, u32x2, true, KVT>, (const u32x2*)Wd, &attr[3]) : go(dec_qkv_kernel<NC_MAX, u32x2, false, KVT>, (const u32x2*)Wd, &attr[1]);
+    return full_tiles ? go(dec_qkv_kernel<NC_MAX, bf16x8, true, KVT>, (const bf16x8*)Wd, &attr[2]) : go(dec_qkv_kernel<NC_MAX, bf16x8, false, KVT>, (const bf16x8*)Wd, &attr[0]);
+}
+
+// kv_scales == nullptr: bf16 page pool; else pool_layer is an fp8 (e4m3fn) pool and kv_scales [Hkv][K | V] this layer's fp32 scales
+hipError_t launch_dec_qkv(hipStream_t s, const bf16_t* h, const bf16_t* ln_w, const void* Wd, const float* wscale, const bf16_t* bias,
+                          const float* inv_freq, const int32_t* ctx_len, const int32_t* block_table, int max_pages,
+                          void* pool_layer, bf16_t* q_out, int B, int H, int Hq, int Hkv, float eps, int part_cus, bf16_t* xn,
+                          const float* pend, const float* pend_scale, const float* kv_scales) {
+    if (kv_scales)
+        return dec_qkv_launch<uint8_t>(s, h, ln_w, Wd, wscale, bias, inv_freq, ctx_len, block_table, max_pages, (uint8_t*)pool_layer, q_out, B, H, Hq, Hkv,
+                                       eps, part_cus, xn, pend, pend_scale, kv_scales);
+    return dec_qkv_launch<bf16_t>(s, h, ln_w, Wd, wscale, bias, inv_freq, ctx_len, block_table, max_pages, (bf16_t*)pool_layer, q_out, B, H, Hq, Hkv,
+                                  eps, part_cus, xn, pend, pend_scale, nullptr);
 }
 
 // part_cus: see launch_dec_qkv

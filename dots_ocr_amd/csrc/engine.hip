@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "common.h"
+#include "decode_layout.h"
 #include "dots_ocr_hip.h"
 #include "kernels.h"
 
@@ -184,8 +185,10 @@ struct DotsEngine {
     int kv_capped = 0;                     // sequences whose generation cap was lowered because the pool ran dry
     std::vector<int32_t> free_pages;       // LIFO free list
     std::vector<std::vector<int32_t>> slot_pages;
-    bf16_t* pool = nullptr;                // [layers][n_pool_pages + 1][Hkv][2][8192]
-    size_t pool_layer_elems = 0;
+    bf16_t* pool = nullptr;                // [layers][n_pool_pages + 1][Hkv][2][8192] bf16, or e4m3 bytes (kv8; decode.hip header)
+    size_t pool_layer_elems = 0;           // per layer, in bf16 units (an fp8 pool's layer is half as many)
+    bool kv8 = false;                      // DotsConfig.kv_cache_dtype == 1: the pool holds e4m3fn values
+    float* kv_scales = nullptr;            // [layers][Hkv][K | V] fp32 (dots_set_kv_scales; 1.0 until set), read by the fp8 writers and reader
     int32_t *block_table = nullptr, *ctx_len = nullptr, *cur_tokens = nullptr, *out_ids = nullptr, *out_lens = nullptr,
             *finished = nullptr, *eos_ids = nullptr, *am_idx = nullptr;
     float* am_val = nullptr;
@@ -569,8 +572,12 @@ int alloc_workspaces(DotsEngine* e) {
     // of max_seq_len, i.e. no sequence can ever be refused for lack of pages)
     const int64_t pool_tokens = c.kv_pool_tokens > 0 ? c.kv_pool_tokens : (int64_t)c.max_batch * e->max_pages * 64;
     e->n_pool_pages = (int)((pool_tokens + 63) / 64);
-    e->pool_layer_elems = (size_t)(e->n_pool_pages + 1) * c.num_kv_heads * 2 * 8192;
+    e->kv8 = c.kv_cache_dtype == 1;
+    e->pool_layer_elems = (size_t)(e->n_pool_pages + 1) * c.num_kv_heads * 2 * 8192 / (e->kv8 ? 2 : 1);
     CK(e->alloc(&e->pool, e->pool_layer_elems * c.num_layers));
+    const std::vector<float> kv_ones((size_t)c.num_layers * c.num_kv_heads * 2, 1.0f);      // lives until the stream is synchronised below
+    CK(e->alloc(&e->kv_scales, kv_ones.size()));
+    CK(hipMemcpyAsync(e->kv_scales, kv_ones.data(), kv_ones.size() * 4, hipMemcpyHostToDevice, e->stream));
     const int mb = (c.max_batch + 15) / 16 * 16;            // rows of the decode buffers: whole 16-row tiles
     CK(e->alloc(&e->block_table, (size_t)mb * e->max_pages));
     CK(e->alloc(&e->ctx_len, (size_t)mb));
@@ -617,6 +624,11 @@ int alloc_workspaces(DotsEngine* e) {
     for (auto& ev : e->ev) CK(hipEventCreate(&ev));
     CK(hipStreamSynchronize(e->stream));
     return DOTS_OK;
+}
+
+// this layer's fp8-KV scales [Hkv][2] for the pool launchers, or nullptr for a bf16 pool
+const float* layer_kv_scales(const DotsEngine* e, int layer) {
+    return e->kv8 ? e->kv_scales + (size_t)layer * e->cfg.num_kv_heads * 2 : nullptr;
 }
 
 // ---- KV page allocator (host side; the kernels only ever see the block table)
@@ -1046,7 +1058,7 @@ int prefill(DotsEngine* e, const int32_t* ids, const int32_t* lens, int B, const
         bf16_t* pool_l = e->pool + e->pool_layer_elems * i;
         CK(launch_rmsnorm(s, e->p_x, Lw.ln1, e->p_xn, T, H, c.rms_norm_eps));
         RET(qkv_rope_on(e, s, e->act_q, e->act_s, e->p_xn, Lw.qkv_w, Lw.qkv_8, Lw.qkv_s, Lw.qkv_b, e->p_qkv, e->p_cs, e->p_tiles, n_tiles, e->p_q, e->p_k, e->p_vt, T, Tpad, H, Hq, Hkv));
-        CK(launch_kv_to_pages(s, e->p_k, e->p_qkv, e->p_tiles, n_tiles, e->block_table, e->max_pages, pool_l, T, Hq, Hkv));
+        CK(launch_kv_to_pages(s, e->p_k, e->p_qkv, e->p_tiles, n_tiles, e->block_table, e->max_pages, pool_l, T, Hq, Hkv, layer_kv_scales(e, i)));
         CK(launch_flash_attn(s, e->p_q, e->p_k, e->p_vt, e->p_att, e->p_qblocks, (int)e->hp_qblocks.size(), T, Tpad, Hq, Hkv, 1, scale));
         RET(dense(e, e->p_att, Lw.o_w, Lw.o_8, Lw.o_s, nullptr, e->p_x, e->p_x, T, H, Nq, H, EPI_RESIDUAL));
         CK(launch_rmsnorm(s, e->p_x, Lw.ln2, e->p_xn, T, H, c.rms_norm_eps));
@@ -1108,8 +1120,9 @@ int decode_step_launches(DotsEngine* e, int n_splits, int part = 0) {
         const LLayer& L = e->ll[same_layer ? 0 : i];
         bf16_t* pool_l = e->pool + e->pool_layer_elems * i;
         CK(launch_dec_qkv(s, e->d_h, L.ln1, L.qkv_wd, L.qkv_s, L.qkv_b, e->lm_inv_freq, e->ctx_len, e->block_table, e->max_pages, pool_l, e->d_q, B, H, Hq,
-                          Hkv, c.rms_norm_eps, part ? e->dec_cus : 0, e->d_xn, pend ? e->d_part_h : nullptr, pend_scale));
-        CK(launch_decode_attn(s, e->d_q, pool_l, e->ctx_len, e->block_table, e->max_pages, e->d_part_o, e->d_part_ml, B, Hq, Hkv, n_splits, scale, part ? e->dec_cus : 0, e->attn_stream));
+                          Hkv, c.rms_norm_eps, part ? e->dec_cus : 0, e->d_xn, pend ? e->d_part_h : nullptr, pend_scale, layer_kv_scales(e, i)));
+        CK(launch_decode_attn(s, e->d_q, pool_l, e->ctx_len, e->block_table, e->max_pages, e->d_part_o, e->d_part_ml, B, Hq, Hkv, n_splits, scale, part ? e->dec_cus : 0, e->attn_stream,
+                              layer_kv_scales(e, i)));
         CK(launch_decode_attn_combine(s, e->d_part_o, e->d_part_ml, e->ctx_len, e->d_att, B, Hq, Hkv, n_splits));
         bool pend_o = false;
         CK(launch_dec_proj(s, e->d_att, L.o_wd, L.o_s, e->d_h, B, H, Nq, part ? e->dec_cus : 0, e->d_part_h, &pend_o));
@@ -1226,6 +1239,7 @@ int dots_create(const DotsConfig* cfg, int device, DotsEngine** out) {
     if (c.max_batch < 1 || c.max_batch > DOTS_MAX_BATCH) return bad("max_batch must be in [1,64]");
     if (c.max_seq_len < 64 || c.max_patches < 4 || c.max_prefill_tokens < 1) return bad("capacity fields too small");
     if (c.kv_pool_tokens < 0 || (c.kv_pool_tokens > 0 && c.kv_pool_tokens < 64)) return bad("kv_pool_tokens must be 0 (default) or >= 64");
+    if (c.kv_cache_dtype != 0 && c.kv_cache_dtype != 1) return bad("kv_cache_dtype must be 0 (bf16) or 1 (fp8 e4m3)");
     if (c.v_merge < 1 || c.v_temporal_patch != 1) return bad("unsupported vision patching");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { g_create_error = "no such HIP device"; return DOTS_E_HIP; }
@@ -1456,7 +1470,7 @@ int dots_generate(DotsEngine* e, const int32_t* input_ids, const int32_t* prompt
     e->stats.decode_steps = steps;
     int64_t newtok = 0;
     double kvb = 0;
-    const double kv_tok = (double)e->cfg.num_layers * e->cfg.num_kv_heads * 128 * 2 * 2;
+    const double kv_tok = (double)e->cfg.num_layers * e->cfg.num_kv_heads * 128 * 2 * (e->kv8 ? 1 : 2);      // bytes per cached token (K and V)
     for (int b = 0; b < B; ++b) {
         newtok += out_lens[b];
         for (int st = 0; st < steps; ++st) kvb += (double)(prompt_lens[b] + st + 1) * kv_tok;
@@ -1622,6 +1636,24 @@ int dots_kv_pool_info(DotsEngine* e, int32_t* total_pages, int32_t* free_pages) 
     if (!e || !total_pages || !free_pages) return DOTS_E_INVALID;
     *total_pages = e->n_pool_pages;
     *free_pages = (int32_t)e->free_pages.size();
+    return DOTS_OK;
+}
+
+int dots_set_kv_scales(DotsEngine* e, const float* scales_host) {
+    if (!e || !scales_host) return e ? e->fail(DOTS_E_INVALID, "null argument") : DOTS_E_INVALID;
+    const DotsConfig& c = e->cfg;
+    const size_t n = (size_t)c.num_layers * c.num_kv_heads * 2;
+    for (size_t i = 0; i < n; ++i)
+        if (!std::isfinite(scales_host[i]) || !(scales_host[i] > 0.f))
+            return e->fail(DOTS_E_INVALID, "kv scale %zu (layer %zu, kv head %zu, %s) is %g: must be finite and > 0", i, i / (2 * c.num_kv_heads),
+                           (i / 2) % c.num_kv_heads, i % 2 ? "V" : "K", (double)scales_host[i]);
+    // a cached token was quantised with the scales of its time: they are fixed while any sequence holds pages
+    if ((int)e->free_pages.size() != e->n_pool_pages)
+        return e->fail(DOTS_E_STATE, "KV scales cannot change while sequences hold KV pages (%d of %d in use): release them first (dots_slots_reset)",
+                       e->n_pool_pages - (int)e->free_pages.size(), e->n_pool_pages);
+    CK(hipSetDevice(e->device));
+    CK(hipMemcpyAsync(e->kv_scales, scales_host, n * 4, hipMemcpyHostToDevice, e->stream));
+    CK(hipStreamSynchronize(e->stream));
     return DOTS_OK;
 }
 
@@ -1803,6 +1835,36 @@ int dots_debug_read_hidden(DotsEngine* e, int which, int layer, void* out_host, 
     CK(hipMemcpyAsync(out_host, e->dbg_hidden + off, (size_t)rows * dim * 2, hipMemcpyDeviceToHost, e->stream));
     CK(hipStreamSynchronize(e->stream));
     *rows_out = rows;
+    return DOTS_OK;
+}
+
+int dots_debug_read_kv(DotsEngine* e, int layer, int seq, int pos0, int n, int which, void* out_host) {
+    if (!e || !out_host) return e ? e->fail(DOTS_E_INVALID, "null argument") : DOTS_E_INVALID;
+    const DotsConfig& c = e->cfg;
+    if (layer < 0 || layer >= c.num_layers || seq < 0 || seq >= c.max_batch || pos0 < 0 || n < 1 || (which != 0 && which != 1) ||
+        (int64_t)pos0 + n > (int64_t)e->max_pages * PAGE)
+        return e->fail(DOTS_E_INVALID, "bad dots_debug_read_kv arguments (layer %d, row %d, positions %d + %d, which %d)", layer, seq, pos0, n, which);
+    RET(dots_synchronize(e));
+    const int Hkv = c.num_kv_heads, es = e->kv8 ? 1 : 2;
+    const size_t page_bytes = (size_t)PAGE_ELEMS * es;                                     // one (page, kv head, K|V)
+    const uint8_t* base = reinterpret_cast<const uint8_t*>(e->pool) + e->pool_layer_elems * 2 * layer;
+    std::vector<uint8_t> pg(page_bytes);
+    uint8_t* out = static_cast<uint8_t*>(out_host);
+    for (int p = pos0 / PAGE; p <= (pos0 + n - 1) / PAGE; ++p) {
+        const int page = e->hp_table[(size_t)seq * e->max_pages + p];
+        if (page >= e->n_pool_pages) return e->fail(DOTS_E_STATE, "position %d of row %d is not in the KV cache", std::max(pos0, p * PAGE), seq);
+        for (int h = 0; h < Hkv; ++h) {
+            CK(hipMemcpyAsync(pg.data(), base + ((size_t)(page * Hkv + h) * 2 + which) * page_bytes, page_bytes, hipMemcpyDeviceToHost, e->stream));
+            CK(hipStreamSynchronize(e->stream));
+            for (int pos = std::max(pos0, p * PAGE); pos < std::min(pos0 + n, (p + 1) * PAGE); ++pos)
+                for (int d = 0; d < 128; ++d) {
+                    const int key = pos & (PAGE - 1), el = which == 0 ? k_chunk(key, d) * 8 + (d & 7) : v_off(key, d);
+                    const size_t o = ((size_t)h * n + (pos - pos0)) * 128 + d;
+                    if (e->kv8) out[o] = pg[kv8_byte(el)];
+                    else std::memcpy(out + o * 2, pg.data() + (size_t)el * 2, 2);
+                }
+        }
+    }
     return DOTS_OK;
 }
 
@@ -2027,9 +2089,11 @@ int dots_op_qkv_proj_rope(DotsEngine* e, const void* x, const void* w, const voi
 // tensors as the HF state dict holds them; the fragment-order / permuted packing the decode step uses happens inside, with
 // the same pack kernels the engine runs at dots_finalize_weights.
 
-int dots_op_dec_qkv(DotsEngine* e, const void* h, const void* ln_w, const void* wqkv, const void* bias, const int32_t* ctx_len_dev,
-                    const int32_t* block_table_dev, int max_pages, void* pool_layer, void* q_out, int B, int H, int Hq, int Hkv, float eps,
-                    float rope_theta, int fp8) {
+namespace {
+// kv_scales == nullptr: a bf16 page pool; else an fp8 one with these [Hkv][2] scales (dots_op_dec_qkv_kv8 / dots_op_decode_attn_kv8)
+int op_dec_qkv(DotsEngine* e, const void* h, const void* ln_w, const void* wqkv, const void* bias, const int32_t* ctx_len_dev,
+               const int32_t* block_table_dev, int max_pages, void* pool_layer, void* q_out, int B, int H, int Hq, int Hkv, float eps,
+               float rope_theta, int fp8, const float* kv_scales) {
     if (!e || !h || !ln_w || !wqkv || !ctx_len_dev || !block_table_dev || !pool_layer || !q_out) return e ? e->fail(DOTS_E_INVALID, "null argument") : DOTS_E_INVALID;
     CK(hipSetDevice(e->device));
     Scratch sc(e);
@@ -2043,13 +2107,13 @@ int dots_op_dec_qkv(DotsEngine* e, const void* h, const void* ln_w, const void* 
     bf16_t* xn = nullptr;                            // scratch sized for THIS call's hidden size (the engine's own d_xn is sized for its model: the tests run the
     CK(sc.get(&xn, (size_t)DOTS_MAX_BATCH * H));     // BASELINE dimensions through a small-model engine)
     CK(launch_dec_qkv(e->stream, (const bf16_t*)h, (const bf16_t*)ln_w, wd, wscale, (const bf16_t*)bias, freq, ctx_len_dev, block_table_dev, max_pages,
-                      (bf16_t*)pool_layer, (bf16_t*)q_out, B, H, Hq, Hkv, eps, e->force_part ? e->dec_cus : 0, xn));      // dots_set_decode_plan(1): the partition plan's kernels
+                      pool_layer, (bf16_t*)q_out, B, H, Hq, Hkv, eps, e->force_part ? e->dec_cus : 0, xn, nullptr, nullptr, kv_scales));      // dots_set_decode_plan(1): the partition plan's kernels
     CK(hipStreamSynchronize(e->stream));
     return DOTS_OK;
 }
 
-int dots_op_decode_attn(DotsEngine* e, const void* q, const void* pool_layer, const int32_t* ctx_len_dev, const int32_t* block_table_dev,
-                        int max_pages, void* out, int B, int Hq, int Hkv, int max_seq_len) {
+int op_decode_attn(DotsEngine* e, const void* q, const void* pool_layer, const int32_t* ctx_len_dev, const int32_t* block_table_dev,
+                   int max_pages, void* out, int B, int Hq, int Hkv, int max_seq_len, const float* kv_scales) {
     if (!e || !q || !pool_layer || !ctx_len_dev || !block_table_dev || !out || B < 1 || B > DOTS_MAX_BATCH) return e ? e->fail(DOTS_E_INVALID, "bad decode_attn arguments") : DOTS_E_INVALID;
     CK(hipSetDevice(e->device));
     Scratch sc(e);
@@ -2062,12 +2126,37 @@ int dots_op_decode_attn(DotsEngine* e, const void* q, const void* pool_layer, co
     CK(sc.get(&att, rb * Hq * 128));
     CK(hipMemsetAsync(po, 0xff, rb * Hq * n_splits * 128 * 4, e->stream));      // NaN: a partial read without having been written shows up
     CK(hipMemsetAsync(pml, 0xff, rb * Hq * n_splits * 2 * 4, e->stream));
-    CK(launch_decode_attn(e->stream, (const bf16_t*)q, (const bf16_t*)pool_layer, ctx_len_dev, block_table_dev, max_pages, po, pml, B, Hq, Hkv, n_splits,
-                          1.0f / sqrtf(128.0f), e->force_part ? e->dec_cus : 0, e->attn_stream));      // dots_set_decode_plan: the plan's kernel choice
+    CK(launch_decode_attn(e->stream, (const bf16_t*)q, pool_layer, ctx_len_dev, block_table_dev, max_pages, po, pml, B, Hq, Hkv, n_splits,
+                          1.0f / sqrtf(128.0f), e->force_part ? e->dec_cus : 0, e->attn_stream, kv_scales));      // dots_set_decode_plan: the plan's kernel choice
     CK(launch_decode_attn_combine(e->stream, po, pml, ctx_len_dev, att, B, Hq, Hkv, n_splits));
     CK(launch_unpack_x(e->stream, att, (bf16_t*)out, B, Hq * 128));
     CK(hipStreamSynchronize(e->stream));
     return DOTS_OK;
+}
+}  // namespace
+
+int dots_op_dec_qkv(DotsEngine* e, const void* h, const void* ln_w, const void* wqkv, const void* bias, const int32_t* ctx_len_dev,
+                    const int32_t* block_table_dev, int max_pages, void* pool_layer, void* q_out, int B, int H, int Hq, int Hkv, float eps,
+                    float rope_theta, int fp8) {
+    return op_dec_qkv(e, h, ln_w, wqkv, bias, ctx_len_dev, block_table_dev, max_pages, pool_layer, q_out, B, H, Hq, Hkv, eps, rope_theta, fp8, nullptr);
+}
+
+int dots_op_dec_qkv_kv8(DotsEngine* e, const void* h, const void* ln_w, const void* wqkv, const void* bias, const int32_t* ctx_len_dev,
+                        const int32_t* block_table_dev, int max_pages, void* pool_layer, void* q_out, int B, int H, int Hq, int Hkv, float eps,
+                        float rope_theta, int fp8, const float* kv_scales_dev) {
+    if (!kv_scales_dev) return e ? e->fail(DOTS_E_INVALID, "null kv_scales") : DOTS_E_INVALID;
+    return op_dec_qkv(e, h, ln_w, wqkv, bias, ctx_len_dev, block_table_dev, max_pages, pool_layer, q_out, B, H, Hq, Hkv, eps, rope_theta, fp8, kv_scales_dev);
+}
+
+int dots_op_decode_attn(DotsEngine* e, const void* q, const void* pool_layer, const int32_t* ctx_len_dev, const int32_t* block_table_dev,
+                        int max_pages, void* out, int B, int Hq, int Hkv, int max_seq_len) {
+    return op_decode_attn(e, q, pool_layer, ctx_len_dev, block_table_dev, max_pages, out, B, Hq, Hkv, max_seq_len, nullptr);
+}
+
+int dots_op_decode_attn_kv8(DotsEngine* e, const void* q, const void* pool_layer, const int32_t* ctx_len_dev, const int32_t* block_table_dev,
+                            int max_pages, void* out, int B, int Hq, int Hkv, int max_seq_len, const float* kv_scales_dev) {
+    if (!kv_scales_dev) return e ? e->fail(DOTS_E_INVALID, "null kv_scales") : DOTS_E_INVALID;
+    return op_decode_attn(e, q, pool_layer, ctx_len_dev, block_table_dev, max_pages, out, B, Hq, Hkv, max_seq_len, kv_scales_dev);
 }
 
 int dots_op_dec_proj(DotsEngine* e, const void* x, const void* w, void* h_inout, int B, int N, int K, int fp8) {

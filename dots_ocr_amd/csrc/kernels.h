@@ -60,8 +60,11 @@ hipError_t launch_flash_attn(hipStream_t s, const bf16_t* q, const bf16_t* k, co
                              int causal, float scale, const XcdPlan* plan = nullptr);
 
 // ---- decode.hip  (KV page pool layout documented there)
+// Every launcher that touches the page pool takes kv_scales: nullptr = a bf16 pool; else pool_layer is an fp8 (e4m3fn) pool and kv_scales
+// the device array [Hkv][K | V] of this layer's fp32 scales (DotsConfig.kv_cache_dtype = 1).
 hipError_t launch_kv_to_pages(hipStream_t s, const bf16_t* k, const bf16_t* qkv, const Tile64* tiles, int n_tiles,
-                              const int32_t* block_table, int max_pages, bf16_t* pool_layer, int64_t T, int Hq, int Hkv);
+                              const int32_t* block_table, int max_pages, void* pool_layer, int64_t T, int Hq, int Hkv,
+                              const float* kv_scales = nullptr);
 // ---- decode_fused.hip: dense layers of the decode step with in-workgroup split-K and fused prologues/epilogues.
 // Activations between them travel as X images [K/8][XR][8], XR = 8 (B <= 8) or 16 (decode_layout.h).
 hipError_t launch_dec_embed(hipStream_t s, const int32_t* tokens, const bf16_t* embed, bf16_t* h, int B, int dim);
@@ -72,8 +75,8 @@ hipError_t launch_dec_embed(hipStream_t s, const int32_t* tokens, const bf16_t* 
 // nullptr): the residual update is applied first — fused into the norm kernel on the xn path, by a launch of its own otherwise.
 hipError_t launch_dec_qkv(hipStream_t s, const bf16_t* h, const bf16_t* ln_w, const void* Wd, const float* wscale, const bf16_t* bias,
                           const float* inv_freq, const int32_t* ctx_len, const int32_t* block_table, int max_pages,
-                          bf16_t* pool_layer, bf16_t* q_out, int B, int H, int Hq, int Hkv, float eps, int part_cus = 0, bf16_t* xn = nullptr,
-                          const float* pend = nullptr, const float* pend_scale = nullptr);
+                          void* pool_layer, bf16_t* q_out, int B, int H, int Hq, int Hkv, float eps, int part_cus = 0, bf16_t* xn = nullptr,
+                          const float* pend = nullptr, const float* pend_scale = nullptr, const float* kv_scales = nullptr);
 // h += X @ W^T.  part != nullptr (DEC_KSPLIT_PARTS x DOTS_MAX_BATCH x N fp32) allows the K-split kernel above 32 rows: *pending is then set and h is NOT
 // updated by this launch — pass `part` (and wscale) as pend / pend_scale to the next launch_dec_qkv / launch_dec_gateup / launch_dec_lmhead, or call launch_dec_norm_ximg(.., part, ..)
 hipError_t launch_dec_proj(hipStream_t s, const bf16_t* X, const void* Wd, const float* wscale, bf16_t* h, int B, int N, int K, int part_cus = 0,
@@ -97,12 +100,13 @@ bool dec_proj_ksplit_supports(int B, int N, int K);
 hipError_t launch_dec_proj_ksplit(hipStream_t s, const bf16_t* X, const void* Wd, bool fp8, float* part, int B, int N, int K, int cus);
 int decode_attn_waves();                       // pages in flight per decode-attention workgroup (engine constant)
 int decode_attn_splits(int max_seq_len);       // KV splits for a context capacity: ceil(pages / waves), at most 64
-hipError_t launch_decode_attn(hipStream_t s, const bf16_t* q, const bf16_t* pool_layer, const int32_t* ctx_len,
+hipError_t launch_decode_attn(hipStream_t s, const bf16_t* q, const void* pool_layer, const int32_t* ctx_len,
                               const int32_t* block_table, int max_pages, float* part_o, float* part_ml,
-                              int B, int Hq, int Hkv, int n_splits, float scale, int part_cus = 0, int stream_mode = -1);
+                              int B, int Hq, int Hkv, int n_splits, float scale, int part_cus = 0, int stream_mode = -1,
+                              const float* kv_scales = nullptr);
 // > 0: launch_decode_attn runs the streaming kernel (round 5) with that many resident workgroups; 0: one workgroup per (row, kv head, split).
-// part_cus > 0: the stream is CU-masked to that many CUs; stream_mode 1 / 0 / -1 = always where legal / never / by items per CU
-int decode_attn_stream_wgs(int B, int Hkv, int n_splits, int max_pages, int part_cus, int stream_mode = -1);
+// part_cus > 0: the stream is CU-masked to that many CUs; stream_mode 1 / 0 / -1 = always where legal / never / by items per CU; kv8: an fp8 pool (always 0)
+int decode_attn_stream_wgs(int B, int Hkv, int n_splits, int max_pages, int part_cus, int stream_mode = -1, bool kv8 = false);
 hipError_t launch_decode_attn_combine(hipStream_t s, const float* part_o, const float* part_ml, const int32_t* ctx_len, bf16_t* out,
                                       int B, int Hq, int Hkv, int n_splits);
 // Per-step token bookkeeping state (device pointers), shared by the arg-max and the sampling kernels.

@@ -6,6 +6,7 @@ No torch types cross this boundary: numpy arrays for host buffers, integers for 
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import Dict, Optional, Sequence
 
 import numpy as np
@@ -29,7 +30,7 @@ class CDotsConfig(C.Structure):
         ("v_use_bias", C.c_int32), ("v_post_norm", C.c_int32),
         ("max_batch", C.c_int32), ("max_seq_len", C.c_int32),
         ("max_patches", C.c_int64), ("max_prefill_tokens", C.c_int64), ("kv_pool_tokens", C.c_int64),
-        ("fp8_weights", C.c_int32), ("_reserved", C.c_int32),
+        ("fp8_weights", C.c_int32), ("kv_cache_dtype", C.c_int32),
     ]
 
 
@@ -85,6 +86,7 @@ def _prototypes(lib):
         "dots_slot_read": (i32, [vp, i32, P(i32), i32, P(i32)]),
         "dots_slot_release": (i32, [vp, i32]),
         "dots_kv_pool_info": (i32, [vp, P(i32), P(i32)]),
+        "dots_set_kv_scales": (i32, [vp, P(f32)]),
         "dots_get_logits": (i32, [vp, P(f32)]),
         "dots_set_next_tokens": (i32, [vp, P(i32), i32]),
         "dots_get_last_tokens": (i32, [vp, P(i32)]),
@@ -92,6 +94,7 @@ def _prototypes(lib):
         "dots_synchronize": (i32, [vp]),
         "dots_debug_capture_hidden": (i32, [vp, i64]),
         "dots_debug_read_hidden": (i32, [vp, i32, i32, vp, P(i64)]),
+        "dots_debug_read_kv": (i32, [vp, i32, i32, i32, i32, i32, vp]),
         "dots_dev_alloc": (i32, [vp, i64, P(vp)]),
         "dots_dev_free": (i32, [vp, vp]),
         "dots_memcpy_h2d": (i32, [vp, vp, vp, i64]),
@@ -107,6 +110,8 @@ def _prototypes(lib):
         "dots_op_qkv_proj_rope": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, P(i32), i32, P(i32), i32, i32, i32, i32, f32, i32]),
         "dots_op_dec_qkv": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, f32, f32, i32]),
         "dots_op_decode_attn": (i32, [vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32]),
+        "dots_op_dec_qkv_kv8": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, f32, f32, i32, vp]),
+        "dots_op_decode_attn_kv8": (i32, [vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, vp]),
         "dots_op_dec_proj": (i32, [vp, vp, vp, vp, i32, i32, i32, i32]),
         "dots_op_dec_gateup": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32]),
         "dots_op_dec_lmhead": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, f32, i32]),
@@ -130,11 +135,23 @@ EXPORTED_SYMBOLS = [
     "dots_dev_free", "dots_memcpy_h2d", "dots_memcpy_d2h", "dots_op_rmsnorm", "dots_op_layernorm", "dots_op_gemm", "dots_op_quant_fp8", "dots_op_gemm_fp8",
     "dots_op_flash_attn", "dots_plan_flash_xcd", "dots_op_qkv_rope_split", "dots_op_qkv_proj_rope", "dots_op_dec_qkv", "dots_op_decode_attn", "dots_op_dec_proj", "dots_op_dec_gateup",
     "dots_op_dec_lmhead", "dots_probe_mfma", "dots_probe_grid_barrier", "dots_probe_cu_mask",
+    "dots_set_kv_scales", "dots_debug_read_kv", "dots_op_dec_qkv_kv8", "dots_op_decode_attn_kv8",
 ]
+
+KV_CACHE_DTYPES = {"bf16": 0, "fp8": 1}      # DotsConfig.kv_cache_dtype; "fp8" = OCP e4m3fn (vLLM's --kv-cache-dtype fp8)
+
+
+def resolve_kv_cache_dtype(kv_cache_dtype: Optional[str]) -> str:
+    """"bf16" | "fp8"; None reads DOTS_OCR_KV_CACHE_DTYPE (unset or empty = bf16).  Anything else raises ValueError."""
+    if kv_cache_dtype is None:
+        kv_cache_dtype = os.environ.get("DOTS_OCR_KV_CACHE_DTYPE", "") or "bf16"
+    if kv_cache_dtype not in KV_CACHE_DTYPES:
+        raise ValueError(f"kv_cache_dtype must be one of {sorted(KV_CACHE_DTYPES)}, got {kv_cache_dtype!r}")
+    return kv_cache_dtype
 
 
 def c_config(cfg: DotsConfig, max_batch: int, max_seq_len: int, max_patches: int, max_prefill_tokens: int, kv_pool_tokens: int = 0,
-             fp8_weights: bool = False) -> CDotsConfig:
+             fp8_weights: bool = False, kv_cache_dtype: str = "bf16") -> CDotsConfig:
     v = cfg.vision
     return CDotsConfig(
         hidden_size=cfg.hidden_size, num_layers=cfg.num_hidden_layers, num_heads=cfg.num_attention_heads,
@@ -146,7 +163,8 @@ def c_config(cfg: DotsConfig, max_batch: int, max_seq_len: int, max_patches: int
         v_channels=v.num_channels, v_temporal_patch=v.temporal_patch_size, v_rms_eps=v.rms_norm_eps,
         v_ln_eps=v.merger_ln_eps, v_use_bias=int(v.use_bias), v_post_norm=int(v.post_norm),
         max_batch=max_batch, max_seq_len=max_seq_len, max_patches=max_patches,
-        max_prefill_tokens=max_prefill_tokens, kv_pool_tokens=kv_pool_tokens, fp8_weights=int(bool(fp8_weights)))
+        max_prefill_tokens=max_prefill_tokens, kv_pool_tokens=kv_pool_tokens, fp8_weights=int(bool(fp8_weights)),
+        kv_cache_dtype=KV_CACHE_DTYPES[kv_cache_dtype])
 
 
 def plan_flash_xcd(lens: Sequence[int], heads: int):
@@ -175,7 +193,9 @@ class Engine:
 
     def __init__(self, cfg: DotsConfig, device: int = 0, max_batch: int = 8, max_seq_len: int = 8192,
                  max_patches: int = 8 * 19824 + 64, max_prefill_tokens: Optional[int] = None, kv_pool_tokens: int = 0,
-                 fp8_weights: bool = False):
+                 fp8_weights: bool = False, kv_cache_dtype: Optional[str] = None):
+        # kv_cache_dtype: "bf16" | "fp8" (e4m3fn paged KV cache, include/dots_ocr_hip.h DotsConfig.kv_cache_dtype); None = $DOTS_OCR_KV_CACHE_DTYPE or bf16
+        self.kv_cache_dtype = resolve_kv_cache_dtype(kv_cache_dtype)        # before the library or the GPU is touched
         self.lib = _lib.load()
         _prototypes(self.lib)
         self.cfg = cfg
@@ -188,7 +208,7 @@ class Engine:
         self.max_prefill_tokens = max_prefill_tokens
         self.kv_pool_tokens = kv_pool_tokens
         self.fp8_weights = bool(fp8_weights)
-        self._cc = c_config(cfg, max_batch, max_seq_len, max_patches, max_prefill_tokens, kv_pool_tokens, fp8_weights)
+        self._cc = c_config(cfg, max_batch, max_seq_len, max_patches, max_prefill_tokens, kv_pool_tokens, fp8_weights, self.kv_cache_dtype)
         h = C.c_void_p()
         rc = self.lib.dots_create(C.byref(self._cc), device, C.byref(h))
         if rc != 0:
@@ -412,6 +432,22 @@ class Engine:
         self._ck(self.lib.dots_kv_pool_info(self.h, C.byref(tot), C.byref(free)), "dots_kv_pool_info")
         return int(tot.value), int(free.value)
 
+    def set_kv_scales(self, scales):
+        """fp8 KV cache scales, fp32 [num_layers, num_kv_heads, 2] (K, V; anything broadcastable to it), each finite and > 0.  Refused
+        (DotsEngineError) while any sequence holds KV pages; accepted and unused with a bf16 cache."""
+        shape = (self.cfg.num_hidden_layers, self.cfg.num_key_value_heads, 2)
+        s = np.ascontiguousarray(np.broadcast_to(np.asarray(scales, dtype=np.float32), shape))
+        self._ck(self.lib.dots_set_kv_scales(self.h, s.ctypes.data_as(C.POINTER(C.c_float))), "dots_set_kv_scales")
+
+    def read_kv(self, layer: int, seq: int, pos0: int, n: int, which: str = "k") -> np.ndarray:
+        """Cached K ("k") or V ("v") of LM layer `layer`, positions pos0 .. pos0 + n - 1 of block-table row `seq` (static batch index or
+        slot): [num_kv_heads, n, 128], uint16 (raw bf16) or uint8 (raw e4m3fn) as the cache stores it."""
+        dt = np.uint8 if self.kv_cache_dtype == "fp8" else np.uint16
+        out = np.empty((self.cfg.num_key_value_heads, int(n), 128), dtype=dt)
+        self._ck(self.lib.dots_debug_read_kv(self.h, int(layer), int(seq), int(pos0), int(n), {"k": 0, "v": 1}[which],
+                                             out.ctypes.data_as(C.c_void_p)), "dots_debug_read_kv")
+        return out
+
     def get_logits(self) -> np.ndarray:
         out = np.empty((self._B, self.cfg.vocab_size), dtype=np.float32)
         self._ck(self.lib.dots_get_logits(self.h, out.ctypes.data_as(C.POINTER(C.c_float))), "dots_get_logits")
@@ -518,6 +554,17 @@ class Engine:
     def op_decode_attn(self, q, pool_layer, ctx_len, block_table, max_pages, out, B, Hq, Hkv, max_seq_len):
         self._ck(self.lib.dots_op_decode_attn(self.h, q, pool_layer, ctx_len, block_table, max_pages, out, B, Hq, Hkv, max_seq_len),
                  "dots_op_decode_attn")
+
+    def op_dec_qkv_kv8(self, h, ln_w, wqkv, bias, ctx_len, block_table, max_pages, pool_layer, q_out, B, H, Hq, Hkv, eps, rope_theta, kv_scales,
+                       fp8=False):
+        """op_dec_qkv on an fp8 (e4m3fn) page pool; kv_scales: device fp32 [Hkv, 2] (K, V)."""
+        self._ck(self.lib.dots_op_dec_qkv_kv8(self.h, h, ln_w, wqkv, bias or None, ctx_len, block_table, max_pages, pool_layer, q_out,
+                                              B, H, Hq, Hkv, eps, rope_theta, int(fp8), kv_scales), "dots_op_dec_qkv_kv8")
+
+    def op_decode_attn_kv8(self, q, pool_layer, ctx_len, block_table, max_pages, out, B, Hq, Hkv, max_seq_len, kv_scales):
+        """op_decode_attn on an fp8 (e4m3fn) page pool; kv_scales: device fp32 [Hkv, 2] (K, V)."""
+        self._ck(self.lib.dots_op_decode_attn_kv8(self.h, q, pool_layer, ctx_len, block_table, max_pages, out, B, Hq, Hkv, max_seq_len,
+                                                  kv_scales), "dots_op_decode_attn_kv8")
 
     def op_dec_proj(self, x, w, h_inout, B, N, K, fp8=False):
         self._ck(self.lib.dots_op_dec_proj(self.h, x, w, h_inout, B, N, K, int(fp8)), "dots_op_dec_proj")

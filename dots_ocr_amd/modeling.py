@@ -51,17 +51,44 @@ def plan_batches(patches_per_seq: Sequence[int], max_batch: int, max_patches: in
     return batches
 
 
+def split_kv_scales(state_dict, num_layers: int, num_kv_heads: int):
+    """The fp8-KV checkpoint convention: per-layer scalars model.layers.{i}.self_attn.k_scale / v_scale.  Returns (the state dict
+    without them, scales [num_layers, num_kv_heads, 2] fp32 broadcast over the kv heads — 1.0 where a layer has none — or None when the
+    checkpoint carries no such tensor).  The scale tensors are never engine weights."""
+    names = {f"model.layers.{i}.self_attn.{kv}_scale": (i, j) for i in range(num_layers) for j, kv in enumerate(("k", "v"))}
+    if not any(n in names for n in state_dict):
+        return state_dict, None
+    scales = np.ones((num_layers, num_kv_heads, 2), np.float32)
+    rest = {}
+    for n, t in state_dict.items():
+        if n in names:
+            i, j = names[n]
+            v = np.asarray(t.detach().float().cpu() if hasattr(t, "detach") else t, dtype=np.float32).reshape(-1)
+            if v.size != 1:
+                raise ValueError(f"{n}: expected one scale per layer, got {v.size} values")
+            scales[i, :, j] = v[0]
+        else:
+            rest[n] = t
+    return rest, scales
+
+
 class DotsOcrHipForCausalLM:
     def __init__(self, cfg: DotsConfig, state_dict, device: int = 0, max_batch: int = 8, max_seq_len: int = 32768,
-                 max_patches: Optional[int] = None, fp8_weights: bool = False):
+                 max_patches: Optional[int] = None, fp8_weights: bool = False, kv_cache_dtype: Optional[str] = None):
         """fp8_weights: quantise the linears to e4m3 with per-output-channel scales at load time (DotsConfig.fp8_weights of the C ABI;
-        DOTS_OCR_FP8=1 in the environment turns it on for callers that cannot pass the keyword, e.g. DotsOCRParser(use_hf=True))."""
+        DOTS_OCR_FP8=1 in the environment turns it on for callers that cannot pass the keyword, e.g. DotsOCRParser(use_hf=True)).
+        kv_cache_dtype: "bf16" or "fp8" (e4m3fn paged KV cache, DotsConfig.kv_cache_dtype); None = $DOTS_OCR_KV_CACHE_DTYPE, unset = bf16.
+        The checkpoint's self_attn.k_scale / v_scale tensors, if any, become the fp8 cache's scales (split_kv_scales)."""
         self.config = cfg
         self.device_index = device
         max_patches = max_patches or max(max_batch * 19824 + 64, 57600 + 64)
         fp8_weights = bool(fp8_weights) or os.environ.get("DOTS_OCR_FP8", "0") not in ("", "0")
-        self.engine = Engine(cfg, device=device, max_batch=max_batch, max_seq_len=max_seq_len, max_patches=max_patches, fp8_weights=fp8_weights)
+        state_dict, kv_scales = split_kv_scales(state_dict, cfg.num_hidden_layers, cfg.num_key_value_heads)
+        self.engine = Engine(cfg, device=device, max_batch=max_batch, max_seq_len=max_seq_len, max_patches=max_patches, fp8_weights=fp8_weights,
+                             kv_cache_dtype=kv_cache_dtype)
         self.engine.load_state_dict(state_dict)
+        if kv_scales is not None:
+            self.engine.set_kv_scales(kv_scales)
         self.max_batch = max_batch
         self.max_seq_len = max_seq_len
         self.max_patches = max_patches

@@ -312,6 +312,9 @@ def main(argv: Optional[List[str]] = None):
     ap.add_argument("--max-batch", type=int, default=8)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--fp8-weights", action="store_true", help="quantise the linears to e4m3 (per-output-channel scale) at load time")
+    ap.add_argument("--kv-cache-dtype", choices=["bf16", "fp8"], default=None,
+                    help="paged KV cache element type (vLLM's flag): fp8 = e4m3fn with per-(layer, kv head) scales (the checkpoint's "
+                         "self_attn.k_scale / v_scale, else 1.0); default $DOTS_OCR_KV_CACHE_DTYPE or bf16")
     ap.add_argument("--static-batching", action="store_true", help="static batches through model.generate instead of continuous batching")
     ap.add_argument("--look-ahead", type=int, default=None,
                     help="continuous batching: vision towers of the next N queued requests run on a CU partition beside the decoding slots "
@@ -323,10 +326,11 @@ def main(argv: Optional[List[str]] = None):
     from .modeling import DotsOcrHipForCausalLM
     from .processing import DotsOcrProcessor
     if a.random_weights:
-        model = DotsOcrHipForCausalLM.from_random(device=a.device, max_batch=a.max_batch, fp8_weights=a.fp8_weights)
+        model = DotsOcrHipForCausalLM.from_random(device=a.device, max_batch=a.max_batch, fp8_weights=a.fp8_weights, kv_cache_dtype=a.kv_cache_dtype)
         proc = DotsOcrProcessor(model.config, engine=model.engine)
     else:
-        model = DotsOcrHipForCausalLM.from_pretrained(a.model_path, device=a.device, max_batch=a.max_batch, fp8_weights=a.fp8_weights)
+        model = DotsOcrHipForCausalLM.from_pretrained(a.model_path, device=a.device, max_batch=a.max_batch, fp8_weights=a.fp8_weights,
+                                                      kv_cache_dtype=a.kv_cache_dtype)
         proc = DotsOcrProcessor.from_pretrained(a.model_path, engine=model.engine)
     uvicorn.run(create_app(model, proc, a.served_model_name, a.max_batch, continuous=not a.static_batching,
                            allow_remote_images=a.allow_remote_images, allow_local_images=a.allow_local_images, look_ahead=a.look_ahead),

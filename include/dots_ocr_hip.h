@@ -69,7 +69,12 @@ typedef struct DotsConfig {
                                  their input activations per token the same way and run on the fp8 MFMA (W8A8).  Every quantised
                                  linear needs N % 256 == 0 and K % 64 == 0.  Embedding table, patch embedding, norms and biases
                                  stay bf16.  (BASELINE configs[4]) */
-    int32_t _reserved;
+    int32_t kv_cache_dtype;   /* paged KV cache element type: 0 = bf16 (default), 1 = fp8 (OCP e4m3fn, vLLM's --kv-cache-dtype fp8), any other
+                                 value is refused (DOTS_E_INVALID).  fp8: one fp32 scale s per (layer, kv head, K|V) (dots_set_kv_scales, default
+                                 1.0); a cached value is e4m3fn(clamp(x / s, -448, 448)) rounded to nearest even, x = what the bf16 cache would
+                                 hold, and reads back as float(stored) * s.  Pages still hold 64 tokens (half the bytes); prefill attention
+                                 runs on its bf16 buffers, every decode step reads the fp8 cache.  DotsStats.decode_bytes counts 1 B per
+                                 KV element.  (csrc/decode.hip header) */
 } DotsConfig;
 
 /* Per-phase device time of the last dots_generate / dots_vit_forward / ... call, measured with
@@ -219,6 +224,11 @@ int dots_slot_release(DotsEngine* e, int slot);
 /* Paged KV pool: pages of 64 tokens in total / currently free (an admission policy checks this before dots_slots_prefill,
  * which refuses with DOTS_E_CAPACITY when prompt + 64 tokens of each new sequence do not fit). */
 int dots_kv_pool_info(DotsEngine* e, int32_t* total_pages, int32_t* free_pages);
+/* fp8 KV cache scales, fp32 [num_layers][num_kv_heads][2] (K, V), each finite and > 0, copied to the device array the decode kernels read
+ * (captured decode graphs see them on replay).  DOTS_E_STATE while any sequence holds KV pages (after a static dots_generate: until
+ * dots_slots_reset or the next dots_prefill releases them): a cached token keeps the scales it was written with.  Accepted for a bf16
+ * cache too, where nothing reads them. */
+int dots_set_kv_scales(DotsEngine* e, const float* scales_host);
 /* Pages an occupied slot owns and its current limit on prompt + generated tokens (prompt + max_new_tokens unless the pool ran dry). */
 int dots_slot_capacity(DotsEngine* e, int slot, int32_t* pages_owned, int32_t* token_limit);
 
@@ -234,6 +244,10 @@ int dots_get_stats(DotsEngine* e, DotsStats* out);
  * dots_debug_read_hidden: which = 0 ViT block `layer` -> [patches, v_embed_dim], which = 1 LM layer `layer` -> [tokens, hidden]. */
 int dots_debug_capture_hidden(DotsEngine* e, int64_t capacity_elems);
 int dots_debug_read_hidden(DotsEngine* e, int which, int layer, void* out_host, int64_t* rows_out);
+/* Cached K (which = 0) or V (which = 1) of LM layer `layer`, positions pos0 .. pos0 + n - 1 of block-table row seq_or_slot (a static
+ * batch's sequence index or a slot), in logical order [num_kv_heads][n][128] and the cache's storage type: bf16, or raw e4m3fn bytes
+ * (kv_cache_dtype = 1).  DOTS_E_STATE if a position's page is not owned by that row.  Synchronises. */
+int dots_debug_read_kv(DotsEngine* e, int layer, int seq_or_slot, int pos0, int n, int which, void* out_host);
 int dots_synchronize(DotsEngine* e);
 
 /* ---- device memory helpers (so a binding needs no other GPU library) ------------------- */
@@ -302,6 +316,14 @@ int dots_op_dec_qkv(DotsEngine* e, const void* h_dev, const void* ln_w_dev, cons
                     int B, int H, int Hq, int Hkv, float eps, float rope_theta, int fp8);
 int dots_op_decode_attn(DotsEngine* e, const void* q_dev, const void* pool_layer_dev, const int32_t* ctx_len_dev,
                         const int32_t* block_table_dev, int max_pages, void* out_dev, int B, int Hq, int Hkv, int max_seq_len);
+/* The same two kernels on an fp8 (e4m3fn) page pool [pages][Hkv][K|V][8192 B] (csrc/decode.hip header) with the fp32 scales
+ * kv_scales_dev [Hkv][2] (K, V) — what a kv_cache_dtype = 1 engine decodes with. */
+int dots_op_dec_qkv_kv8(DotsEngine* e, const void* h_dev, const void* ln_w_dev, const void* wqkv_dev, const void* bias_dev,
+                        const int32_t* ctx_len_dev, const int32_t* block_table_dev, int max_pages, void* pool_layer_dev, void* q_out_dev,
+                        int B, int H, int Hq, int Hkv, float eps, float rope_theta, int fp8, const float* kv_scales_dev);
+int dots_op_decode_attn_kv8(DotsEngine* e, const void* q_dev, const void* pool_layer_dev, const int32_t* ctx_len_dev,
+                            const int32_t* block_table_dev, int max_pages, void* out_dev, int B, int Hq, int Hkv, int max_seq_len,
+                            const float* kv_scales_dev);
 int dots_op_dec_proj(DotsEngine* e, const void* x_dev, const void* w_dev, void* h_inout_dev, int B, int N, int K, int fp8);
 int dots_op_dec_gateup(DotsEngine* e, const void* h_dev, const void* ln_w_dev, const void* gate_w_dev, const void* up_w_dev, void* act_out_dev,
                        int B, int H, int I, float eps, int fp8);
