@@ -656,12 +656,14 @@ DEVI uint64_t splitmix64(uint64_t x) {
     return x ^ (x >> 31);
 }
 
+// own != nullptr: rows with own[b] != 0 carry their own parameters and are left to the row-selection stage below
 __global__ __launch_bounds__(SAMPLE_THREADS) void sample_step_kernel(const float* __restrict__ logits, int V, int ld, float inv_temp,
-                                                                     float top_p, uint64_t seed, StepState st) {
+                                                                     float top_p, uint64_t seed, StepState st, const int32_t* __restrict__ own) {
     __shared__ float red[SAMPLE_THREADS / 64];
     __shared__ float scan[SAMPLE_THREADS];
     const int b = blockIdx.x, tid = threadIdx.x;
     if (st.sel && !st.sel[b]) return;                                // uniform per workgroup
+    if (own && own[b]) return;
     const float* row = logits + (size_t)b * ld;
     const int C = (V + SAMPLE_THREADS - 1) / SAMPLE_THREADS;         // contiguous chunk per thread: index order is preserved
     const int lo = tid * C, hi = min(V, lo + C);
@@ -710,6 +712,419 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_step_kernel(const float
         }
         commit_token(st, b, tok);
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Per-row token selection: every row of a step may carry its own RowParams.  Three launches handle any mix of rows:
+//   select_partial_kernel (ARGMAX_CHUNKS x B workgroups): penalised logits (rows with penalties: written to rs.pen, never over the
+//     logits), arg max partials of them — the greedy answer and the softmax maximum m of every row in one read;
+//   select_thresh_kernel + select_rows_kernel (B workgroups of 1024 each): greedy rows merge the partials and commit (the second kernel);
+//     sampled rows find their kept set in the first kernel (rs.thr) and draw in the second, over the tempered values
+//     t_i = (l_i - m) / T with integer weights w_i = floor(exp(t_i) 2^40) (t_i >= -27; below that w_i = 0: such a token can never be
+//     drawn, 2^-39 of the maximum's mass) and keys k_i = bits(-t_i) (monotone: a smaller key is a larger t):
+//       1. one read: a 2048-bin histogram of counts and masses, bins uniform in t over [-27, 0];
+//       2. the k-th largest key (top-k) and then the nucleus key (top-p over the weights of the kept set) are exact radix selects
+//          (4 digits of 8 bits) over the elements of one bin.  The bins that can hold either boundary are gathered into LDS with one
+//          more read when they hold at most SEL_CAP elements (the common case), else the digits are read from memory;
+//       3. one read: inverse CDF in index order over the kept weights, x = floor(h 2^-64 * total), h = splitmix64(seed ^ splitmix64(n)),
+//          n = tokens the row has generated so far.  Integer sums: the result does not depend on the order of the atomics.
+//   Reads of a sampled row: 4 (partial, histogram, gather, draw), 2 without top-k and top-p (partial, draw); a greedy row: 1.
+constexpr int SEL_THREADS = 1024, SEL_BINS = 2048, SEL_CAP = 8192, SEL_DIG = 256;
+constexpr float SEL_TCUT = 27.0f;
+constexpr float SEL_BIN_SCALE = (float)SEL_BINS / SEL_TCUT;
+constexpr uint32_t SEL_NONE = 0xffffffffu;
+
+DEVI bool row_has_pen(const RowParams& p) { return p.repetition_penalty != 1.0f || p.frequency_penalty != 0.0f || p.presence_penalty != 0.0f; }
+
+// HF / vLLM repetition penalty on every token seen in the prompt or the output, then OpenAI frequency / presence on the output counts
+DEVI float penalise(float l, int c, bool seen_prompt, const RowParams& p) {
+    if ((seen_prompt || c > 0) && p.repetition_penalty != 1.0f) l = l > 0.f ? l / p.repetition_penalty : l * p.repetition_penalty;
+    if (c > 0) l = l - (p.frequency_penalty * (float)c + p.presence_penalty);
+    return l;
+}
+
+__global__ __launch_bounds__(256) void select_partial_kernel(const float* __restrict__ logits, int V, int ld, RowSel rs, StepState st,
+                                                             float* __restrict__ pval, int32_t* __restrict__ pidx) {
+    __shared__ float sv[4];
+    __shared__ int si[4];
+    const int c = blockIdx.x, b = blockIdx.y;
+    if (st.sel && !st.sel[b]) return;
+    const bool own = rs.own[b] != 0;
+    if (!own && !rs.legacy_greedy) return;
+    const int per = (V + ARGMAX_CHUNKS - 1) / ARGMAX_CHUNKS;
+    const int lo = c * per, hi = min(V, lo + per);
+    const float* row = logits + (size_t)b * ld;
+    float best = -INFINITY;
+    int bi = 0x7fffffff;
+    const RowParams p = own ? rs.params[b] : RowParams{0.f, 1.f, 0, 1.f, 0.f, 0.f, 0};
+    if (own && rs.cnt && row_has_pen(p)) {
+        const int W = (V + 31) >> 5;
+        const int32_t* cnt = rs.cnt + (size_t)b * V;
+        const uint32_t* seen = rs.seen + (size_t)b * W;
+        float* pen = rs.pen + (size_t)b * V;
+        for (int i = lo + threadIdx.x; i < hi; i += 256) {
+            const float l = penalise(row[i], cnt[i], (seen[i >> 5] >> (i & 31)) & 1u, p);
+            pen[i] = l;
+            argmax_merge(best, bi, l, i);
+        }
+    } else {
+        for (int i = lo + threadIdx.x; i < hi; i += 256) argmax_merge(best, bi, row[i], i);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) argmax_merge(best, bi, __shfl_xor(best, o, 64), __shfl_xor(bi, o, 64));
+    if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = best; si[threadIdx.x >> 6] = bi; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < 4; ++k) argmax_merge(best, bi, sv[k], si[k]);
+        pval[b * ARGMAX_CHUNKS + c] = best;
+        pidx[b * ARGMAX_CHUNKS + c] = bi;
+    }
+}
+
+DEVI uint32_t sel_key(float t) { return __float_as_uint(0.f - t); }              // 0 - (+-0) = +0: the maximum has key 0
+DEVI float sel_t(uint32_t key) { return -__uint_as_float(key); }
+DEVI bool sel_in(float t) { return t >= -SEL_TCUT; }
+DEVI uint32_t sel_bin(float t) { return min((uint32_t)(-t * SEL_BIN_SCALE), (uint32_t)(SEL_BINS - 1)); }
+DEVI uint64_t sel_w(float t) { return (uint64_t)(__expf(t) * 1099511627776.0f); }      // 2^40; t in [-27, 0]
+
+// Wave 0 scans h[0, 64 * PER) and finds the first entry whose inclusive prefix sum reaches target: .bin (SEL_NONE when the total stays
+// below it) and .before = the sum of the entries before it (the total when none).  Every thread must call; the result is in registers.
+struct Cross { uint32_t bin; uint64_t before; };
+template <int PER, typename T>
+DEVI Cross find_cross(const T* h, uint64_t target, Cross* xch) {
+    if (threadIdx.x < 64) {
+        const int lane = threadIdx.x;
+        uint64_t s = 0;
+        for (int j = 0; j < PER; ++j) s += h[lane * PER + j];
+        uint64_t incl = s;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint64_t v = __shfl_up(incl, o, 64);
+            if (lane >= o) incl += v;
+        }
+        const uint64_t hit = __ballot(incl >= target);
+        if (hit == 0) {
+            if (lane == 63) { xch->bin = SEL_NONE; xch->before = incl; }
+        } else if (lane == __ffsll((unsigned long long)hit) - 1) {
+            uint64_t acc = incl - s;
+            int j = 0;
+            for (; j < PER - 1; ++j) {
+                if (acc + h[lane * PER + j] >= target) break;
+                acc += h[lane * PER + j];
+            }
+            xch->bin = lane * PER + j;
+            xch->before = acc;
+        }
+    }
+    __syncthreads();
+    const Cross r = *xch;
+    __syncthreads();                                                     // xch may be reused at once
+    return r;
+}
+
+// sum of h[0, n) (every thread must call)
+template <int PER, typename T>
+DEVI uint64_t sum_below(const T* h, uint32_t n, uint64_t* xch) {
+    if (threadIdx.x < 64) {
+        uint64_t s = 0;
+        for (int j = 0; j < PER; ++j) s += (uint32_t)(threadIdx.x * PER + j) < n ? (uint64_t)h[threadIdx.x * PER + j] : 0;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        if (threadIdx.x == 0) *xch = s;
+    }
+    __syncthreads();
+    const uint64_t r = *xch;
+    __syncthreads();
+    return r;
+}
+
+struct SelLds {
+    uint32_t h0_cnt[SEL_BINS];
+    uint64_t h0_mass[SEL_BINS];
+    uint32_t d_cnt[SEL_DIG];
+    uint64_t d_mass[SEL_DIG];
+    uint32_t cand[SEL_CAP];
+    uint32_t n_cand;
+    Cross cr;
+    uint64_t tmp, cnt_le, mass_le;
+    float best;
+    int bi, tok;
+};
+
+// Exact radix select over the elements that each() visits (key, weight): the smallest key K whose cumulative count (by_mass = 0) or
+// weight (1) over the keys <= K reaches target (>= 1, <= the total).  Returns K; L.cnt_le / L.mass_le = count / weight of the keys <= K.
+template <typename Each>
+DEVI uint32_t radix_select(Each each, uint64_t target, bool by_mass, SelLds& L) {
+    uint32_t prefix = 0;
+    uint64_t cnt_before = 0, mass_before = 0;
+    for (int shift = 24; shift >= 0; shift -= 8) {
+        for (int j = threadIdx.x; j < SEL_DIG; j += SEL_THREADS) { L.d_cnt[j] = 0; L.d_mass[j] = 0; }
+        __syncthreads();
+        const uint64_t hi_mask = shift == 24 ? 0 : ~0ull << (shift + 8);
+        each([&](uint32_t key, uint64_t w) {
+            if (((uint64_t)key & hi_mask) != ((uint64_t)prefix & hi_mask)) return;
+            const uint32_t d = (key >> shift) & (SEL_DIG - 1);
+            atomicAdd(&L.d_cnt[d], 1u);
+            if (w) atomicAdd((unsigned long long*)&L.d_mass[d], (unsigned long long)w);
+        });
+        __syncthreads();
+        const Cross c = by_mass ? find_cross<SEL_DIG / 64>(L.d_mass, target, &L.cr) : find_cross<SEL_DIG / 64>(L.d_cnt, target, &L.cr);
+        const uint32_t d = c.bin;
+        const uint64_t bef = c.before;
+        const uint64_t other = by_mass ? sum_below<SEL_DIG / 64>(L.d_cnt, d, &L.tmp) : sum_below<SEL_DIG / 64>(L.d_mass, d, &L.tmp);
+        if (by_mass) { mass_before += bef; cnt_before += other; } else { cnt_before += bef; mass_before += other; }
+        target -= bef;
+        prefix |= d << shift;
+        if (shift == 0) { L.cnt_le = cnt_before + L.d_cnt[d]; L.mass_le = mass_before + L.d_mass[d]; }
+        __syncthreads();
+    }
+    return prefix;
+}
+
+DEVI void commit_row(const StepState& st, const RowSel& rs, int b, int V, bool pen, int tok) {
+    if (pen && !st.finished[b] && tok >= 0 && tok < V) rs.cnt[(size_t)b * V + tok] += 1;     // output counts of the rows with penalties
+    commit_token(st, b, tok);
+}
+
+// the merged arg max partials of row b -> L.best / L.bi (every thread must call)
+DEVI void merge_partials(const float* __restrict__ pval, const int32_t* __restrict__ pidx, int b, float* o_best, int* o_bi) {
+    if (threadIdx.x < 64) {
+        float best = pval[b * ARGMAX_CHUNKS + threadIdx.x];
+        int bi = pidx[b * ARGMAX_CHUNKS + threadIdx.x];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) argmax_merge(best, bi, __shfl_xor(best, o, 64), __shfl_xor(bi, o, 64));
+        if (threadIdx.x == 0) { *o_best = best; *o_bi = bi; }
+    }
+    __syncthreads();
+}
+
+// steps 1-2 of a sampled row: rs.thr[b] = the largest key it keeps
+__global__ __launch_bounds__(SEL_THREADS) void select_thresh_kernel(const float* __restrict__ logits, int V, int ld, RowSel rs,
+                                                                    const int32_t* __restrict__ sel, const float* __restrict__ pval,
+                                                                    const int32_t* __restrict__ pidx) {
+    __shared__ SelLds L;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    if ((sel && !sel[b]) || !rs.own[b]) return;                       // uniform per workgroup
+    const RowParams p = rs.params[b];
+    if (!(p.temperature > 0.f)) return;
+    if (p.top_k <= 0 && !(p.top_p < 1.0f)) {                          // no filter: every token with weight is kept
+        if (tid == 0) rs.thr[b] = SEL_NONE;
+        return;
+    }
+    merge_partials(pval, pidx, b, &L.best, &L.bi);
+    const bool pen = rs.cnt && row_has_pen(p);
+    const float* row = pen ? rs.pen + (size_t)b * V : logits + (size_t)b * ld;
+    const float m = L.best, inv_t = 1.0f / p.temperature;
+
+    // ---- 1. histogram of the tempered values
+    for (int j = tid; j < SEL_BINS; j += SEL_THREADS) { L.h0_cnt[j] = 0; L.h0_mass[j] = 0; }
+    if (tid == 0) L.n_cand = 0;
+    __syncthreads();
+    for (int i = tid; i < V; i += SEL_THREADS) {          // coalesced: order does not matter here
+        const float t = (row[i] - m) * inv_t;
+        if (!sel_in(t)) continue;
+        const uint32_t bn = sel_bin(t);
+        atomicAdd(&L.h0_cnt[bn], 1u);
+        atomicAdd((unsigned long long*)&L.h0_mass[bn], (unsigned long long)sel_w(t));
+    }
+    __syncthreads();
+
+    const bool use_k = p.top_k > 0, use_p = p.top_p < 1.0f;
+    uint32_t kb = SEL_NONE;                                              // bin of the k-th largest value (SEL_NONE: top-k keeps all)
+    uint64_t k_before = 0;
+    if (use_k) {
+        const Cross c = find_cross<SEL_BINS / 64>(L.h0_cnt, (uint64_t)p.top_k, &L.cr);
+        kb = c.bin;
+        k_before = c.before;
+    }
+    const uint64_t z_all = sum_below<SEL_BINS / 64>(L.h0_mass, SEL_BINS, &L.tmp);
+    const uint64_t m_below_kb = kb == SEL_NONE ? z_all : sum_below<SEL_BINS / 64>(L.h0_mass, kb, &L.tmp);
+    // bins that can hold the nucleus boundary: the kept mass lies in [m_below_kb, m_below_kb + mass(kb)]
+    uint32_t pb_lo = SEL_NONE;
+    if (use_p) {
+        const uint64_t zlo = kb == SEL_NONE ? z_all : m_below_kb;
+        const Cross c = find_cross<SEL_BINS / 64>(L.h0_mass, max((uint64_t)1, (uint64_t)((double)p.top_p * (double)zlo)), &L.cr);
+        pb_lo = c.bin == SEL_NONE ? kb : c.bin;
+    }
+    // ---- 2. gather the candidate bins [g_lo, g_hi] into LDS when they fit
+    uint32_t g_lo = SEL_NONE, g_hi = SEL_NONE;
+    if (kb != SEL_NONE) { g_lo = kb; g_hi = kb; }
+    if (use_p && pb_lo != SEL_NONE) { g_lo = min(g_lo, pb_lo); g_hi = g_hi == SEL_NONE ? pb_lo : g_hi; }
+    bool gathered = false;
+    if (g_lo != SEL_NONE) {
+        const uint64_t n = sum_below<SEL_BINS / 64>(L.h0_cnt, g_hi + 1, &L.tmp) - sum_below<SEL_BINS / 64>(L.h0_cnt, g_lo, &L.tmp);
+        if (n <= SEL_CAP) {
+            for (int i = tid; i < V; i += SEL_THREADS) {          // coalesced: order does not matter here
+                const float t = (row[i] - m) * inv_t;
+                if (!sel_in(t)) continue;
+                const uint32_t bn = sel_bin(t);
+                if (bn < g_lo || bn > g_hi) continue;
+                const uint32_t j = atomicAdd(&L.n_cand, 1u);
+                if (j < SEL_CAP) L.cand[j] = sel_key(t);         // the histogram counted exactly these: j < SEL_CAP
+            }
+            __syncthreads();
+            gathered = true;
+        }
+    }
+    // visit every element of bin bn with key <= kmax: from LDS when gathered, else from memory
+    auto in_bin = [&](uint32_t bn, uint32_t kmax) {
+        const bool lds = gathered && bn >= g_lo && bn <= g_hi;
+        return [&, bn, kmax, lds](auto fn) {
+            if (lds) {
+                const int n = (int)min(L.n_cand, (uint32_t)SEL_CAP);
+                for (int j = tid; j < n; j += SEL_THREADS) {
+                    const uint32_t key = L.cand[j];
+                    const float t = sel_t(key);
+                    if (sel_bin(t) == bn && key <= kmax) fn(key, sel_w(t));
+                }
+            } else {
+                for (int i = tid; i < V; i += SEL_THREADS) {          // coalesced: order does not matter here
+                    const float t = (row[i] - m) * inv_t;
+                    if (!sel_in(t) || sel_bin(t) != bn) continue;
+                    const uint32_t key = sel_key(t);
+                    if (key <= kmax) fn(key, sel_w(t));
+                }
+            }
+        };
+    };
+    uint32_t kmax = SEL_NONE;                                            // keep the keys <= kmax
+    uint64_t z = z_all;                                                  // their total weight
+    if (kb != SEL_NONE) {
+        kmax = radix_select(in_bin(kb, SEL_NONE), (uint64_t)p.top_k - k_before, false, L);
+        z = m_below_kb + L.mass_le;
+    }
+    if (use_p) {
+        const uint64_t target = max((uint64_t)1, (uint64_t)((double)p.top_p * (double)z));
+        if (kb != SEL_NONE) {                                            // the kept part of bin kb only
+            if (tid == 0) L.h0_mass[kb] = z - m_below_kb;
+            for (int j = kb + 1 + tid; j < SEL_BINS; j += SEL_THREADS) L.h0_mass[j] = 0;
+            __syncthreads();
+        }
+        const Cross c = find_cross<SEL_BINS / 64>(L.h0_mass, target, &L.cr);
+        if (c.bin != SEL_NONE) kmax = radix_select(in_bin(c.bin, c.bin == kb ? kmax : SEL_NONE), target - c.before, true, L);
+    }
+    if (tid == 0) rs.thr[b] = kmax;
+}
+
+// step 3 of a sampled row, and the commit of every row the stage owns
+__global__ __launch_bounds__(SEL_THREADS) void select_rows_kernel(const float* __restrict__ logits, int V, int ld, RowSel rs, StepState st,
+                                                                  const float* __restrict__ pval, const int32_t* __restrict__ pidx) {
+    constexpr int NWV = SEL_THREADS / 64;
+    __shared__ float s_best;
+    __shared__ int s_bi, s_tok, s_wave;
+    __shared__ uint64_t part[NWV], s_before;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    if (st.sel && !st.sel[b]) return;                                 // uniform per workgroup
+    const bool own = rs.own[b] != 0;
+    if (!own && !rs.legacy_greedy) return;
+    merge_partials(pval, pidx, b, &s_best, &s_bi);
+    const RowParams p = own ? rs.params[b] : RowParams{0.f, 1.f, 0, 1.f, 0.f, 0.f, 0};
+    const bool pen = own && rs.cnt && row_has_pen(p);
+    if (!(p.temperature > 0.f)) {
+        if (tid == 0) commit_row(st, rs, b, V, pen, s_bi);
+        return;
+    }
+    const float* row = pen ? rs.pen + (size_t)b * V : logits + (size_t)b * ld;
+    const float m = s_best, inv_t = 1.0f / p.temperature;
+    const uint32_t kmax = rs.thr[b];
+    // ---- 3. inverse CDF in index order over the kept weights.  Wave w owns the contiguous segment [w seg, (w + 1) seg) and walks it 64
+    // consecutive elements at a time (coalesced loads); the segment sums locate the wave holding x, which walks its segment once more
+    // with a wave-wide inclusive scan per 64 elements.
+    const int wave = tid >> 6, lane = tid & 63;
+    const int seg = (V + NWV - 1) / NWV;
+    const int lo = min(V, wave * seg), hi = min(V, lo + seg);
+    auto weight = [&](int i) -> uint64_t {
+        if (i >= hi) return 0;
+        const float t = (row[i] - m) * inv_t;
+        return sel_in(t) && sel_key(t) <= kmax ? sel_w(t) : 0;
+    };
+    uint64_t s = 0;
+    for (int i = lo + lane; i < hi; i += 64) s += weight(i);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if (lane == 0) part[wave] = s;
+    __syncthreads();
+    const uint64_t h = splitmix64(p.seed ^ splitmix64((uint64_t)(uint32_t)st.out_lens[b]));
+    if (tid == 0) {
+        uint64_t total = 0;
+        for (int w = 0; w < NWV; ++w) total += part[w];
+        const uint64_t x = __umul64hi(h, total);                         // floor(h 2^-64 total) < total
+        uint64_t acc = 0;
+        int w = 0;
+        for (; w < NWV - 1; ++w) {
+            if (acc + part[w] > x) break;
+            acc += part[w];
+        }
+        s_wave = w;
+        s_before = acc;
+        s_tok = -1;
+    }
+    __syncthreads();
+    if (wave == s_wave) {
+        uint64_t total = 0;
+        for (int w = 0; w < NWV; ++w) total += part[w];
+        const uint64_t x = __umul64hi(h, total);
+        uint64_t acc = s_before;
+        for (int base = lo; base < hi; base += 64) {
+            const uint64_t w = weight(base + lane);
+            uint64_t incl = w;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const uint64_t v = __shfl_up(incl, o, 64);
+                if (lane >= o) incl += v;
+            }
+            const uint64_t hit = __ballot(w > 0 && acc + incl > x);
+            if (hit) {
+                if (lane == __ffsll((unsigned long long)hit) - 1) s_tok = base + lane;
+                break;
+            }
+            acc += __shfl(incl, 63, 64);
+        }
+    }
+    __syncthreads();
+    if (tid == 0) commit_row(st, rs, b, V, pen, s_tok >= 0 ? s_tok : s_bi);     // no token: a numerical corner, the arg max
+}
+
+__global__ __launch_bounds__(256) void pen_prompt_kernel(const int32_t* __restrict__ src, const int32_t* __restrict__ last,
+                                                         const int32_t* __restrict__ dst, int image_token, int V, int32_t* __restrict__ cnt,
+                                                         uint32_t* __restrict__ seen) {
+    const int b = blockIdx.x, r = dst ? dst[b] : b, W = (V + 31) >> 5;
+    int32_t* c = cnt + (size_t)r * V;
+    uint32_t* w = seen + (size_t)r * W;
+    for (int i = threadIdx.x; i < V; i += 256) c[i] = 0;
+    for (int i = threadIdx.x; i < W; i += 256) w[i] = 0;
+    __threadfence();
+    __syncthreads();
+    const int t0 = b ? last[b - 1] + 1 : 0, t1 = last[b];
+    for (int t = t0 + threadIdx.x; t <= t1; t += 256) {
+        const int id = src[t] >= 0 ? src[t] : image_token;
+        if (id >= 0 && id < V) atomicOr(&w[id >> 5], 1u << (id & 31));
+    }
+}
+
+__global__ __launch_bounds__(256) void pen_history_kernel(const int32_t* __restrict__ hist, const int32_t* __restrict__ hist_lens, int stride,
+                                                          const int32_t* __restrict__ n_prompt, int V, int32_t* __restrict__ cnt,
+                                                          uint32_t* __restrict__ seen, int32_t* __restrict__ out_lens) {
+    const int b = blockIdx.x, W = (V + 31) >> 5;
+    int32_t* c = cnt + (size_t)b * V;
+    uint32_t* w = seen + (size_t)b * W;
+    for (int i = threadIdx.x; i < V; i += 256) c[i] = 0;
+    for (int i = threadIdx.x; i < W; i += 256) w[i] = 0;
+    __threadfence();
+    __syncthreads();
+    const int n = min(hist_lens[b], stride), np = min(n_prompt[b], n);
+    for (int j = threadIdx.x; j < n; j += 256) {
+        const int id = hist[(size_t)b * stride + j];
+        if (id < 0 || id >= V) continue;
+        if (j < np) atomicOr(&w[id >> 5], 1u << (id & 31));
+        else atomicAdd(&c[id], 1);
+    }
+    if (threadIdx.x == 0) out_lens[b] = n - np;
+}
+
+__global__ void set_row_params_kernel(RowParams* table, int32_t* own, int row, RowParams p, int flag) {
+    table[row] = p;
+    own[row] = flag;
 }
 
 }  // namespace
@@ -856,8 +1271,33 @@ hipError_t launch_argmax_step(hipStream_t s, const float* logits, int V, int ld,
 }
 
 hipError_t launch_sample_step(hipStream_t s, const float* logits, int V, int ld, int B, float temperature, float top_p, uint64_t seed,
-                              const StepState& st) {
+                              const StepState& st, const int32_t* own) {
     if (temperature <= 0.f || top_p <= 0.f) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(sample_step_kernel, dim3(B), dim3(SAMPLE_THREADS), 0, s, logits, V, ld, 1.0f / temperature, fminf(top_p, 1.0f), seed, st);
+    hipLaunchKernelGGL(sample_step_kernel, dim3(B), dim3(SAMPLE_THREADS), 0, s, logits, V, ld, 1.0f / temperature, fminf(top_p, 1.0f), seed, st, own);
+    return hipGetLastError();
+}
+
+hipError_t launch_select_rows(hipStream_t s, const float* logits, int V, int ld, int B, const RowSel& rs, float* pval, int32_t* pidx, const StepState& st) {
+    if (B < 1 || B > DOTS_MAX_BATCH || V < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(select_partial_kernel, dim3(ARGMAX_CHUNKS, B), dim3(256), 0, s, logits, V, ld, rs, st, pval, pidx);
+    hipLaunchKernelGGL(select_thresh_kernel, dim3(B), dim3(SEL_THREADS), 0, s, logits, V, ld, rs, st.sel, (const float*)pval, (const int32_t*)pidx);
+    hipLaunchKernelGGL(select_rows_kernel, dim3(B), dim3(SEL_THREADS), 0, s, logits, V, ld, rs, st, (const float*)pval, (const int32_t*)pidx);
+    return hipGetLastError();
+}
+
+hipError_t launch_pen_prompt(hipStream_t s, const int32_t* src, const int32_t* last, const int32_t* dst, int B, int image_token, int V,
+                             int32_t* cnt, uint32_t* seen) {
+    hipLaunchKernelGGL(pen_prompt_kernel, dim3(B), dim3(256), 0, s, src, last, dst, image_token, V, cnt, seen);
+    return hipGetLastError();
+}
+
+hipError_t launch_pen_history(hipStream_t s, const int32_t* hist, const int32_t* hist_lens, int stride, const int32_t* n_prompt, int B, int V,
+                              int32_t* cnt, uint32_t* seen, int32_t* out_lens) {
+    hipLaunchKernelGGL(pen_history_kernel, dim3(B), dim3(256), 0, s, hist, hist_lens, stride, n_prompt, V, cnt, seen, out_lens);
+    return hipGetLastError();
+}
+
+hipError_t launch_set_row_params(hipStream_t s, RowParams* table, int32_t* own, int row, const RowParams& p, int flag) {
+    hipLaunchKernelGGL(set_row_params_kernel, dim3(1), dim3(1), 0, s, table, own, row, p, flag);
     return hipGetLastError();
 }

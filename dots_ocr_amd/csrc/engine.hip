@@ -11,6 +11,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -195,6 +196,16 @@ struct DotsEngine {
     int n_eos = 0;
     float temperature = 0.f, top_p = 1.f;      // temperature <= 0: greedy (arg max)
     uint64_t seed = 0;
+    // per-row selection (dots_set_row_sampling): device table + own flags, allocated on first use; penalty state
+    // (output counts, prompt-presence bits, penalised-logit scratch) allocated when a row first carries a penalty
+    RowParams* d_rowp = nullptr;
+    int32_t* d_row_own = nullptr;
+    uint32_t* d_row_thr = nullptr;
+    int32_t* pen_cnt = nullptr;
+    uint32_t* pen_seen = nullptr;
+    float* pen_logits = nullptr;
+    int row_own[DOTS_MAX_BATCH] = {0};
+    int n_own = 0;                         // rows with their own parameters: > 0 switches the step to the per-row stage
     int out_cap = 0;                       // row stride of out_ids for the current generation
     bf16_t *d_h = nullptr, *d_q = nullptr, *d_att = nullptr, *d_act = nullptr, *d_xn = nullptr;      // d_xn: normalised rows of batches above 32 rows (decode_b64.hip)
     float* d_part_h = nullptr;                     // [DEC_KSPLIT_PARTS][DOTS_MAX_BATCH][hidden] fp32: the K-quarter sums of a projection above 32 rows (decode_b64.hip)
@@ -216,8 +227,9 @@ struct DotsEngine {
     int32_t *d_sel = nullptr, *d_sel_new = nullptr, *d_max_len = nullptr, *p_dst = nullptr;
     const int32_t* sel_now = nullptr;      // selection mask of the next select_tokens() call
     // captured decode steps, keyed by everything the capture bakes in: rows, KV splits, static batch (out_cap = row stride of
-    // the output buffer) or slot mode (out_cap = 0), number of EOS ids; sampling changes drop the cache (dots_set_sampling)
-    struct StepGraph { int rows, splits, out_cap, n_eos, part; hipGraph_t graph; hipGraphExec_t exec; };
+    // the output buffer) or slot mode (out_cap = 0), number of EOS ids, whether any row carries its own parameters (rowp: the per-row
+    // selection stage); engine-wide sampling changes drop the cache (dots_set_sampling), per-row ones live in device memory
+    struct StepGraph { int rows, splits, out_cap, n_eos, part, rowp; hipGraph_t graph; hipGraphExec_t exec; };
     std::vector<StepGraph> step_graphs;
     std::vector<int> h_prompt_lens;
     int steps_done = 0;
@@ -263,6 +275,10 @@ struct DotsEngine {
         hipFree(p);
     }
 };
+
+static_assert(sizeof(RowParams) == sizeof(DotsSamplingParams) && offsetof(RowParams, seed) == offsetof(DotsSamplingParams, seed) &&
+                  offsetof(RowParams, presence_penalty) == offsetof(DotsSamplingParams, presence_penalty),
+              "RowParams (kernels.h) must mirror DotsSamplingParams");
 
 #define CK(expr)                                                                                         \
     do {                                                                                                 \
@@ -836,7 +852,12 @@ int select_tokens(DotsEngine* e, int advance) {
     st.eos_ids = e->eos_ids; st.n_eos = e->n_eos; st.advance_ctx = advance;
     if (e->slot_mode) { st.sel = e->sel_now; st.max_len = e->d_max_len; st.out_stride = c.max_seq_len; st.cap = c.max_seq_len; }
     else { st.sel = nullptr; st.max_len = nullptr; st.out_stride = e->out_cap; st.cap = e->out_cap; }
-    if (e->temperature > 0.f)
+    if (e->n_own > 0) {          // per-row stage for the rows with their own parameters (+ the greedy rows that follow the engine)
+        const RowSel rs{e->d_rowp, e->d_row_own, e->pen_cnt, e->pen_seen, e->pen_logits, e->d_row_thr, e->temperature > 0.f ? 0 : 1};
+        CK(launch_select_rows(e->stream, e->d_logits, c.vocab_size, c.vocab_size, e->B_sel, rs, e->am_val, e->am_idx, st));
+        if (e->temperature > 0.f)
+            CK(launch_sample_step(e->stream, e->d_logits, c.vocab_size, c.vocab_size, e->B_sel, e->temperature, e->top_p, e->seed, st, e->d_row_own));
+    } else if (e->temperature > 0.f)
         CK(launch_sample_step(e->stream, e->d_logits, c.vocab_size, c.vocab_size, e->B_sel, e->temperature, e->top_p, e->seed, st));
     else
         CK(launch_argmax_step(e->stream, e->d_logits, c.vocab_size, c.vocab_size, e->B_sel, e->am_val, e->am_idx, st));
@@ -849,6 +870,44 @@ void drop_step_graphs(DotsEngine* e) {
         hipGraphDestroy(g.graph);
     }
     e->step_graphs.clear();
+}
+
+int ensure_row_table(DotsEngine* e) {
+    if (e->d_rowp) return DOTS_OK;
+    CK(e->alloc(&e->d_rowp, DOTS_MAX_BATCH));
+    CK(e->alloc(&e->d_row_own, DOTS_MAX_BATCH));
+    CK(e->alloc(&e->d_row_thr, DOTS_MAX_BATCH));
+    return DOTS_OK;
+}
+
+int ensure_pen_state(DotsEngine* e) {
+    if (e->pen_cnt) return DOTS_OK;
+    const size_t rows = e->cfg.max_batch, V = e->cfg.vocab_size;
+    CK(e->alloc(&e->pen_cnt, rows * V));
+    CK(e->alloc(&e->pen_seen, rows * ((V + 31) / 32)));
+    CK(e->alloc(&e->pen_logits, rows * V));
+    drop_step_graphs(e);                                   // graphs captured before hold no penalty state
+    return DOTS_OK;
+}
+
+// the row's entry back to the engine-wide setting (stream ordered)
+int clear_row(DotsEngine* e, int row) {
+    if (!e->row_own[row]) return DOTS_OK;
+    CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, RowParams{}, 0));
+    e->row_own[row] = 0;
+    e->n_own -= 1;
+    return DOTS_OK;
+}
+
+int check_row_params(DotsEngine* e, const DotsSamplingParams& p, RowParams* out) {
+    if (!(p.temperature >= 0.f) || !std::isfinite(p.temperature)) return e->fail(DOTS_E_INVALID, "temperature must be finite and >= 0");
+    if (!(p.top_p > 0.f)) return e->fail(DOTS_E_INVALID, "top_p must be in (0, 1]");
+    if (p.top_k < 0) return e->fail(DOTS_E_INVALID, "top_k must be 0 (off) or >= 1");
+    if (!(p.repetition_penalty > 0.f) || !std::isfinite(p.repetition_penalty)) return e->fail(DOTS_E_INVALID, "repetition_penalty must be finite and > 0");
+    if (!(p.frequency_penalty >= -2.f && p.frequency_penalty <= 2.f)) return e->fail(DOTS_E_INVALID, "frequency_penalty must be in [-2, 2]");
+    if (!(p.presence_penalty >= -2.f && p.presence_penalty <= 2.f)) return e->fail(DOTS_E_INVALID, "presence_penalty must be in [-2, 2]");
+    *out = RowParams{p.temperature, p.top_p > 1.f ? 1.f : p.top_p, p.top_k, p.repetition_penalty, p.frequency_penalty, p.presence_penalty, p.seed};
+    return DOTS_OK;
 }
 
 // CU-masked side streams of the vision prefetch, created on first use.  Mask bit i = CU i / 8 of XCD i % 8 (profiles/r01_probe_cu_mask.txt):
@@ -1070,6 +1129,8 @@ int prefill(DotsEngine* e, const int32_t* ids, const int32_t* lens, int B, const
             e->dbg_lm_rows = T;
         }
     }
+    // prompt-presence bits (repetition penalty) of the prefilled rows, once any row has used a penalty
+    if (e->pen_cnt) CK(launch_pen_prompt(s, e->p_src, e->p_last, slots ? e->p_dst : nullptr, B, c.image_token_id, c.vocab_size, e->pen_cnt, e->pen_seen));
     // last position of every sequence -> final norm -> lm_head -> first token
     CK(launch_gather_rows(s, e->p_x, e->p_last, slots ? e->p_dst : nullptr, e->d_h, B, H));
     CK(launch_dec_lmhead(s, e->d_h, e->final_norm, e->lm_head_d, e->lm_head_s, e->d_logits, rows, H, c.vocab_size, c.rms_norm_eps));
@@ -1142,10 +1203,14 @@ int splits_for_ctx(int max_ctx) { return decode_attn_splits(max_ctx); }
 
 // The captured decode step for (rows = e->B, splits, out_cap, e->n_eos): looked up in the cache or captured now.
 int step_graph(DotsEngine* e, int rows, int n_splits, int out_cap, hipGraphExec_t* exec, int part = 0) {
+    const int rowp = e->n_own > 0 ? 1 : 0;
     for (auto& g : e->step_graphs)
-        if (g.rows == rows && g.splits == n_splits && g.out_cap == out_cap && g.n_eos == e->n_eos && g.part == part) { *exec = g.exec; return DOTS_OK; }
+        if (g.rows == rows && g.splits == n_splits && g.out_cap == out_cap && g.n_eos == e->n_eos && g.part == part && g.rowp == rowp) {
+            *exec = g.exec;
+            return DOTS_OK;
+        }
     if (e->step_graphs.size() >= 32) drop_step_graphs(e);
-    DotsEngine::StepGraph g{rows, n_splits, out_cap, e->n_eos, part, nullptr, nullptr};
+    DotsEngine::StepGraph g{rows, n_splits, out_cap, e->n_eos, part, rowp, nullptr, nullptr};
     CK(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
     int r = decode_step_launches(e, n_splits, part);
     hipError_t ce = hipStreamEndCapture(e->stream, &g.graph);
@@ -1516,6 +1581,9 @@ int dots_slots_reset(DotsEngine* e) {
     CK(hipMemsetAsync(e->ctx_len, 0, e->cfg.max_batch * 4, s));
     CK(hipMemsetAsync(e->out_lens, 0, e->cfg.max_batch * 4, s));
     CK(hipMemsetAsync(e->finished, 0, e->cfg.max_batch * 4, s));
+    if (e->d_row_own) CK(hipMemsetAsync(e->d_row_own, 0, DOTS_MAX_BATCH * 4, s));
+    std::fill(e->row_own, e->row_own + DOTS_MAX_BATCH, 0);
+    e->n_own = 0;
     CK(hipStreamSynchronize(s));
     e->slot_mode = true;
     e->sel_dirty = true;
@@ -1624,6 +1692,7 @@ int dots_slot_release(DotsEngine* e, int slot) {
     if (!e) return DOTS_E_INVALID;
     if (!e->slot_mode || slot < 0 || slot >= e->cfg.max_batch || !e->slot_active[slot]) return e->fail(DOTS_E_STATE, "slot %d is not occupied", slot);
     CK(hipSetDevice(e->device));
+    RET(clear_row(e, slot));
     e->slot_active[slot] = 0;
     e->sel_dirty = true;
     CK(hipMemsetAsync(e->ctx_len + slot, 0, 4, e->stream));          // an idle row attends over one key only ...
@@ -1750,6 +1819,20 @@ int dots_set_sampling(DotsEngine* e, float temperature, float top_p, uint64_t se
     e->top_p = top_p > 1.f ? 1.f : top_p;
     e->seed = seed;
     drop_step_graphs(e);                                   // the captured decode steps bake these values in
+    return DOTS_OK;
+}
+
+int dots_set_row_sampling(DotsEngine* e, int row, const DotsSamplingParams* p) {
+    if (!e) return DOTS_E_INVALID;
+    if (row < 0 || row >= e->cfg.max_batch) return e->fail(DOTS_E_INVALID, "row %d out of range [0, %d)", row, e->cfg.max_batch);
+    CK(hipSetDevice(e->device));
+    if (!p) return e->d_rowp ? clear_row(e, row) : DOTS_OK;
+    RowParams rp;
+    RET(check_row_params(e, *p, &rp));
+    RET(ensure_row_table(e));
+    if (rp.repetition_penalty != 1.f || rp.frequency_penalty != 0.f || rp.presence_penalty != 0.f) RET(ensure_pen_state(e));
+    CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, rp, 1));
+    if (!e->row_own[row]) { e->row_own[row] = 1; e->n_own += 1; }
     return DOTS_OK;
 }
 
@@ -2210,6 +2293,93 @@ int dots_op_dec_lmhead(DotsEngine* e, const void* h, const void* ln_w, const voi
     CK(launch_dec_lmhead(e->stream, (const bf16_t*)h, (const bf16_t*)ln_w, wd, wscale, (float*)logits_out, B, H, V, eps, e->force_part ? e->dec_cus : 0, xn));
     CK(hipStreamSynchronize(e->stream));
     return DOTS_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// dots_op_select_tokens / dots_bench_select_tokens.  mode 2 = the per-row stage once (the op); mode 0 / 1 / 2 with iters > 0 = the legacy
+// arg max pair / the legacy sampler (params[0].temperature, top_p, seed) / the per-row stage, replayed iters times between two events
+// with every row marked finished (nothing is appended), *ms = the mean time of one replay.
+int select_op(DotsEngine* e, const float* logits_dev, int B, int V, const DotsSamplingParams* params_host, const int32_t* hist_dev,
+              const int32_t* hist_lens_dev, int hist_stride, const int32_t* n_prompt_dev, int32_t* out_tokens_dev, int mode, int iters, float* ms) {
+    if (!e || !logits_dev || B < 1 || B > DOTS_MAX_BATCH || V < 1 || !params_host || !hist_dev || !hist_lens_dev || hist_stride < 1 || !n_prompt_dev ||
+        (!out_tokens_dev && !ms) || mode < 0 || mode > 2)
+        return e ? e->fail(DOTS_E_INVALID, "bad select_tokens arguments") : DOTS_E_INVALID;
+    std::vector<RowParams> rp(B);
+    for (int b = 0; b < B; ++b) RET(check_row_params(e, params_host[b], &rp[b]));
+    if (mode == 1 && !(rp[0].temperature > 0.f)) return e->fail(DOTS_E_INVALID, "the legacy sampler needs temperature > 0");
+    const std::vector<int32_t> own(B, 1);
+    CK(hipSetDevice(e->device));
+    Scratch sc(e);
+    const size_t W = ((size_t)V + 31) / 32;
+    RowParams* tab = nullptr;
+    int32_t *own_d = nullptr, *cnt = nullptr, *pidx = nullptr, *cur = nullptr, *ctx = nullptr, *ids = nullptr, *lens = nullptr, *fin = nullptr;
+    uint32_t *seen = nullptr, *thr = nullptr;
+    float *pen = nullptr, *pval = nullptr;
+    CK(sc.get(&tab, B));
+    CK(sc.get(&own_d, B));
+    CK(sc.get(&thr, B));
+    CK(sc.get(&cnt, (size_t)B * V));
+    CK(sc.get(&seen, (size_t)B * W));
+    CK(sc.get(&pen, (size_t)B * V));
+    CK(sc.get(&pval, (size_t)B * 64));
+    CK(sc.get(&pidx, (size_t)B * 64));
+    CK(sc.get(&cur, B));
+    CK(sc.get(&ctx, B));
+    CK(sc.get(&ids, (size_t)B * (hist_stride + 1)));
+    CK(sc.get(&lens, B));
+    CK(sc.get(&fin, B));
+    CK(hipMemcpyAsync(tab, rp.data(), B * sizeof(RowParams), hipMemcpyHostToDevice, e->stream));
+    CK(hipMemcpyAsync(own_d, own.data(), B * 4, hipMemcpyHostToDevice, e->stream));
+    CK(launch_pen_history(e->stream, hist_dev, hist_lens_dev, hist_stride, n_prompt_dev, B, V, cnt, seen, lens));
+    StepState st;
+    st.cur_tokens = cur; st.ctx_len = ctx; st.out_ids = ids; st.out_lens = lens; st.finished = fin;
+    st.eos_ids = e->eos_ids; st.sel = nullptr; st.max_len = nullptr;
+    st.n_eos = 0; st.out_stride = hist_stride + 1; st.cap = hist_stride + 2; st.advance_ctx = 0;
+    const RowSel rs{tab, own_d, cnt, seen, pen, thr, 0};
+    auto run = [&]() -> hipError_t {
+        if (mode == 0) return launch_argmax_step(e->stream, logits_dev, V, V, B, pval, pidx, st);
+        if (mode == 1) return launch_sample_step(e->stream, logits_dev, V, V, B, rp[0].temperature, rp[0].top_p, rp[0].seed, st);
+        return launch_select_rows(e->stream, logits_dev, V, V, B, rs, pval, pidx, st);
+    };
+    if (iters <= 0) {
+        CK(run());
+        CK(hipMemcpyAsync(out_tokens_dev, cur, B * 4, hipMemcpyDeviceToDevice, e->stream));
+        CK(hipStreamSynchronize(e->stream));
+        return DOTS_OK;
+    }
+    const std::vector<int32_t> ones(B, 1);
+    CK(hipMemcpyAsync(fin, ones.data(), B * 4, hipMemcpyHostToDevice, e->stream));
+    for (int i = 0; i < 3; ++i) CK(run());                                  // warm-up
+    hipEvent_t t0 = nullptr, t1 = nullptr;
+    CK(hipEventCreate(&t0));
+    CK(hipEventCreate(&t1));
+    hipError_t r = hipEventRecord(t0, e->stream);
+    for (int i = 0; i < iters && r == hipSuccess; ++i) r = run();
+    if (r == hipSuccess) r = hipEventRecord(t1, e->stream);
+    if (r == hipSuccess) r = hipEventSynchronize(t1);
+    float total = 0.f;
+    if (r == hipSuccess) r = hipEventElapsedTime(&total, t0, t1);
+    hipEventDestroy(t0);
+    hipEventDestroy(t1);
+    CK(r);
+    *ms = total / iters;
+    return DOTS_OK;
+}
+}  // namespace
+
+extern "C" {
+int dots_op_select_tokens(DotsEngine* e, const float* logits_dev, int B, int V, const DotsSamplingParams* params_host, const int32_t* hist_dev,
+                          const int32_t* hist_lens_dev, int hist_stride, const int32_t* n_prompt_dev, int32_t* out_tokens_dev) {
+    if (!out_tokens_dev) return e ? e->fail(DOTS_E_INVALID, "bad select_tokens arguments") : DOTS_E_INVALID;
+    return select_op(e, logits_dev, B, V, params_host, hist_dev, hist_lens_dev, hist_stride, n_prompt_dev, out_tokens_dev, 2, 0, nullptr);
+}
+
+int dots_bench_select_tokens(DotsEngine* e, const float* logits_dev, int B, int V, const DotsSamplingParams* params_host, const int32_t* hist_dev,
+                             const int32_t* hist_lens_dev, int hist_stride, const int32_t* n_prompt_dev, int mode, int iters, float* ms_out) {
+    if (!ms_out || iters < 1) return e ? e->fail(DOTS_E_INVALID, "bad bench_select_tokens arguments") : DOTS_E_INVALID;
+    return select_op(e, logits_dev, B, V, params_host, hist_dev, hist_lens_dev, hist_stride, n_prompt_dev, nullptr, mode, iters, ms_out);
 }
 
 }  // extern "C"

@@ -118,8 +118,35 @@ struct StepState {
     int n_eos, out_stride, cap, advance_ctx;
 };
 hipError_t launch_argmax_step(hipStream_t s, const float* logits, int V, int ld, int B, float* pval, int32_t* pidx, const StepState& st);
+// own != nullptr: skip the rows with own[b] != 0 (they carry per-row parameters: launch_select_rows)
 hipError_t launch_sample_step(hipStream_t s, const float* logits, int V, int ld, int B, float temperature, float top_p, uint64_t seed,
-                              const StepState& st);
+                              const StepState& st, const int32_t* own = nullptr);
+// Per-row token selection (decode.hip).  RowParams mirrors DotsSamplingParams (include/dots_ocr_hip.h) field for field.
+struct RowParams { float temperature, top_p; int32_t top_k; float repetition_penalty, frequency_penalty, presence_penalty; uint64_t seed; };
+// Device state of the stage.  params / own: [DOTS_MAX_BATCH]; a row with own[b] == 0 follows the engine-wide setting: the stage selects it
+// only when legacy_greedy != 0 (arg max), otherwise launch_sample_step(.., own) does.  cnt [rows][V] int32 (generated-token counts),
+// seen [rows][ceil(V / 32)] (prompt-presence bits) and pen [rows][V] fp32 (penalised logits, scratch) are nullptr until a penalty is used.
+struct RowSel {
+    const RowParams* params;
+    const int32_t* own;
+    int32_t* cnt;
+    const uint32_t* seen;
+    float* pen;
+    uint32_t* thr;              // [DOTS_MAX_BATCH] scratch: the largest key a sampled row keeps (decode.hip)
+    int legacy_greedy;
+};
+// pval / pidx: ARGMAX_CHUNKS (64) partials per row, as launch_argmax_step
+hipError_t launch_select_rows(hipStream_t s, const float* logits, int V, int ld, int B, const RowSel& rs, float* pval, int32_t* pidx, const StepState& st);
+// Prompt-presence bits of freshly prefilled rows from the packed prompt (src as launch_embed_gather: < 0 = an image row, i.e. image_token);
+// sequence b ends at packed token last[b] and lives in row dst[b] (dst == nullptr: row b).  Clears the rows' counts too.
+hipError_t launch_pen_prompt(hipStream_t s, const int32_t* src, const int32_t* last, const int32_t* dst, int B, int image_token, int V,
+                             int32_t* cnt, uint32_t* seen);
+// Penalty state from explicit histories (dots_op_select_tokens): row b holds hist[b][0, n_prompt[b]) prompt ids, then its generated ids up
+// to hist_lens[b]; out_lens[b] = generated count.
+hipError_t launch_pen_history(hipStream_t s, const int32_t* hist, const int32_t* hist_lens, int stride, const int32_t* n_prompt, int B, int V,
+                              int32_t* cnt, uint32_t* seen, int32_t* out_lens);
+// table[row] = p, own[row] = flag, in stream order
+hipError_t launch_set_row_params(hipStream_t s, RowParams* table, int32_t* own, int row, const RowParams& p, int flag);
 // row-major [rows, K] -> MFMA fragment order (decode.hip): 16-row tiles x K/32 chunks of 1 KiB
 hipError_t launch_pack_frag(hipStream_t s, const bf16_t* src, bf16_t* dst, int64_t rows, int K);
 // fused qkv weight [(Hq + 2 Hkv) * 128, K]: as launch_pack_frag, q / k head rows permuted so that a 16-row tile holds whole RoPE pairs

@@ -6,7 +6,9 @@ No torch types cross this boundary: numpy arrays for host buffers, integers for 
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
+from dataclasses import dataclass
 from typing import Dict, Optional, Sequence
 
 import numpy as np
@@ -45,6 +47,64 @@ class CDotsStats(C.Structure):
     ]
 
 
+class CDotsSamplingParams(C.Structure):
+    _fields_ = [
+        ("temperature", C.c_float), ("top_p", C.c_float), ("top_k", C.c_int32),
+        ("repetition_penalty", C.c_float), ("frequency_penalty", C.c_float), ("presence_penalty", C.c_float),
+        ("seed", C.c_uint64),
+    ]
+
+
+@dataclass(frozen=True)
+class SamplingParams:
+    """Token selection of one request / decode row (include/dots_ocr_hip.h DotsSamplingParams).
+
+    temperature 0 = greedy; top_k <= 0 = off, and top_k is clamped to TOP_K_MAX (a k at or above the vocabulary keeps every token);
+    top_p is clamped to (0, 1]; repetition_penalty 1 and frequency / presence 0 = off.  The float fields are checked as the fp32 values
+    the engine receives.  Invalid values raise ValueError."""
+    temperature: float = 0.0
+    top_p: float = 1.0
+    top_k: int = 0
+    repetition_penalty: float = 1.0
+    frequency_penalty: float = 0.0
+    presence_penalty: float = 0.0
+    seed: int = 0
+
+    TOP_K_MAX = 2 ** 31 - 1                      # int32_t top_k of DotsSamplingParams
+
+    def __post_init__(self):
+        f32 = lambda v: C.c_float(float(v)).value                                      # noqa: E731 (what the C struct holds)
+        t, p, r = f32(self.temperature), float(self.top_p), f32(self.repetition_penalty)
+        f, pr = f32(self.frequency_penalty), f32(self.presence_penalty)
+        if not (math.isfinite(t) and t >= 0):
+            raise ValueError(f"temperature must be finite and >= 0, got {self.temperature!r}")
+        if not (p > 0) or math.isnan(p):
+            raise ValueError(f"top_p must be in (0, 1], got {self.top_p!r}")
+        if not (math.isfinite(r) and r > 0):
+            raise ValueError(f"repetition_penalty must be finite and > 0, got {self.repetition_penalty!r}")
+        for name, v in (("frequency_penalty", f), ("presence_penalty", pr)):
+            if not (-2.0 <= v <= 2.0):
+                raise ValueError(f"{name} must be in [-2, 2], got {v!r}")
+        k = int(self.top_k)
+        if k != self.top_k:
+            raise ValueError(f"top_k must be an integer, got {self.top_k!r}")
+        object.__setattr__(self, "temperature", t)
+        object.__setattr__(self, "top_p", min(p, 1.0))
+        object.__setattr__(self, "top_k", min(max(k, 0), self.TOP_K_MAX))
+        object.__setattr__(self, "repetition_penalty", r)
+        object.__setattr__(self, "frequency_penalty", f)
+        object.__setattr__(self, "presence_penalty", pr)
+        object.__setattr__(self, "seed", int(self.seed) & (2 ** 64 - 1))
+
+    @property
+    def has_penalty(self) -> bool:
+        return self.repetition_penalty != 1.0 or self.frequency_penalty != 0.0 or self.presence_penalty != 0.0
+
+    def to_c(self) -> CDotsSamplingParams:
+        return CDotsSamplingParams(self.temperature, self.top_p, self.top_k, self.repetition_penalty, self.frequency_penalty,
+                                   self.presence_penalty, self.seed)
+
+
 class DotsEngineError(RuntimeError):
     pass
 
@@ -74,6 +134,7 @@ def _prototypes(lib):
         "dots_generate": (i32, [vp, P(i32), P(i32), i32, vp, i32, i64, P(i64), i32, i32, P(i32), i32, P(i32), P(i32)]),
         "dots_preprocess_image": (i32, [vp, vp, i32, i32, i32, i32, i32, P(i32), P(i32), i32, P(i32), P(i32), i32, P(f32), P(f32), f32, vp]),
         "dots_set_sampling": (i32, [vp, f32, f32, C.c_uint64]),
+        "dots_set_row_sampling": (i32, [vp, i32, P(CDotsSamplingParams)]),
         "dots_set_decode_plan": (i32, [vp, i32]),
         "dots_set_gemm_plan": (i32, [vp, i32]),
         "dots_tower_tail": (i32, [vp, i32, P(i32)]),
@@ -115,6 +176,8 @@ def _prototypes(lib):
         "dots_op_dec_proj": (i32, [vp, vp, vp, vp, i32, i32, i32, i32]),
         "dots_op_dec_gateup": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32]),
         "dots_op_dec_lmhead": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, f32, i32]),
+        "dots_op_select_tokens": (i32, [vp, vp, i32, i32, P(CDotsSamplingParams), vp, vp, i32, vp, vp]),
+        "dots_bench_select_tokens": (i32, [vp, vp, i32, i32, P(CDotsSamplingParams), vp, vp, i32, vp, i32, i32, P(f32)]),
         "dots_probe_mfma": (i32, [i32, vp, vp, vp, vp]),
         "dots_probe_grid_barrier": (i32, [i32, i32, i32, i32, i32, P(f32), P(i32)]),
         "dots_probe_cu_mask": (i32, [P(C.c_uint32), i32, i32, i32, i32, P(C.c_uint32)]),
@@ -136,6 +199,7 @@ EXPORTED_SYMBOLS = [
     "dots_op_flash_attn", "dots_plan_flash_xcd", "dots_op_qkv_rope_split", "dots_op_qkv_proj_rope", "dots_op_dec_qkv", "dots_op_decode_attn", "dots_op_dec_proj", "dots_op_dec_gateup",
     "dots_op_dec_lmhead", "dots_probe_mfma", "dots_probe_grid_barrier", "dots_probe_cu_mask",
     "dots_set_kv_scales", "dots_debug_read_kv", "dots_op_dec_qkv_kv8", "dots_op_decode_attn_kv8",
+    "dots_set_row_sampling", "dots_op_select_tokens", "dots_bench_select_tokens",
 ]
 
 KV_CACHE_DTYPES = {"bf16": 0, "fp8": 1}      # DotsConfig.kv_cache_dtype; "fp8" = OCP e4m3fn (vLLM's --kv-cache-dtype fp8)
@@ -359,6 +423,37 @@ class Engine:
     def set_sampling(self, temperature: float = 0.0, top_p: float = 1.0, seed: int = 0):
         """temperature 0 = greedy; otherwise softmax(logits/T) restricted to the top_p nucleus, reproducible from seed."""
         self._ck(self.lib.dots_set_sampling(self.h, float(temperature), float(top_p), int(seed) & (2 ** 64 - 1)), "dots_set_sampling")
+
+    def set_row_sampling(self, row: int, params: Optional[SamplingParams]):
+        """Give decode row `row` (a slot, or sequence `row` of a static batch) its own SamplingParams from the next selected token on;
+        None returns it to the set_sampling setting.  Captured decode graphs are kept.  Set a row's penalties BEFORE its prefill: for a
+        penalty switched on mid-run, only tokens selected after the switch are counted, and the prompt counts only if some row had used a
+        penalty before that row's prefill (include/dots_ocr_hip.h)."""
+        if params is None:
+            self._ck(self.lib.dots_set_row_sampling(self.h, int(row), None), "dots_set_row_sampling")
+            return
+        if not isinstance(params, SamplingParams):
+            raise TypeError("params must be a SamplingParams or None")
+        c = params.to_c()
+        self._ck(self.lib.dots_set_row_sampling(self.h, int(row), C.byref(c)), "dots_set_row_sampling")
+
+    def select_tokens(self, logits, B: int, V: int, params: Sequence[SamplingParams], hist, hist_lens, hist_stride: int, n_prompt, out_tokens):
+        """The per-row selection stage on device buffers (dots_op_select_tokens): logits fp32 [B, V], hist int32 [B, hist_stride]
+        (prompt ids then generated ids), hist_lens / n_prompt / out_tokens int32 [B]."""
+        if len(params) != B:
+            raise ValueError("one SamplingParams per row")
+        arr = (CDotsSamplingParams * B)(*[p.to_c() for p in params])
+        self._ck(self.lib.dots_op_select_tokens(self.h, logits, int(B), int(V), arr, hist, hist_lens, int(hist_stride), n_prompt, out_tokens),
+                 "dots_op_select_tokens")
+
+    def bench_select_tokens(self, logits, B: int, V: int, params: Sequence[SamplingParams], hist, hist_lens, hist_stride: int, n_prompt,
+                            mode: int, iters: int) -> float:
+        """mean ms of one selection stage: mode 0 = arg max pair, 1 = engine-wide sampler (params[0]), 2 = per-row stage"""
+        arr = (CDotsSamplingParams * B)(*[p.to_c() for p in params])
+        ms = C.c_float()
+        self._ck(self.lib.dots_bench_select_tokens(self.h, logits, int(B), int(V), arr, hist, hist_lens, int(hist_stride), n_prompt, int(mode),
+                                                   int(iters), C.byref(ms)), "dots_bench_select_tokens")
+        return float(ms.value)
 
     def set_decode_plan(self, plan: int):
         """0 = launch plan by stream (whole chip / CU partition beside a prefetched tower), 1 = the partition plan (whole-tile projections,

@@ -129,7 +129,9 @@ class DotsOcrHipForCausalLM:
     # ------------------------------------------------------------------ generate
     def generate(self, input_ids=None, attention_mask=None, pixel_values=None, image_grid_thw=None,
                  max_new_tokens: int = 128, do_sample: Optional[bool] = None, temperature: Optional[float] = None,
-                 top_p: Optional[float] = None, seed: int = 0, eos_token_id=None, pad_token_id=None, continuous: Optional[bool] = None, **_):
+                 top_p: Optional[float] = None, seed: int = 0, eos_token_id=None, pad_token_id=None, continuous: Optional[bool] = None,
+                 top_k: Optional[int] = None, repetition_penalty: Optional[float] = None, frequency_penalty: Optional[float] = None,
+                 presence_penalty: Optional[float] = None, **_):
         """HF-shaped generate.  do_sample / temperature / top_p default to the checkpoint's generation_config.json (greedy when it
         is absent); with sampling on, tokens are drawn on the GPU from softmax(logits / temperature) restricted to the top_p
         nucleus, reproducibly from `seed`.  Returns LongTensor
@@ -137,10 +139,25 @@ class DotsOcrHipForCausalLM:
 
         More sequences than engine slots (B > max_batch) run with continuous batching: a slot is refilled with the next
         sequence as soon as its page hits EOS instead of waiting for the slowest page of a static batch
-        (`continuous=True/False` forces either mode; greedy results are identical)."""
+        (`continuous=True/False` forces either mode; greedy results are identical).
+
+        top_k / repetition_penalty (HF) and frequency_penalty / presence_penalty (OpenAI), when given with a non-neutral value, switch
+        to per-row selection (Engine.set_row_sampling): sequence b is drawn with seed + b, whatever row or batch it lands
+        in; the rows are cleared afterwards.  These keys are deliberately not read from generation_config.json: that would change the
+        default output of existing checkpoints."""
+        import dataclasses
         import torch
         t_eff, p_eff = resolve_sampling(self.generation_config, do_sample, temperature, top_p)
         self.engine.set_sampling(t_eff, p_eff, seed if t_eff > 0 else 0)
+        row_sp = None
+        if (top_k or 0) > 0 or repetition_penalty not in (None, 1.0) or (frequency_penalty or 0.0) != 0.0 or (presence_penalty or 0.0) != 0.0:
+            from .engine import SamplingParams
+            base = SamplingParams(temperature=t_eff, top_p=p_eff, top_k=int(top_k or 0),
+                                  repetition_penalty=1.0 if repetition_penalty is None else float(repetition_penalty),
+                                  frequency_penalty=float(frequency_penalty or 0.0), presence_penalty=float(presence_penalty or 0.0), seed=seed)
+
+            def row_sp(b):
+                return dataclasses.replace(base, seed=int(seed) + b)
         ids = input_ids.detach().cpu().numpy()
         B, T = ids.shape
         mask = attention_mask.detach().cpu().numpy().astype(bool) if attention_mask is not None else np.ones_like(ids, bool)
@@ -194,9 +211,10 @@ class DotsOcrHipForCausalLM:
                 if img_of_seq[b]:
                     lo, hi = int(patch_off[img_of_seq[b][0]]), int(patch_off[img_of_seq[b][-1] + 1])
                     pix = pv_dev[lo:hi] if pv_dev is not None else pv_host[lo:hi]
-                    reqs.append(Request(prompts[b], pix, grid[img_of_seq[b][0]:img_of_seq[b][-1] + 1], max_new_tokens))
+                    reqs.append(Request(prompts[b], pix, grid[img_of_seq[b][0]:img_of_seq[b][-1] + 1], max_new_tokens,
+                                        sampling=row_sp(b) if row_sp else None))
                 else:
-                    reqs.append(Request(prompts[b], None, None, max_new_tokens))
+                    reqs.append(Request(prompts[b], None, None, max_new_tokens, sampling=row_sp(b) if row_sp else None))
             outs = ContinuousBatcher(self.engine, eos_ids=eos).run(reqs)
             for b, o in enumerate(outs):
                 new_tokens[b, :len(o)] = o
@@ -219,8 +237,13 @@ class DotsOcrHipForCausalLM:
             pix, g, on_dev = pixels_of(plan[0])
             self.engine.vit_prefetch(pix, g, on_device=on_dev)
         prefetched = pipelined                   # a tower is in flight / waiting to be taken
+        rows_set = 0                             # rows given per-row parameters (cleared on the way out)
         try:
             for k, sl in enumerate(plan):
+                if row_sp:
+                    for j, b in enumerate(sl):
+                        self.engine.set_row_sampling(j, row_sp(b))
+                    rows_set = max(rows_set, len(sl))
                 lens = np.array([len(prompts[b]) for b in sl], np.int32)
                 packed = np.concatenate([prompts[b] for b in sl])
                 pix, g, on_dev = pixels_of(sl)
@@ -246,6 +269,9 @@ class DotsOcrHipForCausalLM:
                 except Exception:
                     pass
             raise
+        finally:
+            for j in range(rows_set):
+                self.engine.set_row_sampling(j, None)
         full = np.concatenate([ids.astype(np.int64), new_tokens[:, :n_max]], axis=1)    # HF stops at the longest sequence
         res = torch.from_numpy(full)
         return res.to(input_ids.device) if input_ids.is_cuda else res

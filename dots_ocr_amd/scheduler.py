@@ -25,6 +25,7 @@ class Request:
     grid_thw: Optional[np.ndarray] = None       # int64 [n_img, 3]
     max_new_tokens: int = 128
     tag: object = None
+    sampling: Optional[object] = None           # engine.SamplingParams of this request, or None = the engine-wide setting
 
     def n_patches(self) -> int:
         if self.grid_thw is None:
@@ -69,6 +70,7 @@ class ContinuousBatcher:
         self.decode_steps = 0
         self.admissions = 0
         self._last_lens: Dict[int, int] = {}                     # slot -> tokens generated as of the last poll
+        self._row_params: Dict[int, object] = {}                 # slot -> the SamplingParams set on it (engine.set_row_sampling)
         self.kv_truncated = 0                                    # sequences ended early by a dry KV pool (finish reason "kv_pool_exhausted")
         engine.set_eos(list(eos_ids))
         if hasattr(engine, "slots_reset"):           # start from an empty engine: no occupied slot, every KV page in the pool
@@ -172,7 +174,19 @@ class ContinuousBatcher:
         slots = [s for s, _, _ in group]
         lens = [int(r.input_ids.shape[0]) for _, _, r in group]
         caps = [int(r.max_new_tokens) for _, _, r in group]
-        self.engine.slots_prefill(slots, np.concatenate([r.input_ids for _, _, r in group]), lens, caps)
+        for s, _, r in group:                        # per-row parameters apply from the first token the prefill selects
+            if r.sampling is not None:
+                self.engine.set_row_sampling(s, r.sampling)
+                self._row_params[s] = r.sampling
+            elif self._row_params.pop(s, None) is not None:
+                self.engine.set_row_sampling(s, None)
+        try:
+            self.engine.slots_prefill(slots, np.concatenate([r.input_ids for _, _, r in group]), lens, caps)
+        except Exception:
+            for s in slots:                          # the slots stay free: leave no entry on them (it would keep the per-row stage on)
+                if self._row_params.pop(s, None) is not None:
+                    self.engine.set_row_sampling(s, None)
+            raise
         for s, rid, r in group:
             self.running[s] = (rid, r)
             self._last_lens[s] = 0                   # a reused slot must not inherit its previous occupant's length (_soon_free counted a

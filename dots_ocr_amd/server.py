@@ -10,9 +10,10 @@ serves exactly that wire format from the MI355X engine, so those callers work un
 
 Concurrent requests (the reference client uses a ThreadPool of up to 64, parser.py:286-290) share the engine the way they
 share a vLLM server: `ContinuousWorker` admits a request into a free sequence slot as soon as one exists and refills slots
-as pages finish (dots_ocr_amd/scheduler.py), for requests with the same sampling parameters; requests with other
-parameters wait for the running set to drain.  `BatchingWorker` (static batches through `model.generate`) remains for
-model objects without engine slots.
+as pages finish (dots_ocr_amd/scheduler.py).  On an engine with per-row selection (Engine.set_row_sampling) every request
+carries its own sampling parameters on its slot and one running set serves them all; on an engine without it, requests with
+other parameters wait for the running set to drain, and a request that asks for top_k or a penalty is refused (400).
+`BatchingWorker` (static batches through `model.generate`) remains for model objects without engine slots.
 """
 from __future__ import annotations
 
@@ -29,11 +30,20 @@ from .processing import ASSISTANT, END_USER, IMG_END, IMG_PAD, IMG_START, USER
 
 
 class _Job:
-    __slots__ = ("image", "text", "max_tokens", "temperature", "top_p", "future")
+    __slots__ = ("image", "text", "max_tokens", "temperature", "top_p", "top_k", "repetition_penalty", "frequency_penalty",
+                 "presence_penalty", "seed", "future")
 
-    def __init__(self, image, text, max_tokens, temperature, top_p):
+    def __init__(self, image, text, max_tokens, temperature, top_p, top_k=0, repetition_penalty=1.0, frequency_penalty=0.0,
+                 presence_penalty=0.0, seed=None):
         self.image, self.text, self.max_tokens, self.temperature, self.top_p = image, text, max_tokens, temperature, top_p
+        self.top_k, self.repetition_penalty = top_k, repetition_penalty
+        self.frequency_penalty, self.presence_penalty, self.seed = frequency_penalty, presence_penalty, seed
         self.future: Future = Future()
+
+    @property
+    def extended(self) -> bool:
+        """asks for a selection knob beyond (temperature, top_p, seed)"""
+        return self.top_k > 0 or self.repetition_penalty != 1.0 or self.frequency_penalty != 0.0 or self.presence_penalty != 0.0
 
 
 class BatchingWorker:
@@ -76,10 +86,14 @@ class BatchingWorker:
                     self._stop = True
                     break
                 pending.append(job)
-            key = (pending[0].max_tokens, pending[0].temperature, pending[0].top_p)
-            batch = [j for j in pending if (j.max_tokens, j.temperature, j.top_p) == key][: self.max_batch]
+            key = self._group_key(pending[0])
+            batch = [j for j in pending if self._group_key(j) == key][: self.max_batch]
             pending = [j for j in pending if j not in batch]
             self._execute(batch)
+
+    @staticmethod
+    def _group_key(j: _Job):
+        return (j.max_tokens, j.temperature, j.top_p, j.top_k, j.repetition_penalty, j.frequency_penalty, j.presence_penalty, j.seed)
 
     def _execute(self, batch: List[_Job]):
         try:
@@ -87,8 +101,12 @@ class BatchingWorker:
             inputs = self.processor(text=[j.text for j in batch], images=images or None, padding=True, return_tensors="pt")
             j0 = batch[0]
             self.seed += 1
+            extra = {}
+            if j0.extended:                                          # only then: generate() keeps today's path otherwise
+                extra = dict(top_k=j0.top_k, repetition_penalty=j0.repetition_penalty, frequency_penalty=j0.frequency_penalty,
+                             presence_penalty=j0.presence_penalty)
             out = self.model.generate(**inputs, max_new_tokens=j0.max_tokens, do_sample=j0.temperature > 0,
-                                      temperature=j0.temperature, top_p=j0.top_p, seed=self.seed)
+                                      temperature=j0.temperature, top_p=j0.top_p, seed=self.seed if j0.seed is None else j0.seed, **extra)
             new = [o[len(i):] for i, o in zip(inputs.input_ids, out)]
             texts = self.processor.batch_decode(new, skip_special_tokens=True, clean_up_tokenization_spaces=False)
             pad = self.processor.tokenizer.pad_token_id
@@ -125,6 +143,22 @@ class ContinuousWorker(BatchingWorker):
     def _key(j: _Job):
         return (j.temperature, j.top_p)
 
+    @property
+    def per_row(self) -> bool:
+        """the engine selects tokens with per-row parameters: one running set serves every request"""
+        return hasattr(self.model.engine, "set_row_sampling")
+
+    def _row_params(self, job: _Job):
+        """the request's SamplingParams on its slot (None: a plain greedy request, the engine-wide greedy path)"""
+        from .engine import SamplingParams
+        if job.temperature <= 0 and not job.extended:
+            return None
+        if job.seed is None:
+            self.seed += 1
+        return SamplingParams(temperature=job.temperature, top_p=job.top_p, top_k=job.top_k, repetition_penalty=job.repetition_penalty,
+                              frequency_penalty=job.frequency_penalty, presence_penalty=job.presence_penalty,
+                              seed=self.seed if job.seed is None else job.seed)
+
     def _finish(self, job: _Job, prompt_tokens: int, toks, kv_truncated: bool = False):
         eos = set(self.model.config.eos_token_ids)
         toks = [int(t) for t in toks]
@@ -138,6 +172,8 @@ class ContinuousWorker(BatchingWorker):
         from collections import deque
         from .scheduler import ContinuousBatcher, Request
         engine = self.model.engine
+        per_row = self.per_row
+        keyf = (lambda j: None) if per_row else self._key             # per-row parameters: one running set, no drains
         waiting: "deque[_Job]" = deque()
         cb, key = None, None
         while True:
@@ -159,21 +195,25 @@ class ContinuousWorker(BatchingWorker):
             if self._stop and not busy and not waiting:
                 return
             try:
-                if not busy and waiting and (cb is None or key != self._key(waiting[0])):
-                    key = self._key(waiting[0])                      # switch sampling parameters between drained sets only
-                    self.seed += 1
-                    engine.set_sampling(key[0], key[1], self.seed)
+                if not busy and waiting and (cb is None or key != keyf(waiting[0])):
+                    key = keyf(waiting[0])                           # switch sampling parameters between drained sets only
+                    if per_row:
+                        engine.set_sampling(0.0, 1.0, 0)             # plain greedy requests; every other request brings its own
+                    else:
+                        self.seed += 1
+                        engine.set_sampling(key[0], key[1], self.seed)
                     cb = ContinuousBatcher(engine, eos_ids=self.model.config.eos_token_ids, chunk=self.chunk, prefetch=self.look_ahead)
                 # admit the FIFO prefix that shares the running parameters; a different request at the head makes the set drain
                 admitted = 0
-                while waiting and self._key(waiting[0]) == key and len(cb.pending) < 2 * cb.n_slots:
+                while waiting and keyf(waiting[0]) == key and len(cb.pending) < 2 * cb.n_slots:
                     job = waiting.popleft()
                     try:
                         inputs = self.processor(text=[job.text], images=[job.image] if job.image is not None else None,
                                                 padding=True, return_tensors="pt")
                         ids = inputs["input_ids"][0].numpy()
                         cb.submit(Request(ids, inputs.get("pixel_values"), None if "image_grid_thw" not in inputs
-                                          else inputs["image_grid_thw"].numpy(), job.max_tokens, tag=job))
+                                          else inputs["image_grid_thw"].numpy(), job.max_tokens, tag=job,
+                                          sampling=self._row_params(job) if per_row else None))
                         admitted += 1
                     except Exception as e:                           # a bad request fails alone
                         job.future.set_exception(e)
@@ -248,6 +288,31 @@ def _parse_messages(messages, processor=None, allow_remote: bool = False, allow_
     return image, "".join(out) + ASSISTANT
 
 
+def _selection_fields(req: dict) -> dict:
+    """top_k (vLLM: -1 or 0 = off), repetition_penalty, frequency_penalty, presence_penalty, seed of a request, validated
+    (ValueError / TypeError on a value out of range) and normalised the way SamplingParams does it."""
+    def num(name, default, cast=float):
+        v = req.get(name)
+        if v is None:
+            return default
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise TypeError(f"{name} must be a number")
+        if cast is int and float(v) != int(v):
+            raise ValueError(f"{name} must be an integer")
+        return cast(v)
+    from .engine import SamplingParams
+    out = dict(top_k=min(max(0, num("top_k", 0, int)), SamplingParams.TOP_K_MAX), repetition_penalty=num("repetition_penalty", 1.0),
+               frequency_penalty=num("frequency_penalty", 0.0), presence_penalty=num("presence_penalty", 0.0), seed=num("seed", None, int))
+    if not (out["repetition_penalty"] > 0 and out["repetition_penalty"] != float("inf")):
+        raise ValueError("repetition_penalty must be finite and > 0")
+    for name in ("frequency_penalty", "presence_penalty"):
+        if not -2.0 <= out[name] <= 2.0:
+            raise ValueError(f"{name} must be in [-2, 2]")
+    if out["seed"] is not None:
+        out["seed"] &= 2 ** 64 - 1
+    return out
+
+
 def create_app(model, processor, model_name: str = "model", max_batch: int = 8, max_wait_ms: float = 5.0, continuous: Optional[bool] = None,
                allow_remote_images: bool = False, allow_local_images: bool = False, look_ahead: Optional[int] = None):
     from fastapi import FastAPI, HTTPException
@@ -282,7 +347,16 @@ def create_app(model, processor, model_name: str = "model", max_batch: int = 8, 
         max_tokens = int(req.get("max_completion_tokens") or req.get("max_tokens") or 16384)
         temperature = float(req.get("temperature", 1.0) if req.get("temperature") is not None else 1.0)
         top_p = float(req.get("top_p", 1.0) if req.get("top_p") is not None else 1.0)
-        fut = worker.submit(_Job(image, text, max_tokens, max(0.0, temperature), min(max(top_p, 1e-6), 1.0)))
+        try:
+            job = _Job(image, text, max_tokens, max(0.0, temperature), min(max(top_p, 1e-6), 1.0), **_selection_fields(req))
+            from .engine import SamplingParams       # the values exactly as the engine will be given them (fp32, int32)
+            SamplingParams(temperature=job.temperature, top_p=job.top_p, top_k=job.top_k, repetition_penalty=job.repetition_penalty,
+                           frequency_penalty=job.frequency_penalty, presence_penalty=job.presence_penalty, seed=job.seed or 0)
+        except (TypeError, ValueError) as e:
+            raise HTTPException(400, f"bad sampling parameters: {e}")
+        if job.extended and isinstance(worker, ContinuousWorker) and not worker.per_row:
+            raise HTTPException(400, "top_k, repetition_penalty, frequency_penalty and presence_penalty need an engine with per-row selection")
+        fut = worker.submit(job)
         try:
             res = await run_in_threadpool(fut.result)
         except Exception as e:

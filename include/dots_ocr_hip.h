@@ -167,6 +167,30 @@ int dots_preprocess_image(DotsEngine* e, const uint8_t* rgb, int rgb_on_device, 
  * parameters the reference passes to its vLLM backend (parser.py:27-28, model/inference.py:38-43).  Reproducible
  * from `seed` (counter-based: seed, batch slot, position). */
 int dots_set_sampling(DotsEngine* e, float temperature, float top_p, uint64_t seed);
+
+/* Per-row token selection.  One row = a slot (continuous batching) or sequence b of a static batch.
+ *   temperature        >= 0; 0 = greedy (arg max of the penalised logits, the lowest index wins a tie)
+ *   top_p              (0, 1]: nucleus over the softmax of the tokens top_k keeps
+ *   top_k              0 = off, else keep every token whose tempered logit is >= the k-th largest (ties kept)
+ *   repetition_penalty > 0, 1 = off: l' = l > 0 ? l / r : l * r for every token in the row's prompt or output (HF, vLLM)
+ *   frequency_penalty, presence_penalty  [-2, 2]: l' -= f * c_t + p * (c_t > 0), c_t = count of t in the row's output (OpenAI)
+ *   seed               the draw of a row's n-th generated token (the prefill's token is n = 0) uses u = hash(seed, n): neither the
+ *                      row index nor the batch enters it
+ * Penalties are applied first (repetition, then frequency / presence), never written over the logits dots_get_logits returns. */
+typedef struct DotsSamplingParams {
+    float temperature, top_p;
+    int32_t top_k;
+    float repetition_penalty, frequency_penalty, presence_penalty;
+    uint64_t seed;
+} DotsSamplingParams;
+/* Give row `row` its own parameters (p == NULL: back to the dots_set_sampling setting), in stream order: they apply from the next token
+ * the engine selects, the first token of a following dots_prefill / dots_slots_prefill included.  Captured decode graphs are kept.
+ * dots_slot_release / dots_slots_reset clear the row.  DOTS_E_INVALID on a value out of range.
+ * Penalty state is exact for a row that carries its penalty from before its prefill (set the row, then prefill it).  Limit: for a penalty
+ * switched on while the row is already running, the counts c_t hold only the tokens selected after the switch, and the prompt-presence
+ * bits exist only if some row of this engine had used a penalty before the row's prefill (the state is allocated on first use and
+ * written by each prefill from then on); the prompt is not kept on the device to rebuild them. */
+int dots_set_row_sampling(DotsEngine* e, int row, const DotsSamplingParams* p);
 /* Launch plan of the decode step (results are bit-identical under either plan).  0 (default) = chosen by where the step runs: the
  * whole-chip plan (qkv / o_proj / down_proj as 8-row half tiles: 256 / 192 / 192 workgroups; one gate|up workgroup per tile pair), or —
  * while the step is replayed on the decode CU partition beside a prefetched vision tower (dots_vit_prefetch) — the PARTITION plan: the
@@ -329,6 +353,16 @@ int dots_op_dec_gateup(DotsEngine* e, const void* h_dev, const void* ln_w_dev, c
                        int B, int H, int I, float eps, int fp8);
 int dots_op_dec_lmhead(DotsEngine* e, const void* h_dev, const void* ln_w_dev, const void* w_dev, void* logits_out_dev, int B, int H, int V,
                        float eps, int fp8);
+/* The per-row selection stage on caller logits: logits_dev fp32 [B, V] (row stride V), params_host [B].  Row b's history hist_dev int32
+ * [B, hist_stride] holds its prompt (n_prompt_dev[b] ids) followed by its generated tokens, hist_lens_dev[b] ids in all; the stage builds
+ * the penalty state the decode loop keeps from it, draws with n = hist_lens - n_prompt, and writes the chosen ids to out_tokens_dev [B]. */
+int dots_op_select_tokens(DotsEngine* e, const float* logits_dev, int B, int V, const DotsSamplingParams* params_host, const int32_t* hist_dev,
+                          const int32_t* hist_lens_dev, int hist_stride, const int32_t* n_prompt_dev, int32_t* out_tokens_dev);
+/* Timing of the selection stage on the same inputs (tools/sampling_bench.py): mode 0 = the arg max pair, 1 = the engine-wide sampler
+ * (params_host[0].temperature / top_p / seed for every row), 2 = the per-row stage; iters replays between HIP events after a warm-up,
+ * every row marked finished so that nothing is appended.  *ms_out = mean milliseconds per replay. */
+int dots_bench_select_tokens(DotsEngine* e, const float* logits_dev, int B, int V, const DotsSamplingParams* params_host, const int32_t* hist_dev,
+                             const int32_t* hist_lens_dev, int hist_stride, const int32_t* n_prompt_dev, int mode, int iters, float* ms_out);
 
 /* MFMA fragment-layout / LDS-DMA probe (csrc/probe_mfma.hip; tests/test_mfma_layout.py). */
 int dots_probe_mfma(int which, const void* A, const void* Bt, void* D, void* stream);
