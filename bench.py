@@ -19,6 +19,11 @@ per-output-channel scale) weights; B = 1.  --fp8 0/1 overrides the weight format
 
 Prints ONE JSON line on rank 0 (see README/DESIGN for the field contract).  --dump-outputs DIR also writes the last timed step's
 token ids as DIR/*.npy (inputs and weights are seeded: the same arguments give the same inputs on every run).
+
+A plain run does only what the headline needs: set-up, the pipeline fill, the warm-up and timed steps, the dump, the line.  --full adds
+everything else, as before: the strictly sequential reference batches (bitwise parity of every pipelined step, roofline_*_sequential,
+throughput_shapes, targets), the rooflines, the decode step replayed alone, mixed64's single-sequence parity, the H2D timing, and on the
+default a4 run the other_configs legs and the CPU baseline (--no-other-configs / --no-cpu-baseline skip those two).
 """
 from __future__ import annotations
 
@@ -53,6 +58,9 @@ def parse():
     ap.add_argument("--max-new-tokens", type=int, default=1024)
     ap.add_argument("--workload", default="a4", choices=["a4", "highres", "tiny", "mixed64", "svg"])
     ap.add_argument("--fp8", type=int, default=None, help="1: e4m3 per-channel weights (DotsConfig.fp8_weights); default: on for --workload svg only")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the reference batches and parity checks, the rooflines and the extra measurements, and on the default a4 run "
+                         "the other_configs legs and the CPU baseline (a plain run times the steps and prints the headline only)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-overlap", action="store_true",
                     help="strictly sequential batches (ViT -> prefill -> decode); default: the tower of batch k+1 runs on a CU-masked side stream "
@@ -71,7 +79,7 @@ def parse():
                          "first) as their slots drain, instead of the static cost shard — for jobs much larger than the ranks' slots, where a static shard "
                          "leaves the ranks that drew short outputs idle at the end (SURVEY §8(e)).  Every rank keeps all pages' pixels resident.")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="default a4 run on one GPU: skip the short highres / mixed64 / svg-fp8 legs whose lines are embedded under `other_configs`")
+                    help="default a4 run on one GPU with --full: skip the short highres / mixed64 / svg-fp8 legs whose lines are embedded under `other_configs`")
     ap.add_argument("--page-sets", type=int, default=None,
                     help="a4 / highres / svg: distinct page sets the steps rotate through (default 2 with the pipelined step, else 1): step k processes set k mod n, "
                          "all sets resident in HBM, each set's tokens checked against its own sequential batch")
@@ -189,10 +197,10 @@ def bench_messages(workload="a4"):
 
 
 def other_config_legs():
-    """BASELINE configs[2] (highres), [3] (mixed64 on this one GPU) and [4] (svg, fp8) as short legs of the DEFAULT run, so that the driver's own record
-    holds them (VERDICT r5 missing #3: they existed only as builder-run files under profiles/).  Each leg is this script in a fresh process (its own
-    engine, its own parity check — a leg that is not parity-clean exits non-zero and is reported as failed); the headline keys of the a4 line are
-    untouched.  About 60 s in all."""
+    """BASELINE configs[2] (highres), [3] (mixed64 on this one GPU) and [4] (svg, fp8) as short legs of the default a4 run with --full, so that its
+    record holds them (VERDICT r5 missing #3: they existed only as builder-run files under profiles/).  Each leg is this script with --full in a fresh
+    process (its own engine, its own parity check — a leg that is not parity-clean exits non-zero and is reported as failed); the headline keys of
+    the a4 line are untouched.  About 70 s in all."""
     import subprocess
     legs = [("highres", ["--workload", "highres", "--batch", "4", "--steps", "8", "--warmup", "4"]),      # configs[2]: batch = 4      # (the adaptive tower tail settles within the warm-up steps: 3 / 1 measured 11.1 pages/s against 14.4 at 5 / 2)
             ("mixed64", ["--workload", "mixed64", "--steps", "1", "--warmup", "0"]),
@@ -206,7 +214,8 @@ def other_config_legs():
             # a clean environment for the leg: the decode partition this process chose for ITS workload (setdefault below) must not become the leg's
             # (round 6: the highres leg inherited a4's 64 decode CUs and reported 11.4 pages/s instead of its own default's 13.8)
             env = {k: v for k, v in os.environ.items() if not (k == "DOTS_OCR_OVERLAP_DEC_CUS" and not _USER_SET_DEC_CUS)}
-            p = subprocess.run([sys.executable, str(Path(__file__).resolve()), *argv, "--no-cpu-baseline", "--no-other-configs"], capture_output=True, text=True, timeout=420, env=env)
+            p = subprocess.run([sys.executable, str(Path(__file__).resolve()), *argv, "--full", "--no-cpu-baseline", "--no-other-configs"],
+                               capture_output=True, text=True, timeout=420, env=env)
             line = [ln for ln in p.stdout.splitlines() if ln.startswith('{"metric"')]
             if p.returncode != 0 or not line:
                 out[name] = {"failed": True, "rc": p.returncode, "stderr_tail": p.stderr[-600:]}
@@ -586,14 +595,16 @@ def main():
     seq_out = None                                   # tokens of the strictly sequential batch: the pipelined steps decode the SAME pages
     pipelined_outs = []                              # (out, out_lens) of every pipelined step, compared after the timed region
     if overlap:
-        # one strictly sequential batch first: warms everything up AND gives the per-kernel whole-chip timings of this very run
-        # (reported beside the timed region's, where the tower and the decode loop share the chip); then the pipeline is primed
-        o0, l0, _, seq_prompts = step(sid=0)
-        seq_out = [(o0.copy(), l0.copy())]
-        seq_stats = eng.stats()
-        for s_ in range(1, n_sets):                  # the other page sets' sequential reference tokens (untimed)
-            o_, l_, _, _ = step(sid=s_)
-            seq_out.append((o_.copy(), l_.copy()))
+        if a.full:
+            # one strictly sequential batch per page set first (untimed): the reference tokens of the parity check after the timed region
+            # AND the per-kernel whole-chip timings of this very run (reported beside the timed region's, where the tower and the decode
+            # loop share the chip); then the pipeline is primed
+            o0, l0, _, seq_prompts = step(sid=0)
+            seq_out = [(o0.copy(), l0.copy())]
+            seq_stats = eng.stats()
+            for s_ in range(1, n_sets):
+                o_, l_, _, _ = step(sid=s_)
+                seq_out.append((o_.copy(), l_.copy()))
         if deep:
             eng.set_eos([])
             eng.slots_reset()                        # sequence-slot mode: every slot free, every KV page in the pool (drops any pending prefetch)
@@ -621,7 +632,7 @@ def main():
     phase = {"vit_ms": 0.0, "prefill_ms": 0.0, "decode_ms": 0.0, "vit_attn_ms": 0.0}
     last = None
     deep_bytes_per_step = 0.0
-    if deep:
+    if deep and a.full:
         # a static batch's decode_bytes = steps x W + kv_tok x sum over rows and steps of (context + 1): solve for W (every weight byte once per step)
         kv_tok = cfg.num_hidden_layers * cfg.num_key_value_heads * 128 * 2 * 2
         L0, st_n = len(seq_prompts[0]), seq_stats["decode_steps"]
@@ -640,7 +651,8 @@ def main():
             st["decode_ms"] = deep_state["last_decode_ms"]
             st["decode_steps"] = half_steps
             st["decode_bytes"] = deep_bytes_per_step
-            st["prefill_flops"] = seq_stats["prefill_flops"]
+            if a.full:
+                st["prefill_flops"] = seq_stats["prefill_flops"]
         for k in phase:
             phase[k] += st[k]
         last = st
@@ -664,7 +676,7 @@ def main():
     # ---- the decode step the timed region replays, ALONE on the chip (outside the timed region, rank 0): one more batch is admitted with no
     # look-ahead tower behind it, so every slot group holds rows; 64 graph replays on the whole chip, host-synchronised on both sides
     dec_alone_rows = None
-    if deep and not sliced and not mixed and rank == 0 and os.environ.get("DOTS_BENCH_DECODE_ALONE", "1") != "0":
+    if a.full and deep and not sliced and not mixed and rank == 0 and os.environ.get("DOTS_BENCH_DECODE_ALONE", "1") != "0":
         try:                                         # an optional extra: whatever goes wrong here must not cost the run its line
             k_ = deep_state["k"]
             eng.vit_take()
@@ -759,47 +771,48 @@ def main():
         if mixed:
             from collections import Counter
             mm = mixed_meter
-            kv_tok = cfg.num_hidden_layers * cfg.num_key_value_heads * 128 * 2 * 2
-            Wb = 2.0 * (sum(int(np.prod(v_.shape)) for k_, v_ in sd.items() if k_.startswith("model.layers.") and v_.dim() == 2) + cfg.vocab_size * cfg.hidden_size)   # 3 087 138 816 B
-            if fp8:
-                Wb /= 2.0
-            # algorithmic decode bytes of the timed region: every weight byte once per decode step + the KV read of every row and step
-            kv_bytes = sum(kv_tok * sum(L_ + t_ for t_ in range(1, n_)) for job in mm["requests"] for (L_, n_) in job)
-            dec_bytes = mm["decode_steps"] * Wb + kv_bytes
-            attn_tf = mm["attn_flops"] / (mm["attn_ms"] / 1e3) / 1e12 if mm["attn_ms"] > 0 else 0.0
-            dec_gbs = dec_bytes / (mm["decode_ms"] / 1e3) / 1e9 if mm["decode_ms"] > 0 else 0.0
-            dec_cus_m = int(os.environ.get("DOTS_OCR_OVERLAP_DEC_CUS", "64")) // 8 * 8
-            res["roofline"] = {"bound": "mfma", "kernel": "flash_attn64_kernel (ViT bidirectional var-len attention) over the timed region's towers: ragged packed batches of the six page sizes",
-                               "achieved": attn_tf, "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": attn_tf / PEAK_BF16_TFLOPS, "traffic": None,
-                               "algorithmic_flops": mm["attn_flops"], "launches": mm["attn_launches"], "towers": mm["towers"],
-                               "sum_of_launch_ms": mm["attn_ms"],
-                               "note": f"HIP-event sums on the stream each tower ran on; look-ahead towers run on the {256 - dec_cus_m}-CU partition beside the decode loop "
-                                       f"(frac is against the WHOLE chip's peak: x 256 / {256 - dec_cus_m} for the partition's), the first group's tower on the whole chip"}
-            res["roofline_decode"] = {"bound": "hbm", "achieved": dec_gbs, "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": dec_gbs / PEAK_HBM_GBS, "traffic": None,
-                                      "decode_steps": mm["decode_steps"], "algorithmic_bytes": dec_bytes, "decode_wall_ms": mm["decode_ms"],
-                                      "note": f"wall time from each slots_decode chunk to the poll after it (host-synchronised), up to {slots} rows per step, on the {dec_cus_m}-CU "
-                                              "partition while a look-ahead tower runs and on the whole chip otherwise"}
             res["phase_ms_per_step"] = {"vit_ms": mm["vit_ms"] / K, "vit_attn_ms": mm["attn_ms"] / K, "decode_ms": mm["decode_ms"] / K, **{k: val / K for k, val in host_ms.items()}}
-            # parity of what was timed: 8 of this rank's pages (every size class first, then the front of the list) decoded again ALONE through the
-            # static single-sequence generate — the continuous batch with look-ahead towers must have produced the same tokens, bit for bit
-            seen, sample = set(), []
-            for i_, sz_ in enumerate(sizes):
-                if sz_ not in seen:
-                    seen.add(sz_); sample.append(i_)
-            sample = (sample + [i_ for i_ in range(len(sizes)) if i_ not in sample])[:8]
-            eng.vit_forward, eng.vit_prefetch, eng.slots_decode, eng.slots_poll = _vf, _vp, _sd, _sp
-            bad = []
-            for i_ in sample:
-                r_ = mm["last_reqs"][i_]
-                single, sl = eng.generate(r_.input_ids, np.asarray([len(r_.input_ids)], np.int32), r_.pixel_values.data_ptr(), np.asarray(r_.grid_thw, np.int64),
-                                          a.max_new_tokens, (), pixel_on_device=True)
-                if not np.array_equal(single[0, :sl[0]], mm["last_outs"][i_]):
-                    bad.append(my_pages[i_])
-            if bad:
-                raise SystemExit(f"bench.py: mixed64: pages {bad} decoded differently in the continuous batch than alone: the timed configuration is NOT parity-clean")
-            res["parity_vs_single_sequence"] = "bitwise"
-            res["pages_checked"] = [int(my_pages[i_]) for i_ in sample]
-            res["tokens_per_page_checked"] = a.max_new_tokens
+            if a.full:
+                kv_tok = cfg.num_hidden_layers * cfg.num_key_value_heads * 128 * 2 * 2
+                Wb = 2.0 * (sum(int(np.prod(v_.shape)) for k_, v_ in sd.items() if k_.startswith("model.layers.") and v_.dim() == 2) + cfg.vocab_size * cfg.hidden_size)   # 3 087 138 816 B
+                if fp8:
+                    Wb /= 2.0
+                # algorithmic decode bytes of the timed region: every weight byte once per decode step + the KV read of every row and step
+                kv_bytes = sum(kv_tok * sum(L_ + t_ for t_ in range(1, n_)) for job in mm["requests"] for (L_, n_) in job)
+                dec_bytes = mm["decode_steps"] * Wb + kv_bytes
+                attn_tf = mm["attn_flops"] / (mm["attn_ms"] / 1e3) / 1e12 if mm["attn_ms"] > 0 else 0.0
+                dec_gbs = dec_bytes / (mm["decode_ms"] / 1e3) / 1e9 if mm["decode_ms"] > 0 else 0.0
+                dec_cus_m = int(os.environ.get("DOTS_OCR_OVERLAP_DEC_CUS", "64")) // 8 * 8
+                res["roofline"] = {"bound": "mfma", "kernel": "flash_attn64_kernel (ViT bidirectional var-len attention) over the timed region's towers: ragged packed batches of the six page sizes",
+                                   "achieved": attn_tf, "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": attn_tf / PEAK_BF16_TFLOPS, "traffic": None,
+                                   "algorithmic_flops": mm["attn_flops"], "launches": mm["attn_launches"], "towers": mm["towers"],
+                                   "sum_of_launch_ms": mm["attn_ms"],
+                                   "note": f"HIP-event sums on the stream each tower ran on; look-ahead towers run on the {256 - dec_cus_m}-CU partition beside the decode loop "
+                                           f"(frac is against the WHOLE chip's peak: x 256 / {256 - dec_cus_m} for the partition's), the first group's tower on the whole chip"}
+                res["roofline_decode"] = {"bound": "hbm", "achieved": dec_gbs, "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": dec_gbs / PEAK_HBM_GBS, "traffic": None,
+                                          "decode_steps": mm["decode_steps"], "algorithmic_bytes": dec_bytes, "decode_wall_ms": mm["decode_ms"],
+                                          "note": f"wall time from each slots_decode chunk to the poll after it (host-synchronised), up to {slots} rows per step, on the {dec_cus_m}-CU "
+                                                  "partition while a look-ahead tower runs and on the whole chip otherwise"}
+                # parity of what was timed: 8 of this rank's pages (every size class first, then the front of the list) decoded again ALONE through the
+                # static single-sequence generate — the continuous batch with look-ahead towers must have produced the same tokens, bit for bit
+                seen, sample = set(), []
+                for i_, sz_ in enumerate(sizes):
+                    if sz_ not in seen:
+                        seen.add(sz_); sample.append(i_)
+                sample = (sample + [i_ for i_ in range(len(sizes)) if i_ not in sample])[:8]
+                eng.vit_forward, eng.vit_prefetch, eng.slots_decode, eng.slots_poll = _vf, _vp, _sd, _sp
+                bad = []
+                for i_ in sample:
+                    r_ = mm["last_reqs"][i_]
+                    single, sl = eng.generate(r_.input_ids, np.asarray([len(r_.input_ids)], np.int32), r_.pixel_values.data_ptr(), np.asarray(r_.grid_thw, np.int64),
+                                              a.max_new_tokens, (), pixel_on_device=True)
+                    if not np.array_equal(single[0, :sl[0]], mm["last_outs"][i_]):
+                        bad.append(my_pages[i_])
+                if bad:
+                    raise SystemExit(f"bench.py: mixed64: pages {bad} decoded differently in the continuous batch than alone: the timed configuration is NOT parity-clean")
+                res["parity_vs_single_sequence"] = "bitwise"
+                res["pages_checked"] = [int(my_pages[i_]) for i_ in sample]
+                res["tokens_per_page_checked"] = a.max_new_tokens
             res["config"] = {"workload": "mixed64: 64 pages " + ", ".join(f"{n}x {w}x{h}" for (w, h), n in sorted(Counter(sizes_all).items())) +
                                          f"; cost-sharded (LPT) over {world} rank(s), continuous batching over {slots} slots per rank, "
                                          f"max_new_tokens={a.max_new_tokens}, EOS disabled",
@@ -865,11 +878,12 @@ def main():
                                               if rd["traffic"] else "not measured for the %d-row step (PMC traffic at B = 8: roofline_decode_sequential.traffic)" % rif)
                 return r, rv, rd
             dec_cus = int(os.environ.get("DOTS_OCR_OVERLAP_DEC_CUS", "128")) // 8 * 8
-            cv, cd = (256 - dec_cus, dec_cus) if overlap and not sliced else (256, 256)
-            res["roofline"], res["roofline_vit"], res["roofline_decode"] = rooflines(phase, K, last, cv, cd)
+            if a.full:
+                cv, cd = (256 - dec_cus, dec_cus) if overlap and not sliced else (256, 256)
+                res["roofline"], res["roofline_vit"], res["roofline_decode"] = rooflines(phase, K, last, cv, cd)
             res["decode_tok_s"] = int(out_lens.sum()) * K / (phase["decode_ms"] / 1e3) if phase["decode_ms"] > 0 else None
             res["phase_ms_per_step"] = {**{k: val / K for k, val in phase.items()}, **{k: val / K for k, val in host_ms.items()}}
-            if overlap:
+            if a.full and overlap:
                 res["overlap"] = {
                     "mode": "software-pipelined batches: the vision tower of batch k+1 (stream masked to CUs %d-255, an equal share of every XCD) runs "
                             "while batch k is prefilled and decoded (decode graph on the stream masked to CUs 0-%d until the tower is done, whole chip "
@@ -917,26 +931,27 @@ def main():
                     "one_batch_in_flight": one,
                     "sequential_batch": {"pages_per_s": n_job_pages / world / (seq_stats["total_ms"] / 1e3) * world, "page_latency_s": seq_stats["total_ms"] / 1e3,
                                          "source": "the strictly sequential batch this run starts with (tower -> prefill -> 1023 decode steps on the whole chip, nothing overlapped)"}}
-            # north_star targets, stated as what the evidence supports: the kernels ALONE on the chip (the sequential batch of this run) and
-            # what the chip sustains over the whole timed step
-            vit_alone = res.get("roofline_vit_sequential", res["roofline_vit"])["frac"]
-            dec_alone = res.get("roofline_decode_sequential", res["roofline_decode"])["frac"]
-            step_s = dt / K
-            res["targets"] = {"vit_mfma_frac_alone": vit_alone, "decode_hbm_frac_alone": dec_alone,
-                              "step_mfma_frac": (last["vit_flops"] + last["prefill_flops"]) / step_s / 1e12 / PEAK_BF16_TFLOPS,
-                              "step_hbm_frac": last["decode_bytes"] / step_s / 1e9 / PEAK_HBM_GBS,
-                              "north_star": {"vit_mfma_frac": 0.40, "decode_hbm_frac": 0.50},
-                              "met": {"vit_mfma": bool(vit_alone >= 0.40), "decode_hbm": bool(dec_alone >= 0.50)}}
-            if dec_alone_rows is not None:          # the timed region's own decode step (all slot groups full) alone on the chip, measured after the timed region
-                res["roofline_decode_alone_rows_in_flight"] = dec_alone_rows
-                res["targets"]["decode_hbm_frac_alone_rows_in_flight"] = dec_alone_rows["frac"]
-                res["targets"]["decode_hbm_basis"] = ("decode_hbm_frac_alone / met.decode_hbm: B = %d (the sequential batch); decode_hbm_frac_alone_rows_in_flight: the "
-                                                      "%d-row step the timed region replays, alone on the chip" % (B, dec_alone_rows["rows"]))
-                res["targets"]["met"]["decode_hbm_rows_in_flight"] = bool(dec_alone_rows["frac"] >= 0.50)
-            if a.workload == "svg":                 # 4096 decode steps at B = 1 dominate this configuration: its roofline is the HBM one
-                res["roofline_vit_attn"] = res["roofline"]
-                res["roofline"] = {**res["roofline_decode"], "kernel": "one decode step (dec_qkv / decode_attn / combine / dec_proj / dec_gateup x 28 + dec_lmhead)"}
-        if not mixed:
+            if a.full:
+                # north_star targets, stated as what the evidence supports: the kernels ALONE on the chip (the sequential batch of this run) and
+                # what the chip sustains over the whole timed step
+                vit_alone = res.get("roofline_vit_sequential", res["roofline_vit"])["frac"]
+                dec_alone = res.get("roofline_decode_sequential", res["roofline_decode"])["frac"]
+                step_s = dt / K
+                res["targets"] = {"vit_mfma_frac_alone": vit_alone, "decode_hbm_frac_alone": dec_alone,
+                                  "step_mfma_frac": (last["vit_flops"] + last["prefill_flops"]) / step_s / 1e12 / PEAK_BF16_TFLOPS,
+                                  "step_hbm_frac": last["decode_bytes"] / step_s / 1e9 / PEAK_HBM_GBS,
+                                  "north_star": {"vit_mfma_frac": 0.40, "decode_hbm_frac": 0.50},
+                                  "met": {"vit_mfma": bool(vit_alone >= 0.40), "decode_hbm": bool(dec_alone >= 0.50)}}
+                if dec_alone_rows is not None:          # the timed region's own decode step (all slot groups full) alone on the chip, measured after the timed region
+                    res["roofline_decode_alone_rows_in_flight"] = dec_alone_rows
+                    res["targets"]["decode_hbm_frac_alone_rows_in_flight"] = dec_alone_rows["frac"]
+                    res["targets"]["decode_hbm_basis"] = ("decode_hbm_frac_alone / met.decode_hbm: B = %d (the sequential batch); decode_hbm_frac_alone_rows_in_flight: the "
+                                                          "%d-row step the timed region replays, alone on the chip" % (B, dec_alone_rows["rows"]))
+                    res["targets"]["met"]["decode_hbm_rows_in_flight"] = bool(dec_alone_rows["frac"] >= 0.50)
+                if a.workload == "svg":                 # 4096 decode steps at B = 1 dominate this configuration: its roofline is the HBM one
+                    res["roofline_vit_attn"] = res["roofline"]
+                    res["roofline"] = {**res["roofline_decode"], "kernel": "one decode step (dec_qkv / decode_attn / combine / dec_proj / dec_gateup x 28 + dec_lmhead)"}
+        if a.full and not mixed:
             # the reference's inputs.to("cuda") (dots_ocr/parser.py:107): `value` is measured with the uint8 pages resident in HBM (the contract of this
             # bench); the upload of one step's pages is timed here, outside the timed region, and the PCIe-inclusive rate stated beside it
             h2d = []
@@ -951,9 +966,9 @@ def main():
                           "note": "uint8 pixels of one step's pages, pageable host memory -> HBM, blocking copies, best of 3, NOT inside the timed region and not hidden "
                                   "behind compute in the PCIe-inclusive figure (worst case: the pipeline could upload batch k+1 while batch k runs)"}
         eng.close()
-        if world == 1 and a.workload == "a4" and not a.no_other_configs and B == 8 and a.max_new_tokens == 1024 and not a.no_overlap and os.environ.get("DOTS_BENCH_OTHER", "1") != "0":
+        if a.full and world == 1 and a.workload == "a4" and not a.no_other_configs and B == 8 and a.max_new_tokens == 1024 and not a.no_overlap and os.environ.get("DOTS_BENCH_OTHER", "1") != "0":
             res["other_configs"] = other_config_legs()
-        if world == 1 and not a.no_cpu_baseline and a.workload == "a4":
+        if a.full and world == 1 and not a.no_cpu_baseline and a.workload == "a4":
             cores = min(os.cpu_count() or 1, 64)
             res["cpu_baseline"] = cpu_baseline(cfg, sd, cores, pages[0], prompts[0], a.max_new_tokens)
         print(json.dumps(res), flush=True)

@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp; ulimit -c 0
 R=$GRAFT_REPO_ROOT; cd $R; mkdir -p $R/gpurun_out/prof
 for mode in seq ovl; do
   rm -rf $R/gpurun_out/prof/*
-  if [ $mode = seq ]; then FL="--no-overlap --max-new-tokens 64"; else FL="--max-new-tokens 128"; fi
+  if [ $mode = seq ]; then FL="--full --no-overlap --max-new-tokens 64"; else FL="--full --max-new-tokens 128"; fi
   timeout 400 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/prof -o r03 -- python bench.py --steps 1 --warmup 0 --no-cpu-baseline $FL > $R/gpurun_out/prof/bench.log 2>&1; echo rc=$?
   grep '^{"metric"' $R/gpurun_out/prof/bench.log | tail -1 > $R/gpurun_out/r03_a4_b8_${mode}_bench_line.json
   db=$(find $R/gpurun_out/prof -name "*.db" | head -1); echo $db
