@@ -206,6 +206,13 @@ struct DotsEngine {
     float* pen_logits = nullptr;
     int row_own[DOTS_MAX_BATCH] = {0};
     int n_own = 0;                         // rows with their own parameters: > 0 switches the step to the per-row stage
+    // log-probabilities (dots_set_row_logprobs): top_n per row (-1 = off) on the device and its host mirror; the outputs
+    // ([max_batch][max_seq_len] positions) and the stage's scratch are allocated by the first row switched on
+    int32_t* d_row_lp = nullptr;
+    float *lp_tok = nullptr, *lp_top = nullptr, *lp_ms = nullptr, *lp_pv = nullptr;
+    int32_t *lp_ids = nullptr, *lp_pi = nullptr, *lp_pos = nullptr;
+    int row_lp[DOTS_MAX_BATCH];
+    int n_lp = 0;                          // rows with logprobs on: > 0 adds the two logprob kernels around the selection stage
     int out_cap = 0;                       // row stride of out_ids for the current generation
     bf16_t *d_h = nullptr, *d_q = nullptr, *d_att = nullptr, *d_act = nullptr, *d_xn = nullptr;      // d_xn: normalised rows of batches above 32 rows (decode_b64.hip)
     float* d_part_h = nullptr;                     // [DEC_KSPLIT_PARTS][DOTS_MAX_BATCH][hidden] fp32: the K-quarter sums of a projection above 32 rows (decode_b64.hip)
@@ -228,8 +235,9 @@ struct DotsEngine {
     const int32_t* sel_now = nullptr;      // selection mask of the next select_tokens() call
     // captured decode steps, keyed by everything the capture bakes in: rows, KV splits, static batch (out_cap = row stride of
     // the output buffer) or slot mode (out_cap = 0), number of EOS ids, whether any row carries its own parameters (rowp: the per-row
-    // selection stage); engine-wide sampling changes drop the cache (dots_set_sampling), per-row ones live in device memory
-    struct StepGraph { int rows, splits, out_cap, n_eos, part, rowp; hipGraph_t graph; hipGraphExec_t exec; };
+    // selection stage), whether any row returns logprobs (lp); engine-wide sampling changes drop the cache (dots_set_sampling), per-row
+    // ones live in device memory
+    struct StepGraph { int rows, splits, out_cap, n_eos, part, rowp, lp; hipGraph_t graph; hipGraphExec_t exec; };
     std::vector<StepGraph> step_graphs;
     std::vector<int> h_prompt_lens;
     int steps_done = 0;
@@ -852,6 +860,11 @@ int select_tokens(DotsEngine* e, int advance) {
     st.eos_ids = e->eos_ids; st.n_eos = e->n_eos; st.advance_ctx = advance;
     if (e->slot_mode) { st.sel = e->sel_now; st.max_len = e->d_max_len; st.out_stride = c.max_seq_len; st.cap = c.max_seq_len; }
     else { st.sel = nullptr; st.max_len = nullptr; st.out_stride = e->out_cap; st.cap = e->out_cap; }
+    // logprobs: the partial kernel reads the logits and snapshots finished / out_lens before selection commits, the final kernel
+    // reads the committed token after it
+    const LogprobState ls{e->d_row_lp, st.sel, e->finished, e->out_lens, e->cur_tokens, e->lp_ms, e->lp_pv, e->lp_pi, e->lp_pos,
+                          e->lp_tok, e->lp_ids, e->lp_top, c.max_seq_len};
+    if (e->n_lp > 0) CK(launch_logprob_partial(e->stream, e->d_logits, c.vocab_size, c.vocab_size, e->B_sel, ls));
     if (e->n_own > 0) {          // per-row stage for the rows with their own parameters (+ the greedy rows that follow the engine)
         const RowSel rs{e->d_rowp, e->d_row_own, e->pen_cnt, e->pen_seen, e->pen_logits, e->d_row_thr, e->temperature > 0.f ? 0 : 1};
         CK(launch_select_rows(e->stream, e->d_logits, c.vocab_size, c.vocab_size, e->B_sel, rs, e->am_val, e->am_idx, st));
@@ -861,6 +874,7 @@ int select_tokens(DotsEngine* e, int advance) {
         CK(launch_sample_step(e->stream, e->d_logits, c.vocab_size, c.vocab_size, e->B_sel, e->temperature, e->top_p, e->seed, st));
     else
         CK(launch_argmax_step(e->stream, e->d_logits, c.vocab_size, c.vocab_size, e->B_sel, e->am_val, e->am_idx, st));
+    if (e->n_lp > 0) CK(launch_logprob_final(e->stream, e->d_logits, c.vocab_size, c.vocab_size, e->B_sel, ls));
     return DOTS_OK;
 }
 
@@ -907,6 +921,44 @@ int check_row_params(DotsEngine* e, const DotsSamplingParams& p, RowParams* out)
     if (!(p.frequency_penalty >= -2.f && p.frequency_penalty <= 2.f)) return e->fail(DOTS_E_INVALID, "frequency_penalty must be in [-2, 2]");
     if (!(p.presence_penalty >= -2.f && p.presence_penalty <= 2.f)) return e->fail(DOTS_E_INVALID, "presence_penalty must be in [-2, 2]");
     *out = RowParams{p.temperature, p.top_p > 1.f ? 1.f : p.top_p, p.top_k, p.repetition_penalty, p.frequency_penalty, p.presence_penalty, p.seed};
+    return DOTS_OK;
+}
+
+// logprob outputs + scratch, allocated by the first row switched on; every output byte starts as 0xFF (NaN / -1)
+int ensure_lp_state(DotsEngine* e) {
+    if (e->lp_tok) return DOTS_OK;
+    const size_t rows = e->cfg.max_batch, pos = (size_t)rows * e->cfg.max_seq_len, K = DOTS_MAX_TOP_LOGPROBS;
+    hipStream_t s = e->stream;
+    CK(e->alloc(&e->lp_ms, rows * LP_CHUNKS * 2));
+    CK(e->alloc(&e->lp_pv, rows * LP_CHUNKS * K));
+    CK(e->alloc(&e->lp_pi, rows * LP_CHUNKS * K));
+    CK(e->alloc(&e->lp_pos, rows));
+    CK(e->alloc(&e->lp_ids, pos * K));
+    CK(e->alloc(&e->lp_top, pos * K));
+    CK(e->alloc(&e->lp_tok, pos));
+    CK(hipMemsetAsync(e->lp_tok, 0xFF, pos * 4, s));
+    CK(hipMemsetAsync(e->lp_ids, 0xFF, pos * K * 4, s));
+    CK(hipMemsetAsync(e->lp_top, 0xFF, pos * K * 4, s));
+    return DOTS_OK;
+}
+
+// positions of `row` back to NaN / -1 (at each prefill of the row once the outputs exist)
+int clear_lp_row(DotsEngine* e, int row) {
+    if (!e->lp_tok) return DOTS_OK;
+    const size_t L = e->cfg.max_seq_len, K = DOTS_MAX_TOP_LOGPROBS;
+    CK(hipMemsetAsync(e->lp_tok + (size_t)row * L, 0xFF, L * 4, e->stream));
+    CK(hipMemsetAsync(e->lp_ids + (size_t)row * L * K, 0xFF, L * K * 4, e->stream));
+    CK(hipMemsetAsync(e->lp_top + (size_t)row * L * K, 0xFF, L * K * 4, e->stream));
+    return DOTS_OK;
+}
+
+// top_n of the row (-1 = off), in stream order; keeps n_lp, the count of rows that are on
+int set_row_lp(DotsEngine* e, int row, int top_n) {
+    const bool was = e->row_lp[row] >= 0;
+    if (!was && top_n < 0) return DOTS_OK;
+    CK(launch_set_row_lp(e->stream, e->d_row_lp, row, top_n));
+    e->row_lp[row] = top_n;
+    e->n_lp += (top_n >= 0 ? 1 : 0) - (was ? 1 : 0);
     return DOTS_OK;
 }
 
@@ -1107,6 +1159,7 @@ int prefill(DotsEngine* e, const int32_t* ids, const int32_t* lens, int B, const
         CK(hipMemcpyAsync(e->p_dst, S.data(), B * 4, hipMemcpyHostToDevice, s));
     }
 
+    for (int b = 0; b < B; ++b) RET(clear_lp_row(e, S[b]));         // logprob positions of the prefilled rows: NaN / -1 until written
     CK(hipEventRecord(e->ev[2], s));
     CK(launch_embed_gather(s, e->p_src, e->embed, e->vis, e->p_x, T, H));
     CK(launch_rope_table(s, e->p_pos, e->lm_inv_freq, e->p_cs, T, 0));
@@ -1203,14 +1256,14 @@ int splits_for_ctx(int max_ctx) { return decode_attn_splits(max_ctx); }
 
 // The captured decode step for (rows = e->B, splits, out_cap, e->n_eos): looked up in the cache or captured now.
 int step_graph(DotsEngine* e, int rows, int n_splits, int out_cap, hipGraphExec_t* exec, int part = 0) {
-    const int rowp = e->n_own > 0 ? 1 : 0;
+    const int rowp = e->n_own > 0 ? 1 : 0, lp = e->n_lp > 0 ? 1 : 0;
     for (auto& g : e->step_graphs)
-        if (g.rows == rows && g.splits == n_splits && g.out_cap == out_cap && g.n_eos == e->n_eos && g.part == part && g.rowp == rowp) {
+        if (g.rows == rows && g.splits == n_splits && g.out_cap == out_cap && g.n_eos == e->n_eos && g.part == part && g.rowp == rowp && g.lp == lp) {
             *exec = g.exec;
             return DOTS_OK;
         }
     if (e->step_graphs.size() >= 32) drop_step_graphs(e);
-    DotsEngine::StepGraph g{rows, n_splits, out_cap, e->n_eos, part, rowp, nullptr, nullptr};
+    DotsEngine::StepGraph g{rows, n_splits, out_cap, e->n_eos, part, rowp, lp, nullptr, nullptr};
     CK(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
     int r = decode_step_launches(e, n_splits, part);
     hipError_t ce = hipStreamEndCapture(e->stream, &g.graph);
@@ -1310,6 +1363,7 @@ int dots_create(const DotsConfig* cfg, int device, DotsEngine** out) {
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { g_create_error = "no such HIP device"; return DOTS_E_HIP; }
     if (hipSetDevice(device) != hipSuccess) { g_create_error = "hipSetDevice failed"; return DOTS_E_HIP; }
     DotsEngine* e = new DotsEngine();
+    std::fill(e->row_lp, e->row_lp + DOTS_MAX_BATCH, -1);
     e->cfg = c;
     e->device = device;
     // DOTS_OCR_CU_RANGE="lo-hi" (experiment, tools/overlap_probe.py): the engine's stream only uses CU-mask bits lo..hi (of 256; bit i = CU i / 8 of XCD i % 8)
@@ -1584,6 +1638,9 @@ int dots_slots_reset(DotsEngine* e) {
     if (e->d_row_own) CK(hipMemsetAsync(e->d_row_own, 0, DOTS_MAX_BATCH * 4, s));
     std::fill(e->row_own, e->row_own + DOTS_MAX_BATCH, 0);
     e->n_own = 0;
+    if (e->d_row_lp) CK(hipMemsetAsync(e->d_row_lp, 0xFF, DOTS_MAX_BATCH * 4, s));
+    std::fill(e->row_lp, e->row_lp + DOTS_MAX_BATCH, -1);
+    e->n_lp = 0;
     CK(hipStreamSynchronize(s));
     e->slot_mode = true;
     e->sel_dirty = true;
@@ -1693,6 +1750,7 @@ int dots_slot_release(DotsEngine* e, int slot) {
     if (!e->slot_mode || slot < 0 || slot >= e->cfg.max_batch || !e->slot_active[slot]) return e->fail(DOTS_E_STATE, "slot %d is not occupied", slot);
     CK(hipSetDevice(e->device));
     RET(clear_row(e, slot));
+    RET(set_row_lp(e, slot, -1));
     e->slot_active[slot] = 0;
     e->sel_dirty = true;
     CK(hipMemsetAsync(e->ctx_len + slot, 0, 4, e->stream));          // an idle row attends over one key only ...
@@ -1833,6 +1891,51 @@ int dots_set_row_sampling(DotsEngine* e, int row, const DotsSamplingParams* p) {
     if (rp.repetition_penalty != 1.f || rp.frequency_penalty != 0.f || rp.presence_penalty != 0.f) RET(ensure_pen_state(e));
     CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, rp, 1));
     if (!e->row_own[row]) { e->row_own[row] = 1; e->n_own += 1; }
+    return DOTS_OK;
+}
+
+int dots_set_row_logprobs(DotsEngine* e, int row, int top_n) {
+    if (!e) return DOTS_E_INVALID;
+    if (row < 0 || row >= e->cfg.max_batch) return e->fail(DOTS_E_INVALID, "row %d out of range [0, %d)", row, e->cfg.max_batch);
+    if (top_n < -1 || top_n > DOTS_MAX_TOP_LOGPROBS) return e->fail(DOTS_E_INVALID, "top_n must be -1 (off) or in [0, %d]", DOTS_MAX_TOP_LOGPROBS);
+    if (top_n < 0 && !e->d_row_lp) return DOTS_OK;
+    if (e->cfg.vocab_size > LP_MAX_V) return e->fail(DOTS_E_INVALID, "logprobs support vocabularies up to %d", LP_MAX_V);
+    CK(hipSetDevice(e->device));
+    if (!e->d_row_lp) {
+        CK(e->alloc(&e->d_row_lp, DOTS_MAX_BATCH));
+        CK(hipMemsetAsync(e->d_row_lp, 0xFF, DOTS_MAX_BATCH * 4, e->stream));
+    }
+    if (top_n >= 0) RET(ensure_lp_state(e));
+    return set_row_lp(e, row, top_n);
+}
+
+int dots_row_logprobs(DotsEngine* e, int row, int pos0, int n, float* tok_lp_host, int32_t* top_ids_host, float* top_lp_host, int32_t* n_out) {
+    if (!e || !n_out || pos0 < 0 || n < 0 || (n > 0 && (!tok_lp_host || !top_ids_host || !top_lp_host)))
+        return e ? e->fail(DOTS_E_INVALID, "bad row_logprobs arguments") : DOTS_E_INVALID;
+    if (e->slot_mode) {
+        if (row < 0 || row >= e->cfg.max_batch || !e->slot_active[row]) return e->fail(DOTS_E_STATE, "slot %d is not occupied", row);
+    } else if (row < 0 || row >= e->B) {
+        return e->fail(DOTS_E_STATE, "row %d is not a sequence of the current static batch (%d rows)", row, e->B);
+    }
+    CK(hipSetDevice(e->device));
+    int32_t len = 0;
+    CK(hipMemcpyAsync(&len, e->out_lens + row, 4, hipMemcpyDeviceToHost, e->stream));
+    CK(hipStreamSynchronize(e->stream));
+    const int take = std::max(0, std::min(n, std::min(len, e->cfg.max_seq_len) - pos0));
+    *n_out = take;
+    if (take <= 0) return DOTS_OK;
+    const size_t K = DOTS_MAX_TOP_LOGPROBS;
+    if (!e->lp_tok) {                                   // never switched on: every position was selected with the row off
+        std::fill(tok_lp_host, tok_lp_host + take, std::nanf(""));
+        std::fill(top_ids_host, top_ids_host + take * K, -1);
+        std::fill(top_lp_host, top_lp_host + take * K, std::nanf(""));
+        return DOTS_OK;
+    }
+    const size_t o = (size_t)row * e->cfg.max_seq_len + pos0;
+    CK(hipMemcpyAsync(tok_lp_host, e->lp_tok + o, (size_t)take * 4, hipMemcpyDeviceToHost, e->stream));
+    CK(hipMemcpyAsync(top_ids_host, e->lp_ids + o * K, (size_t)take * K * 4, hipMemcpyDeviceToHost, e->stream));
+    CK(hipMemcpyAsync(top_lp_host, e->lp_top + o * K, (size_t)take * K * 4, hipMemcpyDeviceToHost, e->stream));
+    CK(hipStreamSynchronize(e->stream));
     return DOTS_OK;
 }
 
@@ -2380,6 +2483,73 @@ int dots_bench_select_tokens(DotsEngine* e, const float* logits_dev, int B, int 
                              const int32_t* hist_lens_dev, int hist_stride, const int32_t* n_prompt_dev, int mode, int iters, float* ms_out) {
     if (!ms_out || iters < 1) return e ? e->fail(DOTS_E_INVALID, "bad bench_select_tokens arguments") : DOTS_E_INVALID;
     return select_op(e, logits_dev, B, V, params_host, hist_dev, hist_lens_dev, hist_stride, n_prompt_dev, nullptr, mode, iters, ms_out);
+}
+
+}  // extern "C"
+
+namespace {
+// dots_op_logprobs / dots_bench_logprobs: the two logprob kernels over caller logits, every row at position 0 of its own output row.
+// which 0 = both kernels, 1 = partial only, 2 = final only; iters > 0 = replays between two events, *ms = mean time of one replay.
+int logprobs_op(DotsEngine* e, const float* logits_dev, int B, int V, int ld, const int32_t* top_n_host, const int32_t* chosen_dev,
+                float* tok_lp_dev, int32_t* top_ids_dev, float* top_lp_dev, int which, int iters, float* ms) {
+    if (!e || !logits_dev || B < 1 || B > DOTS_MAX_BATCH || V < 1 || V > LP_MAX_V || ld < V || !top_n_host || which < 0 || which > 2)
+        return e ? e->fail(DOTS_E_INVALID, "bad logprobs arguments") : DOTS_E_INVALID;
+    for (int b = 0; b < B; ++b)
+        if (top_n_host[b] < -1 || top_n_host[b] > DOTS_MAX_TOP_LOGPROBS) return e->fail(DOTS_E_INVALID, "top_n of row %d not in [-1, %d]", b, DOTS_MAX_TOP_LOGPROBS);
+    CK(hipSetDevice(e->device));
+    Scratch sc(e);
+    const size_t K = DOTS_MAX_TOP_LOGPROBS;
+    int32_t *tn = nullptr, *pi = nullptr, *pos = nullptr, *cho = nullptr, *ids = nullptr;
+    float *ms_p = nullptr, *pv = nullptr, *tok = nullptr, *top = nullptr;
+    CK(sc.get(&tn, B));
+    CK(sc.get(&ms_p, (size_t)B * LP_CHUNKS * 2));
+    CK(sc.get(&pv, (size_t)B * LP_CHUNKS * K));
+    CK(sc.get(&pi, (size_t)B * LP_CHUNKS * K));
+    CK(sc.get(&pos, B));
+    if (!chosen_dev) { CK(sc.get(&cho, B)); chosen_dev = cho; }           // timing: token 0 of every row
+    if (!tok_lp_dev) { CK(sc.get(&tok, B)); CK(sc.get(&ids, (size_t)B * K)); CK(sc.get(&top, (size_t)B * K)); tok_lp_dev = tok; top_ids_dev = ids; top_lp_dev = top; }
+    CK(hipMemcpyAsync(tn, top_n_host, B * 4, hipMemcpyHostToDevice, e->stream));
+    const LogprobState ls{tn, nullptr, nullptr, nullptr, chosen_dev, ms_p, pv, pi, pos, tok_lp_dev, top_ids_dev, top_lp_dev, 1};
+    auto run = [&](int w) -> hipError_t {
+        hipError_t r = hipSuccess;
+        if (w != 2) r = launch_logprob_partial(e->stream, logits_dev, V, ld, B, ls);
+        if (r == hipSuccess && w != 1) r = launch_logprob_final(e->stream, logits_dev, V, ld, B, ls);
+        return r;
+    };
+    if (iters <= 0) {
+        CK(run(0));
+        CK(hipStreamSynchronize(e->stream));
+        return DOTS_OK;
+    }
+    for (int i = 0; i < 3; ++i) CK(run(0));                              // warm-up; also leaves the partials the final kernel reads
+    hipEvent_t t0 = nullptr, t1 = nullptr;
+    CK(hipEventCreate(&t0));
+    CK(hipEventCreate(&t1));
+    hipError_t r = hipEventRecord(t0, e->stream);
+    for (int i = 0; i < iters && r == hipSuccess; ++i) r = run(which);
+    if (r == hipSuccess) r = hipEventRecord(t1, e->stream);
+    if (r == hipSuccess) r = hipEventSynchronize(t1);
+    float total = 0.f;
+    if (r == hipSuccess) r = hipEventElapsedTime(&total, t0, t1);
+    hipEventDestroy(t0);
+    hipEventDestroy(t1);
+    CK(r);
+    *ms = total / iters;
+    return DOTS_OK;
+}
+}  // namespace
+
+extern "C" {
+int dots_op_logprobs(DotsEngine* e, const float* logits_dev, int B, int V, int ld, const int32_t* top_n_host, const int32_t* chosen_dev,
+                     float* tok_lp_dev, int32_t* top_ids_dev, float* top_lp_dev) {
+    if (!chosen_dev || !tok_lp_dev || !top_ids_dev || !top_lp_dev) return e ? e->fail(DOTS_E_INVALID, "bad logprobs arguments") : DOTS_E_INVALID;
+    return logprobs_op(e, logits_dev, B, V, ld, top_n_host, chosen_dev, tok_lp_dev, top_ids_dev, top_lp_dev, 0, 0, nullptr);
+}
+
+int dots_bench_logprobs(DotsEngine* e, const float* logits_dev, int B, int V, int ld, const int32_t* top_n_host, int which, int iters,
+                        float* ms_out) {
+    if (!ms_out || iters < 1) return e ? e->fail(DOTS_E_INVALID, "bad bench_logprobs arguments") : DOTS_E_INVALID;
+    return logprobs_op(e, logits_dev, B, V, ld, top_n_host, nullptr, nullptr, nullptr, nullptr, which, iters, ms_out);
 }
 
 }  // extern "C"

@@ -147,6 +147,36 @@ hipError_t launch_pen_history(hipStream_t s, const int32_t* hist, const int32_t*
                               int32_t* cnt, uint32_t* seen, int32_t* out_lens);
 // table[row] = p, own[row] = flag, in stream order
 hipError_t launch_set_row_params(hipStream_t s, RowParams* table, int32_t* own, int row, const RowParams& p, int flag);
+
+// ---- logprobs.hip: log-probabilities of the raw logits of every selected row
+#ifndef DOTS_MAX_TOP_LOGPROBS
+#define DOTS_MAX_TOP_LOGPROBS 20
+#endif
+constexpr int LP_CHUNKS = 64;                  // vocabulary chunks per row (grid x of the partial kernel)
+constexpr int LP_MAX_CHUNK = 4096;             // values of one chunk a 256-thread workgroup holds in registers
+constexpr int LP_MAX_V = LP_CHUNKS * LP_MAX_CHUNK;
+//   top_n    [rows] -1 = off (the row is skipped), 0 = the chosen token only, 1..DOTS_MAX_TOP_LOGPROBS
+//   sel / finished / out_lens  as StepState (nullptr: every row / none finished / position 0); read BEFORE the selection kernels
+//   chosen   [rows] the token selection committed (StepState.cur_tokens); read AFTER them
+//   part_ms  [rows][LP_CHUNKS][2] (m, s), part_v / part_i [rows][LP_CHUNKS][DOTS_MAX_TOP_LOGPROBS], pos [rows]: scratch
+//   tok_lp   [rows][stride], top_ids / top_lp [rows][stride][DOTS_MAX_TOP_LOGPROBS]: row b's token of this step goes to position
+//            out_lens[b] (taken before the commit); a row already finished is not written
+struct LogprobState {
+    const int32_t *top_n, *sel, *finished, *out_lens, *chosen;
+    float* part_ms;
+    float* part_v;
+    int32_t* part_i;
+    int32_t* pos;
+    float* tok_lp;
+    int32_t* top_ids;
+    float* top_lp;
+    int stride;
+};
+// V <= LP_MAX_V, ld >= V; grid (LP_CHUNKS, B) / B
+hipError_t launch_logprob_partial(hipStream_t s, const float* logits, int V, int ld, int B, const LogprobState& st);
+hipError_t launch_logprob_final(hipStream_t s, const float* logits, int V, int ld, int B, const LogprobState& st);
+// table[row] = top_n, in stream order
+hipError_t launch_set_row_lp(hipStream_t s, int32_t* table, int row, int top_n);
 // row-major [rows, K] -> MFMA fragment order (decode.hip): 16-row tiles x K/32 chunks of 1 KiB
 hipError_t launch_pack_frag(hipStream_t s, const bf16_t* src, bf16_t* dst, int64_t rows, int K);
 // fused qkv weight [(Hq + 2 Hkv) * 128, K]: as launch_pack_frag, q / k head rows permuted so that a 16-row tile holds whole RoPE pairs

@@ -178,6 +178,10 @@ def _prototypes(lib):
         "dots_op_dec_lmhead": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, f32, i32]),
         "dots_op_select_tokens": (i32, [vp, vp, i32, i32, P(CDotsSamplingParams), vp, vp, i32, vp, vp]),
         "dots_bench_select_tokens": (i32, [vp, vp, i32, i32, P(CDotsSamplingParams), vp, vp, i32, vp, i32, i32, P(f32)]),
+        "dots_set_row_logprobs": (i32, [vp, i32, i32]),
+        "dots_row_logprobs": (i32, [vp, i32, i32, i32, P(f32), P(i32), P(f32), P(i32)]),
+        "dots_op_logprobs": (i32, [vp, vp, i32, i32, i32, P(i32), vp, vp, vp, vp]),
+        "dots_bench_logprobs": (i32, [vp, vp, i32, i32, i32, P(i32), i32, i32, P(f32)]),
         "dots_probe_mfma": (i32, [i32, vp, vp, vp, vp]),
         "dots_probe_grid_barrier": (i32, [i32, i32, i32, i32, i32, P(f32), P(i32)]),
         "dots_probe_cu_mask": (i32, [P(C.c_uint32), i32, i32, i32, i32, P(C.c_uint32)]),
@@ -200,7 +204,10 @@ EXPORTED_SYMBOLS = [
     "dots_op_dec_lmhead", "dots_probe_mfma", "dots_probe_grid_barrier", "dots_probe_cu_mask",
     "dots_set_kv_scales", "dots_debug_read_kv", "dots_op_dec_qkv_kv8", "dots_op_decode_attn_kv8",
     "dots_set_row_sampling", "dots_op_select_tokens", "dots_bench_select_tokens",
+    "dots_set_row_logprobs", "dots_row_logprobs", "dots_op_logprobs", "dots_bench_logprobs",
 ]
+
+MAX_TOP_LOGPROBS = 20                        # DOTS_MAX_TOP_LOGPROBS: top entries kept per position
 
 KV_CACHE_DTYPES = {"bf16": 0, "fp8": 1}      # DotsConfig.kv_cache_dtype; "fp8" = OCP e4m3fn (vLLM's --kv-cache-dtype fp8)
 
@@ -453,6 +460,47 @@ class Engine:
         ms = C.c_float()
         self._ck(self.lib.dots_bench_select_tokens(self.h, logits, int(B), int(V), arr, hist, hist_lens, int(hist_stride), n_prompt, int(mode),
                                                    int(iters), C.byref(ms)), "dots_bench_select_tokens")
+        return float(ms.value)
+
+    def set_row_logprobs(self, row: int, top_n: Optional[int]):
+        """Row `row` (a slot, or sequence `row` of a static batch) returns log-probabilities of the raw logits for every token selected
+        from now on, the first token of a following prefill included: the chosen token's and the top_n (0..20) largest.  None = off.
+        Slot release and slots_reset switch the row off."""
+        n = -1 if top_n is None else int(top_n)
+        if top_n is not None and not 0 <= n <= MAX_TOP_LOGPROBS:
+            raise ValueError(f"top_n must be None or in [0, {MAX_TOP_LOGPROBS}], got {top_n!r}")
+        self._ck(self.lib.dots_set_row_logprobs(self.h, int(row), n), "dots_set_row_logprobs")
+
+    def row_logprobs(self, row: int, n: int, pos0: int = 0):
+        """Positions [pos0, pos0 + n) of the row's generated tokens, cut to the positions that exist: (tok_lp float32 [m],
+        top_ids int32 [m, 20], top_lp float32 [m, 20]); -1 / NaN beyond the row's top_n and where the row was off.  An occupied slot
+        (before slot_release), or a row of the last static batch."""
+        n = max(0, int(n))
+        K = MAX_TOP_LOGPROBS
+        tok = np.empty((max(1, n),), np.float32)
+        ids = np.empty((max(1, n), K), np.int32)
+        top = np.empty((max(1, n), K), np.float32)
+        m = C.c_int32(0)
+        fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))                          # noqa: E731
+        self._ck(self.lib.dots_row_logprobs(self.h, int(row), int(pos0), n, fp(tok), _i32p(ids), fp(top), C.byref(m)), "dots_row_logprobs")
+        k = int(m.value)
+        return tok[:k].copy(), ids[:k].copy(), top[:k].copy()
+
+    def op_logprobs(self, logits, B: int, V: int, ld: int, top_n: Sequence[int], chosen, tok_lp, top_ids, top_lp):
+        """The logprob stage on device buffers (dots_op_logprobs): logits fp32 [B, ld], chosen int32 [B]; writes tok_lp fp32 [B],
+        top_ids int32 [B, 20], top_lp fp32 [B, 20] of the rows with top_n[b] >= 0 (-1 = skipped)."""
+        tn = np.ascontiguousarray(top_n, dtype=np.int32)
+        if tn.shape != (B,):
+            raise ValueError("one top_n per row")
+        self._ck(self.lib.dots_op_logprobs(self.h, logits, int(B), int(V), int(ld), _i32p(tn), chosen, tok_lp, top_ids, top_lp),
+                 "dots_op_logprobs")
+
+    def bench_logprobs(self, logits, B: int, V: int, ld: int, top_n: Sequence[int], which: int = 0, iters: int = 200) -> float:
+        """mean ms of one replay of the logprob stage: which 0 = both kernels, 1 = the partial kernel, 2 = the final kernel"""
+        tn = np.ascontiguousarray(top_n, dtype=np.int32)
+        ms = C.c_float()
+        self._ck(self.lib.dots_bench_logprobs(self.h, logits, int(B), int(V), int(ld), _i32p(tn), int(which), int(iters), C.byref(ms)),
+                 "dots_bench_logprobs")
         return float(ms.value)
 
     def set_decode_plan(self, plan: int):

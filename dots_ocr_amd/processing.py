@@ -36,6 +36,32 @@ class BatchFeature(dict):
         return BatchFeature({k: (v.to(device) if isinstance(v, torch.Tensor) else v) for k, v in self.items()})
 
 
+def _byte_to_unicode() -> dict:
+    """The byte-level BPE alphabet (GPT-2, shared by Qwen2 tokenizers): printable bytes map to themselves, the rest to U+0100 onwards."""
+    bs = list(range(ord("!"), ord("~") + 1)) + list(range(ord("\u00a1"), ord("\u00ac") + 1)) + list(range(ord("\u00ae"), ord("\u00ff") + 1))
+    cs = bs[:]
+    n = 0
+    for b in range(256):
+        if b not in bs:
+            bs.append(b)
+            cs.append(256 + n)
+            n += 1
+    return {b: chr(c) for b, c in zip(bs, cs)}
+
+
+BYTE_TO_UNICODE = _byte_to_unicode()
+UNICODE_TO_BYTE = {c: b for b, c in BYTE_TO_UNICODE.items()}
+
+
+def byte_level_token_bytes(token: str) -> bytes:
+    """The raw bytes of a byte-level BPE vocabulary entry (its characters mapped back through BYTE_TO_UNICODE); a string with a
+    character outside that alphabet is not a byte-level entry and gives its own UTF-8."""
+    try:
+        return bytes(UNICODE_TO_BYTE[ch] for ch in token)
+    except KeyError:
+        return token.encode("utf-8")
+
+
 class SyntheticByteTokenizer:
     """Stand-in used only when no checkpoint tokenizer exists: UTF-8 bytes are ids 0..255, the chat /
     image special tokens sit just below the vocabulary end (image pad == config.image_token_id)."""
@@ -90,6 +116,13 @@ class SyntheticByteTokenizer:
             parts.append(buf.decode("utf-8", errors="replace"))
         return "".join(parts)
 
+    def token_bytes(self, token_id: int) -> bytes:
+        """the byte itself for ids < 256, else the UTF-8 of the text decode(skip_special_tokens=False) gives"""
+        t = int(token_id)
+        if 0 <= t < 256:
+            return bytes([t])
+        return self.decode([t], skip_special_tokens=False).encode("utf-8")
+
 
 class HFJsonTokenizer:
     """The checkpoint's tokenizer.json via the `tokenizers` runtime."""
@@ -98,6 +131,7 @@ class HFJsonTokenizer:
         from tokenizers import Tokenizer
         self.tk = Tokenizer.from_file(str(path / "tokenizer.json"))
         self.pad_token_id = cfg.pad_token_id
+        self._added = None                           # id -> content of the added / special tokens (token_bytes), read on first use
         self.special_tokens_map = {}                 # bos/eos/pad strings a chat template may reference
         for name in ("special_tokens_map.json", "tokenizer_config.json"):
             f = path / name
@@ -115,6 +149,17 @@ class HFJsonTokenizer:
 
     def decode(self, ids: Sequence[int], skip_special_tokens: bool = True) -> str:
         return self.tk.decode([int(i) for i in ids], skip_special_tokens=skip_special_tokens)
+
+    def token_bytes(self, token_id: int) -> bytes:
+        """raw bytes of one vocabulary entry: byte-level BPE tokens through the byte <-> unicode table, added / special tokens as the
+        UTF-8 of their content"""
+        t = int(token_id)
+        if self._added is None:
+            self._added = {int(i): a.content for i, a in self.tk.get_added_tokens_decoder().items()}
+        if t in self._added:
+            return self._added[t].encode("utf-8")
+        tok = self.tk.id_to_token(t)
+        return b"" if tok is None else byte_level_token_bytes(tok)
 
 
 def process_vision_info(messages):
@@ -283,3 +328,7 @@ class DotsOcrProcessor:
 
     def decode(self, ids, **kw):
         return self.batch_decode([ids], **kw)[0]
+
+    def token_bytes(self, token_id: int) -> bytes:
+        """raw bytes of one token (the `bytes` field of an OpenAI logprobs entry)"""
+        return self.tokenizer.token_bytes(token_id)

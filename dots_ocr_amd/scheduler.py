@@ -26,6 +26,8 @@ class Request:
     max_new_tokens: int = 128
     tag: object = None
     sampling: Optional[object] = None           # engine.SamplingParams of this request, or None = the engine-wide setting
+    logprobs: Optional[int] = None              # top_n (0..20) of per-token log-probabilities to return, None = off; a finished request
+                                                # then carries logprobs_out = Engine.row_logprobs(slot, its token count)
 
     def n_patches(self) -> int:
         if self.grid_thw is None:
@@ -71,6 +73,7 @@ class ContinuousBatcher:
         self.admissions = 0
         self._last_lens: Dict[int, int] = {}                     # slot -> tokens generated as of the last poll
         self._row_params: Dict[int, object] = {}                 # slot -> the SamplingParams set on it (engine.set_row_sampling)
+        self._row_lp: Dict[int, int] = {}                        # slot -> the logprobs top_n set on it (engine.set_row_logprobs)
         self.kv_truncated = 0                                    # sequences ended early by a dry KV pool (finish reason "kv_pool_exhausted")
         engine.set_eos(list(eos_ids))
         if hasattr(engine, "slots_reset"):           # start from an empty engine: no occupied slot, every KV page in the pool
@@ -180,12 +183,19 @@ class ContinuousBatcher:
                 self._row_params[s] = r.sampling
             elif self._row_params.pop(s, None) is not None:
                 self.engine.set_row_sampling(s, None)
+            if r.logprobs is not None:               # logprobs likewise, the prefill's token included
+                self.engine.set_row_logprobs(s, r.logprobs)
+                self._row_lp[s] = r.logprobs
+            elif self._row_lp.pop(s, None) is not None:
+                self.engine.set_row_logprobs(s, None)
         try:
             self.engine.slots_prefill(slots, np.concatenate([r.input_ids for _, _, r in group]), lens, caps)
         except Exception:
             for s in slots:                          # the slots stay free: leave no entry on them (it would keep the per-row stage on)
                 if self._row_params.pop(s, None) is not None:
                     self.engine.set_row_sampling(s, None)
+                if self._row_lp.pop(s, None) is not None:
+                    self.engine.set_row_logprobs(s, None)
             raise
         for s, rid, r in group:
             self.running[s] = (rid, r)
@@ -293,6 +303,8 @@ class ContinuousBatcher:
                     _, limit = self.engine.slot_capacity(s)
                     req.kv_truncated = bool(limit < int(req.input_ids.shape[0]) + int(req.max_new_tokens) and len(toks) >= limit - int(req.input_ids.shape[0]))
                     self.kv_truncated += int(req.kv_truncated)
+                if req.logprobs is not None:         # read before the release switches the slot's logprobs off
+                    req.logprobs_out = self.engine.row_logprobs(s, len(toks))
                 done.append((rid, req, toks))
                 self.engine.slot_release(s)
         self._last_lens = {s: int(lens[s]) for s in self.running}      # after the finished slots have left: only what is still decoding

@@ -13,11 +13,14 @@ share a vLLM server: `ContinuousWorker` admits a request into a free sequence sl
 as pages finish (dots_ocr_amd/scheduler.py).  On an engine with per-row selection (Engine.set_row_sampling) every request
 carries its own sampling parameters on its slot and one running set serves them all; on an engine without it, requests with
 other parameters wait for the running set to drain, and a request that asks for top_k or a penalty is refused (400).
+`logprobs` / `top_logprobs` return the OpenAI `choices[0].logprobs` object (raw-logit log-probabilities, Engine.set_row_logprobs); they
+need continuous batching on an engine that has them, else 400.
 `BatchingWorker` (static batches through `model.generate`) remains for model objects without engine slots.
 """
 from __future__ import annotations
 
 import argparse
+import math
 import queue
 import threading
 import time
@@ -31,13 +34,14 @@ from .processing import ASSISTANT, END_USER, IMG_END, IMG_PAD, IMG_START, USER
 
 class _Job:
     __slots__ = ("image", "text", "max_tokens", "temperature", "top_p", "top_k", "repetition_penalty", "frequency_penalty",
-                 "presence_penalty", "seed", "future")
+                 "presence_penalty", "seed", "logprobs", "future")
 
     def __init__(self, image, text, max_tokens, temperature, top_p, top_k=0, repetition_penalty=1.0, frequency_penalty=0.0,
-                 presence_penalty=0.0, seed=None):
+                 presence_penalty=0.0, seed=None, logprobs=None):
         self.image, self.text, self.max_tokens, self.temperature, self.top_p = image, text, max_tokens, temperature, top_p
         self.top_k, self.repetition_penalty = top_k, repetition_penalty
         self.frequency_penalty, self.presence_penalty, self.seed = frequency_penalty, presence_penalty, seed
+        self.logprobs = logprobs                    # top_logprobs (0..20) when the request asked for logprobs, else None
         self.future: Future = Future()
 
     @property
@@ -159,14 +163,22 @@ class ContinuousWorker(BatchingWorker):
                               frequency_penalty=job.frequency_penalty, presence_penalty=job.presence_penalty,
                               seed=self.seed if job.seed is None else job.seed)
 
-    def _finish(self, job: _Job, prompt_tokens: int, toks, kv_truncated: bool = False):
+    @property
+    def has_logprobs(self) -> bool:
+        """the engine returns per-token log-probabilities (Engine.set_row_logprobs)"""
+        return hasattr(self.model.engine, "set_row_logprobs")
+
+    def _finish(self, job: _Job, prompt_tokens: int, toks, kv_truncated: bool = False, logprobs=None):
         eos = set(self.model.config.eos_token_ids)
         toks = [int(t) for t in toks]
         text = self.processor.batch_decode([toks], skip_special_tokens=True, clean_up_tokenization_spaces=False)[0]
         # "kv_pool_exhausted": the engine ended the sequence at what its KV pages hold (vLLM would preempt and recompute; here the
         # caller sees that the output is short for a reason other than max_tokens and can resubmit)
         reason = "stop" if toks and toks[-1] in eos else ("kv_pool_exhausted" if kv_truncated else "length")
-        job.future.set_result({"text": text, "prompt_tokens": prompt_tokens, "completion_tokens": len(toks), "finish_reason": reason})
+        res = {"text": text, "prompt_tokens": prompt_tokens, "completion_tokens": len(toks), "finish_reason": reason}
+        if job.logprobs is not None:
+            res["logprobs"] = _logprobs_object(self.processor, toks, logprobs, job.logprobs)
+        job.future.set_result(res)
 
     def _run(self):
         from collections import deque
@@ -213,13 +225,14 @@ class ContinuousWorker(BatchingWorker):
                         ids = inputs["input_ids"][0].numpy()
                         cb.submit(Request(ids, inputs.get("pixel_values"), None if "image_grid_thw" not in inputs
                                           else inputs["image_grid_thw"].numpy(), job.max_tokens, tag=job,
-                                          sampling=self._row_params(job) if per_row else None))
+                                          sampling=self._row_params(job) if per_row else None, logprobs=job.logprobs))
                         admitted += 1
                     except Exception as e:                           # a bad request fails alone
                         job.future.set_exception(e)
                 if cb is not None and not cb.idle:
                     for _, req, toks in cb.step():
-                        self._finish(req.tag, int(req.input_ids.shape[0]), toks, getattr(req, "kv_truncated", False))
+                        self._finish(req.tag, int(req.input_ids.shape[0]), toks, getattr(req, "kv_truncated", False),
+                                     getattr(req, "logprobs_out", None))
                     if admitted:
                         self.batches.append(len(cb.running))
             except Exception as e:                                   # engine failure: fail everything in flight, start clean
@@ -313,6 +326,40 @@ def _selection_fields(req: dict) -> dict:
     return out
 
 
+def _logprob_fields(req: dict) -> Optional[int]:
+    """`logprobs` (bool) and `top_logprobs` (0..20, only with logprobs: true) of a request -> the top_n to return, or None when the
+    request does not ask for logprobs.  ValueError / TypeError on a bad value."""
+    from .engine import MAX_TOP_LOGPROBS
+    lp, top = req.get("logprobs"), req.get("top_logprobs")
+    if lp is not None and not isinstance(lp, bool):
+        raise TypeError("logprobs must be a boolean")
+    if top is not None:
+        if isinstance(top, bool) or not isinstance(top, int):
+            raise TypeError("top_logprobs must be an integer")
+        if not lp:
+            raise ValueError("top_logprobs needs logprobs: true")
+        if not 0 <= top <= MAX_TOP_LOGPROBS:
+            raise ValueError(f"top_logprobs must be in [0, {MAX_TOP_LOGPROBS}]")
+    return (top or 0) if lp else None
+
+
+def _logprobs_object(processor, toks, logprobs, top_n: int) -> dict:
+    """The OpenAI `choices[i].logprobs` object: one entry per generated id (the final EOS included), each with `top_n` alternatives.
+    logprobs = (tok_lp [n], top_ids [n, 20], top_lp [n, 20]) as Engine.row_logprobs returns them."""
+    tok_lp, top_ids, top_lp = logprobs
+
+    def entry(t, v):
+        v = float(v)
+        return {"token": processor.tokenizer.decode([int(t)], skip_special_tokens=False), "logprob": v if math.isfinite(v) else -9999.0,
+                "bytes": list(processor.token_bytes(int(t)))}
+    content = []
+    for n, t in enumerate(toks):
+        e = entry(t, tok_lp[n])
+        e["top_logprobs"] = [entry(top_ids[n][k], top_lp[n][k]) for k in range(top_n)]
+        content.append(e)
+    return {"content": content}
+
+
 def create_app(model, processor, model_name: str = "model", max_batch: int = 8, max_wait_ms: float = 5.0, continuous: Optional[bool] = None,
                allow_remote_images: bool = False, allow_local_images: bool = False, look_ahead: Optional[int] = None):
     from fastapi import FastAPI, HTTPException
@@ -356,15 +403,24 @@ def create_app(model, processor, model_name: str = "model", max_batch: int = 8, 
             raise HTTPException(400, f"bad sampling parameters: {e}")
         if job.extended and isinstance(worker, ContinuousWorker) and not worker.per_row:
             raise HTTPException(400, "top_k, repetition_penalty, frequency_penalty and presence_penalty need an engine with per-row selection")
+        try:
+            job.logprobs = _logprob_fields(req)
+        except (TypeError, ValueError) as e:
+            raise HTTPException(400, f"bad logprobs parameters: {e}")
+        if job.logprobs is not None and not (isinstance(worker, ContinuousWorker) and worker.has_logprobs):
+            raise HTTPException(400, "logprobs need continuous batching on an engine that returns log-probabilities (Engine.set_row_logprobs)")
         fut = worker.submit(job)
         try:
             res = await run_in_threadpool(fut.result)
         except Exception as e:
             raise HTTPException(500, f"generation failed: {e}")
+        choice = {"index": 0, "message": {"role": "assistant", "content": res["text"]}, "finish_reason": res["finish_reason"]}
+        if job.logprobs is not None:                 # only when asked: other responses stay exactly as they were
+            choice["logprobs"] = res["logprobs"]
         return {
             "id": "chatcmpl-" + uuid.uuid4().hex, "object": "chat.completion", "created": int(time.time()),
             "model": req.get("model", model_name),
-            "choices": [{"index": 0, "message": {"role": "assistant", "content": res["text"]}, "finish_reason": res["finish_reason"]}],
+            "choices": [choice],
             "usage": {"prompt_tokens": res["prompt_tokens"], "completion_tokens": res["completion_tokens"],
                       "total_tokens": res["prompt_tokens"] + res["completion_tokens"]},
         }

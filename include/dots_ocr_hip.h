@@ -191,6 +191,22 @@ typedef struct DotsSamplingParams {
  * bits exist only if some row of this engine had used a penalty before the row's prefill (the state is allocated on first use and
  * written by each prefill from then on); the prompt is not kept on the device to rebuild them. */
 int dots_set_row_sampling(DotsEngine* e, int row, const DotsSamplingParams* p);
+
+/* Log-probabilities: log_softmax of the raw fp32 logits of the step (before penalties, temperature, top-k and top-p:
+ * the values dots_get_logits returns), for every token a row commits, the prefill's first token included.  The top entries are
+ * ordered by value descending, then index ascending.  lse comes from per-chunk (max, sum) pairs merged in a fixed chunk order, so a
+ * row's values are bitwise the same alone, in any batch and in any slot.  Tokens and logits are the same with logprobs on or off. */
+#define DOTS_MAX_TOP_LOGPROBS 20
+/* Row `row` (a slot, or sequence b of a static batch) returns log-probabilities of the raw logits for every token selected from now on
+ * (the first token of a following dots_prefill / dots_slots_prefill included).  top_n: -1 = off, 0 = the chosen token only, 1..20.
+ * Stream ordered; captured decode graphs are kept.  dots_slot_release / dots_slots_reset switch the row off.  The output buffers
+ * (max_batch x max_seq_len x 164 B) are allocated by the first call that switches a row on; from then on every prefill of a row
+ * fills its positions with NaN / -1 first, whether or not the row is on.  DOTS_E_INVALID for a vocabulary above 262 144. */
+int dots_set_row_logprobs(DotsEngine* e, int row, int top_n);
+/* Positions [pos0, pos0 + n) of the row's generated tokens: tok_lp float [n], top_ids int32 [n][20], top_lp float [n][20]
+ * (entries beyond the row's top_n, and positions selected while the row was off: -1 / NaN).  *n_out = positions that exist.
+ * Slot mode: an occupied slot (read before dots_slot_release).  Static mode: rows < B after dots_generate / dots_decode_step. */
+int dots_row_logprobs(DotsEngine* e, int row, int pos0, int n, float* tok_lp_host, int32_t* top_ids_host, float* top_lp_host, int32_t* n_out);
 /* Launch plan of the decode step (results are bit-identical under either plan).  0 (default) = chosen by where the step runs: the
  * whole-chip plan (qkv / o_proj / down_proj as 8-row half tiles: 256 / 192 / 192 workgroups; one gate|up workgroup per tile pair), or —
  * while the step is replayed on the decode CU partition beside a prefetched vision tower (dots_vit_prefetch) — the PARTITION plan: the
@@ -363,6 +379,15 @@ int dots_op_select_tokens(DotsEngine* e, const float* logits_dev, int B, int V, 
  * every row marked finished so that nothing is appended.  *ms_out = mean milliseconds per replay. */
 int dots_bench_select_tokens(DotsEngine* e, const float* logits_dev, int B, int V, const DotsSamplingParams* params_host, const int32_t* hist_dev,
                              const int32_t* hist_lens_dev, int hist_stride, const int32_t* n_prompt_dev, int mode, int iters, float* ms_out);
+/* The log-probability stage over caller logits: logits_dev fp32 [B, ld] (V <= ld), top_n_host [B] (-1 = row skipped, 0..20),
+ * chosen_dev int32 [B] the chosen ids; writes tok_lp_dev float [B], top_ids_dev int32 [B][20], top_lp_dev float [B][20] of every row
+ * with top_n >= 0 (entries beyond top_n: -1 / NaN).  The same two kernels the engine runs. */
+int dots_op_logprobs(DotsEngine* e, const float* logits_dev, int B, int V, int ld, const int32_t* top_n_host,
+                     const int32_t* chosen_dev, float* tok_lp_dev, int32_t* top_ids_dev, float* top_lp_dev);
+/* Timing of that stage on the same inputs (tools/logprobs_bench.py): which 0 = both kernels, 1 = the partial kernel, 2 = the final
+ * kernel; iters replays between HIP events after a warm-up.  *ms_out = mean milliseconds per replay. */
+int dots_bench_logprobs(DotsEngine* e, const float* logits_dev, int B, int V, int ld, const int32_t* top_n_host, int which, int iters,
+                        float* ms_out);
 
 /* MFMA fragment-layout / LDS-DMA probe (csrc/probe_mfma.hip; tests/test_mfma_layout.py). */
 int dots_probe_mfma(int which, const void* A, const void* Bt, void* D, void* stream);
