@@ -568,7 +568,9 @@ constexpr int ARGMAX_CHUNKS = 64;
 // Commit one selected token of row (slot) b: append to its output, EOS / length bookkeeping, next-step input.
 // A finished row keeps decoding (fixed-shape graph) but its context is frozen, so it rewrites the same KV position for ever
 // and can idle in its slot until the host refills it (continuous batching).
-DEVI void commit_token(const StepState& st, int b, int tok) {
+// rules: the row's logit rules (per-row stage only) or nullptr: its stop ids finish it too, RULE_IGNORE_EOS takes the engine's
+// EOS ids out of the test.  The arg-max and engine-wide sampler paths pass nullptr (a constant after inlining).
+DEVI void commit_token(const StepState& st, int b, int tok, const RowRules* rules = nullptr) {
     const bool done = st.finished[b] != 0;
     if (st.advance_ctx && !done) st.ctx_len[b] += 1;
     if (!done) {
@@ -577,7 +579,10 @@ DEVI void commit_token(const StepState& st, int b, int tok) {
         st.out_ids[(size_t)b * st.out_stride + n] = tok;
         st.out_lens[b] = n + 1;
         bool eos = false;
-        for (int k = 0; k < st.n_eos; ++k) eos = eos || (tok == st.eos_ids[k]);
+        if (!(rules && (rules->flags & RULE_IGNORE_EOS)))
+            for (int k = 0; k < st.n_eos; ++k) eos = eos || (tok == st.eos_ids[k]);
+        if (rules)
+            for (int k = 0; k < min(rules->n_stop, DOTS_MAX_STOP_IDS); ++k) eos = eos || (tok == rules->stop[k]);
         if (eos || n + 1 >= cap) st.finished[b] = 1;
     }
     st.cur_tokens[b] = tok;
@@ -743,10 +748,14 @@ DEVI float penalise(float l, int c, bool seen_prompt, const RowParams& p) {
     return l;
 }
 
+// does row b carry logit rules in this launch (uniform per workgroup)
+DEVI bool row_ruled(const RowSel& rs, int b) { return rs.rules && (rs.rules[b].flags & RULE_ON); }
+
 __global__ __launch_bounds__(256) void select_partial_kernel(const float* __restrict__ logits, int V, int ld, RowSel rs, StepState st,
                                                              float* __restrict__ pval, int32_t* __restrict__ pidx) {
     __shared__ float sv[4];
     __shared__ int si[4];
+    __shared__ int s_kill[16 + DOTS_MAX_STOP_IDS], s_nkill;
     const int c = blockIdx.x, b = blockIdx.y;
     if (st.sel && !st.sel[b]) return;
     const bool own = rs.own[b] != 0;
@@ -757,7 +766,41 @@ __global__ __launch_bounds__(256) void select_partial_kernel(const float* __rest
     float best = -INFINITY;
     int bi = 0x7fffffff;
     const RowParams p = own ? rs.params[b] : RowParams{0.f, 1.f, 0, 1.f, 0.f, 0.f, 0};
-    if (own && rs.cnt && row_has_pen(p)) {
+    if (own && row_ruled(rs, b)) {
+        // Logit rules, in vLLM's order: l + bias (-inf: banned / not allowed), -inf for the EOS and stop ids below min_tokens,
+        // then the penalties on that value (-inf stays -inf: r > 0 and the subtrahend is finite).  Still one read of the logits; the shaped
+        // values go to the scratch the threshold and draw kernels read.
+        const RowRules& r = rs.rules[b];
+        const bool pen_on = rs.cnt && row_has_pen(p);
+        const float* img = (r.flags & RULE_IMG) ? rs.rule_img + (size_t)b * V : nullptr;
+        // below min_tokens: the EOS / stop ids that fall into THIS chunk (of ~V / 64 ids: none for most chunks, so the loop below compares
+        // nothing there).  The order of the list does not enter the result.
+        int n_kill = 0;
+        if (st.out_lens[b] < r.min_tokens) {
+            const int ne = min(st.n_eos, 16), ns = min(r.n_stop, DOTS_MAX_STOP_IDS);
+            if (threadIdx.x == 0) s_nkill = 0;
+            __syncthreads();
+            if ((int)threadIdx.x < ne + ns) {
+                const int id = (int)threadIdx.x < ne ? st.eos_ids[threadIdx.x] : r.stop[threadIdx.x - ne];
+                if (id >= lo && id < hi) s_kill[atomicAdd(&s_nkill, 1)] = id;
+            }
+            __syncthreads();
+            n_kill = s_nkill;
+        }
+        const int W = (V + 31) >> 5;
+        const int32_t* cnt = pen_on ? rs.cnt + (size_t)b * V : nullptr;
+        const uint32_t* seen = pen_on ? rs.seen + (size_t)b * W : nullptr;
+        float* shaped = rs.pen + (size_t)b * V;
+        const bool sampled = p.temperature > 0.f;                    // a greedy row needs the arg max only
+        for (int i = lo + threadIdx.x; i < hi; i += 256) {
+            float l = row[i];
+            if (img) l += img[i];
+            for (int k = 0; k < n_kill; ++k) l = s_kill[k] == i ? -INFINITY : l;
+            if (pen_on) l = penalise(l, cnt[i], (seen[i >> 5] >> (i & 31)) & 1u, p);
+            if (sampled) shaped[i] = l;
+            argmax_merge(best, bi, l, i);
+        }
+    } else if (own && rs.cnt && row_has_pen(p)) {
         const int W = (V + 31) >> 5;
         const int32_t* cnt = rs.cnt + (size_t)b * V;
         const uint32_t* seen = rs.seen + (size_t)b * W;
@@ -883,7 +926,7 @@ DEVI uint32_t radix_select(Each each, uint64_t target, bool by_mass, SelLds& L) 
 
 DEVI void commit_row(const StepState& st, const RowSel& rs, int b, int V, bool pen, int tok) {
     if (pen && !st.finished[b] && tok >= 0 && tok < V) rs.cnt[(size_t)b * V + tok] += 1;     // output counts of the rows with penalties
-    commit_token(st, b, tok);
+    commit_token(st, b, tok, row_ruled(rs, b) ? rs.rules + b : nullptr);
 }
 
 // the merged arg max partials of row b -> L.best / L.bi (every thread must call)
@@ -912,7 +955,7 @@ __global__ __launch_bounds__(SEL_THREADS) void select_thresh_kernel(const float*
         return;
     }
     merge_partials(pval, pidx, b, &L.best, &L.bi);
-    const bool pen = rs.cnt && row_has_pen(p);
+    const bool pen = (rs.cnt && row_has_pen(p)) || row_ruled(rs, b);      // the shaped values of the partial kernel
     const float* row = pen ? rs.pen + (size_t)b * V : logits + (size_t)b * ld;
     const float m = L.best, inv_t = 1.0f / p.temperature;
 
@@ -1024,7 +1067,7 @@ __global__ __launch_bounds__(SEL_THREADS) void select_rows_kernel(const float* _
         if (tid == 0) commit_row(st, rs, b, V, pen, s_bi);
         return;
     }
-    const float* row = pen ? rs.pen + (size_t)b * V : logits + (size_t)b * ld;
+    const float* row = pen || row_ruled(rs, b) ? rs.pen + (size_t)b * V : logits + (size_t)b * ld;
     const float m = s_best, inv_t = 1.0f / p.temperature;
     const uint32_t kmax = rs.thr[b];
     // ---- 3. inverse CDF in index order over the kept weights.  Wave w owns the contiguous segment [w seg, (w + 1) seg) and walks it 64
@@ -1126,6 +1169,22 @@ __global__ void set_row_params_kernel(RowParams* table, int32_t* own, int row, R
     table[row] = p;
     own[row] = flag;
 }
+
+// the row's image: -inf (an allowed list follows) or 0 everywhere
+__global__ __launch_bounds__(256) void rules_fill_kernel(float* __restrict__ img, int V, float v) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < V) img[i] = v;
+}
+// allowed ids back to 0 (vals == nullptr; duplicates write the same value) / img[id] += bias (distinct ids: -inf stays -inf)
+__global__ __launch_bounds__(256) void rules_scatter_kernel(float* __restrict__ img, int V, const int32_t* __restrict__ ids,
+                                                            const float* __restrict__ vals, int n) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= n) return;
+    const int id = ids[j];
+    if (id < 0 || id >= V) return;
+    img[id] = vals ? img[id] + vals[j] : 0.f;
+}
+__global__ void set_row_rules_kernel(RowRules* table, int row, RowRules r) { table[row] = r; }
 
 }  // namespace
 
@@ -1299,5 +1358,19 @@ hipError_t launch_pen_history(hipStream_t s, const int32_t* hist, const int32_t*
 
 hipError_t launch_set_row_params(hipStream_t s, RowParams* table, int32_t* own, int row, const RowParams& p, int flag) {
     hipLaunchKernelGGL(set_row_params_kernel, dim3(1), dim3(1), 0, s, table, own, row, p, flag);
+    return hipGetLastError();
+}
+
+hipError_t launch_set_row_rules(hipStream_t s, RowRules* table, float* img, int row, int V, const RowRules& r, const int32_t* allowed, int n_allowed,
+                                const int32_t* bias_ids, const float* bias_val, int n_bias) {
+    if (row < 0 || row >= DOTS_MAX_BATCH || V < 1 || r.n_stop < 0 || r.n_stop > DOTS_MAX_STOP_IDS) return hipErrorInvalidValue;
+    if (r.flags & RULE_IMG) {
+        if (!img) return hipErrorInvalidValue;
+        float* dst = img + (size_t)row * V;
+        hipLaunchKernelGGL(rules_fill_kernel, dim3((V + 255) / 256), dim3(256), 0, s, dst, V, n_allowed > 0 ? -INFINITY : 0.f);
+        if (n_allowed > 0) hipLaunchKernelGGL(rules_scatter_kernel, dim3((n_allowed + 255) / 256), dim3(256), 0, s, dst, V, allowed, (const float*)nullptr, n_allowed);
+        if (n_bias > 0) hipLaunchKernelGGL(rules_scatter_kernel, dim3((n_bias + 255) / 256), dim3(256), 0, s, dst, V, bias_ids, bias_val, n_bias);
+    }
+    hipLaunchKernelGGL(set_row_rules_kernel, dim3(1), dim3(1), 0, s, table, row, r);
     return hipGetLastError();
 }

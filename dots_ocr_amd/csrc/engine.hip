@@ -205,7 +205,17 @@ struct DotsEngine {
     uint32_t* pen_seen = nullptr;
     float* pen_logits = nullptr;
     int row_own[DOTS_MAX_BATCH] = {0};
-    int n_own = 0;                         // rows with their own parameters: > 0 switches the step to the per-row stage
+    int n_own = 0;                         // rows whose own flag is set on the device (own parameters or logit rules): > 0 = the per-row stage
+    // logit rules (dots_set_row_logit_rules): per-row table + the dense "bias or -inf" image [max_batch][V], allocated by the
+    // first row that carries rules.  rule_stage: pinned host staging of one call's id / value lists ([V + DOTS_MAX_LOGIT_BIAS] int32, then
+    // [DOTS_MAX_LOGIT_BIAS] fp32) and its device twin; rule_ev guards the pinned buffer's reuse.
+    RowRules* d_rules = nullptr;
+    float* rule_img = nullptr;
+    int32_t *rule_stage = nullptr, *rule_stage_host = nullptr;
+    hipEvent_t rule_ev = nullptr;
+    int row_rules[DOTS_MAX_BATCH] = {0};
+    int n_rules = 0;                       // rows with rules: > 0 hands the table to the per-row stage
+    int32_t h_eos[16] = {0};               // host mirror of eos_ids (the never-selectable checks of the rules)
     // log-probabilities (dots_set_row_logprobs): top_n per row (-1 = off) on the device and its host mirror; the outputs
     // ([max_batch][max_seq_len] positions) and the stage's scratch are allocated by the first row switched on
     int32_t* d_row_lp = nullptr;
@@ -235,9 +245,9 @@ struct DotsEngine {
     const int32_t* sel_now = nullptr;      // selection mask of the next select_tokens() call
     // captured decode steps, keyed by everything the capture bakes in: rows, KV splits, static batch (out_cap = row stride of
     // the output buffer) or slot mode (out_cap = 0), number of EOS ids, whether any row carries its own parameters (rowp: the per-row
-    // selection stage), whether any row returns logprobs (lp); engine-wide sampling changes drop the cache (dots_set_sampling), per-row
-    // ones live in device memory
-    struct StepGraph { int rows, splits, out_cap, n_eos, part, rowp, lp; hipGraph_t graph; hipGraphExec_t exec; };
+    // selection stage), whether any row returns logprobs (lp), whether any row carries logit rules (rules: the stage then gets their
+    // table); engine-wide sampling changes drop the cache (dots_set_sampling), per-row ones live in device memory
+    struct StepGraph { int rows, splits, out_cap, n_eos, part, rowp, lp, rules; hipGraph_t graph; hipGraphExec_t exec; };
     std::vector<StepGraph> step_graphs;
     std::vector<int> h_prompt_lens;
     int steps_done = 0;
@@ -866,7 +876,8 @@ int select_tokens(DotsEngine* e, int advance) {
                           e->lp_tok, e->lp_ids, e->lp_top, c.max_seq_len};
     if (e->n_lp > 0) CK(launch_logprob_partial(e->stream, e->d_logits, c.vocab_size, c.vocab_size, e->B_sel, ls));
     if (e->n_own > 0) {          // per-row stage for the rows with their own parameters (+ the greedy rows that follow the engine)
-        const RowSel rs{e->d_rowp, e->d_row_own, e->pen_cnt, e->pen_seen, e->pen_logits, e->d_row_thr, e->temperature > 0.f ? 0 : 1};
+        const RowSel rs{e->d_rowp, e->d_row_own, e->pen_cnt, e->pen_seen, e->pen_logits, e->d_row_thr, e->temperature > 0.f ? 0 : 1,
+                        e->n_rules > 0 ? e->d_rules : nullptr, e->rule_img};
         CK(launch_select_rows(e->stream, e->d_logits, c.vocab_size, c.vocab_size, e->B_sel, rs, e->am_val, e->am_idx, st));
         if (e->temperature > 0.f)
             CK(launch_sample_step(e->stream, e->d_logits, c.vocab_size, c.vocab_size, e->B_sel, e->temperature, e->top_p, e->seed, st, e->d_row_own));
@@ -899,17 +910,56 @@ int ensure_pen_state(DotsEngine* e) {
     const size_t rows = e->cfg.max_batch, V = e->cfg.vocab_size;
     CK(e->alloc(&e->pen_cnt, rows * V));
     CK(e->alloc(&e->pen_seen, rows * ((V + 31) / 32)));
-    CK(e->alloc(&e->pen_logits, rows * V));
+    if (!e->pen_logits) CK(e->alloc(&e->pen_logits, rows * V));      // shared with the logit rules
     drop_step_graphs(e);                                   // graphs captured before hold no penalty state
     return DOTS_OK;
 }
 
-// the row's entry back to the engine-wide setting (stream ordered)
+// table, image, shaped-logit scratch and staging of the logit rules, allocated by the first row that carries rules
+int ensure_rules_state(DotsEngine* e) {
+    if (e->d_rules) return DOTS_OK;
+    // each piece is allocated once: a call that failed half way is resumed by the next one, nothing is allocated twice
+    const size_t rows = e->cfg.max_batch, V = e->cfg.vocab_size, n_stage = V + 2 * DOTS_MAX_LOGIT_BIAS;
+    if (!e->rule_img) CK(e->alloc(&e->rule_img, rows * V));
+    if (!e->pen_logits) CK(e->alloc(&e->pen_logits, rows * V));
+    if (!e->rule_stage) CK(e->alloc(&e->rule_stage, n_stage));
+    if (!e->rule_stage_host) {
+        CK(hipHostMalloc((void**)&e->rule_stage_host, n_stage * 4, hipHostMallocDefault));
+        std::memset(e->rule_stage_host, 0, n_stage * 4);
+    }
+    if (!e->rule_ev) CK(hipEventCreateWithFlags(&e->rule_ev, hipEventDisableTiming));
+    CK(e->alloc(&e->d_rules, DOTS_MAX_BATCH));             // zeroed by alloc(): no row carries rules; set last, it is the guard above
+    drop_step_graphs(e);                                   // graphs captured before hold no shaped-logit scratch
+    return DOTS_OK;
+}
+
+// what a row without parameters of its own is selected with once the per-row stage owns it (logit rules): the engine-wide setting as it stands
+RowParams engine_row_params(const DotsEngine* e) { return RowParams{e->temperature, e->top_p, 0, 1.f, 0.f, 0.f, e->seed}; }
+
+// the row's entry back to the engine-wide setting (stream ordered); a row that still carries logit rules stays with the per-row stage
 int clear_row(DotsEngine* e, int row) {
     if (!e->row_own[row]) return DOTS_OK;
+    if (e->row_rules[row]) {
+        CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, engine_row_params(e), 1));
+        e->row_own[row] = 0;
+        return DOTS_OK;
+    }
     CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, RowParams{}, 0));
     e->row_own[row] = 0;
     e->n_own -= 1;
+    return DOTS_OK;
+}
+
+// the row's logit rules off (stream ordered)
+int clear_row_rules(DotsEngine* e, int row) {
+    if (!e->row_rules[row]) return DOTS_OK;
+    CK(launch_set_row_rules(e->stream, e->d_rules, e->rule_img, row, e->cfg.vocab_size, RowRules{}, nullptr, 0, nullptr, nullptr, 0));
+    e->row_rules[row] = 0;
+    e->n_rules -= 1;
+    if (!e->row_own[row]) {
+        CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, RowParams{}, 0));
+        e->n_own -= 1;
+    }
     return DOTS_OK;
 }
 
@@ -921,6 +971,49 @@ int check_row_params(DotsEngine* e, const DotsSamplingParams& p, RowParams* out)
     if (!(p.frequency_penalty >= -2.f && p.frequency_penalty <= 2.f)) return e->fail(DOTS_E_INVALID, "frequency_penalty must be in [-2, 2]");
     if (!(p.presence_penalty >= -2.f && p.presence_penalty <= 2.f)) return e->fail(DOTS_E_INVALID, "presence_penalty must be in [-2, 2]");
     *out = RowParams{p.temperature, p.top_p > 1.f ? 1.f : p.top_p, p.top_k, p.repetition_penalty, p.frequency_penalty, p.presence_penalty, p.seed};
+    return DOTS_OK;
+}
+
+// Validate one row's logit rules against vocabulary V and the engine's EOS ids -> the device entry.  Refused: a value out of range, a
+// duplicate bias id, and rules that could never select a token (an empty allowed list, one that the bans cover, or — with min_tokens > 0 —
+// one that the bans, the EOS ids and the stop ids cover together).
+int check_logit_rules(DotsEngine* e, const DotsLogitRules& r, int V, const int32_t* eos, int n_eos, RowRules* out) {
+    if (r.n_bias < 0 || r.n_bias > DOTS_MAX_LOGIT_BIAS || (r.n_bias && (!r.bias_ids || !r.bias_values)))
+        return e->fail(DOTS_E_INVALID, "logit rules: n_bias must be in [0, %d]", DOTS_MAX_LOGIT_BIAS);
+    if (r.n_allowed < 0 || r.n_allowed > V || (r.n_allowed && !r.allowed_ids)) return e->fail(DOTS_E_INVALID, "logit rules: n_allowed must be in [0, %d]", V);
+    if (r.allowed_ids && r.n_allowed == 0) return e->fail(DOTS_E_INVALID, "logit rules: the allowed list is empty");
+    if (r.min_tokens < 0) return e->fail(DOTS_E_INVALID, "logit rules: min_tokens must be >= 0");
+    if (r.n_stop < 0 || r.n_stop > DOTS_MAX_STOP_IDS) return e->fail(DOTS_E_INVALID, "logit rules: n_stop must be in [0, %d]", DOTS_MAX_STOP_IDS);
+    std::vector<uint8_t> mark(V, 0);                       // 1 = carries a bias, 2 = banned, 4 = allowed, 8 = EOS or stop id
+    for (int j = 0; j < r.n_bias; ++j) {
+        const int id = r.bias_ids[j];
+        const float v = r.bias_values[j];
+        if (id < 0 || id >= V) return e->fail(DOTS_E_INVALID, "logit rules: bias id %d outside [0, %d)", id, V);
+        if (mark[id] & 1) return e->fail(DOTS_E_INVALID, "logit rules: bias id %d given twice", id);
+        if (!(std::isfinite(v) || (std::isinf(v) && v < 0.f))) return e->fail(DOTS_E_INVALID, "logit rules: the bias of id %d must be finite or -inf", id);
+        mark[id] |= std::isinf(v) ? 3 : 1;
+    }
+    for (int j = 0; j < r.n_stop; ++j) {
+        if (r.stop_ids[j] < 0 || r.stop_ids[j] >= V) return e->fail(DOTS_E_INVALID, "logit rules: stop id %d outside [0, %d)", r.stop_ids[j], V);
+        mark[r.stop_ids[j]] |= 8;
+    }
+    for (int j = 0; j < n_eos; ++j) if (eos[j] >= 0 && eos[j] < V) mark[eos[j]] |= 8;
+    if (r.allowed_ids) {
+        int free_now = 0, free_early = 0;                  // allowed ids that are not banned / and neither an EOS nor a stop id
+        for (int j = 0; j < r.n_allowed; ++j) {
+            const int id = r.allowed_ids[j];
+            if (id < 0 || id >= V) return e->fail(DOTS_E_INVALID, "logit rules: allowed id %d outside [0, %d)", id, V);
+            if (!(mark[id] & 2)) { free_now += 1; free_early += (mark[id] & 8) ? 0 : 1; }
+        }
+        if (!free_now) return e->fail(DOTS_E_INVALID, "logit rules: every allowed id is banned by the bias");
+        if (r.min_tokens > 0 && !free_early) return e->fail(DOTS_E_INVALID, "logit rules: below min_tokens every allowed id is an EOS or a stop id");
+    }
+    RowRules rr{};
+    rr.flags = RULE_ON | ((r.n_bias || r.allowed_ids) ? RULE_IMG : 0) | (r.ignore_eos ? RULE_IGNORE_EOS : 0);
+    rr.min_tokens = r.min_tokens;
+    rr.n_stop = r.n_stop;
+    std::copy(r.stop_ids, r.stop_ids + r.n_stop, rr.stop);
+    *out = rr;
     return DOTS_OK;
 }
 
@@ -1256,14 +1349,14 @@ int splits_for_ctx(int max_ctx) { return decode_attn_splits(max_ctx); }
 
 // The captured decode step for (rows = e->B, splits, out_cap, e->n_eos): looked up in the cache or captured now.
 int step_graph(DotsEngine* e, int rows, int n_splits, int out_cap, hipGraphExec_t* exec, int part = 0) {
-    const int rowp = e->n_own > 0 ? 1 : 0, lp = e->n_lp > 0 ? 1 : 0;
+    const int rowp = e->n_own > 0 ? 1 : 0, lp = e->n_lp > 0 ? 1 : 0, rules = e->n_rules > 0 ? 1 : 0;
     for (auto& g : e->step_graphs)
-        if (g.rows == rows && g.splits == n_splits && g.out_cap == out_cap && g.n_eos == e->n_eos && g.part == part && g.rowp == rowp && g.lp == lp) {
+        if (g.rows == rows && g.splits == n_splits && g.out_cap == out_cap && g.n_eos == e->n_eos && g.part == part && g.rowp == rowp && g.lp == lp && g.rules == rules) {
             *exec = g.exec;
             return DOTS_OK;
         }
     if (e->step_graphs.size() >= 32) drop_step_graphs(e);
-    DotsEngine::StepGraph g{rows, n_splits, out_cap, e->n_eos, part, rowp, lp, nullptr, nullptr};
+    DotsEngine::StepGraph g{rows, n_splits, out_cap, e->n_eos, part, rowp, lp, rules, nullptr, nullptr};
     CK(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
     int r = decode_step_launches(e, n_splits, part);
     hipError_t ce = hipStreamEndCapture(e->stream, &g.graph);
@@ -1396,6 +1489,8 @@ void dots_destroy(DotsEngine* e) {
     if (e->s_vit) hipStreamDestroy(e->s_vit);
     if (e->s_dec) hipStreamDestroy(e->s_dec);
     for (void* p : e->allocs) hipFree(p);
+    if (e->rule_stage_host) hipHostFree(e->rule_stage_host);
+    if (e->rule_ev) hipEventDestroy(e->rule_ev);
     for (auto& ev : e->ev) if (ev) hipEventDestroy(ev);
     for (auto& ev : e->attn_ev) hipEventDestroy(ev);
     if (e->stream) hipStreamDestroy(e->stream);
@@ -1544,6 +1639,7 @@ int dots_generate(DotsEngine* e, const int32_t* input_ids, const int32_t* prompt
     if (n_img > 0) RET(dots_vit_forward(e, pixel_values, on_device, total_patches, grid_thw, n_img, nullptr));
     e->n_eos = n_eos;
     if (n_eos) CK(hipMemcpyAsync(e->eos_ids, eos_ids, n_eos * 4, hipMemcpyHostToDevice, s));
+    if (n_eos) std::copy(eos_ids, eos_ids + n_eos, e->h_eos);
     e->out_cap = max_new_tokens;
     RET(prefill(e, input_ids, prompt_lens, B));
 
@@ -1607,6 +1703,7 @@ int dots_set_eos(DotsEngine* e, const int32_t* eos_ids, int n_eos) {
     if (n_eos) CK(hipMemcpyAsync(e->eos_ids, eos_ids, n_eos * 4, hipMemcpyHostToDevice, e->stream));
     CK(hipStreamSynchronize(e->stream));
     e->n_eos = n_eos;
+    std::copy(eos_ids, eos_ids + n_eos, e->h_eos);
     return DOTS_OK;
 }
 
@@ -1638,6 +1735,9 @@ int dots_slots_reset(DotsEngine* e) {
     if (e->d_row_own) CK(hipMemsetAsync(e->d_row_own, 0, DOTS_MAX_BATCH * 4, s));
     std::fill(e->row_own, e->row_own + DOTS_MAX_BATCH, 0);
     e->n_own = 0;
+    if (e->d_rules) CK(hipMemsetAsync(e->d_rules, 0, DOTS_MAX_BATCH * sizeof(RowRules), s));
+    std::fill(e->row_rules, e->row_rules + DOTS_MAX_BATCH, 0);
+    e->n_rules = 0;
     if (e->d_row_lp) CK(hipMemsetAsync(e->d_row_lp, 0xFF, DOTS_MAX_BATCH * 4, s));
     std::fill(e->row_lp, e->row_lp + DOTS_MAX_BATCH, -1);
     e->n_lp = 0;
@@ -1750,6 +1850,7 @@ int dots_slot_release(DotsEngine* e, int slot) {
     if (!e->slot_mode || slot < 0 || slot >= e->cfg.max_batch || !e->slot_active[slot]) return e->fail(DOTS_E_STATE, "slot %d is not occupied", slot);
     CK(hipSetDevice(e->device));
     RET(clear_row(e, slot));
+    RET(clear_row_rules(e, slot));
     RET(set_row_lp(e, slot, -1));
     e->slot_active[slot] = 0;
     e->sel_dirty = true;
@@ -1890,7 +1991,41 @@ int dots_set_row_sampling(DotsEngine* e, int row, const DotsSamplingParams* p) {
     RET(ensure_row_table(e));
     if (rp.repetition_penalty != 1.f || rp.frequency_penalty != 0.f || rp.presence_penalty != 0.f) RET(ensure_pen_state(e));
     CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, rp, 1));
-    if (!e->row_own[row]) { e->row_own[row] = 1; e->n_own += 1; }
+    if (!e->row_own[row]) { e->row_own[row] = 1; e->n_own += e->row_rules[row] ? 0 : 1; }
+    return DOTS_OK;
+}
+
+int dots_set_row_logit_rules(DotsEngine* e, int row, const DotsLogitRules* r) {
+    if (!e) return DOTS_E_INVALID;
+    if (row < 0 || row >= e->cfg.max_batch) return e->fail(DOTS_E_INVALID, "row %d out of range [0, %d)", row, e->cfg.max_batch);
+    CK(hipSetDevice(e->device));
+    if (!r) return e->d_rules ? clear_row_rules(e, row) : DOTS_OK;
+    RowRules rr;
+    RET(check_logit_rules(e, *r, e->cfg.vocab_size, e->h_eos, e->n_eos, &rr));
+    RET(ensure_row_table(e));
+    RET(ensure_rules_state(e));
+    const int V = e->cfg.vocab_size, n_allowed = r->allowed_ids ? r->n_allowed : 0;
+    if (rr.flags & RULE_IMG) {
+        CK(hipEventSynchronize(e->rule_ev));               // the previous call's upload has left the pinned buffer (an unrecorded event: at once)
+        int32_t* h = e->rule_stage_host;
+        if (n_allowed) std::copy(r->allowed_ids, r->allowed_ids + n_allowed, h);
+        if (r->n_bias) {
+            std::copy(r->bias_ids, r->bias_ids + r->n_bias, h + V);
+            std::memcpy(h + V + DOTS_MAX_LOGIT_BIAS, r->bias_values, (size_t)r->n_bias * 4);
+        }
+        if (n_allowed) CK(hipMemcpyAsync(e->rule_stage, h, (size_t)n_allowed * 4, hipMemcpyHostToDevice, e->stream));
+        // ids and values in one copy: the whole [2][DOTS_MAX_LOGIT_BIAS] block, of which the kernel reads the first n_bias of each half
+        if (r->n_bias) CK(hipMemcpyAsync(e->rule_stage + V, h + V, (size_t)2 * DOTS_MAX_LOGIT_BIAS * 4, hipMemcpyHostToDevice, e->stream));
+        CK(hipEventRecord(e->rule_ev, e->stream));
+    }
+    CK(launch_set_row_rules(e->stream, e->d_rules, e->rule_img, row, V, rr, e->rule_stage, n_allowed, e->rule_stage + V,
+                            reinterpret_cast<const float*>(e->rule_stage + V + DOTS_MAX_LOGIT_BIAS), r->n_bias));
+    if (!e->row_own[row]) CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, engine_row_params(e), 1));
+    if (!e->row_rules[row]) {
+        e->row_rules[row] = 1;
+        e->n_rules += 1;
+        if (!e->row_own[row]) e->n_own += 1;
+    }
     return DOTS_OK;
 }
 
@@ -2404,11 +2539,17 @@ namespace {
 // dots_op_select_tokens / dots_bench_select_tokens.  mode 2 = the per-row stage once (the op); mode 0 / 1 / 2 with iters > 0 = the legacy
 // arg max pair / the legacy sampler (params[0].temperature, top_p, seed) / the per-row stage, replayed iters times between two events
 // with every row marked finished (nothing is appended), *ms = the mean time of one replay.
+// rules_host != nullptr (mode 2 only): row b carries rules_host[b] unless that entry is empty (no bias, allowed list, min_tokens, stop id or
+// ignore_eos), the engine's EOS ids are live, and n_gen_host[b] (or hist_lens - n_prompt when nullptr) is the row's generated count.
 int select_op(DotsEngine* e, const float* logits_dev, int B, int V, const DotsSamplingParams* params_host, const int32_t* hist_dev,
-              const int32_t* hist_lens_dev, int hist_stride, const int32_t* n_prompt_dev, int32_t* out_tokens_dev, int mode, int iters, float* ms) {
+              const int32_t* hist_lens_dev, int hist_stride, const int32_t* n_prompt_dev, int32_t* out_tokens_dev, int mode, int iters, float* ms,
+              const DotsLogitRules* rules_host = nullptr, const int32_t* n_gen_host = nullptr) {
     if (!e || !logits_dev || B < 1 || B > DOTS_MAX_BATCH || V < 1 || !params_host || !hist_dev || !hist_lens_dev || hist_stride < 1 || !n_prompt_dev ||
-        (!out_tokens_dev && !ms) || mode < 0 || mode > 2)
+        (!out_tokens_dev && !ms) || mode < 0 || mode > 2 || (rules_host && mode != 2) || (n_gen_host && !rules_host))
         return e ? e->fail(DOTS_E_INVALID, "bad select_tokens arguments") : DOTS_E_INVALID;
+    if (n_gen_host)
+        for (int b = 0; b < B; ++b)
+            if (n_gen_host[b] < 0 || n_gen_host[b] > hist_stride) return e->fail(DOTS_E_INVALID, "n_gen must be in [0, hist_stride]");
     std::vector<RowParams> rp(B);
     for (int b = 0; b < B; ++b) RET(check_row_params(e, params_host[b], &rp[b]));
     if (mode == 1 && !(rp[0].temperature > 0.f)) return e->fail(DOTS_E_INVALID, "the legacy sampler needs temperature > 0");
@@ -2439,8 +2580,32 @@ int select_op(DotsEngine* e, const float* logits_dev, int B, int V, const DotsSa
     StepState st;
     st.cur_tokens = cur; st.ctx_len = ctx; st.out_ids = ids; st.out_lens = lens; st.finished = fin;
     st.eos_ids = e->eos_ids; st.sel = nullptr; st.max_len = nullptr;
-    st.n_eos = 0; st.out_stride = hist_stride + 1; st.cap = hist_stride + 2; st.advance_ctx = 0;
-    const RowSel rs{tab, own_d, cnt, seen, pen, thr, 0};
+    st.n_eos = rules_host ? e->n_eos : 0; st.out_stride = hist_stride + 1; st.cap = hist_stride + 2; st.advance_ctx = 0;
+    RowRules* rtab = nullptr;
+    float* img = nullptr;
+    if (rules_host) {
+        int32_t* stage = nullptr;
+        CK(sc.get(&rtab, DOTS_MAX_BATCH));
+        CK(sc.get(&img, (size_t)B * V));
+        CK(sc.get(&stage, (size_t)V + 2 * DOTS_MAX_LOGIT_BIAS));
+        for (int b = 0; b < B; ++b) {
+            const DotsLogitRules& r = rules_host[b];
+            if (!r.n_bias && !r.allowed_ids && !r.min_tokens && !r.n_stop && !r.ignore_eos) continue;
+            RowRules rr;
+            RET(check_logit_rules(e, r, V, e->h_eos, e->n_eos, &rr));
+            const int n_allowed = r.allowed_ids ? r.n_allowed : 0;
+            if (n_allowed) CK(hipMemcpyAsync(stage, r.allowed_ids, (size_t)n_allowed * 4, hipMemcpyHostToDevice, e->stream));
+            if (r.n_bias) {
+                CK(hipMemcpyAsync(stage + V, r.bias_ids, (size_t)r.n_bias * 4, hipMemcpyHostToDevice, e->stream));
+                CK(hipMemcpyAsync(stage + V + DOTS_MAX_LOGIT_BIAS, r.bias_values, (size_t)r.n_bias * 4, hipMemcpyHostToDevice, e->stream));
+            }
+            CK(launch_set_row_rules(e->stream, rtab, img, b, V, rr, stage, n_allowed, stage + V,
+                                    reinterpret_cast<const float*>(stage + V + DOTS_MAX_LOGIT_BIAS), r.n_bias));
+            CK(hipStreamSynchronize(e->stream));           // the caller's lists and the staging buffer are free again
+        }
+        if (n_gen_host) CK(hipMemcpyAsync(lens, n_gen_host, B * 4, hipMemcpyHostToDevice, e->stream));
+    }
+    const RowSel rs{tab, own_d, cnt, seen, pen, thr, 0, rtab, img};
     auto run = [&]() -> hipError_t {
         if (mode == 0) return launch_argmax_step(e->stream, logits_dev, V, V, B, pval, pidx, st);
         if (mode == 1) return launch_sample_step(e->stream, logits_dev, V, V, B, rp[0].temperature, rp[0].top_p, rp[0].seed, st);
@@ -2483,6 +2648,20 @@ int dots_bench_select_tokens(DotsEngine* e, const float* logits_dev, int B, int 
                              const int32_t* hist_lens_dev, int hist_stride, const int32_t* n_prompt_dev, int mode, int iters, float* ms_out) {
     if (!ms_out || iters < 1) return e ? e->fail(DOTS_E_INVALID, "bad bench_select_tokens arguments") : DOTS_E_INVALID;
     return select_op(e, logits_dev, B, V, params_host, hist_dev, hist_lens_dev, hist_stride, n_prompt_dev, nullptr, mode, iters, ms_out);
+}
+
+int dots_op_select_tokens_rules(DotsEngine* e, const float* logits_dev, int B, int V, const DotsSamplingParams* params_host, const DotsLogitRules* rules_host,
+                                const int32_t* n_gen_host, const int32_t* hist_dev, const int32_t* hist_lens_dev, int hist_stride,
+                                const int32_t* n_prompt_dev, int32_t* out_tokens_dev) {
+    if (!out_tokens_dev || !rules_host) return e ? e->fail(DOTS_E_INVALID, "bad select_tokens arguments") : DOTS_E_INVALID;
+    return select_op(e, logits_dev, B, V, params_host, hist_dev, hist_lens_dev, hist_stride, n_prompt_dev, out_tokens_dev, 2, 0, nullptr, rules_host, n_gen_host);
+}
+
+int dots_bench_select_tokens_rules(DotsEngine* e, const float* logits_dev, int B, int V, const DotsSamplingParams* params_host, const DotsLogitRules* rules_host,
+                                   const int32_t* n_gen_host, const int32_t* hist_dev, const int32_t* hist_lens_dev, int hist_stride,
+                                   const int32_t* n_prompt_dev, int iters, float* ms_out) {
+    if (!ms_out || iters < 1 || !rules_host) return e ? e->fail(DOTS_E_INVALID, "bad bench_select_tokens arguments") : DOTS_E_INVALID;
+    return select_op(e, logits_dev, B, V, params_host, hist_dev, hist_lens_dev, hist_stride, n_prompt_dev, nullptr, 2, iters, ms_out, rules_host, n_gen_host);
 }
 
 }  // extern "C"

@@ -126,14 +126,24 @@ struct RowParams { float temperature, top_p; int32_t top_k; float repetition_pen
 // Device state of the stage.  params / own: [DOTS_MAX_BATCH]; a row with own[b] == 0 follows the engine-wide setting: the stage selects it
 // only when legacy_greedy != 0 (arg max), otherwise launch_sample_step(.., own) does.  cnt [rows][V] int32 (generated-token counts),
 // seen [rows][ceil(V / 32)] (prompt-presence bits) and pen [rows][V] fp32 (penalised logits, scratch) are nullptr until a penalty is used.
+// Logit rules of a row.  flags: RULE_ON = the row carries rules (it always has own[b] != 0 too), RULE_IMG = its row of the
+// dense "bias or -inf" image is live (a bias or an allowed list), RULE_IGNORE_EOS.  While the row has generated fewer than min_tokens
+// tokens every engine EOS id and every stop id is -inf; a stop id finishes the row as an EOS id does.
+#ifndef DOTS_MAX_STOP_IDS
+#define DOTS_MAX_STOP_IDS 16
+#endif
+enum { RULE_ON = 1, RULE_IMG = 2, RULE_IGNORE_EOS = 4 };
+struct RowRules { int32_t flags, min_tokens, n_stop, stop[DOTS_MAX_STOP_IDS]; };
 struct RowSel {
     const RowParams* params;
     const int32_t* own;
     int32_t* cnt;
     const uint32_t* seen;
-    float* pen;
+    float* pen;                 // [rows][V] scratch: the shaped (ruled and / or penalised) logits of the rows that have any
     uint32_t* thr;              // [DOTS_MAX_BATCH] scratch: the largest key a sampled row keeps (decode.hip)
     int legacy_greedy;
+    const RowRules* rules;      // [DOTS_MAX_BATCH], or nullptr = no row of this launch carries rules
+    const float* rule_img;      // [rows][V] fp32: the bias of a token, -inf for a banned / not allowed one, 0 elsewhere
 };
 // pval / pidx: ARGMAX_CHUNKS (64) partials per row, as launch_argmax_step
 hipError_t launch_select_rows(hipStream_t s, const float* logits, int V, int ld, int B, const RowSel& rs, float* pval, int32_t* pidx, const StepState& st);
@@ -147,6 +157,11 @@ hipError_t launch_pen_history(hipStream_t s, const int32_t* hist, const int32_t*
                               int32_t* cnt, uint32_t* seen, int32_t* out_lens);
 // table[row] = p, own[row] = flag, in stream order
 hipError_t launch_set_row_params(hipStream_t s, RowParams* table, int32_t* own, int row, const RowParams& p, int flag);
+// Logit rules of one row, in stream order: its image row (when r.flags has RULE_IMG) = -inf everywhere but the n_allowed ids of allowed
+// (n_allowed == 0: 0 everywhere), plus bias_val[j] at bias_ids[j] (n_bias distinct ids); then table[row] = r.  allowed / bias_ids /
+// bias_val are device arrays of ids in [0, V).
+hipError_t launch_set_row_rules(hipStream_t s, RowRules* table, float* img, int row, int V, const RowRules& r, const int32_t* allowed, int n_allowed,
+                                const int32_t* bias_ids, const float* bias_val, int n_bias);
 
 // ---- logprobs.hip: log-probabilities of the raw logits of every selected row
 #ifndef DOTS_MAX_TOP_LOGPROBS

@@ -105,6 +105,116 @@ class SamplingParams:
                                    self.presence_penalty, self.seed)
 
 
+MAX_LOGIT_BIAS = 1024                        # DOTS_MAX_LOGIT_BIAS: (id, value) pairs per row
+MAX_STOP_IDS = 16                            # DOTS_MAX_STOP_IDS: stop ids per row
+
+
+class CDotsLogitRules(C.Structure):
+    _fields_ = [
+        ("bias_ids", C.POINTER(C.c_int32)), ("bias_values", C.POINTER(C.c_float)), ("n_bias", C.c_int32),
+        ("allowed_ids", C.POINTER(C.c_int32)), ("n_allowed", C.c_int32), ("min_tokens", C.c_int32),
+        ("stop_ids", C.c_int32 * MAX_STOP_IDS), ("n_stop", C.c_int32), ("ignore_eos", C.c_int32),
+    ]
+
+
+def _id_tuple(name, ids):
+    out = []
+    for v in ids:
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError(f"{name} must hold integer token ids, got {v!r}")
+        if not 0 <= int(v) < 2 ** 31:
+            raise ValueError(f"{name} must hold token ids >= 0, got {v!r}")
+        out.append(int(v))
+    return tuple(out)
+
+
+@dataclass(frozen=True)
+class LogitRules:
+    """Logit rules of one request / decode row (include/dots_ocr_hip.h DotsLogitRules).
+
+    bias: {id: value} or (id, value) pairs, at most MAX_LOGIT_BIAS, value finite or -inf (a ban), no id twice; allowed: None or a non-empty
+    id list (every other id is -inf); min_tokens: EOS and stop ids are -inf while fewer tokens exist; stop: at most MAX_STOP_IDS ids that
+    finish this row only; ignore_eos: the engine's EOS ids do not finish it.  vocab_size (optional) bounds every id.  Rules that could
+    never select a token raise ValueError: an allowed list the bans cover, or — with min_tokens > 0 — one that bans, stop ids and
+    eos_ids (optional: the engine's EOS ids the row will run under) cover together; the engine repeats the check with its own EOS ids."""
+    bias: tuple = ()
+    allowed: Optional[tuple] = None
+    min_tokens: int = 0
+    stop: tuple = ()
+    ignore_eos: bool = False
+    vocab_size: Optional[int] = None
+    eos_ids: Optional[tuple] = None
+
+    def __post_init__(self):
+        pairs = list(self.bias.items()) if isinstance(self.bias, dict) else [tuple(x) for x in self.bias]
+        if len(pairs) > MAX_LOGIT_BIAS:
+            raise ValueError(f"at most {MAX_LOGIT_BIAS} bias entries, got {len(pairs)}")
+        ids = _id_tuple("bias", [p[0] for p in pairs])
+        if len(set(ids)) != len(ids):
+            raise ValueError("bias holds an id twice")
+        vals = []
+        for _, v in pairs:
+            f = C.c_float(float(v)).value if math.isfinite(float(v)) else float(v)
+            if math.isnan(f) or f == math.inf:
+                raise ValueError(f"a bias value must be finite or -inf, got {v!r}")
+            vals.append(f)
+        allowed = None
+        if self.allowed is not None:
+            allowed = tuple(sorted(set(_id_tuple("allowed", self.allowed))))
+            if not allowed:
+                raise ValueError("allowed must be None or a non-empty id list")
+        stop = _id_tuple("stop", self.stop)
+        if len(stop) > MAX_STOP_IDS:
+            raise ValueError(f"at most {MAX_STOP_IDS} stop ids, got {len(stop)}")
+        if isinstance(self.min_tokens, bool) or int(self.min_tokens) != self.min_tokens or not 0 <= int(self.min_tokens) < 2 ** 31:
+            raise ValueError(f"min_tokens must be an integer >= 0, got {self.min_tokens!r}")
+        if self.vocab_size is not None:
+            V = int(self.vocab_size)
+            for name, seq in (("bias", ids), ("allowed", allowed or ()), ("stop", stop)):
+                for t in seq:
+                    if t >= V:
+                        raise ValueError(f"{name} id {t} outside [0, {V})")
+        if allowed is not None:
+            banned = {t for t, v in zip(ids, vals) if v == -math.inf}
+            free = [t for t in allowed if t not in banned]
+            if not free:
+                raise ValueError("every allowed id is banned by the bias: nothing could be selected")
+            held = set(stop) | set(int(t) for t in (self.eos_ids or ()))
+            if int(self.min_tokens) > 0 and all(t in held for t in free):
+                raise ValueError("below min_tokens every allowed id is an EOS or a stop id: nothing could be selected")
+        object.__setattr__(self, "bias", tuple(zip(ids, vals)))
+        object.__setattr__(self, "allowed", allowed)
+        object.__setattr__(self, "min_tokens", int(self.min_tokens))
+        object.__setattr__(self, "stop", stop)
+        object.__setattr__(self, "ignore_eos", bool(self.ignore_eos))
+        object.__setattr__(self, "vocab_size", None if self.vocab_size is None else int(self.vocab_size))
+        object.__setattr__(self, "eos_ids", None if self.eos_ids is None else tuple(int(t) for t in self.eos_ids))
+
+    @property
+    def empty(self) -> bool:
+        """no rule at all: the row behaves as one without LogitRules"""
+        return not self.bias and self.allowed is None and self.min_tokens == 0 and not self.stop and not self.ignore_eos
+
+    def to_c(self) -> CDotsLogitRules:
+        """The C struct; the arrays it points to are kept alive on the returned object (`_keep`)."""
+        ids = np.asarray([t for t, _ in self.bias], np.int32)
+        vals = np.asarray([v for _, v in self.bias], np.float32)
+        allowed = None if self.allowed is None else np.asarray(self.allowed, np.int32)
+        c = CDotsLogitRules()
+        c.bias_ids = _i32p(ids) if len(ids) else None
+        c.bias_values = vals.ctypes.data_as(C.POINTER(C.c_float)) if len(ids) else None
+        c.n_bias = len(ids)
+        c.allowed_ids = _i32p(allowed) if allowed is not None else None
+        c.n_allowed = 0 if allowed is None else len(allowed)
+        c.min_tokens = self.min_tokens
+        for j, t in enumerate(self.stop):
+            c.stop_ids[j] = t
+        c.n_stop = len(self.stop)
+        c.ignore_eos = int(self.ignore_eos)
+        c._keep = (ids, vals, allowed)
+        return c
+
+
 class DotsEngineError(RuntimeError):
     pass
 
@@ -178,6 +288,9 @@ def _prototypes(lib):
         "dots_op_dec_lmhead": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, f32, i32]),
         "dots_op_select_tokens": (i32, [vp, vp, i32, i32, P(CDotsSamplingParams), vp, vp, i32, vp, vp]),
         "dots_bench_select_tokens": (i32, [vp, vp, i32, i32, P(CDotsSamplingParams), vp, vp, i32, vp, i32, i32, P(f32)]),
+        "dots_set_row_logit_rules": (i32, [vp, i32, P(CDotsLogitRules)]),
+        "dots_op_select_tokens_rules": (i32, [vp, vp, i32, i32, P(CDotsSamplingParams), P(CDotsLogitRules), P(i32), vp, vp, i32, vp, vp]),
+        "dots_bench_select_tokens_rules": (i32, [vp, vp, i32, i32, P(CDotsSamplingParams), P(CDotsLogitRules), P(i32), vp, vp, i32, vp, i32, P(f32)]),
         "dots_set_row_logprobs": (i32, [vp, i32, i32]),
         "dots_row_logprobs": (i32, [vp, i32, i32, i32, P(f32), P(i32), P(f32), P(i32)]),
         "dots_op_logprobs": (i32, [vp, vp, i32, i32, i32, P(i32), vp, vp, vp, vp]),
@@ -205,6 +318,7 @@ EXPORTED_SYMBOLS = [
     "dots_set_kv_scales", "dots_debug_read_kv", "dots_op_dec_qkv_kv8", "dots_op_decode_attn_kv8",
     "dots_set_row_sampling", "dots_op_select_tokens", "dots_bench_select_tokens",
     "dots_set_row_logprobs", "dots_row_logprobs", "dots_op_logprobs", "dots_bench_logprobs",
+    "dots_set_row_logit_rules", "dots_op_select_tokens_rules", "dots_bench_select_tokens_rules",
 ]
 
 MAX_TOP_LOGPROBS = 20                        # DOTS_MAX_TOP_LOGPROBS: top entries kept per position
@@ -460,6 +574,50 @@ class Engine:
         ms = C.c_float()
         self._ck(self.lib.dots_bench_select_tokens(self.h, logits, int(B), int(V), arr, hist, hist_lens, int(hist_stride), n_prompt, int(mode),
                                                    int(iters), C.byref(ms)), "dots_bench_select_tokens")
+        return float(ms.value)
+
+    def set_row_logit_rules(self, row: int, rules: Optional["LogitRules"]):
+        """Give decode row `row` (a slot, or sequence `row` of a static batch) LogitRules from the next selected token on (set, then
+        prefill); None or empty rules clear them.  Captured decode graphs are kept; slot release and slots_reset clear the row.  A row
+        with rules but no SamplingParams of its own is selected with the engine-wide temperature / top_p / seed as they stand now
+        (DESIGN §6.3)."""
+        if rules is None or (isinstance(rules, LogitRules) and rules.empty):
+            self._ck(self.lib.dots_set_row_logit_rules(self.h, int(row), None), "dots_set_row_logit_rules")
+            return
+        if not isinstance(rules, LogitRules):
+            raise TypeError("rules must be a LogitRules or None")
+        c = rules.to_c()
+        self._ck(self.lib.dots_set_row_logit_rules(self.h, int(row), C.byref(c)), "dots_set_row_logit_rules")
+
+    @staticmethod
+    def _rules_array(rules: Sequence[Optional["LogitRules"]]):
+        cs = [(r if r is not None else LogitRules()).to_c() for r in rules]
+        arr = (CDotsLogitRules * len(cs))(*cs)
+        arr._keep = cs
+        return arr
+
+    def select_tokens_rules(self, logits, B: int, V: int, params: Sequence[SamplingParams], rules: Sequence[Optional["LogitRules"]],
+                            n_gen: Optional[Sequence[int]], hist, hist_lens, hist_stride: int, n_prompt, out_tokens):
+        """select_tokens with LogitRules per row (None / empty = a row without rules) and each row's generated count n_gen (None:
+        hist_lens - n_prompt); the engine's EOS ids are live (dots_op_select_tokens_rules)."""
+        if len(params) != B or len(rules) != B:
+            raise ValueError("one SamplingParams and one LogitRules (or None) per row")
+        arr = (CDotsSamplingParams * B)(*[p.to_c() for p in params])
+        rarr = self._rules_array(rules)
+        ng = None if n_gen is None else np.ascontiguousarray(n_gen, dtype=np.int32)
+        self._ck(self.lib.dots_op_select_tokens_rules(self.h, logits, int(B), int(V), arr, rarr, None if ng is None else _i32p(ng), hist, hist_lens,
+                                                      int(hist_stride), n_prompt, out_tokens), "dots_op_select_tokens_rules")
+
+    def bench_select_tokens_rules(self, logits, B: int, V: int, params: Sequence[SamplingParams], rules: Sequence[Optional["LogitRules"]],
+                                  n_gen: Optional[Sequence[int]], hist, hist_lens, hist_stride: int, n_prompt, iters: int) -> float:
+        """mean ms of one per-row selection stage with these rules"""
+        arr = (CDotsSamplingParams * B)(*[p.to_c() for p in params])
+        rarr = self._rules_array(rules)
+        ng = None if n_gen is None else np.ascontiguousarray(n_gen, dtype=np.int32)
+        ms = C.c_float()
+        self._ck(self.lib.dots_bench_select_tokens_rules(self.h, logits, int(B), int(V), arr, rarr, None if ng is None else _i32p(ng), hist,
+                                                         hist_lens, int(hist_stride), n_prompt, int(iters), C.byref(ms)),
+                 "dots_bench_select_tokens_rules")
         return float(ms.value)
 
     def set_row_logprobs(self, row: int, top_n: Optional[int]):

@@ -131,7 +131,8 @@ class DotsOcrHipForCausalLM:
                  max_new_tokens: int = 128, do_sample: Optional[bool] = None, temperature: Optional[float] = None,
                  top_p: Optional[float] = None, seed: int = 0, eos_token_id=None, pad_token_id=None, continuous: Optional[bool] = None,
                  top_k: Optional[int] = None, repetition_penalty: Optional[float] = None, frequency_penalty: Optional[float] = None,
-                 presence_penalty: Optional[float] = None, **_):
+                 presence_penalty: Optional[float] = None, logit_bias=None, allowed_token_ids=None, min_tokens: int = 0,
+                 stop_token_ids=None, ignore_eos: bool = False, **_):
         """HF-shaped generate.  do_sample / temperature / top_p default to the checkpoint's generation_config.json (greedy when it
         is absent); with sampling on, tokens are drawn on the GPU from softmax(logits / temperature) restricted to the top_p
         nucleus, reproducibly from `seed`.  Returns LongTensor
@@ -144,7 +145,11 @@ class DotsOcrHipForCausalLM:
         top_k / repetition_penalty (HF) and frequency_penalty / presence_penalty (OpenAI), when given with a non-neutral value, switch
         to per-row selection (Engine.set_row_sampling): sequence b is drawn with seed + b, whatever row or batch it lands
         in; the rows are cleared afterwards.  These keys are deliberately not read from generation_config.json: that would change the
-        default output of existing checkpoints."""
+        default output of existing checkpoints.
+
+        logit_bias ({id: value}, -inf = a ban) / allowed_token_ids / min_tokens / stop_token_ids / ignore_eos (vLLM SamplingParams) give
+        every sequence the same LogitRules (Engine.set_row_logit_rules, DESIGN §6.3) and switch to per-row selection in the same way;
+        a stop id ends its sequence as an EOS does and is kept as its last token."""
         import dataclasses
         import torch
         t_eff, p_eff = resolve_sampling(self.generation_config, do_sample, temperature, top_p)
@@ -158,6 +163,19 @@ class DotsOcrHipForCausalLM:
 
             def row_sp(b):
                 return dataclasses.replace(base, seed=int(seed) + b)
+        rules = None
+        if logit_bias or allowed_token_ids is not None or int(min_tokens or 0) > 0 or stop_token_ids or ignore_eos:
+            from .engine import LogitRules, SamplingParams
+            rules = LogitRules(bias={int(k): float(v) for k, v in dict(logit_bias or {}).items()}, allowed=allowed_token_ids,
+                               min_tokens=int(min_tokens or 0), stop=tuple(stop_token_ids or ()), ignore_eos=bool(ignore_eos),
+                               vocab_size=self.config.vocab_size,
+                               eos_ids=self.config.eos_token_ids if eos_token_id is None else
+                               ([eos_token_id] if isinstance(eos_token_id, int) else list(eos_token_id)))
+            if row_sp is None:                   # a sampled row with rules draws with seed + b as the penalised rows do
+                base = SamplingParams(temperature=t_eff, top_p=p_eff, seed=seed)
+
+                def row_sp(b):
+                    return dataclasses.replace(base, seed=int(seed) + b)
         ids = input_ids.detach().cpu().numpy()
         B, T = ids.shape
         mask = attention_mask.detach().cpu().numpy().astype(bool) if attention_mask is not None else np.ones_like(ids, bool)
@@ -212,9 +230,9 @@ class DotsOcrHipForCausalLM:
                     lo, hi = int(patch_off[img_of_seq[b][0]]), int(patch_off[img_of_seq[b][-1] + 1])
                     pix = pv_dev[lo:hi] if pv_dev is not None else pv_host[lo:hi]
                     reqs.append(Request(prompts[b], pix, grid[img_of_seq[b][0]:img_of_seq[b][-1] + 1], max_new_tokens,
-                                        sampling=row_sp(b) if row_sp else None))
+                                        sampling=row_sp(b) if row_sp else None, rules=rules))
                 else:
-                    reqs.append(Request(prompts[b], None, None, max_new_tokens, sampling=row_sp(b) if row_sp else None))
+                    reqs.append(Request(prompts[b], None, None, max_new_tokens, sampling=row_sp(b) if row_sp else None, rules=rules))
             outs = ContinuousBatcher(self.engine, eos_ids=eos).run(reqs)
             for b, o in enumerate(outs):
                 new_tokens[b, :len(o)] = o
@@ -240,9 +258,13 @@ class DotsOcrHipForCausalLM:
         rows_set = 0                             # rows given per-row parameters (cleared on the way out)
         try:
             for k, sl in enumerate(plan):
+                if rules is not None:
+                    self.engine.set_eos(eos)         # the engine checks a row's rules against the EOS ids of THIS call
                 if row_sp:
                     for j, b in enumerate(sl):
                         self.engine.set_row_sampling(j, row_sp(b))
+                        if rules is not None:
+                            self.engine.set_row_logit_rules(j, rules)
                     rows_set = max(rows_set, len(sl))
                 lens = np.array([len(prompts[b]) for b in sl], np.int32)
                 packed = np.concatenate([prompts[b] for b in sl])
@@ -272,6 +294,8 @@ class DotsOcrHipForCausalLM:
         finally:
             for j in range(rows_set):
                 self.engine.set_row_sampling(j, None)
+                if rules is not None:
+                    self.engine.set_row_logit_rules(j, None)
         full = np.concatenate([ids.astype(np.int64), new_tokens[:, :n_max]], axis=1)    # HF stops at the longest sequence
         res = torch.from_numpy(full)
         return res.to(input_ids.device) if input_ids.is_cuda else res

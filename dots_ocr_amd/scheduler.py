@@ -18,6 +18,10 @@ from typing import Deque, Dict, Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 
 
+class RequestRejected(ValueError):
+    """The engine refused a request's own per-row parameters (sampling, logprobs, logit rules) at admission."""
+
+
 @dataclass
 class Request:
     input_ids: np.ndarray                       # int32 [T]; image pad tokens already expanded (processor output)
@@ -28,6 +32,7 @@ class Request:
     sampling: Optional[object] = None           # engine.SamplingParams of this request, or None = the engine-wide setting
     logprobs: Optional[int] = None              # top_n (0..20) of per-token log-probabilities to return, None = off; a finished request
                                                 # then carries logprobs_out = Engine.row_logprobs(slot, its token count)
+    rules: Optional[object] = None              # engine.LogitRules of this request (bias, allowed ids, min_tokens, stop ids, ignore_eos), or None
 
     def n_patches(self) -> int:
         if self.grid_thw is None:
@@ -74,7 +79,10 @@ class ContinuousBatcher:
         self._last_lens: Dict[int, int] = {}                     # slot -> tokens generated as of the last poll
         self._row_params: Dict[int, object] = {}                 # slot -> the SamplingParams set on it (engine.set_row_sampling)
         self._row_lp: Dict[int, int] = {}                        # slot -> the logprobs top_n set on it (engine.set_row_logprobs)
+        self._row_rules: Dict[int, object] = {}                  # slot -> the LogitRules set on it (engine.set_row_logit_rules)
         self.kv_truncated = 0                                    # sequences ended early by a dry KV pool (finish reason "kv_pool_exhausted")
+        self._rejected: List[Tuple[int, Request]] = []           # requests whose own parameters the engine refused (reported by step())
+        self.eos_ids = tuple(int(t) for t in eos_ids)
         engine.set_eos(list(eos_ids))
         if hasattr(engine, "slots_reset"):           # start from an empty engine: no occupied slot, every KV page in the pool
             engine.slots_reset()                     # (a static batch or a failed run may have left both behind)
@@ -93,6 +101,17 @@ class ContinuousBatcher:
             raise ValueError(f"prompt of {ids.shape[0]} tokens exceeds max_prefill_tokens={self.max_prefill_tokens}")
         if req.n_patches() > self.max_patches:
             raise ValueError(f"request has {req.n_patches()} vision patches, more than max_patches={self.max_patches}")
+        if req.rules is not None and not hasattr(self.engine, "set_row_logit_rules"):
+            raise ValueError("this engine cannot honour logit rules (no set_row_logit_rules)")
+        if req.rules is not None and hasattr(req.rules, "eos_ids"):
+            # what the engine will check at admission, checked here against the EOS ids and the vocabulary this batcher runs under: rules
+            # that could never select a token are refused before the request is queued, where it fails alone
+            import dataclasses
+            try:
+                dataclasses.replace(req.rules, eos_ids=self.eos_ids,
+                                    vocab_size=getattr(getattr(self.engine, "cfg", None), "vocab_size", req.rules.vocab_size))
+            except ValueError as e:
+                raise RequestRejected(str(e))
         req.input_ids = ids
         # like HF generate, stop at the context capacity instead of failing
         req.max_new_tokens = max(1, min(int(req.max_new_tokens), self.max_seq_len - ids.shape[0]))
@@ -109,7 +128,7 @@ class ContinuousBatcher:
 
     @property
     def idle(self) -> bool:
-        return not self.pending and not self.running and not self._ahead
+        return not self.pending and not self.running and not self._ahead and not self._rejected
 
     def free_slots(self) -> List[int]:
         return [s for s in range(self.n_slots) if s not in self.running]
@@ -172,30 +191,49 @@ class ContinuousBatcher:
         host = [p.detach().cpu().numpy() if hasattr(p, "detach") else np.asarray(p) for p in pvs]
         return np.concatenate(host).astype(np.float32, copy=False), grid, False, None
 
-    def _prefill(self, group):
+    def _clear_rows(self, slots):
+        """no per-row entry stays on these (free) slots: it would keep the per-row stage on"""
+        for s in slots:
+            if self._row_params.pop(s, None) is not None:
+                self.engine.set_row_sampling(s, None)
+            if self._row_lp.pop(s, None) is not None:
+                self.engine.set_row_logprobs(s, None)
+            if self._row_rules.pop(s, None) is not None:
+                self.engine.set_row_logit_rules(s, None)
+
+    def _set_rows(self, s, r):
+        """per-row parameters of request r on slot s; they apply from the first token the prefill selects"""
+        if r.sampling is not None:
+            self._row_params[s] = r.sampling         # recorded first: a call that raises half way is still cleared
+            self.engine.set_row_sampling(s, r.sampling)
+        elif self._row_params.pop(s, None) is not None:
+            self.engine.set_row_sampling(s, None)
+        if r.logprobs is not None:                   # logprobs likewise, the prefill's token included
+            self._row_lp[s] = r.logprobs
+            self.engine.set_row_logprobs(s, r.logprobs)
+        elif self._row_lp.pop(s, None) is not None:
+            self.engine.set_row_logprobs(s, None)
+        if r.rules is not None:                      # logit rules likewise
+            self._row_rules[s] = r.rules
+            self.engine.set_row_logit_rules(s, r.rules)
+        elif self._row_rules.pop(s, None) is not None:
+            self.engine.set_row_logit_rules(s, None)
+
+    def _prefill(self, group, rows_set: bool = False):
         # image rows are consumed in packed order, so sequences with images keep their relative order: pack the group as is
         slots = [s for s, _, _ in group]
         lens = [int(r.input_ids.shape[0]) for _, _, r in group]
         caps = [int(r.max_new_tokens) for _, _, r in group]
-        for s, _, r in group:                        # per-row parameters apply from the first token the prefill selects
-            if r.sampling is not None:
-                self.engine.set_row_sampling(s, r.sampling)
-                self._row_params[s] = r.sampling
-            elif self._row_params.pop(s, None) is not None:
-                self.engine.set_row_sampling(s, None)
-            if r.logprobs is not None:               # logprobs likewise, the prefill's token included
-                self.engine.set_row_logprobs(s, r.logprobs)
-                self._row_lp[s] = r.logprobs
-            elif self._row_lp.pop(s, None) is not None:
-                self.engine.set_row_logprobs(s, None)
+        for s, _, r in ([] if rows_set else group):       # a prefetched group: its tower has run, so it goes in (or fails) as a whole
+            try:
+                self._set_rows(s, r)
+            except Exception:
+                self._clear_rows(slots)              # nothing of this group stays behind; the caller puts the group back in the queue
+                raise
         try:
             self.engine.slots_prefill(slots, np.concatenate([r.input_ids for _, _, r in group]), lens, caps)
         except Exception:
-            for s in slots:                          # the slots stay free: leave no entry on them (it would keep the per-row stage on)
-                if self._row_params.pop(s, None) is not None:
-                    self.engine.set_row_sampling(s, None)
-                if self._row_lp.pop(s, None) is not None:
-                    self.engine.set_row_logprobs(s, None)
+            self._clear_rows(slots)                  # the slots stay free
             raise
         for s, rid, r in group:
             self.running[s] = (rid, r)
@@ -204,13 +242,26 @@ class ContinuousBatcher:
         self.admissions += 1
 
     def _admit(self, group):
-        with_img = [(rid, r) for _, rid, r in group if r.n_patches() > 0]
+        # per-row parameters first, before the tower runs: a request whose own parameters the engine refuses (submit() and the server
+        # validate what they can see; this is the engine's last word) is rejected alone — the rest of the group goes on without it
+        kept = []
+        for s, rid, r in group:
+            try:
+                self._set_rows(s, r)
+                kept.append((s, rid, r))
+            except Exception as e:
+                self._clear_rows([s])
+                r.error = RequestRejected(str(e))
+                self._rejected.append((rid, r))
+        if not kept:
+            return
+        with_img = [(rid, r) for _, rid, r in kept if r.n_patches() > 0]
         if with_img:
             pv, grid, on_dev, keep = self._pixels(with_img)
             self.engine.vit_forward(pv, grid, on_device=on_dev)
             if on_dev:
                 self.engine.synchronize()            # `keep` may be a temporary
-        self._prefill(group)
+        self._prefill(kept, rows_set=True)
 
     # ------------------------------------------------------------------ look-ahead (prefetched towers)
     def _admit_ahead(self) -> bool:
@@ -311,7 +362,13 @@ class ContinuousBatcher:
         return done
 
     def step(self) -> List[Tuple[int, Request, np.ndarray]]:
-        """Admit what fits, run one decode chunk, return the requests that finished: (id, request, new token ids)."""
+        """Admit what fits, run one decode chunk, return the requests that finished: (id, request, new token ids).  A request the engine
+        refused at admission comes back at once with no tokens and `request.error` set (RequestRejected)."""
+        out = self._step()
+        rejected, self._rejected = self._rejected, []
+        return [(rid, r, np.zeros(0, np.int32)) for rid, r in rejected] + out
+
+    def _step(self) -> List[Tuple[int, Request, np.ndarray]]:
         if self._ahead:                              # a prefetched group waits for its slots: nothing may overtake it
             admitted = self._admit_ahead()
         else:
@@ -326,7 +383,7 @@ class ContinuousBatcher:
                     # the prefetched group, finds every request (server.py fails their futures; a lost request would hang its HTTP call)
                     for s, _, _ in group:
                         self.running.pop(s, None)
-                    self.pending.extendleft(reversed([(rid, r) for _, rid, r in group]))
+                    self.pending.extendleft(reversed([(rid, r) for _, rid, r in group if getattr(r, "error", None) is None]))
                     raise
         self._look_ahead()
         if admitted:
@@ -334,6 +391,8 @@ class ContinuousBatcher:
             if done:
                 return done
         if not self.running:
+            if self._rejected:                       # the whole group was refused: report it, admit the next one on the next step
+                return []
             if self._ahead:                          # nothing runs, so every slot and page is free: the group fits by construction
                 raise RuntimeError("a prefetched group could not be admitted into an empty engine")
             if self.pending:                         # nothing runs, nothing could be admitted: it never will be
@@ -371,7 +430,11 @@ class ContinuousBatcher:
     def run(self, requests: Iterable[Request]) -> List[np.ndarray]:
         ids = [self.submit(r) for r in requests]
         out: Dict[int, np.ndarray] = {}
+        refused = None
         while not self.idle:
-            for rid, _, toks in self.step():
+            for rid, req, toks in self.step():
                 out[rid] = toks
+                refused = refused or getattr(req, "error", None)
+        if refused is not None:                      # every other request has finished
+            raise refused
         return [out[i] for i in ids]

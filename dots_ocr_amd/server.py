@@ -15,6 +15,8 @@ carries its own sampling parameters on its slot and one running set serves them 
 other parameters wait for the running set to drain, and a request that asks for top_k or a penalty is refused (400).
 `logprobs` / `top_logprobs` return the OpenAI `choices[0].logprobs` object (raw-logit log-probabilities, Engine.set_row_logprobs); they
 need continuous batching on an engine that has them, else 400.
+`logit_bias`, `allowed_token_ids`, `min_tokens`, `stop_token_ids` and `ignore_eos` travel as the request's LogitRules on its slot
+(Engine.set_row_logit_rules); a worker that cannot honour them (static batching, an engine without the call) answers 400.
 `BatchingWorker` (static batches through `model.generate`) remains for model objects without engine slots.
 """
 from __future__ import annotations
@@ -29,12 +31,13 @@ from concurrent.futures import Future
 from typing import List, Optional
 
 from .image_utils import fetch_image
+from .scheduler import RequestRejected
 from .processing import ASSISTANT, END_USER, IMG_END, IMG_PAD, IMG_START, USER
 
 
 class _Job:
     __slots__ = ("image", "text", "max_tokens", "temperature", "top_p", "top_k", "repetition_penalty", "frequency_penalty",
-                 "presence_penalty", "seed", "logprobs", "future")
+                 "presence_penalty", "seed", "logprobs", "rules", "future")
 
     def __init__(self, image, text, max_tokens, temperature, top_p, top_k=0, repetition_penalty=1.0, frequency_penalty=0.0,
                  presence_penalty=0.0, seed=None, logprobs=None):
@@ -42,6 +45,7 @@ class _Job:
         self.top_k, self.repetition_penalty = top_k, repetition_penalty
         self.frequency_penalty, self.presence_penalty, self.seed = frequency_penalty, presence_penalty, seed
         self.logprobs = logprobs                    # top_logprobs (0..20) when the request asked for logprobs, else None
+        self.rules = None                           # engine.LogitRules when the request carries logit rules, else None
         self.future: Future = Future()
 
     @property
@@ -168,8 +172,15 @@ class ContinuousWorker(BatchingWorker):
         """the engine returns per-token log-probabilities (Engine.set_row_logprobs)"""
         return hasattr(self.model.engine, "set_row_logprobs")
 
+    @property
+    def has_rules(self) -> bool:
+        """the engine takes per-request logit rules (Engine.set_row_logit_rules)"""
+        return hasattr(self.model.engine, "set_row_logit_rules")
+
     def _finish(self, job: _Job, prompt_tokens: int, toks, kv_truncated: bool = False, logprobs=None):
         eos = set(self.model.config.eos_token_ids)
+        if job.rules is not None:                    # the request's own stop ids end it as an EOS does; ignore_eos takes the EOS ids out
+            eos = (set() if job.rules.ignore_eos else eos) | set(job.rules.stop)
         toks = [int(t) for t in toks]
         text = self.processor.batch_decode([toks], skip_special_tokens=True, clean_up_tokenization_spaces=False)[0]
         # "kv_pool_exhausted": the engine ended the sequence at what its KV pages hold (vLLM would preempt and recompute; here the
@@ -225,12 +236,15 @@ class ContinuousWorker(BatchingWorker):
                         ids = inputs["input_ids"][0].numpy()
                         cb.submit(Request(ids, inputs.get("pixel_values"), None if "image_grid_thw" not in inputs
                                           else inputs["image_grid_thw"].numpy(), job.max_tokens, tag=job,
-                                          sampling=self._row_params(job) if per_row else None, logprobs=job.logprobs))
+                                          sampling=self._row_params(job) if per_row else None, logprobs=job.logprobs, rules=job.rules))
                         admitted += 1
                     except Exception as e:                           # a bad request fails alone
                         job.future.set_exception(e)
                 if cb is not None and not cb.idle:
                     for _, req, toks in cb.step():
+                        if getattr(req, "error", None) is not None:      # refused at admission: this request alone
+                            req.tag.future.set_exception(req.error)
+                            continue
                         self._finish(req.tag, int(req.input_ids.shape[0]), toks, getattr(req, "kv_truncated", False),
                                      getattr(req, "logprobs_out", None))
                     if admitted:
@@ -343,6 +357,51 @@ def _logprob_fields(req: dict) -> Optional[int]:
     return (top or 0) if lp else None
 
 
+RULE_FIELDS = ("logit_bias", "allowed_token_ids", "min_tokens", "stop_token_ids", "ignore_eos")
+
+
+def _rule_fields(req: dict, vocab_size: Optional[int], max_tokens: int, eos_ids=None):
+    """`logit_bias` (OpenAI: {"id": value in [-100, 100]}), `allowed_token_ids`, `min_tokens`, `stop_token_ids`, `ignore_eos` (vLLM) of a
+    request -> engine.LogitRules, or None when the request uses none of them.  ValueError / TypeError on a bad value."""
+    if all(req.get(k) is None for k in RULE_FIELDS):
+        return None
+    from .engine import LogitRules
+
+    def id_list(name):
+        v = req.get(name)
+        if v is None:
+            return None
+        if not isinstance(v, list) or any(isinstance(t, bool) or not isinstance(t, int) for t in v):
+            raise TypeError(f"{name} must be a list of integer token ids")
+        return v
+    bias = {}
+    lb = req.get("logit_bias")
+    if lb is not None:
+        if not isinstance(lb, dict):
+            raise TypeError("logit_bias must be an object of token id -> bias")
+        for k, v in lb.items():
+            try:
+                t = int(k)
+            except (TypeError, ValueError):
+                raise ValueError(f"logit_bias key {k!r} is not a token id")
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not -100.0 <= float(v) <= 100.0:
+                raise ValueError(f"logit_bias[{k!r}] must be a number in [-100, 100]")
+            if t in bias:
+                raise ValueError(f"logit_bias names token {t} twice")
+            bias[t] = float(v)
+    mt = req.get("min_tokens")
+    if mt is not None and (isinstance(mt, bool) or not isinstance(mt, int) or mt < 0):
+        raise TypeError("min_tokens must be an integer >= 0")
+    if mt is not None and mt > max_tokens:
+        raise ValueError(f"min_tokens ({mt}) exceeds max_tokens ({max_tokens})")
+    ie = req.get("ignore_eos")
+    if ie is not None and not isinstance(ie, bool):
+        raise TypeError("ignore_eos must be a boolean")
+    rules = LogitRules(bias=bias, allowed=id_list("allowed_token_ids"), min_tokens=mt or 0, stop=tuple(id_list("stop_token_ids") or ()),
+                       ignore_eos=bool(ie), vocab_size=vocab_size, eos_ids=eos_ids)
+    return None if rules.empty else rules
+
+
 def _logprobs_object(processor, toks, logprobs, top_n: int) -> dict:
     """The OpenAI `choices[i].logprobs` object: one entry per generated id (the final EOS included), each with `top_n` alternatives.
     logprobs = (tok_lp [n], top_ids [n, 20], top_lp [n, 20]) as Engine.row_logprobs returns them."""
@@ -409,9 +468,19 @@ def create_app(model, processor, model_name: str = "model", max_batch: int = 8, 
             raise HTTPException(400, f"bad logprobs parameters: {e}")
         if job.logprobs is not None and not (isinstance(worker, ContinuousWorker) and worker.has_logprobs):
             raise HTTPException(400, "logprobs need continuous batching on an engine that returns log-probabilities (Engine.set_row_logprobs)")
+        try:
+            mcfg = getattr(model, "config", None)     # the EOS ids the request will run under: never-selectable rules are a 400 here
+            job.rules = _rule_fields(req, getattr(mcfg, "vocab_size", None), max_tokens, getattr(mcfg, "eos_token_ids", None))
+        except (TypeError, ValueError) as e:
+            raise HTTPException(400, f"bad logit rules: {e}")
+        if job.rules is not None and not (isinstance(worker, ContinuousWorker) and worker.has_rules):
+            raise HTTPException(400, "logit_bias, allowed_token_ids, min_tokens, stop_token_ids and ignore_eos need continuous batching on an "
+                                     "engine with per-row logit rules (Engine.set_row_logit_rules)")
         fut = worker.submit(job)
         try:
             res = await run_in_threadpool(fut.result)
+        except RequestRejected as e:                 # the engine refused this request's own parameters: its fault alone
+            raise HTTPException(400, f"request refused: {e}")
         except Exception as e:
             raise HTTPException(500, f"generation failed: {e}")
         choice = {"index": 0, "message": {"role": "assistant", "content": res["text"]}, "finish_reason": res["finish_reason"]}

@@ -192,6 +192,43 @@ typedef struct DotsSamplingParams {
  * written by each prefill from then on); the prompt is not kept on the device to rebuild them. */
 int dots_set_row_sampling(DotsEngine* e, int row, const DotsSamplingParams* p);
 
+/* Per-row logit rules: which tokens a row may emit and when it stops.  One row = a slot, or sequence b of a static batch.
+ *   bias_ids / bias_values  n_bias <= DOTS_MAX_LOGIT_BIAS pairs (id, value): the value is added to the token's logit; finite, or -inf = a
+ *                           ban.  A duplicate id is refused.
+ *   allowed_ids             NULL = every id is allowed, else n_allowed >= 1 ids: every id outside the list is -inf
+ *   min_tokens              while the row has generated fewer than min_tokens tokens (the prefill's token is n = 0) every engine EOS id
+ *                           (dots_set_eos) and every id of stop_ids is -inf
+ *   stop_ids                n_stop <= DOTS_MAX_STOP_IDS ids that finish this row only, as an EOS id does: the id is appended, the row is finished
+ *   ignore_eos              != 0: the engine's EOS ids do not finish this row (its stop ids and its length cap still do)
+ * Order (vLLM's): raw logit + bias, -inf for banned / not allowed / min_tokens ids, then the penalties of DotsSamplingParams on that value
+ * (-inf stays -inf), then the greedy arg max (lowest index on a tie) or the tempered top-k / top-p draw.  A -inf token has weight 0: it is
+ * never drawn and never counted into top-k or the nucleus.  dots_get_logits and the logprobs stay on the raw logits. */
+#define DOTS_MAX_LOGIT_BIAS 1024
+#define DOTS_MAX_STOP_IDS 16
+typedef struct DotsLogitRules {
+    const int32_t* bias_ids;
+    const float* bias_values;
+    int32_t n_bias;
+    const int32_t* allowed_ids;
+    int32_t n_allowed;
+    int32_t min_tokens;
+    int32_t stop_ids[DOTS_MAX_STOP_IDS];
+    int32_t n_stop;
+    int32_t ignore_eos;
+} DotsLogitRules;
+/* Give row `row` logit rules (r == NULL: none), in stream order: they apply from the next token the engine selects, the first token of a
+ * following dots_prefill / dots_slots_prefill included (set, then prefill).  The lists are copied before the call returns.  Values live in
+ * device memory: captured decode graphs are kept (one more graph per step shape exists for "some row has rules").  dots_slot_release /
+ * dots_slots_reset clear the row.  The first call allocates the state: an fp32 image and a shaped-logit scratch of max_batch x vocab each
+ * (the latter shared with the penalties).
+ * A row with rules is always selected by the per-row stage.  If it has no DotsSamplingParams of its own, the stage uses the engine-wide
+ * temperature / top_p / seed of dots_set_sampling AS THEY STAND WHEN THE RULES ARE SET (or when its own parameters are cleared), with the
+ * per-row draw u = hash(seed, n): a later dots_set_sampling does not reach it.
+ * DOTS_E_INVALID: a value out of range, an id outside [0, vocab), a duplicate bias id, and rules that could never select a token — an empty
+ * allowed list, one entirely banned by the bias, or (min_tokens > 0) one that bans, engine EOS ids and stop ids cover together.  The EOS ids
+ * are those set at the call.  Should a row end up all -inf all the same (EOS ids changed later), it commits the lowest index, id 0. */
+int dots_set_row_logit_rules(DotsEngine* e, int row, const DotsLogitRules* r);
+
 /* Log-probabilities: log_softmax of the raw fp32 logits of the step (before penalties, temperature, top-k and top-p:
  * the values dots_get_logits returns), for every token a row commits, the prefill's first token included.  The top entries are
  * ordered by value descending, then index ascending.  lse comes from per-chunk (max, sum) pairs merged in a fixed chunk order, so a
@@ -379,6 +416,15 @@ int dots_op_select_tokens(DotsEngine* e, const float* logits_dev, int B, int V, 
  * every row marked finished so that nothing is appended.  *ms_out = mean milliseconds per replay. */
 int dots_bench_select_tokens(DotsEngine* e, const float* logits_dev, int B, int V, const DotsSamplingParams* params_host, const int32_t* hist_dev,
                              const int32_t* hist_lens_dev, int hist_stride, const int32_t* n_prompt_dev, int mode, int iters, float* ms_out);
+/* dots_op_select_tokens with logit rules: rules_host [B] (an entry with no bias, allowed list, min_tokens, stop id and ignore_eos = a row
+ * without rules), the engine's EOS ids live, and n_gen_host [B] = each row's generated count n in [0, hist_stride] (NULL: hist_lens -
+ * n_prompt): it seeds the draw and is compared with min_tokens.  dots_bench_select_tokens_rules times the stage on the same inputs. */
+int dots_op_select_tokens_rules(DotsEngine* e, const float* logits_dev, int B, int V, const DotsSamplingParams* params_host, const DotsLogitRules* rules_host,
+                                const int32_t* n_gen_host, const int32_t* hist_dev, const int32_t* hist_lens_dev, int hist_stride,
+                                const int32_t* n_prompt_dev, int32_t* out_tokens_dev);
+int dots_bench_select_tokens_rules(DotsEngine* e, const float* logits_dev, int B, int V, const DotsSamplingParams* params_host, const DotsLogitRules* rules_host,
+                                   const int32_t* n_gen_host, const int32_t* hist_dev, const int32_t* hist_lens_dev, int hist_stride,
+                                   const int32_t* n_prompt_dev, int iters, float* ms_out);
 /* The log-probability stage over caller logits: logits_dev fp32 [B, ld] (V <= ld), top_n_host [B] (-1 = row skipped, 0..20),
  * chosen_dev int32 [B] the chosen ids; writes tok_lp_dev float [B], top_ids_dev int32 [B][20], top_lp_dev float [B][20] of every row
  * with top_n >= 0 (entries beyond top_n: -1 / NaN).  The same two kernels the engine runs. */

@@ -7,6 +7,10 @@
           sampler     the engine-wide sampler, T = 0.7, top_p = 0.9 (sample_step_kernel)
           rows_greedy the per-row stage, every row greedy without penalties
           rows_loaded the per-row stage, every row at T = 0.1, top_p = 0.9, top_k = 50 + all three penalties
+    python tools/sampling_bench.py --rules [--rows 1 8 64] [--iters 200]
+        the logit-rule leg (profiles/logit_rules.txt): rows_greedy and rows_loaded as above, each again with every row
+        carrying a 300-entry bias and a 5 000-id allowed list (+ min_tokens in force: two EOS ids and four stop ids masked), and the
+        host-side cost of setting one row's rules (Engine.set_row_logit_rules, mean wall time over 50 calls, synchronised at the end)
     python tools/sampling_bench.py --rows 64 --iters 20
         under `rocprofv3 --kernel-trace --stats -- python tools/sampling_bench.py ...` for the per-kernel split.
 Logits: a seeded N(0, 2) background with 64 planted tokens in [8, 14] per row (an LM-like peaked head); histories of 1200 prompt ids
@@ -28,6 +32,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, nargs="+", default=[1, 8, 64])
     ap.add_argument("--iters", type=int, default=200)
+    ap.add_argument("--rules", action="store_true", help="the logit-rule leg instead of the four stages")
     a = ap.parse_args()
     import torch
     from dots_ocr_amd.config import DotsConfig
@@ -51,6 +56,38 @@ def main():
               for b in range(B_max)]
     cases = [("argmax", 0, lambda B: [greedy] * B), ("sampler", 1, lambda B: [legacy] * B),
              ("rows_greedy", 2, lambda B: [greedy] * B), ("rows_loaded", 2, lambda B: loaded[:B])]
+    if a.rules:
+        import time
+        from dots_ocr_amd.engine import LogitRules
+        eng.set_eos([151643, 151645])
+        rules = []
+        for b in range(B_max):
+            allowed = rng.choice(V, 5000, replace=False)
+            allowed[:64] = np.argsort(-logits[b])[:64]                # the peaked head stays selectable
+            allowed = sorted(set(int(x) for x in allowed))
+            bias = {int(t): float(v) for t, v in zip(allowed[:300], rng.uniform(-2.0, 2.0, 300))}
+            rules.append(LogitRules(bias=bias, allowed=allowed, min_tokens=10 ** 6, stop=allowed[300:304]))
+        for B in a.rows:
+            for name, params in (("rows_greedy", [greedy] * B), ("rows_loaded", loaded[:B])):
+                for tag, rl in (("", [None] * B), ("+rules", rules[:B])):
+                    ms = eng.bench_select_tokens_rules(d_l.data_ptr(), B, V, params, rl, None, d_h.data_ptr(), d_n.data_ptr(), n_prompt + n_gen,
+                                                       d_p.data_ptr(), a.iters)
+                    print(json.dumps({"rows": B, "V": V, "stage": name + tag, "us": round(ms * 1e3, 2), "iters": a.iters}), flush=True)
+        eng.close()
+        # setting a row's rules on an engine of the real vocabulary width (no weights needed: only the selection state is touched)
+        big = Engine(DotsConfig.tiny(vocab=V), max_batch=4, max_seq_len=512, max_patches=256, max_prefill_tokens=256)
+        big.set_row_logit_rules(0, rules[0])                             # first call: allocates the state
+        big.synchronize()
+        t0 = time.perf_counter()
+        for i in range(50):
+            big.set_row_logit_rules(i % 4, rules[i % B_max])
+        t1 = time.perf_counter()
+        big.synchronize()
+        t2 = time.perf_counter()
+        print(json.dumps({"stage": "set_row_logit_rules", "V": V, "bias": 300, "allowed": len(rules[0].allowed), "host_us_per_call": round((t1 - t0) / 50 * 1e6, 1),
+                          "with_final_sync_us_per_call": round((t2 - t0) / 50 * 1e6, 1)}), flush=True)
+        big.close()
+        return
     for B in a.rows:
         for name, mode, params in cases:
             ms = eng.bench_select_tokens(d_l.data_ptr(), B, V, params(B), d_h.data_ptr(), d_n.data_ptr(), n_prompt + n_gen, d_p.data_ptr(),
