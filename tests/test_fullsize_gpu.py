@@ -53,6 +53,9 @@ def _flash(eng, q, k, v, causal=False, Hkv=None):
 
 
 def test_flash_attn_a4_sampled_rows_match_oracle(eng):
+    """iid randn inputs: the output shrinks like 1 / sqrt(keys) and the absolute floor does not, so this check does not see a dropped tile at this
+    size (test_attention_probes_cpu.py reproduces that); test_attention_probes_gpu.py covers the same shape with probes that do.  Kept as the
+    oracle-parity check on dense V."""
     g = torch.Generator(device="cuda").manual_seed(1)
     H = 12
     q = torch.randn(N_A4, H, 128, device="cuda", generator=g).bfloat16()
@@ -154,6 +157,8 @@ def test_flash_attn_a4_properties(eng):
 
 
 def test_causal_gqa_full_prompt_length_sampled_rows(eng):
+    """Dense randn V at the LM prompt length: oracle parity of sampled rows.  A causal mask off by one or a dropped ragged tile stays inside this
+    tolerance; test_attention_probes_gpu.py::test_flash_attn_causal_gqa_probes_match_fp64 plants the diagonal neighbours that show them."""
     g = torch.Generator(device="cuda").manual_seed(3)
     T, Hq, Hkv = 5200, 12, 2
     q = torch.randn(T, Hq, 128, device="cuda", generator=g).bfloat16()
