@@ -6,7 +6,7 @@ from dots_ocr_amd.image_utils import PILimage_to_base64
 
 
 def inference_with_vllm(image, prompt, protocol="http", ip="localhost", port=8000, temperature=0.1, top_p=0.9,
-                        max_completion_tokens=32768, model_name="rednote-hilab/dots.mocr", system_prompt=None):
+                        max_completion_tokens=32768, model_name="rednote-hilab/dots.mocr", system_prompt=None, extra_body=None):
     import requests
     from openai import OpenAI        # optional dependency, imported lazily
     client = OpenAI(api_key=os.environ.get("API_KEY", "0"), base_url=f"{protocol}://{ip}:{port}/v1")
@@ -16,7 +16,7 @@ def inference_with_vllm(image, prompt, protocol="http", ip="localhost", port=800
         {"type": "text", "text": f"<|img|><|imgpad|><|endofimg|>{prompt}"}]})
     try:
         r = client.chat.completions.create(messages=messages, model=model_name, max_completion_tokens=max_completion_tokens,
-                                           temperature=temperature, top_p=top_p)
+                                           temperature=temperature, top_p=top_p, **({"extra_body": extra_body} if extra_body else {}))
         return r.choices[0].message.content
     except requests.exceptions.RequestException as e:
         print(f"request error: {e}")

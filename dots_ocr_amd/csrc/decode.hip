@@ -570,7 +570,10 @@ constexpr int ARGMAX_CHUNKS = 64;
 // and can idle in its slot until the host refills it (continuous batching).
 // rules: the row's logit rules (per-row stage only) or nullptr: its stop ids finish it too, RULE_IGNORE_EOS takes the engine's
 // EOS ids out of the test.  The arg-max and engine-wide sampler paths pass nullptr (a constant after inlining).
-DEVI void commit_token(const StepState& st, int b, int tok, const RowRules* rules = nullptr) {
+// guide: the launch's guides (per-row stage only) or nullptr.  A guided row that is not finished advances its automaton by the
+// bytes of the committed token; an EOS or stop id moves nothing and finishes the row, RULE_IGNORE_EOS or not (the guide allowed it because
+// the state is accepting; with nothing else left to allow, a row that ignored it could only repeat it).
+DEVI void commit_token(const StepState& st, int b, int tok, const RowRules* rules = nullptr, const GuideSel* guide = nullptr) {
     const bool done = st.finished[b] != 0;
     if (st.advance_ctx && !done) st.ctx_len[b] += 1;
     if (!done) {
@@ -579,10 +582,18 @@ DEVI void commit_token(const StepState& st, int b, int tok, const RowRules* rule
         st.out_ids[(size_t)b * st.out_stride + n] = tok;
         st.out_lens[b] = n + 1;
         bool eos = false;
-        if (!(rules && (rules->flags & RULE_IGNORE_EOS)))
+        const bool guided = guide && guide->rows[b].table;
+        if (guided || !(rules && (rules->flags & RULE_IGNORE_EOS)))
             for (int k = 0; k < st.n_eos; ++k) eos = eos || (tok == st.eos_ids[k]);
         if (rules)
             for (int k = 0; k < min(rules->n_stop, DOTS_MAX_STOP_IDS); ++k) eos = eos || (tok == rules->stop[k]);
+        if (guided && !eos && tok >= 0 && tok < guide->V) {
+            RowGuide& rg = guide->rows[b];
+            uint32_t s = (uint32_t)rg.state;
+            for (int j = guide->tok_off[tok], end = guide->tok_off[tok + 1]; j < end && s != GUIDE_DEAD; ++j)
+                s = rg.table[(size_t)s * 256 + guide->tok_bytes[j]];
+            if (s != GUIDE_DEAD) rg.state = (int32_t)s;              // a token the guide did not allow (the all -inf fallback) moves nothing
+        }
         if (eos || n + 1 >= cap) st.finished[b] = 1;
     }
     st.cur_tokens[b] = tok;
@@ -750,6 +761,8 @@ DEVI float penalise(float l, int c, bool seen_prompt, const RowParams& p) {
 
 // does row b carry logit rules in this launch (uniform per workgroup)
 DEVI bool row_ruled(const RowSel& rs, int b) { return rs.rules && (rs.rules[b].flags & RULE_ON); }
+// does row b hold a guide in this launch (uniform per workgroup)
+DEVI bool row_guided(const RowSel& rs, int b) { return rs.guide.rows && rs.guide.rows[b].table; }
 
 __global__ __launch_bounds__(256) void select_partial_kernel(const float* __restrict__ logits, int V, int ld, RowSel rs, StepState st,
                                                              float* __restrict__ pval, int32_t* __restrict__ pidx) {
@@ -766,27 +779,35 @@ __global__ __launch_bounds__(256) void select_partial_kernel(const float* __rest
     float best = -INFINITY;
     int bi = 0x7fffffff;
     const RowParams p = own ? rs.params[b] : RowParams{0.f, 1.f, 0, 1.f, 0.f, 0.f, 0};
-    if (own && row_ruled(rs, b)) {
+    const bool ruled = own && row_ruled(rs, b), guided = own && row_guided(rs, b);
+    if (ruled || guided) {
         // Logit rules, in vLLM's order: l + bias (-inf: banned / not allowed), -inf for the EOS and stop ids below min_tokens,
         // then the penalties on that value (-inf stays -inf: r > 0 and the subtrahend is finite).  Still one read of the logits; the shaped
         // values go to the scratch the threshold and draw kernels read.
-        const RowRules& r = rs.rules[b];
+        // A guide enters with the allowed list: -inf where the row's bit of guide_mask_kernel is clear; the EOS and stop ids
+        // are allowed iff the row's state is accepting, whatever their bit.  A guided row without rules runs this branch with no image.
+        const RowRules* r = ruled ? rs.rules + b : nullptr;
         const bool pen_on = rs.cnt && row_has_pen(p);
-        const float* img = (r.flags & RULE_IMG) ? rs.rule_img + (size_t)b * V : nullptr;
-        // below min_tokens: the EOS / stop ids that fall into THIS chunk (of ~V / 64 ids: none for most chunks, so the loop below compares
-        // nothing there).  The order of the list does not enter the result.
+        const float* img = (r && (r->flags & RULE_IMG)) ? rs.rule_img + (size_t)b * V : nullptr;
+        const uint32_t* gbits = guided ? rs.guide.mask + (size_t)b * rs.guide.words : nullptr;
+        const bool early = r && st.out_lens[b] < r->min_tokens;
+        bool accepting = true;
+        if (guided) { const RowGuide& rg = rs.guide.rows[b]; accepting = rg.accepting[rg.state] != 0; }
+        // the EOS / stop ids that fall into THIS chunk (of ~V / 64 ids: none for most chunks, so the loops below compare nothing there):
+        // -inf below min_tokens, and on a guided row whose state is not accepting.  The order of the list does not enter the result.
         int n_kill = 0;
-        if (st.out_lens[b] < r.min_tokens) {
-            const int ne = min(st.n_eos, 16), ns = min(r.n_stop, DOTS_MAX_STOP_IDS);
+        if (early || guided) {
+            const int ne = min(st.n_eos, 16), ns = r ? min(r->n_stop, DOTS_MAX_STOP_IDS) : 0;
             if (threadIdx.x == 0) s_nkill = 0;
             __syncthreads();
             if ((int)threadIdx.x < ne + ns) {
-                const int id = (int)threadIdx.x < ne ? st.eos_ids[threadIdx.x] : r.stop[threadIdx.x - ne];
+                const int id = (int)threadIdx.x < ne ? st.eos_ids[threadIdx.x] : r->stop[threadIdx.x - ne];
                 if (id >= lo && id < hi) s_kill[atomicAdd(&s_nkill, 1)] = id;
             }
             __syncthreads();
             n_kill = s_nkill;
         }
+        const bool kill = early || !accepting;                       // what an EOS / stop id of this chunk gets
         const int W = (V + 31) >> 5;
         const int32_t* cnt = pen_on ? rs.cnt + (size_t)b * V : nullptr;
         const uint32_t* seen = pen_on ? rs.seen + (size_t)b * W : nullptr;
@@ -795,7 +816,9 @@ __global__ __launch_bounds__(256) void select_partial_kernel(const float* __rest
         for (int i = lo + threadIdx.x; i < hi; i += 256) {
             float l = row[i];
             if (img) l += img[i];
-            for (int k = 0; k < n_kill; ++k) l = s_kill[k] == i ? -INFINITY : l;
+            bool term = false;                                       // an EOS / stop id: the guide's bit does not speak for it
+            for (int k = 0; k < n_kill; ++k) term = term || s_kill[k] == i;
+            if (term ? kill : (gbits && !((gbits[i >> 5] >> (i & 31)) & 1u))) l = -INFINITY;
             if (pen_on) l = penalise(l, cnt[i], (seen[i >> 5] >> (i & 31)) & 1u, p);
             if (sampled) shaped[i] = l;
             argmax_merge(best, bi, l, i);
@@ -926,7 +949,7 @@ DEVI uint32_t radix_select(Each each, uint64_t target, bool by_mass, SelLds& L) 
 
 DEVI void commit_row(const StepState& st, const RowSel& rs, int b, int V, bool pen, int tok) {
     if (pen && !st.finished[b] && tok >= 0 && tok < V) rs.cnt[(size_t)b * V + tok] += 1;     // output counts of the rows with penalties
-    commit_token(st, b, tok, row_ruled(rs, b) ? rs.rules + b : nullptr);
+    commit_token(st, b, tok, row_ruled(rs, b) ? rs.rules + b : nullptr, rs.guide.rows ? &rs.guide : nullptr);
 }
 
 // the merged arg max partials of row b -> L.best / L.bi (every thread must call)
@@ -955,7 +978,7 @@ __global__ __launch_bounds__(SEL_THREADS) void select_thresh_kernel(const float*
         return;
     }
     merge_partials(pval, pidx, b, &L.best, &L.bi);
-    const bool pen = (rs.cnt && row_has_pen(p)) || row_ruled(rs, b);      // the shaped values of the partial kernel
+    const bool pen = (rs.cnt && row_has_pen(p)) || row_ruled(rs, b) || row_guided(rs, b);      // the shaped values of the partial kernel
     const float* row = pen ? rs.pen + (size_t)b * V : logits + (size_t)b * ld;
     const float m = L.best, inv_t = 1.0f / p.temperature;
 
@@ -1067,7 +1090,7 @@ __global__ __launch_bounds__(SEL_THREADS) void select_rows_kernel(const float* _
         if (tid == 0) commit_row(st, rs, b, V, pen, s_bi);
         return;
     }
-    const float* row = pen || row_ruled(rs, b) ? rs.pen + (size_t)b * V : logits + (size_t)b * ld;
+    const float* row = pen || row_ruled(rs, b) || row_guided(rs, b) ? rs.pen + (size_t)b * V : logits + (size_t)b * ld;
     const float m = s_best, inv_t = 1.0f / p.temperature;
     const uint32_t kmax = rs.thr[b];
     // ---- 3. inverse CDF in index order over the kept weights.  Wave w owns the contiguous segment [w seg, (w + 1) seg) and walks it 64

@@ -216,6 +216,17 @@ struct DotsEngine {
     int row_rules[DOTS_MAX_BATCH] = {0};
     int n_rules = 0;                       // rows with rules: > 0 hands the table to the per-row stage
     int32_t h_eos[16] = {0};               // host mirror of eos_ids (the never-selectable checks of the rules)
+    // guided decoding (dots_set_row_guide): the packed bytes of the vocabulary (dots_set_token_bytes), the guides created on
+    // this engine (device tables; rows = how many rows hold each), and — allocated by the first row that takes a guide — the row table and
+    // the allowed bits [max_batch][guide_mask_words(V)].  row_guide[row] = guide id + 1, 0 = none.
+    int32_t* tok_off = nullptr;
+    uint8_t* tok_bytes = nullptr;
+    struct Guide { uint16_t* table = nullptr; uint8_t* accepting = nullptr; int n_states = 0, start = 0, rows = 0; };
+    std::vector<Guide> guides;
+    RowGuide* d_guides = nullptr;
+    uint32_t* guide_mask = nullptr;
+    int row_guide[DOTS_MAX_BATCH] = {0};
+    int n_guided = 0;                      // rows with a guide: > 0 adds the mask kernel in front of the per-row stage
     // log-probabilities (dots_set_row_logprobs): top_n per row (-1 = off) on the device and its host mirror; the outputs
     // ([max_batch][max_seq_len] positions) and the stage's scratch are allocated by the first row switched on
     int32_t* d_row_lp = nullptr;
@@ -246,8 +257,9 @@ struct DotsEngine {
     // captured decode steps, keyed by everything the capture bakes in: rows, KV splits, static batch (out_cap = row stride of
     // the output buffer) or slot mode (out_cap = 0), number of EOS ids, whether any row carries its own parameters (rowp: the per-row
     // selection stage), whether any row returns logprobs (lp), whether any row carries logit rules (rules: the stage then gets their
-    // table); engine-wide sampling changes drop the cache (dots_set_sampling), per-row ones live in device memory
-    struct StepGraph { int rows, splits, out_cap, n_eos, part, rowp, lp, rules; hipGraph_t graph; hipGraphExec_t exec; };
+    // table), whether any row holds a guide (guided: the mask kernel and the guides' tables); engine-wide sampling changes drop the cache
+    // (dots_set_sampling), per-row ones live in device memory
+    struct StepGraph { int rows, splits, out_cap, n_eos, part, rowp, lp, rules, guided; hipGraph_t graph; hipGraphExec_t exec; };
     std::vector<StepGraph> step_graphs;
     std::vector<int> h_prompt_lens;
     int steps_done = 0;
@@ -876,8 +888,12 @@ int select_tokens(DotsEngine* e, int advance) {
                           e->lp_tok, e->lp_ids, e->lp_top, c.max_seq_len};
     if (e->n_lp > 0) CK(launch_logprob_partial(e->stream, e->d_logits, c.vocab_size, c.vocab_size, e->B_sel, ls));
     if (e->n_own > 0) {          // per-row stage for the rows with their own parameters (+ the greedy rows that follow the engine)
-        const RowSel rs{e->d_rowp, e->d_row_own, e->pen_cnt, e->pen_seen, e->pen_logits, e->d_row_thr, e->temperature > 0.f ? 0 : 1,
-                        e->n_rules > 0 ? e->d_rules : nullptr, e->rule_img};
+        RowSel rs{e->d_rowp, e->d_row_own, e->pen_cnt, e->pen_seen, e->pen_logits, e->d_row_thr, e->temperature > 0.f ? 0 : 1,
+                  e->n_rules > 0 ? e->d_rules : nullptr, e->rule_img, GuideSel{}};
+        if (e->n_guided > 0) {       // the guided rows' allowed bits from their current states, before the stage reads the logits
+            rs.guide = GuideSel{e->d_guides, e->guide_mask, e->tok_off, e->tok_bytes, guide_mask_words(c.vocab_size), c.vocab_size};
+            CK(launch_guide_mask(e->stream, rs.guide, e->B_sel, st.sel));
+        }
         CK(launch_select_rows(e->stream, e->d_logits, c.vocab_size, c.vocab_size, e->B_sel, rs, e->am_val, e->am_idx, st));
         if (e->temperature > 0.f)
             CK(launch_sample_step(e->stream, e->d_logits, c.vocab_size, c.vocab_size, e->B_sel, e->temperature, e->top_p, e->seed, st, e->d_row_own));
@@ -933,13 +949,24 @@ int ensure_rules_state(DotsEngine* e) {
     return DOTS_OK;
 }
 
+// row table and allowed bits of the guides, allocated by the first row that takes one
+int ensure_guide_state(DotsEngine* e) {
+    if (e->d_guides) return DOTS_OK;
+    const size_t rows = e->cfg.max_batch, V = e->cfg.vocab_size;
+    if (!e->guide_mask) CK(e->alloc(&e->guide_mask, rows * guide_mask_words((int)V)));
+    if (!e->pen_logits) CK(e->alloc(&e->pen_logits, rows * V));       // the shaped logits of a sampled guided row
+    CK(e->alloc(&e->d_guides, DOTS_MAX_BATCH));            // zeroed by alloc(): no row holds a guide; set last, it is the guard above
+    drop_step_graphs(e);                                   // graphs captured before hold no guide state
+    return DOTS_OK;
+}
+
 // what a row without parameters of its own is selected with once the per-row stage owns it (logit rules): the engine-wide setting as it stands
 RowParams engine_row_params(const DotsEngine* e) { return RowParams{e->temperature, e->top_p, 0, 1.f, 0.f, 0.f, e->seed}; }
 
 // the row's entry back to the engine-wide setting (stream ordered); a row that still carries logit rules stays with the per-row stage
 int clear_row(DotsEngine* e, int row) {
     if (!e->row_own[row]) return DOTS_OK;
-    if (e->row_rules[row]) {
+    if (e->row_rules[row] || e->row_guide[row]) {
         CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, engine_row_params(e), 1));
         e->row_own[row] = 0;
         return DOTS_OK;
@@ -956,7 +983,21 @@ int clear_row_rules(DotsEngine* e, int row) {
     CK(launch_set_row_rules(e->stream, e->d_rules, e->rule_img, row, e->cfg.vocab_size, RowRules{}, nullptr, 0, nullptr, nullptr, 0));
     e->row_rules[row] = 0;
     e->n_rules -= 1;
-    if (!e->row_own[row]) {
+    if (!e->row_own[row] && !e->row_guide[row]) {
+        CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, RowParams{}, 0));
+        e->n_own -= 1;
+    }
+    return DOTS_OK;
+}
+
+// the row's guide off (stream ordered)
+int clear_row_guide(DotsEngine* e, int row) {
+    if (!e->row_guide[row]) return DOTS_OK;
+    CK(launch_set_row_guide(e->stream, e->d_guides, row, RowGuide{}));
+    e->guides[e->row_guide[row] - 1].rows -= 1;
+    e->row_guide[row] = 0;
+    e->n_guided -= 1;
+    if (!e->row_own[row] && !e->row_rules[row]) {
         CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, RowParams{}, 0));
         e->n_own -= 1;
     }
@@ -1277,6 +1318,8 @@ int prefill(DotsEngine* e, const int32_t* ids, const int32_t* lens, int B, const
     }
     // prompt-presence bits (repetition penalty) of the prefilled rows, once any row has used a penalty
     if (e->pen_cnt) CK(launch_pen_prompt(s, e->p_src, e->p_last, slots ? e->p_dst : nullptr, B, c.image_token_id, c.vocab_size, e->pen_cnt, e->pen_seen));
+    // the automata of the prefilled rows that hold a guide start over: the first token is already selected under the guide
+    if (e->n_guided > 0) CK(launch_guide_reset_rows(s, e->d_guides, slots ? e->p_dst : nullptr, B));
     // last position of every sequence -> final norm -> lm_head -> first token
     CK(launch_gather_rows(s, e->p_x, e->p_last, slots ? e->p_dst : nullptr, e->d_h, B, H));
     CK(launch_dec_lmhead(s, e->d_h, e->final_norm, e->lm_head_d, e->lm_head_s, e->d_logits, rows, H, c.vocab_size, c.rms_norm_eps));
@@ -1349,14 +1392,15 @@ int splits_for_ctx(int max_ctx) { return decode_attn_splits(max_ctx); }
 
 // The captured decode step for (rows = e->B, splits, out_cap, e->n_eos): looked up in the cache or captured now.
 int step_graph(DotsEngine* e, int rows, int n_splits, int out_cap, hipGraphExec_t* exec, int part = 0) {
-    const int rowp = e->n_own > 0 ? 1 : 0, lp = e->n_lp > 0 ? 1 : 0, rules = e->n_rules > 0 ? 1 : 0;
+    const int rowp = e->n_own > 0 ? 1 : 0, lp = e->n_lp > 0 ? 1 : 0, rules = e->n_rules > 0 ? 1 : 0, guided = e->n_guided > 0 ? 1 : 0;
     for (auto& g : e->step_graphs)
-        if (g.rows == rows && g.splits == n_splits && g.out_cap == out_cap && g.n_eos == e->n_eos && g.part == part && g.rowp == rowp && g.lp == lp && g.rules == rules) {
+        if (g.rows == rows && g.splits == n_splits && g.out_cap == out_cap && g.n_eos == e->n_eos && g.part == part && g.rowp == rowp && g.lp == lp && g.rules == rules &&
+            g.guided == guided) {
             *exec = g.exec;
             return DOTS_OK;
         }
     if (e->step_graphs.size() >= 32) drop_step_graphs(e);
-    DotsEngine::StepGraph g{rows, n_splits, out_cap, e->n_eos, part, rowp, lp, rules, nullptr, nullptr};
+    DotsEngine::StepGraph g{rows, n_splits, out_cap, e->n_eos, part, rowp, lp, rules, guided, nullptr, nullptr};
     CK(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
     int r = decode_step_launches(e, n_splits, part);
     hipError_t ce = hipStreamEndCapture(e->stream, &g.graph);
@@ -1738,6 +1782,10 @@ int dots_slots_reset(DotsEngine* e) {
     if (e->d_rules) CK(hipMemsetAsync(e->d_rules, 0, DOTS_MAX_BATCH * sizeof(RowRules), s));
     std::fill(e->row_rules, e->row_rules + DOTS_MAX_BATCH, 0);
     e->n_rules = 0;
+    if (e->d_guides) CK(hipMemsetAsync(e->d_guides, 0, DOTS_MAX_BATCH * sizeof(RowGuide), s));
+    std::fill(e->row_guide, e->row_guide + DOTS_MAX_BATCH, 0);
+    for (auto& g : e->guides) g.rows = 0;
+    e->n_guided = 0;
     if (e->d_row_lp) CK(hipMemsetAsync(e->d_row_lp, 0xFF, DOTS_MAX_BATCH * 4, s));
     std::fill(e->row_lp, e->row_lp + DOTS_MAX_BATCH, -1);
     e->n_lp = 0;
@@ -1851,6 +1899,7 @@ int dots_slot_release(DotsEngine* e, int slot) {
     CK(hipSetDevice(e->device));
     RET(clear_row(e, slot));
     RET(clear_row_rules(e, slot));
+    RET(clear_row_guide(e, slot));
     RET(set_row_lp(e, slot, -1));
     e->slot_active[slot] = 0;
     e->sel_dirty = true;
@@ -1991,7 +2040,7 @@ int dots_set_row_sampling(DotsEngine* e, int row, const DotsSamplingParams* p) {
     RET(ensure_row_table(e));
     if (rp.repetition_penalty != 1.f || rp.frequency_penalty != 0.f || rp.presence_penalty != 0.f) RET(ensure_pen_state(e));
     CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, rp, 1));
-    if (!e->row_own[row]) { e->row_own[row] = 1; e->n_own += e->row_rules[row] ? 0 : 1; }
+    if (!e->row_own[row]) { e->row_own[row] = 1; e->n_own += (e->row_rules[row] || e->row_guide[row]) ? 0 : 1; }
     return DOTS_OK;
 }
 
@@ -2024,8 +2073,103 @@ int dots_set_row_logit_rules(DotsEngine* e, int row, const DotsLogitRules* r) {
     if (!e->row_rules[row]) {
         e->row_rules[row] = 1;
         e->n_rules += 1;
-        if (!e->row_own[row]) e->n_own += 1;
+        if (!e->row_own[row] && !e->row_guide[row]) e->n_own += 1;
     }
+    return DOTS_OK;
+}
+
+int dots_set_token_bytes(DotsEngine* e, const int32_t* offsets, const uint8_t* bytes) {
+    if (!e || !offsets) return e ? e->fail(DOTS_E_INVALID, "null argument") : DOTS_E_INVALID;
+    const int V = e->cfg.vocab_size;
+    if (offsets[0] != 0) return e->fail(DOTS_E_INVALID, "token bytes: offsets[0] must be 0");
+    for (int t = 0; t < V; ++t)
+        if (offsets[t + 1] < offsets[t]) return e->fail(DOTS_E_INVALID, "token bytes: offsets must not decrease (token %d)", t);
+    const size_t n = (size_t)offsets[V];
+    if (n && !bytes) return e->fail(DOTS_E_INVALID, "null argument");
+    if (e->n_guided > 0) return e->fail(DOTS_E_STATE, "token bytes cannot change while %d row(s) hold a guide", e->n_guided);
+    CK(hipSetDevice(e->device));
+    CK(hipStreamSynchronize(e->stream));                   // nothing in flight reads the previous image
+    if (e->tok_off) { e->release(e->tok_off); e->tok_off = nullptr; }
+    if (e->tok_bytes) { e->release(e->tok_bytes); e->tok_bytes = nullptr; }
+    CK(e->alloc(&e->tok_bytes, n + 16));
+    if (n) CK(hipMemcpyAsync(e->tok_bytes, bytes, n, hipMemcpyHostToDevice, e->stream));
+    int32_t* off = nullptr;
+    CK(e->alloc(&off, (size_t)V + 1));
+    CK(hipMemcpyAsync(off, offsets, ((size_t)V + 1) * 4, hipMemcpyHostToDevice, e->stream));
+    CK(hipStreamSynchronize(e->stream));                   // the caller's arrays are free again
+    e->tok_off = off;
+    drop_step_graphs(e);                                   // a captured step holds the previous pointers
+    return DOTS_OK;
+}
+
+int dots_guide_create(DotsEngine* e, const uint16_t* table, int n_states, const uint8_t* accepting, int start, int32_t* id_out) {
+    if (!e || !table || !accepting || !id_out) return e ? e->fail(DOTS_E_INVALID, "null argument") : DOTS_E_INVALID;
+    if (n_states < 1 || n_states > DOTS_MAX_GUIDE_STATES) return e->fail(DOTS_E_INVALID, "guide: n_states must be in [1, %d]", DOTS_MAX_GUIDE_STATES);
+    if (start < 0 || start >= n_states) return e->fail(DOTS_E_INVALID, "guide: start state %d outside [0, %d)", start, n_states);
+    for (size_t i = 0; i < (size_t)n_states * 256; ++i)
+        if (table[i] != GUIDE_DEAD && table[i] >= n_states)
+            return e->fail(DOTS_E_INVALID, "guide: state %zu, byte %zu leads to state %d outside [0, %d)", i / 256, i % 256, (int)table[i], n_states);
+    CK(hipSetDevice(e->device));
+    DotsEngine::Guide g;
+    g.n_states = n_states;
+    g.start = start;
+    CK(e->alloc(&g.table, (size_t)n_states * 256));
+    CK(hipMemcpyAsync(g.table, table, (size_t)n_states * 512, hipMemcpyHostToDevice, e->stream));
+    CK(e->alloc(&g.accepting, (size_t)n_states));
+    CK(hipMemcpyAsync(g.accepting, accepting, (size_t)n_states, hipMemcpyHostToDevice, e->stream));
+    CK(hipStreamSynchronize(e->stream));                   // the caller's arrays are free again
+    size_t id = 0;
+    while (id < e->guides.size() && e->guides[id].table) ++id;          // a destroyed guide's id is reused
+    if (id == e->guides.size()) e->guides.push_back(g); else e->guides[id] = g;
+    *id_out = (int32_t)id;
+    return DOTS_OK;
+}
+
+int dots_guide_destroy(DotsEngine* e, int32_t id) {
+    if (!e) return DOTS_E_INVALID;
+    if (id < 0 || id >= (int)e->guides.size() || !e->guides[id].table) return e->fail(DOTS_E_INVALID, "no guide %d", id);
+    if (e->guides[id].rows > 0) return e->fail(DOTS_E_STATE, "guide %d is held by %d row(s): clear them first (dots_set_row_guide(row, -1))", id, e->guides[id].rows);
+    CK(hipSetDevice(e->device));
+    CK(hipStreamSynchronize(e->stream));                   // steps in flight may still walk its table
+    e->release(e->guides[id].table);
+    e->release(e->guides[id].accepting);
+    e->guides[id] = DotsEngine::Guide{};
+    return DOTS_OK;
+}
+
+int dots_set_row_guide(DotsEngine* e, int row, int32_t id) {
+    if (!e) return DOTS_E_INVALID;
+    if (row < 0 || row >= e->cfg.max_batch) return e->fail(DOTS_E_INVALID, "row %d out of range [0, %d)", row, e->cfg.max_batch);
+    CK(hipSetDevice(e->device));
+    if (id < 0) return e->d_guides ? clear_row_guide(e, row) : DOTS_OK;
+    if (id >= (int)e->guides.size() || !e->guides[id].table) return e->fail(DOTS_E_INVALID, "no guide %d", id);
+    if (!e->tok_off) return e->fail(DOTS_E_STATE, "the token bytes are not set (dots_set_token_bytes): a guide cannot judge any token");
+    RET(ensure_row_table(e));
+    RET(ensure_guide_state(e));
+    const DotsEngine::Guide& g = e->guides[id];
+    CK(launch_set_row_guide(e->stream, e->d_guides, row, RowGuide{g.table, g.accepting, g.n_states, g.start, g.start, 0}));
+    if (!e->row_own[row] && !e->row_rules[row] && !e->row_guide[row])
+        CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, engine_row_params(e), 1));
+    if (e->row_guide[row]) e->guides[e->row_guide[row] - 1].rows -= 1;
+    else {
+        e->n_guided += 1;
+        if (!e->row_own[row] && !e->row_rules[row]) e->n_own += 1;
+    }
+    e->row_guide[row] = id + 1;
+    e->guides[id].rows += 1;
+    return DOTS_OK;
+}
+
+int dots_row_guide_state(DotsEngine* e, int row, int32_t* state_out) {
+    if (!e || !state_out) return e ? e->fail(DOTS_E_INVALID, "null argument") : DOTS_E_INVALID;
+    if (row < 0 || row >= e->cfg.max_batch) return e->fail(DOTS_E_INVALID, "row %d out of range [0, %d)", row, e->cfg.max_batch);
+    *state_out = -1;
+    if (!e->d_guides || !e->row_guide[row]) return DOTS_OK;
+    CK(hipSetDevice(e->device));
+    RowGuide rg;
+    CK(hipMemcpyAsync(&rg, e->d_guides + row, sizeof(rg), hipMemcpyDeviceToHost, e->stream));
+    CK(hipStreamSynchronize(e->stream));
+    *state_out = rg.state;
     return DOTS_OK;
 }
 
@@ -2543,10 +2687,25 @@ namespace {
 // ignore_eos), the engine's EOS ids are live, and n_gen_host[b] (or hist_lens - n_prompt when nullptr) is the row's generated count.
 int select_op(DotsEngine* e, const float* logits_dev, int B, int V, const DotsSamplingParams* params_host, const int32_t* hist_dev,
               const int32_t* hist_lens_dev, int hist_stride, const int32_t* n_prompt_dev, int32_t* out_tokens_dev, int mode, int iters, float* ms,
-              const DotsLogitRules* rules_host = nullptr, const int32_t* n_gen_host = nullptr) {
+              const DotsLogitRules* rules_host = nullptr, const int32_t* n_gen_host = nullptr, const int32_t* guide_ids_host = nullptr,
+              const int32_t* states_host = nullptr, int32_t* states_out_host = nullptr) {
     if (!e || !logits_dev || B < 1 || B > DOTS_MAX_BATCH || V < 1 || !params_host || !hist_dev || !hist_lens_dev || hist_stride < 1 || !n_prompt_dev ||
-        (!out_tokens_dev && !ms) || mode < 0 || mode > 2 || (rules_host && mode != 2) || (n_gen_host && !rules_host))
+        (!out_tokens_dev && !ms) || mode < 0 || mode > 2 || (rules_host && mode != 2) || (n_gen_host && !rules_host) ||
+        (guide_ids_host && (!rules_host || !states_host)))
         return e ? e->fail(DOTS_E_INVALID, "bad select_tokens arguments") : DOTS_E_INVALID;
+    // guide_ids_host != nullptr: row b holds guide guide_ids_host[b] (-1: none) of this engine at state states_host[b]; V must be the engine's
+    // vocabulary (the token bytes are its).  states_out_host (may be nullptr) receives the rows' states after the commit, -1 for a row without.
+    if (guide_ids_host) {
+        if (!e->tok_off) return e->fail(DOTS_E_STATE, "the token bytes are not set (dots_set_token_bytes)");
+        if (V != e->cfg.vocab_size) return e->fail(DOTS_E_INVALID, "guided selection needs V = the engine's vocabulary %d", e->cfg.vocab_size);
+        for (int b = 0; b < B; ++b) {
+            const int id = guide_ids_host[b];
+            if (id < 0) continue;
+            if (id >= (int)e->guides.size() || !e->guides[id].table) return e->fail(DOTS_E_INVALID, "row %d: no guide %d", b, id);
+            if (states_host[b] < 0 || states_host[b] >= e->guides[id].n_states)
+                return e->fail(DOTS_E_INVALID, "row %d: state %d outside [0, %d)", b, states_host[b], e->guides[id].n_states);
+        }
+    }
     if (n_gen_host)
         for (int b = 0; b < B; ++b)
             if (n_gen_host[b] < 0 || n_gen_host[b] > hist_stride) return e->fail(DOTS_E_INVALID, "n_gen must be in [0, hist_stride]");
@@ -2605,8 +2764,32 @@ int select_op(DotsEngine* e, const float* logits_dev, int B, int V, const DotsSa
         }
         if (n_gen_host) CK(hipMemcpyAsync(lens, n_gen_host, B * 4, hipMemcpyHostToDevice, e->stream));
     }
-    const RowSel rs{tab, own_d, cnt, seen, pen, thr, 0, rtab, img};
+    RowSel rs{tab, own_d, cnt, seen, pen, thr, 0, rtab, img, GuideSel{}};
+    RowGuide* gtab = nullptr;
+    int32_t* gstates = nullptr;
+    if (guide_ids_host) {
+        uint32_t* gmask = nullptr;
+        CK(sc.get(&gtab, DOTS_MAX_BATCH));
+        CK(sc.get(&gstates, DOTS_MAX_BATCH));
+        CK(sc.get(&gmask, (size_t)B * guide_mask_words(V)));
+        std::vector<RowGuide> rows(DOTS_MAX_BATCH, RowGuide{});
+        for (int b = 0; b < B; ++b) {
+            if (guide_ids_host[b] < 0) continue;
+            const DotsEngine::Guide& g = e->guides[guide_ids_host[b]];
+            rows[b] = RowGuide{g.table, g.accepting, g.n_states, g.start, states_host[b], 0};
+        }
+        CK(hipMemcpyAsync(gtab, rows.data(), DOTS_MAX_BATCH * sizeof(RowGuide), hipMemcpyHostToDevice, e->stream));
+        CK(hipMemcpyAsync(gstates, states_host, B * 4, hipMemcpyHostToDevice, e->stream));
+        CK(hipStreamSynchronize(e->stream));               // `rows` is a local
+        rs.guide = GuideSel{gtab, gmask, e->tok_off, e->tok_bytes, guide_mask_words(V), V};
+    }
     auto run = [&]() -> hipError_t {
+        if (rs.guide.rows) {
+            // every replay starts from the given states (a timed replay commits nothing: its rows are marked finished)
+            hipError_t r = launch_guide_set_states(e->stream, gtab, gstates, B);
+            if (r == hipSuccess) r = launch_guide_mask(e->stream, rs.guide, B, nullptr);
+            if (r != hipSuccess) return r;
+        }
         if (mode == 0) return launch_argmax_step(e->stream, logits_dev, V, V, B, pval, pidx, st);
         if (mode == 1) return launch_sample_step(e->stream, logits_dev, V, V, B, rp[0].temperature, rp[0].top_p, rp[0].seed, st);
         return launch_select_rows(e->stream, logits_dev, V, V, B, rs, pval, pidx, st);
@@ -2614,7 +2797,10 @@ int select_op(DotsEngine* e, const float* logits_dev, int B, int V, const DotsSa
     if (iters <= 0) {
         CK(run());
         CK(hipMemcpyAsync(out_tokens_dev, cur, B * 4, hipMemcpyDeviceToDevice, e->stream));
+        std::vector<RowGuide> after(states_out_host ? B : 0);
+        if (states_out_host) CK(hipMemcpyAsync(after.data(), gtab, B * sizeof(RowGuide), hipMemcpyDeviceToHost, e->stream));
         CK(hipStreamSynchronize(e->stream));
+        for (size_t b = 0; b < after.size(); ++b) states_out_host[b] = after[b].table ? after[b].state : -1;
         return DOTS_OK;
     }
     const std::vector<int32_t> ones(B, 1);
@@ -2662,6 +2848,22 @@ int dots_bench_select_tokens_rules(DotsEngine* e, const float* logits_dev, int B
                                    const int32_t* n_prompt_dev, int iters, float* ms_out) {
     if (!ms_out || iters < 1 || !rules_host) return e ? e->fail(DOTS_E_INVALID, "bad bench_select_tokens arguments") : DOTS_E_INVALID;
     return select_op(e, logits_dev, B, V, params_host, hist_dev, hist_lens_dev, hist_stride, n_prompt_dev, nullptr, 2, iters, ms_out, rules_host, n_gen_host);
+}
+
+int dots_op_select_tokens_guided(DotsEngine* e, const float* logits_dev, int B, int V, const DotsSamplingParams* params_host, const DotsLogitRules* rules_host,
+                                 const int32_t* n_gen_host, const int32_t* guide_ids_host, const int32_t* states_host, const int32_t* hist_dev,
+                                 const int32_t* hist_lens_dev, int hist_stride, const int32_t* n_prompt_dev, int32_t* out_tokens_dev, int32_t* states_out_host) {
+    if (!out_tokens_dev || !rules_host || !guide_ids_host) return e ? e->fail(DOTS_E_INVALID, "bad select_tokens arguments") : DOTS_E_INVALID;
+    return select_op(e, logits_dev, B, V, params_host, hist_dev, hist_lens_dev, hist_stride, n_prompt_dev, out_tokens_dev, 2, 0, nullptr, rules_host, n_gen_host,
+                     guide_ids_host, states_host, states_out_host);
+}
+
+int dots_bench_select_tokens_guided(DotsEngine* e, const float* logits_dev, int B, int V, const DotsSamplingParams* params_host, const DotsLogitRules* rules_host,
+                                    const int32_t* n_gen_host, const int32_t* guide_ids_host, const int32_t* states_host, const int32_t* hist_dev,
+                                    const int32_t* hist_lens_dev, int hist_stride, const int32_t* n_prompt_dev, int iters, float* ms_out) {
+    if (!ms_out || iters < 1 || !rules_host || !guide_ids_host) return e ? e->fail(DOTS_E_INVALID, "bad bench_select_tokens arguments") : DOTS_E_INVALID;
+    return select_op(e, logits_dev, B, V, params_host, hist_dev, hist_lens_dev, hist_stride, n_prompt_dev, nullptr, 2, iters, ms_out, rules_host, n_gen_host,
+                     guide_ids_host, states_host, nullptr);
 }
 
 }  // extern "C"

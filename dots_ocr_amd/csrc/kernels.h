@@ -134,6 +134,16 @@ struct RowParams { float temperature, top_p; int32_t top_k; float repetition_pen
 #endif
 enum { RULE_ON = 1, RULE_IMG = 2, RULE_IGNORE_EOS = 4 };
 struct RowRules { int32_t flags, min_tokens, n_stop, stop[DOTS_MAX_STOP_IDS]; };
+// Guided decoding.  A guide is a byte DFA in device memory: table [n_states][256] uint16 (GUIDE_DEAD = no transition; every other
+// entry < n_states) and accepting [n_states] uint8.  RowGuide: the guide a row holds (table == nullptr: none) and the state its automaton
+// is in; the commit of a token walks that token's bytes from it.  GuideSel: what a launch of the per-row stage needs to honour the guides —
+// the row table, the allowed bits guide_mask_kernel leaves ([rows][words] uint32, words = guide_mask_words(V): even, so that a wave's 64
+// bits are one aligned 8-byte store), and the packed bytes of every vocabulary entry (tok_off [V + 1], tok_bytes; an entry without bytes can
+// never be selected on a guided row).  rows == nullptr = no row of this launch is guided.
+constexpr uint16_t GUIDE_DEAD = 0xFFFF;
+struct RowGuide { const uint16_t* table; const uint8_t* accepting; int32_t n_states, start, state, _pad; };
+struct GuideSel { RowGuide* rows; uint32_t* mask; const int32_t* tok_off; const uint8_t* tok_bytes; int32_t words, V; };
+inline int guide_mask_words(int V) { return ((V + 63) / 64) * 2; }
 struct RowSel {
     const RowParams* params;
     const int32_t* own;
@@ -144,6 +154,7 @@ struct RowSel {
     int legacy_greedy;
     const RowRules* rules;      // [DOTS_MAX_BATCH], or nullptr = no row of this launch carries rules
     const float* rule_img;      // [rows][V] fp32: the bias of a token, -inf for a banned / not allowed one, 0 elsewhere
+    GuideSel guide;             // guide.rows == nullptr = no row of this launch is guided
 };
 // pval / pidx: ARGMAX_CHUNKS (64) partials per row, as launch_argmax_step
 hipError_t launch_select_rows(hipStream_t s, const float* logits, int V, int ld, int B, const RowSel& rs, float* pval, int32_t* pidx, const StepState& st);
@@ -162,6 +173,16 @@ hipError_t launch_set_row_params(hipStream_t s, RowParams* table, int32_t* own, 
 // bias_val are device arrays of ids in [0, V).
 hipError_t launch_set_row_rules(hipStream_t s, RowRules* table, float* img, int row, int V, const RowRules& r, const int32_t* allowed, int n_allowed,
                                 const int32_t* bias_ids, const float* bias_val, int n_bias);
+// ---- guided.hip: guided decoding
+// The allowed bits of every guided row of the launch (rows without a guide and rows that sel masks out are skipped), from each row's
+// current state: bit t = token t has bytes and walking them never leaves the automaton.  Runs before launch_select_rows.
+hipError_t launch_guide_mask(hipStream_t s, const GuideSel& g, int B, const int32_t* sel);
+// table[row] = g (with state = g.start), in stream order
+hipError_t launch_set_row_guide(hipStream_t s, RowGuide* table, int row, const RowGuide& g);
+// state = start for the n rows dst[0 .. n) (dst == nullptr: rows 0 .. n - 1) that hold a guide, in stream order (a prefill)
+hipError_t launch_guide_reset_rows(hipStream_t s, RowGuide* table, const int32_t* dst, int n);
+// table[row].state = state for rows [0, n) (explicit states of dots_op_select_tokens_guided)
+hipError_t launch_guide_set_states(hipStream_t s, RowGuide* table, const int32_t* states, int n);
 
 // ---- logprobs.hip: log-probabilities of the raw logits of every selected row
 #ifndef DOTS_MAX_TOP_LOGPROBS

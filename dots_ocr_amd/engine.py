@@ -291,6 +291,15 @@ def _prototypes(lib):
         "dots_set_row_logit_rules": (i32, [vp, i32, P(CDotsLogitRules)]),
         "dots_op_select_tokens_rules": (i32, [vp, vp, i32, i32, P(CDotsSamplingParams), P(CDotsLogitRules), P(i32), vp, vp, i32, vp, vp]),
         "dots_bench_select_tokens_rules": (i32, [vp, vp, i32, i32, P(CDotsSamplingParams), P(CDotsLogitRules), P(i32), vp, vp, i32, vp, i32, P(f32)]),
+        "dots_set_token_bytes": (i32, [vp, P(i32), vp]),
+        "dots_guide_create": (i32, [vp, vp, i32, vp, i32, P(i32)]),
+        "dots_guide_destroy": (i32, [vp, i32]),
+        "dots_set_row_guide": (i32, [vp, i32, i32]),
+        "dots_row_guide_state": (i32, [vp, i32, P(i32)]),
+        "dots_op_select_tokens_guided": (i32, [vp, vp, i32, i32, P(CDotsSamplingParams), P(CDotsLogitRules), P(i32), P(i32), P(i32), vp, vp, i32, vp, vp,
+                                               P(i32)]),
+        "dots_bench_select_tokens_guided": (i32, [vp, vp, i32, i32, P(CDotsSamplingParams), P(CDotsLogitRules), P(i32), P(i32), P(i32), vp, vp, i32, vp,
+                                                  i32, P(f32)]),
         "dots_set_row_logprobs": (i32, [vp, i32, i32]),
         "dots_row_logprobs": (i32, [vp, i32, i32, i32, P(f32), P(i32), P(f32), P(i32)]),
         "dots_op_logprobs": (i32, [vp, vp, i32, i32, i32, P(i32), vp, vp, vp, vp]),
@@ -319,6 +328,8 @@ EXPORTED_SYMBOLS = [
     "dots_set_row_sampling", "dots_op_select_tokens", "dots_bench_select_tokens",
     "dots_set_row_logprobs", "dots_row_logprobs", "dots_op_logprobs", "dots_bench_logprobs",
     "dots_set_row_logit_rules", "dots_op_select_tokens_rules", "dots_bench_select_tokens_rules",
+    "dots_set_token_bytes", "dots_guide_create", "dots_guide_destroy", "dots_set_row_guide", "dots_row_guide_state",
+    "dots_op_select_tokens_guided", "dots_bench_select_tokens_guided",
 ]
 
 MAX_TOP_LOGPROBS = 20                        # DOTS_MAX_TOP_LOGPROBS: top entries kept per position
@@ -399,6 +410,7 @@ class Engine:
         if rc != 0:
             raise DotsEngineError(f"dots_create failed ({rc}): {self.lib.dots_last_error(None).decode()}")
         self.h = h
+        self.token_bytes = None                  # guided.TokenBytes once set_token_bytes has run
 
     # ------------------------------------------------------------------ plumbing
     def _ck(self, rc: int, what: str):
@@ -618,6 +630,79 @@ class Engine:
         self._ck(self.lib.dots_bench_select_tokens_rules(self.h, logits, int(B), int(V), arr, rarr, None if ng is None else _i32p(ng), hist,
                                                          hist_lens, int(hist_stride), n_prompt, int(iters), C.byref(ms)),
                  "dots_bench_select_tokens_rules")
+        return float(ms.value)
+
+    # ------------------------------------------------------------------ guided decoding
+    def set_token_bytes(self, tokens, special_ids: Sequence[int] = ()):
+        """The bytes of every vocabulary entry, once per engine: a guided.TokenBytes, or a sequence of vocab_size bytes objects.  Ids in
+        special_ids (chat and image tokens) and entries without bytes can never be selected on a guided row."""
+        from .guided import TokenBytes
+        tb = tokens if isinstance(tokens, TokenBytes) and not special_ids else TokenBytes(
+            [tokens.token(t) for t in range(tokens.vocab_size)] if isinstance(tokens, TokenBytes) else tokens, special_ids)
+        if tb.vocab_size != self.cfg.vocab_size:
+            raise ValueError(f"token bytes for {tb.vocab_size} entries, the engine's vocabulary has {self.cfg.vocab_size}")
+        off = np.ascontiguousarray(tb.offsets, dtype=np.int32)
+        data = np.ascontiguousarray(tb.data, dtype=np.uint8)
+        self._ck(self.lib.dots_set_token_bytes(self.h, _i32p(off), data.ctypes.data_as(C.c_void_p) if data.size else None), "dots_set_token_bytes")
+        self.token_bytes = tb
+
+    def create_guide(self, guide) -> int:
+        """Upload a guided.Guide; returns the handle set_row_guide takes.  Any number of rows may hold one guide."""
+        table = np.ascontiguousarray(guide.table, dtype=np.uint16)
+        acc = np.ascontiguousarray(guide.accepting, dtype=np.uint8)
+        if table.ndim != 2 or table.shape[1] != 256 or acc.shape != (table.shape[0],):
+            raise ValueError("a guide's table must be uint16 [S, 256] with accepting uint8 [S]")
+        gid = C.c_int32(-1)
+        self._ck(self.lib.dots_guide_create(self.h, table.ctypes.data_as(C.c_void_p), int(table.shape[0]), acc.ctypes.data_as(C.c_void_p),
+                                            int(guide.start), C.byref(gid)), "dots_guide_create")
+        return int(gid.value)
+
+    def destroy_guide(self, handle: int):
+        """Free a guide; refused (DotsEngineError) while a row holds it."""
+        self._ck(self.lib.dots_guide_destroy(self.h, int(handle)), "dots_guide_destroy")
+
+    def set_row_guide(self, row: int, handle: Optional[int]):
+        """Row `row` (a slot, or sequence `row` of a static batch) follows the guide from its start state, from the next selected token on
+        (set, then prefill: the prefill starts the automaton over and selects its first token under the guide); None clears.  Captured
+        decode graphs are kept; slot release and slots_reset clear the row.  Needs set_token_bytes first."""
+        self._ck(self.lib.dots_set_row_guide(self.h, int(row), -1 if handle is None else int(handle)), "dots_set_row_guide")
+
+    def row_guide_state(self, row: int) -> int:
+        """the state of the row's automaton, -1 for a row without a guide"""
+        st = C.c_int32(-1)
+        self._ck(self.lib.dots_row_guide_state(self.h, int(row), C.byref(st)), "dots_row_guide_state")
+        return int(st.value)
+
+    def _guided_args(self, B, params, rules, n_gen, guides, states):
+        if len(params) != B or len(rules) != B or len(guides) != B or len(states) != B:
+            raise ValueError("one SamplingParams, LogitRules (or None), guide handle (or None) and state per row")
+        arr = (CDotsSamplingParams * B)(*[p.to_c() for p in params])
+        rarr = self._rules_array(rules)
+        ng = None if n_gen is None else np.ascontiguousarray(n_gen, dtype=np.int32)
+        gid = np.ascontiguousarray([-1 if g is None else int(g) for g in guides], dtype=np.int32)
+        st = np.ascontiguousarray([0 if g is None else int(s) for g, s in zip(guides, states)], dtype=np.int32)
+        return arr, rarr, ng, gid, st
+
+    def select_tokens_guided(self, logits, B: int, V: int, params: Sequence[SamplingParams], rules: Sequence[Optional["LogitRules"]],
+                             n_gen: Optional[Sequence[int]], guides: Sequence[Optional[int]], states: Sequence[int], hist, hist_lens,
+                             hist_stride: int, n_prompt, out_tokens) -> np.ndarray:
+        """select_tokens_rules with a guide handle (None = an unguided row) and an explicit automaton state per row; V must be the engine's
+        vocabulary.  Returns the rows' states after the commit (-1 for an unguided row)."""
+        arr, rarr, ng, gid, st = self._guided_args(B, params, rules, n_gen, guides, states)
+        out = np.full((B,), -1, np.int32)
+        self._ck(self.lib.dots_op_select_tokens_guided(self.h, logits, int(B), int(V), arr, rarr, None if ng is None else _i32p(ng), _i32p(gid), _i32p(st),
+                                                       hist, hist_lens, int(hist_stride), n_prompt, out_tokens, _i32p(out)), "dots_op_select_tokens_guided")
+        return out
+
+    def bench_select_tokens_guided(self, logits, B: int, V: int, params: Sequence[SamplingParams], rules: Sequence[Optional["LogitRules"]],
+                                   n_gen: Optional[Sequence[int]], guides: Sequence[Optional[int]], states: Sequence[int], hist, hist_lens,
+                                   hist_stride: int, n_prompt, iters: int) -> float:
+        """mean ms of one per-row selection stage with these guides, the mask kernel included"""
+        arr, rarr, ng, gid, st = self._guided_args(B, params, rules, n_gen, guides, states)
+        ms = C.c_float()
+        self._ck(self.lib.dots_bench_select_tokens_guided(self.h, logits, int(B), int(V), arr, rarr, None if ng is None else _i32p(ng), _i32p(gid),
+                                                          _i32p(st), hist, hist_lens, int(hist_stride), n_prompt, int(iters), C.byref(ms)),
+                 "dots_bench_select_tokens_guided")
         return float(ms.value)
 
     def set_row_logprobs(self, row: int, top_n: Optional[int]):

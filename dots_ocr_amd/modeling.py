@@ -132,7 +132,8 @@ class DotsOcrHipForCausalLM:
                  top_p: Optional[float] = None, seed: int = 0, eos_token_id=None, pad_token_id=None, continuous: Optional[bool] = None,
                  top_k: Optional[int] = None, repetition_penalty: Optional[float] = None, frequency_penalty: Optional[float] = None,
                  presence_penalty: Optional[float] = None, logit_bias=None, allowed_token_ids=None, min_tokens: int = 0,
-                 stop_token_ids=None, ignore_eos: bool = False, **_):
+                 stop_token_ids=None, ignore_eos: bool = False, guided_regex=None, guided_choice=None, guided_json=None,
+                 guided_whitespace_pattern=None, **_):
         """HF-shaped generate.  do_sample / temperature / top_p default to the checkpoint's generation_config.json (greedy when it
         is absent); with sampling on, tokens are drawn on the GPU from softmax(logits / temperature) restricted to the top_p
         nucleus, reproducibly from `seed`.  Returns LongTensor
@@ -149,7 +150,11 @@ class DotsOcrHipForCausalLM:
 
         logit_bias ({id: value}, -inf = a ban) / allowed_token_ids / min_tokens / stop_token_ids / ignore_eos (vLLM SamplingParams) give
         every sequence the same LogitRules (Engine.set_row_logit_rules, DESIGN §6.3) and switch to per-row selection in the same way;
-        a stop id ends its sequence as an EOS does and is kept as its last token."""
+        a stop id ends its sequence as an EOS does and is kept as its last token.
+
+        guided_regex / guided_choice / guided_json (at most one; guided_whitespace_pattern with the last) compile to one guide that every
+        sequence follows on the GPU (dots_ocr_amd/guided.py, Engine.set_row_guide); the engine needs its token bytes first
+        (Engine.set_token_bytes).  A sequence ends with an EOS id once its text matches; cut at max_new_tokens it is a prefix of a match."""
         import dataclasses
         import torch
         t_eff, p_eff = resolve_sampling(self.generation_config, do_sample, temperature, top_p)
@@ -176,6 +181,33 @@ class DotsOcrHipForCausalLM:
 
                 def row_sp(b):
                     return dataclasses.replace(base, seed=int(seed) + b)
+        from .guided import compile_request
+        guide_obj = compile_request(guided_regex, guided_choice, guided_json, whitespace=guided_whitespace_pattern)
+        guide = None
+        if guide_obj is not None:
+            if getattr(self.engine, "token_bytes", None) is None:
+                raise ValueError("guided decoding needs the vocabulary's bytes: call engine.set_token_bytes(...) once (DotsOcrProcessor.token_bytes)")
+            if row_sp is None:                   # a sampled guided row draws with seed + b as the ruled rows do
+                from .engine import SamplingParams
+                base = SamplingParams(temperature=t_eff, top_p=p_eff, seed=seed)
+
+                def row_sp(b):
+                    return dataclasses.replace(base, seed=int(seed) + b)
+            guide = self.engine.create_guide(guide_obj)
+        try:
+            return self._generate(input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens, eos_token_id, pad_token_id, continuous,
+                                  row_sp, rules, guide)
+        finally:
+            if guide is not None:
+                try:
+                    self.engine.destroy_guide(guide)
+                except Exception as e:               # a run that failed with rows still holding the guide: its own error is the one to
+                    import warnings                  # raise; the handle stays until the rows are cleared (slots_reset)
+                    warnings.warn(f"guide {guide} could not be destroyed: {e}")
+
+    def _generate(self, input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens, eos_token_id, pad_token_id, continuous, row_sp, rules,
+                  guide):
+        import torch
         ids = input_ids.detach().cpu().numpy()
         B, T = ids.shape
         mask = attention_mask.detach().cpu().numpy().astype(bool) if attention_mask is not None else np.ones_like(ids, bool)
@@ -230,9 +262,9 @@ class DotsOcrHipForCausalLM:
                     lo, hi = int(patch_off[img_of_seq[b][0]]), int(patch_off[img_of_seq[b][-1] + 1])
                     pix = pv_dev[lo:hi] if pv_dev is not None else pv_host[lo:hi]
                     reqs.append(Request(prompts[b], pix, grid[img_of_seq[b][0]:img_of_seq[b][-1] + 1], max_new_tokens,
-                                        sampling=row_sp(b) if row_sp else None, rules=rules))
+                                        sampling=row_sp(b) if row_sp else None, rules=rules, guide=guide))
                 else:
-                    reqs.append(Request(prompts[b], None, None, max_new_tokens, sampling=row_sp(b) if row_sp else None, rules=rules))
+                    reqs.append(Request(prompts[b], None, None, max_new_tokens, sampling=row_sp(b) if row_sp else None, rules=rules, guide=guide))
             outs = ContinuousBatcher(self.engine, eos_ids=eos).run(reqs)
             for b, o in enumerate(outs):
                 new_tokens[b, :len(o)] = o
@@ -265,6 +297,8 @@ class DotsOcrHipForCausalLM:
                         self.engine.set_row_sampling(j, row_sp(b))
                         if rules is not None:
                             self.engine.set_row_logit_rules(j, rules)
+                        if guide is not None:
+                            self.engine.set_row_guide(j, guide)
                     rows_set = max(rows_set, len(sl))
                 lens = np.array([len(prompts[b]) for b in sl], np.int32)
                 packed = np.concatenate([prompts[b] for b in sl])
@@ -296,6 +330,8 @@ class DotsOcrHipForCausalLM:
                 self.engine.set_row_sampling(j, None)
                 if rules is not None:
                     self.engine.set_row_logit_rules(j, None)
+                if guide is not None:
+                    self.engine.set_row_guide(j, None)
         full = np.concatenate([ids.astype(np.int64), new_tokens[:, :n_max]], axis=1)    # HF stops at the longest sequence
         res = torch.from_numpy(full)
         return res.to(input_ids.device) if input_ids.is_cuda else res

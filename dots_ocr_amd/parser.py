@@ -33,8 +33,11 @@ class DotsOCRParser:
     def __init__(self, protocol="http", ip="localhost", port=8000, model_name="model", temperature=0.1, top_p=1.0,
                  max_completion_tokens=16384, num_thread=64, dpi=200, output_dir="./output", min_pixels=None,
                  max_pixels=None, use_hf=False, model_path="./weights/DotsOCR", model=None, processor=None,
-                 hf_max_new_tokens=24000):
+                 hf_max_new_tokens=24000, guided=False):
         self.dpi = dpi
+        # guided: opt-in guided decoding for the two layout prompt modes: the server request carries guided_layout, the
+        # in-process model generates under guided.layout_schema().  Off by default: the output is then exactly what it was.
+        self.guided = bool(guided)
         self.protocol, self.ip, self.port, self.model_name = protocol, ip, port, model_name
         self.temperature, self.top_p, self.max_completion_tokens = temperature, top_p, max_completion_tokens
         self.num_thread = num_thread
@@ -72,9 +75,20 @@ class DotsOCRParser:
             flat.extend(imgs)
         return self.processor(text=texts, images=flat, videos=None, padding=True, return_tensors="pt")
 
+    def _guided_layout(self, prompts) -> bool:
+        """guided decoding applies: the switch is on and every prompt is one of the layout modes' (their output is the layout array)"""
+        layout = {dict_promptmode_to_prompt[m] for m in ("prompt_layout_all_en", "prompt_layout_only_en")}
+        return self.guided and all(p in layout for p in prompts)
+
     def _inference_batch_with_hf(self, images, prompts) -> List[str]:
         inputs = self._build_inputs(images, prompts)
-        generated = self.model.generate(**inputs, max_new_tokens=self.hf_max_new_tokens)
+        kw = {}
+        if self._guided_layout(prompts):
+            from .guided import layout_schema
+            if getattr(self.model.engine, "token_bytes", None) is None:
+                self.model.engine.set_token_bytes(self.processor.guide_token_bytes())
+            kw["guided_json"] = layout_schema()
+        generated = self.model.generate(**inputs, max_new_tokens=self.hf_max_new_tokens, **kw)
         trimmed = [out[len(inp):] for inp, out in zip(inputs.input_ids, generated)]
         return self.processor.batch_decode(trimmed, skip_special_tokens=True, clean_up_tokenization_spaces=False)
 
@@ -85,7 +99,8 @@ class DotsOCRParser:
         from dots_ocr.model.inference import inference_with_vllm
         return inference_with_vllm(image, prompt, model_name=self.model_name, protocol=self.protocol, ip=self.ip,
                                    port=self.port, temperature=self.temperature, top_p=self.top_p,
-                                   max_completion_tokens=self.max_completion_tokens)
+                                   max_completion_tokens=self.max_completion_tokens,
+                                   **({"extra_body": {"guided_layout": True}} if self._guided_layout([prompt]) else {}))
 
     # ------------------------------------------------------------------ per-page pipeline
     def get_prompt(self, prompt_mode, bbox=None, origin_image=None, image=None, min_pixels=None, max_pixels=None):

@@ -150,13 +150,17 @@ class HFJsonTokenizer:
     def decode(self, ids: Sequence[int], skip_special_tokens: bool = True) -> str:
         return self.tk.decode([int(i) for i in ids], skip_special_tokens=skip_special_tokens)
 
+    def added_tokens(self) -> dict:
+        """id -> content of the added / special tokens (read from the tokenizer on first use)"""
+        if self._added is None:
+            self._added = {int(i): a.content for i, a in self.tk.get_added_tokens_decoder().items()}
+        return self._added
+
     def token_bytes(self, token_id: int) -> bytes:
         """raw bytes of one vocabulary entry: byte-level BPE tokens through the byte <-> unicode table, added / special tokens as the
         UTF-8 of their content"""
         t = int(token_id)
-        if self._added is None:
-            self._added = {int(i): a.content for i, a in self.tk.get_added_tokens_decoder().items()}
-        if t in self._added:
+        if t in self.added_tokens():
             return self._added[t].encode("utf-8")
         tok = self.tk.id_to_token(t)
         return b"" if tok is None else byte_level_token_bytes(tok)
@@ -332,3 +336,17 @@ class DotsOcrProcessor:
     def token_bytes(self, token_id: int) -> bytes:
         """raw bytes of one token (the `bytes` field of an OpenAI logprobs entry)"""
         return self.tokenizer.token_bytes(token_id)
+
+    def guide_token_bytes(self):
+        """The byte image of the whole vocabulary for guided decoding (Engine.set_token_bytes): guided.TokenBytes with the
+        chat / image / added tokens (and, for the synthetic tokenizer, every id that is no byte) marked special — a guide never allows
+        them."""
+        from .guided import TokenBytes
+        V = self.cfg.vocab_size
+        toks = [self.token_bytes(t) for t in range(V)]
+        if isinstance(self.tokenizer, SyntheticByteTokenizer):
+            special = range(256, V)
+        else:
+            added = self.tokenizer.added_tokens() if hasattr(self.tokenizer, "added_tokens") else {}
+            special = set(added) | {self.cfg.image_token_id, *self.cfg.eos_token_ids}
+        return TokenBytes(toks, special)

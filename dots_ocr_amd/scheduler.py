@@ -33,6 +33,7 @@ class Request:
     logprobs: Optional[int] = None              # top_n (0..20) of per-token log-probabilities to return, None = off; a finished request
                                                 # then carries logprobs_out = Engine.row_logprobs(slot, its token count)
     rules: Optional[object] = None              # engine.LogitRules of this request (bias, allowed ids, min_tokens, stop ids, ignore_eos), or None
+    guide: Optional[int] = None                 # handle of Engine.create_guide the request's output must follow, or None
 
     def n_patches(self) -> int:
         if self.grid_thw is None:
@@ -80,6 +81,7 @@ class ContinuousBatcher:
         self._row_params: Dict[int, object] = {}                 # slot -> the SamplingParams set on it (engine.set_row_sampling)
         self._row_lp: Dict[int, int] = {}                        # slot -> the logprobs top_n set on it (engine.set_row_logprobs)
         self._row_rules: Dict[int, object] = {}                  # slot -> the LogitRules set on it (engine.set_row_logit_rules)
+        self._row_guide: Dict[int, int] = {}                     # slot -> the guide handle set on it (engine.set_row_guide)
         self.kv_truncated = 0                                    # sequences ended early by a dry KV pool (finish reason "kv_pool_exhausted")
         self._rejected: List[Tuple[int, Request]] = []           # requests whose own parameters the engine refused (reported by step())
         self.eos_ids = tuple(int(t) for t in eos_ids)
@@ -103,6 +105,8 @@ class ContinuousBatcher:
             raise ValueError(f"request has {req.n_patches()} vision patches, more than max_patches={self.max_patches}")
         if req.rules is not None and not hasattr(self.engine, "set_row_logit_rules"):
             raise ValueError("this engine cannot honour logit rules (no set_row_logit_rules)")
+        if req.guide is not None and not hasattr(self.engine, "set_row_guide"):
+            raise ValueError("this engine cannot honour a guide (no set_row_guide)")
         if req.rules is not None and hasattr(req.rules, "eos_ids"):
             # what the engine will check at admission, checked here against the EOS ids and the vocabulary this batcher runs under: rules
             # that could never select a token are refused before the request is queued, where it fails alone
@@ -200,6 +204,8 @@ class ContinuousBatcher:
                 self.engine.set_row_logprobs(s, None)
             if self._row_rules.pop(s, None) is not None:
                 self.engine.set_row_logit_rules(s, None)
+            if self._row_guide.pop(s, None) is not None:
+                self.engine.set_row_guide(s, None)
 
     def _set_rows(self, s, r):
         """per-row parameters of request r on slot s; they apply from the first token the prefill selects"""
@@ -218,6 +224,11 @@ class ContinuousBatcher:
             self.engine.set_row_logit_rules(s, r.rules)
         elif self._row_rules.pop(s, None) is not None:
             self.engine.set_row_logit_rules(s, None)
+        if r.guide is not None:                      # the guide likewise: the row is set before its prefill, which starts the automaton
+            self._row_guide[s] = r.guide
+            self.engine.set_row_guide(s, r.guide)
+        elif self._row_guide.pop(s, None) is not None:
+            self.engine.set_row_guide(s, None)
 
     def _prefill(self, group, rows_set: bool = False):
         # image rows are consumed in packed order, so sequences with images keep their relative order: pack the group as is
@@ -358,6 +369,7 @@ class ContinuousBatcher:
                     req.logprobs_out = self.engine.row_logprobs(s, len(toks))
                 done.append((rid, req, toks))
                 self.engine.slot_release(s)
+                self._row_guide.pop(s, None)         # the release cleared the row's guide: its handle is free to be evicted
         self._last_lens = {s: int(lens[s]) for s in self.running}      # after the finished slots have left: only what is still decoding
         return done
 

@@ -27,6 +27,7 @@ import queue
 import threading
 import time
 import uuid
+from collections import OrderedDict
 from concurrent.futures import Future
 from typing import List, Optional
 
@@ -37,7 +38,7 @@ from .processing import ASSISTANT, END_USER, IMG_END, IMG_PAD, IMG_START, USER
 
 class _Job:
     __slots__ = ("image", "text", "max_tokens", "temperature", "top_p", "top_k", "repetition_penalty", "frequency_penalty",
-                 "presence_penalty", "seed", "logprobs", "rules", "future")
+                 "presence_penalty", "seed", "logprobs", "rules", "guide", "future")
 
     def __init__(self, image, text, max_tokens, temperature, top_p, top_k=0, repetition_penalty=1.0, frequency_penalty=0.0,
                  presence_penalty=0.0, seed=None, logprobs=None):
@@ -46,6 +47,7 @@ class _Job:
         self.frequency_penalty, self.presence_penalty, self.seed = frequency_penalty, presence_penalty, seed
         self.logprobs = logprobs                    # top_logprobs (0..20) when the request asked for logprobs, else None
         self.rules = None                           # engine.LogitRules when the request carries logit rules, else None
+        self.guide = None                           # guided.Guide when the request carries a guided decoding field, else None
         self.future: Future = Future()
 
     @property
@@ -145,6 +147,14 @@ class ContinuousWorker(BatchingWorker):
         # beside the occupied slots.  Measured on A4 pages of mixed output length (tools/serve_bench.py, profiles/r04_serve_bench_a4_*.json):
         # 8 slots 3.26 -> 3.50 pages/s with k = 2, 16 slots 4.13 -> 4.36 with k = 8; identical tokens.  0 switches it off.
         self.look_ahead = (2 if max_batch <= 8 else min(8, max_batch // 2)) if look_ahead is None else max(0, int(look_ahead))
+        # guided decoding: the vocabulary's bytes go to the engine once, here; compiled guides are kept as engine handles in a
+        # small LRU keyed by pattern (_guide_handle), a handle is evicted only when no request in flight uses it
+        self._guides: "OrderedDict[str, int]" = OrderedDict()
+        self._guide_users: dict = {}
+        engine = getattr(model, "engine", None)
+        if engine is not None and hasattr(engine, "set_token_bytes") and getattr(engine, "token_bytes", None) is None \
+                and hasattr(processor, "guide_token_bytes"):
+            engine.set_token_bytes(processor.guide_token_bytes())
         super().__init__(model, processor, max_batch=max_batch, max_wait_ms=max_wait_ms, seed=seed)
 
     @staticmethod
@@ -177,9 +187,37 @@ class ContinuousWorker(BatchingWorker):
         """the engine takes per-request logit rules (Engine.set_row_logit_rules)"""
         return hasattr(self.model.engine, "set_row_logit_rules")
 
+    GUIDE_CACHE = 16                                 # compiled guides kept on the engine
+
+    @property
+    def has_guides(self) -> bool:
+        """the engine takes guides and knows its vocabulary's bytes (Engine.set_row_guide / set_token_bytes)"""
+        return hasattr(self.model.engine, "set_row_guide") and getattr(self.model.engine, "token_bytes", None) is not None
+
+    def _guide_handle(self, job: _Job) -> Optional[int]:
+        """the engine handle of the job's guide, compiled guides cached per pattern (worker thread only)"""
+        if job.guide is None:
+            return None
+        key = job.guide.pattern
+        h = self._guides.get(key)
+        if h is None:
+            for old in [k for k in self._guides if not self._guide_users.get(self._guides[k])][:max(0, len(self._guides) + 1 - self.GUIDE_CACHE)]:
+                self.model.engine.destroy_guide(self._guides.pop(old))       # no request in flight uses it, so no row holds it
+            h = self._guides[key] = self.model.engine.create_guide(job.guide)
+        self._guides.move_to_end(key)
+        self._guide_users[h] = self._guide_users.get(h, 0) + 1
+        return h
+
+    def _guide_done(self, req):
+        h = getattr(req, "guide", None)
+        if h is not None and self._guide_users.get(h, 0) > 0:
+            self._guide_users[h] -= 1
+
     def _finish(self, job: _Job, prompt_tokens: int, toks, kv_truncated: bool = False, logprobs=None):
         eos = set(self.model.config.eos_token_ids)
-        if job.rules is not None:                    # the request's own stop ids end it as an EOS does; ignore_eos takes the EOS ids out
+        if job.guide is not None:                    # a guided row ends at an EOS id whether or not ignore_eos is set
+            eos = eos | (set(job.rules.stop) if job.rules is not None else set())
+        elif job.rules is not None:                    # the request's own stop ids end it as an EOS does; ignore_eos takes the EOS ids out
             eos = (set() if job.rules.ignore_eos else eos) | set(job.rules.stop)
         toks = [int(t) for t in toks]
         text = self.processor.batch_decode([toks], skip_special_tokens=True, clean_up_tokenization_spaces=False)[0]
@@ -234,14 +272,21 @@ class ContinuousWorker(BatchingWorker):
                         inputs = self.processor(text=[job.text], images=[job.image] if job.image is not None else None,
                                                 padding=True, return_tensors="pt")
                         ids = inputs["input_ids"][0].numpy()
-                        cb.submit(Request(ids, inputs.get("pixel_values"), None if "image_grid_thw" not in inputs
-                                          else inputs["image_grid_thw"].numpy(), job.max_tokens, tag=job,
-                                          sampling=self._row_params(job) if per_row else None, logprobs=job.logprobs, rules=job.rules))
+                        req = Request(ids, inputs.get("pixel_values"), None if "image_grid_thw" not in inputs
+                                      else inputs["image_grid_thw"].numpy(), job.max_tokens, tag=job,
+                                      sampling=self._row_params(job) if per_row else None, logprobs=job.logprobs, rules=job.rules,
+                                      guide=self._guide_handle(job))
+                        try:
+                            cb.submit(req)
+                        except Exception:
+                            self._guide_done(req)
+                            raise
                         admitted += 1
                     except Exception as e:                           # a bad request fails alone
                         job.future.set_exception(e)
                 if cb is not None and not cb.idle:
                     for _, req, toks in cb.step():
+                        self._guide_done(req)
                         if getattr(req, "error", None) is not None:      # refused at admission: this request alone
                             req.tag.future.set_exception(req.error)
                             continue
@@ -255,6 +300,7 @@ class ContinuousWorker(BatchingWorker):
                         if not req.tag.future.done():
                             req.tag.future.set_exception(e)
                 cb, key = None, None
+                self._guide_users.clear()                            # the next ContinuousBatcher resets the slots: no row holds a guide
 
 
 def _load_request_image(url: str, allow_remote: bool, allow_local: bool):
@@ -355,6 +401,48 @@ def _logprob_fields(req: dict) -> Optional[int]:
         if not 0 <= top <= MAX_TOP_LOGPROBS:
             raise ValueError(f"top_logprobs must be in [0, {MAX_TOP_LOGPROBS}]")
     return (top or 0) if lp else None
+
+
+GUIDE_FIELDS = ("guided_regex", "guided_choice", "guided_json", "guided_layout", "guided_whitespace_pattern", "response_format")
+
+
+def _guide_fields(req: dict, min_tokens: int = 0):
+    """`guided_regex`, `guided_choice`, `guided_json` (object or JSON string) with `guided_whitespace_pattern` (vLLM),
+    `response_format: {"type": "json_schema", "json_schema": {"schema": ...}}` (OpenAI) and this server's `guided_layout: true`
+    (guided.layout_schema) -> the compiled guided.Guide, or None when the request carries none.  At most one of them; a compile error, a
+    recursive format ({"type": "json_object"}) and a `min_tokens` above the guide's shortest match raise ValueError (a 400).  The
+    min_tokens test is a cheap sufficient one in bytes: a match shorter than min_tokens bytes could end before min_tokens tokens, where
+    the EOS is still forbidden and nothing else is allowed; a longer shortest match cannot."""
+    from .guided import compile_request
+    rf = req.get("response_format")
+    schema = None
+    if rf is not None:
+        if not isinstance(rf, dict):
+            raise ValueError("response_format must be an object")
+        kind = rf.get("type")
+        if kind == "json_object":
+            raise ValueError("response_format json_object: free-form JSON is recursive; give a schema")
+        if kind == "json_schema":
+            js = rf.get("json_schema")
+            if not isinstance(js, dict) or not isinstance(js.get("schema"), dict):
+                raise ValueError("response_format json_schema needs json_schema.schema")
+            schema = js["schema"]
+        elif kind not in (None, "text"):
+            raise ValueError(f"unsupported response_format type {kind!r}")
+    gj = req.get("guided_json")
+    if gj is not None and schema is not None:
+        raise ValueError("at most one of the guided decoding fields may be given, got guided_json, response_format")
+    if gj is not None and not isinstance(gj, (dict, str)):
+        raise ValueError("guided_json must be a schema object or a JSON string")
+    layout = req.get("guided_layout")
+    if layout is not None and not isinstance(layout, bool):
+        raise ValueError("guided_layout must be true or false")
+    guide = compile_request(req.get("guided_regex"), req.get("guided_choice"), gj if gj is not None else schema, bool(layout),
+                            whitespace=req.get("guided_whitespace_pattern"))
+    if guide is not None and min_tokens > guide.min_length:
+        raise ValueError(f"min_tokens={min_tokens} exceeds the guide's shortest match ({guide.min_length} bytes): the row could be left "
+                         "with nothing to select")
+    return guide
 
 
 RULE_FIELDS = ("logit_bias", "allowed_token_ids", "min_tokens", "stop_token_ids", "ignore_eos")
@@ -476,6 +564,14 @@ def create_app(model, processor, model_name: str = "model", max_batch: int = 8, 
         if job.rules is not None and not (isinstance(worker, ContinuousWorker) and worker.has_rules):
             raise HTTPException(400, "logit_bias, allowed_token_ids, min_tokens, stop_token_ids and ignore_eos need continuous batching on an "
                                      "engine with per-row logit rules (Engine.set_row_logit_rules)")
+        if any(req.get(k) is not None for k in GUIDE_FIELDS):
+            try:                                     # compiling a large schema takes a while: off the event loop
+                job.guide = await run_in_threadpool(_guide_fields, req, job.rules.min_tokens if job.rules is not None else 0)
+            except (TypeError, ValueError) as e:
+                raise HTTPException(400, f"bad guided decoding parameters: {e}")
+            if job.guide is not None and not (isinstance(worker, ContinuousWorker) and worker.has_guides):
+                raise HTTPException(400, "guided_regex, guided_choice, guided_json, guided_layout and a json_schema response_format need "
+                                         "continuous batching on an engine with guides (Engine.set_row_guide) that knows its token bytes")
         fut = worker.submit(job)
         try:
             res = await run_in_threadpool(fut.result)

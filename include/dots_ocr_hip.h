@@ -229,6 +229,37 @@ typedef struct DotsLogitRules {
  * are those set at the call.  Should a row end up all -inf all the same (EOS ids changed later), it commits the lowest index, id 0. */
 int dots_set_row_logit_rules(DotsEngine* e, int row, const DotsLogitRules* r);
 
+/* ---- Guided decoding: a row's output follows a byte automaton that lives on the device and advances at every commit, so
+ * that it holds inside captured decode chunks.  The host compiles a pattern to a trimmed DFA (dots_ocr_amd/guided.py).
+ *
+ * dots_set_token_bytes  the packed UTF-8 bytes of every vocabulary entry: offsets_host int32 [vocab + 1] (offsets[0] = 0, non-decreasing),
+ *                       bytes_host the offsets[vocab] bytes.  An entry without bytes (give the special ids none) can never be selected on a
+ *                       guided row.  Once per engine; DOTS_E_STATE while a row holds a guide.  Synchronises.
+ * dots_guide_create     table_host uint16 [n_states][256] (0xFFFF = no transition, every other entry < n_states), accepting_host uint8
+ *                       [n_states], start; n_states <= DOTS_MAX_GUIDE_STATES.  The automaton must be TRIMMED: from every state an accepting
+ *                       one is reachable (then "the walk never meets 0xFFFF" is the whole test of a token).  Copied to device memory;
+ *                       *id_out names it.  Any number of rows may hold one guide.  Synchronises.
+ * dots_guide_destroy    DOTS_E_STATE while a row holds it.  Synchronises.
+ * dots_set_row_guide    row `row` follows guide id from its start state (id < 0: none), written in stream order by a one-thread kernel:
+ *                       captured decode graphs are kept (one more graph per step shape exists for "some row holds a guide").  A following
+ *                       dots_prefill / dots_slots_prefill of the row starts the automaton over; the prefill's first token is already
+ *                       selected under the guide.  dots_slot_release / dots_slots_reset clear the row.  DOTS_E_STATE before
+ *                       dots_set_token_bytes.  The first call allocates the allowed bits (max_batch x vocab / 8 bytes) and the row table.
+ * dots_row_guide_state  the state the row's automaton is in (-1: the row holds no guide).  Synchronises.
+ *
+ * A guided row at state s: token t is allowed iff it has bytes and walking them from s never leaves the automaton; the engine's EOS ids and
+ * the row's stop ids are allowed iff s is accepting; every other id is -inf.  This enters where the allowed list of DotsLogitRules does
+ * (raw logit + bias, -inf for banned / not allowed / min_tokens / guide, penalties, arg max or draw); dots_get_logits and the logprobs stay
+ * on the raw logits.  The commit walks the chosen token's bytes.  An EOS id finishes a guided row whether or not ignore_eos is set.  Like a
+ * row with rules, a guided row without DotsSamplingParams of its own is selected with the engine-wide setting as it stands at the call.
+ * A row the guide (and min_tokens) leave nothing for commits id 0, as an all -inf row of the rules does; its state does not move. */
+#define DOTS_MAX_GUIDE_STATES 4096
+int dots_set_token_bytes(DotsEngine* e, const int32_t* offsets_host, const uint8_t* bytes_host);
+int dots_guide_create(DotsEngine* e, const uint16_t* table_host, int n_states, const uint8_t* accepting_host, int start, int32_t* id_out);
+int dots_guide_destroy(DotsEngine* e, int32_t id);
+int dots_set_row_guide(DotsEngine* e, int row, int32_t id);
+int dots_row_guide_state(DotsEngine* e, int row, int32_t* state_out);
+
 /* Log-probabilities: log_softmax of the raw fp32 logits of the step (before penalties, temperature, top-k and top-p:
  * the values dots_get_logits returns), for every token a row commits, the prefill's first token included.  The top entries are
  * ordered by value descending, then index ascending.  lse comes from per-chunk (max, sum) pairs merged in a fixed chunk order, so a
@@ -425,6 +456,15 @@ int dots_op_select_tokens_rules(DotsEngine* e, const float* logits_dev, int B, i
 int dots_bench_select_tokens_rules(DotsEngine* e, const float* logits_dev, int B, int V, const DotsSamplingParams* params_host, const DotsLogitRules* rules_host,
                                    const int32_t* n_gen_host, const int32_t* hist_dev, const int32_t* hist_lens_dev, int hist_stride,
                                    const int32_t* n_prompt_dev, int iters, float* ms_out);
+/* dots_op_select_tokens_rules with guides: row b holds guide guide_ids_host[b] of this engine (-1: none) at state states_host[b]; V must be
+ * the engine's vocabulary (the token bytes are the engine's).  states_out_host (may be NULL) receives each row's state after the commit,
+ * -1 for a row without a guide.  dots_bench_select_tokens_guided times the stage, the mask kernel included, on the same inputs. */
+int dots_op_select_tokens_guided(DotsEngine* e, const float* logits_dev, int B, int V, const DotsSamplingParams* params_host, const DotsLogitRules* rules_host,
+                                 const int32_t* n_gen_host, const int32_t* guide_ids_host, const int32_t* states_host, const int32_t* hist_dev,
+                                 const int32_t* hist_lens_dev, int hist_stride, const int32_t* n_prompt_dev, int32_t* out_tokens_dev, int32_t* states_out_host);
+int dots_bench_select_tokens_guided(DotsEngine* e, const float* logits_dev, int B, int V, const DotsSamplingParams* params_host, const DotsLogitRules* rules_host,
+                                    const int32_t* n_gen_host, const int32_t* guide_ids_host, const int32_t* states_host, const int32_t* hist_dev,
+                                    const int32_t* hist_lens_dev, int hist_stride, const int32_t* n_prompt_dev, int iters, float* ms_out);
 /* The log-probability stage over caller logits: logits_dev fp32 [B, ld] (V <= ld), top_n_host [B] (-1 = row skipped, 0..20),
  * chosen_dev int32 [B] the chosen ids; writes tok_lp_dev float [B], top_ids_dev int32 [B][20], top_lp_dev float [B][20] of every row
  * with top_n >= 0 (entries beyond top_n: -1 / NaN).  The same two kernels the engine runs. */
