@@ -763,6 +763,8 @@ DEVI float penalise(float l, int c, bool seen_prompt, const RowParams& p) {
 DEVI bool row_ruled(const RowSel& rs, int b) { return rs.rules && (rs.rules[b].flags & RULE_ON); }
 // does row b hold a guide in this launch (uniform per workgroup)
 DEVI bool row_guided(const RowSel& rs, int b) { return rs.guide.rows && rs.guide.rows[b].table; }
+// does row b carry an n-gram rule in this launch (uniform per workgroup)
+DEVI bool row_ngram(const RowSel& rs, int b) { return rs.ngram.rows && rs.ngram.rows[b].n > 0; }
 
 __global__ __launch_bounds__(256) void select_partial_kernel(const float* __restrict__ logits, int V, int ld, RowSel rs, StepState st,
                                                              float* __restrict__ pval, int32_t* __restrict__ pidx) {
@@ -779,17 +781,19 @@ __global__ __launch_bounds__(256) void select_partial_kernel(const float* __rest
     float best = -INFINITY;
     int bi = 0x7fffffff;
     const RowParams p = own ? rs.params[b] : RowParams{0.f, 1.f, 0, 1.f, 0.f, 0.f, 0};
-    const bool ruled = own && row_ruled(rs, b), guided = own && row_guided(rs, b);
-    if (ruled || guided) {
+    const bool ruled = own && row_ruled(rs, b), guided = own && row_guided(rs, b), ngram = own && row_ngram(rs, b);
+    if (ruled || guided || ngram) {
         // Logit rules, in vLLM's order: l + bias (-inf: banned / not allowed), -inf for the EOS and stop ids below min_tokens,
         // then the penalties on that value (-inf stays -inf: r > 0 and the subtrahend is finite).  Still one read of the logits; the shaped
         // values go to the scratch the threshold and draw kernels read.
         // A guide enters with the allowed list: -inf where the row's bit of guide_mask_kernel is clear; the EOS and stop ids
         // are allowed iff the row's state is accepting, whatever their bit.  A guided row without rules runs this branch with no image.
+        // An n-gram rule enters there too: -inf where the row's bit of ngram_ban_kernel is set, EOS and stop ids included.
         const RowRules* r = ruled ? rs.rules + b : nullptr;
         const bool pen_on = rs.cnt && row_has_pen(p);
         const float* img = (r && (r->flags & RULE_IMG)) ? rs.rule_img + (size_t)b * V : nullptr;
         const uint32_t* gbits = guided ? rs.guide.mask + (size_t)b * rs.guide.words : nullptr;
+        const uint32_t* nbits = ngram ? rs.ngram.mask + (size_t)b * rs.ngram.words : nullptr;
         const bool early = r && st.out_lens[b] < r->min_tokens;
         bool accepting = true;
         if (guided) { const RowGuide& rg = rs.guide.rows[b]; accepting = rg.accepting[rg.state] != 0; }
@@ -819,6 +823,7 @@ __global__ __launch_bounds__(256) void select_partial_kernel(const float* __rest
             bool term = false;                                       // an EOS / stop id: the guide's bit does not speak for it
             for (int k = 0; k < n_kill; ++k) term = term || s_kill[k] == i;
             if (term ? kill : (gbits && !((gbits[i >> 5] >> (i & 31)) & 1u))) l = -INFINITY;
+            if (nbits && ((nbits[i >> 5] >> (i & 31)) & 1u)) l = -INFINITY;
             if (pen_on) l = penalise(l, cnt[i], (seen[i >> 5] >> (i & 31)) & 1u, p);
             if (sampled) shaped[i] = l;
             argmax_merge(best, bi, l, i);
@@ -978,7 +983,7 @@ __global__ __launch_bounds__(SEL_THREADS) void select_thresh_kernel(const float*
         return;
     }
     merge_partials(pval, pidx, b, &L.best, &L.bi);
-    const bool pen = (rs.cnt && row_has_pen(p)) || row_ruled(rs, b) || row_guided(rs, b);      // the shaped values of the partial kernel
+    const bool pen = (rs.cnt && row_has_pen(p)) || row_ruled(rs, b) || row_guided(rs, b) || row_ngram(rs, b);      // the shaped values of the partial kernel
     const float* row = pen ? rs.pen + (size_t)b * V : logits + (size_t)b * ld;
     const float m = L.best, inv_t = 1.0f / p.temperature;
 
@@ -1090,7 +1095,7 @@ __global__ __launch_bounds__(SEL_THREADS) void select_rows_kernel(const float* _
         if (tid == 0) commit_row(st, rs, b, V, pen, s_bi);
         return;
     }
-    const float* row = pen || row_ruled(rs, b) || row_guided(rs, b) ? rs.pen + (size_t)b * V : logits + (size_t)b * ld;
+    const float* row = pen || row_ruled(rs, b) || row_guided(rs, b) || row_ngram(rs, b) ? rs.pen + (size_t)b * V : logits + (size_t)b * ld;
     const float m = s_best, inv_t = 1.0f / p.temperature;
     const uint32_t kmax = rs.thr[b];
     // ---- 3. inverse CDF in index order over the kept weights.  Wave w owns the contiguous segment [w seg, (w + 1) seg) and walks it 64

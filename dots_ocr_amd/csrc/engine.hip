@@ -227,6 +227,12 @@ struct DotsEngine {
     uint32_t* guide_mask = nullptr;
     int row_guide[DOTS_MAX_BATCH] = {0};
     int n_guided = 0;                      // rows with a guide: > 0 adds the mask kernel in front of the per-row stage
+    // no-repeat n-gram blocking (dots_set_row_ngram): allocated by the first row that takes a rule — the row table and the
+    // banned bits [max_batch][ngram_mask_words(V)].  row_ngram[row] = the row carries a rule.
+    RowNgram* d_ngram = nullptr;
+    uint32_t* ngram_mask = nullptr;
+    int row_ngram[DOTS_MAX_BATCH] = {0};
+    int n_ngram = 0;                       // rows with an n-gram rule: > 0 adds the ban kernel in front of the per-row stage
     // log-probabilities (dots_set_row_logprobs): top_n per row (-1 = off) on the device and its host mirror; the outputs
     // ([max_batch][max_seq_len] positions) and the stage's scratch are allocated by the first row switched on
     int32_t* d_row_lp = nullptr;
@@ -257,9 +263,9 @@ struct DotsEngine {
     // captured decode steps, keyed by everything the capture bakes in: rows, KV splits, static batch (out_cap = row stride of
     // the output buffer) or slot mode (out_cap = 0), number of EOS ids, whether any row carries its own parameters (rowp: the per-row
     // selection stage), whether any row returns logprobs (lp), whether any row carries logit rules (rules: the stage then gets their
-    // table), whether any row holds a guide (guided: the mask kernel and the guides' tables); engine-wide sampling changes drop the cache
-    // (dots_set_sampling), per-row ones live in device memory
-    struct StepGraph { int rows, splits, out_cap, n_eos, part, rowp, lp, rules, guided; hipGraph_t graph; hipGraphExec_t exec; };
+    // table), whether any row holds a guide (guided: the mask kernel and the guides' tables), whether any row carries an n-gram rule (ngram:
+    // the ban kernel and its bits); engine-wide sampling changes drop the cache (dots_set_sampling), per-row ones live in device memory
+    struct StepGraph { int rows, splits, out_cap, n_eos, part, rowp, lp, rules, guided, ngram; hipGraph_t graph; hipGraphExec_t exec; };
     std::vector<StepGraph> step_graphs;
     std::vector<int> h_prompt_lens;
     int steps_done = 0;
@@ -889,7 +895,11 @@ int select_tokens(DotsEngine* e, int advance) {
     if (e->n_lp > 0) CK(launch_logprob_partial(e->stream, e->d_logits, c.vocab_size, c.vocab_size, e->B_sel, ls));
     if (e->n_own > 0) {          // per-row stage for the rows with their own parameters (+ the greedy rows that follow the engine)
         RowSel rs{e->d_rowp, e->d_row_own, e->pen_cnt, e->pen_seen, e->pen_logits, e->d_row_thr, e->temperature > 0.f ? 0 : 1,
-                  e->n_rules > 0 ? e->d_rules : nullptr, e->rule_img, GuideSel{}};
+                  e->n_rules > 0 ? e->d_rules : nullptr, e->rule_img, GuideSel{}, NgramSel{}};
+        if (e->n_ngram > 0) {        // the n-gram rows' banned bits from their own output so far, before the stage reads the logits
+            rs.ngram = NgramSel{e->d_ngram, e->ngram_mask, ngram_mask_words(c.vocab_size), c.vocab_size};
+            CK(launch_ngram_ban(e->stream, rs.ngram, e->B_sel, st.out_ids, st.out_lens, st.out_stride, st.finished, st.sel));
+        }
         if (e->n_guided > 0) {       // the guided rows' allowed bits from their current states, before the stage reads the logits
             rs.guide = GuideSel{e->d_guides, e->guide_mask, e->tok_off, e->tok_bytes, guide_mask_words(c.vocab_size), c.vocab_size};
             CK(launch_guide_mask(e->stream, rs.guide, e->B_sel, st.sel));
@@ -960,13 +970,25 @@ int ensure_guide_state(DotsEngine* e) {
     return DOTS_OK;
 }
 
+// row table and banned bits of the n-gram rules, allocated by the first row that takes one
+int ensure_ngram_state(DotsEngine* e) {
+    if (e->d_ngram) return DOTS_OK;
+    // each piece is allocated once: a call that failed half way is resumed by the next one
+    const size_t rows = e->cfg.max_batch, V = e->cfg.vocab_size;
+    if (!e->ngram_mask) CK(e->alloc(&e->ngram_mask, rows * ngram_mask_words((int)V)));
+    if (!e->pen_logits) CK(e->alloc(&e->pen_logits, rows * V));       // the shaped logits of a sampled n-gram row
+    CK(e->alloc(&e->d_ngram, DOTS_MAX_BATCH));             // zeroed by alloc(): no row carries a rule; set last, it is the guard above
+    drop_step_graphs(e);                                   // graphs captured before hold no n-gram state
+    return DOTS_OK;
+}
+
 // what a row without parameters of its own is selected with once the per-row stage owns it (logit rules): the engine-wide setting as it stands
 RowParams engine_row_params(const DotsEngine* e) { return RowParams{e->temperature, e->top_p, 0, 1.f, 0.f, 0.f, e->seed}; }
 
 // the row's entry back to the engine-wide setting (stream ordered); a row that still carries logit rules stays with the per-row stage
 int clear_row(DotsEngine* e, int row) {
     if (!e->row_own[row]) return DOTS_OK;
-    if (e->row_rules[row] || e->row_guide[row]) {
+    if (e->row_rules[row] || e->row_guide[row] || e->row_ngram[row]) {
         CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, engine_row_params(e), 1));
         e->row_own[row] = 0;
         return DOTS_OK;
@@ -983,7 +1005,7 @@ int clear_row_rules(DotsEngine* e, int row) {
     CK(launch_set_row_rules(e->stream, e->d_rules, e->rule_img, row, e->cfg.vocab_size, RowRules{}, nullptr, 0, nullptr, nullptr, 0));
     e->row_rules[row] = 0;
     e->n_rules -= 1;
-    if (!e->row_own[row] && !e->row_guide[row]) {
+    if (!e->row_own[row] && !e->row_guide[row] && !e->row_ngram[row]) {
         CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, RowParams{}, 0));
         e->n_own -= 1;
     }
@@ -997,7 +1019,20 @@ int clear_row_guide(DotsEngine* e, int row) {
     e->guides[e->row_guide[row] - 1].rows -= 1;
     e->row_guide[row] = 0;
     e->n_guided -= 1;
-    if (!e->row_own[row] && !e->row_rules[row]) {
+    if (!e->row_own[row] && !e->row_rules[row] && !e->row_ngram[row]) {
+        CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, RowParams{}, 0));
+        e->n_own -= 1;
+    }
+    return DOTS_OK;
+}
+
+// the row's n-gram rule off (stream ordered)
+int clear_row_ngram(DotsEngine* e, int row) {
+    if (!e->row_ngram[row]) return DOTS_OK;
+    CK(launch_set_row_ngram(e->stream, e->d_ngram, row, RowNgram{}));
+    e->row_ngram[row] = 0;
+    e->n_ngram -= 1;
+    if (!e->row_own[row] && !e->row_rules[row] && !e->row_guide[row]) {
         CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, RowParams{}, 0));
         e->n_own -= 1;
     }
@@ -1055,6 +1090,29 @@ int check_logit_rules(DotsEngine* e, const DotsLogitRules& r, int V, const int32
     rr.n_stop = r.n_stop;
     std::copy(r.stop_ids, r.stop_ids + r.n_stop, rr.stop);
     *out = rr;
+    return DOTS_OK;
+}
+
+// Validate one row's n-gram rule against vocabulary V and the longest output max_len -> the device entry
+int check_ngram_rule(DotsEngine* e, const DotsNgramRule& r, int V, int max_len, RowNgram* out) {
+    if (V > NGRAM_MAX_V) return e->fail(DOTS_E_INVALID, "n-gram rule: the vocabulary %d exceeds the %d ids the ban kernel holds", V, NGRAM_MAX_V);
+    if (r.size < 1 || r.size > DOTS_MAX_NGRAM_SIZE) return e->fail(DOTS_E_INVALID, "n-gram rule: size must be in [1, %d], got %d", DOTS_MAX_NGRAM_SIZE, r.size);
+    if (r.window != 0 && (r.window < r.size || r.window > max_len))
+        return e->fail(DOTS_E_INVALID, "n-gram rule: window must be 0 (the whole output) or in [size = %d, %d], got %d", r.size, max_len, r.window);
+    if (r.n_whitelist < 0 || r.n_whitelist > DOTS_MAX_NGRAM_WHITELIST)
+        return e->fail(DOTS_E_INVALID, "n-gram rule: n_whitelist must be in [0, %d]", DOTS_MAX_NGRAM_WHITELIST);
+    RowNgram rn{};
+    rn.n = r.size;
+    rn.window = r.window;
+    rn.n_white = r.n_whitelist;
+    for (int j = 0; j < r.n_whitelist; ++j) {
+        const int id = r.whitelist[j];
+        if (id < 0 || id >= V) return e->fail(DOTS_E_INVALID, "n-gram rule: whitelist id %d outside [0, %d)", id, V);
+        for (int k = 0; k < j; ++k)
+            if (r.whitelist[k] == id) return e->fail(DOTS_E_INVALID, "n-gram rule: whitelist id %d given twice", id);
+        rn.white[j] = id;
+    }
+    *out = rn;
     return DOTS_OK;
 }
 
@@ -1392,15 +1450,16 @@ int splits_for_ctx(int max_ctx) { return decode_attn_splits(max_ctx); }
 
 // The captured decode step for (rows = e->B, splits, out_cap, e->n_eos): looked up in the cache or captured now.
 int step_graph(DotsEngine* e, int rows, int n_splits, int out_cap, hipGraphExec_t* exec, int part = 0) {
-    const int rowp = e->n_own > 0 ? 1 : 0, lp = e->n_lp > 0 ? 1 : 0, rules = e->n_rules > 0 ? 1 : 0, guided = e->n_guided > 0 ? 1 : 0;
+    const int rowp = e->n_own > 0 ? 1 : 0, lp = e->n_lp > 0 ? 1 : 0, rules = e->n_rules > 0 ? 1 : 0, guided = e->n_guided > 0 ? 1 : 0,
+              ngram = e->n_ngram > 0 ? 1 : 0;
     for (auto& g : e->step_graphs)
         if (g.rows == rows && g.splits == n_splits && g.out_cap == out_cap && g.n_eos == e->n_eos && g.part == part && g.rowp == rowp && g.lp == lp && g.rules == rules &&
-            g.guided == guided) {
+            g.guided == guided && g.ngram == ngram) {
             *exec = g.exec;
             return DOTS_OK;
         }
     if (e->step_graphs.size() >= 32) drop_step_graphs(e);
-    DotsEngine::StepGraph g{rows, n_splits, out_cap, e->n_eos, part, rowp, lp, rules, guided, nullptr, nullptr};
+    DotsEngine::StepGraph g{rows, n_splits, out_cap, e->n_eos, part, rowp, lp, rules, guided, ngram, nullptr, nullptr};
     CK(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
     int r = decode_step_launches(e, n_splits, part);
     hipError_t ce = hipStreamEndCapture(e->stream, &g.graph);
@@ -1786,6 +1845,9 @@ int dots_slots_reset(DotsEngine* e) {
     std::fill(e->row_guide, e->row_guide + DOTS_MAX_BATCH, 0);
     for (auto& g : e->guides) g.rows = 0;
     e->n_guided = 0;
+    if (e->d_ngram) CK(hipMemsetAsync(e->d_ngram, 0, DOTS_MAX_BATCH * sizeof(RowNgram), s));
+    std::fill(e->row_ngram, e->row_ngram + DOTS_MAX_BATCH, 0);
+    e->n_ngram = 0;
     if (e->d_row_lp) CK(hipMemsetAsync(e->d_row_lp, 0xFF, DOTS_MAX_BATCH * 4, s));
     std::fill(e->row_lp, e->row_lp + DOTS_MAX_BATCH, -1);
     e->n_lp = 0;
@@ -1900,6 +1962,7 @@ int dots_slot_release(DotsEngine* e, int slot) {
     RET(clear_row(e, slot));
     RET(clear_row_rules(e, slot));
     RET(clear_row_guide(e, slot));
+    RET(clear_row_ngram(e, slot));
     RET(set_row_lp(e, slot, -1));
     e->slot_active[slot] = 0;
     e->sel_dirty = true;
@@ -2040,7 +2103,7 @@ int dots_set_row_sampling(DotsEngine* e, int row, const DotsSamplingParams* p) {
     RET(ensure_row_table(e));
     if (rp.repetition_penalty != 1.f || rp.frequency_penalty != 0.f || rp.presence_penalty != 0.f) RET(ensure_pen_state(e));
     CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, rp, 1));
-    if (!e->row_own[row]) { e->row_own[row] = 1; e->n_own += (e->row_rules[row] || e->row_guide[row]) ? 0 : 1; }
+    if (!e->row_own[row]) { e->row_own[row] = 1; e->n_own += (e->row_rules[row] || e->row_guide[row] || e->row_ngram[row]) ? 0 : 1; }
     return DOTS_OK;
 }
 
@@ -2073,7 +2136,7 @@ int dots_set_row_logit_rules(DotsEngine* e, int row, const DotsLogitRules* r) {
     if (!e->row_rules[row]) {
         e->row_rules[row] = 1;
         e->n_rules += 1;
-        if (!e->row_own[row] && !e->row_guide[row]) e->n_own += 1;
+        if (!e->row_own[row] && !e->row_guide[row] && !e->row_ngram[row]) e->n_own += 1;
     }
     return DOTS_OK;
 }
@@ -2148,15 +2211,35 @@ int dots_set_row_guide(DotsEngine* e, int row, int32_t id) {
     RET(ensure_guide_state(e));
     const DotsEngine::Guide& g = e->guides[id];
     CK(launch_set_row_guide(e->stream, e->d_guides, row, RowGuide{g.table, g.accepting, g.n_states, g.start, g.start, 0}));
-    if (!e->row_own[row] && !e->row_rules[row] && !e->row_guide[row])
+    if (!e->row_own[row] && !e->row_rules[row] && !e->row_guide[row] && !e->row_ngram[row])
         CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, engine_row_params(e), 1));
     if (e->row_guide[row]) e->guides[e->row_guide[row] - 1].rows -= 1;
     else {
         e->n_guided += 1;
-        if (!e->row_own[row] && !e->row_rules[row]) e->n_own += 1;
+        if (!e->row_own[row] && !e->row_rules[row] && !e->row_ngram[row]) e->n_own += 1;
     }
     e->row_guide[row] = id + 1;
     e->guides[id].rows += 1;
+    return DOTS_OK;
+}
+
+int dots_set_row_ngram(DotsEngine* e, int row, const DotsNgramRule* r) {
+    if (!e) return DOTS_E_INVALID;
+    if (row < 0 || row >= e->cfg.max_batch) return e->fail(DOTS_E_INVALID, "row %d out of range [0, %d)", row, e->cfg.max_batch);
+    CK(hipSetDevice(e->device));
+    if (!r) return e->d_ngram ? clear_row_ngram(e, row) : DOTS_OK;
+    RowNgram rn;
+    RET(check_ngram_rule(e, *r, e->cfg.vocab_size, e->cfg.max_seq_len, &rn));
+    RET(ensure_row_table(e));
+    RET(ensure_ngram_state(e));
+    CK(launch_set_row_ngram(e->stream, e->d_ngram, row, rn));
+    if (!e->row_own[row] && !e->row_rules[row] && !e->row_guide[row] && !e->row_ngram[row])
+        CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, engine_row_params(e), 1));
+    if (!e->row_ngram[row]) {
+        e->row_ngram[row] = 1;
+        e->n_ngram += 1;
+        if (!e->row_own[row] && !e->row_rules[row] && !e->row_guide[row]) e->n_own += 1;
+    }
     return DOTS_OK;
 }
 
@@ -2688,11 +2771,17 @@ namespace {
 int select_op(DotsEngine* e, const float* logits_dev, int B, int V, const DotsSamplingParams* params_host, const int32_t* hist_dev,
               const int32_t* hist_lens_dev, int hist_stride, const int32_t* n_prompt_dev, int32_t* out_tokens_dev, int mode, int iters, float* ms,
               const DotsLogitRules* rules_host = nullptr, const int32_t* n_gen_host = nullptr, const int32_t* guide_ids_host = nullptr,
-              const int32_t* states_host = nullptr, int32_t* states_out_host = nullptr) {
+              const int32_t* states_host = nullptr, int32_t* states_out_host = nullptr, const DotsNgramRule* ngram_host = nullptr) {
     if (!e || !logits_dev || B < 1 || B > DOTS_MAX_BATCH || V < 1 || !params_host || !hist_dev || !hist_lens_dev || hist_stride < 1 || !n_prompt_dev ||
         (!out_tokens_dev && !ms) || mode < 0 || mode > 2 || (rules_host && mode != 2) || (n_gen_host && !rules_host) ||
-        (guide_ids_host && (!rules_host || !states_host)))
+        (guide_ids_host && (!rules_host || !states_host)) || (ngram_host && !rules_host))
         return e ? e->fail(DOTS_E_INVALID, "bad select_tokens arguments") : DOTS_E_INVALID;
+    // ngram_host != nullptr: row b carries ngram_host[b] unless its size is 0; its history is hist[n_prompt[b] .. hist_lens[b]), copied to
+    // the front of the stage's output rows (where the engine keeps a row's own output).  A window may reach hist_stride.
+    std::vector<RowNgram> ngrams(ngram_host ? DOTS_MAX_BATCH : 0, RowNgram{});
+    if (ngram_host)
+        for (int b = 0; b < B; ++b)
+            if (ngram_host[b].size != 0) RET(check_ngram_rule(e, ngram_host[b], V, hist_stride, &ngrams[b]));
     // guide_ids_host != nullptr: row b holds guide guide_ids_host[b] (-1: none) of this engine at state states_host[b]; V must be the engine's
     // vocabulary (the token bytes are its).  states_out_host (may be nullptr) receives the rows' states after the commit, -1 for a row without.
     if (guide_ids_host) {
@@ -2764,7 +2853,16 @@ int select_op(DotsEngine* e, const float* logits_dev, int B, int V, const DotsSa
         }
         if (n_gen_host) CK(hipMemcpyAsync(lens, n_gen_host, B * 4, hipMemcpyHostToDevice, e->stream));
     }
-    RowSel rs{tab, own_d, cnt, seen, pen, thr, 0, rtab, img, GuideSel{}};
+    RowSel rs{tab, own_d, cnt, seen, pen, thr, 0, rtab, img, GuideSel{}, NgramSel{}};
+    if (ngram_host) {
+        RowNgram* ntab = nullptr;
+        uint32_t* nmask = nullptr;
+        CK(sc.get(&ntab, DOTS_MAX_BATCH));
+        CK(sc.get(&nmask, (size_t)B * ngram_mask_words(V)));
+        CK(hipMemcpyAsync(ntab, ngrams.data(), DOTS_MAX_BATCH * sizeof(RowNgram), hipMemcpyHostToDevice, e->stream));
+        CK(launch_ngram_history(e->stream, hist_dev, hist_lens_dev, hist_stride, n_prompt_dev, B, ids, st.out_stride));
+        rs.ngram = NgramSel{ntab, nmask, ngram_mask_words(V), V};
+    }
     RowGuide* gtab = nullptr;
     int32_t* gstates = nullptr;
     if (guide_ids_host) {
@@ -2788,6 +2886,11 @@ int select_op(DotsEngine* e, const float* logits_dev, int B, int V, const DotsSa
             // every replay starts from the given states (a timed replay commits nothing: its rows are marked finished)
             hipError_t r = launch_guide_set_states(e->stream, gtab, gstates, B);
             if (r == hipSuccess) r = launch_guide_mask(e->stream, rs.guide, B, nullptr);
+            if (r != hipSuccess) return r;
+        }
+        if (rs.ngram.rows) {
+            // a timed replay marks its rows finished so that nothing is appended: the ban kernel is told of none, or it would skip them all
+            hipError_t r = launch_ngram_ban(e->stream, rs.ngram, B, st.out_ids, st.out_lens, st.out_stride, iters > 0 ? nullptr : st.finished, nullptr);
             if (r != hipSuccess) return r;
         }
         if (mode == 0) return launch_argmax_step(e->stream, logits_dev, V, V, B, pval, pidx, st);
@@ -2864,6 +2967,22 @@ int dots_bench_select_tokens_guided(DotsEngine* e, const float* logits_dev, int 
     if (!ms_out || iters < 1 || !rules_host || !guide_ids_host) return e ? e->fail(DOTS_E_INVALID, "bad bench_select_tokens arguments") : DOTS_E_INVALID;
     return select_op(e, logits_dev, B, V, params_host, hist_dev, hist_lens_dev, hist_stride, n_prompt_dev, nullptr, 2, iters, ms_out, rules_host, n_gen_host,
                      guide_ids_host, states_host, nullptr);
+}
+
+int dots_op_select_tokens_ngram(DotsEngine* e, const float* logits_dev, int B, int V, const DotsSamplingParams* params_host, const DotsLogitRules* rules_host,
+                                const DotsNgramRule* ngram_host, const int32_t* hist_dev, const int32_t* hist_lens_dev, int hist_stride,
+                                const int32_t* n_prompt_dev, int32_t* out_tokens_dev) {
+    if (!out_tokens_dev || !rules_host || !ngram_host) return e ? e->fail(DOTS_E_INVALID, "bad select_tokens arguments") : DOTS_E_INVALID;
+    return select_op(e, logits_dev, B, V, params_host, hist_dev, hist_lens_dev, hist_stride, n_prompt_dev, out_tokens_dev, 2, 0, nullptr, rules_host, nullptr,
+                     nullptr, nullptr, nullptr, ngram_host);
+}
+
+int dots_bench_select_tokens_ngram(DotsEngine* e, const float* logits_dev, int B, int V, const DotsSamplingParams* params_host, const DotsLogitRules* rules_host,
+                                   const DotsNgramRule* ngram_host, const int32_t* hist_dev, const int32_t* hist_lens_dev, int hist_stride,
+                                   const int32_t* n_prompt_dev, int iters, float* ms_out) {
+    if (!ms_out || iters < 1 || !rules_host || !ngram_host) return e ? e->fail(DOTS_E_INVALID, "bad bench_select_tokens arguments") : DOTS_E_INVALID;
+    return select_op(e, logits_dev, B, V, params_host, hist_dev, hist_lens_dev, hist_stride, n_prompt_dev, nullptr, 2, iters, ms_out, rules_host, nullptr,
+                     nullptr, nullptr, nullptr, ngram_host);
 }
 
 }  // extern "C"

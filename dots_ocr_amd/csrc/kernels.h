@@ -144,6 +144,21 @@ constexpr uint16_t GUIDE_DEAD = 0xFFFF;
 struct RowGuide { const uint16_t* table; const uint8_t* accepting; int32_t n_states, start, state, _pad; };
 struct GuideSel { RowGuide* rows; uint32_t* mask; const int32_t* tok_off; const uint8_t* tok_bytes; int32_t words, V; };
 inline int guide_mask_words(int V) { return ((V + 63) / 64) * 2; }
+// No-repeat n-gram blocking.  RowNgram: the rule a row carries (n == 0: none).  With out[0 .. L) the tokens the row has
+// generated and P = out[L - n + 1 .. L), the id out[i + n - 1] is banned for every i in [max(0, L - window), L - n] (window == 0: from 0)
+// with out[i .. i + n - 1) == P, unless it is one of the n_white ids of white.  NgramSel: what a launch of the per-row stage needs — the
+// row table and the banned bits ngram_ban_kernel leaves ([rows][words] uint32, words = ngram_mask_words(V); bit t set = token t is -inf).
+// rows == nullptr = no row of this launch carries an n-gram rule.
+#ifndef DOTS_MAX_NGRAM_SIZE
+#define DOTS_MAX_NGRAM_SIZE 64
+#endif
+#ifndef DOTS_MAX_NGRAM_WHITELIST
+#define DOTS_MAX_NGRAM_WHITELIST 16
+#endif
+struct RowNgram { int32_t n, window, n_white, white[DOTS_MAX_NGRAM_WHITELIST]; };
+struct NgramSel { const RowNgram* rows; uint32_t* mask; int32_t words, V; };
+inline int ngram_mask_words(int V) { return (V + 31) / 32; }
+constexpr int NGRAM_MAX_V = 64 * 1024 * 8;     // the banned bits of one row are built in LDS: 64 KB per workgroup
 struct RowSel {
     const RowParams* params;
     const int32_t* own;
@@ -155,6 +170,7 @@ struct RowSel {
     const RowRules* rules;      // [DOTS_MAX_BATCH], or nullptr = no row of this launch carries rules
     const float* rule_img;      // [rows][V] fp32: the bias of a token, -inf for a banned / not allowed one, 0 elsewhere
     GuideSel guide;             // guide.rows == nullptr = no row of this launch is guided
+    NgramSel ngram;             // ngram.rows == nullptr = no row of this launch carries an n-gram rule
 };
 // pval / pidx: ARGMAX_CHUNKS (64) partials per row, as launch_argmax_step
 hipError_t launch_select_rows(hipStream_t s, const float* logits, int V, int ld, int B, const RowSel& rs, float* pval, int32_t* pidx, const StepState& st);
@@ -183,6 +199,18 @@ hipError_t launch_set_row_guide(hipStream_t s, RowGuide* table, int row, const R
 hipError_t launch_guide_reset_rows(hipStream_t s, RowGuide* table, const int32_t* dst, int n);
 // table[row].state = state for rows [0, n) (explicit states of dots_op_select_tokens_guided)
 hipError_t launch_guide_set_states(hipStream_t s, RowGuide* table, const int32_t* states, int n);
+// ---- ngram.hip: no-repeat n-gram blocking
+// The banned bits of every row of the launch that carries an n-gram rule, from the row's own output out_ids[b * out_stride + 0 .. out_lens[b])
+// (StepState's arrays).  Rows without a rule, rows that sel masks out and rows with finished[b] != 0 (finished == nullptr: none) are
+// skipped and keep the bits of their last step.  Runs before launch_select_rows.
+hipError_t launch_ngram_ban(hipStream_t s, const NgramSel& g, int B, const int32_t* out_ids, const int32_t* out_lens, int out_stride,
+                            const int32_t* finished, const int32_t* sel);
+// table[row] = r, in stream order
+hipError_t launch_set_row_ngram(hipStream_t s, RowNgram* table, int row, const RowNgram& r);
+// out_ids[b * out_stride + j] = hist[b * stride + n_prompt[b] + j] for j < hist_lens[b] - n_prompt[b], the count launch_pen_history leaves
+// in out_lens (explicit histories of dots_op_select_tokens_ngram; out_stride >= stride)
+hipError_t launch_ngram_history(hipStream_t s, const int32_t* hist, const int32_t* hist_lens, int stride, const int32_t* n_prompt, int B,
+                                int32_t* out_ids, int out_stride);
 
 // ---- logprobs.hip: log-probabilities of the raw logits of every selected row
 #ifndef DOTS_MAX_TOP_LOGPROBS

@@ -215,6 +215,79 @@ class LogitRules:
         return c
 
 
+MAX_NGRAM_SIZE = 64                          # DOTS_MAX_NGRAM_SIZE: the longest n-gram a rule may name
+MAX_NGRAM_WHITELIST = 16                     # DOTS_MAX_NGRAM_WHITELIST: whitelisted ids per row
+
+
+class CDotsNgramRule(C.Structure):
+    _fields_ = [("size", C.c_int32), ("window", C.c_int32), ("n_whitelist", C.c_int32), ("whitelist", C.c_int32 * MAX_NGRAM_WHITELIST)]
+
+
+@dataclass(frozen=True)
+class NgramRule:
+    """No-repeat n-gram rule of one request / decode row (include/dots_ocr_hip.h DotsNgramRule).
+
+    size: n in [1, MAX_NGRAM_SIZE] — the row never completes an n-gram its own output already holds; window: 0 = the whole output, else
+    W >= size — only n-grams inside the last W generated tokens count; whitelist: at most MAX_NGRAM_WHITELIST distinct ids the rule never
+    bans (table tags, EOS).  vocab_size / max_seq_len (optional) bound the ids and the window; the engine repeats the check.  The prompt
+    is not part of the history (vLLM's convention; Hugging Face generate() counts it)."""
+    size: int
+    window: int = 0
+    whitelist: tuple = ()
+    vocab_size: Optional[int] = None
+    max_seq_len: Optional[int] = None
+
+    def __post_init__(self):
+        for name in ("size", "window"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"{name} must be an integer, got {v!r}")
+        n, w = int(self.size), int(self.window)
+        if not 1 <= n <= MAX_NGRAM_SIZE:
+            raise ValueError(f"size must be in [1, {MAX_NGRAM_SIZE}], got {n}")
+        if w != 0 and w < n:
+            raise ValueError(f"window must be 0 (the whole output) or >= size = {n}, got {w}")
+        if self.max_seq_len is not None and w > int(self.max_seq_len):
+            raise ValueError(f"window {w} exceeds max_seq_len {int(self.max_seq_len)}")
+        white = _id_tuple("whitelist", self.whitelist)
+        if len(white) > MAX_NGRAM_WHITELIST:
+            raise ValueError(f"at most {MAX_NGRAM_WHITELIST} whitelist ids, got {len(white)}")
+        if len(set(white)) != len(white):
+            raise ValueError("whitelist holds an id twice")
+        if self.vocab_size is not None:
+            for t in white:
+                if t >= int(self.vocab_size):
+                    raise ValueError(f"whitelist id {t} outside [0, {int(self.vocab_size)})")
+        object.__setattr__(self, "size", n)
+        object.__setattr__(self, "window", w)
+        object.__setattr__(self, "whitelist", white)
+        object.__setattr__(self, "vocab_size", None if self.vocab_size is None else int(self.vocab_size))
+        object.__setattr__(self, "max_seq_len", None if self.max_seq_len is None else int(self.max_seq_len))
+
+    def to_c(self) -> CDotsNgramRule:
+        c = CDotsNgramRule(self.size, self.window, len(self.whitelist))
+        for j, t in enumerate(self.whitelist):
+            c.whitelist[j] = t
+        return c
+
+
+def banned_ngram_ids(out, n: int, window: int = 0, whitelist=()) -> set:
+    """The ids an NgramRule(n, window, whitelist) bans after the generated tokens `out` — the restatement the kernels are
+    tested against.  With L = len(out) and P = out[L - n + 1:], every i in [max(0, L - window), L - n] (window 0: from 0) with
+    out[i:i + n - 1] == P bans out[i + n - 1] unless it is whitelisted."""
+    out = [int(t) for t in out]
+    L, n, window = len(out), int(n), int(window)
+    if n < 1 or L < n - 1:
+        return set()
+    prefix = out[L - n + 1:] if n > 1 else []
+    white = set(int(t) for t in whitelist)
+    banned = set()
+    for i in range(max(0, L - window) if window > 0 else 0, L - n + 1):
+        if out[i:i + n - 1] == prefix and out[i + n - 1] not in white:
+            banned.add(out[i + n - 1])
+    return banned
+
+
 class DotsEngineError(RuntimeError):
     pass
 
@@ -300,6 +373,10 @@ def _prototypes(lib):
                                                P(i32)]),
         "dots_bench_select_tokens_guided": (i32, [vp, vp, i32, i32, P(CDotsSamplingParams), P(CDotsLogitRules), P(i32), P(i32), P(i32), vp, vp, i32, vp,
                                                   i32, P(f32)]),
+        "dots_set_row_ngram": (i32, [vp, i32, P(CDotsNgramRule)]),
+        "dots_op_select_tokens_ngram": (i32, [vp, vp, i32, i32, P(CDotsSamplingParams), P(CDotsLogitRules), P(CDotsNgramRule), vp, vp, i32, vp, vp]),
+        "dots_bench_select_tokens_ngram": (i32, [vp, vp, i32, i32, P(CDotsSamplingParams), P(CDotsLogitRules), P(CDotsNgramRule), vp, vp, i32, vp, i32,
+                                                 P(f32)]),
         "dots_set_row_logprobs": (i32, [vp, i32, i32]),
         "dots_row_logprobs": (i32, [vp, i32, i32, i32, P(f32), P(i32), P(f32), P(i32)]),
         "dots_op_logprobs": (i32, [vp, vp, i32, i32, i32, P(i32), vp, vp, vp, vp]),
@@ -330,6 +407,7 @@ EXPORTED_SYMBOLS = [
     "dots_set_row_logit_rules", "dots_op_select_tokens_rules", "dots_bench_select_tokens_rules",
     "dots_set_token_bytes", "dots_guide_create", "dots_guide_destroy", "dots_set_row_guide", "dots_row_guide_state",
     "dots_op_select_tokens_guided", "dots_bench_select_tokens_guided",
+    "dots_set_row_ngram", "dots_op_select_tokens_ngram", "dots_bench_select_tokens_ngram",
 ]
 
 MAX_TOP_LOGPROBS = 20                        # DOTS_MAX_TOP_LOGPROBS: top entries kept per position
@@ -703,6 +781,45 @@ class Engine:
         self._ck(self.lib.dots_bench_select_tokens_guided(self.h, logits, int(B), int(V), arr, rarr, None if ng is None else _i32p(ng), _i32p(gid),
                                                           _i32p(st), hist, hist_lens, int(hist_stride), n_prompt, int(iters), C.byref(ms)),
                  "dots_bench_select_tokens_guided")
+        return float(ms.value)
+
+    # ------------------------------------------------------------------ no-repeat n-gram blocking
+    def set_row_ngram(self, row: int, rule: Optional["NgramRule"]):
+        """Give decode row `row` (a slot, or sequence `row` of a static batch) an NgramRule from the next selected token on; None clears
+        it.  Exact for a row that is already running: the ban is computed on the device from the row's own output at every step.
+        Captured decode graphs are kept; slot release and slots_reset clear the row.  A row with a rule but no SamplingParams of its own
+        is selected with the engine-wide temperature / top_p / seed as they stand now."""
+        if rule is None:
+            self._ck(self.lib.dots_set_row_ngram(self.h, int(row), None), "dots_set_row_ngram")
+            return
+        if not isinstance(rule, NgramRule):
+            raise TypeError("rule must be an NgramRule or None")
+        c = rule.to_c()
+        self._ck(self.lib.dots_set_row_ngram(self.h, int(row), C.byref(c)), "dots_set_row_ngram")
+
+    def _ngram_args(self, B, params, rules, ngrams):
+        if len(params) != B or len(rules) != B or len(ngrams) != B:
+            raise ValueError("one SamplingParams, LogitRules (or None) and NgramRule (or None) per row")
+        arr = (CDotsSamplingParams * B)(*[p.to_c() for p in params])
+        rarr = self._rules_array(rules)
+        narr = (CDotsNgramRule * B)(*[CDotsNgramRule() if g is None else g.to_c() for g in ngrams])
+        return arr, rarr, narr
+
+    def select_tokens_ngram(self, logits, B: int, V: int, params: Sequence[SamplingParams], rules: Sequence[Optional["LogitRules"]],
+                            ngrams: Sequence[Optional["NgramRule"]], hist, hist_lens, hist_stride: int, n_prompt, out_tokens):
+        """select_tokens_rules with an NgramRule per row (None = a row without); a row's history is hist[n_prompt .. hist_lens)
+        (dots_op_select_tokens_ngram)."""
+        arr, rarr, narr = self._ngram_args(B, params, rules, ngrams)
+        self._ck(self.lib.dots_op_select_tokens_ngram(self.h, logits, int(B), int(V), arr, rarr, narr, hist, hist_lens, int(hist_stride), n_prompt,
+                                                      out_tokens), "dots_op_select_tokens_ngram")
+
+    def bench_select_tokens_ngram(self, logits, B: int, V: int, params: Sequence[SamplingParams], rules: Sequence[Optional["LogitRules"]],
+                                  ngrams: Sequence[Optional["NgramRule"]], hist, hist_lens, hist_stride: int, n_prompt, iters: int) -> float:
+        """mean ms of one per-row selection stage with these n-gram rules, the ban kernel included"""
+        arr, rarr, narr = self._ngram_args(B, params, rules, ngrams)
+        ms = C.c_float()
+        self._ck(self.lib.dots_bench_select_tokens_ngram(self.h, logits, int(B), int(V), arr, rarr, narr, hist, hist_lens, int(hist_stride), n_prompt,
+                                                         int(iters), C.byref(ms)), "dots_bench_select_tokens_ngram")
         return float(ms.value)
 
     def set_row_logprobs(self, row: int, top_n: Optional[int]):

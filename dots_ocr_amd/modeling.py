@@ -133,7 +133,8 @@ class DotsOcrHipForCausalLM:
                  top_k: Optional[int] = None, repetition_penalty: Optional[float] = None, frequency_penalty: Optional[float] = None,
                  presence_penalty: Optional[float] = None, logit_bias=None, allowed_token_ids=None, min_tokens: int = 0,
                  stop_token_ids=None, ignore_eos: bool = False, guided_regex=None, guided_choice=None, guided_json=None,
-                 guided_whitespace_pattern=None, **_):
+                 guided_whitespace_pattern=None, no_repeat_ngram_size: Optional[int] = None, no_repeat_ngram_window: Optional[int] = None,
+                 no_repeat_ngram_whitelist=None, **_):
         """HF-shaped generate.  do_sample / temperature / top_p default to the checkpoint's generation_config.json (greedy when it
         is absent); with sampling on, tokens are drawn on the GPU from softmax(logits / temperature) restricted to the top_p
         nucleus, reproducibly from `seed`.  Returns LongTensor
@@ -154,7 +155,11 @@ class DotsOcrHipForCausalLM:
 
         guided_regex / guided_choice / guided_json (at most one; guided_whitespace_pattern with the last) compile to one guide that every
         sequence follows on the GPU (dots_ocr_amd/guided.py, Engine.set_row_guide); the engine needs its token bytes first
-        (Engine.set_token_bytes).  A sequence ends with an EOS id once its text matches; cut at max_new_tokens it is a prefix of a match."""
+        (Engine.set_token_bytes).  A sequence ends with an EOS id once its text matches; cut at max_new_tokens it is a prefix of a match.
+
+        no_repeat_ngram_size (n >= 1; None or 0 = off) with no_repeat_ngram_window (0 / None = the whole output) and
+        no_repeat_ngram_whitelist (token ids never banned) give every sequence the same NgramRule (Engine.set_row_ngram): a
+        sequence never completes an n-gram its own OUTPUT already holds.  Unlike HF generate, the prompt is not part of the history."""
         import dataclasses
         import torch
         t_eff, p_eff = resolve_sampling(self.generation_config, do_sample, temperature, top_p)
@@ -194,9 +199,21 @@ class DotsOcrHipForCausalLM:
                 def row_sp(b):
                     return dataclasses.replace(base, seed=int(seed) + b)
             guide = self.engine.create_guide(guide_obj)
+        ngram = None
+        if no_repeat_ngram_size:
+            from .engine import NgramRule, SamplingParams
+            ngram = NgramRule(no_repeat_ngram_size, no_repeat_ngram_window or 0, tuple(no_repeat_ngram_whitelist or ()),
+                              vocab_size=self.config.vocab_size, max_seq_len=self.max_seq_len)
+            if row_sp is None:                   # a sampled n-gram row draws with seed + b as the ruled rows do
+                base = SamplingParams(temperature=t_eff, top_p=p_eff, seed=seed)
+
+                def row_sp(b):
+                    return dataclasses.replace(base, seed=int(seed) + b)
+        elif no_repeat_ngram_window or no_repeat_ngram_whitelist:
+            raise ValueError("no_repeat_ngram_window / no_repeat_ngram_whitelist need no_repeat_ngram_size")
         try:
             return self._generate(input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens, eos_token_id, pad_token_id, continuous,
-                                  row_sp, rules, guide)
+                                  row_sp, rules, guide, ngram)
         finally:
             if guide is not None:
                 try:
@@ -206,7 +223,7 @@ class DotsOcrHipForCausalLM:
                     warnings.warn(f"guide {guide} could not be destroyed: {e}")
 
     def _generate(self, input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens, eos_token_id, pad_token_id, continuous, row_sp, rules,
-                  guide):
+                  guide, ngram=None):
         import torch
         ids = input_ids.detach().cpu().numpy()
         B, T = ids.shape
@@ -262,9 +279,10 @@ class DotsOcrHipForCausalLM:
                     lo, hi = int(patch_off[img_of_seq[b][0]]), int(patch_off[img_of_seq[b][-1] + 1])
                     pix = pv_dev[lo:hi] if pv_dev is not None else pv_host[lo:hi]
                     reqs.append(Request(prompts[b], pix, grid[img_of_seq[b][0]:img_of_seq[b][-1] + 1], max_new_tokens,
-                                        sampling=row_sp(b) if row_sp else None, rules=rules, guide=guide))
+                                        sampling=row_sp(b) if row_sp else None, rules=rules, guide=guide, ngram=ngram))
                 else:
-                    reqs.append(Request(prompts[b], None, None, max_new_tokens, sampling=row_sp(b) if row_sp else None, rules=rules, guide=guide))
+                    reqs.append(Request(prompts[b], None, None, max_new_tokens, sampling=row_sp(b) if row_sp else None, rules=rules, guide=guide,
+                                        ngram=ngram))
             outs = ContinuousBatcher(self.engine, eos_ids=eos).run(reqs)
             for b, o in enumerate(outs):
                 new_tokens[b, :len(o)] = o
@@ -299,6 +317,8 @@ class DotsOcrHipForCausalLM:
                             self.engine.set_row_logit_rules(j, rules)
                         if guide is not None:
                             self.engine.set_row_guide(j, guide)
+                        if ngram is not None:
+                            self.engine.set_row_ngram(j, ngram)
                     rows_set = max(rows_set, len(sl))
                 lens = np.array([len(prompts[b]) for b in sl], np.int32)
                 packed = np.concatenate([prompts[b] for b in sl])
@@ -332,6 +352,8 @@ class DotsOcrHipForCausalLM:
                     self.engine.set_row_logit_rules(j, None)
                 if guide is not None:
                     self.engine.set_row_guide(j, None)
+                if ngram is not None:
+                    self.engine.set_row_ngram(j, None)
         full = np.concatenate([ids.astype(np.int64), new_tokens[:, :n_max]], axis=1)    # HF stops at the longest sequence
         res = torch.from_numpy(full)
         return res.to(input_ids.device) if input_ids.is_cuda else res

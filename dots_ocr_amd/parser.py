@@ -33,8 +33,14 @@ class DotsOCRParser:
     def __init__(self, protocol="http", ip="localhost", port=8000, model_name="model", temperature=0.1, top_p=1.0,
                  max_completion_tokens=16384, num_thread=64, dpi=200, output_dir="./output", min_pixels=None,
                  max_pixels=None, use_hf=False, model_path="./weights/DotsOCR", model=None, processor=None,
-                 hf_max_new_tokens=24000, guided=False):
+                 hf_max_new_tokens=24000, guided=False, no_repeat_ngram_size=None, no_repeat_ngram_window=None,
+                 no_repeat_ngram_whitelist=None):
         self.dpi = dpi
+        # no-repeat n-gram blocking, opt-in: the server request carries the three fields, the in-process model generates
+        # with them.  With the default None the request and the call are exactly what they were.
+        self.no_repeat_ngram_size = no_repeat_ngram_size
+        self.no_repeat_ngram_window = no_repeat_ngram_window
+        self.no_repeat_ngram_whitelist = None if no_repeat_ngram_whitelist is None else [int(t) for t in no_repeat_ngram_whitelist]
         # guided: opt-in guided decoding for the two layout prompt modes: the server request carries guided_layout, the
         # in-process model generates under guided.layout_schema().  Off by default: the output is then exactly what it was.
         self.guided = bool(guided)
@@ -80,9 +86,14 @@ class DotsOCRParser:
         layout = {dict_promptmode_to_prompt[m] for m in ("prompt_layout_all_en", "prompt_layout_only_en")}
         return self.guided and all(p in layout for p in prompts)
 
+    def _ngram_fields(self) -> dict:
+        """the no_repeat_ngram_* settings that are set, under the names generate() and the server share"""
+        return {k: v for k, v in (("no_repeat_ngram_size", self.no_repeat_ngram_size), ("no_repeat_ngram_window", self.no_repeat_ngram_window),
+                                  ("no_repeat_ngram_whitelist", self.no_repeat_ngram_whitelist)) if v is not None}
+
     def _inference_batch_with_hf(self, images, prompts) -> List[str]:
         inputs = self._build_inputs(images, prompts)
-        kw = {}
+        kw = self._ngram_fields()
         if self._guided_layout(prompts):
             from .guided import layout_schema
             if getattr(self.model.engine, "token_bytes", None) is None:
@@ -97,10 +108,11 @@ class DotsOCRParser:
 
     def _inference_with_vllm(self, image, prompt):
         from dots_ocr.model.inference import inference_with_vllm
+        extra = {**({"guided_layout": True} if self._guided_layout([prompt]) else {}), **self._ngram_fields()}
         return inference_with_vllm(image, prompt, model_name=self.model_name, protocol=self.protocol, ip=self.ip,
                                    port=self.port, temperature=self.temperature, top_p=self.top_p,
                                    max_completion_tokens=self.max_completion_tokens,
-                                   **({"extra_body": {"guided_layout": True}} if self._guided_layout([prompt]) else {}))
+                                   **({"extra_body": extra} if extra else {}))
 
     # ------------------------------------------------------------------ per-page pipeline
     def get_prompt(self, prompt_mode, bbox=None, origin_image=None, image=None, min_pixels=None, max_pixels=None):

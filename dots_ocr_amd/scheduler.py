@@ -34,6 +34,7 @@ class Request:
                                                 # then carries logprobs_out = Engine.row_logprobs(slot, its token count)
     rules: Optional[object] = None              # engine.LogitRules of this request (bias, allowed ids, min_tokens, stop ids, ignore_eos), or None
     guide: Optional[int] = None                 # handle of Engine.create_guide the request's output must follow, or None
+    ngram: Optional[object] = None              # engine.NgramRule of this request (no-repeat n-gram blocking), or None
 
     def n_patches(self) -> int:
         if self.grid_thw is None:
@@ -82,6 +83,7 @@ class ContinuousBatcher:
         self._row_lp: Dict[int, int] = {}                        # slot -> the logprobs top_n set on it (engine.set_row_logprobs)
         self._row_rules: Dict[int, object] = {}                  # slot -> the LogitRules set on it (engine.set_row_logit_rules)
         self._row_guide: Dict[int, int] = {}                     # slot -> the guide handle set on it (engine.set_row_guide)
+        self._row_ngram: Dict[int, object] = {}                  # slot -> the NgramRule set on it (engine.set_row_ngram)
         self.kv_truncated = 0                                    # sequences ended early by a dry KV pool (finish reason "kv_pool_exhausted")
         self._rejected: List[Tuple[int, Request]] = []           # requests whose own parameters the engine refused (reported by step())
         self.eos_ids = tuple(int(t) for t in eos_ids)
@@ -107,6 +109,8 @@ class ContinuousBatcher:
             raise ValueError("this engine cannot honour logit rules (no set_row_logit_rules)")
         if req.guide is not None and not hasattr(self.engine, "set_row_guide"):
             raise ValueError("this engine cannot honour a guide (no set_row_guide)")
+        if req.ngram is not None and not hasattr(self.engine, "set_row_ngram"):
+            raise ValueError("this engine cannot honour an n-gram rule (no set_row_ngram)")
         if req.rules is not None and hasattr(req.rules, "eos_ids"):
             # what the engine will check at admission, checked here against the EOS ids and the vocabulary this batcher runs under: rules
             # that could never select a token are refused before the request is queued, where it fails alone
@@ -206,6 +210,8 @@ class ContinuousBatcher:
                 self.engine.set_row_logit_rules(s, None)
             if self._row_guide.pop(s, None) is not None:
                 self.engine.set_row_guide(s, None)
+            if self._row_ngram.pop(s, None) is not None:
+                self.engine.set_row_ngram(s, None)
 
     def _set_rows(self, s, r):
         """per-row parameters of request r on slot s; they apply from the first token the prefill selects"""
@@ -229,6 +235,11 @@ class ContinuousBatcher:
             self.engine.set_row_guide(s, r.guide)
         elif self._row_guide.pop(s, None) is not None:
             self.engine.set_row_guide(s, None)
+        if r.ngram is not None:                      # the n-gram rule likewise; it needs no reset, the row's output starts empty
+            self._row_ngram[s] = r.ngram
+            self.engine.set_row_ngram(s, r.ngram)
+        elif self._row_ngram.pop(s, None) is not None:
+            self.engine.set_row_ngram(s, None)
 
     def _prefill(self, group, rows_set: bool = False):
         # image rows are consumed in packed order, so sequences with images keep their relative order: pack the group as is
@@ -368,6 +379,8 @@ class ContinuousBatcher:
                 if req.logprobs is not None:         # read before the release switches the slot's logprobs off
                     req.logprobs_out = self.engine.row_logprobs(s, len(toks))
                 done.append((rid, req, toks))
+                if self._row_ngram.pop(s, None) is not None:     # the rule leaves with its request (the engine's release clears the row too)
+                    self.engine.set_row_ngram(s, None)
                 self.engine.slot_release(s)
                 self._row_guide.pop(s, None)         # the release cleared the row's guide: its handle is free to be evicted
         self._last_lens = {s: int(lens[s]) for s in self.running}      # after the finished slots have left: only what is still decoding

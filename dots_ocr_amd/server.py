@@ -17,6 +17,10 @@ other parameters wait for the running set to drain, and a request that asks for 
 need continuous batching on an engine that has them, else 400.
 `logit_bias`, `allowed_token_ids`, `min_tokens`, `stop_token_ids` and `ignore_eos` travel as the request's LogitRules on its slot
 (Engine.set_row_logit_rules); a worker that cannot honour them (static batching, an engine without the call) answers 400.
+`no_repeat_ngram_size`, `no_repeat_ngram_window` and `no_repeat_ngram_whitelist` (token ids) travel as the request's NgramRule on its slot
+(Engine.set_row_ngram): the row never completes an n-gram its own output already holds, inside the last `window` generated
+tokens when one is given, whitelisted ids excepted.  The prompt is not part of the history (vLLM's convention).  Bad values, and a worker
+that cannot honour the fields (static batching, an engine without the call), answer 400.
 `BatchingWorker` (static batches through `model.generate`) remains for model objects without engine slots.
 """
 from __future__ import annotations
@@ -38,7 +42,7 @@ from .processing import ASSISTANT, END_USER, IMG_END, IMG_PAD, IMG_START, USER
 
 class _Job:
     __slots__ = ("image", "text", "max_tokens", "temperature", "top_p", "top_k", "repetition_penalty", "frequency_penalty",
-                 "presence_penalty", "seed", "logprobs", "rules", "guide", "future")
+                 "presence_penalty", "seed", "logprobs", "rules", "guide", "ngram", "future")
 
     def __init__(self, image, text, max_tokens, temperature, top_p, top_k=0, repetition_penalty=1.0, frequency_penalty=0.0,
                  presence_penalty=0.0, seed=None, logprobs=None):
@@ -48,6 +52,7 @@ class _Job:
         self.logprobs = logprobs                    # top_logprobs (0..20) when the request asked for logprobs, else None
         self.rules = None                           # engine.LogitRules when the request carries logit rules, else None
         self.guide = None                           # guided.Guide when the request carries a guided decoding field, else None
+        self.ngram = None                           # engine.NgramRule when the request carries no_repeat_ngram_size, else None
         self.future: Future = Future()
 
     @property
@@ -187,6 +192,11 @@ class ContinuousWorker(BatchingWorker):
         """the engine takes per-request logit rules (Engine.set_row_logit_rules)"""
         return hasattr(self.model.engine, "set_row_logit_rules")
 
+    @property
+    def has_ngram(self) -> bool:
+        """the engine takes per-request n-gram rules (Engine.set_row_ngram)"""
+        return hasattr(self.model.engine, "set_row_ngram")
+
     GUIDE_CACHE = 16                                 # compiled guides kept on the engine
 
     @property
@@ -275,7 +285,7 @@ class ContinuousWorker(BatchingWorker):
                         req = Request(ids, inputs.get("pixel_values"), None if "image_grid_thw" not in inputs
                                       else inputs["image_grid_thw"].numpy(), job.max_tokens, tag=job,
                                       sampling=self._row_params(job) if per_row else None, logprobs=job.logprobs, rules=job.rules,
-                                      guide=self._guide_handle(job))
+                                      guide=self._guide_handle(job), ngram=job.ngram)
                         try:
                             cb.submit(req)
                         except Exception:
@@ -490,6 +500,29 @@ def _rule_fields(req: dict, vocab_size: Optional[int], max_tokens: int, eos_ids=
     return None if rules.empty else rules
 
 
+NGRAM_FIELDS = ("no_repeat_ngram_size", "no_repeat_ngram_window", "no_repeat_ngram_whitelist")
+
+
+def _ngram_fields(req: dict, vocab_size: Optional[int], max_seq_len: Optional[int] = None):
+    """`no_repeat_ngram_size` (HF's name; 0 or absent = off), `no_repeat_ngram_window` (0 or absent = the whole output) and
+    `no_repeat_ngram_whitelist` (token ids) of a request -> engine.NgramRule, or None when the request asks for none.  ValueError /
+    TypeError on a bad value."""
+    if all(req.get(k) is None for k in NGRAM_FIELDS):
+        return None
+    from .engine import NgramRule
+    n, w, wl = (req.get(k) for k in NGRAM_FIELDS)
+    for name, v in (("no_repeat_ngram_size", n), ("no_repeat_ngram_window", w)):
+        if v is not None and (isinstance(v, bool) or not isinstance(v, int) or v < 0):
+            raise TypeError(f"{name} must be an integer >= 0")
+    if wl is not None and (not isinstance(wl, list) or any(isinstance(t, bool) or not isinstance(t, int) for t in wl)):
+        raise TypeError("no_repeat_ngram_whitelist must be a list of integer token ids")
+    if not n:
+        if w or wl:
+            raise ValueError("no_repeat_ngram_window and no_repeat_ngram_whitelist need no_repeat_ngram_size >= 1")
+        return None
+    return NgramRule(n, w or 0, tuple(wl or ()), vocab_size=vocab_size, max_seq_len=max_seq_len)
+
+
 def _logprobs_object(processor, toks, logprobs, top_n: int) -> dict:
     """The OpenAI `choices[i].logprobs` object: one entry per generated id (the final EOS included), each with `top_n` alternatives.
     logprobs = (tok_lp [n], top_ids [n, 20], top_lp [n, 20]) as Engine.row_logprobs returns them."""
@@ -564,6 +597,13 @@ def create_app(model, processor, model_name: str = "model", max_batch: int = 8, 
         if job.rules is not None and not (isinstance(worker, ContinuousWorker) and worker.has_rules):
             raise HTTPException(400, "logit_bias, allowed_token_ids, min_tokens, stop_token_ids and ignore_eos need continuous batching on an "
                                      "engine with per-row logit rules (Engine.set_row_logit_rules)")
+        try:
+            job.ngram = _ngram_fields(req, getattr(mcfg, "vocab_size", None), getattr(getattr(model, "engine", None), "max_seq_len", None))
+        except (TypeError, ValueError) as e:
+            raise HTTPException(400, f"bad n-gram rule: {e}")
+        if job.ngram is not None and not (isinstance(worker, ContinuousWorker) and worker.has_ngram):
+            raise HTTPException(400, "no_repeat_ngram_size, no_repeat_ngram_window and no_repeat_ngram_whitelist need continuous batching on an "
+                                     "engine with per-row n-gram rules (Engine.set_row_ngram)")
         if any(req.get(k) is not None for k in GUIDE_FIELDS):
             try:                                     # compiling a large schema takes a while: off the event loop
                 job.guide = await run_in_threadpool(_guide_fields, req, job.rules.min_tokens if job.rules is not None else 0)

@@ -260,6 +260,39 @@ int dots_guide_destroy(DotsEngine* e, int32_t id);
 int dots_set_row_guide(DotsEngine* e, int row, int32_t id);
 int dots_row_guide_state(DotsEngine* e, int row, int32_t* state_out);
 
+/* ---- No-repeat n-gram blocking: a row never completes an n-gram it has already produced.  The ban is computed on the device
+ * at every step from the row's own output, so it holds inside captured decode chunks.
+ *
+ * Let out[0 .. L) be the tokens the row has generated so far (the prefill's token is out[0]; the prompt is NOT part of the history, which is
+ * the convention of vLLM's logits processors — Hugging Face generate() also feeds the prompt to its no_repeat_ngram_size processor).  With
+ * n = size and W = window: if L < n - 1 nothing is banned; otherwise P = out[L - n + 1 .. L) (empty for n = 1), and for every i with
+ * max(0, L - W) <= i <= L - n (W = 0: from 0) and out[i .. i + n - 1) == P the id out[i + n - 1] is banned unless it is in the whitelist.
+ * So only n-grams lying wholly inside the last W generated tokens count.  With W = 0 and no whitelist this is what transformers'
+ * NoRepeatNGramLogitsProcessor(n) bans when given out as input_ids.
+ *
+ * A banned id is -inf where the allowed list of DotsLogitRules and the guide's bit enter (raw logit + bias, -inf for banned / not allowed /
+ * min_tokens / guide / n-gram, penalties, arg max or draw); dots_get_logits and the logprobs stay on the raw logits.  EOS and stop ids get no
+ * special treatment: whitelist them if they must stay selectable.  Like a row with rules, an n-gram row without DotsSamplingParams of its
+ * own is selected with the engine-wide setting as it stands at the call.  A row the ban, the rules and a guide together leave nothing for
+ * commits id 0 (a guide's state does not move), as an all -inf row of the rules does.
+ *
+ * dots_set_row_ngram    row `row` carries *r from the next selected token on (NULL: none), written in stream order by a one-thread kernel:
+ *                       captured decode graphs are kept (one more graph per step shape exists for "some row carries an n-gram rule").
+ *                       Switching it on for a running row is exact from the next step: the history is always on the device.  A prefill
+ *                       needs no reset, the row's output starts empty.  dots_slot_release / dots_slots_reset clear the row.  The first
+ *                       call allocates the banned bits (max_batch x vocab / 8 bytes) and the row table.
+ * DOTS_E_INVALID: size outside [1, DOTS_MAX_NGRAM_SIZE], window neither 0 nor in [size, max_seq_len], more than DOTS_MAX_NGRAM_WHITELIST
+ * whitelist ids, one outside [0, vocab) or given twice, a vocabulary above 524 288. */
+#define DOTS_MAX_NGRAM_SIZE 64
+#define DOTS_MAX_NGRAM_WHITELIST 16
+typedef struct DotsNgramRule {
+    int32_t size;                /* n: 1 .. DOTS_MAX_NGRAM_SIZE */
+    int32_t window;              /* W: 0 = the whole output, else size .. max_seq_len */
+    int32_t n_whitelist;         /* 0 .. DOTS_MAX_NGRAM_WHITELIST */
+    int32_t whitelist[DOTS_MAX_NGRAM_WHITELIST]; /* ids that are never banned by this rule */
+} DotsNgramRule;
+int dots_set_row_ngram(DotsEngine* e, int row, const DotsNgramRule* r);
+
 /* Log-probabilities: log_softmax of the raw fp32 logits of the step (before penalties, temperature, top-k and top-p:
  * the values dots_get_logits returns), for every token a row commits, the prefill's first token included.  The top entries are
  * ordered by value descending, then index ascending.  lse comes from per-chunk (max, sum) pairs merged in a fixed chunk order, so a
@@ -465,6 +498,15 @@ int dots_op_select_tokens_guided(DotsEngine* e, const float* logits_dev, int B, 
 int dots_bench_select_tokens_guided(DotsEngine* e, const float* logits_dev, int B, int V, const DotsSamplingParams* params_host, const DotsLogitRules* rules_host,
                                     const int32_t* n_gen_host, const int32_t* guide_ids_host, const int32_t* states_host, const int32_t* hist_dev,
                                     const int32_t* hist_lens_dev, int hist_stride, const int32_t* n_prompt_dev, int iters, float* ms_out);
+/* dots_op_select_tokens_rules with n-gram rules: row b carries ngram_host[b] unless its size is 0.  Its history is hist[n_prompt[b] ..
+ * hist_lens[b]) — the generated part of the row — and a window may reach hist_stride.  No guides and no explicit n_gen here (min_tokens counts
+ * hist_lens - n_prompt).  dots_bench_select_tokens_ngram times the stage, the ban kernel included, on the same inputs. */
+int dots_op_select_tokens_ngram(DotsEngine* e, const float* logits_dev, int B, int V, const DotsSamplingParams* params_host, const DotsLogitRules* rules_host,
+                                const DotsNgramRule* ngram_host, const int32_t* hist_dev, const int32_t* hist_lens_dev, int hist_stride,
+                                const int32_t* n_prompt_dev, int32_t* out_tokens_dev);
+int dots_bench_select_tokens_ngram(DotsEngine* e, const float* logits_dev, int B, int V, const DotsSamplingParams* params_host, const DotsLogitRules* rules_host,
+                                   const DotsNgramRule* ngram_host, const int32_t* hist_dev, const int32_t* hist_lens_dev, int hist_stride,
+                                   const int32_t* n_prompt_dev, int iters, float* ms_out);
 /* The log-probability stage over caller logits: logits_dev fp32 [B, ld] (V <= ld), top_n_host [B] (-1 = row skipped, 0..20),
  * chosen_dev int32 [B] the chosen ids; writes tok_lp_dev float [B], top_ids_dev int32 [B][20], top_lp_dev float [B][20] of every row
  * with top_n >= 0 (entries beyond top_n: -1 / NaN).  The same two kernels the engine runs. */

@@ -15,6 +15,11 @@
         the guided-decoding leg (profiles/guided.txt): rows_greedy and rows_loaded with 0 / 1 / all rows following the layout
         guide (guided.layout_schema) from assorted states over a synthetic byte-level token table, the mask kernel included; the ruled
         stage of the same build beside them; and the host-side cost of Engine.create_guide and Engine.set_row_guide
+    python tools/sampling_bench.py --ngram [--rows 1 8 64] [--iters 200]
+        the n-gram leg (profiles/ngram.txt): rows_greedy and rows_loaded with every row carrying a no-repeat rule n = 30, first
+        with W = 90 and then with W = 0, the ban kernel included, over generated histories of 64 / 1024 / 16 384 tokens — random ids
+        (ordinary text: a candidate is dropped at its first token) and a period-7 loop (the worst case: every candidate matches all 29) —
+        beside the same stage of the same build without a rule; and the host-side cost of Engine.set_row_ngram
     python tools/sampling_bench.py --rows 64 --iters 20
         under `rocprofv3 --kernel-trace --stats -- python tools/sampling_bench.py ...` for the per-kernel split.
 Logits: a seeded N(0, 2) background with 64 planted tokens in [8, 14] per row (an LM-like peaked head); histories of 1200 prompt ids
@@ -38,9 +43,12 @@ def main():
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--rules", action="store_true", help="the logit-rule leg instead of the four stages")
     ap.add_argument("--guided", action="store_true", help="the guided-decoding leg instead of the four stages")
+    ap.add_argument("--ngram", action="store_true", help="the no-repeat n-gram leg instead of the four stages")
     a = ap.parse_args()
     if a.guided:
         return guided_leg(a)
+    if a.ngram:
+        return ngram_leg(a)
     import torch
     from dots_ocr_amd.config import DotsConfig
     from dots_ocr_amd.engine import Engine, SamplingParams
@@ -169,6 +177,57 @@ def guided_leg(a):
     print(json.dumps({"stage": "set_row_guide", "host_us_per_call": round((t1 - t0) / 50 * 1e6, 1),
                       "with_final_sync_us_per_call": round((t2 - t0) / 50 * 1e6, 1)}), flush=True)
     eng.close()
+
+
+def ngram_leg(a):
+    import time
+    import torch
+    from dots_ocr_amd.config import DotsConfig
+    from dots_ocr_amd.engine import Engine, NgramRule, SamplingParams
+    eng = Engine(DotsConfig.tiny(), max_batch=4, max_seq_len=512, max_patches=256, max_prefill_tokens=256)
+    rng = np.random.default_rng(0)
+    B_max = max(a.rows)
+    logits = rng.normal(0.0, 2.0, (B_max, V)).astype(np.float32)
+    for b in range(B_max):
+        logits[b, rng.choice(V, 64, replace=False)] = rng.uniform(8.0, 14.0, 64)
+    d_l = torch.from_numpy(logits).cuda()
+    n_prompt = 1200
+    greedy = SamplingParams()
+    loaded = [SamplingParams(temperature=0.1, top_p=0.9, top_k=50, repetition_penalty=1.1, frequency_penalty=0.2, presence_penalty=0.2, seed=b)
+              for b in range(B_max)]
+    for n_gen in (64, 1024, 16384):
+        stride = n_prompt + n_gen
+        for kind in ("random", "loop"):
+            hist = rng.integers(0, V, (B_max, stride)).astype(np.int32)
+            if kind == "loop":
+                hist[:, n_prompt:] = hist[:, n_prompt:n_prompt + 7][:, np.arange(n_gen) % 7]
+            d_h = torch.from_numpy(hist).cuda()
+            d_n = torch.full((B_max,), stride, dtype=torch.int32, device="cuda")
+            d_p = torch.full((B_max,), n_prompt, dtype=torch.int32, device="cuda")
+            torch.cuda.synchronize()
+            for B in a.rows:
+                for name, params in (("rows_greedy", [greedy] * B), ("rows_loaded", loaded[:B])):
+                    for tag, rule in (("", None), ("+ngram(n=30,W=90)", NgramRule(30, 90)), ("+ngram(n=30,W=0)", NgramRule(30, 0))):
+                        if rule is not None and n_gen < rule.window:
+                            continue                                     # the window would reach past the history: same as W = 0
+                        ms = eng.bench_select_tokens_ngram(d_l.data_ptr(), B, V, params, [None] * B, [rule] * B, d_h.data_ptr(), d_n.data_ptr(), stride,
+                                                           d_p.data_ptr(), a.iters)
+                        print(json.dumps({"rows": B, "V": V, "history": n_gen, "kind": kind, "stage": name + tag, "us": round(ms * 1e3, 2),
+                                          "iters": a.iters}), flush=True)
+    eng.close()
+    big = Engine(DotsConfig.tiny(vocab=V), max_batch=4, max_seq_len=512, max_patches=256, max_prefill_tokens=256)
+    rule = NgramRule(30, 90, tuple(range(16)))
+    big.set_row_ngram(0, rule)                                           # first call: allocates the state
+    big.synchronize()
+    t0 = time.perf_counter()
+    for i in range(50):
+        big.set_row_ngram(i % 4, rule)
+    t1 = time.perf_counter()
+    big.synchronize()
+    t2 = time.perf_counter()
+    print(json.dumps({"stage": "set_row_ngram", "V": V, "host_us_per_call": round((t1 - t0) / 50 * 1e6, 1),
+                      "with_final_sync_us_per_call": round((t2 - t0) / 50 * 1e6, 1)}), flush=True)
+    big.close()
 
 
 if __name__ == "__main__":
