@@ -29,6 +29,7 @@
 #include "common.h"
 #include "decode_layout.h"
 #include "kernels.h"
+#include "step_dev.h"
 
 namespace {
 TRACE_DECL
@@ -563,45 +564,7 @@ __global__ __launch_bounds__(128) void decode_attn_combine_kernel(const float* _
 
 // ------------------------------------------------------------------------------------------------
 // greedy step glue: argmax (first index wins ties, like torch.argmax) in two stages, then EOS / length bookkeeping.
-constexpr int ARGMAX_CHUNKS = 64;
-
-// Commit one selected token of row (slot) b: append to its output, EOS / length bookkeeping, next-step input.
-// A finished row keeps decoding (fixed-shape graph) but its context is frozen, so it rewrites the same KV position for ever
-// and can idle in its slot until the host refills it (continuous batching).
-// rules: the row's logit rules (per-row stage only) or nullptr: its stop ids finish it too, RULE_IGNORE_EOS takes the engine's
-// EOS ids out of the test.  The arg-max and engine-wide sampler paths pass nullptr (a constant after inlining).
-// guide: the launch's guides (per-row stage only) or nullptr.  A guided row that is not finished advances its automaton by the
-// bytes of the committed token; an EOS or stop id moves nothing and finishes the row, RULE_IGNORE_EOS or not (the guide allowed it because
-// the state is accepting; with nothing else left to allow, a row that ignored it could only repeat it).
-DEVI void commit_token(const StepState& st, int b, int tok, const RowRules* rules = nullptr, const GuideSel* guide = nullptr) {
-    const bool done = st.finished[b] != 0;
-    if (st.advance_ctx && !done) st.ctx_len[b] += 1;
-    if (!done) {
-        const int n = st.out_lens[b];
-        const int cap = st.max_len ? st.max_len[b] : st.cap;
-        st.out_ids[(size_t)b * st.out_stride + n] = tok;
-        st.out_lens[b] = n + 1;
-        bool eos = false;
-        const bool guided = guide && guide->rows[b].table;
-        if (guided || !(rules && (rules->flags & RULE_IGNORE_EOS)))
-            for (int k = 0; k < st.n_eos; ++k) eos = eos || (tok == st.eos_ids[k]);
-        if (rules)
-            for (int k = 0; k < min(rules->n_stop, DOTS_MAX_STOP_IDS); ++k) eos = eos || (tok == rules->stop[k]);
-        if (guided && !eos && tok >= 0 && tok < guide->V) {
-            RowGuide& rg = guide->rows[b];
-            uint32_t s = (uint32_t)rg.state;
-            for (int j = guide->tok_off[tok], end = guide->tok_off[tok + 1]; j < end && s != GUIDE_DEAD; ++j)
-                s = rg.table[(size_t)s * 256 + guide->tok_bytes[j]];
-            if (s != GUIDE_DEAD) rg.state = (int32_t)s;              // a token the guide did not allow (the all -inf fallback) moves nothing
-        }
-        if (eos || n + 1 >= cap) st.finished[b] = 1;
-    }
-    st.cur_tokens[b] = tok;
-}
-
-DEVI void argmax_merge(float& best, int& bi, float ov, int oi) {
-    if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-}
+// ARGMAX_CHUNKS, commit_token and argmax_merge live in step_dev.h: the speculative accept walk (spec.hip) commits through the same code.
 
 // grid (ARGMAX_CHUNKS, B): partial (value, index) of one vocabulary chunk
 __global__ __launch_bounds__(256) void argmax_partial_kernel(const float* __restrict__ logits, int V, int ld,

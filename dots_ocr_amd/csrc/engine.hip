@@ -240,6 +240,12 @@ struct DotsEngine {
     int32_t *lp_ids = nullptr, *lp_pi = nullptr, *lp_pos = nullptr;
     int row_lp[DOTS_MAX_BATCH];
     int n_lp = 0;                          // rows with logprobs on: > 0 adds the two logprob kernels around the selection stage
+    // n-gram speculative decoding (dots_set_speculation): spec_k drafts per slot and step (0 = off), the drafter's n-gram
+    // sizes (spec_max_n == 0: host drafts only), and — allocated by the first call that switches it on — the slots' drafts, the expanded
+    // row arrays of a speculating step and the counters (kernels.h SpecState)
+    int spec_k = 0, spec_min_n = 0, spec_max_n = 0;
+    int32_t *sp_drafts = nullptr, *sp_ndraft = nullptr, *sp_nlive = nullptr, *sp_tokens = nullptr, *sp_ctx = nullptr, *sp_table = nullptr;
+    unsigned long long* sp_stats = nullptr;
     int out_cap = 0;                       // row stride of out_ids for the current generation
     bf16_t *d_h = nullptr, *d_q = nullptr, *d_att = nullptr, *d_act = nullptr, *d_xn = nullptr;      // d_xn: normalised rows of batches above 32 rows (decode_b64.hip)
     float* d_part_h = nullptr;                     // [DEC_KSPLIT_PARTS][DOTS_MAX_BATCH][hidden] fp32: the K-quarter sums of a projection above 32 rows (decode_b64.hip)
@@ -264,8 +270,9 @@ struct DotsEngine {
     // the output buffer) or slot mode (out_cap = 0), number of EOS ids, whether any row carries its own parameters (rowp: the per-row
     // selection stage), whether any row returns logprobs (lp), whether any row carries logit rules (rules: the stage then gets their
     // table), whether any row holds a guide (guided: the mask kernel and the guides' tables), whether any row carries an n-gram rule (ngram:
-    // the ban kernel and its bits); engine-wide sampling changes drop the cache (dots_set_sampling), per-row ones live in device memory
-    struct StepGraph { int rows, splits, out_cap, n_eos, part, rowp, lp, rules, guided, ngram; hipGraph_t graph; hipGraphExec_t exec; };
+    // the ban kernel and its bits), the draft count of a speculating step (spec: 0 = the plain step); engine-wide sampling changes drop
+    // the cache (dots_set_sampling), per-row ones live in device memory
+    struct StepGraph { int rows, splits, out_cap, n_eos, part, rowp, lp, rules, guided, ngram, spec; hipGraph_t graph; hipGraphExec_t exec; };
     std::vector<StepGraph> step_graphs;
     std::vector<int> h_prompt_lens;
     int steps_done = 0;
@@ -880,6 +887,21 @@ int vit_forward(DotsEngine* e, const float* pix_dev, int64_t N, const int64_t* g
     return DOTS_OK;
 }
 
+// the bookkeeping arrays of a slot-mode step, as select_tokens hands them to the selection kernels (the speculative kernels of spec.hip
+// read and commit through the same state)
+StepState step_state(const DotsEngine* e, int advance, const int32_t* sel) {
+    StepState st;
+    st.cur_tokens = e->cur_tokens; st.ctx_len = e->ctx_len; st.out_ids = e->out_ids; st.out_lens = e->out_lens; st.finished = e->finished;
+    st.eos_ids = e->eos_ids; st.n_eos = e->n_eos; st.advance_ctx = advance;
+    st.sel = sel; st.max_len = e->d_max_len; st.out_stride = e->cfg.max_seq_len; st.cap = e->cfg.max_seq_len;
+    return st;
+}
+
+SpecState spec_state(const DotsEngine* e) {
+    return SpecState{e->sp_drafts, e->sp_ndraft, e->sp_nlive, e->sp_tokens, e->sp_ctx, e->sp_table, e->sp_stats,
+                     e->n_own > 0 ? e->d_row_own : nullptr, e->n_lp > 0 ? e->d_row_lp : nullptr, e->spec_k, e->temperature > 0.f ? 0 : 1};
+}
+
 // greedy arg max or temperature / top-p sampling over the fp32 logits of the step
 int select_tokens(DotsEngine* e, int advance) {
     const DotsConfig& c = e->cfg;
@@ -1271,6 +1293,9 @@ int prefill(DotsEngine* e, const int32_t* ids, const int32_t* lens, int B, const
         S[b] = slots ? slots[b] : b;
         if (slots) {
             if (S[b] < 0 || S[b] >= c.max_batch) return e->fail(DOTS_E_INVALID, "slot %d out of range [0, %d)", S[b], c.max_batch);
+            if (e->spec_k && S[b] >= c.max_batch / (e->spec_k + 1))
+                return e->fail(DOTS_E_CAPACITY, "slot %d is not usable while speculating: with %d drafts a slot takes %d rows of a step, so only slots [0, max_batch / (k + 1)) = [0, %d) are",
+                               S[b], e->spec_k, e->spec_k + 1, c.max_batch / (e->spec_k + 1));
             if (e->slot_mode && e->slot_active[S[b]]) return e->fail(DOTS_E_STATE, "slot %d is occupied", S[b]);
             for (int a = 0; a < b; ++a)
                 if (S[a] == S[b]) return e->fail(DOTS_E_INVALID, "slot %d listed twice", S[b]);
@@ -1346,6 +1371,10 @@ int prefill(DotsEngine* e, const int32_t* ids, const int32_t* lens, int B, const
             CK(hipMemcpyAsync(e->d_max_len + S[b], max_new + b, 4, hipMemcpyHostToDevice, s));
             CK(hipMemsetAsync(e->out_lens + S[b], 0, 4, s));
             CK(hipMemsetAsync(e->finished + S[b], 0, 4, s));
+            if (e->sp_ndraft) {                            // a new sequence: no drafts, its own counters from zero
+                CK(hipMemsetAsync(e->sp_ndraft + S[b], 0, 4, s));
+                CK(hipMemsetAsync(e->sp_stats + (size_t)S[b] * 3, 0, 3 * sizeof(unsigned long long), s));
+            }
         }
         CK(hipMemcpyAsync(e->d_sel_new, sel_new, DOTS_MAX_BATCH * 4, hipMemcpyHostToDevice, s));
         CK(hipMemcpyAsync(e->p_dst, S.data(), B * 4, hipMemcpyHostToDevice, s));
@@ -1417,9 +1446,18 @@ int decode_step_launches(DotsEngine* e, int n_splits, int part = 0) {
     const DotsConfig& c = e->cfg;
     hipStream_t s = e->stream;
     const int H = c.hidden_size, Hq = c.num_heads, Hkv = c.num_kv_heads, Nq = Hq * 128, I = c.intermediate_size;
-    const int B = e->B;
+    // A speculating step (slot mode, dots_set_speculation): `rows` slots become B = rows x (k + 1) rows whose tokens, contexts and
+    // block-table rows spec_expand_kernel builds; the first `rows` of them are the rows of the plain step
+    const int rows = e->B, spec_k = e->slot_mode ? e->spec_k : 0;
+    const int B = rows * (spec_k + 1);
     const float scale = 1.0f / sqrtf(128.0f);
-    CK(launch_dec_embed(s, e->cur_tokens, e->embed, e->d_h, B, H));
+    const int32_t *tokens = e->cur_tokens, *ctx_len = e->ctx_len, *block_table = e->block_table;
+    const SpecState sp = spec_state(e);
+    if (spec_k) {
+        CK(launch_spec_expand(s, sp, step_state(e, 1, e->d_sel), e->block_table, e->max_pages, rows, e->n_pool_pages));
+        tokens = e->sp_tokens; ctx_len = e->sp_ctx; block_table = e->sp_table;
+    }
+    CK(launch_dec_embed(s, tokens, e->embed, e->d_h, B, H));
     if (e->force_part) part = 1;                                                   // dots_set_decode_plan(1): the partition plan on every step (tests, A/B runs)
     static const bool same_layer = getenv("DOTS_OCR_DEBUG_SAME_LAYER") != nullptr;   // experiment: all weight reads hit the Infinity Cache
     bool pend = false;                              // down_proj of the previous layer left its K-quarter sums in d_part_h: the next norm launch applies them
@@ -1427,11 +1465,11 @@ int decode_step_launches(DotsEngine* e, int n_splits, int part = 0) {
     for (int i = 0; i < c.num_layers; ++i) {
         const LLayer& L = e->ll[same_layer ? 0 : i];
         bf16_t* pool_l = e->pool + e->pool_layer_elems * i;
-        CK(launch_dec_qkv(s, e->d_h, L.ln1, L.qkv_wd, L.qkv_s, L.qkv_b, e->lm_inv_freq, e->ctx_len, e->block_table, e->max_pages, pool_l, e->d_q, B, H, Hq,
+        CK(launch_dec_qkv(s, e->d_h, L.ln1, L.qkv_wd, L.qkv_s, L.qkv_b, e->lm_inv_freq, ctx_len, block_table, e->max_pages, pool_l, e->d_q, B, H, Hq,
                           Hkv, c.rms_norm_eps, part ? e->dec_cus : 0, e->d_xn, pend ? e->d_part_h : nullptr, pend_scale, layer_kv_scales(e, i)));
-        CK(launch_decode_attn(s, e->d_q, pool_l, e->ctx_len, e->block_table, e->max_pages, e->d_part_o, e->d_part_ml, B, Hq, Hkv, n_splits, scale, part ? e->dec_cus : 0, e->attn_stream,
+        CK(launch_decode_attn(s, e->d_q, pool_l, ctx_len, block_table, e->max_pages, e->d_part_o, e->d_part_ml, B, Hq, Hkv, n_splits, scale, part ? e->dec_cus : 0, e->attn_stream,
                               layer_kv_scales(e, i)));
-        CK(launch_decode_attn_combine(s, e->d_part_o, e->d_part_ml, e->ctx_len, e->d_att, B, Hq, Hkv, n_splits));
+        CK(launch_decode_attn_combine(s, e->d_part_o, e->d_part_ml, ctx_len, e->d_att, B, Hq, Hkv, n_splits));
         bool pend_o = false;
         CK(launch_dec_proj(s, e->d_att, L.o_wd, L.o_s, e->d_h, B, H, Nq, part ? e->dec_cus : 0, e->d_part_h, &pend_o));
         CK(launch_dec_gateup(s, e->d_h, L.ln2, L.w13_wd, L.w13_s, e->d_act, B, H, I, c.rms_norm_eps, part ? e->dec_cus : 0, e->d_xn, pend_o ? e->d_part_h : nullptr, L.o_s));
@@ -1440,9 +1478,19 @@ int decode_step_launches(DotsEngine* e, int n_splits, int part = 0) {
     }
     CK(launch_dec_lmhead(s, e->d_h, e->final_norm, e->lm_head_d, e->lm_head_s, e->d_logits, B, H, c.vocab_size, c.rms_norm_eps, part ? e->dec_cus : 0, e->d_xn,
                          pend ? e->d_part_h : nullptr, pend_scale));
-    e->B_sel = B;
+    if (spec_k) CK(launch_spec_argmax(s, sp, e->d_logits, c.vocab_size, c.vocab_size, rows, e->am_val, e->am_idx));
+    e->B_sel = rows;
     e->sel_now = e->d_sel;
     RET(select_tokens(e, 1));
+    if (spec_k) {
+        // the selection stage committed row 0 of every slot; the accept walk commits what the drafts got right, then the drafter reads
+        // the grown output
+        const StepState st = step_state(e, 1, e->d_sel);
+        CK(launch_spec_accept(s, sp, st, rows, e->am_val, e->am_idx));
+        if (e->spec_max_n > 0)
+            CK(launch_ngram_draft(s, st.out_ids, st.out_lens, st.out_stride, st.finished, st.sel, sp.own, sp.lp, sp.engine_greedy, rows, spec_k, e->spec_min_n,
+                                  e->spec_max_n, e->sp_drafts, DOTS_MAX_SPEC_DRAFTS, e->sp_ndraft));
+    }
     return DOTS_OK;
 }
 
@@ -1451,15 +1499,15 @@ int splits_for_ctx(int max_ctx) { return decode_attn_splits(max_ctx); }
 // The captured decode step for (rows = e->B, splits, out_cap, e->n_eos): looked up in the cache or captured now.
 int step_graph(DotsEngine* e, int rows, int n_splits, int out_cap, hipGraphExec_t* exec, int part = 0) {
     const int rowp = e->n_own > 0 ? 1 : 0, lp = e->n_lp > 0 ? 1 : 0, rules = e->n_rules > 0 ? 1 : 0, guided = e->n_guided > 0 ? 1 : 0,
-              ngram = e->n_ngram > 0 ? 1 : 0;
+              ngram = e->n_ngram > 0 ? 1 : 0, spec = e->slot_mode ? e->spec_k : 0;
     for (auto& g : e->step_graphs)
         if (g.rows == rows && g.splits == n_splits && g.out_cap == out_cap && g.n_eos == e->n_eos && g.part == part && g.rowp == rowp && g.lp == lp && g.rules == rules &&
-            g.guided == guided && g.ngram == ngram) {
+            g.guided == guided && g.ngram == ngram && g.spec == spec) {
             *exec = g.exec;
             return DOTS_OK;
         }
     if (e->step_graphs.size() >= 32) drop_step_graphs(e);
-    DotsEngine::StepGraph g{rows, n_splits, out_cap, e->n_eos, part, rowp, lp, rules, guided, ngram, nullptr, nullptr};
+    DotsEngine::StepGraph g{rows, n_splits, out_cap, e->n_eos, part, rowp, lp, rules, guided, ngram, spec, nullptr, nullptr};
     CK(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
     int r = decode_step_launches(e, n_splits, part);
     hipError_t ce = hipStreamEndCapture(e->stream, &g.graph);
@@ -1851,6 +1899,7 @@ int dots_slots_reset(DotsEngine* e) {
     if (e->d_row_lp) CK(hipMemsetAsync(e->d_row_lp, 0xFF, DOTS_MAX_BATCH * 4, s));
     std::fill(e->row_lp, e->row_lp + DOTS_MAX_BATCH, -1);
     e->n_lp = 0;
+    if (e->sp_ndraft) CK(hipMemsetAsync(e->sp_ndraft, 0, DOTS_MAX_BATCH * 4, s));
     CK(hipStreamSynchronize(s));
     e->slot_mode = true;
     e->sel_dirty = true;
@@ -1877,14 +1926,25 @@ int dots_slots_decode(DotsEngine* e, int n_steps) {
     // ---- paged KV: every running sequence gets the pages the next n_steps positions need, now.  Pool dry: the sequence keeps what it
     // has and its generation cap is lowered to what its pages hold — it finishes there with "length", like HF generate at the
     // context capacity (an admission policy that leaves head-room makes this rare: dots_ocr_amd/scheduler.py).
+    // A speculating step may advance a row by spec_k + 1 positions and writes KV that far ahead: pages and the host's bound on the
+    // context count n_steps x (k + 1) (dots_slots_poll brings the bound back to the row's true context)
+    n_steps *= e->spec_k + 1;
     for (int b = 0; b < rows; ++b) {
         if (!e->slot_active[b] || e->slot_done[b]) continue;
         // A step at context c writes KV position c and brings the sequence to c + 2 tokens, so n_steps more steps need positions
         // [0, ctx + n_steps), and a sequence limited to slot_limit tokens never writes beyond position slot_limit - 2.
-        const int want = std::min(e->slot_ctx_ub[b] + n_steps, e->slot_limit[b] - 1);
+        int want = std::min(e->slot_ctx_ub[b] + n_steps, e->slot_limit[b] - 1);
         bool changed = false;
         const int have = grow_pages(e, b, want, &changed);
         if (changed) CK(upload_table_row(e, b));
+        if (have < want && e->spec_k) {
+            // before a speculating row is capped, its bound becomes its true context: steps that accepted fewer than k drafts left it too high
+            int32_t ctx = 0;
+            CK(hipMemcpyAsync(&ctx, e->ctx_len + b, 4, hipMemcpyDeviceToHost, s));
+            CK(hipStreamSynchronize(s));
+            e->slot_ctx_ub[b] = std::min(e->slot_ctx_ub[b], (int)ctx);
+            want = std::min(e->slot_ctx_ub[b] + n_steps, e->slot_limit[b] - 1);
+        }
         if (have < want) {
             // Positions [0, have) exist: the last step the row may take is the one at context have - 1, which leaves it with have + 1
             // tokens.  commit_token finishes a row when a step brings it to its cap — so a row that already sits AT context `have`
@@ -1900,6 +1960,7 @@ int dots_slots_decode(DotsEngine* e, int n_steps) {
         }
         e->slot_ctx_ub[b] = std::min(e->slot_ctx_ub[b] + n_steps, e->slot_limit[b] - 1);
     }
+    n_steps /= e->spec_k + 1;
     const int n_splits = splits_for_ctx(e->cfg.max_seq_len);
     e->B = rows;
     static const bool use_graph = getenv("DOTS_OCR_NO_GRAPH") == nullptr;
@@ -1934,7 +1995,12 @@ int dots_slots_poll(DotsEngine* e, int32_t* finished, int32_t* out_lens) {
     CK(hipStreamSynchronize(e->stream));
     for (int b = 0; b < mb; ++b) {
         if (!e->slot_mode || !e->slot_active[b]) { finished[b] = -1; out_lens[b] = 0; }      // -1: free slot
-        else if (finished[b]) e->slot_done[b] = 1;                                           // takes no more pages
+        else {
+            if (finished[b]) e->slot_done[b] = 1;                                            // takes no more pages
+            // every issued step has run: the context is prompt + generated - 1 exactly.  A speculating step advances a row by 1 .. k + 1
+            // positions, so dots_slots_decode counts k + 1 per step; without this the bound (and the pages taken ahead) would run away
+            if (e->spec_k) e->slot_ctx_ub[b] = std::min(e->slot_ctx_ub[b], e->slot_prompt[b] + out_lens[b] - 1);
+        }
     }
     return DOTS_OK;
 }
@@ -2240,6 +2306,73 @@ int dots_set_row_ngram(DotsEngine* e, int row, const DotsNgramRule* r) {
         e->n_ngram += 1;
         if (!e->row_own[row] && !e->row_rules[row] && !e->row_guide[row]) e->n_own += 1;
     }
+    return DOTS_OK;
+}
+
+// ---------------------------------------------------------------------------------- n-gram speculative decoding
+int dots_set_speculation(DotsEngine* e, int k, int min_n, int max_n) {
+    if (!e) return DOTS_E_INVALID;
+    if (k < 0 || k > DOTS_MAX_SPEC_DRAFTS) return e->fail(DOTS_E_INVALID, "k must be in [0, %d], got %d", DOTS_MAX_SPEC_DRAFTS, k);
+    if (k > 0 && max_n != 0 && (min_n < 1 || max_n < min_n || max_n > DOTS_MAX_NGRAM_SIZE))
+        return e->fail(DOTS_E_INVALID, "n-gram sizes must satisfy 1 <= min_n <= max_n <= %d (max_n = 0: host drafts only), got %d .. %d", DOTS_MAX_NGRAM_SIZE, min_n, max_n);
+    if (k > 0 && e->cfg.max_batch / (k + 1) < 1)
+        return e->fail(DOTS_E_CAPACITY, "%d drafts need %d rows per slot, max_batch is %d", k, k + 1, e->cfg.max_batch);
+    if (e->slot_mode)
+        for (int b = 0; b < e->cfg.max_batch; ++b)
+            if (e->slot_active[b]) return e->fail(DOTS_E_STATE, "speculation cannot change while slot %d is occupied", b);
+    CK(hipSetDevice(e->device));
+    hipStream_t s = e->stream;
+    if (k > 0 && !e->sp_stats) {
+        // each piece is allocated once: a call that failed half way is resumed by the next one
+        if (!e->sp_drafts) CK(e->alloc(&e->sp_drafts, (size_t)DOTS_MAX_BATCH * DOTS_MAX_SPEC_DRAFTS));
+        if (!e->sp_ndraft) CK(e->alloc(&e->sp_ndraft, (size_t)DOTS_MAX_BATCH));
+        if (!e->sp_nlive) CK(e->alloc(&e->sp_nlive, (size_t)DOTS_MAX_BATCH));
+        if (!e->sp_tokens) CK(e->alloc(&e->sp_tokens, (size_t)DOTS_MAX_BATCH));
+        if (!e->sp_ctx) CK(e->alloc(&e->sp_ctx, (size_t)DOTS_MAX_BATCH));
+        if (!e->sp_table) {
+            CK(e->alloc(&e->sp_table, (size_t)DOTS_MAX_BATCH * e->max_pages));
+            const std::vector<int32_t> idle((size_t)DOTS_MAX_BATCH * e->max_pages, e->n_pool_pages);      // every row on the scratch page
+            CK(hipMemcpyAsync(e->sp_table, idle.data(), idle.size() * 4, hipMemcpyHostToDevice, s));
+            CK(hipStreamSynchronize(s));
+        }
+        CK(e->alloc(&e->sp_stats, (size_t)(DOTS_MAX_BATCH + 1) * 3));      // set last, it is the guard above
+    }
+    if (e->sp_stats) {
+        CK(hipMemsetAsync(e->sp_stats, 0, (size_t)(DOTS_MAX_BATCH + 1) * 3 * sizeof(unsigned long long), s));
+        CK(hipMemsetAsync(e->sp_ndraft, 0, DOTS_MAX_BATCH * 4, s));
+        CK(hipStreamSynchronize(s));
+    }
+    drop_step_graphs(e);                                     // a captured step bakes in the draft count and the drafter's sizes
+    e->spec_k = k;
+    e->spec_min_n = k > 0 && max_n > 0 ? min_n : 0;
+    e->spec_max_n = k > 0 ? max_n : 0;
+    return DOTS_OK;
+}
+
+int dots_set_row_drafts(DotsEngine* e, int row, const int32_t* ids_host, int n) {
+    if (!e) return DOTS_E_INVALID;
+    if (row < 0 || row >= e->cfg.max_batch) return e->fail(DOTS_E_INVALID, "row %d out of range [0, %d)", row, e->cfg.max_batch);
+    if (n < 0 || n > e->spec_k) return e->fail(DOTS_E_INVALID, "%d drafts given, the engine speculates %d per step (dots_set_speculation)", n, e->spec_k);
+    if (n > 0 && !ids_host) return e->fail(DOTS_E_INVALID, "null argument");
+    for (int j = 0; j < n; ++j)
+        if (ids_host[j] < 0 || ids_host[j] >= e->cfg.vocab_size) return e->fail(DOTS_E_INVALID, "draft id %d out of range [0, %d)", ids_host[j], e->cfg.vocab_size);
+    if (!e->slot_mode || !e->slot_active[row]) return e->fail(DOTS_E_STATE, "slot %d is not occupied", row);
+    if (!e->spec_k) return DOTS_OK;                          // n == 0 with speculation off: nothing to clear
+    CK(hipSetDevice(e->device));
+    CK(launch_spec_set_drafts(e->stream, e->sp_drafts, e->sp_ndraft, row, ids_host, n));
+    return DOTS_OK;
+}
+
+int dots_spec_stats(DotsEngine* e, int row, int64_t* steps, int64_t* drafted, int64_t* accepted) {
+    if (!e || !steps || !drafted || !accepted) return e ? e->fail(DOTS_E_INVALID, "null argument") : DOTS_E_INVALID;
+    if (row < -1 || row >= e->cfg.max_batch) return e->fail(DOTS_E_INVALID, "row %d out of range [-1, %d)", row, e->cfg.max_batch);
+    *steps = *drafted = *accepted = 0;
+    if (!e->sp_stats) return DOTS_OK;
+    CK(hipSetDevice(e->device));
+    unsigned long long v[3] = {0, 0, 0};
+    CK(hipMemcpyAsync(v, e->sp_stats + (size_t)(row < 0 ? DOTS_MAX_BATCH : row) * 3, sizeof(v), hipMemcpyDeviceToHost, e->stream));
+    CK(hipStreamSynchronize(e->stream));
+    *steps = (int64_t)v[0]; *drafted = (int64_t)v[1]; *accepted = (int64_t)v[2];
     return DOTS_OK;
 }
 
@@ -3040,6 +3173,17 @@ int logprobs_op(DotsEngine* e, const float* logits_dev, int B, int V, int ld, co
 }  // namespace
 
 extern "C" {
+int dots_op_ngram_draft(DotsEngine* e, const int32_t* hist_dev, const int32_t* hist_lens_dev, int hist_stride, int B, int k, int min_n, int max_n,
+                        int32_t* drafts_dev, int32_t* n_drafts_dev) {
+    if (!e || !hist_dev || !hist_lens_dev || !drafts_dev || !n_drafts_dev) return e ? e->fail(DOTS_E_INVALID, "null argument") : DOTS_E_INVALID;
+    if (B < 1 || B > DOTS_MAX_BATCH || hist_stride < 1 || k < 1 || k > DOTS_MAX_SPEC_DRAFTS || min_n < 1 || max_n < min_n || max_n > DOTS_MAX_NGRAM_SIZE)
+        return e->fail(DOTS_E_INVALID, "ngram_draft: B in [1, %d], k in [1, %d], 1 <= min_n <= max_n <= %d", DOTS_MAX_BATCH, DOTS_MAX_SPEC_DRAFTS, DOTS_MAX_NGRAM_SIZE);
+    CK(hipSetDevice(e->device));
+    CK(launch_ngram_draft(e->stream, hist_dev, hist_lens_dev, hist_stride, nullptr, nullptr, nullptr, nullptr, 1, B, k, min_n, max_n, drafts_dev, k, n_drafts_dev));
+    CK(hipStreamSynchronize(e->stream));
+    return DOTS_OK;
+}
+
 int dots_op_logprobs(DotsEngine* e, const float* logits_dev, int B, int V, int ld, const int32_t* top_n_host, const int32_t* chosen_dev,
                      float* tok_lp_dev, int32_t* top_ids_dev, float* top_lp_dev) {
     if (!chosen_dev || !tok_lp_dev || !top_ids_dev || !top_lp_dev) return e ? e->fail(DOTS_E_INVALID, "bad logprobs arguments") : DOTS_E_INVALID;

@@ -211,6 +211,39 @@ hipError_t launch_set_row_ngram(hipStream_t s, RowNgram* table, int row, const R
 // in out_lens (explicit histories of dots_op_select_tokens_ngram; out_stride >= stride)
 hipError_t launch_ngram_history(hipStream_t s, const int32_t* hist, const int32_t* hist_lens, int stride, const int32_t* n_prompt, int B,
                                 int32_t* out_ids, int out_stride);
+// ---- spec.hip: n-gram speculative decoding of greedy rows
+// A speculating step runs over R = rows x (k + 1) rows, draft-major: row j * rows + b carries token j of (last token, draft 1 .. k) of slot
+// b at context ctx + j on the slot's own KV pages.  SpecState: the slots' drafts of the next step (drafts [DOTS_MAX_BATCH]
+// [DOTS_MAX_SPEC_DRAFTS], n_draft [DOTS_MAX_BATCH]), the expanded row arrays of the step (tokens / ctx_len [DOTS_MAX_BATCH], block_table
+// [DOTS_MAX_BATCH][max_pages]), n_live [DOTS_MAX_BATCH] (draft rows of slot b this step verifies; -1: the slot takes no step) and the
+// counters stats [DOTS_MAX_BATCH + 1][3] (steps, drafted, accepted; the last row holds the totals).  own / lp: the per-row selection flags
+// and the logprob table (nullptr: none exist) — a row that carries either, or any row while engine_greedy == 0, verifies no draft.
+#ifndef DOTS_MAX_SPEC_DRAFTS
+#define DOTS_MAX_SPEC_DRAFTS 15
+#endif
+struct SpecState {
+    int32_t *drafts, *n_draft, *n_live, *tokens, *ctx_len, *block_table;
+    unsigned long long* stats;
+    const int32_t *own, *lp;
+    int32_t k, engine_greedy;
+};
+// the step's row arrays from the slots' state (st: the StepState of the selection stage; block_table [rows][max_pages]); an idle draft row
+// gets context 0 and a table row of scratch_page, like a released slot
+hipError_t launch_spec_expand(hipStream_t s, const SpecState& sp, const StepState& st, const int32_t* block_table, int max_pages, int rows, int scratch_page);
+// arg-max partials (as launch_argmax_step's first kernel) of the live draft rows [rows, rows * (k + 1)) of logits
+hipError_t launch_spec_argmax(hipStream_t s, const SpecState& sp, const float* logits, int V, int ld, int rows, float* pval, int32_t* pidx);
+// after the selection stage committed the first `rows` rows: per slot, while the row is not finished and draft j equals the token just
+// committed, commit the arg max of draft row j + 1 (commit_token: EOS, cap and output as in a sequential step); counts into sp.stats and
+// clears the slot's drafts
+hipError_t launch_spec_accept(hipStream_t s, const SpecState& sp, const StepState& st, int rows, const float* pval, const int32_t* pidx);
+// drafts[b * draft_stride + 0 .. n_draft[b]) = the continuation of the longest suffix n-gram (min_n .. max_n) of out_ids[b * out_stride +
+// 0 .. out_lens[b]) that occurred before, at most k ids (the rule: include/dots_ocr_hip.h).  Rows that sel masks out, finished rows, rows
+// with own[b] != 0 or lp[b] >= 0, and every row while engine_greedy == 0 draft nothing (finished / sel / own / lp may be nullptr).
+hipError_t launch_ngram_draft(hipStream_t s, const int32_t* out_ids, const int32_t* out_lens, int out_stride, const int32_t* finished, const int32_t* sel,
+                              const int32_t* own, const int32_t* lp, int engine_greedy, int B, int k, int min_n, int max_n, int32_t* drafts,
+                              int draft_stride, int32_t* n_draft);
+// drafts[row][0 .. n) = ids_host, n_draft[row] = n, in stream order (the ids travel as a kernel argument)
+hipError_t launch_spec_set_drafts(hipStream_t s, int32_t* drafts, int32_t* n_draft, int row, const int32_t* ids_host, int n);
 
 // ---- logprobs.hip: log-probabilities of the raw logits of every selected row
 #ifndef DOTS_MAX_TOP_LOGPROBS

@@ -1,0 +1,207 @@
+// N-gram speculative decoding of greedy rows: the three kernels a speculating decode step adds around the unchanged layer
+// loop, and the stream-ordered writer of a row's drafts.
+//
+// A slot b that holds d drafts occupies 1 + d rows of one step.  The step runs over R = rows x (k + 1) rows, draft-major: row
+// r = j * rows + b carries token j of (last committed token, draft 1 .. k) of slot b at context ctx + j, and all the rows of a slot name
+// the slot's KV pages.  dec_qkv appends the K/V of every row in a launch of its own before the attention launch, so row j attends over
+// what rows 0 .. j - 1 appended and — every decode kernel being row-independent and batch-invariant bit for bit — its logits are those of
+// the sequential step at that position.  The first `rows` rows are the rows of an unspeculated step: the existing selection stage
+// commits their tokens with its present arguments.
+//
+//   spec_expand_kernel   head of the step: tokens, context lengths and block-table rows of the R rows from the slots' state and drafts
+//   spec_argmax_kernel   after the lm_head: the arg-max partials of the live draft rows (the merge rule of argmax_partial_kernel)
+//   spec_accept_kernel   after the selection stage: walks a slot's drafts and commits through commit_token while they hold
+//   ngram_draft_kernel   end of the step: the next step's drafts from the row's own output (prompt lookup without the prompt)
+//
+// Draft row (b, j >= 1) is LIVE iff slot b is selected, not finished, plain greedy (no parameters, rules, guide or n-gram rule of its own,
+// no logprobs, engine-wide arg max), holds at least j drafts and j < max_len[b] - out_lens[b]: a live row writes KV position ctx + j, and
+// the last condition is "the sequence may still reach that position", which is also what its pages cover (the host lowers max_len when
+// the pool runs dry).  Every other draft row idles like a released slot: context 0 on the scratch page.
+#include <climits>
+
+#include "kernels.h"
+#include "step_dev.h"
+
+namespace {
+
+constexpr int ND_THREADS = 256;
+
+// the drafts slot b verifies in this step, or -1 when the slot takes no step at all (free or finished)
+DEVI int spec_live_drafts(const SpecState& sp, const StepState& st, int b) {
+    if ((st.sel && !st.sel[b]) || st.finished[b]) return -1;
+    if (!sp.engine_greedy || (sp.own && sp.own[b]) || (sp.lp && sp.lp[b] >= 0)) return 0;
+    const int room = (st.max_len ? st.max_len[b] : st.cap) - st.out_lens[b] - 1;      // draft rows whose token could still be committed
+    return max(0, min(min(sp.n_draft[b], sp.k), room));
+}
+
+// grid (R = rows * (k + 1)), 64 threads
+__global__ __launch_bounds__(64) void spec_expand_kernel(SpecState sp, StepState st, const int32_t* __restrict__ block_table, int max_pages,
+                                                         int rows, int scratch_page) {
+    const int r = blockIdx.x, j = r / rows, b = r - j * rows;
+    const int nl = spec_live_drafts(sp, st, b);
+    const bool live = j == 0 || j <= nl;
+    const int32_t* __restrict__ src = block_table + (size_t)b * max_pages;
+    int32_t* __restrict__ dst = sp.block_table + (size_t)r * max_pages;
+    for (int p = threadIdx.x; p < max_pages; p += 64) dst[p] = live ? src[p] : scratch_page;
+    if (threadIdx.x == 0) {
+        sp.tokens[r] = j >= 1 && live ? sp.drafts[b * DOTS_MAX_SPEC_DRAFTS + j - 1] : st.cur_tokens[b];
+        sp.ctx_len[r] = j == 0 ? st.ctx_len[b] : live ? st.ctx_len[b] + j : 0;
+        if (j == 0) sp.n_live[b] = nl;
+    }
+}
+
+// grid (ARGMAX_CHUNKS, R - rows): the partials of draft row rows + blockIdx.y, as argmax_partial_kernel (decode.hip) leaves them
+__global__ __launch_bounds__(256) void spec_argmax_kernel(const float* __restrict__ logits, int V, int ld, int rows, const int32_t* __restrict__ n_live,
+                                                          float* __restrict__ pval, int32_t* __restrict__ pidx) {
+    __shared__ float sv[4];
+    __shared__ int si[4];
+    const int c = blockIdx.x, r = rows + blockIdx.y, j = r / rows, b = r - j * rows;
+    if (j > n_live[b]) return;                                        // an idle row: nobody reads its partials
+    const int per = (V + ARGMAX_CHUNKS - 1) / ARGMAX_CHUNKS;
+    const int lo = c * per, hi = min(V, lo + per);
+    const float* row = logits + (size_t)r * ld;
+    float best = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int i = lo + threadIdx.x; i < hi; i += 256) argmax_merge(best, bi, row[i], i);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) argmax_merge(best, bi, __shfl_xor(best, o, 64), __shfl_xor(bi, o, 64));
+    if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = best; si[threadIdx.x >> 6] = bi; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < 4; ++k) argmax_merge(best, bi, sv[k], si[k]);
+        pval[r * ARGMAX_CHUNKS + c] = best;
+        pidx[r * ARGMAX_CHUNKS + c] = bi;
+    }
+}
+
+// grid (rows), one wave.  Row 0's token is committed (the selection stage ran); draft j is right iff it equals the token committed before
+// it, and then the arg max of draft row j + 1 is the next token of the sequential run.
+__global__ __launch_bounds__(64) void spec_accept_kernel(SpecState sp, StepState st, int rows, const float* __restrict__ pval,
+                                                         const int32_t* __restrict__ pidx) {
+    __shared__ int32_t s_tok[DOTS_MAX_SPEC_DRAFTS];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int nl = sp.n_live[b];                                      // uniform
+    for (int j = 0; j < nl; ++j) {
+        const int r = (j + 1) * rows + b;
+        float best = pval[r * ARGMAX_CHUNKS + lane];
+        int bi = pidx[r * ARGMAX_CHUNKS + lane];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) argmax_merge(best, bi, __shfl_xor(best, o, 64), __shfl_xor(bi, o, 64));
+        if (lane == 0) s_tok[j] = bi;
+    }
+    __syncthreads();
+    if (lane != 0) return;
+    sp.n_draft[b] = 0;                                                // the drafts are spent, whatever became of them
+    if (nl < 0) return;
+    int acc = 0;
+    while (acc < nl && !st.finished[b] && sp.drafts[b * DOTS_MAX_SPEC_DRAFTS + acc] == st.cur_tokens[b]) {
+        commit_token(st, b, s_tok[acc]);
+        ++acc;
+    }
+    unsigned long long* mine = sp.stats + (size_t)b * 3;
+    mine[0] += 1; mine[1] += (unsigned long long)nl; mine[2] += (unsigned long long)acc;
+    unsigned long long* all = sp.stats + (size_t)DOTS_MAX_BATCH * 3;
+    atomicAdd(all + 0, 1ull); atomicAdd(all + 1, (unsigned long long)nl); atomicAdd(all + 2, (unsigned long long)acc);
+}
+
+// The drafting rule (include/dots_ocr_hip.h): for n from max_n down to min_n with n + 1 <= L, key = out[L - n .. L); among the matches
+// out[i .. i + n) == key with i + n < L the largest i with i + n + k <= L if there is one, else the smallest i; the draft is
+// out[i + n .. min(i + n + k, L)).  The first n with a match wins.
+// grid (B), ND_THREADS threads: the threads stride over i, each keeps (largest full, smallest any), one LDS reduction per n.
+__global__ __launch_bounds__(ND_THREADS) void ngram_draft_kernel(const int32_t* __restrict__ out_ids, const int32_t* __restrict__ out_lens, int out_stride,
+                                                                 const int32_t* __restrict__ finished, const int32_t* __restrict__ sel,
+                                                                 const int32_t* __restrict__ own, const int32_t* __restrict__ lp, int engine_greedy, int k,
+                                                                 int min_n, int max_n, int32_t* __restrict__ drafts, int draft_stride,
+                                                                 int32_t* __restrict__ n_draft) {
+    __shared__ int32_t s_suf[DOTS_MAX_NGRAM_SIZE];
+    __shared__ int s_full[ND_THREADS / 64], s_any[ND_THREADS / 64];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const bool plain = engine_greedy && !(own && own[b]) && !(lp && lp[b] >= 0);
+    if ((sel && !sel[b]) || (finished && finished[b]) || !plain) {    // uniform per workgroup
+        if (tid == 0) n_draft[b] = 0;
+        return;
+    }
+    const int L = min(max(out_lens[b], 0), out_stride);
+    const int32_t* __restrict__ out = out_ids + (size_t)b * out_stride;
+    const int n_top = min(max_n, L - 1);                              // the longest key with n + 1 <= L
+    if (tid < n_top) s_suf[tid] = out[L - n_top + tid];
+    __syncthreads();
+    for (int n = n_top; n >= min_n; --n) {
+        const int32_t* key = s_suf + (n_top - n);
+        int full = -1, any = INT_MAX;
+        for (int i = tid; i + n < L; i += ND_THREADS) {
+            bool hit = true;
+            for (int j = n - 1; j >= 0; --j)
+                if (out[i + j] != key[j]) { hit = false; break; }
+            if (!hit) continue;
+            any = min(any, i);
+            if (i + n + k <= L) full = max(full, i);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            full = max(full, __shfl_xor(full, o, 64));
+            any = min(any, __shfl_xor(any, o, 64));
+        }
+        if ((tid & 63) == 0) { s_full[tid >> 6] = full; s_any[tid >> 6] = any; }
+        __syncthreads();
+        for (int w = 0; w < ND_THREADS / 64; ++w) { full = max(full, s_full[w]); any = min(any, s_any[w]); }
+        __syncthreads();                                              // the partials are read: the next n may overwrite them
+        const int i = full >= 0 ? full : any;                         // uniform from here
+        if (i == INT_MAX) continue;
+        const int cnt = min(k, L - (i + n));
+        if (tid < cnt) drafts[(size_t)b * draft_stride + tid] = out[i + n + tid];
+        if (tid == 0) n_draft[b] = cnt;
+        return;
+    }
+    if (tid == 0) n_draft[b] = 0;
+}
+
+struct DraftIds { int32_t v[DOTS_MAX_SPEC_DRAFTS]; };
+__global__ void spec_set_drafts_kernel(int32_t* drafts, int32_t* n_draft, int row, DraftIds ids, int n) {
+    for (int j = 0; j < n; ++j) drafts[row * DOTS_MAX_SPEC_DRAFTS + j] = ids.v[j];
+    n_draft[row] = n;
+}
+
+bool spec_ok(const SpecState& sp, int rows) {
+    return sp.drafts && sp.n_draft && sp.n_live && sp.tokens && sp.ctx_len && sp.block_table && sp.stats && sp.k >= 1 && sp.k <= DOTS_MAX_SPEC_DRAFTS &&
+           rows >= 1 && rows * (sp.k + 1) <= DOTS_MAX_BATCH;
+}
+
+}  // namespace
+
+hipError_t launch_spec_expand(hipStream_t s, const SpecState& sp, const StepState& st, const int32_t* block_table, int max_pages, int rows, int scratch_page) {
+    if (!spec_ok(sp, rows) || !block_table || max_pages < 1 || scratch_page < 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(spec_expand_kernel, dim3(rows * (sp.k + 1)), dim3(64), 0, s, sp, st, block_table, max_pages, rows, scratch_page);
+    return hipGetLastError();
+}
+
+hipError_t launch_spec_argmax(hipStream_t s, const SpecState& sp, const float* logits, int V, int ld, int rows, float* pval, int32_t* pidx) {
+    if (!spec_ok(sp, rows) || !logits || !pval || !pidx || V < 1 || ld < V) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(spec_argmax_kernel, dim3(ARGMAX_CHUNKS, rows * sp.k), dim3(256), 0, s, logits, V, ld, rows, (const int32_t*)sp.n_live, pval, pidx);
+    return hipGetLastError();
+}
+
+hipError_t launch_spec_accept(hipStream_t s, const SpecState& sp, const StepState& st, int rows, const float* pval, const int32_t* pidx) {
+    if (!spec_ok(sp, rows) || !pval || !pidx) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(spec_accept_kernel, dim3(rows), dim3(64), 0, s, sp, st, rows, pval, pidx);
+    return hipGetLastError();
+}
+
+hipError_t launch_ngram_draft(hipStream_t s, const int32_t* out_ids, const int32_t* out_lens, int out_stride, const int32_t* finished, const int32_t* sel,
+                              const int32_t* own, const int32_t* lp, int engine_greedy, int B, int k, int min_n, int max_n, int32_t* drafts,
+                              int draft_stride, int32_t* n_draft) {
+    if (!out_ids || !out_lens || !drafts || !n_draft || out_stride < 1 || B < 1 || B > DOTS_MAX_BATCH || k < 1 || k > DOTS_MAX_SPEC_DRAFTS ||
+        draft_stride < k || min_n < 1 || max_n < min_n || max_n > DOTS_MAX_NGRAM_SIZE)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(ngram_draft_kernel, dim3(B), dim3(ND_THREADS), 0, s, out_ids, out_lens, out_stride, finished, sel, own, lp, engine_greedy, k, min_n,
+                       max_n, drafts, draft_stride, n_draft);
+    return hipGetLastError();
+}
+
+hipError_t launch_spec_set_drafts(hipStream_t s, int32_t* drafts, int32_t* n_draft, int row, const int32_t* ids_host, int n) {
+    if (!drafts || !n_draft || row < 0 || row >= DOTS_MAX_BATCH || n < 0 || n > DOTS_MAX_SPEC_DRAFTS || (n && !ids_host)) return hipErrorInvalidValue;
+    DraftIds ids{};
+    for (int j = 0; j < n; ++j) ids.v[j] = ids_host[j];
+    hipLaunchKernelGGL(spec_set_drafts_kernel, dim3(1), dim3(1), 0, s, drafts, n_draft, row, ids, n);
+    return hipGetLastError();
+}

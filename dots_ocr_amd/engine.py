@@ -377,6 +377,10 @@ def _prototypes(lib):
         "dots_op_select_tokens_ngram": (i32, [vp, vp, i32, i32, P(CDotsSamplingParams), P(CDotsLogitRules), P(CDotsNgramRule), vp, vp, i32, vp, vp]),
         "dots_bench_select_tokens_ngram": (i32, [vp, vp, i32, i32, P(CDotsSamplingParams), P(CDotsLogitRules), P(CDotsNgramRule), vp, vp, i32, vp, i32,
                                                  P(f32)]),
+        "dots_set_speculation": (i32, [vp, i32, i32, i32]),
+        "dots_set_row_drafts": (i32, [vp, i32, P(i32), i32]),
+        "dots_spec_stats": (i32, [vp, i32, P(i64), P(i64), P(i64)]),
+        "dots_op_ngram_draft": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]),
         "dots_set_row_logprobs": (i32, [vp, i32, i32]),
         "dots_row_logprobs": (i32, [vp, i32, i32, i32, P(f32), P(i32), P(f32), P(i32)]),
         "dots_op_logprobs": (i32, [vp, vp, i32, i32, i32, P(i32), vp, vp, vp, vp]),
@@ -408,7 +412,38 @@ EXPORTED_SYMBOLS = [
     "dots_set_token_bytes", "dots_guide_create", "dots_guide_destroy", "dots_set_row_guide", "dots_row_guide_state",
     "dots_op_select_tokens_guided", "dots_bench_select_tokens_guided",
     "dots_set_row_ngram", "dots_op_select_tokens_ngram", "dots_bench_select_tokens_ngram",
+    "dots_set_speculation", "dots_set_row_drafts", "dots_spec_stats", "dots_op_ngram_draft",
 ]
+
+MAX_SPEC_DRAFTS = 15                         # DOTS_MAX_SPEC_DRAFTS: drafts per slot and step
+MAX_NGRAM_SIZE = 64                          # DOTS_MAX_NGRAM_SIZE: longest n-gram the drafter looks up
+
+
+def ngram_draft(history: Sequence[int], k: int, min_n: int = 2, max_n: int = 4) -> list:
+    """The drafting rule of the speculative step (include/dots_ocr_hip.h), stated on the host: what ngram_draft_kernel must
+    produce.  history = the tokens a row has generated, out[0 .. L).  For n from max_n down to min_n with n + 1 <= L the key is the
+    suffix out[L - n .. L); among the matches out[i .. i + n) == key with i + n < L the largest i with a full continuation
+    (i + n + k <= L) wins, else the smallest i; the draft is out[i + n .. min(i + n + k, L)).  The first n with a match wins."""
+    out = [int(t) for t in history]
+    L = len(out)
+    if k < 1 or min_n < 1 or max_n < min_n:
+        raise ValueError("ngram_draft needs k >= 1 and 1 <= min_n <= max_n")
+    for n in range(max_n, min_n - 1, -1):
+        if n + 1 > L:
+            continue
+        key = out[L - n:]
+        hits = [i for i in range(L - n) if out[i:i + n] == key]
+        if not hits:
+            continue
+        full = [i for i in hits if i + n + k <= L]
+        i = max(full) if full else min(hits)
+        return out[i + n:min(i + n + k, L)]
+    return []
+
+
+def spec_usable_slots(max_batch: int, k: int) -> int:
+    """slots a speculating engine can fill: a slot takes k + 1 rows of a step"""
+    return int(max_batch) // (int(k) + 1)
 
 MAX_TOP_LOGPROBS = 20                        # DOTS_MAX_TOP_LOGPROBS: top entries kept per position
 
@@ -821,6 +856,53 @@ class Engine:
         self._ck(self.lib.dots_bench_select_tokens_ngram(self.h, logits, int(B), int(V), arr, rarr, narr, hist, hist_lens, int(hist_stride), n_prompt,
                                                          int(iters), C.byref(ms)), "dots_bench_select_tokens_ngram")
         return float(ms.value)
+
+    # ------------------------------------------------------------------ n-gram speculative decoding
+    def set_speculation(self, k: int, min_n: int = 2, max_n: int = 4):
+        """k drafts per slot and decode step for the plain greedy rows of the continuous path (0 = off, the default); the built-in drafter
+        continues the row's longest repeated suffix n-gram, min_n <= n <= max_n (max_n = 0: no drafter, set_row_drafts only).  Tokens are
+        exactly those of the unspeculated engine.  Only while no slot is occupied; the usable slots become usable_slots.  generate()
+        (the static batch) ignores it."""
+        k = int(k)
+        if not 0 <= k <= MAX_SPEC_DRAFTS:
+            raise ValueError(f"k must be in [0, {MAX_SPEC_DRAFTS}], got {k!r}")
+        self._ck(self.lib.dots_set_speculation(self.h, k, int(min_n), int(max_n)), "dots_set_speculation")
+        self.spec_k = k
+
+    @property
+    def usable_slots(self) -> int:
+        """slots slots_prefill accepts: max_batch, or max_batch // (k + 1) while speculating"""
+        return spec_usable_slots(self.max_batch, getattr(self, "spec_k", 0))
+
+    def set_row_drafts(self, row: int, ids: Sequence[int]):
+        """The drafts slot `row` verifies in its next step (at most k), replacing what the drafter left; spent by that step."""
+        a = np.ascontiguousarray(list(ids), dtype=np.int32)
+        self._ck(self.lib.dots_set_row_drafts(self.h, int(row), _i32p(a) if a.size else None, int(a.size)), "dots_set_row_drafts")
+
+    def spec_stats(self, row: int = -1) -> dict:
+        """{"steps", "drafted", "accepted"} of slot `row` since its prefill, or (row = -1) of the engine since set_speculation"""
+        st, dr, ac = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._ck(self.lib.dots_spec_stats(self.h, int(row), C.byref(st), C.byref(dr), C.byref(ac)), "dots_spec_stats")
+        return {"steps": int(st.value), "drafted": int(dr.value), "accepted": int(ac.value)}
+
+    def ngram_draft_op(self, histories: Sequence[Sequence[int]], k: int, min_n: int = 2, max_n: int = 4) -> list:
+        """ngram_draft_kernel alone (dots_op_ngram_draft): one launch over the rows of `histories`, -> one draft list per row."""
+        B = len(histories)
+        stride = max(1, max(len(h) for h in histories))
+        hist = np.zeros((B, stride), np.int32)
+        for b, h in enumerate(histories):
+            hist[b, :len(h)] = np.asarray(h, np.int32)
+        lens = np.asarray([len(h) for h in histories], np.int32)
+        d_hist, d_lens = self.to_device(hist), self.to_device(lens)
+        d_out, d_n = self.to_device(np.full((B, int(k)), -1, np.int32)), self.to_device(np.full((B,), -1, np.int32))
+        try:
+            self._ck(self.lib.dots_op_ngram_draft(self.h, C.c_void_p(d_hist), C.c_void_p(d_lens), stride, B, int(k), int(min_n), int(max_n),
+                                                  C.c_void_p(d_out), C.c_void_p(d_n)), "dots_op_ngram_draft")
+            out, n = self.to_host(d_out, (B, int(k)), np.int32), self.to_host(d_n, (B,), np.int32)
+        finally:
+            for ptr in (d_hist, d_lens, d_out, d_n):
+                self.dev_free(ptr)
+        return [out[b, :int(n[b])].tolist() for b in range(B)]
 
     def set_row_logprobs(self, row: int, top_n: Optional[int]):
         """Row `row` (a slot, or sequence `row` of a static batch) returns log-probabilities of the raw logits for every token selected

@@ -134,7 +134,8 @@ class DotsOcrHipForCausalLM:
                  presence_penalty: Optional[float] = None, logit_bias=None, allowed_token_ids=None, min_tokens: int = 0,
                  stop_token_ids=None, ignore_eos: bool = False, guided_regex=None, guided_choice=None, guided_json=None,
                  guided_whitespace_pattern=None, no_repeat_ngram_size: Optional[int] = None, no_repeat_ngram_window: Optional[int] = None,
-                 no_repeat_ngram_whitelist=None, **_):
+                 no_repeat_ngram_whitelist=None, speculative_ngram: Optional[int] = None, prompt_lookup_min: int = 2, prompt_lookup_max: int = 4,
+                 **_):
         """HF-shaped generate.  do_sample / temperature / top_p default to the checkpoint's generation_config.json (greedy when it
         is absent); with sampling on, tokens are drawn on the GPU from softmax(logits / temperature) restricted to the top_p
         nucleus, reproducibly from `seed`.  Returns LongTensor
@@ -159,7 +160,13 @@ class DotsOcrHipForCausalLM:
 
         no_repeat_ngram_size (n >= 1; None or 0 = off) with no_repeat_ngram_window (0 / None = the whole output) and
         no_repeat_ngram_whitelist (token ids never banned) give every sequence the same NgramRule (Engine.set_row_ngram): a
-        sequence never completes an n-gram its own OUTPUT already holds.  Unlike HF generate, the prompt is not part of the history."""
+        sequence never completes an n-gram its own OUTPUT already holds.  Unlike HF generate, the prompt is not part of the history.
+
+        speculative_ngram (k >= 1; None or 0 = off) with prompt_lookup_min / prompt_lookup_max (vLLM's speculative_config names) runs the
+        call with n-gram speculative decoding (Engine.set_speculation): it takes the continuous path, where a greedy
+        sequence verifies up to k drafted tokens per decode step, max_batch // (k + 1) sequences at a time.  The tokens are exactly
+        those of the call without it; sampled or rule-carrying sequences simply run unspeculated.  The engine is left with speculation
+        off."""
         import dataclasses
         import torch
         t_eff, p_eff = resolve_sampling(self.generation_config, do_sample, temperature, top_p)
@@ -211,10 +218,24 @@ class DotsOcrHipForCausalLM:
                     return dataclasses.replace(base, seed=int(seed) + b)
         elif no_repeat_ngram_window or no_repeat_ngram_whitelist:
             raise ValueError("no_repeat_ngram_window / no_repeat_ngram_whitelist need no_repeat_ngram_size")
+        spec_k = int(speculative_ngram or 0)
+        if spec_k:
+            if continuous is False:
+                raise ValueError("speculative_ngram runs on the continuous path: continuous=False cannot be combined with it")
+            continuous = True
+            self.engine.slots_reset()            # speculation changes only while no slot is occupied
+            self.engine.set_speculation(spec_k, int(prompt_lookup_min), int(prompt_lookup_max))
         try:
             return self._generate(input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens, eos_token_id, pad_token_id, continuous,
                                   row_sp, rules, guide, ngram)
         finally:
+            if spec_k:
+                try:
+                    self.engine.slots_reset()
+                    self.engine.set_speculation(0)
+                except Exception as e:               # the run's own error is the one to raise
+                    import warnings
+                    warnings.warn(f"speculation could not be switched off: {e}")
             if guide is not None:
                 try:
                     self.engine.destroy_guide(guide)

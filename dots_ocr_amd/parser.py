@@ -34,8 +34,12 @@ class DotsOCRParser:
                  max_completion_tokens=16384, num_thread=64, dpi=200, output_dir="./output", min_pixels=None,
                  max_pixels=None, use_hf=False, model_path="./weights/DotsOCR", model=None, processor=None,
                  hf_max_new_tokens=24000, guided=False, no_repeat_ngram_size=None, no_repeat_ngram_window=None,
-                 no_repeat_ngram_whitelist=None):
+                 no_repeat_ngram_whitelist=None, speculative_ngram=None, prompt_lookup_min=2, prompt_lookup_max=4):
         self.dpi = dpi
+        # n-gram speculative decoding, opt-in: the in-process model generates with it (same tokens, fewer decode steps).  A
+        # server speculates by its own --speculative-ngram flag, as vLLM does: requests carry nothing.
+        self.speculative_ngram = None if not speculative_ngram else int(speculative_ngram)
+        self.prompt_lookup_min, self.prompt_lookup_max = int(prompt_lookup_min), int(prompt_lookup_max)
         # no-repeat n-gram blocking, opt-in: the server request carries the three fields, the in-process model generates
         # with them.  With the default None the request and the call are exactly what they were.
         self.no_repeat_ngram_size = no_repeat_ngram_size
@@ -94,6 +98,8 @@ class DotsOCRParser:
     def _inference_batch_with_hf(self, images, prompts) -> List[str]:
         inputs = self._build_inputs(images, prompts)
         kw = self._ngram_fields()
+        if self.speculative_ngram:
+            kw.update(speculative_ngram=self.speculative_ngram, prompt_lookup_min=self.prompt_lookup_min, prompt_lookup_max=self.prompt_lookup_max)
         if self._guided_layout(prompts):
             from .guided import layout_schema
             if getattr(self.model.engine, "token_bytes", None) is None:

@@ -69,7 +69,9 @@ class ContinuousBatcher:
         self.admit_group = None if admit_group is None else max(1, int(admit_group))
         self._ahead: List[Tuple[int, Request]] = []             # requests whose tower has been prefetched, in packed order
         self._ahead_keep = None                                  # their (device) pixels stay alive until the rows are taken
-        self.n_slots = int(engine.max_batch)
+        # a speculating engine (Engine.set_speculation) fills max_batch // (k + 1) slots: a slot takes up to k + 1 rows of a
+        # step.  A chunk of c steps may then finish a row before c tokens; nothing else changes, the lengths come from the poll
+        self.n_slots = int(getattr(engine, "usable_slots", engine.max_batch))
         self.max_patches = int(engine.max_patches)
         self.max_prefill_tokens = int(engine.max_prefill_tokens)
         self.max_seq_len = int(engine.max_seq_len)

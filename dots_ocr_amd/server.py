@@ -637,7 +637,7 @@ def create_app(model, processor, model_name: str = "model", max_batch: int = 8, 
     return app
 
 
-def main(argv: Optional[List[str]] = None):
+def build_arg_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="OpenAI-compatible server for the dots.ocr MI355X engine")
     ap.add_argument("--model-path", default="./weights/DotsOCR")
     ap.add_argument("--random-weights", action="store_true", help="seeded random weights (no checkpoint): plumbing tests only")
@@ -656,7 +656,40 @@ def main(argv: Optional[List[str]] = None):
                          "(default 2 up to 8 slots, min(8, slots / 2) above; 0 = off)")
     ap.add_argument("--allow-remote-images", action="store_true", help="let requests name http(s) image URLs (off: data: URLs only)")
     ap.add_argument("--allow-local-images", action="store_true", help="let requests name image paths on the server's file system")
+    ap.add_argument("--speculative-ngram", type=int, default=0, metavar="K",
+                    help="n-gram speculative decoding (vLLM's speculative_config method \"ngram\"): greedy requests verify up to K drafted tokens "
+                         "per decode step, exactly the same tokens; the server then runs max_batch // (K + 1) requests at a time.  Sampled or "
+                         "rule-carrying requests run unspeculated.  0 = off (default)")
+    ap.add_argument("--prompt-lookup-min", type=int, default=2, metavar="N", help="shortest n-gram the drafter looks up (with --speculative-ngram)")
+    ap.add_argument("--prompt-lookup-max", type=int, default=4, metavar="N", help="longest n-gram the drafter looks up (with --speculative-ngram)")
+    return ap
+
+
+def speculation_args(a) -> Optional[tuple]:
+    """(k, min_n, max_n) of the parsed flags, or None when speculation is off.  ValueError on values the engine would refuse."""
+    from .engine import MAX_NGRAM_SIZE, MAX_SPEC_DRAFTS, spec_usable_slots
+    k = int(a.speculative_ngram)
+    if k == 0:
+        return None
+    if not 1 <= k <= MAX_SPEC_DRAFTS:
+        raise ValueError(f"--speculative-ngram must be in [0, {MAX_SPEC_DRAFTS}], got {k}")
+    lo, hi = int(a.prompt_lookup_min), int(a.prompt_lookup_max)
+    if not 1 <= lo <= hi <= MAX_NGRAM_SIZE:
+        raise ValueError(f"need 1 <= --prompt-lookup-min <= --prompt-lookup-max <= {MAX_NGRAM_SIZE}, got {lo} and {hi}")
+    if a.static_batching:
+        raise ValueError("--speculative-ngram needs continuous batching: it cannot be combined with --static-batching")
+    if spec_usable_slots(a.max_batch, k) < 1:
+        raise ValueError(f"--speculative-ngram {k} needs --max-batch >= {k + 1}: a request takes {k + 1} rows of a decode step")
+    return k, lo, hi
+
+
+def main(argv: Optional[List[str]] = None):
+    ap = build_arg_parser()
     a = ap.parse_args(argv)
+    try:
+        spec = speculation_args(a)
+    except ValueError as e:
+        ap.error(str(e))
     import uvicorn
     from .modeling import DotsOcrHipForCausalLM
     from .processing import DotsOcrProcessor
@@ -667,6 +700,8 @@ def main(argv: Optional[List[str]] = None):
         model = DotsOcrHipForCausalLM.from_pretrained(a.model_path, device=a.device, max_batch=a.max_batch, fp8_weights=a.fp8_weights,
                                                       kv_cache_dtype=a.kv_cache_dtype)
         proc = DotsOcrProcessor.from_pretrained(a.model_path, engine=model.engine)
+    if spec is not None:                             # server-wide, before any slot is occupied; /health and the requests are unchanged
+        model.engine.set_speculation(*spec)
     uvicorn.run(create_app(model, proc, a.served_model_name, a.max_batch, continuous=not a.static_batching,
                            allow_remote_images=a.allow_remote_images, allow_local_images=a.allow_local_images, look_ahead=a.look_ahead),
                 host=a.host, port=a.port)

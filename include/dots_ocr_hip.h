@@ -293,6 +293,39 @@ typedef struct DotsNgramRule {
 } DotsNgramRule;
 int dots_set_row_ngram(DotsEngine* e, int row, const DotsNgramRule* r);
 
+/* ---- N-gram speculative decoding of greedy rows: opt-in, engine-wide, slot mode only.  With k drafts a slot occupies up to
+ * k + 1 rows of one decode step: row j carries token j of (last committed token, draft 1 .. k) at context ctx + j on the slot's own KV
+ * pages, and sees the K/V rows 0 .. j - 1 appended in the step's qkv launch.  Every decode kernel is row-independent and batch-invariant
+ * bit for bit, so row j's logits are those of the sequential step at that position; the step commits row 0's token as an unspeculated
+ * step does and then, while draft j equals the token just committed, the arg max of row j + 1 — through the same bookkeeping (EOS ids,
+ * generation cap, output, context).  The tokens of a greedy row are therefore EXACTLY those of the unspeculated engine; a step commits
+ * 1 .. k + 1 of them, so dots_slots_decode(n) may finish a row before n steps have run.  The K/V of rejected drafts stay where they were
+ * written; the next step overwrites those positions.
+ *
+ * Only plain greedy rows speculate: a row with DotsSamplingParams, DotsLogitRules, a guide, an n-gram rule or logprobs of its own, and
+ * every row while dots_set_sampling has a temperature > 0, verifies no draft and decodes inside the speculating step exactly as before.
+ * dots_generate / dots_decode_step (the closed static batch) ignore the setting.
+ *
+ * The built-in drafter looks the row's last tokens up in the row's OWN output (the prompt is not searched: image pads and a short
+ * instruction).  With out[0 .. L) the tokens generated so far, for n from max_n down to min_n with n + 1 <= L: key = out[L - n .. L);
+ * among the i with out[i .. i + n) == key and i + n < L take the largest i with i + n + k <= L if one exists, else the smallest i; the
+ * draft is out[i + n .. min(i + n + k, L)).  The first n that has a match wins; no match = no drafts.
+ *
+ * dots_set_speculation  k drafts per slot and step: 0 = off (the default: a step launches exactly the kernels it launched before), 1 ..
+ *                       DOTS_MAX_SPEC_DRAFTS.  1 <= min_n <= max_n <= DOTS_MAX_NGRAM_SIZE, or max_n = 0: no built-in drafter, the host
+ *                       drafts (dots_set_row_drafts).  With k > 0 the usable slots are [0, max_batch / (k + 1)): dots_slots_prefill into a
+ *                       higher slot returns DOTS_E_CAPACITY.  Allowed only while no slot is occupied (DOTS_E_STATE); zeroes the counters
+ *                       and drops the captured steps.  DOTS_E_CAPACITY when max_batch < k + 1.
+ * dots_set_row_drafts   the n <= k drafts slot `row` verifies in its NEXT step, replacing what the drafter left (stream ordered; they are
+ *                       spent by that step).  DOTS_E_INVALID: n > k or an id outside [0, vocab); DOTS_E_STATE: the slot is not occupied.
+ *                       A row that does not speculate ignores them.
+ * dots_spec_stats       speculating steps the row took, draft tokens it verified (after the generation cap cut them) and draft tokens it
+ *                       committed, since the row's prefill; row = -1: the engine's totals since the last dots_set_speculation. */
+#define DOTS_MAX_SPEC_DRAFTS 15
+int dots_set_speculation(DotsEngine* e, int k, int min_n, int max_n);
+int dots_set_row_drafts(DotsEngine* e, int row, const int32_t* ids_host, int n);
+int dots_spec_stats(DotsEngine* e, int row, int64_t* steps, int64_t* drafted, int64_t* accepted);
+
 /* Log-probabilities: log_softmax of the raw fp32 logits of the step (before penalties, temperature, top-k and top-p:
  * the values dots_get_logits returns), for every token a row commits, the prefill's first token included.  The top entries are
  * ordered by value descending, then index ascending.  lse comes from per-chunk (max, sum) pairs merged in a fixed chunk order, so a
@@ -507,6 +540,10 @@ int dots_op_select_tokens_ngram(DotsEngine* e, const float* logits_dev, int B, i
 int dots_bench_select_tokens_ngram(DotsEngine* e, const float* logits_dev, int B, int V, const DotsSamplingParams* params_host, const DotsLogitRules* rules_host,
                                    const DotsNgramRule* ngram_host, const int32_t* hist_dev, const int32_t* hist_lens_dev, int hist_stride,
                                    const int32_t* n_prompt_dev, int iters, float* ms_out);
+/* The drafter alone on caller-supplied histories: hist int32 [B][hist_stride] holds row b's generated tokens hist[b][0 .. hist_lens[b]);
+ * writes drafts int32 [B][k] and n_drafts int32 [B] by the rule above (every row drafts: no finished / selection state is read). */
+int dots_op_ngram_draft(DotsEngine* e, const int32_t* hist_dev, const int32_t* hist_lens_dev, int hist_stride, int B, int k, int min_n, int max_n,
+                        int32_t* drafts_dev, int32_t* n_drafts_dev);
 /* The log-probability stage over caller logits: logits_dev fp32 [B, ld] (V <= ld), top_n_host [B] (-1 = row skipped, 0..20),
  * chosen_dev int32 [B] the chosen ids; writes tok_lp_dev float [B], top_ids_dev int32 [B][20], top_lp_dev float [B][20] of every row
  * with top_n >= 0 (entries beyond top_n: -1 / NaN).  The same two kernels the engine runs. */

@@ -1,0 +1,131 @@
+#!/usr/bin/env python3
+"""What a speculating decode step costs and what it has to accept to pay (profiles/spec_ngram.txt).
+
+    python tools/spec_bench.py [--slots 1 8] [--k 0 1 3 7] [--steps 64] [--repeats 3] [--prompt 512]
+
+Full-size language model with seeded random weights (the vision tower, which no text-only prompt touches, is cut to one block so that the
+weights are made quickly), one engine of 64 rows.  Per slot count: the reference tokens come from an unspeculated run; then for every
+k and every acceptance level the same sequences are decoded again, one step per slots_decode call, with drafts planted through
+Engine.set_row_drafts before every step:
+
+    acceptance 0     k drafts per slot, all wrong: every draft row is live (it computes and writes K/V) and none is accepted
+    acceptance half  the first ceil(k / 2) drafts are the true continuation, the rest wrong
+    acceptance full  all k are the true continuation
+
+Every run is checked to reproduce the reference tokens exactly.  Reported per run (median of `repeats`, each `steps` steps, wall clock
+around the loop with a final synchronise, so the per-step host work of planting the drafts is inside — it is inside for k = 0 too, which
+plants nothing but pays the same one-step-per-call loop):
+
+    ms_per_step, tokens_per_step, tokens_per_s per slot count, k and acceptance
+    break_even = cost(k) / cost(0) - 1 from the acceptance-0 rows: the accepted tokens per step above which speculating is faster
+
+One JSON line per measurement on stdout, then a table.
+"""
+import argparse
+import dataclasses
+import json
+import statistics
+import sys
+import time
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+import numpy as np  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--slots", type=int, nargs="+", default=[1, 8])
+    ap.add_argument("--k", type=int, nargs="+", default=[0, 1, 3, 7])
+    ap.add_argument("--steps", type=int, default=64)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--prompt", type=int, default=512)
+    ap.add_argument("--tiny", action="store_true", help="the small-dims model instead of the full-size one (a plumbing check, not a measurement)")
+    a = ap.parse_args()
+    from dots_ocr_amd.config import DotsConfig
+    from dots_ocr_amd.engine import Engine
+    from dots_ocr_amd.weights import random_state_dict
+    if a.tiny:
+        cfg = DotsConfig.tiny(layers=3, v_layers=1)
+    else:
+        cfg = DotsConfig()
+        cfg = dataclasses.replace(cfg, vision=dataclasses.replace(cfg.vision, num_hidden_layers=1))
+    k_max = max(a.k)
+    n_tok = 2 + a.steps * (k_max + 1)                                # tokens a row may reach: the prefill's, the warm-up step's, then k + 1 per step
+    seq = a.prompt + n_tok + 64
+    eng = Engine(cfg, max_batch=64, max_seq_len=seq, max_patches=256, max_prefill_tokens=max(a.slots) * a.prompt)
+    eng.load_state_dict(random_state_dict(cfg, seed=0, threads=16))
+    eng.set_eos([])
+    rng = np.random.default_rng(0)
+    prompts = [rng.integers(0, cfg.vocab_size - 4096, a.prompt).astype(np.int32) for _ in range(max(a.slots))]
+    results = {}
+    for S in a.slots:
+        if any(S * (k + 1) > 64 for k in a.k):
+            raise SystemExit(f"{S} slots x (k + 1) rows exceed the 64 rows of a step")
+        slots = list(range(S))
+
+        def run(k, true_drafts, T=None):
+            """`steps` steps with k drafts per slot of which the first true_drafts are right: (seconds, tokens committed, token lists)"""
+            eng.slots_reset()
+            eng.set_speculation(k, 2, 0)
+            eng.slots_prefill(slots, np.concatenate(prompts[:S]), [a.prompt] * S, [n_tok] * S)
+            eng.slots_decode(1)                                       # the captured step exists before the clock starts
+            eng.synchronize()
+            _, lens = eng.slots_poll()
+            start = [int(lens[b]) for b in slots]
+            pos = list(start)
+            t0 = time.perf_counter()
+            for _ in range(a.steps):
+                for b in slots:
+                    if k:
+                        d = [int(t) for t in T[b][pos[b]:pos[b] + k]]
+                        d = d[:true_drafts] + [(t + 1) % (cfg.vocab_size - 4096) for t in d[true_drafts:]]
+                        eng.set_row_drafts(b, d)
+                    pos[b] += 1 + (min(true_drafts, k) if k else 0)
+                eng.slots_decode(1)
+            eng.synchronize()
+            dt = time.perf_counter() - t0
+            _, lens = eng.slots_poll()
+            toks = [eng.slot_read(b, int(lens[b])).tolist() for b in slots]
+            assert [int(lens[b]) for b in slots] == pos, (k, true_drafts, [int(lens[b]) for b in slots], pos)
+            if T is not None:
+                assert all(toks[b] == T[b][:len(toks[b])] for b in slots), "a speculating run left the reference tokens"
+            for b in slots:
+                eng.slot_release(b)
+            return dt, sum(pos) - sum(start), toks
+
+        # reference tokens: unspeculated, as many as the fastest run will need
+        eng.slots_reset()
+        eng.set_speculation(0)
+        eng.slots_prefill(slots, np.concatenate(prompts[:S]), [a.prompt] * S, [n_tok] * S)
+        for _ in range(-(-n_tok // 16)):
+            eng.slots_decode(16)
+        _, lens = eng.slots_poll()
+        T = [eng.slot_read(b, int(lens[b])).tolist() for b in slots]
+        assert all(len(t) == n_tok for t in T)
+        for b in slots:
+            eng.slot_release(b)
+        for k in a.k:
+            levels = [("-", 0)] if k == 0 else [("0", 0), ("half", -(-k // 2)), ("full", k)]
+            for name, true_drafts in levels:
+                runs = [run(k, true_drafts, T) for _ in range(a.repeats)]
+                dt = statistics.median(r[0] for r in runs)
+                rec = {"slots": S, "k": k, "rows": S * (k + 1), "acceptance": name, "steps": a.steps, "ms_per_step": round(dt / a.steps * 1e3, 4),
+                       "ms_per_step_min_max": [round(min(r[0] for r in runs) / a.steps * 1e3, 4), round(max(r[0] for r in runs) / a.steps * 1e3, 4)],
+                       "tokens_per_step": round(runs[0][1] / a.steps / S, 3), "tokens_per_s": round(runs[0][1] / dt, 1)}
+                results[(S, k, name)] = rec
+                print(json.dumps(rec), flush=True)
+    print()
+    print(f"{'slots':>5} {'k':>2} {'rows':>4} {'accept':>6} {'ms/step':>9} {'tok/step/slot':>13} {'tokens/s':>10} {'break-even accepted/step':>25}")
+    for (S, k, name), r in results.items():
+        base = results.get((S, 0, "-"))
+        be = ""
+        if k and name == "0" and base:
+            be = f"{r['ms_per_step'] / base['ms_per_step'] - 1:.3f}"
+        print(f"{S:>5} {k:>2} {r['rows']:>4} {name:>6} {r['ms_per_step']:>9.4f} {r['tokens_per_step']:>13.3f} {r['tokens_per_s']:>10.1f} {be:>25}")
+    eng.close()
+
+
+if __name__ == "__main__":
+    main()
