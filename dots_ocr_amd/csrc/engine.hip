@@ -185,6 +185,13 @@ struct DotsEngine {
     int n_pool_pages = 0;                  // allocatable pages; page n_pool_pages is the scratch page idle rows write to
     int kv_capped = 0;                     // sequences whose generation cap was lowered because the pool ran dry
     std::vector<int32_t> free_pages;       // LIFO free list
+    // holders of every page (0 = in the free list).  Only dots_slots_fork makes a count exceed 1: the children's block-table rows name the
+    // source's full prompt pages.  A page with more than one holder is never written
+    std::vector<int32_t> page_refs;
+    // dots_slots_fork: the slots the most recent dots_slots_prefill filled, in the order of its packed prompts (hp_last[i] = last packed
+    // token of fresh_slots[i]); emptied by whatever invalidates that prefill's workspace (p_src, d_logits): any decode step, any other prefill
+    std::vector<int> fresh_slots;
+    int32_t* fk_dev = nullptr;             // [3][DOTS_MAX_BATCH] int32: a fork's destination slots, their tail pages, and (first entry) L - 1
     std::vector<std::vector<int32_t>> slot_pages;
     bf16_t* pool = nullptr;                // [layers][n_pool_pages + 1][Hkv][2][8192] bf16, or e4m3 bytes (kv8; decode.hip header)
     size_t pool_layer_elems = 0;           // per layer, in bf16 units (an fp8 pool's layer is half as many)
@@ -649,6 +656,7 @@ int alloc_workspaces(DotsEngine* e) {
     CK(e->alloc(&e->d_sel_new, (size_t)DOTS_MAX_BATCH));
     CK(e->alloc(&e->d_max_len, (size_t)DOTS_MAX_BATCH));
     CK(e->alloc(&e->p_dst, (size_t)DOTS_MAX_BATCH));
+    CK(e->alloc(&e->fk_dev, (size_t)3 * DOTS_MAX_BATCH));
     CK(e->alloc(&e->am_idx, (size_t)mb * 64));
     CK(e->alloc(&e->am_val, (size_t)mb * 64));
     CK(e->alloc(&e->d_h, (size_t)mb * H));
@@ -678,6 +686,7 @@ int alloc_workspaces(DotsEngine* e) {
     e->hp_table.assign((size_t)mb * e->max_pages, e->n_pool_pages);
     e->slot_pages.assign(mb, {});
     e->free_pages.resize(e->n_pool_pages);
+    e->page_refs.assign(e->n_pool_pages, 0);
     for (int p = 0; p < e->n_pool_pages; ++p) e->free_pages[p] = e->n_pool_pages - 1 - p;      // pop_back hands out page 0 first
     CK(hipMemcpyAsync(e->block_table, e->hp_table.data(), e->hp_table.size() * 4, hipMemcpyHostToDevice, e->stream));
     for (auto& ev : e->ev) CK(hipEventCreate(&ev));
@@ -695,9 +704,11 @@ hipError_t upload_table_row(DotsEngine* e, int slot) {
     return hipMemcpyAsync(e->block_table + (size_t)slot * e->max_pages, e->hp_table.data() + (size_t)slot * e->max_pages, (size_t)e->max_pages * 4,
                           hipMemcpyHostToDevice, e->stream);
 }
+// the slot lets go of every page its row names; a page goes back to the free list when its last holder lets go (dots_slots_fork shares pages)
 void release_pages(DotsEngine* e, int slot) {
     auto& mine = e->slot_pages[slot];
-    for (auto it = mine.rbegin(); it != mine.rend(); ++it) e->free_pages.push_back(*it);
+    for (auto it = mine.rbegin(); it != mine.rend(); ++it)
+        if (--e->page_refs[*it] == 0) e->free_pages.push_back(*it);
     mine.clear();
     std::fill(e->hp_table.begin() + (size_t)slot * e->max_pages, e->hp_table.begin() + (size_t)(slot + 1) * e->max_pages, e->n_pool_pages);
 }
@@ -709,6 +720,7 @@ bool reserve_pages(DotsEngine* e, int slot, int tokens) {
     for (int p = 0; p < need; ++p) {
         mine.push_back(e->free_pages.back());
         e->free_pages.pop_back();
+        e->page_refs[mine.back()] = 1;
         e->hp_table[(size_t)slot * e->max_pages + p] = mine.back();
     }
     return true;
@@ -722,6 +734,7 @@ int grow_pages(DotsEngine* e, int slot, int tokens, bool* changed) {
     while ((int)mine.size() < need && !e->free_pages.empty()) {
         e->hp_table[(size_t)slot * e->max_pages + mine.size()] = e->free_pages.back();
         mine.push_back(e->free_pages.back());
+        e->page_refs[mine.back()] = 1;
         e->free_pages.pop_back();
         *changed = true;
     }
@@ -1305,6 +1318,7 @@ int prefill(DotsEngine* e, const int32_t* ids, const int32_t* lens, int B, const
         }
     }
     if (T > e->TP) return e->fail(DOTS_E_CAPACITY, "packed prompt tokens %lld > max_prefill_tokens %lld", (long long)T, (long long)e->TP);
+    e->fresh_slots.clear();                                 // the workspace of the previous prefill is about to be overwritten (dots_slots_fork)
     e->hp_pos.resize(T); e->hp_src.resize(T); e->hp_last.assign(DOTS_MAX_BATCH, 0);
     int64_t t = 0, vis_used = 0;
     for (int b = 0; b < B; ++b) {
@@ -1424,6 +1438,7 @@ int prefill(DotsEngine* e, const int32_t* ids, const int32_t* lens, int B, const
         }
         e->sel_dirty = true;
         e->B = 0;                                          // the static-batch entry points need a static prefill first
+        e->fresh_slots = S;                                // these sequences may be forked until the next step (dots_slots_fork)
     } else {
         e->B = B;
         e->h_prompt_lens = L;
@@ -1762,6 +1777,7 @@ int dots_decode_step(DotsEngine* e) {
     int max_ctx = 0;
     for (int b = 0; b < e->B; ++b) max_ctx = std::max(max_ctx, e->h_prompt_lens[b] + e->steps_done + 1);
     if (max_ctx >= e->cfg.max_seq_len) return e->fail(DOTS_E_CAPACITY, "sequence reached max_seq_len");
+    e->fresh_slots.clear();
     RET(decode_step_launches(e, splits_for_ctx(e->cfg.max_seq_len)));
     e->steps_done += 1;
     return DOTS_OK;
@@ -1867,6 +1883,117 @@ int dots_slots_prefill(DotsEngine* e, const int32_t* slots, int n, const int32_t
     return prefill(e, input_ids, prompt_lens, n, slots, max_new_tokens);
 }
 
+// Parallel sampling: n free slots become copies of the freshly prefilled sequence in src_slot.  Everything is validated and
+// counted before anything changes; the children then share the source's full prompt pages (reference counts), get a copy of its tail page
+// and select their own first token from the source's last-position logits.
+int dots_slots_fork(DotsEngine* e, int src_slot, const int32_t* dst_slots, int n) {
+    if (!e) return DOTS_E_INVALID;
+    if (!e->finalized) return e->fail(DOTS_E_STATE, "weights not finalized");
+    if (!dst_slots || n < 1 || n >= DOTS_MAX_BATCH) return e->fail(DOTS_E_INVALID, "dots_slots_fork: n must be in [1, %d) and dst_slots given", DOTS_MAX_BATCH);
+    const DotsConfig& c = e->cfg;
+    const int mb = c.max_batch, V = c.vocab_size;
+    if (src_slot < 0 || src_slot >= mb) return e->fail(DOTS_E_INVALID, "source slot %d out of range [0, %d)", src_slot, mb);
+    const auto fresh = std::find(e->fresh_slots.begin(), e->fresh_slots.end(), src_slot);
+    if (!e->slot_mode || !e->slot_active[src_slot] || fresh == e->fresh_slots.end())
+        return e->fail(DOTS_E_STATE, "slot %d cannot be forked: only a sequence of the most recent dots_slots_prefill, before any decode step", src_slot);
+    const int usable = e->spec_k ? mb / (e->spec_k + 1) : mb;
+    for (int i = 0; i < n; ++i) {
+        const int d = dst_slots[i];
+        if (d < 0 || d >= mb) return e->fail(DOTS_E_INVALID, "slot %d out of range [0, %d)", d, mb);
+        if (d >= usable)
+            return e->fail(DOTS_E_CAPACITY, "slot %d is not usable while speculating: with %d drafts only slots [0, %d) are", d, e->spec_k, usable);
+        if (d == src_slot) return e->fail(DOTS_E_INVALID, "slot %d is the source of the fork", d);
+        if (e->slot_active[d]) return e->fail(DOTS_E_STATE, "slot %d is occupied", d);
+        for (int a = 0; a < i; ++a)
+            if (dst_slots[a] == d) return e->fail(DOTS_E_INVALID, "slot %d listed twice", d);
+    }
+    // ---- page arithmetic: the children name the source's floor(L / 64) full prompt pages and own the rest of the admission reserve
+    const int L = e->slot_prompt[src_slot], max_new = e->slot_limit[src_slot] - L;
+    const int shared = L / 64, own = (admit_tokens(e, L, max_new) + 63) / 64 - shared;          // own >= 1: the reserve is at least L + 1 tokens
+    const auto& src_pages = e->slot_pages[src_slot];
+    if ((int)src_pages.size() < shared + (L % 64 ? 1 : 0)) return e->fail(DOTS_E_STATE, "slot %d does not hold its prompt pages", src_slot);
+    if (shared + own > e->max_pages || (int64_t)n * own > (int64_t)e->free_pages.size())
+        return e->fail(DOTS_E_CAPACITY, "KV pool exhausted: %d forked sequences need %d pages of 64 tokens each, %d of %d are free", n, own,
+                       (int)e->free_pages.size(), e->n_pool_pages);
+    CK(hipSetDevice(e->device));
+    hipStream_t s = e->stream;
+    // ---- from here on the call changes state; a failed launch gives the children's pages back (the slots are not marked occupied yet)
+    struct ForkGuard {
+        DotsEngine* e; const int32_t* dst; int n; bool armed = true;
+        ~ForkGuard() {
+            if (!armed) return;
+            for (int i = 0; i < n; ++i) { release_pages(e, dst[i]); (void)upload_table_row(e, dst[i]); }
+        }
+    } guard{e, dst_slots, n};
+    int32_t stage[3 * DOTS_MAX_BATCH] = {0}, sel_new[DOTS_MAX_BATCH] = {0};
+    int rows = 0;
+    for (int i = 0; i < n; ++i) {
+        const int d = dst_slots[i];
+        auto& mine = e->slot_pages[d];
+        for (int p = 0; p < shared; ++p) {                 // one more holder of a page nobody writes any more: every row appends at positions >= L
+            mine.push_back(src_pages[p]);
+            e->page_refs[src_pages[p]] += 1;
+            e->hp_table[(size_t)d * e->max_pages + p] = src_pages[p];
+        }
+        bool changed = false;
+        grow_pages(e, d, (shared + own) * 64, &changed);   // cannot fall short: counted above
+        CK(upload_table_row(e, d));
+        stage[i] = d;
+        stage[DOTS_MAX_BATCH + i] = mine[shared];
+        sel_new[d] = 1;
+        rows = std::max(rows, d + 1);
+    }
+    stage[2 * DOTS_MAX_BATCH] = L - 1;
+    CK(hipMemcpyAsync(e->fk_dev, stage, sizeof(stage), hipMemcpyHostToDevice, s));
+    const int32_t *fk_dst = e->fk_dev, *fk_pages = e->fk_dev + DOTS_MAX_BATCH, *fk_last = e->fk_dev + 2 * DOTS_MAX_BATCH;
+    // the tail page: behind the prefill's page writers on the same stream; its source is written by nobody until the source's first step
+    if (L % 64) {
+        const size_t page_bytes = (size_t)c.num_kv_heads * 2 * 8192 * (e->kv8 ? 1 : 2);
+        CK(launch_kv_fork_pages(s, e->pool, e->pool_layer_elems * 2, page_bytes, c.num_layers, src_pages[shared], fk_pages, n));
+    }
+    // ---- per-row decode state, as the prefill sets it
+    const int32_t cap = max_new;
+    for (int i = 0; i < n; ++i) {
+        const int d = dst_slots[i];
+        CK(hipMemcpyAsync(e->ctx_len + d, &L, 4, hipMemcpyHostToDevice, s));
+        CK(hipMemcpyAsync(e->d_max_len + d, &cap, 4, hipMemcpyHostToDevice, s));
+        CK(hipMemsetAsync(e->out_lens + d, 0, 4, s));
+        CK(hipMemsetAsync(e->finished + d, 0, 4, s));
+        if (e->sp_ndraft) {
+            CK(hipMemsetAsync(e->sp_ndraft + d, 0, 4, s));
+            CK(hipMemsetAsync(e->sp_stats + (size_t)d * 3, 0, 3 * sizeof(unsigned long long), s));
+        }
+        RET(clear_lp_row(e, d));
+        // the source's last-position logits row (rows of d_logits are slots; nothing has run over them since the prefill)
+        CK(hipMemcpyAsync(e->d_logits + (size_t)d * V, e->d_logits + (size_t)src_slot * V, (size_t)V * 4, hipMemcpyDeviceToDevice, s));
+    }
+    CK(hipMemcpyAsync(e->d_sel_new, sel_new, sizeof(sel_new), hipMemcpyHostToDevice, s));
+    if (e->pen_cnt) {
+        // prompt-presence bits and zeroed counts of every child from the source's packed prompt, still in p_src: one sequence per launch,
+        // so that each starts at the source's first token
+        const int b = (int)(fresh - e->fresh_slots.begin());
+        const int32_t* src0 = e->p_src + (b ? e->hp_last[b - 1] + 1 : 0);
+        for (int i = 0; i < n; ++i) CK(launch_pen_prompt(s, src0, fk_last, fk_dst + i, 1, c.image_token_id, V, e->pen_cnt, e->pen_seen));
+    }
+    if (e->n_guided > 0) CK(launch_guide_reset_rows(s, e->d_guides, fk_dst, n));
+    CK(hipStreamSynchronize(s));                           // L, cap and the staged arrays are stack variables
+    // ---- the children's first tokens: the selection stage over a mask of the children only
+    e->B_sel = rows;
+    e->sel_now = e->d_sel_new;
+    RET(select_tokens(e, 0));
+    for (int i = 0; i < n; ++i) {
+        const int d = dst_slots[i];
+        e->slot_active[d] = 1;
+        e->slot_limit[d] = L + max_new;
+        e->slot_prompt[d] = L;
+        e->slot_ctx_ub[d] = L;
+        e->slot_done[d] = 0;
+    }
+    e->sel_dirty = true;
+    guard.armed = false;
+    return DOTS_OK;
+}
+
 // Enter slot mode with every slot free and every KV page in the pool (whatever a static batch or an abandoned serving loop left behind).
 int dots_slots_reset(DotsEngine* e) {
     if (!e) return DOTS_E_INVALID;
@@ -1878,6 +2005,7 @@ int dots_slots_reset(DotsEngine* e) {
         e->pref_pending = e->pref_deferred = false;
     }
     for (int b = 0; b < (int)e->slot_pages.size(); ++b) release_pages(e, b);
+    e->fresh_slots.clear();
     CK(hipMemcpyAsync(e->block_table, e->hp_table.data(), e->hp_table.size() * 4, hipMemcpyHostToDevice, s));
     std::fill(e->slot_active, e->slot_active + DOTS_MAX_BATCH, 0);
     CK(hipMemsetAsync(e->ctx_len, 0, e->cfg.max_batch * 4, s));
@@ -1917,6 +2045,7 @@ int dots_slots_decode(DotsEngine* e, int n_steps) {
     for (int b = 0; b < e->cfg.max_batch; ++b)
         if (e->slot_active[b]) rows = b + 1;
     if (!rows) return e->fail(DOTS_E_STATE, "every slot is free");
+    e->fresh_slots.clear();                                 // the step overwrites the logits a fork selects from (dots_slots_fork)
     if (e->sel_dirty) {
         int32_t sel[DOTS_MAX_BATCH];
         for (int b = 0; b < DOTS_MAX_BATCH; ++b) sel[b] = e->slot_active[b];

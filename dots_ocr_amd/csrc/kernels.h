@@ -65,6 +65,11 @@ hipError_t launch_flash_attn(hipStream_t s, const bf16_t* q, const bf16_t* k, co
 hipError_t launch_kv_to_pages(hipStream_t s, const bf16_t* k, const bf16_t* qkv, const Tile64* tiles, int n_tiles,
                               const int32_t* block_table, int max_pages, void* pool_layer, int64_t T, int Hq, int Hkv,
                               const float* kv_scales = nullptr);
+// ---- kv_fork.hip: the tail-page copy of dots_slots_fork.  In every one of `layers` layers (layer_bytes apart) page src_page is
+// copied whole (page_bytes = Hkv x 2 x 8192 elements, bf16 or e4m3) to the n pages dst_pages[0 .. n) (device array, n < DOTS_MAX_BATCH);
+// the caller guarantees that every index names a page of the pool and that no destination is the source
+hipError_t launch_kv_fork_pages(hipStream_t s, void* pool, size_t layer_bytes, size_t page_bytes, int layers, int src_page, const int32_t* dst_pages,
+                                int n);
 // ---- decode_fused.hip: dense layers of the decode step with in-workgroup split-K and fused prologues/epilogues.
 // Activations between them travel as X images [K/8][XR][8], XR = 8 (B <= 8) or 16 (decode_layout.h).
 hipError_t launch_dec_embed(hipStream_t s, const int32_t* tokens, const bf16_t* embed, bf16_t* h, int B, int dim);

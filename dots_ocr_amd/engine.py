@@ -326,6 +326,7 @@ def _prototypes(lib):
         "dots_set_eos": (i32, [vp, P(i32), i32]),
         "dots_slots_prefill": (i32, [vp, P(i32), i32, P(i32), P(i32), P(i32)]),
         "dots_slots_decode": (i32, [vp, i32]),
+        "dots_slots_fork": (i32, [vp, i32, P(i32), i32]),
         "dots_slots_poll": (i32, [vp, P(i32), P(i32)]),
         "dots_slot_read": (i32, [vp, i32, P(i32), i32, P(i32)]),
         "dots_slot_release": (i32, [vp, i32]),
@@ -413,6 +414,7 @@ EXPORTED_SYMBOLS = [
     "dots_op_select_tokens_guided", "dots_bench_select_tokens_guided",
     "dots_set_row_ngram", "dots_op_select_tokens_ngram", "dots_bench_select_tokens_ngram",
     "dots_set_speculation", "dots_set_row_drafts", "dots_spec_stats", "dots_op_ngram_draft",
+    "dots_slots_fork",
 ]
 
 MAX_SPEC_DRAFTS = 15                         # DOTS_MAX_SPEC_DRAFTS: drafts per slot and step
@@ -980,6 +982,14 @@ class Engine:
         cap = np.ascontiguousarray(max_new_tokens, dtype=np.int32)
         assert sl.shape == lens.shape == cap.shape and ids.shape[0] == int(lens.sum())
         self._ck(self.lib.dots_slots_prefill(self.h, _i32p(sl), sl.shape[0], _i32p(ids), _i32p(lens), _i32p(cap)), "dots_slots_prefill")
+
+    def slots_fork(self, src: int, dst_slots: Sequence[int]):
+        """Parallel sampling: every free slot of dst_slots becomes a copy of the sequence slots_prefill just put into slot src (no decode
+        step since): the same prompt over the same KV pages, and its own first token under the row parameters already set on it.  From
+        then on each is an independent sequence, equal bit for bit to a prefill of the prompt into that slot."""
+        dst = np.ascontiguousarray(dst_slots, dtype=np.int32)
+        assert dst.ndim == 1
+        self._ck(self.lib.dots_slots_fork(self.h, int(src), _i32p(dst) if dst.shape[0] else None, dst.shape[0]), "dots_slots_fork")
 
     def slots_reset(self):
         """Slot mode, every slot free, every KV page in the pool."""

@@ -135,7 +135,7 @@ class DotsOcrHipForCausalLM:
                  stop_token_ids=None, ignore_eos: bool = False, guided_regex=None, guided_choice=None, guided_json=None,
                  guided_whitespace_pattern=None, no_repeat_ngram_size: Optional[int] = None, no_repeat_ngram_window: Optional[int] = None,
                  no_repeat_ngram_whitelist=None, speculative_ngram: Optional[int] = None, prompt_lookup_min: int = 2, prompt_lookup_max: int = 4,
-                 **_):
+                 num_return_sequences: int = 1, **_):
         """HF-shaped generate.  do_sample / temperature / top_p default to the checkpoint's generation_config.json (greedy when it
         is absent); with sampling on, tokens are drawn on the GPU from softmax(logits / temperature) restricted to the top_p
         nucleus, reproducibly from `seed`.  Returns LongTensor
@@ -166,11 +166,20 @@ class DotsOcrHipForCausalLM:
         call with n-gram speculative decoding (Engine.set_speculation): it takes the continuous path, where a greedy
         sequence verifies up to k drafted tokens per decode step, max_batch // (k + 1) sequences at a time.  The tokens are exactly
         those of the call without it; sampled or rule-carrying sequences simply run unspeculated.  The engine is left with speculation
-        off."""
+        off.
+
+        num_return_sequences (n >= 1, HF's name) returns n sequences per prompt from one vision tower and one prefill of it (parallel
+        sampling: Engine.slots_fork): LongTensor [B * n, T + new], row i * n + j = sequence j of prompt i as HF lays it out,
+        drawn with seed + i * n + j.  It runs on the continuous path; continuous=False with n > 1 is a ValueError."""
         import dataclasses
         import torch
         t_eff, p_eff = resolve_sampling(self.generation_config, do_sample, temperature, top_p)
         self.engine.set_sampling(t_eff, p_eff, seed if t_eff > 0 else 0)
+        nrs = num_return_sequences
+        if isinstance(nrs, bool) or not isinstance(nrs, int) or nrs < 1:
+            raise ValueError(f"num_return_sequences must be an integer >= 1, got {nrs!r}")
+        if nrs > 1 and continuous is False:
+            raise ValueError("num_return_sequences > 1 runs on the continuous path: continuous=False cannot be combined with it")
         row_sp = None
         if (top_k or 0) > 0 or repetition_penalty not in (None, 1.0) or (frequency_penalty or 0.0) != 0.0 or (presence_penalty or 0.0) != 0.0:
             from .engine import SamplingParams
@@ -218,6 +227,13 @@ class DotsOcrHipForCausalLM:
                     return dataclasses.replace(base, seed=int(seed) + b)
         elif no_repeat_ngram_window or no_repeat_ngram_whitelist:
             raise ValueError("no_repeat_ngram_window / no_repeat_ngram_whitelist need no_repeat_ngram_size")
+        if nrs > 1:
+            continuous = True
+            from .engine import SamplingParams
+            per_seq = row_sp(0) if row_sp else SamplingParams(temperature=t_eff, top_p=p_eff, seed=seed)
+
+            def row_sp(b):                       # prompt b's sequences take seeds seed + b * n .. + n - 1 (the scheduler adds the index)
+                return dataclasses.replace(per_seq, seed=int(seed) + b * nrs)
         spec_k = int(speculative_ngram or 0)
         if spec_k:
             if continuous is False:
@@ -227,7 +243,7 @@ class DotsOcrHipForCausalLM:
             self.engine.set_speculation(spec_k, int(prompt_lookup_min), int(prompt_lookup_max))
         try:
             return self._generate(input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens, eos_token_id, pad_token_id, continuous,
-                                  row_sp, rules, guide, ngram)
+                                  row_sp, rules, guide, ngram, nrs)
         finally:
             if spec_k:
                 try:
@@ -244,7 +260,7 @@ class DotsOcrHipForCausalLM:
                     warnings.warn(f"guide {guide} could not be destroyed: {e}")
 
     def _generate(self, input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens, eos_token_id, pad_token_id, continuous, row_sp, rules,
-                  guide, ngram=None):
+                  guide, ngram=None, nrs=1):
         import torch
         ids = input_ids.detach().cpu().numpy()
         B, T = ids.shape
@@ -287,7 +303,7 @@ class DotsOcrHipForCausalLM:
         if longest >= self.max_seq_len:
             raise ValueError(f"prompt of {longest} tokens does not fit max_seq_len={self.max_seq_len}")
         max_new_tokens = max(1, min(int(max_new_tokens), self.max_seq_len - longest))
-        new_tokens = np.full((B, max_new_tokens), pad, dtype=np.int64)
+        new_tokens = np.full((B * nrs, max_new_tokens), pad, dtype=np.int64)
         n_max = 0
         seq_patches = [int(sum(patch_off[g + 1] - patch_off[g] for g in img_of_seq[b])) for b in range(B)]
         if continuous is None:
@@ -300,11 +316,13 @@ class DotsOcrHipForCausalLM:
                     lo, hi = int(patch_off[img_of_seq[b][0]]), int(patch_off[img_of_seq[b][-1] + 1])
                     pix = pv_dev[lo:hi] if pv_dev is not None else pv_host[lo:hi]
                     reqs.append(Request(prompts[b], pix, grid[img_of_seq[b][0]:img_of_seq[b][-1] + 1], max_new_tokens,
-                                        sampling=row_sp(b) if row_sp else None, rules=rules, guide=guide, ngram=ngram))
+                                        sampling=row_sp(b) if row_sp else None, rules=rules, guide=guide, ngram=ngram, n=nrs))
                 else:
                     reqs.append(Request(prompts[b], None, None, max_new_tokens, sampling=row_sp(b) if row_sp else None, rules=rules, guide=guide,
-                                        ngram=ngram))
+                                        ngram=ngram, n=nrs))
             outs = ContinuousBatcher(self.engine, eos_ids=eos).run(reqs)
+            if nrs > 1:                          # row i * n + j = sequence j of prompt i
+                outs = [o for r in reqs for o in r.outputs]
             for b, o in enumerate(outs):
                 new_tokens[b, :len(o)] = o
                 n_max = max(n_max, len(o))
@@ -375,7 +393,7 @@ class DotsOcrHipForCausalLM:
                     self.engine.set_row_guide(j, None)
                 if ngram is not None:
                     self.engine.set_row_ngram(j, None)
-        full = np.concatenate([ids.astype(np.int64), new_tokens[:, :n_max]], axis=1)    # HF stops at the longest sequence
+        full = np.concatenate([np.repeat(ids.astype(np.int64), nrs, axis=0), new_tokens[:, :n_max]], axis=1)    # HF stops at the longest sequence
         res = torch.from_numpy(full)
         return res.to(input_ids.device) if input_ids.is_cuda else res
 

@@ -35,6 +35,9 @@ class Request:
     rules: Optional[object] = None              # engine.LogitRules of this request (bias, allowed ids, min_tokens, stop ids, ignore_eos), or None
     guide: Optional[int] = None                 # handle of Engine.create_guide the request's output must follow, or None
     ngram: Optional[object] = None              # engine.NgramRule of this request (no-repeat n-gram blocking), or None
+    n: int = 1                                  # parallel sampling: n sequences from one tower and one prefill; sequence i runs under
+                                                # `sampling` with seed + i, everything else shared.  A finished request with n > 1 carries outputs
+                                                # (the n token arrays in index order), logprobs_out as a list in that order and kv_truncated_each
 
     def n_patches(self) -> int:
         if self.grid_thw is None:
@@ -86,6 +89,8 @@ class ContinuousBatcher:
         self._row_rules: Dict[int, object] = {}                  # slot -> the LogitRules set on it (engine.set_row_logit_rules)
         self._row_guide: Dict[int, int] = {}                     # slot -> the guide handle set on it (engine.set_row_guide)
         self._row_ngram: Dict[int, object] = {}                  # slot -> the NgramRule set on it (engine.set_row_ngram)
+        self._kids: Dict[int, List[int]] = {}                    # request id -> the slots planned for sequences 1 .. n - 1 of a request with n > 1
+        self._seq_index: Dict[int, int] = {}                     # slot -> index of its sequence within a request with n > 1
         self.kv_truncated = 0                                    # sequences ended early by a dry KV pool (finish reason "kv_pool_exhausted")
         self._rejected: List[Tuple[int, Request]] = []           # requests whose own parameters the engine refused (reported by step())
         self.eos_ids = tuple(int(t) for t in eos_ids)
@@ -107,6 +112,12 @@ class ContinuousBatcher:
             raise ValueError(f"prompt of {ids.shape[0]} tokens exceeds max_prefill_tokens={self.max_prefill_tokens}")
         if req.n_patches() > self.max_patches:
             raise ValueError(f"request has {req.n_patches()} vision patches, more than max_patches={self.max_patches}")
+        if isinstance(req.n, bool) or not isinstance(req.n, (int, np.integer)) or req.n < 1:
+            raise ValueError(f"n must be an integer >= 1, got {req.n!r}")
+        if req.n > self.n_slots:
+            raise ValueError(f"n = {req.n} sequences need more than the {self.n_slots} usable slots")
+        if req.n > 1 and not hasattr(self.engine, "slots_fork"):
+            raise ValueError("this engine cannot fork a prefilled sequence (no slots_fork): n > 1 is not available")
         if req.rules is not None and not hasattr(self.engine, "set_row_logit_rules"):
             raise ValueError("this engine cannot honour logit rules (no set_row_logit_rules)")
         if req.guide is not None and not hasattr(self.engine, "set_row_guide"):
@@ -125,8 +136,8 @@ class ContinuousBatcher:
         req.input_ids = ids
         # like HF generate, stop at the context capacity instead of failing
         req.max_new_tokens = max(1, min(int(req.max_new_tokens), self.max_seq_len - ids.shape[0]))
-        if hasattr(self.engine, "kv_pool_info") and self._admit_pages(ids.shape[0], req.max_new_tokens) > self.engine.kv_pool_info()[0]:
-            raise ValueError(f"prompt of {ids.shape[0]} tokens needs {self._admit_pages(ids.shape[0], req.max_new_tokens)} KV pages, "
+        if hasattr(self.engine, "kv_pool_info") and self._group_pages(req) > self.engine.kv_pool_info()[0]:
+            raise ValueError(f"prompt of {ids.shape[0]} tokens needs {self._group_pages(req)} KV pages, "
                              f"the pool holds {self.engine.kv_pool_info()[0]}")
         if self.full_reservation and hasattr(self.engine, "kv_pool_info") and self._worst_pages(req) > self.engine.kv_pool_info()[0]:
             raise ValueError(f"prompt + max_new_tokens = {ids.shape[0]} + {req.max_new_tokens} tokens need {self._worst_pages(req)} KV pages under full "
@@ -149,8 +160,25 @@ class ContinuousBatcher:
     def _admit_pages(self, prompt: int, max_new: int) -> int:
         return (min(prompt + min(int(max_new), self.ADMIT_AHEAD), self.max_seq_len) + 63) // 64
 
-    def _worst_pages(self, r: Request) -> int:
-        return (min(int(r.input_ids.shape[0]) + int(r.max_new_tokens), self.max_seq_len) + 63) // 64
+    def _group_pages(self, r: Request) -> int:
+        """pages a request takes at admission: sequence 0 its prompt + ADMIT_AHEAD, each further sequence of n > 1 the same less the full
+        prompt pages it shares with sequence 0 (Engine.slots_fork)"""
+        t = int(r.input_ids.shape[0])
+        need = self._admit_pages(t, r.max_new_tokens)
+        return need + (int(r.n) - 1) * (need - t // 64)
+
+    def _worst_pages(self, r: Request, n: Optional[int] = None) -> int:
+        """pages of the request's sequences at their caps, the shared prompt pages counted once; n: of that many of its sequences only
+        (what is still running: a conservative count, as if sequence 0 were among them)"""
+        t, n = int(r.input_ids.shape[0]), int(r.n) if n is None else n
+        worst = (min(t + int(r.max_new_tokens), self.max_seq_len) + 63) // 64
+        return worst + (n - 1) * (worst - t // 64)
+
+    def _running_worst(self) -> int:
+        seqs: Dict[int, Tuple[Request, int]] = {}
+        for rid, r in self.running.values():
+            seqs[rid] = (r, seqs.get(rid, (r, 0))[1] + 1)
+        return sum(self._worst_pages(r, k) for r, k in seqs.values())
 
     def _fits_full_reservation(self, admitted: Sequence[Request], new: Sequence[Request]) -> bool:
         """Full reservation (headroom_pages=None): the worst case of everything in flight — running, already in this group, prefetched —
@@ -158,7 +186,7 @@ class ContinuousBatcher:
         if not self.full_reservation or not hasattr(self.engine, "kv_pool_info"):
             return True
         total = self.engine.kv_pool_info()[0]
-        committed = sum(self._worst_pages(r) for _, r in self.running.values()) + sum(self._worst_pages(r) for r in admitted)
+        committed = self._running_worst() + sum(self._worst_pages(r) for r in admitted)
         return committed + sum(self._worst_pages(r) for r in new) <= total
 
     def plan_admission(self) -> List[Tuple[int, int, Request]]:
@@ -170,13 +198,16 @@ class ContinuousBatcher:
         while self.pending and free and (self.admit_group is None or len(group) < self.admit_group):
             rid, req = self.pending[0]
             p, t = req.n_patches(), int(req.input_ids.shape[0])
+            if req.n > len(free):
+                break                                # n sequences need n slots: the head of the queue waits for them, nothing overtakes it
             if group and (patches + p > self.max_patches or tokens + t > self.max_prefill_tokens):
                 break
             # paged KV, on demand: a sequence reserves its prompt + ADMIT_AHEAD tokens now and grows page by page; admit only while every
             # running sequence (and this one) could still take `headroom` more pages, so that a dry pool — which ends a sequence early
             # at what its pages hold — stays the exception.  Nothing running: admit whatever fits (submit() checked that it can).
-            need = self._admit_pages(t, req.max_new_tokens)
-            reserve = self.headroom_pages * (len(self.running) + len(group) + 1) if (self.running or group) else 0
+            need = self._group_pages(req)
+            taken = len(self.running) + sum(r.n for _, _, r in group)
+            reserve = self.headroom_pages * (taken + req.n) if (self.running or group) else 0
             if (self.running or group) and not self._fits_full_reservation([r for _, _, r in group], [req]):
                 break                                # worst case of everything in flight must fit the pool (submit() checked a lone request)
             if need + reserve > pages_free:
@@ -184,6 +215,8 @@ class ContinuousBatcher:
             pages_free -= need
             self.pending.popleft()
             group.append((free.pop(0), rid, req))
+            if req.n > 1:
+                self._kids[rid] = [free.pop(0) for _ in range(req.n - 1)]
             patches += p
             tokens += t
         return group
@@ -215,11 +248,14 @@ class ContinuousBatcher:
             if self._row_ngram.pop(s, None) is not None:
                 self.engine.set_row_ngram(s, None)
 
-    def _set_rows(self, s, r):
-        """per-row parameters of request r on slot s; they apply from the first token the prefill selects"""
+    def _set_rows(self, s, r, index: int = 0):
+        """per-row parameters of request r on slot s; they apply from the first token the prefill selects.  index: the sequence of a
+        request with n > 1 — its seed is the request's + index (vLLM's rule), everything else is shared"""
         if r.sampling is not None:
-            self._row_params[s] = r.sampling         # recorded first: a call that raises half way is still cleared
-            self.engine.set_row_sampling(s, r.sampling)
+            import dataclasses
+            sp = r.sampling if index == 0 else dataclasses.replace(r.sampling, seed=int(r.sampling.seed) + index)
+            self._row_params[s] = sp                 # recorded first: a call that raises half way is still cleared
+            self.engine.set_row_sampling(s, sp)
         elif self._row_params.pop(s, None) is not None:
             self.engine.set_row_sampling(s, None)
         if r.logprobs is not None:                   # logprobs likewise, the prefill's token included
@@ -248,21 +284,41 @@ class ContinuousBatcher:
         slots = [s for s, _, _ in group]
         lens = [int(r.input_ids.shape[0]) for _, _, r in group]
         caps = [int(r.max_new_tokens) for _, _, r in group]
-        for s, _, r in ([] if rows_set else group):       # a prefetched group: its tower has run, so it goes in (or fails) as a whole
+        kids = {rid: self._kids.pop(rid) for _, rid, r in group if r.n > 1}       # the slots of sequences 1 .. n - 1 (parallel sampling)
+        every = slots + [k for ks in kids.values() for k in ks]
+        for s, rid, r in ([] if rows_set else group):     # a prefetched group: its tower has run, so it goes in (or fails) as a whole
             try:
                 self._set_rows(s, r)
+                for j, k in enumerate(kids.get(rid, ()), 1):
+                    self._set_rows(k, r, j)
             except Exception:
-                self._clear_rows(slots)              # nothing of this group stays behind; the caller puts the group back in the queue
+                self._clear_rows(every)              # nothing of this group stays behind; the caller puts the group back in the queue
                 raise
         try:
             self.engine.slots_prefill(slots, np.concatenate([r.input_ids for _, _, r in group]), lens, caps)
         except Exception:
-            self._clear_rows(slots)                  # the slots stay free
+            self._clear_rows(every)                  # the slots stay free
+            raise
+        forked: List[int] = []
+        try:                                         # one fork per request with n > 1, before any decode step: the prefill is still fresh
+            for s, rid, r in group:
+                if rid in kids:
+                    self.engine.slots_fork(s, kids[rid])
+                    forked += kids[rid]
+        except Exception:
+            for s in slots + forked:                 # the prefill went in: give its slots back, the caller re-queues the group
+                self.engine.slot_release(s)
+            self._clear_rows(every)
             raise
         for s, rid, r in group:
-            self.running[s] = (rid, r)
-            self._last_lens[s] = 0                   # a reused slot must not inherit its previous occupant's length (_soon_free counted a
+            for j, k in enumerate([s] + kids.get(rid, [])):
+                self.running[k] = (rid, r)
+                self._last_lens[k] = 0               # a reused slot must not inherit its previous occupant's length (_soon_free counted a
                                                      # just-admitted long request as "about to finish" and the look-ahead group was sized for slots that stayed busy)
+                if r.n > 1:
+                    self._seq_index[k] = j
+            if r.n > 1:
+                r._parts = {}
         self.admissions += 1
 
     def _admit(self, group):
@@ -272,9 +328,11 @@ class ContinuousBatcher:
         for s, rid, r in group:
             try:
                 self._set_rows(s, r)
+                for j, k in enumerate(self._kids.get(rid, ()), 1):
+                    self._set_rows(k, r, j)
                 kept.append((s, rid, r))
             except Exception as e:
-                self._clear_rows([s])
+                self._clear_rows([s] + self._kids.pop(rid, []))
                 r.error = RequestRejected(str(e))
                 self._rejected.append((rid, r))
         if not kept:
@@ -291,24 +349,31 @@ class ContinuousBatcher:
     def _admit_ahead(self) -> bool:
         """The group whose tower was prefetched goes in as a whole as soon as it has the slots and the pages."""
         free = self.free_slots()
-        if len(free) < len(self._ahead):
+        if len(free) < sum(r.n for _, r in self._ahead):
             return False
         # sequences are decoding and the tower is still running: taking the group now would queue every decode chunk behind the tower
         # (vit_take makes the engine's stream wait for it) — keep decoding, take it when its rows exist.  Nothing running: wait for it.
         if self.running and hasattr(self.engine, "vit_ready") and not self.engine.vit_ready():
             return False
         if hasattr(self.engine, "kv_pool_info"):
-            need = sum(self._admit_pages(int(r.input_ids.shape[0]), r.max_new_tokens) for _, r in self._ahead)
-            reserve = self.headroom_pages * (len(self.running) + len(self._ahead)) if self.running else 0
+            need = sum(self._group_pages(r) for _, r in self._ahead)
+            reserve = self.headroom_pages * (len(self.running) + sum(r.n for _, r in self._ahead)) if self.running else 0
             if need + reserve > self.engine.kv_pool_info()[1]:
                 return False
             if self.running and not self._fits_full_reservation([], [r for _, r in self._ahead]):
                 return False
         group = self._ahead
+        placed = []
+        for rid, r in group:                         # lowest slots first; the sequences of a request with n > 1 side by side
+            placed.append((free.pop(0), rid, r))
+            if r.n > 1:
+                self._kids[rid] = [free.pop(0) for _ in range(r.n - 1)]
         try:
             self.engine.vit_take()
-            self._prefill([(free[i], rid, r) for i, (rid, r) in enumerate(group)])
+            self._prefill(placed)
         except Exception:
+            for rid, _ in group:
+                self._kids.pop(rid, None)
             # the rows are gone (or were never there): the group goes back to the head of the queue so that the caller's failure
             # handling — which walks `pending` and `running` — sees its requests, and the next step does not take a stale batch
             self._ahead, self._ahead_keep = [], None
@@ -336,10 +401,10 @@ class ContinuousBatcher:
             if len(self.free_slots()) + self._soon_free(2 * self.chunk + k * self.tower_steps_per_page) >= k:
                 cap = k
                 break
-        while self.pending and len(group) < cap:
+        while self.pending and sum(r.n for _, r in group) + self.pending[0][1].n <= cap:      # cap counts slots: a request takes n of them
             rid, req = self.pending[0]
             p, t = req.n_patches(), int(req.input_ids.shape[0])
-            pg = self._admit_pages(t, req.max_new_tokens)
+            pg = self._group_pages(req)
             if p == 0 or patches + p > self.max_patches or tokens + t > self.max_prefill_tokens or pages + pg > total_pages:
                 break                                # a text-only request goes through the ordinary admission, in its turn
             if self.full_reservation and sum(self._worst_pages(r) for _, r in group) + self._worst_pages(req) > total_pages:
@@ -378,9 +443,25 @@ class ContinuousBatcher:
                     _, limit = self.engine.slot_capacity(s)
                     req.kv_truncated = bool(limit < int(req.input_ids.shape[0]) + int(req.max_new_tokens) and len(toks) >= limit - int(req.input_ids.shape[0]))
                     self.kv_truncated += int(req.kv_truncated)
+                lp_out = None
                 if req.logprobs is not None:         # read before the release switches the slot's logprobs off
-                    req.logprobs_out = self.engine.row_logprobs(s, len(toks))
-                done.append((rid, req, toks))
+                    lp_out = self.engine.row_logprobs(s, len(toks))
+                if req.n == 1:
+                    if req.logprobs is not None:
+                        req.logprobs_out = lp_out
+                    done.append((rid, req, toks))
+                else:
+                    # one sequence of n: its slot goes back now, the request is reported once, when its last sequence has finished
+                    req._parts[self._seq_index.pop(s)] = (toks, lp_out, req.kv_truncated)
+                    if len(req._parts) == req.n:
+                        parts = [req._parts[j] for j in range(req.n)]
+                        req.outputs = [t for t, _, _ in parts]
+                        if req.logprobs is not None:
+                            req.logprobs_out = [l for _, l, _ in parts]
+                        req.kv_truncated_each = [k for _, _, k in parts]
+                        req.kv_truncated = any(req.kv_truncated_each)
+                        del req._parts
+                        done.append((rid, req, req.outputs[0]))
                 if self._row_ngram.pop(s, None) is not None:     # the rule leaves with its request (the engine's release clears the row too)
                     self.engine.set_row_ngram(s, None)
                 self.engine.slot_release(s)
@@ -408,8 +489,10 @@ class ContinuousBatcher:
                     # vit_forward / slots_prefill failed: plan_admission popped these requests and nothing registered them yet — put them
                     # back at the head of the queue (in order) so that the caller's failure handling, which walks `pending`, `running` and
                     # the prefetched group, finds every request (server.py fails their futures; a lost request would hang its HTTP call)
-                    for s, _, _ in group:
-                        self.running.pop(s, None)
+                    for s, rid, _ in group:
+                        for k in [s] + self._kids.pop(rid, []):
+                            self.running.pop(k, None)
+                            self._seq_index.pop(k, None)
                     self.pending.extendleft(reversed([(rid, r) for _, rid, r in group if getattr(r, "error", None) is None]))
                     raise
         self._look_ahead()

@@ -42,7 +42,7 @@ from .processing import ASSISTANT, END_USER, IMG_END, IMG_PAD, IMG_START, USER
 
 class _Job:
     __slots__ = ("image", "text", "max_tokens", "temperature", "top_p", "top_k", "repetition_penalty", "frequency_penalty",
-                 "presence_penalty", "seed", "logprobs", "rules", "guide", "ngram", "future")
+                 "presence_penalty", "seed", "logprobs", "rules", "guide", "ngram", "n", "future")
 
     def __init__(self, image, text, max_tokens, temperature, top_p, top_k=0, repetition_penalty=1.0, frequency_penalty=0.0,
                  presence_penalty=0.0, seed=None, logprobs=None):
@@ -53,6 +53,7 @@ class _Job:
         self.rules = None                           # engine.LogitRules when the request carries logit rules, else None
         self.guide = None                           # guided.Guide when the request carries a guided decoding field, else None
         self.ngram = None                           # engine.NgramRule when the request carries no_repeat_ngram_size, else None
+        self.n = 1                                  # sequences to return (parallel sampling)
         self.future: Future = Future()
 
     @property
@@ -176,11 +177,12 @@ class ContinuousWorker(BatchingWorker):
         from .engine import SamplingParams
         if job.temperature <= 0 and not job.extended:
             return None
-        if job.seed is None:
-            self.seed += 1
+        seed = job.seed
+        if seed is None:                             # n sequences run under seed .. seed + n - 1: they take n values of the counter
+            seed = self.seed + 1
+            self.seed += job.n
         return SamplingParams(temperature=job.temperature, top_p=job.top_p, top_k=job.top_k, repetition_penalty=job.repetition_penalty,
-                              frequency_penalty=job.frequency_penalty, presence_penalty=job.presence_penalty,
-                              seed=self.seed if job.seed is None else job.seed)
+                              frequency_penalty=job.frequency_penalty, presence_penalty=job.presence_penalty, seed=seed)
 
     @property
     def has_logprobs(self) -> bool:
@@ -224,6 +226,15 @@ class ContinuousWorker(BatchingWorker):
             self._guide_users[h] -= 1
 
     def _finish(self, job: _Job, prompt_tokens: int, toks, kv_truncated: bool = False, logprobs=None):
+        job.future.set_result(self._result(job, prompt_tokens, toks, kv_truncated, logprobs))
+
+    def _finish_group(self, job: _Job, prompt_tokens: int, req):
+        """a request with n > 1: one result per sequence, in index order; the prompt is counted once"""
+        lps = getattr(req, "logprobs_out", None) or [None] * job.n
+        each = [self._result(job, prompt_tokens, t, k, l) for t, k, l in zip(req.outputs, req.kv_truncated_each, lps)]
+        job.future.set_result({"prompt_tokens": prompt_tokens, "completion_tokens": sum(r["completion_tokens"] for r in each), "choices": each})
+
+    def _result(self, job: _Job, prompt_tokens: int, toks, kv_truncated: bool = False, logprobs=None):
         eos = set(self.model.config.eos_token_ids)
         if job.guide is not None:                    # a guided row ends at an EOS id whether or not ignore_eos is set
             eos = eos | (set(job.rules.stop) if job.rules is not None else set())
@@ -237,7 +248,7 @@ class ContinuousWorker(BatchingWorker):
         res = {"text": text, "prompt_tokens": prompt_tokens, "completion_tokens": len(toks), "finish_reason": reason}
         if job.logprobs is not None:
             res["logprobs"] = _logprobs_object(self.processor, toks, logprobs, job.logprobs)
-        job.future.set_result(res)
+        return res
 
     def _run(self):
         from collections import deque
@@ -285,7 +296,7 @@ class ContinuousWorker(BatchingWorker):
                         req = Request(ids, inputs.get("pixel_values"), None if "image_grid_thw" not in inputs
                                       else inputs["image_grid_thw"].numpy(), job.max_tokens, tag=job,
                                       sampling=self._row_params(job) if per_row else None, logprobs=job.logprobs, rules=job.rules,
-                                      guide=self._guide_handle(job), ngram=job.ngram)
+                                      guide=self._guide_handle(job), ngram=job.ngram, n=job.n)
                         try:
                             cb.submit(req)
                         except Exception:
@@ -299,6 +310,9 @@ class ContinuousWorker(BatchingWorker):
                         self._guide_done(req)
                         if getattr(req, "error", None) is not None:      # refused at admission: this request alone
                             req.tag.future.set_exception(req.error)
+                            continue
+                        if req.n > 1:
+                            self._finish_group(req.tag, int(req.input_ids.shape[0]), req)
                             continue
                         self._finish(req.tag, int(req.input_ids.shape[0]), toks, getattr(req, "kv_truncated", False),
                                      getattr(req, "logprobs_out", None))
@@ -612,6 +626,16 @@ def create_app(model, processor, model_name: str = "model", max_batch: int = 8, 
             if job.guide is not None and not (isinstance(worker, ContinuousWorker) and worker.has_guides):
                 raise HTTPException(400, "guided_regex, guided_choice, guided_json, guided_layout and a json_schema response_format need "
                                          "continuous batching on an engine with guides (Engine.set_row_guide) that knows its token bytes")
+        n = req.get("n")
+        if n is not None:                            # parallel sampling: n sequences of one page from one tower and one prefill
+            if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+                raise HTTPException(400, "n must be an integer >= 1")
+            if n > 1 and not (isinstance(worker, ContinuousWorker) and hasattr(model.engine, "slots_fork")):
+                raise HTTPException(400, "n > 1 needs continuous batching on an engine that forks a prefilled sequence (Engine.slots_fork)")
+            slots = int(getattr(getattr(model, "engine", None), "usable_slots", max_batch))
+            if n > slots:
+                raise HTTPException(400, f"n = {n} exceeds the {slots} sequences this server runs at a time")
+            job.n = n
         fut = worker.submit(job)
         try:
             res = await run_in_threadpool(fut.result)
@@ -619,13 +643,16 @@ def create_app(model, processor, model_name: str = "model", max_batch: int = 8, 
             raise HTTPException(400, f"request refused: {e}")
         except Exception as e:
             raise HTTPException(500, f"generation failed: {e}")
-        choice = {"index": 0, "message": {"role": "assistant", "content": res["text"]}, "finish_reason": res["finish_reason"]}
-        if job.logprobs is not None:                 # only when asked: other responses stay exactly as they were
-            choice["logprobs"] = res["logprobs"]
+        choices = []
+        for index, r in enumerate(res["choices"] if job.n > 1 else [res]):
+            choice = {"index": index, "message": {"role": "assistant", "content": r["text"]}, "finish_reason": r["finish_reason"]}
+            if job.logprobs is not None:             # only when asked: other responses stay exactly as they were
+                choice["logprobs"] = r["logprobs"]
+            choices.append(choice)
         return {
             "id": "chatcmpl-" + uuid.uuid4().hex, "object": "chat.completion", "created": int(time.time()),
             "model": req.get("model", model_name),
-            "choices": [choice],
+            "choices": choices,
             "usage": {"prompt_tokens": res["prompt_tokens"], "completion_tokens": res["completion_tokens"],
                       "total_tokens": res["prompt_tokens"] + res["completion_tokens"]},
         }

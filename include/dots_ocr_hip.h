@@ -386,8 +386,21 @@ int dots_set_gemm_plan(DotsEngine* e, int plan);
  * dots_slots_poll    finished[b] = -1 free / 0 running / 1 finished, out_lens[b] = tokens generated so far; both
  *                    int32 [max_batch].  Synchronises the stream.
  * dots_slot_read     copies min(n, capacity) generated ids of one occupied slot, *n_out = n.
- * dots_slot_release  marks the slot free. */
+ * dots_slot_release  marks the slot free.
+ * dots_slots_fork    parallel sampling: gives each of the n free slots dst_slots_host[i] a copy of the freshly prefilled sequence
+ *                    in src_slot — same prompt, same KV, the source's cap on generated tokens — and its own first token, selected from the
+ *                    source's last-position logits under the row parameters already set on that slot (sampling, logprobs, logit rules,
+ *                    guide, n-gram rule: set, then fork, as with dots_slots_prefill).  From then on a child is an independent sequence: it
+ *                    generates, bit for bit, what a dots_slots_prefill of the same prompt into that slot would have.  src_slot must have
+ *                    been filled by the most recent dots_slots_prefill with no decode step issued since (DOTS_E_STATE otherwise); several
+ *                    forks may follow one prefill.  A child's block-table row names the source's floor(L / 64) full prompt pages
+ *                    (reference counted: a page returns to the pool when its last holder is released; dots_kv_pool_info counts physical
+ *                    pages) and takes ceil(min(L + min(max_new, 64), max_seq_len) / 64) - floor(L / 64) pages of its own, the first of
+ *                    which receives a copy of the source's partially filled page.  Refused with nothing changed: a destination out of
+ *                    range, repeated or equal to the source (DOTS_E_INVALID), occupied (DOTS_E_STATE), not usable while speculating, or a
+ *                    pool that cannot serve the children's pages (DOTS_E_CAPACITY).  Synchronises the stream. */
 int dots_slots_reset(DotsEngine* e);
+int dots_slots_fork(DotsEngine* e, int src_slot, const int32_t* dst_slots_host, int n);
 int dots_set_eos(DotsEngine* e, const int32_t* eos_ids_host, int n_eos);
 int dots_slots_prefill(DotsEngine* e, const int32_t* slots_host, int n, const int32_t* input_ids_host,
                        const int32_t* prompt_lens_host, const int32_t* max_new_tokens_host);
