@@ -917,7 +917,7 @@ DEVI uint32_t radix_select(Each each, uint64_t target, bool by_mass, SelLds& L) 
 
 DEVI void commit_row(const StepState& st, const RowSel& rs, int b, int V, bool pen, int tok) {
     if (pen && !st.finished[b] && tok >= 0 && tok < V) rs.cnt[(size_t)b * V + tok] += 1;     // output counts of the rows with penalties
-    commit_token(st, b, tok, row_ruled(rs, b) ? rs.rules + b : nullptr, rs.guide.rows ? &rs.guide : nullptr);
+    commit_token(st, b, tok, row_ruled(rs, b) ? rs.rules + b : nullptr, rs.guide.rows ? &rs.guide : nullptr, rs.stop.rows ? &rs.stop : nullptr);
 }
 
 // the merged arg max partials of row b -> L.best / L.bi (every thread must call)

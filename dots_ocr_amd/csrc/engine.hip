@@ -240,6 +240,14 @@ struct DotsEngine {
     uint32_t* ngram_mask = nullptr;
     int row_ngram[DOTS_MAX_BATCH] = {0};
     int n_ngram = 0;                       // rows with an n-gram rule: > 0 adds the ban kernel in front of the per-row stage
+    // stop strings (dots_set_row_stop): the automata created on this engine (device tables; rows = how many rows hold each) and
+    // — allocated by the first row that takes one — the row table.  row_stop[row] = automaton id + 1, 0 = none; row_stop_min its min_tokens.
+    struct Stop { uint16_t* table = nullptr; uint16_t* match_len = nullptr; uint8_t* match_id = nullptr; int n_states = 0, rows = 0; };
+    std::vector<Stop> stops;
+    RowStop* d_stop = nullptr;
+    int row_stop[DOTS_MAX_BATCH] = {0};
+    int row_stop_min[DOTS_MAX_BATCH] = {0};
+    int n_stop_rows = 0;                   // rows with stop strings: they are selected by the per-row stage, whose commit walks the automaton
     // log-probabilities (dots_set_row_logprobs): top_n per row (-1 = off) on the device and its host mirror; the outputs
     // ([max_batch][max_seq_len] positions) and the stage's scratch are allocated by the first row switched on
     int32_t* d_row_lp = nullptr;
@@ -930,7 +938,10 @@ int select_tokens(DotsEngine* e, int advance) {
     if (e->n_lp > 0) CK(launch_logprob_partial(e->stream, e->d_logits, c.vocab_size, c.vocab_size, e->B_sel, ls));
     if (e->n_own > 0) {          // per-row stage for the rows with their own parameters (+ the greedy rows that follow the engine)
         RowSel rs{e->d_rowp, e->d_row_own, e->pen_cnt, e->pen_seen, e->pen_logits, e->d_row_thr, e->temperature > 0.f ? 0 : 1,
-                  e->n_rules > 0 ? e->d_rules : nullptr, e->rule_img, GuideSel{}, NgramSel{}};
+                  e->n_rules > 0 ? e->d_rules : nullptr, e->rule_img, GuideSel{}, NgramSel{}, StopSel{}};
+        // the stop-string rows' table, once any row has held one (allocating it drops the captured steps, so no cache key changes): the
+        // commit of a row that holds an automaton walks it, no launch is added
+        if (e->d_stop) rs.stop = StopSel{e->d_stop, e->tok_off, e->tok_bytes, c.vocab_size, 0};
         if (e->n_ngram > 0) {        // the n-gram rows' banned bits from their own output so far, before the stage reads the logits
             rs.ngram = NgramSel{e->d_ngram, e->ngram_mask, ngram_mask_words(c.vocab_size), c.vocab_size};
             CK(launch_ngram_ban(e->stream, rs.ngram, e->B_sel, st.out_ids, st.out_lens, st.out_stride, st.finished, st.sel));
@@ -1017,13 +1028,21 @@ int ensure_ngram_state(DotsEngine* e) {
     return DOTS_OK;
 }
 
+// row table of the stop strings, allocated by the first row that takes an automaton
+int ensure_stop_state(DotsEngine* e) {
+    if (e->d_stop) return DOTS_OK;
+    CK(e->alloc(&e->d_stop, DOTS_MAX_BATCH));              // zeroed by alloc(): no row holds an automaton
+    drop_step_graphs(e);                                   // graphs captured before hold no stop table
+    return DOTS_OK;
+}
+
 // what a row without parameters of its own is selected with once the per-row stage owns it (logit rules): the engine-wide setting as it stands
 RowParams engine_row_params(const DotsEngine* e) { return RowParams{e->temperature, e->top_p, 0, 1.f, 0.f, 0.f, e->seed}; }
 
 // the row's entry back to the engine-wide setting (stream ordered); a row that still carries logit rules stays with the per-row stage
 int clear_row(DotsEngine* e, int row) {
     if (!e->row_own[row]) return DOTS_OK;
-    if (e->row_rules[row] || e->row_guide[row] || e->row_ngram[row]) {
+    if (e->row_rules[row] || e->row_guide[row] || e->row_ngram[row] || e->row_stop[row]) {
         CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, engine_row_params(e), 1));
         e->row_own[row] = 0;
         return DOTS_OK;
@@ -1040,7 +1059,7 @@ int clear_row_rules(DotsEngine* e, int row) {
     CK(launch_set_row_rules(e->stream, e->d_rules, e->rule_img, row, e->cfg.vocab_size, RowRules{}, nullptr, 0, nullptr, nullptr, 0));
     e->row_rules[row] = 0;
     e->n_rules -= 1;
-    if (!e->row_own[row] && !e->row_guide[row] && !e->row_ngram[row]) {
+    if (!e->row_own[row] && !e->row_guide[row] && !e->row_ngram[row] && !e->row_stop[row]) {
         CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, RowParams{}, 0));
         e->n_own -= 1;
     }
@@ -1054,7 +1073,7 @@ int clear_row_guide(DotsEngine* e, int row) {
     e->guides[e->row_guide[row] - 1].rows -= 1;
     e->row_guide[row] = 0;
     e->n_guided -= 1;
-    if (!e->row_own[row] && !e->row_rules[row] && !e->row_ngram[row]) {
+    if (!e->row_own[row] && !e->row_rules[row] && !e->row_ngram[row] && !e->row_stop[row]) {
         CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, RowParams{}, 0));
         e->n_own -= 1;
     }
@@ -1067,10 +1086,44 @@ int clear_row_ngram(DotsEngine* e, int row) {
     CK(launch_set_row_ngram(e->stream, e->d_ngram, row, RowNgram{}));
     e->row_ngram[row] = 0;
     e->n_ngram -= 1;
-    if (!e->row_own[row] && !e->row_rules[row] && !e->row_guide[row]) {
+    if (!e->row_own[row] && !e->row_rules[row] && !e->row_guide[row] && !e->row_stop[row]) {
         CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, RowParams{}, 0));
         e->n_own -= 1;
     }
+    return DOTS_OK;
+}
+
+// the row's stop strings off (stream ordered)
+int clear_row_stop(DotsEngine* e, int row) {
+    if (!e->row_stop[row]) return DOTS_OK;
+    CK(launch_set_row_stop(e->stream, e->d_stop, row, RowStop{}));
+    e->stops[e->row_stop[row] - 1].rows -= 1;
+    e->row_stop[row] = 0;
+    e->row_stop_min[row] = 0;
+    e->n_stop_rows -= 1;
+    if (!e->row_own[row] && !e->row_rules[row] && !e->row_guide[row] && !e->row_ngram[row]) {
+        CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, RowParams{}, 0));
+        e->n_own -= 1;
+    }
+    return DOTS_OK;
+}
+
+// row `row` holds automaton id (a live one) from the root with no hit (stream ordered); the row goes to the per-row stage
+int assign_row_stop(DotsEngine* e, int row, int id, int min_tokens) {
+    RET(ensure_row_table(e));
+    RET(ensure_stop_state(e));
+    const DotsEngine::Stop& a = e->stops[id];
+    CK(launch_set_row_stop(e->stream, e->d_stop, row, RowStop{a.table, a.match_len, a.match_id, a.n_states, 0, min_tokens, -1, 0, 0, -1, 0}));
+    if (!e->row_own[row] && !e->row_rules[row] && !e->row_guide[row] && !e->row_ngram[row] && !e->row_stop[row])
+        CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, engine_row_params(e), 1));
+    if (e->row_stop[row]) e->stops[e->row_stop[row] - 1].rows -= 1;
+    else {
+        e->n_stop_rows += 1;
+        if (!e->row_own[row] && !e->row_rules[row] && !e->row_guide[row] && !e->row_ngram[row]) e->n_own += 1;
+    }
+    e->row_stop[row] = id + 1;
+    e->row_stop_min[row] = min_tokens;
+    e->stops[id].rows += 1;
     return DOTS_OK;
 }
 
@@ -1421,6 +1474,8 @@ int prefill(DotsEngine* e, const int32_t* ids, const int32_t* lens, int B, const
     if (e->pen_cnt) CK(launch_pen_prompt(s, e->p_src, e->p_last, slots ? e->p_dst : nullptr, B, c.image_token_id, c.vocab_size, e->pen_cnt, e->pen_seen));
     // the automata of the prefilled rows that hold a guide start over: the first token is already selected under the guide
     if (e->n_guided > 0) CK(launch_guide_reset_rows(s, e->d_guides, slots ? e->p_dst : nullptr, B));
+    // so do the stop automata of the prefilled rows, and their hit records are cleared: the first token's bytes are the first ones walked
+    if (e->n_stop_rows > 0) CK(launch_stop_reset_rows(s, e->d_stop, slots ? e->p_dst : nullptr, B));
     // last position of every sequence -> final norm -> lm_head -> first token
     CK(launch_gather_rows(s, e->p_x, e->p_last, slots ? e->p_dst : nullptr, e->d_h, B, H));
     CK(launch_dec_lmhead(s, e->d_h, e->final_norm, e->lm_head_d, e->lm_head_s, e->d_logits, rows, H, c.vocab_size, c.rms_norm_eps));
@@ -1829,7 +1884,7 @@ int dots_generate(DotsEngine* e, const int32_t* input_ids, const int32_t* prompt
         if (exec) CK(hipGraphLaunch(cur != s && exec_part ? exec_part : exec, cur));
         else RET(decode_step_launches(e, n_splits));
         ++steps;
-        if (n_eos && (step % 16 == 0)) {       // early exit once every sequence hit EOS
+        if ((n_eos || e->n_stop_rows > 0) && (step % 16 == 0)) {       // early exit once every sequence hit EOS (or its stop string)
             CK(hipMemcpyAsync(fin.data(), e->finished, B * 4, hipMemcpyDeviceToHost, cur));
             CK(hipStreamSynchronize(cur));
             bool all = true;
@@ -1976,6 +2031,25 @@ int dots_slots_fork(DotsEngine* e, int src_slot, const int32_t* dst_slots, int n
         for (int i = 0; i < n; ++i) CK(launch_pen_prompt(s, src0, fk_last, fk_dst + i, 1, c.image_token_id, V, e->pen_cnt, e->pen_seen));
     }
     if (e->n_guided > 0) CK(launch_guide_reset_rows(s, e->d_guides, fk_dst, n));
+    if (e->row_stop[src_slot]) {
+        // the children inherit the source's stop strings (automaton and min_tokens) at the root with no hit; like every row that holds an
+        // automaton they are selected by the per-row stage
+        const int id = e->row_stop[src_slot] - 1;
+        for (int i = 0; i < n; ++i) {
+            const int d = dst_slots[i];
+            const bool staged = e->row_own[d] || e->row_rules[d] || e->row_guide[d] || e->row_ngram[d] || e->row_stop[d];
+            if (!staged) {
+                CK(launch_set_row_params(s, e->d_rowp, e->d_row_own, d, engine_row_params(e), 1));
+                e->n_own += 1;
+            }
+            if (e->row_stop[d]) e->stops[e->row_stop[d] - 1].rows -= 1; else e->n_stop_rows += 1;
+            e->row_stop[d] = id + 1;
+            e->row_stop_min[d] = e->row_stop_min[src_slot];
+            e->stops[id].rows += 1;
+        }
+        CK(launch_stop_fork_rows(s, e->d_stop, src_slot, fk_dst, n));
+    } else if (e->n_stop_rows > 0)
+        CK(launch_stop_reset_rows(s, e->d_stop, fk_dst, n));
     CK(hipStreamSynchronize(s));                           // L, cap and the staged arrays are stack variables
     // ---- the children's first tokens: the selection stage over a mask of the children only
     e->B_sel = rows;
@@ -2024,6 +2098,11 @@ int dots_slots_reset(DotsEngine* e) {
     if (e->d_ngram) CK(hipMemsetAsync(e->d_ngram, 0, DOTS_MAX_BATCH * sizeof(RowNgram), s));
     std::fill(e->row_ngram, e->row_ngram + DOTS_MAX_BATCH, 0);
     e->n_ngram = 0;
+    if (e->d_stop) CK(hipMemsetAsync(e->d_stop, 0, DOTS_MAX_BATCH * sizeof(RowStop), s));
+    std::fill(e->row_stop, e->row_stop + DOTS_MAX_BATCH, 0);
+    std::fill(e->row_stop_min, e->row_stop_min + DOTS_MAX_BATCH, 0);
+    for (auto& a : e->stops) a.rows = 0;
+    e->n_stop_rows = 0;
     if (e->d_row_lp) CK(hipMemsetAsync(e->d_row_lp, 0xFF, DOTS_MAX_BATCH * 4, s));
     std::fill(e->row_lp, e->row_lp + DOTS_MAX_BATCH, -1);
     e->n_lp = 0;
@@ -2158,6 +2237,7 @@ int dots_slot_release(DotsEngine* e, int slot) {
     RET(clear_row_rules(e, slot));
     RET(clear_row_guide(e, slot));
     RET(clear_row_ngram(e, slot));
+    RET(clear_row_stop(e, slot));
     RET(set_row_lp(e, slot, -1));
     e->slot_active[slot] = 0;
     e->sel_dirty = true;
@@ -2298,7 +2378,7 @@ int dots_set_row_sampling(DotsEngine* e, int row, const DotsSamplingParams* p) {
     RET(ensure_row_table(e));
     if (rp.repetition_penalty != 1.f || rp.frequency_penalty != 0.f || rp.presence_penalty != 0.f) RET(ensure_pen_state(e));
     CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, rp, 1));
-    if (!e->row_own[row]) { e->row_own[row] = 1; e->n_own += (e->row_rules[row] || e->row_guide[row] || e->row_ngram[row]) ? 0 : 1; }
+    if (!e->row_own[row]) { e->row_own[row] = 1; e->n_own += (e->row_rules[row] || e->row_guide[row] || e->row_ngram[row] || e->row_stop[row]) ? 0 : 1; }
     return DOTS_OK;
 }
 
@@ -2331,7 +2411,7 @@ int dots_set_row_logit_rules(DotsEngine* e, int row, const DotsLogitRules* r) {
     if (!e->row_rules[row]) {
         e->row_rules[row] = 1;
         e->n_rules += 1;
-        if (!e->row_own[row] && !e->row_guide[row] && !e->row_ngram[row]) e->n_own += 1;
+        if (!e->row_own[row] && !e->row_guide[row] && !e->row_ngram[row] && !e->row_stop[row]) e->n_own += 1;
     }
     return DOTS_OK;
 }
@@ -2345,6 +2425,7 @@ int dots_set_token_bytes(DotsEngine* e, const int32_t* offsets, const uint8_t* b
     const size_t n = (size_t)offsets[V];
     if (n && !bytes) return e->fail(DOTS_E_INVALID, "null argument");
     if (e->n_guided > 0) return e->fail(DOTS_E_STATE, "token bytes cannot change while %d row(s) hold a guide", e->n_guided);
+    if (e->n_stop_rows > 0) return e->fail(DOTS_E_STATE, "token bytes cannot change while %d row(s) hold stop strings", e->n_stop_rows);
     CK(hipSetDevice(e->device));
     CK(hipStreamSynchronize(e->stream));                   // nothing in flight reads the previous image
     if (e->tok_off) { e->release(e->tok_off); e->tok_off = nullptr; }
@@ -2406,12 +2487,12 @@ int dots_set_row_guide(DotsEngine* e, int row, int32_t id) {
     RET(ensure_guide_state(e));
     const DotsEngine::Guide& g = e->guides[id];
     CK(launch_set_row_guide(e->stream, e->d_guides, row, RowGuide{g.table, g.accepting, g.n_states, g.start, g.start, 0}));
-    if (!e->row_own[row] && !e->row_rules[row] && !e->row_guide[row] && !e->row_ngram[row])
+    if (!e->row_own[row] && !e->row_rules[row] && !e->row_guide[row] && !e->row_ngram[row] && !e->row_stop[row])
         CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, engine_row_params(e), 1));
     if (e->row_guide[row]) e->guides[e->row_guide[row] - 1].rows -= 1;
     else {
         e->n_guided += 1;
-        if (!e->row_own[row] && !e->row_rules[row] && !e->row_ngram[row]) e->n_own += 1;
+        if (!e->row_own[row] && !e->row_rules[row] && !e->row_ngram[row] && !e->row_stop[row]) e->n_own += 1;
     }
     e->row_guide[row] = id + 1;
     e->guides[id].rows += 1;
@@ -2428,13 +2509,85 @@ int dots_set_row_ngram(DotsEngine* e, int row, const DotsNgramRule* r) {
     RET(ensure_row_table(e));
     RET(ensure_ngram_state(e));
     CK(launch_set_row_ngram(e->stream, e->d_ngram, row, rn));
-    if (!e->row_own[row] && !e->row_rules[row] && !e->row_guide[row] && !e->row_ngram[row])
+    if (!e->row_own[row] && !e->row_rules[row] && !e->row_guide[row] && !e->row_ngram[row] && !e->row_stop[row])
         CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, engine_row_params(e), 1));
     if (!e->row_ngram[row]) {
         e->row_ngram[row] = 1;
         e->n_ngram += 1;
-        if (!e->row_own[row] && !e->row_rules[row] && !e->row_guide[row]) e->n_own += 1;
+        if (!e->row_own[row] && !e->row_rules[row] && !e->row_guide[row] && !e->row_stop[row]) e->n_own += 1;
     }
+    return DOTS_OK;
+}
+
+// ---------------------------------------------------------------------------------- stop strings
+int dots_stop_create(DotsEngine* e, const uint16_t* table, int n_states, const uint16_t* match_len, const uint8_t* match_id, int32_t* handle_out) {
+    if (!e || !table || !match_len || !match_id || !handle_out) return e ? e->fail(DOTS_E_INVALID, "null argument") : DOTS_E_INVALID;
+    if (!e->tok_off) return e->fail(DOTS_E_STATE, "the token bytes are not set (dots_set_token_bytes): a stop string cannot be matched");
+    if (n_states < 1 || n_states > STOP_MAX_STATES) return e->fail(DOTS_E_INVALID, "stop strings: n_states must be in [1, %d]", STOP_MAX_STATES);
+    for (size_t i = 0; i < (size_t)n_states * 256; ++i)
+        if (table[i] >= n_states)
+            return e->fail(DOTS_E_INVALID, "stop strings: state %zu, byte %zu leads to state %d outside [0, %d)", i / 256, i % 256, (int)table[i], n_states);
+    for (int i = 0; i < n_states; ++i)
+        if (match_len[i] > DOTS_MAX_STOP_BYTES || (match_len[i] && match_id[i] >= DOTS_MAX_STOP_STRINGS))
+            return e->fail(DOTS_E_INVALID, "stop strings: state %d matches %d bytes of string %d (at most %d bytes, %d strings)", i, (int)match_len[i],
+                           (int)match_id[i], DOTS_MAX_STOP_BYTES, DOTS_MAX_STOP_STRINGS);
+    if (match_len[0]) return e->fail(DOTS_E_INVALID, "stop strings: the root state cannot end a string");
+    CK(hipSetDevice(e->device));
+    DotsEngine::Stop a;
+    a.n_states = n_states;
+    CK(e->alloc(&a.table, (size_t)n_states * 256));
+    CK(hipMemcpyAsync(a.table, table, (size_t)n_states * 512, hipMemcpyHostToDevice, e->stream));
+    CK(e->alloc(&a.match_len, (size_t)n_states));
+    CK(hipMemcpyAsync(a.match_len, match_len, (size_t)n_states * 2, hipMemcpyHostToDevice, e->stream));
+    CK(e->alloc(&a.match_id, (size_t)n_states));
+    CK(hipMemcpyAsync(a.match_id, match_id, (size_t)n_states, hipMemcpyHostToDevice, e->stream));
+    CK(hipStreamSynchronize(e->stream));                   // the caller's arrays are free again
+    size_t id = 0;
+    while (id < e->stops.size() && e->stops[id].table) ++id;            // a destroyed automaton's id is reused
+    if (id == e->stops.size()) e->stops.push_back(a); else e->stops[id] = a;
+    *handle_out = (int32_t)id + 1;
+    return DOTS_OK;
+}
+
+int dots_stop_destroy(DotsEngine* e, int32_t handle) {
+    if (!e) return DOTS_E_INVALID;
+    if (!e->tok_off) return e->fail(DOTS_E_STATE, "the token bytes are not set (dots_set_token_bytes): no stop automaton exists");
+    const int id = handle - 1;
+    if (id < 0 || id >= (int)e->stops.size() || !e->stops[id].table) return e->fail(DOTS_E_INVALID, "no stop automaton %d", handle);
+    if (e->stops[id].rows > 0)
+        return e->fail(DOTS_E_STATE, "stop automaton %d is held by %d row(s): clear them first (dots_set_row_stop(row, 0, 0))", handle, e->stops[id].rows);
+    CK(hipSetDevice(e->device));
+    CK(hipStreamSynchronize(e->stream));                   // steps in flight may still walk its table
+    e->release(e->stops[id].table);
+    e->release(e->stops[id].match_len);
+    e->release(e->stops[id].match_id);
+    e->stops[id] = DotsEngine::Stop{};
+    return DOTS_OK;
+}
+
+int dots_set_row_stop(DotsEngine* e, int row, int32_t handle, int min_tokens) {
+    if (!e) return DOTS_E_INVALID;
+    if (!e->tok_off) return e->fail(DOTS_E_STATE, "the token bytes are not set (dots_set_token_bytes): a stop string cannot be matched");
+    if (row < 0 || row >= e->cfg.max_batch) return e->fail(DOTS_E_INVALID, "row %d out of range [0, %d)", row, e->cfg.max_batch);
+    CK(hipSetDevice(e->device));
+    if (handle == 0) return e->d_stop ? clear_row_stop(e, row) : DOTS_OK;
+    const int id = handle - 1;
+    if (id < 0 || id >= (int)e->stops.size() || !e->stops[id].table) return e->fail(DOTS_E_INVALID, "no stop automaton %d", handle);
+    if (min_tokens < 0) return e->fail(DOTS_E_INVALID, "stop strings: min_tokens must be >= 0");
+    return assign_row_stop(e, row, id, min_tokens);
+}
+
+int dots_row_stop_hit(DotsEngine* e, int row, int32_t* out) {
+    if (!e || !out) return e ? e->fail(DOTS_E_INVALID, "null argument") : DOTS_E_INVALID;
+    if (!e->tok_off) return e->fail(DOTS_E_STATE, "the token bytes are not set (dots_set_token_bytes): no row holds stop strings");
+    if (row < 0 || row >= e->cfg.max_batch) return e->fail(DOTS_E_INVALID, "row %d out of range [0, %d)", row, e->cfg.max_batch);
+    out[0] = -1; out[1] = 0; out[2] = 0; out[3] = -1;
+    if (!e->d_stop || !e->row_stop[row]) return DOTS_OK;
+    CK(hipSetDevice(e->device));
+    RowStop rs;
+    CK(hipMemcpyAsync(&rs, e->d_stop + row, sizeof(rs), hipMemcpyDeviceToHost, e->stream));
+    CK(hipStreamSynchronize(e->stream));
+    if (rs.hit_tok >= 0) { out[0] = rs.hit_tok; out[1] = rs.hit_bytes; out[2] = rs.hit_len; out[3] = rs.hit_id; }
     return DOTS_OK;
 }
 

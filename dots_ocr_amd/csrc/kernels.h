@@ -164,6 +164,26 @@ struct RowNgram { int32_t n, window, n_white, white[DOTS_MAX_NGRAM_WHITELIST]; }
 struct NgramSel { const RowNgram* rows; uint32_t* mask; int32_t words, V; };
 inline int ngram_mask_words(int V) { return (V + 31) / 32; }
 constexpr int NGRAM_MAX_V = 64 * 1024 * 8;     // the banned bits of one row are built in LDS: 64 KB per workgroup
+// Stop strings.  A stop automaton is the Aho-Corasick automaton of a row's stop strings with its failure links folded into a
+// dense byte DFA in device memory: table [n_states][256] uint16 (every entry < n_states: there is no dead state; state 0 is the root),
+// match_len [n_states] uint16 (bytes of the longest listed string that ends at the state, 0: none) and match_id [n_states] uint8 (its index
+// in the caller's list).  RowStop: the automaton a row holds (table == nullptr: none), the state it is in, and the hit record the commit
+// that finishes the row leaves (hit_tok == -1: no hit yet; step_dev.h stop_walk).  StopSel: what a launch of the per-row stage needs — the
+// row table and the packed bytes of every vocabulary entry.  rows == nullptr = no row of this engine ever held stop strings.
+#ifndef DOTS_MAX_STOP_STRINGS
+#define DOTS_MAX_STOP_STRINGS 16
+#endif
+#ifndef DOTS_MAX_STOP_BYTES
+#define DOTS_MAX_STOP_BYTES 64
+#endif
+constexpr int STOP_MAX_STATES = DOTS_MAX_STOP_STRINGS * DOTS_MAX_STOP_BYTES + 1;
+struct RowStop {
+    const uint16_t* table;
+    const uint16_t* match_len;
+    const uint8_t* match_id;
+    int32_t n_states, state, min_tokens, hit_tok, hit_bytes, hit_len, hit_id, _pad;
+};
+struct StopSel { RowStop* rows; const int32_t* tok_off; const uint8_t* tok_bytes; int32_t V, _pad; };
 struct RowSel {
     const RowParams* params;
     const int32_t* own;
@@ -176,6 +196,7 @@ struct RowSel {
     const float* rule_img;      // [rows][V] fp32: the bias of a token, -inf for a banned / not allowed one, 0 elsewhere
     GuideSel guide;             // guide.rows == nullptr = no row of this launch is guided
     NgramSel ngram;             // ngram.rows == nullptr = no row of this launch carries an n-gram rule
+    StopSel stop;               // stop.rows == nullptr = no row of this engine ever held stop strings
 };
 // pval / pidx: ARGMAX_CHUNKS (64) partials per row, as launch_argmax_step
 hipError_t launch_select_rows(hipStream_t s, const float* logits, int V, int ld, int B, const RowSel& rs, float* pval, int32_t* pidx, const StepState& st);
@@ -216,6 +237,13 @@ hipError_t launch_set_row_ngram(hipStream_t s, RowNgram* table, int row, const R
 // in out_lens (explicit histories of dots_op_select_tokens_ngram; out_stride >= stride)
 hipError_t launch_ngram_history(hipStream_t s, const int32_t* hist, const int32_t* hist_lens, int stride, const int32_t* n_prompt, int B,
                                 int32_t* out_ids, int out_stride);
+// ---- stop.hip: stop strings, the stream-ordered writers of the row table (the walk itself is step_dev.h stop_walk)
+// table[row] = r with the automaton at the root and no hit (r.table == nullptr: the row holds none)
+hipError_t launch_set_row_stop(hipStream_t s, RowStop* table, int row, const RowStop& r);
+// root state and no hit for the n rows dst[0 .. n) (dst == nullptr: rows 0 .. n - 1) that hold an automaton, in stream order (a prefill)
+hipError_t launch_stop_reset_rows(hipStream_t s, RowStop* table, const int32_t* dst, int n);
+// table[dst[i]] = table[src] at the root with no hit, i < n (dots_slots_fork: the children inherit the source's automaton and min_tokens)
+hipError_t launch_stop_fork_rows(hipStream_t s, RowStop* table, int src, const int32_t* dst, int n);
 // ---- spec.hip: n-gram speculative decoding of greedy rows
 // A speculating step runs over R = rows x (k + 1) rows, draft-major: row j * rows + b carries token j of (last token, draft 1 .. k) of slot
 // b at context ctx + j on the slot's own KV pages.  SpecState: the slots' drafts of the next step (drafts [DOTS_MAX_BATCH]

@@ -6,6 +6,26 @@
 
 constexpr int ARGMAX_CHUNKS = 64;
 
+// The walk of a row's stop automaton over the bytes of token `tok`, which the row just appended at output index n.  At the first byte where
+// a listed string ends (match_len[state] > 0) with n >= min_tokens: the hit record is written, the row is finished, the walk ends.  Below
+// min_tokens the automaton still advances, so a string that straddles the boundary is found.  A token without bytes moves nothing.
+DEVI void stop_walk(const StopSel& ss, const StepState& st, int b, int tok, int n) {
+    RowStop& rs = ss.rows[b];
+    if (!rs.table || tok < 0 || tok >= ss.V) return;
+    uint32_t s = (uint32_t)rs.state < (uint32_t)rs.n_states ? (uint32_t)rs.state : 0u;
+    const int j0 = ss.tok_off[tok], end = ss.tok_off[tok + 1];
+    for (int j = j0; j < end; ++j) {
+        s = rs.table[(size_t)s * 256 + ss.tok_bytes[j]];              // every entry < n_states (checked at dots_stop_create)
+        const int len = rs.match_len[s];
+        if (len > 0 && n >= rs.min_tokens) {
+            rs.hit_tok = n; rs.hit_bytes = j - j0 + 1; rs.hit_len = len; rs.hit_id = rs.match_id[s];
+            st.finished[b] = 1;
+            break;
+        }
+    }
+    rs.state = (int32_t)s;
+}
+
 // Commit one selected token of row (slot) b: append to its output, EOS / length bookkeeping, next-step input.
 // A finished row keeps decoding (fixed-shape graph) but its context is frozen, so it rewrites the same KV position for ever
 // and can idle in its slot until the host refills it (continuous batching).
@@ -14,7 +34,10 @@ constexpr int ARGMAX_CHUNKS = 64;
 // guide: the launch's guides (per-row stage only) or nullptr.  A guided row that is not finished advances its automaton by the
 // bytes of the committed token; an EOS or stop id moves nothing and finishes the row, RULE_IGNORE_EOS or not (the guide allowed it because
 // the state is accepting; with nothing else left to allow, a row that ignored it could only repeat it).
-DEVI void commit_token(const StepState& st, int b, int tok, const RowRules* rules = nullptr, const GuideSel* guide = nullptr) {
+// stop: the engine's stop-string rows (per-row stage only) or nullptr.  A row that holds an automaton and is not finished walks
+// the bytes of the committed token (stop_walk); an EOS or stop id is not walked.
+DEVI void commit_token(const StepState& st, int b, int tok, const RowRules* rules = nullptr, const GuideSel* guide = nullptr,
+                       const StopSel* stop = nullptr) {
     const bool done = st.finished[b] != 0;
     if (st.advance_ctx && !done) st.ctx_len[b] += 1;
     if (!done) {
@@ -35,6 +58,7 @@ DEVI void commit_token(const StepState& st, int b, int tok, const RowRules* rule
                 s = rg.table[(size_t)s * 256 + guide->tok_bytes[j]];
             if (s != GUIDE_DEAD) rg.state = (int32_t)s;              // a token the guide did not allow (the all -inf fallback) moves nothing
         }
+        if (stop && !eos) stop_walk(*stop, st, b, tok, n);
         if (eos || n + 1 >= cap) st.finished[b] = 1;
     }
     st.cur_tokens[b] = tok;

@@ -8,6 +8,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 import os
+from collections import OrderedDict
 from dataclasses import dataclass
 from typing import Dict, Optional, Sequence
 
@@ -107,6 +108,8 @@ class SamplingParams:
 
 MAX_LOGIT_BIAS = 1024                        # DOTS_MAX_LOGIT_BIAS: (id, value) pairs per row
 MAX_STOP_IDS = 16                            # DOTS_MAX_STOP_IDS: stop ids per row
+MAX_STOP_STRINGS = 16                        # DOTS_MAX_STOP_STRINGS: stop strings per row
+MAX_STOP_BYTES = 64                          # DOTS_MAX_STOP_BYTES: UTF-8 bytes of one stop string; so at most 16 x 64 + 1 = 1025 states
 
 
 class CDotsLogitRules(C.Structure):
@@ -378,6 +381,10 @@ def _prototypes(lib):
         "dots_op_select_tokens_ngram": (i32, [vp, vp, i32, i32, P(CDotsSamplingParams), P(CDotsLogitRules), P(CDotsNgramRule), vp, vp, i32, vp, vp]),
         "dots_bench_select_tokens_ngram": (i32, [vp, vp, i32, i32, P(CDotsSamplingParams), P(CDotsLogitRules), P(CDotsNgramRule), vp, vp, i32, vp, i32,
                                                  P(f32)]),
+        "dots_stop_create": (i32, [vp, vp, i32, vp, vp, P(i32)]),
+        "dots_stop_destroy": (i32, [vp, i32]),
+        "dots_set_row_stop": (i32, [vp, i32, i32, i32]),
+        "dots_row_stop_hit": (i32, [vp, i32, P(i32)]),
         "dots_set_speculation": (i32, [vp, i32, i32, i32]),
         "dots_set_row_drafts": (i32, [vp, i32, P(i32), i32]),
         "dots_spec_stats": (i32, [vp, i32, P(i64), P(i64), P(i64)]),
@@ -415,6 +422,7 @@ EXPORTED_SYMBOLS = [
     "dots_set_row_ngram", "dots_op_select_tokens_ngram", "dots_bench_select_tokens_ngram",
     "dots_set_speculation", "dots_set_row_drafts", "dots_spec_stats", "dots_op_ngram_draft",
     "dots_slots_fork",
+    "dots_stop_create", "dots_stop_destroy", "dots_set_row_stop", "dots_row_stop_hit",
 ]
 
 MAX_SPEC_DRAFTS = 15                         # DOTS_MAX_SPEC_DRAFTS: drafts per slot and step
@@ -526,6 +534,7 @@ class Engine:
             raise DotsEngineError(f"dots_create failed ({rc}): {self.lib.dots_last_error(None).decode()}")
         self.h = h
         self.token_bytes = None                  # guided.TokenBytes once set_token_bytes has run
+        self._stops = OrderedDict()              # tuple of stop strings -> handle (create_stop): a small LRU of uploaded automata
 
     # ------------------------------------------------------------------ plumbing
     def _ck(self, rc: int, what: str):
@@ -787,6 +796,56 @@ class Engine:
         st = C.c_int32(-1)
         self._ck(self.lib.dots_row_guide_state(self.h, int(row), C.byref(st)), "dots_row_guide_state")
         return int(st.value)
+
+    # ------------------------------------------------------------------ stop strings
+    STOP_CACHE = 32                              # automata kept on the engine, keyed by their strings
+
+    def create_stop(self, strings) -> int:
+        """Upload the automaton of 1 .. 16 stop strings (a list of str, or a stop_strings.StopAutomaton); returns the handle set_row_stop
+        takes.  Handles are cached by the tuple of strings, so a server does not upload half a megabyte per request; the least recently
+        used automaton no row holds is freed when the cache is full.  Needs set_token_bytes first; bad strings raise ValueError."""
+        from .stop_strings import StopAutomaton, compile_stop
+        key = strings.strings if isinstance(strings, StopAutomaton) else None
+        if key is None:
+            from .stop_strings import check_stop_strings
+            key = check_stop_strings(strings)
+        h = self._stops.get(key)
+        if h is not None:
+            self._stops.move_to_end(key)
+            return h
+        a = strings if isinstance(strings, StopAutomaton) else compile_stop(key)
+        table = np.ascontiguousarray(a.table, dtype=np.uint16)
+        mlen = np.ascontiguousarray(a.match_len, dtype=np.uint16)
+        mid = np.ascontiguousarray(a.match_id, dtype=np.uint8)
+        if table.ndim != 2 or table.shape[1] != 256 or mlen.shape != (table.shape[0],) or mid.shape != mlen.shape:
+            raise ValueError("a stop automaton's table must be uint16 [S, 256] with match_len uint16 [S] and match_id uint8 [S]")
+        hid = C.c_int32(0)
+        self._ck(self.lib.dots_stop_create(self.h, table.ctypes.data_as(C.c_void_p), int(table.shape[0]), mlen.ctypes.data_as(C.c_void_p),
+                                           mid.ctypes.data_as(C.c_void_p), C.byref(hid)), "dots_stop_create")
+        for old in list(self._stops)[:max(0, len(self._stops) + 1 - self.STOP_CACHE)]:
+            if self.lib.dots_stop_destroy(self.h, int(self._stops[old])) == 0:       # refused while a row holds it: it stays cached
+                del self._stops[old]
+        self._stops[key] = int(hid.value)
+        return int(hid.value)
+
+    def destroy_stop(self, handle: int):
+        """Free an automaton; refused (DotsEngineError) while a row holds it."""
+        self._ck(self.lib.dots_stop_destroy(self.h, int(handle)), "dots_stop_destroy")
+        for k in [k for k, h in self._stops.items() if h == int(handle)]:
+            del self._stops[k]
+
+    def set_row_stop(self, row: int, handle: Optional[int], min_tokens: int = 0):
+        """Row `row` (a slot, or sequence `row` of a static batch) ends at the token that completes one of the automaton's strings, taken
+        only at token index >= min_tokens (set, then prefill: the prefill starts the automaton over, clears the hit and walks its first
+        token); None or 0 clears.  Captured decode graphs are kept; slot release and slots_reset clear the row, slots_fork hands the
+        source's automaton to its children."""
+        self._ck(self.lib.dots_set_row_stop(self.h, int(row), int(handle or 0), int(min_tokens)), "dots_set_row_stop")
+
+    def row_stop_hit(self, row: int):
+        """(token index, bytes of that token consumed, match length in bytes, match id) of the row's stop, or None: no hit (yet)"""
+        out = (C.c_int32 * 4)(-1, 0, 0, -1)
+        self._ck(self.lib.dots_row_stop_hit(self.h, int(row), out), "dots_row_stop_hit")
+        return None if out[0] < 0 else (int(out[0]), int(out[1]), int(out[2]), int(out[3]))
 
     def _guided_args(self, B, params, rules, n_gen, guides, states):
         if len(params) != B or len(rules) != B or len(guides) != B or len(states) != B:

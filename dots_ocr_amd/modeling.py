@@ -135,7 +135,7 @@ class DotsOcrHipForCausalLM:
                  stop_token_ids=None, ignore_eos: bool = False, guided_regex=None, guided_choice=None, guided_json=None,
                  guided_whitespace_pattern=None, no_repeat_ngram_size: Optional[int] = None, no_repeat_ngram_window: Optional[int] = None,
                  no_repeat_ngram_whitelist=None, speculative_ngram: Optional[int] = None, prompt_lookup_min: int = 2, prompt_lookup_max: int = 4,
-                 num_return_sequences: int = 1, **_):
+                 num_return_sequences: int = 1, stop_strings=None, **_):
         """HF-shaped generate.  do_sample / temperature / top_p default to the checkpoint's generation_config.json (greedy when it
         is absent); with sampling on, tokens are drawn on the GPU from softmax(logits / temperature) restricted to the top_p
         nucleus, reproducibly from `seed`.  Returns LongTensor
@@ -167,6 +167,11 @@ class DotsOcrHipForCausalLM:
         sequence verifies up to k drafted tokens per decode step, max_batch // (k + 1) sequences at a time.  The tokens are exactly
         those of the call without it; sampled or rule-carrying sequences simply run unspeculated.  The engine is left with speculation
         off.
+
+        stop_strings (HF's name: a str or a list of at most 16 str of at most 64 UTF-8 bytes) ends a sequence on the GPU at the token that
+        completes one of them in its generated text (Engine.set_row_stop; with min_tokens, no match is taken below it).  The
+        returned ids end at that token, as HF's do; cutting the TEXT at the match is the caller's (stop_strings.cut_text).  The engine
+        needs its token bytes first (Engine.set_token_bytes).
 
         num_return_sequences (n >= 1, HF's name) returns n sequences per prompt from one vision tower and one prefill of it (parallel
         sampling: Engine.slots_fork): LongTensor [B * n, T + new], row i * n + j = sequence j of prompt i as HF lays it out,
@@ -227,6 +232,18 @@ class DotsOcrHipForCausalLM:
                     return dataclasses.replace(base, seed=int(seed) + b)
         elif no_repeat_ngram_window or no_repeat_ngram_whitelist:
             raise ValueError("no_repeat_ngram_window / no_repeat_ngram_whitelist need no_repeat_ngram_size")
+        stop = None
+        if stop_strings is not None:
+            from .stop_strings import check_stop_strings
+            stop = check_stop_strings(stop_strings)
+            if getattr(self.engine, "token_bytes", None) is None:
+                raise ValueError("stop strings need the vocabulary's bytes: call engine.set_token_bytes(...) once (DotsOcrProcessor.token_bytes)")
+            if row_sp is None:                   # a sampled row with stop strings draws with seed + b as the ruled rows do
+                from .engine import SamplingParams
+                base = SamplingParams(temperature=t_eff, top_p=p_eff, seed=seed)
+
+                def row_sp(b):
+                    return dataclasses.replace(base, seed=int(seed) + b)
         if nrs > 1:
             continuous = True
             from .engine import SamplingParams
@@ -243,7 +260,7 @@ class DotsOcrHipForCausalLM:
             self.engine.set_speculation(spec_k, int(prompt_lookup_min), int(prompt_lookup_max))
         try:
             return self._generate(input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens, eos_token_id, pad_token_id, continuous,
-                                  row_sp, rules, guide, ngram, nrs)
+                                  row_sp, rules, guide, ngram, nrs, stop, int(min_tokens or 0))
         finally:
             if spec_k:
                 try:
@@ -260,7 +277,7 @@ class DotsOcrHipForCausalLM:
                     warnings.warn(f"guide {guide} could not be destroyed: {e}")
 
     def _generate(self, input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens, eos_token_id, pad_token_id, continuous, row_sp, rules,
-                  guide, ngram=None, nrs=1):
+                  guide, ngram=None, nrs=1, stop=None, stop_min=0):
         import torch
         ids = input_ids.detach().cpu().numpy()
         B, T = ids.shape
@@ -316,10 +333,10 @@ class DotsOcrHipForCausalLM:
                     lo, hi = int(patch_off[img_of_seq[b][0]]), int(patch_off[img_of_seq[b][-1] + 1])
                     pix = pv_dev[lo:hi] if pv_dev is not None else pv_host[lo:hi]
                     reqs.append(Request(prompts[b], pix, grid[img_of_seq[b][0]:img_of_seq[b][-1] + 1], max_new_tokens,
-                                        sampling=row_sp(b) if row_sp else None, rules=rules, guide=guide, ngram=ngram, n=nrs))
+                                        sampling=row_sp(b) if row_sp else None, rules=rules, guide=guide, ngram=ngram, n=nrs, stop=stop))
                 else:
                     reqs.append(Request(prompts[b], None, None, max_new_tokens, sampling=row_sp(b) if row_sp else None, rules=rules, guide=guide,
-                                        ngram=ngram, n=nrs))
+                                        ngram=ngram, n=nrs, stop=stop))
             outs = ContinuousBatcher(self.engine, eos_ids=eos).run(reqs)
             if nrs > 1:                          # row i * n + j = sequence j of prompt i
                 outs = [o for r in reqs for o in r.outputs]
@@ -358,6 +375,8 @@ class DotsOcrHipForCausalLM:
                             self.engine.set_row_guide(j, guide)
                         if ngram is not None:
                             self.engine.set_row_ngram(j, ngram)
+                        if stop is not None:
+                            self.engine.set_row_stop(j, self.engine.create_stop(stop), stop_min)
                     rows_set = max(rows_set, len(sl))
                 lens = np.array([len(prompts[b]) for b in sl], np.int32)
                 packed = np.concatenate([prompts[b] for b in sl])
@@ -393,6 +412,8 @@ class DotsOcrHipForCausalLM:
                     self.engine.set_row_guide(j, None)
                 if ngram is not None:
                     self.engine.set_row_ngram(j, None)
+                if stop is not None:
+                    self.engine.set_row_stop(j, None)
         full = np.concatenate([np.repeat(ids.astype(np.int64), nrs, axis=0), new_tokens[:, :n_max]], axis=1)    # HF stops at the longest sequence
         res = torch.from_numpy(full)
         return res.to(input_ids.device) if input_ids.is_cuda else res

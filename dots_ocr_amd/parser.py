@@ -34,8 +34,14 @@ class DotsOCRParser:
                  max_completion_tokens=16384, num_thread=64, dpi=200, output_dir="./output", min_pixels=None,
                  max_pixels=None, use_hf=False, model_path="./weights/DotsOCR", model=None, processor=None,
                  hf_max_new_tokens=24000, guided=False, no_repeat_ngram_size=None, no_repeat_ngram_window=None,
-                 no_repeat_ngram_whitelist=None, speculative_ngram=None, prompt_lookup_min=2, prompt_lookup_max=4):
+                 no_repeat_ngram_whitelist=None, speculative_ngram=None, prompt_lookup_min=2, prompt_lookup_max=4, stop=None):
         self.dpi = dpi
+        # stop strings, opt-in: the server request carries `stop`, the in-process model generates with stop_strings and the
+        # text is cut where the match starts.  With the default None the request and the call are exactly what they were.
+        self.stop = None
+        if stop is not None:
+            from .stop_strings import check_stop_strings
+            self.stop = list(check_stop_strings(stop))
         # n-gram speculative decoding, opt-in: the in-process model generates with it (same tokens, fewer decode steps).  A
         # server speculates by its own --speculative-ngram flag, as vLLM does: requests carry nothing.
         self.speculative_ngram = None if not speculative_ngram else int(speculative_ngram)
@@ -105,16 +111,32 @@ class DotsOCRParser:
             if getattr(self.model.engine, "token_bytes", None) is None:
                 self.model.engine.set_token_bytes(self.processor.guide_token_bytes())
             kw["guided_json"] = layout_schema()
+        if self.stop:
+            if getattr(self.model.engine, "token_bytes", None) is None:
+                self.model.engine.set_token_bytes(self.processor.guide_token_bytes())
+            kw["stop_strings"] = self.stop
         generated = self.model.generate(**inputs, max_new_tokens=self.hf_max_new_tokens, **kw)
         trimmed = [out[len(inp):] for inp, out in zip(inputs.input_ids, generated)]
-        return self.processor.batch_decode(trimmed, skip_special_tokens=True, clean_up_tokenization_spaces=False)
+        texts = self.processor.batch_decode(trimmed, skip_special_tokens=True, clean_up_tokenization_spaces=False)
+        if self.stop:                               # the ids end at the token that completed a match: cut the text where the match starts
+            from .stop_strings import first_stop, stopped_text
+            tb, pad = self.model.engine.token_bytes.token, self.processor.tokenizer.pad_token_id
+            for i, ids in enumerate(trimmed):
+                toks = [int(t) for t in ids.tolist()]
+                while toks and toks[-1] == pad:
+                    toks.pop()
+                hit = first_stop([tb(t) for t in toks], self.stop)
+                if hit is not None:
+                    texts[i] = stopped_text(toks, hit, tb)
+        return texts
 
     def _inference_with_hf(self, image, prompt) -> str:
         return self._inference_batch_with_hf([image], [prompt])[0]
 
     def _inference_with_vllm(self, image, prompt):
         from dots_ocr.model.inference import inference_with_vllm
-        extra = {**({"guided_layout": True} if self._guided_layout([prompt]) else {}), **self._ngram_fields()}
+        extra = {**({"guided_layout": True} if self._guided_layout([prompt]) else {}), **self._ngram_fields(),
+                 **({"stop": self.stop} if self.stop else {})}
         return inference_with_vllm(image, prompt, model_name=self.model_name, protocol=self.protocol, ip=self.ip,
                                    port=self.port, temperature=self.temperature, top_p=self.top_p,
                                    max_completion_tokens=self.max_completion_tokens,

@@ -38,6 +38,11 @@ class Request:
     n: int = 1                                  # parallel sampling: n sequences from one tower and one prefill; sequence i runs under
                                                 # `sampling` with seed + i, everything else shared.  A finished request with n > 1 carries outputs
                                                 # (the n token arrays in index order), logprobs_out as a list in that order and kv_truncated_each
+    stop: Optional[Sequence[str]] = None        # stop strings: the row ends on the device at the token that completes one of them.  A
+                                                # finished request carries stop_hit = Engine.row_stop_hit(slot) — (token index, bytes into it,
+                                                # match length, match id) or None — as a list in index order when n > 1
+    include_stop_str_in_output: bool = False    # vLLM's field: where text built from the tokens is cut (stop_strings.cut_text); the tokens
+                                                # always end at the one that completed the match
 
     def n_patches(self) -> int:
         if self.grid_thw is None:
@@ -89,6 +94,7 @@ class ContinuousBatcher:
         self._row_rules: Dict[int, object] = {}                  # slot -> the LogitRules set on it (engine.set_row_logit_rules)
         self._row_guide: Dict[int, int] = {}                     # slot -> the guide handle set on it (engine.set_row_guide)
         self._row_ngram: Dict[int, object] = {}                  # slot -> the NgramRule set on it (engine.set_row_ngram)
+        self._row_stop: Dict[int, int] = {}                      # slot -> the stop automaton handle set on it (engine.set_row_stop)
         self._kids: Dict[int, List[int]] = {}                    # request id -> the slots planned for sequences 1 .. n - 1 of a request with n > 1
         self._seq_index: Dict[int, int] = {}                     # slot -> index of its sequence within a request with n > 1
         self.kv_truncated = 0                                    # sequences ended early by a dry KV pool (finish reason "kv_pool_exhausted")
@@ -124,6 +130,14 @@ class ContinuousBatcher:
             raise ValueError("this engine cannot honour a guide (no set_row_guide)")
         if req.ngram is not None and not hasattr(self.engine, "set_row_ngram"):
             raise ValueError("this engine cannot honour an n-gram rule (no set_row_ngram)")
+        if req.stop is not None:
+            if not hasattr(self.engine, "set_row_stop"):
+                raise ValueError("this engine cannot honour stop strings (no set_row_stop)")
+            from .stop_strings import check_stop_strings
+            try:
+                req.stop = check_stop_strings(req.stop)
+            except ValueError as e:
+                raise RequestRejected(str(e))
         if req.rules is not None and hasattr(req.rules, "eos_ids"):
             # what the engine will check at admission, checked here against the EOS ids and the vocabulary this batcher runs under: rules
             # that could never select a token are refused before the request is queued, where it fails alone
@@ -247,6 +261,8 @@ class ContinuousBatcher:
                 self.engine.set_row_guide(s, None)
             if self._row_ngram.pop(s, None) is not None:
                 self.engine.set_row_ngram(s, None)
+            if self._row_stop.pop(s, None) is not None:
+                self.engine.set_row_stop(s, None)
 
     def _set_rows(self, s, r, index: int = 0):
         """per-row parameters of request r on slot s; they apply from the first token the prefill selects.  index: the sequence of a
@@ -278,6 +294,12 @@ class ContinuousBatcher:
             self.engine.set_row_ngram(s, r.ngram)
         elif self._row_ngram.pop(s, None) is not None:
             self.engine.set_row_ngram(s, None)
+        if r.stop is not None:                       # the stop strings likewise: the prefill starts the automaton over and walks its first token
+            h = self.engine.create_stop(r.stop)      # cached by the engine per tuple of strings
+            self._row_stop[s] = h
+            self.engine.set_row_stop(s, h, int(getattr(r.rules, "min_tokens", 0) or 0))
+        elif self._row_stop.pop(s, None) is not None:
+            self.engine.set_row_stop(s, None)
 
     def _prefill(self, group, rows_set: bool = False):
         # image rows are consumed in packed order, so sequences with images keep their relative order: pack the group as is
@@ -446,19 +468,26 @@ class ContinuousBatcher:
                 lp_out = None
                 if req.logprobs is not None:         # read before the release switches the slot's logprobs off
                     lp_out = self.engine.row_logprobs(s, len(toks))
+                hit = None
+                if req.stop is not None:             # read before the release clears the row's automaton and its hit record
+                    hit = self.engine.row_stop_hit(s)
                 if req.n == 1:
+                    if req.stop is not None:
+                        req.stop_hit = hit
                     if req.logprobs is not None:
                         req.logprobs_out = lp_out
                     done.append((rid, req, toks))
                 else:
                     # one sequence of n: its slot goes back now, the request is reported once, when its last sequence has finished
-                    req._parts[self._seq_index.pop(s)] = (toks, lp_out, req.kv_truncated)
+                    req._parts[self._seq_index.pop(s)] = (toks, lp_out, req.kv_truncated, hit)
                     if len(req._parts) == req.n:
                         parts = [req._parts[j] for j in range(req.n)]
-                        req.outputs = [t for t, _, _ in parts]
+                        req.outputs = [t for t, _, _, _ in parts]
                         if req.logprobs is not None:
-                            req.logprobs_out = [l for _, l, _ in parts]
-                        req.kv_truncated_each = [k for _, _, k in parts]
+                            req.logprobs_out = [l for _, l, _, _ in parts]
+                        if req.stop is not None:
+                            req.stop_hit = [h for _, _, _, h in parts]
+                        req.kv_truncated_each = [k for _, _, k, _ in parts]
                         req.kv_truncated = any(req.kv_truncated_each)
                         del req._parts
                         done.append((rid, req, req.outputs[0]))
@@ -466,6 +495,7 @@ class ContinuousBatcher:
                     self.engine.set_row_ngram(s, None)
                 self.engine.slot_release(s)
                 self._row_guide.pop(s, None)         # the release cleared the row's guide: its handle is free to be evicted
+                self._row_stop.pop(s, None)          # and its stop strings
         self._last_lens = {s: int(lens[s]) for s in self.running}      # after the finished slots have left: only what is still decoding
         return done
 

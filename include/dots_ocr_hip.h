@@ -293,6 +293,42 @@ typedef struct DotsNgramRule {
 } DotsNgramRule;
 int dots_set_row_ngram(DotsEngine* e, int row, const DotsNgramRule* r);
 
+/* ---- Stop strings: a row ends at the token that completes one of a few pieces of TEXT.  The check is a byte automaton on the
+ * device that the commit of every token advances, so the stop is exact inside captured decode chunks and in dots_generate, and a stopped
+ * row writes no further KV.  The host compiles 1 .. DOTS_MAX_STOP_STRINGS strings of 1 .. DOTS_MAX_STOP_BYTES bytes each into an
+ * Aho-Corasick automaton with its failure links folded into a dense byte DFA (dots_ocr_amd/stop_strings.py).
+ *
+ * The matching rule: the row's output is scanned as a byte stream — the concatenated bytes (dots_set_token_bytes) of the tokens it has
+ * generated; the prompt is not part of it, and a token without bytes contributes nothing and leaves the state alone.  The row stops at
+ * the first byte at which any listed string ends; if several end there the longest (earliest start) is the match.  The token that holds
+ * that byte is appended whole and is the row's last.  An engine EOS id or a stop id of the row's DotsLogitRules finishes the row as before
+ * and is not walked.  While the index of the token (the prefill's token is 0) is below min_tokens the automaton advances but no match is
+ * taken, so a string that straddles the boundary is still found.
+ *
+ * dots_stop_create    table_host uint16 [n_states][256] (every entry < n_states, state 0 = the root), match_len_host uint16 [n_states] (bytes
+ *                     of the longest listed string ending at the state, 0 = none; <= DOTS_MAX_STOP_BYTES), match_id_host uint8 [n_states]
+ *                     (its index, < DOTS_MAX_STOP_STRINGS); n_states <= DOTS_MAX_STOP_STRINGS x DOTS_MAX_STOP_BYTES + 1.  Copied to device
+ *                     memory; *handle_out (>= 1) names it.  Any number of rows may hold one automaton.  Synchronises.
+ * dots_stop_destroy   DOTS_E_STATE while a row holds it.  Synchronises.
+ * dots_set_row_stop   row `row` (a slot, or sequence `row` of a static batch) holds the automaton from its root, with no hit (handle 0:
+ *                     none), written in stream order by a one-thread kernel; captured decode graphs are kept and no graph is added.  A
+ *                     following dots_prefill / dots_slots_prefill of the row starts the automaton over and clears the hit; the prefill's
+ *                     first token is already walked.  dots_slot_release / dots_slots_reset clear the row; dots_slots_fork gives every child
+ *                     the source's automaton and min_tokens at the root.  A row with stop strings is selected by the per-row stage (with the
+ *                     engine-wide setting as it stands at the call if it has no DotsSamplingParams of its own) and verifies no draft of a
+ *                     speculating step.
+ * dots_row_stop_hit   out[4] = {index of the token that completed the match, bytes of that token consumed including the matching byte,
+ *                     length of the matched string in bytes, its index in the list}, or {-1, 0, 0, -1}: no hit (yet), or the row holds no
+ *                     stop strings.  Synchronises.
+ * All four: DOTS_E_STATE before dots_set_token_bytes, DOTS_E_INVALID on a bad size, handle or row. */
+#define DOTS_MAX_STOP_STRINGS 16
+#define DOTS_MAX_STOP_BYTES 64
+int dots_stop_create(DotsEngine* e, const uint16_t* table_host, int n_states, const uint16_t* match_len_host, const uint8_t* match_id_host,
+                     int32_t* handle_out);
+int dots_stop_destroy(DotsEngine* e, int32_t handle);
+int dots_set_row_stop(DotsEngine* e, int row, int32_t handle, int min_tokens);
+int dots_row_stop_hit(DotsEngine* e, int row, int32_t* out);
+
 /* ---- N-gram speculative decoding of greedy rows: opt-in, engine-wide, slot mode only.  With k drafts a slot occupies up to
  * k + 1 rows of one decode step: row j carries token j of (last committed token, draft 1 .. k) at context ctx + j on the slot's own KV
  * pages, and sees the K/V rows 0 .. j - 1 appended in the step's qkv launch.  Every decode kernel is row-independent and batch-invariant
