@@ -16,6 +16,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -23,6 +24,7 @@
 #include "decode_layout.h"
 #include "dots_ocr_hip.h"
 #include "kernels.h"
+#include "row_stage.h"
 
 namespace {
 
@@ -203,6 +205,8 @@ struct DotsEngine {
     int n_eos = 0;
     float temperature = 0.f, top_p = 1.f;      // temperature <= 0: greedy (arg max)
     uint64_t seed = 0;
+    // which rows the per-row selection stage owns and for which features (row_stage.h): the only host record of it
+    RowStage stage;
     // per-row selection (dots_set_row_sampling): device table + own flags, allocated on first use; penalty state
     // (output counts, prompt-presence bits, penalised-logit scratch) allocated when a row first carries a penalty
     RowParams* d_rowp = nullptr;
@@ -211,8 +215,6 @@ struct DotsEngine {
     int32_t* pen_cnt = nullptr;
     uint32_t* pen_seen = nullptr;
     float* pen_logits = nullptr;
-    int row_own[DOTS_MAX_BATCH] = {0};
-    int n_own = 0;                         // rows whose own flag is set on the device (own parameters or logit rules): > 0 = the per-row stage
     // logit rules (dots_set_row_logit_rules): per-row table + the dense "bias or -inf" image [max_batch][V], allocated by the
     // first row that carries rules.  rule_stage: pinned host staging of one call's id / value lists ([V + DOTS_MAX_LOGIT_BIAS] int32, then
     // [DOTS_MAX_LOGIT_BIAS] fp32) and its device twin; rule_ev guards the pinned buffer's reuse.
@@ -220,12 +222,10 @@ struct DotsEngine {
     float* rule_img = nullptr;
     int32_t *rule_stage = nullptr, *rule_stage_host = nullptr;
     hipEvent_t rule_ev = nullptr;
-    int row_rules[DOTS_MAX_BATCH] = {0};
-    int n_rules = 0;                       // rows with rules: > 0 hands the table to the per-row stage
     int32_t h_eos[16] = {0};               // host mirror of eos_ids (the never-selectable checks of the rules)
     // guided decoding (dots_set_row_guide): the packed bytes of the vocabulary (dots_set_token_bytes), the guides created on
     // this engine (device tables; rows = how many rows hold each), and — allocated by the first row that takes a guide — the row table and
-    // the allowed bits [max_batch][guide_mask_words(V)].  row_guide[row] = guide id + 1, 0 = none.
+    // the allowed bits [max_batch][guide_mask_words(V)].  row_guide[row] = guide id + 1 of a row that holds one.
     int32_t* tok_off = nullptr;
     uint8_t* tok_bytes = nullptr;
     struct Guide { uint16_t* table = nullptr; uint8_t* accepting = nullptr; int n_states = 0, start = 0, rows = 0; };
@@ -233,21 +233,17 @@ struct DotsEngine {
     RowGuide* d_guides = nullptr;
     uint32_t* guide_mask = nullptr;
     int row_guide[DOTS_MAX_BATCH] = {0};
-    int n_guided = 0;                      // rows with a guide: > 0 adds the mask kernel in front of the per-row stage
     // no-repeat n-gram blocking (dots_set_row_ngram): allocated by the first row that takes a rule — the row table and the
-    // banned bits [max_batch][ngram_mask_words(V)].  row_ngram[row] = the row carries a rule.
+    // banned bits [max_batch][ngram_mask_words(V)]
     RowNgram* d_ngram = nullptr;
     uint32_t* ngram_mask = nullptr;
-    int row_ngram[DOTS_MAX_BATCH] = {0};
-    int n_ngram = 0;                       // rows with an n-gram rule: > 0 adds the ban kernel in front of the per-row stage
     // stop strings (dots_set_row_stop): the automata created on this engine (device tables; rows = how many rows hold each) and
-    // — allocated by the first row that takes one — the row table.  row_stop[row] = automaton id + 1, 0 = none; row_stop_min its min_tokens.
+    // — allocated by the first row that takes one — the row table.  Of a row that holds one: row_stop[row] = automaton id + 1, row_stop_min its min_tokens.
     struct Stop { uint16_t* table = nullptr; uint16_t* match_len = nullptr; uint8_t* match_id = nullptr; int n_states = 0, rows = 0; };
     std::vector<Stop> stops;
     RowStop* d_stop = nullptr;
     int row_stop[DOTS_MAX_BATCH] = {0};
     int row_stop_min[DOTS_MAX_BATCH] = {0};
-    int n_stop_rows = 0;                   // rows with stop strings: they are selected by the per-row stage, whose commit walks the automaton
     // log-probabilities (dots_set_row_logprobs): top_n per row (-1 = off) on the device and its host mirror; the outputs
     // ([max_batch][max_seq_len] positions) and the stage's scratch are allocated by the first row switched on
     int32_t* d_row_lp = nullptr;
@@ -286,8 +282,14 @@ struct DotsEngine {
     // selection stage), whether any row returns logprobs (lp), whether any row carries logit rules (rules: the stage then gets their
     // table), whether any row holds a guide (guided: the mask kernel and the guides' tables), whether any row carries an n-gram rule (ngram:
     // the ban kernel and its bits), the draft count of a speculating step (spec: 0 = the plain step); engine-wide sampling changes drop
-    // the cache (dots_set_sampling), per-row ones live in device memory
-    struct StepGraph { int rows, splits, out_cap, n_eos, part, rowp, lp, rules, guided, ngram, spec; hipGraph_t graph; hipGraphExec_t exec; };
+    // the cache (dots_set_sampling), per-row ones live in device memory.  step_key() builds the key from the engine's state: a feature that
+    // changes what a step launches adds a member here and a line there
+    struct StepKey {
+        int rows, splits, out_cap, n_eos, part, rowp, lp, rules, guided, ngram, spec;
+        bool operator==(const StepKey& o) const { return std::memcmp(this, &o, sizeof(StepKey)) == 0; }
+    };
+    static_assert(std::has_unique_object_representations_v<StepKey>, "StepKey is compared bytewise: plain ints, no padding");
+    struct StepGraph { StepKey key; hipGraph_t graph; hipGraphExec_t exec; };
     std::vector<StepGraph> step_graphs;
     std::vector<int> h_prompt_lens;
     int steps_done = 0;
@@ -920,33 +922,30 @@ StepState step_state(const DotsEngine* e, int advance, const int32_t* sel) {
 
 SpecState spec_state(const DotsEngine* e) {
     return SpecState{e->sp_drafts, e->sp_ndraft, e->sp_nlive, e->sp_tokens, e->sp_ctx, e->sp_table, e->sp_stats,
-                     e->n_own > 0 ? e->d_row_own : nullptr, e->n_lp > 0 ? e->d_row_lp : nullptr, e->spec_k, e->temperature > 0.f ? 0 : 1};
+                     e->stage.staged_rows() > 0 ? e->d_row_own : nullptr, e->n_lp > 0 ? e->d_row_lp : nullptr, e->spec_k, e->temperature > 0.f ? 0 : 1};
 }
 
 // greedy arg max or temperature / top-p sampling over the fp32 logits of the step
 int select_tokens(DotsEngine* e, int advance) {
     const DotsConfig& c = e->cfg;
-    StepState st;
-    st.cur_tokens = e->cur_tokens; st.ctx_len = e->ctx_len; st.out_ids = e->out_ids; st.out_lens = e->out_lens; st.finished = e->finished;
-    st.eos_ids = e->eos_ids; st.n_eos = e->n_eos; st.advance_ctx = advance;
-    if (e->slot_mode) { st.sel = e->sel_now; st.max_len = e->d_max_len; st.out_stride = c.max_seq_len; st.cap = c.max_seq_len; }
-    else { st.sel = nullptr; st.max_len = nullptr; st.out_stride = e->out_cap; st.cap = e->out_cap; }
+    StepState st = step_state(e, advance, e->sel_now);
+    if (!e->slot_mode) { st.sel = nullptr; st.max_len = nullptr; st.out_stride = e->out_cap; st.cap = e->out_cap; }      // a static batch
     // logprobs: the partial kernel reads the logits and snapshots finished / out_lens before selection commits, the final kernel
     // reads the committed token after it
     const LogprobState ls{e->d_row_lp, st.sel, e->finished, e->out_lens, e->cur_tokens, e->lp_ms, e->lp_pv, e->lp_pi, e->lp_pos,
                           e->lp_tok, e->lp_ids, e->lp_top, c.max_seq_len};
     if (e->n_lp > 0) CK(launch_logprob_partial(e->stream, e->d_logits, c.vocab_size, c.vocab_size, e->B_sel, ls));
-    if (e->n_own > 0) {          // per-row stage for the rows with their own parameters (+ the greedy rows that follow the engine)
+    if (e->stage.staged_rows() > 0) {      // per-row stage for the rows with their own parameters (+ the greedy rows that follow the engine)
         RowSel rs{e->d_rowp, e->d_row_own, e->pen_cnt, e->pen_seen, e->pen_logits, e->d_row_thr, e->temperature > 0.f ? 0 : 1,
-                  e->n_rules > 0 ? e->d_rules : nullptr, e->rule_img, GuideSel{}, NgramSel{}, StopSel{}};
+                  e->stage.rows(ROW_RULES) > 0 ? e->d_rules : nullptr, e->rule_img, GuideSel{}, NgramSel{}, StopSel{}};
         // the stop-string rows' table, once any row has held one (allocating it drops the captured steps, so no cache key changes): the
         // commit of a row that holds an automaton walks it, no launch is added
         if (e->d_stop) rs.stop = StopSel{e->d_stop, e->tok_off, e->tok_bytes, c.vocab_size, 0};
-        if (e->n_ngram > 0) {        // the n-gram rows' banned bits from their own output so far, before the stage reads the logits
+        if (e->stage.rows(ROW_NGRAM) > 0) {        // the n-gram rows' banned bits from their own output so far, before the stage reads the logits
             rs.ngram = NgramSel{e->d_ngram, e->ngram_mask, ngram_mask_words(c.vocab_size), c.vocab_size};
             CK(launch_ngram_ban(e->stream, rs.ngram, e->B_sel, st.out_ids, st.out_lens, st.out_stride, st.finished, st.sel));
         }
-        if (e->n_guided > 0) {       // the guided rows' allowed bits from their current states, before the stage reads the logits
+        if (e->stage.rows(ROW_GUIDE) > 0) {        // the guided rows' allowed bits from their current states, before the stage reads the logits
             rs.guide = GuideSel{e->d_guides, e->guide_mask, e->tok_off, e->tok_bytes, guide_mask_words(c.vocab_size), c.vocab_size};
             CK(launch_guide_mask(e->stream, rs.guide, e->B_sel, st.sel));
         }
@@ -1039,92 +1038,66 @@ int ensure_stop_state(DotsEngine* e) {
 // what a row without parameters of its own is selected with once the per-row stage owns it (logit rules): the engine-wide setting as it stands
 RowParams engine_row_params(const DotsEngine* e) { return RowParams{e->temperature, e->top_p, 0, 1.f, 0.f, 0.f, e->seed}; }
 
-// the row's entry back to the engine-wide setting (stream ordered); a row that still carries logit rules stays with the per-row stage
-int clear_row(DotsEngine* e, int row) {
-    if (!e->row_own[row]) return DOTS_OK;
-    if (e->row_rules[row] || e->row_guide[row] || e->row_ngram[row] || e->row_stop[row]) {
-        CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, engine_row_params(e), 1));
-        e->row_own[row] = 0;
-        return DOTS_OK;
-    }
-    CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, RowParams{}, 0));
-    e->row_own[row] = 0;
-    e->n_own -= 1;
+// Row `row` takes feature f: it enters the per-row stage unless another feature holds it there already, with the engine-wide setting as
+// its entry and the own flag set (stream ordered).  Own parameters are that entry themselves: their setter has written it.
+int enter_row_stage(DotsEngine* e, int row, RowFeature f) {
+    RET(ensure_row_table(e));
+    if (e->stage.attach(row, f) && f != ROW_PARAMS) CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, engine_row_params(e), 1));
     return DOTS_OK;
 }
 
-// the row's logit rules off (stream ordered)
-int clear_row_rules(DotsEngine* e, int row) {
-    if (!e->row_rules[row]) return DOTS_OK;
-    CK(launch_set_row_rules(e->stream, e->d_rules, e->rule_img, row, e->cfg.vocab_size, RowRules{}, nullptr, 0, nullptr, nullptr, 0));
-    e->row_rules[row] = 0;
-    e->n_rules -= 1;
-    if (!e->row_own[row] && !e->row_guide[row] && !e->row_ngram[row] && !e->row_stop[row]) {
-        CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, RowParams{}, 0));
-        e->n_own -= 1;
-    }
+// Feature f comes off row `row`: with its last feature the row leaves the stage (entry and own flag zeroed); own parameters taken off a
+// row that stays give the entry back to the engine-wide setting (stream ordered)
+int leave_row_stage(DotsEngine* e, int row, RowFeature f) {
+    if (!e->stage.has(row, f)) return DOTS_OK;
+    if (e->stage.detach(row, f)) CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, RowParams{}, 0));
+    else if (f == ROW_PARAMS) CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, engine_row_params(e), 1));
     return DOTS_OK;
 }
 
-// the row's guide off (stream ordered)
-int clear_row_guide(DotsEngine* e, int row) {
-    if (!e->row_guide[row]) return DOTS_OK;
-    CK(launch_set_row_guide(e->stream, e->d_guides, row, RowGuide{}));
-    e->guides[e->row_guide[row] - 1].rows -= 1;
-    e->row_guide[row] = 0;
-    e->n_guided -= 1;
-    if (!e->row_own[row] && !e->row_rules[row] && !e->row_ngram[row] && !e->row_stop[row]) {
-        CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, RowParams{}, 0));
-        e->n_own -= 1;
+// feature f off row `row` (stream ordered): the feature's own table entry and reference count, then the stage
+int clear_row_feature(DotsEngine* e, int row, RowFeature f) {
+    if (!e->stage.has(row, f)) return DOTS_OK;
+    switch (f) {
+    case ROW_RULES:
+        CK(launch_set_row_rules(e->stream, e->d_rules, e->rule_img, row, e->cfg.vocab_size, RowRules{}, nullptr, 0, nullptr, nullptr, 0));
+        break;
+    case ROW_GUIDE:
+        CK(launch_set_row_guide(e->stream, e->d_guides, row, RowGuide{}));
+        e->guides[e->row_guide[row] - 1].rows -= 1;
+        e->row_guide[row] = 0;
+        break;
+    case ROW_NGRAM:
+        CK(launch_set_row_ngram(e->stream, e->d_ngram, row, RowNgram{}));
+        break;
+    case ROW_STOP:
+        CK(launch_set_row_stop(e->stream, e->d_stop, row, RowStop{}));
+        e->stops[e->row_stop[row] - 1].rows -= 1;
+        e->row_stop[row] = e->row_stop_min[row] = 0;
+        break;
+    default: break;                                        // own parameters: the stage entry is all there is
     }
+    return leave_row_stage(e, row, f);
+}
+
+// host side of row `row` taking automaton id (a live one): stage membership, the automata's reference counts and the row's payload.  The
+// caller writes the row's table entry (dots_set_row_stop one row, dots_slots_fork all children at once)
+int hold_row_stop(DotsEngine* e, int row, int id, int min_tokens) {
+    if (e->stage.has(row, ROW_STOP)) e->stops[e->row_stop[row] - 1].rows -= 1;
+    RET(enter_row_stage(e, row, ROW_STOP));
+    e->row_stop[row] = id + 1;
+    e->row_stop_min[row] = min_tokens;
+    e->stops[id].rows += 1;
     return DOTS_OK;
 }
 
-// the row's n-gram rule off (stream ordered)
-int clear_row_ngram(DotsEngine* e, int row) {
-    if (!e->row_ngram[row]) return DOTS_OK;
-    CK(launch_set_row_ngram(e->stream, e->d_ngram, row, RowNgram{}));
-    e->row_ngram[row] = 0;
-    e->n_ngram -= 1;
-    if (!e->row_own[row] && !e->row_rules[row] && !e->row_guide[row] && !e->row_stop[row]) {
-        CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, RowParams{}, 0));
-        e->n_own -= 1;
-    }
-    return DOTS_OK;
-}
-
-// the row's stop strings off (stream ordered)
-int clear_row_stop(DotsEngine* e, int row) {
-    if (!e->row_stop[row]) return DOTS_OK;
-    CK(launch_set_row_stop(e->stream, e->d_stop, row, RowStop{}));
-    e->stops[e->row_stop[row] - 1].rows -= 1;
-    e->row_stop[row] = 0;
-    e->row_stop_min[row] = 0;
-    e->n_stop_rows -= 1;
-    if (!e->row_own[row] && !e->row_rules[row] && !e->row_guide[row] && !e->row_ngram[row]) {
-        CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, RowParams{}, 0));
-        e->n_own -= 1;
-    }
-    return DOTS_OK;
-}
-
-// row `row` holds automaton id (a live one) from the root with no hit (stream ordered); the row goes to the per-row stage
+// row `row` holds automaton id (a live one) from the root with no hit (stream ordered)
 int assign_row_stop(DotsEngine* e, int row, int id, int min_tokens) {
     RET(ensure_row_table(e));
     RET(ensure_stop_state(e));
     const DotsEngine::Stop& a = e->stops[id];
     CK(launch_set_row_stop(e->stream, e->d_stop, row, RowStop{a.table, a.match_len, a.match_id, a.n_states, 0, min_tokens, -1, 0, 0, -1, 0}));
-    if (!e->row_own[row] && !e->row_rules[row] && !e->row_guide[row] && !e->row_ngram[row] && !e->row_stop[row])
-        CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, engine_row_params(e), 1));
-    if (e->row_stop[row]) e->stops[e->row_stop[row] - 1].rows -= 1;
-    else {
-        e->n_stop_rows += 1;
-        if (!e->row_own[row] && !e->row_rules[row] && !e->row_guide[row] && !e->row_ngram[row]) e->n_own += 1;
-    }
-    e->row_stop[row] = id + 1;
-    e->row_stop_min[row] = min_tokens;
-    e->stops[id].rows += 1;
-    return DOTS_OK;
+    return hold_row_stop(e, row, id, min_tokens);
 }
 
 int check_row_params(DotsEngine* e, const DotsSamplingParams& p, RowParams* out) {
@@ -1473,9 +1446,9 @@ int prefill(DotsEngine* e, const int32_t* ids, const int32_t* lens, int B, const
     // prompt-presence bits (repetition penalty) of the prefilled rows, once any row has used a penalty
     if (e->pen_cnt) CK(launch_pen_prompt(s, e->p_src, e->p_last, slots ? e->p_dst : nullptr, B, c.image_token_id, c.vocab_size, e->pen_cnt, e->pen_seen));
     // the automata of the prefilled rows that hold a guide start over: the first token is already selected under the guide
-    if (e->n_guided > 0) CK(launch_guide_reset_rows(s, e->d_guides, slots ? e->p_dst : nullptr, B));
+    if (e->stage.rows(ROW_GUIDE) > 0) CK(launch_guide_reset_rows(s, e->d_guides, slots ? e->p_dst : nullptr, B));
     // so do the stop automata of the prefilled rows, and their hit records are cleared: the first token's bytes are the first ones walked
-    if (e->n_stop_rows > 0) CK(launch_stop_reset_rows(s, e->d_stop, slots ? e->p_dst : nullptr, B));
+    if (e->stage.rows(ROW_STOP) > 0) CK(launch_stop_reset_rows(s, e->d_stop, slots ? e->p_dst : nullptr, B));
     // last position of every sequence -> final norm -> lm_head -> first token
     CK(launch_gather_rows(s, e->p_x, e->p_last, slots ? e->p_dst : nullptr, e->d_h, B, H));
     CK(launch_dec_lmhead(s, e->d_h, e->final_norm, e->lm_head_d, e->lm_head_s, e->d_logits, rows, H, c.vocab_size, c.rms_norm_eps));
@@ -1566,18 +1539,29 @@ int decode_step_launches(DotsEngine* e, int n_splits, int part = 0) {
 
 int splits_for_ctx(int max_ctx) { return decode_attn_splits(max_ctx); }
 
+// everything a captured step bakes in, from the engine's state as it stands (DotsEngine::StepKey)
+DotsEngine::StepKey step_key(const DotsEngine* e, int rows, int n_splits, int out_cap, int part) {
+    DotsEngine::StepKey k;
+    k.rows = rows; k.splits = n_splits; k.out_cap = out_cap; k.n_eos = e->n_eos; k.part = part;
+    k.rowp = e->stage.staged_rows() > 0;
+    k.lp = e->n_lp > 0;
+    k.rules = e->stage.rows(ROW_RULES) > 0;
+    k.guided = e->stage.rows(ROW_GUIDE) > 0;
+    k.ngram = e->stage.rows(ROW_NGRAM) > 0;
+    k.spec = e->slot_mode ? e->spec_k : 0;
+    return k;
+}
+
 // The captured decode step for (rows = e->B, splits, out_cap, e->n_eos): looked up in the cache or captured now.
 int step_graph(DotsEngine* e, int rows, int n_splits, int out_cap, hipGraphExec_t* exec, int part = 0) {
-    const int rowp = e->n_own > 0 ? 1 : 0, lp = e->n_lp > 0 ? 1 : 0, rules = e->n_rules > 0 ? 1 : 0, guided = e->n_guided > 0 ? 1 : 0,
-              ngram = e->n_ngram > 0 ? 1 : 0, spec = e->slot_mode ? e->spec_k : 0;
+    const DotsEngine::StepKey key = step_key(e, rows, n_splits, out_cap, part);
     for (auto& g : e->step_graphs)
-        if (g.rows == rows && g.splits == n_splits && g.out_cap == out_cap && g.n_eos == e->n_eos && g.part == part && g.rowp == rowp && g.lp == lp && g.rules == rules &&
-            g.guided == guided && g.ngram == ngram && g.spec == spec) {
+        if (g.key == key) {
             *exec = g.exec;
             return DOTS_OK;
         }
     if (e->step_graphs.size() >= 32) drop_step_graphs(e);
-    DotsEngine::StepGraph g{rows, n_splits, out_cap, e->n_eos, part, rowp, lp, rules, guided, ngram, spec, nullptr, nullptr};
+    DotsEngine::StepGraph g{key, nullptr, nullptr};
     CK(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
     int r = decode_step_launches(e, n_splits, part);
     hipError_t ce = hipStreamEndCapture(e->stream, &g.graph);
@@ -1884,7 +1868,7 @@ int dots_generate(DotsEngine* e, const int32_t* input_ids, const int32_t* prompt
         if (exec) CK(hipGraphLaunch(cur != s && exec_part ? exec_part : exec, cur));
         else RET(decode_step_launches(e, n_splits));
         ++steps;
-        if ((n_eos || e->n_stop_rows > 0) && (step % 16 == 0)) {       // early exit once every sequence hit EOS (or its stop string)
+        if ((n_eos || e->stage.rows(ROW_STOP) > 0) && (step % 16 == 0)) {       // early exit once every sequence hit EOS (or its stop string)
             CK(hipMemcpyAsync(fin.data(), e->finished, B * 4, hipMemcpyDeviceToHost, cur));
             CK(hipStreamSynchronize(cur));
             bool all = true;
@@ -2030,25 +2014,12 @@ int dots_slots_fork(DotsEngine* e, int src_slot, const int32_t* dst_slots, int n
         const int32_t* src0 = e->p_src + (b ? e->hp_last[b - 1] + 1 : 0);
         for (int i = 0; i < n; ++i) CK(launch_pen_prompt(s, src0, fk_last, fk_dst + i, 1, c.image_token_id, V, e->pen_cnt, e->pen_seen));
     }
-    if (e->n_guided > 0) CK(launch_guide_reset_rows(s, e->d_guides, fk_dst, n));
-    if (e->row_stop[src_slot]) {
-        // the children inherit the source's stop strings (automaton and min_tokens) at the root with no hit; like every row that holds an
-        // automaton they are selected by the per-row stage
-        const int id = e->row_stop[src_slot] - 1;
-        for (int i = 0; i < n; ++i) {
-            const int d = dst_slots[i];
-            const bool staged = e->row_own[d] || e->row_rules[d] || e->row_guide[d] || e->row_ngram[d] || e->row_stop[d];
-            if (!staged) {
-                CK(launch_set_row_params(s, e->d_rowp, e->d_row_own, d, engine_row_params(e), 1));
-                e->n_own += 1;
-            }
-            if (e->row_stop[d]) e->stops[e->row_stop[d] - 1].rows -= 1; else e->n_stop_rows += 1;
-            e->row_stop[d] = id + 1;
-            e->row_stop_min[d] = e->row_stop_min[src_slot];
-            e->stops[id].rows += 1;
-        }
+    if (e->stage.rows(ROW_GUIDE) > 0) CK(launch_guide_reset_rows(s, e->d_guides, fk_dst, n));
+    if (e->stage.has(src_slot, ROW_STOP)) {
+        // the children inherit the source's stop strings (automaton and min_tokens) at the root with no hit: one launch writes all their entries
+        for (int i = 0; i < n; ++i) RET(hold_row_stop(e, dst_slots[i], e->row_stop[src_slot] - 1, e->row_stop_min[src_slot]));
         CK(launch_stop_fork_rows(s, e->d_stop, src_slot, fk_dst, n));
-    } else if (e->n_stop_rows > 0)
+    } else if (e->stage.rows(ROW_STOP) > 0)
         CK(launch_stop_reset_rows(s, e->d_stop, fk_dst, n));
     CK(hipStreamSynchronize(s));                           // L, cap and the staged arrays are stack variables
     // ---- the children's first tokens: the selection stage over a mask of the children only
@@ -2085,24 +2056,17 @@ int dots_slots_reset(DotsEngine* e) {
     CK(hipMemsetAsync(e->ctx_len, 0, e->cfg.max_batch * 4, s));
     CK(hipMemsetAsync(e->out_lens, 0, e->cfg.max_batch * 4, s));
     CK(hipMemsetAsync(e->finished, 0, e->cfg.max_batch * 4, s));
-    if (e->d_row_own) CK(hipMemsetAsync(e->d_row_own, 0, DOTS_MAX_BATCH * 4, s));
-    std::fill(e->row_own, e->row_own + DOTS_MAX_BATCH, 0);
-    e->n_own = 0;
-    if (e->d_rules) CK(hipMemsetAsync(e->d_rules, 0, DOTS_MAX_BATCH * sizeof(RowRules), s));
-    std::fill(e->row_rules, e->row_rules + DOTS_MAX_BATCH, 0);
-    e->n_rules = 0;
-    if (e->d_guides) CK(hipMemsetAsync(e->d_guides, 0, DOTS_MAX_BATCH * sizeof(RowGuide), s));
+    // no row carries any feature: the features' row tables (in RowFeature order; the own flags stand for the parameters), then the host record
+    const struct { void* table; size_t row_bytes; } feature_tables[ROW_FEATURES] = {
+        {e->d_row_own, 4}, {e->d_rules, sizeof(RowRules)}, {e->d_guides, sizeof(RowGuide)}, {e->d_ngram, sizeof(RowNgram)}, {e->d_stop, sizeof(RowStop)}};
+    for (const auto& t : feature_tables)
+        if (t.table) CK(hipMemsetAsync(t.table, 0, DOTS_MAX_BATCH * t.row_bytes, s));
+    e->stage.reset();
     std::fill(e->row_guide, e->row_guide + DOTS_MAX_BATCH, 0);
     for (auto& g : e->guides) g.rows = 0;
-    e->n_guided = 0;
-    if (e->d_ngram) CK(hipMemsetAsync(e->d_ngram, 0, DOTS_MAX_BATCH * sizeof(RowNgram), s));
-    std::fill(e->row_ngram, e->row_ngram + DOTS_MAX_BATCH, 0);
-    e->n_ngram = 0;
-    if (e->d_stop) CK(hipMemsetAsync(e->d_stop, 0, DOTS_MAX_BATCH * sizeof(RowStop), s));
     std::fill(e->row_stop, e->row_stop + DOTS_MAX_BATCH, 0);
     std::fill(e->row_stop_min, e->row_stop_min + DOTS_MAX_BATCH, 0);
     for (auto& a : e->stops) a.rows = 0;
-    e->n_stop_rows = 0;
     if (e->d_row_lp) CK(hipMemsetAsync(e->d_row_lp, 0xFF, DOTS_MAX_BATCH * 4, s));
     std::fill(e->row_lp, e->row_lp + DOTS_MAX_BATCH, -1);
     e->n_lp = 0;
@@ -2233,11 +2197,7 @@ int dots_slot_release(DotsEngine* e, int slot) {
     if (!e) return DOTS_E_INVALID;
     if (!e->slot_mode || slot < 0 || slot >= e->cfg.max_batch || !e->slot_active[slot]) return e->fail(DOTS_E_STATE, "slot %d is not occupied", slot);
     CK(hipSetDevice(e->device));
-    RET(clear_row(e, slot));
-    RET(clear_row_rules(e, slot));
-    RET(clear_row_guide(e, slot));
-    RET(clear_row_ngram(e, slot));
-    RET(clear_row_stop(e, slot));
+    for (int f = 0; f < ROW_FEATURES; ++f) RET(clear_row_feature(e, slot, (RowFeature)f));
     RET(set_row_lp(e, slot, -1));
     e->slot_active[slot] = 0;
     e->sel_dirty = true;
@@ -2372,21 +2332,20 @@ int dots_set_row_sampling(DotsEngine* e, int row, const DotsSamplingParams* p) {
     if (!e) return DOTS_E_INVALID;
     if (row < 0 || row >= e->cfg.max_batch) return e->fail(DOTS_E_INVALID, "row %d out of range [0, %d)", row, e->cfg.max_batch);
     CK(hipSetDevice(e->device));
-    if (!p) return e->d_rowp ? clear_row(e, row) : DOTS_OK;
+    if (!p) return clear_row_feature(e, row, ROW_PARAMS);
     RowParams rp;
     RET(check_row_params(e, *p, &rp));
     RET(ensure_row_table(e));
     if (rp.repetition_penalty != 1.f || rp.frequency_penalty != 0.f || rp.presence_penalty != 0.f) RET(ensure_pen_state(e));
     CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, rp, 1));
-    if (!e->row_own[row]) { e->row_own[row] = 1; e->n_own += (e->row_rules[row] || e->row_guide[row] || e->row_ngram[row] || e->row_stop[row]) ? 0 : 1; }
-    return DOTS_OK;
+    return enter_row_stage(e, row, ROW_PARAMS);
 }
 
 int dots_set_row_logit_rules(DotsEngine* e, int row, const DotsLogitRules* r) {
     if (!e) return DOTS_E_INVALID;
     if (row < 0 || row >= e->cfg.max_batch) return e->fail(DOTS_E_INVALID, "row %d out of range [0, %d)", row, e->cfg.max_batch);
     CK(hipSetDevice(e->device));
-    if (!r) return e->d_rules ? clear_row_rules(e, row) : DOTS_OK;
+    if (!r) return clear_row_feature(e, row, ROW_RULES);
     RowRules rr;
     RET(check_logit_rules(e, *r, e->cfg.vocab_size, e->h_eos, e->n_eos, &rr));
     RET(ensure_row_table(e));
@@ -2407,12 +2366,9 @@ int dots_set_row_logit_rules(DotsEngine* e, int row, const DotsLogitRules* r) {
     }
     CK(launch_set_row_rules(e->stream, e->d_rules, e->rule_img, row, V, rr, e->rule_stage, n_allowed, e->rule_stage + V,
                             reinterpret_cast<const float*>(e->rule_stage + V + DOTS_MAX_LOGIT_BIAS), r->n_bias));
-    if (!e->row_own[row]) CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, engine_row_params(e), 1));
-    if (!e->row_rules[row]) {
-        e->row_rules[row] = 1;
-        e->n_rules += 1;
-        if (!e->row_own[row] && !e->row_guide[row] && !e->row_ngram[row] && !e->row_stop[row]) e->n_own += 1;
-    }
+    // not enter_row_stage(): the entry is rewritten whenever the row has no parameters of its own, staged already or not (known wart)
+    if (!e->stage.has(row, ROW_PARAMS)) CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, engine_row_params(e), 1));
+    e->stage.attach(row, ROW_RULES);
     return DOTS_OK;
 }
 
@@ -2424,8 +2380,8 @@ int dots_set_token_bytes(DotsEngine* e, const int32_t* offsets, const uint8_t* b
         if (offsets[t + 1] < offsets[t]) return e->fail(DOTS_E_INVALID, "token bytes: offsets must not decrease (token %d)", t);
     const size_t n = (size_t)offsets[V];
     if (n && !bytes) return e->fail(DOTS_E_INVALID, "null argument");
-    if (e->n_guided > 0) return e->fail(DOTS_E_STATE, "token bytes cannot change while %d row(s) hold a guide", e->n_guided);
-    if (e->n_stop_rows > 0) return e->fail(DOTS_E_STATE, "token bytes cannot change while %d row(s) hold stop strings", e->n_stop_rows);
+    if (e->stage.rows(ROW_GUIDE) > 0) return e->fail(DOTS_E_STATE, "token bytes cannot change while %d row(s) hold a guide", e->stage.rows(ROW_GUIDE));
+    if (e->stage.rows(ROW_STOP) > 0) return e->fail(DOTS_E_STATE, "token bytes cannot change while %d row(s) hold stop strings", e->stage.rows(ROW_STOP));
     CK(hipSetDevice(e->device));
     CK(hipStreamSynchronize(e->stream));                   // nothing in flight reads the previous image
     if (e->tok_off) { e->release(e->tok_off); e->tok_off = nullptr; }
@@ -2480,20 +2436,15 @@ int dots_set_row_guide(DotsEngine* e, int row, int32_t id) {
     if (!e) return DOTS_E_INVALID;
     if (row < 0 || row >= e->cfg.max_batch) return e->fail(DOTS_E_INVALID, "row %d out of range [0, %d)", row, e->cfg.max_batch);
     CK(hipSetDevice(e->device));
-    if (id < 0) return e->d_guides ? clear_row_guide(e, row) : DOTS_OK;
+    if (id < 0) return clear_row_feature(e, row, ROW_GUIDE);
     if (id >= (int)e->guides.size() || !e->guides[id].table) return e->fail(DOTS_E_INVALID, "no guide %d", id);
     if (!e->tok_off) return e->fail(DOTS_E_STATE, "the token bytes are not set (dots_set_token_bytes): a guide cannot judge any token");
     RET(ensure_row_table(e));
     RET(ensure_guide_state(e));
     const DotsEngine::Guide& g = e->guides[id];
     CK(launch_set_row_guide(e->stream, e->d_guides, row, RowGuide{g.table, g.accepting, g.n_states, g.start, g.start, 0}));
-    if (!e->row_own[row] && !e->row_rules[row] && !e->row_guide[row] && !e->row_ngram[row] && !e->row_stop[row])
-        CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, engine_row_params(e), 1));
-    if (e->row_guide[row]) e->guides[e->row_guide[row] - 1].rows -= 1;
-    else {
-        e->n_guided += 1;
-        if (!e->row_own[row] && !e->row_rules[row] && !e->row_ngram[row] && !e->row_stop[row]) e->n_own += 1;
-    }
+    if (e->stage.has(row, ROW_GUIDE)) e->guides[e->row_guide[row] - 1].rows -= 1;
+    RET(enter_row_stage(e, row, ROW_GUIDE));
     e->row_guide[row] = id + 1;
     e->guides[id].rows += 1;
     return DOTS_OK;
@@ -2503,20 +2454,13 @@ int dots_set_row_ngram(DotsEngine* e, int row, const DotsNgramRule* r) {
     if (!e) return DOTS_E_INVALID;
     if (row < 0 || row >= e->cfg.max_batch) return e->fail(DOTS_E_INVALID, "row %d out of range [0, %d)", row, e->cfg.max_batch);
     CK(hipSetDevice(e->device));
-    if (!r) return e->d_ngram ? clear_row_ngram(e, row) : DOTS_OK;
+    if (!r) return clear_row_feature(e, row, ROW_NGRAM);
     RowNgram rn;
     RET(check_ngram_rule(e, *r, e->cfg.vocab_size, e->cfg.max_seq_len, &rn));
     RET(ensure_row_table(e));
     RET(ensure_ngram_state(e));
     CK(launch_set_row_ngram(e->stream, e->d_ngram, row, rn));
-    if (!e->row_own[row] && !e->row_rules[row] && !e->row_guide[row] && !e->row_ngram[row] && !e->row_stop[row])
-        CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, engine_row_params(e), 1));
-    if (!e->row_ngram[row]) {
-        e->row_ngram[row] = 1;
-        e->n_ngram += 1;
-        if (!e->row_own[row] && !e->row_rules[row] && !e->row_guide[row] && !e->row_stop[row]) e->n_own += 1;
-    }
-    return DOTS_OK;
+    return enter_row_stage(e, row, ROW_NGRAM);
 }
 
 // ---------------------------------------------------------------------------------- stop strings
@@ -2570,7 +2514,7 @@ int dots_set_row_stop(DotsEngine* e, int row, int32_t handle, int min_tokens) {
     if (!e->tok_off) return e->fail(DOTS_E_STATE, "the token bytes are not set (dots_set_token_bytes): a stop string cannot be matched");
     if (row < 0 || row >= e->cfg.max_batch) return e->fail(DOTS_E_INVALID, "row %d out of range [0, %d)", row, e->cfg.max_batch);
     CK(hipSetDevice(e->device));
-    if (handle == 0) return e->d_stop ? clear_row_stop(e, row) : DOTS_OK;
+    if (handle == 0) return clear_row_feature(e, row, ROW_STOP);
     const int id = handle - 1;
     if (id < 0 || id >= (int)e->stops.size() || !e->stops[id].table) return e->fail(DOTS_E_INVALID, "no stop automaton %d", handle);
     if (min_tokens < 0) return e->fail(DOTS_E_INVALID, "stop strings: min_tokens must be >= 0");
@@ -2582,7 +2526,7 @@ int dots_row_stop_hit(DotsEngine* e, int row, int32_t* out) {
     if (!e->tok_off) return e->fail(DOTS_E_STATE, "the token bytes are not set (dots_set_token_bytes): no row holds stop strings");
     if (row < 0 || row >= e->cfg.max_batch) return e->fail(DOTS_E_INVALID, "row %d out of range [0, %d)", row, e->cfg.max_batch);
     out[0] = -1; out[1] = 0; out[2] = 0; out[3] = -1;
-    if (!e->d_stop || !e->row_stop[row]) return DOTS_OK;
+    if (!e->stage.has(row, ROW_STOP)) return DOTS_OK;
     CK(hipSetDevice(e->device));
     RowStop rs;
     CK(hipMemcpyAsync(&rs, e->d_stop + row, sizeof(rs), hipMemcpyDeviceToHost, e->stream));
@@ -2662,7 +2606,7 @@ int dots_row_guide_state(DotsEngine* e, int row, int32_t* state_out) {
     if (!e || !state_out) return e ? e->fail(DOTS_E_INVALID, "null argument") : DOTS_E_INVALID;
     if (row < 0 || row >= e->cfg.max_batch) return e->fail(DOTS_E_INVALID, "row %d out of range [0, %d)", row, e->cfg.max_batch);
     *state_out = -1;
-    if (!e->d_guides || !e->row_guide[row]) return DOTS_OK;
+    if (!e->stage.has(row, ROW_GUIDE)) return DOTS_OK;
     CK(hipSetDevice(e->device));
     RowGuide rg;
     CK(hipMemcpyAsync(&rg, e->d_guides + row, sizeof(rg), hipMemcpyDeviceToHost, e->stream));

@@ -1,0 +1,43 @@
+// Which rows the per-row selection stage owns, and why.  Host only: no HIP, no engine type, nothing but DOTS_MAX_BATCH
+// (kernels.h; a stand-alone program defines it itself — tests/row_stage_model.cpp checks this record against a brute-force model).
+//
+// A row is selected by the per-row stage exactly while it carries at least one feature; its device `own` flag is 1 for as long.  This
+// record is the only holder of that fact: the engine asks it, and acts on the entered / left transitions that attach / detach report.
+#pragma once
+
+#ifndef DOTS_MAX_BATCH
+#error "row_stage.h needs DOTS_MAX_BATCH"
+#endif
+
+enum RowFeature { ROW_PARAMS, ROW_RULES, ROW_GUIDE, ROW_NGRAM, ROW_STOP, ROW_FEATURES };
+
+struct RowStage {
+    bool has(int row, RowFeature f) const { return (bits[row] >> f) & 1u; }
+    bool staged(int row) const { return bits[row] != 0; }          // carries any feature
+    int rows(RowFeature f) const { return n_rows[f]; }             // rows that carry f
+    int staged_rows() const { return n_staged; }                   // rows that carry any feature: > 0 = the per-row stage runs
+    // true: the row has just entered the stage.  A feature the row already holds changes nothing
+    bool attach(int row, RowFeature f) {
+        if (has(row, f)) return false;
+        const bool entered = !staged(row);
+        bits[row] |= 1u << f;
+        n_rows[f] += 1;
+        n_staged += entered;
+        return entered;
+    }
+    // true: the row has just left the stage.  A feature the row does not hold changes nothing
+    bool detach(int row, RowFeature f) {
+        if (!has(row, f)) return false;
+        bits[row] &= ~(1u << f);
+        n_rows[f] -= 1;
+        const bool left = !staged(row);
+        n_staged -= left;
+        return left;
+    }
+    void reset() { *this = RowStage{}; }
+
+private:
+    unsigned char bits[DOTS_MAX_BATCH] = {0};
+    int n_rows[ROW_FEATURES] = {0};
+    int n_staged = 0;
+};
