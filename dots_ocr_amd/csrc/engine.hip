@@ -257,6 +257,13 @@ struct DotsEngine {
     int spec_k = 0, spec_min_n = 0, spec_max_n = 0;
     int32_t *sp_drafts = nullptr, *sp_ndraft = nullptr, *sp_nlive = nullptr, *sp_tokens = nullptr, *sp_ctx = nullptr, *sp_table = nullptr;
     unsigned long long* sp_stats = nullptr;
+    // which staged rows speculate (dots_set_speculation_rows: DOTS_SPEC_ROWS_* bits, 0 = plain greedy rows only) and the device array of
+    // every row's speculation class (kernels.h SpecRow), which spec_row_class() derives and the row setters write in stream order;
+    // sp_cand: the candidates of the draft rows of sampled slots.  row_pen / row_sampled: of a row that holds ROW_PARAMS, whether its
+    // parameters carry a penalty / a temperature > 0 (the two facts about them the class needs)
+    int spec_rows = 0;
+    int32_t *sp_cls = nullptr, *sp_cand = nullptr;
+    bool row_pen[DOTS_MAX_BATCH] = {false}, row_sampled[DOTS_MAX_BATCH] = {false};
     int out_cap = 0;                       // row stride of out_ids for the current generation
     bf16_t *d_h = nullptr, *d_q = nullptr, *d_att = nullptr, *d_act = nullptr, *d_xn = nullptr;      // d_xn: normalised rows of batches above 32 rows (decode_b64.hip)
     float* d_part_h = nullptr;                     // [DEC_KSPLIT_PARTS][DOTS_MAX_BATCH][hidden] fp32: the K-quarter sums of a projection above 32 rows (decode_b64.hip)
@@ -281,11 +288,12 @@ struct DotsEngine {
     // the output buffer) or slot mode (out_cap = 0), number of EOS ids, whether any row carries its own parameters (rowp: the per-row
     // selection stage), whether any row returns logprobs (lp), whether any row carries logit rules (rules: the stage then gets their
     // table), whether any row holds a guide (guided: the mask kernel and the guides' tables), whether any row carries an n-gram rule (ngram:
-    // the ban kernel and its bits), the draft count of a speculating step (spec: 0 = the plain step); engine-wide sampling changes drop
+    // the ban kernel and its bits), the draft count of a speculating step (spec: 0 = the plain step), whether that step draws the draft
+    // rows of sampled slots (draw: the two launches of launch_spec_draw); engine-wide sampling changes drop
     // the cache (dots_set_sampling), per-row ones live in device memory.  step_key() builds the key from the engine's state: a feature that
     // changes what a step launches adds a member here and a line there
     struct StepKey {
-        int rows, splits, out_cap, n_eos, part, rowp, lp, rules, guided, ngram, spec;
+        int rows, splits, out_cap, n_eos, part, rowp, lp, rules, guided, ngram, spec, draw;
         bool operator==(const StepKey& o) const { return std::memcmp(this, &o, sizeof(StepKey)) == 0; }
     };
     static_assert(std::has_unique_object_representations_v<StepKey>, "StepKey is compared bytewise: plain ints, no padding");
@@ -920,9 +928,39 @@ StepState step_state(const DotsEngine* e, int advance, const int32_t* sel) {
     return st;
 }
 
+// does a speculating step draw the draft rows of sampled slots (launch_spec_draw)?  Only while rows with parameters may speculate and at
+// least one row holds parameters: with dots_set_speculation_rows at 0 a step launches what it always did
+bool spec_draws(const DotsEngine* e) {
+    return e->slot_mode && e->spec_k > 0 && (e->spec_rows & SPEC_ROWS_SAMPLED) && e->stage.rows(ROW_PARAMS) > 0;
+}
+
 SpecState spec_state(const DotsEngine* e) {
-    return SpecState{e->sp_drafts, e->sp_ndraft, e->sp_nlive, e->sp_tokens, e->sp_ctx, e->sp_table, e->sp_stats,
-                     e->stage.staged_rows() > 0 ? e->d_row_own : nullptr, e->n_lp > 0 ? e->d_row_lp : nullptr, e->spec_k, e->temperature > 0.f ? 0 : 1};
+    return SpecState{e->sp_drafts, e->sp_ndraft, e->sp_nlive, e->sp_tokens, e->sp_ctx, e->sp_table, e->sp_stats, e->sp_cls,
+                     spec_draws(e) ? e->sp_cand : nullptr, e->spec_k, e->temperature > 0.f ? 0 : 1};
+}
+
+// The speculation class of a row (kernels.h SpecRow), from the host's record alone.  THE place that decides it: the stage
+// features and the penalty of the row's parameters through RowStage::speculates, and logprobs (not a stage feature).  The engine-wide
+// temperature is not a row's fact: the kernels get it as engine_greedy.
+int spec_row_class(const DotsEngine* e, int row) {
+    if (e->row_lp[row] >= 0 || !e->stage.speculates(row, e->row_pen[row], e->spec_rows)) return SPEC_ROW_NONE;
+    return e->stage.has(row, ROW_PARAMS) && e->row_sampled[row] ? SPEC_ROW_DRAW : SPEC_ROW_ARGMAX;
+}
+
+// the row's class to the device in stream order, after anything that may change it (the array exists once speculation was switched on)
+int sync_spec_class(DotsEngine* e, int row) {
+    if (e->sp_cls) CK(launch_spec_set_class(e->stream, e->sp_cls, row, spec_row_class(e, row)));
+    return DOTS_OK;
+}
+
+// every row's class from the host's record in one copy (the setting changed, or the array is new); the call waits for it
+int upload_spec_classes(DotsEngine* e) {
+    if (!e->sp_cls) return DOTS_OK;
+    int32_t cls[DOTS_MAX_BATCH];
+    for (int b = 0; b < DOTS_MAX_BATCH; ++b) cls[b] = spec_row_class(e, b);
+    CK(hipMemcpyAsync(e->sp_cls, cls, sizeof(cls), hipMemcpyHostToDevice, e->stream));
+    CK(hipStreamSynchronize(e->stream));
+    return DOTS_OK;
 }
 
 // greedy arg max or temperature / top-p sampling over the fp32 logits of the step
@@ -1043,7 +1081,7 @@ RowParams engine_row_params(const DotsEngine* e) { return RowParams{e->temperatu
 int enter_row_stage(DotsEngine* e, int row, RowFeature f) {
     RET(ensure_row_table(e));
     if (e->stage.attach(row, f) && f != ROW_PARAMS) CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, engine_row_params(e), 1));
-    return DOTS_OK;
+    return sync_spec_class(e, row);
 }
 
 // Feature f comes off row `row`: with its last feature the row leaves the stage (entry and own flag zeroed); own parameters taken off a
@@ -1052,7 +1090,7 @@ int leave_row_stage(DotsEngine* e, int row, RowFeature f) {
     if (!e->stage.has(row, f)) return DOTS_OK;
     if (e->stage.detach(row, f)) CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, RowParams{}, 0));
     else if (f == ROW_PARAMS) CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, engine_row_params(e), 1));
-    return DOTS_OK;
+    return sync_spec_class(e, row);
 }
 
 // feature f off row `row` (stream ordered): the feature's own table entry and reference count, then the stage
@@ -1212,7 +1250,7 @@ int set_row_lp(DotsEngine* e, int row, int top_n) {
     CK(launch_set_row_lp(e->stream, e->d_row_lp, row, top_n));
     e->row_lp[row] = top_n;
     e->n_lp += (top_n >= 0 ? 1 : 0) - (was ? 1 : 0);
-    return DOTS_OK;
+    return sync_spec_class(e, row);
 }
 
 // CU-masked side streams of the vision prefetch, created on first use.  Mask bit i = CU i / 8 of XCD i % 8 (profiles/r01_probe_cu_mask.txt):
@@ -1522,6 +1560,9 @@ int decode_step_launches(DotsEngine* e, int n_splits, int part = 0) {
     CK(launch_dec_lmhead(s, e->d_h, e->final_norm, e->lm_head_d, e->lm_head_s, e->d_logits, B, H, c.vocab_size, c.rms_norm_eps, part ? e->dec_cus : 0, e->d_xn,
                          pend ? e->d_part_h : nullptr, pend_scale));
     if (spec_k) CK(launch_spec_argmax(s, sp, e->d_logits, c.vocab_size, c.vocab_size, rows, e->am_val, e->am_idx));
+    // the candidates of the draft rows of sampled slots, before the selection stage moves out_lens: draft row j draws with counter out_lens + j
+    if (spec_k && sp.cand)
+        CK(launch_spec_draw(s, sp, e->d_logits, c.vocab_size, c.vocab_size, rows, e->d_rowp, e->d_row_thr, e->out_lens, e->am_val, e->am_idx));
     e->B_sel = rows;
     e->sel_now = e->d_sel;
     RET(select_tokens(e, 1));
@@ -1529,9 +1570,10 @@ int decode_step_launches(DotsEngine* e, int n_splits, int part = 0) {
         // the selection stage committed row 0 of every slot; the accept walk commits what the drafts got right, then the drafter reads
         // the grown output
         const StepState st = step_state(e, 1, e->d_sel);
-        CK(launch_spec_accept(s, sp, st, rows, e->am_val, e->am_idx));
+        CK(launch_spec_accept(s, sp, st, rows, e->am_val, e->am_idx,
+                              e->d_stop ? StopSel{e->d_stop, e->tok_off, e->tok_bytes, c.vocab_size, 0} : StopSel{}));
         if (e->spec_max_n > 0)
-            CK(launch_ngram_draft(s, st.out_ids, st.out_lens, st.out_stride, st.finished, st.sel, sp.own, sp.lp, sp.engine_greedy, rows, spec_k, e->spec_min_n,
+            CK(launch_ngram_draft(s, st.out_ids, st.out_lens, st.out_stride, st.finished, st.sel, sp.cls, sp.engine_greedy, rows, spec_k, e->spec_min_n,
                                   e->spec_max_n, e->sp_drafts, DOTS_MAX_SPEC_DRAFTS, e->sp_ndraft));
     }
     return DOTS_OK;
@@ -1549,6 +1591,7 @@ DotsEngine::StepKey step_key(const DotsEngine* e, int rows, int n_splits, int ou
     k.guided = e->stage.rows(ROW_GUIDE) > 0;
     k.ngram = e->stage.rows(ROW_NGRAM) > 0;
     k.spec = e->slot_mode ? e->spec_k : 0;
+    k.draw = spec_draws(e);
     return k;
 }
 
@@ -2071,6 +2114,7 @@ int dots_slots_reset(DotsEngine* e) {
     std::fill(e->row_lp, e->row_lp + DOTS_MAX_BATCH, -1);
     e->n_lp = 0;
     if (e->sp_ndraft) CK(hipMemsetAsync(e->sp_ndraft, 0, DOTS_MAX_BATCH * 4, s));
+    if (e->sp_cls) CK(hipMemsetAsync(e->sp_cls, 0, DOTS_MAX_BATCH * 4, s));         // SPEC_ROW_ARGMAX: no row carries anything
     CK(hipStreamSynchronize(s));
     e->slot_mode = true;
     e->sel_dirty = true;
@@ -2338,6 +2382,8 @@ int dots_set_row_sampling(DotsEngine* e, int row, const DotsSamplingParams* p) {
     RET(ensure_row_table(e));
     if (rp.repetition_penalty != 1.f || rp.frequency_penalty != 0.f || rp.presence_penalty != 0.f) RET(ensure_pen_state(e));
     CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, rp, 1));
+    e->row_pen[row] = rp.repetition_penalty != 1.f || rp.frequency_penalty != 0.f || rp.presence_penalty != 0.f;
+    e->row_sampled[row] = rp.temperature > 0.f;
     return enter_row_stage(e, row, ROW_PARAMS);
 }
 
@@ -2369,7 +2415,7 @@ int dots_set_row_logit_rules(DotsEngine* e, int row, const DotsLogitRules* r) {
     // not enter_row_stage(): the entry is rewritten whenever the row has no parameters of its own, staged already or not (known wart)
     if (!e->stage.has(row, ROW_PARAMS)) CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, engine_row_params(e), 1));
     e->stage.attach(row, ROW_RULES);
-    return DOTS_OK;
+    return sync_spec_class(e, row);
 }
 
 int dots_set_token_bytes(DotsEngine* e, const int32_t* offsets, const uint8_t* bytes) {
@@ -2561,7 +2607,10 @@ int dots_set_speculation(DotsEngine* e, int k, int min_n, int max_n) {
             CK(hipMemcpyAsync(e->sp_table, idle.data(), idle.size() * 4, hipMemcpyHostToDevice, s));
             CK(hipStreamSynchronize(s));
         }
+        if (!e->sp_cand) CK(e->alloc(&e->sp_cand, (size_t)DOTS_MAX_BATCH * DOTS_MAX_SPEC_DRAFTS));
+        if (!e->sp_cls) CK(e->alloc(&e->sp_cls, (size_t)DOTS_MAX_BATCH));
         CK(e->alloc(&e->sp_stats, (size_t)(DOTS_MAX_BATCH + 1) * 3));      // set last, it is the guard above
+        RET(upload_spec_classes(e));                                       // rows may have taken features before the array existed
     }
     if (e->sp_stats) {
         CK(hipMemsetAsync(e->sp_stats, 0, (size_t)(DOTS_MAX_BATCH + 1) * 3 * sizeof(unsigned long long), s));
@@ -2573,6 +2622,18 @@ int dots_set_speculation(DotsEngine* e, int k, int min_n, int max_n) {
     e->spec_min_n = k > 0 && max_n > 0 ? min_n : 0;
     e->spec_max_n = k > 0 ? max_n : 0;
     return DOTS_OK;
+}
+
+int dots_set_speculation_rows(DotsEngine* e, int flags) {
+    if (!e) return DOTS_E_INVALID;
+    if (flags & ~SPEC_ROWS_ALL) return e->fail(DOTS_E_INVALID, "unknown speculation row flags 0x%x (DOTS_SPEC_ROWS_SAMPLED | DOTS_SPEC_ROWS_STOP)", flags);
+    if (e->slot_mode)
+        for (int b = 0; b < e->cfg.max_batch; ++b)
+            if (e->slot_active[b]) return e->fail(DOTS_E_STATE, "the speculating rows cannot change while slot %d is occupied", b);
+    CK(hipSetDevice(e->device));
+    e->spec_rows = flags;
+    drop_step_graphs(e);                                     // a captured step bakes in whether it draws the draft rows of sampled slots
+    return upload_spec_classes(e);                           // free slots may hold features: every row's class under the new setting
 }
 
 int dots_set_row_drafts(DotsEngine* e, int row, const int32_t* ids_host, int n) {
@@ -3405,7 +3466,7 @@ int dots_op_ngram_draft(DotsEngine* e, const int32_t* hist_dev, const int32_t* h
     if (B < 1 || B > DOTS_MAX_BATCH || hist_stride < 1 || k < 1 || k > DOTS_MAX_SPEC_DRAFTS || min_n < 1 || max_n < min_n || max_n > DOTS_MAX_NGRAM_SIZE)
         return e->fail(DOTS_E_INVALID, "ngram_draft: B in [1, %d], k in [1, %d], 1 <= min_n <= max_n <= %d", DOTS_MAX_BATCH, DOTS_MAX_SPEC_DRAFTS, DOTS_MAX_NGRAM_SIZE);
     CK(hipSetDevice(e->device));
-    CK(launch_ngram_draft(e->stream, hist_dev, hist_lens_dev, hist_stride, nullptr, nullptr, nullptr, nullptr, 1, B, k, min_n, max_n, drafts_dev, k, n_drafts_dev));
+    CK(launch_ngram_draft(e->stream, hist_dev, hist_lens_dev, hist_stride, nullptr, nullptr, nullptr, 1, B, k, min_n, max_n, drafts_dev, k, n_drafts_dev));
     CK(hipStreamSynchronize(e->stream));
     return DOTS_OK;
 }

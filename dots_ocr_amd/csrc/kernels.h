@@ -244,20 +244,31 @@ hipError_t launch_set_row_stop(hipStream_t s, RowStop* table, int row, const Row
 hipError_t launch_stop_reset_rows(hipStream_t s, RowStop* table, const int32_t* dst, int n);
 // table[dst[i]] = table[src] at the root with no hit, i < n (dots_slots_fork: the children inherit the source's automaton and min_tokens)
 hipError_t launch_stop_fork_rows(hipStream_t s, RowStop* table, int src, const int32_t* dst, int n);
-// ---- spec.hip: n-gram speculative decoding of greedy rows
+// ---- spec.hip: n-gram speculative decoding
 // A speculating step runs over R = rows x (k + 1) rows, draft-major: row j * rows + b carries token j of (last token, draft 1 .. k) of slot
 // b at context ctx + j on the slot's own KV pages.  SpecState: the slots' drafts of the next step (drafts [DOTS_MAX_BATCH]
 // [DOTS_MAX_SPEC_DRAFTS], n_draft [DOTS_MAX_BATCH]), the expanded row arrays of the step (tokens / ctx_len [DOTS_MAX_BATCH], block_table
 // [DOTS_MAX_BATCH][max_pages]), n_live [DOTS_MAX_BATCH] (draft rows of slot b this step verifies; -1: the slot takes no step) and the
-// counters stats [DOTS_MAX_BATCH + 1][3] (steps, drafted, accepted; the last row holds the totals).  own / lp: the per-row selection flags
-// and the logprob table (nullptr: none exist) — a row that carries either, or any row while engine_greedy == 0, verifies no draft.
+// counters stats [DOTS_MAX_BATCH + 1][3] (steps, drafted, accepted; the last row holds the totals).
+// cls [DOTS_MAX_BATCH]: the speculation class of every row (SpecRow), a host fact (engine.hip spec_row_class: the row's stage features, its
+// parameters, its logprobs and dots_set_speculation_rows) that the stream-ordered row setters write, so it holds inside captured chunks.
+// The kernels ask nothing else about a row; while engine_greedy == 0 (an engine-wide temperature) no row verifies a draft whatever its class.
+// cand [DOTS_MAX_BATCH][DOTS_MAX_SPEC_DRAFTS]: the candidate tokens of the live draft rows of SPEC_ROW_DRAW slots (spec_draw_kernel);
+// nullptr until a step runs that kernel.
 #ifndef DOTS_MAX_SPEC_DRAFTS
 #define DOTS_MAX_SPEC_DRAFTS 15
 #endif
+// 0 is what a row nobody touched holds: plain greedy
+enum SpecRow : int32_t {
+    SPEC_ROW_ARGMAX = 0,       // speculates; a draft row's candidate is its arg max
+    SPEC_ROW_NONE = 1,         // verifies no draft and drafts nothing
+    SPEC_ROW_DRAW = 2,         // speculates; a draft row's candidate is drawn by the row's own sampler (parameters with temperature > 0)
+};
 struct SpecState {
     int32_t *drafts, *n_draft, *n_live, *tokens, *ctx_len, *block_table;
     unsigned long long* stats;
-    const int32_t *own, *lp;
+    const int32_t* cls;
+    int32_t* cand;
     int32_t k, engine_greedy;
 };
 // the step's row arrays from the slots' state (st: the StepState of the selection stage; block_table [rows][max_pages]); an idle draft row
@@ -265,16 +276,24 @@ struct SpecState {
 hipError_t launch_spec_expand(hipStream_t s, const SpecState& sp, const StepState& st, const int32_t* block_table, int max_pages, int rows, int scratch_page);
 // arg-max partials (as launch_argmax_step's first kernel) of the live draft rows [rows, rows * (k + 1)) of logits
 hipError_t launch_spec_argmax(hipStream_t s, const SpecState& sp, const float* logits, int V, int ld, int rows, float* pval, int32_t* pidx);
+// The candidates of the live draft rows of SPEC_ROW_DRAW slots, after launch_spec_argmax and BEFORE the selection stage commits anything:
+// draft row r = j * rows + b is selected with params[b] over logits row r with counter out_lens[b] + j, by the selection stage's own
+// arithmetic (select_dev.h), into sp.cand[b][j - 1].  thr [DOTS_MAX_BATCH] is RowSel::thr: the stage uses entries [0, rows), the draft rows
+// entries [rows, rows * (k + 1)).  Two launches of rows * k workgroups; every other draft row's workgroup exits at once.
+hipError_t launch_spec_draw(hipStream_t s, const SpecState& sp, const float* logits, int V, int ld, int rows, const RowParams* params, uint32_t* thr,
+                            const int32_t* out_lens, const float* pval, const int32_t* pidx);
 // after the selection stage committed the first `rows` rows: per slot, while the row is not finished and draft j equals the token just
-// committed, commit the arg max of draft row j + 1 (commit_token: EOS, cap and output as in a sequential step); counts into sp.stats and
-// clears the slot's drafts
-hipError_t launch_spec_accept(hipStream_t s, const SpecState& sp, const StepState& st, int rows, const float* pval, const int32_t* pidx);
+// committed, commit the candidate of draft row j + 1 (its arg max, or sp.cand for a SPEC_ROW_DRAW slot) through commit_token: EOS, cap,
+// output and — stop.rows != nullptr — the row's stop automaton as in a sequential step; counts into sp.stats and clears the slot's drafts
+hipError_t launch_spec_accept(hipStream_t s, const SpecState& sp, const StepState& st, int rows, const float* pval, const int32_t* pidx, const StopSel& stop);
 // drafts[b * draft_stride + 0 .. n_draft[b]) = the continuation of the longest suffix n-gram (min_n .. max_n) of out_ids[b * out_stride +
 // 0 .. out_lens[b]) that occurred before, at most k ids (the rule: include/dots_ocr_hip.h).  Rows that sel masks out, finished rows, rows
-// with own[b] != 0 or lp[b] >= 0, and every row while engine_greedy == 0 draft nothing (finished / sel / own / lp may be nullptr).
+// with cls[b] == SPEC_ROW_NONE, and every row while engine_greedy == 0 draft nothing (finished / sel / cls may be nullptr).
 hipError_t launch_ngram_draft(hipStream_t s, const int32_t* out_ids, const int32_t* out_lens, int out_stride, const int32_t* finished, const int32_t* sel,
-                              const int32_t* own, const int32_t* lp, int engine_greedy, int B, int k, int min_n, int max_n, int32_t* drafts,
-                              int draft_stride, int32_t* n_draft);
+                              const int32_t* cls, int engine_greedy, int B, int k, int min_n, int max_n, int32_t* drafts, int draft_stride,
+                              int32_t* n_draft);
+// cls[row] = value, in stream order
+hipError_t launch_spec_set_class(hipStream_t s, int32_t* cls, int row, int value);
 // drafts[row][0 .. n) = ids_host, n_draft[row] = n, in stream order (the ids travel as a kernel argument)
 hipError_t launch_spec_set_drafts(hipStream_t s, int32_t* drafts, int32_t* n_draft, int row, const int32_t* ids_host, int n);
 

@@ -1,5 +1,5 @@
-// N-gram speculative decoding of greedy rows: the three kernels a speculating decode step adds around the unchanged layer
-// loop, and the stream-ordered writer of a row's drafts.
+// N-gram speculative decoding: the kernels a speculating decode step adds around the unchanged layer loop, and the
+// stream-ordered writers of a row's drafts and of its speculation class.
 //
 // A slot b that holds d drafts occupies 1 + d rows of one step.  The step runs over R = rows x (k + 1) rows, draft-major: row
 // r = j * rows + b carries token j of (last committed token, draft 1 .. k) of slot b at context ctx + j, and all the rows of a slot name
@@ -10,16 +10,19 @@
 //
 //   spec_expand_kernel   head of the step: tokens, context lengths and block-table rows of the R rows from the slots' state and drafts
 //   spec_argmax_kernel   after the lm_head: the arg-max partials of the live draft rows (the merge rule of argmax_partial_kernel)
+//   spec_thresh_kernel, spec_draw_kernel   then, only while a row with parameters may speculate (dots_set_speculation_rows): the candidates
+//                        of the live draft rows of SPEC_ROW_DRAW slots, by the selection stage's own arithmetic (select_dev.h)
 //   spec_accept_kernel   after the selection stage: walks a slot's drafts and commits through commit_token while they hold
 //   ngram_draft_kernel   end of the step: the next step's drafts from the row's own output (prompt lookup without the prompt)
 //
-// Draft row (b, j >= 1) is LIVE iff slot b is selected, not finished, plain greedy (no parameters, rules, guide or n-gram rule of its own,
-// no logprobs, engine-wide arg max), holds at least j drafts and j < max_len[b] - out_lens[b]: a live row writes KV position ctx + j, and
+// Draft row (b, j >= 1) is LIVE iff slot b is selected, not finished, a speculating row (sp.cls[b] != SPEC_ROW_NONE: the host's fact,
+// kernels.h SpecRow; engine-wide arg max), holds at least j drafts and j < max_len[b] - out_lens[b]: a live row writes KV position ctx + j, and
 // the last condition is "the sequence may still reach that position", which is also what its pages cover (the host lowers max_len when
 // the pool runs dry).  Every other draft row idles like a released slot: context 0 on the scratch page.
 #include <climits>
 
 #include "kernels.h"
+#include "select_dev.h"
 #include "step_dev.h"
 
 namespace {
@@ -29,7 +32,7 @@ constexpr int ND_THREADS = 256;
 // the drafts slot b verifies in this step, or -1 when the slot takes no step at all (free or finished)
 DEVI int spec_live_drafts(const SpecState& sp, const StepState& st, int b) {
     if ((st.sel && !st.sel[b]) || st.finished[b]) return -1;
-    if (!sp.engine_greedy || (sp.own && sp.own[b]) || (sp.lp && sp.lp[b] >= 0)) return 0;
+    if (!sp.engine_greedy || sp.cls[b] == SPEC_ROW_NONE) return 0;
     const int room = (st.max_len ? st.max_len[b] : st.cap) - st.out_lens[b] - 1;      // draft rows whose token could still be committed
     return max(0, min(min(sp.n_draft[b], sp.k), room));
 }
@@ -74,14 +77,62 @@ __global__ __launch_bounds__(256) void spec_argmax_kernel(const float* __restric
     }
 }
 
+// The candidates of the draft rows of sampled slots.  grid (rows * k): workgroup x serves draft row r = rows + x = j * rows + b, and exits at
+// once unless the row is live and its slot is SPEC_ROW_DRAW.  The row is selected exactly as select_thresh_kernel / select_rows_kernel
+// (decode.hip) select row b of a sequential step at that position: the same device functions over logits row r (a speculating row has no
+// penalty, rules, guide or n-gram rule, so the raw logits are what the stage would read), params[b], the softmax maximum from the partials
+// spec_argmax_kernel left for r, and the counter out_lens[b] + j — out_lens as the head of the step saw it: both kernels run before the
+// selection stage commits.
+__global__ __launch_bounds__(SEL_THREADS) void spec_thresh_kernel(const float* __restrict__ logits, int V, int ld, int rows, SpecState sp,
+                                                                  const RowParams* __restrict__ params, uint32_t* __restrict__ thr,
+                                                                  const float* __restrict__ pval, const int32_t* __restrict__ pidx) {
+    __shared__ SelLds L;
+    const int r = rows + blockIdx.x, j = r / rows, b = r - j * rows;
+    if (j > sp.n_live[b] || sp.cls[b] != SPEC_ROW_DRAW) return;      // uniform per workgroup
+    const RowParams p = params[b];
+    if (!(p.temperature > 0.f)) return;
+    if (sel_unfiltered(p)) {
+        if (threadIdx.x == 0) thr[r] = SEL_NONE;
+        return;
+    }
+    merge_partials(pval, pidx, r, &L.best, &L.bi);
+    sel_threshold(logits + (size_t)r * ld, V, p, L.best, thr + r, L);
+}
+
+__global__ __launch_bounds__(SEL_THREADS) void spec_draw_kernel(const float* __restrict__ logits, int V, int ld, int rows, SpecState sp,
+                                                                const RowParams* __restrict__ params, const uint32_t* __restrict__ thr,
+                                                                const int32_t* __restrict__ out_lens, const float* __restrict__ pval,
+                                                                const int32_t* __restrict__ pidx) {
+    __shared__ float s_best;
+    __shared__ int s_bi;
+    __shared__ DrawLds D;
+    const int r = rows + blockIdx.x, j = r / rows, b = r - j * rows;
+    if (j > sp.n_live[b] || sp.cls[b] != SPEC_ROW_DRAW) return;      // uniform per workgroup
+    merge_partials(pval, pidx, r, &s_best, &s_bi);
+    const RowParams p = params[b];
+    int tok = -1;
+    if (p.temperature > 0.f) tok = sel_draw(logits + (size_t)r * ld, V, p, s_best, thr[r], (uint32_t)(out_lens[b] + j), D);
+    if (threadIdx.x == 0) sp.cand[b * DOTS_MAX_SPEC_DRAFTS + j - 1] = tok >= 0 ? tok : s_bi;      // no token: the arg max, as select_rows_kernel
+}
+
 // grid (rows), one wave.  Row 0's token is committed (the selection stage ran); draft j is right iff it equals the token committed before
-// it, and then the arg max of draft row j + 1 is the next token of the sequential run.
+// it, and then the candidate of draft row j + 1 — its arg max, or for a SPEC_ROW_DRAW slot the token spec_draw_kernel drew — is the next
+// token of the sequential run.
+// The commit is commit_token with the row's stop automaton (stop.rows != nullptr: some row of the engine held one; a row without one walks
+// nothing).  That is exactly what commit_row (decode.hip) does for a speculating row in a sequential step: such a row has no penalty (no
+// count to add), no rules (rules == nullptr) and no guide (commit_token reads the guide only through rows[b].table, which is null), so
+// EOS, the cap, min_tokens and the hit record come out of the same code, and a match finishes the row mid-walk.
 __global__ __launch_bounds__(64) void spec_accept_kernel(SpecState sp, StepState st, int rows, const float* __restrict__ pval,
-                                                         const int32_t* __restrict__ pidx) {
+                                                         const int32_t* __restrict__ pidx, StopSel stop) {
     __shared__ int32_t s_tok[DOTS_MAX_SPEC_DRAFTS];
     const int b = blockIdx.x, lane = threadIdx.x;
     const int nl = sp.n_live[b];                                      // uniform
+    const bool drawn = sp.cand && sp.cls[b] == SPEC_ROW_DRAW;         // uniform
     for (int j = 0; j < nl; ++j) {
+        if (drawn) {
+            if (lane == 0) s_tok[j] = sp.cand[b * DOTS_MAX_SPEC_DRAFTS + j];
+            continue;
+        }
         const int r = (j + 1) * rows + b;
         float best = pval[r * ARGMAX_CHUNKS + lane];
         int bi = pidx[r * ARGMAX_CHUNKS + lane];
@@ -95,7 +146,8 @@ __global__ __launch_bounds__(64) void spec_accept_kernel(SpecState sp, StepState
     if (nl < 0) return;
     int acc = 0;
     while (acc < nl && !st.finished[b] && sp.drafts[b * DOTS_MAX_SPEC_DRAFTS + acc] == st.cur_tokens[b]) {
-        commit_token(st, b, s_tok[acc]);
+        if (stop.rows) commit_token(st, b, s_tok[acc], nullptr, nullptr, &stop);
+        else commit_token(st, b, s_tok[acc]);
         ++acc;
     }
     unsigned long long* mine = sp.stats + (size_t)b * 3;
@@ -110,14 +162,13 @@ __global__ __launch_bounds__(64) void spec_accept_kernel(SpecState sp, StepState
 // grid (B), ND_THREADS threads: the threads stride over i, each keeps (largest full, smallest any), one LDS reduction per n.
 __global__ __launch_bounds__(ND_THREADS) void ngram_draft_kernel(const int32_t* __restrict__ out_ids, const int32_t* __restrict__ out_lens, int out_stride,
                                                                  const int32_t* __restrict__ finished, const int32_t* __restrict__ sel,
-                                                                 const int32_t* __restrict__ own, const int32_t* __restrict__ lp, int engine_greedy, int k,
-                                                                 int min_n, int max_n, int32_t* __restrict__ drafts, int draft_stride,
-                                                                 int32_t* __restrict__ n_draft) {
+                                                                 const int32_t* __restrict__ cls, int engine_greedy, int k, int min_n, int max_n,
+                                                                 int32_t* __restrict__ drafts, int draft_stride, int32_t* __restrict__ n_draft) {
     __shared__ int32_t s_suf[DOTS_MAX_NGRAM_SIZE];
     __shared__ int s_full[ND_THREADS / 64], s_any[ND_THREADS / 64];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const bool plain = engine_greedy && !(own && own[b]) && !(lp && lp[b] >= 0);
-    if ((sel && !sel[b]) || (finished && finished[b]) || !plain) {    // uniform per workgroup
+    const bool speculates = engine_greedy && !(cls && cls[b] == SPEC_ROW_NONE);
+    if ((sel && !sel[b]) || (finished && finished[b]) || !speculates) {      // uniform per workgroup
         if (tid == 0) n_draft[b] = 0;
         return;
     }
@@ -162,8 +213,10 @@ __global__ void spec_set_drafts_kernel(int32_t* drafts, int32_t* n_draft, int ro
     n_draft[row] = n;
 }
 
+__global__ void spec_set_class_kernel(int32_t* cls, int row, int value) { cls[row] = value; }
+
 bool spec_ok(const SpecState& sp, int rows) {
-    return sp.drafts && sp.n_draft && sp.n_live && sp.tokens && sp.ctx_len && sp.block_table && sp.stats && sp.k >= 1 && sp.k <= DOTS_MAX_SPEC_DRAFTS &&
+    return sp.drafts && sp.n_draft && sp.n_live && sp.tokens && sp.ctx_len && sp.block_table && sp.stats && sp.cls && sp.k >= 1 && sp.k <= DOTS_MAX_SPEC_DRAFTS &&
            rows >= 1 && rows * (sp.k + 1) <= DOTS_MAX_BATCH;
 }
 
@@ -181,20 +234,30 @@ hipError_t launch_spec_argmax(hipStream_t s, const SpecState& sp, const float* l
     return hipGetLastError();
 }
 
-hipError_t launch_spec_accept(hipStream_t s, const SpecState& sp, const StepState& st, int rows, const float* pval, const int32_t* pidx) {
+hipError_t launch_spec_draw(hipStream_t s, const SpecState& sp, const float* logits, int V, int ld, int rows, const RowParams* params, uint32_t* thr,
+                            const int32_t* out_lens, const float* pval, const int32_t* pidx) {
+    if (!spec_ok(sp, rows) || !sp.cand || !logits || !params || !thr || !out_lens || !pval || !pidx || V < 1 || ld < V) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(spec_thresh_kernel, dim3(rows * sp.k), dim3(SEL_THREADS), 0, s, logits, V, ld, rows, sp, params, thr, pval, pidx);
+    hipLaunchKernelGGL(spec_draw_kernel, dim3(rows * sp.k), dim3(SEL_THREADS), 0, s, logits, V, ld, rows, sp, params, (const uint32_t*)thr, out_lens, pval,
+                       pidx);
+    return hipGetLastError();
+}
+
+hipError_t launch_spec_accept(hipStream_t s, const SpecState& sp, const StepState& st, int rows, const float* pval, const int32_t* pidx, const StopSel& stop) {
     if (!spec_ok(sp, rows) || !pval || !pidx) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(spec_accept_kernel, dim3(rows), dim3(64), 0, s, sp, st, rows, pval, pidx);
+    if (stop.rows && (!stop.tok_off || !stop.tok_bytes)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(spec_accept_kernel, dim3(rows), dim3(64), 0, s, sp, st, rows, pval, pidx, stop);
     return hipGetLastError();
 }
 
 hipError_t launch_ngram_draft(hipStream_t s, const int32_t* out_ids, const int32_t* out_lens, int out_stride, const int32_t* finished, const int32_t* sel,
-                              const int32_t* own, const int32_t* lp, int engine_greedy, int B, int k, int min_n, int max_n, int32_t* drafts,
-                              int draft_stride, int32_t* n_draft) {
+                              const int32_t* cls, int engine_greedy, int B, int k, int min_n, int max_n, int32_t* drafts, int draft_stride,
+                              int32_t* n_draft) {
     if (!out_ids || !out_lens || !drafts || !n_draft || out_stride < 1 || B < 1 || B > DOTS_MAX_BATCH || k < 1 || k > DOTS_MAX_SPEC_DRAFTS ||
         draft_stride < k || min_n < 1 || max_n < min_n || max_n > DOTS_MAX_NGRAM_SIZE)
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(ngram_draft_kernel, dim3(B), dim3(ND_THREADS), 0, s, out_ids, out_lens, out_stride, finished, sel, own, lp, engine_greedy, k, min_n,
-                       max_n, drafts, draft_stride, n_draft);
+    hipLaunchKernelGGL(ngram_draft_kernel, dim3(B), dim3(ND_THREADS), 0, s, out_ids, out_lens, out_stride, finished, sel, cls, engine_greedy, k, min_n, max_n,
+                       drafts, draft_stride, n_draft);
     return hipGetLastError();
 }
 
@@ -203,5 +266,11 @@ hipError_t launch_spec_set_drafts(hipStream_t s, int32_t* drafts, int32_t* n_dra
     DraftIds ids{};
     for (int j = 0; j < n; ++j) ids.v[j] = ids_host[j];
     hipLaunchKernelGGL(spec_set_drafts_kernel, dim3(1), dim3(1), 0, s, drafts, n_draft, row, ids, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_spec_set_class(hipStream_t s, int32_t* cls, int row, int value) {
+    if (!cls || row < 0 || row >= DOTS_MAX_BATCH || value < SPEC_ROW_ARGMAX || value > SPEC_ROW_DRAW) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(spec_set_class_kernel, dim3(1), dim3(1), 0, s, cls, row, value);
     return hipGetLastError();
 }

@@ -386,6 +386,7 @@ def _prototypes(lib):
         "dots_set_row_stop": (i32, [vp, i32, i32, i32]),
         "dots_row_stop_hit": (i32, [vp, i32, P(i32)]),
         "dots_set_speculation": (i32, [vp, i32, i32, i32]),
+        "dots_set_speculation_rows": (i32, [vp, i32]),
         "dots_set_row_drafts": (i32, [vp, i32, P(i32), i32]),
         "dots_spec_stats": (i32, [vp, i32, P(i64), P(i64), P(i64)]),
         "dots_op_ngram_draft": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]),
@@ -420,7 +421,7 @@ EXPORTED_SYMBOLS = [
     "dots_set_token_bytes", "dots_guide_create", "dots_guide_destroy", "dots_set_row_guide", "dots_row_guide_state",
     "dots_op_select_tokens_guided", "dots_bench_select_tokens_guided",
     "dots_set_row_ngram", "dots_op_select_tokens_ngram", "dots_bench_select_tokens_ngram",
-    "dots_set_speculation", "dots_set_row_drafts", "dots_spec_stats", "dots_op_ngram_draft",
+    "dots_set_speculation", "dots_set_speculation_rows", "dots_set_row_drafts", "dots_spec_stats", "dots_op_ngram_draft",
     "dots_slots_fork",
     "dots_stop_create", "dots_stop_destroy", "dots_set_row_stop", "dots_row_stop_hit",
 ]
@@ -454,6 +455,29 @@ def ngram_draft(history: Sequence[int], k: int, min_n: int = 2, max_n: int = 4) 
 def spec_usable_slots(max_batch: int, k: int) -> int:
     """slots a speculating engine can fill: a slot takes k + 1 rows of a step"""
     return int(max_batch) // (int(k) + 1)
+
+
+SPEC_ROWS = {"sampled": 1, "stop": 2}        # DOTS_SPEC_ROWS_SAMPLED / DOTS_SPEC_ROWS_STOP
+
+
+def spec_rows_flags(value) -> int:
+    """The DOTS_SPEC_ROWS_* bits of a speculative_rows setting: None or "greedy" = 0 (plain greedy rows only), "all" = every bit, or one
+    name / a tuple or list of names out of "sampled" and "stop".  ValueError on anything else."""
+    if value is None:
+        return 0
+    names = (value,) if isinstance(value, str) else tuple(value)
+    flags = 0
+    for n in names:
+        if n == "all":
+            flags |= sum(SPEC_ROWS.values())
+        elif n == "greedy" and len(names) == 1:
+            pass
+        elif isinstance(n, str) and n in SPEC_ROWS:
+            flags |= SPEC_ROWS[n]
+        else:
+            raise ValueError(f"speculative_rows takes \"all\", \"greedy\" or names out of {sorted(SPEC_ROWS)}, got {value!r}")
+    return flags
+
 
 MAX_TOP_LOGPROBS = 20                        # DOTS_MAX_TOP_LOGPROBS: top entries kept per position
 
@@ -929,6 +953,15 @@ class Engine:
             raise ValueError(f"k must be in [0, {MAX_SPEC_DRAFTS}], got {k!r}")
         self._ck(self.lib.dots_set_speculation(self.h, k, int(min_n), int(max_n)), "dots_set_speculation")
         self.spec_k = k
+
+    def set_speculation_rows(self, sampled: bool = False, stop: bool = False):
+        """Which rows beside the plain greedy ones verify drafts: sampled = rows with SamplingParams that carry no penalty
+        (any temperature, top_k, top_p, seed: the draft rows are drawn by the row's own sampler with the counter of their output index, so
+        the tokens are those of the unspeculated engine for the same seed), stop = rows with stop strings (the row ends at the same token).
+        A row with both needs both.  Default: neither.  Only while no slot is occupied; the setting survives set_speculation."""
+        flags = (SPEC_ROWS["sampled"] if sampled else 0) | (SPEC_ROWS["stop"] if stop else 0)
+        self._ck(self.lib.dots_set_speculation_rows(self.h, flags), "dots_set_speculation_rows")
+        self.spec_rows = flags
 
     @property
     def usable_slots(self) -> int:

@@ -135,7 +135,7 @@ class DotsOcrHipForCausalLM:
                  stop_token_ids=None, ignore_eos: bool = False, guided_regex=None, guided_choice=None, guided_json=None,
                  guided_whitespace_pattern=None, no_repeat_ngram_size: Optional[int] = None, no_repeat_ngram_window: Optional[int] = None,
                  no_repeat_ngram_whitelist=None, speculative_ngram: Optional[int] = None, prompt_lookup_min: int = 2, prompt_lookup_max: int = 4,
-                 num_return_sequences: int = 1, stop_strings=None, **_):
+                 num_return_sequences: int = 1, stop_strings=None, speculative_rows=None, **_):
         """HF-shaped generate.  do_sample / temperature / top_p default to the checkpoint's generation_config.json (greedy when it
         is absent); with sampling on, tokens are drawn on the GPU from softmax(logits / temperature) restricted to the top_p
         nucleus, reproducibly from `seed`.  Returns LongTensor
@@ -167,6 +167,13 @@ class DotsOcrHipForCausalLM:
         sequence verifies up to k drafted tokens per decode step, max_batch // (k + 1) sequences at a time.  The tokens are exactly
         those of the call without it; sampled or rule-carrying sequences simply run unspeculated.  The engine is left with speculation
         off.
+
+        speculative_rows (with speculative_ngram; None = the above) lets more sequences verify drafts: "sampled", "stop", a tuple of
+        both, or "all" (Engine.set_speculation_rows).  With "stop" a greedy sequence with stop_strings speculates and ends at the same
+        token.  With "sampled" a sampled call (temperature > 0) without penalties speculates: every sequence is then drawn by the
+        per-row sampler with seed + b (as a call with top_k is) instead of the engine-wide one, and its tokens are exactly those of the
+        same call on an engine that does not speculate.  Sequences with penalties, logit rules, a guide or an n-gram rule run
+        unspeculated.  The engine is left with the setting off.
 
         stop_strings (HF's name: a str or a list of at most 16 str of at most 64 UTF-8 bytes) ends a sequence on the GPU at the token that
         completes one of them in its generated text (Engine.set_row_stop; with min_tokens, no match is taken below it).  The
@@ -252,12 +259,27 @@ class DotsOcrHipForCausalLM:
             def row_sp(b):                       # prompt b's sequences take seeds seed + b * n .. + n - 1 (the scheduler adds the index)
                 return dataclasses.replace(per_seq, seed=int(seed) + b * nrs)
         spec_k = int(speculative_ngram or 0)
+        from .engine import SPEC_ROWS, spec_rows_flags
+        spec_rows = spec_rows_flags(speculative_rows)
+        if spec_rows and not spec_k:
+            raise ValueError("speculative_rows needs speculative_ngram")
         if spec_k:
             if continuous is False:
                 raise ValueError("speculative_ngram runs on the continuous path: continuous=False cannot be combined with it")
             continuous = True
+            if (spec_rows & SPEC_ROWS["sampled"]) and t_eff > 0:
+                # the engine-wide sampler hashes the slot index and never speculates: the sequences take parameters of their own
+                if row_sp is None:
+                    from .engine import SamplingParams
+                    base = SamplingParams(temperature=t_eff, top_p=p_eff, seed=seed)
+
+                    def row_sp(b):
+                        return dataclasses.replace(base, seed=int(seed) + b)
+                self.engine.set_sampling(0.0, 1.0, 0)
             self.engine.slots_reset()            # speculation changes only while no slot is occupied
             self.engine.set_speculation(spec_k, int(prompt_lookup_min), int(prompt_lookup_max))
+            if spec_rows:
+                self.engine.set_speculation_rows(sampled=bool(spec_rows & SPEC_ROWS["sampled"]), stop=bool(spec_rows & SPEC_ROWS["stop"]))
         try:
             return self._generate(input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens, eos_token_id, pad_token_id, continuous,
                                   row_sp, rules, guide, ngram, nrs, stop, int(min_tokens or 0))
@@ -266,6 +288,8 @@ class DotsOcrHipForCausalLM:
                 try:
                     self.engine.slots_reset()
                     self.engine.set_speculation(0)
+                    if spec_rows:
+                        self.engine.set_speculation_rows()
                 except Exception as e:               # the run's own error is the one to raise
                     import warnings
                     warnings.warn(f"speculation could not be switched off: {e}")

@@ -34,7 +34,8 @@ class DotsOCRParser:
                  max_completion_tokens=16384, num_thread=64, dpi=200, output_dir="./output", min_pixels=None,
                  max_pixels=None, use_hf=False, model_path="./weights/DotsOCR", model=None, processor=None,
                  hf_max_new_tokens=24000, guided=False, no_repeat_ngram_size=None, no_repeat_ngram_window=None,
-                 no_repeat_ngram_whitelist=None, speculative_ngram=None, prompt_lookup_min=2, prompt_lookup_max=4, stop=None):
+                 no_repeat_ngram_whitelist=None, speculative_ngram=None, prompt_lookup_min=2, prompt_lookup_max=4, stop=None,
+                 speculative_rows=None):
         self.dpi = dpi
         # stop strings, opt-in: the server request carries `stop`, the in-process model generates with stop_strings and the
         # text is cut where the match starts.  With the default None the request and the call are exactly what they were.
@@ -46,6 +47,12 @@ class DotsOCRParser:
         # server speculates by its own --speculative-ngram flag, as vLLM does: requests carry nothing.
         self.speculative_ngram = None if not speculative_ngram else int(speculative_ngram)
         self.prompt_lookup_min, self.prompt_lookup_max = int(prompt_lookup_min), int(prompt_lookup_max)
+        # which sequences beside the plain greedy ones speculate (generate(speculative_rows=): "sampled", "stop", a tuple, "all"); None =
+        # greedy only.  A server decides by its own --speculative-rows flag.
+        from .engine import spec_rows_flags
+        if spec_rows_flags(speculative_rows) and not self.speculative_ngram:
+            raise ValueError("speculative_rows needs speculative_ngram")
+        self.speculative_rows = speculative_rows
         # no-repeat n-gram blocking, opt-in: the server request carries the three fields, the in-process model generates
         # with them.  With the default None the request and the call are exactly what they were.
         self.no_repeat_ngram_size = no_repeat_ngram_size
@@ -106,6 +113,8 @@ class DotsOCRParser:
         kw = self._ngram_fields()
         if self.speculative_ngram:
             kw.update(speculative_ngram=self.speculative_ngram, prompt_lookup_min=self.prompt_lookup_min, prompt_lookup_max=self.prompt_lookup_max)
+            if self.speculative_rows is not None:
+                kw["speculative_rows"] = self.speculative_rows
         if self._guided_layout(prompts):
             from .guided import layout_schema
             if getattr(self.model.engine, "token_bytes", None) is None:

@@ -329,7 +329,7 @@ int dots_stop_destroy(DotsEngine* e, int32_t handle);
 int dots_set_row_stop(DotsEngine* e, int row, int32_t handle, int min_tokens);
 int dots_row_stop_hit(DotsEngine* e, int row, int32_t* out);
 
-/* ---- N-gram speculative decoding of greedy rows: opt-in, engine-wide, slot mode only.  With k drafts a slot occupies up to
+/* ---- N-gram speculative decoding: opt-in, engine-wide, slot mode only.  With k drafts a slot occupies up to
  * k + 1 rows of one decode step: row j carries token j of (last committed token, draft 1 .. k) at context ctx + j on the slot's own KV
  * pages, and sees the K/V rows 0 .. j - 1 appended in the step's qkv launch.  Every decode kernel is row-independent and batch-invariant
  * bit for bit, so row j's logits are those of the sequential step at that position; the step commits row 0's token as an unspeculated
@@ -338,9 +338,17 @@ int dots_row_stop_hit(DotsEngine* e, int row, int32_t* out);
  * 1 .. k + 1 of them, so dots_slots_decode(n) may finish a row before n steps have run.  The K/V of rejected drafts stay where they were
  * written; the next step overwrites those positions.
  *
- * Only plain greedy rows speculate: a row with DotsSamplingParams, DotsLogitRules, a guide, an n-gram rule or logprobs of its own, and
- * every row while dots_set_sampling has a temperature > 0, verifies no draft and decodes inside the speculating step exactly as before.
- * dots_generate / dots_decode_step (the closed static batch) ignore the setting.
+ * By default only plain greedy rows speculate: a row with DotsSamplingParams, DotsLogitRules, a guide, an n-gram rule, stop strings or
+ * logprobs of its own, and every row while dots_set_sampling has a temperature > 0, verifies no draft and decodes inside the speculating
+ * step exactly as before.  dots_generate / dots_decode_step (the closed static batch) ignore the setting.
+ *
+ * dots_set_speculation_rows widens that: DOTS_SPEC_ROWS_SAMPLED lets a row with DotsSamplingParams speculate when they carry no penalty
+ * (any temperature, top_k, top_p and seed), DOTS_SPEC_ROWS_STOP a row with stop strings; a row with both needs both bits.  A sampled
+ * row's draft row j is selected by the row's own sampler with the counter of the output index it stands for (tokens generated + j), over
+ * integer sums that do not depend on the order of the atomics: it is the token the unspeculated engine draws there, so the row's tokens
+ * are EXACTLY those of the unspeculated engine for the same seed.  The accept walk advances the stop automaton through the commit a
+ * sequential step uses: the row finishes at the same token, with the same hit record.  Rows with penalties, logit rules, a guide, an
+ * n-gram rule or logprobs, and every row under an engine-wide temperature, never speculate.
  *
  * The built-in drafter looks the row's last tokens up in the row's OWN output (the prompt is not searched: image pads and a short
  * instruction).  With out[0 .. L) the tokens generated so far, for n from max_n down to min_n with n + 1 <= L: key = out[L - n .. L);
@@ -352,13 +360,19 @@ int dots_row_stop_hit(DotsEngine* e, int row, int32_t* out);
  *                       drafts (dots_set_row_drafts).  With k > 0 the usable slots are [0, max_batch / (k + 1)): dots_slots_prefill into a
  *                       higher slot returns DOTS_E_CAPACITY.  Allowed only while no slot is occupied (DOTS_E_STATE); zeroes the counters
  *                       and drops the captured steps.  DOTS_E_CAPACITY when max_batch < k + 1.
+ * dots_set_speculation_rows  flags: DOTS_SPEC_ROWS_SAMPLED | DOTS_SPEC_ROWS_STOP; 0 (the default) = plain greedy rows only, and a step
+ *                       launches exactly what it launched before.  The setting survives dots_set_speculation calls.  Allowed only while
+ *                       no slot is occupied (DOTS_E_STATE); unknown bits: DOTS_E_INVALID.
  * dots_set_row_drafts   the n <= k drafts slot `row` verifies in its NEXT step, replacing what the drafter left (stream ordered; they are
  *                       spent by that step).  DOTS_E_INVALID: n > k or an id outside [0, vocab); DOTS_E_STATE: the slot is not occupied.
  *                       A row that does not speculate ignores them.
  * dots_spec_stats       speculating steps the row took, draft tokens it verified (after the generation cap cut them) and draft tokens it
  *                       committed, since the row's prefill; row = -1: the engine's totals since the last dots_set_speculation. */
 #define DOTS_MAX_SPEC_DRAFTS 15
+#define DOTS_SPEC_ROWS_SAMPLED 1
+#define DOTS_SPEC_ROWS_STOP 2
 int dots_set_speculation(DotsEngine* e, int k, int min_n, int max_n);
+int dots_set_speculation_rows(DotsEngine* e, int flags);
 int dots_set_row_drafts(DotsEngine* e, int row, const int32_t* ids_host, int n);
 int dots_spec_stats(DotsEngine* e, int row, int64_t* steps, int64_t* drafted, int64_t* accepted);
 

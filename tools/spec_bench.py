@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """What a speculating decode step costs and what it has to accept to pay (profiles/spec_ngram.txt).
 
-    python tools/spec_bench.py [--slots 1 8] [--k 0 1 3 7] [--steps 64] [--repeats 3] [--prompt 512]
+    python tools/spec_bench.py [--slots 1 8] [--k 0 1 3 7] [--steps 64] [--repeats 3] [--prompt 512] [--sampled]
 
 Full-size language model with seeded random weights (the vision tower, which no text-only prompt touches, is cut to one block so that the
 weights are made quickly), one engine of 64 rows.  Per slot count: the reference tokens come from an unspeculated run; then for every
@@ -18,6 +18,12 @@ plants nothing but pays the same one-step-per-call loop):
 
     ms_per_step, tokens_per_step, tokens_per_s per slot count, k and acceptance
     break_even = cost(k) / cost(0) - 1 from the acceptance-0 rows: the accepted tokens per step above which speculating is faster
+
+--sampled (profiles/spec_sampled.txt) runs the same legs three times on engines set to Engine.set_speculation_rows(sampled=True): with
+plain greedy rows, with SamplingParams(temperature=0.1, seed=...) rows (a draft row rereads its logits twice: partials and draw) and
+with temperature=0.8, top_k=20, top_p=0.9 rows (four reads: partials, histogram, gather, draw).  The difference between a sampled
+leg and the greedy leg at the same slots, k and acceptance is the cost of the two draft-row launches (spec_thresh_kernel,
+spec_draw_kernel); the k = 0 step of a sampled leg pays the per-row selection stage instead of the arg max, as it does without speculation.
 
 One JSON line per measurement on stdout, then a table.
 """
@@ -41,10 +47,11 @@ def main():
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--prompt", type=int, default=512)
+    ap.add_argument("--sampled", action="store_true", help="also run sampled speculating rows (2-read and 4-read parameter sets) beside the greedy leg")
     ap.add_argument("--tiny", action="store_true", help="the small-dims model instead of the full-size one (a plumbing check, not a measurement)")
     a = ap.parse_args()
     from dots_ocr_amd.config import DotsConfig
-    from dots_ocr_amd.engine import Engine
+    from dots_ocr_amd.engine import Engine, SamplingParams
     from dots_ocr_amd.weights import random_state_dict
     if a.tiny:
         cfg = DotsConfig.tiny(layers=3, v_layers=1)
@@ -60,70 +67,83 @@ def main():
     rng = np.random.default_rng(0)
     prompts = [rng.integers(0, cfg.vocab_size - 4096, a.prompt).astype(np.int32) for _ in range(max(a.slots))]
     results = {}
-    for S in a.slots:
-        if any(S * (k + 1) > 64 for k in a.k):
-            raise SystemExit(f"{S} slots x (k + 1) rows exceed the 64 rows of a step")
-        slots = list(range(S))
+    legs = [("greedy", None)]
+    if a.sampled:
+        legs += [("T0.1", dict(temperature=0.1)), ("T0.8_k20_p0.9", dict(temperature=0.8, top_k=20, top_p=0.9))]
+    for leg, params in legs:
+      for S in a.slots:
+          if any(S * (k + 1) > 64 for k in a.k):
+              raise SystemExit(f"{S} slots x (k + 1) rows exceed the 64 rows of a step")
+          slots = list(range(S))
 
-        def run(k, true_drafts, T=None):
-            """`steps` steps with k drafts per slot of which the first true_drafts are right: (seconds, tokens committed, token lists)"""
-            eng.slots_reset()
-            eng.set_speculation(k, 2, 0)
-            eng.slots_prefill(slots, np.concatenate(prompts[:S]), [a.prompt] * S, [n_tok] * S)
-            eng.slots_decode(1)                                       # the captured step exists before the clock starts
-            eng.synchronize()
-            _, lens = eng.slots_poll()
-            start = [int(lens[b]) for b in slots]
-            pos = list(start)
-            t0 = time.perf_counter()
-            for _ in range(a.steps):
-                for b in slots:
-                    if k:
-                        d = [int(t) for t in T[b][pos[b]:pos[b] + k]]
-                        d = d[:true_drafts] + [(t + 1) % (cfg.vocab_size - 4096) for t in d[true_drafts:]]
-                        eng.set_row_drafts(b, d)
-                    pos[b] += 1 + (min(true_drafts, k) if k else 0)
-                eng.slots_decode(1)
-            eng.synchronize()
-            dt = time.perf_counter() - t0
-            _, lens = eng.slots_poll()
-            toks = [eng.slot_read(b, int(lens[b])).tolist() for b in slots]
-            assert [int(lens[b]) for b in slots] == pos, (k, true_drafts, [int(lens[b]) for b in slots], pos)
-            if T is not None:
-                assert all(toks[b] == T[b][:len(toks[b])] for b in slots), "a speculating run left the reference tokens"
-            for b in slots:
-                eng.slot_release(b)
-            return dt, sum(pos) - sum(start), toks
+          def set_rows():
+              """the leg's parameters on every slot (a release clears them): row b draws with seed 1000 + b"""
+              if params is not None:
+                  for b in slots:
+                      eng.set_row_sampling(b, SamplingParams(seed=1000 + b, **params))
 
-        # reference tokens: unspeculated, as many as the fastest run will need
-        eng.slots_reset()
-        eng.set_speculation(0)
-        eng.slots_prefill(slots, np.concatenate(prompts[:S]), [a.prompt] * S, [n_tok] * S)
-        for _ in range(-(-n_tok // 16)):
-            eng.slots_decode(16)
-        _, lens = eng.slots_poll()
-        T = [eng.slot_read(b, int(lens[b])).tolist() for b in slots]
-        assert all(len(t) == n_tok for t in T)
-        for b in slots:
-            eng.slot_release(b)
-        for k in a.k:
-            levels = [("-", 0)] if k == 0 else [("0", 0), ("half", -(-k // 2)), ("full", k)]
-            for name, true_drafts in levels:
-                runs = [run(k, true_drafts, T) for _ in range(a.repeats)]
-                dt = statistics.median(r[0] for r in runs)
-                rec = {"slots": S, "k": k, "rows": S * (k + 1), "acceptance": name, "steps": a.steps, "ms_per_step": round(dt / a.steps * 1e3, 4),
-                       "ms_per_step_min_max": [round(min(r[0] for r in runs) / a.steps * 1e3, 4), round(max(r[0] for r in runs) / a.steps * 1e3, 4)],
-                       "tokens_per_step": round(runs[0][1] / a.steps / S, 3), "tokens_per_s": round(runs[0][1] / dt, 1)}
-                results[(S, k, name)] = rec
-                print(json.dumps(rec), flush=True)
+          def run(k, true_drafts, T=None):
+              """`steps` steps with k drafts per slot of which the first true_drafts are right: (seconds, tokens committed, token lists)"""
+              eng.slots_reset()
+              eng.set_speculation(k, 2, 0)
+              eng.set_speculation_rows(sampled=a.sampled)
+              set_rows()
+              eng.slots_prefill(slots, np.concatenate(prompts[:S]), [a.prompt] * S, [n_tok] * S)
+              eng.slots_decode(1)                                       # the captured step exists before the clock starts
+              eng.synchronize()
+              _, lens = eng.slots_poll()
+              start = [int(lens[b]) for b in slots]
+              pos = list(start)
+              t0 = time.perf_counter()
+              for _ in range(a.steps):
+                  for b in slots:
+                      if k:
+                          d = [int(t) for t in T[b][pos[b]:pos[b] + k]]
+                          d = d[:true_drafts] + [(t + 1) % (cfg.vocab_size - 4096) for t in d[true_drafts:]]
+                          eng.set_row_drafts(b, d)
+                      pos[b] += 1 + (min(true_drafts, k) if k else 0)
+                  eng.slots_decode(1)
+              eng.synchronize()
+              dt = time.perf_counter() - t0
+              _, lens = eng.slots_poll()
+              toks = [eng.slot_read(b, int(lens[b])).tolist() for b in slots]
+              assert [int(lens[b]) for b in slots] == pos, (k, true_drafts, [int(lens[b]) for b in slots], pos)
+              if T is not None:
+                  assert all(toks[b] == T[b][:len(toks[b])] for b in slots), "a speculating run left the reference tokens"
+              for b in slots:
+                  eng.slot_release(b)
+              return dt, sum(pos) - sum(start), toks
+
+          # reference tokens: unspeculated, as many as the fastest run will need
+          eng.slots_reset()
+          eng.set_speculation(0)
+          set_rows()
+          eng.slots_prefill(slots, np.concatenate(prompts[:S]), [a.prompt] * S, [n_tok] * S)
+          for _ in range(-(-n_tok // 16)):
+              eng.slots_decode(16)
+          _, lens = eng.slots_poll()
+          T = [eng.slot_read(b, int(lens[b])).tolist() for b in slots]
+          assert all(len(t) == n_tok for t in T)
+          for b in slots:
+              eng.slot_release(b)
+          for k in a.k:
+              levels = [("-", 0)] if k == 0 else [("0", 0), ("half", -(-k // 2)), ("full", k)]
+              for name, true_drafts in levels:
+                  runs = [run(k, true_drafts, T) for _ in range(a.repeats)]
+                  dt = statistics.median(r[0] for r in runs)
+                  rec = {"leg": leg, "slots": S, "k": k, "rows": S * (k + 1), "acceptance": name, "steps": a.steps, "ms_per_step": round(dt / a.steps * 1e3, 4),
+                         "ms_per_step_min_max": [round(min(r[0] for r in runs) / a.steps * 1e3, 4), round(max(r[0] for r in runs) / a.steps * 1e3, 4)],
+                         "tokens_per_step": round(runs[0][1] / a.steps / S, 3), "tokens_per_s": round(runs[0][1] / dt, 1)}
+                  results[(leg, S, k, name)] = rec
+                  print(json.dumps(rec), flush=True)
     print()
-    print(f"{'slots':>5} {'k':>2} {'rows':>4} {'accept':>6} {'ms/step':>9} {'tok/step/slot':>13} {'tokens/s':>10} {'break-even accepted/step':>25}")
-    for (S, k, name), r in results.items():
-        base = results.get((S, 0, "-"))
+    print(f"{'leg':>14} {'slots':>5} {'k':>2} {'rows':>4} {'accept':>6} {'ms/step':>9} {'tok/step/slot':>13} {'tokens/s':>10} {'break-even accepted/step':>25}")
+    for (leg, S, k, name), r in results.items():
+        base = results.get((leg, S, 0, "-"))
         be = ""
         if k and name == "0" and base:
             be = f"{r['ms_per_step'] / base['ms_per_step'] - 1:.3f}"
-        print(f"{S:>5} {k:>2} {r['rows']:>4} {name:>6} {r['ms_per_step']:>9.4f} {r['tokens_per_step']:>13.3f} {r['tokens_per_s']:>10.1f} {be:>25}")
+        print(f"{leg:>14} {S:>5} {k:>2} {r['rows']:>4} {name:>6} {r['ms_per_step']:>9.4f} {r['tokens_per_step']:>13.3f} {r['tokens_per_s']:>10.1f} {be:>25}")
     eng.close()
 
 
