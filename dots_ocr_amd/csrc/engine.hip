@@ -5,403 +5,11 @@
 // The decode step is captured once per dots_generate call into a hipGraph and replayed: every
 // per-step quantity (token ids, context lengths, block tables) lives in device memory and is read
 // through pointers, so the graph never needs parameter updates (SURVEY §7 "hard parts").
-#include <hip/hip_runtime.h>
-#include <hip/hip_fp16.h>
+#include "engine.h"
 
-#include <algorithm>
-#include <cmath>
-#include <cstdarg>
-#include <cstddef>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <type_traits>
-#include <unordered_map>
-#include <vector>
-
-#include "common.h"
-#include "decode_layout.h"
-#include "dots_ocr_hip.h"
-#include "kernels.h"
-#include "row_stage.h"
-
+namespace engine {
 namespace {
-
 thread_local std::string g_create_error;
-
-struct Tensor {
-    bf16_t* p = nullptr;
-    std::vector<int64_t> shape;
-    int64_t numel() const { int64_t n = 1; for (auto s : shape) n *= s; return n; }
-};
-
-// *_s: per-output-channel fp32 scales of the fp8 configuration (cfg.fp8_weights; quant.hip), nullptr in bf16 mode.  In fp8 mode the
-// row-major matrices hold bf16(q) (exact e4m3 values) and the decode copies (*_wd) hold the e4m3 bytes in fragment order.
-// *_8: the e4m3 bytes row-major — the weight operand of the fp8-MFMA GEMMs (gemm.hip: gemm_fp8_256pp_kernel) of ViT / prefill.
-struct VLayer {
-    bf16_t *norm1, *qkv_w, *qkv_b, *proj_w, *proj_b, *norm2, *w13, *b13, *w2, *b2;
-    float *qkv_s, *proj_s, *w13_s, *w2_s;
-    uint8_t *qkv_8, *proj_8, *w13_8, *w2_8;
-};
-struct LLayer {
-    bf16_t *ln1, *qkv_w, *qkv_b, *o_w, *ln2, *w13, *down_w;          // row-major [N][K]: prefill GEMMs
-    void *qkv_wd, *o_wd, *w13_wd, *down_wd;                          // MFMA fragment order: decode skinny GEMMs
-    float *qkv_s, *o_s, *w13_s, *down_s;
-    uint8_t *qkv_8, *o_8, *w13_8, *down_8;
-};
-
-__global__ void pack_w13_kernel(const bf16_t* __restrict__ gate, const bf16_t* __restrict__ up, bf16_t* __restrict__ out, int I, int K) {
-    // out row r: group G = r/64; rows [0,32) of the group = gate[G*32 ..], rows [32,64) = up[G*32 ..]
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;      // 16-B chunk index
-    const int cpr = K / 8;
-    if (idx >= (int64_t)2 * I * cpr) return;
-    const int r = (int)(idx / cpr), c = (int)(idx % cpr);
-    const int G = r >> 6, wi = r & 63;
-    const bf16_t* src = (wi < 32 ? gate + (size_t)(G * 32 + wi) * K : up + (size_t)(G * 32 + wi - 32) * K) + c * 8;
-    *reinterpret_cast<u32x4*>(out + (size_t)r * K + c * 8) = *reinterpret_cast<const u32x4*>(src);
-}
-
-__global__ void pack_b13_kernel(const bf16_t* __restrict__ gate, const bf16_t* __restrict__ up, bf16_t* __restrict__ out, int I) {
-    const int r = blockIdx.x * 256 + threadIdx.x;
-    if (r >= 2 * I) return;
-    const int G = r >> 6, wi = r & 63;
-    out[r] = wi < 32 ? gate[G * 32 + wi] : up[G * 32 + wi - 32];
-}
-
-__global__ void convert_kernel(const void* __restrict__ src, int dtype, bf16_t* __restrict__ dst, int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    if (dtype == DOTS_DTYPE_F32) dst[i] = f2bf(reinterpret_cast<const float*>(src)[i]);
-    else if (dtype == DOTS_DTYPE_F16) dst[i] = f2bf(__half2float(reinterpret_cast<const __half*>(src)[i]));
-    else dst[i] = reinterpret_cast<const bf16_t*>(src)[i];
-}
-
-// rows [n, K] -> [n, Kpad] zero padded
-__global__ void pad_rows_kernel(const bf16_t* __restrict__ src, bf16_t* __restrict__ dst, int n, int K, int Kpad) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (int64_t)n * Kpad) return;
-    const int r = (int)(i / Kpad), c = (int)(i % Kpad);
-    dst[i] = c < K ? src[(size_t)r * K + c] : (bf16_t)0;
-}
-
-inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
-
-}  // namespace
-
-hipError_t launch_pack_w13(hipStream_t s, const bf16_t* gate, const bf16_t* up, bf16_t* out, int I, int K) {
-    const int64_t n = (int64_t)2 * I * (K / 8);
-    hipLaunchKernelGGL(pack_w13_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, gate, up, out, I, K);
-    return hipGetLastError();
-}
-hipError_t launch_convert_to_bf16(hipStream_t s, const void* src, int dtype, bf16_t* dst, int64_t n) {
-    hipLaunchKernelGGL(convert_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, dtype, dst, n);
-    return hipGetLastError();
-}
-
-struct DotsEngine {
-    DotsConfig cfg{};
-    int device = 0;
-    hipStream_t stream = nullptr;
-    std::string err;
-    std::vector<void*> allocs;
-    bool finalized = false;
-
-    std::unordered_map<std::string, Tensor> raw;     // checkpoint tensors as loaded (bf16, device)
-
-    // packed weights
-    bf16_t *patch_w = nullptr, *patch_b = nullptr, *patch_norm = nullptr;
-    int patch_k = 0, patch_kpad = 0;
-    std::vector<VLayer> vl;
-    bf16_t *v_post_norm = nullptr, *m_ln_w = nullptr, *m_ln_b = nullptr, *m0_w = nullptr, *m0_b = nullptr, *m2_w = nullptr, *m2_b = nullptr;
-    bf16_t *embed = nullptr, *final_norm = nullptr, *lm_head = nullptr;
-    void* lm_head_d = nullptr;
-    float *m0_s = nullptr, *m2_s = nullptr, *lm_head_s = nullptr;
-    uint8_t *m0_8 = nullptr, *m2_8 = nullptr;
-    // fp8 mode: per-token quantised activations of the GEMM being launched (max rows x max K bytes) + their scales
-    uint8_t* act_q = nullptr;
-    float* act_s = nullptr;
-    uint8_t* act_q_v = nullptr;            // the vision tower's own quantisation scratch (it may run beside a prefill: dots_vit_prefetch)
-    float* act_s_v = nullptr;
-    // ---- vision prefetch (dots_vit_prefetch): the tower of the NEXT page batch runs on `s_vit`, a stream masked to the upper
-    // 256 - dec_cus CUs (an equal share of every XCD), while the decode loop of the current batch is replayed on `s_dec`, masked to
-    // the lower dec_cus CUs.  Without the masks the two streams time-slice the chip and nothing overlaps (tools/overlap_probe.py).
-    hipStream_t s_vit = nullptr, s_dec = nullptr;
-    int dec_cus = 128;
-    hipEvent_t ev_vis_ready = nullptr, ev_xs = nullptr;     // tower finished / cross-stream ordering
-    bf16_t* vis_pref = nullptr;            // merged vision rows of the prefetched batch (swapped with `vis` when taken)
-    int64_t vis_pref_rows = 0;
-    bool pref_pending = false;             // a prefetch was requested and not yet taken
-    bool pref_deferred = false;            // ... and its tower is still to be launched (behind the next prefill)
-    const float* pref_pix = nullptr;       // deferred request
-    int64_t pref_patches = 0;
-    std::vector<int64_t> pref_grid;
-    hipStream_t vs = nullptr;              // the stream vit_forward is currently enqueuing to (stream or s_vit)
-    // ---- tower tail (round 5): the LAST `tail` blocks of a prefetched tower (and its merger) run on `s_vit_full`, a stream without a CU
-    // mask.  The two partitions cannot be re-balanced in small steps (a partition has to be a whole number of CUs per shader engine of
-    // every XCD — 32, 64, 96, ... CUs: with 56 every decode kernel ran at half speed, profiles/r05_decode_wide_ab.txt), so when the
-    // decode loop of a step drains before the tower the decode partition would idle until the tower is done.  Instead the tower is split
-    // in time: (L - tail) blocks beside the decode loop on its partition, the rest on the whole chip.  tail is chosen per launch from the
-    // previous launch's measurements (events): tail = L - D / t_block, D = when the last decode chunk ended after the tower had started,
-    // t_block = the partition's time per block — i.e. the head ends about when the decode loop does; a decode loop that outlasts the
-    // tower gives tail = 0.  OFF by default (tail 0): the rule assumes that the decode work of a step is FINITE (bench.py's fixed
-    // half_steps per admission); a serving loop whose host merely stopped issuing chunks while it waited for the tower would be read as
-    // "decode drained".  Measured on the a4 bench: 5.74 (off) -> 5.81 pages/s (adaptive, 8 blocks) — the chip is power-limited, a block
-    // on 256 CUs takes 27.6 ms against 30.4 on 192 (profiles/r05_tower_tail_ab.txt).
-    hipStream_t s_vit_full = nullptr;
-    hipEvent_t ev_tw0 = nullptr, ev_tw_sw = nullptr, ev_dec_end = nullptr;      // tower start / end of its partition part / end of the last decode chunk
-    int tail_fixed = 0;                    // dots_tower_tail / DOTS_OCR_TOWER_TAIL_LAYERS: blocks on the whole chip (default 0 = off), -1 = adaptive
-    int tail_now = 0;                      // tail of the tower being launched / launched last
-    int tail_head_blocks = 0;              // blocks of the last prefetched tower that ran on the partition (0: no measurement yet)
-    uint64_t tw_seq = 0, dec_end_seq = 0, dec_end_at_tw = 0;     // launch counters: was a decode chunk recorded after the last tower started?
-    std::vector<LLayer> ll;
-    float *v_inv_freq = nullptr, *lm_inv_freq = nullptr;
-
-    // ---- ViT workspace (max_patches rows)
-    int64_t P = 0, Ppad = 0;
-    bf16_t *v_xa = nullptr, *v_x = nullptr, *v_xn = nullptr, *v_qkv = nullptr, *v_q = nullptr, *v_k = nullptr, *v_vt = nullptr,
-           *v_att = nullptr, *v_act = nullptr, *v_mh = nullptr, *vis = nullptr;
-    float* v_pix = nullptr;
-    float2* v_cs = nullptr;
-    int32_t* v_pos = nullptr;
-    Tile64* v_tiles = nullptr;
-    QBlock* v_qblocks = nullptr;
-    int64_t vis_rows = 0;
-    std::vector<int32_t> h_pos;
-    std::vector<Tile64> h_tiles;
-    std::vector<QBlock> h_qblocks;
-
-    // ---- prefill workspace (max_prefill_tokens rows)
-    int64_t TP = 0, TPpad = 0;
-    bf16_t *p_x = nullptr, *p_xn = nullptr, *p_qkv = nullptr, *p_q = nullptr, *p_k = nullptr, *p_vt = nullptr, *p_att = nullptr, *p_act = nullptr;
-    float2* p_cs = nullptr;
-    int32_t *p_pos = nullptr, *p_src = nullptr, *p_last = nullptr;
-    Tile64* p_tiles = nullptr;
-    QBlock* p_qblocks = nullptr;
-    std::vector<int32_t> hp_pos, hp_src, hp_last, hp_table;
-    std::vector<Tile64> hp_tiles;
-    std::vector<QBlock> hp_qblocks;
-
-    // ---- KV pool + decode state
-    int max_pages = 0;                     // block-table width: pages of one sequence at max_seq_len
-    int n_pool_pages = 0;                  // allocatable pages; page n_pool_pages is the scratch page idle rows write to
-    int kv_capped = 0;                     // sequences whose generation cap was lowered because the pool ran dry
-    std::vector<int32_t> free_pages;       // LIFO free list
-    // holders of every page (0 = in the free list).  Only dots_slots_fork makes a count exceed 1: the children's block-table rows name the
-    // source's full prompt pages.  A page with more than one holder is never written
-    std::vector<int32_t> page_refs;
-    // dots_slots_fork: the slots the most recent dots_slots_prefill filled, in the order of its packed prompts (hp_last[i] = last packed
-    // token of fresh_slots[i]); emptied by whatever invalidates that prefill's workspace (p_src, d_logits): any decode step, any other prefill
-    std::vector<int> fresh_slots;
-    int32_t* fk_dev = nullptr;             // [3][DOTS_MAX_BATCH] int32: a fork's destination slots, their tail pages, and (first entry) L - 1
-    std::vector<std::vector<int32_t>> slot_pages;
-    bf16_t* pool = nullptr;                // [layers][n_pool_pages + 1][Hkv][2][8192] bf16, or e4m3 bytes (kv8; decode.hip header)
-    size_t pool_layer_elems = 0;           // per layer, in bf16 units (an fp8 pool's layer is half as many)
-    bool kv8 = false;                      // DotsConfig.kv_cache_dtype == 1: the pool holds e4m3fn values
-    float* kv_scales = nullptr;            // [layers][Hkv][K | V] fp32 (dots_set_kv_scales; 1.0 until set), read by the fp8 writers and reader
-    int32_t *block_table = nullptr, *ctx_len = nullptr, *cur_tokens = nullptr, *out_ids = nullptr, *out_lens = nullptr,
-            *finished = nullptr, *eos_ids = nullptr, *am_idx = nullptr;
-    float* am_val = nullptr;
-    int n_eos = 0;
-    float temperature = 0.f, top_p = 1.f;      // temperature <= 0: greedy (arg max)
-    uint64_t seed = 0;
-    // which rows the per-row selection stage owns and for which features (row_stage.h): the only host record of it
-    RowStage stage;
-    // per-row selection (dots_set_row_sampling): device table + own flags, allocated on first use; penalty state
-    // (output counts, prompt-presence bits, penalised-logit scratch) allocated when a row first carries a penalty
-    RowParams* d_rowp = nullptr;
-    int32_t* d_row_own = nullptr;
-    uint32_t* d_row_thr = nullptr;
-    int32_t* pen_cnt = nullptr;
-    uint32_t* pen_seen = nullptr;
-    float* pen_logits = nullptr;
-    // logit rules (dots_set_row_logit_rules): per-row table + the dense "bias or -inf" image [max_batch][V], allocated by the
-    // first row that carries rules.  rule_stage: pinned host staging of one call's id / value lists ([V + DOTS_MAX_LOGIT_BIAS] int32, then
-    // [DOTS_MAX_LOGIT_BIAS] fp32) and its device twin; rule_ev guards the pinned buffer's reuse.
-    RowRules* d_rules = nullptr;
-    float* rule_img = nullptr;
-    int32_t *rule_stage = nullptr, *rule_stage_host = nullptr;
-    hipEvent_t rule_ev = nullptr;
-    int32_t h_eos[16] = {0};               // host mirror of eos_ids (the never-selectable checks of the rules)
-    // guided decoding (dots_set_row_guide): the packed bytes of the vocabulary (dots_set_token_bytes), the guides created on
-    // this engine (device tables; rows = how many rows hold each), and — allocated by the first row that takes a guide — the row table and
-    // the allowed bits [max_batch][guide_mask_words(V)].  row_guide[row] = guide id + 1 of a row that holds one.
-    int32_t* tok_off = nullptr;
-    uint8_t* tok_bytes = nullptr;
-    struct Guide { uint16_t* table = nullptr; uint8_t* accepting = nullptr; int n_states = 0, start = 0, rows = 0; };
-    std::vector<Guide> guides;
-    RowGuide* d_guides = nullptr;
-    uint32_t* guide_mask = nullptr;
-    int row_guide[DOTS_MAX_BATCH] = {0};
-    // no-repeat n-gram blocking (dots_set_row_ngram): allocated by the first row that takes a rule — the row table and the
-    // banned bits [max_batch][ngram_mask_words(V)]
-    RowNgram* d_ngram = nullptr;
-    uint32_t* ngram_mask = nullptr;
-    // stop strings (dots_set_row_stop): the automata created on this engine (device tables; rows = how many rows hold each) and
-    // — allocated by the first row that takes one — the row table.  Of a row that holds one: row_stop[row] = automaton id + 1, row_stop_min its min_tokens.
-    struct Stop { uint16_t* table = nullptr; uint16_t* match_len = nullptr; uint8_t* match_id = nullptr; int n_states = 0, rows = 0; };
-    std::vector<Stop> stops;
-    RowStop* d_stop = nullptr;
-    int row_stop[DOTS_MAX_BATCH] = {0};
-    int row_stop_min[DOTS_MAX_BATCH] = {0};
-    // log-probabilities (dots_set_row_logprobs): top_n per row (-1 = off) on the device and its host mirror; the outputs
-    // ([max_batch][max_seq_len] positions) and the stage's scratch are allocated by the first row switched on
-    int32_t* d_row_lp = nullptr;
-    float *lp_tok = nullptr, *lp_top = nullptr, *lp_ms = nullptr, *lp_pv = nullptr;
-    int32_t *lp_ids = nullptr, *lp_pi = nullptr, *lp_pos = nullptr;
-    int row_lp[DOTS_MAX_BATCH];
-    int n_lp = 0;                          // rows with logprobs on: > 0 adds the two logprob kernels around the selection stage
-    // n-gram speculative decoding (dots_set_speculation): spec_k drafts per slot and step (0 = off), the drafter's n-gram
-    // sizes (spec_max_n == 0: host drafts only), and — allocated by the first call that switches it on — the slots' drafts, the expanded
-    // row arrays of a speculating step and the counters (kernels.h SpecState)
-    int spec_k = 0, spec_min_n = 0, spec_max_n = 0;
-    int32_t *sp_drafts = nullptr, *sp_ndraft = nullptr, *sp_nlive = nullptr, *sp_tokens = nullptr, *sp_ctx = nullptr, *sp_table = nullptr;
-    unsigned long long* sp_stats = nullptr;
-    // which staged rows speculate (dots_set_speculation_rows: DOTS_SPEC_ROWS_* bits, 0 = plain greedy rows only) and the device array of
-    // every row's speculation class (kernels.h SpecRow), which spec_row_class() derives and the row setters write in stream order;
-    // sp_cand: the candidates of the draft rows of sampled slots.  row_pen / row_sampled: of a row that holds ROW_PARAMS, whether its
-    // parameters carry a penalty / a temperature > 0 (the two facts about them the class needs)
-    int spec_rows = 0;
-    int32_t *sp_cls = nullptr, *sp_cand = nullptr;
-    bool row_pen[DOTS_MAX_BATCH] = {false}, row_sampled[DOTS_MAX_BATCH] = {false};
-    int out_cap = 0;                       // row stride of out_ids for the current generation
-    bf16_t *d_h = nullptr, *d_q = nullptr, *d_att = nullptr, *d_act = nullptr, *d_xn = nullptr;      // d_xn: normalised rows of batches above 32 rows (decode_b64.hip)
-    float* d_part_h = nullptr;                     // [DEC_KSPLIT_PARTS][DOTS_MAX_BATCH][hidden] fp32: the K-quarter sums of a projection above 32 rows (decode_b64.hip)
-    float *d_part_o = nullptr, *d_part_ml = nullptr, *d_logits = nullptr;
-    // decode launch plan forced on every step (dots_set_decode_plan): 0 = by stream (whole chip / CU partition), 1 = always the partition plan
-    int force_part = 0;
-    int attn_stream = -1;                  // decode attention kernel (dots_set_decode_plan bits 1-2): -1 = by items per CU, 1 = streaming wherever legal, 0 = per split
-    int B = 0;                             // sequences of the current batch
-    int B_sel = 0;                         // rows the token-selection kernel runs over
-    // ---- continuous batching: every sequence slot b < max_batch is free or occupied; the decode graph runs over rows
-    // [0, highest occupied slot] and only commits tokens for occupied, unfinished slots
-    bool slot_mode = false;
-    bool sel_dirty = true;
-    int slot_active[DOTS_MAX_BATCH] = {0};
-    int slot_limit[DOTS_MAX_BATCH] = {0};  // prompt length + generation cap of the slot's sequence (lowered when the page pool runs dry)
-    int slot_prompt[DOTS_MAX_BATCH] = {0}; // prompt length
-    int slot_ctx_ub[DOTS_MAX_BATCH] = {0}; // host-side upper bound of the slot's context: prompt + decode steps issued (finished rows stop earlier)
-    int slot_done[DOTS_MAX_BATCH] = {0};   // seen finished at the last poll: grows no more
-    int32_t *d_sel = nullptr, *d_sel_new = nullptr, *d_max_len = nullptr, *p_dst = nullptr;
-    const int32_t* sel_now = nullptr;      // selection mask of the next select_tokens() call
-    // captured decode steps, keyed by everything the capture bakes in: rows, KV splits, static batch (out_cap = row stride of
-    // the output buffer) or slot mode (out_cap = 0), number of EOS ids, whether any row carries its own parameters (rowp: the per-row
-    // selection stage), whether any row returns logprobs (lp), whether any row carries logit rules (rules: the stage then gets their
-    // table), whether any row holds a guide (guided: the mask kernel and the guides' tables), whether any row carries an n-gram rule (ngram:
-    // the ban kernel and its bits), the draft count of a speculating step (spec: 0 = the plain step), whether that step draws the draft
-    // rows of sampled slots (draw: the two launches of launch_spec_draw); engine-wide sampling changes drop
-    // the cache (dots_set_sampling), per-row ones live in device memory.  step_key() builds the key from the engine's state: a feature that
-    // changes what a step launches adds a member here and a line there
-    struct StepKey {
-        int rows, splits, out_cap, n_eos, part, rowp, lp, rules, guided, ngram, spec, draw;
-        bool operator==(const StepKey& o) const { return std::memcmp(this, &o, sizeof(StepKey)) == 0; }
-    };
-    static_assert(std::has_unique_object_representations_v<StepKey>, "StepKey is compared bytewise: plain ints, no padding");
-    struct StepGraph { StepKey key; hipGraph_t graph; hipGraphExec_t exec; };
-    std::vector<StepGraph> step_graphs;
-    std::vector<int> h_prompt_lens;
-    int steps_done = 0;
-
-    // ---- image preprocessing scratch (grown on demand)
-    uint8_t *pp_in = nullptr, *pp_tmp = nullptr, *pp_out = nullptr;
-    int32_t* pp_tab = nullptr;
-    size_t pp_in_cap = 0, pp_tmp_cap = 0, pp_out_cap = 0, pp_tab_cap = 0;
-
-    // ---- debug: residual stream after every ViT block / LM prefill layer (dots_debug_capture_hidden)
-    bf16_t* dbg_hidden = nullptr;
-    size_t dbg_cap = 0;                    // elements
-    int64_t dbg_vit_rows = 0, dbg_lm_rows = 0;
-
-    // ---- timing
-    hipEvent_t ev[8]{};
-    std::vector<hipEvent_t> attn_ev;
-    DotsStats stats{};
-    int attn_pairs = 0;
-
-    int fail(int code, const char* fmt, ...) {
-        char buf[1024];
-        va_list ap;
-        va_start(ap, fmt);
-        vsnprintf(buf, sizeof(buf), fmt, ap);
-        va_end(ap);
-        err = buf;
-        return code;
-    }
-    template <typename T>
-    hipError_t alloc(T** p, size_t count) {
-        void* q = nullptr;
-        hipError_t e = hipMalloc(&q, std::max<size_t>(count * sizeof(T), 256));
-        if (e != hipSuccess) return e;
-        allocs.push_back(q);
-        *p = reinterpret_cast<T*>(q);
-        return hipMemsetAsync(q, 0, std::max<size_t>(count * sizeof(T), 256), stream);
-    }
-    void release(void* p) {
-        if (!p) return;
-        auto it = std::find(allocs.begin(), allocs.end(), p);
-        if (it != allocs.end()) allocs.erase(it);
-        hipFree(p);
-    }
-};
-
-static_assert(sizeof(RowParams) == sizeof(DotsSamplingParams) && offsetof(RowParams, seed) == offsetof(DotsSamplingParams, seed) &&
-                  offsetof(RowParams, presence_penalty) == offsetof(DotsSamplingParams, presence_penalty),
-              "RowParams (kernels.h) must mirror DotsSamplingParams");
-
-#define CK(expr)                                                                                         \
-    do {                                                                                                 \
-        hipError_t e_ = (expr);                                                                          \
-        if (e_ != hipSuccess) return e->fail(DOTS_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
-namespace {
-
-// ---------------------------------------------------------------------------------- weights
-const Tensor* find(DotsEngine* e, const std::string& name) {
-    auto it = e->raw.find(name);
-    return it == e->raw.end() ? nullptr : &it->second;
-}
-
-int need(DotsEngine* e, const std::string& name, std::initializer_list<int64_t> shape, bf16_t** out) {
-    const Tensor* t = find(e, name);
-    if (!t) return e->fail(DOTS_E_STATE, "missing weight %s", name.c_str());
-    if (t->shape != std::vector<int64_t>(shape)) return e->fail(DOTS_E_INVALID, "weight %s has unexpected shape", name.c_str());
-    *out = t->p;
-    return DOTS_OK;
-}
-
-int optional(DotsEngine* e, const std::string& name, std::initializer_list<int64_t> shape, bf16_t** out) {
-    const Tensor* t = find(e, name);
-    *out = nullptr;
-    if (!t) return DOTS_OK;
-    if (t->shape != std::vector<int64_t>(shape)) return e->fail(DOTS_E_INVALID, "weight %s has unexpected shape", name.c_str());
-    *out = t->p;
-    return DOTS_OK;
-}
-
-void drop(DotsEngine* e, const std::string& name) {
-    auto it = e->raw.find(name);
-    if (it == e->raw.end()) return;
-    e->release(it->second.p);
-    e->raw.erase(it);
-}
-
-#define RET(x) do { int r_ = (x); if (r_ != DOTS_OK) return r_; } while (0)
-
-// fp8 mode: W <- bf16(q) in place + a fresh scale array + the e4m3 bytes row-major; bf16 mode: *scale = *w8 = nullptr
-int quantize(DotsEngine* e, bf16_t* W, float** scale, int64_t N, int K, uint8_t** w8 = nullptr) {
-    *scale = nullptr;
-    if (w8) *w8 = nullptr;
-    if (!e->cfg.fp8_weights) return DOTS_OK;
-    CK(e->alloc(scale, (size_t)N));
-    CK(launch_quant_rows_fp8(e->stream, W, *scale, N, K));
-    if (w8) {
-        if (!gemm_fp8_supports((int)N, K)) return e->fail(DOTS_E_INVALID, "fp8_weights: a %lld x %d linear does not fit the fp8 GEMM (N %% 256, K %% 64)", (long long)N, K);
-        CK(e->alloc(w8, (size_t)N * K));
-        CK(launch_bf16q_to_fp8(e->stream, W, *w8, N * K));
-    }
-    return DOTS_OK;
-}
 
 // One dense layer of ViT / prefill: bf16 MFMA GEMM, or in fp8 mode per-token activation quantisation + the fp8 MFMA GEMM.
 int dense_on(DotsEngine* e, hipStream_t st, uint8_t* aq, float* as, const bf16_t* A, const bf16_t* W, const uint8_t* W8, const float* wscale,
@@ -444,341 +52,9 @@ int qkv_rope_on(DotsEngine* e, hipStream_t st, uint8_t* aq, float* as, const bf1
     return DOTS_OK;
 }
 
-// decode copy of a (quantised) row-major matrix: bf16 fragments, or e4m3 fragments in fp8 mode
-int decode_copy(DotsEngine* e, const bf16_t* W, void** out, int64_t rows, int K, int rot_rows) {
-    const size_t elems = (size_t)((rows + 15) / 16 * 16) * K;
-    if (e->cfg.fp8_weights) {
-        uint8_t* d = nullptr;
-        CK(e->alloc(&d, elems));
-        CK(launch_pack_frag_fp8(e->stream, W, d, rows, K, rot_rows));
-        *out = d;
-    } else {
-        bf16_t* d = nullptr;
-        CK(e->alloc(&d, elems));
-        if (rot_rows) CK(launch_pack_frag_qkv(e->stream, W, d, e->cfg.num_heads, e->cfg.num_kv_heads, K));
-        else CK(launch_pack_frag(e->stream, W, d, rows, K));
-        *out = d;
-    }
-    return DOTS_OK;
-}
-
-int finalize_weights(DotsEngine* e) {
-    const DotsConfig& c = e->cfg;
-    hipStream_t s = e->stream;
-    const int E = c.v_embed_dim, Iv = c.v_intermediate;
-    // ---- vision
-    {
-        const std::string pre = "vision_tower.patch_embed.patchifier.";
-        const Tensor* pw = find(e, pre + "proj.weight");
-        if (!pw) return e->fail(DOTS_E_STATE, "missing weight %sproj.weight", pre.c_str());
-        const int K = c.v_channels * c.v_patch * c.v_patch;
-        if (pw->numel() != (int64_t)E * K) return e->fail(DOTS_E_INVALID, "patch embed weight has unexpected size");
-        e->patch_k = K;
-        e->patch_kpad = (int)round_up(K, 64);
-        CK(e->alloc(&e->patch_w, (size_t)E * e->patch_kpad));
-        const int64_t n = (int64_t)E * e->patch_kpad;
-        hipLaunchKernelGGL(pad_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, pw->p, e->patch_w, E, K, e->patch_kpad);
-        RET(optional(e, pre + "proj.bias", {E}, &e->patch_b));
-        RET(need(e, pre + "norm.weight", {E}, &e->patch_norm));
-    }
-    e->vl.resize(c.v_layers);
-    for (int i = 0; i < c.v_layers; ++i) {
-        const std::string p = "vision_tower.blocks." + std::to_string(i) + ".";
-        VLayer& L = e->vl[i];
-        RET(need(e, p + "norm1.weight", {E}, &L.norm1));
-        RET(need(e, p + "attn.qkv.weight", {3 * E, E}, &L.qkv_w));
-        RET(optional(e, p + "attn.qkv.bias", {3 * E}, &L.qkv_b));
-        RET(need(e, p + "attn.proj.weight", {E, E}, &L.proj_w));
-        RET(optional(e, p + "attn.proj.bias", {E}, &L.proj_b));
-        RET(need(e, p + "norm2.weight", {E}, &L.norm2));
-        bf16_t *f1, *f3, *b1, *b3;
-        RET(need(e, p + "mlp.fc1.weight", {Iv, E}, &f1));
-        RET(need(e, p + "mlp.fc3.weight", {Iv, E}, &f3));
-        RET(need(e, p + "mlp.fc2.weight", {E, Iv}, &L.w2));
-        RET(optional(e, p + "mlp.fc1.bias", {Iv}, &b1));
-        RET(optional(e, p + "mlp.fc3.bias", {Iv}, &b3));
-        RET(optional(e, p + "mlp.fc2.bias", {E}, &L.b2));
-        CK(e->alloc(&L.w13, (size_t)2 * Iv * E));
-        CK(launch_pack_w13(s, f1, f3, L.w13, Iv, E));
-        L.b13 = nullptr;
-        if (b1 && b3) {
-            CK(e->alloc(&L.b13, (size_t)2 * Iv));
-            hipLaunchKernelGGL(pack_b13_kernel, dim3((2 * Iv + 255) / 256), dim3(256), 0, s, b1, b3, L.b13, Iv);
-        }
-        RET(quantize(e, L.qkv_w, &L.qkv_s, 3 * E, E, &L.qkv_8));
-        RET(quantize(e, L.proj_w, &L.proj_s, E, E, &L.proj_8));
-        RET(quantize(e, L.w13, &L.w13_s, 2 * Iv, E, &L.w13_8));          // packed row order: the scale index the SwiGLU epilogue uses
-        RET(quantize(e, L.w2, &L.w2_s, E, Iv, &L.w2_8));
-        CK(hipStreamSynchronize(s));
-        drop(e, p + "mlp.fc1.weight");
-        drop(e, p + "mlp.fc3.weight");
-    }
-    if (c.v_post_norm) RET(need(e, "vision_tower.post_trunk_norm.weight", {E}, &e->v_post_norm));
-    const int Mg = E * c.v_merge * c.v_merge;
-    RET(need(e, "vision_tower.merger.ln_q.weight", {E}, &e->m_ln_w));
-    RET(need(e, "vision_tower.merger.ln_q.bias", {E}, &e->m_ln_b));
-    RET(need(e, "vision_tower.merger.mlp.0.weight", {Mg, Mg}, &e->m0_w));
-    RET(need(e, "vision_tower.merger.mlp.0.bias", {Mg}, &e->m0_b));
-    RET(need(e, "vision_tower.merger.mlp.2.weight", {c.hidden_size, Mg}, &e->m2_w));
-    RET(need(e, "vision_tower.merger.mlp.2.bias", {c.hidden_size}, &e->m2_b));
-    RET(quantize(e, e->m0_w, &e->m0_s, Mg, Mg, &e->m0_8));
-    RET(quantize(e, e->m2_w, &e->m2_s, c.hidden_size, Mg, &e->m2_8));
-
-    // ---- language model
-    const int H = c.hidden_size, I = c.intermediate_size, Nq = c.num_heads * 128, Nkv = c.num_kv_heads * 128;
-    RET(need(e, "model.embed_tokens.weight", {c.vocab_size, H}, &e->embed));
-    RET(need(e, "model.norm.weight", {H}, &e->final_norm));
-    if (find(e, "lm_head.weight")) RET(need(e, "lm_head.weight", {c.vocab_size, H}, &e->lm_head));
-    else e->lm_head = e->embed;                      // tie_word_embeddings
-    if (c.fp8_weights) {                             // the embedding table stays bf16: quantise a copy of the (possibly tied) head
-        bf16_t* tmp = nullptr;
-        CK(hipMalloc(reinterpret_cast<void**>(&tmp), (size_t)c.vocab_size * H * 2));
-        hipError_t r = hipMemcpyAsync(tmp, e->lm_head, (size_t)c.vocab_size * H * 2, hipMemcpyDeviceToDevice, s);
-        int rc = r == hipSuccess ? quantize(e, tmp, &e->lm_head_s, c.vocab_size, H) : DOTS_E_HIP;
-        if (rc == DOTS_OK) rc = decode_copy(e, tmp, &e->lm_head_d, c.vocab_size, H, 0);
-        hipStreamSynchronize(s);
-        hipFree(tmp);
-        if (rc != DOTS_OK) return r == hipSuccess ? rc : e->fail(DOTS_E_HIP, "lm_head copy failed: %s", hipGetErrorString(r));
-    } else {
-        RET(decode_copy(e, e->lm_head, &e->lm_head_d, c.vocab_size, H, 0));
-    }
-    e->ll.resize(c.num_layers);
-    for (int i = 0; i < c.num_layers; ++i) {
-        const std::string p = "model.layers." + std::to_string(i) + ".";
-        LLayer& L = e->ll[i];
-        RET(need(e, p + "input_layernorm.weight", {H}, &L.ln1));
-        RET(need(e, p + "post_attention_layernorm.weight", {H}, &L.ln2));
-        bf16_t *qw, *kw, *vw, *qb, *kb, *vb, *gw, *uw;
-        RET(need(e, p + "self_attn.q_proj.weight", {Nq, H}, &qw));
-        RET(need(e, p + "self_attn.k_proj.weight", {Nkv, H}, &kw));
-        RET(need(e, p + "self_attn.v_proj.weight", {Nkv, H}, &vw));
-        RET(optional(e, p + "self_attn.q_proj.bias", {Nq}, &qb));
-        RET(optional(e, p + "self_attn.k_proj.bias", {Nkv}, &kb));
-        RET(optional(e, p + "self_attn.v_proj.bias", {Nkv}, &vb));
-        RET(need(e, p + "self_attn.o_proj.weight", {H, Nq}, &L.o_w));
-        RET(need(e, p + "mlp.gate_proj.weight", {I, H}, &gw));
-        RET(need(e, p + "mlp.up_proj.weight", {I, H}, &uw));
-        RET(need(e, p + "mlp.down_proj.weight", {H, I}, &L.down_w));
-        CK(e->alloc(&L.qkv_w, (size_t)(Nq + 2 * Nkv) * H));
-        CK(hipMemcpyAsync(L.qkv_w, qw, (size_t)Nq * H * 2, hipMemcpyDeviceToDevice, s));
-        CK(hipMemcpyAsync(L.qkv_w + (size_t)Nq * H, kw, (size_t)Nkv * H * 2, hipMemcpyDeviceToDevice, s));
-        CK(hipMemcpyAsync(L.qkv_w + (size_t)(Nq + Nkv) * H, vw, (size_t)Nkv * H * 2, hipMemcpyDeviceToDevice, s));
-        L.qkv_b = nullptr;
-        if (qb && kb && vb) {
-            CK(e->alloc(&L.qkv_b, (size_t)(Nq + 2 * Nkv)));
-            CK(hipMemcpyAsync(L.qkv_b, qb, (size_t)Nq * 2, hipMemcpyDeviceToDevice, s));
-            CK(hipMemcpyAsync(L.qkv_b + Nq, kb, (size_t)Nkv * 2, hipMemcpyDeviceToDevice, s));
-            CK(hipMemcpyAsync(L.qkv_b + Nq + Nkv, vb, (size_t)Nkv * 2, hipMemcpyDeviceToDevice, s));
-        }
-        CK(e->alloc(&L.w13, (size_t)2 * I * H));
-        CK(launch_pack_w13(s, gw, uw, L.w13, I, H));
-        RET(quantize(e, L.qkv_w, &L.qkv_s, Nq + 2 * Nkv, H, &L.qkv_8));
-        RET(quantize(e, L.o_w, &L.o_s, H, Nq, &L.o_8));
-        RET(quantize(e, L.w13, &L.w13_s, 2 * I, H, &L.w13_8));
-        RET(quantize(e, L.down_w, &L.down_s, H, I, &L.down_8));
-        // decode copies in MFMA fragment order (+3.1 GB of 288 GB, half of that in fp8 mode: every decode weight load is one contiguous chunk)
-        RET(decode_copy(e, L.qkv_w, &L.qkv_wd, Nq + 2 * Nkv, H, Nq + Nkv));                   // q / k rows permuted: whole RoPE pairs per tile
-        RET(decode_copy(e, L.o_w, &L.o_wd, H, Nq, 0));
-        RET(decode_copy(e, L.w13, &L.w13_wd, 2 * I, H, 0));
-        RET(decode_copy(e, L.down_w, &L.down_wd, H, I, 0));
-        CK(hipStreamSynchronize(s));
-        for (const char* n : {"self_attn.q_proj.weight", "self_attn.k_proj.weight", "self_attn.v_proj.weight",
-                              "mlp.gate_proj.weight", "mlp.up_proj.weight"})
-            drop(e, p + n);
-    }
-    // ---- rope frequency tables (same fp32 formula as the oracle / transformers)
-    {
-        std::vector<float> vf(32), lf(64);
-        for (int i = 0; i < 32; ++i) vf[i] = 1.0f / powf(10000.0f, (float)(2 * i) / 64.0f);
-        for (int i = 0; i < 64; ++i) lf[i] = 1.0f / powf(c.rope_theta, (float)(2 * i) / 128.0f);
-        CK(e->alloc(&e->v_inv_freq, 32));
-        CK(e->alloc(&e->lm_inv_freq, 64));
-        CK(hipMemcpyAsync(e->v_inv_freq, vf.data(), 32 * 4, hipMemcpyHostToDevice, s));
-        CK(hipMemcpyAsync(e->lm_inv_freq, lf.data(), 64 * 4, hipMemcpyHostToDevice, s));
-        CK(hipStreamSynchronize(s));
-    }
-    e->finalized = true;
-    return DOTS_OK;
-}
-
-int alloc_workspaces(DotsEngine* e) {
-    const DotsConfig& c = e->cfg;
-    const int E = c.v_embed_dim, H = c.hidden_size, Nq = c.num_heads * 128, Nkv = c.num_kv_heads * 128;
-    const int Mg = E * c.v_merge * c.v_merge;
-    e->P = c.max_patches;
-    e->Ppad = e->P + 64 * 256;                    // every image padded to a multiple of 64 keys
-    const int kpad = (int)round_up(c.v_channels * c.v_patch * c.v_patch, 64);
-    if (c.fp8_weights) {
-        const size_t v_max = (size_t)e->P * std::max(E, c.v_intermediate);          // the merger's inputs are [P / g][E g]: P E bytes as well
-        const size_t p_max = (size_t)c.max_prefill_tokens * std::max(H, std::max(Nq, c.intermediate_size));
-        CK(e->alloc(&e->act_q, p_max));
-        CK(e->alloc(&e->act_s, (size_t)c.max_prefill_tokens));
-        CK(e->alloc(&e->act_q_v, v_max));
-        CK(e->alloc(&e->act_s_v, (size_t)e->P));
-    }
-    CK(e->alloc(&e->v_xa, (size_t)e->P * kpad));
-    CK(e->alloc(&e->v_x, (size_t)e->P * E));
-    CK(e->alloc(&e->v_xn, (size_t)e->P * E));
-    CK(e->alloc(&e->v_qkv, (size_t)e->P * 3 * E));
-    CK(e->alloc(&e->v_q, (size_t)e->P * E));
-    CK(e->alloc(&e->v_k, (size_t)(e->P + 64) * E));
-    CK(e->alloc(&e->v_vt, (size_t)e->Ppad * E));
-    CK(e->alloc(&e->v_att, (size_t)e->P * E));
-    CK(e->alloc(&e->v_act, (size_t)e->P * c.v_intermediate));
-    CK(e->alloc(&e->v_mh, (size_t)(e->P / 4 + 1) * Mg));
-    CK(e->alloc(&e->vis, (size_t)(e->P / 4 + 1) * H));
-    CK(e->alloc(&e->vis_pref, (size_t)(e->P / 4 + 1) * H));
-    CK(e->alloc(&e->v_cs, (size_t)e->P * 64));
-    CK(e->alloc(&e->v_pos, (size_t)e->P * 2));
-    CK(e->alloc(&e->v_tiles, (size_t)(e->P / 64 + 256)));
-    CK(e->alloc(&e->v_qblocks, (size_t)(e->P / 128 + 256) * c.v_heads));
-
-    e->TP = c.max_prefill_tokens;
-    e->TPpad = e->TP + 64 * c.max_batch;
-    CK(e->alloc(&e->p_x, (size_t)e->TP * H));
-    CK(e->alloc(&e->p_xn, (size_t)e->TP * H));
-    CK(e->alloc(&e->p_qkv, (size_t)e->TP * (Nq + 2 * Nkv)));
-    CK(e->alloc(&e->p_q, (size_t)e->TP * Nq));
-    CK(e->alloc(&e->p_k, (size_t)(e->TP + 64) * Nkv));
-    CK(e->alloc(&e->p_vt, (size_t)e->TPpad * Nkv));
-    CK(e->alloc(&e->p_att, (size_t)e->TP * Nq));
-    CK(e->alloc(&e->p_act, (size_t)e->TP * c.intermediate_size));
-    CK(e->alloc(&e->p_cs, (size_t)e->TP * 64));
-    CK(e->alloc(&e->p_pos, (size_t)e->TP));
-    CK(e->alloc(&e->p_src, (size_t)e->TP));
-    CK(e->alloc(&e->p_last, (size_t)DOTS_MAX_BATCH));
-    CK(e->alloc(&e->p_tiles, (size_t)(e->TP / 64 + c.max_batch + 1)));
-    CK(e->alloc(&e->p_qblocks, (size_t)(e->TP / 128 + c.max_batch + 1) * c.num_heads));
-
-    e->max_pages = (c.max_seq_len + 63) / 64;
-    // paged KV: a pool of 64-token pages shared by all sequence slots; a sequence reserves ceil((prompt + generation cap) / 64)
-    // pages when it is prefilled and returns them when its slot is released (kv_pool_tokens = 0: room for max_batch sequences
-    // of max_seq_len, i.e. no sequence can ever be refused for lack of pages)
-    const int64_t pool_tokens = c.kv_pool_tokens > 0 ? c.kv_pool_tokens : (int64_t)c.max_batch * e->max_pages * 64;
-    e->n_pool_pages = (int)((pool_tokens + 63) / 64);
-    e->kv8 = c.kv_cache_dtype == 1;
-    e->pool_layer_elems = (size_t)(e->n_pool_pages + 1) * c.num_kv_heads * 2 * 8192 / (e->kv8 ? 2 : 1);
-    CK(e->alloc(&e->pool, e->pool_layer_elems * c.num_layers));
-    const std::vector<float> kv_ones((size_t)c.num_layers * c.num_kv_heads * 2, 1.0f);      // lives until the stream is synchronised below
-    CK(e->alloc(&e->kv_scales, kv_ones.size()));
-    CK(hipMemcpyAsync(e->kv_scales, kv_ones.data(), kv_ones.size() * 4, hipMemcpyHostToDevice, e->stream));
-    const int mb = (c.max_batch + 15) / 16 * 16;            // rows of the decode buffers: whole 16-row tiles
-    CK(e->alloc(&e->block_table, (size_t)mb * e->max_pages));
-    CK(e->alloc(&e->ctx_len, (size_t)mb));
-    CK(e->alloc(&e->cur_tokens, (size_t)mb));
-    CK(e->alloc(&e->out_ids, (size_t)mb * c.max_seq_len));
-    CK(e->alloc(&e->out_lens, (size_t)mb));
-    CK(e->alloc(&e->finished, (size_t)mb));
-    CK(e->alloc(&e->eos_ids, (size_t)16));
-    CK(e->alloc(&e->d_sel, (size_t)DOTS_MAX_BATCH));
-    CK(e->alloc(&e->d_sel_new, (size_t)DOTS_MAX_BATCH));
-    CK(e->alloc(&e->d_max_len, (size_t)DOTS_MAX_BATCH));
-    CK(e->alloc(&e->p_dst, (size_t)DOTS_MAX_BATCH));
-    CK(e->alloc(&e->fk_dev, (size_t)3 * DOTS_MAX_BATCH));
-    CK(e->alloc(&e->am_idx, (size_t)mb * 64));
-    CK(e->alloc(&e->am_val, (size_t)mb * 64));
-    CK(e->alloc(&e->d_h, (size_t)mb * H));
-    CK(e->alloc(&e->d_q, (size_t)mb * Nq));
-    CK(e->alloc(&e->d_att, (size_t)mb * Nq));
-    CK(e->alloc(&e->d_act, (size_t)mb * c.intermediate_size));
-    CK(e->alloc(&e->d_xn, (size_t)DOTS_MAX_BATCH * H));
-    CK(e->alloc(&e->d_part_h, (size_t)DEC_KSPLIT_PARTS * DOTS_MAX_BATCH * H));
-    CK(e->alloc(&e->d_logits, (size_t)mb * c.vocab_size));
-    CK(e->alloc(&e->d_part_o, (size_t)mb * c.num_heads * 64 * 128));
-    CK(e->alloc(&e->d_part_ml, (size_t)mb * c.num_heads * 64 * 2));
-    if (const char* fm = getenv("DOTS_OCR_DECODE_PLAN")) {
-        // the same rule as dots_set_decode_plan: a bit field since round 5 (bit 0 partition plan, + 2 streaming / + 4 per-split attention) — it used to be
-        // "any non-zero = partition plan", so an old setting of 2 or 3 now means the (slower) streaming attention kernel: values outside 0..5 and 6 / 7
-        // (both attention bits) are refused instead of silently re-interpreted
-        const int plan = atoi(fm);
-        if (plan < 0 || plan > 5 || (plan & 6) == 6) {
-            fprintf(stderr, "dots.ocr: DOTS_OCR_DECODE_PLAN=%s ignored: must be 0 / 1 (partition plan on every step), + 2 (streaming attention) or + 4 (per-split attention)\n", fm);
-        } else {
-            e->force_part = plan & 1;
-            e->attn_stream = (plan & 2) ? 1 : (plan & 4) ? 0 : -1;
-        }
-    }
-    if (const char* v = getenv("DOTS_OCR_TOWER_TAIL_LAYERS")) e->tail_fixed = std::max(-1, std::min(atoi(v), c.v_layers));      // dots_tower_tail
-    // every slot starts free: its block-table row points at the scratch page (an idle row of the fixed-shape decode graph
-    // keeps appending K/V at position 0 of whatever page its row names; it must never be a page a live sequence owns)
-    e->hp_table.assign((size_t)mb * e->max_pages, e->n_pool_pages);
-    e->slot_pages.assign(mb, {});
-    e->free_pages.resize(e->n_pool_pages);
-    e->page_refs.assign(e->n_pool_pages, 0);
-    for (int p = 0; p < e->n_pool_pages; ++p) e->free_pages[p] = e->n_pool_pages - 1 - p;      // pop_back hands out page 0 first
-    CK(hipMemcpyAsync(e->block_table, e->hp_table.data(), e->hp_table.size() * 4, hipMemcpyHostToDevice, e->stream));
-    for (auto& ev : e->ev) CK(hipEventCreate(&ev));
-    CK(hipStreamSynchronize(e->stream));
-    return DOTS_OK;
-}
-
 // this layer's fp8-KV scales [Hkv][2] for the pool launchers, or nullptr for a bf16 pool
 const float* layer_kv_scales(const DotsEngine* e, int layer) {
     return e->kv8 ? e->kv_scales + (size_t)layer * e->cfg.num_kv_heads * 2 : nullptr;
-}
-
-// ---- KV page allocator (host side; the kernels only ever see the block table)
-hipError_t upload_table_row(DotsEngine* e, int slot) {
-    return hipMemcpyAsync(e->block_table + (size_t)slot * e->max_pages, e->hp_table.data() + (size_t)slot * e->max_pages, (size_t)e->max_pages * 4,
-                          hipMemcpyHostToDevice, e->stream);
-}
-// the slot lets go of every page its row names; a page goes back to the free list when its last holder lets go (dots_slots_fork shares pages)
-void release_pages(DotsEngine* e, int slot) {
-    auto& mine = e->slot_pages[slot];
-    for (auto it = mine.rbegin(); it != mine.rend(); ++it)
-        if (--e->page_refs[*it] == 0) e->free_pages.push_back(*it);
-    mine.clear();
-    std::fill(e->hp_table.begin() + (size_t)slot * e->max_pages, e->hp_table.begin() + (size_t)(slot + 1) * e->max_pages, e->n_pool_pages);
-}
-// pages for `tokens` positions of the sequence in `slot` (it holds none yet); false: the pool cannot serve them
-bool reserve_pages(DotsEngine* e, int slot, int tokens) {
-    const int need = (tokens + 63) / 64;
-    if (need > (int)e->free_pages.size() || need > e->max_pages) return false;
-    auto& mine = e->slot_pages[slot];
-    for (int p = 0; p < need; ++p) {
-        mine.push_back(e->free_pages.back());
-        e->free_pages.pop_back();
-        e->page_refs[mine.back()] = 1;
-        e->hp_table[(size_t)slot * e->max_pages + p] = mine.back();
-    }
-    return true;
-}
-
-// On-demand growth (continuous batching): make the sequence in `slot` own pages for `tokens` positions; returns the positions its pages
-// cover afterwards (< tokens when the pool ran dry).  *changed: the block-table row has to be uploaded.
-int grow_pages(DotsEngine* e, int slot, int tokens, bool* changed) {
-    auto& mine = e->slot_pages[slot];
-    const int need = std::min((tokens + 63) / 64, e->max_pages);
-    while ((int)mine.size() < need && !e->free_pages.empty()) {
-        e->hp_table[(size_t)slot * e->max_pages + mine.size()] = e->free_pages.back();
-        mine.push_back(e->free_pages.back());
-        e->page_refs[mine.back()] = 1;
-        e->free_pages.pop_back();
-        *changed = true;
-    }
-    return (int)mine.size() * 64;
-}
-// tokens a slot sequence reserves at admission: its prompt plus the first page-worth of generated tokens (the rest on demand)
-constexpr int KV_ADMIT_AHEAD = 64;
-int admit_tokens(const DotsEngine* e, int prompt, int max_new) { return std::min(prompt + std::min(max_new, KV_ADMIT_AHEAD), e->cfg.max_seq_len); }
-
-// sequences -> 64-token tiles and 128-row query blocks
-// (Tile64.seq = the KV slot of the sequence: seq_ids[s], or s itself)
-void build_worklists(const std::vector<int>& lens, int Hq, std::vector<Tile64>& tiles, std::vector<QBlock>& qblocks, int64_t* Tpad_used,
-                     const int* seq_ids = nullptr) {
-    tiles.clear();
-    qblocks.clear();
-    int tok0 = 0, pad0 = 0;
-    for (size_t s = 0; s < lens.size(); ++s) {
-        const int n = lens[s];
-        const int seq = seq_ids ? seq_ids[s] : (int)s;
-        for (int t = 0; t * 64 < n; ++t) tiles.push_back(Tile64{tok0 + t * 64, std::min(64, n - t * 64), pad0 + t * 64, seq, t, 0});
-        for (int h = 0; h < Hq; ++h)
-            for (int q = 0; q < n; q += flash_rows_per_block()) qblocks.push_back(QBlock{q, n, tok0, pad0, h, 0});
-        tok0 += n;
-        pad0 += (int)round_up(n, 64);
-    }
-    *Tpad_used = pad0;
 }
 
 hipError_t attn_event(DotsEngine* e, int idx) {
@@ -812,8 +88,6 @@ int check_vision_request(DotsEngine* e, int64_t N, const int64_t* grid, int n_im
     if (n_seq > 256) return e->fail(DOTS_E_CAPACITY, "more than 256 images per call");
     return DOTS_OK;
 }
-
-int chain_streams(DotsEngine* e, hipStream_t from, hipStream_t to);
 
 int vit_forward(DotsEngine* e, const float* pix_dev, int64_t N, const int64_t* grid, int n_img, void* out_dev, bf16_t* vis_out, int64_t* rows_out) {
     const DotsConfig& c = e->cfg;
@@ -918,341 +192,6 @@ int vit_forward(DotsEngine* e, const float* pix_dev, int64_t N, const int64_t* g
     return DOTS_OK;
 }
 
-// the bookkeeping arrays of a slot-mode step, as select_tokens hands them to the selection kernels (the speculative kernels of spec.hip
-// read and commit through the same state)
-StepState step_state(const DotsEngine* e, int advance, const int32_t* sel) {
-    StepState st;
-    st.cur_tokens = e->cur_tokens; st.ctx_len = e->ctx_len; st.out_ids = e->out_ids; st.out_lens = e->out_lens; st.finished = e->finished;
-    st.eos_ids = e->eos_ids; st.n_eos = e->n_eos; st.advance_ctx = advance;
-    st.sel = sel; st.max_len = e->d_max_len; st.out_stride = e->cfg.max_seq_len; st.cap = e->cfg.max_seq_len;
-    return st;
-}
-
-// does a speculating step draw the draft rows of sampled slots (launch_spec_draw)?  Only while rows with parameters may speculate and at
-// least one row holds parameters: with dots_set_speculation_rows at 0 a step launches what it always did
-bool spec_draws(const DotsEngine* e) {
-    return e->slot_mode && e->spec_k > 0 && (e->spec_rows & SPEC_ROWS_SAMPLED) && e->stage.rows(ROW_PARAMS) > 0;
-}
-
-SpecState spec_state(const DotsEngine* e) {
-    return SpecState{e->sp_drafts, e->sp_ndraft, e->sp_nlive, e->sp_tokens, e->sp_ctx, e->sp_table, e->sp_stats, e->sp_cls,
-                     spec_draws(e) ? e->sp_cand : nullptr, e->spec_k, e->temperature > 0.f ? 0 : 1};
-}
-
-// The speculation class of a row (kernels.h SpecRow), from the host's record alone.  THE place that decides it: the stage
-// features and the penalty of the row's parameters through RowStage::speculates, and logprobs (not a stage feature).  The engine-wide
-// temperature is not a row's fact: the kernels get it as engine_greedy.
-int spec_row_class(const DotsEngine* e, int row) {
-    if (e->row_lp[row] >= 0 || !e->stage.speculates(row, e->row_pen[row], e->spec_rows)) return SPEC_ROW_NONE;
-    return e->stage.has(row, ROW_PARAMS) && e->row_sampled[row] ? SPEC_ROW_DRAW : SPEC_ROW_ARGMAX;
-}
-
-// the row's class to the device in stream order, after anything that may change it (the array exists once speculation was switched on)
-int sync_spec_class(DotsEngine* e, int row) {
-    if (e->sp_cls) CK(launch_spec_set_class(e->stream, e->sp_cls, row, spec_row_class(e, row)));
-    return DOTS_OK;
-}
-
-// every row's class from the host's record in one copy (the setting changed, or the array is new); the call waits for it
-int upload_spec_classes(DotsEngine* e) {
-    if (!e->sp_cls) return DOTS_OK;
-    int32_t cls[DOTS_MAX_BATCH];
-    for (int b = 0; b < DOTS_MAX_BATCH; ++b) cls[b] = spec_row_class(e, b);
-    CK(hipMemcpyAsync(e->sp_cls, cls, sizeof(cls), hipMemcpyHostToDevice, e->stream));
-    CK(hipStreamSynchronize(e->stream));
-    return DOTS_OK;
-}
-
-// greedy arg max or temperature / top-p sampling over the fp32 logits of the step
-int select_tokens(DotsEngine* e, int advance) {
-    const DotsConfig& c = e->cfg;
-    StepState st = step_state(e, advance, e->sel_now);
-    if (!e->slot_mode) { st.sel = nullptr; st.max_len = nullptr; st.out_stride = e->out_cap; st.cap = e->out_cap; }      // a static batch
-    // logprobs: the partial kernel reads the logits and snapshots finished / out_lens before selection commits, the final kernel
-    // reads the committed token after it
-    const LogprobState ls{e->d_row_lp, st.sel, e->finished, e->out_lens, e->cur_tokens, e->lp_ms, e->lp_pv, e->lp_pi, e->lp_pos,
-                          e->lp_tok, e->lp_ids, e->lp_top, c.max_seq_len};
-    if (e->n_lp > 0) CK(launch_logprob_partial(e->stream, e->d_logits, c.vocab_size, c.vocab_size, e->B_sel, ls));
-    if (e->stage.staged_rows() > 0) {      // per-row stage for the rows with their own parameters (+ the greedy rows that follow the engine)
-        RowSel rs{e->d_rowp, e->d_row_own, e->pen_cnt, e->pen_seen, e->pen_logits, e->d_row_thr, e->temperature > 0.f ? 0 : 1,
-                  e->stage.rows(ROW_RULES) > 0 ? e->d_rules : nullptr, e->rule_img, GuideSel{}, NgramSel{}, StopSel{}};
-        // the stop-string rows' table, once any row has held one (allocating it drops the captured steps, so no cache key changes): the
-        // commit of a row that holds an automaton walks it, no launch is added
-        if (e->d_stop) rs.stop = StopSel{e->d_stop, e->tok_off, e->tok_bytes, c.vocab_size, 0};
-        if (e->stage.rows(ROW_NGRAM) > 0) {        // the n-gram rows' banned bits from their own output so far, before the stage reads the logits
-            rs.ngram = NgramSel{e->d_ngram, e->ngram_mask, ngram_mask_words(c.vocab_size), c.vocab_size};
-            CK(launch_ngram_ban(e->stream, rs.ngram, e->B_sel, st.out_ids, st.out_lens, st.out_stride, st.finished, st.sel));
-        }
-        if (e->stage.rows(ROW_GUIDE) > 0) {        // the guided rows' allowed bits from their current states, before the stage reads the logits
-            rs.guide = GuideSel{e->d_guides, e->guide_mask, e->tok_off, e->tok_bytes, guide_mask_words(c.vocab_size), c.vocab_size};
-            CK(launch_guide_mask(e->stream, rs.guide, e->B_sel, st.sel));
-        }
-        CK(launch_select_rows(e->stream, e->d_logits, c.vocab_size, c.vocab_size, e->B_sel, rs, e->am_val, e->am_idx, st));
-        if (e->temperature > 0.f)
-            CK(launch_sample_step(e->stream, e->d_logits, c.vocab_size, c.vocab_size, e->B_sel, e->temperature, e->top_p, e->seed, st, e->d_row_own));
-    } else if (e->temperature > 0.f)
-        CK(launch_sample_step(e->stream, e->d_logits, c.vocab_size, c.vocab_size, e->B_sel, e->temperature, e->top_p, e->seed, st));
-    else
-        CK(launch_argmax_step(e->stream, e->d_logits, c.vocab_size, c.vocab_size, e->B_sel, e->am_val, e->am_idx, st));
-    if (e->n_lp > 0) CK(launch_logprob_final(e->stream, e->d_logits, c.vocab_size, c.vocab_size, e->B_sel, ls));
-    return DOTS_OK;
-}
-
-void drop_step_graphs(DotsEngine* e) {
-    for (auto& g : e->step_graphs) {
-        hipGraphExecDestroy(g.exec);
-        hipGraphDestroy(g.graph);
-    }
-    e->step_graphs.clear();
-}
-
-int ensure_row_table(DotsEngine* e) {
-    if (e->d_rowp) return DOTS_OK;
-    CK(e->alloc(&e->d_rowp, DOTS_MAX_BATCH));
-    CK(e->alloc(&e->d_row_own, DOTS_MAX_BATCH));
-    CK(e->alloc(&e->d_row_thr, DOTS_MAX_BATCH));
-    return DOTS_OK;
-}
-
-int ensure_pen_state(DotsEngine* e) {
-    if (e->pen_cnt) return DOTS_OK;
-    const size_t rows = e->cfg.max_batch, V = e->cfg.vocab_size;
-    CK(e->alloc(&e->pen_cnt, rows * V));
-    CK(e->alloc(&e->pen_seen, rows * ((V + 31) / 32)));
-    if (!e->pen_logits) CK(e->alloc(&e->pen_logits, rows * V));      // shared with the logit rules
-    drop_step_graphs(e);                                   // graphs captured before hold no penalty state
-    return DOTS_OK;
-}
-
-// table, image, shaped-logit scratch and staging of the logit rules, allocated by the first row that carries rules
-int ensure_rules_state(DotsEngine* e) {
-    if (e->d_rules) return DOTS_OK;
-    // each piece is allocated once: a call that failed half way is resumed by the next one, nothing is allocated twice
-    const size_t rows = e->cfg.max_batch, V = e->cfg.vocab_size, n_stage = V + 2 * DOTS_MAX_LOGIT_BIAS;
-    if (!e->rule_img) CK(e->alloc(&e->rule_img, rows * V));
-    if (!e->pen_logits) CK(e->alloc(&e->pen_logits, rows * V));
-    if (!e->rule_stage) CK(e->alloc(&e->rule_stage, n_stage));
-    if (!e->rule_stage_host) {
-        CK(hipHostMalloc((void**)&e->rule_stage_host, n_stage * 4, hipHostMallocDefault));
-        std::memset(e->rule_stage_host, 0, n_stage * 4);
-    }
-    if (!e->rule_ev) CK(hipEventCreateWithFlags(&e->rule_ev, hipEventDisableTiming));
-    CK(e->alloc(&e->d_rules, DOTS_MAX_BATCH));             // zeroed by alloc(): no row carries rules; set last, it is the guard above
-    drop_step_graphs(e);                                   // graphs captured before hold no shaped-logit scratch
-    return DOTS_OK;
-}
-
-// row table and allowed bits of the guides, allocated by the first row that takes one
-int ensure_guide_state(DotsEngine* e) {
-    if (e->d_guides) return DOTS_OK;
-    const size_t rows = e->cfg.max_batch, V = e->cfg.vocab_size;
-    if (!e->guide_mask) CK(e->alloc(&e->guide_mask, rows * guide_mask_words((int)V)));
-    if (!e->pen_logits) CK(e->alloc(&e->pen_logits, rows * V));       // the shaped logits of a sampled guided row
-    CK(e->alloc(&e->d_guides, DOTS_MAX_BATCH));            // zeroed by alloc(): no row holds a guide; set last, it is the guard above
-    drop_step_graphs(e);                                   // graphs captured before hold no guide state
-    return DOTS_OK;
-}
-
-// row table and banned bits of the n-gram rules, allocated by the first row that takes one
-int ensure_ngram_state(DotsEngine* e) {
-    if (e->d_ngram) return DOTS_OK;
-    // each piece is allocated once: a call that failed half way is resumed by the next one
-    const size_t rows = e->cfg.max_batch, V = e->cfg.vocab_size;
-    if (!e->ngram_mask) CK(e->alloc(&e->ngram_mask, rows * ngram_mask_words((int)V)));
-    if (!e->pen_logits) CK(e->alloc(&e->pen_logits, rows * V));       // the shaped logits of a sampled n-gram row
-    CK(e->alloc(&e->d_ngram, DOTS_MAX_BATCH));             // zeroed by alloc(): no row carries a rule; set last, it is the guard above
-    drop_step_graphs(e);                                   // graphs captured before hold no n-gram state
-    return DOTS_OK;
-}
-
-// row table of the stop strings, allocated by the first row that takes an automaton
-int ensure_stop_state(DotsEngine* e) {
-    if (e->d_stop) return DOTS_OK;
-    CK(e->alloc(&e->d_stop, DOTS_MAX_BATCH));              // zeroed by alloc(): no row holds an automaton
-    drop_step_graphs(e);                                   // graphs captured before hold no stop table
-    return DOTS_OK;
-}
-
-// what a row without parameters of its own is selected with once the per-row stage owns it (logit rules): the engine-wide setting as it stands
-RowParams engine_row_params(const DotsEngine* e) { return RowParams{e->temperature, e->top_p, 0, 1.f, 0.f, 0.f, e->seed}; }
-
-// Row `row` takes feature f: it enters the per-row stage unless another feature holds it there already, with the engine-wide setting as
-// its entry and the own flag set (stream ordered).  Own parameters are that entry themselves: their setter has written it.
-int enter_row_stage(DotsEngine* e, int row, RowFeature f) {
-    RET(ensure_row_table(e));
-    if (e->stage.attach(row, f) && f != ROW_PARAMS) CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, engine_row_params(e), 1));
-    return sync_spec_class(e, row);
-}
-
-// Feature f comes off row `row`: with its last feature the row leaves the stage (entry and own flag zeroed); own parameters taken off a
-// row that stays give the entry back to the engine-wide setting (stream ordered)
-int leave_row_stage(DotsEngine* e, int row, RowFeature f) {
-    if (!e->stage.has(row, f)) return DOTS_OK;
-    if (e->stage.detach(row, f)) CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, RowParams{}, 0));
-    else if (f == ROW_PARAMS) CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, engine_row_params(e), 1));
-    return sync_spec_class(e, row);
-}
-
-// feature f off row `row` (stream ordered): the feature's own table entry and reference count, then the stage
-int clear_row_feature(DotsEngine* e, int row, RowFeature f) {
-    if (!e->stage.has(row, f)) return DOTS_OK;
-    switch (f) {
-    case ROW_RULES:
-        CK(launch_set_row_rules(e->stream, e->d_rules, e->rule_img, row, e->cfg.vocab_size, RowRules{}, nullptr, 0, nullptr, nullptr, 0));
-        break;
-    case ROW_GUIDE:
-        CK(launch_set_row_guide(e->stream, e->d_guides, row, RowGuide{}));
-        e->guides[e->row_guide[row] - 1].rows -= 1;
-        e->row_guide[row] = 0;
-        break;
-    case ROW_NGRAM:
-        CK(launch_set_row_ngram(e->stream, e->d_ngram, row, RowNgram{}));
-        break;
-    case ROW_STOP:
-        CK(launch_set_row_stop(e->stream, e->d_stop, row, RowStop{}));
-        e->stops[e->row_stop[row] - 1].rows -= 1;
-        e->row_stop[row] = e->row_stop_min[row] = 0;
-        break;
-    default: break;                                        // own parameters: the stage entry is all there is
-    }
-    return leave_row_stage(e, row, f);
-}
-
-// host side of row `row` taking automaton id (a live one): stage membership, the automata's reference counts and the row's payload.  The
-// caller writes the row's table entry (dots_set_row_stop one row, dots_slots_fork all children at once)
-int hold_row_stop(DotsEngine* e, int row, int id, int min_tokens) {
-    if (e->stage.has(row, ROW_STOP)) e->stops[e->row_stop[row] - 1].rows -= 1;
-    RET(enter_row_stage(e, row, ROW_STOP));
-    e->row_stop[row] = id + 1;
-    e->row_stop_min[row] = min_tokens;
-    e->stops[id].rows += 1;
-    return DOTS_OK;
-}
-
-// row `row` holds automaton id (a live one) from the root with no hit (stream ordered)
-int assign_row_stop(DotsEngine* e, int row, int id, int min_tokens) {
-    RET(ensure_row_table(e));
-    RET(ensure_stop_state(e));
-    const DotsEngine::Stop& a = e->stops[id];
-    CK(launch_set_row_stop(e->stream, e->d_stop, row, RowStop{a.table, a.match_len, a.match_id, a.n_states, 0, min_tokens, -1, 0, 0, -1, 0}));
-    return hold_row_stop(e, row, id, min_tokens);
-}
-
-int check_row_params(DotsEngine* e, const DotsSamplingParams& p, RowParams* out) {
-    if (!(p.temperature >= 0.f) || !std::isfinite(p.temperature)) return e->fail(DOTS_E_INVALID, "temperature must be finite and >= 0");
-    if (!(p.top_p > 0.f)) return e->fail(DOTS_E_INVALID, "top_p must be in (0, 1]");
-    if (p.top_k < 0) return e->fail(DOTS_E_INVALID, "top_k must be 0 (off) or >= 1");
-    if (!(p.repetition_penalty > 0.f) || !std::isfinite(p.repetition_penalty)) return e->fail(DOTS_E_INVALID, "repetition_penalty must be finite and > 0");
-    if (!(p.frequency_penalty >= -2.f && p.frequency_penalty <= 2.f)) return e->fail(DOTS_E_INVALID, "frequency_penalty must be in [-2, 2]");
-    if (!(p.presence_penalty >= -2.f && p.presence_penalty <= 2.f)) return e->fail(DOTS_E_INVALID, "presence_penalty must be in [-2, 2]");
-    *out = RowParams{p.temperature, p.top_p > 1.f ? 1.f : p.top_p, p.top_k, p.repetition_penalty, p.frequency_penalty, p.presence_penalty, p.seed};
-    return DOTS_OK;
-}
-
-// Validate one row's logit rules against vocabulary V and the engine's EOS ids -> the device entry.  Refused: a value out of range, a
-// duplicate bias id, and rules that could never select a token (an empty allowed list, one that the bans cover, or — with min_tokens > 0 —
-// one that the bans, the EOS ids and the stop ids cover together).
-int check_logit_rules(DotsEngine* e, const DotsLogitRules& r, int V, const int32_t* eos, int n_eos, RowRules* out) {
-    if (r.n_bias < 0 || r.n_bias > DOTS_MAX_LOGIT_BIAS || (r.n_bias && (!r.bias_ids || !r.bias_values)))
-        return e->fail(DOTS_E_INVALID, "logit rules: n_bias must be in [0, %d]", DOTS_MAX_LOGIT_BIAS);
-    if (r.n_allowed < 0 || r.n_allowed > V || (r.n_allowed && !r.allowed_ids)) return e->fail(DOTS_E_INVALID, "logit rules: n_allowed must be in [0, %d]", V);
-    if (r.allowed_ids && r.n_allowed == 0) return e->fail(DOTS_E_INVALID, "logit rules: the allowed list is empty");
-    if (r.min_tokens < 0) return e->fail(DOTS_E_INVALID, "logit rules: min_tokens must be >= 0");
-    if (r.n_stop < 0 || r.n_stop > DOTS_MAX_STOP_IDS) return e->fail(DOTS_E_INVALID, "logit rules: n_stop must be in [0, %d]", DOTS_MAX_STOP_IDS);
-    std::vector<uint8_t> mark(V, 0);                       // 1 = carries a bias, 2 = banned, 4 = allowed, 8 = EOS or stop id
-    for (int j = 0; j < r.n_bias; ++j) {
-        const int id = r.bias_ids[j];
-        const float v = r.bias_values[j];
-        if (id < 0 || id >= V) return e->fail(DOTS_E_INVALID, "logit rules: bias id %d outside [0, %d)", id, V);
-        if (mark[id] & 1) return e->fail(DOTS_E_INVALID, "logit rules: bias id %d given twice", id);
-        if (!(std::isfinite(v) || (std::isinf(v) && v < 0.f))) return e->fail(DOTS_E_INVALID, "logit rules: the bias of id %d must be finite or -inf", id);
-        mark[id] |= std::isinf(v) ? 3 : 1;
-    }
-    for (int j = 0; j < r.n_stop; ++j) {
-        if (r.stop_ids[j] < 0 || r.stop_ids[j] >= V) return e->fail(DOTS_E_INVALID, "logit rules: stop id %d outside [0, %d)", r.stop_ids[j], V);
-        mark[r.stop_ids[j]] |= 8;
-    }
-    for (int j = 0; j < n_eos; ++j) if (eos[j] >= 0 && eos[j] < V) mark[eos[j]] |= 8;
-    if (r.allowed_ids) {
-        int free_now = 0, free_early = 0;                  // allowed ids that are not banned / and neither an EOS nor a stop id
-        for (int j = 0; j < r.n_allowed; ++j) {
-            const int id = r.allowed_ids[j];
-            if (id < 0 || id >= V) return e->fail(DOTS_E_INVALID, "logit rules: allowed id %d outside [0, %d)", id, V);
-            if (!(mark[id] & 2)) { free_now += 1; free_early += (mark[id] & 8) ? 0 : 1; }
-        }
-        if (!free_now) return e->fail(DOTS_E_INVALID, "logit rules: every allowed id is banned by the bias");
-        if (r.min_tokens > 0 && !free_early) return e->fail(DOTS_E_INVALID, "logit rules: below min_tokens every allowed id is an EOS or a stop id");
-    }
-    RowRules rr{};
-    rr.flags = RULE_ON | ((r.n_bias || r.allowed_ids) ? RULE_IMG : 0) | (r.ignore_eos ? RULE_IGNORE_EOS : 0);
-    rr.min_tokens = r.min_tokens;
-    rr.n_stop = r.n_stop;
-    std::copy(r.stop_ids, r.stop_ids + r.n_stop, rr.stop);
-    *out = rr;
-    return DOTS_OK;
-}
-
-// Validate one row's n-gram rule against vocabulary V and the longest output max_len -> the device entry
-int check_ngram_rule(DotsEngine* e, const DotsNgramRule& r, int V, int max_len, RowNgram* out) {
-    if (V > NGRAM_MAX_V) return e->fail(DOTS_E_INVALID, "n-gram rule: the vocabulary %d exceeds the %d ids the ban kernel holds", V, NGRAM_MAX_V);
-    if (r.size < 1 || r.size > DOTS_MAX_NGRAM_SIZE) return e->fail(DOTS_E_INVALID, "n-gram rule: size must be in [1, %d], got %d", DOTS_MAX_NGRAM_SIZE, r.size);
-    if (r.window != 0 && (r.window < r.size || r.window > max_len))
-        return e->fail(DOTS_E_INVALID, "n-gram rule: window must be 0 (the whole output) or in [size = %d, %d], got %d", r.size, max_len, r.window);
-    if (r.n_whitelist < 0 || r.n_whitelist > DOTS_MAX_NGRAM_WHITELIST)
-        return e->fail(DOTS_E_INVALID, "n-gram rule: n_whitelist must be in [0, %d]", DOTS_MAX_NGRAM_WHITELIST);
-    RowNgram rn{};
-    rn.n = r.size;
-    rn.window = r.window;
-    rn.n_white = r.n_whitelist;
-    for (int j = 0; j < r.n_whitelist; ++j) {
-        const int id = r.whitelist[j];
-        if (id < 0 || id >= V) return e->fail(DOTS_E_INVALID, "n-gram rule: whitelist id %d outside [0, %d)", id, V);
-        for (int k = 0; k < j; ++k)
-            if (r.whitelist[k] == id) return e->fail(DOTS_E_INVALID, "n-gram rule: whitelist id %d given twice", id);
-        rn.white[j] = id;
-    }
-    *out = rn;
-    return DOTS_OK;
-}
-
-// logprob outputs + scratch, allocated by the first row switched on; every output byte starts as 0xFF (NaN / -1)
-int ensure_lp_state(DotsEngine* e) {
-    if (e->lp_tok) return DOTS_OK;
-    const size_t rows = e->cfg.max_batch, pos = (size_t)rows * e->cfg.max_seq_len, K = DOTS_MAX_TOP_LOGPROBS;
-    hipStream_t s = e->stream;
-    CK(e->alloc(&e->lp_ms, rows * LP_CHUNKS * 2));
-    CK(e->alloc(&e->lp_pv, rows * LP_CHUNKS * K));
-    CK(e->alloc(&e->lp_pi, rows * LP_CHUNKS * K));
-    CK(e->alloc(&e->lp_pos, rows));
-    CK(e->alloc(&e->lp_ids, pos * K));
-    CK(e->alloc(&e->lp_top, pos * K));
-    CK(e->alloc(&e->lp_tok, pos));
-    CK(hipMemsetAsync(e->lp_tok, 0xFF, pos * 4, s));
-    CK(hipMemsetAsync(e->lp_ids, 0xFF, pos * K * 4, s));
-    CK(hipMemsetAsync(e->lp_top, 0xFF, pos * K * 4, s));
-    return DOTS_OK;
-}
-
-// positions of `row` back to NaN / -1 (at each prefill of the row once the outputs exist)
-int clear_lp_row(DotsEngine* e, int row) {
-    if (!e->lp_tok) return DOTS_OK;
-    const size_t L = e->cfg.max_seq_len, K = DOTS_MAX_TOP_LOGPROBS;
-    CK(hipMemsetAsync(e->lp_tok + (size_t)row * L, 0xFF, L * 4, e->stream));
-    CK(hipMemsetAsync(e->lp_ids + (size_t)row * L * K, 0xFF, L * K * 4, e->stream));
-    CK(hipMemsetAsync(e->lp_top + (size_t)row * L * K, 0xFF, L * K * 4, e->stream));
-    return DOTS_OK;
-}
-
-// top_n of the row (-1 = off), in stream order; keeps n_lp, the count of rows that are on
-int set_row_lp(DotsEngine* e, int row, int top_n) {
-    const bool was = e->row_lp[row] >= 0;
-    if (!was && top_n < 0) return DOTS_OK;
-    CK(launch_set_row_lp(e->stream, e->d_row_lp, row, top_n));
-    e->row_lp[row] = top_n;
-    e->n_lp += (top_n >= 0 ? 1 : 0) - (was ? 1 : 0);
-    return sync_spec_class(e, row);
-}
-
 // CU-masked side streams of the vision prefetch, created on first use.  Mask bit i = CU i / 8 of XCD i % 8 (profiles/r01_probe_cu_mask.txt):
 // bits [0, dec_cus) for the decode loop, [dec_cus, 256) for the tower — each an equal share of every XCD.
 int ensure_overlap_streams(DotsEngine* e) {
@@ -1296,29 +235,6 @@ int pick_tower_tail(DotsEngine* e) {
     return std::max(0, std::min(tail, L / 2));
 }
 
-// make `to` wait for everything enqueued on `from` so far
-int chain_streams(DotsEngine* e, hipStream_t from, hipStream_t to) {
-    if (from == to) return DOTS_OK;
-    CK(hipEventRecord(e->ev_xs, from));
-    CK(hipStreamWaitEvent(to, e->ev_xs, 0));
-    return DOTS_OK;
-}
-
-// The stream the next decode chunk should be replayed on: the lower CU partition while a prefetched tower is still running (the two then
-// share the chip instead of time-slicing it), the whole chip otherwise.  Hands the dependency over when the stream changes.
-int pick_decode_stream(DotsEngine* e, hipStream_t* cur) {
-    hipStream_t want = e->stream;
-    if (e->s_vit && e->pref_pending && !e->pref_deferred && hipEventQuery(e->ev_vis_ready) == hipErrorNotReady) {
-        (void)hipGetLastError();                   // "not ready" must not stay behind as the thread's last error (PyTorch / RCCL check it)
-        want = e->s_dec;
-    }
-    if (want != *cur) {
-        RET(chain_streams(e, *cur, want));
-        *cur = want;
-    }
-    return DOTS_OK;
-}
-
 int stage_pixels(DotsEngine* e, hipStream_t st, const float* pixel_values, int on_device, int64_t total_patches, const float** pix) {
     *pix = pixel_values;
     if (!on_device) {
@@ -1352,10 +268,85 @@ int launch_prefetched_tower(DotsEngine* e) {
     return r;
 }
 
+// everything a captured step bakes in, from the engine's state as it stands (DotsEngine::StepKey)
+DotsEngine::StepKey step_key(const DotsEngine* e, int rows, int n_splits, int out_cap, int part) {
+    DotsEngine::StepKey k;
+    k.rows = rows; k.splits = n_splits; k.out_cap = out_cap; k.n_eos = e->n_eos; k.part = part;
+    k.rowp = e->stage.staged_rows() > 0;
+    k.lp = e->n_lp > 0;
+    k.rules = e->stage.rows(ROW_RULES) > 0;
+    k.guided = e->stage.rows(ROW_GUIDE) > 0;
+    k.ngram = e->stage.rows(ROW_NGRAM) > 0;
+    k.spec = e->slot_mode ? e->spec_k : 0;
+    k.draw = spec_draws(e);
+    return k;
+}
+
+double decode_step_bytes(const DotsConfig& c) {
+    const double H = c.hidden_size, Nq = c.num_heads * 128.0, Nkv = c.num_kv_heads * 128.0, I = c.intermediate_size;
+    // SURVEY §8(d): every weight byte once per step.  bf16: 2 B per weight; fp8 mode: 1 B per linear weight + 4 B per output channel
+    // (scale), norms and biases stay bf16
+    const double lin = H * (Nq + 2 * Nkv) + Nq * H + 3 * H * I, chans = (Nq + 2 * Nkv) + H + 2 * I + H;
+    const double small = 2.0 * ((c.attention_bias ? Nq + 2 * Nkv : 0) + 2 * H);
+    if (c.fp8_weights) return c.num_layers * (lin + 4.0 * chans + small) + 2.0 * H + (double)c.vocab_size * (H + 4.0);
+    return c.num_layers * (2.0 * lin + small) + 2.0 * H + 2.0 * (double)c.vocab_size * H;
+}
+}  // namespace
+
+// sequences -> 64-token tiles and 128-row query blocks
+// (Tile64.seq = the KV slot of the sequence: seq_ids[s], or s itself)
+void build_worklists(const std::vector<int>& lens, int Hq, std::vector<Tile64>& tiles, std::vector<QBlock>& qblocks, int64_t* Tpad_used,
+                     const int* seq_ids) {
+    tiles.clear();
+    qblocks.clear();
+    int tok0 = 0, pad0 = 0;
+    for (size_t s = 0; s < lens.size(); ++s) {
+        const int n = lens[s];
+        const int seq = seq_ids ? seq_ids[s] : (int)s;
+        for (int t = 0; t * 64 < n; ++t) tiles.push_back(Tile64{tok0 + t * 64, std::min(64, n - t * 64), pad0 + t * 64, seq, t, 0});
+        for (int h = 0; h < Hq; ++h)
+            for (int q = 0; q < n; q += flash_rows_per_block()) qblocks.push_back(QBlock{q, n, tok0, pad0, h, 0});
+        tok0 += n;
+        pad0 += (int)round_up(n, 64);
+    }
+    *Tpad_used = pad0;
+}
+
+void drop_step_graphs(DotsEngine* e) {
+    for (auto& g : e->step_graphs) {
+        hipGraphExecDestroy(g.exec);
+        hipGraphDestroy(g.graph);
+    }
+    e->step_graphs.clear();
+}
+
+// make `to` wait for everything enqueued on `from` so far
+int chain_streams(DotsEngine* e, hipStream_t from, hipStream_t to) {
+    if (from == to) return DOTS_OK;
+    CK(hipEventRecord(e->ev_xs, from));
+    CK(hipStreamWaitEvent(to, e->ev_xs, 0));
+    return DOTS_OK;
+}
+
+// The stream the next decode chunk should be replayed on: the lower CU partition while a prefetched tower is still running (the two then
+// share the chip instead of time-slicing it), the whole chip otherwise.  Hands the dependency over when the stream changes.
+int pick_decode_stream(DotsEngine* e, hipStream_t* cur) {
+    hipStream_t want = e->stream;
+    if (e->s_vit && e->pref_pending && !e->pref_deferred && hipEventQuery(e->ev_vis_ready) == hipErrorNotReady) {
+        (void)hipGetLastError();                   // "not ready" must not stay behind as the thread's last error (PyTorch / RCCL check it)
+        want = e->s_dec;
+    }
+    if (want != *cur) {
+        RET(chain_streams(e, *cur, want));
+        *cur = want;
+    }
+    return DOTS_OK;
+}
+
 // Prefill B packed prompts.  slots == nullptr: the static batch (sequence b -> slot b, every slot reset).
 // slots != nullptr: continuous batching, sequence b goes into the free slot slots[b] with its own generation cap;
 // the other slots' KV pages, contexts and outputs are not touched.
-int prefill(DotsEngine* e, const int32_t* ids, const int32_t* lens, int B, const int32_t* slots = nullptr, const int32_t* max_new = nullptr) {
+int prefill(DotsEngine* e, const int32_t* ids, const int32_t* lens, int B, const int32_t* slots, const int32_t* max_new) {
     const DotsConfig& c = e->cfg;
     hipStream_t s = e->stream;
     const int H = c.hidden_size, Hq = c.num_heads, Hkv = c.num_kv_heads, Nq = Hq * 128, Nkv = Hkv * 128, NQKV = Nq + 2 * Nkv;
@@ -1523,7 +514,7 @@ int prefill(DotsEngine* e, const int32_t* ids, const int32_t* lens, int B, const
 
 // every launch of one decode step; identical in eager mode and under graph capture
 // part: the launch plan for a stream that is CU-masked to half the chip (whole 16-row tiles: half as many workgroups per projection)
-int decode_step_launches(DotsEngine* e, int n_splits, int part = 0) {
+int decode_step_launches(DotsEngine* e, int n_splits, int part) {
     const DotsConfig& c = e->cfg;
     hipStream_t s = e->stream;
     const int H = c.hidden_size, Hq = c.num_heads, Hkv = c.num_kv_heads, Nq = Hq * 128, I = c.intermediate_size;
@@ -1581,22 +572,8 @@ int decode_step_launches(DotsEngine* e, int n_splits, int part = 0) {
 
 int splits_for_ctx(int max_ctx) { return decode_attn_splits(max_ctx); }
 
-// everything a captured step bakes in, from the engine's state as it stands (DotsEngine::StepKey)
-DotsEngine::StepKey step_key(const DotsEngine* e, int rows, int n_splits, int out_cap, int part) {
-    DotsEngine::StepKey k;
-    k.rows = rows; k.splits = n_splits; k.out_cap = out_cap; k.n_eos = e->n_eos; k.part = part;
-    k.rowp = e->stage.staged_rows() > 0;
-    k.lp = e->n_lp > 0;
-    k.rules = e->stage.rows(ROW_RULES) > 0;
-    k.guided = e->stage.rows(ROW_GUIDE) > 0;
-    k.ngram = e->stage.rows(ROW_NGRAM) > 0;
-    k.spec = e->slot_mode ? e->spec_k : 0;
-    k.draw = spec_draws(e);
-    return k;
-}
-
 // The captured decode step for (rows = e->B, splits, out_cap, e->n_eos): looked up in the cache or captured now.
-int step_graph(DotsEngine* e, int rows, int n_splits, int out_cap, hipGraphExec_t* exec, int part = 0) {
+int step_graph(DotsEngine* e, int rows, int n_splits, int out_cap, hipGraphExec_t* exec, int part) {
     const DotsEngine::StepKey key = step_key(e, rows, n_splits, out_cap, part);
     for (auto& g : e->step_graphs)
         if (g.key == key) {
@@ -1621,65 +598,12 @@ int step_graph(DotsEngine* e, int rows, int n_splits, int out_cap, hipGraphExec_
     *exec = g.exec;
     return DOTS_OK;
 }
+}  // namespace engine
 
-double decode_step_bytes(const DotsConfig& c) {
-    const double H = c.hidden_size, Nq = c.num_heads * 128.0, Nkv = c.num_kv_heads * 128.0, I = c.intermediate_size;
-    // SURVEY §8(d): every weight byte once per step.  bf16: 2 B per weight; fp8 mode: 1 B per linear weight + 4 B per output channel
-    // (scale), norms and biases stay bf16
-    const double lin = H * (Nq + 2 * Nkv) + Nq * H + 3 * H * I, chans = (Nq + 2 * Nkv) + H + 2 * I + H;
-    const double small = 2.0 * ((c.attention_bias ? Nq + 2 * Nkv : 0) + 2 * H);
-    if (c.fp8_weights) return c.num_layers * (lin + 4.0 * chans + small) + 2.0 * H + (double)c.vocab_size * (H + 4.0);
-    return c.num_layers * (2.0 * lin + small) + 2.0 * H + 2.0 * (double)c.vocab_size * H;
-}
-
-}  // namespace
-
-// scratch device buffers of the single-kernel entry points, released (after a stream sync) on scope exit
-namespace {
-struct Scratch {
-    DotsEngine* e;
-    std::vector<void*> ptrs;
-    explicit Scratch(DotsEngine* e_) : e(e_) {}
-    template <typename T>
-    hipError_t get(T** p, size_t n) {
-        hipError_t r = e->alloc(p, n);
-        if (r == hipSuccess) ptrs.push_back(*p);
-        return r;
-    }
-    ~Scratch() {
-        hipStreamSynchronize(e->stream);
-        for (void* p : ptrs) e->release(p);
-    }
-};
-
-// Decode operand of a single-kernel entry point from a ROW-MAJOR bf16 weight: bf16 fragments (fp8 == 0), or a quantised copy packed
-// as e4m3 fragments + its scales — the same kernels dots_finalize_weights runs.
-int op_weight(DotsEngine* e, Scratch& sc, const bf16_t* w, int64_t rows, int K, int Hq, int Hkv, bool qkv, int fp8, void** wd, float** scale) {
-    *scale = nullptr;
-    if (fp8) {
-        bf16_t* q = nullptr;
-        uint8_t* d = nullptr;
-        CK(sc.get(&q, (size_t)rows * K));
-        CK(sc.get(scale, (size_t)rows));
-        CK(sc.get(&d, (size_t)((rows + 15) / 16 * 16) * K));
-        CK(hipMemcpyAsync(q, w, (size_t)rows * K * 2, hipMemcpyDeviceToDevice, e->stream));
-        CK(launch_quant_rows_fp8(e->stream, q, *scale, rows, K));
-        CK(launch_pack_frag_fp8(e->stream, q, d, rows, K, qkv ? (Hq + Hkv) * 128 : 0));
-        *wd = d;
-    } else {
-        bf16_t* d = nullptr;
-        CK(sc.get(&d, (size_t)((rows + 15) / 16 * 16) * K));
-        if (qkv) CK(launch_pack_frag_qkv(e->stream, w, d, Hq, Hkv, K));
-        else CK(launch_pack_frag(e->stream, w, d, rows, K));
-        *wd = d;
-    }
-    return DOTS_OK;
-}
-}  // namespace
+using namespace engine;
 
 // ===================================================================================== C ABI
 extern "C" {
-
 const char* dots_last_error(DotsEngine* e) { return e ? e->err.c_str() : g_create_error.c_str(); }
 
 void* dots_stream(DotsEngine* e) { return e ? (void*)e->stream : nullptr; }
@@ -1743,39 +667,6 @@ void dots_destroy(DotsEngine* e) {
     for (auto& ev : e->attn_ev) hipEventDestroy(ev);
     if (e->stream) hipStreamDestroy(e->stream);
     delete e;
-}
-
-int dots_load_weight(DotsEngine* e, const char* name, const void* data, int dtype, const int64_t* shape, int ndim) {
-    if (!e || !name || !data || !shape || ndim < 1) return e ? e->fail(DOTS_E_INVALID, "null argument") : DOTS_E_INVALID;
-    if (e->finalized) return e->fail(DOTS_E_STATE, "weights already finalized");
-    CK(hipSetDevice(e->device));
-    Tensor t;
-    t.shape.assign(shape, shape + ndim);
-    const int64_t n = t.numel();
-    const size_t esz = dtype == DOTS_DTYPE_F32 ? 4 : 2;
-    if (dtype != DOTS_DTYPE_BF16 && dtype != DOTS_DTYPE_F32 && dtype != DOTS_DTYPE_F16) return e->fail(DOTS_E_INVALID, "unsupported dtype %d", dtype);
-    CK(e->alloc(&t.p, (size_t)n));
-    if (dtype == DOTS_DTYPE_BF16) {
-        CK(hipMemcpyAsync(t.p, data, n * 2, hipMemcpyHostToDevice, e->stream));
-        CK(hipStreamSynchronize(e->stream));
-    } else {
-        void* tmp = nullptr;
-        CK(hipMalloc(&tmp, n * esz));
-        CK(hipMemcpyAsync(tmp, data, n * esz, hipMemcpyHostToDevice, e->stream));
-        CK(launch_convert_to_bf16(e->stream, tmp, dtype, t.p, n));
-        CK(hipStreamSynchronize(e->stream));
-        hipFree(tmp);
-    }
-    drop(e, name);
-    e->raw[name] = t;
-    return DOTS_OK;
-}
-
-int dots_finalize_weights(DotsEngine* e) {
-    if (!e) return DOTS_E_INVALID;
-    if (e->finalized) return DOTS_OK;
-    CK(hipSetDevice(e->device));
-    return finalize_weights(e);
 }
 
 int dots_vit_forward(DotsEngine* e, const float* pixel_values, int on_device, int64_t total_patches,
@@ -1944,346 +835,6 @@ int dots_generate(DotsEngine* e, const int32_t* input_ids, const int32_t* prompt
     return DOTS_OK;
 }
 
-// ---------------------------------------------------------------------------------- continuous batching
-int dots_set_eos(DotsEngine* e, const int32_t* eos_ids, int n_eos) {
-    if (!e) return DOTS_E_INVALID;
-    if (n_eos < 0 || n_eos > 16 || (n_eos && !eos_ids)) return e->fail(DOTS_E_INVALID, "n_eos must be in [0,16]");
-    CK(hipSetDevice(e->device));
-    if (n_eos) CK(hipMemcpyAsync(e->eos_ids, eos_ids, n_eos * 4, hipMemcpyHostToDevice, e->stream));
-    CK(hipStreamSynchronize(e->stream));
-    e->n_eos = n_eos;
-    std::copy(eos_ids, eos_ids + n_eos, e->h_eos);
-    return DOTS_OK;
-}
-
-int dots_slots_prefill(DotsEngine* e, const int32_t* slots, int n, const int32_t* input_ids, const int32_t* prompt_lens,
-                       const int32_t* max_new_tokens) {
-    if (!e) return DOTS_E_INVALID;
-    if (!e->finalized) return e->fail(DOTS_E_STATE, "weights not finalized");
-    if (!slots || !input_ids || !prompt_lens || !max_new_tokens) return e->fail(DOTS_E_INVALID, "null argument");
-    CK(hipSetDevice(e->device));
-    return prefill(e, input_ids, prompt_lens, n, slots, max_new_tokens);
-}
-
-// Parallel sampling: n free slots become copies of the freshly prefilled sequence in src_slot.  Everything is validated and
-// counted before anything changes; the children then share the source's full prompt pages (reference counts), get a copy of its tail page
-// and select their own first token from the source's last-position logits.
-int dots_slots_fork(DotsEngine* e, int src_slot, const int32_t* dst_slots, int n) {
-    if (!e) return DOTS_E_INVALID;
-    if (!e->finalized) return e->fail(DOTS_E_STATE, "weights not finalized");
-    if (!dst_slots || n < 1 || n >= DOTS_MAX_BATCH) return e->fail(DOTS_E_INVALID, "dots_slots_fork: n must be in [1, %d) and dst_slots given", DOTS_MAX_BATCH);
-    const DotsConfig& c = e->cfg;
-    const int mb = c.max_batch, V = c.vocab_size;
-    if (src_slot < 0 || src_slot >= mb) return e->fail(DOTS_E_INVALID, "source slot %d out of range [0, %d)", src_slot, mb);
-    const auto fresh = std::find(e->fresh_slots.begin(), e->fresh_slots.end(), src_slot);
-    if (!e->slot_mode || !e->slot_active[src_slot] || fresh == e->fresh_slots.end())
-        return e->fail(DOTS_E_STATE, "slot %d cannot be forked: only a sequence of the most recent dots_slots_prefill, before any decode step", src_slot);
-    const int usable = e->spec_k ? mb / (e->spec_k + 1) : mb;
-    for (int i = 0; i < n; ++i) {
-        const int d = dst_slots[i];
-        if (d < 0 || d >= mb) return e->fail(DOTS_E_INVALID, "slot %d out of range [0, %d)", d, mb);
-        if (d >= usable)
-            return e->fail(DOTS_E_CAPACITY, "slot %d is not usable while speculating: with %d drafts only slots [0, %d) are", d, e->spec_k, usable);
-        if (d == src_slot) return e->fail(DOTS_E_INVALID, "slot %d is the source of the fork", d);
-        if (e->slot_active[d]) return e->fail(DOTS_E_STATE, "slot %d is occupied", d);
-        for (int a = 0; a < i; ++a)
-            if (dst_slots[a] == d) return e->fail(DOTS_E_INVALID, "slot %d listed twice", d);
-    }
-    // ---- page arithmetic: the children name the source's floor(L / 64) full prompt pages and own the rest of the admission reserve
-    const int L = e->slot_prompt[src_slot], max_new = e->slot_limit[src_slot] - L;
-    const int shared = L / 64, own = (admit_tokens(e, L, max_new) + 63) / 64 - shared;          // own >= 1: the reserve is at least L + 1 tokens
-    const auto& src_pages = e->slot_pages[src_slot];
-    if ((int)src_pages.size() < shared + (L % 64 ? 1 : 0)) return e->fail(DOTS_E_STATE, "slot %d does not hold its prompt pages", src_slot);
-    if (shared + own > e->max_pages || (int64_t)n * own > (int64_t)e->free_pages.size())
-        return e->fail(DOTS_E_CAPACITY, "KV pool exhausted: %d forked sequences need %d pages of 64 tokens each, %d of %d are free", n, own,
-                       (int)e->free_pages.size(), e->n_pool_pages);
-    CK(hipSetDevice(e->device));
-    hipStream_t s = e->stream;
-    // ---- from here on the call changes state; a failed launch gives the children's pages back (the slots are not marked occupied yet)
-    struct ForkGuard {
-        DotsEngine* e; const int32_t* dst; int n; bool armed = true;
-        ~ForkGuard() {
-            if (!armed) return;
-            for (int i = 0; i < n; ++i) { release_pages(e, dst[i]); (void)upload_table_row(e, dst[i]); }
-        }
-    } guard{e, dst_slots, n};
-    int32_t stage[3 * DOTS_MAX_BATCH] = {0}, sel_new[DOTS_MAX_BATCH] = {0};
-    int rows = 0;
-    for (int i = 0; i < n; ++i) {
-        const int d = dst_slots[i];
-        auto& mine = e->slot_pages[d];
-        for (int p = 0; p < shared; ++p) {                 // one more holder of a page nobody writes any more: every row appends at positions >= L
-            mine.push_back(src_pages[p]);
-            e->page_refs[src_pages[p]] += 1;
-            e->hp_table[(size_t)d * e->max_pages + p] = src_pages[p];
-        }
-        bool changed = false;
-        grow_pages(e, d, (shared + own) * 64, &changed);   // cannot fall short: counted above
-        CK(upload_table_row(e, d));
-        stage[i] = d;
-        stage[DOTS_MAX_BATCH + i] = mine[shared];
-        sel_new[d] = 1;
-        rows = std::max(rows, d + 1);
-    }
-    stage[2 * DOTS_MAX_BATCH] = L - 1;
-    CK(hipMemcpyAsync(e->fk_dev, stage, sizeof(stage), hipMemcpyHostToDevice, s));
-    const int32_t *fk_dst = e->fk_dev, *fk_pages = e->fk_dev + DOTS_MAX_BATCH, *fk_last = e->fk_dev + 2 * DOTS_MAX_BATCH;
-    // the tail page: behind the prefill's page writers on the same stream; its source is written by nobody until the source's first step
-    if (L % 64) {
-        const size_t page_bytes = (size_t)c.num_kv_heads * 2 * 8192 * (e->kv8 ? 1 : 2);
-        CK(launch_kv_fork_pages(s, e->pool, e->pool_layer_elems * 2, page_bytes, c.num_layers, src_pages[shared], fk_pages, n));
-    }
-    // ---- per-row decode state, as the prefill sets it
-    const int32_t cap = max_new;
-    for (int i = 0; i < n; ++i) {
-        const int d = dst_slots[i];
-        CK(hipMemcpyAsync(e->ctx_len + d, &L, 4, hipMemcpyHostToDevice, s));
-        CK(hipMemcpyAsync(e->d_max_len + d, &cap, 4, hipMemcpyHostToDevice, s));
-        CK(hipMemsetAsync(e->out_lens + d, 0, 4, s));
-        CK(hipMemsetAsync(e->finished + d, 0, 4, s));
-        if (e->sp_ndraft) {
-            CK(hipMemsetAsync(e->sp_ndraft + d, 0, 4, s));
-            CK(hipMemsetAsync(e->sp_stats + (size_t)d * 3, 0, 3 * sizeof(unsigned long long), s));
-        }
-        RET(clear_lp_row(e, d));
-        // the source's last-position logits row (rows of d_logits are slots; nothing has run over them since the prefill)
-        CK(hipMemcpyAsync(e->d_logits + (size_t)d * V, e->d_logits + (size_t)src_slot * V, (size_t)V * 4, hipMemcpyDeviceToDevice, s));
-    }
-    CK(hipMemcpyAsync(e->d_sel_new, sel_new, sizeof(sel_new), hipMemcpyHostToDevice, s));
-    if (e->pen_cnt) {
-        // prompt-presence bits and zeroed counts of every child from the source's packed prompt, still in p_src: one sequence per launch,
-        // so that each starts at the source's first token
-        const int b = (int)(fresh - e->fresh_slots.begin());
-        const int32_t* src0 = e->p_src + (b ? e->hp_last[b - 1] + 1 : 0);
-        for (int i = 0; i < n; ++i) CK(launch_pen_prompt(s, src0, fk_last, fk_dst + i, 1, c.image_token_id, V, e->pen_cnt, e->pen_seen));
-    }
-    if (e->stage.rows(ROW_GUIDE) > 0) CK(launch_guide_reset_rows(s, e->d_guides, fk_dst, n));
-    if (e->stage.has(src_slot, ROW_STOP)) {
-        // the children inherit the source's stop strings (automaton and min_tokens) at the root with no hit: one launch writes all their entries
-        for (int i = 0; i < n; ++i) RET(hold_row_stop(e, dst_slots[i], e->row_stop[src_slot] - 1, e->row_stop_min[src_slot]));
-        CK(launch_stop_fork_rows(s, e->d_stop, src_slot, fk_dst, n));
-    } else if (e->stage.rows(ROW_STOP) > 0)
-        CK(launch_stop_reset_rows(s, e->d_stop, fk_dst, n));
-    CK(hipStreamSynchronize(s));                           // L, cap and the staged arrays are stack variables
-    // ---- the children's first tokens: the selection stage over a mask of the children only
-    e->B_sel = rows;
-    e->sel_now = e->d_sel_new;
-    RET(select_tokens(e, 0));
-    for (int i = 0; i < n; ++i) {
-        const int d = dst_slots[i];
-        e->slot_active[d] = 1;
-        e->slot_limit[d] = L + max_new;
-        e->slot_prompt[d] = L;
-        e->slot_ctx_ub[d] = L;
-        e->slot_done[d] = 0;
-    }
-    e->sel_dirty = true;
-    guard.armed = false;
-    return DOTS_OK;
-}
-
-// Enter slot mode with every slot free and every KV page in the pool (whatever a static batch or an abandoned serving loop left behind).
-int dots_slots_reset(DotsEngine* e) {
-    if (!e) return DOTS_E_INVALID;
-    if (!e->finalized) return e->fail(DOTS_E_STATE, "weights not finalized");
-    CK(hipSetDevice(e->device));
-    hipStream_t s = e->stream;
-    if (e->pref_pending) {                               // a prefetched tower nobody took (an abandoned serving loop): drop it
-        if (!e->pref_deferred) CK(hipStreamWaitEvent(s, e->ev_vis_ready, 0));
-        e->pref_pending = e->pref_deferred = false;
-    }
-    for (int b = 0; b < (int)e->slot_pages.size(); ++b) release_pages(e, b);
-    e->fresh_slots.clear();
-    CK(hipMemcpyAsync(e->block_table, e->hp_table.data(), e->hp_table.size() * 4, hipMemcpyHostToDevice, s));
-    std::fill(e->slot_active, e->slot_active + DOTS_MAX_BATCH, 0);
-    CK(hipMemsetAsync(e->ctx_len, 0, e->cfg.max_batch * 4, s));
-    CK(hipMemsetAsync(e->out_lens, 0, e->cfg.max_batch * 4, s));
-    CK(hipMemsetAsync(e->finished, 0, e->cfg.max_batch * 4, s));
-    // no row carries any feature: the features' row tables (in RowFeature order; the own flags stand for the parameters), then the host record
-    const struct { void* table; size_t row_bytes; } feature_tables[ROW_FEATURES] = {
-        {e->d_row_own, 4}, {e->d_rules, sizeof(RowRules)}, {e->d_guides, sizeof(RowGuide)}, {e->d_ngram, sizeof(RowNgram)}, {e->d_stop, sizeof(RowStop)}};
-    for (const auto& t : feature_tables)
-        if (t.table) CK(hipMemsetAsync(t.table, 0, DOTS_MAX_BATCH * t.row_bytes, s));
-    e->stage.reset();
-    std::fill(e->row_guide, e->row_guide + DOTS_MAX_BATCH, 0);
-    for (auto& g : e->guides) g.rows = 0;
-    std::fill(e->row_stop, e->row_stop + DOTS_MAX_BATCH, 0);
-    std::fill(e->row_stop_min, e->row_stop_min + DOTS_MAX_BATCH, 0);
-    for (auto& a : e->stops) a.rows = 0;
-    if (e->d_row_lp) CK(hipMemsetAsync(e->d_row_lp, 0xFF, DOTS_MAX_BATCH * 4, s));
-    std::fill(e->row_lp, e->row_lp + DOTS_MAX_BATCH, -1);
-    e->n_lp = 0;
-    if (e->sp_ndraft) CK(hipMemsetAsync(e->sp_ndraft, 0, DOTS_MAX_BATCH * 4, s));
-    if (e->sp_cls) CK(hipMemsetAsync(e->sp_cls, 0, DOTS_MAX_BATCH * 4, s));         // SPEC_ROW_ARGMAX: no row carries anything
-    CK(hipStreamSynchronize(s));
-    e->slot_mode = true;
-    e->sel_dirty = true;
-    e->B = 0;
-    return DOTS_OK;
-}
-
-int dots_slots_decode(DotsEngine* e, int n_steps) {
-    if (!e) return DOTS_E_INVALID;
-    if (!e->slot_mode) return e->fail(DOTS_E_STATE, "no slot has been prefilled");
-    if (n_steps < 1) return e->fail(DOTS_E_INVALID, "n_steps must be >= 1");
-    CK(hipSetDevice(e->device));
-    hipStream_t s = e->stream;
-    int rows = 0;
-    for (int b = 0; b < e->cfg.max_batch; ++b)
-        if (e->slot_active[b]) rows = b + 1;
-    if (!rows) return e->fail(DOTS_E_STATE, "every slot is free");
-    e->fresh_slots.clear();                                 // the step overwrites the logits a fork selects from (dots_slots_fork)
-    if (e->sel_dirty) {
-        int32_t sel[DOTS_MAX_BATCH];
-        for (int b = 0; b < DOTS_MAX_BATCH; ++b) sel[b] = e->slot_active[b];
-        CK(hipMemcpyAsync(e->d_sel, sel, DOTS_MAX_BATCH * 4, hipMemcpyHostToDevice, s));
-        e->sel_dirty = false;
-    }
-    // ---- paged KV: every running sequence gets the pages the next n_steps positions need, now.  Pool dry: the sequence keeps what it
-    // has and its generation cap is lowered to what its pages hold — it finishes there with "length", like HF generate at the
-    // context capacity (an admission policy that leaves head-room makes this rare: dots_ocr_amd/scheduler.py).
-    // A speculating step may advance a row by spec_k + 1 positions and writes KV that far ahead: pages and the host's bound on the
-    // context count n_steps x (k + 1) (dots_slots_poll brings the bound back to the row's true context)
-    n_steps *= e->spec_k + 1;
-    for (int b = 0; b < rows; ++b) {
-        if (!e->slot_active[b] || e->slot_done[b]) continue;
-        // A step at context c writes KV position c and brings the sequence to c + 2 tokens, so n_steps more steps need positions
-        // [0, ctx + n_steps), and a sequence limited to slot_limit tokens never writes beyond position slot_limit - 2.
-        int want = std::min(e->slot_ctx_ub[b] + n_steps, e->slot_limit[b] - 1);
-        bool changed = false;
-        const int have = grow_pages(e, b, want, &changed);
-        if (changed) CK(upload_table_row(e, b));
-        if (have < want && e->spec_k) {
-            // before a speculating row is capped, its bound becomes its true context: steps that accepted fewer than k drafts left it too high
-            int32_t ctx = 0;
-            CK(hipMemcpyAsync(&ctx, e->ctx_len + b, 4, hipMemcpyDeviceToHost, s));
-            CK(hipStreamSynchronize(s));
-            e->slot_ctx_ub[b] = std::min(e->slot_ctx_ub[b], (int)ctx);
-            want = std::min(e->slot_ctx_ub[b] + n_steps, e->slot_limit[b] - 1);
-        }
-        if (have < want) {
-            // Positions [0, have) exist: the last step the row may take is the one at context have - 1, which leaves it with have + 1
-            // tokens.  commit_token finishes a row when a step brings it to its cap — so a row that already sits AT context `have`
-            // (the pool ran dry exactly on its page boundary) must be stopped here: its next step would write position
-            // `have` through a block-table entry it does not own (the scratch page every idle row writes) and read it back.
-            e->slot_limit[b] = have + 1;
-            const int32_t cap = have + 1 - e->slot_prompt[b];               // generated tokens; >= the tokens generated so far
-            static const int32_t one = 1;
-            CK(hipMemcpyAsync(e->d_max_len + b, &cap, 4, hipMemcpyHostToDevice, s));
-            if (have <= e->slot_ctx_ub[b]) CK(hipMemcpyAsync(e->finished + b, &one, 4, hipMemcpyHostToDevice, s));
-            CK(hipStreamSynchronize(s));                                     // `cap` is a stack variable
-            e->kv_capped += 1;
-        }
-        e->slot_ctx_ub[b] = std::min(e->slot_ctx_ub[b] + n_steps, e->slot_limit[b] - 1);
-    }
-    n_steps /= e->spec_k + 1;
-    const int n_splits = splits_for_ctx(e->cfg.max_seq_len);
-    e->B = rows;
-    static const bool use_graph = getenv("DOTS_OCR_NO_GRAPH") == nullptr;
-    // beside a prefetched vision tower (the next admission's: dots_vit_prefetch) the chunk is replayed on the decode partition, with the
-    // half-chip launch plan when the rows allow it — exactly as dots_generate does
-    hipStream_t cur = s;
-    if (use_graph) { int r0 = pick_decode_stream(e, &cur); if (r0 != DOTS_OK) { e->B = 0; return r0; } }
-    const int part = cur != s ? 1 : 0;
-    hipGraphExec_t exec = nullptr;
-    if (use_graph) {
-        int r = step_graph(e, rows, n_splits, 0, &exec, part);
-        if (r != DOTS_OK) { e->B = 0; return r; }
-    }
-    int r = DOTS_OK;
-    for (int i = 0; i < n_steps && r == DOTS_OK; ++i) {
-        if (exec) { if (hipGraphLaunch(exec, cur) != hipSuccess) r = e->fail(DOTS_E_HIP, "hipGraphLaunch failed"); }
-        else r = decode_step_launches(e, n_splits);
-    }
-    if (r == DOTS_OK && e->ev_dec_end && hipEventRecord(e->ev_dec_end, cur) == hipSuccess) ++e->dec_end_seq;      // pick_tower_tail
-    if (r == DOTS_OK) r = chain_streams(e, cur, s);
-    e->B = 0;
-    e->stats.decode_steps += n_steps;
-    return r;
-}
-
-int dots_slots_poll(DotsEngine* e, int32_t* finished, int32_t* out_lens) {
-    if (!e || !finished || !out_lens) return e ? e->fail(DOTS_E_INVALID, "null argument") : DOTS_E_INVALID;
-    CK(hipSetDevice(e->device));
-    const int mb = e->cfg.max_batch;
-    CK(hipMemcpyAsync(finished, e->finished, mb * 4, hipMemcpyDeviceToHost, e->stream));
-    CK(hipMemcpyAsync(out_lens, e->out_lens, mb * 4, hipMemcpyDeviceToHost, e->stream));
-    CK(hipStreamSynchronize(e->stream));
-    for (int b = 0; b < mb; ++b) {
-        if (!e->slot_mode || !e->slot_active[b]) { finished[b] = -1; out_lens[b] = 0; }      // -1: free slot
-        else {
-            if (finished[b]) e->slot_done[b] = 1;                                            // takes no more pages
-            // every issued step has run: the context is prompt + generated - 1 exactly.  A speculating step advances a row by 1 .. k + 1
-            // positions, so dots_slots_decode counts k + 1 per step; without this the bound (and the pages taken ahead) would run away
-            if (e->spec_k) e->slot_ctx_ub[b] = std::min(e->slot_ctx_ub[b], e->slot_prompt[b] + out_lens[b] - 1);
-        }
-    }
-    return DOTS_OK;
-}
-
-int dots_slot_read(DotsEngine* e, int slot, int32_t* out_ids, int capacity, int32_t* n_out) {
-    if (!e || !out_ids || !n_out || capacity < 0) return e ? e->fail(DOTS_E_INVALID, "bad slot_read arguments") : DOTS_E_INVALID;
-    if (!e->slot_mode || slot < 0 || slot >= e->cfg.max_batch || !e->slot_active[slot]) return e->fail(DOTS_E_STATE, "slot %d is not occupied", slot);
-    CK(hipSetDevice(e->device));
-    int32_t n = 0;
-    CK(hipMemcpyAsync(&n, e->out_lens + slot, 4, hipMemcpyDeviceToHost, e->stream));
-    CK(hipStreamSynchronize(e->stream));
-    *n_out = n;
-    const int take = std::min<int>(n, capacity);
-    if (take > 0) {
-        CK(hipMemcpyAsync(out_ids, e->out_ids + (size_t)slot * e->cfg.max_seq_len, (size_t)take * 4, hipMemcpyDeviceToHost, e->stream));
-        CK(hipStreamSynchronize(e->stream));
-    }
-    return DOTS_OK;
-}
-
-int dots_slot_release(DotsEngine* e, int slot) {
-    if (!e) return DOTS_E_INVALID;
-    if (!e->slot_mode || slot < 0 || slot >= e->cfg.max_batch || !e->slot_active[slot]) return e->fail(DOTS_E_STATE, "slot %d is not occupied", slot);
-    CK(hipSetDevice(e->device));
-    for (int f = 0; f < ROW_FEATURES; ++f) RET(clear_row_feature(e, slot, (RowFeature)f));
-    RET(set_row_lp(e, slot, -1));
-    e->slot_active[slot] = 0;
-    e->sel_dirty = true;
-    CK(hipMemsetAsync(e->ctx_len + slot, 0, 4, e->stream));          // an idle row attends over one key only ...
-    release_pages(e, slot);                                          // ... of the scratch page: its own pages go back to the pool
-    CK(upload_table_row(e, slot));
-    return DOTS_OK;
-}
-
-int dots_kv_pool_info(DotsEngine* e, int32_t* total_pages, int32_t* free_pages) {
-    if (!e || !total_pages || !free_pages) return DOTS_E_INVALID;
-    *total_pages = e->n_pool_pages;
-    *free_pages = (int32_t)e->free_pages.size();
-    return DOTS_OK;
-}
-
-int dots_set_kv_scales(DotsEngine* e, const float* scales_host) {
-    if (!e || !scales_host) return e ? e->fail(DOTS_E_INVALID, "null argument") : DOTS_E_INVALID;
-    const DotsConfig& c = e->cfg;
-    const size_t n = (size_t)c.num_layers * c.num_kv_heads * 2;
-    for (size_t i = 0; i < n; ++i)
-        if (!std::isfinite(scales_host[i]) || !(scales_host[i] > 0.f))
-            return e->fail(DOTS_E_INVALID, "kv scale %zu (layer %zu, kv head %zu, %s) is %g: must be finite and > 0", i, i / (2 * c.num_kv_heads),
-                           (i / 2) % c.num_kv_heads, i % 2 ? "V" : "K", (double)scales_host[i]);
-    // a cached token was quantised with the scales of its time: they are fixed while any sequence holds pages
-    if ((int)e->free_pages.size() != e->n_pool_pages)
-        return e->fail(DOTS_E_STATE, "KV scales cannot change while sequences hold KV pages (%d of %d in use): release them first (dots_slots_reset)",
-                       e->n_pool_pages - (int)e->free_pages.size(), e->n_pool_pages);
-    CK(hipSetDevice(e->device));
-    CK(hipMemcpyAsync(e->kv_scales, scales_host, n * 4, hipMemcpyHostToDevice, e->stream));
-    CK(hipStreamSynchronize(e->stream));
-    return DOTS_OK;
-}
-
-int dots_slot_capacity(DotsEngine* e, int slot, int32_t* pages_owned, int32_t* token_limit) {
-    if (!e || !pages_owned || !token_limit) return DOTS_E_INVALID;
-    if (!e->slot_mode || slot < 0 || slot >= e->cfg.max_batch || !e->slot_active[slot]) return e->fail(DOTS_E_STATE, "slot %d is not occupied", slot);
-    *pages_owned = (int32_t)e->slot_pages[slot].size();
-    *token_limit = e->slot_limit[slot];
-    return DOTS_OK;
-}
-
 int dots_get_stats(DotsEngine* e, DotsStats* out) {
     if (!e || !out) return DOTS_E_INVALID;
     CK(hipSetDevice(e->device));
@@ -2359,365 +910,6 @@ int dots_preprocess_image(DotsEngine* e, const uint8_t* rgb, int on_device, int 
     }
     CK(launch_normalize_patchify(s, src, out, rw, rh / P, rw / P, P, m, rescale, mean3, std3));
     CK(hipStreamSynchronize(s));          // the host tables / image buffers may be reused by the caller
-    return DOTS_OK;
-}
-
-int dots_set_sampling(DotsEngine* e, float temperature, float top_p, uint64_t seed) {
-    if (!e) return DOTS_E_INVALID;
-    if (!(temperature >= 0.f) || !(top_p > 0.f)) return e->fail(DOTS_E_INVALID, "temperature must be >= 0 and top_p in (0, 1]");
-    e->temperature = temperature;
-    e->top_p = top_p > 1.f ? 1.f : top_p;
-    e->seed = seed;
-    drop_step_graphs(e);                                   // the captured decode steps bake these values in
-    return DOTS_OK;
-}
-
-int dots_set_row_sampling(DotsEngine* e, int row, const DotsSamplingParams* p) {
-    if (!e) return DOTS_E_INVALID;
-    if (row < 0 || row >= e->cfg.max_batch) return e->fail(DOTS_E_INVALID, "row %d out of range [0, %d)", row, e->cfg.max_batch);
-    CK(hipSetDevice(e->device));
-    if (!p) return clear_row_feature(e, row, ROW_PARAMS);
-    RowParams rp;
-    RET(check_row_params(e, *p, &rp));
-    RET(ensure_row_table(e));
-    if (rp.repetition_penalty != 1.f || rp.frequency_penalty != 0.f || rp.presence_penalty != 0.f) RET(ensure_pen_state(e));
-    CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, rp, 1));
-    e->row_pen[row] = rp.repetition_penalty != 1.f || rp.frequency_penalty != 0.f || rp.presence_penalty != 0.f;
-    e->row_sampled[row] = rp.temperature > 0.f;
-    return enter_row_stage(e, row, ROW_PARAMS);
-}
-
-int dots_set_row_logit_rules(DotsEngine* e, int row, const DotsLogitRules* r) {
-    if (!e) return DOTS_E_INVALID;
-    if (row < 0 || row >= e->cfg.max_batch) return e->fail(DOTS_E_INVALID, "row %d out of range [0, %d)", row, e->cfg.max_batch);
-    CK(hipSetDevice(e->device));
-    if (!r) return clear_row_feature(e, row, ROW_RULES);
-    RowRules rr;
-    RET(check_logit_rules(e, *r, e->cfg.vocab_size, e->h_eos, e->n_eos, &rr));
-    RET(ensure_row_table(e));
-    RET(ensure_rules_state(e));
-    const int V = e->cfg.vocab_size, n_allowed = r->allowed_ids ? r->n_allowed : 0;
-    if (rr.flags & RULE_IMG) {
-        CK(hipEventSynchronize(e->rule_ev));               // the previous call's upload has left the pinned buffer (an unrecorded event: at once)
-        int32_t* h = e->rule_stage_host;
-        if (n_allowed) std::copy(r->allowed_ids, r->allowed_ids + n_allowed, h);
-        if (r->n_bias) {
-            std::copy(r->bias_ids, r->bias_ids + r->n_bias, h + V);
-            std::memcpy(h + V + DOTS_MAX_LOGIT_BIAS, r->bias_values, (size_t)r->n_bias * 4);
-        }
-        if (n_allowed) CK(hipMemcpyAsync(e->rule_stage, h, (size_t)n_allowed * 4, hipMemcpyHostToDevice, e->stream));
-        // ids and values in one copy: the whole [2][DOTS_MAX_LOGIT_BIAS] block, of which the kernel reads the first n_bias of each half
-        if (r->n_bias) CK(hipMemcpyAsync(e->rule_stage + V, h + V, (size_t)2 * DOTS_MAX_LOGIT_BIAS * 4, hipMemcpyHostToDevice, e->stream));
-        CK(hipEventRecord(e->rule_ev, e->stream));
-    }
-    CK(launch_set_row_rules(e->stream, e->d_rules, e->rule_img, row, V, rr, e->rule_stage, n_allowed, e->rule_stage + V,
-                            reinterpret_cast<const float*>(e->rule_stage + V + DOTS_MAX_LOGIT_BIAS), r->n_bias));
-    // not enter_row_stage(): the entry is rewritten whenever the row has no parameters of its own, staged already or not (known wart)
-    if (!e->stage.has(row, ROW_PARAMS)) CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, engine_row_params(e), 1));
-    e->stage.attach(row, ROW_RULES);
-    return sync_spec_class(e, row);
-}
-
-int dots_set_token_bytes(DotsEngine* e, const int32_t* offsets, const uint8_t* bytes) {
-    if (!e || !offsets) return e ? e->fail(DOTS_E_INVALID, "null argument") : DOTS_E_INVALID;
-    const int V = e->cfg.vocab_size;
-    if (offsets[0] != 0) return e->fail(DOTS_E_INVALID, "token bytes: offsets[0] must be 0");
-    for (int t = 0; t < V; ++t)
-        if (offsets[t + 1] < offsets[t]) return e->fail(DOTS_E_INVALID, "token bytes: offsets must not decrease (token %d)", t);
-    const size_t n = (size_t)offsets[V];
-    if (n && !bytes) return e->fail(DOTS_E_INVALID, "null argument");
-    if (e->stage.rows(ROW_GUIDE) > 0) return e->fail(DOTS_E_STATE, "token bytes cannot change while %d row(s) hold a guide", e->stage.rows(ROW_GUIDE));
-    if (e->stage.rows(ROW_STOP) > 0) return e->fail(DOTS_E_STATE, "token bytes cannot change while %d row(s) hold stop strings", e->stage.rows(ROW_STOP));
-    CK(hipSetDevice(e->device));
-    CK(hipStreamSynchronize(e->stream));                   // nothing in flight reads the previous image
-    if (e->tok_off) { e->release(e->tok_off); e->tok_off = nullptr; }
-    if (e->tok_bytes) { e->release(e->tok_bytes); e->tok_bytes = nullptr; }
-    CK(e->alloc(&e->tok_bytes, n + 16));
-    if (n) CK(hipMemcpyAsync(e->tok_bytes, bytes, n, hipMemcpyHostToDevice, e->stream));
-    int32_t* off = nullptr;
-    CK(e->alloc(&off, (size_t)V + 1));
-    CK(hipMemcpyAsync(off, offsets, ((size_t)V + 1) * 4, hipMemcpyHostToDevice, e->stream));
-    CK(hipStreamSynchronize(e->stream));                   // the caller's arrays are free again
-    e->tok_off = off;
-    drop_step_graphs(e);                                   // a captured step holds the previous pointers
-    return DOTS_OK;
-}
-
-int dots_guide_create(DotsEngine* e, const uint16_t* table, int n_states, const uint8_t* accepting, int start, int32_t* id_out) {
-    if (!e || !table || !accepting || !id_out) return e ? e->fail(DOTS_E_INVALID, "null argument") : DOTS_E_INVALID;
-    if (n_states < 1 || n_states > DOTS_MAX_GUIDE_STATES) return e->fail(DOTS_E_INVALID, "guide: n_states must be in [1, %d]", DOTS_MAX_GUIDE_STATES);
-    if (start < 0 || start >= n_states) return e->fail(DOTS_E_INVALID, "guide: start state %d outside [0, %d)", start, n_states);
-    for (size_t i = 0; i < (size_t)n_states * 256; ++i)
-        if (table[i] != GUIDE_DEAD && table[i] >= n_states)
-            return e->fail(DOTS_E_INVALID, "guide: state %zu, byte %zu leads to state %d outside [0, %d)", i / 256, i % 256, (int)table[i], n_states);
-    CK(hipSetDevice(e->device));
-    DotsEngine::Guide g;
-    g.n_states = n_states;
-    g.start = start;
-    CK(e->alloc(&g.table, (size_t)n_states * 256));
-    CK(hipMemcpyAsync(g.table, table, (size_t)n_states * 512, hipMemcpyHostToDevice, e->stream));
-    CK(e->alloc(&g.accepting, (size_t)n_states));
-    CK(hipMemcpyAsync(g.accepting, accepting, (size_t)n_states, hipMemcpyHostToDevice, e->stream));
-    CK(hipStreamSynchronize(e->stream));                   // the caller's arrays are free again
-    size_t id = 0;
-    while (id < e->guides.size() && e->guides[id].table) ++id;          // a destroyed guide's id is reused
-    if (id == e->guides.size()) e->guides.push_back(g); else e->guides[id] = g;
-    *id_out = (int32_t)id;
-    return DOTS_OK;
-}
-
-int dots_guide_destroy(DotsEngine* e, int32_t id) {
-    if (!e) return DOTS_E_INVALID;
-    if (id < 0 || id >= (int)e->guides.size() || !e->guides[id].table) return e->fail(DOTS_E_INVALID, "no guide %d", id);
-    if (e->guides[id].rows > 0) return e->fail(DOTS_E_STATE, "guide %d is held by %d row(s): clear them first (dots_set_row_guide(row, -1))", id, e->guides[id].rows);
-    CK(hipSetDevice(e->device));
-    CK(hipStreamSynchronize(e->stream));                   // steps in flight may still walk its table
-    e->release(e->guides[id].table);
-    e->release(e->guides[id].accepting);
-    e->guides[id] = DotsEngine::Guide{};
-    return DOTS_OK;
-}
-
-int dots_set_row_guide(DotsEngine* e, int row, int32_t id) {
-    if (!e) return DOTS_E_INVALID;
-    if (row < 0 || row >= e->cfg.max_batch) return e->fail(DOTS_E_INVALID, "row %d out of range [0, %d)", row, e->cfg.max_batch);
-    CK(hipSetDevice(e->device));
-    if (id < 0) return clear_row_feature(e, row, ROW_GUIDE);
-    if (id >= (int)e->guides.size() || !e->guides[id].table) return e->fail(DOTS_E_INVALID, "no guide %d", id);
-    if (!e->tok_off) return e->fail(DOTS_E_STATE, "the token bytes are not set (dots_set_token_bytes): a guide cannot judge any token");
-    RET(ensure_row_table(e));
-    RET(ensure_guide_state(e));
-    const DotsEngine::Guide& g = e->guides[id];
-    CK(launch_set_row_guide(e->stream, e->d_guides, row, RowGuide{g.table, g.accepting, g.n_states, g.start, g.start, 0}));
-    if (e->stage.has(row, ROW_GUIDE)) e->guides[e->row_guide[row] - 1].rows -= 1;
-    RET(enter_row_stage(e, row, ROW_GUIDE));
-    e->row_guide[row] = id + 1;
-    e->guides[id].rows += 1;
-    return DOTS_OK;
-}
-
-int dots_set_row_ngram(DotsEngine* e, int row, const DotsNgramRule* r) {
-    if (!e) return DOTS_E_INVALID;
-    if (row < 0 || row >= e->cfg.max_batch) return e->fail(DOTS_E_INVALID, "row %d out of range [0, %d)", row, e->cfg.max_batch);
-    CK(hipSetDevice(e->device));
-    if (!r) return clear_row_feature(e, row, ROW_NGRAM);
-    RowNgram rn;
-    RET(check_ngram_rule(e, *r, e->cfg.vocab_size, e->cfg.max_seq_len, &rn));
-    RET(ensure_row_table(e));
-    RET(ensure_ngram_state(e));
-    CK(launch_set_row_ngram(e->stream, e->d_ngram, row, rn));
-    return enter_row_stage(e, row, ROW_NGRAM);
-}
-
-// ---------------------------------------------------------------------------------- stop strings
-int dots_stop_create(DotsEngine* e, const uint16_t* table, int n_states, const uint16_t* match_len, const uint8_t* match_id, int32_t* handle_out) {
-    if (!e || !table || !match_len || !match_id || !handle_out) return e ? e->fail(DOTS_E_INVALID, "null argument") : DOTS_E_INVALID;
-    if (!e->tok_off) return e->fail(DOTS_E_STATE, "the token bytes are not set (dots_set_token_bytes): a stop string cannot be matched");
-    if (n_states < 1 || n_states > STOP_MAX_STATES) return e->fail(DOTS_E_INVALID, "stop strings: n_states must be in [1, %d]", STOP_MAX_STATES);
-    for (size_t i = 0; i < (size_t)n_states * 256; ++i)
-        if (table[i] >= n_states)
-            return e->fail(DOTS_E_INVALID, "stop strings: state %zu, byte %zu leads to state %d outside [0, %d)", i / 256, i % 256, (int)table[i], n_states);
-    for (int i = 0; i < n_states; ++i)
-        if (match_len[i] > DOTS_MAX_STOP_BYTES || (match_len[i] && match_id[i] >= DOTS_MAX_STOP_STRINGS))
-            return e->fail(DOTS_E_INVALID, "stop strings: state %d matches %d bytes of string %d (at most %d bytes, %d strings)", i, (int)match_len[i],
-                           (int)match_id[i], DOTS_MAX_STOP_BYTES, DOTS_MAX_STOP_STRINGS);
-    if (match_len[0]) return e->fail(DOTS_E_INVALID, "stop strings: the root state cannot end a string");
-    CK(hipSetDevice(e->device));
-    DotsEngine::Stop a;
-    a.n_states = n_states;
-    CK(e->alloc(&a.table, (size_t)n_states * 256));
-    CK(hipMemcpyAsync(a.table, table, (size_t)n_states * 512, hipMemcpyHostToDevice, e->stream));
-    CK(e->alloc(&a.match_len, (size_t)n_states));
-    CK(hipMemcpyAsync(a.match_len, match_len, (size_t)n_states * 2, hipMemcpyHostToDevice, e->stream));
-    CK(e->alloc(&a.match_id, (size_t)n_states));
-    CK(hipMemcpyAsync(a.match_id, match_id, (size_t)n_states, hipMemcpyHostToDevice, e->stream));
-    CK(hipStreamSynchronize(e->stream));                   // the caller's arrays are free again
-    size_t id = 0;
-    while (id < e->stops.size() && e->stops[id].table) ++id;            // a destroyed automaton's id is reused
-    if (id == e->stops.size()) e->stops.push_back(a); else e->stops[id] = a;
-    *handle_out = (int32_t)id + 1;
-    return DOTS_OK;
-}
-
-int dots_stop_destroy(DotsEngine* e, int32_t handle) {
-    if (!e) return DOTS_E_INVALID;
-    if (!e->tok_off) return e->fail(DOTS_E_STATE, "the token bytes are not set (dots_set_token_bytes): no stop automaton exists");
-    const int id = handle - 1;
-    if (id < 0 || id >= (int)e->stops.size() || !e->stops[id].table) return e->fail(DOTS_E_INVALID, "no stop automaton %d", handle);
-    if (e->stops[id].rows > 0)
-        return e->fail(DOTS_E_STATE, "stop automaton %d is held by %d row(s): clear them first (dots_set_row_stop(row, 0, 0))", handle, e->stops[id].rows);
-    CK(hipSetDevice(e->device));
-    CK(hipStreamSynchronize(e->stream));                   // steps in flight may still walk its table
-    e->release(e->stops[id].table);
-    e->release(e->stops[id].match_len);
-    e->release(e->stops[id].match_id);
-    e->stops[id] = DotsEngine::Stop{};
-    return DOTS_OK;
-}
-
-int dots_set_row_stop(DotsEngine* e, int row, int32_t handle, int min_tokens) {
-    if (!e) return DOTS_E_INVALID;
-    if (!e->tok_off) return e->fail(DOTS_E_STATE, "the token bytes are not set (dots_set_token_bytes): a stop string cannot be matched");
-    if (row < 0 || row >= e->cfg.max_batch) return e->fail(DOTS_E_INVALID, "row %d out of range [0, %d)", row, e->cfg.max_batch);
-    CK(hipSetDevice(e->device));
-    if (handle == 0) return clear_row_feature(e, row, ROW_STOP);
-    const int id = handle - 1;
-    if (id < 0 || id >= (int)e->stops.size() || !e->stops[id].table) return e->fail(DOTS_E_INVALID, "no stop automaton %d", handle);
-    if (min_tokens < 0) return e->fail(DOTS_E_INVALID, "stop strings: min_tokens must be >= 0");
-    return assign_row_stop(e, row, id, min_tokens);
-}
-
-int dots_row_stop_hit(DotsEngine* e, int row, int32_t* out) {
-    if (!e || !out) return e ? e->fail(DOTS_E_INVALID, "null argument") : DOTS_E_INVALID;
-    if (!e->tok_off) return e->fail(DOTS_E_STATE, "the token bytes are not set (dots_set_token_bytes): no row holds stop strings");
-    if (row < 0 || row >= e->cfg.max_batch) return e->fail(DOTS_E_INVALID, "row %d out of range [0, %d)", row, e->cfg.max_batch);
-    out[0] = -1; out[1] = 0; out[2] = 0; out[3] = -1;
-    if (!e->stage.has(row, ROW_STOP)) return DOTS_OK;
-    CK(hipSetDevice(e->device));
-    RowStop rs;
-    CK(hipMemcpyAsync(&rs, e->d_stop + row, sizeof(rs), hipMemcpyDeviceToHost, e->stream));
-    CK(hipStreamSynchronize(e->stream));
-    if (rs.hit_tok >= 0) { out[0] = rs.hit_tok; out[1] = rs.hit_bytes; out[2] = rs.hit_len; out[3] = rs.hit_id; }
-    return DOTS_OK;
-}
-
-// ---------------------------------------------------------------------------------- n-gram speculative decoding
-int dots_set_speculation(DotsEngine* e, int k, int min_n, int max_n) {
-    if (!e) return DOTS_E_INVALID;
-    if (k < 0 || k > DOTS_MAX_SPEC_DRAFTS) return e->fail(DOTS_E_INVALID, "k must be in [0, %d], got %d", DOTS_MAX_SPEC_DRAFTS, k);
-    if (k > 0 && max_n != 0 && (min_n < 1 || max_n < min_n || max_n > DOTS_MAX_NGRAM_SIZE))
-        return e->fail(DOTS_E_INVALID, "n-gram sizes must satisfy 1 <= min_n <= max_n <= %d (max_n = 0: host drafts only), got %d .. %d", DOTS_MAX_NGRAM_SIZE, min_n, max_n);
-    if (k > 0 && e->cfg.max_batch / (k + 1) < 1)
-        return e->fail(DOTS_E_CAPACITY, "%d drafts need %d rows per slot, max_batch is %d", k, k + 1, e->cfg.max_batch);
-    if (e->slot_mode)
-        for (int b = 0; b < e->cfg.max_batch; ++b)
-            if (e->slot_active[b]) return e->fail(DOTS_E_STATE, "speculation cannot change while slot %d is occupied", b);
-    CK(hipSetDevice(e->device));
-    hipStream_t s = e->stream;
-    if (k > 0 && !e->sp_stats) {
-        // each piece is allocated once: a call that failed half way is resumed by the next one
-        if (!e->sp_drafts) CK(e->alloc(&e->sp_drafts, (size_t)DOTS_MAX_BATCH * DOTS_MAX_SPEC_DRAFTS));
-        if (!e->sp_ndraft) CK(e->alloc(&e->sp_ndraft, (size_t)DOTS_MAX_BATCH));
-        if (!e->sp_nlive) CK(e->alloc(&e->sp_nlive, (size_t)DOTS_MAX_BATCH));
-        if (!e->sp_tokens) CK(e->alloc(&e->sp_tokens, (size_t)DOTS_MAX_BATCH));
-        if (!e->sp_ctx) CK(e->alloc(&e->sp_ctx, (size_t)DOTS_MAX_BATCH));
-        if (!e->sp_table) {
-            CK(e->alloc(&e->sp_table, (size_t)DOTS_MAX_BATCH * e->max_pages));
-            const std::vector<int32_t> idle((size_t)DOTS_MAX_BATCH * e->max_pages, e->n_pool_pages);      // every row on the scratch page
-            CK(hipMemcpyAsync(e->sp_table, idle.data(), idle.size() * 4, hipMemcpyHostToDevice, s));
-            CK(hipStreamSynchronize(s));
-        }
-        if (!e->sp_cand) CK(e->alloc(&e->sp_cand, (size_t)DOTS_MAX_BATCH * DOTS_MAX_SPEC_DRAFTS));
-        if (!e->sp_cls) CK(e->alloc(&e->sp_cls, (size_t)DOTS_MAX_BATCH));
-        CK(e->alloc(&e->sp_stats, (size_t)(DOTS_MAX_BATCH + 1) * 3));      // set last, it is the guard above
-        RET(upload_spec_classes(e));                                       // rows may have taken features before the array existed
-    }
-    if (e->sp_stats) {
-        CK(hipMemsetAsync(e->sp_stats, 0, (size_t)(DOTS_MAX_BATCH + 1) * 3 * sizeof(unsigned long long), s));
-        CK(hipMemsetAsync(e->sp_ndraft, 0, DOTS_MAX_BATCH * 4, s));
-        CK(hipStreamSynchronize(s));
-    }
-    drop_step_graphs(e);                                     // a captured step bakes in the draft count and the drafter's sizes
-    e->spec_k = k;
-    e->spec_min_n = k > 0 && max_n > 0 ? min_n : 0;
-    e->spec_max_n = k > 0 ? max_n : 0;
-    return DOTS_OK;
-}
-
-int dots_set_speculation_rows(DotsEngine* e, int flags) {
-    if (!e) return DOTS_E_INVALID;
-    if (flags & ~SPEC_ROWS_ALL) return e->fail(DOTS_E_INVALID, "unknown speculation row flags 0x%x (DOTS_SPEC_ROWS_SAMPLED | DOTS_SPEC_ROWS_STOP)", flags);
-    if (e->slot_mode)
-        for (int b = 0; b < e->cfg.max_batch; ++b)
-            if (e->slot_active[b]) return e->fail(DOTS_E_STATE, "the speculating rows cannot change while slot %d is occupied", b);
-    CK(hipSetDevice(e->device));
-    e->spec_rows = flags;
-    drop_step_graphs(e);                                     // a captured step bakes in whether it draws the draft rows of sampled slots
-    return upload_spec_classes(e);                           // free slots may hold features: every row's class under the new setting
-}
-
-int dots_set_row_drafts(DotsEngine* e, int row, const int32_t* ids_host, int n) {
-    if (!e) return DOTS_E_INVALID;
-    if (row < 0 || row >= e->cfg.max_batch) return e->fail(DOTS_E_INVALID, "row %d out of range [0, %d)", row, e->cfg.max_batch);
-    if (n < 0 || n > e->spec_k) return e->fail(DOTS_E_INVALID, "%d drafts given, the engine speculates %d per step (dots_set_speculation)", n, e->spec_k);
-    if (n > 0 && !ids_host) return e->fail(DOTS_E_INVALID, "null argument");
-    for (int j = 0; j < n; ++j)
-        if (ids_host[j] < 0 || ids_host[j] >= e->cfg.vocab_size) return e->fail(DOTS_E_INVALID, "draft id %d out of range [0, %d)", ids_host[j], e->cfg.vocab_size);
-    if (!e->slot_mode || !e->slot_active[row]) return e->fail(DOTS_E_STATE, "slot %d is not occupied", row);
-    if (!e->spec_k) return DOTS_OK;                          // n == 0 with speculation off: nothing to clear
-    CK(hipSetDevice(e->device));
-    CK(launch_spec_set_drafts(e->stream, e->sp_drafts, e->sp_ndraft, row, ids_host, n));
-    return DOTS_OK;
-}
-
-int dots_spec_stats(DotsEngine* e, int row, int64_t* steps, int64_t* drafted, int64_t* accepted) {
-    if (!e || !steps || !drafted || !accepted) return e ? e->fail(DOTS_E_INVALID, "null argument") : DOTS_E_INVALID;
-    if (row < -1 || row >= e->cfg.max_batch) return e->fail(DOTS_E_INVALID, "row %d out of range [-1, %d)", row, e->cfg.max_batch);
-    *steps = *drafted = *accepted = 0;
-    if (!e->sp_stats) return DOTS_OK;
-    CK(hipSetDevice(e->device));
-    unsigned long long v[3] = {0, 0, 0};
-    CK(hipMemcpyAsync(v, e->sp_stats + (size_t)(row < 0 ? DOTS_MAX_BATCH : row) * 3, sizeof(v), hipMemcpyDeviceToHost, e->stream));
-    CK(hipStreamSynchronize(e->stream));
-    *steps = (int64_t)v[0]; *drafted = (int64_t)v[1]; *accepted = (int64_t)v[2];
-    return DOTS_OK;
-}
-
-int dots_row_guide_state(DotsEngine* e, int row, int32_t* state_out) {
-    if (!e || !state_out) return e ? e->fail(DOTS_E_INVALID, "null argument") : DOTS_E_INVALID;
-    if (row < 0 || row >= e->cfg.max_batch) return e->fail(DOTS_E_INVALID, "row %d out of range [0, %d)", row, e->cfg.max_batch);
-    *state_out = -1;
-    if (!e->stage.has(row, ROW_GUIDE)) return DOTS_OK;
-    CK(hipSetDevice(e->device));
-    RowGuide rg;
-    CK(hipMemcpyAsync(&rg, e->d_guides + row, sizeof(rg), hipMemcpyDeviceToHost, e->stream));
-    CK(hipStreamSynchronize(e->stream));
-    *state_out = rg.state;
-    return DOTS_OK;
-}
-
-int dots_set_row_logprobs(DotsEngine* e, int row, int top_n) {
-    if (!e) return DOTS_E_INVALID;
-    if (row < 0 || row >= e->cfg.max_batch) return e->fail(DOTS_E_INVALID, "row %d out of range [0, %d)", row, e->cfg.max_batch);
-    if (top_n < -1 || top_n > DOTS_MAX_TOP_LOGPROBS) return e->fail(DOTS_E_INVALID, "top_n must be -1 (off) or in [0, %d]", DOTS_MAX_TOP_LOGPROBS);
-    if (top_n < 0 && !e->d_row_lp) return DOTS_OK;
-    if (e->cfg.vocab_size > LP_MAX_V) return e->fail(DOTS_E_INVALID, "logprobs support vocabularies up to %d", LP_MAX_V);
-    CK(hipSetDevice(e->device));
-    if (!e->d_row_lp) {
-        CK(e->alloc(&e->d_row_lp, DOTS_MAX_BATCH));
-        CK(hipMemsetAsync(e->d_row_lp, 0xFF, DOTS_MAX_BATCH * 4, e->stream));
-    }
-    if (top_n >= 0) RET(ensure_lp_state(e));
-    return set_row_lp(e, row, top_n);
-}
-
-int dots_row_logprobs(DotsEngine* e, int row, int pos0, int n, float* tok_lp_host, int32_t* top_ids_host, float* top_lp_host, int32_t* n_out) {
-    if (!e || !n_out || pos0 < 0 || n < 0 || (n > 0 && (!tok_lp_host || !top_ids_host || !top_lp_host)))
-        return e ? e->fail(DOTS_E_INVALID, "bad row_logprobs arguments") : DOTS_E_INVALID;
-    if (e->slot_mode) {
-        if (row < 0 || row >= e->cfg.max_batch || !e->slot_active[row]) return e->fail(DOTS_E_STATE, "slot %d is not occupied", row);
-    } else if (row < 0 || row >= e->B) {
-        return e->fail(DOTS_E_STATE, "row %d is not a sequence of the current static batch (%d rows)", row, e->B);
-    }
-    CK(hipSetDevice(e->device));
-    int32_t len = 0;
-    CK(hipMemcpyAsync(&len, e->out_lens + row, 4, hipMemcpyDeviceToHost, e->stream));
-    CK(hipStreamSynchronize(e->stream));
-    const int take = std::max(0, std::min(n, std::min(len, e->cfg.max_seq_len) - pos0));
-    *n_out = take;
-    if (take <= 0) return DOTS_OK;
-    const size_t K = DOTS_MAX_TOP_LOGPROBS;
-    if (!e->lp_tok) {                                   // never switched on: every position was selected with the row off
-        std::fill(tok_lp_host, tok_lp_host + take, std::nanf(""));
-        std::fill(top_ids_host, top_ids_host + take * K, -1);
-        std::fill(top_lp_host, top_lp_host + take * K, std::nanf(""));
-        return DOTS_OK;
-    }
-    const size_t o = (size_t)row * e->cfg.max_seq_len + pos0;
-    CK(hipMemcpyAsync(tok_lp_host, e->lp_tok + o, (size_t)take * 4, hipMemcpyDeviceToHost, e->stream));
-    CK(hipMemcpyAsync(top_ids_host, e->lp_ids + o * K, (size_t)take * K * 4, hipMemcpyDeviceToHost, e->stream));
-    CK(hipMemcpyAsync(top_lp_host, e->lp_top + o * K, (size_t)take * K * 4, hipMemcpyDeviceToHost, e->stream));
-    CK(hipStreamSynchronize(e->stream));
     return DOTS_OK;
 }
 
@@ -2874,613 +1066,4 @@ int dots_memcpy_d2h(DotsEngine* e, void* dst, const void* src, int64_t bytes) {
     CK(hipStreamSynchronize(e->stream));
     return DOTS_OK;
 }
-
-// ---------------------------------------------------------------- single-kernel entry points
-int dots_op_rmsnorm(DotsEngine* e, const void* x, const void* w, void* y, int64_t rows, int dim, float eps) {
-    if (!e) return DOTS_E_INVALID;
-    CK(hipSetDevice(e->device));
-    CK(launch_rmsnorm(e->stream, (const bf16_t*)x, (const bf16_t*)w, (bf16_t*)y, rows, dim, eps));
-    return DOTS_OK;
-}
-int dots_op_layernorm(DotsEngine* e, const void* x, const void* w, const void* b, void* y, int64_t rows, int dim, float eps) {
-    if (!e) return DOTS_E_INVALID;
-    CK(hipSetDevice(e->device));
-    CK(launch_layernorm(e->stream, (const bf16_t*)x, (const bf16_t*)w, (const bf16_t*)b, (bf16_t*)y, rows, dim, eps));
-    return DOTS_OK;
-}
-int dots_op_gemm(DotsEngine* e, const void* A, const void* W, const void* bias, const void* residual, void* C,
-                 int64_t M, int N, int K, int epilogue, const float* colscale) {
-    if (!e) return DOTS_E_INVALID;
-    CK(hipSetDevice(e->device));
-    const int ldc = epilogue == EPI_SWIGLU ? N / 2 : N;
-    CK(launch_gemm(e->stream, (const bf16_t*)A, (const bf16_t*)W, (const bf16_t*)bias, (const bf16_t*)residual, C, M, N, K, K, ldc, epilogue, colscale));
-    return DOTS_OK;
-}
-
-int dots_op_gemm_fp8(DotsEngine* e, const void* A, const void* W, const void* bias, const void* residual, void* C, int64_t M, int N, int K,
-                     int epilogue) {
-    if (!e || !A || !W || !C) return e ? e->fail(DOTS_E_INVALID, "null argument") : DOTS_E_INVALID;
-    if (!gemm_fp8_supports(N, K) || epilogue == EPI_F32) return e->fail(DOTS_E_INVALID, "fp8 GEMM needs N %% 256 == 0, K %% 64 == 0 and a bf16 output");
-    CK(hipSetDevice(e->device));
-    Scratch sc(e);
-    bf16_t* wq = nullptr;
-    uint8_t *w8 = nullptr, *a8 = nullptr;
-    float *ws = nullptr, *as = nullptr;
-    CK(sc.get(&wq, (size_t)N * K));
-    CK(sc.get(&w8, (size_t)N * K));
-    CK(sc.get(&ws, (size_t)N));
-    CK(sc.get(&a8, (size_t)M * K));
-    CK(sc.get(&as, (size_t)M));
-    CK(hipMemcpyAsync(wq, W, (size_t)N * K * 2, hipMemcpyDeviceToDevice, e->stream));
-    CK(launch_quant_rows_fp8(e->stream, wq, ws, N, K));
-    CK(launch_bf16q_to_fp8(e->stream, wq, w8, (int64_t)N * K));
-    CK(launch_quant_act_fp8(e->stream, (const bf16_t*)A, a8, as, M, K, K));
-    const int ldc = epilogue == EPI_SWIGLU ? N / 2 : N;
-    CK(launch_gemm_fp8(e->stream, a8, as, w8, ws, (const bf16_t*)bias, (const bf16_t*)residual, C, M, N, K, ldc, epilogue));
-    CK(hipStreamSynchronize(e->stream));
-    return DOTS_OK;
-}
-
-int dots_op_quant_fp8(DotsEngine* e, void* w_inout, float* scale_out, int64_t N, int K) {
-    if (!e || !w_inout || !scale_out) return e ? e->fail(DOTS_E_INVALID, "null argument") : DOTS_E_INVALID;
-    CK(hipSetDevice(e->device));
-    CK(launch_quant_rows_fp8(e->stream, (bf16_t*)w_inout, scale_out, N, K));
-    CK(hipStreamSynchronize(e->stream));
-    return DOTS_OK;
-}
-
-static int upload_lists(DotsEngine* e, const int32_t* cu, int n_seq, int Hq, std::vector<Tile64>& tiles, std::vector<QBlock>& qb,
-                        Tile64** d_tiles, QBlock** d_qb, int64_t* Tpad) {
-    std::vector<int> lens(n_seq);
-    for (int i = 0; i < n_seq; ++i) lens[i] = cu[i + 1] - cu[i];
-    build_worklists(lens, Hq, tiles, qb, Tpad);
-    CK(e->alloc(d_tiles, tiles.size() + 1));
-    CK(e->alloc(d_qb, qb.size() + 1));
-    CK(hipMemcpyAsync(*d_tiles, tiles.data(), tiles.size() * sizeof(Tile64), hipMemcpyHostToDevice, e->stream));
-    CK(hipMemcpyAsync(*d_qb, qb.data(), qb.size() * sizeof(QBlock), hipMemcpyHostToDevice, e->stream));
-    CK(hipStreamSynchronize(e->stream));
-    return DOTS_OK;
-}
-
-int dots_op_flash_attn(DotsEngine* e, const void* q, const void* k, const void* vt, void* out, const int32_t* cu, int n_seq,
-                       int Hq, int Hkv, int causal, float scale) {
-    if (!e || !cu || n_seq < 1) return DOTS_E_INVALID;
-    CK(hipSetDevice(e->device));
-    std::vector<Tile64> tiles;
-    std::vector<QBlock> qb;
-    Tile64* dt = nullptr;
-    QBlock* dq = nullptr;
-    int64_t Tpad = 0;
-    RET(upload_lists(e, cu, n_seq, Hq, tiles, qb, &dt, &dq, &Tpad));
-    const int64_t T = cu[n_seq];
-    const XcdPlan xcd_plan = make_xcd_plan(qb.data(), (int)qb.size());
-    hipError_t r = launch_flash_attn(e->stream, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)vt, (bf16_t*)out, dq, (int)qb.size(), T, Tpad, Hq, Hkv, causal, scale, &xcd_plan);
-    hipStreamSynchronize(e->stream);
-    e->release(dt);
-    e->release(dq);
-    CK(r);
-    return DOTS_OK;
-}
-
-int dots_plan_flash_xcd(const int32_t* lens, int n_seq, int Hq, int32_t* base8, int32_t* cnt8, int64_t* cost8) {
-    if (!lens || n_seq < 1 || Hq < 1 || !base8 || !cnt8 || !cost8) return DOTS_E_INVALID;
-    std::vector<int> L(lens, lens + n_seq);
-    for (int n : L)
-        if (n < 1) return DOTS_E_INVALID;
-    std::vector<Tile64> tiles;
-    std::vector<QBlock> qb;
-    int64_t Tpad = 0;
-    build_worklists(L, Hq, tiles, qb, &Tpad);
-    const XcdPlan p = make_xcd_plan(qb.data(), (int)qb.size());
-    for (int x = 0; x < 8; ++x) {
-        base8[x] = p.base[x];
-        cnt8[x] = p.cnt[x];
-        cost8[x] = 0;
-        for (int i = p.base[x]; i < p.base[x] + p.cnt[x]; ++i) cost8[x] += ((qb[i].n + 63) / 64 + 1) & ~1;
-    }
-    return (int)qb.size();
-}
-
-int dots_op_qkv_rope_split(DotsEngine* e, const void* qkv, void* q, void* k, void* vt, const int32_t* cu, int n_seq,
-                           const int32_t* pos_host, int Hq, int Hkv, int rope2d, float theta) {
-    if (!e || !cu || n_seq < 1 || !pos_host) return DOTS_E_INVALID;
-    CK(hipSetDevice(e->device));
-    std::vector<Tile64> tiles;
-    std::vector<QBlock> qb;
-    Tile64* dt = nullptr;
-    QBlock* dq = nullptr;
-    int64_t Tpad = 0;
-    RET(upload_lists(e, cu, n_seq, Hq, tiles, qb, &dt, &dq, &Tpad));
-    const int64_t T = cu[n_seq];
-    int32_t* dpos = nullptr;
-    float2* cs = nullptr;
-    float* freq = nullptr;
-    const int nf = rope2d ? 32 : 64;
-    std::vector<float> f(nf);
-    for (int i = 0; i < nf; ++i) f[i] = 1.0f / powf(theta, (float)(2 * i) / (rope2d ? 64.0f : 128.0f));
-    CK(e->alloc(&dpos, (size_t)T * (rope2d ? 2 : 1)));
-    CK(e->alloc(&cs, (size_t)T * 64));
-    CK(e->alloc(&freq, (size_t)nf));
-    CK(hipMemcpyAsync(dpos, pos_host, (size_t)T * (rope2d ? 2 : 1) * 4, hipMemcpyHostToDevice, e->stream));
-    CK(hipMemcpyAsync(freq, f.data(), nf * 4, hipMemcpyHostToDevice, e->stream));
-    CK(launch_rope_table(e->stream, dpos, freq, cs, T, rope2d));
-    hipError_t r = launch_qkv_rope_split(e->stream, (const bf16_t*)qkv, cs, dt, (int)tiles.size(), (bf16_t*)q, (bf16_t*)k, (bf16_t*)vt, T, Tpad, Hq, Hkv);
-    hipStreamSynchronize(e->stream);
-    e->release(dt); e->release(dq); e->release(dpos); e->release(cs); e->release(freq);
-    CK(r);
-    return DOTS_OK;
-}
-
-// The qkv projection of a prefill pass + rope + head-major split, either as the engine's fused path (fused != 0: the GEMM's rope epilogue writes q / k,
-// the split kernel only transposes v) or as the two kernels of rounds 1-5 — the test holds the two to the same bits.  fused != 0 fails with
-// DOTS_E_INVALID when the process's GEMM plan / the shape has no fused kernel.
-int dots_op_qkv_proj_rope(DotsEngine* e, const void* x, const void* w, const void* bias, void* qkv_ws, void* q, void* k, void* vt, const int32_t* cu, int n_seq,
-                          const int32_t* pos_host, int K, int Hq, int Hkv, int rope2d, float theta, int fused) {
-    if (!e || !x || !w || !qkv_ws || !q || !k || !vt || !cu || n_seq < 1 || !pos_host) return DOTS_E_INVALID;
-    CK(hipSetDevice(e->device));
-    std::vector<Tile64> tiles;
-    std::vector<QBlock> qb;
-    Tile64* dt = nullptr;
-    QBlock* dq = nullptr;
-    int64_t Tpad = 0;
-    RET(upload_lists(e, cu, n_seq, Hq, tiles, qb, &dt, &dq, &Tpad));
-    const int64_t T = cu[n_seq];
-    const int N = (Hq + 2 * Hkv) * 128;
-    int32_t* dpos = nullptr;
-    float2* cs = nullptr;
-    float* freq = nullptr;
-    const int nf = rope2d ? 32 : 64;
-    std::vector<float> f(nf);
-    for (int i = 0; i < nf; ++i) f[i] = 1.0f / powf(theta, (float)(2 * i) / (rope2d ? 64.0f : 128.0f));
-    CK(e->alloc(&dpos, (size_t)T * (rope2d ? 2 : 1)));
-    CK(e->alloc(&cs, (size_t)T * 64));
-    CK(e->alloc(&freq, (size_t)nf));
-    CK(hipMemcpyAsync(dpos, pos_host, (size_t)T * (rope2d ? 2 : 1) * 4, hipMemcpyHostToDevice, e->stream));
-    CK(hipMemcpyAsync(freq, f.data(), nf * 4, hipMemcpyHostToDevice, e->stream));
-    CK(launch_rope_table(e->stream, dpos, freq, cs, T, rope2d));
-    hipError_t r;
-    if (fused) {
-        r = launch_gemm_qk_rope(e->stream, (const bf16_t*)x, (const bf16_t*)w, (const bf16_t*)bias, (bf16_t*)qkv_ws, T, N, K, K, N, cs, (bf16_t*)q, (bf16_t*)k, Hq, Hkv);
-        if (r == hipSuccess) r = launch_qkv_rope_split(e->stream, (const bf16_t*)qkv_ws, cs, dt, (int)tiles.size(), (bf16_t*)q, (bf16_t*)k, (bf16_t*)vt, T, Tpad, Hq, Hkv, true);
-    } else {
-        r = launch_gemm(e->stream, (const bf16_t*)x, (const bf16_t*)w, (const bf16_t*)bias, nullptr, qkv_ws, T, N, K, K, N, EPI_NONE);
-        if (r == hipSuccess) r = launch_qkv_rope_split(e->stream, (const bf16_t*)qkv_ws, cs, dt, (int)tiles.size(), (bf16_t*)q, (bf16_t*)k, (bf16_t*)vt, T, Tpad, Hq, Hkv);
-    }
-    hipStreamSynchronize(e->stream);
-    e->release(dt); e->release(dq); e->release(dpos); e->release(cs); e->release(freq);
-    if (r == hipErrorNotSupported) { (void)hipGetLastError(); return e->fail(DOTS_E_INVALID, "no fused qkv + rope kernel for this shape / GEMM plan"); }
-    CK(r);
-    return DOTS_OK;
-}
-
-// ---- single decode kernels at caller-chosen dimensions (tests/test_decode_kernels_gpu.py).  Inputs are ROW-MAJOR bf16
-// tensors as the HF state dict holds them; the fragment-order / permuted packing the decode step uses happens inside, with
-// the same pack kernels the engine runs at dots_finalize_weights.
-
-namespace {
-// kv_scales == nullptr: a bf16 page pool; else an fp8 one with these [Hkv][2] scales (dots_op_dec_qkv_kv8 / dots_op_decode_attn_kv8)
-int op_dec_qkv(DotsEngine* e, const void* h, const void* ln_w, const void* wqkv, const void* bias, const int32_t* ctx_len_dev,
-               const int32_t* block_table_dev, int max_pages, void* pool_layer, void* q_out, int B, int H, int Hq, int Hkv, float eps,
-               float rope_theta, int fp8, const float* kv_scales) {
-    if (!e || !h || !ln_w || !wqkv || !ctx_len_dev || !block_table_dev || !pool_layer || !q_out) return e ? e->fail(DOTS_E_INVALID, "null argument") : DOTS_E_INVALID;
-    CK(hipSetDevice(e->device));
-    Scratch sc(e);
-    void* wd = nullptr;
-    float *freq = nullptr, *wscale = nullptr;
-    CK(sc.get(&freq, 64));
-    float f[64];
-    for (int i = 0; i < 64; ++i) f[i] = 1.0f / powf(rope_theta, (float)(2 * i) / 128.0f);
-    CK(hipMemcpyAsync(freq, f, sizeof(f), hipMemcpyHostToDevice, e->stream));
-    RET(op_weight(e, sc, (const bf16_t*)wqkv, (int64_t)(Hq + 2 * Hkv) * 128, H, Hq, Hkv, true, fp8, &wd, &wscale));
-    bf16_t* xn = nullptr;                            // scratch sized for THIS call's hidden size (the engine's own d_xn is sized for its model: the tests run the
-    CK(sc.get(&xn, (size_t)DOTS_MAX_BATCH * H));     // BASELINE dimensions through a small-model engine)
-    CK(launch_dec_qkv(e->stream, (const bf16_t*)h, (const bf16_t*)ln_w, wd, wscale, (const bf16_t*)bias, freq, ctx_len_dev, block_table_dev, max_pages,
-                      pool_layer, (bf16_t*)q_out, B, H, Hq, Hkv, eps, e->force_part ? e->dec_cus : 0, xn, nullptr, nullptr, kv_scales));      // dots_set_decode_plan(1): the partition plan's kernels
-    CK(hipStreamSynchronize(e->stream));
-    return DOTS_OK;
-}
-
-int op_decode_attn(DotsEngine* e, const void* q, const void* pool_layer, const int32_t* ctx_len_dev, const int32_t* block_table_dev,
-                   int max_pages, void* out, int B, int Hq, int Hkv, int max_seq_len, const float* kv_scales) {
-    if (!e || !q || !pool_layer || !ctx_len_dev || !block_table_dev || !out || B < 1 || B > DOTS_MAX_BATCH) return e ? e->fail(DOTS_E_INVALID, "bad decode_attn arguments") : DOTS_E_INVALID;
-    CK(hipSetDevice(e->device));
-    Scratch sc(e);
-    const int n_splits = splits_for_ctx(max_seq_len);
-    float *po = nullptr, *pml = nullptr;
-    bf16_t* att = nullptr;
-    const size_t rb = (size_t)(B + 15) / 16 * 16;
-    CK(sc.get(&po, rb * Hq * n_splits * 128));
-    CK(sc.get(&pml, rb * Hq * n_splits * 2));
-    CK(sc.get(&att, rb * Hq * 128));
-    CK(hipMemsetAsync(po, 0xff, rb * Hq * n_splits * 128 * 4, e->stream));      // NaN: a partial read without having been written shows up
-    CK(hipMemsetAsync(pml, 0xff, rb * Hq * n_splits * 2 * 4, e->stream));
-    CK(launch_decode_attn(e->stream, (const bf16_t*)q, pool_layer, ctx_len_dev, block_table_dev, max_pages, po, pml, B, Hq, Hkv, n_splits,
-                          1.0f / sqrtf(128.0f), e->force_part ? e->dec_cus : 0, e->attn_stream, kv_scales));      // dots_set_decode_plan: the plan's kernel choice
-    CK(launch_decode_attn_combine(e->stream, po, pml, ctx_len_dev, att, B, Hq, Hkv, n_splits));
-    CK(launch_unpack_x(e->stream, att, (bf16_t*)out, B, Hq * 128));
-    CK(hipStreamSynchronize(e->stream));
-    return DOTS_OK;
-}
-}  // namespace
-
-int dots_op_dec_qkv(DotsEngine* e, const void* h, const void* ln_w, const void* wqkv, const void* bias, const int32_t* ctx_len_dev,
-                    const int32_t* block_table_dev, int max_pages, void* pool_layer, void* q_out, int B, int H, int Hq, int Hkv, float eps,
-                    float rope_theta, int fp8) {
-    return op_dec_qkv(e, h, ln_w, wqkv, bias, ctx_len_dev, block_table_dev, max_pages, pool_layer, q_out, B, H, Hq, Hkv, eps, rope_theta, fp8, nullptr);
-}
-
-int dots_op_dec_qkv_kv8(DotsEngine* e, const void* h, const void* ln_w, const void* wqkv, const void* bias, const int32_t* ctx_len_dev,
-                        const int32_t* block_table_dev, int max_pages, void* pool_layer, void* q_out, int B, int H, int Hq, int Hkv, float eps,
-                        float rope_theta, int fp8, const float* kv_scales_dev) {
-    if (!kv_scales_dev) return e ? e->fail(DOTS_E_INVALID, "null kv_scales") : DOTS_E_INVALID;
-    return op_dec_qkv(e, h, ln_w, wqkv, bias, ctx_len_dev, block_table_dev, max_pages, pool_layer, q_out, B, H, Hq, Hkv, eps, rope_theta, fp8, kv_scales_dev);
-}
-
-int dots_op_decode_attn(DotsEngine* e, const void* q, const void* pool_layer, const int32_t* ctx_len_dev, const int32_t* block_table_dev,
-                        int max_pages, void* out, int B, int Hq, int Hkv, int max_seq_len) {
-    return op_decode_attn(e, q, pool_layer, ctx_len_dev, block_table_dev, max_pages, out, B, Hq, Hkv, max_seq_len, nullptr);
-}
-
-int dots_op_decode_attn_kv8(DotsEngine* e, const void* q, const void* pool_layer, const int32_t* ctx_len_dev, const int32_t* block_table_dev,
-                            int max_pages, void* out, int B, int Hq, int Hkv, int max_seq_len, const float* kv_scales_dev) {
-    if (!kv_scales_dev) return e ? e->fail(DOTS_E_INVALID, "null kv_scales") : DOTS_E_INVALID;
-    return op_decode_attn(e, q, pool_layer, ctx_len_dev, block_table_dev, max_pages, out, B, Hq, Hkv, max_seq_len, kv_scales_dev);
-}
-
-int dots_op_dec_proj(DotsEngine* e, const void* x, const void* w, void* h_inout, int B, int N, int K, int fp8) {
-    if (!e || !x || !w || !h_inout || B < 1 || B > DOTS_MAX_BATCH) return e ? e->fail(DOTS_E_INVALID, "bad dec_proj arguments") : DOTS_E_INVALID;
-    CK(hipSetDevice(e->device));
-    Scratch sc(e);
-    bf16_t* xi = nullptr;
-    void* wd = nullptr;
-    float* wscale = nullptr;
-    CK(sc.get(&xi, (size_t)(B + 15) / 16 * 16 * K));
-    CK(launch_pack_x(e->stream, (const bf16_t*)x, xi, B, K));
-    RET(op_weight(e, sc, (const bf16_t*)w, N, K, 0, 0, false, fp8, &wd, &wscale));
-    bool pend = false;
-    float* part = nullptr;
-    CK(sc.get(&part, (size_t)DEC_KSPLIT_PARTS * DOTS_MAX_BATCH * N));
-    CK(launch_dec_proj(e->stream, xi, wd, wscale, (bf16_t*)h_inout, B, N, K, e->force_part ? e->dec_cus : 0, part, &pend));
-    if (pend) CK(launch_dec_norm_ximg(e->stream, (const bf16_t*)h_inout, nullptr, nullptr, B, N, 0.f, part, wscale));        // the K-split kernel leaves the residual update to its consumer
-    CK(hipStreamSynchronize(e->stream));
-    return DOTS_OK;
-}
-
-int dots_op_dec_gateup(DotsEngine* e, const void* h, const void* ln_w, const void* gate_w, const void* up_w, void* act_out, int B, int H, int I, float eps,
-                       int fp8) {
-    if (!e || !h || !ln_w || !gate_w || !up_w || !act_out || B < 1 || B > DOTS_MAX_BATCH) return e ? e->fail(DOTS_E_INVALID, "bad dec_gateup arguments") : DOTS_E_INVALID;
-    CK(hipSetDevice(e->device));
-    Scratch sc(e);
-    bf16_t *w13 = nullptr, *act = nullptr;
-    void* w13d = nullptr;
-    float* wscale = nullptr;
-    CK(sc.get(&w13, (size_t)2 * I * H));
-    CK(sc.get(&act, (size_t)(B + 15) / 16 * 16 * I));
-    CK(launch_pack_w13(e->stream, (const bf16_t*)gate_w, (const bf16_t*)up_w, w13, I, H));
-    RET(op_weight(e, sc, w13, (int64_t)2 * I, H, 0, 0, false, fp8, &w13d, &wscale));
-    bf16_t* xn = nullptr;
-    CK(sc.get(&xn, (size_t)DOTS_MAX_BATCH * H));
-    CK(launch_dec_gateup(e->stream, (const bf16_t*)h, (const bf16_t*)ln_w, w13d, wscale, act, B, H, I, eps, e->force_part ? e->dec_cus : 0, xn));
-    CK(launch_unpack_x(e->stream, act, (bf16_t*)act_out, B, I));
-    CK(hipStreamSynchronize(e->stream));
-    return DOTS_OK;
-}
-
-int dots_op_dec_lmhead(DotsEngine* e, const void* h, const void* ln_w, const void* w, void* logits_out, int B, int H, int V, float eps, int fp8) {
-    if (!e || !h || !ln_w || !w || !logits_out || B < 1 || B > DOTS_MAX_BATCH) return e ? e->fail(DOTS_E_INVALID, "bad dec_lmhead arguments") : DOTS_E_INVALID;
-    CK(hipSetDevice(e->device));
-    Scratch sc(e);
-    void* wd = nullptr;
-    float* wscale = nullptr;
-    RET(op_weight(e, sc, (const bf16_t*)w, V, H, 0, 0, false, fp8, &wd, &wscale));
-    bf16_t* xn = nullptr;
-    CK(sc.get(&xn, (size_t)DOTS_MAX_BATCH * H));
-    CK(launch_dec_lmhead(e->stream, (const bf16_t*)h, (const bf16_t*)ln_w, wd, wscale, (float*)logits_out, B, H, V, eps, e->force_part ? e->dec_cus : 0, xn));
-    CK(hipStreamSynchronize(e->stream));
-    return DOTS_OK;
-}
-
-}  // extern "C"
-
-namespace {
-// dots_op_select_tokens / dots_bench_select_tokens.  mode 2 = the per-row stage once (the op); mode 0 / 1 / 2 with iters > 0 = the legacy
-// arg max pair / the legacy sampler (params[0].temperature, top_p, seed) / the per-row stage, replayed iters times between two events
-// with every row marked finished (nothing is appended), *ms = the mean time of one replay.
-// rules_host != nullptr (mode 2 only): row b carries rules_host[b] unless that entry is empty (no bias, allowed list, min_tokens, stop id or
-// ignore_eos), the engine's EOS ids are live, and n_gen_host[b] (or hist_lens - n_prompt when nullptr) is the row's generated count.
-int select_op(DotsEngine* e, const float* logits_dev, int B, int V, const DotsSamplingParams* params_host, const int32_t* hist_dev,
-              const int32_t* hist_lens_dev, int hist_stride, const int32_t* n_prompt_dev, int32_t* out_tokens_dev, int mode, int iters, float* ms,
-              const DotsLogitRules* rules_host = nullptr, const int32_t* n_gen_host = nullptr, const int32_t* guide_ids_host = nullptr,
-              const int32_t* states_host = nullptr, int32_t* states_out_host = nullptr, const DotsNgramRule* ngram_host = nullptr) {
-    if (!e || !logits_dev || B < 1 || B > DOTS_MAX_BATCH || V < 1 || !params_host || !hist_dev || !hist_lens_dev || hist_stride < 1 || !n_prompt_dev ||
-        (!out_tokens_dev && !ms) || mode < 0 || mode > 2 || (rules_host && mode != 2) || (n_gen_host && !rules_host) ||
-        (guide_ids_host && (!rules_host || !states_host)) || (ngram_host && !rules_host))
-        return e ? e->fail(DOTS_E_INVALID, "bad select_tokens arguments") : DOTS_E_INVALID;
-    // ngram_host != nullptr: row b carries ngram_host[b] unless its size is 0; its history is hist[n_prompt[b] .. hist_lens[b]), copied to
-    // the front of the stage's output rows (where the engine keeps a row's own output).  A window may reach hist_stride.
-    std::vector<RowNgram> ngrams(ngram_host ? DOTS_MAX_BATCH : 0, RowNgram{});
-    if (ngram_host)
-        for (int b = 0; b < B; ++b)
-            if (ngram_host[b].size != 0) RET(check_ngram_rule(e, ngram_host[b], V, hist_stride, &ngrams[b]));
-    // guide_ids_host != nullptr: row b holds guide guide_ids_host[b] (-1: none) of this engine at state states_host[b]; V must be the engine's
-    // vocabulary (the token bytes are its).  states_out_host (may be nullptr) receives the rows' states after the commit, -1 for a row without.
-    if (guide_ids_host) {
-        if (!e->tok_off) return e->fail(DOTS_E_STATE, "the token bytes are not set (dots_set_token_bytes)");
-        if (V != e->cfg.vocab_size) return e->fail(DOTS_E_INVALID, "guided selection needs V = the engine's vocabulary %d", e->cfg.vocab_size);
-        for (int b = 0; b < B; ++b) {
-            const int id = guide_ids_host[b];
-            if (id < 0) continue;
-            if (id >= (int)e->guides.size() || !e->guides[id].table) return e->fail(DOTS_E_INVALID, "row %d: no guide %d", b, id);
-            if (states_host[b] < 0 || states_host[b] >= e->guides[id].n_states)
-                return e->fail(DOTS_E_INVALID, "row %d: state %d outside [0, %d)", b, states_host[b], e->guides[id].n_states);
-        }
-    }
-    if (n_gen_host)
-        for (int b = 0; b < B; ++b)
-            if (n_gen_host[b] < 0 || n_gen_host[b] > hist_stride) return e->fail(DOTS_E_INVALID, "n_gen must be in [0, hist_stride]");
-    std::vector<RowParams> rp(B);
-    for (int b = 0; b < B; ++b) RET(check_row_params(e, params_host[b], &rp[b]));
-    if (mode == 1 && !(rp[0].temperature > 0.f)) return e->fail(DOTS_E_INVALID, "the legacy sampler needs temperature > 0");
-    const std::vector<int32_t> own(B, 1);
-    CK(hipSetDevice(e->device));
-    Scratch sc(e);
-    const size_t W = ((size_t)V + 31) / 32;
-    RowParams* tab = nullptr;
-    int32_t *own_d = nullptr, *cnt = nullptr, *pidx = nullptr, *cur = nullptr, *ctx = nullptr, *ids = nullptr, *lens = nullptr, *fin = nullptr;
-    uint32_t *seen = nullptr, *thr = nullptr;
-    float *pen = nullptr, *pval = nullptr;
-    CK(sc.get(&tab, B));
-    CK(sc.get(&own_d, B));
-    CK(sc.get(&thr, B));
-    CK(sc.get(&cnt, (size_t)B * V));
-    CK(sc.get(&seen, (size_t)B * W));
-    CK(sc.get(&pen, (size_t)B * V));
-    CK(sc.get(&pval, (size_t)B * 64));
-    CK(sc.get(&pidx, (size_t)B * 64));
-    CK(sc.get(&cur, B));
-    CK(sc.get(&ctx, B));
-    CK(sc.get(&ids, (size_t)B * (hist_stride + 1)));
-    CK(sc.get(&lens, B));
-    CK(sc.get(&fin, B));
-    CK(hipMemcpyAsync(tab, rp.data(), B * sizeof(RowParams), hipMemcpyHostToDevice, e->stream));
-    CK(hipMemcpyAsync(own_d, own.data(), B * 4, hipMemcpyHostToDevice, e->stream));
-    CK(launch_pen_history(e->stream, hist_dev, hist_lens_dev, hist_stride, n_prompt_dev, B, V, cnt, seen, lens));
-    StepState st;
-    st.cur_tokens = cur; st.ctx_len = ctx; st.out_ids = ids; st.out_lens = lens; st.finished = fin;
-    st.eos_ids = e->eos_ids; st.sel = nullptr; st.max_len = nullptr;
-    st.n_eos = rules_host ? e->n_eos : 0; st.out_stride = hist_stride + 1; st.cap = hist_stride + 2; st.advance_ctx = 0;
-    RowRules* rtab = nullptr;
-    float* img = nullptr;
-    if (rules_host) {
-        int32_t* stage = nullptr;
-        CK(sc.get(&rtab, DOTS_MAX_BATCH));
-        CK(sc.get(&img, (size_t)B * V));
-        CK(sc.get(&stage, (size_t)V + 2 * DOTS_MAX_LOGIT_BIAS));
-        for (int b = 0; b < B; ++b) {
-            const DotsLogitRules& r = rules_host[b];
-            if (!r.n_bias && !r.allowed_ids && !r.min_tokens && !r.n_stop && !r.ignore_eos) continue;
-            RowRules rr;
-            RET(check_logit_rules(e, r, V, e->h_eos, e->n_eos, &rr));
-            const int n_allowed = r.allowed_ids ? r.n_allowed : 0;
-            if (n_allowed) CK(hipMemcpyAsync(stage, r.allowed_ids, (size_t)n_allowed * 4, hipMemcpyHostToDevice, e->stream));
-            if (r.n_bias) {
-                CK(hipMemcpyAsync(stage + V, r.bias_ids, (size_t)r.n_bias * 4, hipMemcpyHostToDevice, e->stream));
-                CK(hipMemcpyAsync(stage + V + DOTS_MAX_LOGIT_BIAS, r.bias_values, (size_t)r.n_bias * 4, hipMemcpyHostToDevice, e->stream));
-            }
-            CK(launch_set_row_rules(e->stream, rtab, img, b, V, rr, stage, n_allowed, stage + V,
-                                    reinterpret_cast<const float*>(stage + V + DOTS_MAX_LOGIT_BIAS), r.n_bias));
-            CK(hipStreamSynchronize(e->stream));           // the caller's lists and the staging buffer are free again
-        }
-        if (n_gen_host) CK(hipMemcpyAsync(lens, n_gen_host, B * 4, hipMemcpyHostToDevice, e->stream));
-    }
-    RowSel rs{tab, own_d, cnt, seen, pen, thr, 0, rtab, img, GuideSel{}, NgramSel{}};
-    if (ngram_host) {
-        RowNgram* ntab = nullptr;
-        uint32_t* nmask = nullptr;
-        CK(sc.get(&ntab, DOTS_MAX_BATCH));
-        CK(sc.get(&nmask, (size_t)B * ngram_mask_words(V)));
-        CK(hipMemcpyAsync(ntab, ngrams.data(), DOTS_MAX_BATCH * sizeof(RowNgram), hipMemcpyHostToDevice, e->stream));
-        CK(launch_ngram_history(e->stream, hist_dev, hist_lens_dev, hist_stride, n_prompt_dev, B, ids, st.out_stride));
-        rs.ngram = NgramSel{ntab, nmask, ngram_mask_words(V), V};
-    }
-    RowGuide* gtab = nullptr;
-    int32_t* gstates = nullptr;
-    if (guide_ids_host) {
-        uint32_t* gmask = nullptr;
-        CK(sc.get(&gtab, DOTS_MAX_BATCH));
-        CK(sc.get(&gstates, DOTS_MAX_BATCH));
-        CK(sc.get(&gmask, (size_t)B * guide_mask_words(V)));
-        std::vector<RowGuide> rows(DOTS_MAX_BATCH, RowGuide{});
-        for (int b = 0; b < B; ++b) {
-            if (guide_ids_host[b] < 0) continue;
-            const DotsEngine::Guide& g = e->guides[guide_ids_host[b]];
-            rows[b] = RowGuide{g.table, g.accepting, g.n_states, g.start, states_host[b], 0};
-        }
-        CK(hipMemcpyAsync(gtab, rows.data(), DOTS_MAX_BATCH * sizeof(RowGuide), hipMemcpyHostToDevice, e->stream));
-        CK(hipMemcpyAsync(gstates, states_host, B * 4, hipMemcpyHostToDevice, e->stream));
-        CK(hipStreamSynchronize(e->stream));               // `rows` is a local
-        rs.guide = GuideSel{gtab, gmask, e->tok_off, e->tok_bytes, guide_mask_words(V), V};
-    }
-    auto run = [&]() -> hipError_t {
-        if (rs.guide.rows) {
-            // every replay starts from the given states (a timed replay commits nothing: its rows are marked finished)
-            hipError_t r = launch_guide_set_states(e->stream, gtab, gstates, B);
-            if (r == hipSuccess) r = launch_guide_mask(e->stream, rs.guide, B, nullptr);
-            if (r != hipSuccess) return r;
-        }
-        if (rs.ngram.rows) {
-            // a timed replay marks its rows finished so that nothing is appended: the ban kernel is told of none, or it would skip them all
-            hipError_t r = launch_ngram_ban(e->stream, rs.ngram, B, st.out_ids, st.out_lens, st.out_stride, iters > 0 ? nullptr : st.finished, nullptr);
-            if (r != hipSuccess) return r;
-        }
-        if (mode == 0) return launch_argmax_step(e->stream, logits_dev, V, V, B, pval, pidx, st);
-        if (mode == 1) return launch_sample_step(e->stream, logits_dev, V, V, B, rp[0].temperature, rp[0].top_p, rp[0].seed, st);
-        return launch_select_rows(e->stream, logits_dev, V, V, B, rs, pval, pidx, st);
-    };
-    if (iters <= 0) {
-        CK(run());
-        CK(hipMemcpyAsync(out_tokens_dev, cur, B * 4, hipMemcpyDeviceToDevice, e->stream));
-        std::vector<RowGuide> after(states_out_host ? B : 0);
-        if (states_out_host) CK(hipMemcpyAsync(after.data(), gtab, B * sizeof(RowGuide), hipMemcpyDeviceToHost, e->stream));
-        CK(hipStreamSynchronize(e->stream));
-        for (size_t b = 0; b < after.size(); ++b) states_out_host[b] = after[b].table ? after[b].state : -1;
-        return DOTS_OK;
-    }
-    const std::vector<int32_t> ones(B, 1);
-    CK(hipMemcpyAsync(fin, ones.data(), B * 4, hipMemcpyHostToDevice, e->stream));
-    for (int i = 0; i < 3; ++i) CK(run());                                  // warm-up
-    hipEvent_t t0 = nullptr, t1 = nullptr;
-    CK(hipEventCreate(&t0));
-    CK(hipEventCreate(&t1));
-    hipError_t r = hipEventRecord(t0, e->stream);
-    for (int i = 0; i < iters && r == hipSuccess; ++i) r = run();
-    if (r == hipSuccess) r = hipEventRecord(t1, e->stream);
-    if (r == hipSuccess) r = hipEventSynchronize(t1);
-    float total = 0.f;
-    if (r == hipSuccess) r = hipEventElapsedTime(&total, t0, t1);
-    hipEventDestroy(t0);
-    hipEventDestroy(t1);
-    CK(r);
-    *ms = total / iters;
-    return DOTS_OK;
-}
-}  // namespace
-
-extern "C" {
-int dots_op_select_tokens(DotsEngine* e, const float* logits_dev, int B, int V, const DotsSamplingParams* params_host, const int32_t* hist_dev,
-                          const int32_t* hist_lens_dev, int hist_stride, const int32_t* n_prompt_dev, int32_t* out_tokens_dev) {
-    if (!out_tokens_dev) return e ? e->fail(DOTS_E_INVALID, "bad select_tokens arguments") : DOTS_E_INVALID;
-    return select_op(e, logits_dev, B, V, params_host, hist_dev, hist_lens_dev, hist_stride, n_prompt_dev, out_tokens_dev, 2, 0, nullptr);
-}
-
-int dots_bench_select_tokens(DotsEngine* e, const float* logits_dev, int B, int V, const DotsSamplingParams* params_host, const int32_t* hist_dev,
-                             const int32_t* hist_lens_dev, int hist_stride, const int32_t* n_prompt_dev, int mode, int iters, float* ms_out) {
-    if (!ms_out || iters < 1) return e ? e->fail(DOTS_E_INVALID, "bad bench_select_tokens arguments") : DOTS_E_INVALID;
-    return select_op(e, logits_dev, B, V, params_host, hist_dev, hist_lens_dev, hist_stride, n_prompt_dev, nullptr, mode, iters, ms_out);
-}
-
-int dots_op_select_tokens_rules(DotsEngine* e, const float* logits_dev, int B, int V, const DotsSamplingParams* params_host, const DotsLogitRules* rules_host,
-                                const int32_t* n_gen_host, const int32_t* hist_dev, const int32_t* hist_lens_dev, int hist_stride,
-                                const int32_t* n_prompt_dev, int32_t* out_tokens_dev) {
-    if (!out_tokens_dev || !rules_host) return e ? e->fail(DOTS_E_INVALID, "bad select_tokens arguments") : DOTS_E_INVALID;
-    return select_op(e, logits_dev, B, V, params_host, hist_dev, hist_lens_dev, hist_stride, n_prompt_dev, out_tokens_dev, 2, 0, nullptr, rules_host, n_gen_host);
-}
-
-int dots_bench_select_tokens_rules(DotsEngine* e, const float* logits_dev, int B, int V, const DotsSamplingParams* params_host, const DotsLogitRules* rules_host,
-                                   const int32_t* n_gen_host, const int32_t* hist_dev, const int32_t* hist_lens_dev, int hist_stride,
-                                   const int32_t* n_prompt_dev, int iters, float* ms_out) {
-    if (!ms_out || iters < 1 || !rules_host) return e ? e->fail(DOTS_E_INVALID, "bad bench_select_tokens arguments") : DOTS_E_INVALID;
-    return select_op(e, logits_dev, B, V, params_host, hist_dev, hist_lens_dev, hist_stride, n_prompt_dev, nullptr, 2, iters, ms_out, rules_host, n_gen_host);
-}
-
-int dots_op_select_tokens_guided(DotsEngine* e, const float* logits_dev, int B, int V, const DotsSamplingParams* params_host, const DotsLogitRules* rules_host,
-                                 const int32_t* n_gen_host, const int32_t* guide_ids_host, const int32_t* states_host, const int32_t* hist_dev,
-                                 const int32_t* hist_lens_dev, int hist_stride, const int32_t* n_prompt_dev, int32_t* out_tokens_dev, int32_t* states_out_host) {
-    if (!out_tokens_dev || !rules_host || !guide_ids_host) return e ? e->fail(DOTS_E_INVALID, "bad select_tokens arguments") : DOTS_E_INVALID;
-    return select_op(e, logits_dev, B, V, params_host, hist_dev, hist_lens_dev, hist_stride, n_prompt_dev, out_tokens_dev, 2, 0, nullptr, rules_host, n_gen_host,
-                     guide_ids_host, states_host, states_out_host);
-}
-
-int dots_bench_select_tokens_guided(DotsEngine* e, const float* logits_dev, int B, int V, const DotsSamplingParams* params_host, const DotsLogitRules* rules_host,
-                                    const int32_t* n_gen_host, const int32_t* guide_ids_host, const int32_t* states_host, const int32_t* hist_dev,
-                                    const int32_t* hist_lens_dev, int hist_stride, const int32_t* n_prompt_dev, int iters, float* ms_out) {
-    if (!ms_out || iters < 1 || !rules_host || !guide_ids_host) return e ? e->fail(DOTS_E_INVALID, "bad bench_select_tokens arguments") : DOTS_E_INVALID;
-    return select_op(e, logits_dev, B, V, params_host, hist_dev, hist_lens_dev, hist_stride, n_prompt_dev, nullptr, 2, iters, ms_out, rules_host, n_gen_host,
-                     guide_ids_host, states_host, nullptr);
-}
-
-int dots_op_select_tokens_ngram(DotsEngine* e, const float* logits_dev, int B, int V, const DotsSamplingParams* params_host, const DotsLogitRules* rules_host,
-                                const DotsNgramRule* ngram_host, const int32_t* hist_dev, const int32_t* hist_lens_dev, int hist_stride,
-                                const int32_t* n_prompt_dev, int32_t* out_tokens_dev) {
-    if (!out_tokens_dev || !rules_host || !ngram_host) return e ? e->fail(DOTS_E_INVALID, "bad select_tokens arguments") : DOTS_E_INVALID;
-    return select_op(e, logits_dev, B, V, params_host, hist_dev, hist_lens_dev, hist_stride, n_prompt_dev, out_tokens_dev, 2, 0, nullptr, rules_host, nullptr,
-                     nullptr, nullptr, nullptr, ngram_host);
-}
-
-int dots_bench_select_tokens_ngram(DotsEngine* e, const float* logits_dev, int B, int V, const DotsSamplingParams* params_host, const DotsLogitRules* rules_host,
-                                   const DotsNgramRule* ngram_host, const int32_t* hist_dev, const int32_t* hist_lens_dev, int hist_stride,
-                                   const int32_t* n_prompt_dev, int iters, float* ms_out) {
-    if (!ms_out || iters < 1 || !rules_host || !ngram_host) return e ? e->fail(DOTS_E_INVALID, "bad bench_select_tokens arguments") : DOTS_E_INVALID;
-    return select_op(e, logits_dev, B, V, params_host, hist_dev, hist_lens_dev, hist_stride, n_prompt_dev, nullptr, 2, iters, ms_out, rules_host, nullptr,
-                     nullptr, nullptr, nullptr, ngram_host);
-}
-
-}  // extern "C"
-
-namespace {
-// dots_op_logprobs / dots_bench_logprobs: the two logprob kernels over caller logits, every row at position 0 of its own output row.
-// which 0 = both kernels, 1 = partial only, 2 = final only; iters > 0 = replays between two events, *ms = mean time of one replay.
-int logprobs_op(DotsEngine* e, const float* logits_dev, int B, int V, int ld, const int32_t* top_n_host, const int32_t* chosen_dev,
-                float* tok_lp_dev, int32_t* top_ids_dev, float* top_lp_dev, int which, int iters, float* ms) {
-    if (!e || !logits_dev || B < 1 || B > DOTS_MAX_BATCH || V < 1 || V > LP_MAX_V || ld < V || !top_n_host || which < 0 || which > 2)
-        return e ? e->fail(DOTS_E_INVALID, "bad logprobs arguments") : DOTS_E_INVALID;
-    for (int b = 0; b < B; ++b)
-        if (top_n_host[b] < -1 || top_n_host[b] > DOTS_MAX_TOP_LOGPROBS) return e->fail(DOTS_E_INVALID, "top_n of row %d not in [-1, %d]", b, DOTS_MAX_TOP_LOGPROBS);
-    CK(hipSetDevice(e->device));
-    Scratch sc(e);
-    const size_t K = DOTS_MAX_TOP_LOGPROBS;
-    int32_t *tn = nullptr, *pi = nullptr, *pos = nullptr, *cho = nullptr, *ids = nullptr;
-    float *ms_p = nullptr, *pv = nullptr, *tok = nullptr, *top = nullptr;
-    CK(sc.get(&tn, B));
-    CK(sc.get(&ms_p, (size_t)B * LP_CHUNKS * 2));
-    CK(sc.get(&pv, (size_t)B * LP_CHUNKS * K));
-    CK(sc.get(&pi, (size_t)B * LP_CHUNKS * K));
-    CK(sc.get(&pos, B));
-    if (!chosen_dev) { CK(sc.get(&cho, B)); chosen_dev = cho; }           // timing: token 0 of every row
-    if (!tok_lp_dev) { CK(sc.get(&tok, B)); CK(sc.get(&ids, (size_t)B * K)); CK(sc.get(&top, (size_t)B * K)); tok_lp_dev = tok; top_ids_dev = ids; top_lp_dev = top; }
-    CK(hipMemcpyAsync(tn, top_n_host, B * 4, hipMemcpyHostToDevice, e->stream));
-    const LogprobState ls{tn, nullptr, nullptr, nullptr, chosen_dev, ms_p, pv, pi, pos, tok_lp_dev, top_ids_dev, top_lp_dev, 1};
-    auto run = [&](int w) -> hipError_t {
-        hipError_t r = hipSuccess;
-        if (w != 2) r = launch_logprob_partial(e->stream, logits_dev, V, ld, B, ls);
-        if (r == hipSuccess && w != 1) r = launch_logprob_final(e->stream, logits_dev, V, ld, B, ls);
-        return r;
-    };
-    if (iters <= 0) {
-        CK(run(0));
-        CK(hipStreamSynchronize(e->stream));
-        return DOTS_OK;
-    }
-    for (int i = 0; i < 3; ++i) CK(run(0));                              // warm-up; also leaves the partials the final kernel reads
-    hipEvent_t t0 = nullptr, t1 = nullptr;
-    CK(hipEventCreate(&t0));
-    CK(hipEventCreate(&t1));
-    hipError_t r = hipEventRecord(t0, e->stream);
-    for (int i = 0; i < iters && r == hipSuccess; ++i) r = run(which);
-    if (r == hipSuccess) r = hipEventRecord(t1, e->stream);
-    if (r == hipSuccess) r = hipEventSynchronize(t1);
-    float total = 0.f;
-    if (r == hipSuccess) r = hipEventElapsedTime(&total, t0, t1);
-    hipEventDestroy(t0);
-    hipEventDestroy(t1);
-    CK(r);
-    *ms = total / iters;
-    return DOTS_OK;
-}
-}  // namespace
-
-extern "C" {
-int dots_op_ngram_draft(DotsEngine* e, const int32_t* hist_dev, const int32_t* hist_lens_dev, int hist_stride, int B, int k, int min_n, int max_n,
-                        int32_t* drafts_dev, int32_t* n_drafts_dev) {
-    if (!e || !hist_dev || !hist_lens_dev || !drafts_dev || !n_drafts_dev) return e ? e->fail(DOTS_E_INVALID, "null argument") : DOTS_E_INVALID;
-    if (B < 1 || B > DOTS_MAX_BATCH || hist_stride < 1 || k < 1 || k > DOTS_MAX_SPEC_DRAFTS || min_n < 1 || max_n < min_n || max_n > DOTS_MAX_NGRAM_SIZE)
-        return e->fail(DOTS_E_INVALID, "ngram_draft: B in [1, %d], k in [1, %d], 1 <= min_n <= max_n <= %d", DOTS_MAX_BATCH, DOTS_MAX_SPEC_DRAFTS, DOTS_MAX_NGRAM_SIZE);
-    CK(hipSetDevice(e->device));
-    CK(launch_ngram_draft(e->stream, hist_dev, hist_lens_dev, hist_stride, nullptr, nullptr, nullptr, 1, B, k, min_n, max_n, drafts_dev, k, n_drafts_dev));
-    CK(hipStreamSynchronize(e->stream));
-    return DOTS_OK;
-}
-
-int dots_op_logprobs(DotsEngine* e, const float* logits_dev, int B, int V, int ld, const int32_t* top_n_host, const int32_t* chosen_dev,
-                     float* tok_lp_dev, int32_t* top_ids_dev, float* top_lp_dev) {
-    if (!chosen_dev || !tok_lp_dev || !top_ids_dev || !top_lp_dev) return e ? e->fail(DOTS_E_INVALID, "bad logprobs arguments") : DOTS_E_INVALID;
-    return logprobs_op(e, logits_dev, B, V, ld, top_n_host, chosen_dev, tok_lp_dev, top_ids_dev, top_lp_dev, 0, 0, nullptr);
-}
-
-int dots_bench_logprobs(DotsEngine* e, const float* logits_dev, int B, int V, int ld, const int32_t* top_n_host, int which, int iters,
-                        float* ms_out) {
-    if (!ms_out || iters < 1) return e ? e->fail(DOTS_E_INVALID, "bad bench_logprobs arguments") : DOTS_E_INVALID;
-    return logprobs_op(e, logits_dev, B, V, ld, top_n_host, nullptr, nullptr, nullptr, nullptr, which, iters, ms_out);
-}
-
 }  // extern "C"

@@ -250,7 +250,7 @@ hipError_t launch_stop_fork_rows(hipStream_t s, RowStop* table, int src, const i
 // [DOTS_MAX_SPEC_DRAFTS], n_draft [DOTS_MAX_BATCH]), the expanded row arrays of the step (tokens / ctx_len [DOTS_MAX_BATCH], block_table
 // [DOTS_MAX_BATCH][max_pages]), n_live [DOTS_MAX_BATCH] (draft rows of slot b this step verifies; -1: the slot takes no step) and the
 // counters stats [DOTS_MAX_BATCH + 1][3] (steps, drafted, accepted; the last row holds the totals).
-// cls [DOTS_MAX_BATCH]: the speculation class of every row (SpecRow), a host fact (engine.hip spec_row_class: the row's stage features, its
+// cls [DOTS_MAX_BATCH]: the speculation class of every row (SpecRow), a host fact (rows.hip spec_row_class: the row's stage features, its
 // parameters, its logprobs and dots_set_speculation_rows) that the stream-ordered row setters write, so it holds inside captured chunks.
 // The kernels ask nothing else about a row; while engine_greedy == 0 (an engine-wide temperature) no row verifies a draft whatever its class.
 // cand [DOTS_MAX_BATCH][DOTS_MAX_SPEC_DRAFTS]: the candidate tokens of the live draft rows of SPEC_ROW_DRAW slots (spec_draw_kernel);
@@ -346,7 +346,7 @@ hipError_t launch_bf16q_to_fp8(hipStream_t s, const bf16_t* src, uint8_t* dst, i
 hipError_t launch_gemm_fp8(hipStream_t s, const uint8_t* Aq, const float* rowscale, const uint8_t* Wq, const float* colscale, const bf16_t* bias,
                            const bf16_t* R, void* C, int64_t M, int N, int K, int ldc, int epi);
 bool gemm_fp8_supports(int N, int K);
-// ---- engine.hip helper kernels
+// ---- weights.hip helper kernels
 hipError_t launch_pack_w13(hipStream_t s, const bf16_t* gate, const bf16_t* up, bf16_t* out, int I, int K);
 hipError_t launch_convert_to_bf16(hipStream_t s, const void* src, int dtype, bf16_t* dst, int64_t n);
 

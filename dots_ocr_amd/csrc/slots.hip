@@ -1,0 +1,396 @@
+// Sequence slots of the dots.ocr engine: the host side of the paged KV pool and the continuous-batching C ABI (prefill into free slots,
+// fork, decode chunks, poll / read / release).
+#include "engine.h"
+
+namespace engine {
+// ---- KV page allocator (host side; the kernels only ever see the block table)
+hipError_t upload_table_row(DotsEngine* e, int slot) {
+    return hipMemcpyAsync(e->block_table + (size_t)slot * e->max_pages, e->hp_table.data() + (size_t)slot * e->max_pages, (size_t)e->max_pages * 4,
+                          hipMemcpyHostToDevice, e->stream);
+}
+// the slot lets go of every page its row names; a page goes back to the free list when its last holder lets go (dots_slots_fork shares pages)
+void release_pages(DotsEngine* e, int slot) {
+    auto& mine = e->slot_pages[slot];
+    for (auto it = mine.rbegin(); it != mine.rend(); ++it)
+        if (--e->page_refs[*it] == 0) e->free_pages.push_back(*it);
+    mine.clear();
+    std::fill(e->hp_table.begin() + (size_t)slot * e->max_pages, e->hp_table.begin() + (size_t)(slot + 1) * e->max_pages, e->n_pool_pages);
+}
+// pages for `tokens` positions of the sequence in `slot` (it holds none yet); false: the pool cannot serve them
+bool reserve_pages(DotsEngine* e, int slot, int tokens) {
+    const int need = (tokens + 63) / 64;
+    if (need > (int)e->free_pages.size() || need > e->max_pages) return false;
+    auto& mine = e->slot_pages[slot];
+    for (int p = 0; p < need; ++p) {
+        mine.push_back(e->free_pages.back());
+        e->free_pages.pop_back();
+        e->page_refs[mine.back()] = 1;
+        e->hp_table[(size_t)slot * e->max_pages + p] = mine.back();
+    }
+    return true;
+}
+
+namespace {
+// On-demand growth (continuous batching): make the sequence in `slot` own pages for `tokens` positions; returns the positions its pages
+// cover afterwards (< tokens when the pool ran dry).  *changed: the block-table row has to be uploaded.
+int grow_pages(DotsEngine* e, int slot, int tokens, bool* changed) {
+    auto& mine = e->slot_pages[slot];
+    const int need = std::min((tokens + 63) / 64, e->max_pages);
+    while ((int)mine.size() < need && !e->free_pages.empty()) {
+        e->hp_table[(size_t)slot * e->max_pages + mine.size()] = e->free_pages.back();
+        mine.push_back(e->free_pages.back());
+        e->page_refs[mine.back()] = 1;
+        e->free_pages.pop_back();
+        *changed = true;
+    }
+    return (int)mine.size() * 64;
+}
+}  // namespace
+
+// tokens a slot sequence reserves at admission: its prompt plus the first page-worth of generated tokens (the rest on demand)
+constexpr int KV_ADMIT_AHEAD = 64;
+int admit_tokens(const DotsEngine* e, int prompt, int max_new) { return std::min(prompt + std::min(max_new, KV_ADMIT_AHEAD), e->cfg.max_seq_len); }
+}  // namespace engine
+
+using namespace engine;
+extern "C" {
+// ---------------------------------------------------------------------------------- continuous batching
+int dots_set_eos(DotsEngine* e, const int32_t* eos_ids, int n_eos) {
+    if (!e) return DOTS_E_INVALID;
+    if (n_eos < 0 || n_eos > 16 || (n_eos && !eos_ids)) return e->fail(DOTS_E_INVALID, "n_eos must be in [0,16]");
+    CK(hipSetDevice(e->device));
+    if (n_eos) CK(hipMemcpyAsync(e->eos_ids, eos_ids, n_eos * 4, hipMemcpyHostToDevice, e->stream));
+    CK(hipStreamSynchronize(e->stream));
+    e->n_eos = n_eos;
+    std::copy(eos_ids, eos_ids + n_eos, e->h_eos);
+    return DOTS_OK;
+}
+
+int dots_slots_prefill(DotsEngine* e, const int32_t* slots, int n, const int32_t* input_ids, const int32_t* prompt_lens,
+                       const int32_t* max_new_tokens) {
+    if (!e) return DOTS_E_INVALID;
+    if (!e->finalized) return e->fail(DOTS_E_STATE, "weights not finalized");
+    if (!slots || !input_ids || !prompt_lens || !max_new_tokens) return e->fail(DOTS_E_INVALID, "null argument");
+    CK(hipSetDevice(e->device));
+    return prefill(e, input_ids, prompt_lens, n, slots, max_new_tokens);
+}
+
+// Parallel sampling: n free slots become copies of the freshly prefilled sequence in src_slot.  Everything is validated and
+// counted before anything changes; the children then share the source's full prompt pages (reference counts), get a copy of its tail page
+// and select their own first token from the source's last-position logits.
+int dots_slots_fork(DotsEngine* e, int src_slot, const int32_t* dst_slots, int n) {
+    if (!e) return DOTS_E_INVALID;
+    if (!e->finalized) return e->fail(DOTS_E_STATE, "weights not finalized");
+    if (!dst_slots || n < 1 || n >= DOTS_MAX_BATCH) return e->fail(DOTS_E_INVALID, "dots_slots_fork: n must be in [1, %d) and dst_slots given", DOTS_MAX_BATCH);
+    const DotsConfig& c = e->cfg;
+    const int mb = c.max_batch, V = c.vocab_size;
+    if (src_slot < 0 || src_slot >= mb) return e->fail(DOTS_E_INVALID, "source slot %d out of range [0, %d)", src_slot, mb);
+    const auto fresh = std::find(e->fresh_slots.begin(), e->fresh_slots.end(), src_slot);
+    if (!e->slot_mode || !e->slot_active[src_slot] || fresh == e->fresh_slots.end())
+        return e->fail(DOTS_E_STATE, "slot %d cannot be forked: only a sequence of the most recent dots_slots_prefill, before any decode step", src_slot);
+    const int usable = e->spec_k ? mb / (e->spec_k + 1) : mb;
+    for (int i = 0; i < n; ++i) {
+        const int d = dst_slots[i];
+        if (d < 0 || d >= mb) return e->fail(DOTS_E_INVALID, "slot %d out of range [0, %d)", d, mb);
+        if (d >= usable)
+            return e->fail(DOTS_E_CAPACITY, "slot %d is not usable while speculating: with %d drafts only slots [0, %d) are", d, e->spec_k, usable);
+        if (d == src_slot) return e->fail(DOTS_E_INVALID, "slot %d is the source of the fork", d);
+        if (e->slot_active[d]) return e->fail(DOTS_E_STATE, "slot %d is occupied", d);
+        for (int a = 0; a < i; ++a)
+            if (dst_slots[a] == d) return e->fail(DOTS_E_INVALID, "slot %d listed twice", d);
+    }
+    // ---- page arithmetic: the children name the source's floor(L / 64) full prompt pages and own the rest of the admission reserve
+    const int L = e->slot_prompt[src_slot], max_new = e->slot_limit[src_slot] - L;
+    const int shared = L / 64, own = (admit_tokens(e, L, max_new) + 63) / 64 - shared;          // own >= 1: the reserve is at least L + 1 tokens
+    const auto& src_pages = e->slot_pages[src_slot];
+    if ((int)src_pages.size() < shared + (L % 64 ? 1 : 0)) return e->fail(DOTS_E_STATE, "slot %d does not hold its prompt pages", src_slot);
+    if (shared + own > e->max_pages || (int64_t)n * own > (int64_t)e->free_pages.size())
+        return e->fail(DOTS_E_CAPACITY, "KV pool exhausted: %d forked sequences need %d pages of 64 tokens each, %d of %d are free", n, own,
+                       (int)e->free_pages.size(), e->n_pool_pages);
+    CK(hipSetDevice(e->device));
+    hipStream_t s = e->stream;
+    // ---- from here on the call changes state; a failed launch gives the children's pages back (the slots are not marked occupied yet)
+    struct ForkGuard {
+        DotsEngine* e; const int32_t* dst; int n; bool armed = true;
+        ~ForkGuard() {
+            if (!armed) return;
+            for (int i = 0; i < n; ++i) { release_pages(e, dst[i]); (void)upload_table_row(e, dst[i]); }
+        }
+    } guard{e, dst_slots, n};
+    int32_t stage[3 * DOTS_MAX_BATCH] = {0}, sel_new[DOTS_MAX_BATCH] = {0};
+    int rows = 0;
+    for (int i = 0; i < n; ++i) {
+        const int d = dst_slots[i];
+        auto& mine = e->slot_pages[d];
+        for (int p = 0; p < shared; ++p) {                 // one more holder of a page nobody writes any more: every row appends at positions >= L
+            mine.push_back(src_pages[p]);
+            e->page_refs[src_pages[p]] += 1;
+            e->hp_table[(size_t)d * e->max_pages + p] = src_pages[p];
+        }
+        bool changed = false;
+        grow_pages(e, d, (shared + own) * 64, &changed);   // cannot fall short: counted above
+        CK(upload_table_row(e, d));
+        stage[i] = d;
+        stage[DOTS_MAX_BATCH + i] = mine[shared];
+        sel_new[d] = 1;
+        rows = std::max(rows, d + 1);
+    }
+    stage[2 * DOTS_MAX_BATCH] = L - 1;
+    CK(hipMemcpyAsync(e->fk_dev, stage, sizeof(stage), hipMemcpyHostToDevice, s));
+    const int32_t *fk_dst = e->fk_dev, *fk_pages = e->fk_dev + DOTS_MAX_BATCH, *fk_last = e->fk_dev + 2 * DOTS_MAX_BATCH;
+    // the tail page: behind the prefill's page writers on the same stream; its source is written by nobody until the source's first step
+    if (L % 64) {
+        const size_t page_bytes = (size_t)c.num_kv_heads * 2 * 8192 * (e->kv8 ? 1 : 2);
+        CK(launch_kv_fork_pages(s, e->pool, e->pool_layer_elems * 2, page_bytes, c.num_layers, src_pages[shared], fk_pages, n));
+    }
+    // ---- per-row decode state, as the prefill sets it
+    const int32_t cap = max_new;
+    for (int i = 0; i < n; ++i) {
+        const int d = dst_slots[i];
+        CK(hipMemcpyAsync(e->ctx_len + d, &L, 4, hipMemcpyHostToDevice, s));
+        CK(hipMemcpyAsync(e->d_max_len + d, &cap, 4, hipMemcpyHostToDevice, s));
+        CK(hipMemsetAsync(e->out_lens + d, 0, 4, s));
+        CK(hipMemsetAsync(e->finished + d, 0, 4, s));
+        if (e->sp_ndraft) {
+            CK(hipMemsetAsync(e->sp_ndraft + d, 0, 4, s));
+            CK(hipMemsetAsync(e->sp_stats + (size_t)d * 3, 0, 3 * sizeof(unsigned long long), s));
+        }
+        RET(clear_lp_row(e, d));
+        // the source's last-position logits row (rows of d_logits are slots; nothing has run over them since the prefill)
+        CK(hipMemcpyAsync(e->d_logits + (size_t)d * V, e->d_logits + (size_t)src_slot * V, (size_t)V * 4, hipMemcpyDeviceToDevice, s));
+    }
+    CK(hipMemcpyAsync(e->d_sel_new, sel_new, sizeof(sel_new), hipMemcpyHostToDevice, s));
+    if (e->pen_cnt) {
+        // prompt-presence bits and zeroed counts of every child from the source's packed prompt, still in p_src: one sequence per launch,
+        // so that each starts at the source's first token
+        const int b = (int)(fresh - e->fresh_slots.begin());
+        const int32_t* src0 = e->p_src + (b ? e->hp_last[b - 1] + 1 : 0);
+        for (int i = 0; i < n; ++i) CK(launch_pen_prompt(s, src0, fk_last, fk_dst + i, 1, c.image_token_id, V, e->pen_cnt, e->pen_seen));
+    }
+    if (e->stage.rows(ROW_GUIDE) > 0) CK(launch_guide_reset_rows(s, e->d_guides, fk_dst, n));
+    if (e->stage.has(src_slot, ROW_STOP)) {
+        // the children inherit the source's stop strings (automaton and min_tokens) at the root with no hit: one launch writes all their entries
+        for (int i = 0; i < n; ++i) RET(hold_row_stop(e, dst_slots[i], e->row_stop[src_slot] - 1, e->row_stop_min[src_slot]));
+        CK(launch_stop_fork_rows(s, e->d_stop, src_slot, fk_dst, n));
+    } else if (e->stage.rows(ROW_STOP) > 0)
+        CK(launch_stop_reset_rows(s, e->d_stop, fk_dst, n));
+    CK(hipStreamSynchronize(s));                           // L, cap and the staged arrays are stack variables
+    // ---- the children's first tokens: the selection stage over a mask of the children only
+    e->B_sel = rows;
+    e->sel_now = e->d_sel_new;
+    RET(select_tokens(e, 0));
+    for (int i = 0; i < n; ++i) {
+        const int d = dst_slots[i];
+        e->slot_active[d] = 1;
+        e->slot_limit[d] = L + max_new;
+        e->slot_prompt[d] = L;
+        e->slot_ctx_ub[d] = L;
+        e->slot_done[d] = 0;
+    }
+    e->sel_dirty = true;
+    guard.armed = false;
+    return DOTS_OK;
+}
+
+// Enter slot mode with every slot free and every KV page in the pool (whatever a static batch or an abandoned serving loop left behind).
+int dots_slots_reset(DotsEngine* e) {
+    if (!e) return DOTS_E_INVALID;
+    if (!e->finalized) return e->fail(DOTS_E_STATE, "weights not finalized");
+    CK(hipSetDevice(e->device));
+    hipStream_t s = e->stream;
+    if (e->pref_pending) {                               // a prefetched tower nobody took (an abandoned serving loop): drop it
+        if (!e->pref_deferred) CK(hipStreamWaitEvent(s, e->ev_vis_ready, 0));
+        e->pref_pending = e->pref_deferred = false;
+    }
+    for (int b = 0; b < (int)e->slot_pages.size(); ++b) release_pages(e, b);
+    e->fresh_slots.clear();
+    CK(hipMemcpyAsync(e->block_table, e->hp_table.data(), e->hp_table.size() * 4, hipMemcpyHostToDevice, s));
+    std::fill(e->slot_active, e->slot_active + DOTS_MAX_BATCH, 0);
+    CK(hipMemsetAsync(e->ctx_len, 0, e->cfg.max_batch * 4, s));
+    CK(hipMemsetAsync(e->out_lens, 0, e->cfg.max_batch * 4, s));
+    CK(hipMemsetAsync(e->finished, 0, e->cfg.max_batch * 4, s));
+    // no row carries any feature: the features' row tables (in RowFeature order; the own flags stand for the parameters), then the host record
+    const struct { void* table; size_t row_bytes; } feature_tables[ROW_FEATURES] = {
+        {e->d_row_own, 4}, {e->d_rules, sizeof(RowRules)}, {e->d_guides, sizeof(RowGuide)}, {e->d_ngram, sizeof(RowNgram)}, {e->d_stop, sizeof(RowStop)}};
+    for (const auto& t : feature_tables)
+        if (t.table) CK(hipMemsetAsync(t.table, 0, DOTS_MAX_BATCH * t.row_bytes, s));
+    e->stage.reset();
+    std::fill(e->row_guide, e->row_guide + DOTS_MAX_BATCH, 0);
+    for (auto& g : e->guides) g.rows = 0;
+    std::fill(e->row_stop, e->row_stop + DOTS_MAX_BATCH, 0);
+    std::fill(e->row_stop_min, e->row_stop_min + DOTS_MAX_BATCH, 0);
+    for (auto& a : e->stops) a.rows = 0;
+    if (e->d_row_lp) CK(hipMemsetAsync(e->d_row_lp, 0xFF, DOTS_MAX_BATCH * 4, s));
+    std::fill(e->row_lp, e->row_lp + DOTS_MAX_BATCH, -1);
+    e->n_lp = 0;
+    if (e->sp_ndraft) CK(hipMemsetAsync(e->sp_ndraft, 0, DOTS_MAX_BATCH * 4, s));
+    if (e->sp_cls) CK(hipMemsetAsync(e->sp_cls, 0, DOTS_MAX_BATCH * 4, s));         // SPEC_ROW_ARGMAX: no row carries anything
+    CK(hipStreamSynchronize(s));
+    e->slot_mode = true;
+    e->sel_dirty = true;
+    e->B = 0;
+    return DOTS_OK;
+}
+
+int dots_slots_decode(DotsEngine* e, int n_steps) {
+    if (!e) return DOTS_E_INVALID;
+    if (!e->slot_mode) return e->fail(DOTS_E_STATE, "no slot has been prefilled");
+    if (n_steps < 1) return e->fail(DOTS_E_INVALID, "n_steps must be >= 1");
+    CK(hipSetDevice(e->device));
+    hipStream_t s = e->stream;
+    int rows = 0;
+    for (int b = 0; b < e->cfg.max_batch; ++b)
+        if (e->slot_active[b]) rows = b + 1;
+    if (!rows) return e->fail(DOTS_E_STATE, "every slot is free");
+    e->fresh_slots.clear();                                 // the step overwrites the logits a fork selects from (dots_slots_fork)
+    if (e->sel_dirty) {
+        int32_t sel[DOTS_MAX_BATCH];
+        for (int b = 0; b < DOTS_MAX_BATCH; ++b) sel[b] = e->slot_active[b];
+        CK(hipMemcpyAsync(e->d_sel, sel, DOTS_MAX_BATCH * 4, hipMemcpyHostToDevice, s));
+        e->sel_dirty = false;
+    }
+    // ---- paged KV: every running sequence gets the pages the next n_steps positions need, now.  Pool dry: the sequence keeps what it
+    // has and its generation cap is lowered to what its pages hold — it finishes there with "length", like HF generate at the
+    // context capacity (an admission policy that leaves head-room makes this rare: dots_ocr_amd/scheduler.py).
+    // A speculating step may advance a row by spec_k + 1 positions and writes KV that far ahead: pages and the host's bound on the
+    // context count n_steps x (k + 1) (dots_slots_poll brings the bound back to the row's true context)
+    n_steps *= e->spec_k + 1;
+    for (int b = 0; b < rows; ++b) {
+        if (!e->slot_active[b] || e->slot_done[b]) continue;
+        // A step at context c writes KV position c and brings the sequence to c + 2 tokens, so n_steps more steps need positions
+        // [0, ctx + n_steps), and a sequence limited to slot_limit tokens never writes beyond position slot_limit - 2.
+        int want = std::min(e->slot_ctx_ub[b] + n_steps, e->slot_limit[b] - 1);
+        bool changed = false;
+        const int have = grow_pages(e, b, want, &changed);
+        if (changed) CK(upload_table_row(e, b));
+        if (have < want && e->spec_k) {
+            // before a speculating row is capped, its bound becomes its true context: steps that accepted fewer than k drafts left it too high
+            int32_t ctx = 0;
+            CK(hipMemcpyAsync(&ctx, e->ctx_len + b, 4, hipMemcpyDeviceToHost, s));
+            CK(hipStreamSynchronize(s));
+            e->slot_ctx_ub[b] = std::min(e->slot_ctx_ub[b], (int)ctx);
+            want = std::min(e->slot_ctx_ub[b] + n_steps, e->slot_limit[b] - 1);
+        }
+        if (have < want) {
+            // Positions [0, have) exist: the last step the row may take is the one at context have - 1, which leaves it with have + 1
+            // tokens.  commit_token finishes a row when a step brings it to its cap — so a row that already sits AT context `have`
+            // (the pool ran dry exactly on its page boundary) must be stopped here: its next step would write position
+            // `have` through a block-table entry it does not own (the scratch page every idle row writes) and read it back.
+            e->slot_limit[b] = have + 1;
+            const int32_t cap = have + 1 - e->slot_prompt[b];               // generated tokens; >= the tokens generated so far
+            static const int32_t one = 1;
+            CK(hipMemcpyAsync(e->d_max_len + b, &cap, 4, hipMemcpyHostToDevice, s));
+            if (have <= e->slot_ctx_ub[b]) CK(hipMemcpyAsync(e->finished + b, &one, 4, hipMemcpyHostToDevice, s));
+            CK(hipStreamSynchronize(s));                                     // `cap` is a stack variable
+            e->kv_capped += 1;
+        }
+        e->slot_ctx_ub[b] = std::min(e->slot_ctx_ub[b] + n_steps, e->slot_limit[b] - 1);
+    }
+    n_steps /= e->spec_k + 1;
+    const int n_splits = splits_for_ctx(e->cfg.max_seq_len);
+    e->B = rows;
+    static const bool use_graph = getenv("DOTS_OCR_NO_GRAPH") == nullptr;
+    // beside a prefetched vision tower (the next admission's: dots_vit_prefetch) the chunk is replayed on the decode partition, with the
+    // half-chip launch plan when the rows allow it — exactly as dots_generate does
+    hipStream_t cur = s;
+    if (use_graph) { int r0 = pick_decode_stream(e, &cur); if (r0 != DOTS_OK) { e->B = 0; return r0; } }
+    const int part = cur != s ? 1 : 0;
+    hipGraphExec_t exec = nullptr;
+    if (use_graph) {
+        int r = step_graph(e, rows, n_splits, 0, &exec, part);
+        if (r != DOTS_OK) { e->B = 0; return r; }
+    }
+    int r = DOTS_OK;
+    for (int i = 0; i < n_steps && r == DOTS_OK; ++i) {
+        if (exec) { if (hipGraphLaunch(exec, cur) != hipSuccess) r = e->fail(DOTS_E_HIP, "hipGraphLaunch failed"); }
+        else r = decode_step_launches(e, n_splits);
+    }
+    if (r == DOTS_OK && e->ev_dec_end && hipEventRecord(e->ev_dec_end, cur) == hipSuccess) ++e->dec_end_seq;      // pick_tower_tail
+    if (r == DOTS_OK) r = chain_streams(e, cur, s);
+    e->B = 0;
+    e->stats.decode_steps += n_steps;
+    return r;
+}
+
+int dots_slots_poll(DotsEngine* e, int32_t* finished, int32_t* out_lens) {
+    if (!e || !finished || !out_lens) return e ? e->fail(DOTS_E_INVALID, "null argument") : DOTS_E_INVALID;
+    CK(hipSetDevice(e->device));
+    const int mb = e->cfg.max_batch;
+    CK(hipMemcpyAsync(finished, e->finished, mb * 4, hipMemcpyDeviceToHost, e->stream));
+    CK(hipMemcpyAsync(out_lens, e->out_lens, mb * 4, hipMemcpyDeviceToHost, e->stream));
+    CK(hipStreamSynchronize(e->stream));
+    for (int b = 0; b < mb; ++b) {
+        if (!e->slot_mode || !e->slot_active[b]) { finished[b] = -1; out_lens[b] = 0; }      // -1: free slot
+        else {
+            if (finished[b]) e->slot_done[b] = 1;                                            // takes no more pages
+            // every issued step has run: the context is prompt + generated - 1 exactly.  A speculating step advances a row by 1 .. k + 1
+            // positions, so dots_slots_decode counts k + 1 per step; without this the bound (and the pages taken ahead) would run away
+            if (e->spec_k) e->slot_ctx_ub[b] = std::min(e->slot_ctx_ub[b], e->slot_prompt[b] + out_lens[b] - 1);
+        }
+    }
+    return DOTS_OK;
+}
+
+int dots_slot_read(DotsEngine* e, int slot, int32_t* out_ids, int capacity, int32_t* n_out) {
+    if (!e || !out_ids || !n_out || capacity < 0) return e ? e->fail(DOTS_E_INVALID, "bad slot_read arguments") : DOTS_E_INVALID;
+    if (!e->slot_mode || slot < 0 || slot >= e->cfg.max_batch || !e->slot_active[slot]) return e->fail(DOTS_E_STATE, "slot %d is not occupied", slot);
+    CK(hipSetDevice(e->device));
+    int32_t n = 0;
+    CK(hipMemcpyAsync(&n, e->out_lens + slot, 4, hipMemcpyDeviceToHost, e->stream));
+    CK(hipStreamSynchronize(e->stream));
+    *n_out = n;
+    const int take = std::min<int>(n, capacity);
+    if (take > 0) {
+        CK(hipMemcpyAsync(out_ids, e->out_ids + (size_t)slot * e->cfg.max_seq_len, (size_t)take * 4, hipMemcpyDeviceToHost, e->stream));
+        CK(hipStreamSynchronize(e->stream));
+    }
+    return DOTS_OK;
+}
+
+int dots_slot_release(DotsEngine* e, int slot) {
+    if (!e) return DOTS_E_INVALID;
+    if (!e->slot_mode || slot < 0 || slot >= e->cfg.max_batch || !e->slot_active[slot]) return e->fail(DOTS_E_STATE, "slot %d is not occupied", slot);
+    CK(hipSetDevice(e->device));
+    for (int f = 0; f < ROW_FEATURES; ++f) RET(clear_row_feature(e, slot, (RowFeature)f));
+    RET(set_row_lp(e, slot, -1));
+    e->slot_active[slot] = 0;
+    e->sel_dirty = true;
+    CK(hipMemsetAsync(e->ctx_len + slot, 0, 4, e->stream));          // an idle row attends over one key only ...
+    release_pages(e, slot);                                          // ... of the scratch page: its own pages go back to the pool
+    CK(upload_table_row(e, slot));
+    return DOTS_OK;
+}
+
+int dots_kv_pool_info(DotsEngine* e, int32_t* total_pages, int32_t* free_pages) {
+    if (!e || !total_pages || !free_pages) return DOTS_E_INVALID;
+    *total_pages = e->n_pool_pages;
+    *free_pages = (int32_t)e->free_pages.size();
+    return DOTS_OK;
+}
+
+int dots_set_kv_scales(DotsEngine* e, const float* scales_host) {
+    if (!e || !scales_host) return e ? e->fail(DOTS_E_INVALID, "null argument") : DOTS_E_INVALID;
+    const DotsConfig& c = e->cfg;
+    const size_t n = (size_t)c.num_layers * c.num_kv_heads * 2;
+    for (size_t i = 0; i < n; ++i)
+        if (!std::isfinite(scales_host[i]) || !(scales_host[i] > 0.f))
+            return e->fail(DOTS_E_INVALID, "kv scale %zu (layer %zu, kv head %zu, %s) is %g: must be finite and > 0", i, i / (2 * c.num_kv_heads),
+                           (i / 2) % c.num_kv_heads, i % 2 ? "V" : "K", (double)scales_host[i]);
+    // a cached token was quantised with the scales of its time: they are fixed while any sequence holds pages
+    if ((int)e->free_pages.size() != e->n_pool_pages)
+        return e->fail(DOTS_E_STATE, "KV scales cannot change while sequences hold KV pages (%d of %d in use): release them first (dots_slots_reset)",
+                       e->n_pool_pages - (int)e->free_pages.size(), e->n_pool_pages);
+    CK(hipSetDevice(e->device));
+    CK(hipMemcpyAsync(e->kv_scales, scales_host, n * 4, hipMemcpyHostToDevice, e->stream));
+    CK(hipStreamSynchronize(e->stream));
+    return DOTS_OK;
+}
+
+int dots_slot_capacity(DotsEngine* e, int slot, int32_t* pages_owned, int32_t* token_limit) {
+    if (!e || !pages_owned || !token_limit) return DOTS_E_INVALID;
+    if (!e->slot_mode || slot < 0 || slot >= e->cfg.max_batch || !e->slot_active[slot]) return e->fail(DOTS_E_STATE, "slot %d is not occupied", slot);
+    *pages_owned = (int32_t)e->slot_pages[slot].size();
+    *token_limit = e->slot_limit[slot];
+    return DOTS_OK;
+}
+}  // extern "C"

@@ -169,7 +169,7 @@ class ContinuousBatcher:
         return [s for s in range(self.n_slots) if s not in self.running]
 
     # ------------------------------------------------------------------ admission
-    ADMIT_AHEAD = 64                                 # tokens beyond the prompt dots_slots_prefill reserves (engine.hip KV_ADMIT_AHEAD)
+    ADMIT_AHEAD = 64                                 # tokens beyond the prompt dots_slots_prefill reserves (slots.hip KV_ADMIT_AHEAD)
 
     def _admit_pages(self, prompt: int, max_new: int) -> int:
         return (min(prompt + min(int(max_new), self.ADMIT_AHEAD), self.max_seq_len) + 63) // 64

@@ -76,7 +76,7 @@ class FakeSlotEngine:
 
 
 class FakePagedEngine(FakeSlotEngine):
-    """FakeSlotEngine + the paged KV pool of the real engine (engine.hip: reserve at admission, grow per decode chunk, lower the cap when
+    """FakeSlotEngine + the paged KV pool of the real engine (slots.hip: reserve at admission, grow per decode chunk, lower the cap when
     the pool runs dry — pages of P positions allow P + 1 tokens in all)."""
     PAGE = 64
 

@@ -7,6 +7,7 @@ from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
 CSRC = ROOT / "dots_ocr_amd" / "csrc"
+ENGINE_SOURCES = ("engine.h", "engine.hip", "weights.hip", "slots.hip", "rows.hip", "ops.hip")      # the engine's host code
 
 
 def test_row_stage_matches_brute_force_model(tmp_path):
@@ -27,7 +28,10 @@ def test_row_stage_matches_brute_force_model(tmp_path):
 
 def test_engine_keeps_no_second_copy_of_stage_membership():
     """The counters and flag arrays RowStage replaced stay gone from the engine, and so does the hand-written conjunction over them."""
-    src = (CSRC / "engine.hip").read_text()
+    src = "".join((CSRC / f).read_text() for f in ENGINE_SOURCES)
     for gone in ("row_own[", "row_rules[", "row_ngram[", "n_own", "n_rules", "n_guided", "n_ngram", "n_stop_rows"):
         assert not re.search(r"\b" + re.escape(gone), src), gone
     assert not re.search(r"!e->row_\w+\[\w+\]\s*&&", src)
+    # one statement of what the stage launches: the step and the single-kernel entry points both go through launch_row_stage
+    for launcher in ("launch_select_rows(", "launch_ngram_ban(", "launch_guide_mask("):
+        assert src.count(launcher) == 1, launcher

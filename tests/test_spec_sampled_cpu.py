@@ -278,5 +278,5 @@ def test_the_kernels_ask_the_class_array_only():
     spec = (CSRC / "spec.hip").read_text()
     assert not re.search(r"\bsp\.(own|lp)\b", spec) and not re.search(r"\bown\[b\]|\blp\[b\]", spec)
     assert len(re.findall(r"SPEC_ROW_NONE", spec)) >= 2                # spec_live_drafts and the drafter
-    eng = (CSRC / "engine.hip").read_text()
+    eng = "".join((CSRC / f).read_text() for f in ("engine.h", "engine.hip", "weights.hip", "slots.hip", "rows.hip", "ops.hip"))
     assert len(re.findall(r"stage\.speculates\(", eng)) == 1
