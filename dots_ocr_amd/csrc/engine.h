@@ -208,6 +208,22 @@ struct DotsEngine {
     int spec_rows = 0;
     int32_t *sp_cls = nullptr, *sp_cand = nullptr;
     bool row_pen[DOTS_MAX_BATCH] = {false}, row_sampled[DOTS_MAX_BATCH] = {false};
+    // beam search (dots_slots_beam): the groups' host records (B == 0: free), beam_of[row] = group index + 1 of a group row,
+    // n_beam_hi = highest used index + 1 (what a step's group kernels are launched over; 0: a step launches nothing of this), and —
+    // allocated by the first group — the device records, the completed-record buffers, the parents beside out_ids and the logprob
+    // partials of the group rows with the tables (top_n = 2B / sel = 1 on group rows) their partial launch reads
+    struct BeamGroup {
+        int B = 0, L = 0, max_new = 0, done_ub = 0;      // done_ub: bound on the records waiting on the device
+        int slots[DOTS_MAX_BEAMS] = {0};
+        std::vector<BeamDone> done;                      // drained so far
+    };
+    std::vector<BeamGroup> beams;
+    int beam_of[DOTS_MAX_BATCH] = {0};
+    int n_beam_hi = 0;
+    BeamGroupDev* d_beam = nullptr;
+    BeamDone* d_beam_done = nullptr;
+    int32_t *beam_parent = nullptr, *bm_pi = nullptr, *bm_pos = nullptr, *bm_topn = nullptr, *bm_sel = nullptr;
+    float *bm_ms = nullptr, *bm_pv = nullptr;
     int out_cap = 0;                       // row stride of out_ids for the current generation
     bf16_t *d_h = nullptr, *d_q = nullptr, *d_att = nullptr, *d_act = nullptr, *d_xn = nullptr;      // d_xn: normalised rows of batches above 32 rows (decode_b64.hip)
     float* d_part_h = nullptr;                     // [DEC_KSPLIT_PARTS][DOTS_MAX_BATCH][hidden] fp32: the K-quarter sums of a projection above 32 rows (decode_b64.hip)
@@ -234,10 +250,10 @@ struct DotsEngine {
     // table), whether any row holds a guide (guided: the mask kernel and the guides' tables), whether any row carries an n-gram rule (ngram:
     // the ban kernel and its bits), the draft count of a speculating step (spec: 0 = the plain step), whether that step draws the draft
     // rows of sampled slots (draw: the two launches of launch_spec_draw); engine-wide sampling changes drop
-    // the cache (dots_set_sampling), per-row ones live in device memory.  step_key() builds the key from the engine's state: a feature that
+    // the cache (dots_set_sampling), per-row ones live in device memory; beam: the group entries a step's beam kernels run over (0: none).  step_key() builds the key from the engine's state: a feature that
     // changes what a step launches adds a member here and a line there
     struct StepKey {
-        int rows, splits, out_cap, n_eos, part, rowp, lp, rules, guided, ngram, spec, draw;
+        int rows, splits, out_cap, n_eos, part, rowp, lp, rules, guided, ngram, spec, draw, beam;
         bool operator==(const StepKey& o) const { return std::memcmp(this, &o, sizeof(StepKey)) == 0; }
     };
     static_assert(std::has_unique_object_representations_v<StepKey>, "StepKey is compared bytewise: plain ints, no padding");
@@ -353,5 +369,14 @@ int prefill(DotsEngine* e, const int32_t* ids, const int32_t* lens, int B, const
 int decode_step_launches(DotsEngine* e, int n_splits, int part = 0);
 int splits_for_ctx(int max_ctx);
 int step_graph(DotsEngine* e, int rows, int n_splits, int out_cap, hipGraphExec_t* exec, int part = 0);
+// slots.hip
+int grow_pages(DotsEngine* e, int slot, int tokens, bool* changed);
+// beam.hip: beam groups
+int beam_step(DotsEngine* e, int rows);
+int beam_before_decode(DotsEngine* e, int n_steps);
+int beam_release_group(DotsEngine* e, int slot);
+int beam_clear_all(DotsEngine* e);
+// a group row carries no stage feature and no logprobs: the row setters refuse it
+inline bool beam_row(const DotsEngine* e, int row) { return row >= 0 && row < DOTS_MAX_BATCH && e->beam_of[row] != 0; }
 
 }  // namespace engine

@@ -279,6 +279,7 @@ DotsEngine::StepKey step_key(const DotsEngine* e, int rows, int n_splits, int ou
     k.ngram = e->stage.rows(ROW_NGRAM) > 0;
     k.spec = e->slot_mode ? e->spec_k : 0;
     k.draw = spec_draws(e);
+    k.beam = e->slot_mode ? e->n_beam_hi : 0;
     return k;
 }
 
@@ -398,8 +399,10 @@ int prefill(DotsEngine* e, const int32_t* ids, const int32_t* lens, int B, const
     // ---- KV pages: a static batch resets every slot and reserves prompt + generation cap (a closed batch: nothing competes for pages);
     // a slot prefill reserves the prompt plus KV_ADMIT_AHEAD tokens for its own sequences only — the rest is taken page by page as the
     // sequences actually grow (dots_slots_decode).  Entering slot mode returns the pages of the previous static batch first.
-    if (!slots || !e->slot_mode)
+    if (!slots || !e->slot_mode) {
         for (int b = 0; b < (int)e->slot_pages.size(); ++b) release_pages(e, b);
+        RET(beam_clear_all(e));
+    }
     const bool whole_table = !slots || !e->slot_mode;
     {
         int need = 0;
@@ -557,6 +560,7 @@ int decode_step_launches(DotsEngine* e, int n_splits, int part) {
     e->B_sel = rows;
     e->sel_now = e->d_sel;
     RET(select_tokens(e, 1));
+    if (e->slot_mode && e->n_beam_hi > 0) RET(beam_step(e, rows));      // the beam groups' rows: masked out of the selection above
     if (spec_k) {
         // the selection stage committed row 0 of every slot; the accept walk commits what the drafts got right, then the drafter reads
         // the grown output

@@ -326,6 +326,42 @@ hipError_t launch_logprob_partial(hipStream_t s, const float* logits, int V, int
 hipError_t launch_logprob_final(hipStream_t s, const float* logits, int V, int ld, int B, const LogprobState& st);
 // table[row] = top_n, in stream order
 hipError_t launch_set_row_lp(hipStream_t s, int32_t* table, int row, int top_n);
+// ---- beam.hip: beam search over shared KV pages
+// A group of B beams lives in B slots, in group order (beam i = slots[i]).  BeamGroupDev is its device record (B == 0: the entry is free):
+// first = floor(L / 64), the first block-table entry the beams do not share with the prompt; cum the beams' cumulative log-probabilities
+// (-inf: dead); spare the page each beam holds outside its table row; act / par / copy_src / copy_dst what one step's select kernel hands
+// the reorder kernel and that one the copy kernel (copy_dst < 0: beam j copies nothing); n_done the completed records waiting in the
+// group's BEAM_DONE_CAP entries of BeamState::done.
+#ifndef DOTS_MAX_BEAMS
+#define DOTS_MAX_BEAMS 8
+#endif
+constexpr int BEAM_MAX_GROUPS = DOTS_MAX_BATCH / 2;
+constexpr int BEAM_DONE_CAP = 4096;
+struct BeamGroupDev {
+    int32_t B, first, n_done, act;
+    int32_t slots[DOTS_MAX_BEAMS];
+    float cum[DOTS_MAX_BEAMS];
+    int32_t spare[DOTS_MAX_BEAMS], par[DOTS_MAX_BEAMS], copy_src[DOTS_MAX_BEAMS], copy_dst[DOTS_MAX_BEAMS];
+};
+struct BeamDone { int32_t step, parent, id; float s; };     // a completed candidate: an EOS id out of beam `parent` at `step`, s = its cum
+// groups [BEAM_MAX_GROUPS], done [BEAM_MAX_GROUPS][BEAM_DONE_CAP], parent [rows][StepState::out_stride] (beside out_ids: -1 = a dead beam);
+// part_*: the logprob partials of the group rows (launch_logprob_partial with top_n = 2B)
+struct BeamState {
+    BeamGroupDev* groups;
+    BeamDone* done;
+    int32_t* parent;
+    const float *part_ms, *part_v;
+    const int32_t* part_i;
+};
+// The selection of groups [g0, g0 + n): one workgroup per group merges the live beams' 2B best (lp, id) pairs, records the EOS candidates,
+// commits the B best others (token, parent, cum, out_lens, ctx_len when st.advance_ctx, finished at the cap) and — reorder != 0 — arms the
+// reorder of this step.  A group whose rows are finished is left alone.
+hipError_t launch_beam_select(hipStream_t s, const BeamState& bs, const StepState& st, int g0, int n, int reorder);
+// The mid-generation fork of groups [0, n), after launch_beam_select of the same step: every beam's block-table entries [first, g) become
+// its parent's (g = the page of the position just written), its tail a copy of the parent's tail page in its own spare page, in every
+// layer; the old tail becomes the spare.  A beam that is its own only child keeps its tail.  Bytes only: page_bytes of a bf16 or fp8 page.
+hipError_t launch_beam_reorder(hipStream_t s, const BeamState& bs, int n, const int32_t* ctx_len, int32_t* block_table, int max_pages, void* pool,
+                               size_t layer_bytes, size_t page_bytes, int layers);
 // row-major [rows, K] -> MFMA fragment order (decode.hip): 16-row tiles x K/32 chunks of 1 KiB
 hipError_t launch_pack_frag(hipStream_t s, const bf16_t* src, bf16_t* dst, int64_t rows, int K);
 // fused qkv weight [(Hq + 2 Hkv) * 128, K]: as launch_pack_frag, q / k head rows permuted so that a 16-row tile holds whole RoPE pairs

@@ -13,6 +13,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "logprobs_dev.h"
 
 namespace {
 
@@ -20,21 +21,7 @@ constexpr int LP_THREADS = 256;
 constexpr int LP_VEC = LP_MAX_CHUNK / (4 * LP_THREADS);         // float4 loads per thread (4)
 constexpr int LP_REG = 4 * LP_VEC;                              // values per thread held in registers (16)
 static_assert(LP_REG <= 32, "one availability bit per register value");
-constexpr int LP_NONE = 0x7fffffff;                             // index of "no candidate"
-
 DEVI int lp_chunk_len(int V) { return (((V + LP_CHUNKS - 1) / LP_CHUNKS) + 3) & ~3; }
-
-// (va, ia) ranks before (vb, ib): larger value, then lower index (the arg max tie rule).  NaN never ranks before anything.
-DEVI bool lp_before(float va, int ia, float vb, int ib) { return va > vb || (va == vb && ia < ib); }
-
-DEVI void lp_wave_best(float& v, int& i) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(v, o, 64);
-        const int oi = __shfl_xor(i, o, 64);
-        if (lp_before(ov, oi, v, i)) { v = ov; i = oi; }
-    }
-}
 
 __global__ __launch_bounds__(LP_THREADS) void logprob_partial_kernel(const float* __restrict__ logits, int V, int ld, LogprobState st) {
     __shared__ float red[LP_THREADS / 64];
@@ -127,38 +114,20 @@ __global__ __launch_bounds__(LP_THREADS) void logprob_partial_kernel(const float
 }
 
 __global__ __launch_bounds__(64) void logprob_final_kernel(const float* __restrict__ logits, int V, int ld, LogprobState st) {
-    __shared__ float cv[LP_CHUNKS][DOTS_MAX_TOP_LOGPROBS];
-    __shared__ int ci[LP_CHUNKS][DOTS_MAX_TOP_LOGPROBS];
-    __shared__ float terms[LP_CHUNKS];
-    __shared__ float lse_s;
+    __shared__ LpFinalLds l;
     const int b = blockIdx.x, c = threadIdx.x;
     if (st.sel && !st.sel[b]) return;
     const int n = st.top_n[b];
     if (n < 0) return;
     const int pos = st.pos[b];
     if (pos < 0 || pos >= st.stride) return;                   // the row was finished before this step: its token is not appended
-    const float mc = st.part_ms[((size_t)b * LP_CHUNKS + c) * 2], sc = st.part_ms[((size_t)b * LP_CHUNKS + c) * 2 + 1];
-    const float M = wave_max(mc);
-    terms[c] = sc > 0.f ? sc * expf(mc - M) : 0.f;
-    for (int r = 0; r < n; ++r) {
-        cv[c][r] = st.part_v[((size_t)b * LP_CHUNKS + c) * DOTS_MAX_TOP_LOGPROBS + r];
-        ci[c][r] = st.part_i[((size_t)b * LP_CHUNKS + c) * DOTS_MAX_TOP_LOGPROBS + r];
-    }
-    __syncthreads();
-    if (c == 0) {
-        float S = 0.f;
-        for (int k = 0; k < LP_CHUNKS; ++k) S += terms[k];          // chunk order
-        lse_s = M + logf(S);
-    }
-    __syncthreads();
-    const float lse = lse_s;
+    const float lse = lp_final_load(l, st.part_ms, st.part_v, st.part_i, b, c, n);
     const size_t o = (size_t)b * st.stride + pos;
     int h = 0;
     for (int r = 0; r < n; ++r) {
-        float gv = h < n ? cv[c][h] : -INFINITY;
-        int gi = h < n ? ci[c][h] : LP_NONE;
-        lp_wave_best(gv, gi);
-        if (gi != LP_NONE && h < n && ci[c][h] == gi) h += 1;
+        float gv;
+        int gi;
+        lp_final_next(l, c, n, h, gv, gi);
         if (c == 0) {
             st.top_ids[o * DOTS_MAX_TOP_LOGPROBS + r] = gi == LP_NONE ? -1 : gi;
             st.top_lp[o * DOTS_MAX_TOP_LOGPROBS + r] = gi == LP_NONE ? __builtin_nanf("") : gv - lse;

@@ -357,6 +357,7 @@ int dots_set_row_sampling(DotsEngine* e, int row, const DotsSamplingParams* p) {
     if (row < 0 || row >= e->cfg.max_batch) return e->fail(DOTS_E_INVALID, "row %d out of range [0, %d)", row, e->cfg.max_batch);
     CK(hipSetDevice(e->device));
     if (!p) return clear_row_feature(e, row, ROW_PARAMS);
+    if (beam_row(e, row)) return e->fail(DOTS_E_INVALID, "slot %d is a row of a beam group: it takes no row parameters, rules, guide, n-gram rule, stop strings or logprobs", row);
     RowParams rp;
     RET(check_row_params(e, *p, &rp));
     RET(ensure_row_table(e));
@@ -372,6 +373,7 @@ int dots_set_row_logit_rules(DotsEngine* e, int row, const DotsLogitRules* r) {
     if (row < 0 || row >= e->cfg.max_batch) return e->fail(DOTS_E_INVALID, "row %d out of range [0, %d)", row, e->cfg.max_batch);
     CK(hipSetDevice(e->device));
     if (!r) return clear_row_feature(e, row, ROW_RULES);
+    if (beam_row(e, row)) return e->fail(DOTS_E_INVALID, "slot %d is a row of a beam group: it takes no row parameters, rules, guide, n-gram rule, stop strings or logprobs", row);
     RowRules rr;
     RET(check_logit_rules(e, *r, e->cfg.vocab_size, e->h_eos, e->n_eos, &rr));
     RET(ensure_row_table(e));
@@ -463,6 +465,7 @@ int dots_set_row_guide(DotsEngine* e, int row, int32_t id) {
     if (row < 0 || row >= e->cfg.max_batch) return e->fail(DOTS_E_INVALID, "row %d out of range [0, %d)", row, e->cfg.max_batch);
     CK(hipSetDevice(e->device));
     if (id < 0) return clear_row_feature(e, row, ROW_GUIDE);
+    if (beam_row(e, row)) return e->fail(DOTS_E_INVALID, "slot %d is a row of a beam group: it takes no row parameters, rules, guide, n-gram rule, stop strings or logprobs", row);
     if (id >= (int)e->guides.size() || !e->guides[id].table) return e->fail(DOTS_E_INVALID, "no guide %d", id);
     if (!e->tok_off) return e->fail(DOTS_E_STATE, "the token bytes are not set (dots_set_token_bytes): a guide cannot judge any token");
     RET(ensure_row_table(e));
@@ -481,6 +484,7 @@ int dots_set_row_ngram(DotsEngine* e, int row, const DotsNgramRule* r) {
     if (row < 0 || row >= e->cfg.max_batch) return e->fail(DOTS_E_INVALID, "row %d out of range [0, %d)", row, e->cfg.max_batch);
     CK(hipSetDevice(e->device));
     if (!r) return clear_row_feature(e, row, ROW_NGRAM);
+    if (beam_row(e, row)) return e->fail(DOTS_E_INVALID, "slot %d is a row of a beam group: it takes no row parameters, rules, guide, n-gram rule, stop strings or logprobs", row);
     RowNgram rn;
     RET(check_ngram_rule(e, *r, e->cfg.vocab_size, e->cfg.max_seq_len, &rn));
     RET(ensure_row_table(e));
@@ -541,6 +545,7 @@ int dots_set_row_stop(DotsEngine* e, int row, int32_t handle, int min_tokens) {
     if (row < 0 || row >= e->cfg.max_batch) return e->fail(DOTS_E_INVALID, "row %d out of range [0, %d)", row, e->cfg.max_batch);
     CK(hipSetDevice(e->device));
     if (handle == 0) return clear_row_feature(e, row, ROW_STOP);
+    if (beam_row(e, row)) return e->fail(DOTS_E_INVALID, "slot %d is a row of a beam group: it takes no row parameters, rules, guide, n-gram rule, stop strings or logprobs", row);
     const int id = handle - 1;
     if (id < 0 || id >= (int)e->stops.size() || !e->stops[id].table) return e->fail(DOTS_E_INVALID, "no stop automaton %d", handle);
     if (min_tokens < 0) return e->fail(DOTS_E_INVALID, "stop strings: min_tokens must be >= 0");
@@ -661,6 +666,7 @@ int dots_set_row_logprobs(DotsEngine* e, int row, int top_n) {
     if (row < 0 || row >= e->cfg.max_batch) return e->fail(DOTS_E_INVALID, "row %d out of range [0, %d)", row, e->cfg.max_batch);
     if (top_n < -1 || top_n > DOTS_MAX_TOP_LOGPROBS) return e->fail(DOTS_E_INVALID, "top_n must be -1 (off) or in [0, %d]", DOTS_MAX_TOP_LOGPROBS);
     if (top_n < 0 && !e->d_row_lp) return DOTS_OK;
+    if (top_n >= 0 && beam_row(e, row)) return e->fail(DOTS_E_INVALID, "slot %d is a row of a beam group: it takes no row parameters, rules, guide, n-gram rule, stop strings or logprobs", row);
     if (e->cfg.vocab_size > LP_MAX_V) return e->fail(DOTS_E_INVALID, "logprobs support vocabularies up to %d", LP_MAX_V);
     CK(hipSetDevice(e->device));
     if (!e->d_row_lp) {

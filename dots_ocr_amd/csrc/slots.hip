@@ -30,7 +30,6 @@ bool reserve_pages(DotsEngine* e, int slot, int tokens) {
     return true;
 }
 
-namespace {
 // On-demand growth (continuous batching): make the sequence in `slot` own pages for `tokens` positions; returns the positions its pages
 // cover afterwards (< tokens when the pool ran dry).  *changed: the block-table row has to be uploaded.
 int grow_pages(DotsEngine* e, int slot, int tokens, bool* changed) {
@@ -45,7 +44,6 @@ int grow_pages(DotsEngine* e, int slot, int tokens, bool* changed) {
     }
     return (int)mine.size() * 64;
 }
-}  // namespace
 
 // tokens a slot sequence reserves at admission: its prompt plus the first page-worth of generated tokens (the rest on demand)
 constexpr int KV_ADMIT_AHEAD = 64;
@@ -203,6 +201,7 @@ int dots_slots_reset(DotsEngine* e) {
         e->pref_pending = e->pref_deferred = false;
     }
     for (int b = 0; b < (int)e->slot_pages.size(); ++b) release_pages(e, b);
+    RET(beam_clear_all(e));
     e->fresh_slots.clear();
     CK(hipMemcpyAsync(e->block_table, e->hp_table.data(), e->hp_table.size() * 4, hipMemcpyHostToDevice, s));
     std::fill(e->slot_active, e->slot_active + DOTS_MAX_BATCH, 0);
@@ -242,10 +241,11 @@ int dots_slots_decode(DotsEngine* e, int n_steps) {
     for (int b = 0; b < e->cfg.max_batch; ++b)
         if (e->slot_active[b]) rows = b + 1;
     if (!rows) return e->fail(DOTS_E_STATE, "every slot is free");
+    RET(beam_before_decode(e, n_steps));                    // a refusal changes nothing
     e->fresh_slots.clear();                                 // the step overwrites the logits a fork selects from (dots_slots_fork)
     if (e->sel_dirty) {
         int32_t sel[DOTS_MAX_BATCH];
-        for (int b = 0; b < DOTS_MAX_BATCH; ++b) sel[b] = e->slot_active[b];
+        for (int b = 0; b < DOTS_MAX_BATCH; ++b) sel[b] = e->slot_active[b] && !e->beam_of[b];      // a group's rows are selected by its own kernels
         CK(hipMemcpyAsync(e->d_sel, sel, DOTS_MAX_BATCH * 4, hipMemcpyHostToDevice, s));
         e->sel_dirty = false;
     }
@@ -257,6 +257,7 @@ int dots_slots_decode(DotsEngine* e, int n_steps) {
     n_steps *= e->spec_k + 1;
     for (int b = 0; b < rows; ++b) {
         if (!e->slot_active[b] || e->slot_done[b]) continue;
+        if (e->beam_of[b]) continue;                        // fully reserved at creation, and the device owns its table row
         // A step at context c writes KV position c and brings the sequence to c + 2 tokens, so n_steps more steps need positions
         // [0, ctx + n_steps), and a sequence limited to slot_limit tokens never writes beyond position slot_limit - 2.
         int want = std::min(e->slot_ctx_ub[b] + n_steps, e->slot_limit[b] - 1);
@@ -351,6 +352,7 @@ int dots_slot_release(DotsEngine* e, int slot) {
     if (!e) return DOTS_E_INVALID;
     if (!e->slot_mode || slot < 0 || slot >= e->cfg.max_batch || !e->slot_active[slot]) return e->fail(DOTS_E_STATE, "slot %d is not occupied", slot);
     CK(hipSetDevice(e->device));
+    if (e->beam_of[slot]) return beam_release_group(e, slot);          // the slots of a beam group go together
     for (int f = 0; f < ROW_FEATURES; ++f) RET(clear_row_feature(e, slot, (RowFeature)f));
     RET(set_row_lp(e, slot, -1));
     e->slot_active[slot] = 0;

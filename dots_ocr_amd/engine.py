@@ -330,6 +330,9 @@ def _prototypes(lib):
         "dots_slots_prefill": (i32, [vp, P(i32), i32, P(i32), P(i32), P(i32)]),
         "dots_slots_decode": (i32, [vp, i32]),
         "dots_slots_fork": (i32, [vp, i32, P(i32), i32]),
+        "dots_slots_beam": (i32, [vp, i32, P(i32), i32]),
+        "dots_beam_info": (i32, [vp, i32, P(i32), P(i32), P(i32)]),
+        "dots_beam_read": (i32, [vp, i32, P(i32), P(i32), P(f32), P(i32), P(i32), i32, P(i32), i32, P(i32)]),
         "dots_slots_poll": (i32, [vp, P(i32), P(i32)]),
         "dots_slot_read": (i32, [vp, i32, P(i32), i32, P(i32)]),
         "dots_slot_release": (i32, [vp, i32]),
@@ -423,6 +426,7 @@ EXPORTED_SYMBOLS = [
     "dots_set_row_ngram", "dots_op_select_tokens_ngram", "dots_bench_select_tokens_ngram",
     "dots_set_speculation", "dots_set_speculation_rows", "dots_set_row_drafts", "dots_spec_stats", "dots_op_ngram_draft",
     "dots_slots_fork",
+    "dots_slots_beam", "dots_beam_info", "dots_beam_read",
     "dots_stop_create", "dots_stop_destroy", "dots_set_row_stop", "dots_row_stop_hit",
 ]
 
@@ -1082,6 +1086,37 @@ class Engine:
         dst = np.ascontiguousarray(dst_slots, dtype=np.int32)
         assert dst.ndim == 1
         self._ck(self.lib.dots_slots_fork(self.h, int(src), _i32p(dst) if dst.shape[0] else None, dst.shape[0]), "dots_slots_fork")
+
+    def slots_beam(self, src: int, dst_slots: Sequence[int]):
+        """Beam search: slot src (just prefilled, no decode step since) and the free slots dst_slots become a group of
+        1 + len(dst_slots) beams, in that order, fully reserved over the source's shared prompt pages; the group's first selection replaces
+        the source's own first token.  slots_decode steps it; slot_release of any of its slots releases all of them."""
+        dst = np.ascontiguousarray(dst_slots, dtype=np.int32)
+        assert dst.ndim == 1
+        self._ck(self.lib.dots_slots_beam(self.h, int(src), _i32p(dst) if dst.shape[0] else None, dst.shape[0]), "dots_slots_beam")
+
+    def beam_info(self, slot: int):
+        """(beams, steps done, completed records so far) of the group that `slot` belongs to"""
+        b, st, nd = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        self._ck(self.lib.dots_beam_info(self.h, int(slot), C.byref(b), C.byref(st), C.byref(nd)), "dots_beam_info")
+        return int(b.value), int(st.value), int(nd.value)
+
+    def beam_read(self, slot: int) -> dict:
+        """The trace of the group that `slot` belongs to: B, steps, cum float32 [B] (-inf: a dead beam), tokens / parents int32 [B, steps]
+        (-1: dead; parents[j, t] = the beam of step t - 1 that beam j of step t extends) and completed = [(step, parent beam, EOS id,
+        np.float32 cum)] in (step, beam, rank) order: the arguments of dots_ocr_amd.beam.rank_hypotheses."""
+        B, steps, nd = self.beam_info(slot)
+        b, st, n = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        cum = np.empty((8,), dtype=np.float32)
+        tokens = np.empty((B, max(1, steps)), dtype=np.int32)
+        parents = np.empty((B, max(1, steps)), dtype=np.int32)
+        done = np.empty((max(1, nd), 4), dtype=np.int32)
+        self._ck(self.lib.dots_beam_read(self.h, int(slot), C.byref(b), C.byref(st), cum.ctypes.data_as(C.POINTER(C.c_float)), _i32p(tokens),
+                                         _i32p(parents), tokens.shape[1], _i32p(done), done.shape[0], C.byref(n)), "dots_beam_read")
+        steps, nd = min(steps, int(st.value)), min(nd, int(n.value))
+        s = done[:nd, 3].copy().view(np.float32)
+        return {"B": B, "steps": steps, "cum": cum[:B].copy(), "tokens": tokens[:, :steps].copy(), "parents": parents[:, :steps].copy(),
+                "completed": [(int(done[k, 0]), int(done[k, 1]), int(done[k, 2]), s[k]) for k in range(nd)]}
 
     def slots_reset(self):
         """Slot mode, every slot free, every KV page in the pool."""

@@ -135,7 +135,8 @@ class DotsOcrHipForCausalLM:
                  stop_token_ids=None, ignore_eos: bool = False, guided_regex=None, guided_choice=None, guided_json=None,
                  guided_whitespace_pattern=None, no_repeat_ngram_size: Optional[int] = None, no_repeat_ngram_window: Optional[int] = None,
                  no_repeat_ngram_whitelist=None, speculative_ngram: Optional[int] = None, prompt_lookup_min: int = 2, prompt_lookup_max: int = 4,
-                 num_return_sequences: int = 1, stop_strings=None, speculative_rows=None, **_):
+                 num_return_sequences: int = 1, stop_strings=None, speculative_rows=None, num_beams: Optional[int] = None,
+                 length_penalty: float = 1.0, early_stopping=None, **_):
         """HF-shaped generate.  do_sample / temperature / top_p default to the checkpoint's generation_config.json (greedy when it
         is absent); with sampling on, tokens are drawn on the GPU from softmax(logits / temperature) restricted to the top_p
         nucleus, reproducibly from `seed`.  Returns LongTensor
@@ -182,7 +183,14 @@ class DotsOcrHipForCausalLM:
 
         num_return_sequences (n >= 1, HF's name) returns n sequences per prompt from one vision tower and one prefill of it (parallel
         sampling: Engine.slots_fork): LongTensor [B * n, T + new], row i * n + j = sequence j of prompt i as HF lays it out,
-        drawn with seed + i * n + j.  It runs on the continuous path; continuous=False with n > 1 is a ValueError."""
+        drawn with seed + i * n + j.  It runs on the continuous path; continuous=False with n > 1 is a ValueError.
+
+        num_beams (2 .. 8; None or 1 = off) runs beam search (Engine.slots_beam): every prompt becomes a group of num_beams
+        beams over one tower and one prefill, and its num_return_sequences (<= num_beams) best hypotheses come back best first, laid out
+        as above, ranked by cum / max(1, len) ** length_penalty.  These are vLLM's beam-search semantics with HF's length normalisation,
+        not HF's BeamSearchScorer: early_stopping is not offered (given, it raises), and the call is refused — nothing is silently
+        dropped — together with sampling (a temperature > 0, top_k, penalties), logit rules, a guide, an n-gram rule, stop strings,
+        speculation or continuous=False."""
         import dataclasses
         import torch
         t_eff, p_eff = resolve_sampling(self.generation_config, do_sample, temperature, top_p)
@@ -192,6 +200,29 @@ class DotsOcrHipForCausalLM:
             raise ValueError(f"num_return_sequences must be an integer >= 1, got {nrs!r}")
         if nrs > 1 and continuous is False:
             raise ValueError("num_return_sequences > 1 runs on the continuous path: continuous=False cannot be combined with it")
+        if early_stopping is not None:
+            raise ValueError("early_stopping is not offered: a beam group ends at its cap, or early only where that is exact (DESIGN §6.9)")
+        beam = None
+        if num_beams is not None and num_beams != 1:
+            from .beam import MAX_BEAMS
+            if isinstance(num_beams, bool) or not isinstance(num_beams, int) or not 2 <= num_beams <= MAX_BEAMS:
+                raise ValueError(f"num_beams must be an integer in [1, {MAX_BEAMS}], got {num_beams!r}")
+            if nrs > num_beams:
+                raise ValueError(f"num_return_sequences = {nrs} exceeds num_beams = {num_beams}")
+            refused = [name for name, on in (
+                ("sampling (temperature > 0)", t_eff > 0), ("top_k", (top_k or 0) > 0), ("repetition_penalty", repetition_penalty not in (None, 1.0)),
+                ("frequency_penalty", (frequency_penalty or 0.0) != 0.0), ("presence_penalty", (presence_penalty or 0.0) != 0.0),
+                ("logit_bias", bool(logit_bias)), ("allowed_token_ids", allowed_token_ids is not None), ("min_tokens", int(min_tokens or 0) > 0),
+                ("stop_token_ids", bool(stop_token_ids)), ("ignore_eos", bool(ignore_eos)),
+                ("a guide", any(g is not None for g in (guided_regex, guided_choice, guided_json))),
+                ("no_repeat_ngram_size", bool(no_repeat_ngram_size)), ("stop_strings", stop_strings is not None),
+                ("speculative_ngram", bool(speculative_ngram)), ("continuous=False", continuous is False)) if on]
+            if refused:
+                raise ValueError(f"num_beams cannot be combined with {', '.join(refused)}")
+            if not hasattr(self.engine, "slots_beam"):
+                raise ValueError("this engine cannot run a beam group (no slots_beam)")
+            beam = (int(num_beams), float(length_penalty))
+            continuous = True
         row_sp = None
         if (top_k or 0) > 0 or repetition_penalty not in (None, 1.0) or (frequency_penalty or 0.0) != 0.0 or (presence_penalty or 0.0) != 0.0:
             from .engine import SamplingParams
@@ -251,7 +282,7 @@ class DotsOcrHipForCausalLM:
 
                 def row_sp(b):
                     return dataclasses.replace(base, seed=int(seed) + b)
-        if nrs > 1:
+        if nrs > 1 and beam is None:
             continuous = True
             from .engine import SamplingParams
             per_seq = row_sp(0) if row_sp else SamplingParams(temperature=t_eff, top_p=p_eff, seed=seed)
@@ -282,7 +313,7 @@ class DotsOcrHipForCausalLM:
                 self.engine.set_speculation_rows(sampled=bool(spec_rows & SPEC_ROWS["sampled"]), stop=bool(spec_rows & SPEC_ROWS["stop"]))
         try:
             return self._generate(input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens, eos_token_id, pad_token_id, continuous,
-                                  row_sp, rules, guide, ngram, nrs, stop, int(min_tokens or 0))
+                                  row_sp, rules, guide, ngram, nrs, stop, int(min_tokens or 0), beam)
         finally:
             if spec_k:
                 try:
@@ -301,7 +332,7 @@ class DotsOcrHipForCausalLM:
                     warnings.warn(f"guide {guide} could not be destroyed: {e}")
 
     def _generate(self, input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens, eos_token_id, pad_token_id, continuous, row_sp, rules,
-                  guide, ngram=None, nrs=1, stop=None, stop_min=0):
+                  guide, ngram=None, nrs=1, stop=None, stop_min=0, beam=None):
         import torch
         ids = input_ids.detach().cpu().numpy()
         B, T = ids.shape
@@ -361,8 +392,12 @@ class DotsOcrHipForCausalLM:
                 else:
                     reqs.append(Request(prompts[b], None, None, max_new_tokens, sampling=row_sp(b) if row_sp else None, rules=rules, guide=guide,
                                         ngram=ngram, n=nrs, stop=stop))
+                if beam is not None:             # a group of beam[0] beams that returns its nrs best hypotheses
+                    reqs[-1].n, reqs[-1].num_beams, reqs[-1].num_return, reqs[-1].length_penalty = 1, beam[0], nrs, beam[1]
             outs = ContinuousBatcher(self.engine, eos_ids=eos).run(reqs)
-            if nrs > 1:                          # row i * n + j = sequence j of prompt i
+            if beam is not None:                 # row i * n + j = the j-th best hypothesis of prompt i (a prompt with fewer: pad rows)
+                outs = [r.outputs[j] if j < len(r.outputs) else np.zeros(0, np.int64) for r in reqs for j in range(nrs)]
+            elif nrs > 1:                        # row i * n + j = sequence j of prompt i
                 outs = [o for r in reqs for o in r.outputs]
             for b, o in enumerate(outs):
                 new_tokens[b, :len(o)] = o

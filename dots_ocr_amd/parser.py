@@ -35,8 +35,15 @@ class DotsOCRParser:
                  max_pixels=None, use_hf=False, model_path="./weights/DotsOCR", model=None, processor=None,
                  hf_max_new_tokens=24000, guided=False, no_repeat_ngram_size=None, no_repeat_ngram_window=None,
                  no_repeat_ngram_whitelist=None, speculative_ngram=None, prompt_lookup_min=2, prompt_lookup_max=4, stop=None,
-                 speculative_rows=None):
+                 speculative_rows=None, num_beams=None, length_penalty=1.0):
         self.dpi = dpi
+        # beam search, opt-in: every page is decoded by a group of num_beams beams and its best hypothesis returned (the
+        # server request carries use_beam_search with temperature 0, the in-process model generates with num_beams).  It combines with
+        # none of the other selection settings: they are refused, not dropped.
+        self.num_beams = None if not num_beams or int(num_beams) == 1 else int(num_beams)
+        self.length_penalty = float(length_penalty)
+        if self.num_beams is not None and (guided or no_repeat_ngram_size or speculative_ngram or stop is not None):
+            raise ValueError("num_beams cannot be combined with guided, no_repeat_ngram_size, speculative_ngram or stop")
         # stop strings, opt-in: the server request carries `stop`, the in-process model generates with stop_strings and the
         # text is cut where the match starts.  With the default None the request and the call are exactly what they were.
         self.stop = None
@@ -124,6 +131,8 @@ class DotsOCRParser:
             if getattr(self.model.engine, "token_bytes", None) is None:
                 self.model.engine.set_token_bytes(self.processor.guide_token_bytes())
             kw["stop_strings"] = self.stop
+        if self.num_beams:
+            kw.update(num_beams=self.num_beams, length_penalty=self.length_penalty, do_sample=False)
         generated = self.model.generate(**inputs, max_new_tokens=self.hf_max_new_tokens, **kw)
         trimmed = [out[len(inp):] for inp, out in zip(inputs.input_ids, generated)]
         texts = self.processor.batch_decode(trimmed, skip_special_tokens=True, clean_up_tokenization_spaces=False)
@@ -145,9 +154,11 @@ class DotsOCRParser:
     def _inference_with_vllm(self, image, prompt):
         from dots_ocr.model.inference import inference_with_vllm
         extra = {**({"guided_layout": True} if self._guided_layout([prompt]) else {}), **self._ngram_fields(),
-                 **({"stop": self.stop} if self.stop else {})}
+                 **({"stop": self.stop} if self.stop else {}),
+                 **({"use_beam_search": True, "beam_width": self.num_beams, "length_penalty": self.length_penalty} if self.num_beams else {})}
         return inference_with_vllm(image, prompt, model_name=self.model_name, protocol=self.protocol, ip=self.ip,
-                                   port=self.port, temperature=self.temperature, top_p=self.top_p,
+                                   port=self.port, temperature=0.0 if self.num_beams else self.temperature,
+                                   top_p=1.0 if self.num_beams else self.top_p,
                                    max_completion_tokens=self.max_completion_tokens,
                                    **({"extra_body": extra} if extra else {}))
 

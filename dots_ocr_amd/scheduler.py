@@ -43,6 +43,17 @@ class Request:
                                                 # match length, match id) or None — as a list in index order when n > 1
     include_stop_str_in_output: bool = False    # vLLM's field: where text built from the tokens is cut (stop_strings.cut_text); the tokens
                                                 # always end at the one that completed the match
+    num_beams: Optional[int] = None             # beam search: a group of 2 .. 8 beams from one tower and one prefill, in num_beams slots.
+                                                # vLLM's beam-search semantics with HF's length normalisation, not HF's BeamSearchScorer.  A finished
+                                                # request carries outputs (the num_return best hypotheses, best first, a final EOS included),
+                                                # cumulative_logprobs, beam_scores and finish_reasons ("stop" | "length") in that order
+    num_return: int = 1                         # hypotheses returned, 1 .. num_beams
+    length_penalty: float = 1.0                 # score = cum / max(1, len) ** length_penalty, len without a final EOS
+
+    @property
+    def width(self) -> int:
+        """slots the request takes: its beams, or its n sequences"""
+        return int(self.num_beams) if self.num_beams else int(self.n)
 
     def n_patches(self) -> int:
         if self.grid_thw is None:
@@ -122,6 +133,8 @@ class ContinuousBatcher:
             raise ValueError(f"n must be an integer >= 1, got {req.n!r}")
         if req.n > self.n_slots:
             raise ValueError(f"n = {req.n} sequences need more than the {self.n_slots} usable slots")
+        if req.num_beams is not None:
+            self._check_beam(req)
         if req.n > 1 and not hasattr(self.engine, "slots_fork"):
             raise ValueError("this engine cannot fork a prefilled sequence (no slots_fork): n > 1 is not available")
         if req.rules is not None and not hasattr(self.engine, "set_row_logit_rules"):
@@ -161,6 +174,36 @@ class ContinuousBatcher:
         self.pending.append((rid, req))
         return rid
 
+    def _check_beam(self, req: Request):
+        """a beam request is refused whole rather than run with anything dropped"""
+        from .beam import MAX_BEAMS
+        B = req.num_beams
+        if isinstance(B, bool) or not isinstance(B, (int, np.integer)) or not 2 <= B <= MAX_BEAMS:
+            raise RequestRejected(f"num_beams must be an integer in [2, {MAX_BEAMS}], got {B!r}")
+        if isinstance(req.num_return, bool) or not isinstance(req.num_return, (int, np.integer)) or not 1 <= req.num_return <= B:
+            raise RequestRejected(f"num_return must be an integer in [1, num_beams = {B}], got {req.num_return!r}")
+        if not np.isfinite(float(req.length_penalty)):
+            raise RequestRejected(f"length_penalty must be finite, got {req.length_penalty!r}")
+        if req.n != 1:
+            raise RequestRejected("beam search returns num_return hypotheses: n must be 1")
+        if B > self.n_slots:
+            raise ValueError(f"num_beams = {B} needs more than the {self.n_slots} usable slots")
+        if not hasattr(self.engine, "slots_beam"):
+            raise ValueError("this engine cannot run a beam group (no slots_beam): num_beams is not available")
+        if getattr(self.engine, "spec_k", 0):
+            raise RequestRejected("beam search cannot run while the engine speculates")
+        sp = req.sampling
+        if sp is not None:
+            plain = (float(getattr(sp, "temperature", 0.0)) == 0.0 and int(getattr(sp, "top_k", 0) or 0) == 0 and float(getattr(sp, "top_p", 1.0)) == 1.0
+                     and float(getattr(sp, "repetition_penalty", 1.0)) == 1.0 and float(getattr(sp, "frequency_penalty", 0.0)) == 0.0
+                     and float(getattr(sp, "presence_penalty", 0.0)) == 0.0)
+            if not plain:
+                raise RequestRejected("a beam request takes no sampling parameters other than temperature = 0 (no top_k, top_p or penalties)")
+            req.sampling = None                      # plain greedy parameters say nothing a beam row could honour or break
+        for name, what in (("rules", "logit rules"), ("guide", "a guide"), ("ngram", "an n-gram rule"), ("stop", "stop strings"), ("logprobs", "logprobs")):
+            if getattr(req, name) is not None:
+                raise RequestRejected(f"a beam request takes no {what}")
+
     @property
     def idle(self) -> bool:
         return not self.pending and not self.running and not self._ahead and not self._rejected
@@ -178,12 +221,23 @@ class ContinuousBatcher:
         """pages a request takes at admission: sequence 0 its prompt + ADMIT_AHEAD, each further sequence of n > 1 the same less the full
         prompt pages it shares with sequence 0 (Engine.slots_fork)"""
         t = int(r.input_ids.shape[0])
+        if r.num_beams:
+            return self._beam_pages(r)
         need = self._admit_pages(t, r.max_new_tokens)
         return need + (int(r.n) - 1) * (need - t // 64)
+
+    def _beam_pages(self, r: Request) -> int:
+        """a beam group is fully reserved when it is made (Engine.slots_beam): the floor(t / 64) full prompt pages once, and per beam the
+        pages of the positions [64 floor(t / 64), t + max_new) plus one spare"""
+        t = int(r.input_ids.shape[0])
+        shared = t // 64
+        return shared + int(r.num_beams) * ((t + int(r.max_new_tokens) + 63) // 64 - shared + 1)
 
     def _worst_pages(self, r: Request, n: Optional[int] = None) -> int:
         """pages of the request's sequences at their caps, the shared prompt pages counted once; n: of that many of its sequences only
         (what is still running: a conservative count, as if sequence 0 were among them)"""
+        if r.num_beams:
+            return self._beam_pages(r)               # the whole group holds its pages until it is released together
         t, n = int(r.input_ids.shape[0]), int(r.n) if n is None else n
         worst = (min(t + int(r.max_new_tokens), self.max_seq_len) + 63) // 64
         return worst + (n - 1) * (worst - t // 64)
@@ -212,16 +266,16 @@ class ContinuousBatcher:
         while self.pending and free and (self.admit_group is None or len(group) < self.admit_group):
             rid, req = self.pending[0]
             p, t = req.n_patches(), int(req.input_ids.shape[0])
-            if req.n > len(free):
-                break                                # n sequences need n slots: the head of the queue waits for them, nothing overtakes it
+            if req.width > len(free):
+                break                                # n sequences (or beams) need n slots: the head of the queue waits for them, nothing overtakes it
             if group and (patches + p > self.max_patches or tokens + t > self.max_prefill_tokens):
                 break
             # paged KV, on demand: a sequence reserves its prompt + ADMIT_AHEAD tokens now and grows page by page; admit only while every
             # running sequence (and this one) could still take `headroom` more pages, so that a dry pool — which ends a sequence early
             # at what its pages hold — stays the exception.  Nothing running: admit whatever fits (submit() checked that it can).
             need = self._group_pages(req)
-            taken = len(self.running) + sum(r.n for _, _, r in group)
-            reserve = self.headroom_pages * (taken + req.n) if (self.running or group) else 0
+            taken = len(self.running) + sum(r.width for _, _, r in group)
+            reserve = self.headroom_pages * (taken + req.width) if (self.running or group) else 0
             if (self.running or group) and not self._fits_full_reservation([r for _, _, r in group], [req]):
                 break                                # worst case of everything in flight must fit the pool (submit() checked a lone request)
             if need + reserve > pages_free:
@@ -229,8 +283,8 @@ class ContinuousBatcher:
             pages_free -= need
             self.pending.popleft()
             group.append((free.pop(0), rid, req))
-            if req.n > 1:
-                self._kids[rid] = [free.pop(0) for _ in range(req.n - 1)]
+            if req.width > 1:
+                self._kids[rid] = [free.pop(0) for _ in range(req.width - 1)]
             patches += p
             tokens += t
         return group
@@ -306,7 +360,7 @@ class ContinuousBatcher:
         slots = [s for s, _, _ in group]
         lens = [int(r.input_ids.shape[0]) for _, _, r in group]
         caps = [int(r.max_new_tokens) for _, _, r in group]
-        kids = {rid: self._kids.pop(rid) for _, rid, r in group if r.n > 1}       # the slots of sequences 1 .. n - 1 (parallel sampling)
+        kids = {rid: self._kids.pop(rid) for _, rid, r in group if r.width > 1}   # the slots of sequences 1 .. n - 1 (parallel sampling) or of beams 1 .. B - 1
         every = slots + [k for ks in kids.values() for k in ks]
         for s, rid, r in ([] if rows_set else group):     # a prefetched group: its tower has run, so it goes in (or fails) as a whole
             try:
@@ -325,8 +379,11 @@ class ContinuousBatcher:
         try:                                         # one fork per request with n > 1, before any decode step: the prefill is still fresh
             for s, rid, r in group:
                 if rid in kids:
-                    self.engine.slots_fork(s, kids[rid])
-                    forked += kids[rid]
+                    if r.num_beams:                  # a group's slots go back with its source
+                        self.engine.slots_beam(s, kids[rid])
+                    else:
+                        self.engine.slots_fork(s, kids[rid])
+                        forked += kids[rid]
         except Exception:
             for s in slots + forked:                 # the prefill went in: give its slots back, the caller re-queues the group
                 self.engine.slot_release(s)
@@ -371,7 +428,7 @@ class ContinuousBatcher:
     def _admit_ahead(self) -> bool:
         """The group whose tower was prefetched goes in as a whole as soon as it has the slots and the pages."""
         free = self.free_slots()
-        if len(free) < sum(r.n for _, r in self._ahead):
+        if len(free) < sum(r.width for _, r in self._ahead):
             return False
         # sequences are decoding and the tower is still running: taking the group now would queue every decode chunk behind the tower
         # (vit_take makes the engine's stream wait for it) — keep decoding, take it when its rows exist.  Nothing running: wait for it.
@@ -379,7 +436,7 @@ class ContinuousBatcher:
             return False
         if hasattr(self.engine, "kv_pool_info"):
             need = sum(self._group_pages(r) for _, r in self._ahead)
-            reserve = self.headroom_pages * (len(self.running) + sum(r.n for _, r in self._ahead)) if self.running else 0
+            reserve = self.headroom_pages * (len(self.running) + sum(r.width for _, r in self._ahead)) if self.running else 0
             if need + reserve > self.engine.kv_pool_info()[1]:
                 return False
             if self.running and not self._fits_full_reservation([], [r for _, r in self._ahead]):
@@ -388,8 +445,8 @@ class ContinuousBatcher:
         placed = []
         for rid, r in group:                         # lowest slots first; the sequences of a request with n > 1 side by side
             placed.append((free.pop(0), rid, r))
-            if r.n > 1:
-                self._kids[rid] = [free.pop(0) for _ in range(r.n - 1)]
+            if r.width > 1:
+                self._kids[rid] = [free.pop(0) for _ in range(r.width - 1)]
         try:
             self.engine.vit_take()
             self._prefill(placed)
@@ -423,7 +480,7 @@ class ContinuousBatcher:
             if len(self.free_slots()) + self._soon_free(2 * self.chunk + k * self.tower_steps_per_page) >= k:
                 cap = k
                 break
-        while self.pending and sum(r.n for _, r in group) + self.pending[0][1].n <= cap:      # cap counts slots: a request takes n of them
+        while self.pending and sum(r.width for _, r in group) + self.pending[0][1].width <= cap:      # cap counts slots: a request takes n of them
             rid, req = self.pending[0]
             p, t = req.n_patches(), int(req.input_ids.shape[0])
             pg = self._group_pages(req)
@@ -455,6 +512,13 @@ class ContinuousBatcher:
         fin, lens = self.engine.slots_poll()
         done = []
         for s in sorted(self.running):
+            if s not in self.running:                # a slot of a beam group that has just been reported
+                continue
+            if self.running[s][1].num_beams:
+                out = self._collect_beam(s, bool(fin[s] == 1))
+                if out is not None:
+                    done.append(out)
+                continue
             if fin[s] == 1:
                 rid, req = self.running.pop(s)
                 toks = self.engine.slot_read(s, int(lens[s]))
@@ -498,6 +562,28 @@ class ContinuousBatcher:
                 self._row_stop.pop(s, None)          # and its stop strings
         self._last_lens = {s: int(lens[s]) for s in self.running}      # after the finished slots have left: only what is still decoding
         return done
+
+    def _collect_beam(self, s: int, finished: bool):
+        """The beam group that slot s belongs to, at a poll: finished (its cap, or no live beam), or — exact for length_penalty >= 0 —
+        ended early because num_return completed hypotheses already outscore whatever a live beam could still become (beam.may_stop).
+        The request is reported once, best hypothesis first, and its slots go back together."""
+        from .beam import may_stop, rank_hypotheses
+        rid, req = self.running[s]
+        tr = self.engine.beam_read(s)
+        if not finished and not may_stop(tr["completed"], tr["cum"], req.max_new_tokens, req.length_penalty, req.num_return):
+            return None
+        # a group ended early is ranked on its completed hypotheses alone: at the cap no live beam could have outscored the returned ones
+        live = tr["cum"] if finished else np.full_like(tr["cum"], -np.inf)
+        hyps = rank_hypotheses(tr["completed"], tr["parents"], tr["tokens"], live, tr["steps"], req.length_penalty, req.num_return)
+        req.outputs = [np.asarray(h["tokens"], np.int32) for h in hyps]
+        req.cumulative_logprobs = [h["cum"] for h in hyps]
+        req.beam_scores = [h["score"] for h in hyps]
+        req.finish_reasons = [h["finish_reason"] for h in hyps]
+        req.kv_truncated = False                     # a group is fully reserved: the pool cannot run dry under it
+        for k in [k for k, (r2, _) in self.running.items() if r2 == rid]:
+            del self.running[k]
+        self.engine.slot_release(s)                  # one slot of the group releases all of them
+        return rid, req, req.outputs[0] if req.outputs else np.zeros(0, np.int32)
 
     def step(self) -> List[Tuple[int, Request, np.ndarray]]:
         """Admit what fits, run one decode chunk, return the requests that finished: (id, request, new token ids).  A request the engine

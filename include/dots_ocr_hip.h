@@ -458,6 +458,36 @@ int dots_slots_decode(DotsEngine* e, int n_steps);
 int dots_slots_poll(DotsEngine* e, int32_t* finished_host, int32_t* out_lens_host);
 int dots_slot_read(DotsEngine* e, int slot, int32_t* out_ids_host, int capacity, int32_t* n_out);
 int dots_slot_release(DotsEngine* e, int slot);
+/* ---- Beam search: a group of B beams, 2 <= B <= DOTS_MAX_BEAMS, over shared KV pages.  These are vLLM's beam-search
+ * semantics with HF's length normalisation applied by the caller; they are not HF's BeamSearchScorer.
+ *
+ * Per step, on the raw logits: every live beam i offers its 2B best (lp, id) pairs (value descending, id ascending; lp = logit - lse,
+ * bitwise what dots_row_logprobs returns for an ordinary row with the same prefix), a candidate is (i, rank r, id, s = fp32(cum[i] + lp));
+ * candidates whose s is NaN or -inf do not exist; a candidate whose id is an EOS id (dots_set_eos) is recorded as completed
+ * (step, parent beam, id, s); the B best others by (s descending, i ascending, r ascending) are the new beams, the rest of the beams is
+ * dead (cum = -inf; token and parent read -1).  The group runs its cap of max_new_tokens steps (or until no beam is live); the first
+ * selection is step 0.
+ *
+ * dots_slots_beam  src_slot and the n_dst free slots dst_slots_host become the group, in group order [src, dst...] (beam i = the i-th of
+ *                  them).  src_slot as for dots_slots_fork: filled by the most recent dots_slots_prefill, no decode step since.  The
+ *                  children share the source's floor(L / 64) full prompt pages; the group is fully reserved now: every beam owns
+ *                  ceil((L + max_new) / 64) - floor(L / 64) pages plus one spare, and its block-table row belongs to the device from here
+ *                  on (the mid-generation fork rewrites it inside the captured steps).  The source's own first token is replaced by the
+ *                  group's first selection.  Refused with nothing changed: bad slots as dots_slots_fork, a pool that cannot serve the pages
+ *                  (DOTS_E_CAPACITY), a speculating engine (DOTS_E_STATE), a group slot that carries row parameters, logit rules, a guide,
+ *                  an n-gram rule, stop strings or logprobs (DOTS_E_INVALID; the row setters refuse a group row likewise).
+ *                  dots_slots_decode steps the group with every other slot (a chunk that could complete more than 4096 hypotheses of one
+ *                  group is refused: DOTS_E_CAPACITY); dots_slots_poll reports its rows finished together; dots_slot_release of any of
+ *                  its slots releases all of them.  Synchronises.
+ * dots_beam_info   B, steps done and completed records so far of the group that `slot` belongs to.  Synchronises.
+ * dots_beam_read   + cum float [B]; tokens / parents int32 [B][step_capacity] (the first min(steps, step_capacity) steps of every beam:
+ *                  parents[j][t] = the beam at step t - 1 that beam j of step t extends); done int32 [done_capacity][4] = (step, parent
+ *                  beam, EOS id, the bits of s), every record since the group was made, in (step, beam, rank) order. */
+#define DOTS_MAX_BEAMS 8
+int dots_slots_beam(DotsEngine* e, int src_slot, const int32_t* dst_slots_host, int n_dst);
+int dots_beam_info(DotsEngine* e, int slot, int32_t* n_beams, int32_t* steps, int32_t* n_done);
+int dots_beam_read(DotsEngine* e, int slot, int32_t* n_beams, int32_t* steps, float* cum_host, int32_t* tokens_host, int32_t* parents_host,
+                   int step_capacity, int32_t* done_host, int done_capacity, int32_t* n_done);
 /* Paged KV pool: pages of 64 tokens in total / currently free (an admission policy checks this before dots_slots_prefill,
  * which refuses with DOTS_E_CAPACITY when prompt + 64 tokens of each new sequence do not fit). */
 int dots_kv_pool_info(DotsEngine* e, int32_t* total_pages, int32_t* free_pages);
