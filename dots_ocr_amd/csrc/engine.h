@@ -207,7 +207,14 @@ struct DotsEngine {
     // parameters carry a penalty / a temperature > 0 (the two facts about them the class needs)
     int spec_rows = 0;
     int32_t *sp_cls = nullptr, *sp_cand = nullptr;
+    // may a row that holds a guide verify drafts (dots_set_speculation_guided; spec_row_class() ORs SPEC_ROWS_GUIDED into the mode), and —
+    // allocated by the first call that switches it on — the states of the draft rows of guided slots (kernels.h SpecState::gstate)
+    int spec_guided = 0;
+    int32_t* sp_gstate = nullptr;
     bool row_pen[DOTS_MAX_BATCH] = {false}, row_sampled[DOTS_MAX_BATCH] = {false};
+    // of a staged row without ROW_PARAMS: the engine-wide setting its stage entry was written from had a temperature > 0.  Such a row is
+    // drawn by the stage whatever dots_set_sampling says later, and its draft rows would be arg maxima: it verifies no draft
+    bool row_entry_sampled[DOTS_MAX_BATCH] = {false};
     // beam search (dots_slots_beam): the groups' host records (B == 0: free), beam_of[row] = group index + 1 of a group row,
     // n_beam_hi = highest used index + 1 (what a step's group kernels are launched over; 0: a step launches nothing of this), and —
     // allocated by the first group — the device records, the completed-record buffers, the parents beside out_ids and the logprob
@@ -249,11 +256,12 @@ struct DotsEngine {
     // selection stage), whether any row returns logprobs (lp), whether any row carries logit rules (rules: the stage then gets their
     // table), whether any row holds a guide (guided: the mask kernel and the guides' tables), whether any row carries an n-gram rule (ngram:
     // the ban kernel and its bits), the draft count of a speculating step (spec: 0 = the plain step), whether that step draws the draft
-    // rows of sampled slots (draw: the two launches of launch_spec_draw); engine-wide sampling changes drop
+    // rows of sampled slots (draw: the two launches of launch_spec_draw), whether some guided row may speculate in it (gspec: the three
+    // launches that select the draft rows of guided slots under their guide); engine-wide sampling changes drop
     // the cache (dots_set_sampling), per-row ones live in device memory; beam: the group entries a step's beam kernels run over (0: none).  step_key() builds the key from the engine's state: a feature that
     // changes what a step launches adds a member here and a line there
     struct StepKey {
-        int rows, splits, out_cap, n_eos, part, rowp, lp, rules, guided, ngram, spec, draw, beam;
+        int rows, splits, out_cap, n_eos, part, rowp, lp, rules, guided, ngram, spec, draw, gspec, beam;
         bool operator==(const StepKey& o) const { return std::memcmp(this, &o, sizeof(StepKey)) == 0; }
     };
     static_assert(std::has_unique_object_representations_v<StepKey>, "StepKey is compared bytewise: plain ints, no padding");
@@ -348,6 +356,8 @@ int admit_tokens(const DotsEngine* e, int prompt, int max_new);
 // rows.hip: what a row is selected with
 StepState step_state(const DotsEngine* e, int advance, const int32_t* sel);
 bool spec_draws(const DotsEngine* e);
+bool spec_guides(const DotsEngine* e);
+GuideSel guide_sel(const DotsEngine* e);
 SpecState spec_state(const DotsEngine* e);
 hipError_t launch_row_stage(hipStream_t s, const float* logits, int V, int ld, int B, const RowSel& rs, float* am_val, int32_t* am_idx,
                             const StepState& st, const int32_t* ban_finished);

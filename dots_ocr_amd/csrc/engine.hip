@@ -279,6 +279,7 @@ DotsEngine::StepKey step_key(const DotsEngine* e, int rows, int n_splits, int ou
     k.ngram = e->stage.rows(ROW_NGRAM) > 0;
     k.spec = e->slot_mode ? e->spec_k : 0;
     k.draw = spec_draws(e);
+    k.gspec = spec_guides(e);
     k.beam = e->slot_mode ? e->n_beam_hi : 0;
     return k;
 }
@@ -555,8 +556,18 @@ int decode_step_launches(DotsEngine* e, int n_splits, int part) {
                          pend ? e->d_part_h : nullptr, pend_scale));
     if (spec_k) CK(launch_spec_argmax(s, sp, e->d_logits, c.vocab_size, c.vocab_size, rows, e->am_val, e->am_idx));
     // the candidates of the draft rows of sampled slots, before the selection stage moves out_lens: draft row j draws with counter out_lens + j
+    // guided slots that speculate (dots_set_speculation_guided): the state each live draft row is selected under, from the slot's state
+    // before anything commits; its allowed bits into the rows of guide_mask the stage does not use; its shaped partials (and values)
+    const GuideSel spec_guide = sp.gstate ? guide_sel(e) : GuideSel{};
+    if (spec_k && sp.gstate) {
+        if (B > c.max_batch) return e->fail(DOTS_E_CAPACITY, "%d rows x %d exceed max_batch %d", rows, spec_k + 1, c.max_batch);      // guide_mask / pen_logits hold max_batch rows
+        CK(launch_spec_guide_chain(s, sp, spec_guide, e->eos_ids, e->n_eos, rows));
+        CK(launch_guide_mask_drafts(s, spec_guide, rows, spec_k, sp.gstate));
+        CK(launch_spec_guide_select(s, sp, spec_guide, e->eos_ids, e->n_eos, e->d_logits, c.vocab_size, c.vocab_size, rows, e->pen_logits, e->am_val, e->am_idx));
+    }
     if (spec_k && sp.cand)
-        CK(launch_spec_draw(s, sp, e->d_logits, c.vocab_size, c.vocab_size, rows, e->d_rowp, e->d_row_thr, e->out_lens, e->am_val, e->am_idx));
+        CK(launch_spec_draw(s, sp, e->d_logits, c.vocab_size, c.vocab_size, rows, e->d_rowp, e->d_row_thr, e->out_lens, e->am_val, e->am_idx,
+                            sp.gstate ? e->pen_logits : nullptr));
     e->B_sel = rows;
     e->sel_now = e->d_sel;
     RET(select_tokens(e, 1));
@@ -566,7 +577,7 @@ int decode_step_launches(DotsEngine* e, int n_splits, int part) {
         // the grown output
         const StepState st = step_state(e, 1, e->d_sel);
         CK(launch_spec_accept(s, sp, st, rows, e->am_val, e->am_idx,
-                              e->d_stop ? StopSel{e->d_stop, e->tok_off, e->tok_bytes, c.vocab_size, 0} : StopSel{}));
+                              e->d_stop ? StopSel{e->d_stop, e->tok_off, e->tok_bytes, c.vocab_size, 0} : StopSel{}, spec_guide));
         if (e->spec_max_n > 0)
             CK(launch_ngram_draft(s, st.out_ids, st.out_lens, st.out_stride, st.finished, st.sel, sp.cls, sp.engine_greedy, rows, spec_k, e->spec_min_n,
                                   e->spec_max_n, e->sp_drafts, DOTS_MAX_SPEC_DRAFTS, e->sp_ndraft));

@@ -12,6 +12,7 @@
 // in global memory: at most 4096 states x 512 B = 2 MB, read-only for the whole launch, so it stays in L2.  Offsets are read coalesced
 // (thread i reads tok_off[i] and tok_off[i + 1]); the bytes of a token are read one by one, which only the surviving lanes pay for.
 // The 64 verdicts of a wave leave as one ballot and one 8-byte vector store by lane 0: no atomics, no read-modify-write of the mask.
+#include "common.h"
 #include "kernels.h"
 
 namespace {
@@ -19,19 +20,13 @@ namespace {
 constexpr int GM_THREADS = 256;
 constexpr int GM_TOKENS = 2048;           // tokens per workgroup: 8 per thread, 64 consecutive ones per wave and pass
 
-// grid (ceil(V / GM_TOKENS), rows)
-__global__ __launch_bounds__(GM_THREADS) void guide_mask_kernel(GuideSel g, const int32_t* __restrict__ sel) {
-    __shared__ uint16_t s_row[256];
-    const int b = blockIdx.y;
-    if (sel && !sel[b]) return;                                       // uniform per workgroup
-    const RowGuide rg = g.rows[b];
-    if (!rg.table) return;
-    const uint16_t* __restrict__ table = rg.table;
-    s_row[threadIdx.x] = table[(size_t)rg.state * 256 + threadIdx.x];
+// The allowed bits of the GM_TOKENS tokens of workgroup blockIdx.x at `state` of `table` into `out` (one row of the mask).  Called by all
+// GM_THREADS threads with uniform arguments; s_row: 256 entries of LDS
+DEVI void guide_mask_row(const GuideSel& g, const uint16_t* __restrict__ table, int state, uint32_t* __restrict__ out, uint16_t* s_row) {
+    s_row[threadIdx.x] = table[(size_t)state * 256 + threadIdx.x];
     __syncthreads();
     const int32_t* __restrict__ off = g.tok_off;
     const uint8_t* __restrict__ bytes = g.tok_bytes;
-    uint32_t* __restrict__ out = g.mask + (size_t)b * g.words;
     const int base = blockIdx.x * GM_TOKENS;
 #pragma unroll 1
     for (int k = 0; k < GM_TOKENS / GM_THREADS; ++k) {
@@ -52,6 +47,29 @@ __global__ __launch_bounds__(GM_THREADS) void guide_mask_kernel(GuideSel g, cons
         // words is even and i0 a multiple of 64: word i0 / 32 of a 256-byte aligned buffer is 8-byte aligned, and i0 / 32 + 1 < words
         if ((threadIdx.x & 63u) == 0) *reinterpret_cast<uint2*>(out + (i0 >> 5)) = make_uint2((uint32_t)bits, (uint32_t)(bits >> 32));
     }
+}
+
+// grid (ceil(V / GM_TOKENS), rows)
+__global__ __launch_bounds__(GM_THREADS) void guide_mask_kernel(GuideSel g, const int32_t* __restrict__ sel) {
+    __shared__ uint16_t s_row[256];
+    const int b = blockIdx.y;
+    if (sel && !sel[b]) return;                                       // uniform per workgroup
+    const RowGuide rg = g.rows[b];
+    if (!rg.table) return;
+    guide_mask_row(g, rg.table, rg.state, g.mask + (size_t)b * g.words, s_row);
+}
+
+// The draft rows of a speculating step.  grid (ceil(V / GM_TOKENS), rows * k): workgroup y serves step row r = rows + y =
+// j * rows + b with the table of slot b at the state the chain kernel (spec.hip) left for r; a dead, idle or unguided row (gstate < 0:
+// its slot then may hold no table) exits at once
+__global__ __launch_bounds__(GM_THREADS) void guide_mask_drafts_kernel(GuideSel g, int rows, const int32_t* __restrict__ gstate) {
+    __shared__ uint16_t s_row[256];
+    const int r = rows + blockIdx.y, b = r % rows;
+    const int state = gstate[r];
+    if (state < 0) return;                                            // uniform per workgroup
+    const RowGuide rg = g.rows[b];
+    if (!rg.table || state >= rg.n_states) return;                    // never: the chain walked this table
+    guide_mask_row(g, rg.table, state, g.mask + (size_t)r * g.words, s_row);
 }
 
 __global__ void set_row_guide_kernel(RowGuide* table, int row, RowGuide g) {
@@ -78,6 +96,14 @@ __global__ void guide_set_states_kernel(RowGuide* table, const int32_t* __restri
 hipError_t launch_guide_mask(hipStream_t s, const GuideSel& g, int B, const int32_t* sel) {
     if (!g.rows || !g.mask || !g.tok_off || !g.tok_bytes || B < 1 || B > DOTS_MAX_BATCH || g.V < 1 || g.words != guide_mask_words(g.V)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(guide_mask_kernel, dim3((g.V + GM_TOKENS - 1) / GM_TOKENS, B), dim3(GM_THREADS), 0, s, g, sel);
+    return hipGetLastError();
+}
+
+hipError_t launch_guide_mask_drafts(hipStream_t s, const GuideSel& g, int rows, int k, const int32_t* gstate) {
+    if (!g.rows || !g.mask || !g.tok_off || !g.tok_bytes || !gstate || rows < 1 || k < 1 || k > DOTS_MAX_SPEC_DRAFTS || rows * (k + 1) > DOTS_MAX_BATCH ||
+        g.V < 1 || g.words != guide_mask_words(g.V))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(guide_mask_drafts_kernel, dim3((g.V + GM_TOKENS - 1) / GM_TOKENS, rows * k), dim3(GM_THREADS), 0, s, g, rows, gstate);
     return hipGetLastError();
 }
 

@@ -219,6 +219,10 @@ hipError_t launch_set_row_rules(hipStream_t s, RowRules* table, float* img, int 
 // The allowed bits of every guided row of the launch (rows without a guide and rows that sel masks out are skipped), from each row's
 // current state: bit t = token t has bytes and walking them never leaves the automaton.  Runs before launch_select_rows.
 hipError_t launch_guide_mask(hipStream_t s, const GuideSel& g, int B, const int32_t* sel);
+// The allowed bits of the draft rows of a speculating step: row r = j * rows + b of g.mask, r in [rows, rows * (k + 1)), from
+// the table of slot b at state gstate[r] (launch_spec_guide_chain); a row with gstate[r] < 0 (dead, idle, unguided) is left alone.  The
+// same walk as launch_guide_mask; g.mask must hold rows * (k + 1) rows.
+hipError_t launch_guide_mask_drafts(hipStream_t s, const GuideSel& g, int rows, int k, const int32_t* gstate);
 // table[row] = g (with state = g.start), in stream order
 hipError_t launch_set_row_guide(hipStream_t s, RowGuide* table, int row, const RowGuide& g);
 // state = start for the n rows dst[0 .. n) (dst == nullptr: rows 0 .. n - 1) that hold a guide, in stream order (a prefill)
@@ -255,6 +259,9 @@ hipError_t launch_stop_fork_rows(hipStream_t s, RowStop* table, int src, const i
 // The kernels ask nothing else about a row; while engine_greedy == 0 (an engine-wide temperature) no row verifies a draft whatever its class.
 // cand [DOTS_MAX_BATCH][DOTS_MAX_SPEC_DRAFTS]: the candidate tokens of the live draft rows of SPEC_ROW_DRAW slots (spec_draw_kernel);
 // nullptr until a step runs that kernel.
+// gstate [DOTS_MAX_BATCH]: while a guided row may speculate (dots_set_speculation_guided), the automaton state every live draft row of a
+// guided slot is selected under, indexed by step row r = j * rows + b (launch_spec_guide_chain); -1 = the row verifies nothing under a
+// guide: dead, idle, or its slot holds none.  nullptr: no step launch asks about guides.
 #ifndef DOTS_MAX_SPEC_DRAFTS
 #define DOTS_MAX_SPEC_DRAFTS 15
 #endif
@@ -269,6 +276,7 @@ struct SpecState {
     unsigned long long* stats;
     const int32_t* cls;
     int32_t* cand;
+    int32_t* gstate;
     int32_t k, engine_greedy;
 };
 // the step's row arrays from the slots' state (st: the StepState of the selection stage; block_table [rows][max_pages]); an idle draft row
@@ -280,12 +288,27 @@ hipError_t launch_spec_argmax(hipStream_t s, const SpecState& sp, const float* l
 // draft row r = j * rows + b is selected with params[b] over logits row r with counter out_lens[b] + j, by the selection stage's own
 // arithmetic (select_dev.h), into sp.cand[b][j - 1].  thr [DOTS_MAX_BATCH] is RowSel::thr: the stage uses entries [0, rows), the draft rows
 // entries [rows, rows * (k + 1)).  Two launches of rows * k workgroups; every other draft row's workgroup exits at once.
+// shaped (with sp.gstate; else nullptr): [rows * (k + 1)][V], a draft row with sp.gstate[r] >= 0 reads its row of it instead of the logits
+// (launch_spec_guide_select left the values and the partials of their maximum there).
 hipError_t launch_spec_draw(hipStream_t s, const SpecState& sp, const float* logits, int V, int ld, int rows, const RowParams* params, uint32_t* thr,
-                            const int32_t* out_lens, const float* pval, const int32_t* pidx);
+                            const int32_t* out_lens, const float* pval, const int32_t* pidx, const float* shaped = nullptr);
+// Guided slots of a speculating step (sp.gstate != nullptr), after the lm_head and before anything is selected:
+// chain: sp.gstate[j * rows + b], j = 1 .. k, = the state of slot b (guide.rows[b].state, which nothing has moved yet) walked over the bytes
+//   of drafts 1 .. j, for j <= n_live[b]; -1 from the first draft on that has no bytes, is one of eos_ids or meets GUIDE_DEAD, for j > n_live[b]
+//   and for a slot without a guide.  One launch of one wave: lane b serves slot b.
+// select: for every draft row with sp.gstate[r] >= 0 the shaped logits (the raw value; -inf where bit r of guide.mask is clear; an id of
+//   eos_ids is allowed iff the state is accepting) — the guided branch of the selection stage without rules or penalty — as arg-max
+//   partials over pval / pidx row r (replacing launch_spec_argmax's) and, for a SPEC_ROW_DRAW slot, as values in shaped [..][V] row r.
+hipError_t launch_spec_guide_chain(hipStream_t s, const SpecState& sp, const GuideSel& guide, const int32_t* eos_ids, int n_eos, int rows);
+hipError_t launch_spec_guide_select(hipStream_t s, const SpecState& sp, const GuideSel& guide, const int32_t* eos_ids, int n_eos, const float* logits,
+                                    int V, int ld, int rows, float* shaped, float* pval, int32_t* pidx);
 // after the selection stage committed the first `rows` rows: per slot, while the row is not finished and draft j equals the token just
 // committed, commit the candidate of draft row j + 1 (its arg max, or sp.cand for a SPEC_ROW_DRAW slot) through commit_token: EOS, cap,
-// output and — stop.rows != nullptr — the row's stop automaton as in a sequential step; counts into sp.stats and clears the slot's drafts
-hipError_t launch_spec_accept(hipStream_t s, const SpecState& sp, const StepState& st, int rows, const float* pval, const int32_t* pidx, const StopSel& stop);
+// output and — stop.rows != nullptr — the row's stop automaton as in a sequential step; counts into sp.stats and clears the slot's drafts.
+// guide (with sp.gstate; else GuideSel{}): a slot that holds a guide commits with it, so its automaton advances as in a sequential step, and
+// its walk also ends at a draft row with sp.gstate < 0
+hipError_t launch_spec_accept(hipStream_t s, const SpecState& sp, const StepState& st, int rows, const float* pval, const int32_t* pidx, const StopSel& stop,
+                              const GuideSel& guide = GuideSel{});
 // drafts[b * draft_stride + 0 .. n_draft[b]) = the continuation of the longest suffix n-gram (min_n .. max_n) of out_ids[b * out_stride +
 // 0 .. out_lens[b]) that occurred before, at most k ids (the rule: include/dots_ocr_hip.h).  Rows that sel masks out, finished rows, rows
 // with cls[b] == SPEC_ROW_NONE, and every row while engine_greedy == 0 draft nothing (finished / sel / cls may be nullptr).

@@ -603,6 +603,54 @@ int dots_op_ngram_draft(DotsEngine* e, const int32_t* hist_dev, const int32_t* h
     return DOTS_OK;
 }
 
+int dots_op_spec_guide_masks(DotsEngine* e, int rows, int k, const int32_t* guide_ids_host, const int32_t* states_host, const int32_t* drafts_host,
+                             const int32_t* n_live_host, int32_t* states_out_host, uint32_t* mask_out_host) {
+    if (!e || !guide_ids_host || !states_host || !drafts_host || !n_live_host || !states_out_host || !mask_out_host)
+        return e ? e->fail(DOTS_E_INVALID, "null argument") : DOTS_E_INVALID;
+    if (rows < 1 || k < 1 || k > DOTS_MAX_SPEC_DRAFTS || rows * (k + 1) > DOTS_MAX_BATCH)
+        return e->fail(DOTS_E_INVALID, "spec_guide_masks: rows >= 1, k in [1, %d], rows x (k + 1) <= %d", DOTS_MAX_SPEC_DRAFTS, DOTS_MAX_BATCH);
+    if (!e->tok_off) return e->fail(DOTS_E_STATE, "the token bytes are not set (dots_set_token_bytes): a guide cannot judge any token");
+    const int V = e->cfg.vocab_size, R = rows * (k + 1), words = guide_mask_words(V);
+    std::vector<RowGuide> tab(DOTS_MAX_BATCH, RowGuide{});
+    std::vector<int32_t> drafts((size_t)DOTS_MAX_BATCH * DOTS_MAX_SPEC_DRAFTS, 0);
+    for (int b = 0; b < rows; ++b) {
+        for (int j = 0; j < k; ++j) {
+            const int t = drafts_host[b * k + j];
+            if (t < 0 || t >= V) return e->fail(DOTS_E_INVALID, "row %d: draft id %d out of range [0, %d)", b, t, V);
+            drafts[(size_t)b * DOTS_MAX_SPEC_DRAFTS + j] = t;
+        }
+        const int id = guide_ids_host[b];
+        if (id < 0) continue;
+        if (id >= (int)e->guides.size() || !e->guides[id].table) return e->fail(DOTS_E_INVALID, "row %d: no guide %d", b, id);
+        const DotsEngine::Guide& g = e->guides[id];
+        if (states_host[b] < 0 || states_host[b] >= g.n_states) return e->fail(DOTS_E_INVALID, "row %d: state %d outside [0, %d)", b, states_host[b], g.n_states);
+        tab[b] = RowGuide{g.table, g.accepting, g.n_states, g.start, states_host[b], 0};
+    }
+    CK(hipSetDevice(e->device));
+    Scratch sc(e);
+    RowGuide* gtab = nullptr;
+    uint32_t* gmask = nullptr;
+    int32_t *d_drafts = nullptr, *d_live = nullptr, *d_state = nullptr;
+    CK(sc.get(&gtab, DOTS_MAX_BATCH));
+    CK(sc.get(&gmask, (size_t)R * words));                 // zeroed: a row the kernels leave alone reads as "nothing allowed"
+    CK(sc.get(&d_drafts, drafts.size()));
+    CK(sc.get(&d_live, DOTS_MAX_BATCH));
+    CK(sc.get(&d_state, DOTS_MAX_BATCH));
+    CK(hipMemcpyAsync(gtab, tab.data(), DOTS_MAX_BATCH * sizeof(RowGuide), hipMemcpyHostToDevice, e->stream));
+    CK(hipMemcpyAsync(d_drafts, drafts.data(), drafts.size() * 4, hipMemcpyHostToDevice, e->stream));
+    CK(hipMemcpyAsync(d_live, n_live_host, (size_t)rows * 4, hipMemcpyHostToDevice, e->stream));
+    CK(hipMemsetAsync(d_state, 0xFF, DOTS_MAX_BATCH * 4, e->stream));
+    SpecState sp{};
+    sp.drafts = d_drafts; sp.n_live = d_live; sp.gstate = d_state; sp.k = k;
+    const GuideSel g{gtab, gmask, e->tok_off, e->tok_bytes, words, V};
+    CK(launch_spec_guide_chain(e->stream, sp, g, e->eos_ids, e->n_eos, rows));
+    CK(launch_guide_mask_drafts(e->stream, g, rows, k, d_state));
+    CK(hipMemcpyAsync(states_out_host, d_state, (size_t)R * 4, hipMemcpyDeviceToHost, e->stream));
+    CK(hipMemcpyAsync(mask_out_host, gmask, (size_t)R * words * 4, hipMemcpyDeviceToHost, e->stream));
+    CK(hipStreamSynchronize(e->stream));                   // the host vectors above are free again, the outputs are there
+    return DOTS_OK;
+}
+
 int dots_op_logprobs(DotsEngine* e, const float* logits_dev, int B, int V, int ld, const int32_t* top_n_host, const int32_t* chosen_dev,
                      float* tok_lp_dev, int32_t* top_ids_dev, float* top_lp_dev) {
     if (!chosen_dev || !tok_lp_dev || !top_ids_dev || !top_lp_dev) return e ? e->fail(DOTS_E_INVALID, "bad logprobs arguments") : DOTS_E_INVALID;

@@ -10,8 +10,9 @@
 #endif
 
 enum RowFeature { ROW_PARAMS, ROW_RULES, ROW_GUIDE, ROW_NGRAM, ROW_STOP, ROW_FEATURES };
-// which staged rows may verify drafts (dots_set_speculation_rows): the values of DOTS_SPEC_ROWS_*
-enum SpecRows { SPEC_ROWS_SAMPLED = 1, SPEC_ROWS_STOP = 2, SPEC_ROWS_ALL = 3 };
+// which staged rows may verify drafts: SAMPLED and STOP are the values of DOTS_SPEC_ROWS_* (dots_set_speculation_rows, whose
+// every bit is SPEC_ROWS_ALL); SPEC_ROWS_GUIDED is internal: the engine ORs it in from dots_set_speculation_guided
+enum SpecRows { SPEC_ROWS_SAMPLED = 1, SPEC_ROWS_STOP = 2, SPEC_ROWS_ALL = 3, SPEC_ROWS_GUIDED = 4 };
 
 struct RowStage {
     bool has(int row, RowFeature f) const { return (bits[row] >> f) & 1u; }
@@ -37,12 +38,14 @@ struct RowStage {
         return left;
     }
     // May the row verify drafts?  A row without features does (plain greedy).  A staged row does iff every feature it
-    // carries is one the mode lets through — own parameters under SPEC_ROWS_SAMPLED, stop strings under SPEC_ROWS_STOP, nothing else under
-    // any mode: penalties, rules, a guide and an n-gram rule depend on the history of rejected tokens — and its parameters, if it has any,
-    // carry no penalty (has_pen: the caller's fact about them; ignored for a row without ROW_PARAMS).  Logprobs and the engine-wide
-    // temperature are not stage features: the caller adds them.
+    // carries is one the mode lets through — own parameters under SPEC_ROWS_SAMPLED, stop strings under SPEC_ROWS_STOP, a guide under
+    // SPEC_ROWS_GUIDED (its state depends on the committed tokens only, so a draft row's state is known at the head of the step), nothing
+    // else under any mode: penalties and an n-gram rule depend on the history of rejected tokens, rules stay sequential — and its
+    // parameters, if it has any, carry no penalty (has_pen: the caller's fact about them; ignored for a row without ROW_PARAMS).  Logprobs
+    // and the engine-wide temperature are not stage features: the caller adds them.
     bool speculates(int row, bool has_pen, int mode) const {
-        const unsigned open = ((mode & SPEC_ROWS_SAMPLED) ? 1u << ROW_PARAMS : 0u) | ((mode & SPEC_ROWS_STOP) ? 1u << ROW_STOP : 0u);
+        const unsigned open = ((mode & SPEC_ROWS_SAMPLED) ? 1u << ROW_PARAMS : 0u) | ((mode & SPEC_ROWS_STOP) ? 1u << ROW_STOP : 0u) |
+                              ((mode & SPEC_ROWS_GUIDED) ? 1u << ROW_GUIDE : 0u);
         if (bits[row] & ~open) return false;
         return !(has(row, ROW_PARAMS) && has_pen);
     }

@@ -9,7 +9,9 @@ namespace {
 // features and the penalty of the row's parameters through RowStage::speculates, and logprobs (not a stage feature).  The engine-wide
 // temperature is not a row's fact: the kernels get it as engine_greedy.
 int spec_row_class(const DotsEngine* e, int row) {
-    if (e->row_lp[row] >= 0 || !e->stage.speculates(row, e->row_pen[row], e->spec_rows)) return SPEC_ROW_NONE;
+    const int mode = e->spec_rows | (e->spec_guided ? SPEC_ROWS_GUIDED : 0);
+    if (e->row_lp[row] >= 0 || !e->stage.speculates(row, e->row_pen[row], mode)) return SPEC_ROW_NONE;
+    if (e->stage.staged(row) && !e->stage.has(row, ROW_PARAMS) && e->row_entry_sampled[row]) return SPEC_ROW_NONE;
     return e->stage.has(row, ROW_PARAMS) && e->row_sampled[row] ? SPEC_ROW_DRAW : SPEC_ROW_ARGMAX;
 }
 
@@ -99,11 +101,18 @@ int ensure_stop_state(DotsEngine* e) {
 // what a row without parameters of its own is selected with once the per-row stage owns it (logit rules): the engine-wide setting as it stands
 RowParams engine_row_params(const DotsEngine* e) { return RowParams{e->temperature, e->top_p, 0, 1.f, 0.f, 0.f, e->seed}; }
 
+// row `row`, which has no parameters of its own, takes the engine-wide setting as its stage entry (stream ordered)
+int write_engine_entry(DotsEngine* e, int row) {
+    CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, engine_row_params(e), 1));
+    e->row_entry_sampled[row] = e->temperature > 0.f;
+    return DOTS_OK;
+}
+
 // Row `row` takes feature f: it enters the per-row stage unless another feature holds it there already, with the engine-wide setting as
 // its entry and the own flag set (stream ordered).  Own parameters are that entry themselves: their setter has written it.
 int enter_row_stage(DotsEngine* e, int row, RowFeature f) {
     RET(ensure_row_table(e));
-    if (e->stage.attach(row, f) && f != ROW_PARAMS) CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, engine_row_params(e), 1));
+    if (e->stage.attach(row, f) && f != ROW_PARAMS) RET(write_engine_entry(e, row));
     return sync_spec_class(e, row);
 }
 
@@ -112,7 +121,7 @@ int enter_row_stage(DotsEngine* e, int row, RowFeature f) {
 int leave_row_stage(DotsEngine* e, int row, RowFeature f) {
     if (!e->stage.has(row, f)) return DOTS_OK;
     if (e->stage.detach(row, f)) CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, RowParams{}, 0));
-    else if (f == ROW_PARAMS) CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, engine_row_params(e), 1));
+    else if (f == ROW_PARAMS) RET(write_engine_entry(e, row));
     return sync_spec_class(e, row);
 }
 
@@ -160,9 +169,20 @@ bool spec_draws(const DotsEngine* e) {
     return e->slot_mode && e->spec_k > 0 && (e->spec_rows & SPEC_ROWS_SAMPLED) && e->stage.rows(ROW_PARAMS) > 0;
 }
 
+// may some guided row verify drafts in a speculating step (the launches under StepKey::gspec)?  A host count: the switch is on and at least
+// one row holds a guide.  With dots_set_speculation_guided off a step launches what it always did
+bool spec_guides(const DotsEngine* e) {
+    return e->slot_mode && e->spec_k > 0 && e->spec_guided && e->stage.rows(ROW_GUIDE) > 0;
+}
+
 SpecState spec_state(const DotsEngine* e) {
     return SpecState{e->sp_drafts, e->sp_ndraft, e->sp_nlive, e->sp_tokens, e->sp_ctx, e->sp_table, e->sp_stats, e->sp_cls,
-                     spec_draws(e) ? e->sp_cand : nullptr, e->spec_k, e->temperature > 0.f ? 0 : 1};
+                     spec_draws(e) ? e->sp_cand : nullptr, spec_guides(e) ? e->sp_gstate : nullptr, e->spec_k, e->temperature > 0.f ? 0 : 1};
+}
+
+// what a launch needs to honour the guides (the row table exists once a row has taken one)
+GuideSel guide_sel(const DotsEngine* e) {
+    return GuideSel{e->d_guides, e->guide_mask, e->tok_off, e->tok_bytes, guide_mask_words(e->cfg.vocab_size), e->cfg.vocab_size};
 }
 
 // The per-row selection stage over `rs`: the n-gram rows' banned bits, the guided rows' allowed bits (neither kernel reads what the other
@@ -194,7 +214,7 @@ int select_tokens(DotsEngine* e, int advance) {
         if (e->stage.rows(ROW_NGRAM) > 0)          // the n-gram rows' banned bits from their own output so far, before the stage reads the logits
             rs.ngram = NgramSel{e->d_ngram, e->ngram_mask, ngram_mask_words(c.vocab_size), c.vocab_size};
         if (e->stage.rows(ROW_GUIDE) > 0)          // the guided rows' allowed bits from their current states, before the stage reads the logits
-            rs.guide = GuideSel{e->d_guides, e->guide_mask, e->tok_off, e->tok_bytes, guide_mask_words(c.vocab_size), c.vocab_size};
+            rs.guide = guide_sel(e);
         CK(launch_row_stage(e->stream, e->d_logits, c.vocab_size, c.vocab_size, e->B_sel, rs, e->am_val, e->am_idx, st, st.finished));
         if (e->temperature > 0.f)
             CK(launch_sample_step(e->stream, e->d_logits, c.vocab_size, c.vocab_size, e->B_sel, e->temperature, e->top_p, e->seed, st, e->d_row_own));
@@ -395,7 +415,7 @@ int dots_set_row_logit_rules(DotsEngine* e, int row, const DotsLogitRules* r) {
     CK(launch_set_row_rules(e->stream, e->d_rules, e->rule_img, row, V, rr, e->rule_stage, n_allowed, e->rule_stage + V,
                             reinterpret_cast<const float*>(e->rule_stage + V + DOTS_MAX_LOGIT_BIAS), r->n_bias));
     // not enter_row_stage(): the entry is rewritten whenever the row has no parameters of its own, staged already or not (known wart)
-    if (!e->stage.has(row, ROW_PARAMS)) CK(launch_set_row_params(e->stream, e->d_rowp, e->d_row_own, row, engine_row_params(e), 1));
+    if (!e->stage.has(row, ROW_PARAMS)) RET(write_engine_entry(e, row));
     e->stage.attach(row, ROW_RULES);
     return sync_spec_class(e, row);
 }
@@ -619,6 +639,19 @@ int dots_set_speculation_rows(DotsEngine* e, int flags) {
     e->spec_rows = flags;
     drop_step_graphs(e);                                     // a captured step bakes in whether it draws the draft rows of sampled slots
     return upload_spec_classes(e);                           // free slots may hold features: every row's class under the new setting
+}
+
+int dots_set_speculation_guided(DotsEngine* e, int on) {
+    if (!e) return DOTS_E_INVALID;
+    if (e->slot_mode)
+        for (int b = 0; b < e->cfg.max_batch; ++b)
+            if (e->slot_active[b]) return e->fail(DOTS_E_STATE, "guided speculation cannot change while slot %d is occupied", b);
+    CK(hipSetDevice(e->device));
+    if (on && !e->sp_gstate) CK(e->alloc(&e->sp_gstate, (size_t)DOTS_MAX_BATCH));
+    if ((on != 0) == (e->spec_guided != 0)) return DOTS_OK;
+    e->spec_guided = on != 0;
+    drop_step_graphs(e);                                     // a captured step bakes in whether it selects the draft rows of guided slots
+    return upload_spec_classes(e);                           // free slots may hold guides: every row's class under the new setting
 }
 
 int dots_set_row_drafts(DotsEngine* e, int row, const int32_t* ids_host, int n) {

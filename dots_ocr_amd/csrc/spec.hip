@@ -12,6 +12,9 @@
 //   spec_argmax_kernel   after the lm_head: the arg-max partials of the live draft rows (the merge rule of argmax_partial_kernel)
 //   spec_thresh_kernel, spec_draw_kernel   then, only while a row with parameters may speculate (dots_set_speculation_rows): the candidates
 //                        of the live draft rows of SPEC_ROW_DRAW slots, by the selection stage's own arithmetic (select_dev.h)
+//   spec_guide_chain_kernel, (guide_mask_drafts_kernel, guided.hip), spec_guide_select_kernel   after spec_argmax_kernel, only while a
+//                        guided row may speculate (dots_set_speculation_guided): the state every live draft row of a guided slot is
+//                        selected under, its allowed bits, and its arg-max partials (and values, for a sampled slot) under the guide
 //   spec_accept_kernel   after the selection stage: walks a slot's drafts and commits through commit_token while they hold
 //   ngram_draft_kernel   end of the step: the next step's drafts from the row's own output (prompt lookup without the prompt)
 //
@@ -83,9 +86,16 @@ __global__ __launch_bounds__(256) void spec_argmax_kernel(const float* __restric
 // penalty, rules, guide or n-gram rule, so the raw logits are what the stage would read), params[b], the softmax maximum from the partials
 // spec_argmax_kernel left for r, and the counter out_lens[b] + j — out_lens as the head of the step saw it: both kernels run before the
 // selection stage commits.
+// A draft row selected under a guide (sp.gstate[r] >= 0) reads its row of `shaped` instead, as select_thresh_kernel / select_rows_kernel
+// read the shaped values of a guided sampled row: spec_guide_select_kernel left them there, and their maximum in the partials of r.
+DEVI const float* spec_draw_row(const SpecState& sp, const float* logits, int ld, const float* shaped, int V, int r) {
+    return sp.gstate && sp.gstate[r] >= 0 ? shaped + (size_t)r * V : logits + (size_t)r * ld;
+}
+
 __global__ __launch_bounds__(SEL_THREADS) void spec_thresh_kernel(const float* __restrict__ logits, int V, int ld, int rows, SpecState sp,
                                                                   const RowParams* __restrict__ params, uint32_t* __restrict__ thr,
-                                                                  const float* __restrict__ pval, const int32_t* __restrict__ pidx) {
+                                                                  const float* __restrict__ pval, const int32_t* __restrict__ pidx,
+                                                                  const float* __restrict__ shaped) {
     __shared__ SelLds L;
     const int r = rows + blockIdx.x, j = r / rows, b = r - j * rows;
     if (j > sp.n_live[b] || sp.cls[b] != SPEC_ROW_DRAW) return;      // uniform per workgroup
@@ -96,13 +106,13 @@ __global__ __launch_bounds__(SEL_THREADS) void spec_thresh_kernel(const float* _
         return;
     }
     merge_partials(pval, pidx, r, &L.best, &L.bi);
-    sel_threshold(logits + (size_t)r * ld, V, p, L.best, thr + r, L);
+    sel_threshold(spec_draw_row(sp, logits, ld, shaped, V, r), V, p, L.best, thr + r, L);
 }
 
 __global__ __launch_bounds__(SEL_THREADS) void spec_draw_kernel(const float* __restrict__ logits, int V, int ld, int rows, SpecState sp,
                                                                 const RowParams* __restrict__ params, const uint32_t* __restrict__ thr,
                                                                 const int32_t* __restrict__ out_lens, const float* __restrict__ pval,
-                                                                const int32_t* __restrict__ pidx) {
+                                                                const int32_t* __restrict__ pidx, const float* __restrict__ shaped) {
     __shared__ float s_best;
     __shared__ int s_bi;
     __shared__ DrawLds D;
@@ -111,8 +121,89 @@ __global__ __launch_bounds__(SEL_THREADS) void spec_draw_kernel(const float* __r
     merge_partials(pval, pidx, r, &s_best, &s_bi);
     const RowParams p = params[b];
     int tok = -1;
-    if (p.temperature > 0.f) tok = sel_draw(logits + (size_t)r * ld, V, p, s_best, thr[r], (uint32_t)(out_lens[b] + j), D);
+    if (p.temperature > 0.f) tok = sel_draw(spec_draw_row(sp, logits, ld, shaped, V, r), V, p, s_best, thr[r], (uint32_t)(out_lens[b] + j), D);
     if (threadIdx.x == 0) sp.cand[b * DOTS_MAX_SPEC_DRAFTS + j - 1] = tok >= 0 ? tok : s_bi;      // no token: the arg max, as select_rows_kernel
+}
+
+// The states of the draft rows of guided slots.  grid (1), one wave: lane b serves slot b.  Draft row (b, j) carries draft j as its input, so
+// the token it selects follows drafts 1 .. j: it is selected under rows[b].state — which nothing has moved yet in this step — walked over
+// their bytes, a pure function of values known here.  If drafts 1 .. j are accepted that is bitwise the state commit_token will have left
+// by then; if they are not, nobody reads the row.  A draft the guide could not have committed at its position — no bytes, an EOS id (it
+// finishes the row and is not walked), a byte without a transition — ends the chain: its row and every later one get -1, and so do the
+// rows past n_live and the rows of a slot without a guide.
+__global__ __launch_bounds__(64) void spec_guide_chain_kernel(SpecState sp, GuideSel g, const int32_t* __restrict__ eos_ids, int n_eos, int rows) {
+    const int b = threadIdx.x;
+    if (b >= rows) return;
+    const RowGuide rg = g.rows[b];
+    const int nl = rg.table ? sp.n_live[b] : 0;
+    uint32_t s = (uint32_t)rg.state;
+    bool dead = false;
+    for (int j = 1; j <= sp.k; ++j) {
+        dead = dead || j > nl;
+        if (!dead) {
+            const int tok = sp.drafts[b * DOTS_MAX_SPEC_DRAFTS + j - 1];
+            dead = tok < 0 || tok >= g.V;
+            int i = 0, end = 0;
+            if (!dead) { i = g.tok_off[tok]; end = g.tok_off[tok + 1]; }
+            dead = dead || i >= end;
+            for (int e = 0; e < n_eos; ++e) dead = dead || tok == eos_ids[e];
+            for (; i < end && !dead; ++i) {
+                s = rg.table[(size_t)s * 256 + g.tok_bytes[i]];
+                dead = s == GUIDE_DEAD;
+            }
+        }
+        sp.gstate[j * rows + b] = dead ? -1 : (int32_t)s;
+    }
+}
+
+// The arg-max partials of the draft rows selected under a guide, and the shaped values of those a sampler will read.  grid (ARGMAX_CHUNKS,
+// rows * k) as spec_argmax_kernel, after it: a row with sp.gstate[r] >= 0 overwrites the raw partials that kernel left for r, every other
+// row exits at once.  The values are those of the guided branch of select_partial_kernel (decode.hip) for a row without rules or penalty —
+// the raw logit, -inf where the row's bit is clear, an engine EOS id allowed iff the state is accepting whatever its bit — in the same
+// chunks under the same merge rule, so the partials are what the stage would leave for the sequential step at that position.
+__global__ __launch_bounds__(256) void spec_guide_select_kernel(const float* __restrict__ logits, int V, int ld, int rows, SpecState sp, GuideSel g,
+                                                                const int32_t* __restrict__ eos_ids, int n_eos, float* __restrict__ shaped_rows,
+                                                                float* __restrict__ pval, int32_t* __restrict__ pidx) {
+    __shared__ float sv[4];
+    __shared__ int si[4];
+    __shared__ int s_kill[16], s_nkill;
+    const int c = blockIdx.x, r = rows + blockIdx.y, j = r / rows, b = r - j * rows;
+    const int state = sp.gstate[r];
+    if (state < 0) return;                                            // uniform per workgroup
+    const int per = (V + ARGMAX_CHUNKS - 1) / ARGMAX_CHUNKS;
+    const int lo = c * per, hi = min(V, lo + per);
+    const bool accepting = g.rows[b].accepting[state] != 0;
+    // the EOS ids that fall into this chunk: the guide's bit does not speak for them
+    if (threadIdx.x == 0) s_nkill = 0;
+    __syncthreads();
+    if ((int)threadIdx.x < min(n_eos, 16)) {
+        const int id = eos_ids[threadIdx.x];
+        if (id >= lo && id < hi) s_kill[atomicAdd(&s_nkill, 1)] = id;
+    }
+    __syncthreads();
+    const int n_kill = s_nkill;
+    const float* row = logits + (size_t)r * ld;
+    const uint32_t* gbits = g.mask + (size_t)r * g.words;
+    float* shaped = sp.cls[b] == SPEC_ROW_DRAW ? shaped_rows + (size_t)r * V : nullptr;      // a greedy slot needs the arg max only
+    float best = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int i = lo + threadIdx.x; i < hi; i += 256) {
+        float l = row[i];
+        bool term = false;
+        for (int k = 0; k < n_kill; ++k) term = term || s_kill[k] == i;
+        if (term ? !accepting : !((gbits[i >> 5] >> (i & 31)) & 1u)) l = -INFINITY;
+        if (shaped) shaped[i] = l;
+        argmax_merge(best, bi, l, i);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) argmax_merge(best, bi, __shfl_xor(best, o, 64), __shfl_xor(bi, o, 64));
+    if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = best; si[threadIdx.x >> 6] = bi; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < 4; ++k) argmax_merge(best, bi, sv[k], si[k]);
+        pval[r * ARGMAX_CHUNKS + c] = best;
+        pidx[r * ARGMAX_CHUNKS + c] = bi;
+    }
 }
 
 // grid (rows), one wave.  Row 0's token is committed (the selection stage ran); draft j is right iff it equals the token committed before
@@ -122,12 +213,17 @@ __global__ __launch_bounds__(SEL_THREADS) void spec_draw_kernel(const float* __r
 // nothing).  That is exactly what commit_row (decode.hip) does for a speculating row in a sequential step: such a row has no penalty (no
 // count to add), no rules (rules == nullptr) and no guide (commit_token reads the guide only through rows[b].table, which is null), so
 // EOS, the cap, min_tokens and the hit record come out of the same code, and a match finishes the row mid-walk.
+// A slot that holds a guide (it speculates only under dots_set_speculation_guided, and then sp.gstate and guide.rows are set) commits with
+// the guide, again as commit_row does: the automaton advances by the bytes of every token of the walk, and an EOS the final state forced
+// finishes the row mid-walk.  Its walk also ends at a draft row the chain marked dead: the draft there is not a token the guide could have
+// committed, so if it equals what was committed that was the all -inf fallback (id 0, the state did not move) and nothing past it is verified.
 __global__ __launch_bounds__(64) void spec_accept_kernel(SpecState sp, StepState st, int rows, const float* __restrict__ pval,
-                                                         const int32_t* __restrict__ pidx, StopSel stop) {
+                                                         const int32_t* __restrict__ pidx, StopSel stop, GuideSel guide) {
     __shared__ int32_t s_tok[DOTS_MAX_SPEC_DRAFTS];
     const int b = blockIdx.x, lane = threadIdx.x;
     const int nl = sp.n_live[b];                                      // uniform
     const bool drawn = sp.cand && sp.cls[b] == SPEC_ROW_DRAW;         // uniform
+    const bool guided = sp.gstate && guide.rows && guide.rows[b].table;      // uniform
     for (int j = 0; j < nl; ++j) {
         if (drawn) {
             if (lane == 0) s_tok[j] = sp.cand[b * DOTS_MAX_SPEC_DRAFTS + j];
@@ -146,7 +242,10 @@ __global__ __launch_bounds__(64) void spec_accept_kernel(SpecState sp, StepState
     if (nl < 0) return;
     int acc = 0;
     while (acc < nl && !st.finished[b] && sp.drafts[b * DOTS_MAX_SPEC_DRAFTS + acc] == st.cur_tokens[b]) {
-        if (stop.rows) commit_token(st, b, s_tok[acc], nullptr, nullptr, &stop);
+        if (guided && sp.gstate[(acc + 1) * rows + b] < 0) break;
+        if (guided && stop.rows) commit_token(st, b, s_tok[acc], nullptr, &guide, &stop);
+        else if (guided) commit_token(st, b, s_tok[acc], nullptr, &guide);
+        else if (stop.rows) commit_token(st, b, s_tok[acc], nullptr, nullptr, &stop);
         else commit_token(st, b, s_tok[acc]);
         ++acc;
     }
@@ -235,18 +334,46 @@ hipError_t launch_spec_argmax(hipStream_t s, const SpecState& sp, const float* l
 }
 
 hipError_t launch_spec_draw(hipStream_t s, const SpecState& sp, const float* logits, int V, int ld, int rows, const RowParams* params, uint32_t* thr,
-                            const int32_t* out_lens, const float* pval, const int32_t* pidx) {
+                            const int32_t* out_lens, const float* pval, const int32_t* pidx, const float* shaped) {
     if (!spec_ok(sp, rows) || !sp.cand || !logits || !params || !thr || !out_lens || !pval || !pidx || V < 1 || ld < V) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(spec_thresh_kernel, dim3(rows * sp.k), dim3(SEL_THREADS), 0, s, logits, V, ld, rows, sp, params, thr, pval, pidx);
+    if (sp.gstate && !shaped) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(spec_thresh_kernel, dim3(rows * sp.k), dim3(SEL_THREADS), 0, s, logits, V, ld, rows, sp, params, thr, pval, pidx, shaped);
     hipLaunchKernelGGL(spec_draw_kernel, dim3(rows * sp.k), dim3(SEL_THREADS), 0, s, logits, V, ld, rows, sp, params, (const uint32_t*)thr, out_lens, pval,
-                       pidx);
+                       pidx, shaped);
     return hipGetLastError();
 }
 
-hipError_t launch_spec_accept(hipStream_t s, const SpecState& sp, const StepState& st, int rows, const float* pval, const int32_t* pidx, const StopSel& stop) {
+namespace {
+bool spec_guide_ok(const SpecState& sp, const GuideSel& g, const int32_t* eos_ids, int n_eos) {
+    return sp.gstate && g.rows && g.mask && g.tok_off && g.tok_bytes && g.V >= 1 && g.words == guide_mask_words(g.V) && n_eos >= 0 && n_eos <= 16 &&
+           (n_eos == 0 || eos_ids);
+}
+}  // namespace
+
+hipError_t launch_spec_guide_chain(hipStream_t s, const SpecState& sp, const GuideSel& guide, const int32_t* eos_ids, int n_eos, int rows) {
+    // of sp the kernel reads drafts, n_live and k and writes gstate: the single-kernel entry point (ops.hip) fills in no more
+    if (!sp.drafts || !sp.n_live || sp.k < 1 || sp.k > DOTS_MAX_SPEC_DRAFTS || rows < 1 || rows * (sp.k + 1) > DOTS_MAX_BATCH ||
+        !spec_guide_ok(sp, guide, eos_ids, n_eos))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(spec_guide_chain_kernel, dim3(1), dim3(64), 0, s, sp, guide, eos_ids, n_eos, rows);
+    return hipGetLastError();
+}
+
+hipError_t launch_spec_guide_select(hipStream_t s, const SpecState& sp, const GuideSel& guide, const int32_t* eos_ids, int n_eos, const float* logits,
+                                    int V, int ld, int rows, float* shaped, float* pval, int32_t* pidx) {
+    if (!spec_ok(sp, rows) || !spec_guide_ok(sp, guide, eos_ids, n_eos) || !logits || !shaped || !pval || !pidx || V != guide.V || ld < V)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(spec_guide_select_kernel, dim3(ARGMAX_CHUNKS, rows * sp.k), dim3(256), 0, s, logits, V, ld, rows, sp, guide, eos_ids, n_eos, shaped,
+                       pval, pidx);
+    return hipGetLastError();
+}
+
+hipError_t launch_spec_accept(hipStream_t s, const SpecState& sp, const StepState& st, int rows, const float* pval, const int32_t* pidx, const StopSel& stop,
+                              const GuideSel& guide) {
     if (!spec_ok(sp, rows) || !pval || !pidx) return hipErrorInvalidValue;
     if (stop.rows && (!stop.tok_off || !stop.tok_bytes)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(spec_accept_kernel, dim3(rows), dim3(64), 0, s, sp, st, rows, pval, pidx, stop);
+    if (guide.rows && (!sp.gstate || !guide.tok_off || !guide.tok_bytes)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(spec_accept_kernel, dim3(rows), dim3(64), 0, s, sp, st, rows, pval, pidx, stop, guide);
     return hipGetLastError();
 }
 

@@ -390,6 +390,8 @@ def _prototypes(lib):
         "dots_row_stop_hit": (i32, [vp, i32, P(i32)]),
         "dots_set_speculation": (i32, [vp, i32, i32, i32]),
         "dots_set_speculation_rows": (i32, [vp, i32]),
+        "dots_set_speculation_guided": (i32, [vp, i32]),
+        "dots_op_spec_guide_masks": (i32, [vp, i32, i32, P(i32), P(i32), P(i32), P(i32), P(i32), P(C.c_uint32)]),
         "dots_set_row_drafts": (i32, [vp, i32, P(i32), i32]),
         "dots_spec_stats": (i32, [vp, i32, P(i64), P(i64), P(i64)]),
         "dots_op_ngram_draft": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]),
@@ -425,6 +427,7 @@ EXPORTED_SYMBOLS = [
     "dots_op_select_tokens_guided", "dots_bench_select_tokens_guided",
     "dots_set_row_ngram", "dots_op_select_tokens_ngram", "dots_bench_select_tokens_ngram",
     "dots_set_speculation", "dots_set_speculation_rows", "dots_set_row_drafts", "dots_spec_stats", "dots_op_ngram_draft",
+    "dots_set_speculation_guided", "dots_op_spec_guide_masks",
     "dots_slots_fork",
     "dots_slots_beam", "dots_beam_info", "dots_beam_read",
     "dots_stop_create", "dots_stop_destroy", "dots_set_row_stop", "dots_row_stop_hit",
@@ -966,6 +969,38 @@ class Engine:
         flags = (SPEC_ROWS["sampled"] if sampled else 0) | (SPEC_ROWS["stop"] if stop else 0)
         self._ck(self.lib.dots_set_speculation_rows(self.h, flags), "dots_set_speculation_rows")
         self.spec_rows = flags
+
+    spec_guided = False                      # Engine.set_speculation_guided: off until switched on
+
+    def set_speculation_guided(self, on: bool = True):
+        """May a row that holds a guide verify drafts?  Off by default.  A guide's state depends on the committed tokens
+        only, so every draft row is selected under the state the sequential engine would hold there: the tokens are those of the
+        unspeculated engine.  A guided row with SamplingParams also needs set_speculation_rows(sampled=True), one with stop strings
+        stop=True.  Only while no slot is occupied; the setting survives set_speculation."""
+        self._ck(self.lib.dots_set_speculation_guided(self.h, 1 if on else 0), "dots_set_speculation_guided")
+        self.spec_guided = bool(on)
+
+    def spec_guide_masks_op(self, guides: Sequence[Optional[int]], states: Sequence[int], drafts: Sequence[Sequence[int]], n_live: Sequence[int], k: int):
+        """The state chain and the draft-row mask kernels alone (dots_op_spec_guide_masks) for `rows` slots: guide handle (None = an
+        unguided slot), state, at most k drafts and live draft rows per slot.  -> (states int32 [rows * (k + 1)], allowed bool
+        [rows * (k + 1)][V]), both indexed by step row r = j * rows + b; state -1 = dead, idle or unguided (its bits are all clear)."""
+        rows, k = len(guides), int(k)
+        if not (len(states) == len(drafts) == len(n_live) == rows):
+            raise ValueError("one guide handle (or None), state, draft list and live count per slot")
+        V = int(self.cfg.vocab_size)
+        words = 2 * ((V + 63) // 64)
+        gid = np.ascontiguousarray([-1 if g is None else int(g) for g in guides], dtype=np.int32)
+        st = np.ascontiguousarray([0 if g is None else int(s) for g, s in zip(guides, states)], dtype=np.int32)
+        dr = np.zeros((rows, k), np.int32)
+        for b, d in enumerate(drafts):
+            dr[b, :len(d)] = np.asarray(list(d), np.int32)
+        nl = np.ascontiguousarray(n_live, dtype=np.int32)
+        s_out = np.full((rows * (k + 1),), -2, np.int32)
+        m_out = np.zeros((rows * (k + 1), words), np.uint32)
+        self._ck(self.lib.dots_op_spec_guide_masks(self.h, rows, k, _i32p(gid), _i32p(st), _i32p(dr), _i32p(nl), _i32p(s_out),
+                                                   m_out.ctypes.data_as(C.POINTER(C.c_uint32))), "dots_op_spec_guide_masks")
+        bits = np.unpackbits(m_out.view(np.uint8), axis=1, bitorder="little")[:, :V].astype(bool)
+        return s_out, bits
 
     @property
     def usable_slots(self) -> int:

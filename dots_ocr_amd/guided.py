@@ -502,6 +502,19 @@ class Guide:
             s = int(self.table[s, b])
         return s
 
+    def draft_states(self, state: int, drafts: Sequence[int], tokens: "TokenBytes", eos_ids: Iterable[int] = ()) -> List[int]:
+        """The state each draft row of a speculating step is selected under (what spec_guide_chain_kernel computes): entry j
+        is `state` walked over the bytes of drafts[0 .. j], or -1 from the first draft on that the guide could not have committed at its
+        position: one without bytes, an EOS id (it finishes the row and is not walked) or one whose walk meets DEAD."""
+        eos = set(int(t) for t in eos_ids)
+        out, s = [], int(state)
+        for t in drafts:
+            data = tokens.token(int(t)) if s >= 0 else b""
+            s = -1 if s < 0 or not data or int(t) in eos else self.walk(s, data)
+            s = -1 if s == DEAD else s
+            out.append(s)
+        return out
+
     def matches(self, data: bytes) -> bool:
         s = self.walk(self.start, data)
         return s != DEAD and bool(self.accepting[s])

@@ -35,7 +35,7 @@ class DotsOCRParser:
                  max_pixels=None, use_hf=False, model_path="./weights/DotsOCR", model=None, processor=None,
                  hf_max_new_tokens=24000, guided=False, no_repeat_ngram_size=None, no_repeat_ngram_window=None,
                  no_repeat_ngram_whitelist=None, speculative_ngram=None, prompt_lookup_min=2, prompt_lookup_max=4, stop=None,
-                 speculative_rows=None, num_beams=None, length_penalty=1.0):
+                 speculative_rows=None, num_beams=None, length_penalty=1.0, speculative_guided=False):
         self.dpi = dpi
         # beam search, opt-in: every page is decoded by a group of num_beams beams and its best hypothesis returned (the
         # server request carries use_beam_search with temperature 0, the in-process model generates with num_beams).  It combines with
@@ -60,6 +60,11 @@ class DotsOCRParser:
         if spec_rows_flags(speculative_rows) and not self.speculative_ngram:
             raise ValueError("speculative_rows needs speculative_ngram")
         self.speculative_rows = speculative_rows
+        # may guided sequences verify drafts (generate(speculative_guided=), Engine.set_speculation_guided).  A server decides by its own
+        # --speculative-guided flag.
+        if speculative_guided and not self.speculative_ngram:
+            raise ValueError("speculative_guided needs speculative_ngram")
+        self.speculative_guided = bool(speculative_guided)
         # no-repeat n-gram blocking, opt-in: the server request carries the three fields, the in-process model generates
         # with them.  With the default None the request and the call are exactly what they were.
         self.no_repeat_ngram_size = no_repeat_ngram_size
@@ -122,6 +127,8 @@ class DotsOCRParser:
             kw.update(speculative_ngram=self.speculative_ngram, prompt_lookup_min=self.prompt_lookup_min, prompt_lookup_max=self.prompt_lookup_max)
             if self.speculative_rows is not None:
                 kw["speculative_rows"] = self.speculative_rows
+            if self.speculative_guided:
+                kw["speculative_guided"] = True
         if self._guided_layout(prompts):
             from .guided import layout_schema
             if getattr(self.model.engine, "token_bytes", None) is None:

@@ -347,8 +347,16 @@ int dots_row_stop_hit(DotsEngine* e, int row, int32_t* out);
  * row's draft row j is selected by the row's own sampler with the counter of the output index it stands for (tokens generated + j), over
  * integer sums that do not depend on the order of the atomics: it is the token the unspeculated engine draws there, so the row's tokens
  * are EXACTLY those of the unspeculated engine for the same seed.  The accept walk advances the stop automaton through the commit a
- * sequential step uses: the row finishes at the same token, with the same hit record.  Rows with penalties, logit rules, a guide, an
- * n-gram rule or logprobs, and every row under an engine-wide temperature, never speculate.
+ * sequential step uses: the row finishes at the same token, with the same hit record.
+ *
+ * dots_set_speculation_guided lets a row that holds a guide speculate too.  A guide's state depends on the committed tokens only, so the
+ * state draft row j must be selected under — the slot's state walked over the bytes of drafts 1 .. j — is known at the head of the step:
+ * the row's allowed bits, its arg max (or, for a sampled row under DOTS_SPEC_ROWS_SAMPLED, its draw) under the guide and the accept walk's
+ * commits are those of the sequential step, so the tokens are again EXACTLY those of the unspeculated engine.  A draft the guide could not
+ * have committed at its position (no bytes, an EOS id, a byte without a transition) verifies nothing from there on.  A row speculates iff
+ * every feature it carries is let through: a guided row with DotsSamplingParams also needs DOTS_SPEC_ROWS_SAMPLED, one with stop strings
+ * DOTS_SPEC_ROWS_STOP.  Rows with penalties, logit rules, an n-gram rule or logprobs, and every row under an engine-wide temperature,
+ * never speculate.
  *
  * The built-in drafter looks the row's last tokens up in the row's OWN output (the prompt is not searched: image pads and a short
  * instruction).  With out[0 .. L) the tokens generated so far, for n from max_n down to min_n with n + 1 <= L: key = out[L - n .. L);
@@ -363,6 +371,10 @@ int dots_row_stop_hit(DotsEngine* e, int row, int32_t* out);
  * dots_set_speculation_rows  flags: DOTS_SPEC_ROWS_SAMPLED | DOTS_SPEC_ROWS_STOP; 0 (the default) = plain greedy rows only, and a step
  *                       launches exactly what it launched before.  The setting survives dots_set_speculation calls.  Allowed only while
  *                       no slot is occupied (DOTS_E_STATE); unknown bits: DOTS_E_INVALID.
+ * dots_set_speculation_guided  on != 0: rows that hold a guide may verify drafts; 0 (the default): they never do, and a step launches
+ *                       exactly what it launched before.  A call of its own, not a bit of dots_set_speculation_rows.  The setting
+ *                       survives dots_set_speculation calls.  Allowed only while no slot is occupied (DOTS_E_STATE); a change drops the
+ *                       captured steps.  The first call that switches it on allocates one int32 per step row.
  * dots_set_row_drafts   the n <= k drafts slot `row` verifies in its NEXT step, replacing what the drafter left (stream ordered; they are
  *                       spent by that step).  DOTS_E_INVALID: n > k or an id outside [0, vocab); DOTS_E_STATE: the slot is not occupied.
  *                       A row that does not speculate ignores them.
@@ -373,6 +385,7 @@ int dots_row_stop_hit(DotsEngine* e, int row, int32_t* out);
 #define DOTS_SPEC_ROWS_STOP 2
 int dots_set_speculation(DotsEngine* e, int k, int min_n, int max_n);
 int dots_set_speculation_rows(DotsEngine* e, int flags);
+int dots_set_speculation_guided(DotsEngine* e, int on);
 int dots_set_row_drafts(DotsEngine* e, int row, const int32_t* ids_host, int n);
 int dots_spec_stats(DotsEngine* e, int row, int64_t* steps, int64_t* drafted, int64_t* accepted);
 
@@ -635,6 +648,13 @@ int dots_bench_select_tokens_ngram(DotsEngine* e, const float* logits_dev, int B
                                    const int32_t* n_prompt_dev, int iters, float* ms_out);
 /* The drafter alone on caller-supplied histories: hist int32 [B][hist_stride] holds row b's generated tokens hist[b][0 .. hist_lens[b]);
  * writes drafts int32 [B][k] and n_drafts int32 [B] by the rule above (every row drafts: no finished / selection state is read). */
+/* The draft-row states and allowed bits of guided slots alone (launch_spec_guide_chain + launch_guide_mask_drafts), at the
+ * engine's vocabulary, token bytes and EOS ids: slot b < rows holds guide guide_ids_host[b] (-1: none) at states_host[b], drafts
+ * drafts_host[b][0 .. k) and n_live_host[b] live draft rows.  states_out_host int32 [rows * (k + 1)] and mask_out_host uint32
+ * [rows * (k + 1)][2 * ceil(vocab / 64)], both indexed by step row r = j * rows + b: the state draft row (b, j) is selected under (-1: dead,
+ * idle or unguided; every entry r < rows is -1) and its allowed bits (all clear where the state is -1). */
+int dots_op_spec_guide_masks(DotsEngine* e, int rows, int k, const int32_t* guide_ids_host, const int32_t* states_host, const int32_t* drafts_host,
+                             const int32_t* n_live_host, int32_t* states_out_host, uint32_t* mask_out_host);
 int dots_op_ngram_draft(DotsEngine* e, const int32_t* hist_dev, const int32_t* hist_lens_dev, int hist_stride, int B, int k, int min_n, int max_n,
                         int32_t* drafts_dev, int32_t* n_drafts_dev);
 /* The log-probability stage over caller logits: logits_dev fp32 [B, ld] (V <= ld), top_n_host [B] (-1 = row skipped, 0..20),

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """What a speculating decode step costs and what it has to accept to pay (profiles/spec_ngram.txt).
 
-    python tools/spec_bench.py [--slots 1 8] [--k 0 1 3 7] [--steps 64] [--repeats 3] [--prompt 512] [--sampled]
+    python tools/spec_bench.py [--slots 1 8] [--k 0 1 3 7] [--steps 64] [--repeats 3] [--prompt 512] [--sampled | --guided]
 
 Full-size language model with seeded random weights (the vision tower, which no text-only prompt touches, is cut to one block so that the
 weights are made quickly), one engine of 64 rows.  Per slot count: the reference tokens come from an unspeculated run; then for every
@@ -24,6 +24,12 @@ plain greedy rows, with SamplingParams(temperature=0.1, seed=...) rows (a draft 
 with temperature=0.8, top_k=20, top_p=0.9 rows (four reads: partials, histogram, gather, draw).  The difference between a sampled
 leg and the greedy leg at the same slots, k and acceptance is the cost of the two draft-row launches (spec_thresh_kernel,
 spec_draw_kernel); the k = 0 step of a sampled leg pays the per-row selection stage instead of the arg max, as it does without speculation.
+
+--guided (profiles/spec_guided.txt) gives every row the layout guide (guided.layout_schema) over a synthetic byte table of the full
+vocabulary and runs the legs twice on one build: guided_off (Engine.set_speculation_guided(False): the guided rows verify nothing, their
+draft rows idle) and guided_on.  A wrong draft is then a token the guide ALLOWS at its position where one exists (another single byte
+with a transition), so that at acceptance 0 the draft rows are alive and pay the chain, the mask and the shaped arg max; `alive` is the
+share of planted drafts the guide could have committed.  break_even of a guided_on row = its cost / the k = 0 cost of guided_off - 1.
 
 One JSON line per measurement on stdout, then a table.
 """
@@ -48,6 +54,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--prompt", type=int, default=512)
     ap.add_argument("--sampled", action="store_true", help="also run sampled speculating rows (2-read and 4-read parameter sets) beside the greedy leg")
+    ap.add_argument("--guided", action="store_true", help="every row holds the layout guide: the legs with Engine.set_speculation_guided off and on")
     ap.add_argument("--tiny", action="store_true", help="the small-dims model instead of the full-size one (a plumbing check, not a measurement)")
     a = ap.parse_args()
     from dots_ocr_amd.config import DotsConfig
@@ -68,6 +75,43 @@ def main():
     prompts = [rng.integers(0, cfg.vocab_size - 4096, a.prompt).astype(np.int32) for _ in range(max(a.slots))]
     results = {}
     legs = [("greedy", None)]
+    guide = tb = handle = None
+    if a.guided:
+        if a.sampled:
+            raise SystemExit("--guided and --sampled are separate measurements")
+        from dots_ocr_amd import guided as G
+        pieces = [b'{"', b'"bbox"', b'": ', b'"category"', b'"text"', b"Text", b"Title", b"Table", b", ", b"], ", b'"}', b"12", b"345", b"ab", b"the ", b"\n"]
+        g2 = np.random.default_rng(1)
+        toks = [bytes([i]) for i in range(256)]
+        toks += [b"".join(pieces[int(j)] for j in g2.integers(0, len(pieces), int(g2.integers(1, 4)))) for _ in range(256, cfg.vocab_size - 4096)]
+        tb = G.TokenBytes(toks + [b""] * (cfg.vocab_size - len(toks)))          # the top 4096 ids: specials without bytes
+        guide = G.compile_json_schema(G.layout_schema())
+        eng.set_token_bytes(tb)
+        handle = eng.create_guide(guide)
+        legs = [("guided_off", None), ("guided_on", None)]
+    alive = [0, 0]                                                   # planted drafts the guide could have committed / all planted (--guided)
+
+    def guided_drafts(Tb, pos, k, true_drafts):
+        """k drafts at output index pos of a guided row: the true ones, then single bytes the guide allows there (alive but wrong).
+        -> (drafts, how many of them the step accepts: the leading true ones the guide could commit)"""
+        d = [int(t) for t in Tb[pos:pos + k]]
+        state = guide.start
+        for t in Tb[:pos]:                                           # as the commit advances it: a token the guide did not allow moves nothing
+            nxt = guide.walk(state, tb.token(int(t))) if tb.token(int(t)) else G.DEAD
+            state = state if nxt == G.DEAD else nxt
+        acc = 0
+        for j in range(min(true_drafts, len(d))):
+            state = guide.walk(state, tb.token(d[j])) if state != G.DEAD and tb.token(d[j]) else G.DEAD
+            acc += state != G.DEAD and acc == j
+        alive[0] += acc - min(true_drafts, len(d))                   # true drafts behind a dead one (the all -inf fallback) are dead too
+        for j in range(true_drafts, len(d)):
+            ok = [c for c in range(256) if state != G.DEAD and guide.table[state, c] != G.DEAD and c != d[j]]
+            d[j] = ok[0] if ok else (d[j] + 1) % 256
+            state = guide.walk(state, bytes([d[j]])) if ok else G.DEAD
+            alive[0] += bool(ok)
+        alive[0] += min(true_drafts, len(d))
+        alive[1] += len(d)
+        return d, acc
     if a.sampled:
         legs += [("T0.1", dict(temperature=0.1)), ("T0.8_k20_p0.9", dict(temperature=0.8, top_k=20, top_p=0.9))]
     for leg, params in legs:
@@ -81,12 +125,17 @@ def main():
               if params is not None:
                   for b in slots:
                       eng.set_row_sampling(b, SamplingParams(seed=1000 + b, **params))
+              if a.guided:
+                  for b in slots:
+                      eng.set_row_guide(b, handle)
 
           def run(k, true_drafts, T=None):
               """`steps` steps with k drafts per slot of which the first true_drafts are right: (seconds, tokens committed, token lists)"""
               eng.slots_reset()
               eng.set_speculation(k, 2, 0)
               eng.set_speculation_rows(sampled=a.sampled)
+              if a.guided:
+                  eng.set_speculation_guided(leg == "guided_on")
               set_rows()
               eng.slots_prefill(slots, np.concatenate(prompts[:S]), [a.prompt] * S, [n_tok] * S)
               eng.slots_decode(1)                                       # the captured step exists before the clock starts
@@ -94,14 +143,26 @@ def main():
               _, lens = eng.slots_poll()
               start = [int(lens[b]) for b in slots]
               pos = list(start)
+              gain = [[1 + (min(true_drafts, k) if k else 0)] * S for _ in range(a.steps)]      # tokens a step commits per slot
+              plan = None
+              if a.guided and k:                                         # the automaton walks stay outside the clock
+                  plan, at = [], list(start)
+                  for i in range(a.steps):
+                      made = [guided_drafts(T[b], at[b], k, true_drafts) for b in slots]
+                      plan.append([m[0] for m in made])
+                      gain[i] = [1 + (m[1] if leg == "guided_on" else 0) for m in made]      # guided_off rows verify nothing
+                      at = [at[b] + gain[i][b] for b in slots]
               t0 = time.perf_counter()
-              for _ in range(a.steps):
+              for i in range(a.steps):
                   for b in slots:
                       if k:
-                          d = [int(t) for t in T[b][pos[b]:pos[b] + k]]
-                          d = d[:true_drafts] + [(t + 1) % (cfg.vocab_size - 4096) for t in d[true_drafts:]]
+                          if plan is not None:
+                              d = plan[i][b]
+                          else:
+                              d = [int(t) for t in T[b][pos[b]:pos[b] + k]]
+                              d = d[:true_drafts] + [(t + 1) % (cfg.vocab_size - 4096) for t in d[true_drafts:]]
                           eng.set_row_drafts(b, d)
-                      pos[b] += 1 + (min(true_drafts, k) if k else 0)
+                      pos[b] += gain[i][b]
                   eng.slots_decode(1)
               eng.synchronize()
               dt = time.perf_counter() - t0
@@ -131,15 +192,19 @@ def main():
               for name, true_drafts in levels:
                   runs = [run(k, true_drafts, T) for _ in range(a.repeats)]
                   dt = statistics.median(r[0] for r in runs)
+                  share = round(alive[0] / alive[1], 3) if alive[1] else None
+                  alive[0] = alive[1] = 0
                   rec = {"leg": leg, "slots": S, "k": k, "rows": S * (k + 1), "acceptance": name, "steps": a.steps, "ms_per_step": round(dt / a.steps * 1e3, 4),
                          "ms_per_step_min_max": [round(min(r[0] for r in runs) / a.steps * 1e3, 4), round(max(r[0] for r in runs) / a.steps * 1e3, 4)],
                          "tokens_per_step": round(runs[0][1] / a.steps / S, 3), "tokens_per_s": round(runs[0][1] / dt, 1)}
+                  if a.guided:
+                      rec["alive"] = share
                   results[(leg, S, k, name)] = rec
                   print(json.dumps(rec), flush=True)
     print()
     print(f"{'leg':>14} {'slots':>5} {'k':>2} {'rows':>4} {'accept':>6} {'ms/step':>9} {'tok/step/slot':>13} {'tokens/s':>10} {'break-even accepted/step':>25}")
     for (leg, S, k, name), r in results.items():
-        base = results.get((leg, S, 0, "-"))
+        base = results.get(("guided_off" if a.guided else leg, S, 0, "-"))
         be = ""
         if k and name == "0" and base:
             be = f"{r['ms_per_step'] / base['ms_per_step'] - 1:.3f}"
