@@ -317,7 +317,7 @@ int dots_slots_beam(DotsEngine* e, int src_slot, const int32_t* dst_slots, int n
     if (src_slot < 0 || src_slot >= mb) return e->fail(DOTS_E_INVALID, "source slot %d out of range [0, %d)", src_slot, mb);
     if (e->spec_k) return e->fail(DOTS_E_STATE, "beam search cannot run while the engine speculates (dots_set_speculation)");
     const auto fresh = std::find(e->fresh_slots.begin(), e->fresh_slots.end(), src_slot);
-    if (!e->slot_mode || !e->slot_active[src_slot] || fresh == e->fresh_slots.end())
+    if (!e->slot_mode || !e->slot_active[src_slot] || fresh == e->fresh_slots.end() || slot_parked(e, src_slot))
         return e->fail(DOTS_E_STATE, "slot %d cannot start a beam group: only a sequence of the most recent dots_slots_prefill, before any decode step", src_slot);
     if (V > LP_MAX_V) return e->fail(DOTS_E_INVALID, "beam search supports vocabularies up to %d", LP_MAX_V);
     if ((size_t)e->max_pages * DOTS_MAX_BEAMS * 4 > 48 * 1024) return e->fail(DOTS_E_INVALID, "beam search supports max_seq_len up to %d", 48 * 1024 / (DOTS_MAX_BEAMS * 4) * 64);

@@ -251,6 +251,25 @@ struct DotsEngine {
     int slot_done[DOTS_MAX_BATCH] = {0};   // seen finished at the last poll: grows no more
     int32_t *d_sel = nullptr, *d_sel_new = nullptr, *d_max_len = nullptr, *p_dst = nullptr;
     const int32_t* sel_now = nullptr;      // selection mask of the next select_tokens() call
+    // ---- suspended sequences (dots_slot_suspend).  swap_host: pinned host memory of swap_total host pages, one host page =
+    // one 64-token page of EVERY layer ([layer][page bytes], the staging layout of kv_swap.hip); swap_used[h] != 0: host page h is taken.
+    // swap_stage / swap_list: the device staging buffer of KV_SWAP_CHUNK_PAGES host pages and the page list the kernels read, allocated by
+    // the first suspend.  parked[slot]: the record of a suspended slot — per logical page of the row where its content is, and the
+    // three device scalars of the row that an idle row loses
+    uint8_t* swap_host = nullptr;
+    int swap_total = 0, swap_free = 0, n_parked = 0;
+    std::vector<uint8_t> swap_used;
+    uint8_t* swap_stage = nullptr;
+    int32_t* swap_list = nullptr;
+    std::vector<int32_t> swap_list_host;
+    struct Parked {
+        bool on = false;
+        // >= 0: a resident page the row still holds with others (page_refs > 1 at suspend); <= -2: host page -(v + 2); -1: a page without
+        // content (taken ahead of the context), replaced by a fresh one at resume
+        std::vector<int32_t> pages;
+        int32_t cur_token = 0, ctx = 0, finished = 0;
+    };
+    Parked parked[DOTS_MAX_BATCH];
     // captured decode steps, keyed by everything the capture bakes in: rows, KV splits, static batch (out_cap = row stride of
     // the output buffer) or slot mode (out_cap = 0), number of EOS ids, whether any row carries its own parameters (rowp: the per-row
     // selection stage), whether any row returns logprobs (lp), whether any row carries logit rules (rules: the stage then gets their
@@ -381,6 +400,9 @@ int splits_for_ctx(int max_ctx);
 int step_graph(DotsEngine* e, int rows, int n_splits, int out_cap, hipGraphExec_t* exec, int part = 0);
 // slots.hip
 int grow_pages(DotsEngine* e, int slot, int tokens, bool* changed);
+// a suspended slot: occupied, its KV parked in host memory (dots_slot_suspend)
+inline bool slot_parked(const DotsEngine* e, int slot) { return slot >= 0 && slot < DOTS_MAX_BATCH && e->parked[slot].on; }
+void swap_free_host(DotsEngine* e);
 // beam.hip: beam groups
 int beam_step(DotsEngine* e, int rows);
 int beam_before_decode(DotsEngine* e, int n_steps);

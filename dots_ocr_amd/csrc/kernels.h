@@ -70,6 +70,15 @@ hipError_t launch_kv_to_pages(hipStream_t s, const bf16_t* k, const bf16_t* qkv,
 // the caller guarantees that every index names a page of the pool and that no destination is the source
 hipError_t launch_kv_fork_pages(hipStream_t s, void* pool, size_t layer_bytes, size_t page_bytes, int layers, int src_page, const int32_t* dst_pages,
                                 int n);
+// ---- kv_swap.hip: the page moves of dots_slot_suspend / dots_slot_resume.  The n <= KV_SWAP_CHUNK_PAGES pages pages[0 .. n)
+// (device array) of every one of `layers` layers are packed into / unpacked from the device staging buffer `stage`, laid out
+// [page j][layer][page_bytes].  Pages are copied whole, as in kv_fork.hip; the caller guarantees that every index names a page of the pool
+// and that `stage` holds n x layers x page_bytes bytes
+constexpr int KV_SWAP_CHUNK_PAGES = 32;
+hipError_t launch_kv_gather_pages(hipStream_t s, const void* pool, size_t layer_bytes, size_t page_bytes, int layers, void* stage, const int32_t* pages,
+                                  int n);
+hipError_t launch_kv_scatter_pages(hipStream_t s, void* pool, size_t layer_bytes, size_t page_bytes, int layers, const void* stage, const int32_t* pages,
+                                   int n);
 // ---- decode_fused.hip: dense layers of the decode step with in-workgroup split-K and fused prologues/epilogues.
 // Activations between them travel as X images [K/8][XR][8], XR = 8 (B <= 8) or 16 (decode_layout.h).
 hipError_t launch_dec_embed(hipStream_t s, const int32_t* tokens, const bf16_t* embed, bf16_t* h, int B, int dim);

@@ -8,8 +8,26 @@ hipError_t upload_table_row(DotsEngine* e, int slot) {
     return hipMemcpyAsync(e->block_table + (size_t)slot * e->max_pages, e->hp_table.data() + (size_t)slot * e->max_pages, (size_t)e->max_pages * 4,
                           hipMemcpyHostToDevice, e->stream);
 }
-// the slot lets go of every page its row names; a page goes back to the free list when its last holder lets go (dots_slots_fork shares pages)
+// the host pages of a suspended slot go back to the host space, and the slot is suspended no more (its resident pages: release_pages)
+static void drop_parked(DotsEngine* e, int slot) {
+    DotsEngine::Parked& pk = e->parked[slot];
+    if (!pk.on) return;
+    for (int32_t v : pk.pages)
+        if (v <= -2) { e->swap_used[-(v + 2)] = 0; e->swap_free += 1; }
+    pk.pages.clear();
+    pk.on = false;
+    e->n_parked -= 1;
+}
+void swap_free_host(DotsEngine* e) {
+    if (e->swap_host) hipHostFree(e->swap_host);
+    e->swap_host = nullptr;
+    e->swap_total = e->swap_free = 0;
+    e->swap_used.clear();
+}
+// the slot lets go of every page its row names; a page goes back to the free list when its last holder lets go (dots_slots_fork shares pages).
+// Of a suspended slot these are the pages that stayed resident, and its host pages go back too
 void release_pages(DotsEngine* e, int slot) {
+    if (slot < DOTS_MAX_BATCH) drop_parked(e, slot);
     auto& mine = e->slot_pages[slot];
     for (auto it = mine.rbegin(); it != mine.rend(); ++it)
         if (--e->page_refs[*it] == 0) e->free_pages.push_back(*it);
@@ -43,6 +61,19 @@ int grow_pages(DotsEngine* e, int slot, int tokens, bool* changed) {
         *changed = true;
     }
     return (int)mine.size() * 64;
+}
+
+// ---- the paging arithmetic of a decode chunk, shared by dots_slots_decode and dots_slots_pages_short.  n counts positions: n_steps x
+// (spec_k + 1).  A step at context c writes KV position c and brings the sequence to c + 2 tokens, so n more steps need positions
+// [0, ctx + n), and a sequence limited to slot_limit tokens never writes beyond position slot_limit - 2.
+// does the chunk give this slot pages: a running sequence that is neither a beam-group row (fully reserved at creation, and the device owns
+// its table row: DESIGN §6.9) nor suspended
+static bool slot_grows(const DotsEngine* e, int b) { return e->slot_active[b] && !e->slot_done[b] && !e->beam_of[b] && !e->parked[b].on; }
+static int chunk_want(const DotsEngine* e, int b, int n) { return std::min(e->slot_ctx_ub[b] + n, e->slot_limit[b] - 1); }
+// pages the slot lacks for chunk_want positions (what grow_pages would take)
+static int chunk_pages_lacking(const DotsEngine* e, int b, int n) {
+    const int need = std::min((chunk_want(e, b, n) + 63) / 64, e->max_pages);
+    return std::max(0, need - (int)e->slot_pages[b].size());
 }
 
 // tokens a slot sequence reserves at admission: its prompt plus the first page-worth of generated tokens (the rest on demand)
@@ -84,7 +115,7 @@ int dots_slots_fork(DotsEngine* e, int src_slot, const int32_t* dst_slots, int n
     const int mb = c.max_batch, V = c.vocab_size;
     if (src_slot < 0 || src_slot >= mb) return e->fail(DOTS_E_INVALID, "source slot %d out of range [0, %d)", src_slot, mb);
     const auto fresh = std::find(e->fresh_slots.begin(), e->fresh_slots.end(), src_slot);
-    if (!e->slot_mode || !e->slot_active[src_slot] || fresh == e->fresh_slots.end())
+    if (!e->slot_mode || !e->slot_active[src_slot] || fresh == e->fresh_slots.end() || slot_parked(e, src_slot))
         return e->fail(DOTS_E_STATE, "slot %d cannot be forked: only a sequence of the most recent dots_slots_prefill, before any decode step", src_slot);
     const int usable = e->spec_k ? mb / (e->spec_k + 1) : mb;
     for (int i = 0; i < n; ++i) {
@@ -245,7 +276,8 @@ int dots_slots_decode(DotsEngine* e, int n_steps) {
     e->fresh_slots.clear();                                 // the step overwrites the logits a fork selects from (dots_slots_fork)
     if (e->sel_dirty) {
         int32_t sel[DOTS_MAX_BATCH];
-        for (int b = 0; b < DOTS_MAX_BATCH; ++b) sel[b] = e->slot_active[b] && !e->beam_of[b];      // a group's rows are selected by its own kernels
+        // a group's rows are selected by its own kernels; a suspended row commits nothing
+        for (int b = 0; b < DOTS_MAX_BATCH; ++b) sel[b] = e->slot_active[b] && !e->beam_of[b] && !e->parked[b].on;
         CK(hipMemcpyAsync(e->d_sel, sel, DOTS_MAX_BATCH * 4, hipMemcpyHostToDevice, s));
         e->sel_dirty = false;
     }
@@ -256,11 +288,8 @@ int dots_slots_decode(DotsEngine* e, int n_steps) {
     // context count n_steps x (k + 1) (dots_slots_poll brings the bound back to the row's true context)
     n_steps *= e->spec_k + 1;
     for (int b = 0; b < rows; ++b) {
-        if (!e->slot_active[b] || e->slot_done[b]) continue;
-        if (e->beam_of[b]) continue;                        // fully reserved at creation, and the device owns its table row
-        // A step at context c writes KV position c and brings the sequence to c + 2 tokens, so n_steps more steps need positions
-        // [0, ctx + n_steps), and a sequence limited to slot_limit tokens never writes beyond position slot_limit - 2.
-        int want = std::min(e->slot_ctx_ub[b] + n_steps, e->slot_limit[b] - 1);
+        if (!slot_grows(e, b)) continue;
+        int want = chunk_want(e, b, n_steps);
         bool changed = false;
         const int have = grow_pages(e, b, want, &changed);
         if (changed) CK(upload_table_row(e, b));
@@ -270,7 +299,7 @@ int dots_slots_decode(DotsEngine* e, int n_steps) {
             CK(hipMemcpyAsync(&ctx, e->ctx_len + b, 4, hipMemcpyDeviceToHost, s));
             CK(hipStreamSynchronize(s));
             e->slot_ctx_ub[b] = std::min(e->slot_ctx_ub[b], (int)ctx);
-            want = std::min(e->slot_ctx_ub[b] + n_steps, e->slot_limit[b] - 1);
+            want = chunk_want(e, b, n_steps);
         }
         if (have < want) {
             // Positions [0, have) exist: the last step the row may take is the one at context have - 1, which leaves it with have + 1
@@ -285,7 +314,7 @@ int dots_slots_decode(DotsEngine* e, int n_steps) {
             CK(hipStreamSynchronize(s));                                     // `cap` is a stack variable
             e->kv_capped += 1;
         }
-        e->slot_ctx_ub[b] = std::min(e->slot_ctx_ub[b] + n_steps, e->slot_limit[b] - 1);
+        e->slot_ctx_ub[b] = chunk_want(e, b, n_steps);
     }
     n_steps /= e->spec_k + 1;
     const int n_splits = splits_for_ctx(e->cfg.max_seq_len);
@@ -322,6 +351,7 @@ int dots_slots_poll(DotsEngine* e, int32_t* finished, int32_t* out_lens) {
     CK(hipStreamSynchronize(e->stream));
     for (int b = 0; b < mb; ++b) {
         if (!e->slot_mode || !e->slot_active[b]) { finished[b] = -1; out_lens[b] = 0; }      // -1: free slot
+        else if (e->parked[b].on) finished[b] = 2;                                           // suspended: out_lens as they stood at suspend
         else {
             if (finished[b]) e->slot_done[b] = 1;                                            // takes no more pages
             // every issued step has run: the context is prompt + generated - 1 exactly.  A speculating step advances a row by 1 .. k + 1
@@ -363,6 +393,174 @@ int dots_slot_release(DotsEngine* e, int slot) {
     return DOTS_OK;
 }
 
+// ---------------------------------------------------------------------------------- suspend / resume
+static size_t kv_page_bytes(const DotsEngine* e) { return (size_t)e->cfg.num_kv_heads * 2 * 8192 * (e->kv8 ? 1 : 2); }      // one page of one layer
+static size_t swap_unit_bytes(const DotsEngine* e) { return kv_page_bytes(e) * e->cfg.num_layers; }                          // one host page
+
+// Moves n pages between the pool and the host space in chunks of KV_SWAP_CHUNK_PAGES through the staging buffer, in order on the engine's
+// stream: pool page pool_pages[i] <-> host page host_pages[i] (ascending, so a chunk is usually ONE copy: one hipMemcpyAsync per run of
+// consecutive host pages).  to_host: gather + copy out, else copy in + scatter.  The caller synchronises.
+static int swap_move(DotsEngine* e, bool to_host, const std::vector<int32_t>& pool_pages, const std::vector<int32_t>& host_pages) {
+    const int n = (int)pool_pages.size();
+    if (!n) return DOTS_OK;
+    hipStream_t s = e->stream;
+    const size_t unit = swap_unit_bytes(e), page_bytes = kv_page_bytes(e);
+    if (!e->swap_list) CK(e->alloc(&e->swap_list, (size_t)e->max_pages));
+    if (!e->swap_stage) CK(e->alloc(&e->swap_stage, (size_t)KV_SWAP_CHUNK_PAGES * unit));
+    e->swap_list_host = pool_pages;                          // outlives the asynchronous upload
+    CK(hipMemcpyAsync(e->swap_list, e->swap_list_host.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+    for (int c0 = 0; c0 < n; c0 += KV_SWAP_CHUNK_PAGES) {
+        const int cn = std::min(KV_SWAP_CHUNK_PAGES, n - c0);
+        if (to_host) CK(launch_kv_gather_pages(s, e->pool, e->pool_layer_elems * 2, page_bytes, e->cfg.num_layers, e->swap_stage, e->swap_list + c0, cn));
+        for (int i = 0; i < cn;) {
+            int run = 1;
+            while (i + run < cn && host_pages[c0 + i + run] == host_pages[c0 + i] + run) ++run;
+            uint8_t *host = e->swap_host + (size_t)host_pages[c0 + i] * unit, *dev = e->swap_stage + (size_t)i * unit;
+            if (to_host) CK(hipMemcpyAsync(host, dev, (size_t)run * unit, hipMemcpyDeviceToHost, s));
+            else CK(hipMemcpyAsync(dev, host, (size_t)run * unit, hipMemcpyHostToDevice, s));
+            i += run;
+        }
+        if (!to_host) CK(launch_kv_scatter_pages(s, e->pool, e->pool_layer_elems * 2, page_bytes, e->cfg.num_layers, e->swap_stage, e->swap_list + c0, cn));
+    }
+    return DOTS_OK;
+}
+
+int dots_kv_swap_reserve(DotsEngine* e, int pages) {
+    if (!e) return DOTS_E_INVALID;
+    if (pages < 0) return e->fail(DOTS_E_INVALID, "dots_kv_swap_reserve: pages must be >= 0, got %d", pages);
+    if (e->n_parked) return e->fail(DOTS_E_STATE, "the host space cannot change while %d slot(s) are suspended", e->n_parked);
+    if (pages == e->swap_total) return DOTS_OK;
+    CK(hipSetDevice(e->device));
+    CK(hipStreamSynchronize(e->stream));
+    swap_free_host(e);
+    if (pages) {
+        void* p = nullptr;
+        CK(hipHostMalloc(&p, (size_t)pages * swap_unit_bytes(e), hipHostMallocDefault));
+        e->swap_host = static_cast<uint8_t*>(p);
+        e->swap_total = e->swap_free = pages;
+        e->swap_used.assign(pages, 0);
+    }
+    return DOTS_OK;
+}
+
+int dots_kv_swap_info(DotsEngine* e, int32_t* total_pages, int32_t* free_pages) {
+    if (!e || !total_pages || !free_pages) return DOTS_E_INVALID;
+    *total_pages = e->swap_total;
+    *free_pages = e->swap_free;
+    return DOTS_OK;
+}
+
+int dots_slot_suspend(DotsEngine* e, int slot) {
+    if (!e) return DOTS_E_INVALID;
+    if (!e->slot_mode || slot < 0 || slot >= e->cfg.max_batch || !e->slot_active[slot]) return e->fail(DOTS_E_STATE, "slot %d is not occupied", slot);
+    if (e->parked[slot].on) return e->fail(DOTS_E_STATE, "slot %d is already suspended", slot);
+    if (e->beam_of[slot]) return e->fail(DOTS_E_STATE, "slot %d is a row of a beam group: a group cannot be suspended", slot);
+    if (e->spec_k) return e->fail(DOTS_E_STATE, "a slot cannot be suspended while the engine speculates (dots_set_speculation)");
+    CK(hipSetDevice(e->device));
+    hipStream_t s = e->stream;
+    // the row's scalars: an idle row sits at context 0, and whatever refills the batch meanwhile must find nothing of this row in them
+    int32_t sc[3] = {0, 0, 0};
+    CK(hipMemcpyAsync(&sc[0], e->cur_tokens + slot, 4, hipMemcpyDeviceToHost, s));
+    CK(hipMemcpyAsync(&sc[1], e->ctx_len + slot, 4, hipMemcpyDeviceToHost, s));
+    CK(hipMemcpyAsync(&sc[2], e->finished + slot, 4, hipMemcpyDeviceToHost, s));
+    CK(hipStreamSynchronize(s));
+    if (sc[2]) return e->fail(DOTS_E_STATE, "slot %d has finished: read and release it", slot);
+    auto& mine = e->slot_pages[slot];
+    const int ctx = sc[1], n_data = (ctx + 63) / 64;         // positions [0, ctx) are written: the token at ctx is the next step's input
+    if (ctx < 1 || n_data > (int)mine.size()) return e->fail(DOTS_E_STATE, "slot %d: context %d is not covered by its %d pages", slot, ctx, (int)mine.size());
+    // ---- what goes where: a page with other holders stays (nobody writes it: DESIGN §6.7), a page of the row alone is copied out if it
+    // holds positions and simply returned if it was taken ahead of the context
+    std::vector<int32_t> where(mine.size()), src, dst;
+    for (int p = 0; p < (int)mine.size(); ++p) {
+        if (e->page_refs[mine[p]] > 1) where[p] = mine[p];
+        else if (p < n_data) { where[p] = -2; src.push_back(mine[p]); }
+        else where[p] = -1;
+    }
+    while (!where.empty() && where.back() == -1) where.pop_back();
+    if ((int)src.size() > e->swap_free)
+        return e->fail(DOTS_E_CAPACITY, "host space exhausted: slot %d needs %d host pages, %d of %d are free (dots_kv_swap_reserve)", slot, (int)src.size(),
+                       e->swap_free, e->swap_total);
+    for (int h = 0; h < e->swap_total && dst.size() < src.size(); ++h)
+        if (!e->swap_used[h]) dst.push_back(h);
+    RET(swap_move(e, true, src, dst));
+    CK(hipMemsetAsync(e->ctx_len + slot, 0, 4, s));          // idles like a released slot: one key of the scratch page
+    CK(hipStreamSynchronize(s));
+    // ---- the copies have landed: only now does anything change hands
+    for (int32_t h : dst) e->swap_used[h] = 1;
+    e->swap_free -= (int)dst.size();
+    {
+        size_t k = 0;
+        for (auto& w : where)
+            if (w == -2) w = -(dst[k++] + 2);
+    }
+    std::vector<int32_t> keep;
+    for (auto it = mine.rbegin(); it != mine.rend(); ++it)
+        if (e->page_refs[*it] == 1) { e->page_refs[*it] = 0; e->free_pages.push_back(*it); }
+    for (int32_t pg : mine)
+        if (e->page_refs[pg] > 1) keep.push_back(pg);
+    mine = keep;                                              // the pages dots_slot_release still has to let go of
+    std::fill(e->hp_table.begin() + (size_t)slot * e->max_pages, e->hp_table.begin() + (size_t)(slot + 1) * e->max_pages, e->n_pool_pages);
+    CK(upload_table_row(e, slot));
+    DotsEngine::Parked& pk = e->parked[slot];
+    pk.on = true;
+    pk.pages = where;
+    pk.cur_token = sc[0]; pk.ctx = ctx; pk.finished = sc[2];
+    e->n_parked += 1;
+    e->slot_ctx_ub[slot] = ctx;
+    e->sel_dirty = true;
+    return DOTS_OK;
+}
+
+int dots_slot_resume(DotsEngine* e, int slot) {
+    if (!e) return DOTS_E_INVALID;
+    if (!e->slot_mode || slot < 0 || slot >= e->cfg.max_batch || !e->slot_active[slot] || !e->parked[slot].on)
+        return e->fail(DOTS_E_STATE, "slot %d is not suspended", slot);
+    DotsEngine::Parked& pk = e->parked[slot];
+    int need = 0;
+    for (int32_t w : pk.pages) need += w < 0;
+    if (need > (int)e->free_pages.size() || (int)pk.pages.size() > e->max_pages)
+        return e->fail(DOTS_E_CAPACITY, "KV pool exhausted: slot %d needs %d pages of 64 tokens to resume, %d of %d are free", slot, need,
+                       (int)e->free_pages.size(), e->n_pool_pages);
+    CK(hipSetDevice(e->device));
+    hipStream_t s = e->stream;
+    // fresh pages in free-list order, taken off the list only once the copies have landed
+    std::vector<int32_t> row(pk.pages.size()), src, dst;
+    for (size_t p = 0, k = 0; p < pk.pages.size(); ++p) {
+        const int32_t w = pk.pages[p];
+        if (w >= 0) { row[p] = w; continue; }
+        row[p] = e->free_pages[e->free_pages.size() - 1 - k++];
+        if (w <= -2) { src.push_back(-(w + 2)); dst.push_back(row[p]); }
+    }
+    RET(swap_move(e, false, dst, src));
+    CK(hipMemcpyAsync(e->cur_tokens + slot, &pk.cur_token, 4, hipMemcpyHostToDevice, s));
+    CK(hipMemcpyAsync(e->ctx_len + slot, &pk.ctx, 4, hipMemcpyHostToDevice, s));
+    CK(hipMemcpyAsync(e->finished + slot, &pk.finished, 4, hipMemcpyHostToDevice, s));
+    for (size_t p = 0; p < row.size(); ++p) e->hp_table[(size_t)slot * e->max_pages + p] = row[p];
+    if (hipError_t r = upload_table_row(e, slot); r != hipSuccess || (r = hipStreamSynchronize(s)) != hipSuccess) {
+        std::fill(e->hp_table.begin() + (size_t)slot * e->max_pages, e->hp_table.begin() + (size_t)(slot + 1) * e->max_pages, e->n_pool_pages);
+        return e->fail(DOTS_E_HIP, "dots_slot_resume: %s", hipGetErrorString(r));
+    }
+    e->free_pages.resize(e->free_pages.size() - need);
+    for (size_t p = 0; p < row.size(); ++p)
+        if (pk.pages[p] < 0) e->page_refs[row[p]] = 1;
+    e->slot_pages[slot] = row;
+    drop_parked(e, slot);                                     // the host pages are free again
+    e->slot_ctx_ub[slot] = pk.ctx;
+    e->sel_dirty = true;
+    return DOTS_OK;
+}
+
+int dots_slots_pages_short(DotsEngine* e, int n_steps, int32_t* pages) {
+    if (!e || !pages) return e ? e->fail(DOTS_E_INVALID, "null argument") : DOTS_E_INVALID;
+    if (!e->slot_mode) return e->fail(DOTS_E_STATE, "no slot has been prefilled");
+    if (n_steps < 1) return e->fail(DOTS_E_INVALID, "n_steps must be >= 1");
+    int64_t lack = 0;
+    for (int b = 0; b < e->cfg.max_batch; ++b)
+        if (slot_grows(e, b)) lack += chunk_pages_lacking(e, b, n_steps * (e->spec_k + 1));
+    *pages = (int32_t)std::max<int64_t>(0, lack - (int64_t)e->free_pages.size());
+    return DOTS_OK;
+}
+
 int dots_kv_pool_info(DotsEngine* e, int32_t* total_pages, int32_t* free_pages) {
     if (!e || !total_pages || !free_pages) return DOTS_E_INVALID;
     *total_pages = e->n_pool_pages;
@@ -379,6 +577,7 @@ int dots_set_kv_scales(DotsEngine* e, const float* scales_host) {
             return e->fail(DOTS_E_INVALID, "kv scale %zu (layer %zu, kv head %zu, %s) is %g: must be finite and > 0", i, i / (2 * c.num_kv_heads),
                            (i / 2) % c.num_kv_heads, i % 2 ? "V" : "K", (double)scales_host[i]);
     // a cached token was quantised with the scales of its time: they are fixed while any sequence holds pages
+    if (e->n_parked) return e->fail(DOTS_E_STATE, "KV scales cannot change while %d slot(s) are suspended: their KV is parked in host memory", e->n_parked);
     if ((int)e->free_pages.size() != e->n_pool_pages)
         return e->fail(DOTS_E_STATE, "KV scales cannot change while sequences hold KV pages (%d of %d in use): release them first (dots_slots_reset)",
                        e->n_pool_pages - (int)e->free_pages.size(), e->n_pool_pages);

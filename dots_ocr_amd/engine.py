@@ -292,7 +292,10 @@ def banned_ngram_ids(out, n: int, window: int = 0, whitelist=()) -> set:
 
 
 class DotsEngineError(RuntimeError):
-    pass
+    code = None                                      # the DOTS_E_* code of the failed call, where there was one
+
+
+E_INVALID, E_HIP, E_STATE, E_CAPACITY = -1, -2, -3, -4      # include/dots_ocr_hip.h
 
 
 _SIGNATURES_SET = False
@@ -337,6 +340,11 @@ def _prototypes(lib):
         "dots_slot_read": (i32, [vp, i32, P(i32), i32, P(i32)]),
         "dots_slot_release": (i32, [vp, i32]),
         "dots_kv_pool_info": (i32, [vp, P(i32), P(i32)]),
+        "dots_kv_swap_reserve": (i32, [vp, i32]),
+        "dots_kv_swap_info": (i32, [vp, P(i32), P(i32)]),
+        "dots_slot_suspend": (i32, [vp, i32]),
+        "dots_slot_resume": (i32, [vp, i32]),
+        "dots_slots_pages_short": (i32, [vp, i32, P(i32)]),
         "dots_set_kv_scales": (i32, [vp, P(f32)]),
         "dots_get_logits": (i32, [vp, P(f32)]),
         "dots_set_next_tokens": (i32, [vp, P(i32), i32]),
@@ -414,6 +422,7 @@ EXPORTED_SYMBOLS = [
     "dots_create", "dots_destroy", "dots_last_error", "dots_stream", "dots_load_weight", "dots_finalize_weights",
     "dots_vit_forward", "dots_vit_prefetch", "dots_vit_take_prefetched", "dots_vit_prefetch_ready", "dots_preprocess_image", "dots_prefill", "dots_decode_step", "dots_generate", "dots_set_sampling", "dots_set_decode_plan", "dots_set_gemm_plan", "dots_tower_tail", "dots_get_logits",
     "dots_set_eos", "dots_slots_prefill", "dots_slots_decode", "dots_slots_poll", "dots_slot_read", "dots_slot_release", "dots_kv_pool_info", "dots_slot_capacity", "dots_slots_reset",
+    "dots_kv_swap_reserve", "dots_kv_swap_info", "dots_slot_suspend", "dots_slot_resume", "dots_slots_pages_short",
     "dots_set_next_tokens", "dots_get_last_tokens", "dots_get_stats", "dots_synchronize", "dots_debug_capture_hidden",
     "dots_debug_read_hidden", "dots_dev_alloc",
     "dots_dev_free", "dots_memcpy_h2d", "dots_memcpy_d2h", "dots_op_rmsnorm", "dots_op_layernorm", "dots_op_gemm", "dots_op_quant_fp8", "dots_op_gemm_fp8",
@@ -570,7 +579,9 @@ class Engine:
     # ------------------------------------------------------------------ plumbing
     def _ck(self, rc: int, what: str):
         if rc != 0:
-            raise DotsEngineError(f"{what} failed ({rc}): {self.lib.dots_last_error(self.h).decode()}")
+            err = DotsEngineError(f"{what} failed ({rc}): {self.lib.dots_last_error(self.h).decode()}")
+            err.code = rc                            # the DOTS_E_* code: E_STATE / E_CAPACITY tell a refusal from a failure
+            raise err
 
     def close(self):
         if getattr(self, "h", None):
@@ -1161,7 +1172,7 @@ class Engine:
         self._ck(self.lib.dots_slots_decode(self.h, int(n_steps)), "dots_slots_decode")
 
     def slots_poll(self):
-        """-> (finished [max_batch]: -1 free / 0 running / 1 finished, out_lens [max_batch])"""
+        """-> (finished [max_batch]: -1 free / 0 running / 1 finished / 2 suspended, out_lens [max_batch])"""
         fin = np.empty((self.max_batch,), dtype=np.int32)
         lens = np.empty((self.max_batch,), dtype=np.int32)
         self._ck(self.lib.dots_slots_poll(self.h, _i32p(fin), _i32p(lens)), "dots_slots_poll")
@@ -1188,6 +1199,32 @@ class Engine:
         tot, free = C.c_int32(0), C.c_int32(0)
         self._ck(self.lib.dots_kv_pool_info(self.h, C.byref(tot), C.byref(free)), "dots_kv_pool_info")
         return int(tot.value), int(free.value)
+
+    # ------------------------------------------------------------------ suspend / resume
+    def kv_swap_reserve(self, pages: int):
+        """Pinned host space for `pages` 64-token KV pages (each across all layers); 0 frees it.  Refused while a slot is suspended."""
+        self._ck(self.lib.dots_kv_swap_reserve(self.h, int(pages)), "dots_kv_swap_reserve")
+
+    def kv_swap_info(self):
+        """(total, free) pages of the host space."""
+        tot, free = C.c_int32(0), C.c_int32(0)
+        self._ck(self.lib.dots_kv_swap_info(self.h, C.byref(tot), C.byref(free)), "dots_kv_swap_info")
+        return int(tot.value), int(free.value)
+
+    def slot_suspend(self, slot: int):
+        """Park a running sequence: the pages it holds alone go to the host space and back to the pool, the slot keeps all its row state
+        and idles (slots_poll reports 2).  DotsEngineError with code DOTS_E_STATE / DOTS_E_CAPACITY and nothing changed when refused."""
+        self._ck(self.lib.dots_slot_suspend(self.h, int(slot)), "dots_slot_suspend")
+
+    def slot_resume(self, slot: int):
+        """Continue a suspended sequence on fresh pages: it generates exactly what it would have generated undisturbed."""
+        self._ck(self.lib.dots_slot_resume(self.h, int(slot)), "dots_slot_resume")
+
+    def slots_pages_short(self, n_steps: int) -> int:
+        """Pages the next slots_decode(n_steps) would fail to obtain (0: it caps no sequence)."""
+        n = C.c_int32(0)
+        self._ck(self.lib.dots_slots_pages_short(self.h, int(n_steps), C.byref(n)), "dots_slots_pages_short")
+        return int(n.value)
 
     def set_kv_scales(self, scales):
         """fp8 KV cache scales, fp32 [num_layers, num_kv_heads, 2] (K, V; anything broadcastable to it), each finite and > 0.  Refused

@@ -66,8 +66,23 @@ class ContinuousBatcher:
     """submit() requests at any time, call step() in a loop (or run() for a closed set)."""
 
     def __init__(self, engine, eos_ids: Sequence[int] = (), chunk: int = 16, headroom_pages: Optional[int] = 2, prefetch: int = 0,
-                 tower_steps_per_page: int = 48, admit_group: Optional[int] = None):
+                 tower_steps_per_page: int = 48, admit_group: Optional[int] = None, preemption: Optional[str] = None,
+                 swap_pages: Optional[int] = None):
         self.engine = engine
+        # preemption (DESIGN §6.10).  None: a dry KV pool ends a sequence early at what its pages hold ("kv_pool_exhausted").  "swap":
+        # before a decode chunk that would run short, the most recently admitted sequences are suspended — their KV parked in swap_pages
+        # pages of pinned host memory (default: as many as the pool has) — and resumed, oldest suspension first, when the pool has room
+        # again; every sequence generates exactly what it would have generated alone (vLLM's swap preemption)
+        if preemption not in (None, "swap"):
+            raise ValueError(f"preemption must be None or 'swap', got {preemption!r}")
+        if preemption == "swap":
+            if not all(hasattr(engine, f) for f in ("slot_suspend", "slot_resume", "slots_pages_short", "kv_swap_reserve", "kv_swap_info")):
+                raise ValueError("this engine cannot suspend a sequence (no slot_suspend): preemption='swap' is not available")
+            if getattr(engine, "spec_k", 0):
+                raise ValueError("preemption='swap' cannot be combined with a speculating engine: a suspended row idles, a draft row cannot")
+        elif swap_pages is not None:
+            raise ValueError("swap_pages needs preemption='swap'")
+        self.preemption = preemption
         self.chunk = max(1, int(chunk))
         # free KV pages kept per running sequence when admitting (see plan_admission).  None = FULL RESERVATION: a sequence is admitted only
         # when the pool could hold prompt + max_new_tokens of every running sequence and of this one, so nothing is ever truncated by a dry
@@ -109,6 +124,13 @@ class ContinuousBatcher:
         self._kids: Dict[int, List[int]] = {}                    # request id -> the slots planned for sequences 1 .. n - 1 of a request with n > 1
         self._seq_index: Dict[int, int] = {}                     # slot -> index of its sequence within a request with n > 1
         self.kv_truncated = 0                                    # sequences ended early by a dry KV pool (finish reason "kv_pool_exhausted")
+        self.preemptions = 0                                     # sequences suspended (preemption="swap")
+        self.resumes = 0                                         # ... and resumed
+        self.swapped_pages = 0                                   # KV pages copied out to host memory (each comes back once)
+        self.suspended: List[int] = []                           # suspended slots, longest suspended first (they stay in `running`)
+        self._parked_pages: Dict[int, int] = {}                  # suspended slot -> host pages it holds = pool pages its resume takes
+        self._admit_seq: Dict[int, int] = {}                     # slot -> admission counter (the victim order: most recent first)
+        self._admit_count = 0
         self._rejected: List[Tuple[int, Request]] = []           # requests whose own parameters the engine refused (reported by step())
         self.eos_ids = tuple(int(t) for t in eos_ids)
         engine.set_eos(list(eos_ids))
@@ -119,6 +141,8 @@ class ContinuousBatcher:
             for s in range(self.n_slots):
                 if fin[s] >= 0:
                     engine.slot_release(s)
+        if preemption == "swap":                     # after the reset: nothing is parked any more, the host space may change
+            engine.kv_swap_reserve(int(engine.kv_pool_info()[0]) if swap_pages is None else max(0, int(swap_pages)))
 
     # ------------------------------------------------------------------ queue
     def submit(self, req: Request) -> int:
@@ -169,6 +193,10 @@ class ContinuousBatcher:
         if self.full_reservation and hasattr(self.engine, "kv_pool_info") and self._worst_pages(req) > self.engine.kv_pool_info()[0]:
             raise ValueError(f"prompt + max_new_tokens = {ids.shape[0]} + {req.max_new_tokens} tokens need {self._worst_pages(req)} KV pages under full "
                              f"reservation, the pool holds {self.engine.kv_pool_info()[0]}")
+        if self.preemption == "swap" and self._worst_pages(req) > self.engine.kv_pool_info()[0]:
+            # with everything else suspended a request must be able to finish on its own: otherwise preemption could not help it
+            raise ValueError(f"prompt + max_new_tokens = {ids.shape[0]} + {req.max_new_tokens} tokens need {self._worst_pages(req)} KV pages, the pool "
+                             f"holds {self.engine.kv_pool_info()[0]}: with preemption='swap' a request must fit the pool alone")
         rid = self._next_id
         self._next_id += 1
         self.pending.append((rid, req))
@@ -260,6 +288,8 @@ class ContinuousBatcher:
     def plan_admission(self) -> List[Tuple[int, int, Request]]:
         """FIFO: pop requests while a slot is free and the group fits the ViT and prefill workspaces.
         Lowest slots first, so the decode graph covers as few rows as possible."""
+        if self.suspended:
+            return []                                # nothing new while anything is suspended: the pool's room goes to the resumes first
         free = self.free_slots()
         group, patches, tokens = [], 0, 0
         pages_free = self.engine.kv_pool_info()[1] if hasattr(self.engine, "kv_pool_info") else 1 << 30
@@ -392,6 +422,8 @@ class ContinuousBatcher:
         for s, rid, r in group:
             for j, k in enumerate([s] + kids.get(rid, [])):
                 self.running[k] = (rid, r)
+                self._admit_count += 1
+                self._admit_seq[k] = self._admit_count
                 self._last_lens[k] = 0               # a reused slot must not inherit its previous occupant's length (_soon_free counted a
                                                      # just-admitted long request as "about to finish" and the look-ahead group was sized for slots that stayed busy)
                 if r.n > 1:
@@ -428,7 +460,7 @@ class ContinuousBatcher:
     def _admit_ahead(self) -> bool:
         """The group whose tower was prefetched goes in as a whole as soon as it has the slots and the pages."""
         free = self.free_slots()
-        if len(free) < sum(r.width for _, r in self._ahead):
+        if self.suspended or len(free) < sum(r.width for _, r in self._ahead):
             return False
         # sequences are decoding and the tower is still running: taking the group now would queue every decode chunk behind the tower
         # (vit_take makes the engine's stream wait for it) — keep decoding, take it when its rows exist.  Nothing running: wait for it.
@@ -521,6 +553,7 @@ class ContinuousBatcher:
                 continue
             if fin[s] == 1:
                 rid, req = self.running.pop(s)
+                self._admit_seq.pop(s, None)
                 toks = self.engine.slot_read(s, int(lens[s]))
                 # a sequence the engine ended early because the KV pool ran dry (its cap was lowered to what its pages hold) is not an
                 # ordinary "length" stop: say so on the request, count it, let the server report it
@@ -582,6 +615,7 @@ class ContinuousBatcher:
         req.kv_truncated = False                     # a group is fully reserved: the pool cannot run dry under it
         for k in [k for k, (r2, _) in self.running.items() if r2 == rid]:
             del self.running[k]
+            self._admit_seq.pop(k, None)
         self.engine.slot_release(s)                  # one slot of the group releases all of them
         return rid, req, req.outputs[0] if req.outputs else np.zeros(0, np.int32)
 
@@ -592,7 +626,56 @@ class ContinuousBatcher:
         rejected, self._rejected = self._rejected, []
         return [(rid, r, np.zeros(0, np.int32)) for rid, r in rejected] + out
 
+    # ------------------------------------------------------------------ preemption
+    def _active(self) -> List[int]:
+        """slots of the sequences that take decode steps: running and not suspended"""
+        return [s for s in self.running if s not in self._parked_pages]
+
+    def _resume(self):
+        """The longest-suspended sequence comes back once the pool can hold its pages, the next chunk of every active sequence and of
+        itself, and the admission headroom; with nothing else active it comes back as soon as its pages fit (submit() made sure that a
+        request can finish alone).  One at a time, in suspension order: nothing overtakes the head."""
+        ahead = -(-self.chunk // 64)                 # pages a sequence can take in one chunk
+        while self.suspended:
+            s = self.suspended[0]
+            need, active = self._parked_pages[s], len(self._active())
+            room = need + ((ahead + self.headroom_pages) * (active + 1) if active else 0)
+            if self.engine.kv_pool_info()[1] < room:
+                return
+            self.engine.slot_resume(s)
+            self.suspended.pop(0)
+            del self._parked_pages[s]
+            self.resumes += 1
+
+    def _preempt(self):
+        """Before a decode chunk: while the engine says the chunk would run short of pages, suspend the most recently admitted active
+        sequence — never a beam-group row (a group is fully reserved and cannot be parked), never the last active sequence.  A full host
+        space ends the loop: the engine then caps a sequence as it does without preemption (counted in kv_truncated)."""
+        from .engine import E_CAPACITY, E_STATE, DotsEngineError
+        while self.engine.slots_pages_short(self.chunk) > 0:
+            active = self._active()
+            victims = [s for s in active if not self.running[s][1].num_beams]
+            if len(active) <= 1 or not victims:
+                return
+            s = max(victims, key=lambda k: self._admit_seq.get(k, 0))
+            host_free = self.engine.kv_swap_info()[1]
+            try:
+                self.engine.slot_suspend(s)
+            except DotsEngineError as e:
+                if getattr(e, "code", None) not in (E_STATE, E_CAPACITY):
+                    raise
+                return                               # the host space is full (or the row cannot be parked): cap as before
+            self._parked_pages[s] = host_free - self.engine.kv_swap_info()[1]
+            self.suspended.append(s)
+            self.preemptions += 1
+            self.swapped_pages += self._parked_pages[s]
+
     def _step(self) -> List[Tuple[int, Request, np.ndarray]]:
+        if self.suspended:
+            self._resume()                           # before admission: a suspended sequence is older than anything in the queue
+            if self.suspended and not self._active():
+                raise RuntimeError(f"slot {self.suspended[0]} is suspended and cannot be resumed into an otherwise idle engine "
+                                   f"(KV pool {self.engine.kv_pool_info()}, {self._parked_pages[self.suspended[0]]} pages parked)")
         if self._ahead:                              # a prefetched group waits for its slots: nothing may overtake it
             admitted = self._admit_ahead()
         else:
@@ -626,6 +709,8 @@ class ContinuousBatcher:
                 raise RuntimeError(f"request {rid} ({req.input_ids.shape[0]} prompt tokens, {req.n_patches()} patches) cannot be admitted "
                                    f"into an empty engine (KV pool {self.engine.kv_pool_info() if hasattr(self.engine, 'kv_pool_info') else '?'})")
             return []
+        if self.preemption == "swap":
+            self._preempt()
         self.engine.slots_decode(self.chunk)
         self.decode_steps += self.chunk
         return self._collect()

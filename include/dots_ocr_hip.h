@@ -446,7 +446,7 @@ int dots_set_gemm_plan(DotsEngine* e, int plan);
  *                    every running sequence is given the KV pages its next n_steps positions need (on-demand paging); if the pool
  *                    is dry the sequence keeps its pages and its generation cap is lowered to what they hold — it finishes there
  *                    (reason "length", as HF generate does at the context capacity); dots_slot_capacity reports the lowered cap.
- * dots_slots_poll    finished[b] = -1 free / 0 running / 1 finished, out_lens[b] = tokens generated so far; both
+ * dots_slots_poll    finished[b] = -1 free / 0 running / 1 finished / 2 suspended (dots_slot_suspend), out_lens[b] = tokens generated so far; both
  *                    int32 [max_batch].  Synchronises the stream.
  * dots_slot_read     copies min(n, capacity) generated ids of one occupied slot, *n_out = n.
  * dots_slot_release  marks the slot free.
@@ -509,8 +509,36 @@ int dots_kv_pool_info(DotsEngine* e, int32_t* total_pages, int32_t* free_pages);
  * dots_slots_reset or the next dots_prefill releases them): a cached token keeps the scales it was written with.  Accepted for a bf16
  * cache too, where nothing reads them. */
 int dots_set_kv_scales(DotsEngine* e, const float* scales_host);
-/* Pages an occupied slot owns and its current limit on prompt + generated tokens (prompt + max_new_tokens unless the pool ran dry). */
+/* Pages an occupied slot owns and its current limit on prompt + generated tokens (prompt + max_new_tokens unless the pool ran dry).  Of a
+ * suspended slot: the pages that stayed resident. */
 int dots_slot_capacity(DotsEngine* e, int slot, int32_t* pages_owned, int32_t* token_limit);
+/* ---- Suspend and resume (vLLM's "swap" preemption): a running sequence is parked in its slot, its KV pages are moved to pinned
+ * host memory and given back to the pool; later it continues on whatever pages are free then and generates, bit for bit, the tokens and
+ * logprobs it would have generated undisturbed.  Opt-in: an engine that never calls these launches what it always did.
+ *
+ * dots_kv_swap_reserve    pinned host space for `pages` 64-token pages (each across all layers); regrown or, with 0, freed.  DOTS_E_STATE
+ *                         while any slot is suspended.  Synchronises.
+ * dots_kv_swap_info       host pages in total / currently free.
+ * dots_slot_suspend       the slot must be occupied, running (not finished), not suspended, not a row of a beam group, and the engine must
+ *                         not speculate (DOTS_E_STATE otherwise).  Every page the row holds alone is returned to the pool, those that hold
+ *                         positions of its context after a copy to the host space; a page with other holders (the shared prompt pages of a
+ *                         fork) stays resident and the row keeps its reference.  DOTS_E_CAPACITY when the host space cannot take the pages.
+ *                         The slot stays occupied and keeps its row state (output, sampling / rule / guide / n-gram / stop state, logprobs):
+ *                         dots_slot_read, dots_row_logprobs, dots_row_guide_state and dots_row_stop_hit work on it, dots_slots_poll reports
+ *                         2 for it with out_lens as at the suspension, dots_slots_decode steps the others and gives it no pages,
+ *                         dots_slot_release frees its host pages too, dots_slots_reset drops everything parked.  While a slot is
+ *                         suspended, dots_set_speculation and dots_set_kv_scales are refused and the slot can be neither forked nor made a
+ *                         beam group.  Synchronises.
+ * dots_slot_resume        fresh pages from the free list, the KV copied back, the row running again.  DOTS_E_STATE: not suspended;
+ *                         DOTS_E_CAPACITY: the pool cannot serve the row's pages.  Synchronises.
+ * dots_slots_pages_short  *pages = how many pages the next dots_slots_decode(n_steps) would fail to obtain (0: no sequence would be capped),
+ *                         by that call's own arithmetic.
+ * Every refusal leaves pool, host space and slots unchanged. */
+int dots_kv_swap_reserve(DotsEngine* e, int pages);
+int dots_kv_swap_info(DotsEngine* e, int32_t* total_pages, int32_t* free_pages);
+int dots_slot_suspend(DotsEngine* e, int slot);
+int dots_slot_resume(DotsEngine* e, int slot);
+int dots_slots_pages_short(DotsEngine* e, int n_steps, int32_t* pages);
 
 /* fp32 logits [B, vocab] of the most recent prefill/decode step (tolerance checks). */
 int dots_get_logits(DotsEngine* e, float* out_host);
