@@ -21,3 +21,23 @@ def inference_with_vllm(image, prompt, protocol="http", ip="localhost", port=800
     except requests.exceptions.RequestException as e:
         print(f"request error: {e}")
         return None
+
+
+def inference_prompts_with_vllm(image, prompts, protocol="http", ip="localhost", port=8000, temperature=0.1, top_p=0.9,
+                                max_completion_tokens=32768, model_name="rednote-hilab/dots.mocr", system_prompt=None, extra_body=None):
+    """Several prompts over ONE page in one request: the dots_ocr_amd server's own `prompts` field.  The page goes through
+    the vision tower and the prefill once; choice i answers prompts[i].  Returns the texts in that order, or None on a request error."""
+    import requests
+    from openai import OpenAI        # optional dependency, imported lazily
+    client = OpenAI(api_key=os.environ.get("API_KEY", "0"), base_url=f"{protocol}://{ip}:{port}/v1")
+    messages = [{"role": "system", "content": system_prompt}] if system_prompt else []
+    messages.append({"role": "user", "content": [
+        {"type": "image_url", "image_url": {"url": PILimage_to_base64(image)}},
+        {"type": "text", "text": prompts[0]}]})
+    try:
+        r = client.chat.completions.create(messages=messages, model=model_name, max_completion_tokens=max_completion_tokens,
+                                           temperature=temperature, top_p=top_p, extra_body={**(extra_body or {}), "prompts": list(prompts)})
+        return [c.message.content for c in sorted(r.choices, key=lambda c: c.index)]
+    except requests.exceptions.RequestException as e:
+        print(f"request error: {e}")
+        return None

@@ -270,6 +270,12 @@ struct DotsEngine {
         int32_t cur_token = 0, ctx = 0, finished = 0;
     };
     Parked parked[DOTS_MAX_BATCH];
+    // extending a live sequence (dots_slots_extend), allocated by the first call: the step-private row arrays of a chunk
+    // (kernels.h ExtendRows), the hidden rows of the slots' last fed tokens ([max_batch][hidden], rows are slots: what the lm_head of the call
+    // reads), and the call's staged lists (ex_stage, ex_stage_cap int32: regrown when a call packs more rows)
+    int32_t *ex_tokens = nullptr, *ex_ctx = nullptr, *ex_table = nullptr, *ex_stage = nullptr;
+    size_t ex_stage_cap = 0;
+    bf16_t* ex_h = nullptr;
     // captured decode steps, keyed by everything the capture bakes in: rows, KV splits, static batch (out_cap = row stride of
     // the output buffer) or slot mode (out_cap = 0), number of EOS ids, whether any row carries its own parameters (rowp: the per-row
     // selection stage), whether any row returns logprobs (lp), whether any row carries logit rules (rules: the stage then gets their
@@ -395,6 +401,8 @@ void drop_step_graphs(DotsEngine* e);
 int chain_streams(DotsEngine* e, hipStream_t from, hipStream_t to);
 int pick_decode_stream(DotsEngine* e, hipStream_t* cur);
 int prefill(DotsEngine* e, const int32_t* ids, const int32_t* lens, int B, const int32_t* slots = nullptr, const int32_t* max_new = nullptr);
+int decode_layers(DotsEngine* e, const int32_t* tokens, const int32_t* ctx_len, const int32_t* block_table, int B, int n_splits, int part, bool* pend,
+                  const float** pend_scale);
 int decode_step_launches(DotsEngine* e, int n_splits, int part = 0);
 int splits_for_ctx(int max_ctx);
 int step_graph(DotsEngine* e, int rows, int n_splits, int out_cap, hipGraphExec_t* exec, int part = 0);

@@ -516,23 +516,15 @@ int prefill(DotsEngine* e, const int32_t* ids, const int32_t* lens, int B, const
     return DOTS_OK;
 }
 
-// every launch of one decode step; identical in eager mode and under graph capture
-// part: the launch plan for a stream that is CU-masked to half the chip (whole 16-row tiles: half as many workgroups per projection)
-int decode_step_launches(DotsEngine* e, int n_splits, int part) {
+// The layers of one decode step over B rows: embedding, then every layer's launches.  tokens / ctx_len [B] and block_table [B][max_pages]
+// are the slots' own arrays in a plain step and step-private ones in a speculating step and in a chunk of dots_slots_extend.  *pend: the
+// last down_proj left its K-quarter sums in d_part_h for the consumer of the residual stream to apply (with *pend_scale)
+int decode_layers(DotsEngine* e, const int32_t* tokens, const int32_t* ctx_len, const int32_t* block_table, int B, int n_splits, int part, bool* pend_out,
+                  const float** pend_scale_out) {
     const DotsConfig& c = e->cfg;
     hipStream_t s = e->stream;
     const int H = c.hidden_size, Hq = c.num_heads, Hkv = c.num_kv_heads, Nq = Hq * 128, I = c.intermediate_size;
-    // A speculating step (slot mode, dots_set_speculation): `rows` slots become B = rows x (k + 1) rows whose tokens, contexts and
-    // block-table rows spec_expand_kernel builds; the first `rows` of them are the rows of the plain step (DESIGN §6.6)
-    const int rows = e->B, spec_k = e->slot_mode ? e->spec_k : 0;
-    const int B = rows * (spec_k + 1);
     const float scale = 1.0f / sqrtf(128.0f);
-    const int32_t *tokens = e->cur_tokens, *ctx_len = e->ctx_len, *block_table = e->block_table;
-    const SpecState sp = spec_state(e);
-    if (spec_k) {
-        CK(launch_spec_expand(s, sp, step_state(e, 1, e->d_sel), e->block_table, e->max_pages, rows, e->n_pool_pages));
-        tokens = e->sp_tokens; ctx_len = e->sp_ctx; block_table = e->sp_table;
-    }
     CK(launch_dec_embed(s, tokens, e->embed, e->d_h, B, H));
     if (e->force_part) part = 1;                                                   // dots_set_decode_plan(1): the partition plan on every step (tests, A/B runs)
     static const bool same_layer = getenv("DOTS_OCR_DEBUG_SAME_LAYER") != nullptr;   // experiment: all weight reads hit the Infinity Cache
@@ -552,6 +544,31 @@ int decode_step_launches(DotsEngine* e, int n_splits, int part) {
         CK(launch_dec_proj(s, e->d_act, L.down_wd, L.down_s, e->d_h, B, H, I, part ? e->dec_cus : 0, e->d_part_h, &pend));
         pend_scale = L.down_s;
     }
+    *pend_out = pend;
+    *pend_scale_out = pend_scale;
+    return DOTS_OK;
+}
+
+// every launch of one decode step; identical in eager mode and under graph capture
+// part: the launch plan for a stream that is CU-masked to half the chip (whole 16-row tiles: half as many workgroups per projection)
+int decode_step_launches(DotsEngine* e, int n_splits, int part) {
+    const DotsConfig& c = e->cfg;
+    hipStream_t s = e->stream;
+    const int H = c.hidden_size;
+    // A speculating step (slot mode, dots_set_speculation): `rows` slots become B = rows x (k + 1) rows whose tokens, contexts and
+    // block-table rows spec_expand_kernel builds; the first `rows` of them are the rows of the plain step (DESIGN §6.6)
+    const int rows = e->B, spec_k = e->slot_mode ? e->spec_k : 0;
+    const int B = rows * (spec_k + 1);
+    const int32_t *tokens = e->cur_tokens, *ctx_len = e->ctx_len, *block_table = e->block_table;
+    const SpecState sp = spec_state(e);
+    if (spec_k) {
+        CK(launch_spec_expand(s, sp, step_state(e, 1, e->d_sel), e->block_table, e->max_pages, rows, e->n_pool_pages));
+        tokens = e->sp_tokens; ctx_len = e->sp_ctx; block_table = e->sp_table;
+    }
+    bool pend = false;
+    const float* pend_scale = nullptr;
+    RET(decode_layers(e, tokens, ctx_len, block_table, B, n_splits, part, &pend, &pend_scale));
+    if (e->force_part) part = 1;                                                   // as the layers ran (decode_layers)
     CK(launch_dec_lmhead(s, e->d_h, e->final_norm, e->lm_head_d, e->lm_head_s, e->d_logits, B, H, c.vocab_size, c.rms_norm_eps, part ? e->dec_cus : 0, e->d_xn,
                          pend ? e->d_part_h : nullptr, pend_scale));
     if (spec_k) CK(launch_spec_argmax(s, sp, e->d_logits, c.vocab_size, c.vocab_size, rows, e->am_val, e->am_idx));

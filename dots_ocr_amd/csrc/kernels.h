@@ -328,6 +328,22 @@ hipError_t launch_ngram_draft(hipStream_t s, const int32_t* out_ids, const int32
 hipError_t launch_spec_set_class(hipStream_t s, int32_t* cls, int row, int value);
 // drafts[row][0 .. n) = ids_host, n_draft[row] = n, in stream order (the ids travel as a kernel argument)
 hipError_t launch_spec_set_drafts(hipStream_t s, int32_t* drafts, int32_t* n_draft, int row, const int32_t* ids_host, int n);
+// ---- extend.hip: more prompt tokens behind a live sequence (dots_slots_extend)
+// ExtendRows: the packed rows of one call — row i feeds token[i] (-1: the slot's pending token, read on the device) to slot slot[i] at
+// context ctx_len[slot] + off[i] — and the step-private arrays of a chunk (tokens / ctx_len [DOTS_MAX_BATCH], block_table [DOTS_MAX_BATCH]
+// [max_pages]), which exist whether or not speculation was ever switched on.
+struct ExtendRows {
+    const int32_t *slot, *off, *token;
+    int32_t *tokens, *ctx_len, *block_table;
+};
+// the arrays of the chunk that holds packed rows [r0, r0 + n_live): step row r < n_live names the slot's KV pages; rows [n_live, rows) idle
+// at context 0 on scratch_page, like a released slot.  Reads the slots' state (cur_tokens .. block_table), writes none of it
+hipError_t launch_extend_expand(hipStream_t s, const ExtendRows& ex, int r0, int n_live, int rows, const int32_t* cur_tokens, const int32_t* ctx_len,
+                                const int32_t* finished, const int32_t* out_ids, const int32_t* out_lens, int out_stride, const int32_t* block_table,
+                                int max_pages, int scratch_page);
+// after the last chunk, for the n extended slots: ctx_len += fed, out_lens = 0, finished = 0, max_len = max_new
+hipError_t launch_extend_commit(hipStream_t s, const int32_t* slots, const int32_t* fed, const int32_t* max_new, int n, int32_t* ctx_len,
+                                int32_t* out_lens, int32_t* finished, int32_t* max_len);
 
 // ---- logprobs.hip: log-probabilities of the raw logits of every selected row
 #ifndef DOTS_MAX_TOP_LOGPROBS

@@ -221,6 +221,175 @@ int dots_slots_fork(DotsEngine* e, int src_slot, const int32_t* dst_slots, int n
     return DOTS_OK;
 }
 
+// More prompt tokens behind live sequences.  Everything is validated and counted before anything changes; the packed rows
+// then run through the layer loop of a decode step in chunks of at most max_batch rows, and the slots end as slots prefilled with the
+// longer prompt, their first token selected from the logits of their last fed row.
+int dots_slots_extend(DotsEngine* e, const int32_t* slots, int n, const int32_t* ids, const int32_t* lens, const int32_t* keep_pending,
+                      const int32_t* max_new_tokens) {
+    if (!e) return DOTS_E_INVALID;
+    if (!e->finalized) return e->fail(DOTS_E_STATE, "weights not finalized");
+    if (!slots || !ids || !lens || !keep_pending || !max_new_tokens) return e->fail(DOTS_E_INVALID, "null argument");
+    const DotsConfig& c = e->cfg;
+    const int mb = c.max_batch, V = c.vocab_size, H = c.hidden_size;
+    if (n < 1 || n > mb) return e->fail(DOTS_E_INVALID, "dots_slots_extend: n must be in [1, %d]", mb);
+    if (!e->slot_mode) return e->fail(DOTS_E_STATE, "dots_slots_extend: the engine runs a static batch; only a slot sequence can be extended");
+    if (e->spec_k) return e->fail(DOTS_E_STATE, "a slot cannot be extended while the engine speculates (dots_set_speculation)");
+    int64_t n_ids = 0;
+    for (int i = 0; i < n; ++i) {
+        const int b = slots[i];
+        if (b < 0 || b >= mb) return e->fail(DOTS_E_INVALID, "slot %d out of range [0, %d)", b, mb);
+        if (!e->slot_active[b]) return e->fail(DOTS_E_STATE, "slot %d is not occupied", b);
+        if (e->parked[b].on) return e->fail(DOTS_E_STATE, "slot %d is suspended: resume it first", b);
+        if (e->beam_of[b]) return e->fail(DOTS_E_STATE, "slot %d is a row of a beam group: a group cannot be extended", b);
+        for (int a = 0; a < i; ++a)
+            if (slots[a] == b) return e->fail(DOTS_E_INVALID, "slot %d listed twice", b);
+        if (lens[i] < 1) return e->fail(DOTS_E_INVALID, "slot %d: at least one token must be fed, got %d", b, lens[i]);
+        if (max_new_tokens[i] < 1) return e->fail(DOTS_E_INVALID, "slot %d: max_new_tokens must be >= 1, got %d", b, max_new_tokens[i]);
+        if (e->stage.has(b, ROW_PARAMS) && e->row_pen[b])
+            return e->fail(DOTS_E_STATE, "slot %d carries a penalty: its prompt-presence image would have to absorb the earlier output, so it cannot be extended", b);
+        for (int j = 0; j < lens[i]; ++j) {
+            const int id = ids[n_ids + j];
+            if (id < 0 || id >= V) return e->fail(DOTS_E_INVALID, "token id %d out of range", id);
+            if (id == c.image_token_id) return e->fail(DOTS_E_INVALID, "slot %d: an image token cannot be fed by an extend (the vision rows enter at the prefill)", b);
+        }
+        n_ids += lens[i];
+    }
+    CK(hipSetDevice(e->device));
+    hipStream_t s = e->stream;
+    // ---- the true contexts (slot_ctx_ub is only a bound once a row has finished early), then the page arithmetic, before anything changes
+    int32_t ctx[DOTS_MAX_BATCH] = {0};
+    CK(hipMemcpyAsync(ctx, e->ctx_len, (size_t)mb * 4, hipMemcpyDeviceToHost, s));
+    CK(hipStreamSynchronize(s));
+    int fed[DOTS_MAX_BATCH], new_prompt[DOTS_MAX_BATCH], old_pages[DOTS_MAX_BATCH];
+    int64_t n_rows = 0, lacking = 0;
+    for (int i = 0; i < n; ++i) {
+        const int b = slots[i], cb = ctx[b];
+        fed[i] = lens[i] + (keep_pending[i] ? 1 : 0);
+        new_prompt[i] = cb + fed[i];
+        const auto& mine = e->slot_pages[b];
+        old_pages[i] = (int)mine.size();
+        if (cb < 1 || (cb + 63) / 64 > (int)mine.size())
+            return e->fail(DOTS_E_STATE, "slot %d: context %d is not covered by its %d pages", b, cb, (int)mine.size());
+        if ((int64_t)new_prompt[i] + max_new_tokens[i] > c.max_seq_len)
+            return e->fail(DOTS_E_CAPACITY, "slot %d: extended prompt (%d + %d) + max_new_tokens (%d) exceeds max_seq_len %d", b, cb, fed[i], max_new_tokens[i],
+                           c.max_seq_len);
+        // every fed position is written: its page must be the row's alone (the shared prompt pages of a fork all lie below the context)
+        for (int p = cb / 64; p < (int)mine.size(); ++p)
+            if (e->page_refs[mine[p]] != 1) return e->fail(DOTS_E_STATE, "slot %d: page %d of its row has other holders and cannot be written", b, p);
+        const int need = std::min((admit_tokens(e, new_prompt[i], max_new_tokens[i]) + 63) / 64, e->max_pages);
+        if (need * 64 < new_prompt[i]) return e->fail(DOTS_E_CAPACITY, "slot %d: %d tokens exceed the block table", b, new_prompt[i]);
+        lacking += std::max(0, need - (int)mine.size());
+        n_rows += fed[i];
+    }
+    if (lacking > (int64_t)e->free_pages.size())
+        return e->fail(DOTS_E_CAPACITY, "KV pool exhausted: the extended sequences need %d more pages of 64 tokens, %d of %d are free", (int)lacking,
+                       (int)e->free_pages.size(), e->n_pool_pages);
+    // ---- the call's device buffers (nothing of the slots changes if one cannot be had)
+    if (!e->ex_tokens) CK(e->alloc(&e->ex_tokens, DOTS_MAX_BATCH));
+    if (!e->ex_ctx) CK(e->alloc(&e->ex_ctx, DOTS_MAX_BATCH));
+    if (!e->ex_table) CK(e->alloc(&e->ex_table, (size_t)DOTS_MAX_BATCH * e->max_pages));
+    if (!e->ex_h) CK(e->alloc(&e->ex_h, (size_t)DOTS_MAX_BATCH * H));
+    const size_t n_stage = 3 * (size_t)n_rows + 5 * (size_t)n;
+    if (e->ex_stage_cap < n_stage) {
+        CK(hipStreamSynchronize(s));
+        e->release(e->ex_stage);
+        e->ex_stage = nullptr;
+        e->ex_stage_cap = 0;
+        CK(e->alloc(&e->ex_stage, n_stage));
+        e->ex_stage_cap = n_stage;
+    }
+    // packed rows, slot by slot in the caller's order: (slot, offset from the slot's context, token or -1 = its pending token); then the
+    // per-slot lists; then, in chunk order, the step row that holds a slot's last fed token and the slot it belongs to
+    std::vector<int32_t> st(n_stage);
+    int32_t *h_slot = st.data(), *h_off = h_slot + n_rows, *h_tok = h_off + n_rows, *h_slots = h_tok + n_rows, *h_fed = h_slots + n, *h_new = h_fed + n,
+            *h_gsrc = h_new + n, *h_gdst = h_gsrc + n;
+    std::vector<int> chunk_g0((size_t)(n_rows + mb - 1) / mb + 1, 0);
+    int32_t sel_new[DOTS_MAX_BATCH] = {0};
+    int rows = 0;
+    {
+        int64_t r = 0, t = 0;
+        int g = 0;
+        for (int i = 0; i < n; ++i) {
+            for (int j = 0; j < fed[i]; ++j, ++r) {
+                h_slot[r] = slots[i];
+                h_off[r] = j;
+                h_tok[r] = keep_pending[i] ? (j == 0 ? -1 : ids[t + j - 1]) : ids[t + j];
+            }
+            t += lens[i];
+            h_slots[i] = slots[i]; h_fed[i] = fed[i]; h_new[i] = max_new_tokens[i];
+            h_gsrc[g] = (int32_t)((r - 1) % mb); h_gdst[g] = slots[i];      // slots end in row order, so the lists are in chunk order
+            chunk_g0[(size_t)((r - 1) / mb) + 1] = ++g;
+            sel_new[slots[i]] = 1;
+            rows = std::max(rows, slots[i] + 1);
+        }
+        for (size_t k = 1; k < chunk_g0.size(); ++k) chunk_g0[k] = std::max(chunk_g0[k], chunk_g0[k - 1]);
+    }
+    CK(hipMemcpyAsync(e->ex_stage, st.data(), n_stage * 4, hipMemcpyHostToDevice, s));
+    CK(hipMemcpyAsync(e->d_sel_new, sel_new, sizeof(sel_new), hipMemcpyHostToDevice, s));
+    CK(hipStreamSynchronize(s));                             // the staged lists are stack and local variables
+    const int32_t *d_slot = e->ex_stage, *d_off = d_slot + n_rows, *d_tok = d_off + n_rows, *d_slots = d_tok + n_rows, *d_fed = d_slots + n,
+                  *d_new = d_fed + n, *d_gsrc = d_new + n, *d_gdst = d_gsrc + n;
+    // ---- from here on the call changes state; a failed launch gives the new pages back
+    struct ExtendGuard {
+        DotsEngine* e; const int32_t* slots; const int* old_pages; int n; bool armed = true;
+        ~ExtendGuard() {
+            if (!armed) return;
+            for (int i = 0; i < n; ++i) {
+                auto& mine = e->slot_pages[slots[i]];
+                while ((int)mine.size() > old_pages[i]) {
+                    e->page_refs[mine.back()] = 0;
+                    e->free_pages.push_back(mine.back());
+                    mine.pop_back();
+                    e->hp_table[(size_t)slots[i] * e->max_pages + mine.size()] = e->n_pool_pages;
+                }
+                (void)upload_table_row(e, slots[i]);
+            }
+        }
+    } guard{e, slots, old_pages, n};
+    for (int i = 0; i < n; ++i) {
+        bool changed = false;
+        grow_pages(e, slots[i], admit_tokens(e, new_prompt[i], max_new_tokens[i]), &changed);      // cannot fall short: counted above
+        if (changed) CK(upload_table_row(e, slots[i]));
+    }
+    e->fresh_slots.clear();                                  // the call overwrites the logits a fork selects from: a fork comes before an extend
+    const ExtendRows ex{d_slot, d_off, d_tok, e->ex_tokens, e->ex_ctx, e->ex_table};
+    const int n_splits = splits_for_ctx(c.max_seq_len);
+    for (int64_t r0 = 0, k = 0; r0 < n_rows; r0 += mb, ++k) {
+        const int cn = (int)std::min<int64_t>(mb, n_rows - r0);
+        CK(launch_extend_expand(s, ex, (int)r0, cn, cn, e->cur_tokens, e->ctx_len, e->finished, e->out_ids, e->out_lens, c.max_seq_len, e->block_table,
+                                e->max_pages, e->n_pool_pages));
+        bool pend = false;
+        const float* pend_scale = nullptr;
+        RET(decode_layers(e, e->ex_tokens, e->ex_ctx, e->ex_table, cn, n_splits, 0, &pend, &pend_scale));
+        const int g0 = chunk_g0[k], g1 = chunk_g0[k + 1];
+        if (g1 == g0) continue;                              // no slot's last token is in this chunk: nothing reads its residual rows
+        // the lm_head's prologue would apply the pending K-quarter sums of the last down_proj; the gather needs the finished rows
+        if (pend) CK(launch_dec_norm_ximg(s, e->d_h, nullptr, nullptr, cn, H, c.rms_norm_eps, e->d_part_h, pend_scale));
+        CK(launch_gather_rows(s, e->d_h, d_gsrc + g0, d_gdst + g0, e->ex_h, g1 - g0, H));
+    }
+    // ---- the slots' state: that of slots prefilled with the longer prompt
+    CK(launch_extend_commit(s, d_slots, d_fed, d_new, n, e->ctx_len, e->out_lens, e->finished, e->d_max_len));
+    for (int i = 0; i < n; ++i) RET(clear_lp_row(e, slots[i]));
+    if (e->stage.rows(ROW_GUIDE) > 0) CK(launch_guide_reset_rows(s, e->d_guides, d_slots, n));
+    if (e->stage.rows(ROW_STOP) > 0) CK(launch_stop_reset_rows(s, e->d_stop, d_slots, n));
+    // ---- the first tokens of the new turn: lm_head over the slots' last fed rows, the selection stage over a mask of the extended slots only
+    CK(launch_dec_lmhead(s, e->ex_h, e->final_norm, e->lm_head_d, e->lm_head_s, e->d_logits, rows, H, V, c.rms_norm_eps, 0, e->d_xn));
+    e->B_sel = rows;
+    e->sel_now = e->d_sel_new;
+    RET(select_tokens(e, 0));
+    CK(hipStreamSynchronize(s));
+    for (int i = 0; i < n; ++i) {
+        const int b = slots[i];
+        e->slot_prompt[b] = new_prompt[i];
+        e->slot_limit[b] = new_prompt[i] + max_new_tokens[i];
+        e->slot_ctx_ub[b] = new_prompt[i];
+        e->slot_done[b] = 0;
+    }
+    e->sel_dirty = true;
+    guard.armed = false;
+    return DOTS_OK;
+}
+
 // Enter slot mode with every slot free and every KV page in the pool (whatever a static batch or an abandoned serving loop left behind).
 int dots_slots_reset(DotsEngine* e) {
     if (!e) return DOTS_E_INVALID;
@@ -375,6 +544,15 @@ int dots_slot_read(DotsEngine* e, int slot, int32_t* out_ids, int capacity, int3
         CK(hipMemcpyAsync(out_ids, e->out_ids + (size_t)slot * e->cfg.max_seq_len, (size_t)take * 4, hipMemcpyDeviceToHost, e->stream));
         CK(hipStreamSynchronize(e->stream));
     }
+    return DOTS_OK;
+}
+
+int dots_slot_logits(DotsEngine* e, int slot, float* out) {
+    if (!e || !out) return e ? e->fail(DOTS_E_INVALID, "null argument") : DOTS_E_INVALID;
+    if (!e->slot_mode || slot < 0 || slot >= e->cfg.max_batch || !e->slot_active[slot]) return e->fail(DOTS_E_STATE, "slot %d is not occupied", slot);
+    CK(hipSetDevice(e->device));
+    CK(hipMemcpyAsync(out, e->d_logits + (size_t)slot * e->cfg.vocab_size, (size_t)e->cfg.vocab_size * 4, hipMemcpyDeviceToHost, e->stream));
+    CK(hipStreamSynchronize(e->stream));
     return DOTS_OK;
 }
 

@@ -333,6 +333,8 @@ def _prototypes(lib):
         "dots_slots_prefill": (i32, [vp, P(i32), i32, P(i32), P(i32), P(i32)]),
         "dots_slots_decode": (i32, [vp, i32]),
         "dots_slots_fork": (i32, [vp, i32, P(i32), i32]),
+        "dots_slot_logits": (i32, [vp, i32, P(C.c_float)]),
+        "dots_slots_extend": (i32, [vp, P(i32), i32, P(i32), P(i32), P(i32), P(i32)]),
         "dots_slots_beam": (i32, [vp, i32, P(i32), i32]),
         "dots_beam_info": (i32, [vp, i32, P(i32), P(i32), P(i32)]),
         "dots_beam_read": (i32, [vp, i32, P(i32), P(i32), P(f32), P(i32), P(i32), i32, P(i32), i32, P(i32)]),
@@ -437,7 +439,7 @@ EXPORTED_SYMBOLS = [
     "dots_set_row_ngram", "dots_op_select_tokens_ngram", "dots_bench_select_tokens_ngram",
     "dots_set_speculation", "dots_set_speculation_rows", "dots_set_row_drafts", "dots_spec_stats", "dots_op_ngram_draft",
     "dots_set_speculation_guided", "dots_op_spec_guide_masks",
-    "dots_slots_fork",
+    "dots_slots_fork", "dots_slots_extend", "dots_slot_logits",
     "dots_slots_beam", "dots_beam_info", "dots_beam_read",
     "dots_stop_create", "dots_stop_destroy", "dots_set_row_stop", "dots_row_stop_hit",
 ]
@@ -1133,6 +1135,22 @@ class Engine:
         assert dst.ndim == 1
         self._ck(self.lib.dots_slots_fork(self.h, int(src), _i32p(dst) if dst.shape[0] else None, dst.shape[0]), "dots_slots_fork")
 
+    def slots_extend(self, slots: Sequence[int], ids_list: Sequence[Sequence[int]], keep_pending=False, max_new_tokens=1):
+        """More prompt tokens behind live sequences: slot slots[i] is fed ids_list[i] (at least one id) behind the KV it
+        holds.  keep_pending (a scalar or one per slot): True keeps the slot's pending token — the last token it selected, whose K/V is
+        not written yet — in the sequence (a next turn behind a generated answer); False drops it (a prefix that was prefilled only to be
+        extended).  Afterwards every slot is what slots_prefill of the longer prompt would have left, with max_new_tokens (a scalar or one
+        per slot) as its cap and its first token selected under everything set on the row.  Read the earlier output first: the call
+        discards it.  A fork of the most recent prefill comes before an extend."""
+        sl = np.ascontiguousarray(slots, dtype=np.int32)
+        assert sl.ndim == 1 and len(ids_list) == sl.shape[0]
+        lens = np.ascontiguousarray([len(x) for x in ids_list], dtype=np.int32)
+        ids = np.ascontiguousarray([t for x in ids_list for t in x] or [0], dtype=np.int32)
+        keep = np.ascontiguousarray(np.broadcast_to(np.asarray(keep_pending, dtype=bool), sl.shape), dtype=np.int32)
+        cap = np.ascontiguousarray(np.broadcast_to(np.asarray(max_new_tokens, dtype=np.int64), sl.shape), dtype=np.int32)
+        self._ck(self.lib.dots_slots_extend(self.h, _i32p(sl) if sl.shape[0] else None, sl.shape[0], _i32p(ids), _i32p(lens), _i32p(keep), _i32p(cap)),
+                 "dots_slots_extend")
+
     def slots_beam(self, src: int, dst_slots: Sequence[int]):
         """Beam search: slot src (just prefilled, no decode step since) and the free slots dst_slots become a group of
         1 + len(dst_slots) beams, in that order, fully reserved over the source's shared prompt pages; the group's first selection replaces
@@ -1183,6 +1201,12 @@ class Engine:
         n = C.c_int32(0)
         self._ck(self.lib.dots_slot_read(self.h, int(slot), _i32p(out), int(capacity), C.byref(n)), "dots_slot_read")
         return out[:min(int(n.value), capacity)].copy()
+
+    def slot_logits(self, slot: int) -> np.ndarray:
+        """fp32 logits [vocab] of an occupied slot's row, as the most recent prefill, extend or plain decode step over it left them"""
+        out = np.empty((self.cfg.vocab_size,), dtype=np.float32)
+        self._ck(self.lib.dots_slot_logits(self.h, int(slot), out.ctypes.data_as(C.POINTER(C.c_float))), "dots_slot_logits")
+        return out
 
     def slot_release(self, slot: int):
         self._ck(self.lib.dots_slot_release(self.h, int(slot)), "dots_slot_release")

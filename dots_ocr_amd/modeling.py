@@ -136,7 +136,7 @@ class DotsOcrHipForCausalLM:
                  guided_whitespace_pattern=None, no_repeat_ngram_size: Optional[int] = None, no_repeat_ngram_window: Optional[int] = None,
                  no_repeat_ngram_whitelist=None, speculative_ngram: Optional[int] = None, prompt_lookup_min: int = 2, prompt_lookup_max: int = 4,
                  num_return_sequences: int = 1, stop_strings=None, speculative_rows=None, num_beams: Optional[int] = None,
-                 length_penalty: float = 1.0, early_stopping=None, speculative_guided: bool = False, **_):
+                 length_penalty: float = 1.0, early_stopping=None, speculative_guided: bool = False, prompt_suffixes=None, **_):
         """HF-shaped generate.  do_sample / temperature / top_p default to the checkpoint's generation_config.json (greedy when it
         is absent); with sampling on, tokens are drawn on the GPU from softmax(logits / temperature) restricted to the top_p
         nucleus, reproducibly from `seed`.  Returns LongTensor
@@ -195,7 +195,14 @@ class DotsOcrHipForCausalLM:
         as above, ranked by cum / max(1, len) ** length_penalty.  These are vLLM's beam-search semantics with HF's length normalisation,
         not HF's BeamSearchScorer: early_stopping is not offered (given, it raises), and the call is refused — nothing is silently
         dropped — together with sampling (a temperature > 0, top_k, penalties), logit rules, a guide, an n-gram rule, stop strings,
-        speculation or continuous=False."""
+        speculation or continuous=False.
+
+        prompt_suffixes ([[ids...], ...], 2 .. 8 lists; one input row only) reads several prompts off one page (Engine.slots_extend,
+        DESIGN §6.11): input_ids is the prefix they share — the image and whatever text comes before the prompts part ways — and
+        sequence j continues prefix + prompt_suffixes[j] from one tower, one prefill of the prefix and one extend.  Returns LongTensor
+        [m, T + new]: row j = the prefix followed by the new tokens of suffix j (the suffix ids are not repeated), drawn with seed + j.
+        It runs on the continuous path and is refused together with num_return_sequences > 1, num_beams, penalties, speculation or
+        continuous=False."""
         import dataclasses
         import torch
         t_eff, p_eff = resolve_sampling(self.generation_config, do_sample, temperature, top_p)
@@ -227,6 +234,19 @@ class DotsOcrHipForCausalLM:
             if not hasattr(self.engine, "slots_beam"):
                 raise ValueError("this engine cannot run a beam group (no slots_beam)")
             beam = (int(num_beams), float(length_penalty))
+            continuous = True
+        suffixes = None
+        if prompt_suffixes is not None:
+            suffixes = [[int(t) for t in x] for x in prompt_suffixes]
+            refused = [name for name, on in (
+                ("more than one input row", input_ids.shape[0] != 1), ("num_return_sequences > 1", nrs > 1), ("num_beams", beam is not None),
+                ("repetition_penalty", repetition_penalty not in (None, 1.0)), ("frequency_penalty", (frequency_penalty or 0.0) != 0.0),
+                ("presence_penalty", (presence_penalty or 0.0) != 0.0), ("speculative_ngram", bool(speculative_ngram)),
+                ("continuous=False", continuous is False)) if on]
+            if refused:
+                raise ValueError(f"prompt_suffixes cannot be combined with {', '.join(refused)}")
+            if not hasattr(self.engine, "slots_extend"):
+                raise ValueError("this engine cannot extend a live sequence (no slots_extend)")
             continuous = True
         row_sp = None
         if (top_k or 0) > 0 or repetition_penalty not in (None, 1.0) or (frequency_penalty or 0.0) != 0.0 or (presence_penalty or 0.0) != 0.0:
@@ -287,6 +307,12 @@ class DotsOcrHipForCausalLM:
 
                 def row_sp(b):
                     return dataclasses.replace(base, seed=int(seed) + b)
+        if suffixes is not None and t_eff > 0 and row_sp is None:      # sampled: suffix j draws with seed + j (the scheduler adds the index)
+            from .engine import SamplingParams
+            base = SamplingParams(temperature=t_eff, top_p=p_eff, seed=seed)
+
+            def row_sp(b):
+                return base
         if nrs > 1 and beam is None:
             continuous = True
             from .engine import SamplingParams
@@ -322,7 +348,7 @@ class DotsOcrHipForCausalLM:
                 self.engine.set_speculation_guided(True)
         try:
             return self._generate(input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens, eos_token_id, pad_token_id, continuous,
-                                  row_sp, rules, guide, ngram, nrs, stop, int(min_tokens or 0), beam)
+                                  row_sp, rules, guide, ngram, nrs, stop, int(min_tokens or 0), beam, suffixes)
         finally:
             if spec_k:
                 try:
@@ -343,8 +369,10 @@ class DotsOcrHipForCausalLM:
                     warnings.warn(f"guide {guide} could not be destroyed: {e}")
 
     def _generate(self, input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens, eos_token_id, pad_token_id, continuous, row_sp, rules,
-                  guide, ngram=None, nrs=1, stop=None, stop_min=0, beam=None):
+                  guide, ngram=None, nrs=1, stop=None, stop_min=0, beam=None, suffixes=None):
         import torch
+        if suffixes:
+            nrs = len(suffixes)                      # the rows of the result: one per suffix, laid out as num_return_sequences lays them out
         ids = input_ids.detach().cpu().numpy()
         B, T = ids.shape
         mask = attention_mask.detach().cpu().numpy().astype(bool) if attention_mask is not None else np.ones_like(ids, bool)
@@ -385,7 +413,7 @@ class DotsOcrHipForCausalLM:
         longest = max(len(p) for p in prompts)
         if longest >= self.max_seq_len:
             raise ValueError(f"prompt of {longest} tokens does not fit max_seq_len={self.max_seq_len}")
-        max_new_tokens = max(1, min(int(max_new_tokens), self.max_seq_len - longest))
+        max_new_tokens = max(1, min(int(max_new_tokens), self.max_seq_len - longest - max((len(x) for x in suffixes or ()), default=0)))
         new_tokens = np.full((B * nrs, max_new_tokens), pad, dtype=np.int64)
         n_max = 0
         seq_patches = [int(sum(patch_off[g + 1] - patch_off[g] for g in img_of_seq[b])) for b in range(B)]
@@ -399,10 +427,11 @@ class DotsOcrHipForCausalLM:
                     lo, hi = int(patch_off[img_of_seq[b][0]]), int(patch_off[img_of_seq[b][-1] + 1])
                     pix = pv_dev[lo:hi] if pv_dev is not None else pv_host[lo:hi]
                     reqs.append(Request(prompts[b], pix, grid[img_of_seq[b][0]:img_of_seq[b][-1] + 1], max_new_tokens,
-                                        sampling=row_sp(b) if row_sp else None, rules=rules, guide=guide, ngram=ngram, n=nrs, stop=stop))
+                                        sampling=row_sp(b) if row_sp else None, rules=rules, guide=guide, ngram=ngram, n=1 if suffixes else nrs,
+                                        stop=stop, suffixes=suffixes))
                 else:
                     reqs.append(Request(prompts[b], None, None, max_new_tokens, sampling=row_sp(b) if row_sp else None, rules=rules, guide=guide,
-                                        ngram=ngram, n=nrs, stop=stop))
+                                        ngram=ngram, n=1 if suffixes else nrs, stop=stop, suffixes=suffixes))
                 if beam is not None:             # a group of beam[0] beams that returns its nrs best hypotheses
                     reqs[-1].n, reqs[-1].num_beams, reqs[-1].num_return, reqs[-1].length_penalty = 1, beam[0], nrs, beam[1]
             outs = ContinuousBatcher(self.engine, eos_ids=eos).run(reqs)

@@ -143,6 +143,9 @@ class DotsOCRParser:
         generated = self.model.generate(**inputs, max_new_tokens=self.hf_max_new_tokens, **kw)
         trimmed = [out[len(inp):] for inp, out in zip(inputs.input_ids, generated)]
         texts = self.processor.batch_decode(trimmed, skip_special_tokens=True, clean_up_tokenization_spaces=False)
+        return self._cut_at_stops(trimmed, texts)
+
+    def _cut_at_stops(self, trimmed, texts) -> List[str]:
         if self.stop:                               # the ids end at the token that completed a match: cut the text where the match starts
             from .stop_strings import first_stop, stopped_text
             tb, pad = self.model.engine.token_bytes.token, self.processor.tokenizer.pad_token_id
@@ -154,6 +157,75 @@ class DotsOCRParser:
                 if hit is not None:
                     texts[i] = stopped_text(toks, hit, tb)
         return texts
+
+    # ------------------------------------------------------------------ several prompts over one page
+    MAX_PROMPTS = 8                                  # prompts of one request (scheduler.ContinuousBatcher.MAX_SUFFIXES)
+
+    def _inference_prompts_with_hf(self, image, prompts) -> List[str]:
+        """one fan-out through model.generate(prompt_suffixes=): the page's tower and the prefill of what the prompts share run once"""
+        import torch
+        from .scheduler import split_common_prefix
+        inputs = self._build_inputs([image], [prompts[0]])
+        ids0 = inputs["input_ids"][0][inputs["attention_mask"][0].bool()].tolist()
+        grids = inputs["image_grid_thw"].tolist()
+        seqs = [ids0]
+        for p in prompts[1:]:
+            messages = [{"role": "user", "content": [{"type": "image", "image": image}, {"type": "text", "text": p}]}]
+            seqs.append(self.processor.encode_prompt(self.processor.apply_chat_template(messages, tokenize=False, add_generation_prompt=True), grids))
+        prefix, suffixes = split_common_prefix(seqs)
+        if any(self.model.config.image_token_id in s for s in suffixes):
+            raise ValueError("the prompts do not share the page: their common prefix does not cover every image token")
+        kw = self._ngram_fields()
+        if self.stop:
+            if getattr(self.model.engine, "token_bytes", None) is None:
+                self.model.engine.set_token_bytes(self.processor.guide_token_bytes())
+            kw["stop_strings"] = self.stop
+        dev = inputs["input_ids"].device
+        generated = self.model.generate(input_ids=torch.tensor([prefix], dtype=torch.long, device=dev), pixel_values=inputs["pixel_values"],
+                                        image_grid_thw=inputs["image_grid_thw"], max_new_tokens=self.hf_max_new_tokens,
+                                        prompt_suffixes=suffixes, **kw)
+        trimmed = [out[len(prefix):] for out in generated]
+        texts = self.processor.batch_decode(trimmed, skip_special_tokens=True, clean_up_tokenization_spaces=False)
+        return self._cut_at_stops(trimmed, texts)
+
+    def _inference_prompts_with_vllm(self, image, prompts) -> List[str]:
+        """one request that carries the server's `prompts` field: choice i answers prompts[i]"""
+        from dots_ocr.model.inference import inference_prompts_with_vllm
+        extra = {**self._ngram_fields(), **({"stop": self.stop} if self.stop else {})}
+        return inference_prompts_with_vllm(image, prompts, model_name=self.model_name, protocol=self.protocol, ip=self.ip, port=self.port,
+                                           temperature=self.temperature, top_p=self.top_p, max_completion_tokens=self.max_completion_tokens,
+                                           **({"extra_body": extra} if extra else {}))
+
+    def parse_image_regions(self, input_path, bboxes, save_dir=None, filename=None, fitz_preprocess=False):
+        """Grounding OCR of many boxes of ONE image: the page is read once — one `prompts` request on the server path, one fan-out through
+        model.generate(prompt_suffixes=) on the in-process path (groups of MAX_PROMPTS boxes) — instead of one tower and one prefill per
+        box.  Returns one result per box, in order: what parse_image(..., prompt_mode="prompt_grounding_ocr", bbox=b) returns for it,
+        saved as <filename>_box_<i>."""
+        mode = "prompt_grounding_ocr"
+        if self.num_beams or self.speculative_ngram:
+            raise ValueError("parse_image_regions cannot be combined with num_beams or speculative_ngram")
+        bboxes = [list(b) for b in bboxes]
+        if not bboxes:
+            return []
+        origin_image = fetch_image(input_path)
+        save_dir = save_dir or self.output_dir
+        filename = filename or os.path.splitext(os.path.basename(str(input_path)))[0]
+        os.makedirs(save_dir, exist_ok=True)
+        image, first, mn, mx = self._prepare(origin_image, mode, "image", bboxes[0], fitz_preprocess)
+        prompts = [first] + [self.get_prompt(mode, b, origin_image, image, min_pixels=mn, max_pixels=mx) for b in bboxes[1:]]
+        responses = []
+        for lo in range(0, len(prompts), self.MAX_PROMPTS):
+            group = prompts[lo:lo + self.MAX_PROMPTS]
+            if len(group) == 1:                     # a lone box is an ordinary request
+                responses.append(self._inference_with_hf(image, group[0]) if self.use_hf else self._inference_with_vllm(image, group[0]))
+            else:
+                responses += self._inference_prompts_with_hf(image, group) if self.use_hf else self._inference_prompts_with_vllm(image, group)
+        results = []
+        for i, response in enumerate(responses):
+            result = self._save(response, origin_image, image, mode, save_dir, f"{filename}_box_{i}", 0, mn, mx)
+            result["file_path"] = input_path
+            results.append(result)
+        return results
 
     def _inference_with_hf(self, image, prompt) -> str:
         return self._inference_batch_with_hf([image], [prompt])[0]

@@ -294,16 +294,7 @@ class DotsOcrProcessor:
                 feats.append(pv)
                 grids.append(thw)
         it = iter(grids)
-        all_ids = []
-        for t in text:
-            pieces = t.split(IMG_PAD)
-            expanded = pieces[0]
-            for piece in pieces[1:]:
-                thw = next(it, None)
-                if thw is None:
-                    raise ValueError("more image placeholders than images")
-                expanded += IMG_PAD * (thw[0] * thw[1] * thw[2] // v.spatial_merge_size ** 2) + piece
-            all_ids.append(self.tokenizer.encode(expanded))
+        all_ids = [self.encode_prompt(t, it) for t in text]
         if next(it, None) is not None:
             raise ValueError("more images than image placeholders")
         L = max(len(x) for x in all_ids)
@@ -321,6 +312,21 @@ class DotsOcrProcessor:
             data["pixel_values"] = torch.from_numpy(np.concatenate(feats, axis=0))
             data["image_grid_thw"] = torch.tensor(grids, dtype=torch.int64)
         return BatchFeature(data)
+
+    def encode_prompt(self, text: str, grids) -> List[int]:
+        """Token ids of one chat-template text whose images are already preprocessed: every image placeholder takes the next (t, h, w) of
+        `grids` (a list or an iterator) and becomes that image's merged rows.  What __call__ produces for the text; several prompts over
+        one page (the server's `prompts`) encode each of them against the one grid without preprocessing the page again."""
+        it = grids if hasattr(grids, "__next__") else iter(grids)
+        m2 = self.cfg.vision.spatial_merge_size ** 2
+        pieces = text.split(IMG_PAD)
+        expanded = pieces[0]
+        for piece in pieces[1:]:
+            thw = next(it, None)
+            if thw is None:
+                raise ValueError("more image placeholders than images")
+            expanded += IMG_PAD * (int(thw[0]) * int(thw[1]) * int(thw[2]) // m2) + piece
+        return self.tokenizer.encode(expanded)
 
     # parser.py:114-116
     def batch_decode(self, sequences, skip_special_tokens: bool = True, clean_up_tokenization_spaces: bool = False):

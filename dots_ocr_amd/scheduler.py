@@ -18,6 +18,19 @@ from typing import Deque, Dict, Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 
 
+def split_common_prefix(seqs: Sequence[Sequence[int]]) -> Tuple[List[int], List[List[int]]]:
+    """(prefix, suffixes) of several token sequences: their longest common prefix, cut back so that every suffix keeps at least one
+    token (a sequence that is a prefix of another still has something to feed: Request.suffixes)."""
+    seqs = [[int(t) for t in s] for s in seqs]
+    if not seqs or any(not s for s in seqs):
+        raise ValueError("every sequence needs at least one token")
+    k, shortest = 0, min(len(s) for s in seqs)
+    while k < shortest and all(s[k] == seqs[0][k] for s in seqs):
+        k += 1
+    k = min(k, shortest - 1)
+    return seqs[0][:k], [s[k:] for s in seqs]
+
+
 class RequestRejected(ValueError):
     """The engine refused a request's own per-row parameters (sampling, logprobs, logit rules) at admission."""
 
@@ -49,11 +62,21 @@ class Request:
                                                 # cumulative_logprobs, beam_scores and finish_reasons ("stop" | "length") in that order
     num_return: int = 1                         # hypotheses returned, 1 .. num_beams
     length_penalty: float = 1.0                 # score = cum / max(1, len) ** length_penalty, len without a final EOS
+    suffixes: Optional[Sequence[Sequence[int]]] = None   # several prompts over one page: 2 .. 8 token lists; input_ids is then the
+                                                # prefix they share (image tokens and pixel values as always) and sequence i reads prefix +
+                                                # suffixes[i] — one tower, one prefill of the prefix, one fork, one Engine.slots_extend.  Sequence i
+                                                # runs under `sampling` with seed + i; the finished request carries outputs, logprobs_out, stop_hit
+                                                # and kv_truncated_each in suffix order, exactly like n > 1
+
+    @property
+    def seqs(self) -> int:
+        """independent sequences of the request: one per suffix, else n"""
+        return len(self.suffixes) if self.suffixes else int(self.n)
 
     @property
     def width(self) -> int:
-        """slots the request takes: its beams, or its n sequences"""
-        return int(self.num_beams) if self.num_beams else int(self.n)
+        """slots the request takes: its beams, or its sequences"""
+        return int(self.num_beams) if self.num_beams else self.seqs
 
     def n_patches(self) -> int:
         if self.grid_thw is None:
@@ -157,6 +180,8 @@ class ContinuousBatcher:
             raise ValueError(f"n must be an integer >= 1, got {req.n!r}")
         if req.n > self.n_slots:
             raise ValueError(f"n = {req.n} sequences need more than the {self.n_slots} usable slots")
+        if req.suffixes is not None:
+            self._check_suffixes(req, ids.shape[0])
         if req.num_beams is not None:
             self._check_beam(req)
         if req.n > 1 and not hasattr(self.engine, "slots_fork"):
@@ -186,7 +211,8 @@ class ContinuousBatcher:
                 raise RequestRejected(str(e))
         req.input_ids = ids
         # like HF generate, stop at the context capacity instead of failing
-        req.max_new_tokens = max(1, min(int(req.max_new_tokens), self.max_seq_len - ids.shape[0]))
+        longest = max((len(x) for x in req.suffixes), default=0) if req.suffixes else 0
+        req.max_new_tokens = max(1, min(int(req.max_new_tokens), self.max_seq_len - ids.shape[0] - longest))
         if hasattr(self.engine, "kv_pool_info") and self._group_pages(req) > self.engine.kv_pool_info()[0]:
             raise ValueError(f"prompt of {ids.shape[0]} tokens needs {self._group_pages(req)} KV pages, "
                              f"the pool holds {self.engine.kv_pool_info()[0]}")
@@ -201,6 +227,41 @@ class ContinuousBatcher:
         self._next_id += 1
         self.pending.append((rid, req))
         return rid
+
+    MAX_SUFFIXES = 8
+
+    def _check_suffixes(self, req: Request, prefix: int):
+        """a request with several prompts is refused whole rather than run with anything dropped"""
+        m = len(req.suffixes)
+        if not 2 <= m <= self.MAX_SUFFIXES:
+            raise RequestRejected(f"suffixes must hold 2 .. {self.MAX_SUFFIXES} token lists, got {m}")
+        if req.n != 1:
+            raise RequestRejected("suffixes cannot be combined with n > 1: every suffix is one sequence")
+        if req.num_beams is not None:
+            raise RequestRejected("suffixes cannot be combined with num_beams")
+        if not all(hasattr(self.engine, f) for f in ("slots_fork", "slots_extend")):
+            raise RequestRejected("suffixes need continuous batching on an engine that extends a live sequence (Engine.slots_extend): "
+                                  "not with static batching")
+        if getattr(self.engine, "spec_k", 0):
+            raise RequestRejected("suffixes cannot run while the engine speculates")
+        sp = req.sampling
+        if sp is not None and (float(getattr(sp, "repetition_penalty", 1.0)) != 1.0 or float(getattr(sp, "frequency_penalty", 0.0)) != 0.0
+                               or float(getattr(sp, "presence_penalty", 0.0)) != 0.0):
+            raise RequestRejected("suffixes cannot be combined with a penalty: an extended row's prompt-presence image would be wrong")
+        if m > self.n_slots:
+            raise ValueError(f"{m} suffixes need more than the {self.n_slots} usable slots")
+        vocab = getattr(getattr(self.engine, "cfg", None), "vocab_size", None)
+        clean = []
+        for i, x in enumerate(req.suffixes):
+            x = [int(t) for t in x]
+            if not x:
+                raise RequestRejected(f"suffix {i} is empty: every suffix keeps at least one token")
+            if vocab is not None and not all(0 <= t < vocab for t in x):
+                raise RequestRejected(f"suffix {i} holds a token id outside [0, {vocab})")
+            if prefix + len(x) >= self.max_seq_len:
+                raise ValueError(f"prefix + suffix {i} = {prefix} + {len(x)} tokens do not fit max_seq_len={self.max_seq_len}")
+            clean.append(x)
+        req.suffixes = clean
 
     def _check_beam(self, req: Request):
         """a beam request is refused whole rather than run with anything dropped"""
@@ -251,6 +312,8 @@ class ContinuousBatcher:
         t = int(r.input_ids.shape[0])
         if r.num_beams:
             return self._beam_pages(r)
+        if r.suffixes:                               # after the extend: every sequence holds its own longer prompt + ADMIT_AHEAD
+            return sum(self._admit_pages(t + len(x), r.max_new_tokens) for x in r.suffixes) - (len(r.suffixes) - 1) * (t // 64)
         need = self._admit_pages(t, r.max_new_tokens)
         return need + (int(r.n) - 1) * (need - t // 64)
 
@@ -266,7 +329,10 @@ class ContinuousBatcher:
         (what is still running: a conservative count, as if sequence 0 were among them)"""
         if r.num_beams:
             return self._beam_pages(r)               # the whole group holds its pages until it is released together
-        t, n = int(r.input_ids.shape[0]), int(r.n) if n is None else n
+        t, n = int(r.input_ids.shape[0]), r.seqs if n is None else n
+        if r.suffixes:                               # the n longest of its sequences: conservative for whatever is still running
+            each = sorted(((min(t + len(x) + int(r.max_new_tokens), self.max_seq_len) + 63) // 64 for x in r.suffixes), reverse=True)[:n]
+            return sum(each) - (len(each) - 1) * (t // 64)
         worst = (min(t + int(r.max_new_tokens), self.max_seq_len) + 63) // 64
         return worst + (n - 1) * (worst - t // 64)
 
@@ -414,6 +480,9 @@ class ContinuousBatcher:
                     else:
                         self.engine.slots_fork(s, kids[rid])
                         forked += kids[rid]
+            for s, rid, r in group:                  # after every fork (an extend ends the prefill's fork window): one extend per request with suffixes
+                if r.suffixes:
+                    self.engine.slots_extend([s] + kids[rid], r.suffixes, keep_pending=False, max_new_tokens=int(r.max_new_tokens))
         except Exception:
             for s in slots + forked:                 # the prefill went in: give its slots back, the caller re-queues the group
                 self.engine.slot_release(s)
@@ -426,9 +495,9 @@ class ContinuousBatcher:
                 self._admit_seq[k] = self._admit_count
                 self._last_lens[k] = 0               # a reused slot must not inherit its previous occupant's length (_soon_free counted a
                                                      # just-admitted long request as "about to finish" and the look-ahead group was sized for slots that stayed busy)
-                if r.n > 1:
+                if r.seqs > 1:
                     self._seq_index[k] = j
-            if r.n > 1:
+            if r.seqs > 1:
                 r._parts = {}
         self.admissions += 1
 
@@ -568,7 +637,7 @@ class ContinuousBatcher:
                 hit = None
                 if req.stop is not None:             # read before the release clears the row's automaton and its hit record
                     hit = self.engine.row_stop_hit(s)
-                if req.n == 1:
+                if req.seqs == 1:
                     if req.stop is not None:
                         req.stop_hit = hit
                     if req.logprobs is not None:
@@ -577,8 +646,8 @@ class ContinuousBatcher:
                 else:
                     # one sequence of n: its slot goes back now, the request is reported once, when its last sequence has finished
                     req._parts[self._seq_index.pop(s)] = (toks, lp_out, req.kv_truncated, hit)
-                    if len(req._parts) == req.n:
-                        parts = [req._parts[j] for j in range(req.n)]
+                    if len(req._parts) == req.seqs:
+                        parts = [req._parts[j] for j in range(req.seqs)]
                         req.outputs = [t for t, _, _, _ in parts]
                         if req.logprobs is not None:
                             req.logprobs_out = [l for _, l, _, _ in parts]

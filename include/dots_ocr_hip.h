@@ -467,6 +467,28 @@ int dots_slots_fork(DotsEngine* e, int src_slot, const int32_t* dst_slots_host, 
 int dots_set_eos(DotsEngine* e, const int32_t* eos_ids_host, int n_eos);
 int dots_slots_prefill(DotsEngine* e, const int32_t* slots_host, int n, const int32_t* input_ids_host,
                        const int32_t* prompt_lens_host, const int32_t* max_new_tokens_host);
+/* ---- Extend a live sequence: more prompt tokens behind the KV cache a slot already holds — several prompts over one
+ * prefilled page, or a next turn behind a generated answer — without a second tower or prefill.
+ *
+ * dots_slots_extend  every listed slot holds the K/V of some context c and one pending token (selected, its K/V not yet written).  ids_host
+ *                    packs lens_host[i] >= 1 tokens per slot.  keep_pending_host[i] = 1: the pending token stays in the sequence and the row
+ *                    is fed [pending, ids...] (a next turn: the pending token is the answer's last token, normally its EOS);
+ *                    0: the pending token is dropped and the row is fed [ids...] (a prefix that was prefilled only to be extended).
+ *                    Afterwards the slot is what a dots_slots_prefill of the longer prompt would have left: prompt = c + tokens fed,
+ *                    limit = prompt + max_new_tokens_host[i], no output, running, logprob positions cleared, guide and stop automata at
+ *                    their start with no hit, the n-gram history and the sampler's counter from zero, and its first token selected from the
+ *                    logits of its last fed token under everything set on the row (set, then extend, as with dots_slots_prefill).  The fed
+ *                    rows run through the decode kernels at their positions, in chunks of at most max_batch rows: the state is, bit for
+ *                    bit, that of feeding the same tokens one decode step at a time.  READ THE EARLIER OUTPUT FIRST (dots_slot_read,
+ *                    dots_row_logprobs, dots_row_stop_hit): the call discards it.  A fork comes before an extend: the call ends the window
+ *                    in which the most recent dots_slots_prefill can be forked.  Pages: every slot is grown to
+ *                    ceil(min(prompt + min(max_new, 64), max_seq_len) / 64) pages.
+ *                    Refused with nothing changed: a slot out of range or listed twice, lens < 1, max_new < 1, an id out of range or an image
+ *                    token (DOTS_E_INVALID); a free or suspended slot, a row of a beam group, a row that carries a penalty, a speculating
+ *                    engine, a static batch (DOTS_E_STATE); prompt + max_new_tokens above max_seq_len, or a pool that cannot serve the
+ *                    pages (DOTS_E_CAPACITY).  Synchronises. */
+int dots_slots_extend(DotsEngine* e, const int32_t* slots_host, int n, const int32_t* ids_host, const int32_t* lens_host,
+                      const int32_t* keep_pending_host, const int32_t* max_new_tokens_host);
 int dots_slots_decode(DotsEngine* e, int n_steps);
 int dots_slots_poll(DotsEngine* e, int32_t* finished_host, int32_t* out_lens_host);
 int dots_slot_read(DotsEngine* e, int slot, int32_t* out_ids_host, int capacity, int32_t* n_out);
@@ -542,6 +564,9 @@ int dots_slots_pages_short(DotsEngine* e, int n_steps, int32_t* pages);
 
 /* fp32 logits [B, vocab] of the most recent prefill/decode step (tolerance checks). */
 int dots_get_logits(DotsEngine* e, float* out_host);
+/* fp32 logits [vocab] of an occupied slot's row as the most recent dots_slots_prefill, dots_slots_extend or decode step that ran over the
+ * row left them (tolerance checks in slot mode; a plain step only: a speculating step lays its rows out differently).  Synchronises. */
+int dots_slot_logits(DotsEngine* e, int slot, float* out_host);
 /* Teacher forcing for per-step logit comparisons: overwrite the token the next decode step feeds. */
 int dots_set_next_tokens(DotsEngine* e, const int32_t* tokens_host, int B);
 /* Tokens chosen by the most recent prefill/decode step, int32 [B]. */
