@@ -706,19 +706,8 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_step_kernel(const float
 // SEL_THREADS .. SEL_NONE, row_has_pen, the key / weight helpers, the LDS record and the bodies of steps 1-2 and 3 live in select_dev.h: the
 // draft rows of a speculating step (spec.hip) select through the same code.
 
-// HF / vLLM repetition penalty on every token seen in the prompt or the output, then OpenAI frequency / presence on the output counts
-DEVI float penalise(float l, int c, bool seen_prompt, const RowParams& p) {
-    if ((seen_prompt || c > 0) && p.repetition_penalty != 1.0f) l = l > 0.f ? l / p.repetition_penalty : l * p.repetition_penalty;
-    if (c > 0) l = l - (p.frequency_penalty * (float)c + p.presence_penalty);
-    return l;
-}
-
-// does row b carry logit rules in this launch (uniform per workgroup)
-DEVI bool row_ruled(const RowSel& rs, int b) { return rs.rules && (rs.rules[b].flags & RULE_ON); }
-// does row b hold a guide in this launch (uniform per workgroup)
-DEVI bool row_guided(const RowSel& rs, int b) { return rs.guide.rows && rs.guide.rows[b].table; }
-// does row b carry an n-gram rule in this launch (uniform per workgroup)
-DEVI bool row_ngram(const RowSel& rs, int b) { return rs.ngram.rows && rs.ngram.rows[b].n > 0; }
+// penalise, shape_logit (the per-element sequence of a shaped row), the row_ruled / row_guided / row_ngram tests and commit_row live in
+// select_dev.h too: the draft rows of a speculating step are shaped and committed through the same code.
 
 __global__ __launch_bounds__(256) void select_partial_kernel(const float* __restrict__ logits, int V, int ld, RowSel rs, StepState st,
                                                              float* __restrict__ pval, int32_t* __restrict__ pidx) {
@@ -771,24 +760,18 @@ __global__ __launch_bounds__(256) void select_partial_kernel(const float* __rest
         const uint32_t* seen = pen_on ? rs.seen + (size_t)b * W : nullptr;
         float* shaped = rs.pen + (size_t)b * V;
         const bool sampled = p.temperature > 0.f;                    // a greedy row needs the arg max only
+        const RowShape sh{img, gbits, nbits, cnt, seen, s_kill, n_kill, kill, nullptr, 0};
         for (int i = lo + threadIdx.x; i < hi; i += 256) {
-            float l = row[i];
-            if (img) l += img[i];
-            bool term = false;                                       // an EOS / stop id: the guide's bit does not speak for it
-            for (int k = 0; k < n_kill; ++k) term = term || s_kill[k] == i;
-            if (term ? kill : (gbits && !((gbits[i >> 5] >> (i & 31)) & 1u))) l = -INFINITY;
-            if (nbits && ((nbits[i >> 5] >> (i & 31)) & 1u)) l = -INFINITY;
-            if (pen_on) l = penalise(l, cnt[i], (seen[i >> 5] >> (i & 31)) & 1u, p);
+            const float l = shape_logit(row[i], i, sh, p);
             if (sampled) shaped[i] = l;
             argmax_merge(best, bi, l, i);
         }
     } else if (own && rs.cnt && row_has_pen(p)) {
         const int W = (V + 31) >> 5;
-        const int32_t* cnt = rs.cnt + (size_t)b * V;
-        const uint32_t* seen = rs.seen + (size_t)b * W;
         float* pen = rs.pen + (size_t)b * V;
+        const RowShape sh{nullptr, nullptr, nullptr, rs.cnt + (size_t)b * V, rs.seen + (size_t)b * W, nullptr, 0, false, nullptr, 0};
         for (int i = lo + threadIdx.x; i < hi; i += 256) {
-            const float l = penalise(row[i], cnt[i], (seen[i >> 5] >> (i & 31)) & 1u, p);
+            const float l = shape_logit(row[i], i, sh, p);
             pen[i] = l;
             argmax_merge(best, bi, l, i);
         }
@@ -804,11 +787,6 @@ __global__ __launch_bounds__(256) void select_partial_kernel(const float* __rest
         pval[b * ARGMAX_CHUNKS + c] = best;
         pidx[b * ARGMAX_CHUNKS + c] = bi;
     }
-}
-
-DEVI void commit_row(const StepState& st, const RowSel& rs, int b, int V, bool pen, int tok) {
-    if (pen && !st.finished[b] && tok >= 0 && tok < V) rs.cnt[(size_t)b * V + tok] += 1;     // output counts of the rows with penalties
-    commit_token(st, b, tok, row_ruled(rs, b) ? rs.rules + b : nullptr, rs.guide.rows ? &rs.guide : nullptr, rs.stop.rows ? &rs.stop : nullptr);
 }
 
 // steps 1-2 of a sampled row: rs.thr[b] = the largest key it keeps (the arithmetic: select_dev.h sel_threshold)

@@ -211,6 +211,10 @@ struct DotsEngine {
     // allocated by the first call that switches it on — the states of the draft rows of guided slots (kernels.h SpecState::gstate)
     int spec_guided = 0;
     int32_t* sp_gstate = nullptr;
+    // which shaped rows may verify drafts (dots_set_speculation_shaped: DOTS_SPEC_SHAPED_* bits; spec_row_class() ORs them into the mode
+    // three bits up): rows with an n-gram rule, with logit rules, with a penalty in their parameters.  No state of its own: the draft rows
+    // use rows [rows, rows * (k + 1)) of ngram_mask and pen_logits, which hold max_batch rows
+    int spec_shaped = 0;
     bool row_pen[DOTS_MAX_BATCH] = {false}, row_sampled[DOTS_MAX_BATCH] = {false};
     // of a staged row without ROW_PARAMS: the engine-wide setting its stage entry was written from had a temperature > 0.  Such a row is
     // drawn by the stage whatever dots_set_sampling says later, and its draft rows would be arg maxima: it verifies no draft
@@ -282,11 +286,12 @@ struct DotsEngine {
     // table), whether any row holds a guide (guided: the mask kernel and the guides' tables), whether any row carries an n-gram rule (ngram:
     // the ban kernel and its bits), the draft count of a speculating step (spec: 0 = the plain step), whether that step draws the draft
     // rows of sampled slots (draw: the two launches of launch_spec_draw), whether some guided row may speculate in it (gspec: the three
-    // launches that select the draft rows of guided slots under their guide); engine-wide sampling changes drop
+    // launches that select the draft rows of guided slots under their guide), which shaped rows may (sspec: the
+    // DOTS_SPEC_SHAPED_* bits that are switched on and held by some row — the draft rows' ban kernel and their shaped selection); engine-wide sampling changes drop
     // the cache (dots_set_sampling), per-row ones live in device memory; beam: the group entries a step's beam kernels run over (0: none).  step_key() builds the key from the engine's state: a feature that
     // changes what a step launches adds a member here and a line there
     struct StepKey {
-        int rows, splits, out_cap, n_eos, part, rowp, lp, rules, guided, ngram, spec, draw, gspec, beam;
+        int rows, splits, out_cap, n_eos, part, rowp, lp, rules, guided, ngram, spec, draw, gspec, sspec, beam;
         bool operator==(const StepKey& o) const { return std::memcmp(this, &o, sizeof(StepKey)) == 0; }
     };
     static_assert(std::has_unique_object_representations_v<StepKey>, "StepKey is compared bytewise: plain ints, no padding");
@@ -382,6 +387,8 @@ int admit_tokens(const DotsEngine* e, int prompt, int max_new);
 StepState step_state(const DotsEngine* e, int advance, const int32_t* sel);
 bool spec_draws(const DotsEngine* e);
 bool spec_guides(const DotsEngine* e);
+int spec_shapes(const DotsEngine* e);
+RowSel spec_row_sel(const DotsEngine* e);
 GuideSel guide_sel(const DotsEngine* e);
 SpecState spec_state(const DotsEngine* e);
 hipError_t launch_row_stage(hipStream_t s, const float* logits, int V, int ld, int B, const RowSel& rs, float* am_val, int32_t* am_idx,

@@ -280,6 +280,7 @@ DotsEngine::StepKey step_key(const DotsEngine* e, int rows, int n_splits, int ou
     k.spec = e->slot_mode ? e->spec_k : 0;
     k.draw = spec_draws(e);
     k.gspec = spec_guides(e);
+    k.sspec = spec_shapes(e);
     k.beam = e->slot_mode ? e->n_beam_hi : 0;
     return k;
 }
@@ -572,19 +573,25 @@ int decode_step_launches(DotsEngine* e, int n_splits, int part) {
     CK(launch_dec_lmhead(s, e->d_h, e->final_norm, e->lm_head_d, e->lm_head_s, e->d_logits, B, H, c.vocab_size, c.rms_norm_eps, part ? e->dec_cus : 0, e->d_xn,
                          pend ? e->d_part_h : nullptr, pend_scale));
     if (spec_k) CK(launch_spec_argmax(s, sp, e->d_logits, c.vocab_size, c.vocab_size, rows, e->am_val, e->am_idx));
-    // the candidates of the draft rows of sampled slots, before the selection stage moves out_lens: draft row j draws with counter out_lens + j
-    // guided slots that speculate (dots_set_speculation_guided): the state each live draft row is selected under, from the slot's state
-    // before anything commits; its allowed bits into the rows of guide_mask the stage does not use; its shaped partials (and values)
-    const GuideSel spec_guide = sp.gstate ? guide_sel(e) : GuideSel{};
-    if (spec_k && sp.gstate) {
-        if (B > c.max_batch) return e->fail(DOTS_E_CAPACITY, "%d rows x %d exceed max_batch %d", rows, spec_k + 1, c.max_batch);      // guide_mask / pen_logits hold max_batch rows
-        CK(launch_spec_guide_chain(s, sp, spec_guide, e->eos_ids, e->n_eos, rows));
-        CK(launch_guide_mask_drafts(s, spec_guide, rows, spec_k, sp.gstate));
-        CK(launch_spec_guide_select(s, sp, spec_guide, e->eos_ids, e->n_eos, e->d_logits, c.vocab_size, c.vocab_size, rows, e->pen_logits, e->am_val, e->am_idx));
+    // Slots whose selection is shaped and that speculate (dots_set_speculation_guided, dots_set_speculation_shaped), from the slots' state
+    // before anything commits.  Guided: the state each live draft row is selected under and its allowed bits, into the rows of guide_mask
+    // the stage does not use.  N-gram: the draft rows' banned bits, into the rows of ngram_mask the stage does not use.  Then the shaped
+    // partials (and values) of every such draft row.  With both switches off (or no row holding such a feature) nothing is launched here
+    const int sspec = spec_k ? spec_shapes(e) : 0;
+    const RowSel spec_rs = spec_k ? spec_row_sel(e) : RowSel{};
+    if (spec_k && (sp.gstate || sspec)) {
+        if (B > c.max_batch) return e->fail(DOTS_E_CAPACITY, "%d rows x %d exceed max_batch %d", rows, spec_k + 1, c.max_batch);      // guide_mask / ngram_mask / pen_logits hold max_batch rows
+        if (sp.gstate) {
+            CK(launch_spec_guide_chain(s, sp, spec_rs.guide, e->eos_ids, e->n_eos, rows, spec_rs.rules));
+            CK(launch_guide_mask_drafts(s, spec_rs.guide, rows, spec_k, sp.gstate));
+        }
+        if (spec_rs.ngram.rows)
+            CK(launch_ngram_ban_drafts(s, spec_rs.ngram, rows, spec_k, e->out_ids, e->out_lens, c.max_seq_len, e->sp_drafts, e->sp_nlive));
+        CK(launch_spec_shape_select(s, sp, spec_rs, step_state(e, 1, e->d_sel), e->d_logits, c.vocab_size, c.vocab_size, rows, e->am_val, e->am_idx));
     }
+    // the candidates of the draft rows of sampled slots, before the selection stage moves out_lens: draft row j draws with counter out_lens + j
     if (spec_k && sp.cand)
-        CK(launch_spec_draw(s, sp, e->d_logits, c.vocab_size, c.vocab_size, rows, e->d_rowp, e->d_row_thr, e->out_lens, e->am_val, e->am_idx,
-                            sp.gstate ? e->pen_logits : nullptr));
+        CK(launch_spec_draw(s, sp, e->d_logits, c.vocab_size, c.vocab_size, rows, spec_rs, e->out_lens, e->am_val, e->am_idx));
     e->B_sel = rows;
     e->sel_now = e->d_sel;
     RET(select_tokens(e, 1));
@@ -593,8 +600,7 @@ int decode_step_launches(DotsEngine* e, int n_splits, int part) {
         // the selection stage committed row 0 of every slot; the accept walk commits what the drafts got right, then the drafter reads
         // the grown output
         const StepState st = step_state(e, 1, e->d_sel);
-        CK(launch_spec_accept(s, sp, st, rows, e->am_val, e->am_idx,
-                              e->d_stop ? StopSel{e->d_stop, e->tok_off, e->tok_bytes, c.vocab_size, 0} : StopSel{}, spec_guide));
+        CK(launch_spec_accept(s, sp, st, rows, c.vocab_size, e->am_val, e->am_idx, spec_rs));
         if (e->spec_max_n > 0)
             CK(launch_ngram_draft(s, st.out_ids, st.out_lens, st.out_stride, st.finished, st.sel, sp.cls, sp.engine_greedy, rows, spec_k, e->spec_min_n,
                                   e->spec_max_n, e->sp_drafts, DOTS_MAX_SPEC_DRAFTS, e->sp_ndraft));

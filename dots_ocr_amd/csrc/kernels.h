@@ -244,6 +244,12 @@ hipError_t launch_guide_set_states(hipStream_t s, RowGuide* table, const int32_t
 // skipped and keep the bits of their last step.  Runs before launch_select_rows.
 hipError_t launch_ngram_ban(hipStream_t s, const NgramSel& g, int B, const int32_t* out_ids, const int32_t* out_lens, int out_stride,
                             const int32_t* finished, const int32_t* sel);
+// The banned bits of the live draft rows of a speculating step: row r = j * rows + b of g.mask, r in [rows, rows * (k + 1)),
+// for every slot b that carries a rule and every j <= n_live[b], from the history out_ids[b][0 .. out_lens[b]) followed by drafts[b][0 .. j)
+// (drafts [DOTS_MAX_BATCH][DOTS_MAX_SPEC_DRAFTS], n_live as SpecState) by the rule of launch_ngram_ban; every other draft row is left
+// alone.  After launch_spec_expand (n_live) and before anything commits; g.mask must hold rows * (k + 1) rows.
+hipError_t launch_ngram_ban_drafts(hipStream_t s, const NgramSel& g, int rows, int k, const int32_t* out_ids, const int32_t* out_lens, int out_stride,
+                                   const int32_t* drafts, const int32_t* n_live);
 // table[row] = r, in stream order
 hipError_t launch_set_row_ngram(hipStream_t s, RowNgram* table, int row, const RowNgram& r);
 // out_ids[b * out_stride + j] = hist[b * stride + n_prompt[b] + j] for j < hist_lens[b] - n_prompt[b], the count launch_pen_history leaves
@@ -293,31 +299,39 @@ struct SpecState {
 hipError_t launch_spec_expand(hipStream_t s, const SpecState& sp, const StepState& st, const int32_t* block_table, int max_pages, int rows, int scratch_page);
 // arg-max partials (as launch_argmax_step's first kernel) of the live draft rows [rows, rows * (k + 1)) of logits
 hipError_t launch_spec_argmax(hipStream_t s, const SpecState& sp, const float* logits, int V, int ld, int rows, float* pval, int32_t* pidx);
+// The RowSel of the draft rows (`rs` below): the stage's tables as the draft-row kernels may use them.  params / own / thr / pen as in the
+// stage (thr and pen: the stage uses rows [0, rows), the draft rows [rows, rows * (k + 1))); guide = the launch's guides while sp.gstate
+// is set, else GuideSel{}; rules (+ rule_img), ngram and cnt (+ seen) only while dots_set_speculation_shaped opens the feature and some row
+// holds it, else null; stop as in the stage.  A slot that carries a feature whose table is null here is SPEC_ROW_NONE.
+//
 // The candidates of the live draft rows of SPEC_ROW_DRAW slots, after launch_spec_argmax and BEFORE the selection stage commits anything:
-// draft row r = j * rows + b is selected with params[b] over logits row r with counter out_lens[b] + j, by the selection stage's own
-// arithmetic (select_dev.h), into sp.cand[b][j - 1].  thr [DOTS_MAX_BATCH] is RowSel::thr: the stage uses entries [0, rows), the draft rows
-// entries [rows, rows * (k + 1)).  Two launches of rows * k workgroups; every other draft row's workgroup exits at once.
-// shaped (with sp.gstate; else nullptr): [rows * (k + 1)][V], a draft row with sp.gstate[r] >= 0 reads its row of it instead of the logits
-// (launch_spec_guide_select left the values and the partials of their maximum there).
-hipError_t launch_spec_draw(hipStream_t s, const SpecState& sp, const float* logits, int V, int ld, int rows, const RowParams* params, uint32_t* thr,
-                            const int32_t* out_lens, const float* pval, const int32_t* pidx, const float* shaped = nullptr);
-// Guided slots of a speculating step (sp.gstate != nullptr), after the lm_head and before anything is selected:
-// chain: sp.gstate[j * rows + b], j = 1 .. k, = the state of slot b (guide.rows[b].state, which nothing has moved yet) walked over the bytes
-//   of drafts 1 .. j, for j <= n_live[b]; -1 from the first draft on that has no bytes, is one of eos_ids or meets GUIDE_DEAD, for j > n_live[b]
-//   and for a slot without a guide.  One launch of one wave: lane b serves slot b.
-// select: for every draft row with sp.gstate[r] >= 0 the shaped logits (the raw value; -inf where bit r of guide.mask is clear; an id of
-//   eos_ids is allowed iff the state is accepting) — the guided branch of the selection stage without rules or penalty — as arg-max
-//   partials over pval / pidx row r (replacing launch_spec_argmax's) and, for a SPEC_ROW_DRAW slot, as values in shaped [..][V] row r.
-hipError_t launch_spec_guide_chain(hipStream_t s, const SpecState& sp, const GuideSel& guide, const int32_t* eos_ids, int n_eos, int rows);
-hipError_t launch_spec_guide_select(hipStream_t s, const SpecState& sp, const GuideSel& guide, const int32_t* eos_ids, int n_eos, const float* logits,
-                                    int V, int ld, int rows, float* shaped, float* pval, int32_t* pidx);
+// draft row r = j * rows + b is selected with rs.params[b] over logits row r with counter out_lens[b] + j, by the selection stage's own
+// arithmetic (select_dev.h), into sp.cand[b][j - 1].  Two launches of rows * k workgroups; every other draft row's workgroup exits at once.
+// A draft row whose selection is shaped (a guided slot with sp.gstate[r] >= 0; a ruled, n-gram or penalised slot) reads row r of rs.pen
+// instead of the logits (launch_spec_shape_select left the values and the partials of their maximum there).
+hipError_t launch_spec_draw(hipStream_t s, const SpecState& sp, const float* logits, int V, int ld, int rows, const RowSel& rs, const int32_t* out_lens,
+                            const float* pval, const int32_t* pidx);
+// Shaped slots of a speculating step, after the lm_head and before anything is selected:
+// chain (sp.gstate != nullptr): sp.gstate[j * rows + b], j = 1 .. k, = the state of slot b (guide.rows[b].state, which nothing has moved yet)
+//   walked over the bytes of drafts 1 .. j, for j <= n_live[b]; -1 from the first draft on that has no bytes, is one of eos_ids or — rules
+//   != nullptr — of the slot's own stop ids, or meets GUIDE_DEAD, for j > n_live[b] and for a slot without a guide.  One launch of one
+//   wave: lane b serves slot b.
+// shape_select: for every live draft row whose selection is shaped, the values of the stage's shape_logit (select_dev.h) under the
+//   hypothesis that the drafts before the row were committed — the rule image, -inf for EOS / stop ids below min_tokens (at output index
+//   out_lens[b] + j) or in a state that is not accepting, bit r of guide.mask, bit r of ngram.mask, the penalties over cnt[b] plus the
+//   drafts before the row — as arg-max partials over pval / pidx row r (replacing launch_spec_argmax's) and, for a SPEC_ROW_DRAW slot, as
+//   values in row r of rs.pen.  st: out_lens and the EOS ids are read, nothing is written.
+hipError_t launch_spec_guide_chain(hipStream_t s, const SpecState& sp, const GuideSel& guide, const int32_t* eos_ids, int n_eos, int rows,
+                                   const RowRules* rules = nullptr);
+hipError_t launch_spec_shape_select(hipStream_t s, const SpecState& sp, const RowSel& rs, const StepState& st, const float* logits, int V, int ld, int rows,
+                                    float* pval, int32_t* pidx);
 // after the selection stage committed the first `rows` rows: per slot, while the row is not finished and draft j equals the token just
-// committed, commit the candidate of draft row j + 1 (its arg max, or sp.cand for a SPEC_ROW_DRAW slot) through commit_token: EOS, cap,
-// output and — stop.rows != nullptr — the row's stop automaton as in a sequential step; counts into sp.stats and clears the slot's drafts.
-// guide (with sp.gstate; else GuideSel{}): a slot that holds a guide commits with it, so its automaton advances as in a sequential step, and
-// its walk also ends at a draft row with sp.gstate < 0
-hipError_t launch_spec_accept(hipStream_t s, const SpecState& sp, const StepState& st, int rows, const float* pval, const int32_t* pidx, const StopSel& stop,
-                              const GuideSel& guide = GuideSel{});
+// committed, commit the candidate of draft row j + 1 (its arg max, or sp.cand for a SPEC_ROW_DRAW slot) as the stage commits a row
+// (select_dev.h commit_row over rs): the output count of a penalised slot, then EOS / the slot's stop ids, the cap, the output, the guide's
+// automaton and the stop automaton as in a sequential step; counts into sp.stats and clears the slot's drafts.  The walk of a guided slot
+// also ends at a draft row with sp.gstate < 0
+hipError_t launch_spec_accept(hipStream_t s, const SpecState& sp, const StepState& st, int rows, int V, const float* pval, const int32_t* pidx,
+                              const RowSel& rs);
 // drafts[b * draft_stride + 0 .. n_draft[b]) = the continuation of the longest suffix n-gram (min_n .. max_n) of out_ids[b * out_stride +
 // 0 .. out_lens[b]) that occurred before, at most k ids (the rule: include/dots_ocr_hip.h).  Rows that sel masks out, finished rows, rows
 // with cls[b] == SPEC_ROW_NONE, and every row while engine_greedy == 0 draft nothing (finished / sel / cls may be nullptr).

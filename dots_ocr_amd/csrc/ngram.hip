@@ -15,11 +15,42 @@
 // Threads stride over the candidates; each compares its n - 1 tokens against P (staged in LDS once) and leaves at the first mismatch, so
 // ordinary text costs about one coalesced 4-byte read per candidate.  A row that really loops (the case the rule exists for) matches long
 // prefixes: the worst case is (n - 1) reads per candidate, all of them L2 hits on a history of at most max_seq_len x 4 bytes.
+#include "common.h"
 #include "kernels.h"
 
 namespace {
 
 constexpr int NG_THREADS = 256;
+
+// The banned bits of one row from a history of L tokens that `out(i)` reads, built in s_bits and stored to dst [g.words].  Called by every
+// thread of the workgroup with uniform arguments; s_p / s_white are the caller's LDS.  ngram_ban_kernel reads the row's own output,
+// ngram_ban_drafts_kernel the output followed by the drafts a draft row takes as committed: one rule, two histories.
+template <typename Hist>
+DEVI void ngram_ban_row(const NgramSel& g, const RowNgram& rule, int n, int L, Hist out, uint32_t* __restrict__ dst, uint32_t* s_bits, int32_t* s_p,
+                        int32_t* s_white) {
+    const int tid = threadIdx.x;
+    const int window = rule.window, n_white = min(max(rule.n_white, 0), DOTS_MAX_NGRAM_WHITELIST);
+    const int m = n - 1;
+    for (int w = tid; w < g.words; w += NG_THREADS) s_bits[w] = 0;
+    if (tid < m && L >= m) s_p[tid] = out(L - m + tid);
+    if (tid < n_white) s_white[tid] = rule.white[tid];
+    __syncthreads();
+    // candidates i in [lo, L - n]: the n-gram out[i .. i + n) lies inside the history (and inside the last `window` tokens)
+    const int lo = window > 0 ? max(0, L - window) : 0;
+    for (int i = lo + tid; i <= L - n; i += NG_THREADS) {
+        bool hit = true;
+        for (int j = 0; j < m; ++j)
+            if (out(i + j) != s_p[j]) { hit = false; break; }
+        if (!hit) continue;
+        const int id = out(i + m);
+        if (id < 0 || id >= g.V) continue;                            // an id from memory indexes the bits only inside [0, V)
+        bool white = false;
+        for (int k = 0; k < n_white; ++k) white = white || s_white[k] == id;
+        if (!white) atomicOr(&s_bits[id >> 5], 1u << (id & 31));
+    }
+    __syncthreads();
+    for (int w = tid; w < g.words; w += NG_THREADS) dst[w] = s_bits[w];
+}
 
 // grid (rows); dynamic LDS: g.words x 4 bytes
 __global__ __launch_bounds__(NG_THREADS) void ngram_ban_kernel(NgramSel g, const int32_t* __restrict__ out_ids, const int32_t* __restrict__ out_lens,
@@ -27,34 +58,39 @@ __global__ __launch_bounds__(NG_THREADS) void ngram_ban_kernel(NgramSel g, const
     extern __shared__ uint32_t s_bits[];
     __shared__ int32_t s_p[DOTS_MAX_NGRAM_SIZE];
     __shared__ int32_t s_white[DOTS_MAX_NGRAM_WHITELIST];
-    const int b = blockIdx.x, tid = threadIdx.x;
+    const int b = blockIdx.x;
     if (sel && !sel[b]) return;                                       // uniform per workgroup, as the two below
     const int n = g.rows[b].n;
     if (n < 1 || n > DOTS_MAX_NGRAM_SIZE) return;
     if (finished && finished[b]) return;
-    const int window = g.rows[b].window, n_white = min(max(g.rows[b].n_white, 0), DOTS_MAX_NGRAM_WHITELIST);
-    const int L = min(max(out_lens[b], 0), out_stride), m = n - 1;
+    const int L = min(max(out_lens[b], 0), out_stride);
     const int32_t* __restrict__ out = out_ids + (size_t)b * out_stride;
-    for (int w = tid; w < g.words; w += NG_THREADS) s_bits[w] = 0;
-    if (tid < m && L >= m) s_p[tid] = out[L - m + tid];
-    if (tid < n_white) s_white[tid] = g.rows[b].white[tid];
+    ngram_ban_row(g, g.rows[b], n, L, [out](int i) { return out[i]; }, g.mask + (size_t)b * g.words, s_bits, s_p, s_white);
+}
+
+// The banned bits of the live draft rows of a speculating step.  grid (rows * k): workgroup x serves step row r = rows + x =
+// j * rows + b and exits at once unless the row is live (j <= n_live[b]: the slot is selected, unfinished and speculates) and the slot
+// carries a rule.  Draft row (b, j) selects the token at output index L + j under the hypothesis that drafts 1 .. j were committed, so its
+// history is out[0 .. L) ++ drafts[b][0 .. j) — values known at the head of the step, L = out_lens[b] before anything commits.  The rule
+// is ngram_ban_row's; the bits go to row r of g.mask, which holds rows * (k + 1) rows: the stage keeps the rows below `rows`.
+// dynamic LDS: g.words x 4 bytes
+__global__ __launch_bounds__(NG_THREADS) void ngram_ban_drafts_kernel(NgramSel g, const int32_t* __restrict__ out_ids, const int32_t* __restrict__ out_lens,
+                                                                      int out_stride, const int32_t* __restrict__ drafts, const int32_t* __restrict__ n_live,
+                                                                      int rows) {
+    extern __shared__ uint32_t s_bits[];
+    __shared__ int32_t s_p[DOTS_MAX_NGRAM_SIZE];
+    __shared__ int32_t s_white[DOTS_MAX_NGRAM_WHITELIST];
+    __shared__ int32_t s_d[DOTS_MAX_SPEC_DRAFTS];
+    const int r = rows + blockIdx.x, j = r / rows, b = r - j * rows;
+    if (j > n_live[b]) return;                                        // uniform per workgroup, as the one below
+    const int n = g.rows[b].n;
+    if (n < 1 || n > DOTS_MAX_NGRAM_SIZE) return;
+    const int L = min(max(out_lens[b], 0), out_stride);
+    const int32_t* __restrict__ out = out_ids + (size_t)b * out_stride;
+    if ((int)threadIdx.x < j) s_d[threadIdx.x] = drafts[b * DOTS_MAX_SPEC_DRAFTS + threadIdx.x];      // j <= n_live[b] <= k <= DOTS_MAX_SPEC_DRAFTS
     __syncthreads();
-    // candidates i in [lo, L - n]: the n-gram out[i .. i + n) lies inside the history (and inside the last `window` tokens)
-    const int lo = window > 0 ? max(0, L - window) : 0;
-    for (int i = lo + tid; i <= L - n; i += NG_THREADS) {
-        bool hit = true;
-        for (int j = 0; j < m; ++j)
-            if (out[i + j] != s_p[j]) { hit = false; break; }
-        if (!hit) continue;
-        const int id = out[i + m];
-        if (id < 0 || id >= g.V) continue;                            // an id from memory indexes the bits only inside [0, V)
-        bool white = false;
-        for (int k = 0; k < n_white; ++k) white = white || s_white[k] == id;
-        if (!white) atomicOr(&s_bits[id >> 5], 1u << (id & 31));
-    }
-    __syncthreads();
-    uint32_t* __restrict__ dst = g.mask + (size_t)b * g.words;
-    for (int w = tid; w < g.words; w += NG_THREADS) dst[w] = s_bits[w];
+    const int32_t* d = s_d;
+    ngram_ban_row(g, g.rows[b], n, L + j, [out, d, L](int i) { return i < L ? out[i] : d[i - L]; }, g.mask + (size_t)r * g.words, s_bits, s_p, s_white);
 }
 
 __global__ void set_row_ngram_kernel(RowNgram* table, int row, RowNgram r) { table[row] = r; }
@@ -75,6 +111,16 @@ hipError_t launch_ngram_ban(hipStream_t s, const NgramSel& g, int B, const int32
         g.words != ngram_mask_words(g.V))
         return hipErrorInvalidValue;
     hipLaunchKernelGGL(ngram_ban_kernel, dim3(B), dim3(NG_THREADS), (size_t)g.words * 4, s, g, out_ids, out_lens, out_stride, finished, sel);
+    return hipGetLastError();
+}
+
+hipError_t launch_ngram_ban_drafts(hipStream_t s, const NgramSel& g, int rows, int k, const int32_t* out_ids, const int32_t* out_lens, int out_stride,
+                                   const int32_t* drafts, const int32_t* n_live) {
+    if (!g.rows || !g.mask || !out_ids || !out_lens || !drafts || !n_live || out_stride < 1 || rows < 1 || k < 1 || k > DOTS_MAX_SPEC_DRAFTS ||
+        rows * (k + 1) > DOTS_MAX_BATCH || g.V < 1 || g.V > NGRAM_MAX_V || g.words != ngram_mask_words(g.V))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(ngram_ban_drafts_kernel, dim3(rows * k), dim3(NG_THREADS), (size_t)g.words * 4, s, g, out_ids, out_lens, out_stride, drafts, n_live,
+                       rows);
     return hipGetLastError();
 }
 

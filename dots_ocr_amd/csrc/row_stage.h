@@ -11,8 +11,12 @@
 
 enum RowFeature { ROW_PARAMS, ROW_RULES, ROW_GUIDE, ROW_NGRAM, ROW_STOP, ROW_FEATURES };
 // which staged rows may verify drafts: SAMPLED and STOP are the values of DOTS_SPEC_ROWS_* (dots_set_speculation_rows, whose
-// every bit is SPEC_ROWS_ALL); SPEC_ROWS_GUIDED is internal: the engine ORs it in from dots_set_speculation_guided
-enum SpecRows { SPEC_ROWS_SAMPLED = 1, SPEC_ROWS_STOP = 2, SPEC_ROWS_ALL = 3, SPEC_ROWS_GUIDED = 4 };
+// every bit is SPEC_ROWS_ALL); the others are internal: the engine ORs SPEC_ROWS_GUIDED in from dots_set_speculation_guided, and NGRAM /
+// RULES / PENALTY — the DOTS_SPEC_SHAPED_* bits moved up by three — from dots_set_speculation_shaped
+enum SpecRows {
+    SPEC_ROWS_SAMPLED = 1, SPEC_ROWS_STOP = 2, SPEC_ROWS_ALL = 3, SPEC_ROWS_GUIDED = 4,
+    SPEC_ROWS_NGRAM = 8, SPEC_ROWS_RULES = 16, SPEC_ROWS_PENALTY = 32
+};
 
 struct RowStage {
     bool has(int row, RowFeature f) const { return (bits[row] >> f) & 1u; }
@@ -39,15 +43,18 @@ struct RowStage {
     }
     // May the row verify drafts?  A row without features does (plain greedy).  A staged row does iff every feature it
     // carries is one the mode lets through — own parameters under SPEC_ROWS_SAMPLED, stop strings under SPEC_ROWS_STOP, a guide under
-    // SPEC_ROWS_GUIDED (its state depends on the committed tokens only, so a draft row's state is known at the head of the step), nothing
-    // else under any mode: penalties and an n-gram rule depend on the history of rejected tokens, rules stay sequential — and its
-    // parameters, if it has any, carry no penalty (has_pen: the caller's fact about them; ignored for a row without ROW_PARAMS).  Logprobs
-    // and the engine-wide temperature are not stage features: the caller adds them.
+    // SPEC_ROWS_GUIDED, an n-gram rule under SPEC_ROWS_NGRAM, logit rules under SPEC_ROWS_RULES — and its parameters, if it has any, carry
+    // no penalty or the mode has SPEC_ROWS_PENALTY (has_pen: the caller's fact about them; ignored for a row without ROW_PARAMS).  None
+    // of these depends on a rejected token: draft row j is selected under the hypothesis that drafts 1 .. j were committed, and under it
+    // the guide's state, the history an n-gram rule reads, the output counts and the output index are known at the head of the step;
+    // rejected rows leave nothing behind.  The bits are opt-ins because each adds launches to a step, not because a row could go wrong.
+    // Logprobs and the engine-wide temperature are not stage features: the caller adds them.
     bool speculates(int row, bool has_pen, int mode) const {
         const unsigned open = ((mode & SPEC_ROWS_SAMPLED) ? 1u << ROW_PARAMS : 0u) | ((mode & SPEC_ROWS_STOP) ? 1u << ROW_STOP : 0u) |
-                              ((mode & SPEC_ROWS_GUIDED) ? 1u << ROW_GUIDE : 0u);
+                              ((mode & SPEC_ROWS_GUIDED) ? 1u << ROW_GUIDE : 0u) | ((mode & SPEC_ROWS_NGRAM) ? 1u << ROW_NGRAM : 0u) |
+                              ((mode & SPEC_ROWS_RULES) ? 1u << ROW_RULES : 0u);
         if (bits[row] & ~open) return false;
-        return !(has(row, ROW_PARAMS) && has_pen);
+        return !(has(row, ROW_PARAMS) && has_pen && !(mode & SPEC_ROWS_PENALTY));
     }
     void reset() { *this = RowStage{}; }
 

@@ -9,7 +9,7 @@ namespace {
 // features and the penalty of the row's parameters through RowStage::speculates, and logprobs (not a stage feature).  The engine-wide
 // temperature is not a row's fact: the kernels get it as engine_greedy.
 int spec_row_class(const DotsEngine* e, int row) {
-    const int mode = e->spec_rows | (e->spec_guided ? SPEC_ROWS_GUIDED : 0);
+    const int mode = e->spec_rows | (e->spec_guided ? SPEC_ROWS_GUIDED : 0) | e->spec_shaped * SPEC_ROWS_NGRAM;      // DOTS_SPEC_SHAPED_* moved up by three bits
     if (e->row_lp[row] >= 0 || !e->stage.speculates(row, e->row_pen[row], mode)) return SPEC_ROW_NONE;
     if (e->stage.staged(row) && !e->stage.has(row, ROW_PARAMS) && e->row_entry_sampled[row]) return SPEC_ROW_NONE;
     return e->stage.has(row, ROW_PARAMS) && e->row_sampled[row] ? SPEC_ROW_DRAW : SPEC_ROW_ARGMAX;
@@ -173,6 +173,32 @@ bool spec_draws(const DotsEngine* e) {
 // one row holds a guide.  With dots_set_speculation_guided off a step launches what it always did
 bool spec_guides(const DotsEngine* e) {
     return e->slot_mode && e->spec_k > 0 && e->spec_guided && e->stage.rows(ROW_GUIDE) > 0;
+}
+
+// Which shaped rows may verify drafts in a speculating step (StepKey::sspec; the DOTS_SPEC_SHAPED_* bits)?  Host counts: a bit is set while
+// dots_set_speculation_shaped has it and at least one row holds the feature — an n-gram rule, logit rules, parameters with a penalty.  0:
+// a step launches what it always did, and the draft-row kernels get no table of these features
+int spec_shapes(const DotsEngine* e) {
+    if (!e->slot_mode || e->spec_k <= 0 || !e->spec_shaped) return 0;
+    int on = 0;
+    if ((e->spec_shaped & DOTS_SPEC_SHAPED_NGRAM) && e->stage.rows(ROW_NGRAM) > 0) on |= DOTS_SPEC_SHAPED_NGRAM;
+    if ((e->spec_shaped & DOTS_SPEC_SHAPED_RULES) && e->stage.rows(ROW_RULES) > 0) on |= DOTS_SPEC_SHAPED_RULES;
+    if ((e->spec_shaped & DOTS_SPEC_SHAPED_PENALTY) && e->pen_cnt && e->stage.rows(ROW_PARAMS) > 0)
+        for (int b = 0; b < e->cfg.max_batch; ++b)
+            if (e->stage.has(b, ROW_PARAMS) && e->row_pen[b]) { on |= DOTS_SPEC_SHAPED_PENALTY; break; }
+    return on;
+}
+
+// The RowSel of the draft rows of a speculating step (kernels.h): the stage's tables as far as the switches open them
+RowSel spec_row_sel(const DotsEngine* e) {
+    const int V = e->cfg.vocab_size, on = spec_shapes(e);
+    RowSel rs{e->d_rowp, e->d_row_own, nullptr, nullptr, e->pen_logits, e->d_row_thr, e->temperature > 0.f ? 0 : 1, nullptr, nullptr, GuideSel{}, NgramSel{}, StopSel{}};
+    if (on & DOTS_SPEC_SHAPED_PENALTY) { rs.cnt = e->pen_cnt; rs.seen = e->pen_seen; }
+    if (on & DOTS_SPEC_SHAPED_RULES) { rs.rules = e->d_rules; rs.rule_img = e->rule_img; }
+    if (on & DOTS_SPEC_SHAPED_NGRAM) rs.ngram = NgramSel{e->d_ngram, e->ngram_mask, ngram_mask_words(V), V};
+    if (spec_guides(e)) rs.guide = guide_sel(e);
+    if (e->d_stop) rs.stop = StopSel{e->d_stop, e->tok_off, e->tok_bytes, V, 0};
+    return rs;
 }
 
 SpecState spec_state(const DotsEngine* e) {
@@ -652,6 +678,20 @@ int dots_set_speculation_guided(DotsEngine* e, int on) {
     e->spec_guided = on != 0;
     drop_step_graphs(e);                                     // a captured step bakes in whether it selects the draft rows of guided slots
     return upload_spec_classes(e);                           // free slots may hold guides: every row's class under the new setting
+}
+
+int dots_set_speculation_shaped(DotsEngine* e, int flags) {
+    if (!e) return DOTS_E_INVALID;
+    if (flags & ~(DOTS_SPEC_SHAPED_NGRAM | DOTS_SPEC_SHAPED_RULES | DOTS_SPEC_SHAPED_PENALTY))
+        return e->fail(DOTS_E_INVALID, "unknown shaped speculation flags 0x%x (DOTS_SPEC_SHAPED_NGRAM | DOTS_SPEC_SHAPED_RULES | DOTS_SPEC_SHAPED_PENALTY)", flags);
+    if (e->slot_mode)
+        for (int b = 0; b < e->cfg.max_batch; ++b)
+            if (e->slot_active[b]) return e->fail(DOTS_E_STATE, "shaped speculation cannot change while slot %d is occupied", b);
+    if (flags == e->spec_shaped) return DOTS_OK;
+    CK(hipSetDevice(e->device));
+    e->spec_shaped = flags;
+    drop_step_graphs(e);                                     // a captured step bakes in whether it shapes the draft rows of such slots
+    return upload_spec_classes(e);                           // free slots may hold features: every row's class under the new setting
 }
 
 int dots_set_row_drafts(DotsEngine* e, int row, const int32_t* ids_host, int n) {

@@ -4,7 +4,9 @@
 // row stands for, so a draft row's candidate is the token the sequential step would have drawn there, bit for bit.
 //   tempered values t_i = (l_i - m) / T, integer weights w_i = floor(exp(t_i) 2^40) (t_i >= -27; below that w_i = 0), keys
 //   k_i = bits(-t_i) (monotone: a smaller key is a larger t); every sum is an integer sum, so no result depends on the order of the atomics.
-// Every function here is called by all SEL_THREADS threads of a workgroup with uniform arguments.
+// Before them, what the stage and the draft-row kernels share about a row whatever its temperature: which features it carries in a launch
+// (row_ruled .. row_penalised), the value a token is selected from (shape_logit) and the commit of a selected token (commit_row).
+// Every function from sel_key on is called by all SEL_THREADS threads of a workgroup with uniform arguments.
 #pragma once
 #include "common.h"
 #include "kernels.h"
@@ -23,6 +25,65 @@ DEVI uint64_t splitmix64(uint64_t x) {
 }
 
 DEVI bool row_has_pen(const RowParams& p) { return p.repetition_penalty != 1.0f || p.frequency_penalty != 0.0f || p.presence_penalty != 0.0f; }
+
+// does row b carry logit rules in this launch (uniform per workgroup)
+DEVI bool row_ruled(const RowSel& rs, int b) { return rs.rules && (rs.rules[b].flags & RULE_ON); }
+// does row b hold a guide in this launch (uniform per workgroup)
+DEVI bool row_guided(const RowSel& rs, int b) { return rs.guide.rows && rs.guide.rows[b].table; }
+// does row b carry an n-gram rule in this launch (uniform per workgroup)
+DEVI bool row_ngram(const RowSel& rs, int b) { return rs.ngram.rows && rs.ngram.rows[b].n > 0; }
+
+// is row b penalised in this launch (uniform per workgroup): the counts exist, the stage owns the row (the entry of a row it does not own
+// is not parameters) and its parameters carry a penalty
+DEVI bool row_penalised(const RowSel& rs, int b) { return rs.cnt && rs.own[b] != 0 && row_has_pen(rs.params[b]); }
+
+// HF / vLLM repetition penalty on every token seen in the prompt or the output, then OpenAI frequency / presence on the output counts
+DEVI float penalise(float l, int c, bool seen_prompt, const RowParams& p) {
+    if ((seen_prompt || c > 0) && p.repetition_penalty != 1.0f) l = l > 0.f ? l / p.repetition_penalty : l * p.repetition_penalty;
+    if (c > 0) l = l - (p.frequency_penalty * (float)c + p.presence_penalty);
+    return l;
+}
+
+// The value token i of a row is selected from, from its logit l.  ONE definition: select_partial_kernel
+// (decode.hip) shapes the rows of a step with it, spec_shape_select_kernel (spec.hip) the draft rows of a speculating step.
+// In vLLM's order: l + the rule image (-inf: banned / not allowed); -inf for an EOS / stop id of the kill list (below min_tokens, or on a
+// guided row whose state is not accepting: the guide's bit does not speak for such an id), else -inf where the guide's bit is clear; -inf
+// where the n-gram bit is set; then the penalties on that value (-inf stays -inf: r > 0 and the subtrahend is finite).
+// RowShape: what the row carries, uniform per workgroup; a null pointer = the row has no such feature.  drafts: the tokens a draft row
+// takes as committed before it, counted on top of cnt (a row of a plain step has none).
+struct RowShape {
+    const float* img;          // its row of the rule image
+    const uint32_t* gbits;     // its allowed bits (a guide)
+    const uint32_t* nbits;     // its banned bits (an n-gram rule)
+    const int32_t* cnt;        // its output counts: != nullptr = the row is penalised
+    const uint32_t* seen;      // its prompt-presence bits (with cnt)
+    const int* kill;           // LDS: the EOS / stop ids that fall into the workgroup's chunk
+    int n_kill;
+    bool kill_on;              // what such an id gets: true = -inf
+    const int32_t* drafts;     // LDS
+    int n_drafts;
+};
+DEVI float shape_logit(float l, int i, const RowShape& s, const RowParams& p) {
+    if (s.img) l += s.img[i];
+    bool term = false;
+    for (int k = 0; k < s.n_kill; ++k) term = term || s.kill[k] == i;
+    if (term ? s.kill_on : (s.gbits && !((s.gbits[i >> 5] >> (i & 31)) & 1u))) l = -INFINITY;
+    if (s.nbits && ((s.nbits[i >> 5] >> (i & 31)) & 1u)) l = -INFINITY;
+    if (s.cnt) {
+        int c = s.cnt[i];
+        for (int k = 0; k < s.n_drafts; ++k) c += s.drafts[k] == i;
+        l = penalise(l, c, (s.seen[i >> 5] >> (i & 31)) & 1u, p);
+    }
+    return l;
+}
+
+// The commit of a row the per-row stage owns: the output count of an unfinished penalised row (pen: the row's parameters carry a penalty and
+// the counts exist), then commit_token with the row's rules, the guides and the stop automata of the launch.  ONE definition:
+// select_rows_kernel commits the rows of a step with it, spec_accept_kernel (spec.hip) every token of its walk.
+DEVI void commit_row(const StepState& st, const RowSel& rs, int b, int V, bool pen, int tok) {
+    if (pen && !st.finished[b] && tok >= 0 && tok < V) rs.cnt[(size_t)b * V + tok] += 1;     // output counts of the rows with penalties
+    commit_token(st, b, tok, row_ruled(rs, b) ? rs.rules + b : nullptr, rs.guide.rows ? &rs.guide : nullptr, rs.stop.rows ? &rs.stop : nullptr);
+}
 
 DEVI uint32_t sel_key(float t) { return __float_as_uint(0.f - t); }              // 0 - (+-0) = +0: the maximum has key 0
 DEVI float sel_t(uint32_t key) { return -__uint_as_float(key); }

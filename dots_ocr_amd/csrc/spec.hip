@@ -12,9 +12,12 @@
 //   spec_argmax_kernel   after the lm_head: the arg-max partials of the live draft rows (the merge rule of argmax_partial_kernel)
 //   spec_thresh_kernel, spec_draw_kernel   then, only while a row with parameters may speculate (dots_set_speculation_rows): the candidates
 //                        of the live draft rows of SPEC_ROW_DRAW slots, by the selection stage's own arithmetic (select_dev.h)
-//   spec_guide_chain_kernel, (guide_mask_drafts_kernel, guided.hip), spec_guide_select_kernel   after spec_argmax_kernel, only while a
-//                        guided row may speculate (dots_set_speculation_guided): the state every live draft row of a guided slot is
-//                        selected under, its allowed bits, and its arg-max partials (and values, for a sampled slot) under the guide
+//   spec_guide_chain_kernel, (guide_mask_drafts_kernel, guided.hip)   after spec_argmax_kernel, only while a guided row may speculate
+//                        (dots_set_speculation_guided): the state every live draft row of a guided slot is selected under, and its allowed bits
+//   (ngram_ban_drafts_kernel, ngram.hip)   only while a row with an n-gram rule may speculate (dots_set_speculation_shaped): the banned
+//                        bits of every live draft row of such a slot, over the slot's output followed by the drafts before the row
+//   spec_shape_select_kernel   then, while a guided, ruled, n-gram or penalised row may speculate: the arg-max partials (and values, for a
+//                        sampled slot) of the live draft rows of such slots, shaped by the selection stage's own function (select_dev.h)
 //   spec_accept_kernel   after the selection stage: walks a slot's drafts and commits through commit_token while they hold
 //   ngram_draft_kernel   end of the step: the next step's drafts from the row's own output (prompt lookup without the prompt)
 //
@@ -82,46 +85,53 @@ __global__ __launch_bounds__(256) void spec_argmax_kernel(const float* __restric
 
 // The candidates of the draft rows of sampled slots.  grid (rows * k): workgroup x serves draft row r = rows + x = j * rows + b, and exits at
 // once unless the row is live and its slot is SPEC_ROW_DRAW.  The row is selected exactly as select_thresh_kernel / select_rows_kernel
-// (decode.hip) select row b of a sequential step at that position: the same device functions over logits row r (a speculating row has no
-// penalty, rules, guide or n-gram rule, so the raw logits are what the stage would read), params[b], the softmax maximum from the partials
-// spec_argmax_kernel left for r, and the counter out_lens[b] + j — out_lens as the head of the step saw it: both kernels run before the
+// (decode.hip) select row b of a sequential step at that position: the same device functions over logits row r (the raw logits are what
+// the stage reads for a row that nothing shapes), rs.params[b], the softmax maximum from the partials left for r, and the counter out_lens[b] + j — out_lens as the head of the step saw it: both kernels run before the
 // selection stage commits.
-// A draft row selected under a guide (sp.gstate[r] >= 0) reads its row of `shaped` instead, as select_thresh_kernel / select_rows_kernel
-// read the shaped values of a guided sampled row: spec_guide_select_kernel left them there, and their maximum in the partials of r.
-DEVI const float* spec_draw_row(const SpecState& sp, const float* logits, int ld, const float* shaped, int V, int r) {
-    return sp.gstate && sp.gstate[r] >= 0 ? shaped + (size_t)r * V : logits + (size_t)r * ld;
+// A draft row whose selection is shaped (spec_row_shaped) reads its row of rs.pen instead, as select_thresh_kernel / select_rows_kernel read
+// the shaped values of a guided, ruled, n-gram or penalised sampled row: spec_shape_select_kernel left them there, and their maximum in
+// the partials of r.
+//
+// Which slots are shaped in this launch, from the device tables (uniform per workgroup).  rs is the RowSel of the draft rows: a table the
+// host's switches (dots_set_speculation_guided / dots_set_speculation_shaped) do not open is a null pointer in it, and a slot that
+// carries that feature is SPEC_ROW_NONE then — it has no live draft row.
+DEVI bool spec_slot_guided(const SpecState& sp, const RowSel& rs, int b) { return sp.gstate && row_guided(rs, b); }
+// is live draft row r of slot b selected from shaped values?  Under a guide only while the chain has a state for it: a dead row verifies nothing
+DEVI bool spec_row_shaped(const SpecState& sp, const RowSel& rs, int b, int r) {
+    if (spec_slot_guided(sp, rs, b)) return sp.gstate[r] >= 0;
+    return row_ruled(rs, b) || row_ngram(rs, b) || row_penalised(rs, b);
+}
+DEVI const float* spec_draw_row(const SpecState& sp, const RowSel& rs, const float* logits, int ld, int V, int b, int r) {
+    return spec_row_shaped(sp, rs, b, r) ? rs.pen + (size_t)r * V : logits + (size_t)r * ld;
 }
 
-__global__ __launch_bounds__(SEL_THREADS) void spec_thresh_kernel(const float* __restrict__ logits, int V, int ld, int rows, SpecState sp,
-                                                                  const RowParams* __restrict__ params, uint32_t* __restrict__ thr,
-                                                                  const float* __restrict__ pval, const int32_t* __restrict__ pidx,
-                                                                  const float* __restrict__ shaped) {
+__global__ __launch_bounds__(SEL_THREADS) void spec_thresh_kernel(const float* __restrict__ logits, int V, int ld, int rows, SpecState sp, RowSel rs,
+                                                                  const float* __restrict__ pval, const int32_t* __restrict__ pidx) {
     __shared__ SelLds L;
     const int r = rows + blockIdx.x, j = r / rows, b = r - j * rows;
     if (j > sp.n_live[b] || sp.cls[b] != SPEC_ROW_DRAW) return;      // uniform per workgroup
-    const RowParams p = params[b];
+    const RowParams p = rs.params[b];
     if (!(p.temperature > 0.f)) return;
     if (sel_unfiltered(p)) {
-        if (threadIdx.x == 0) thr[r] = SEL_NONE;
+        if (threadIdx.x == 0) rs.thr[r] = SEL_NONE;
         return;
     }
     merge_partials(pval, pidx, r, &L.best, &L.bi);
-    sel_threshold(spec_draw_row(sp, logits, ld, shaped, V, r), V, p, L.best, thr + r, L);
+    sel_threshold(spec_draw_row(sp, rs, logits, ld, V, b, r), V, p, L.best, rs.thr + r, L);
 }
 
-__global__ __launch_bounds__(SEL_THREADS) void spec_draw_kernel(const float* __restrict__ logits, int V, int ld, int rows, SpecState sp,
-                                                                const RowParams* __restrict__ params, const uint32_t* __restrict__ thr,
+__global__ __launch_bounds__(SEL_THREADS) void spec_draw_kernel(const float* __restrict__ logits, int V, int ld, int rows, SpecState sp, RowSel rs,
                                                                 const int32_t* __restrict__ out_lens, const float* __restrict__ pval,
-                                                                const int32_t* __restrict__ pidx, const float* __restrict__ shaped) {
+                                                                const int32_t* __restrict__ pidx) {
     __shared__ float s_best;
     __shared__ int s_bi;
     __shared__ DrawLds D;
     const int r = rows + blockIdx.x, j = r / rows, b = r - j * rows;
     if (j > sp.n_live[b] || sp.cls[b] != SPEC_ROW_DRAW) return;      // uniform per workgroup
     merge_partials(pval, pidx, r, &s_best, &s_bi);
-    const RowParams p = params[b];
+    const RowParams p = rs.params[b];
     int tok = -1;
-    if (p.temperature > 0.f) tok = sel_draw(spec_draw_row(sp, logits, ld, shaped, V, r), V, p, s_best, thr[r], (uint32_t)(out_lens[b] + j), D);
+    if (p.temperature > 0.f) tok = sel_draw(spec_draw_row(sp, rs, logits, ld, V, b, r), V, p, s_best, rs.thr[r], (uint32_t)(out_lens[b] + j), D);
     if (threadIdx.x == 0) sp.cand[b * DOTS_MAX_SPEC_DRAFTS + j - 1] = tok >= 0 ? tok : s_bi;      // no token: the arg max, as select_rows_kernel
 }
 
@@ -131,11 +141,13 @@ __global__ __launch_bounds__(SEL_THREADS) void spec_draw_kernel(const float* __r
 // by then; if they are not, nobody reads the row.  A draft the guide could not have committed at its position — no bytes, an EOS id (it
 // finishes the row and is not walked), a byte without a transition — ends the chain: its row and every later one get -1, and so do the
 // rows past n_live and the rows of a slot without a guide.
-__global__ __launch_bounds__(64) void spec_guide_chain_kernel(SpecState sp, GuideSel g, const int32_t* __restrict__ eos_ids, int n_eos, int rows) {
+__global__ __launch_bounds__(64) void spec_guide_chain_kernel(SpecState sp, GuideSel g, const int32_t* __restrict__ eos_ids, int n_eos, int rows,
+                                                              const RowRules* __restrict__ rules) {
     const int b = threadIdx.x;
     if (b >= rows) return;
     const RowGuide rg = g.rows[b];
     const int nl = rg.table ? sp.n_live[b] : 0;
+    const int n_stop = rules && (rules[b].flags & RULE_ON) ? min(rules[b].n_stop, DOTS_MAX_STOP_IDS) : 0;
     uint32_t s = (uint32_t)rg.state;
     bool dead = false;
     for (int j = 1; j <= sp.k; ++j) {
@@ -147,6 +159,7 @@ __global__ __launch_bounds__(64) void spec_guide_chain_kernel(SpecState sp, Guid
             if (!dead) { i = g.tok_off[tok]; end = g.tok_off[tok + 1]; }
             dead = dead || i >= end;
             for (int e = 0; e < n_eos; ++e) dead = dead || tok == eos_ids[e];
+            for (int e = 0; e < n_stop; ++e) dead = dead || tok == rules[b].stop[e];
             for (; i < end && !dead; ++i) {
                 s = rg.table[(size_t)s * 256 + g.tok_bytes[i]];
                 dead = s == GUIDE_DEAD;
@@ -156,42 +169,57 @@ __global__ __launch_bounds__(64) void spec_guide_chain_kernel(SpecState sp, Guid
     }
 }
 
-// The arg-max partials of the draft rows selected under a guide, and the shaped values of those a sampler will read.  grid (ARGMAX_CHUNKS,
-// rows * k) as spec_argmax_kernel, after it: a row with sp.gstate[r] >= 0 overwrites the raw partials that kernel left for r, every other
-// row exits at once.  The values are those of the guided branch of select_partial_kernel (decode.hip) for a row without rules or penalty —
-// the raw logit, -inf where the row's bit is clear, an engine EOS id allowed iff the state is accepting whatever its bit — in the same
-// chunks under the same merge rule, so the partials are what the stage would leave for the sequential step at that position.
-__global__ __launch_bounds__(256) void spec_guide_select_kernel(const float* __restrict__ logits, int V, int ld, int rows, SpecState sp, GuideSel g,
-                                                                const int32_t* __restrict__ eos_ids, int n_eos, float* __restrict__ shaped_rows,
-                                                                float* __restrict__ pval, int32_t* __restrict__ pidx) {
+// The arg-max partials of the draft rows whose selection is shaped, and the shaped values of those a sampler will read.  grid (ARGMAX_CHUNKS,
+// rows * k) as spec_argmax_kernel, after it: a live row with spec_row_shaped overwrites the raw partials that kernel left for r, every other
+// row exits at once.  Draft row r = (b, j) selects the token at output index out_lens[b] + j under the hypothesis that drafts 1 .. j were
+// committed; if they were not, nobody reads the row.  Under that hypothesis everything that shapes it is known here, before anything
+// commits: the rule image, the stop ids and the prompt-presence bits are the slot's own and do not move; "below min_tokens" is
+// out_lens[b] + j < min_tokens; the guide's state is gstate[r] and its bits are row r of guide.mask (the chain and guide_mask_drafts_kernel);
+// the n-gram bits are row r of ngram.mask (ngram_ban_drafts_kernel); the output counts are cnt[b] plus the occurrences among drafts
+// 1 .. j, which the workgroup holds in LDS — cnt itself moves only in a commit, so a rejected draft leaves nothing behind.  The values
+// are shape_logit's (select_dev.h), the function select_partial_kernel (decode.hip) shapes row b with, in the same chunks under the same
+// merge rule, so the partials are what the stage would leave for the sequential step at that position.
+__global__ __launch_bounds__(256) void spec_shape_select_kernel(const float* __restrict__ logits, int V, int ld, int rows, SpecState sp, RowSel rs,
+                                                                StepState st, float* __restrict__ pval, int32_t* __restrict__ pidx) {
     __shared__ float sv[4];
     __shared__ int si[4];
-    __shared__ int s_kill[16], s_nkill;
+    __shared__ int s_kill[16 + DOTS_MAX_STOP_IDS], s_nkill;
+    __shared__ int32_t s_d[DOTS_MAX_SPEC_DRAFTS];
     const int c = blockIdx.x, r = rows + blockIdx.y, j = r / rows, b = r - j * rows;
-    const int state = sp.gstate[r];
-    if (state < 0) return;                                            // uniform per workgroup
+    if (j > sp.n_live[b] || !spec_row_shaped(sp, rs, b, r)) return;  // uniform per workgroup
     const int per = (V + ARGMAX_CHUNKS - 1) / ARGMAX_CHUNKS;
     const int lo = c * per, hi = min(V, lo + per);
-    const bool accepting = g.rows[b].accepting[state] != 0;
-    // the EOS ids that fall into this chunk: the guide's bit does not speak for them
+    const bool ruled = row_ruled(rs, b), guided = spec_slot_guided(sp, rs, b), ngram = row_ngram(rs, b), pen_on = row_penalised(rs, b);
+    const RowParams p = pen_on ? rs.params[b] : RowParams{0.f, 1.f, 0, 1.f, 0.f, 0.f, 0};
+    const int n_stop = ruled ? min(rs.rules[b].n_stop, DOTS_MAX_STOP_IDS) : 0;
+    const bool early = ruled && st.out_lens[b] + j < rs.rules[b].min_tokens;
+    const bool accepting = guided ? rs.guide.rows[b].accepting[sp.gstate[r]] != 0 : true;
+    // the EOS / stop ids that fall into this chunk (-inf below min_tokens, and on a guided row whose state is not accepting), and the
+    // drafts before the row (j <= n_live[b] <= DOTS_MAX_SPEC_DRAFTS)
     if (threadIdx.x == 0) s_nkill = 0;
+    if ((int)threadIdx.x < j) s_d[threadIdx.x] = sp.drafts[b * DOTS_MAX_SPEC_DRAFTS + threadIdx.x];
     __syncthreads();
-    if ((int)threadIdx.x < min(n_eos, 16)) {
-        const int id = eos_ids[threadIdx.x];
+    if ((early || guided) && (int)threadIdx.x < min(st.n_eos, 16) + n_stop) {
+        const int ne = min(st.n_eos, 16);
+        const int id = (int)threadIdx.x < ne ? st.eos_ids[threadIdx.x] : rs.rules[b].stop[threadIdx.x - ne];
         if (id >= lo && id < hi) s_kill[atomicAdd(&s_nkill, 1)] = id;
     }
     __syncthreads();
-    const int n_kill = s_nkill;
+    const int W = (V + 31) >> 5;
+    RowShape sh;
+    sh.img = ruled && (rs.rules[b].flags & RULE_IMG) ? rs.rule_img + (size_t)b * V : nullptr;
+    sh.gbits = guided ? rs.guide.mask + (size_t)r * rs.guide.words : nullptr;
+    sh.nbits = ngram ? rs.ngram.mask + (size_t)r * rs.ngram.words : nullptr;
+    sh.cnt = pen_on ? rs.cnt + (size_t)b * V : nullptr;
+    sh.seen = pen_on ? rs.seen + (size_t)b * W : nullptr;
+    sh.kill = s_kill; sh.n_kill = s_nkill; sh.kill_on = early || !accepting;
+    sh.drafts = s_d; sh.n_drafts = j;
     const float* row = logits + (size_t)r * ld;
-    const uint32_t* gbits = g.mask + (size_t)r * g.words;
-    float* shaped = sp.cls[b] == SPEC_ROW_DRAW ? shaped_rows + (size_t)r * V : nullptr;      // a greedy slot needs the arg max only
+    float* shaped = sp.cls[b] == SPEC_ROW_DRAW ? rs.pen + (size_t)r * V : nullptr;      // a greedy slot needs the arg max only
     float best = -INFINITY;
     int bi = 0x7fffffff;
     for (int i = lo + threadIdx.x; i < hi; i += 256) {
-        float l = row[i];
-        bool term = false;
-        for (int k = 0; k < n_kill; ++k) term = term || s_kill[k] == i;
-        if (term ? !accepting : !((gbits[i >> 5] >> (i & 31)) & 1u)) l = -INFINITY;
+        const float l = shape_logit(row[i], i, sh, p);
         if (shaped) shaped[i] = l;
         argmax_merge(best, bi, l, i);
     }
@@ -209,21 +237,21 @@ __global__ __launch_bounds__(256) void spec_guide_select_kernel(const float* __r
 // grid (rows), one wave.  Row 0's token is committed (the selection stage ran); draft j is right iff it equals the token committed before
 // it, and then the candidate of draft row j + 1 — its arg max, or for a SPEC_ROW_DRAW slot the token spec_draw_kernel drew — is the next
 // token of the sequential run.
-// The commit is commit_token with the row's stop automaton (stop.rows != nullptr: some row of the engine held one; a row without one walks
-// nothing).  That is exactly what commit_row (decode.hip) does for a speculating row in a sequential step: such a row has no penalty (no
-// count to add), no rules (rules == nullptr) and no guide (commit_token reads the guide only through rows[b].table, which is null), so
-// EOS, the cap, min_tokens and the hit record come out of the same code, and a match finishes the row mid-walk.
-// A slot that holds a guide (it speculates only under dots_set_speculation_guided, and then sp.gstate and guide.rows are set) commits with
-// the guide, again as commit_row does: the automaton advances by the bytes of every token of the walk, and an EOS the final state forced
-// finishes the row mid-walk.  Its walk also ends at a draft row the chain marked dead: the draft there is not a token the guide could have
+// The commit is commit_row (select_dev.h), the function select_rows_kernel commits row b of a sequential step with, over rs, the RowSel of
+// the draft rows: the output count of a penalised slot moves with every token of the walk and with nothing else, the slot's rules decide
+// EOS / stop ids, its guide's automaton advances by the bytes of every token, its stop automaton walks them, and EOS, the cap and the hit
+// record come out of the same code; any of them finishes the row mid-walk.  A table of rs that is null (the switch that opens it is off, or
+// no row holds the feature) is one no speculating slot has an entry in.
+// The walk of a guided slot also ends at a draft row the chain marked dead: the draft there is not a token the guide could have
 // committed, so if it equals what was committed that was the all -inf fallback (id 0, the state did not move) and nothing past it is verified.
-__global__ __launch_bounds__(64) void spec_accept_kernel(SpecState sp, StepState st, int rows, const float* __restrict__ pval,
-                                                         const int32_t* __restrict__ pidx, StopSel stop, GuideSel guide) {
+__global__ __launch_bounds__(64) void spec_accept_kernel(SpecState sp, StepState st, int rows, int V, const float* __restrict__ pval,
+                                                         const int32_t* __restrict__ pidx, RowSel rs) {
     __shared__ int32_t s_tok[DOTS_MAX_SPEC_DRAFTS];
     const int b = blockIdx.x, lane = threadIdx.x;
     const int nl = sp.n_live[b];                                      // uniform
     const bool drawn = sp.cand && sp.cls[b] == SPEC_ROW_DRAW;         // uniform
-    const bool guided = sp.gstate && guide.rows && guide.rows[b].table;      // uniform
+    const bool guided = spec_slot_guided(sp, rs, b);                  // uniform
+    const bool pen = row_penalised(rs, b);                      // uniform
     for (int j = 0; j < nl; ++j) {
         if (drawn) {
             if (lane == 0) s_tok[j] = sp.cand[b * DOTS_MAX_SPEC_DRAFTS + j];
@@ -243,10 +271,7 @@ __global__ __launch_bounds__(64) void spec_accept_kernel(SpecState sp, StepState
     int acc = 0;
     while (acc < nl && !st.finished[b] && sp.drafts[b * DOTS_MAX_SPEC_DRAFTS + acc] == st.cur_tokens[b]) {
         if (guided && sp.gstate[(acc + 1) * rows + b] < 0) break;
-        if (guided && stop.rows) commit_token(st, b, s_tok[acc], nullptr, &guide, &stop);
-        else if (guided) commit_token(st, b, s_tok[acc], nullptr, &guide);
-        else if (stop.rows) commit_token(st, b, s_tok[acc], nullptr, nullptr, &stop);
-        else commit_token(st, b, s_tok[acc]);
+        commit_row(st, rs, b, V, pen, s_tok[acc]);
         ++acc;
     }
     unsigned long long* mine = sp.stats + (size_t)b * 3;
@@ -333,13 +358,26 @@ hipError_t launch_spec_argmax(hipStream_t s, const SpecState& sp, const float* l
     return hipGetLastError();
 }
 
-hipError_t launch_spec_draw(hipStream_t s, const SpecState& sp, const float* logits, int V, int ld, int rows, const RowParams* params, uint32_t* thr,
-                            const int32_t* out_lens, const float* pval, const int32_t* pidx, const float* shaped) {
-    if (!spec_ok(sp, rows) || !sp.cand || !logits || !params || !thr || !out_lens || !pval || !pidx || V < 1 || ld < V) return hipErrorInvalidValue;
-    if (sp.gstate && !shaped) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(spec_thresh_kernel, dim3(rows * sp.k), dim3(SEL_THREADS), 0, s, logits, V, ld, rows, sp, params, thr, pval, pidx, shaped);
-    hipLaunchKernelGGL(spec_draw_kernel, dim3(rows * sp.k), dim3(SEL_THREADS), 0, s, logits, V, ld, rows, sp, params, (const uint32_t*)thr, out_lens, pval,
-                       pidx, shaped);
+namespace {
+bool spec_shaped_sel(const SpecState& sp, const RowSel& rs) { return sp.gstate || rs.rules || rs.ngram.rows || rs.cnt; }
+bool spec_row_sel_ok(const SpecState& sp, const RowSel& rs, int V) {
+    if (!spec_shaped_sel(sp, rs)) return true;
+    if (!rs.params || !rs.own || !rs.pen) return false;
+    if (rs.rules && !rs.rule_img) return false;
+    if (rs.cnt && !rs.seen) return false;
+    if (rs.ngram.rows && (!rs.ngram.mask || rs.ngram.V != V || rs.ngram.words != ngram_mask_words(V))) return false;
+    if (sp.gstate && (!rs.guide.rows || !rs.guide.mask || !rs.guide.tok_off || !rs.guide.tok_bytes || rs.guide.V != V || rs.guide.words != guide_mask_words(V)))
+        return false;
+    return true;
+}
+}  // namespace
+
+hipError_t launch_spec_draw(hipStream_t s, const SpecState& sp, const float* logits, int V, int ld, int rows, const RowSel& rs, const int32_t* out_lens,
+                            const float* pval, const int32_t* pidx) {
+    if (!spec_ok(sp, rows) || !sp.cand || !logits || !rs.params || !rs.thr || !out_lens || !pval || !pidx || V < 1 || ld < V) return hipErrorInvalidValue;
+    if (!spec_row_sel_ok(sp, rs, V)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(spec_thresh_kernel, dim3(rows * sp.k), dim3(SEL_THREADS), 0, s, logits, V, ld, rows, sp, rs, pval, pidx);
+    hipLaunchKernelGGL(spec_draw_kernel, dim3(rows * sp.k), dim3(SEL_THREADS), 0, s, logits, V, ld, rows, sp, rs, out_lens, pval, pidx);
     return hipGetLastError();
 }
 
@@ -350,30 +388,31 @@ bool spec_guide_ok(const SpecState& sp, const GuideSel& g, const int32_t* eos_id
 }
 }  // namespace
 
-hipError_t launch_spec_guide_chain(hipStream_t s, const SpecState& sp, const GuideSel& guide, const int32_t* eos_ids, int n_eos, int rows) {
+hipError_t launch_spec_guide_chain(hipStream_t s, const SpecState& sp, const GuideSel& guide, const int32_t* eos_ids, int n_eos, int rows,
+                                   const RowRules* rules) {
     // of sp the kernel reads drafts, n_live and k and writes gstate: the single-kernel entry point (ops.hip) fills in no more
     if (!sp.drafts || !sp.n_live || sp.k < 1 || sp.k > DOTS_MAX_SPEC_DRAFTS || rows < 1 || rows * (sp.k + 1) > DOTS_MAX_BATCH ||
         !spec_guide_ok(sp, guide, eos_ids, n_eos))
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(spec_guide_chain_kernel, dim3(1), dim3(64), 0, s, sp, guide, eos_ids, n_eos, rows);
+    hipLaunchKernelGGL(spec_guide_chain_kernel, dim3(1), dim3(64), 0, s, sp, guide, eos_ids, n_eos, rows, rules);
     return hipGetLastError();
 }
 
-hipError_t launch_spec_guide_select(hipStream_t s, const SpecState& sp, const GuideSel& guide, const int32_t* eos_ids, int n_eos, const float* logits,
-                                    int V, int ld, int rows, float* shaped, float* pval, int32_t* pidx) {
-    if (!spec_ok(sp, rows) || !spec_guide_ok(sp, guide, eos_ids, n_eos) || !logits || !shaped || !pval || !pidx || V != guide.V || ld < V)
+hipError_t launch_spec_shape_select(hipStream_t s, const SpecState& sp, const RowSel& rs, const StepState& st, const float* logits, int V, int ld, int rows,
+                                    float* pval, int32_t* pidx) {
+    if (!spec_ok(sp, rows) || !spec_shaped_sel(sp, rs) || !spec_row_sel_ok(sp, rs, V) || !logits || !pval || !pidx || V < 1 || ld < V || !st.out_lens ||
+        st.n_eos < 0 || st.n_eos > 16 || (st.n_eos && !st.eos_ids))
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(spec_guide_select_kernel, dim3(ARGMAX_CHUNKS, rows * sp.k), dim3(256), 0, s, logits, V, ld, rows, sp, guide, eos_ids, n_eos, shaped,
-                       pval, pidx);
+    hipLaunchKernelGGL(spec_shape_select_kernel, dim3(ARGMAX_CHUNKS, rows * sp.k), dim3(256), 0, s, logits, V, ld, rows, sp, rs, st, pval, pidx);
     return hipGetLastError();
 }
 
-hipError_t launch_spec_accept(hipStream_t s, const SpecState& sp, const StepState& st, int rows, const float* pval, const int32_t* pidx, const StopSel& stop,
-                              const GuideSel& guide) {
-    if (!spec_ok(sp, rows) || !pval || !pidx) return hipErrorInvalidValue;
-    if (stop.rows && (!stop.tok_off || !stop.tok_bytes)) return hipErrorInvalidValue;
-    if (guide.rows && (!sp.gstate || !guide.tok_off || !guide.tok_bytes)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(spec_accept_kernel, dim3(rows), dim3(64), 0, s, sp, st, rows, pval, pidx, stop, guide);
+hipError_t launch_spec_accept(hipStream_t s, const SpecState& sp, const StepState& st, int rows, int V, const float* pval, const int32_t* pidx,
+                              const RowSel& rs) {
+    if (!spec_ok(sp, rows) || !pval || !pidx || V < 1 || !spec_row_sel_ok(sp, rs, V)) return hipErrorInvalidValue;
+    if (rs.stop.rows && (!rs.stop.tok_off || !rs.stop.tok_bytes)) return hipErrorInvalidValue;
+    if (rs.guide.rows && (!sp.gstate || !rs.guide.tok_off || !rs.guide.tok_bytes)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(spec_accept_kernel, dim3(rows), dim3(64), 0, s, sp, st, rows, V, pval, pidx, rs);
     return hipGetLastError();
 }
 

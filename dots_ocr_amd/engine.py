@@ -401,6 +401,7 @@ def _prototypes(lib):
         "dots_set_speculation": (i32, [vp, i32, i32, i32]),
         "dots_set_speculation_rows": (i32, [vp, i32]),
         "dots_set_speculation_guided": (i32, [vp, i32]),
+        "dots_set_speculation_shaped": (i32, [vp, i32]),
         "dots_op_spec_guide_masks": (i32, [vp, i32, i32, P(i32), P(i32), P(i32), P(i32), P(i32), P(C.c_uint32)]),
         "dots_set_row_drafts": (i32, [vp, i32, P(i32), i32]),
         "dots_spec_stats": (i32, [vp, i32, P(i64), P(i64), P(i64)]),
@@ -438,7 +439,7 @@ EXPORTED_SYMBOLS = [
     "dots_op_select_tokens_guided", "dots_bench_select_tokens_guided",
     "dots_set_row_ngram", "dots_op_select_tokens_ngram", "dots_bench_select_tokens_ngram",
     "dots_set_speculation", "dots_set_speculation_rows", "dots_set_row_drafts", "dots_spec_stats", "dots_op_ngram_draft",
-    "dots_set_speculation_guided", "dots_op_spec_guide_masks",
+    "dots_set_speculation_guided", "dots_op_spec_guide_masks", "dots_set_speculation_shaped",
     "dots_slots_fork", "dots_slots_extend", "dots_slot_logits",
     "dots_slots_beam", "dots_beam_info", "dots_beam_read",
     "dots_stop_create", "dots_stop_destroy", "dots_set_row_stop", "dots_row_stop_hit",
@@ -495,6 +496,50 @@ def spec_rows_flags(value) -> int:
         else:
             raise ValueError(f"speculative_rows takes \"all\", \"greedy\" or names out of {sorted(SPEC_ROWS)}, got {value!r}")
     return flags
+
+
+SPEC_SHAPED = {"ngram": 1, "rules": 2, "penalties": 4}      # DOTS_SPEC_SHAPED_NGRAM / _RULES / _PENALTY
+
+
+def spec_shaped_flags(value) -> int:
+    """The DOTS_SPEC_SHAPED_* bits of a speculative_shaped setting: None, False or "" = 0, True or "all" = every bit, or names out of
+    "ngram", "rules" and "penalties" as a comma list, a tuple or a list.  ValueError on anything else."""
+    if value is None or value is False or value == "":
+        return 0
+    if value is True:
+        return sum(SPEC_SHAPED.values())
+    names = tuple(n.strip() for n in value.split(",")) if isinstance(value, str) else tuple(value)
+    flags = 0
+    for n in names:
+        if n == "all":
+            flags |= sum(SPEC_SHAPED.values())
+        elif isinstance(n, str) and n in SPEC_SHAPED:
+            flags |= SPEC_SHAPED[n]
+        else:
+            raise ValueError(f"speculative_shaped takes \"all\" or names out of {sorted(SPEC_SHAPED)}, got {value!r}")
+    return flags
+
+
+def draft_row_history(out, drafts, j: int) -> list:
+    """The history draft row j >= 1 of a speculating step is selected under ("Why a shaped row is exact"): the tokens the
+    row has generated followed by drafts 1 .. j, which the row takes as committed.  banned_ngram_ids(draft_row_history(out, drafts, j),
+    n, window, whitelist) is what ngram_ban_drafts_kernel must leave for that row."""
+    j = int(j)
+    if not 1 <= j <= len(drafts):
+        raise ValueError(f"draft row {j} of {len(drafts)} drafts")
+    return [int(t) for t in out] + [int(t) for t in drafts[:j]]
+
+
+def draft_row_counts(counts, drafts, j: int) -> dict:
+    """The output counts draft row j >= 1 is penalised with: counts (id -> occurrences in the row's output at the head of the step) plus the
+    occurrences among drafts 1 .. j.  The row's own counts are not touched: they move only when a token is committed."""
+    j = int(j)
+    if not 1 <= j <= len(drafts):
+        raise ValueError(f"draft row {j} of {len(drafts)} drafts")
+    c = {int(t): int(v) for t, v in dict(counts).items()}
+    for t in drafts[:j]:
+        c[int(t)] = c.get(int(t), 0) + 1
+    return c
 
 
 MAX_TOP_LOGPROBS = 20                        # DOTS_MAX_TOP_LOGPROBS: top entries kept per position
@@ -992,6 +1037,18 @@ class Engine:
         stop=True.  Only while no slot is occupied; the setting survives set_speculation."""
         self._ck(self.lib.dots_set_speculation_guided(self.h, 1 if on else 0), "dots_set_speculation_guided")
         self.spec_guided = bool(on)
+
+    spec_shaped = 0                          # Engine.set_speculation_shaped: the DOTS_SPEC_SHAPED_* bits, 0 until switched on
+
+    def set_speculation_shaped(self, ngram: bool = False, rules: bool = False, penalties: bool = False):
+        """Which rows whose logits are shaped verify drafts: ngram = rows with an NgramRule, rules = rows with LogitRules,
+        penalties = rows whose SamplingParams carry a repetition / frequency / presence penalty (such a row needs
+        set_speculation_rows(sampled=True) too, as any row with parameters).  Every draft row is selected under the history, the output
+        counts and the output index the sequential engine would hold there, and a rejected draft leaves nothing behind: the tokens are
+        those of the unspeculated engine.  Default: none.  Only while no slot is occupied; the setting survives set_speculation."""
+        flags = (SPEC_SHAPED["ngram"] if ngram else 0) | (SPEC_SHAPED["rules"] if rules else 0) | (SPEC_SHAPED["penalties"] if penalties else 0)
+        self._ck(self.lib.dots_set_speculation_shaped(self.h, flags), "dots_set_speculation_shaped")
+        self.spec_shaped = flags
 
     def spec_guide_masks_op(self, guides: Sequence[Optional[int]], states: Sequence[int], drafts: Sequence[Sequence[int]], n_live: Sequence[int], k: int):
         """The state chain and the draft-row mask kernels alone (dots_op_spec_guide_masks) for `rows` slots: guide handle (None = an

@@ -136,7 +136,7 @@ class DotsOcrHipForCausalLM:
                  guided_whitespace_pattern=None, no_repeat_ngram_size: Optional[int] = None, no_repeat_ngram_window: Optional[int] = None,
                  no_repeat_ngram_whitelist=None, speculative_ngram: Optional[int] = None, prompt_lookup_min: int = 2, prompt_lookup_max: int = 4,
                  num_return_sequences: int = 1, stop_strings=None, speculative_rows=None, num_beams: Optional[int] = None,
-                 length_penalty: float = 1.0, early_stopping=None, speculative_guided: bool = False, prompt_suffixes=None, **_):
+                 length_penalty: float = 1.0, early_stopping=None, speculative_guided: bool = False, prompt_suffixes=None, speculative_shaped=None, **_):
         """HF-shaped generate.  do_sample / temperature / top_p default to the checkpoint's generation_config.json (greedy when it
         is absent); with sampling on, tokens are drawn on the GPU from softmax(logits / temperature) restricted to the top_p
         nucleus, reproducibly from `seed`.  Returns LongTensor
@@ -174,12 +174,19 @@ class DotsOcrHipForCausalLM:
         token.  With "sampled" a sampled call (temperature > 0) without penalties speculates: every sequence is then drawn by the
         per-row sampler with seed + b (as a call with top_k is) instead of the engine-wide one, and its tokens are exactly those of the
         same call on an engine that does not speculate.  Sequences with penalties, logit rules or an n-gram rule run
-        unspeculated, and so do guided ones without speculative_guided.  The engine is left with the setting off.
+        unspeculated without speculative_shaped, and so do guided ones without speculative_guided.  The engine is left with the setting off.
 
         speculative_guided (with speculative_ngram; False = the above) lets a sequence that follows a guide verify drafts too
         (Engine.set_speculation_guided): every draft row is selected under the state its guide would hold there, so the tokens are
         again exactly those of the call without it.  A sampled guided call also needs speculative_rows "sampled", one with
         stop_strings "stop".  The engine is left with the setting off.
+
+        speculative_shaped (with speculative_ngram; None = the above) lets sequences whose logits are shaped verify drafts
+        (Engine.set_speculation_shaped): "ngram" (no_repeat_ngram_size), "rules" (logit_bias, allowed_token_ids, min_tokens,
+        stop_token_ids, ignore_eos), "penalties" (repetition / frequency / presence penalty; such a call also needs speculative_rows
+        "sampled"), a comma list or a tuple of them, or "all".  Every draft row is selected under the history, the output counts and
+        the output index the sequence would have there, so the tokens are again exactly those of the call without it.  The engine is
+        left with the setting off.
 
         stop_strings (HF's name: a str or a list of at most 16 str of at most 64 UTF-8 bytes) ends a sequence on the GPU at the token that
         completes one of them in its generated text (Engine.set_row_stop; with min_tokens, no match is taken below it).  The
@@ -327,6 +334,10 @@ class DotsOcrHipForCausalLM:
             raise ValueError("speculative_rows needs speculative_ngram")
         if speculative_guided and not spec_k:
             raise ValueError("speculative_guided needs speculative_ngram")
+        from .engine import SPEC_SHAPED, spec_shaped_flags
+        spec_shaped = spec_shaped_flags(speculative_shaped)
+        if spec_shaped and not spec_k:
+            raise ValueError("speculative_shaped needs speculative_ngram")
         if spec_k:
             if continuous is False:
                 raise ValueError("speculative_ngram runs on the continuous path: continuous=False cannot be combined with it")
@@ -346,6 +357,9 @@ class DotsOcrHipForCausalLM:
                 self.engine.set_speculation_rows(sampled=bool(spec_rows & SPEC_ROWS["sampled"]), stop=bool(spec_rows & SPEC_ROWS["stop"]))
             if speculative_guided:
                 self.engine.set_speculation_guided(True)
+            if spec_shaped:
+                self.engine.set_speculation_shaped(ngram=bool(spec_shaped & SPEC_SHAPED["ngram"]), rules=bool(spec_shaped & SPEC_SHAPED["rules"]),
+                                                   penalties=bool(spec_shaped & SPEC_SHAPED["penalties"]))
         try:
             return self._generate(input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens, eos_token_id, pad_token_id, continuous,
                                   row_sp, rules, guide, ngram, nrs, stop, int(min_tokens or 0), beam, suffixes)
@@ -358,6 +372,8 @@ class DotsOcrHipForCausalLM:
                         self.engine.set_speculation_rows()
                     if speculative_guided:
                         self.engine.set_speculation_guided(False)
+                    if spec_shaped:
+                        self.engine.set_speculation_shaped()
                 except Exception as e:               # the run's own error is the one to raise
                     import warnings
                     warnings.warn(f"speculation could not be switched off: {e}")

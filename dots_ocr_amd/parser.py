@@ -35,7 +35,7 @@ class DotsOCRParser:
                  max_pixels=None, use_hf=False, model_path="./weights/DotsOCR", model=None, processor=None,
                  hf_max_new_tokens=24000, guided=False, no_repeat_ngram_size=None, no_repeat_ngram_window=None,
                  no_repeat_ngram_whitelist=None, speculative_ngram=None, prompt_lookup_min=2, prompt_lookup_max=4, stop=None,
-                 speculative_rows=None, num_beams=None, length_penalty=1.0, speculative_guided=False):
+                 speculative_rows=None, num_beams=None, length_penalty=1.0, speculative_guided=False, speculative_shaped=None):
         self.dpi = dpi
         # beam search, opt-in: every page is decoded by a group of num_beams beams and its best hypothesis returned (the
         # server request carries use_beam_search with temperature 0, the in-process model generates with num_beams).  It combines with
@@ -65,6 +65,12 @@ class DotsOCRParser:
         if speculative_guided and not self.speculative_ngram:
             raise ValueError("speculative_guided needs speculative_ngram")
         self.speculative_guided = bool(speculative_guided)
+        # which sequences whose logits are shaped verify drafts (generate(speculative_shaped=): "ngram", "rules", "penalties", a comma list,
+        # a tuple, "all"; Engine.set_speculation_shaped); None = none.  A server decides by its own --speculative-shaped flag.
+        from .engine import spec_shaped_flags
+        if spec_shaped_flags(speculative_shaped) and not self.speculative_ngram:
+            raise ValueError("speculative_shaped needs speculative_ngram")
+        self.speculative_shaped = speculative_shaped if spec_shaped_flags(speculative_shaped) else None
         # no-repeat n-gram blocking, opt-in: the server request carries the three fields, the in-process model generates
         # with them.  With the default None the request and the call are exactly what they were.
         self.no_repeat_ngram_size = no_repeat_ngram_size
@@ -129,6 +135,8 @@ class DotsOCRParser:
                 kw["speculative_rows"] = self.speculative_rows
             if self.speculative_guided:
                 kw["speculative_guided"] = True
+            if self.speculative_shaped is not None:
+                kw["speculative_shaped"] = self.speculative_shaped
         if self._guided_layout(prompts):
             from .guided import layout_schema
             if getattr(self.model.engine, "token_bytes", None) is None:

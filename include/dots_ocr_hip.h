@@ -355,8 +355,15 @@ int dots_row_stop_hit(DotsEngine* e, int row, int32_t* out);
  * commits are those of the sequential step, so the tokens are again EXACTLY those of the unspeculated engine.  A draft the guide could not
  * have committed at its position (no bytes, an EOS id, a byte without a transition) verifies nothing from there on.  A row speculates iff
  * every feature it carries is let through: a guided row with DotsSamplingParams also needs DOTS_SPEC_ROWS_SAMPLED, one with stop strings
- * DOTS_SPEC_ROWS_STOP.  Rows with penalties, logit rules, an n-gram rule or logprobs, and every row under an engine-wide temperature,
- * never speculate.
+ * DOTS_SPEC_ROWS_STOP.
+ *
+ * dots_set_speculation_shaped closes the set: DOTS_SPEC_SHAPED_NGRAM lets a row with an n-gram rule speculate, DOTS_SPEC_SHAPED_RULES a
+ * row with DotsLogitRules, DOTS_SPEC_SHAPED_PENALTY a row whose DotsSamplingParams carry a penalty (it needs DOTS_SPEC_ROWS_SAMPLED too,
+ * as any row with parameters).  Draft row j is selected under the hypothesis that drafts 1 .. j were committed, and under it everything
+ * that shapes the selection is known at the head of the step: the history the n-gram rule reads is the output followed by those drafts,
+ * the output counts are the row's counts plus their occurrences, the output index min_tokens is compared with is tokens generated + j.
+ * The counts change only when a token is committed, so a rejected draft leaves nothing behind, and the tokens are again EXACTLY those of
+ * the unspeculated engine.  Rows with logprobs, and every row under an engine-wide temperature, never speculate.
  *
  * The built-in drafter looks the row's last tokens up in the row's OWN output (the prompt is not searched: image pads and a short
  * instruction).  With out[0 .. L) the tokens generated so far, for n from max_n down to min_n with n + 1 <= L: key = out[L - n .. L);
@@ -375,6 +382,10 @@ int dots_row_stop_hit(DotsEngine* e, int row, int32_t* out);
  *                       exactly what it launched before.  A call of its own, not a bit of dots_set_speculation_rows.  The setting
  *                       survives dots_set_speculation calls.  Allowed only while no slot is occupied (DOTS_E_STATE); a change drops the
  *                       captured steps.  The first call that switches it on allocates one int32 per step row.
+ * dots_set_speculation_shaped  flags: DOTS_SPEC_SHAPED_NGRAM | DOTS_SPEC_SHAPED_RULES | DOTS_SPEC_SHAPED_PENALTY; 0 (the default): such rows
+ *                       never verify a draft, and a step launches exactly what it launched before.  A call of its own, not bits of
+ *                       dots_set_speculation_rows.  The setting survives dots_set_speculation calls.  Allowed only while no slot is
+ *                       occupied (DOTS_E_STATE); unknown bits: DOTS_E_INVALID; a change drops the captured steps.  Allocates nothing.
  * dots_set_row_drafts   the n <= k drafts slot `row` verifies in its NEXT step, replacing what the drafter left (stream ordered; they are
  *                       spent by that step).  DOTS_E_INVALID: n > k or an id outside [0, vocab); DOTS_E_STATE: the slot is not occupied.
  *                       A row that does not speculate ignores them.
@@ -383,9 +394,13 @@ int dots_row_stop_hit(DotsEngine* e, int row, int32_t* out);
 #define DOTS_MAX_SPEC_DRAFTS 15
 #define DOTS_SPEC_ROWS_SAMPLED 1
 #define DOTS_SPEC_ROWS_STOP 2
+#define DOTS_SPEC_SHAPED_NGRAM 1
+#define DOTS_SPEC_SHAPED_RULES 2
+#define DOTS_SPEC_SHAPED_PENALTY 4
 int dots_set_speculation(DotsEngine* e, int k, int min_n, int max_n);
 int dots_set_speculation_rows(DotsEngine* e, int flags);
 int dots_set_speculation_guided(DotsEngine* e, int on);
+int dots_set_speculation_shaped(DotsEngine* e, int flags);
 int dots_set_row_drafts(DotsEngine* e, int row, const int32_t* ids_host, int n);
 int dots_spec_stats(DotsEngine* e, int row, int64_t* steps, int64_t* drafted, int64_t* accepted);
 

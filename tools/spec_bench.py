@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """What a speculating decode step costs and what it has to accept to pay (profiles/spec_ngram.txt).
 
-    python tools/spec_bench.py [--slots 1 8] [--k 0 1 3 7] [--steps 64] [--repeats 3] [--prompt 512] [--sampled | --guided]
+    python tools/spec_bench.py [--slots 1 8] [--k 0 1 3 7] [--steps 64] [--repeats 3] [--prompt 512] [--sampled | --guided | --shaped]
 
 Full-size language model with seeded random weights (the vision tower, which no text-only prompt touches, is cut to one block so that the
 weights are made quickly), one engine of 64 rows.  Per slot count: the reference tokens come from an unspeculated run; then for every
@@ -31,6 +31,12 @@ draft rows idle) and guided_on.  A wrong draft is then a token the guide ALLOWS 
 with a transition), so that at acceptance 0 the draft rows are alive and pay the chain, the mask and the shaped arg max; `alive` is the
 share of planted drafts the guide could have committed.  break_even of a guided_on row = its cost / the k = 0 cost of guided_off - 1.
 
+--shaped (profiles/spec_shaped.txt; run it with --slots 1 2 4 8 --k 0 1 3 7) gives every row an n-gram rule (size 6, window 256), logit
+rules (a bias on 16 ids, min_tokens past the run) and greedy parameters with a repetition, frequency and presence penalty, and runs the
+legs twice on one build: shaped_off (Engine.set_speculation_shaped(): the rows verify nothing, their draft rows idle) and shaped_on (all
+three bits, with set_speculation_rows(sampled=True) for the parameters).  A live draft row then pays the draft rows' ban kernel and the
+shaped selection.  break_even of a shaped_on row = its cost / the k = 0 cost of shaped_off - 1.
+
 One JSON line per measurement on stdout, then a table.
 """
 import argparse
@@ -55,10 +61,11 @@ def main():
     ap.add_argument("--prompt", type=int, default=512)
     ap.add_argument("--sampled", action="store_true", help="also run sampled speculating rows (2-read and 4-read parameter sets) beside the greedy leg")
     ap.add_argument("--guided", action="store_true", help="every row holds the layout guide: the legs with Engine.set_speculation_guided off and on")
+    ap.add_argument("--shaped", action="store_true", help="every row carries an n-gram rule, logit rules and penalties: the legs with Engine.set_speculation_shaped off and on")
     ap.add_argument("--tiny", action="store_true", help="the small-dims model instead of the full-size one (a plumbing check, not a measurement)")
     a = ap.parse_args()
     from dots_ocr_amd.config import DotsConfig
-    from dots_ocr_amd.engine import Engine, SamplingParams
+    from dots_ocr_amd.engine import Engine, LogitRules, NgramRule, SamplingParams
     from dots_ocr_amd.weights import random_state_dict
     if a.tiny:
         cfg = DotsConfig.tiny(layers=3, v_layers=1)
@@ -89,6 +96,10 @@ def main():
         eng.set_token_bytes(tb)
         handle = eng.create_guide(guide)
         legs = [("guided_off", None), ("guided_on", None)]
+    if a.shaped:
+        if a.sampled or a.guided:
+            raise SystemExit("--shaped, --guided and --sampled are separate measurements")
+        legs = [("shaped_off", None), ("shaped_on", None)]
     alive = [0, 0]                                                   # planted drafts the guide could have committed / all planted (--guided)
 
     def guided_drafts(Tb, pos, k, true_drafts):
@@ -128,14 +139,22 @@ def main():
               if a.guided:
                   for b in slots:
                       eng.set_row_guide(b, handle)
+              if a.shaped:
+                  for b in slots:
+                      eng.set_row_sampling(b, SamplingParams(temperature=0.0, repetition_penalty=1.05, frequency_penalty=0.1, presence_penalty=0.1))
+                      eng.set_row_logit_rules(b, LogitRules(bias={1000 + 7 * i + b: 0.5 for i in range(16)}, min_tokens=n_tok + 1, vocab_size=cfg.vocab_size))
+                      eng.set_row_ngram(b, NgramRule(6, 256))
 
           def run(k, true_drafts, T=None):
               """`steps` steps with k drafts per slot of which the first true_drafts are right: (seconds, tokens committed, token lists)"""
               eng.slots_reset()
               eng.set_speculation(k, 2, 0)
-              eng.set_speculation_rows(sampled=a.sampled)
+              eng.set_speculation_rows(sampled=a.sampled or a.shaped)
               if a.guided:
                   eng.set_speculation_guided(leg == "guided_on")
+              if a.shaped:
+                  on = leg == "shaped_on"
+                  eng.set_speculation_shaped(ngram=on, rules=on, penalties=on)
               set_rows()
               eng.slots_prefill(slots, np.concatenate(prompts[:S]), [a.prompt] * S, [n_tok] * S)
               eng.slots_decode(1)                                       # the captured step exists before the clock starts
@@ -143,7 +162,8 @@ def main():
               _, lens = eng.slots_poll()
               start = [int(lens[b]) for b in slots]
               pos = list(start)
-              gain = [[1 + (min(true_drafts, k) if k else 0)] * S for _ in range(a.steps)]      # tokens a step commits per slot
+              verifies = leg != "shaped_off"                            # shaped_off rows verify nothing
+              gain = [[1 + (min(true_drafts, k) if k and verifies else 0)] * S for _ in range(a.steps)]      # tokens a step commits per slot
               plan = None
               if a.guided and k:                                         # the automaton walks stay outside the clock
                   plan, at = [], list(start)
@@ -204,7 +224,7 @@ def main():
     print()
     print(f"{'leg':>14} {'slots':>5} {'k':>2} {'rows':>4} {'accept':>6} {'ms/step':>9} {'tok/step/slot':>13} {'tokens/s':>10} {'break-even accepted/step':>25}")
     for (leg, S, k, name), r in results.items():
-        base = results.get(("guided_off" if a.guided else leg, S, 0, "-"))
+        base = results.get(("guided_off" if a.guided else "shaped_off" if a.shaped else leg, S, 0, "-"))
         be = ""
         if k and name == "0" and base:
             be = f"{r['ms_per_step'] / base['ms_per_step'] - 1:.3f}"
