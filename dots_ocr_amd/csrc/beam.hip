@@ -326,6 +326,7 @@ int dots_slots_beam(DotsEngine* e, int src_slot, const int32_t* dst_slots, int n
         if (d < 0 || d >= mb) return e->fail(DOTS_E_INVALID, "slot %d out of range [0, %d)", d, mb);
         if (d == src_slot) return e->fail(DOTS_E_INVALID, "slot %d is the source of the group", d);
         if (e->slot_active[d]) return e->fail(DOTS_E_STATE, "slot %d is occupied", d);
+        if (slot_filling(e, d)) return e->fail(DOTS_E_STATE, "slot %d is filling", d);
         for (int a = 0; a < i; ++a)
             if (dst_slots[a] == d) return e->fail(DOTS_E_INVALID, "slot %d listed twice", d);
     }

@@ -280,6 +280,28 @@ struct DotsEngine {
     int32_t *ex_tokens = nullptr, *ex_ctx = nullptr, *ex_table = nullptr, *ex_stage = nullptr;
     size_t ex_stage_cap = 0;
     bf16_t* ex_h = nullptr;
+    // chunked prefill (dots_slots_prefill_begin / dots_slots_prefill_advance).  fill[slot]: the record of a FILLING slot — not
+    // occupied yet (slot_active == 0), so every step treats its row as a free one: context 0, and the DEVICE block-table row stays on the
+    // scratch page until the fill completes, while hp_table and fill_table (the table the passes read) name its pages.  src: the prompt as
+    // launch_embed_gather reads it; seen: its prompt-presence bits, accumulated pass by pass on the host; order: begin order (FIFO).
+    // Allocated by the first begin: fill_x, the embedded prompts ([(n_pool_pages) * 64][hidden], position p of a slot at row page * 64 +
+    // p % 64 of its own KV page — the pool's allocator is the staging buffer's), and the lists of a pass (staging rows, work items)
+    struct Fill {
+        bool on = false;
+        int L = 0, max_new = 0, cursor = 0;
+        uint64_t order = 0;
+        std::vector<int32_t> src;
+        std::vector<uint32_t> seen;
+    };
+    Fill fill[DOTS_MAX_BATCH];
+    int n_filling = 0;
+    uint64_t fill_order = 0;
+    bf16_t* fill_x = nullptr;
+    int32_t *fill_rows = nullptr, *fill_table = nullptr;
+    PagedQBlock* fill_items = nullptr;
+    std::vector<int32_t> hp_rows;
+    std::vector<PagedQBlock> hp_items;
+    bool fresh_chunked = false;            // fresh_slots were completed by a pass: p_src holds that pass only (dots_slots_fork copies the source's presence bits)
     // captured decode steps, keyed by everything the capture bakes in: rows, KV splits, static batch (out_cap = row stride of
     // the output buffer) or slot mode (out_cap = 0), number of EOS ids, whether any row carries its own parameters (rowp: the per-row
     // selection stage), whether any row returns logprobs (lp), whether any row carries logit rules (rules: the stage then gets their
@@ -408,6 +430,11 @@ void drop_step_graphs(DotsEngine* e);
 int chain_streams(DotsEngine* e, hipStream_t from, hipStream_t to);
 int pick_decode_stream(DotsEngine* e, hipStream_t* cur);
 int prefill(DotsEngine* e, const int32_t* ids, const int32_t* lens, int B, const int32_t* slots = nullptr, const int32_t* max_new = nullptr);
+// chunked prefill: a filling slot holds pages and staged rows but is not occupied
+int prefill_begin(DotsEngine* e, const int32_t* ids, const int32_t* lens, int B, const int32_t* slots, const int32_t* max_new);
+int prefill_advance(DotsEngine* e, int max_tokens, int32_t* remaining);
+inline bool slot_filling(const DotsEngine* e, int slot) { return slot >= 0 && slot < DOTS_MAX_BATCH && e->fill[slot].on; }
+void drop_fill(DotsEngine* e, int slot);      // the record only: the pages go with release_pages
 int decode_layers(DotsEngine* e, const int32_t* tokens, const int32_t* ctx_len, const int32_t* block_table, int B, int n_splits, int part, bool* pend,
                   const float** pend_scale);
 int decode_step_launches(DotsEngine* e, int n_splits, int part = 0);

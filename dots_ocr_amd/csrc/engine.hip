@@ -368,6 +368,7 @@ int prefill(DotsEngine* e, const int32_t* ids, const int32_t* lens, int B, const
                 return e->fail(DOTS_E_CAPACITY, "slot %d is not usable while speculating: with %d drafts a slot takes %d rows of a step, so only slots [0, max_batch / (k + 1)) = [0, %d) are",
                                S[b], e->spec_k, e->spec_k + 1, c.max_batch / (e->spec_k + 1));
             if (e->slot_mode && e->slot_active[S[b]]) return e->fail(DOTS_E_STATE, "slot %d is occupied", S[b]);
+            if (e->slot_mode && slot_filling(e, S[b])) return e->fail(DOTS_E_STATE, "slot %d is filling (dots_slots_prefill_begin)", S[b]);
             for (int a = 0; a < b; ++a)
                 if (S[a] == S[b]) return e->fail(DOTS_E_INVALID, "slot %d listed twice", S[b]);
             if (max_new[b] < 1 || lens[b] + max_new[b] > c.max_seq_len)
@@ -501,6 +502,7 @@ int prefill(DotsEngine* e, const int32_t* ids, const int32_t* lens, int B, const
         e->sel_dirty = true;
         e->B = 0;                                          // the static-batch entry points need a static prefill first
         e->fresh_slots = S;                                // these sequences may be forked until the next step (dots_slots_fork)
+        e->fresh_chunked = false;
     } else {
         e->B = B;
         e->h_prompt_lens = L;
@@ -515,6 +517,266 @@ int prefill(DotsEngine* e, const int32_t* ids, const int32_t* lens, int B, const
     for (int b = 0; b < B; ++b) pf += 2.0 * lin * L[b] + (double)c.num_layers * 2.0 * L[b] * (double)L[b] * Nq + 2.0 * (double)c.vocab_size * H;
     e->stats.prefill_flops = pf;
     return DOTS_OK;
+}
+
+// ---- chunked prefill: the same prompts filled in passes of at most max_tokens positions over their own KV pages.
+// begin: validates as prefill() does — except that the packed length is bounded by the pool only, not by the workspace — reserves the
+// pages, embeds every prompt whole into the staging buffer (the tower's rows are consumed here) and leaves the slots FILLING.
+int prefill_begin(DotsEngine* e, const int32_t* ids, const int32_t* lens, int B, const int32_t* slots, const int32_t* max_new) {
+    const DotsConfig& c = e->cfg;
+    hipStream_t s = e->stream;
+    const int H = c.hidden_size;
+    if (e->spec_k) return e->fail(DOTS_E_STATE, "a chunked prefill cannot begin while the engine speculates (dots_set_speculation), as a slot cannot be extended or suspended then");
+    if (e->TP < 64) return e->fail(DOTS_E_CAPACITY, "a chunked prefill needs max_prefill_tokens >= 64, it is %lld", (long long)e->TP);
+    if (B < 1 || B > c.max_batch) return e->fail(DOTS_E_CAPACITY, "batch %d exceeds max_batch %d", B, c.max_batch);
+    std::vector<int> L(B), S(B);
+    int64_t T = 0;
+    for (int b = 0; b < B; ++b) {
+        if (lens[b] < 1 || lens[b] >= c.max_seq_len) return e->fail(DOTS_E_CAPACITY, "prompt %d length %d not in [1, max_seq_len)", b, lens[b]);
+        L[b] = lens[b];
+        T += lens[b];
+        S[b] = slots[b];
+        if (S[b] < 0 || S[b] >= c.max_batch) return e->fail(DOTS_E_INVALID, "slot %d out of range [0, %d)", S[b], c.max_batch);
+        if (e->slot_mode && e->slot_active[S[b]]) return e->fail(DOTS_E_STATE, "slot %d is occupied", S[b]);
+        if (e->slot_mode && slot_filling(e, S[b])) return e->fail(DOTS_E_STATE, "slot %d is filling", S[b]);
+        for (int a = 0; a < b; ++a)
+            if (S[a] == S[b]) return e->fail(DOTS_E_INVALID, "slot %d listed twice", S[b]);
+        if (max_new[b] < 1 || lens[b] + max_new[b] > c.max_seq_len)
+            return e->fail(DOTS_E_CAPACITY, "slot %d: prompt (%d) + max_new_tokens (%d) exceeds max_seq_len %d", S[b], lens[b], max_new[b], c.max_seq_len);
+    }
+    std::vector<std::vector<int32_t>> src(B);
+    int64_t t = 0, vis_used = 0;
+    for (int b = 0; b < B; ++b) {
+        src[b].resize(L[b]);
+        for (int i = 0; i < L[b]; ++i, ++t) {
+            const int id = ids[t];
+            if (id == c.image_token_id) src[b][i] = -(int32_t)(++vis_used);
+            else if (id < 0 || id >= c.vocab_size) return e->fail(DOTS_E_INVALID, "token id %d out of range", id);
+            else src[b][i] = id;
+        }
+    }
+    if (vis_used != (vis_used ? e->vis_rows : 0))
+        return e->fail(DOTS_E_STATE, "prompt has %lld image tokens but the vision tower produced %lld rows", (long long)vis_used, (long long)e->vis_rows);
+    if (!e->slot_mode) {                                   // entering slot mode, as a slot prefill does: every slot free, every page in the pool
+        for (int b = 0; b < (int)e->slot_pages.size(); ++b) release_pages(e, b);
+        RET(beam_clear_all(e));
+        CK(hipMemcpyAsync(e->block_table, e->hp_table.data(), e->hp_table.size() * 4, hipMemcpyHostToDevice, s));
+        std::fill(e->slot_active, e->slot_active + DOTS_MAX_BATCH, 0);
+        CK(hipMemsetAsync(e->ctx_len, 0, c.max_batch * 4, s));
+        e->slot_mode = true;
+        e->B = 0;
+    }
+    int need = 0;
+    for (int b = 0; b < B; ++b) need += (admit_tokens(e, L[b], max_new[b]) + 63) / 64;
+    if (need > (int)e->free_pages.size())
+        return e->fail(DOTS_E_CAPACITY, "KV pool exhausted: these sequences need %d pages of 64 tokens, %d of %d are free", need, (int)e->free_pages.size(), e->n_pool_pages);
+    // the buffers of the feature, once: nothing of the slots has changed if one cannot be had
+    if (!e->fill_x) CK(e->alloc(&e->fill_x, (size_t)e->n_pool_pages * 64 * H));
+    if (!e->fill_rows) CK(e->alloc(&e->fill_rows, (size_t)e->TP));
+    if (!e->fill_table) CK(e->alloc(&e->fill_table, (size_t)DOTS_MAX_BATCH * e->max_pages));
+    if (!e->fill_items) CK(e->alloc(&e->fill_items, (size_t)(e->TP / 64 + c.max_batch + 1)));
+    for (int b = 0; b < B; ++b) reserve_pages(e, S[b], admit_tokens(e, L[b], max_new[b]));      // cannot fall short: counted above
+    struct Guard {
+        DotsEngine* e; const std::vector<int>& S; bool armed = true;
+        ~Guard() {
+            if (!armed) return;
+            for (int sl : S) release_pages(e, sl);
+        }
+    } guard{e, S};
+    // the device table row of a filling slot stays on the scratch page (a decode step runs its row as a free one); the passes read fill_table
+    for (int b = 0; b < B; ++b)
+        CK(hipMemcpyAsync(e->fill_table + (size_t)S[b] * e->max_pages, e->hp_table.data() + (size_t)S[b] * e->max_pages, (size_t)e->max_pages * 4, hipMemcpyHostToDevice, s));
+    // ---- embed every prompt whole, through the workspace in pieces of at most TP rows, into the rows of its own pages
+    const int piece = (int)e->TP;
+    e->hp_pos.resize(piece); e->hp_src.resize(piece); e->hp_rows.resize(piece);
+    for (int b = 0; b < B; ++b) {
+        const auto& pages = e->slot_pages[S[b]];
+        for (int p0 = 0; p0 < L[b]; p0 += piece) {
+            const int n = std::min(piece, L[b] - p0);
+            for (int i = 0; i < n; ++i) {
+                e->hp_pos[i] = i;
+                e->hp_src[i] = src[b][p0 + i];
+                e->hp_rows[i] = pages[(p0 + i) / 64] * 64 + (p0 + i) % 64;
+            }
+            CK(hipMemcpyAsync(e->p_src, e->hp_src.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+            CK(hipMemcpyAsync(e->p_pos, e->hp_pos.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+            CK(hipMemcpyAsync(e->fill_rows, e->hp_rows.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+            CK(launch_embed_gather(s, e->p_src, e->embed, e->vis, e->p_x, n, H));
+            CK(launch_gather_rows(s, e->p_x, e->p_pos, e->fill_rows, e->fill_x, n, H));
+            CK(hipStreamSynchronize(s));                   // the host lists are reused by the next piece
+        }
+    }
+    e->fresh_slots.clear();                                // p_src and p_x were overwritten (dots_slots_fork)
+    const int W = (c.vocab_size + 31) / 32;
+    for (int b = 0; b < B; ++b) {
+        DotsEngine::Fill& f = e->fill[S[b]];
+        f.on = true;
+        f.L = L[b]; f.max_new = max_new[b]; f.cursor = 0;
+        f.order = ++e->fill_order;
+        f.src = std::move(src[b]);
+        f.seen.assign(W, 0u);
+        e->n_filling += 1;
+    }
+    guard.armed = false;
+    e->vis_rows = 0;                                       // the tower's rows are in the staging buffer: `vis` is free again
+    if (e->pref_deferred) RET(launch_prefetched_tower(e));
+    return DOTS_OK;
+}
+
+// advance: one pass of prefill()'s layer loop over up to max_tokens positions of the filling slots, oldest begin first; every cut falls on
+// a multiple of 64 positions of its sequence or at its end.  Attention reads the pages (launch_flash_attn_paged), the page just written
+// included, in the first pass of a prompt too — so what a position computes does not depend on where the cuts fall.
+int prefill_advance(DotsEngine* e, int max_tokens, int32_t* remaining) {
+    const DotsConfig& c = e->cfg;
+    hipStream_t s = e->stream;
+    const int H = c.hidden_size, Hq = c.num_heads, Hkv = c.num_kv_heads, Nq = Hq * 128, V = c.vocab_size;
+    if (max_tokens < 64 || max_tokens % 64 || max_tokens > e->TP)
+        return e->fail(DOTS_E_INVALID, "max_tokens must be a positive multiple of 64 and at most max_prefill_tokens (%lld), got %d", (long long)e->TP, max_tokens);
+    auto left = [&] {
+        int64_t r = 0;
+        for (int b = 0; b < c.max_batch; ++b)
+            if (e->fill[b].on) r += e->fill[b].L - e->fill[b].cursor;
+        return (int32_t)std::min<int64_t>(r, INT32_MAX);
+    };
+    if (!e->slot_mode || !e->n_filling) { *remaining = 0; return DOTS_OK; }
+    // ---- what this pass takes
+    std::vector<int> order;
+    for (int b = 0; b < c.max_batch; ++b)
+        if (e->fill[b].on) order.push_back(b);
+    std::sort(order.begin(), order.end(), [&](int a, int b) { return e->fill[a].order < e->fill[b].order; });
+    struct Part { int slot, take, tok0; bool done; };
+    std::vector<Part> parts;
+    int T = 0;
+    for (int b : order) {
+        const DotsEngine::Fill& f = e->fill[b];
+        int take = std::min(f.L - f.cursor, max_tokens - T);
+        if (take < f.L - f.cursor) take = take / 64 * 64;
+        if (take <= 0) break;                              // FIFO: a later fill does not overtake
+        parts.push_back(Part{b, take, T, f.cursor + take == f.L});
+        T += take;
+    }
+    e->hp_pos.resize(T); e->hp_src.resize(T); e->hp_rows.resize(T); e->hp_last.assign(DOTS_MAX_BATCH, 0);
+    e->hp_tiles.clear(); e->hp_items.clear();
+    std::vector<int32_t> done_slots;
+    int32_t sel_new[DOTS_MAX_BATCH] = {0};
+    int pad0 = 0, rows = 0;
+    for (const Part& p : parts) {
+        const DotsEngine::Fill& f = e->fill[p.slot];
+        const auto& pages = e->slot_pages[p.slot];
+        for (int i = 0; i < p.take; ++i) {
+            const int pos = f.cursor + i;
+            e->hp_pos[p.tok0 + i] = pos;
+            e->hp_src[p.tok0 + i] = f.src[pos];
+            e->hp_rows[p.tok0 + i] = pages[pos / 64] * 64 + pos % 64;
+        }
+        for (int r = 0; r < p.take; r += 64) {
+            const int n = std::min(64, p.take - r);
+            e->hp_tiles.push_back(Tile64{p.tok0 + r, n, pad0 + r, p.slot, (f.cursor + r) / 64, 0});
+            e->hp_items.push_back(PagedQBlock{p.tok0 + r, n, f.cursor + r, p.slot});
+        }
+        pad0 += (int)round_up(p.take, 64);
+        if (p.done) {
+            e->hp_last[done_slots.size()] = p.tok0 + p.take - 1;
+            done_slots.push_back(p.slot);
+            sel_new[p.slot] = 1;
+            rows = std::max(rows, p.slot + 1);
+        }
+    }
+    const int64_t Tpad = pad0;
+    const int n_tiles = (int)e->hp_tiles.size(), n_done = (int)done_slots.size();
+    e->fresh_slots.clear();                                // the workspace (and, with a completed slot, the logits) are about to be overwritten
+    CK(hipMemcpyAsync(e->p_pos, e->hp_pos.data(), (size_t)T * 4, hipMemcpyHostToDevice, s));
+    CK(hipMemcpyAsync(e->p_src, e->hp_src.data(), (size_t)T * 4, hipMemcpyHostToDevice, s));
+    CK(hipMemcpyAsync(e->fill_rows, e->hp_rows.data(), (size_t)T * 4, hipMemcpyHostToDevice, s));
+    CK(hipMemcpyAsync(e->p_tiles, e->hp_tiles.data(), (size_t)n_tiles * sizeof(Tile64), hipMemcpyHostToDevice, s));
+    CK(hipMemcpyAsync(e->fill_items, e->hp_items.data(), (size_t)n_tiles * sizeof(PagedQBlock), hipMemcpyHostToDevice, s));
+    CK(hipEventRecord(e->ev[2], s));
+    CK(launch_gather_rows(s, e->fill_x, e->fill_rows, nullptr, e->p_x, T, H));
+    CK(launch_rope_table(s, e->p_pos, e->lm_inv_freq, e->p_cs, T, 0));
+    const float scale = 1.0f / sqrtf(128.0f);
+    for (int i = 0; i < c.num_layers; ++i) {
+        const LLayer& Lw = e->ll[i];
+        bf16_t* pool_l = e->pool + e->pool_layer_elems * i;
+        CK(launch_rmsnorm(s, e->p_x, Lw.ln1, e->p_xn, T, H, c.rms_norm_eps));
+        RET(qkv_rope_on(e, s, e->act_q, e->act_s, e->p_xn, Lw.qkv_w, Lw.qkv_8, Lw.qkv_s, Lw.qkv_b, e->p_qkv, e->p_cs, e->p_tiles, n_tiles, e->p_q, e->p_k, e->p_vt, T, Tpad, H, Hq, Hkv));
+        CK(launch_kv_to_pages(s, e->p_k, e->p_qkv, e->p_tiles, n_tiles, e->fill_table, e->max_pages, pool_l, T, Hq, Hkv, layer_kv_scales(e, i)));
+        CK(launch_flash_attn_paged(s, e->p_q, pool_l, e->fill_table, e->max_pages, c.max_batch, e->hp_items.data(), e->fill_items, n_tiles, e->p_att, T, Hq, Hkv, scale,
+                                   layer_kv_scales(e, i)));
+        RET(dense(e, e->p_att, Lw.o_w, Lw.o_8, Lw.o_s, nullptr, e->p_x, e->p_x, T, H, Nq, H, EPI_RESIDUAL));
+        CK(launch_rmsnorm(s, e->p_x, Lw.ln2, e->p_xn, T, H, c.rms_norm_eps));
+        RET(dense(e, e->p_xn, Lw.w13, Lw.w13_8, Lw.w13_s, nullptr, nullptr, e->p_act, T, 2 * c.intermediate_size, H, c.intermediate_size, EPI_SWIGLU));
+        RET(dense(e, e->p_act, Lw.down_w, Lw.down_8, Lw.down_s, nullptr, e->p_x, e->p_x, T, H, c.intermediate_size, H, EPI_RESIDUAL));
+    }
+    // the pass has been issued: the cursors move and the presence bits of its tokens are accumulated
+    for (const Part& p : parts) {
+        DotsEngine::Fill& f = e->fill[p.slot];
+        for (int i = 0; i < p.take; ++i) {
+            const int id = f.src[f.cursor + i] >= 0 ? f.src[f.cursor + i] : c.image_token_id;
+            if (id >= 0 && id < V) f.seen[id >> 5] |= 1u << (id & 31);
+        }
+        f.cursor += p.take;
+    }
+    if (n_done) {
+        // ---- the slots whose last prompt token is in this pass complete exactly as at the end of prefill()
+        const int W = (V + 31) / 32;
+        for (int j = 0; j < n_done; ++j) {
+            const int b = done_slots[j];
+            const DotsEngine::Fill& f = e->fill[b];
+            CK(upload_table_row(e, b));                    // the row becomes a live one: its pages, its context
+            CK(hipMemcpyAsync(e->ctx_len + b, &f.L, 4, hipMemcpyHostToDevice, s));
+            CK(hipMemcpyAsync(e->d_max_len + b, &f.max_new, 4, hipMemcpyHostToDevice, s));
+            CK(hipMemsetAsync(e->out_lens + b, 0, 4, s));
+            CK(hipMemsetAsync(e->finished + b, 0, 4, s));
+            if (e->sp_ndraft) {
+                CK(hipMemsetAsync(e->sp_ndraft + b, 0, 4, s));
+                CK(hipMemsetAsync(e->sp_stats + (size_t)b * 3, 0, 3 * sizeof(unsigned long long), s));
+            }
+            if (e->pen_cnt) {                              // the one-shot image: the prompt's presence bits, no generated token counted
+                CK(hipMemsetAsync(e->pen_cnt + (size_t)b * V, 0, (size_t)V * 4, s));
+                CK(hipMemcpyAsync(e->pen_seen + (size_t)b * W, f.seen.data(), (size_t)W * 4, hipMemcpyHostToDevice, s));
+            }
+            RET(clear_lp_row(e, b));
+        }
+        CK(hipMemcpyAsync(e->d_sel_new, sel_new, DOTS_MAX_BATCH * 4, hipMemcpyHostToDevice, s));
+        CK(hipMemcpyAsync(e->p_dst, done_slots.data(), (size_t)n_done * 4, hipMemcpyHostToDevice, s));
+        CK(hipMemcpyAsync(e->p_last, e->hp_last.data(), DOTS_MAX_BATCH * 4, hipMemcpyHostToDevice, s));
+        if (e->stage.rows(ROW_GUIDE) > 0) CK(launch_guide_reset_rows(s, e->d_guides, e->p_dst, n_done));
+        if (e->stage.rows(ROW_STOP) > 0) CK(launch_stop_reset_rows(s, e->d_stop, e->p_dst, n_done));
+        CK(launch_gather_rows(s, e->p_x, e->p_last, e->p_dst, e->d_h, n_done, H));
+        CK(launch_dec_lmhead(s, e->d_h, e->final_norm, e->lm_head_d, e->lm_head_s, e->d_logits, rows, H, V, c.rms_norm_eps));
+        e->B_sel = rows;
+        e->sel_now = e->d_sel_new;
+        RET(select_tokens(e, 0));
+    }
+    CK(hipEventRecord(e->ev[3], s));
+    CK(hipStreamSynchronize(s));                           // the host lists and the records' scalars were read by asynchronous copies
+    for (int b : done_slots) {
+        const DotsEngine::Fill& f = e->fill[b];
+        e->slot_active[b] = 1;
+        e->slot_limit[b] = f.L + f.max_new;
+        e->slot_prompt[b] = f.L;
+        e->slot_ctx_ub[b] = f.L;
+        e->slot_done[b] = 0;
+        drop_fill(e, b);
+    }
+    if (n_done) {
+        e->sel_dirty = true;
+        e->fresh_slots.assign(done_slots.begin(), done_slots.end());      // may be forked until the next step, as after a prefill
+        e->fresh_chunked = true;
+    }
+    e->steps_done = 0;
+    e->stats.prefill_tokens = T;
+    *remaining = left();
+    return DOTS_OK;
+}
+
+void drop_fill(DotsEngine* e, int slot) {
+    if (slot < 0 || slot >= DOTS_MAX_BATCH || !e->fill[slot].on) return;
+    DotsEngine::Fill& f = e->fill[slot];
+    f.on = false;
+    f.src.clear(); f.src.shrink_to_fit();
+    f.seen.clear();
+    e->n_filling -= 1;
 }
 
 // The layers of one decode step over B rows: embedding, then every layer's launches.  tokens / ctx_len [B] and block_table [B][max_pages]

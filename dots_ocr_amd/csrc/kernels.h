@@ -59,6 +59,16 @@ hipError_t launch_flash_attn(hipStream_t s, const bf16_t* q, const bf16_t* k, co
                              const QBlock* blocks, int n_blocks, int64_t T, int64_t Tpad, int Hq, int Hkv,
                              int causal, float scale, const XcdPlan* plan = nullptr);
 
+// ---- attn_paged.hip: causal flash attention of a block of query rows over a sequence's own KV pages (chunked prefill)
+// One work item = one 64-position query block of one sequence: positions [q0, q0 + n), q0 % 64 == 0, 1 <= n <= 64; its q rows are rows
+// tok0 .. tok0 + n - 1 of q [Hq][T][128] (rope applied) and of out [T][Hq * 128]; its keys are pages 0 .. q0 / 64 of block-table row seq.
+struct PagedQBlock { int32_t tok0, n, q0, seq; };
+// items_host / items_dev: the same n_items work items; the host copy is checked before the launch (hipErrorInvalidValue for a q0 that is
+// no multiple of 64, a block outside [1, 64] rows, T, max_pages or the table's table_rows rows).  kv_scales as below.
+hipError_t launch_flash_attn_paged(hipStream_t s, const bf16_t* q, const void* pool_layer, const int32_t* block_table, int max_pages, int table_rows,
+                                   const PagedQBlock* items_host, const PagedQBlock* items_dev, int n_items, bf16_t* out, int64_t T, int Hq, int Hkv,
+                                   float scale, const float* kv_scales = nullptr);
+
 // ---- decode.hip  (KV page pool layout documented there)
 // Every launcher that touches the page pool takes kv_scales: nullptr = a bf16 pool; else pool_layer is an fp8 (e4m3fn) pool and kv_scales
 // the device array [Hkv][K | V] of this layer's fp32 scales (DotsConfig.kv_cache_dtype = 1).

@@ -362,6 +362,33 @@ int dots_op_flash_attn(DotsEngine* e, const void* q, const void* k, const void* 
     return DOTS_OK;
 }
 
+int dots_op_flash_attn_paged(DotsEngine* e, const void* q, const void* pool_layer, const int32_t* block_table_dev, int max_pages, int table_rows,
+                             void* out, const int32_t* rows_host, const int32_t* prefix_host, const int32_t* n_new_host, int n_seq, int Hq, int Hkv,
+                             float scale, const float* kv_scales_dev) {
+    if (!e) return DOTS_E_INVALID;
+    if (!q || !pool_layer || !block_table_dev || !out || !prefix_host || !n_new_host || n_seq < 1 || max_pages < 1 || table_rows < 1 || Hkv < 1 || Hq % Hkv)
+        return e->fail(DOTS_E_INVALID, "bad flash_attn_paged arguments");
+    CK(hipSetDevice(e->device));
+    std::vector<PagedQBlock> items;
+    int64_t T = 0;
+    for (int b = 0; b < n_seq; ++b) {
+        const int c = prefix_host[b], m = n_new_host[b], row = rows_host ? rows_host[b] : b;
+        if (c < 0 || c % 64) return e->fail(DOTS_E_INVALID, "sequence %d: a prefix of %d positions is not a multiple of 64 (unaligned prefixes are not supported)", b, c);
+        if (m < 1 || (int64_t)c + m > (int64_t)max_pages * 64 || row < 0 || row >= table_rows || T + m > INT32_MAX)
+            return e->fail(DOTS_E_INVALID, "sequence %d: prefix %d + %d new rows on table row %d does not fit %d pages / %d rows", b, c, m, row, max_pages, table_rows);
+        for (int r = 0; r < m; r += 64) items.push_back(PagedQBlock{(int32_t)(T + r), std::min(64, m - r), c + r, row});
+        T += m;
+    }
+    Scratch sc(e);
+    PagedQBlock* d_items = nullptr;
+    CK(sc.get(&d_items, items.size()));
+    CK(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(PagedQBlock), hipMemcpyHostToDevice, e->stream));
+    CK(launch_flash_attn_paged(e->stream, (const bf16_t*)q, pool_layer, block_table_dev, max_pages, table_rows, items.data(), d_items, (int)items.size(),
+                               (bf16_t*)out, T, Hq, Hkv, scale, kv_scales_dev));
+    CK(hipStreamSynchronize(e->stream));
+    return DOTS_OK;
+}
+
 int dots_plan_flash_xcd(const int32_t* lens, int n_seq, int Hq, int32_t* base8, int32_t* cnt8, int64_t* cost8) {
     if (!lens || n_seq < 1 || Hq < 1 || !base8 || !cnt8 || !cost8) return DOTS_E_INVALID;
     std::vector<int> L(lens, lens + n_seq);

@@ -622,7 +622,7 @@ int dots_set_speculation(DotsEngine* e, int k, int min_n, int max_n) {
         return e->fail(DOTS_E_CAPACITY, "%d drafts need %d rows per slot, max_batch is %d", k, k + 1, e->cfg.max_batch);
     if (e->slot_mode)
         for (int b = 0; b < e->cfg.max_batch; ++b)
-            if (e->slot_active[b]) return e->fail(DOTS_E_STATE, "speculation cannot change while slot %d is occupied", b);
+            if (e->slot_active[b] || slot_filling(e, b)) return e->fail(DOTS_E_STATE, "speculation cannot change while slot %d is occupied or filling", b);
     CK(hipSetDevice(e->device));
     hipStream_t s = e->stream;
     if (k > 0 && !e->sp_stats) {

@@ -28,6 +28,7 @@ void swap_free_host(DotsEngine* e) {
 // Of a suspended slot these are the pages that stayed resident, and its host pages go back too
 void release_pages(DotsEngine* e, int slot) {
     if (slot < DOTS_MAX_BATCH) drop_parked(e, slot);
+    drop_fill(e, slot);                                    // a filling slot's staged rows live in the rows of its pages: they go with them
     auto& mine = e->slot_pages[slot];
     for (auto it = mine.rbegin(); it != mine.rend(); ++it)
         if (--e->page_refs[*it] == 0) e->free_pages.push_back(*it);
@@ -104,6 +105,24 @@ int dots_slots_prefill(DotsEngine* e, const int32_t* slots, int n, const int32_t
     return prefill(e, input_ids, prompt_lens, n, slots, max_new_tokens);
 }
 
+// Chunked prefill: begin reserves and stages, every advance fills up to max_tokens positions
+int dots_slots_prefill_begin(DotsEngine* e, const int32_t* slots, int n, const int32_t* input_ids, const int32_t* prompt_lens,
+                             const int32_t* max_new_tokens) {
+    if (!e) return DOTS_E_INVALID;
+    if (!e->finalized) return e->fail(DOTS_E_STATE, "weights not finalized");
+    if (!slots || !input_ids || !prompt_lens || !max_new_tokens) return e->fail(DOTS_E_INVALID, "null argument");
+    CK(hipSetDevice(e->device));
+    return prefill_begin(e, input_ids, prompt_lens, n, slots, max_new_tokens);
+}
+
+int dots_slots_prefill_advance(DotsEngine* e, int max_tokens, int32_t* remaining) {
+    if (!e) return DOTS_E_INVALID;
+    if (!e->finalized) return e->fail(DOTS_E_STATE, "weights not finalized");
+    if (!remaining) return e->fail(DOTS_E_INVALID, "null argument");
+    CK(hipSetDevice(e->device));
+    return prefill_advance(e, max_tokens, remaining);
+}
+
 // Parallel sampling: n free slots become copies of the freshly prefilled sequence in src_slot.  Everything is validated and
 // counted before anything changes; the children then share the source's full prompt pages (reference counts), get a copy of its tail page
 // and select their own first token from the source's last-position logits.
@@ -125,6 +144,7 @@ int dots_slots_fork(DotsEngine* e, int src_slot, const int32_t* dst_slots, int n
             return e->fail(DOTS_E_CAPACITY, "slot %d is not usable while speculating: with %d drafts only slots [0, %d) are", d, e->spec_k, usable);
         if (d == src_slot) return e->fail(DOTS_E_INVALID, "slot %d is the source of the fork", d);
         if (e->slot_active[d]) return e->fail(DOTS_E_STATE, "slot %d is occupied", d);
+        if (slot_filling(e, d)) return e->fail(DOTS_E_STATE, "slot %d is filling", d);
         for (int a = 0; a < i; ++a)
             if (dst_slots[a] == d) return e->fail(DOTS_E_INVALID, "slot %d listed twice", d);
     }
@@ -189,7 +209,14 @@ int dots_slots_fork(DotsEngine* e, int src_slot, const int32_t* dst_slots, int n
         CK(hipMemcpyAsync(e->d_logits + (size_t)d * V, e->d_logits + (size_t)src_slot * V, (size_t)V * 4, hipMemcpyDeviceToDevice, s));
     }
     CK(hipMemcpyAsync(e->d_sel_new, sel_new, sizeof(sel_new), hipMemcpyHostToDevice, s));
-    if (e->pen_cnt) {
+    if (e->pen_cnt && e->fresh_chunked) {
+        // a source filled in passes: p_src holds its last pass only, but its own presence bits are the whole prompt's and nothing has been counted yet
+        const size_t W = (size_t)(V + 31) / 32;
+        for (int i = 0; i < n; ++i) {
+            CK(hipMemsetAsync(e->pen_cnt + (size_t)dst_slots[i] * V, 0, (size_t)V * 4, s));
+            CK(hipMemcpyAsync(e->pen_seen + dst_slots[i] * W, e->pen_seen + src_slot * W, W * 4, hipMemcpyDeviceToDevice, s));
+        }
+    } else if (e->pen_cnt) {
         // prompt-presence bits and zeroed counts of every child from the source's packed prompt, still in p_src: one sequence per launch,
         // so that each starts at the source's first token
         const int b = (int)(fresh - e->fresh_slots.begin());
@@ -519,7 +546,8 @@ int dots_slots_poll(DotsEngine* e, int32_t* finished, int32_t* out_lens) {
     CK(hipMemcpyAsync(out_lens, e->out_lens, mb * 4, hipMemcpyDeviceToHost, e->stream));
     CK(hipStreamSynchronize(e->stream));
     for (int b = 0; b < mb; ++b) {
-        if (!e->slot_mode || !e->slot_active[b]) { finished[b] = -1; out_lens[b] = 0; }      // -1: free slot
+        if (e->slot_mode && e->fill[b].on) { finished[b] = 3; out_lens[b] = 0; }             // filling (dots_slots_prefill_begin): nothing generated yet
+        else if (!e->slot_mode || !e->slot_active[b]) { finished[b] = -1; out_lens[b] = 0; }      // -1: free slot
         else if (e->parked[b].on) finished[b] = 2;                                           // suspended: out_lens as they stood at suspend
         else {
             if (finished[b]) e->slot_done[b] = 1;                                            // takes no more pages
@@ -558,7 +586,7 @@ int dots_slot_logits(DotsEngine* e, int slot, float* out) {
 
 int dots_slot_release(DotsEngine* e, int slot) {
     if (!e) return DOTS_E_INVALID;
-    if (!e->slot_mode || slot < 0 || slot >= e->cfg.max_batch || !e->slot_active[slot]) return e->fail(DOTS_E_STATE, "slot %d is not occupied", slot);
+    if (!e->slot_mode || slot < 0 || slot >= e->cfg.max_batch || (!e->slot_active[slot] && !e->fill[slot].on)) return e->fail(DOTS_E_STATE, "slot %d is not occupied", slot);
     CK(hipSetDevice(e->device));
     if (e->beam_of[slot]) return beam_release_group(e, slot);          // the slots of a beam group go together
     for (int f = 0; f < ROW_FEATURES; ++f) RET(clear_row_feature(e, slot, (RowFeature)f));

@@ -331,6 +331,8 @@ def _prototypes(lib):
         "dots_slots_reset": (i32, [vp]),
         "dots_set_eos": (i32, [vp, P(i32), i32]),
         "dots_slots_prefill": (i32, [vp, P(i32), i32, P(i32), P(i32), P(i32)]),
+        "dots_slots_prefill_begin": (i32, [vp, P(i32), i32, P(i32), P(i32), P(i32)]),
+        "dots_slots_prefill_advance": (i32, [vp, i32, P(i32)]),
         "dots_slots_decode": (i32, [vp, i32]),
         "dots_slots_fork": (i32, [vp, i32, P(i32), i32]),
         "dots_slot_logits": (i32, [vp, i32, P(C.c_float)]),
@@ -366,6 +368,7 @@ def _prototypes(lib):
         "dots_op_quant_fp8": (i32, [vp, vp, vp, i64, i32]),
         "dots_op_gemm_fp8": (i32, [vp, vp, vp, vp, vp, vp, i64, i32, i32, i32]),
         "dots_op_flash_attn": (i32, [vp, vp, vp, vp, vp, P(i32), i32, i32, i32, i32, f32]),
+        "dots_op_flash_attn_paged": (i32, [vp, vp, vp, vp, i32, i32, vp, P(i32), P(i32), P(i32), i32, i32, i32, f32, vp]),
         "dots_plan_flash_xcd": (i32, [P(i32), i32, i32, P(i32), P(i32), P(i64)]),
         "dots_op_qkv_rope_split": (i32, [vp, vp, vp, vp, vp, P(i32), i32, P(i32), i32, i32, i32, f32]),
         "dots_op_qkv_proj_rope": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, P(i32), i32, P(i32), i32, i32, i32, i32, f32, i32]),
@@ -443,6 +446,7 @@ EXPORTED_SYMBOLS = [
     "dots_slots_fork", "dots_slots_extend", "dots_slot_logits",
     "dots_slots_beam", "dots_beam_info", "dots_beam_read",
     "dots_stop_create", "dots_stop_destroy", "dots_set_row_stop", "dots_row_stop_hit",
+    "dots_op_flash_attn_paged", "dots_slots_prefill_begin", "dots_slots_prefill_advance",
 ]
 
 MAX_SPEC_DRAFTS = 15                         # DOTS_MAX_SPEC_DRAFTS: drafts per slot and step
@@ -1184,6 +1188,31 @@ class Engine:
         assert sl.shape == lens.shape == cap.shape and ids.shape[0] == int(lens.sum())
         self._ck(self.lib.dots_slots_prefill(self.h, _i32p(sl), sl.shape[0], _i32p(ids), _i32p(lens), _i32p(cap)), "dots_slots_prefill")
 
+    # chunked prefill
+    def slots_prefill_begin(self, slots: Sequence[int], input_ids: np.ndarray, prompt_lens: Sequence[int], max_new_tokens: Sequence[int]):
+        """slots_prefill's arguments; the prompts may together be longer than max_prefill_tokens.  Reserves the pages, embeds the prompts
+        (the vision rows of vit_forward are consumed here) and leaves the slots filling (slots_poll reports 3): slots_prefill_advance fills
+        them.  Refused on a speculating engine."""
+        sl = np.ascontiguousarray(slots, dtype=np.int32)
+        ids = np.ascontiguousarray(input_ids, dtype=np.int32)
+        lens = np.ascontiguousarray(prompt_lens, dtype=np.int32)
+        cap = np.ascontiguousarray(max_new_tokens, dtype=np.int32)
+        assert sl.shape == lens.shape == cap.shape and ids.shape[0] == int(lens.sum())
+        self._ck(self.lib.dots_slots_prefill_begin(self.h, _i32p(sl), sl.shape[0], _i32p(ids), _i32p(lens), _i32p(cap)), "dots_slots_prefill_begin")
+
+    def slots_prefill_advance(self, max_tokens: int) -> int:
+        """One pass over up to max_tokens positions (a multiple of 64, at most max_prefill_tokens) of the filling slots, oldest first; a slot
+        whose prompt ends in the pass is then what slots_prefill would have left.  -> positions still to fill."""
+        left = C.c_int32(0)
+        self._ck(self.lib.dots_slots_prefill_advance(self.h, int(max_tokens), C.byref(left)), "dots_slots_prefill_advance")
+        return int(left.value)
+
+    def slots_prefill_chunked(self, slots: Sequence[int], input_ids: np.ndarray, prompt_lens: Sequence[int], max_new_tokens: Sequence[int], chunk: int):
+        """slots_prefill in passes of at most `chunk` positions: the same logits, KV and tokens whatever the chunk."""
+        self.slots_prefill_begin(slots, input_ids, prompt_lens, max_new_tokens)
+        while self.slots_prefill_advance(chunk) > 0:
+            pass
+
     def slots_fork(self, src: int, dst_slots: Sequence[int]):
         """Parallel sampling: every free slot of dst_slots becomes a copy of the sequence slots_prefill just put into slot src (no decode
         step since): the same prompt over the same KV pages, and its own first token under the row parameters already set on it.  From
@@ -1247,7 +1276,7 @@ class Engine:
         self._ck(self.lib.dots_slots_decode(self.h, int(n_steps)), "dots_slots_decode")
 
     def slots_poll(self):
-        """-> (finished [max_batch]: -1 free / 0 running / 1 finished / 2 suspended, out_lens [max_batch])"""
+        """-> (finished [max_batch]: -1 free / 0 running / 1 finished / 2 suspended / 3 filling, out_lens [max_batch])"""
         fin = np.empty((self.max_batch,), dtype=np.int32)
         lens = np.empty((self.max_batch,), dtype=np.int32)
         self._ck(self.lib.dots_slots_poll(self.h, _i32p(fin), _i32p(lens)), "dots_slots_poll")
@@ -1435,6 +1464,20 @@ class Engine:
         """op_dec_qkv on an fp8 (e4m3fn) page pool; kv_scales: device fp32 [Hkv, 2] (K, V)."""
         self._ck(self.lib.dots_op_dec_qkv_kv8(self.h, h, ln_w, wqkv, bias or None, ctx_len, block_table, max_pages, pool_layer, q_out,
                                               B, H, Hq, Hkv, eps, rope_theta, int(fp8), kv_scales), "dots_op_dec_qkv_kv8")
+
+    def op_flash_attn_paged(self, q, pool_layer, block_table, max_pages, table_rows, out, prefix, n_new, Hq, Hkv, scale, kv_scales=None, rows=None):
+        """Causal attention of new query rows over keys that lie in the page pool (csrc/attn_paged.hip).  Sequence b: prefix[b] positions
+        (a multiple of 64) before its n_new[b] rows, pages = row rows[b] (None: b) of the device table [table_rows, max_pages];
+        q device bf16 [Hq, sum n_new, 128]; kv_scales: device fp32 [Hkv, 2] of an fp8 pool, or None for a bf16 pool."""
+        pre = np.ascontiguousarray(prefix, dtype=np.int32)
+        new = np.ascontiguousarray(n_new, dtype=np.int32)
+        if pre.ndim != 1 or pre.shape != new.shape:
+            raise ValueError("prefix and n_new must be 1-D and of equal length")
+        rw = None if rows is None else np.ascontiguousarray(rows, dtype=np.int32)
+        if rw is not None and rw.shape != pre.shape:
+            raise ValueError("rows must match prefix")
+        self._ck(self.lib.dots_op_flash_attn_paged(self.h, q, pool_layer, block_table, max_pages, table_rows, out, None if rw is None else _i32p(rw),
+                                                   _i32p(pre), _i32p(new), pre.shape[0], Hq, Hkv, scale, kv_scales), "dots_op_flash_attn_paged")
 
     def op_decode_attn_kv8(self, q, pool_layer, ctx_len, block_table, max_pages, out, B, Hq, Hkv, max_seq_len, kv_scales):
         """op_decode_attn on an fp8 (e4m3fn) page pool; kv_scales: device fp32 [Hkv, 2] (K, V)."""

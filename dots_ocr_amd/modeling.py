@@ -136,7 +136,8 @@ class DotsOcrHipForCausalLM:
                  guided_whitespace_pattern=None, no_repeat_ngram_size: Optional[int] = None, no_repeat_ngram_window: Optional[int] = None,
                  no_repeat_ngram_whitelist=None, speculative_ngram: Optional[int] = None, prompt_lookup_min: int = 2, prompt_lookup_max: int = 4,
                  num_return_sequences: int = 1, stop_strings=None, speculative_rows=None, num_beams: Optional[int] = None,
-                 length_penalty: float = 1.0, early_stopping=None, speculative_guided: bool = False, prompt_suffixes=None, speculative_shaped=None, **_):
+                 length_penalty: float = 1.0, early_stopping=None, speculative_guided: bool = False, prompt_suffixes=None, speculative_shaped=None,
+                 prefill_chunk: Optional[int] = None, **_):
         """HF-shaped generate.  do_sample / temperature / top_p default to the checkpoint's generation_config.json (greedy when it
         is absent); with sampling on, tokens are drawn on the GPU from softmax(logits / temperature) restricted to the top_p
         nucleus, reproducibly from `seed`.  Returns LongTensor
@@ -209,7 +210,12 @@ class DotsOcrHipForCausalLM:
         sequence j continues prefix + prompt_suffixes[j] from one tower, one prefill of the prefix and one extend.  Returns LongTensor
         [m, T + new]: row j = the prefix followed by the new tokens of suffix j (the suffix ids are not repeated), drawn with seed + j.
         It runs on the continuous path and is refused together with num_return_sequences > 1, num_beams, penalties, speculation or
-        continuous=False."""
+        continuous=False.
+
+        prefill_chunk (N, a multiple of 64 and at most the engine's max_prefill_tokens; None = off) fills every prompt in passes of N
+        positions between which the sequences already running keep decoding (ContinuousBatcher(prefill_chunk=)), and
+        admits prompts longer than the prefill workspace.  The tokens do not depend on N.  It runs on the continuous path and is refused
+        together with speculative_ngram or continuous=False."""
         import dataclasses
         import torch
         t_eff, p_eff = resolve_sampling(self.generation_config, do_sample, temperature, top_p)
@@ -219,6 +225,12 @@ class DotsOcrHipForCausalLM:
             raise ValueError(f"num_return_sequences must be an integer >= 1, got {nrs!r}")
         if nrs > 1 and continuous is False:
             raise ValueError("num_return_sequences > 1 runs on the continuous path: continuous=False cannot be combined with it")
+        if prefill_chunk is not None:
+            if continuous is False:
+                raise ValueError("prefill_chunk runs on the continuous path: continuous=False cannot be combined with it")
+            if speculative_ngram:
+                raise ValueError("prefill_chunk cannot be combined with speculative_ngram: a speculating engine fills a prompt in one pass")
+            continuous = True
         if early_stopping is not None:
             raise ValueError("early_stopping is not offered: a beam group ends at its cap, or early only where that is exact (DESIGN §6.9)")
         beam = None
@@ -362,7 +374,7 @@ class DotsOcrHipForCausalLM:
                                                    penalties=bool(spec_shaped & SPEC_SHAPED["penalties"]))
         try:
             return self._generate(input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens, eos_token_id, pad_token_id, continuous,
-                                  row_sp, rules, guide, ngram, nrs, stop, int(min_tokens or 0), beam, suffixes)
+                                  row_sp, rules, guide, ngram, nrs, stop, int(min_tokens or 0), beam, suffixes, prefill_chunk)
         finally:
             if spec_k:
                 try:
@@ -385,7 +397,7 @@ class DotsOcrHipForCausalLM:
                     warnings.warn(f"guide {guide} could not be destroyed: {e}")
 
     def _generate(self, input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens, eos_token_id, pad_token_id, continuous, row_sp, rules,
-                  guide, ngram=None, nrs=1, stop=None, stop_min=0, beam=None, suffixes=None):
+                  guide, ngram=None, nrs=1, stop=None, stop_min=0, beam=None, suffixes=None, prefill_chunk=None):
         import torch
         if suffixes:
             nrs = len(suffixes)                      # the rows of the result: one per suffix, laid out as num_return_sequences lays them out
@@ -450,7 +462,7 @@ class DotsOcrHipForCausalLM:
                                         ngram=ngram, n=1 if suffixes else nrs, stop=stop, suffixes=suffixes))
                 if beam is not None:             # a group of beam[0] beams that returns its nrs best hypotheses
                     reqs[-1].n, reqs[-1].num_beams, reqs[-1].num_return, reqs[-1].length_penalty = 1, beam[0], nrs, beam[1]
-            outs = ContinuousBatcher(self.engine, eos_ids=eos).run(reqs)
+            outs = ContinuousBatcher(self.engine, eos_ids=eos, **({} if prefill_chunk is None else {"prefill_chunk": prefill_chunk})).run(reqs)
             if beam is not None:                 # row i * n + j = the j-th best hypothesis of prompt i (a prompt with fewer: pad rows)
                 outs = [r.outputs[j] if j < len(r.outputs) else np.zeros(0, np.int64) for r in reqs for j in range(nrs)]
             elif nrs > 1:                        # row i * n + j = sequence j of prompt i

@@ -35,8 +35,15 @@ class DotsOCRParser:
                  max_pixels=None, use_hf=False, model_path="./weights/DotsOCR", model=None, processor=None,
                  hf_max_new_tokens=24000, guided=False, no_repeat_ngram_size=None, no_repeat_ngram_window=None,
                  no_repeat_ngram_whitelist=None, speculative_ngram=None, prompt_lookup_min=2, prompt_lookup_max=4, stop=None,
-                 speculative_rows=None, num_beams=None, length_penalty=1.0, speculative_guided=False, speculative_shaped=None):
+                 speculative_rows=None, num_beams=None, length_penalty=1.0, speculative_guided=False, speculative_shaped=None,
+                 prefill_chunk=None):
         self.dpi = dpi
+        # chunked prefill, opt-in: the in-process model fills every page's prompt in passes of prefill_chunk positions
+        # between which the pages already running keep decoding (same tokens).  A server chunks by its own --enable-chunked-prefill flag, as
+        # vLLM does: requests carry nothing.
+        self.prefill_chunk = None if prefill_chunk is None else int(prefill_chunk)
+        if self.prefill_chunk is not None and speculative_ngram:
+            raise ValueError("prefill_chunk cannot be combined with speculative_ngram")
         # beam search, opt-in: every page is decoded by a group of num_beams beams and its best hypothesis returned (the
         # server request carries use_beam_search with temperature 0, the in-process model generates with num_beams).  It combines with
         # none of the other selection settings: they are refused, not dropped.
@@ -148,6 +155,8 @@ class DotsOCRParser:
             kw["stop_strings"] = self.stop
         if self.num_beams:
             kw.update(num_beams=self.num_beams, length_penalty=self.length_penalty, do_sample=False)
+        if self.prefill_chunk is not None:
+            kw["prefill_chunk"] = self.prefill_chunk
         generated = self.model.generate(**inputs, max_new_tokens=self.hf_max_new_tokens, **kw)
         trimmed = [out[len(inp):] for inp, out in zip(inputs.input_ids, generated)]
         texts = self.processor.batch_decode(trimmed, skip_special_tokens=True, clean_up_tokenization_spaces=False)
@@ -336,7 +345,7 @@ class DotsOCRParser:
         t, p_ = resolve_sampling(getattr(self.model, "generation_config", None))
         engine.set_sampling(t, p_, 0)
         eos = list(self.model.config.eos_token_ids)
-        cb = ContinuousBatcher(engine, eos_ids=eos)
+        cb = ContinuousBatcher(engine, eos_ids=eos, **({} if self.prefill_chunk is None else {"prefill_chunk": self.prefill_chunk}))
         n = len(images)
         results = [None] * n
         with ThreadPool(max(1, min(8, self.num_thread, n))) as prep_pool, ThreadPool(max(1, min(8, self.num_thread, n))) as post_pool:

@@ -90,8 +90,25 @@ class ContinuousBatcher:
 
     def __init__(self, engine, eos_ids: Sequence[int] = (), chunk: int = 16, headroom_pages: Optional[int] = 2, prefetch: int = 0,
                  tower_steps_per_page: int = 48, admit_group: Optional[int] = None, preemption: Optional[str] = None,
-                 swap_pages: Optional[int] = None):
+                 swap_pages: Optional[int] = None, prefill_chunk: Optional[int] = None):
         self.engine = engine
+        # chunked prefill.  None: an admitted group is prefilled in one pass (Engine.slots_prefill), during which nothing
+        # decodes.  N: admission only BEGINS the group's fill (Engine.slots_prefill_begin); every step then runs at most one pass of N
+        # positions (Engine.slots_prefill_advance) and its decode chunk, so no decode chunk waits for more than one pass, and a prompt
+        # may be longer than the engine's max_prefill_tokens.  A request joins `running` in the step whose pass completed its fill
+        if prefill_chunk is not None:
+            if isinstance(prefill_chunk, bool) or not isinstance(prefill_chunk, (int, np.integer)) or prefill_chunk < 64 or prefill_chunk % 64:
+                raise ValueError(f"prefill_chunk must be a positive multiple of 64, got {prefill_chunk!r}")
+            if prefill_chunk > int(engine.max_prefill_tokens):
+                raise ValueError(f"prefill_chunk = {prefill_chunk} exceeds the engine's max_prefill_tokens = {int(engine.max_prefill_tokens)}")
+            if not all(hasattr(engine, f) for f in ("slots_prefill_begin", "slots_prefill_advance")):
+                raise ValueError("this engine cannot fill a prompt in passes (no slots_prefill_begin): prefill_chunk is not available")
+            if getattr(engine, "spec_k", 0):
+                raise ValueError("prefill_chunk cannot be combined with a speculating engine")
+        self.prefill_chunk = None if prefill_chunk is None else int(prefill_chunk)
+        self.filling: List[Tuple[int, int, Request]] = []        # (slot, request id, request) whose fill has begun, oldest first
+        self._fill_kids: Dict[int, List[int]] = {}               # request id -> the slots its fork / beam group takes once its fill completes
+        self.fill_passes = 0
         # preemption.  None: a dry KV pool ends a sequence early at what its pages hold ("kv_pool_exhausted").  "swap":
         # before a decode chunk that would run short, the most recently admitted sequences are suspended — their KV parked in swap_pages
         # pages of pinned host memory (default: as many as the pool has) — and resumed, oldest suspension first, when the pool has room
@@ -172,7 +189,7 @@ class ContinuousBatcher:
         ids = np.ascontiguousarray(req.input_ids, dtype=np.int32).reshape(-1)
         if ids.shape[0] < 1 or ids.shape[0] >= self.max_seq_len:
             raise ValueError(f"prompt of {ids.shape[0]} tokens does not fit max_seq_len={self.max_seq_len}")
-        if ids.shape[0] > self.max_prefill_tokens:
+        if ids.shape[0] > self.max_prefill_tokens and self.prefill_chunk is None:
             raise ValueError(f"prompt of {ids.shape[0]} tokens exceeds max_prefill_tokens={self.max_prefill_tokens}")
         if req.n_patches() > self.max_patches:
             raise ValueError(f"request has {req.n_patches()} vision patches, more than max_patches={self.max_patches}")
@@ -295,10 +312,11 @@ class ContinuousBatcher:
 
     @property
     def idle(self) -> bool:
-        return not self.pending and not self.running and not self._ahead and not self._rejected
+        return not self.pending and not self.running and not self._ahead and not self._rejected and not self.filling
 
     def free_slots(self) -> List[int]:
-        return [s for s in range(self.n_slots) if s not in self.running]
+        held = {s for s, _, _ in self.filling} | {k for ks in self._fill_kids.values() for k in ks}
+        return [s for s in range(self.n_slots) if s not in self.running and s not in held]
 
     # ------------------------------------------------------------------ admission
     ADMIT_AHEAD = 64                                 # tokens beyond the prompt dots_slots_prefill reserves (slots.hip KV_ADMIT_AHEAD)
@@ -340,6 +358,8 @@ class ContinuousBatcher:
         seqs: Dict[int, Tuple[Request, int]] = {}
         for rid, r in self.running.values():
             seqs[rid] = (r, seqs.get(rid, (r, 0))[1] + 1)
+        for _, rid, r in self.filling:                # a filling request will run all its sequences
+            seqs[rid] = (r, r.seqs)
         return sum(self._worst_pages(r, k) for r, k in seqs.values())
 
     def _fits_full_reservation(self, admitted: Sequence[Request], new: Sequence[Request]) -> bool:
@@ -364,15 +384,17 @@ class ContinuousBatcher:
             p, t = req.n_patches(), int(req.input_ids.shape[0])
             if req.width > len(free):
                 break                                # n sequences (or beams) need n slots: the head of the queue waits for them, nothing overtakes it
-            if group and (patches + p > self.max_patches or tokens + t > self.max_prefill_tokens):
+            # the prefill workspace bounds a group that is prefilled in one pass; a group filled in passes is bounded by the pool alone
+            if group and (patches + p > self.max_patches or (self.prefill_chunk is None and tokens + t > self.max_prefill_tokens)):
                 break
             # paged KV, on demand: a sequence reserves its prompt + ADMIT_AHEAD tokens now and grows page by page; admit only while every
             # running sequence (and this one) could still take `headroom` more pages, so that a dry pool — which ends a sequence early
             # at what its pages hold — stays the exception.  Nothing running: admit whatever fits (submit() checked that it can).
             need = self._group_pages(req)
-            taken = len(self.running) + sum(r.width for _, _, r in group)
-            reserve = self.headroom_pages * (taken + req.width) if (self.running or group) else 0
-            if (self.running or group) and not self._fits_full_reservation([r for _, _, r in group], [req]):
+            taken = len(self.running) + sum(r.width for _, _, r in self.filling) + sum(r.width for _, _, r in group)
+            busy = bool(self.running or self.filling or group)
+            reserve = self.headroom_pages * (taken + req.width) if busy else 0
+            if busy and not self._fits_full_reservation([r for _, _, r in group], [req]):
                 break                                # worst case of everything in flight must fit the pool (submit() checked a lone request)
             if need + reserve > pages_free:
                 break                                                                    # wait for a running sequence to return its pages
@@ -467,10 +489,26 @@ class ContinuousBatcher:
                 self._clear_rows(every)              # nothing of this group stays behind; the caller puts the group back in the queue
                 raise
         try:
-            self.engine.slots_prefill(slots, np.concatenate([r.input_ids for _, _, r in group]), lens, caps)
+            if self.prefill_chunk is not None:
+                self.engine.slots_prefill_begin(slots, np.concatenate([r.input_ids for _, _, r in group]), lens, caps)
+            else:
+                self.engine.slots_prefill(slots, np.concatenate([r.input_ids for _, _, r in group]), lens, caps)
         except Exception:
             self._clear_rows(every)                  # the slots stay free
             raise
+        if self.prefill_chunk is not None:           # the slots are filling: _advance_fill takes it from here, pass by pass
+            self.filling += group
+            self._fill_kids.update(kids)
+            self.admissions += 1
+            return
+        self._after_prefill(group, kids)
+        self.admissions += 1
+
+    def _after_prefill(self, group, kids):
+        """the requests of `group` hold a fresh prefill (one pass, or the pass that completed their fill): fork, beam group or extend of a
+        request with several sequences, before any decode step; then they are running"""
+        slots = [s for s, _, _ in group]
+        every = slots + [k for ks in kids.values() for k in ks]
         forked: List[int] = []
         try:                                         # one fork per request with n > 1, before any decode step: the prefill is still fresh
             for s, rid, r in group:
@@ -499,7 +537,24 @@ class ContinuousBatcher:
                     self._seq_index[k] = j
             if r.seqs > 1:
                 r._parts = {}
-        self.admissions += 1
+
+    def _advance_fill(self) -> bool:
+        """One pass over the filling slots, oldest first.  The requests whose fill it completed do their fork, beam conversion or extend
+        now — the pass is their fresh prefill — and join `running`.  -> whether any did"""
+        self.engine.slots_prefill_advance(self.prefill_chunk)
+        self.fill_passes += 1
+        fin, _ = self.engine.slots_poll()
+        joined = [(s, rid, r) for s, rid, r in self.filling if fin[s] != 3]
+        if not joined:
+            return False
+        self.filling = [(s, rid, r) for s, rid, r in self.filling if fin[s] == 3]
+        kids = {rid: self._fill_kids.pop(rid) for _, rid, _ in joined if rid in self._fill_kids}
+        try:
+            self._after_prefill(joined, kids)
+        except Exception:                            # their slots were given back: the requests return to the head of the queue for the caller
+            self.pending.extendleft(reversed([(rid, r) for _, rid, r in joined]))
+            raise
+        return True
 
     def _admit(self, group):
         # per-row parameters first, before the tower runs: a request whose own parameters the engine refuses (submit() and the server
@@ -585,7 +640,8 @@ class ContinuousBatcher:
             rid, req = self.pending[0]
             p, t = req.n_patches(), int(req.input_ids.shape[0])
             pg = self._group_pages(req)
-            if p == 0 or patches + p > self.max_patches or tokens + t > self.max_prefill_tokens or pages + pg > total_pages:
+            if (p == 0 or patches + p > self.max_patches or (self.prefill_chunk is None and tokens + t > self.max_prefill_tokens)
+                    or pages + pg > total_pages):
                 break                                # a text-only request goes through the ordinary admission, in its turn
             if self.full_reservation and sum(self._worst_pages(r) for _, r in group) + self._worst_pages(req) > total_pages:
                 break                                # full reservation: the group must fit an EMPTY pool by its worst case (its tower may run ahead;
@@ -764,11 +820,15 @@ class ContinuousBatcher:
                     self.pending.extendleft(reversed([(rid, r) for _, rid, r in group if getattr(r, "error", None) is None]))
                     raise
         self._look_ahead()
+        if self.prefill_chunk is not None:           # at most one pass per step, then the step's decode chunk over the running rows
+            admitted = bool(self.filling) and self._advance_fill()
         if admitted:
             done = self._collect()                   # a 1-token cap or an immediate EOS finishes at prefill
             if done:
                 return done
         if not self.running:
+            if self.filling:                         # nothing decodes yet: the next step runs the next pass
+                return []
             if self._rejected:                       # the whole group was refused: report it, admit the next one on the next step
                 return []
             if self._ahead:                          # nothing runs, so every slot and page is free: the group fits by construction

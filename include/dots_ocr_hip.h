@@ -461,7 +461,8 @@ int dots_set_gemm_plan(DotsEngine* e, int plan);
  *                    every running sequence is given the KV pages its next n_steps positions need (on-demand paging); if the pool
  *                    is dry the sequence keeps its pages and its generation cap is lowered to what they hold — it finishes there
  *                    (reason "length", as HF generate does at the context capacity); dots_slot_capacity reports the lowered cap.
- * dots_slots_poll    finished[b] = -1 free / 0 running / 1 finished / 2 suspended (dots_slot_suspend), out_lens[b] = tokens generated so far; both
+ * dots_slots_poll    finished[b] = -1 free / 0 running / 1 finished / 2 suspended (dots_slot_suspend) / 3 filling (dots_slots_prefill_begin),
+ *                    out_lens[b] = tokens generated so far; both
  *                    int32 [max_batch].  Synchronises the stream.
  * dots_slot_read     copies min(n, capacity) generated ids of one occupied slot, *n_out = n.
  * dots_slot_release  marks the slot free.
@@ -504,6 +505,26 @@ int dots_slots_prefill(DotsEngine* e, const int32_t* slots_host, int n, const in
  *                    pages (DOTS_E_CAPACITY).  Synchronises. */
 int dots_slots_extend(DotsEngine* e, const int32_t* slots_host, int n, const int32_t* ids_host, const int32_t* lens_host,
                       const int32_t* keep_pending_host, const int32_t* max_new_tokens_host);
+/* ---- Chunked prefill: the prompts of dots_slots_prefill filled in passes over their own KV pages, so that decode chunks of
+ * the running slots can run between the passes and a prompt may be longer than max_prefill_tokens.
+ *
+ * dots_slots_prefill_begin    arguments and checks of dots_slots_prefill, except that the packed length is bounded by max_seq_len per prompt
+ *                             and by the pool only.  Reserves every slot's admission pages (all or nothing), embeds every prompt whole —
+ *                             vision rows included: run dots_vit_forward for exactly these sequences first, its rows are free again when the
+ *                             call returns — and leaves the slots FILLING at position 0.  Refused on a speculating engine (DOTS_E_STATE).
+ * dots_slots_prefill_advance  one pass of the prefill's layer loop over up to max_tokens positions (a positive multiple of 64, at most
+ *                             max_prefill_tokens) of the filling slots, oldest begin first; a cut falls on a multiple of 64 positions of its
+ *                             sequence or at its end.  A slot whose last prompt token is in the pass completes as at the end of
+ *                             dots_slots_prefill (first token selected, running, forkable until the next step).  *remaining = positions
+ *                             still to fill over all filling slots.  What a position computes does not depend on the cuts: logits, KV pages
+ *                             and everything generated afterwards are identical in every bit for every max_tokens.
+ * A filling slot is inert: decode steps, dots_slots_extend and dots_slots_prefill of other slots may run between passes and touch nothing
+ * of it.  dots_slots_poll reports 3; dots_slot_release returns its pages; dots_slots_reset drops every fill; dots_slot_suspend,
+ * dots_slots_extend, dots_slots_fork, dots_slots_beam, dots_slot_read and dots_slot_logits refuse it (DOTS_E_STATE), as do
+ * dots_slots_prefill and dots_slots_prefill_begin into it. */
+int dots_slots_prefill_begin(DotsEngine* e, const int32_t* slots_host, int n, const int32_t* input_ids_host, const int32_t* prompt_lens_host,
+                             const int32_t* max_new_tokens_host);
+int dots_slots_prefill_advance(DotsEngine* e, int max_tokens, int32_t* remaining);
 int dots_slots_decode(DotsEngine* e, int n_steps);
 int dots_slots_poll(DotsEngine* e, int32_t* finished_host, int32_t* out_lens_host);
 int dots_slot_read(DotsEngine* e, int slot, int32_t* out_ids_host, int capacity, int32_t* n_out);
@@ -628,6 +649,15 @@ int dots_op_gemm_fp8(DotsEngine* e, const void* A_dev, const void* W_dev, const 
  * out bf16 [T, Hq*128]. */
 int dots_op_flash_attn(DotsEngine* e, const void* q_dev, const void* k_dev, const void* vt_dev, void* out_dev,
                        const int32_t* cu_seqlens_host, int n_seq, int Hq, int Hkv, int causal, float scale);
+/* Causal flash attention of blocks of NEW query rows over sequences whose keys already lie in the page pool (csrc/attn_paged.hip; what a
+ * pass of dots_slots_prefill_advance runs).  Sequence b has prefix_host[b] positions in its pages (a multiple of 64; DOTS_E_INVALID
+ * otherwise) and n_new_host[b] >= 1 new rows at positions prefix .. prefix + n_new - 1, whose keys and values are in the pages too; its
+ * pages are row rows_host[b] (NULL: row b) of block_table_dev int32 [table_rows, max_pages].  q bf16 [Hq, T, 128] head-major, rope
+ * applied, T = sum n_new, the sequences' rows packed in order; pool_layer as dots_op_decode_attn (kv_scales_dev == NULL) or
+ * dots_op_decode_attn_kv8 (kv_scales_dev fp32 [Hkv][2]).  out bf16 [T, Hq*128].  Row at position p attends to keys 0 .. p. */
+int dots_op_flash_attn_paged(DotsEngine* e, const void* q_dev, const void* pool_layer_dev, const int32_t* block_table_dev, int max_pages,
+                             int table_rows, void* out_dev, const int32_t* rows_host, const int32_t* prefix_host, const int32_t* n_new_host,
+                             int n_seq, int Hq, int Hkv, float scale, const float* kv_scales_dev);
 /* Host-only (no device, no engine): how the flash-attention work list of a packed batch of sequences of lens[0 .. n_seq) patches and Hq heads
  * is cut across the 8 XCDs — base8[x] / cnt8[x] = the contiguous chunk of (sequence, head, query block) items XCD x walks, cost8[x] = its KV
  * tiles (csrc/kernels.h: XcdPlan; equal COST per XCD, not equal count: tests/test_cabi_cpu.py checks the balance on BASELINE configs[3]'s
