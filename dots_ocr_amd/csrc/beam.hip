@@ -345,9 +345,10 @@ int dots_slots_beam(DotsEngine* e, int src_slot, const int32_t* dst_slots, int n
     if ((int)src_pages.size() < shared + (L % 64 ? 1 : 0)) return e->fail(DOTS_E_STATE, "slot %d does not hold its prompt pages", src_slot);
     const int src_has = (int)src_pages.size() - shared;
     const int64_t need = (int64_t)std::max(own - src_has, 0) + 1 + (int64_t)n_dst * (own + 1);
+    ensure_free(e, need);
     if (shared + own > e->max_pages || need > (int64_t)e->free_pages.size())
         return e->fail(DOTS_E_CAPACITY, "KV pool exhausted: a group of %d beams needs %lld more pages of 64 tokens (%d per beam and a spare each), %d of %d are free", B,
-                       (long long)need, own, (int)e->free_pages.size(), e->n_pool_pages);
+                       (long long)need, own, free_count(e), e->n_pool_pages);
     CK(hipSetDevice(e->device));
     hipStream_t s = e->stream;
     RET(ensure_beam_state(e));

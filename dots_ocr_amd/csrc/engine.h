@@ -20,6 +20,7 @@
 #include "decode_layout.h"
 #include "dots_ocr_hip.h"
 #include "kernels.h"
+#include "prefix_cache.h"
 #include "row_stage.h"
 
 struct Tensor {
@@ -292,6 +293,12 @@ struct DotsEngine {
         uint64_t order = 0;
         std::vector<int32_t> src;
         std::vector<uint32_t> seen;
+        // prefix cache: the pass that completes a full prompt page inserts it behind cache_parent (-1: the root) while
+        // cache is set; ids: the prompt as given (the blocks' identity), key: its image's
+        bool cache = false, keyed = false;
+        int32_t cache_parent = -1;
+        uint8_t key[16] = {0};
+        std::vector<int32_t> ids;
     };
     Fill fill[DOTS_MAX_BATCH];
     int n_filling = 0;
@@ -301,6 +308,9 @@ struct DotsEngine {
     PagedQBlock* fill_items = nullptr;
     std::vector<int32_t> hp_rows;
     std::vector<PagedQBlock> hp_items;
+    // prefix cache (dots_prefix_cache_enable): the block index (csrc/prefix_cache.h) over page_refs, nullptr = off.  The tower
+    // rows a block retains are the rows of its page in fill_x, which nobody writes while the page is held
+    prefix_cache::Index* pc = nullptr;
     bool fresh_chunked = false;            // fresh_slots were completed by a pass: p_src holds that pass only (dots_slots_fork copies the source's presence bits)
     // captured decode steps, keyed by everything the capture bakes in: rows, KV splits, static batch (out_cap = row stride of
     // the output buffer) or slot mode (out_cap = 0), number of EOS ids, whether any row carries its own parameters (rowp: the per-row
@@ -431,7 +441,9 @@ int chain_streams(DotsEngine* e, hipStream_t from, hipStream_t to);
 int pick_decode_stream(DotsEngine* e, hipStream_t* cur);
 int prefill(DotsEngine* e, const int32_t* ids, const int32_t* lens, int B, const int32_t* slots = nullptr, const int32_t* max_new = nullptr);
 // chunked prefill: a filling slot holds pages and staged rows but is not occupied
-int prefill_begin(DotsEngine* e, const int32_t* ids, const int32_t* lens, int B, const int32_t* slots, const int32_t* max_new);
+// leases / keys (both or neither): dots_slots_prefill_begin_cached — a prompt with a lease starts behind its cached pages
+int prefill_begin(DotsEngine* e, const int32_t* ids, const int32_t* lens, int B, const int32_t* slots, const int32_t* max_new, const int32_t* leases = nullptr,
+                  const uint8_t* const* keys = nullptr);
 int prefill_advance(DotsEngine* e, int max_tokens, int32_t* remaining);
 inline bool slot_filling(const DotsEngine* e, int slot) { return slot >= 0 && slot < DOTS_MAX_BATCH && e->fill[slot].on; }
 void drop_fill(DotsEngine* e, int slot);      // the record only: the pages go with release_pages
@@ -442,6 +454,9 @@ int splits_for_ctx(int max_ctx);
 int step_graph(DotsEngine* e, int rows, int n_splits, int out_cap, hipGraphExec_t* exec, int part = 0);
 // slots.hip
 int grow_pages(DotsEngine* e, int slot, int tokens, bool* changed);
+// the prefix cache's evictable pages count as free: ensure_free moves up to `need` of them into the free list (off: nothing happens)
+void ensure_free(DotsEngine* e, int64_t need);
+int free_count(const DotsEngine* e);
 // a suspended slot: occupied, its KV parked in host memory (dots_slot_suspend)
 inline bool slot_parked(const DotsEngine* e, int slot) { return slot >= 0 && slot < DOTS_MAX_BATCH && e->parked[slot].on; }
 void swap_free_host(DotsEngine* e);

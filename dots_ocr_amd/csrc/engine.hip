@@ -410,8 +410,9 @@ int prefill(DotsEngine* e, const int32_t* ids, const int32_t* lens, int B, const
     {
         int need = 0;
         for (int b = 0; b < B; ++b) need += ((slots ? admit_tokens(e, L[b], max_new[b]) : std::min(L[b] + e->out_cap, c.max_seq_len)) + 63) / 64;
+        ensure_free(e, need);
         if (need > (int)e->free_pages.size()) {
-            const int have = (int)e->free_pages.size();
+            const int have = free_count(e);
             if (whole_table) CK(hipMemcpyAsync(e->block_table, e->hp_table.data(), e->hp_table.size() * 4, hipMemcpyHostToDevice, s));
             return e->fail(DOTS_E_CAPACITY, "KV pool exhausted: these sequences need %d pages of 64 tokens, %d of %d are free", need, have, e->n_pool_pages);
         }
@@ -522,10 +523,16 @@ int prefill(DotsEngine* e, const int32_t* ids, const int32_t* lens, int B, const
 // ---- chunked prefill: the same prompts filled in passes of at most max_tokens positions over their own KV pages.
 // begin: validates as prefill() does — except that the packed length is bounded by the pool only, not by the workspace — reserves the
 // pages, embeds every prompt whole into the staging buffer (the tower's rows are consumed here) and leaves the slots FILLING.
-int prefill_begin(DotsEngine* e, const int32_t* ids, const int32_t* lens, int B, const int32_t* slots, const int32_t* max_new) {
+// With leases / keys (dots_slots_prefill_begin_cached) a prompt that holds a lease names the lease's pages in the first
+// entries of its table row, reserves and embeds the rest only, and starts with its cursor behind them; a lease stays the caller's until
+// the call has succeeded.
+int prefill_begin(DotsEngine* e, const int32_t* ids, const int32_t* lens, int B, const int32_t* slots, const int32_t* max_new, const int32_t* leases,
+                  const uint8_t* const* keys) {
     const DotsConfig& c = e->cfg;
     hipStream_t s = e->stream;
     const int H = c.hidden_size;
+    const bool cached = leases != nullptr;
+    if (cached && !e->pc) return e->fail(DOTS_E_STATE, "the prefix cache is off (dots_prefix_cache_enable)");
     if (e->spec_k) return e->fail(DOTS_E_STATE, "a chunked prefill cannot begin while the engine speculates (dots_set_speculation), as a slot cannot be extended or suspended then");
     if (e->TP < 64) return e->fail(DOTS_E_CAPACITY, "a chunked prefill needs max_prefill_tokens >= 64, it is %lld", (long long)e->TP);
     if (B < 1 || B > c.max_batch) return e->fail(DOTS_E_CAPACITY, "batch %d exceeds max_batch %d", B, c.max_batch);
@@ -544,13 +551,28 @@ int prefill_begin(DotsEngine* e, const int32_t* ids, const int32_t* lens, int B,
         if (max_new[b] < 1 || lens[b] + max_new[b] > c.max_seq_len)
             return e->fail(DOTS_E_CAPACITY, "slot %d: prompt (%d) + max_new_tokens (%d) exceeds max_seq_len %d", S[b], lens[b], max_new[b], c.max_seq_len);
     }
+    // a leased prompt: hit[b] positions are in the lease's pages; one whose lease needs no tower takes no rows of `vis`
+    std::vector<const prefix_cache::Lease*> lease(B, nullptr);
+    std::vector<int> hit(B, 0);
+    for (int b = 0, t0 = 0; cached && b < B; t0 += L[b], ++b) {
+        if (!leases[b]) continue;
+        lease[b] = e->pc->lease(leases[b]);
+        if (!lease[b]) return e->fail(DOTS_E_INVALID, "prompt %d: lease %d is not held", b, leases[b]);
+        for (int a = 0; a < b; ++a)
+            if (leases[a] == leases[b]) return e->fail(DOTS_E_INVALID, "lease %d given twice", leases[b]);
+        hit[b] = lease[b]->hit_tokens;
+        // the lease was taken for this very prompt: the prompt's blocks find the lease's pages
+        if (!e->pc->eligible(ids + t0, L[b], keys[b]) || !e->pc->matches(leases[b], ids + t0, L[b], keys[b]))
+            return e->fail(DOTS_E_INVALID, "prompt %d: lease %d was not taken for this prompt", b, leases[b]);
+    }
     std::vector<std::vector<int32_t>> src(B);
     int64_t t = 0, vis_used = 0;
     for (int b = 0; b < B; ++b) {
         src[b].resize(L[b]);
+        const bool no_tower = lease[b] && !lease[b]->needs_tower;
         for (int i = 0; i < L[b]; ++i, ++t) {
             const int id = ids[t];
-            if (id == c.image_token_id) src[b][i] = -(int32_t)(++vis_used);
+            if (id == c.image_token_id) src[b][i] = no_tower ? INT32_MIN : -(int32_t)(++vis_used);
             else if (id < 0 || id >= c.vocab_size) return e->fail(DOTS_E_INVALID, "token id %d out of range", id);
             else src[b][i] = id;
         }
@@ -567,15 +589,25 @@ int prefill_begin(DotsEngine* e, const int32_t* ids, const int32_t* lens, int B,
         e->B = 0;
     }
     int need = 0;
-    for (int b = 0; b < B; ++b) need += (admit_tokens(e, L[b], max_new[b]) + 63) / 64;
+    for (int b = 0; b < B; ++b) need += (admit_tokens(e, L[b], max_new[b]) + 63) / 64 - hit[b] / 64;
+    ensure_free(e, need);
     if (need > (int)e->free_pages.size())
-        return e->fail(DOTS_E_CAPACITY, "KV pool exhausted: these sequences need %d pages of 64 tokens, %d of %d are free", need, (int)e->free_pages.size(), e->n_pool_pages);
+        return e->fail(DOTS_E_CAPACITY, "KV pool exhausted: these sequences need %d pages of 64 tokens, %d of %d are free", need, free_count(e), e->n_pool_pages);
     // the buffers of the feature, once: nothing of the slots has changed if one cannot be had
     if (!e->fill_x) CK(e->alloc(&e->fill_x, (size_t)e->n_pool_pages * 64 * H));
     if (!e->fill_rows) CK(e->alloc(&e->fill_rows, (size_t)e->TP));
     if (!e->fill_table) CK(e->alloc(&e->fill_table, (size_t)DOTS_MAX_BATCH * e->max_pages));
     if (!e->fill_items) CK(e->alloc(&e->fill_items, (size_t)(e->TP / 64 + c.max_batch + 1)));
-    for (int b = 0; b < B; ++b) reserve_pages(e, S[b], admit_tokens(e, L[b], max_new[b]));      // cannot fall short: counted above
+    for (int b = 0; b < B; ++b) {
+        auto& mine = e->slot_pages[S[b]];
+        for (int p = 0; p < hit[b] / 64; ++p) {            // one more holder of a cached page, which nobody writes: the cursor starts behind it
+            mine.push_back(lease[b]->chain[p]);
+            e->page_refs[mine.back()] += 1;
+            e->hp_table[(size_t)S[b] * e->max_pages + p] = mine.back();
+        }
+        bool changed = false;
+        grow_pages(e, S[b], admit_tokens(e, L[b], max_new[b]), &changed);      // cannot fall short: counted above
+    }
     struct Guard {
         DotsEngine* e; const std::vector<int>& S; bool armed = true;
         ~Guard() {
@@ -591,11 +623,11 @@ int prefill_begin(DotsEngine* e, const int32_t* ids, const int32_t* lens, int B,
     e->hp_pos.resize(piece); e->hp_src.resize(piece); e->hp_rows.resize(piece);
     for (int b = 0; b < B; ++b) {
         const auto& pages = e->slot_pages[S[b]];
-        for (int p0 = 0; p0 < L[b]; p0 += piece) {
+        for (int p0 = hit[b]; p0 < L[b]; p0 += piece) {
             const int n = std::min(piece, L[b] - p0);
             for (int i = 0; i < n; ++i) {
                 e->hp_pos[i] = i;
-                e->hp_src[i] = src[b][p0 + i];
+                e->hp_src[i] = src[b][p0 + i] == INT32_MIN ? 0 : src[b][p0 + i];      // a row the cache retains: overwritten below
                 e->hp_rows[i] = pages[(p0 + i) / 64] * 64 + (p0 + i) % 64;
             }
             CK(hipMemcpyAsync(e->p_src, e->hp_src.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
@@ -605,19 +637,44 @@ int prefill_begin(DotsEngine* e, const int32_t* ids, const int32_t* lens, int B,
             CK(launch_gather_rows(s, e->p_x, e->p_pos, e->fill_rows, e->fill_x, n, H));
             CK(hipStreamSynchronize(s));                   // the host lists are reused by the next piece
         }
+        // image positions behind the hit of a prompt that ran no tower: the rows the lease's tail block retains, at the same offsets of
+        // its page of the staging buffer (all of them lie in the first page the slot fills: prefix_cache.h)
+        int pad0 = 0, pad_n = 0;
+        if (lease[b] && lease[b]->tail_page >= 0 && e->pc->tail_rows(lease[b]->tail_page, &pad0, &pad_n)) {
+            for (int i = 0; i < pad_n; ++i) {
+                e->hp_pos[i] = lease[b]->tail_page * 64 + pad0 + i;
+                e->hp_rows[i] = pages[hit[b] / 64] * 64 + pad0 + i;
+            }
+            CK(hipMemcpyAsync(e->p_pos, e->hp_pos.data(), (size_t)pad_n * 4, hipMemcpyHostToDevice, s));
+            CK(hipMemcpyAsync(e->fill_rows, e->hp_rows.data(), (size_t)pad_n * 4, hipMemcpyHostToDevice, s));
+            CK(launch_gather_rows(s, e->fill_x, e->p_pos, e->fill_rows, e->fill_x, pad_n, H));
+            CK(hipStreamSynchronize(s));
+        }
     }
     e->fresh_slots.clear();                                // p_src and p_x were overwritten (dots_slots_fork)
     const int W = (c.vocab_size + 31) / 32;
     for (int b = 0; b < B; ++b) {
         DotsEngine::Fill& f = e->fill[S[b]];
         f.on = true;
-        f.L = L[b]; f.max_new = max_new[b]; f.cursor = 0;
+        f.L = L[b]; f.max_new = max_new[b]; f.cursor = hit[b];
         f.order = ++e->fill_order;
         f.src = std::move(src[b]);
         f.seen.assign(W, 0u);
         e->n_filling += 1;
     }
+    for (int b = 0, t0 = 0; cached && b < B; t0 += L[b], ++b) {
+        DotsEngine::Fill& f = e->fill[S[b]];
+        for (int i = 0; i < hit[b]; ++i) f.seen[ids[t0 + i] >> 5] |= 1u << (ids[t0 + i] & 31);      // the presence bits of the skipped positions
+        f.cache = e->pc->eligible(ids + t0, L[b], keys[b]);
+        if (!f.cache) continue;
+        f.ids.assign(ids + t0, ids + t0 + L[b]);
+        f.keyed = keys[b] != nullptr;
+        if (keys[b]) std::memcpy(f.key, keys[b], 16);
+        f.cache_parent = hit[b] ? lease[b]->chain[hit[b] / 64 - 1] : -1;
+    }
     guard.armed = false;
+    for (int b = 0; cached && b < B; ++b)
+        if (leases[b]) e->pc->release(leases[b]);          // the slot holds the pages now
     e->vis_rows = 0;                                       // the tower's rows are in the staging buffer: `vis` is free again
     if (e->pref_deferred) RET(launch_prefetched_tower(e));
     return DOTS_OK;
@@ -714,6 +771,12 @@ int prefill_advance(DotsEngine* e, int max_tokens, int32_t* remaining) {
             const int id = f.src[f.cursor + i] >= 0 ? f.src[f.cursor + i] : c.image_token_id;
             if (id >= 0 && id < V) f.seen[id >> 5] |= 1u << (id & 31);
         }
+        // the full prompt pages this pass completed enter the prefix cache, each behind the one before it
+        for (int k = f.cursor / 64; f.cache && (k + 1) * 64 <= std::min(f.cursor + p.take, f.L); ++k) {
+            const int32_t page = e->slot_pages[p.slot][k];
+            if (e->pc && e->pc->insert(f.cache_parent, f.ids.data(), f.L, k, f.keyed ? f.key : nullptr, page)) f.cache_parent = page;
+            else f.cache = false;                          // an equal block is resident: this one and what follows it stay the slot's own
+        }
         f.cursor += p.take;
     }
     if (n_done) {
@@ -776,6 +839,8 @@ void drop_fill(DotsEngine* e, int slot) {
     f.on = false;
     f.src.clear(); f.src.shrink_to_fit();
     f.seen.clear();
+    f.ids.clear(); f.ids.shrink_to_fit();
+    f.cache = false;
     e->n_filling -= 1;
 }
 
@@ -967,6 +1032,7 @@ void dots_destroy(DotsEngine* e) {
     for (auto& ev : e->ev) if (ev) hipEventDestroy(ev);
     for (auto& ev : e->attn_ev) hipEventDestroy(ev);
     if (e->stream) hipStreamDestroy(e->stream);
+    delete e->pc;
     delete e;
 }
 

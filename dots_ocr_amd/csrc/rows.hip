@@ -623,6 +623,7 @@ int dots_set_speculation(DotsEngine* e, int k, int min_n, int max_n) {
     if (e->slot_mode)
         for (int b = 0; b < e->cfg.max_batch; ++b)
             if (e->slot_active[b] || slot_filling(e, b)) return e->fail(DOTS_E_STATE, "speculation cannot change while slot %d is occupied or filling", b);
+    if (k > 0 && e->pc) return e->fail(DOTS_E_STATE, "the engine cannot speculate while the prefix cache is on (dots_prefix_cache_enable)");
     CK(hipSetDevice(e->device));
     hipStream_t s = e->stream;
     if (k > 0 && !e->sp_stats) {

@@ -35,9 +35,22 @@ void release_pages(DotsEngine* e, int slot) {
     mine.clear();
     std::fill(e->hp_table.begin() + (size_t)slot * e->max_pages, e->hp_table.begin() + (size_t)(slot + 1) * e->max_pages, e->n_pool_pages);
 }
+// ---- the prefix cache's pages in the allocator: a page whose only holder is the index is as good as free.  Every place
+// that counts free pages or takes one calls ensure_free first; with the cache off that is a null test
+void ensure_free(DotsEngine* e, int64_t need) {
+    if (!e->pc || free_count(e) < need) return;           // a request the pool cannot serve evicts nothing
+    while ((int64_t)e->free_pages.size() < need) {
+        const int32_t page = e->pc->evict_one();
+        if (page < 0) return;
+        e->free_pages.push_back(page);
+    }
+}
+int free_count(const DotsEngine* e) { return (int)e->free_pages.size() + (e->pc ? e->pc->evictable_pages() : 0); }
+
 // pages for `tokens` positions of the sequence in `slot` (it holds none yet); false: the pool cannot serve them
 bool reserve_pages(DotsEngine* e, int slot, int tokens) {
     const int need = (tokens + 63) / 64;
+    ensure_free(e, need);
     if (need > (int)e->free_pages.size() || need > e->max_pages) return false;
     auto& mine = e->slot_pages[slot];
     for (int p = 0; p < need; ++p) {
@@ -54,6 +67,7 @@ bool reserve_pages(DotsEngine* e, int slot, int tokens) {
 int grow_pages(DotsEngine* e, int slot, int tokens, bool* changed) {
     auto& mine = e->slot_pages[slot];
     const int need = std::min((tokens + 63) / 64, e->max_pages);
+    ensure_free(e, std::min<int64_t>(need - (int64_t)mine.size(), free_count(e)));      // a pool that runs dry gives what it has
     while ((int)mine.size() < need && !e->free_pages.empty()) {
         e->hp_table[(size_t)slot * e->max_pages + mine.size()] = e->free_pages.back();
         mine.push_back(e->free_pages.back());
@@ -123,6 +137,65 @@ int dots_slots_prefill_advance(DotsEngine* e, int max_tokens, int32_t* remaining
     return prefill_advance(e, max_tokens, remaining);
 }
 
+// ---------------------------------------------------------------------------------- prefix cache
+int dots_prefix_cache_enable(DotsEngine* e, int on) {
+    if (!e) return DOTS_E_INVALID;
+    if (!e->finalized) return e->fail(DOTS_E_STATE, "weights not finalized");
+    if (e->spec_k) return e->fail(DOTS_E_STATE, "the prefix cache cannot be used while the engine speculates (dots_set_speculation)");
+    for (int b = 0; b < e->cfg.max_batch; ++b)
+        if ((e->slot_mode && e->slot_active[b]) || slot_filling(e, b))
+            return e->fail(DOTS_E_STATE, "the prefix cache cannot change while slot %d is occupied or filling", b);
+    if (on && !e->pc) e->pc = new prefix_cache::Index(&e->page_refs, e->n_pool_pages, e->cfg.image_token_id);
+    if (!on && e->pc) {
+        e->pc->clear(&e->free_pages);
+        delete e->pc;
+        e->pc = nullptr;
+    }
+    return DOTS_OK;
+}
+
+int dots_prefix_cache_lookup(DotsEngine* e, const int32_t* ids, int len, const uint8_t* image_key, int32_t* lease, int32_t* hit_tokens, int32_t* needs_tower) {
+    if (!e) return DOTS_E_INVALID;
+    if (!ids || !lease || !hit_tokens || !needs_tower) return e->fail(DOTS_E_INVALID, "null argument");
+    if (!e->pc) return e->fail(DOTS_E_STATE, "the prefix cache is off (dots_prefix_cache_enable)");
+    if (len < 1 || len >= e->cfg.max_seq_len) return e->fail(DOTS_E_CAPACITY, "prompt length %d not in [1, max_seq_len)", len);
+    *lease = *hit_tokens = 0;
+    if (!e->pc->eligible(ids, len, image_key)) {           // bypass: not looked up, not counted
+        *needs_tower = prefix_cache::find_pads(ids, len, e->cfg.image_token_id).n > 0;
+        return DOTS_OK;
+    }
+    int hit = 0, tower = 0;
+    *lease = e->pc->lookup(ids, len, image_key, &hit, &tower);
+    *hit_tokens = hit;
+    *needs_tower = tower;
+    return DOTS_OK;
+}
+
+int dots_prefix_cache_release(DotsEngine* e, int32_t lease) {
+    if (!e) return DOTS_E_INVALID;
+    if (!e->pc) return e->fail(DOTS_E_STATE, "the prefix cache is off (dots_prefix_cache_enable)");
+    if (!e->pc->release(lease)) return e->fail(DOTS_E_INVALID, "lease %d is not held", lease);
+    return DOTS_OK;
+}
+
+int dots_slots_prefill_begin_cached(DotsEngine* e, const int32_t* slots, int n, const int32_t* input_ids, const int32_t* prompt_lens,
+                                    const int32_t* max_new_tokens, const int32_t* leases, const uint8_t* const* image_keys) {
+    if (!e) return DOTS_E_INVALID;
+    if (!e->finalized) return e->fail(DOTS_E_STATE, "weights not finalized");
+    if (!slots || !input_ids || !prompt_lens || !max_new_tokens || !leases || !image_keys) return e->fail(DOTS_E_INVALID, "null argument");
+    CK(hipSetDevice(e->device));
+    return prefill_begin(e, input_ids, prompt_lens, n, slots, max_new_tokens, leases, image_keys);
+}
+
+int dots_prefix_cache_info(DotsEngine* e, int64_t* out6) {
+    if (!e || !out6) return e ? e->fail(DOTS_E_INVALID, "null argument") : DOTS_E_INVALID;
+    if (!e->pc) return e->fail(DOTS_E_STATE, "the prefix cache is off (dots_prefix_cache_enable)");
+    const prefix_cache::Info& i = e->pc->info();
+    out6[0] = i.lookups; out6[1] = i.hit_tokens; out6[2] = i.inserted; out6[3] = i.evicted;
+    out6[4] = e->pc->resident_pages(); out6[5] = e->pc->evictable_pages();
+    return DOTS_OK;
+}
+
 // Parallel sampling: n free slots become copies of the freshly prefilled sequence in src_slot.  Everything is validated and
 // counted before anything changes; the children then share the source's full prompt pages (reference counts), get a copy of its tail page
 // and select their own first token from the source's last-position logits.
@@ -153,9 +226,10 @@ int dots_slots_fork(DotsEngine* e, int src_slot, const int32_t* dst_slots, int n
     const int shared = L / 64, own = (admit_tokens(e, L, max_new) + 63) / 64 - shared;          // own >= 1: the reserve is at least L + 1 tokens
     const auto& src_pages = e->slot_pages[src_slot];
     if ((int)src_pages.size() < shared + (L % 64 ? 1 : 0)) return e->fail(DOTS_E_STATE, "slot %d does not hold its prompt pages", src_slot);
+    ensure_free(e, (int64_t)n * own);
     if (shared + own > e->max_pages || (int64_t)n * own > (int64_t)e->free_pages.size())
         return e->fail(DOTS_E_CAPACITY, "KV pool exhausted: %d forked sequences need %d pages of 64 tokens each, %d of %d are free", n, own,
-                       (int)e->free_pages.size(), e->n_pool_pages);
+                       free_count(e), e->n_pool_pages);
     CK(hipSetDevice(e->device));
     hipStream_t s = e->stream;
     // ---- from here on the call changes state; a failed launch gives the children's pages back (the slots are not marked occupied yet)
@@ -308,9 +382,10 @@ int dots_slots_extend(DotsEngine* e, const int32_t* slots, int n, const int32_t*
         lacking += std::max(0, need - (int)mine.size());
         n_rows += fed[i];
     }
+    ensure_free(e, lacking);
     if (lacking > (int64_t)e->free_pages.size())
         return e->fail(DOTS_E_CAPACITY, "KV pool exhausted: the extended sequences need %d more pages of 64 tokens, %d of %d are free", (int)lacking,
-                       (int)e->free_pages.size(), e->n_pool_pages);
+                       free_count(e), e->n_pool_pages);
     // ---- the call's device buffers (nothing of the slots changes if one cannot be had)
     if (!e->ex_tokens) CK(e->alloc(&e->ex_tokens, DOTS_MAX_BATCH));
     if (!e->ex_ctx) CK(e->alloc(&e->ex_ctx, DOTS_MAX_BATCH));
@@ -428,6 +503,7 @@ int dots_slots_reset(DotsEngine* e) {
         e->pref_pending = e->pref_deferred = false;
     }
     for (int b = 0; b < (int)e->slot_pages.size(); ++b) release_pages(e, b);
+    if (e->pc) e->pc->release_all();                      // the leases of an abandoned serving loop; the cached blocks stay
     RET(beam_clear_all(e));
     e->fresh_slots.clear();
     CK(hipMemcpyAsync(e->block_table, e->hp_table.data(), e->hp_table.size() * 4, hipMemcpyHostToDevice, s));
@@ -724,9 +800,10 @@ int dots_slot_resume(DotsEngine* e, int slot) {
     DotsEngine::Parked& pk = e->parked[slot];
     int need = 0;
     for (int32_t w : pk.pages) need += w < 0;
+    ensure_free(e, need);
     if (need > (int)e->free_pages.size() || (int)pk.pages.size() > e->max_pages)
         return e->fail(DOTS_E_CAPACITY, "KV pool exhausted: slot %d needs %d pages of 64 tokens to resume, %d of %d are free", slot, need,
-                       (int)e->free_pages.size(), e->n_pool_pages);
+                       free_count(e), e->n_pool_pages);
     CK(hipSetDevice(e->device));
     hipStream_t s = e->stream;
     // fresh pages in free-list order, taken off the list only once the copies have landed
@@ -763,14 +840,14 @@ int dots_slots_pages_short(DotsEngine* e, int n_steps, int32_t* pages) {
     int64_t lack = 0;
     for (int b = 0; b < e->cfg.max_batch; ++b)
         if (slot_grows(e, b)) lack += chunk_pages_lacking(e, b, n_steps * (e->spec_k + 1));
-    *pages = (int32_t)std::max<int64_t>(0, lack - (int64_t)e->free_pages.size());
+    *pages = (int32_t)std::max<int64_t>(0, lack - (int64_t)free_count(e));
     return DOTS_OK;
 }
 
 int dots_kv_pool_info(DotsEngine* e, int32_t* total_pages, int32_t* free_pages) {
     if (!e || !total_pages || !free_pages) return DOTS_E_INVALID;
     *total_pages = e->n_pool_pages;
-    *free_pages = (int32_t)e->free_pages.size();
+    *free_pages = (int32_t)free_count(e);
     return DOTS_OK;
 }
 
@@ -786,7 +863,7 @@ int dots_set_kv_scales(DotsEngine* e, const float* scales_host) {
     if (e->n_parked) return e->fail(DOTS_E_STATE, "KV scales cannot change while %d slot(s) are suspended: their KV is parked in host memory", e->n_parked);
     if ((int)e->free_pages.size() != e->n_pool_pages)
         return e->fail(DOTS_E_STATE, "KV scales cannot change while sequences hold KV pages (%d of %d in use): release them first (dots_slots_reset)",
-                       e->n_pool_pages - (int)e->free_pages.size(), e->n_pool_pages);
+                       e->n_pool_pages - free_count(e), e->n_pool_pages);
     CK(hipSetDevice(e->device));
     CK(hipMemcpyAsync(e->kv_scales, scales_host, n * 4, hipMemcpyHostToDevice, e->stream));
     CK(hipStreamSynchronize(e->stream));

@@ -333,6 +333,11 @@ def _prototypes(lib):
         "dots_slots_prefill": (i32, [vp, P(i32), i32, P(i32), P(i32), P(i32)]),
         "dots_slots_prefill_begin": (i32, [vp, P(i32), i32, P(i32), P(i32), P(i32)]),
         "dots_slots_prefill_advance": (i32, [vp, i32, P(i32)]),
+        "dots_prefix_cache_enable": (i32, [vp, i32]),
+        "dots_prefix_cache_lookup": (i32, [vp, P(i32), i32, C.c_char_p, P(i32), P(i32), P(i32)]),
+        "dots_prefix_cache_release": (i32, [vp, i32]),
+        "dots_slots_prefill_begin_cached": (i32, [vp, P(i32), i32, P(i32), P(i32), P(i32), P(i32), P(C.c_char_p)]),
+        "dots_prefix_cache_info": (i32, [vp, P(i64)]),
         "dots_slots_decode": (i32, [vp, i32]),
         "dots_slots_fork": (i32, [vp, i32, P(i32), i32]),
         "dots_slot_logits": (i32, [vp, i32, P(C.c_float)]),
@@ -447,6 +452,7 @@ EXPORTED_SYMBOLS = [
     "dots_slots_beam", "dots_beam_info", "dots_beam_read",
     "dots_stop_create", "dots_stop_destroy", "dots_set_row_stop", "dots_row_stop_hit",
     "dots_op_flash_attn_paged", "dots_slots_prefill_begin", "dots_slots_prefill_advance",
+    "dots_prefix_cache_enable", "dots_prefix_cache_lookup", "dots_prefix_cache_release", "dots_slots_prefill_begin_cached", "dots_prefix_cache_info",
 ]
 
 MAX_SPEC_DRAFTS = 15                         # DOTS_MAX_SPEC_DRAFTS: drafts per slot and step
@@ -1212,6 +1218,52 @@ class Engine:
         self.slots_prefill_begin(slots, input_ids, prompt_lens, max_new_tokens)
         while self.slots_prefill_advance(chunk) > 0:
             pass
+
+    # prefix cache over the chunked prefill
+    def prefix_cache_enable(self, on: bool = True):
+        """Full prompt pages written by chunked fills stay resident and are reused by later prompts that begin with the same blocks (and the
+        same image key).  Refused while a slot is occupied or filling and on a speculating engine; off drops every block."""
+        self._ck(self.lib.dots_prefix_cache_enable(self.h, 1 if on else 0), "dots_prefix_cache_enable")
+
+    @staticmethod
+    def _image_key(key):
+        if key is None:
+            return None
+        key = bytes(key)
+        if len(key) != 16:
+            raise ValueError(f"an image key is 16 bytes, got {len(key)}")
+        return key
+
+    def prefix_cache_lookup(self, input_ids: np.ndarray, image_key: Optional[bytes] = None):
+        """-> (lease, hit_tokens, needs_tower).  The lease (0: none) pins the matched pages until slots_prefill_begin_cached takes it or
+        prefix_cache_release gives it back; needs_tower False: the prompt's fill needs no vit_forward."""
+        ids = np.ascontiguousarray(input_ids, dtype=np.int32)
+        lease, hit, tower = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        self._ck(self.lib.dots_prefix_cache_lookup(self.h, _i32p(ids), ids.shape[0], self._image_key(image_key), C.byref(lease), C.byref(hit), C.byref(tower)),
+                 "dots_prefix_cache_lookup")
+        return int(lease.value), int(hit.value), bool(tower.value)
+
+    def prefix_cache_release(self, lease: int):
+        self._ck(self.lib.dots_prefix_cache_release(self.h, int(lease)), "dots_prefix_cache_release")
+
+    def slots_prefill_begin_cached(self, slots: Sequence[int], input_ids: np.ndarray, prompt_lens: Sequence[int], max_new_tokens: Sequence[int],
+                                   leases: Sequence[int], image_keys: Sequence[Optional[bytes]]):
+        """slots_prefill_begin with one lease (0: none) and one image key (None: none) per prompt: a leased prompt starts behind its cached
+        pages, and the full prompt pages these fills complete enter the cache.  A refused call leaves the leases held."""
+        sl = np.ascontiguousarray(slots, dtype=np.int32)
+        ids = np.ascontiguousarray(input_ids, dtype=np.int32)
+        lens = np.ascontiguousarray(prompt_lens, dtype=np.int32)
+        cap = np.ascontiguousarray(max_new_tokens, dtype=np.int32)
+        ls = np.ascontiguousarray(leases, dtype=np.int32)
+        assert sl.shape == lens.shape == cap.shape == ls.shape and ids.shape[0] == int(lens.sum()) and len(image_keys) == sl.shape[0]
+        keys = (C.c_char_p * sl.shape[0])(*[self._image_key(k) for k in image_keys])
+        self._ck(self.lib.dots_slots_prefill_begin_cached(self.h, _i32p(sl), sl.shape[0], _i32p(ids), _i32p(lens), _i32p(cap), _i32p(ls), keys),
+                 "dots_slots_prefill_begin_cached")
+
+    def prefix_cache_info(self) -> dict:
+        out = (C.c_int64 * 6)()
+        self._ck(self.lib.dots_prefix_cache_info(self.h, out), "dots_prefix_cache_info")
+        return dict(zip(("lookups", "hit_tokens", "inserted", "evicted", "resident", "evictable"), (int(v) for v in out)))
 
     def slots_fork(self, src: int, dst_slots: Sequence[int]):
         """Parallel sampling: every free slot of dst_slots becomes a copy of the sequence slots_prefill just put into slot src (no decode

@@ -137,7 +137,7 @@ class DotsOcrHipForCausalLM:
                  no_repeat_ngram_whitelist=None, speculative_ngram: Optional[int] = None, prompt_lookup_min: int = 2, prompt_lookup_max: int = 4,
                  num_return_sequences: int = 1, stop_strings=None, speculative_rows=None, num_beams: Optional[int] = None,
                  length_penalty: float = 1.0, early_stopping=None, speculative_guided: bool = False, prompt_suffixes=None, speculative_shaped=None,
-                 prefill_chunk: Optional[int] = None, **_):
+                 prefill_chunk: Optional[int] = None, enable_prefix_caching: bool = False, image_keys=None, **_):
         """HF-shaped generate.  do_sample / temperature / top_p default to the checkpoint's generation_config.json (greedy when it
         is absent); with sampling on, tokens are drawn on the GPU from softmax(logits / temperature) restricted to the top_p
         nucleus, reproducibly from `seed`.  Returns LongTensor
@@ -215,7 +215,13 @@ class DotsOcrHipForCausalLM:
         prefill_chunk (N, a multiple of 64 and at most the engine's max_prefill_tokens; None = off) fills every prompt in passes of N
         positions between which the sequences already running keep decoding (ContinuousBatcher(prefill_chunk=)), and
         admits prompts longer than the prefill workspace.  The tokens do not depend on N.  It runs on the continuous path and is refused
-        together with speculative_ngram or continuous=False."""
+        together with speculative_ngram or continuous=False.
+
+        enable_prefix_caching (with prefill_chunk) keeps the full KV pages of the prompts it fills, in this call and in later ones, and
+        starts a prompt that begins with the same tokens and the same image behind them (ContinuousBatcher(prefix_caching=True), DESIGN
+        §6.13): the same tokens as without it.  image_keys: per sequence 16 bytes that name its image (or None) — the caller's promise that
+        equal keys mean equal pixels and grid, for instance a digest of the decoded image's bytes and size; a sequence with an image and
+        no key bypasses the cache."""
         import dataclasses
         import torch
         t_eff, p_eff = resolve_sampling(self.generation_config, do_sample, temperature, top_p)
@@ -231,6 +237,10 @@ class DotsOcrHipForCausalLM:
             if speculative_ngram:
                 raise ValueError("prefill_chunk cannot be combined with speculative_ngram: a speculating engine fills a prompt in one pass")
             continuous = True
+        if enable_prefix_caching and prefill_chunk is None:
+            raise ValueError("enable_prefix_caching needs prefill_chunk: only pages written by a chunked fill are cached")
+        if image_keys is not None and (not enable_prefix_caching or len(image_keys) != int(input_ids.shape[0])):
+            raise ValueError("image_keys needs enable_prefix_caching and one entry (16 bytes or None) per sequence")
         if early_stopping is not None:
             raise ValueError("early_stopping is not offered: a beam group ends at its cap, or early only where that is exact (DESIGN §6.9)")
         beam = None
@@ -374,7 +384,8 @@ class DotsOcrHipForCausalLM:
                                                    penalties=bool(spec_shaped & SPEC_SHAPED["penalties"]))
         try:
             return self._generate(input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens, eos_token_id, pad_token_id, continuous,
-                                  row_sp, rules, guide, ngram, nrs, stop, int(min_tokens or 0), beam, suffixes, prefill_chunk)
+                                  row_sp, rules, guide, ngram, nrs, stop, int(min_tokens or 0), beam, suffixes, prefill_chunk,
+                                  (image_keys or [None] * int(input_ids.shape[0])) if enable_prefix_caching else None)
         finally:
             if spec_k:
                 try:
@@ -397,7 +408,7 @@ class DotsOcrHipForCausalLM:
                     warnings.warn(f"guide {guide} could not be destroyed: {e}")
 
     def _generate(self, input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens, eos_token_id, pad_token_id, continuous, row_sp, rules,
-                  guide, ngram=None, nrs=1, stop=None, stop_min=0, beam=None, suffixes=None, prefill_chunk=None):
+                  guide, ngram=None, nrs=1, stop=None, stop_min=0, beam=None, suffixes=None, prefill_chunk=None, image_keys=None):
         import torch
         if suffixes:
             nrs = len(suffixes)                      # the rows of the result: one per suffix, laid out as num_return_sequences lays them out
@@ -457,12 +468,18 @@ class DotsOcrHipForCausalLM:
                     reqs.append(Request(prompts[b], pix, grid[img_of_seq[b][0]:img_of_seq[b][-1] + 1], max_new_tokens,
                                         sampling=row_sp(b) if row_sp else None, rules=rules, guide=guide, ngram=ngram, n=1 if suffixes else nrs,
                                         stop=stop, suffixes=suffixes))
+                    if image_keys and image_keys[b] is not None:      # the caller names the image; the grid it was resized to is part of what is cached
+                        import hashlib
+                        reqs[-1].image_key = hashlib.blake2b(bytes(image_keys[b]) + reqs[-1].grid_thw.tobytes(), digest_size=16).digest()
                 else:
                     reqs.append(Request(prompts[b], None, None, max_new_tokens, sampling=row_sp(b) if row_sp else None, rules=rules, guide=guide,
                                         ngram=ngram, n=1 if suffixes else nrs, stop=stop, suffixes=suffixes))
                 if beam is not None:             # a group of beam[0] beams that returns its nrs best hypotheses
                     reqs[-1].n, reqs[-1].num_beams, reqs[-1].num_return, reqs[-1].length_penalty = 1, beam[0], nrs, beam[1]
-            outs = ContinuousBatcher(self.engine, eos_ids=eos, **({} if prefill_chunk is None else {"prefill_chunk": prefill_chunk})).run(reqs)
+            chunk_kw = {} if prefill_chunk is None else {"prefill_chunk": prefill_chunk}
+            if image_keys is not None:           # enable_prefix_caching
+                chunk_kw["prefix_caching"] = True
+            outs = ContinuousBatcher(self.engine, eos_ids=eos, **chunk_kw).run(reqs)
             if beam is not None:                 # row i * n + j = the j-th best hypothesis of prompt i (a prompt with fewer: pad rows)
                 outs = [r.outputs[j] if j < len(r.outputs) else np.zeros(0, np.int64) for r in reqs for j in range(nrs)]
             elif nrs > 1:                        # row i * n + j = sequence j of prompt i

@@ -36,8 +36,14 @@ class DotsOCRParser:
                  hf_max_new_tokens=24000, guided=False, no_repeat_ngram_size=None, no_repeat_ngram_window=None,
                  no_repeat_ngram_whitelist=None, speculative_ngram=None, prompt_lookup_min=2, prompt_lookup_max=4, stop=None,
                  speculative_rows=None, num_beams=None, length_penalty=1.0, speculative_guided=False, speculative_shaped=None,
-                 prefill_chunk=None):
+                 prefill_chunk=None, enable_prefix_caching=False):
         self.dpi = dpi
+        # prefix caching, opt-in over prefill_chunk: the in-process model keeps the full KV pages of the pages it has read and
+        # starts a page it meets again — with another prompt, or in a retry — behind them, keyed on the decoded image's bytes and size.  A
+        # server caches by its own --enable-prefix-caching flag: requests carry nothing.
+        self.enable_prefix_caching = bool(enable_prefix_caching)
+        if self.enable_prefix_caching and prefill_chunk is None:
+            raise ValueError("enable_prefix_caching needs prefill_chunk")
         # chunked prefill, opt-in: the in-process model fills every page's prompt in passes of prefill_chunk positions
         # between which the pages already running keep decoding (same tokens).  A server chunks by its own --enable-chunked-prefill flag, as
         # vLLM does: requests carry nothing.
@@ -157,10 +163,28 @@ class DotsOCRParser:
             kw.update(num_beams=self.num_beams, length_penalty=self.length_penalty, do_sample=False)
         if self.prefill_chunk is not None:
             kw["prefill_chunk"] = self.prefill_chunk
+        if self.enable_prefix_caching:
+            kw.update(enable_prefix_caching=True, image_keys=[self._image_key(im) for im in images])
         generated = self.model.generate(**inputs, max_new_tokens=self.hf_max_new_tokens, **kw)
         trimmed = [out[len(inp):] for inp, out in zip(inputs.input_ids, generated)]
         texts = self.processor.batch_decode(trimmed, skip_special_tokens=True, clean_up_tokenization_spaces=False)
         return self._cut_at_stops(trimmed, texts)
+
+    @staticmethod
+    def _image_key(image, grid=None) -> Optional[bytes]:
+        """16 bytes that name a decoded image for the prefix cache: blake2b over its mode, size and bytes (and the grid it was resized to,
+        where the caller knows it: generate() adds it itself)"""
+        if image is None:
+            return None
+        import hashlib
+        h = hashlib.blake2b(digest_size=16)
+        h.update(repr((image.mode, image.size, None if grid is None else grid.tolist())).encode())
+        h.update(image.tobytes())
+        return h.digest()
+
+    def _chunk_kw(self) -> dict:
+        kw = {} if self.prefill_chunk is None else {"prefill_chunk": self.prefill_chunk}
+        return dict(kw, prefix_caching=True) if self.enable_prefix_caching else kw
 
     def _cut_at_stops(self, trimmed, texts) -> List[str]:
         if self.stop:                               # the ids end at the token that completed a match: cut the text where the match starts
@@ -345,7 +369,7 @@ class DotsOCRParser:
         t, p_ = resolve_sampling(getattr(self.model, "generation_config", None))
         engine.set_sampling(t, p_, 0)
         eos = list(self.model.config.eos_token_ids)
-        cb = ContinuousBatcher(engine, eos_ids=eos, **({} if self.prefill_chunk is None else {"prefill_chunk": self.prefill_chunk}))
+        cb = ContinuousBatcher(engine, eos_ids=eos, **self._chunk_kw())
         n = len(images)
         results = [None] * n
         with ThreadPool(max(1, min(8, self.num_thread, n))) as prep_pool, ThreadPool(max(1, min(8, self.num_thread, n))) as post_pool:
@@ -358,8 +382,9 @@ class DotsOCRParser:
                     inputs = self._build_inputs([image], [prompt])
                     ids = inputs["input_ids"][0]
                     ids = ids[inputs["attention_mask"][0].bool()].cpu().numpy()
-                    cb.submit(Request(ids, inputs.get("pixel_values"), None if "image_grid_thw" not in inputs
-                                      else inputs["image_grid_thw"].cpu().numpy(), self.hf_max_new_tokens, tag=nxt))
+                    grid = None if "image_grid_thw" not in inputs else inputs["image_grid_thw"].cpu().numpy()
+                    cb.submit(Request(ids, inputs.get("pixel_values"), grid, self.hf_max_new_tokens, tag=nxt,
+                                      image_key=self._image_key(image, grid) if self.enable_prefix_caching and grid is not None else None))
                     nxt += 1
                 for _, req, toks in cb.step():
                     i = req.tag

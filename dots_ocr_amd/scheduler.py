@@ -67,6 +67,8 @@ class Request:
                                                 # suffixes[i] — one tower, one prefill of the prefix, one fork, one Engine.slots_extend.  Sequence i
                                                 # runs under `sampling` with seed + i; the finished request carries outputs, logprobs_out, stop_hit
                                                 # and kv_truncated_each in suffix order, exactly like n > 1
+    image_key: Optional[bytes] = None           # prefix caching: 16 bytes, the caller's promise that equal keys mean equal pixels and
+                                                # grid.  An image request without one bypasses the cache.  A finished request carries cached_tokens
 
     @property
     def seqs(self) -> int:
@@ -90,8 +92,21 @@ class ContinuousBatcher:
 
     def __init__(self, engine, eos_ids: Sequence[int] = (), chunk: int = 16, headroom_pages: Optional[int] = 2, prefetch: int = 0,
                  tower_steps_per_page: int = 48, admit_group: Optional[int] = None, preemption: Optional[str] = None,
-                 swap_pages: Optional[int] = None, prefill_chunk: Optional[int] = None):
+                 swap_pages: Optional[int] = None, prefill_chunk: Optional[int] = None, prefix_caching: Optional[bool] = None):
         self.engine = engine
+        # prefix caching, over the chunked prefill only.  Admission and the look-ahead ask the engine first
+        # (Engine.prefix_cache_lookup): a request starts its fill behind the pages it hit, takes that many pages less, and — when the lookup
+        # says so — sends no pixels to the tower.  The lease a lookup returns pins those pages until the begin that takes it; every path that
+        # gives a request back to the queue gives its lease back to the engine
+        if prefix_caching:
+            if prefill_chunk is None:
+                raise ValueError("prefix_caching needs prefill_chunk: only pages written by a chunked fill are cached")
+            if not all(hasattr(engine, f) for f in ("prefix_cache_enable", "prefix_cache_lookup", "prefix_cache_release", "slots_prefill_begin_cached")):
+                raise ValueError("this engine has no prefix cache (no prefix_cache_lookup): prefix_caching is not available")
+        self.prefix_caching = bool(prefix_caching)
+        self._leases: Dict[int, Tuple[int, int, bool]] = {}      # request id -> (lease, hit tokens, needs the tower) of a lookup not yet consumed
+        self.prefix_hits = 0                                     # requests whose fill began behind cached pages
+        self.prefix_hit_tokens = 0                               # ... and the positions they skipped
         # chunked prefill.  None: an admitted group is prefilled in one pass (Engine.slots_prefill), during which nothing
         # decodes.  N: admission only BEGINS the group's fill (Engine.slots_prefill_begin); every step then runs at most one pass of N
         # positions (Engine.slots_prefill_advance) and its decode chunk, so no decode chunk waits for more than one pass, and a prompt
@@ -181,6 +196,8 @@ class ContinuousBatcher:
             for s in range(self.n_slots):
                 if fin[s] >= 0:
                     engine.slot_release(s)
+        if self.prefix_caching:                      # after the reset: no slot is occupied or filling
+            engine.prefix_cache_enable(True)
         if preemption == "swap":                     # after the reset: nothing is parked any more, the host space may change
             engine.kv_swap_reserve(int(engine.kv_pool_info()[0]) if swap_pages is None else max(0, int(swap_pages)))
 
@@ -371,34 +388,61 @@ class ContinuousBatcher:
         committed = self._running_worst() + sum(self._worst_pages(r) for r in admitted)
         return committed + sum(self._worst_pages(r) for r in new) <= total
 
+    # ------------------------------------------------------------------ prefix caching
+    def _lookup(self, rid: int, req: Request) -> Tuple[int, int, bool]:
+        """(lease, hit tokens, needs the tower) of the request: the engine's answer, held until _prefill consumes it or _unlease drops it.
+        Off: no lease, no hit, the tower whenever there are patches — and no engine call"""
+        if not self.prefix_caching:
+            return 0, 0, req.n_patches() > 0
+        if rid not in self._leases:
+            ids = np.ascontiguousarray(req.input_ids, dtype=np.int32).reshape(-1)
+            self._leases[rid] = self.engine.prefix_cache_lookup(ids, req.image_key)
+        return self._leases[rid]
+
+    def _unlease(self, rids):
+        """the requests go back to the queue (or nowhere): their leases go back to the engine"""
+        for rid in rids:
+            lease = self._leases.pop(rid, (0, 0, True))[0]
+            if lease:
+                self.engine.prefix_cache_release(lease)
+
+    def _tower_patches(self, rid: int, req: Request) -> int:
+        """patches the request sends to the tower: none when its image rows are cached"""
+        return req.n_patches() if self._lookup(rid, req)[2] else 0
+
     def plan_admission(self) -> List[Tuple[int, int, Request]]:
         """FIFO: pop requests while a slot is free and the group fits the ViT and prefill workspaces.
         Lowest slots first, so the decode graph covers as few rows as possible."""
         if self.suspended:
             return []                                # nothing new while anything is suspended: the pool's room goes to the resumes first
         free = self.free_slots()
-        group, patches, tokens = [], 0, 0
+        group, patches, tokens, planned = [], 0, 0, 0
         pages_free = self.engine.kv_pool_info()[1] if hasattr(self.engine, "kv_pool_info") else 1 << 30
         while self.pending and free and (self.admit_group is None or len(group) < self.admit_group):
             rid, req = self.pending[0]
-            p, t = req.n_patches(), int(req.input_ids.shape[0])
             if req.width > len(free):
                 break                                # n sequences (or beams) need n slots: the head of the queue waits for them, nothing overtakes it
+            p, t = self._tower_patches(rid, req), int(req.input_ids.shape[0])
             # the prefill workspace bounds a group that is prefilled in one pass; a group filled in passes is bounded by the pool alone
             if group and (patches + p > self.max_patches or (self.prefill_chunk is None and tokens + t > self.max_prefill_tokens)):
+                self._unlease([rid])                 # not in this group: it is looked up again when its turn comes
                 break
             # paged KV, on demand: a sequence reserves its prompt + ADMIT_AHEAD tokens now and grows page by page; admit only while every
             # running sequence (and this one) could still take `headroom` more pages, so that a dry pool — which ends a sequence early
             # at what its pages hold — stays the exception.  Nothing running: admit whatever fits (submit() checked that it can).
-            need = self._group_pages(req)
+            need = self._group_pages(req) - self._lookup(rid, req)[1] // 64      # the pages it hit are there already
+            if self.prefix_caching:                  # ... and its lease took them out of the free count: read it again, less what this group plans to take
+                pages_free = self.engine.kv_pool_info()[1] - planned
             taken = len(self.running) + sum(r.width for _, _, r in self.filling) + sum(r.width for _, _, r in group)
             busy = bool(self.running or self.filling or group)
             reserve = self.headroom_pages * (taken + req.width) if busy else 0
-            if busy and not self._fits_full_reservation([r for _, _, r in group], [req]):
-                break                                # worst case of everything in flight must fit the pool (submit() checked a lone request)
-            if need + reserve > pages_free:
-                break                                                                    # wait for a running sequence to return its pages
+            if (busy and not self._fits_full_reservation([r for _, _, r in group], [req])) or need + reserve > pages_free:
+                # the worst case of everything in flight must fit the pool (submit() checked a lone request), and the admission pages must
+                # be free now: wait for a running sequence to return its pages
+                self._unlease([rid])
+                break
             pages_free -= need
+            planned += need
             self.pending.popleft()
             group.append((free.pop(0), rid, req))
             if req.width > 1:
@@ -487,14 +531,25 @@ class ContinuousBatcher:
                     self._set_rows(k, r, j)
             except Exception:
                 self._clear_rows(every)              # nothing of this group stays behind; the caller puts the group back in the queue
+                self._unlease([rid for _, rid, _ in group])
                 raise
         try:
-            if self.prefill_chunk is not None:
+            if self.prefix_caching:
+                got = [self._lookup(rid, r) for _, rid, r in group]
+                self.engine.slots_prefill_begin_cached(slots, np.concatenate([r.input_ids for _, _, r in group]), lens, caps, [g[0] for g in got],
+                                                       [r.image_key for _, _, r in group])
+                for (_, rid, r), (_, hit, _) in zip(group, got):             # the begin consumed the leases
+                    del self._leases[rid]
+                    r.cached_tokens = hit
+                    self.prefix_hits += hit > 0
+                    self.prefix_hit_tokens += hit
+            elif self.prefill_chunk is not None:
                 self.engine.slots_prefill_begin(slots, np.concatenate([r.input_ids for _, _, r in group]), lens, caps)
             else:
                 self.engine.slots_prefill(slots, np.concatenate([r.input_ids for _, _, r in group]), lens, caps)
         except Exception:
             self._clear_rows(every)                  # the slots stay free
+            self._unlease([rid for _, rid, _ in group])
             raise
         if self.prefill_chunk is not None:           # the slots are filling: _advance_fill takes it from here, pass by pass
             self.filling += group
@@ -568,11 +623,12 @@ class ContinuousBatcher:
                 kept.append((s, rid, r))
             except Exception as e:
                 self._clear_rows([s] + self._kids.pop(rid, []))
+                self._unlease([rid])
                 r.error = RequestRejected(str(e))
                 self._rejected.append((rid, r))
         if not kept:
             return
-        with_img = [(rid, r) for _, rid, r in kept if r.n_patches() > 0]
+        with_img = [(rid, r) for _, rid, r in kept if self._tower_patches(rid, r) > 0]      # a request whose image rows are cached sends no pixels
         if with_img:
             pv, grid, on_dev, keep = self._pixels(with_img)
             self.engine.vit_forward(pv, grid, on_device=on_dev)
@@ -591,7 +647,7 @@ class ContinuousBatcher:
         if self.running and hasattr(self.engine, "vit_ready") and not self.engine.vit_ready():
             return False
         if hasattr(self.engine, "kv_pool_info"):
-            need = sum(self._group_pages(r) for _, r in self._ahead)
+            need = sum(self._group_pages(r) - self._lookup(rid, r)[1] // 64 for rid, r in self._ahead)
             reserve = self.headroom_pages * (len(self.running) + sum(r.width for _, r in self._ahead)) if self.running else 0
             if need + reserve > self.engine.kv_pool_info()[1]:
                 return False
@@ -612,6 +668,7 @@ class ContinuousBatcher:
             # the rows are gone (or were never there): the group goes back to the head of the queue so that the caller's failure
             # handling — which walks `pending` and `running` — sees its requests, and the next step does not take a stale batch
             self._ahead, self._ahead_keep = [], None
+            self._unlease([rid for rid, _ in group])
             self.pending.extendleft(reversed(group))
             raise
         self._ahead, self._ahead_keep = [], None
@@ -638,12 +695,16 @@ class ContinuousBatcher:
                 break
         while self.pending and sum(r.width for _, r in group) + self.pending[0][1].width <= cap:      # cap counts slots: a request takes n of them
             rid, req = self.pending[0]
-            p, t = req.n_patches(), int(req.input_ids.shape[0])
-            pg = self._group_pages(req)
+            # a request whose image rows are cached needs no tower: like a text-only request it ends the group and goes through the ordinary
+            # admission in its turn.  The others keep their lease while their tower runs ahead: _admit_ahead's begin relies on it
+            p, t = self._tower_patches(rid, req), int(req.input_ids.shape[0])
+            pg = self._group_pages(req) - self._lookup(rid, req)[1] // 64
             if (p == 0 or patches + p > self.max_patches or (self.prefill_chunk is None and tokens + t > self.max_prefill_tokens)
                     or pages + pg > total_pages):
+                self._unlease([rid])
                 break                                # a text-only request goes through the ordinary admission, in its turn
             if self.full_reservation and sum(self._worst_pages(r) for _, r in group) + self._worst_pages(req) > total_pages:
+                self._unlease([rid])
                 break                                # full reservation: the group must fit an EMPTY pool by its worst case (its tower may run ahead;
                                                      # _admit_ahead holds it back until it also fits beside what is still running)
             self.pending.popleft()
@@ -655,6 +716,7 @@ class ContinuousBatcher:
             pv, grid, on_dev, keep = self._pixels(group)
             self.engine.vit_prefetch(pv, grid, on_device=on_dev)
         except Exception:
+            self._unlease([rid for rid, _ in group])
             self.pending.extendleft(reversed(group))     # nothing was prefetched: the requests keep their place in the queue
             raise
         self._ahead, self._ahead_keep = group, keep
@@ -817,6 +879,7 @@ class ContinuousBatcher:
                         for k in [s] + self._kids.pop(rid, []):
                             self.running.pop(k, None)
                             self._seq_index.pop(k, None)
+                    self._unlease([rid for _, rid, _ in group])
                     self.pending.extendleft(reversed([(rid, r) for _, rid, r in group if getattr(r, "error", None) is None]))
                     raise
         self._look_ahead()

@@ -525,6 +525,38 @@ int dots_slots_extend(DotsEngine* e, const int32_t* slots_host, int n, const int
 int dots_slots_prefill_begin(DotsEngine* e, const int32_t* slots_host, int n, const int32_t* input_ids_host, const int32_t* prompt_lens_host,
                              const int32_t* max_new_tokens_host);
 int dots_slots_prefill_advance(DotsEngine* e, int max_tokens, int32_t* remaining);
+/* ---- Prefix cache over the chunked prefill, off until switched on: full prompt pages (64 positions) that a pass of
+ * dots_slots_prefill_advance wrote stay resident after their sequence is released, indexed by (the block before, the 64 token ids, the
+ * 16-byte key of the prompt's image if a pad lies in the block or before it), and a later prompt that begins with the same blocks starts
+ * its fill behind them.  Such a fill equals the cold chunked fill of the same prompt in every bit.  The index holds one reference on every
+ * cached page; a page held by the index alone is evicted (least recently used first, deepest block first among equally old) whenever the
+ * free list cannot serve a request, and counts as free in dots_kv_pool_info, dots_slots_pages_short and every admission check.  A prompt
+ * with more than one image, or with an image and no key, is neither looked up nor inserted.  The key is the caller's promise that equal
+ * keys mean equal pixels and grid.
+ *
+ * dots_prefix_cache_enable   on != 0 / 0.  DOTS_E_STATE while a slot is occupied or filling, and on a speculating engine (which in turn
+ *                            cannot start to speculate while the cache is on).  Off drops every block and lease; the pages return.
+ * dots_prefix_cache_lookup   walks the blocks of ids_host[0 .. len).  *hit_tokens = min(64 * matched, 64 * ((len - 1) / 64)): at least
+ *                            one position is always computed.  *needs_tower = 0 when no image position lies at or behind *hit_tokens,
+ *                            or when a resident block retains the tower's rows for all of them (they end in the page behind the hit).
+ *                            *lease (> 0) holds a reference on every page the answer relies on until it is given to
+ *                            dots_slots_prefill_begin_cached or to dots_prefix_cache_release; 0: nothing matched, or the prompt
+ *                            bypasses the cache (then nothing is counted either).  image_key: 16 bytes or NULL.
+ * dots_prefix_cache_release  gives an unused lease back (DOTS_E_INVALID: not held).
+ * dots_slots_prefill_begin_cached  dots_slots_prefill_begin + per prompt a lease (0: none) and an image key (NULL: none).  A leased
+ *                            prompt's table row names the lease's pages first; only the other pages are reserved and only positions
+ *                            at or behind the hit are embedded and filled.  Run dots_vit_forward for exactly the prompts that hold
+ *                            image tokens and no lease with needs_tower == 0.  The full prompt pages these fills complete are inserted
+ *                            as their pass is issued.  A lease is consumed by success only: a refused call leaves it held.
+ *                            dots_slots_prefill_begin itself never looks up and never inserts.
+ * dots_prefix_cache_info     int64 [6]: lookups, hit tokens, blocks inserted, blocks evicted, resident pages, evictable pages. */
+int dots_prefix_cache_enable(DotsEngine* e, int on);
+int dots_prefix_cache_lookup(DotsEngine* e, const int32_t* ids_host, int len, const uint8_t* image_key, int32_t* lease, int32_t* hit_tokens,
+                             int32_t* needs_tower);
+int dots_prefix_cache_release(DotsEngine* e, int32_t lease);
+int dots_slots_prefill_begin_cached(DotsEngine* e, const int32_t* slots_host, int n, const int32_t* input_ids_host, const int32_t* prompt_lens_host,
+                                    const int32_t* max_new_tokens_host, const int32_t* leases_host, const uint8_t* const* image_keys);
+int dots_prefix_cache_info(DotsEngine* e, int64_t* out6);
 int dots_slots_decode(DotsEngine* e, int n_steps);
 int dots_slots_poll(DotsEngine* e, int32_t* finished_host, int32_t* out_lens_host);
 int dots_slot_read(DotsEngine* e, int slot, int32_t* out_ids_host, int capacity, int32_t* n_out);
