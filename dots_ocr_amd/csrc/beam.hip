@@ -321,15 +321,7 @@ int dots_slots_beam(DotsEngine* e, int src_slot, const int32_t* dst_slots, int n
         return e->fail(DOTS_E_STATE, "slot %d cannot start a beam group: only a sequence of the most recent dots_slots_prefill, before any decode step", src_slot);
     if (V > LP_MAX_V) return e->fail(DOTS_E_INVALID, "beam search supports vocabularies up to %d", LP_MAX_V);
     if ((size_t)e->max_pages * DOTS_MAX_BEAMS * 4 > 48 * 1024) return e->fail(DOTS_E_INVALID, "beam search supports max_seq_len up to %d", 48 * 1024 / (DOTS_MAX_BEAMS * 4) * 64);
-    for (int i = 0; i < n_dst; ++i) {
-        const int d = dst_slots[i];
-        if (d < 0 || d >= mb) return e->fail(DOTS_E_INVALID, "slot %d out of range [0, %d)", d, mb);
-        if (d == src_slot) return e->fail(DOTS_E_INVALID, "slot %d is the source of the group", d);
-        if (e->slot_active[d]) return e->fail(DOTS_E_STATE, "slot %d is occupied", d);
-        if (slot_filling(e, d)) return e->fail(DOTS_E_STATE, "slot %d is filling", d);
-        for (int a = 0; a < i; ++a)
-            if (dst_slots[a] == d) return e->fail(DOTS_E_INVALID, "slot %d listed twice", d);
-    }
+    for (int i = 0; i < n_dst; ++i) RET(check_free_slot(e, dst_slots, i, src_slot, "group"));
     for (int i = 0; i < B; ++i) {
         const int r = i ? dst_slots[i - 1] : src_slot;
         if (e->stage.staged(r) || e->row_lp[r] >= 0)
@@ -353,25 +345,15 @@ int dots_slots_beam(DotsEngine* e, int src_slot, const int32_t* dst_slots, int n
     hipStream_t s = e->stream;
     RET(ensure_beam_state(e));
     // ---- from here on the call changes state; a failed launch gives the children's pages back (the source keeps what it grew by)
-    struct BeamGuard {
-        DotsEngine* e; const int32_t* dst; int n; bool armed = true;
-        ~BeamGuard() {
-            if (!armed) return;
-            for (int i = 0; i < n; ++i) { release_pages(e, dst[i]); (void)upload_table_row(e, dst[i]); }
-        }
-    } guard{e, dst_slots, n_dst};
+    PageGuard guard{e, dst_slots, n_dst, true};
     BeamGroupDev gd{};
     gd.B = B; gd.first = shared;
     int32_t stage[3 * DOTS_MAX_BATCH] = {0};
+    std::vector<LiveRow> live(B);
     for (int i = 0; i < B; ++i) {
         const int d = i ? dst_slots[i - 1] : src_slot;
         auto& mine = e->slot_pages[d];
-        if (i)
-            for (int p = 0; p < shared; ++p) {             // one more holder of a page nobody writes any more
-                mine.push_back(src_pages[p]);
-                e->page_refs[src_pages[p]] += 1;
-                e->hp_table[(size_t)d * e->max_pages + p] = src_pages[p];
-            }
+        if (i) share_pages(e, d, src_pages.data(), shared);
         bool changed = false;
         grow_pages(e, d, (shared + own) * 64, &changed);   // cannot fall short: counted above
         CK(upload_table_row(e, d));                        // the last upload of this row: from here on the device reorders it
@@ -384,22 +366,17 @@ int dots_slots_beam(DotsEngine* e, int src_slot, const int32_t* dst_slots, int n
         gd.cum[i] = i ? -INFINITY : 0.f;
         gd.par[i] = 0;
         gd.copy_dst[i] = -1;
+        live[i] = LiveRow{d, L, max_new};
     }
     CK(hipMemcpyAsync(e->fk_dev, stage, sizeof(stage), hipMemcpyHostToDevice, s));
-    if (L % 64) {                                          // the tail page, as a fork copies it
-        const size_t page_bytes = (size_t)c.num_kv_heads * 2 * 8192 * (e->kv8 ? 1 : 2);
-        CK(launch_kv_fork_pages(s, e->pool, e->pool_layer_elems * 2, page_bytes, c.num_layers, src_pages[shared], e->fk_dev + DOTS_MAX_BATCH, n_dst));
-    }
-    const int32_t cap = max_new;
+    // the tail page, as a fork copies it
+    if (L % 64) CK(launch_kv_fork_pages(s, e->pool, e->pool_layer_elems * 2, kv_page_bytes(e), c.num_layers, src_pages[shared], e->fk_dev + DOTS_MAX_BATCH, n_dst));
+    // the source too: its own first token is replaced by the group's.  A group row's logprob positions stay as they are (rows_go_live)
+    RET(rows_go_live(e, live, false));
     int rows = 0;
     for (int i = 0; i < B; ++i) {
-        const int d = gd.slots[i];
-        rows = std::max(rows, d + 1);
-        CK(hipMemcpyAsync(e->ctx_len + d, &L, 4, hipMemcpyHostToDevice, s));
-        CK(hipMemcpyAsync(e->d_max_len + d, &cap, 4, hipMemcpyHostToDevice, s));
-        CK(hipMemsetAsync(e->out_lens + d, 0, 4, s));      // the source's own first token is replaced by the group's
-        CK(hipMemsetAsync(e->finished + d, 0, 4, s));
-        e->beam_of[d] = gi + 1;
+        rows = std::max(rows, gd.slots[i] + 1);
+        e->beam_of[gd.slots[i]] = gi + 1;
     }
     DotsEngine::BeamGroup& g = e->beams[gi];
     g = DotsEngine::BeamGroup{};
@@ -423,17 +400,9 @@ int dots_slots_beam(DotsEngine* e, int src_slot, const int32_t* dst_slots, int n
     CK(launch_beam_select(s, beam_state(e), step_state(e, 0, nullptr), gi, 1, 0));
     CK(hipStreamSynchronize(s));                           // the staged arrays are stack variables
     g.done_ub = done_per_step(e, g);
-    for (int i = 1; i < B; ++i) {
-        const int d = gd.slots[i];
-        e->slot_active[d] = 1;
-        e->slot_limit[d] = L + max_new;
-        e->slot_prompt[d] = L;
-        e->slot_ctx_ub[d] = L;
-        e->slot_done[d] = 0;
-    }
+    mark_live(e, live.data() + 1, n_dst);                 // the source's record stands
     e->fresh_slots.erase(std::find(e->fresh_slots.begin(), e->fresh_slots.end(), src_slot));      // the source is no plain sequence any more
     recount_groups(e);
-    e->sel_dirty = true;
     guard.armed = false;
     group_guard.armed = false;
     return DOTS_OK;

@@ -44,6 +44,9 @@ struct LLayer {
     uint8_t *qkv_8, *o_8, *w13_8, *down_8;
 };
 
+// a row that goes live in a slot: its context (the prompt length) and its generation cap ("what admitting a slot consists of")
+struct LiveRow { int32_t slot, ctx, cap; };
+
 struct DotsEngine {
     DotsConfig cfg{};
     int device = 0;
@@ -256,6 +259,10 @@ struct DotsEngine {
     int slot_done[DOTS_MAX_BATCH] = {0};   // seen finished at the last poll: grows no more
     int32_t *d_sel = nullptr, *d_sel_new = nullptr, *d_max_len = nullptr, *p_dst = nullptr;
     const int32_t* sel_now = nullptr;      // selection mask of the next select_tokens() call
+    // what an admission uploads asynchronously, staged here so that it outlives the call (as hp_pos / hp_last do): the rows going live
+    // (rows_go_live), and the mask [DOTS_MAX_BATCH] and slot list [DOTS_MAX_BATCH] of a first-token selection (stage_new_rows)
+    std::vector<LiveRow> hp_live;
+    std::vector<int32_t> hp_new;
     // ---- suspended sequences (dots_slot_suspend).  swap_host: pinned host memory of swap_total host pages, one host page =
     // one 64-token page of EVERY layer ([layer][page bytes], the staging layout of kv_swap.hip); swap_used[h] != 0: host page h is taken.
     // swap_stage / swap_list: the device staging buffer of KV_SWAP_CHUNK_PAGES host pages and the page list the kernels read, allocated by
@@ -415,6 +422,36 @@ hipError_t upload_table_row(DotsEngine* e, int slot);
 void release_pages(DotsEngine* e, int slot);
 bool reserve_pages(DotsEngine* e, int slot, int tokens);
 int admit_tokens(const DotsEngine* e, int prompt, int max_new);
+int grow_pages(DotsEngine* e, int slot, int tokens, bool* changed);
+// the first n entries of the slot's (empty) row name another holder's pages, which nobody writes any more: one more holder of each
+void share_pages(DotsEngine* e, int slot, const int32_t* pages, int n);
+// the prefix cache's evictable pages count as free: ensure_free moves up to `need` of them into the free list (off: nothing happens)
+void ensure_free(DotsEngine* e, int64_t need);
+int free_count(const DotsEngine* e);
+inline size_t kv_page_bytes(const DotsEngine* e) { return (size_t)e->cfg.num_kv_heads * 2 * 8192 * (e->kv8 ? 1 : 2); }      // one page of one layer
+// gives the pages of a list of slots back unless disarmed: between an admission's first page and its success the slots are not occupied,
+// so dots_slot_release would refuse them.  upload: the device table rows follow (not a filling slot's, which stays on the scratch page)
+struct PageGuard {
+    DotsEngine* e; const int32_t* slots; int n; bool upload, armed = true;
+    ~PageGuard() {
+        for (int i = 0; armed && i < n; ++i) {
+            release_pages(e, slots[i]);
+            if (upload) (void)upload_table_row(e, slots[i]);
+        }
+    }
+};
+// slots.hip: what admitting a slot consists of, shared by prefill, chunked fill, fork, beam group and extend
+inline bool slot_occupied(const DotsEngine* e, int slot) { return e->slot_mode && slot >= 0 && slot < e->cfg.max_batch && e->slot_active[slot]; }
+int check_free_slot(DotsEngine* e, const int32_t* slots, int i, int src = -1, const char* src_of = "");
+int check_prompt(DotsEngine* e, int b, int len, const int32_t* slots, const int32_t* max_new);
+int map_prompt(DotsEngine* e, const int32_t* ids, int n, bool no_tower, int32_t* src, int64_t* vis_used);
+int check_vis_rows(DotsEngine* e, int64_t vis_used);
+int enter_slot_mode(DotsEngine* e);
+int rows_go_live(DotsEngine* e, const std::vector<LiveRow>& rows, bool clear_lp = true);
+int stage_new_rows(DotsEngine* e, const std::vector<LiveRow>& rows, int32_t* d_list, int* n_rows);
+int restart_automata(DotsEngine* e, const int32_t* d_rows, int n, bool stops = true);
+int select_first_tokens(DotsEngine* e, int rows, const bf16_t* h, bf16_t* xn = nullptr);
+void mark_live(DotsEngine* e, const LiveRow* rows, int n, bool occupy = true);
 // rows.hip: what a row is selected with
 StepState step_state(const DotsEngine* e, int advance, const int32_t* sel);
 bool spec_draws(const DotsEngine* e);
@@ -452,12 +489,7 @@ int decode_layers(DotsEngine* e, const int32_t* tokens, const int32_t* ctx_len, 
 int decode_step_launches(DotsEngine* e, int n_splits, int part = 0);
 int splits_for_ctx(int max_ctx);
 int step_graph(DotsEngine* e, int rows, int n_splits, int out_cap, hipGraphExec_t* exec, int part = 0);
-// slots.hip
-int grow_pages(DotsEngine* e, int slot, int tokens, bool* changed);
-// the prefix cache's evictable pages count as free: ensure_free moves up to `need` of them into the free list (off: nothing happens)
-void ensure_free(DotsEngine* e, int64_t need);
-int free_count(const DotsEngine* e);
-// a suspended slot: occupied, its KV parked in host memory (dots_slot_suspend)
+// slots.hip: a suspended slot: occupied, its KV parked in host memory (dots_slot_suspend)
 inline bool slot_parked(const DotsEngine* e, int slot) { return slot >= 0 && slot < DOTS_MAX_BATCH && e->parked[slot].on; }
 void swap_free_host(DotsEngine* e);
 // beam.hip: beam groups

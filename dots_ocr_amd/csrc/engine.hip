@@ -346,6 +346,36 @@ int pick_decode_stream(DotsEngine* e, hipStream_t* cur) {
     return DOTS_OK;
 }
 
+namespace {
+// The Qwen2 layers of a prefill pass over the T packed rows of p_x (Tpad padded; the tiles of hp_tiles / p_tiles): K/V go to the pages that
+// `table` names, attn(layer, pool_layer) launches the pass's attention into p_att.  capture: the residual stream after every layer is kept
+// for dots_debug_capture_hidden
+template <typename Attn>
+int prefill_layers(DotsEngine* e, int64_t T, int64_t Tpad, const int32_t* table, bool capture, Attn attn) {
+    const DotsConfig& c = e->cfg;
+    hipStream_t s = e->stream;
+    const int H = c.hidden_size, Hq = c.num_heads, Hkv = c.num_kv_heads, Nq = Hq * 128, n_tiles = (int)e->hp_tiles.size();
+    for (int i = 0; i < c.num_layers; ++i) {
+        const LLayer& Lw = e->ll[i];
+        bf16_t* pool_l = e->pool + e->pool_layer_elems * i;
+        CK(launch_rmsnorm(s, e->p_x, Lw.ln1, e->p_xn, T, H, c.rms_norm_eps));
+        RET(qkv_rope_on(e, s, e->act_q, e->act_s, e->p_xn, Lw.qkv_w, Lw.qkv_8, Lw.qkv_s, Lw.qkv_b, e->p_qkv, e->p_cs, e->p_tiles, n_tiles, e->p_q, e->p_k, e->p_vt, T, Tpad, H, Hq, Hkv));
+        CK(launch_kv_to_pages(s, e->p_k, e->p_qkv, e->p_tiles, n_tiles, table, e->max_pages, pool_l, T, Hq, Hkv, layer_kv_scales(e, i)));
+        CK(attn(i, pool_l));
+        RET(dense(e, e->p_att, Lw.o_w, Lw.o_8, Lw.o_s, nullptr, e->p_x, e->p_x, T, H, Nq, H, EPI_RESIDUAL));
+        CK(launch_rmsnorm(s, e->p_x, Lw.ln2, e->p_xn, T, H, c.rms_norm_eps));
+        RET(dense(e, e->p_xn, Lw.w13, Lw.w13_8, Lw.w13_s, nullptr, nullptr, e->p_act, T, 2 * c.intermediate_size, H, c.intermediate_size, EPI_SWIGLU));
+        RET(dense(e, e->p_act, Lw.down_w, Lw.down_8, Lw.down_s, nullptr, e->p_x, e->p_x, T, H, c.intermediate_size, H, EPI_RESIDUAL));
+        const size_t voff = (size_t)c.v_layers * e->dbg_vit_rows * c.v_embed_dim;       // LM layers are stored behind the ViT blocks
+        if (capture && e->dbg_hidden && voff + (size_t)(i + 1) * T * H <= e->dbg_cap) {
+            CK(hipMemcpyAsync(e->dbg_hidden + voff + (size_t)i * T * H, e->p_x, (size_t)T * H * 2, hipMemcpyDeviceToDevice, s));
+            e->dbg_lm_rows = T;
+        }
+    }
+    return DOTS_OK;
+}
+}  // namespace
+
 // Prefill B packed prompts.  slots == nullptr: the static batch (sequence b -> slot b, every slot reset).
 // slots != nullptr: continuous batching, sequence b goes into the free slot slots[b] with its own generation cap;
 // the other slots' KV pages, contexts and outputs are not touched.
@@ -356,42 +386,25 @@ int prefill(DotsEngine* e, const int32_t* ids, const int32_t* lens, int B, const
     if (B < 1 || B > c.max_batch) return e->fail(DOTS_E_CAPACITY, "batch %d exceeds max_batch %d", B, c.max_batch);
     int64_t T = 0;
     std::vector<int> L(B), S(B);
+    std::vector<LiveRow> live(slots ? B : 0);
     int rows = B;                                           // rows of the last-position / lm_head / selection stage
     for (int b = 0; b < B; ++b) {
-        if (lens[b] < 1 || lens[b] >= c.max_seq_len) return e->fail(DOTS_E_CAPACITY, "prompt %d length %d not in [1, max_seq_len)", b, lens[b]);
+        RET(check_prompt(e, b, lens[b], slots, max_new));
         L[b] = lens[b];
         T += lens[b];
         S[b] = slots ? slots[b] : b;
-        if (slots) {
-            if (S[b] < 0 || S[b] >= c.max_batch) return e->fail(DOTS_E_INVALID, "slot %d out of range [0, %d)", S[b], c.max_batch);
-            if (e->spec_k && S[b] >= c.max_batch / (e->spec_k + 1))
-                return e->fail(DOTS_E_CAPACITY, "slot %d is not usable while speculating: with %d drafts a slot takes %d rows of a step, so only slots [0, max_batch / (k + 1)) = [0, %d) are",
-                               S[b], e->spec_k, e->spec_k + 1, c.max_batch / (e->spec_k + 1));
-            if (e->slot_mode && e->slot_active[S[b]]) return e->fail(DOTS_E_STATE, "slot %d is occupied", S[b]);
-            if (e->slot_mode && slot_filling(e, S[b])) return e->fail(DOTS_E_STATE, "slot %d is filling (dots_slots_prefill_begin)", S[b]);
-            for (int a = 0; a < b; ++a)
-                if (S[a] == S[b]) return e->fail(DOTS_E_INVALID, "slot %d listed twice", S[b]);
-            if (max_new[b] < 1 || lens[b] + max_new[b] > c.max_seq_len)
-                return e->fail(DOTS_E_CAPACITY, "slot %d: prompt (%d) + max_new_tokens (%d) exceeds max_seq_len %d", S[b], lens[b], max_new[b], c.max_seq_len);
-            rows = std::max(rows, S[b] + 1);
-        }
+        if (slots) live[b] = LiveRow{S[b], L[b], max_new[b]};
     }
     if (T > e->TP) return e->fail(DOTS_E_CAPACITY, "packed prompt tokens %lld > max_prefill_tokens %lld", (long long)T, (long long)e->TP);
     e->fresh_slots.clear();                                 // the workspace of the previous prefill is about to be overwritten (dots_slots_fork)
     e->hp_pos.resize(T); e->hp_src.resize(T); e->hp_last.assign(DOTS_MAX_BATCH, 0);
     int64_t t = 0, vis_used = 0;
-    for (int b = 0; b < B; ++b) {
-        for (int i = 0; i < L[b]; ++i, ++t) {
-            e->hp_pos[t] = i;
-            const int id = ids[t];
-            if (id == c.image_token_id) e->hp_src[t] = -(int32_t)(++vis_used);
-            else if (id < 0 || id >= c.vocab_size) return e->fail(DOTS_E_INVALID, "token id %d out of range", id);
-            else e->hp_src[t] = id;
-        }
-        e->hp_last[b] = (int32_t)(t - 1);
+    for (int b = 0; b < B; t += L[b], ++b) {
+        for (int i = 0; i < L[b]; ++i) e->hp_pos[t + i] = i;
+        RET(map_prompt(e, ids + t, L[b], false, e->hp_src.data() + t, &vis_used));
+        e->hp_last[b] = (int32_t)(t + L[b] - 1);
     }
-    if (vis_used != (vis_used ? e->vis_rows : 0))
-        return e->fail(DOTS_E_STATE, "prompt has %lld image tokens but the vision tower produced %lld rows", (long long)vis_used, (long long)e->vis_rows);
+    RET(check_vis_rows(e, vis_used));
     int64_t Tpad = 0;
     build_worklists(L, Hq, e->hp_tiles, e->hp_qblocks, &Tpad, S.data());
     CK(hipMemcpyAsync(e->p_pos, e->hp_pos.data(), T * 4, hipMemcpyHostToDevice, s));
@@ -402,106 +415,54 @@ int prefill(DotsEngine* e, const int32_t* ids, const int32_t* lens, int B, const
     // ---- KV pages: a static batch resets every slot and reserves prompt + generation cap (a closed batch: nothing competes for pages);
     // a slot prefill reserves the prompt plus KV_ADMIT_AHEAD tokens for its own sequences only — the rest is taken page by page as the
     // sequences actually grow (dots_slots_decode).  Entering slot mode returns the pages of the previous static batch first.
-    if (!slots || !e->slot_mode) {
+    if (slots && !e->slot_mode) RET(enter_slot_mode(e));
+    if (!slots) {
         for (int b = 0; b < (int)e->slot_pages.size(); ++b) release_pages(e, b);
         RET(beam_clear_all(e));
     }
-    const bool whole_table = !slots || !e->slot_mode;
     {
         int need = 0;
         for (int b = 0; b < B; ++b) need += ((slots ? admit_tokens(e, L[b], max_new[b]) : std::min(L[b] + e->out_cap, c.max_seq_len)) + 63) / 64;
         ensure_free(e, need);
         if (need > (int)e->free_pages.size()) {
             const int have = free_count(e);
-            if (whole_table) CK(hipMemcpyAsync(e->block_table, e->hp_table.data(), e->hp_table.size() * 4, hipMemcpyHostToDevice, s));
+            if (!slots) CK(hipMemcpyAsync(e->block_table, e->hp_table.data(), e->hp_table.size() * 4, hipMemcpyHostToDevice, s));
             return e->fail(DOTS_E_CAPACITY, "KV pool exhausted: these sequences need %d pages of 64 tokens, %d of %d are free", need, have, e->n_pool_pages);
         }
         for (int b = 0; b < B; ++b) reserve_pages(e, S[b], slots ? admit_tokens(e, L[b], max_new[b]) : std::min(L[b] + e->out_cap, c.max_seq_len));
-        if (whole_table) CK(hipMemcpyAsync(e->block_table, e->hp_table.data(), e->hp_table.size() * 4, hipMemcpyHostToDevice, s));
+        if (!slots) CK(hipMemcpyAsync(e->block_table, e->hp_table.data(), e->hp_table.size() * 4, hipMemcpyHostToDevice, s));
         else for (int b = 0; b < B; ++b) CK(upload_table_row(e, S[b]));
     }
-    // from here on a failed launch must give the pages back (the slots are not marked occupied yet, so dots_slot_release would refuse them)
-    struct PageGuard {
-        DotsEngine* e; const std::vector<int>& S; bool slots, armed = true;
-        ~PageGuard() {
-            if (!armed || !slots) return;
-            for (int sl : S) { release_pages(e, sl); (void)upload_table_row(e, sl); }
-        }
-    } page_guard{e, S, slots != nullptr};
+    // from here on a failed launch must give the pages back
+    PageGuard page_guard{e, S.data(), B, true, slots != nullptr};
     if (!slots) {
         e->slot_mode = false;
         std::fill(e->slot_active, e->slot_active + DOTS_MAX_BATCH, 0);
         CK(hipMemcpyAsync(e->ctx_len, lens, B * 4, hipMemcpyHostToDevice, s));
         CK(hipMemsetAsync(e->out_lens, 0, c.max_batch * 4, s));
         CK(hipMemsetAsync(e->finished, 0, c.max_batch * 4, s));
+        for (int b = 0; b < B; ++b) RET(clear_lp_row(e, b));           // logprob positions of the prefilled rows: NaN / -1 until written
     } else {
-        if (!e->slot_mode) {                               // entering slot mode: every slot starts free
-            std::fill(e->slot_active, e->slot_active + DOTS_MAX_BATCH, 0);
-            CK(hipMemsetAsync(e->ctx_len, 0, c.max_batch * 4, s));
-            e->slot_mode = true;
-        }
-        int32_t sel_new[DOTS_MAX_BATCH] = {0};
-        for (int b = 0; b < B; ++b) {
-            sel_new[S[b]] = 1;
-            CK(hipMemcpyAsync(e->ctx_len + S[b], lens + b, 4, hipMemcpyHostToDevice, s));
-            CK(hipMemcpyAsync(e->d_max_len + S[b], max_new + b, 4, hipMemcpyHostToDevice, s));
-            CK(hipMemsetAsync(e->out_lens + S[b], 0, 4, s));
-            CK(hipMemsetAsync(e->finished + S[b], 0, 4, s));
-            if (e->sp_ndraft) {                            // a new sequence: no drafts, its own counters from zero
-                CK(hipMemsetAsync(e->sp_ndraft + S[b], 0, 4, s));
-                CK(hipMemsetAsync(e->sp_stats + (size_t)S[b] * 3, 0, 3 * sizeof(unsigned long long), s));
-            }
-        }
-        CK(hipMemcpyAsync(e->d_sel_new, sel_new, DOTS_MAX_BATCH * 4, hipMemcpyHostToDevice, s));
-        CK(hipMemcpyAsync(e->p_dst, S.data(), B * 4, hipMemcpyHostToDevice, s));
+        // written ahead of the layer loop: only the selection stage below and the step after it read the rows' state
+        RET(rows_go_live(e, live));
+        RET(stage_new_rows(e, live, e->p_dst, &rows));
     }
-
-    for (int b = 0; b < B; ++b) RET(clear_lp_row(e, S[b]));         // logprob positions of the prefilled rows: NaN / -1 until written
+    const int32_t* d_rows = slots ? e->p_dst : nullptr;     // the rows of the prompts, in order (static batch: rows [0, B))
     CK(hipEventRecord(e->ev[2], s));
     CK(launch_embed_gather(s, e->p_src, e->embed, e->vis, e->p_x, T, H));
     CK(launch_rope_table(s, e->p_pos, e->lm_inv_freq, e->p_cs, T, 0));
-    const float scale = 1.0f / sqrtf(128.0f);
-    const int n_tiles = (int)e->hp_tiles.size();
-    for (int i = 0; i < c.num_layers; ++i) {
-        const LLayer& Lw = e->ll[i];
-        bf16_t* pool_l = e->pool + e->pool_layer_elems * i;
-        CK(launch_rmsnorm(s, e->p_x, Lw.ln1, e->p_xn, T, H, c.rms_norm_eps));
-        RET(qkv_rope_on(e, s, e->act_q, e->act_s, e->p_xn, Lw.qkv_w, Lw.qkv_8, Lw.qkv_s, Lw.qkv_b, e->p_qkv, e->p_cs, e->p_tiles, n_tiles, e->p_q, e->p_k, e->p_vt, T, Tpad, H, Hq, Hkv));
-        CK(launch_kv_to_pages(s, e->p_k, e->p_qkv, e->p_tiles, n_tiles, e->block_table, e->max_pages, pool_l, T, Hq, Hkv, layer_kv_scales(e, i)));
-        CK(launch_flash_attn(s, e->p_q, e->p_k, e->p_vt, e->p_att, e->p_qblocks, (int)e->hp_qblocks.size(), T, Tpad, Hq, Hkv, 1, scale));
-        RET(dense(e, e->p_att, Lw.o_w, Lw.o_8, Lw.o_s, nullptr, e->p_x, e->p_x, T, H, Nq, H, EPI_RESIDUAL));
-        CK(launch_rmsnorm(s, e->p_x, Lw.ln2, e->p_xn, T, H, c.rms_norm_eps));
-        RET(dense(e, e->p_xn, Lw.w13, Lw.w13_8, Lw.w13_s, nullptr, nullptr, e->p_act, T, 2 * c.intermediate_size, H, c.intermediate_size, EPI_SWIGLU));
-        RET(dense(e, e->p_act, Lw.down_w, Lw.down_8, Lw.down_s, nullptr, e->p_x, e->p_x, T, H, c.intermediate_size, H, EPI_RESIDUAL));
-        const size_t voff = (size_t)c.v_layers * e->dbg_vit_rows * c.v_embed_dim;       // LM layers are stored behind the ViT blocks
-        if (e->dbg_hidden && voff + (size_t)(i + 1) * T * H <= e->dbg_cap) {
-            CK(hipMemcpyAsync(e->dbg_hidden + voff + (size_t)i * T * H, e->p_x, (size_t)T * H * 2, hipMemcpyDeviceToDevice, s));
-            e->dbg_lm_rows = T;
-        }
-    }
+    RET(prefill_layers(e, T, Tpad, e->block_table, true, [&](int, bf16_t*) {
+        return launch_flash_attn(s, e->p_q, e->p_k, e->p_vt, e->p_att, e->p_qblocks, (int)e->hp_qblocks.size(), T, Tpad, Hq, Hkv, 1, 1.0f / sqrtf(128.0f));
+    }));
     // prompt-presence bits (repetition penalty) of the prefilled rows, once any row has used a penalty
-    if (e->pen_cnt) CK(launch_pen_prompt(s, e->p_src, e->p_last, slots ? e->p_dst : nullptr, B, c.image_token_id, c.vocab_size, e->pen_cnt, e->pen_seen));
-    // the automata of the prefilled rows that hold a guide start over: the first token is already selected under the guide
-    if (e->stage.rows(ROW_GUIDE) > 0) CK(launch_guide_reset_rows(s, e->d_guides, slots ? e->p_dst : nullptr, B));
-    // so do the stop automata of the prefilled rows, and their hit records are cleared: the first token's bytes are the first ones walked
-    if (e->stage.rows(ROW_STOP) > 0) CK(launch_stop_reset_rows(s, e->d_stop, slots ? e->p_dst : nullptr, B));
+    if (e->pen_cnt) CK(launch_pen_prompt(s, e->p_src, e->p_last, d_rows, B, c.image_token_id, c.vocab_size, e->pen_cnt, e->pen_seen));
+    RET(restart_automata(e, d_rows, B));
     // last position of every sequence -> final norm -> lm_head -> first token
-    CK(launch_gather_rows(s, e->p_x, e->p_last, slots ? e->p_dst : nullptr, e->d_h, B, H));
-    CK(launch_dec_lmhead(s, e->d_h, e->final_norm, e->lm_head_d, e->lm_head_s, e->d_logits, rows, H, c.vocab_size, c.rms_norm_eps));
-    e->B_sel = rows;
-    e->sel_now = e->d_sel_new;
-    RET(select_tokens(e, 0));
+    CK(launch_gather_rows(s, e->p_x, e->p_last, d_rows, e->d_h, B, H));
+    RET(select_first_tokens(e, rows, e->d_h));
     CK(hipEventRecord(e->ev[3], s));
     if (slots) {
-        for (int b = 0; b < B; ++b) {
-            e->slot_active[S[b]] = 1;
-            e->slot_limit[S[b]] = L[b] + max_new[b];
-            e->slot_prompt[S[b]] = L[b];
-            e->slot_ctx_ub[S[b]] = L[b];
-            e->slot_done[S[b]] = 0;
-        }
-        e->sel_dirty = true;
-        e->B = 0;                                          // the static-batch entry points need a static prefill first
+        mark_live(e, live.data(), B);
         e->fresh_slots = S;                                // these sequences may be forked until the next step (dots_slots_fork)
         e->fresh_chunked = false;
     } else {
@@ -536,21 +497,8 @@ int prefill_begin(DotsEngine* e, const int32_t* ids, const int32_t* lens, int B,
     if (e->spec_k) return e->fail(DOTS_E_STATE, "a chunked prefill cannot begin while the engine speculates (dots_set_speculation), as a slot cannot be extended or suspended then");
     if (e->TP < 64) return e->fail(DOTS_E_CAPACITY, "a chunked prefill needs max_prefill_tokens >= 64, it is %lld", (long long)e->TP);
     if (B < 1 || B > c.max_batch) return e->fail(DOTS_E_CAPACITY, "batch %d exceeds max_batch %d", B, c.max_batch);
-    std::vector<int> L(B), S(B);
-    int64_t T = 0;
-    for (int b = 0; b < B; ++b) {
-        if (lens[b] < 1 || lens[b] >= c.max_seq_len) return e->fail(DOTS_E_CAPACITY, "prompt %d length %d not in [1, max_seq_len)", b, lens[b]);
-        L[b] = lens[b];
-        T += lens[b];
-        S[b] = slots[b];
-        if (S[b] < 0 || S[b] >= c.max_batch) return e->fail(DOTS_E_INVALID, "slot %d out of range [0, %d)", S[b], c.max_batch);
-        if (e->slot_mode && e->slot_active[S[b]]) return e->fail(DOTS_E_STATE, "slot %d is occupied", S[b]);
-        if (e->slot_mode && slot_filling(e, S[b])) return e->fail(DOTS_E_STATE, "slot %d is filling", S[b]);
-        for (int a = 0; a < b; ++a)
-            if (S[a] == S[b]) return e->fail(DOTS_E_INVALID, "slot %d listed twice", S[b]);
-        if (max_new[b] < 1 || lens[b] + max_new[b] > c.max_seq_len)
-            return e->fail(DOTS_E_CAPACITY, "slot %d: prompt (%d) + max_new_tokens (%d) exceeds max_seq_len %d", S[b], lens[b], max_new[b], c.max_seq_len);
-    }
+    for (int b = 0; b < B; ++b) RET(check_prompt(e, b, lens[b], slots, max_new));
+    const std::vector<int> L(lens, lens + B), S(slots, slots + B);
     // a leased prompt: hit[b] positions are in the lease's pages; one whose lease needs no tower takes no rows of `vis`
     std::vector<const prefix_cache::Lease*> lease(B, nullptr);
     std::vector<int> hit(B, 0);
@@ -566,28 +514,13 @@ int prefill_begin(DotsEngine* e, const int32_t* ids, const int32_t* lens, int B,
             return e->fail(DOTS_E_INVALID, "prompt %d: lease %d was not taken for this prompt", b, leases[b]);
     }
     std::vector<std::vector<int32_t>> src(B);
-    int64_t t = 0, vis_used = 0;
-    for (int b = 0; b < B; ++b) {
+    int64_t vis_used = 0;
+    for (int b = 0, t0 = 0; b < B; t0 += L[b], ++b) {
         src[b].resize(L[b]);
-        const bool no_tower = lease[b] && !lease[b]->needs_tower;
-        for (int i = 0; i < L[b]; ++i, ++t) {
-            const int id = ids[t];
-            if (id == c.image_token_id) src[b][i] = no_tower ? INT32_MIN : -(int32_t)(++vis_used);
-            else if (id < 0 || id >= c.vocab_size) return e->fail(DOTS_E_INVALID, "token id %d out of range", id);
-            else src[b][i] = id;
-        }
+        RET(map_prompt(e, ids + t0, L[b], lease[b] && !lease[b]->needs_tower, src[b].data(), &vis_used));
     }
-    if (vis_used != (vis_used ? e->vis_rows : 0))
-        return e->fail(DOTS_E_STATE, "prompt has %lld image tokens but the vision tower produced %lld rows", (long long)vis_used, (long long)e->vis_rows);
-    if (!e->slot_mode) {                                   // entering slot mode, as a slot prefill does: every slot free, every page in the pool
-        for (int b = 0; b < (int)e->slot_pages.size(); ++b) release_pages(e, b);
-        RET(beam_clear_all(e));
-        CK(hipMemcpyAsync(e->block_table, e->hp_table.data(), e->hp_table.size() * 4, hipMemcpyHostToDevice, s));
-        std::fill(e->slot_active, e->slot_active + DOTS_MAX_BATCH, 0);
-        CK(hipMemsetAsync(e->ctx_len, 0, c.max_batch * 4, s));
-        e->slot_mode = true;
-        e->B = 0;
-    }
+    RET(check_vis_rows(e, vis_used));
+    if (!e->slot_mode) RET(enter_slot_mode(e));
     int need = 0;
     for (int b = 0; b < B; ++b) need += (admit_tokens(e, L[b], max_new[b]) + 63) / 64 - hit[b] / 64;
     ensure_free(e, need);
@@ -598,23 +531,12 @@ int prefill_begin(DotsEngine* e, const int32_t* ids, const int32_t* lens, int B,
     if (!e->fill_rows) CK(e->alloc(&e->fill_rows, (size_t)e->TP));
     if (!e->fill_table) CK(e->alloc(&e->fill_table, (size_t)DOTS_MAX_BATCH * e->max_pages));
     if (!e->fill_items) CK(e->alloc(&e->fill_items, (size_t)(e->TP / 64 + c.max_batch + 1)));
+    PageGuard guard{e, slots, B, false};
     for (int b = 0; b < B; ++b) {
-        auto& mine = e->slot_pages[S[b]];
-        for (int p = 0; p < hit[b] / 64; ++p) {            // one more holder of a cached page, which nobody writes: the cursor starts behind it
-            mine.push_back(lease[b]->chain[p]);
-            e->page_refs[mine.back()] += 1;
-            e->hp_table[(size_t)S[b] * e->max_pages + p] = mine.back();
-        }
+        if (hit[b]) share_pages(e, S[b], lease[b]->chain.data(), hit[b] / 64);      // the cached pages: the cursor starts behind them
         bool changed = false;
         grow_pages(e, S[b], admit_tokens(e, L[b], max_new[b]), &changed);      // cannot fall short: counted above
     }
-    struct Guard {
-        DotsEngine* e; const std::vector<int>& S; bool armed = true;
-        ~Guard() {
-            if (!armed) return;
-            for (int sl : S) release_pages(e, sl);
-        }
-    } guard{e, S};
     // the device table row of a filling slot stays on the scratch page (a decode step runs its row as a free one); the passes read fill_table
     for (int b = 0; b < B; ++b)
         CK(hipMemcpyAsync(e->fill_table + (size_t)S[b] * e->max_pages, e->hp_table.data() + (size_t)S[b] * e->max_pages, (size_t)e->max_pages * 4, hipMemcpyHostToDevice, s));
@@ -686,7 +608,7 @@ int prefill_begin(DotsEngine* e, const int32_t* ids, const int32_t* lens, int B,
 int prefill_advance(DotsEngine* e, int max_tokens, int32_t* remaining) {
     const DotsConfig& c = e->cfg;
     hipStream_t s = e->stream;
-    const int H = c.hidden_size, Hq = c.num_heads, Hkv = c.num_kv_heads, Nq = Hq * 128, V = c.vocab_size;
+    const int H = c.hidden_size, V = c.vocab_size;
     if (max_tokens < 64 || max_tokens % 64 || max_tokens > e->TP)
         return e->fail(DOTS_E_INVALID, "max_tokens must be a positive multiple of 64 and at most max_prefill_tokens (%lld), got %d", (long long)e->TP, max_tokens);
     auto left = [&] {
@@ -714,9 +636,8 @@ int prefill_advance(DotsEngine* e, int max_tokens, int32_t* remaining) {
     }
     e->hp_pos.resize(T); e->hp_src.resize(T); e->hp_rows.resize(T); e->hp_last.assign(DOTS_MAX_BATCH, 0);
     e->hp_tiles.clear(); e->hp_items.clear();
-    std::vector<int32_t> done_slots;
-    int32_t sel_new[DOTS_MAX_BATCH] = {0};
-    int pad0 = 0, rows = 0;
+    std::vector<LiveRow> done;                             // the slots whose last prompt token is in this pass
+    int pad0 = 0;
     for (const Part& p : parts) {
         const DotsEngine::Fill& f = e->fill[p.slot];
         const auto& pages = e->slot_pages[p.slot];
@@ -733,14 +654,12 @@ int prefill_advance(DotsEngine* e, int max_tokens, int32_t* remaining) {
         }
         pad0 += (int)round_up(p.take, 64);
         if (p.done) {
-            e->hp_last[done_slots.size()] = p.tok0 + p.take - 1;
-            done_slots.push_back(p.slot);
-            sel_new[p.slot] = 1;
-            rows = std::max(rows, p.slot + 1);
+            e->hp_last[done.size()] = p.tok0 + p.take - 1;
+            done.push_back(LiveRow{p.slot, f.L, f.max_new});
         }
     }
     const int64_t Tpad = pad0;
-    const int n_tiles = (int)e->hp_tiles.size(), n_done = (int)done_slots.size();
+    const int n_tiles = (int)e->hp_tiles.size(), n_done = (int)done.size();
     e->fresh_slots.clear();                                // the workspace (and, with a completed slot, the logits) are about to be overwritten
     CK(hipMemcpyAsync(e->p_pos, e->hp_pos.data(), (size_t)T * 4, hipMemcpyHostToDevice, s));
     CK(hipMemcpyAsync(e->p_src, e->hp_src.data(), (size_t)T * 4, hipMemcpyHostToDevice, s));
@@ -750,20 +669,10 @@ int prefill_advance(DotsEngine* e, int max_tokens, int32_t* remaining) {
     CK(hipEventRecord(e->ev[2], s));
     CK(launch_gather_rows(s, e->fill_x, e->fill_rows, nullptr, e->p_x, T, H));
     CK(launch_rope_table(s, e->p_pos, e->lm_inv_freq, e->p_cs, T, 0));
-    const float scale = 1.0f / sqrtf(128.0f);
-    for (int i = 0; i < c.num_layers; ++i) {
-        const LLayer& Lw = e->ll[i];
-        bf16_t* pool_l = e->pool + e->pool_layer_elems * i;
-        CK(launch_rmsnorm(s, e->p_x, Lw.ln1, e->p_xn, T, H, c.rms_norm_eps));
-        RET(qkv_rope_on(e, s, e->act_q, e->act_s, e->p_xn, Lw.qkv_w, Lw.qkv_8, Lw.qkv_s, Lw.qkv_b, e->p_qkv, e->p_cs, e->p_tiles, n_tiles, e->p_q, e->p_k, e->p_vt, T, Tpad, H, Hq, Hkv));
-        CK(launch_kv_to_pages(s, e->p_k, e->p_qkv, e->p_tiles, n_tiles, e->fill_table, e->max_pages, pool_l, T, Hq, Hkv, layer_kv_scales(e, i)));
-        CK(launch_flash_attn_paged(s, e->p_q, pool_l, e->fill_table, e->max_pages, c.max_batch, e->hp_items.data(), e->fill_items, n_tiles, e->p_att, T, Hq, Hkv, scale,
-                                   layer_kv_scales(e, i)));
-        RET(dense(e, e->p_att, Lw.o_w, Lw.o_8, Lw.o_s, nullptr, e->p_x, e->p_x, T, H, Nq, H, EPI_RESIDUAL));
-        CK(launch_rmsnorm(s, e->p_x, Lw.ln2, e->p_xn, T, H, c.rms_norm_eps));
-        RET(dense(e, e->p_xn, Lw.w13, Lw.w13_8, Lw.w13_s, nullptr, nullptr, e->p_act, T, 2 * c.intermediate_size, H, c.intermediate_size, EPI_SWIGLU));
-        RET(dense(e, e->p_act, Lw.down_w, Lw.down_8, Lw.down_s, nullptr, e->p_x, e->p_x, T, H, c.intermediate_size, H, EPI_RESIDUAL));
-    }
+    RET(prefill_layers(e, T, Tpad, e->fill_table, false, [&](int layer, bf16_t* pool_l) {
+        return launch_flash_attn_paged(s, e->p_q, pool_l, e->fill_table, e->max_pages, c.max_batch, e->hp_items.data(), e->fill_items, n_tiles, e->p_att, T, c.num_heads,
+                                       c.num_kv_heads, 1.0f / sqrtf(128.0f), layer_kv_scales(e, layer));
+    }));
     // the pass has been issued: the cursors move and the presence bits of its tokens are accumulated
     for (const Part& p : parts) {
         DotsEngine::Fill& f = e->fill[p.slot];
@@ -782,49 +691,31 @@ int prefill_advance(DotsEngine* e, int max_tokens, int32_t* remaining) {
     if (n_done) {
         // ---- the slots whose last prompt token is in this pass complete exactly as at the end of prefill()
         const int W = (V + 31) / 32;
-        for (int j = 0; j < n_done; ++j) {
-            const int b = done_slots[j];
-            const DotsEngine::Fill& f = e->fill[b];
-            CK(upload_table_row(e, b));                    // the row becomes a live one: its pages, its context
-            CK(hipMemcpyAsync(e->ctx_len + b, &f.L, 4, hipMemcpyHostToDevice, s));
-            CK(hipMemcpyAsync(e->d_max_len + b, &f.max_new, 4, hipMemcpyHostToDevice, s));
-            CK(hipMemsetAsync(e->out_lens + b, 0, 4, s));
-            CK(hipMemsetAsync(e->finished + b, 0, 4, s));
-            if (e->sp_ndraft) {
-                CK(hipMemsetAsync(e->sp_ndraft + b, 0, 4, s));
-                CK(hipMemsetAsync(e->sp_stats + (size_t)b * 3, 0, 3 * sizeof(unsigned long long), s));
-            }
+        for (const LiveRow& r : done) {
+            CK(upload_table_row(e, r.slot));               // the row becomes a live one: its pages, its context
             if (e->pen_cnt) {                              // the one-shot image: the prompt's presence bits, no generated token counted
-                CK(hipMemsetAsync(e->pen_cnt + (size_t)b * V, 0, (size_t)V * 4, s));
-                CK(hipMemcpyAsync(e->pen_seen + (size_t)b * W, f.seen.data(), (size_t)W * 4, hipMemcpyHostToDevice, s));
+                CK(hipMemsetAsync(e->pen_cnt + (size_t)r.slot * V, 0, (size_t)V * 4, s));
+                CK(hipMemcpyAsync(e->pen_seen + (size_t)r.slot * W, e->fill[r.slot].seen.data(), (size_t)W * 4, hipMemcpyHostToDevice, s));
             }
-            RET(clear_lp_row(e, b));
         }
-        CK(hipMemcpyAsync(e->d_sel_new, sel_new, DOTS_MAX_BATCH * 4, hipMemcpyHostToDevice, s));
-        CK(hipMemcpyAsync(e->p_dst, done_slots.data(), (size_t)n_done * 4, hipMemcpyHostToDevice, s));
+        // behind the layer loop, which reads none of it: until here the rows ran as free ones in every step
+        int rows = 0;
+        RET(rows_go_live(e, done));
+        RET(stage_new_rows(e, done, e->p_dst, &rows));
         CK(hipMemcpyAsync(e->p_last, e->hp_last.data(), DOTS_MAX_BATCH * 4, hipMemcpyHostToDevice, s));
-        if (e->stage.rows(ROW_GUIDE) > 0) CK(launch_guide_reset_rows(s, e->d_guides, e->p_dst, n_done));
-        if (e->stage.rows(ROW_STOP) > 0) CK(launch_stop_reset_rows(s, e->d_stop, e->p_dst, n_done));
+        RET(restart_automata(e, e->p_dst, n_done));
         CK(launch_gather_rows(s, e->p_x, e->p_last, e->p_dst, e->d_h, n_done, H));
-        CK(launch_dec_lmhead(s, e->d_h, e->final_norm, e->lm_head_d, e->lm_head_s, e->d_logits, rows, H, V, c.rms_norm_eps));
-        e->B_sel = rows;
-        e->sel_now = e->d_sel_new;
-        RET(select_tokens(e, 0));
+        RET(select_first_tokens(e, rows, e->d_h));
     }
     CK(hipEventRecord(e->ev[3], s));
-    CK(hipStreamSynchronize(s));                           // the host lists and the records' scalars were read by asynchronous copies
-    for (int b : done_slots) {
-        const DotsEngine::Fill& f = e->fill[b];
-        e->slot_active[b] = 1;
-        e->slot_limit[b] = f.L + f.max_new;
-        e->slot_prompt[b] = f.L;
-        e->slot_ctx_ub[b] = f.L;
-        e->slot_done[b] = 0;
-        drop_fill(e, b);
-    }
+    CK(hipStreamSynchronize(s));                           // the host lists and the fills' presence bits were read by asynchronous copies
     if (n_done) {
-        e->sel_dirty = true;
-        e->fresh_slots.assign(done_slots.begin(), done_slots.end());      // may be forked until the next step, as after a prefill
+        mark_live(e, done.data(), n_done);
+        e->fresh_slots.clear();
+        for (const LiveRow& r : done) {
+            drop_fill(e, r.slot);
+            e->fresh_slots.push_back(r.slot);              // may be forked until the next step, as after a prefill
+        }
         e->fresh_chunked = true;
     }
     e->steps_done = 0;

@@ -702,7 +702,7 @@ int dots_set_row_drafts(DotsEngine* e, int row, const int32_t* ids_host, int n) 
     if (n > 0 && !ids_host) return e->fail(DOTS_E_INVALID, "null argument");
     for (int j = 0; j < n; ++j)
         if (ids_host[j] < 0 || ids_host[j] >= e->cfg.vocab_size) return e->fail(DOTS_E_INVALID, "draft id %d out of range [0, %d)", ids_host[j], e->cfg.vocab_size);
-    if (!e->slot_mode || !e->slot_active[row]) return e->fail(DOTS_E_STATE, "slot %d is not occupied", row);
+    if (!slot_occupied(e, row)) return e->fail(DOTS_E_STATE, "slot %d is not occupied", row);
     if (!e->spec_k) return DOTS_OK;                          // n == 0 with speculation off: nothing to clear
     CK(hipSetDevice(e->device));
     CK(launch_spec_set_drafts(e->stream, e->sp_drafts, e->sp_ndraft, row, ids_host, n));
@@ -755,7 +755,7 @@ int dots_row_logprobs(DotsEngine* e, int row, int pos0, int n, float* tok_lp_hos
     if (!e || !n_out || pos0 < 0 || n < 0 || (n > 0 && (!tok_lp_host || !top_ids_host || !top_lp_host)))
         return e ? e->fail(DOTS_E_INVALID, "bad row_logprobs arguments") : DOTS_E_INVALID;
     if (e->slot_mode) {
-        if (row < 0 || row >= e->cfg.max_batch || !e->slot_active[row]) return e->fail(DOTS_E_STATE, "slot %d is not occupied", row);
+        if (!slot_occupied(e, row)) return e->fail(DOTS_E_STATE, "slot %d is not occupied", row);
     } else if (row < 0 || row >= e->B) {
         return e->fail(DOTS_E_STATE, "row %d is not a sequence of the current static batch (%d rows)", row, e->B);
     }

@@ -1,5 +1,5 @@
-// Sequence slots of the dots.ocr engine: the host side of the paged KV pool and the continuous-batching C ABI (prefill into free slots,
-// fork, decode chunks, poll / read / release).
+// Sequence slots of the dots.ocr engine: the host side of the paged KV pool, the steps of admitting a slot and the continuous-batching
+// C ABI (prefill into free slots, fork, decode chunks, poll / read / release).
 #include "engine.h"
 
 namespace engine {
@@ -94,6 +94,139 @@ static int chunk_pages_lacking(const DotsEngine* e, int b, int n) {
 // tokens a slot sequence reserves at admission: its prompt plus the first page-worth of generated tokens (the rest on demand)
 constexpr int KV_ADMIT_AHEAD = 64;
 int admit_tokens(const DotsEngine* e, int prompt, int max_new) { return std::min(prompt + std::min(max_new, KV_ADMIT_AHEAD), e->cfg.max_seq_len); }
+
+void share_pages(DotsEngine* e, int slot, const int32_t* pages, int n) {
+    auto& mine = e->slot_pages[slot];
+    for (int p = 0; p < n; ++p) {
+        mine.push_back(pages[p]);
+        e->page_refs[pages[p]] += 1;
+        e->hp_table[(size_t)slot * e->max_pages + p] = pages[p];
+    }
+}
+
+// ---- what admitting a slot consists of: one implementation of every step that prefill(), prefill_begin() / prefill_advance(),
+// dots_slots_fork, dots_slots_beam and dots_slots_extend share
+// slots[i] of a list of free destination slots, against the engine and the entries before it; src: the source slot of a fork or group
+int check_free_slot(DotsEngine* e, const int32_t* slots, int i, int src, const char* src_of) {
+    const int d = slots[i], mb = e->cfg.max_batch, usable = e->spec_k ? mb / (e->spec_k + 1) : mb;
+    if (d < 0 || d >= mb) return e->fail(DOTS_E_INVALID, "slot %d out of range [0, %d)", d, mb);
+    if (d >= usable)
+        return e->fail(DOTS_E_CAPACITY, "slot %d is not usable while speculating: with %d drafts a slot takes %d rows of a step, so only slots [0, max_batch / (k + 1)) = [0, %d) are",
+                       d, e->spec_k, e->spec_k + 1, usable);
+    if (d == src) return e->fail(DOTS_E_INVALID, "slot %d is the source of the %s", d, src_of);
+    if (slot_occupied(e, d)) return e->fail(DOTS_E_STATE, "slot %d is occupied", d);
+    if (e->slot_mode && slot_filling(e, d)) return e->fail(DOTS_E_STATE, "slot %d is filling (dots_slots_prefill_begin)", d);
+    for (int a = 0; a < i; ++a)
+        if (slots[a] == d) return e->fail(DOTS_E_INVALID, "slot %d listed twice", d);
+    return DOTS_OK;
+}
+
+// prompt b of a prefill: its length, then (slots given) its destination slot and its generation cap
+int check_prompt(DotsEngine* e, int b, int len, const int32_t* slots, const int32_t* max_new) {
+    const int msl = e->cfg.max_seq_len;
+    if (len < 1 || len >= msl) return e->fail(DOTS_E_CAPACITY, "prompt %d length %d not in [1, max_seq_len)", b, len);
+    if (!slots) return DOTS_OK;
+    RET(check_free_slot(e, slots, b));
+    if (max_new[b] < 1 || len + max_new[b] > msl)
+        return e->fail(DOTS_E_CAPACITY, "slot %d: prompt (%d) + max_new_tokens (%d) exceeds max_seq_len %d", slots[b], len, max_new[b], msl);
+    return DOTS_OK;
+}
+
+// the ids of one prompt as launch_embed_gather reads them: the id, or -(k) for the k-th row of `vis` counted in *vis_used (no_tower: the
+// prompt runs no tower, its image rows come from the prefix cache — INT32_MIN)
+int map_prompt(DotsEngine* e, const int32_t* ids, int n, bool no_tower, int32_t* src, int64_t* vis_used) {
+    for (int i = 0; i < n; ++i) {
+        const int id = ids[i];
+        if (id == e->cfg.image_token_id) src[i] = no_tower ? INT32_MIN : -(int32_t)(++*vis_used);
+        else if (id < 0 || id >= e->cfg.vocab_size) return e->fail(DOTS_E_INVALID, "token id %d out of range", id);
+        else src[i] = id;
+    }
+    return DOTS_OK;
+}
+int check_vis_rows(DotsEngine* e, int64_t vis_used) {
+    if (vis_used == (vis_used ? e->vis_rows : 0)) return DOTS_OK;
+    return e->fail(DOTS_E_STATE, "prompt has %lld image tokens but the vision tower produced %lld rows", (long long)vis_used, (long long)e->vis_rows);
+}
+
+// slot mode with every slot free, every page in the pool and every device table row on the scratch page
+int enter_slot_mode(DotsEngine* e) {
+    for (int b = 0; b < (int)e->slot_pages.size(); ++b) release_pages(e, b);
+    RET(beam_clear_all(e));
+    CK(hipMemcpyAsync(e->block_table, e->hp_table.data(), e->hp_table.size() * 4, hipMemcpyHostToDevice, e->stream));
+    std::fill(e->slot_active, e->slot_active + DOTS_MAX_BATCH, 0);
+    CK(hipMemsetAsync(e->ctx_len, 0, e->cfg.max_batch * 4, e->stream));
+    e->slot_mode = true;
+    e->B = 0;                                              // the static-batch entry points need a static prefill first
+    return DOTS_OK;
+}
+
+// The device state of rows going live, which the selection stage and the step after it read: context, generation cap, nothing generated,
+// not finished, no drafts and the speculation counters from zero, logprob positions unset.  Resets beyond what a caller did before it
+// called this: a beam group's rows get the speculation counters zeroed, which nothing can show (a group is refused while the engine
+// speculates, and dots_set_speculation zeroes every counter).  clear_lp = false keeps what a group's rows do show: they return no
+// logprobs, and dots_row_logprobs of one reads the positions of the row's previous occupant
+int rows_go_live(DotsEngine* e, const std::vector<LiveRow>& rows, bool clear_lp) {
+    hipStream_t s = e->stream;
+    e->hp_live = rows;
+    for (const LiveRow& r : e->hp_live) {
+        CK(hipMemcpyAsync(e->ctx_len + r.slot, &r.ctx, 4, hipMemcpyHostToDevice, s));
+        CK(hipMemcpyAsync(e->d_max_len + r.slot, &r.cap, 4, hipMemcpyHostToDevice, s));
+        CK(hipMemsetAsync(e->out_lens + r.slot, 0, 4, s));
+        CK(hipMemsetAsync(e->finished + r.slot, 0, 4, s));
+        if (e->sp_ndraft) {
+            CK(hipMemsetAsync(e->sp_ndraft + r.slot, 0, 4, s));
+            CK(hipMemsetAsync(e->sp_stats + (size_t)r.slot * 3, 0, 3 * sizeof(unsigned long long), s));
+        }
+        if (clear_lp) RET(clear_lp_row(e, r.slot));
+    }
+    return DOTS_OK;
+}
+
+// the mask of the next first-token selection: these rows only; d_list (p_dst or nullptr) gets their slots in order.  *n_rows: the rows
+// the lm_head and the selection stage run over
+int stage_new_rows(DotsEngine* e, const std::vector<LiveRow>& rows, int32_t* d_list, int* n_rows) {
+    e->hp_new.assign(2 * DOTS_MAX_BATCH, 0);
+    *n_rows = 0;
+    for (size_t i = 0; i < rows.size(); ++i) {
+        e->hp_new[rows[i].slot] = 1;
+        e->hp_new[DOTS_MAX_BATCH + i] = rows[i].slot;
+        *n_rows = std::max(*n_rows, rows[i].slot + 1);
+    }
+    CK(hipMemcpyAsync(e->d_sel_new, e->hp_new.data(), DOTS_MAX_BATCH * 4, hipMemcpyHostToDevice, e->stream));
+    if (d_list) CK(hipMemcpyAsync(d_list, e->hp_new.data() + DOTS_MAX_BATCH, rows.size() * 4, hipMemcpyHostToDevice, e->stream));
+    return DOTS_OK;
+}
+
+// the automata of the rows that hold a guide start over (the first token is selected under the guide), and so do their stop automata,
+// whose hit records are cleared: the first token's bytes are the first ones walked.  d_rows: device list of n rows, nullptr = rows [0, n)
+int restart_automata(DotsEngine* e, const int32_t* d_rows, int n, bool stops) {
+    if (e->stage.rows(ROW_GUIDE) > 0) CK(launch_guide_reset_rows(e->stream, e->d_guides, d_rows, n));
+    if (stops && e->stage.rows(ROW_STOP) > 0) CK(launch_stop_reset_rows(e->stream, e->d_stop, d_rows, n));
+    return DOTS_OK;
+}
+
+// the first tokens: final norm and lm_head over the rows of h (nullptr: the logits are in place), then the selection stage over the mask
+// of stage_new_rows
+int select_first_tokens(DotsEngine* e, int rows, const bf16_t* h, bf16_t* xn) {
+    const DotsConfig& c = e->cfg;
+    if (h) CK(launch_dec_lmhead(e->stream, h, e->final_norm, e->lm_head_d, e->lm_head_s, e->d_logits, rows, c.hidden_size, c.vocab_size, c.rms_norm_eps, 0, xn));
+    e->B_sel = rows;
+    e->sel_now = e->d_sel_new;
+    return select_tokens(e, 0);
+}
+
+// the host record of live slots; occupy = false: the slots are occupied already (an extend)
+void mark_live(DotsEngine* e, const LiveRow* rows, int n, bool occupy) {
+    for (int i = 0; i < n; ++i) {
+        const int b = rows[i].slot;
+        if (occupy) e->slot_active[b] = 1;
+        e->slot_limit[b] = rows[i].ctx + rows[i].cap;
+        e->slot_prompt[b] = rows[i].ctx;
+        e->slot_ctx_ub[b] = rows[i].ctx;
+        e->slot_done[b] = 0;
+    }
+    e->sel_dirty = true;
+}
 }  // namespace engine
 
 using namespace engine;
@@ -209,18 +342,7 @@ int dots_slots_fork(DotsEngine* e, int src_slot, const int32_t* dst_slots, int n
     const auto fresh = std::find(e->fresh_slots.begin(), e->fresh_slots.end(), src_slot);
     if (!e->slot_mode || !e->slot_active[src_slot] || fresh == e->fresh_slots.end() || slot_parked(e, src_slot))
         return e->fail(DOTS_E_STATE, "slot %d cannot be forked: only a sequence of the most recent dots_slots_prefill, before any decode step", src_slot);
-    const int usable = e->spec_k ? mb / (e->spec_k + 1) : mb;
-    for (int i = 0; i < n; ++i) {
-        const int d = dst_slots[i];
-        if (d < 0 || d >= mb) return e->fail(DOTS_E_INVALID, "slot %d out of range [0, %d)", d, mb);
-        if (d >= usable)
-            return e->fail(DOTS_E_CAPACITY, "slot %d is not usable while speculating: with %d drafts only slots [0, %d) are", d, e->spec_k, usable);
-        if (d == src_slot) return e->fail(DOTS_E_INVALID, "slot %d is the source of the fork", d);
-        if (e->slot_active[d]) return e->fail(DOTS_E_STATE, "slot %d is occupied", d);
-        if (slot_filling(e, d)) return e->fail(DOTS_E_STATE, "slot %d is filling", d);
-        for (int a = 0; a < i; ++a)
-            if (dst_slots[a] == d) return e->fail(DOTS_E_INVALID, "slot %d listed twice", d);
-    }
+    for (int i = 0; i < n; ++i) RET(check_free_slot(e, dst_slots, i, src_slot, "fork"));
     // ---- page arithmetic: the children name the source's floor(L / 64) full prompt pages and own the rest of the admission reserve
     const int L = e->slot_prompt[src_slot], max_new = e->slot_limit[src_slot] - L;
     const int shared = L / 64, own = (admit_tokens(e, L, max_new) + 63) / 64 - shared;          // own >= 1: the reserve is at least L + 1 tokens
@@ -233,56 +355,30 @@ int dots_slots_fork(DotsEngine* e, int src_slot, const int32_t* dst_slots, int n
     CK(hipSetDevice(e->device));
     hipStream_t s = e->stream;
     // ---- from here on the call changes state; a failed launch gives the children's pages back (the slots are not marked occupied yet)
-    struct ForkGuard {
-        DotsEngine* e; const int32_t* dst; int n; bool armed = true;
-        ~ForkGuard() {
-            if (!armed) return;
-            for (int i = 0; i < n; ++i) { release_pages(e, dst[i]); (void)upload_table_row(e, dst[i]); }
-        }
-    } guard{e, dst_slots, n};
-    int32_t stage[3 * DOTS_MAX_BATCH] = {0}, sel_new[DOTS_MAX_BATCH] = {0};
-    int rows = 0;
+    PageGuard guard{e, dst_slots, n, true};
+    int32_t stage[3 * DOTS_MAX_BATCH] = {0};
+    std::vector<LiveRow> live(n);
     for (int i = 0; i < n; ++i) {
         const int d = dst_slots[i];
-        auto& mine = e->slot_pages[d];
-        for (int p = 0; p < shared; ++p) {                 // one more holder of a page nobody writes any more: every row appends at positions >= L
-            mine.push_back(src_pages[p]);
-            e->page_refs[src_pages[p]] += 1;
-            e->hp_table[(size_t)d * e->max_pages + p] = src_pages[p];
-        }
+        share_pages(e, d, src_pages.data(), shared);       // every row appends at positions >= L
         bool changed = false;
         grow_pages(e, d, (shared + own) * 64, &changed);   // cannot fall short: counted above
         CK(upload_table_row(e, d));
         stage[i] = d;
-        stage[DOTS_MAX_BATCH + i] = mine[shared];
-        sel_new[d] = 1;
-        rows = std::max(rows, d + 1);
+        stage[DOTS_MAX_BATCH + i] = e->slot_pages[d][shared];
+        live[i] = LiveRow{d, L, max_new};
     }
     stage[2 * DOTS_MAX_BATCH] = L - 1;
     CK(hipMemcpyAsync(e->fk_dev, stage, sizeof(stage), hipMemcpyHostToDevice, s));
     const int32_t *fk_dst = e->fk_dev, *fk_pages = e->fk_dev + DOTS_MAX_BATCH, *fk_last = e->fk_dev + 2 * DOTS_MAX_BATCH;
     // the tail page: behind the prefill's page writers on the same stream; its source is written by nobody until the source's first step
-    if (L % 64) {
-        const size_t page_bytes = (size_t)c.num_kv_heads * 2 * 8192 * (e->kv8 ? 1 : 2);
-        CK(launch_kv_fork_pages(s, e->pool, e->pool_layer_elems * 2, page_bytes, c.num_layers, src_pages[shared], fk_pages, n));
-    }
-    // ---- per-row decode state, as the prefill sets it
-    const int32_t cap = max_new;
-    for (int i = 0; i < n; ++i) {
-        const int d = dst_slots[i];
-        CK(hipMemcpyAsync(e->ctx_len + d, &L, 4, hipMemcpyHostToDevice, s));
-        CK(hipMemcpyAsync(e->d_max_len + d, &cap, 4, hipMemcpyHostToDevice, s));
-        CK(hipMemsetAsync(e->out_lens + d, 0, 4, s));
-        CK(hipMemsetAsync(e->finished + d, 0, 4, s));
-        if (e->sp_ndraft) {
-            CK(hipMemsetAsync(e->sp_ndraft + d, 0, 4, s));
-            CK(hipMemsetAsync(e->sp_stats + (size_t)d * 3, 0, 3 * sizeof(unsigned long long), s));
-        }
-        RET(clear_lp_row(e, d));
-        // the source's last-position logits row (rows of d_logits are slots; nothing has run over them since the prefill)
-        CK(hipMemcpyAsync(e->d_logits + (size_t)d * V, e->d_logits + (size_t)src_slot * V, (size_t)V * 4, hipMemcpyDeviceToDevice, s));
-    }
-    CK(hipMemcpyAsync(e->d_sel_new, sel_new, sizeof(sel_new), hipMemcpyHostToDevice, s));
+    if (L % 64) CK(launch_kv_fork_pages(s, e->pool, e->pool_layer_elems * 2, kv_page_bytes(e), c.num_layers, src_pages[shared], fk_pages, n));
+    RET(rows_go_live(e, live));
+    // the source's last-position logits row (rows of d_logits are slots; nothing has run over them since the prefill)
+    for (int i = 0; i < n; ++i)
+        CK(hipMemcpyAsync(e->d_logits + (size_t)dst_slots[i] * V, e->d_logits + (size_t)src_slot * V, (size_t)V * 4, hipMemcpyDeviceToDevice, s));
+    int rows = 0;
+    RET(stage_new_rows(e, live, nullptr, &rows));
     if (e->pen_cnt && e->fresh_chunked) {
         // a source filled in passes: p_src holds its last pass only, but its own presence bits are the whole prompt's and nothing has been counted yet
         const size_t W = (size_t)(V + 31) / 32;
@@ -297,27 +393,17 @@ int dots_slots_fork(DotsEngine* e, int src_slot, const int32_t* dst_slots, int n
         const int32_t* src0 = e->p_src + (b ? e->hp_last[b - 1] + 1 : 0);
         for (int i = 0; i < n; ++i) CK(launch_pen_prompt(s, src0, fk_last, fk_dst + i, 1, c.image_token_id, V, e->pen_cnt, e->pen_seen));
     }
-    if (e->stage.rows(ROW_GUIDE) > 0) CK(launch_guide_reset_rows(s, e->d_guides, fk_dst, n));
-    if (e->stage.has(src_slot, ROW_STOP)) {
+    const bool inherits = e->stage.has(src_slot, ROW_STOP);
+    RET(restart_automata(e, fk_dst, n, !inherits));
+    if (inherits) {
         // the children inherit the source's stop strings (automaton and min_tokens) at the root with no hit: one launch writes all their entries
         for (int i = 0; i < n; ++i) RET(hold_row_stop(e, dst_slots[i], e->row_stop[src_slot] - 1, e->row_stop_min[src_slot]));
         CK(launch_stop_fork_rows(s, e->d_stop, src_slot, fk_dst, n));
-    } else if (e->stage.rows(ROW_STOP) > 0)
-        CK(launch_stop_reset_rows(s, e->d_stop, fk_dst, n));
-    CK(hipStreamSynchronize(s));                           // L, cap and the staged arrays are stack variables
-    // ---- the children's first tokens: the selection stage over a mask of the children only
-    e->B_sel = rows;
-    e->sel_now = e->d_sel_new;
-    RET(select_tokens(e, 0));
-    for (int i = 0; i < n; ++i) {
-        const int d = dst_slots[i];
-        e->slot_active[d] = 1;
-        e->slot_limit[d] = L + max_new;
-        e->slot_prompt[d] = L;
-        e->slot_ctx_ub[d] = L;
-        e->slot_done[d] = 0;
     }
-    e->sel_dirty = true;
+    CK(hipStreamSynchronize(s));                           // `stage` is a stack array
+    // ---- the children's first tokens, from the logits in place
+    RET(select_first_tokens(e, rows, nullptr));
+    mark_live(e, live.data(), n);
     guard.armed = false;
     return DOTS_OK;
 }
@@ -406,7 +492,7 @@ int dots_slots_extend(DotsEngine* e, const int32_t* slots, int n, const int32_t*
     int32_t *h_slot = st.data(), *h_off = h_slot + n_rows, *h_tok = h_off + n_rows, *h_slots = h_tok + n_rows, *h_fed = h_slots + n, *h_new = h_fed + n,
             *h_gsrc = h_new + n, *h_gdst = h_gsrc + n;
     std::vector<int> chunk_g0((size_t)(n_rows + mb - 1) / mb + 1, 0);
-    int32_t sel_new[DOTS_MAX_BATCH] = {0};
+    std::vector<LiveRow> live(n);
     int rows = 0;
     {
         int64_t r = 0, t = 0;
@@ -421,14 +507,13 @@ int dots_slots_extend(DotsEngine* e, const int32_t* slots, int n, const int32_t*
             h_slots[i] = slots[i]; h_fed[i] = fed[i]; h_new[i] = max_new_tokens[i];
             h_gsrc[g] = (int32_t)((r - 1) % mb); h_gdst[g] = slots[i];      // slots end in row order, so the lists are in chunk order
             chunk_g0[(size_t)((r - 1) / mb) + 1] = ++g;
-            sel_new[slots[i]] = 1;
-            rows = std::max(rows, slots[i] + 1);
+            live[i] = LiveRow{slots[i], new_prompt[i], max_new_tokens[i]};
         }
         for (size_t k = 1; k < chunk_g0.size(); ++k) chunk_g0[k] = std::max(chunk_g0[k], chunk_g0[k - 1]);
     }
     CK(hipMemcpyAsync(e->ex_stage, st.data(), n_stage * 4, hipMemcpyHostToDevice, s));
-    CK(hipMemcpyAsync(e->d_sel_new, sel_new, sizeof(sel_new), hipMemcpyHostToDevice, s));
-    CK(hipStreamSynchronize(s));                             // the staged lists are stack and local variables
+    RET(stage_new_rows(e, live, nullptr, &rows));
+    CK(hipStreamSynchronize(s));                             // the staged lists are local variables
     const int32_t *d_slot = e->ex_stage, *d_off = d_slot + n_rows, *d_tok = d_off + n_rows, *d_slots = d_tok + n_rows, *d_fed = d_slots + n,
                   *d_new = d_fed + n, *d_gsrc = d_new + n, *d_gdst = d_gsrc + n;
     // ---- from here on the call changes state; a failed launch gives the new pages back
@@ -472,22 +557,11 @@ int dots_slots_extend(DotsEngine* e, const int32_t* slots, int n, const int32_t*
     // ---- the slots' state: that of slots prefilled with the longer prompt
     CK(launch_extend_commit(s, d_slots, d_fed, d_new, n, e->ctx_len, e->out_lens, e->finished, e->d_max_len));
     for (int i = 0; i < n; ++i) RET(clear_lp_row(e, slots[i]));
-    if (e->stage.rows(ROW_GUIDE) > 0) CK(launch_guide_reset_rows(s, e->d_guides, d_slots, n));
-    if (e->stage.rows(ROW_STOP) > 0) CK(launch_stop_reset_rows(s, e->d_stop, d_slots, n));
+    RET(restart_automata(e, d_slots, n));
     // ---- the first tokens of the new turn: lm_head over the slots' last fed rows, the selection stage over a mask of the extended slots only
-    CK(launch_dec_lmhead(s, e->ex_h, e->final_norm, e->lm_head_d, e->lm_head_s, e->d_logits, rows, H, V, c.rms_norm_eps, 0, e->d_xn));
-    e->B_sel = rows;
-    e->sel_now = e->d_sel_new;
-    RET(select_tokens(e, 0));
+    RET(select_first_tokens(e, rows, e->ex_h, e->d_xn));
     CK(hipStreamSynchronize(s));
-    for (int i = 0; i < n; ++i) {
-        const int b = slots[i];
-        e->slot_prompt[b] = new_prompt[i];
-        e->slot_limit[b] = new_prompt[i] + max_new_tokens[i];
-        e->slot_ctx_ub[b] = new_prompt[i];
-        e->slot_done[b] = 0;
-    }
-    e->sel_dirty = true;
+    mark_live(e, live.data(), n, false);
     guard.armed = false;
     return DOTS_OK;
 }
@@ -502,13 +576,9 @@ int dots_slots_reset(DotsEngine* e) {
         if (!e->pref_deferred) CK(hipStreamWaitEvent(s, e->ev_vis_ready, 0));
         e->pref_pending = e->pref_deferred = false;
     }
-    for (int b = 0; b < (int)e->slot_pages.size(); ++b) release_pages(e, b);
+    RET(enter_slot_mode(e));
     if (e->pc) e->pc->release_all();                      // the leases of an abandoned serving loop; the cached blocks stay
-    RET(beam_clear_all(e));
     e->fresh_slots.clear();
-    CK(hipMemcpyAsync(e->block_table, e->hp_table.data(), e->hp_table.size() * 4, hipMemcpyHostToDevice, s));
-    std::fill(e->slot_active, e->slot_active + DOTS_MAX_BATCH, 0);
-    CK(hipMemsetAsync(e->ctx_len, 0, e->cfg.max_batch * 4, s));
     CK(hipMemsetAsync(e->out_lens, 0, e->cfg.max_batch * 4, s));
     CK(hipMemsetAsync(e->finished, 0, e->cfg.max_batch * 4, s));
     // no row carries any feature: the features' row tables (in RowFeature order; the own flags stand for the parameters), then the host record
@@ -528,9 +598,7 @@ int dots_slots_reset(DotsEngine* e) {
     if (e->sp_ndraft) CK(hipMemsetAsync(e->sp_ndraft, 0, DOTS_MAX_BATCH * 4, s));
     if (e->sp_cls) CK(hipMemsetAsync(e->sp_cls, 0, DOTS_MAX_BATCH * 4, s));         // SPEC_ROW_ARGMAX: no row carries anything
     CK(hipStreamSynchronize(s));
-    e->slot_mode = true;
     e->sel_dirty = true;
-    e->B = 0;
     return DOTS_OK;
 }
 
@@ -637,7 +705,7 @@ int dots_slots_poll(DotsEngine* e, int32_t* finished, int32_t* out_lens) {
 
 int dots_slot_read(DotsEngine* e, int slot, int32_t* out_ids, int capacity, int32_t* n_out) {
     if (!e || !out_ids || !n_out || capacity < 0) return e ? e->fail(DOTS_E_INVALID, "bad slot_read arguments") : DOTS_E_INVALID;
-    if (!e->slot_mode || slot < 0 || slot >= e->cfg.max_batch || !e->slot_active[slot]) return e->fail(DOTS_E_STATE, "slot %d is not occupied", slot);
+    if (!slot_occupied(e, slot)) return e->fail(DOTS_E_STATE, "slot %d is not occupied", slot);
     CK(hipSetDevice(e->device));
     int32_t n = 0;
     CK(hipMemcpyAsync(&n, e->out_lens + slot, 4, hipMemcpyDeviceToHost, e->stream));
@@ -653,7 +721,7 @@ int dots_slot_read(DotsEngine* e, int slot, int32_t* out_ids, int capacity, int3
 
 int dots_slot_logits(DotsEngine* e, int slot, float* out) {
     if (!e || !out) return e ? e->fail(DOTS_E_INVALID, "null argument") : DOTS_E_INVALID;
-    if (!e->slot_mode || slot < 0 || slot >= e->cfg.max_batch || !e->slot_active[slot]) return e->fail(DOTS_E_STATE, "slot %d is not occupied", slot);
+    if (!slot_occupied(e, slot)) return e->fail(DOTS_E_STATE, "slot %d is not occupied", slot);
     CK(hipSetDevice(e->device));
     CK(hipMemcpyAsync(out, e->d_logits + (size_t)slot * e->cfg.vocab_size, (size_t)e->cfg.vocab_size * 4, hipMemcpyDeviceToHost, e->stream));
     CK(hipStreamSynchronize(e->stream));
@@ -662,7 +730,7 @@ int dots_slot_logits(DotsEngine* e, int slot, float* out) {
 
 int dots_slot_release(DotsEngine* e, int slot) {
     if (!e) return DOTS_E_INVALID;
-    if (!e->slot_mode || slot < 0 || slot >= e->cfg.max_batch || (!e->slot_active[slot] && !e->fill[slot].on)) return e->fail(DOTS_E_STATE, "slot %d is not occupied", slot);
+    if (!slot_occupied(e, slot) && !(e->slot_mode && slot_filling(e, slot))) return e->fail(DOTS_E_STATE, "slot %d is not occupied", slot);
     CK(hipSetDevice(e->device));
     if (e->beam_of[slot]) return beam_release_group(e, slot);          // the slots of a beam group go together
     for (int f = 0; f < ROW_FEATURES; ++f) RET(clear_row_feature(e, slot, (RowFeature)f));
@@ -676,7 +744,6 @@ int dots_slot_release(DotsEngine* e, int slot) {
 }
 
 // ---------------------------------------------------------------------------------- suspend / resume
-static size_t kv_page_bytes(const DotsEngine* e) { return (size_t)e->cfg.num_kv_heads * 2 * 8192 * (e->kv8 ? 1 : 2); }      // one page of one layer
 static size_t swap_unit_bytes(const DotsEngine* e) { return kv_page_bytes(e) * e->cfg.num_layers; }                          // one host page
 
 // Moves n pages between the pool and the host space in chunks of KV_SWAP_CHUNK_PAGES through the staging buffer, in order on the engine's
@@ -734,7 +801,7 @@ int dots_kv_swap_info(DotsEngine* e, int32_t* total_pages, int32_t* free_pages) 
 
 int dots_slot_suspend(DotsEngine* e, int slot) {
     if (!e) return DOTS_E_INVALID;
-    if (!e->slot_mode || slot < 0 || slot >= e->cfg.max_batch || !e->slot_active[slot]) return e->fail(DOTS_E_STATE, "slot %d is not occupied", slot);
+    if (!slot_occupied(e, slot)) return e->fail(DOTS_E_STATE, "slot %d is not occupied", slot);
     if (e->parked[slot].on) return e->fail(DOTS_E_STATE, "slot %d is already suspended", slot);
     if (e->beam_of[slot]) return e->fail(DOTS_E_STATE, "slot %d is a row of a beam group: a group cannot be suspended", slot);
     if (e->spec_k) return e->fail(DOTS_E_STATE, "a slot cannot be suspended while the engine speculates (dots_set_speculation)");
@@ -795,7 +862,7 @@ int dots_slot_suspend(DotsEngine* e, int slot) {
 
 int dots_slot_resume(DotsEngine* e, int slot) {
     if (!e) return DOTS_E_INVALID;
-    if (!e->slot_mode || slot < 0 || slot >= e->cfg.max_batch || !e->slot_active[slot] || !e->parked[slot].on)
+    if (!slot_occupied(e, slot) || !e->parked[slot].on)
         return e->fail(DOTS_E_STATE, "slot %d is not suspended", slot);
     DotsEngine::Parked& pk = e->parked[slot];
     int need = 0;
@@ -872,7 +939,7 @@ int dots_set_kv_scales(DotsEngine* e, const float* scales_host) {
 
 int dots_slot_capacity(DotsEngine* e, int slot, int32_t* pages_owned, int32_t* token_limit) {
     if (!e || !pages_owned || !token_limit) return DOTS_E_INVALID;
-    if (!e->slot_mode || slot < 0 || slot >= e->cfg.max_batch || !e->slot_active[slot]) return e->fail(DOTS_E_STATE, "slot %d is not occupied", slot);
+    if (!slot_occupied(e, slot)) return e->fail(DOTS_E_STATE, "slot %d is not occupied", slot);
     *pages_owned = (int32_t)e->slot_pages[slot].size();
     *token_limit = e->slot_limit[slot];
     return DOTS_OK;
