@@ -35,6 +35,7 @@
 #include "common.h"
 #include "decode_layout.h"
 #include "kernels.h"
+#include "switches.h"
 
 namespace {
 
@@ -189,9 +190,9 @@ hipError_t launch_flash_attn_paged(hipStream_t s, const bf16_t* q, const void* p
     // register file holds without spilling (K and V fragments 128 registers, O 32 per head; 6 heads spilled 180 registers).  One head per
     // wave — three times the workgroups, two waves per SIMD — was measured for launches with few work items and lost everywhere (one A4
     // prompt 0.36 against 0.27 ms, a 1 024-position pass of the full-size model 18.4 against 13.7 ms: profiles/chunked_prefill.txt).
-    // DOTS_OCR_PAGED_ATTN_HEADS=1 still selects it: the choice changes no bit (header), which tests/test_paged_prefill_attn_gpu.py checks.
+    // DOTS_OCR_PAGED_ATTN_HEADS=1 still selects it (read per call): the choice changes no bit (header), which tests/test_paged_prefill_attn_gpu.py checks.
     int g_heads = group % 3 == 0 ? 3 : (group % 2 == 0 ? 2 : 1);
-    if (const char* env = getenv("DOTS_OCR_PAGED_ATTN_HEADS"); env && atoi(env) == 1) g_heads = 1;
+    if (sw::parse_paged_attn_one_head(sw::read_now(sw::PAGED_ATTN_HEADS))) g_heads = 1;
 #define PAGED_GO(GV)                                                                                                                       \
     do {                                                                                                                                   \
         const dim3 grid(n_items, Hq / GV);                                                                                                 \

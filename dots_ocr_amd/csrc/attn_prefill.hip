@@ -33,6 +33,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace {
 
@@ -718,55 +719,34 @@ hipError_t launch_flash_attn(hipStream_t s, const bf16_t* q, const bf16_t* k, co
     if (n_blocks <= 0) return hipSuccess;
     if (Hq % Hkv != 0) return hipErrorInvalidValue;
     const float c = scale * 1.44269504088896340736f;
-    dim3 grid(n_blocks);                      // n_blocks = work items (seq x head x query block)
-    // DOTS_OCR_ATTN_MODE: 2 (default) = bidirectional: 4 waves x 64 rows, LDS-DMA tiles, softmax interleaved with the MFMAs (round 4);
-    // causal: as 1.  1 = 8 waves, ping-pong halves + LDS fragment look-ahead (rounds 1-3), 0 = the round-1 schedule
-    static const int mode = getenv("DOTS_OCR_ATTN_MODE") ? atoi(getenv("DOTS_OCR_ATTN_MODE")) : 2;
-    auto go = [&](auto kern, int threads, int lds) -> hipError_t {
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            if (e != hipSuccess) return e;
+    // mode 2 (default) = bidirectional: 4 waves x 64 rows, LDS-DMA tiles, softmax interleaved with the MFMAs (round 4); causal: on the same
+    // 64-row kernel since round 6 (prefill_f64).  1 = 8 waves, ping-pong halves + LDS fragment look-ahead (rounds 1-3), 0 = the round-1 schedule
+    const LaunchSwitches& lsw = launch_switches();
+    const int group = Hq / Hkv;
+    if (flash_rows_per_block() == 256 && lsw.attn_mode == 2 && (!causal || lsw.prefill_f64)) {
+        XcdPlan pl;
+        if (plan) pl = *plan;
+        else {                                               // no plan from the caller: xcd_remap's equal-count chunks
+            const int qn = n_blocks / 8, rn = n_blocks % 8;
+            for (int x = 0, pos = 0; x < 8; ++x) { pl.base[x] = pos; pl.cnt[x] = qn + (x < rn ? 1 : 0); pos += pl.cnt[x]; }
         }
-        hipLaunchKernelGGL(kern, grid, dim3(threads), lds, s, q, k, vt, out, blocks, n_blocks, T, Tpad, Hq, Hq / Hkv, c);
-        return hipGetLastError();
-    };
-    if (flash_rows_per_block() == 256) {
-        // causal (LM prefill) on the 64-row kernel since round 6; DOTS_OCR_PREFILL_F64=0: the 8-wave kernel of rounds 1-3 (A/B switch)
-        static const bool causal64 = !(getenv("DOTS_OCR_PREFILL_F64") && atoi(getenv("DOTS_OCR_PREFILL_F64")) == 0);
-        if (mode == 2 && (!causal || causal64)) {
-            // dynamic LDS > 64 KB is opted into once per DEVICE (engines on several GPUs may live in one process): bit d of the mask
-            static uint32_t attr_done[2] = {0, 0};
-            int dev = 0;
-            hipError_t e = hipGetDevice(&dev);
-            if (e != hipSuccess) return e;
-            const uint32_t bit = 1u << (dev & 31);
-            if (!(__atomic_load_n(&attr_done[causal ? 1 : 0], __ATOMIC_ACQUIRE) & bit)) {
-                e = causal ? hipFuncSetAttribute(reinterpret_cast<const void*>(flash_attn64_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, RING_BYTES)
-                           : hipFuncSetAttribute(reinterpret_cast<const void*>(flash_attn64_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, RING_BYTES);
-                if (e != hipSuccess) return e;
-                __atomic_fetch_or(&attr_done[causal ? 1 : 0], bit, __ATOMIC_RELEASE);
-            }
-            XcdPlan pl;
-            if (plan) pl = *plan;
-            else {                                               // no plan from the caller: xcd_remap's equal-count chunks
-                const int qn = n_blocks / 8, rn = n_blocks % 8;
-                for (int x = 0, pos = 0; x < 8; ++x) { pl.base[x] = pos; pl.cnt[x] = qn + (x < rn ? 1 : 0); pos += pl.cnt[x]; }
-            }
-            int mx = 0;
-            for (int x = 0; x < 8; ++x) mx = std::max(mx, (int)pl.cnt[x]);
-            if (causal) hipLaunchKernelGGL(flash_attn64_kernel<true>, dim3(8 * mx), dim3(256), RING_BYTES, s, q, k, vt, out, blocks, n_blocks, T, Tpad, Hq, Hq / Hkv, c, pl);
-            else hipLaunchKernelGGL(flash_attn64_kernel<false>, dim3(8 * mx), dim3(256), RING_BYTES, s, q, k, vt, out, blocks, n_blocks, T, Tpad, Hq, Hq / Hkv, c, pl);
-            return hipGetLastError();
-        }
-        if (mode >= 1) return causal ? go(flash_attn_kernel<true, 8, 1>, 512, 3 * BUF_BYTES) : go(flash_attn_kernel<false, 8, 1>, 512, 3 * BUF_BYTES);
-        return causal ? go(flash_attn_kernel<true, 8, 0>, 512, 2 * BUF_BYTES) : go(flash_attn_kernel<false, 8, 0>, 512, 2 * BUF_BYTES);
+        int mx = 0;
+        for (int x = 0; x < 8; ++x) mx = std::max(mx, (int)pl.cnt[x]);
+        return causal ? launch_dyn_lds<flash_attn64_kernel<true>>(dim3(8 * mx), dim3(256), RING_BYTES, s, q, k, vt, out, blocks, n_blocks, T, Tpad, Hq, group, c, pl)
+                      : launch_dyn_lds<flash_attn64_kernel<false>>(dim3(8 * mx), dim3(256), RING_BYTES, s, q, k, vt, out, blocks, n_blocks, T, Tpad, Hq, group, c, pl);
     }
-    return causal ? go(flash_attn_kernel<true, 4, 0>, 256, 2 * BUF_BYTES) : go(flash_attn_kernel<false, 4, 0>, 256, 2 * BUF_BYTES);
+    // flash_attn_kernel<CAUSAL, waves, MODE>: n_blocks work items (seq x head x query block)
+    auto go = [&](auto waves, auto mode, int lds) {
+        constexpr int NW = decltype(waves)::value, MODE = decltype(mode)::value;
+        return causal ? launch_dyn_lds<flash_attn_kernel<true, NW, MODE>>(dim3(n_blocks), dim3(NW * 64), lds, s, q, k, vt, out, blocks, n_blocks, T, Tpad, Hq, group, c)
+                      : launch_dyn_lds<flash_attn_kernel<false, NW, MODE>>(dim3(n_blocks), dim3(NW * 64), lds, s, q, k, vt, out, blocks, n_blocks, T, Tpad, Hq, group, c);
+    };
+    if (flash_rows_per_block() == 256) return lsw.attn_mode >= 1 ? go(int_c<8>{}, int_c<1>{}, 3 * BUF_BYTES) : go(int_c<8>{}, int_c<0>{}, 2 * BUF_BYTES);
+    return go(int_c<4>{}, int_c<0>{}, 2 * BUF_BYTES);
 }
 
 // query rows per work item: 256 (8 waves sharing each K/V tile, 1 workgroup per CU; default: half the global->LDS staging
 // work per wave, measured +2-3 % in interleaved A/B) or 128 (4 waves, 2 independent workgroups per CU; DOTS_OCR_ATTN_ROWS128=1)
 int flash_rows_per_block() {
-    static const int rows = getenv("DOTS_OCR_ATTN_ROWS128") ? 128 : 256;
-    return rows;
+    return launch_switches().attn_rows128 ? 128 : 256;
 }

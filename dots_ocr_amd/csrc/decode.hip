@@ -29,6 +29,7 @@
 #include "common.h"
 #include "decode_layout.h"
 #include "kernels.h"
+#include "launch.h"
 #include "select_dev.h"
 #include "step_dev.h"
 
@@ -938,18 +939,8 @@ hipError_t launch_unpack_x(hipStream_t s, const bf16_t* x, bf16_t* dst, int rows
 // batch (a sequence's partial sums must depend on its own context only).  DOTS_OCR_ATTN_WAVES overrides it for experiments.
 // Measured round 6 (profiles/r06_decode_attn_waves_ab.txt): 1 and 2 waves are slower everywhere; 8 waves gain 1.5 % of the step at 8 rows, lose 6 % at one
 // row (svg) and 1.4 % at 64 rows on the 64-CU partition: 4 stays.
-int decode_attn_waves() {
-    static const int nw = [] {
-        const char* e = getenv("DOTS_OCR_ATTN_WAVES");
-        const int v = e ? atoi(e) : 4;
-        return (v == 1 || v == 2 || v == 8) ? v : 4;
-    }();
-    return nw;
-}
-int decode_attn_splits(int max_seq_len) {
-    const int pages = (max_seq_len + PAGE - 1) / PAGE, nw = decode_attn_waves();
-    return std::max(1, std::min((pages + nw - 1) / nw, 64));
-}
+int decode_attn_waves() { return launch_switches().attn_waves; }
+int decode_attn_splits(int max_seq_len) { return sw::attn_splits(max_seq_len, PAGE, decode_attn_waves()); }
 
 // Which decode-attention kernel runs (process-wide; both produce the same bits): the per-split kernel (default), or the streaming kernel
 // with one workgroup per CU.  MEASURED (profiles/r05_decode_attn_stream_ab.txt): the streaming kernel is the slower one everywhere — 237 vs
@@ -960,17 +951,10 @@ int decode_attn_splits(int max_seq_len) {
 // process default (DOTS_OCR_ATTN_STREAM=1: wherever legal; DOTS_OCR_ATTN_STREAM_MIN=n: from n items per CU; unset: never).
 // The streaming kernel reads bf16 pages only: 0 for an fp8 pool (kv8), whatever the mode.
 int decode_attn_stream_wgs(int B, int Hkv, int n_splits, int max_pages, int part_cus, int stream_mode, bool kv8) {
-    static const int env_mode = [] { const char* e = getenv("DOTS_OCR_ATTN_STREAM"); return e ? (atoi(e) != 0 ? 1 : 0) : -1; }();
-    static const int min_items = [] { const char* e = getenv("DOTS_OCR_ATTN_STREAM_MIN"); return e ? std::max(1, atoi(e)) : 0; }();
+    const int env_mode = launch_switches().attn_stream, min_items = launch_switches().attn_stream_min;
     const int mode = stream_mode >= 0 ? stream_mode : (env_mode >= 0 ? env_mode : (min_items > 0 ? -1 : 0));
     if (kv8 || mode == 0 || decode_attn_waves() != ST_NW || (int64_t)n_splits * ST_NW < max_pages || B > MAX_DECODE_ROWS) return 0;
-    static int n_cus = 0;
-    if (n_cus == 0) {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 1) { (void)hipGetLastError(); v = 256; }
-        n_cus = v;
-    }
-    const int cus = part_cus > 0 ? std::min(part_cus, n_cus) : n_cus, items = B * Hkv * n_splits;
+    const int n_cus = device_cus(), cus = part_cus > 0 ? std::min(part_cus, n_cus) : n_cus, items = B * Hkv * n_splits;
     if (mode == 1) return std::min(cus, items);
     return items >= min_items * cus ? cus : 0;
 }
@@ -982,40 +966,31 @@ hipError_t launch_decode_attn(hipStream_t s, const bf16_t* q, const void* pool_l
     const float sl = scale * 1.44269504088896340736f;
     const int nw = decode_attn_waves(), group = Hq / Hkv;
     if (const int wgs = decode_attn_stream_wgs(B, Hkv, n_splits, max_pages, part_cus, stream_mode, kv_scales != nullptr)) {
-        static uint32_t attr = 0;
         const size_t lds_s = (size_t)ST_NW * ST_PAGE_BYTES + ((size_t)ST_NW * group * AT_LD + 2 * ST_NW * 16) * sizeof(float) + 2 * MAX_DECODE_ROWS * sizeof(int);
-        int dev = 0;
-        hipError_t e = hipGetDevice(&dev);
-        if (e != hipSuccess) return e;
-        const uint32_t bit = 1u << (dev & 31);
-        if (!(__atomic_load_n(&attr, __ATOMIC_ACQUIRE) & bit)) {            // dynamic LDS above 64 KiB: opted into once per device
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&decode_attn_stream_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s);
-            if (e != hipSuccess) return e;
-            __atomic_fetch_or(&attr, bit, __ATOMIC_RELEASE);
-        }
-        hipLaunchKernelGGL(decode_attn_stream_kernel, dim3(wgs), dim3(ST_NW * 64), lds_s, s, q, (const bf16_t*)pool_layer, ctx_len, block_table, max_pages, part_o, part_ml,
-                           B, Hq, Hkv, n_splits, sl);
-        return hipGetLastError();
+        return launch_dyn_lds<decode_attn_stream_kernel>(dim3(wgs), dim3(ST_NW * 64), lds_s, s, q, (const bf16_t*)pool_layer, ctx_len, block_table, max_pages, part_o, part_ml,
+                                                         B, Hq, Hkv, n_splits, sl);
     }
     const dim3 grid(n_splits, Hkv, B);
     const size_t lds = ((size_t)nw * group * AT_LD + 2 * nw * 16) * sizeof(float);
     const bool one = (int64_t)n_splits * nw >= max_pages;        // every wave owns at most one page: the light-weight instantiation
-#define ATTN_GO(NWV, ONEV)                                                                                                                    \
-    do {                                                                                                                                      \
-        if (kv_scales)                                                                                                                        \
-            hipLaunchKernelGGL((decode_attn_kernel<NWV, ONEV, uint8_t>), grid, dim3(NWV * 64), lds, s, q, (const uint8_t*)pool_layer, ctx_len, \
-                               block_table, max_pages, part_o, part_ml, Hq, Hkv, n_splits, sl, kv_scales);                                    \
-        else                                                                                                                                  \
-            hipLaunchKernelGGL((decode_attn_kernel<NWV, ONEV>), grid, dim3(NWV * 64), lds, s, q, (const bf16_t*)pool_layer, ctx_len,           \
-                               block_table, max_pages, part_o, part_ml, Hq, Hkv, n_splits, sl, nullptr);                                      \
-    } while (0)
+    // decode_attn_kernel<waves, ONE, pool element>
+    auto go = [&](auto nwv, auto onev) {
+        constexpr int NW = decltype(nwv)::value;
+        constexpr bool ONE = decltype(onev)::value;
+        if (kv_scales)
+            hipLaunchKernelGGL((decode_attn_kernel<NW, ONE, uint8_t>), grid, dim3(NW * 64), lds, s, q, (const uint8_t*)pool_layer, ctx_len, block_table, max_pages, part_o, part_ml,
+                               Hq, Hkv, n_splits, sl, kv_scales);
+        else
+            hipLaunchKernelGGL((decode_attn_kernel<NW, ONE>), grid, dim3(NW * 64), lds, s, q, (const bf16_t*)pool_layer, ctx_len, block_table, max_pages, part_o, part_ml,
+                               Hq, Hkv, n_splits, sl, nullptr);
+    };
+    auto go_nw = [&](auto nwv) { if (one) go(nwv, std::true_type{}); else go(nwv, std::false_type{}); };
     switch (nw) {
-        case 1: if (one) ATTN_GO(1, true); else ATTN_GO(1, false); break;
-        case 2: if (one) ATTN_GO(2, true); else ATTN_GO(2, false); break;
-        case 8: if (one) ATTN_GO(8, true); else ATTN_GO(8, false); break;
-        default: if (one) ATTN_GO(4, true); else ATTN_GO(4, false); break;
+        case 1: go_nw(int_c<1>{}); break;
+        case 2: go_nw(int_c<2>{}); break;
+        case 8: go_nw(int_c<8>{}); break;
+        default: go_nw(int_c<4>{}); break;
     }
-#undef ATTN_GO
     return hipGetLastError();
 }
 

@@ -23,6 +23,7 @@
 #include "common.h"
 #include "decode_layout.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace {
 TRACE_DECL
@@ -385,55 +386,28 @@ __global__ __launch_bounds__(NWV * 64) void dec_stream64_kernel(const bf16_t* __
     TRACE(6);
 }
 
-template <typename Kern>
-hipError_t ensure_lds64(Kern kern, size_t bytes, uint32_t* done_mask) {
-    if (bytes <= 64 * 1024) return hipSuccess;
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    const uint32_t bit = 1u << (dev & 31);
-    if (__atomic_load_n(done_mask, __ATOMIC_ACQUIRE) & bit) return hipSuccess;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) return e;
-    __atomic_fetch_or(done_mask, bit, __ATOMIC_RELEASE);
-    return hipSuccess;
-}
-
-int device_cus() {
-    static int n_cus = 0;
-    if (n_cus == 0) {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 1) { (void)hipGetLastError(); v = 256; }
-        n_cus = v;
-    }
-    return n_cus;
-}
-
 template <int MODE, typename WT>
 hipError_t stream64_launch(hipStream_t s, const bf16_t* xn, const WT* Wd, const float* wscale, void* out, int B, int K, int N, int n_items, int cus) {
-    static uint32_t attr[6] = {0, 0, 0, 0, 0, 0};
     const int L = K / 128;
     const size_t lds = (size_t)S64_NBUF * S64_TT * L * 1024;
     const int G = std::max(1, std::min(n_items, cus));
     const int per_wg = (n_items + G - 1) / G;
-    auto go = [&](auto kern, int nwv, uint32_t* done) -> hipError_t {
-        hipError_t e = ensure_lds64(kern, lds, done);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3(G), dim3(nwv * 64), lds, s, xn, Wd, wscale, out, B, K, N, n_items);
-        return hipGetLastError();
+    // dec_stream64_kernel<MODE, WT, waves, ring depth, K chunk>
+    auto go = [&](auto nwv, auto depth, auto chunk) {
+        return launch_dyn_lds<dec_stream64_kernel<MODE, WT, decltype(nwv)::value, decltype(depth)::value, decltype(chunk)::value>>(
+            dim3(G), dim3(decltype(nwv)::value * 64), lds, s, xn, Wd, wscale, out, B, K, N, n_items);
     };
     // few items per workgroup (the whole chip): few waves with a deep ring each; many (a CU partition; the lm_head): 12 waves
-    static const int force = [] { const char* e = getenv("DOTS_OCR_S64_WAVES"); return e ? atoi(e) : 0; }();      // A/B switch: 4 / 8 / 12
+    const int force = launch_switches().s64_waves;
     const int nwv = force ? force : (per_wg <= 4 ? 4 : per_wg <= 8 ? 8 : 12);
     if (L == 12) {
-        if (nwv == 4) return go(dec_stream64_kernel<MODE, WT, 4, 24, 12>, 4, &attr[0]);
-        if (nwv == 8) return go(dec_stream64_kernel<MODE, WT, 8, 12, 12>, 8, &attr[1]);
-        if constexpr (MODE == S64_GATEUP) return go(dec_stream64_kernel<MODE, WT, 12, 8, 12>, 12, &attr[2]);
-        else return go(dec_stream64_kernel<MODE, WT, 12, 6, 12>, 12, &attr[2]);
+        if (nwv == 4) return go(int_c<4>{}, int_c<24>{}, int_c<12>{});
+        if (nwv == 8) return go(int_c<8>{}, int_c<12>{}, int_c<12>{});
+        return go(int_c<12>{}, int_c<(MODE == S64_GATEUP ? 8 : 6)>{}, int_c<12>{});
     }
-    if (nwv == 4) return go(dec_stream64_kernel<MODE, WT, 4, 24, 6>, 4, &attr[3]);
-    if (nwv == 8) return go(dec_stream64_kernel<MODE, WT, 8, 12, 6>, 8, &attr[4]);
-    return go(dec_stream64_kernel<MODE, WT, 12, 6, 6>, 12, &attr[5]);
+    if (nwv == 4) return go(int_c<4>{}, int_c<24>{}, int_c<6>{});
+    if (nwv == 8) return go(int_c<8>{}, int_c<12>{}, int_c<6>{});
+    return go(int_c<12>{}, int_c<6>{}, int_c<6>{});
 }
 
 }  // namespace
@@ -443,8 +417,7 @@ void dots_trace_set_b64(unsigned long long* buf) { (void)hipMemcpyToSymbol(HIP_S
 #endif
 
 bool dec_stream64_supports(int B, int H) {
-    static const bool off = getenv("DOTS_OCR_DEC_S64") && atoi(getenv("DOTS_OCR_DEC_S64")) == 0;      // A/B switch: the round-4 two-tile kernels
-    return !off && B > 32 && B <= MAX_DECODE_ROWS && (H == 128 * 12 || H == 128 * 6);       // K chunk = 12 k-steps (dots.ocr) or 6 (the tests' small model)
+    return launch_switches().dec_s64 && B > 32 && B <= MAX_DECODE_ROWS && (H == 128 * 12 || H == 128 * 6);       // K chunk = 12 k-steps (dots.ocr) or 6 (the tests' small model)
 }
 
 hipError_t launch_dec_norm_ximg(hipStream_t s, const bf16_t* h_in, const bf16_t* ln_w, bf16_t* xn, int B, int H, float eps, const float* part, const float* pscale) {
@@ -457,8 +430,8 @@ hipError_t launch_dec_norm_ximg(hipStream_t s, const bf16_t* h_in, const bf16_t*
 
 // the projections above 32 rows as four K quarters: part[4][64][N] <- the quarters' slice sums (h is NOT updated: launch_dec_norm_ximg(.., part, wscale) does that).
 bool dec_proj_ksplit_supports(int B, int N, int K) {
-    const char* env = getenv("DOTS_OCR_DEC_KSPLIT");                // A/B switch, read per call (tests flip it): 0 = dec_proj_wide_kernel over the full K,
-    const int mode = env ? atoi(env) : 1;                           // 1 = long K only (down_proj), 2 = o_proj too
+    const int mode = sw::parse_dec_ksplit(sw::read_now(sw::DEC_KSPLIT));      // read per call: the tests flip it
+    // 0 = dec_proj_wide_kernel over the full K, 1 = long K only (down_proj), 2 = o_proj too
     const int min_ks = mode >= 2 ? 16 : 64;
     return mode > 0 && B > 32 && B <= MAX_DECODE_ROWS && N % 16 == 0 && N <= 512 * NC_MAX && K % 32 == 0 && K / 32 >= min_ks;      // N: what the norm kernel's rows hold
 }
@@ -466,22 +439,24 @@ bool dec_proj_ksplit_supports(int B, int N, int K) {
 hipError_t launch_dec_proj_ksplit(hipStream_t s, const bf16_t* X, const void* Wd, bool fp8, float* part, int B, int N, int K, int cus) {
     if (!dec_proj_ksplit_supports(B, N, K) || !part) return hipErrorInvalidValue;
     if (cus <= 0) cus = device_cus();
-    static uint32_t attr[12] = {0};
     const int n_units = N / 8;
     // 4 K quarters x ceil(n_units / nu) workgroups in ONE round on the CUs the stream may use; a workgroup takes up to 12 units (6 MFMAs of 16 weight rows)
     const int nu = std::max(1, std::min(12, (DEC_KSPLIT_PARTS * n_units + cus - 1) / cus)), nm = (nu + 1) / 2;
     const size_t lds = (size_t)KS_WAVES * nm * S64_TT * 64 * sizeof(f32x4);
     const dim3 grid(DEC_KSPLIT_PARTS, (n_units + nu - 1) / nu);
-    auto go = [&](auto kern, auto wd, uint32_t* done) -> hipError_t {
-        hipError_t e = ensure_lds64(kern, lds, done);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, grid, dim3(KS_WAVES * 64), lds, s, X, wd, part, B, N, K, nu);
-        return hipGetLastError();
+    auto go = [&](auto nmv) {
+        return by_weight_type(Wd, fp8, [&](auto wd) {
+            return launch_dyn_lds<dec_proj_ksplit_kernel<decltype(nmv)::value, weight_t<decltype(wd)>>>(grid, dim3(KS_WAVES * 64), lds, s, X, wd, part, B, N, K, nu);
+        });
     };
-#define KSPLIT(NMV) if (nm == NMV) return fp8 ? go(dec_proj_ksplit_kernel<NMV, u32x2>, (const u32x2*)Wd, &attr[2 * (NMV - 1)]) : go(dec_proj_ksplit_kernel<NMV, bf16x8>, (const bf16x8*)Wd, &attr[2 * (NMV - 1) + 1])
-    KSPLIT(1); KSPLIT(2); KSPLIT(3); KSPLIT(4); KSPLIT(5);
-    return fp8 ? go(dec_proj_ksplit_kernel<6, u32x2>, (const u32x2*)Wd, &attr[10]) : go(dec_proj_ksplit_kernel<6, bf16x8>, (const bf16x8*)Wd, &attr[11]);
-#undef KSPLIT
+    switch (nm) {
+        case 1: return go(int_c<1>{});
+        case 2: return go(int_c<2>{});
+        case 3: return go(int_c<3>{});
+        case 4: return go(int_c<4>{});
+        case 5: return go(int_c<5>{});
+        default: return go(int_c<6>{});
+    }
 }
 
 // act = silu(gate) * up of rmsnorm(h), B in (32, 64]: norm kernel -> xn (scratch: 64 x H bf16), then the streaming kernel.  cus: CUs the stream may use.

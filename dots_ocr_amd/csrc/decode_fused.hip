@@ -38,6 +38,7 @@
 #include "common.h"
 #include "decode_layout.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace {
 TRACE_DECL
@@ -969,21 +970,6 @@ __global__ __launch_bounds__(1024) void dec_lmhead2_kernel(const bf16_t* __restr
     if (m + 16 < B) *reinterpret_cast<f32x4*>(logits + (size_t)(m + 16) * V + n_tile * 16 + 4 * g) = acc1;
 }
 
-// Dynamic-LDS opt-in above 64 KiB, once per (kernel, device): handles of different devices may live in one process.
-template <typename Kern>
-hipError_t ensure_lds(Kern kern, size_t bytes, uint32_t* done_mask) {
-    if (bytes <= 64 * 1024) return hipSuccess;
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    const uint32_t bit = 1u << (dev & 31);
-    if (__atomic_load_n(done_mask, __ATOMIC_ACQUIRE) & bit) return hipSuccess;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) return e;
-    __atomic_fetch_or(done_mask, bit, __ATOMIC_RELEASE);
-    return hipSuccess;
-}
-
 }  // namespace
 
 #ifdef DOTS_TRACE
@@ -998,23 +984,6 @@ hipError_t launch_dec_embed(hipStream_t s, const int32_t* tokens, const bf16_t* 
 
 // Wd / wscale of the launchers: wscale == nullptr -> Wd is the bf16 fragment image (launch_pack_frag*), else Wd is the e4m3
 // fragment image (launch_pack_frag_fp8) and wscale its per-row fp32 scales.
-// CUs a decode stream may use: the partition it is masked to, or the device.  DOTS_OCR_DEC_WIDE_CUS overrides (tests, A/B runs; read per call).
-static int wide_cus(int part_cus) {
-    if (const char* e = getenv("DOTS_OCR_DEC_WIDE_CUS")) { const int v = atoi(e); if (v > 0) return v; }
-    if (part_cus > 0) return part_cus;
-    static int n_cus = 0;
-    if (n_cus == 0) {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 1) { (void)hipGetLastError(); v = 256; }
-        n_cus = v;
-    }
-    return n_cus;
-}
-// batches above 16 rows run the wide kernels (DOTS_OCR_DEC_WIDE=0: the per-tile kernels, A/B switch; same bits)
-static bool wide_on() {
-    static const bool on = !(getenv("DOTS_OCR_DEC_WIDE") && atoi(getenv("DOTS_OCR_DEC_WIDE")) == 0);
-    return on;
-}
 
 // part_cus > 0: the stream is CU-masked to that many CUs (the decode partition of the pipelined step): whole 16-row weight tiles per workgroup
 // (half as many workgroups) at B <= 16, as many features per workgroup as one round on those CUs needs above.
@@ -1024,62 +993,43 @@ static hipError_t dec_qkv_launch(hipStream_t s, const bf16_t* h, const bf16_t* l
                           KVT* pool_layer, bf16_t* q_out, int B, int H, int Hq, int Hkv, float eps, int part_cus, bf16_t* xn,
                           const float* pend, const float* pend_scale, const float* kv_scales) {
     if (H % 32 || H > 512 * NC_MAX || B < 1 || B > MAX_DECODE_ROWS) return hipErrorInvalidValue;
-    const int full_tiles = part_cus > 0;
-    {   // a pending K-split residual update that the X-image path below will not fuse into its norm launch gets a launch of its own
-        static const bool ximg_on0 = !(getenv("DOTS_OCR_QKV_XIMG") && atoi(getenv("DOTS_OCR_QKV_XIMG")) == 0);
-        if (pend && !(B > 16 && wide_on() && xn && B > 32 && ximg_on0)) {
-            HIP_CHECK_RET(launch_dec_norm_ximg(s, h, nullptr, nullptr, B, H, eps, pend, pend_scale));
-            pend = nullptr;
-        }
+    const bool wide = B > 16 && launch_switches().dec_wide;
+    // round 6, above 32 rows: the rows are normalised once by a small kernel (X image in xn) instead of by every workgroup
+    const bool ximg = wide && xn && B > 32 && launch_switches().qkv_ximg;
+    if (pend && !ximg) {          // a pending K-split residual update that the X-image norm launch will not fuse gets a launch of its own
+        HIP_CHECK_RET(launch_dec_norm_ximg(s, h, nullptr, nullptr, B, H, eps, pend, pend_scale));
+        pend = nullptr;
     }
-    if (B > 16 && wide_on()) {
-        static uint32_t attr_w[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        // round 6, above 32 rows: the rows are normalised once by a small kernel (X image in xn) instead of by every workgroup
-        static const bool ximg_on = !(getenv("DOTS_OCR_QKV_XIMG") && atoi(getenv("DOTS_OCR_QKV_XIMG")) == 0);     // A/B switch
-        const bool ximg = xn && B > 32 && ximg_on;
+    if (wide) {
         if (ximg) HIP_CHECK_RET(launch_dec_norm_ximg(s, h, ln_w, xn, B, H, eps, pend, pend_scale));
         const int n_out = (Hq + 2 * Hkv) * 8, cus = wide_cus(part_cus);
         const int nm = (n_out + cus - 1) / cus >= 2 ? 2 : 1, tt = B <= 32 ? 2 : 4;
         const size_t lds_w = (size_t)16 * nm * tt * 64 * sizeof(f32x4) + MAX_DECODE_ROWS * sizeof(float);
         const dim3 grid_w(1, (n_out + nm - 1) / nm);
-        auto go = [&](auto kern, auto wd, uint32_t* done) -> hipError_t {
-            hipError_t e = ensure_lds(kern, lds_w, done);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(kern, grid_w, dim3(1024), lds_w, s, h, ln_w, wd, wscale, bias, inv_freq, ctx_len, block_table, max_pages, pool_layer, q_out, B, H, Hq, Hkv, eps, kv_scales);
-            return hipGetLastError();
+        auto go = [&](auto nmv, auto ttv, auto xv) {
+            return by_weight_type(Wd, wscale != nullptr, [&](auto wd) {
+                constexpr bool X = decltype(xv)::value;
+                return launch_dyn_lds<dec_qkv_wide_kernel<decltype(nmv)::value, decltype(ttv)::value, NC_MAX, weight_t<decltype(wd)>, X, KVT>>(
+                    grid_w, dim3(1024), lds_w, s, X ? xn : h, ln_w, wd, wscale, bias, inv_freq, ctx_len, block_table, max_pages, pool_layer, q_out, B, H, Hq, Hkv, eps, kv_scales);
+            });
         };
-#define QKV_WIDE(NMV, TTV, IDX)                                                                                                     \
-        return wscale ? go(dec_qkv_wide_kernel<NMV, TTV, NC_MAX, u32x2, false, KVT>, (const u32x2*)Wd, &attr_w[IDX])                  \
-                      : go(dec_qkv_wide_kernel<NMV, TTV, NC_MAX, bf16x8, false, KVT>, (const bf16x8*)Wd, &attr_w[IDX + 1])
-        if (ximg) {          // tt == 4
-            const bf16_t* hx = xn;
-            auto gox = [&](auto kern, auto wd, uint32_t* done) -> hipError_t {
-                hipError_t e = ensure_lds(kern, lds_w, done);
-                if (e != hipSuccess) return e;
-                hipLaunchKernelGGL(kern, grid_w, dim3(1024), lds_w, s, hx, ln_w, wd, wscale, bias, inv_freq, ctx_len, block_table, max_pages, pool_layer, q_out, B, H, Hq, Hkv, eps, kv_scales);
-                return hipGetLastError();
-            };
-            if (nm == 1) return wscale ? gox(dec_qkv_wide_kernel<1, 4, NC_MAX, u32x2, true, KVT>, (const u32x2*)Wd, &attr_w[8]) : gox(dec_qkv_wide_kernel<1, 4, NC_MAX, bf16x8, true, KVT>, (const bf16x8*)Wd, &attr_w[9]);
-            return wscale ? gox(dec_qkv_wide_kernel<2, 4, NC_MAX, u32x2, true, KVT>, (const u32x2*)Wd, &attr_w[10]) : gox(dec_qkv_wide_kernel<2, 4, NC_MAX, bf16x8, true, KVT>, (const bf16x8*)Wd, &attr_w[11]);
-        }
-        if (nm == 1 && tt == 2) { QKV_WIDE(1, 2, 0); }
-        if (nm == 1) { QKV_WIDE(1, 4, 2); }
-        if (tt == 2) { QKV_WIDE(2, 2, 4); }
-        QKV_WIDE(2, 4, 6);
-#undef QKV_WIDE
+        if (ximg) return nm == 1 ? go(int_c<1>{}, int_c<4>{}, std::true_type{}) : go(int_c<2>{}, int_c<4>{}, std::true_type{});          // tt == 4
+        if (nm == 1) return tt == 2 ? go(int_c<1>{}, int_c<2>{}, std::false_type{}) : go(int_c<1>{}, int_c<4>{}, std::false_type{});
+        return tt == 2 ? go(int_c<2>{}, int_c<2>{}, std::false_type{}) : go(int_c<2>{}, int_c<4>{}, std::false_type{});
     }
-    static uint32_t attr[4] = {0, 0, 0, 0};
     const int XR = B <= 8 ? 8 : 16;
     const size_t lds = (size_t)XR * H * 2 + 16 * 64 * sizeof(f32x4), lds_max = (size_t)16 * H * 2 + 16 * 64 * sizeof(f32x4);
-    const dim3 grid((B + 15) / 16, (Hq + 2 * Hkv) * (full_tiles ? 8 : 16));
-    auto go = [&](auto kern, auto wd, uint32_t* done) -> hipError_t {
-        hipError_t e = ensure_lds(kern, lds_max, done);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, grid, dim3(1024), lds, s, h, ln_w, wd, wscale, bias, inv_freq, ctx_len, block_table, max_pages, pool_layer, q_out, B, H, Hq, Hkv, eps, XR, kv_scales);
-        return hipGetLastError();
-    };
-    if (wscale) return full_tiles ? go(dec_qkv_kernel<NC_MAX, u32x2, true, KVT>, (const u32x2*)Wd, &attr[3]) : go(dec_qkv_kernel<NC_MAX, u32x2, false, KVT>, (const u32x2*)Wd, &attr[1]);
-    return full_tiles ? go(dec_qkv_kernel<NC_MAX, bf16x8, true, KVT>, (const bf16x8*)Wd, &attr[2]) : go(dec_qkv_kernel<NC_MAX, bf16x8, false, KVT>, (const bf16x8*)Wd, &attr[0]);
+    return by_weight_type(Wd, wscale != nullptr, [&](auto wd) {
+        auto go = [&](auto full) {
+            constexpr bool F = decltype(full)::value;
+            constexpr auto kern = dec_qkv_kernel<NC_MAX, weight_t<decltype(wd)>, F, KVT>;
+            HIP_CHECK_RET(ensure_dyn_lds<kern>(lds_max));
+            hipLaunchKernelGGL(kern, dim3((B + 15) / 16, (Hq + 2 * Hkv) * (F ? 8 : 16)), dim3(1024), lds, s, h, ln_w, wd, wscale, bias, inv_freq, ctx_len, block_table, max_pages,
+                               pool_layer, q_out, B, H, Hq, Hkv, eps, XR, kv_scales);
+            return hipGetLastError();
+        };
+        return part_cus > 0 ? go(std::true_type{}) : go(std::false_type{});
+    });
 }
 
 // kv_scales == nullptr: bf16 page pool; else pool_layer is an fp8 (e4m3fn) pool and kv_scales [Hkv][K | V] this layer's fp32 scales
@@ -1098,136 +1048,81 @@ hipError_t launch_dec_qkv(hipStream_t s, const bf16_t* h, const bf16_t* ln_w, co
 hipError_t launch_dec_proj(hipStream_t s, const bf16_t* X, const void* Wd, const float* wscale, bf16_t* h, int B, int N, int K, int part_cus,
                            float* part, bool* pending) {
     if (N % 16 || K % 32 || K / 32 < 16 || B < 1 || B > MAX_DECODE_ROWS) return hipErrorInvalidValue;
+    const bool wide = launch_switches().dec_wide, fp8 = wscale != nullptr;
     if (pending) *pending = false;
-    if (part && pending && wide_on() && dec_proj_ksplit_supports(B, N, K)) {         // round 6: four K quarters, the residual update is the consumer's (decode_b64.hip)
+    if (part && pending && wide && dec_proj_ksplit_supports(B, N, K)) {         // round 6: four K quarters, the residual update is the consumer's (decode_b64.hip)
         *pending = true;
-        return launch_dec_proj_ksplit(s, X, Wd, wscale != nullptr, part, B, N, K, wide_cus(part_cus));
+        return launch_dec_proj_ksplit(s, X, Wd, fp8, part, B, N, K, wide_cus(part_cus));
     }
-    const int full_tiles = part_cus > 0;
-    if (B > 16 && wide_on()) {
-        static uint32_t attr_w[16] = {0};
+    if (B > 16 && wide) {
         const int n_units = N / 8, cus = wide_cus(part_cus);
         const bool one = (K / 32 + 15) / 16 <= WIDE_G;                            // a slice is at most WIDE_G k-steps: one round
         const int nu = std::max(1, std::min(4, (n_units + cus - 1) / cus)), nm = (nu + 1) / 2, tt = B <= 32 ? 2 : 4;
         const size_t lds_w = (size_t)16 * nm * tt * 64 * sizeof(f32x4);
         const dim3 grid_w(1, (n_units + nu - 1) / nu);
-        auto go = [&](auto kern, auto wd, uint32_t* done) -> hipError_t {
-            hipError_t e = ensure_lds(kern, lds_w, done);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(kern, grid_w, dim3(1024), lds_w, s, X, wd, wscale, h, B, N, K, nu);
-            return hipGetLastError();
+        auto go1 = [&](auto nmv, auto ttv, auto onev) {
+            return by_weight_type(Wd, fp8, [&](auto wd) {
+                return launch_dyn_lds<dec_proj_wide_kernel<decltype(nmv)::value, decltype(ttv)::value, weight_t<decltype(wd)>, decltype(onev)::value>>(
+                    grid_w, dim3(1024), lds_w, s, X, wd, wscale, h, B, N, K, nu);
+            });
         };
-#define PROJ_WIDE(NMV, TTV, IDX)                                                                                                  \
-        if (one) return wscale ? go(dec_proj_wide_kernel<NMV, TTV, u32x2, true>, (const u32x2*)Wd, &attr_w[8 + IDX])               \
-                               : go(dec_proj_wide_kernel<NMV, TTV, bf16x8, true>, (const bf16x8*)Wd, &attr_w[8 + IDX + 1]);         \
-        return wscale ? go(dec_proj_wide_kernel<NMV, TTV, u32x2, false>, (const u32x2*)Wd, &attr_w[IDX])                            \
-                      : go(dec_proj_wide_kernel<NMV, TTV, bf16x8, false>, (const bf16x8*)Wd, &attr_w[IDX + 1])
-        if (nm == 1 && tt == 2) { PROJ_WIDE(1, 2, 0); }
-        if (nm == 1) { PROJ_WIDE(1, 4, 2); }
-        if (tt == 2) { PROJ_WIDE(2, 2, 4); }
-        PROJ_WIDE(2, 4, 6);
-#undef PROJ_WIDE
+        auto go = [&](auto nmv, auto ttv) { return one ? go1(nmv, ttv, std::true_type{}) : go1(nmv, ttv, std::false_type{}); };
+        if (nm == 1) return tt == 2 ? go(int_c<1>{}, int_c<2>{}) : go(int_c<1>{}, int_c<4>{});
+        return tt == 2 ? go(int_c<2>{}, int_c<2>{}) : go(int_c<2>{}, int_c<4>{});
     }
+    const bool full_tiles = part_cus > 0;
     const int need = (K / 32 + 15) / 16, XR = B <= 8 ? 8 : 16;
     const dim3 grid((B + 15) / 16, full_tiles ? N / 16 : N / 8);
-#define PROJ_LAUNCH(G, F)                                                                                                                        \
-    do {                                                                                                                                         \
-        if (wscale) hipLaunchKernelGGL((dec_proj_kernel<G, u32x2, F>), grid, dim3(1024), 0, s, X, (const u32x2*)Wd, wscale, h, B, N, K, XR);      \
-        else hipLaunchKernelGGL((dec_proj_kernel<G, bf16x8, F>), grid, dim3(1024), 0, s, X, (const bf16x8*)Wd, wscale, h, B, N, K, XR);           \
-    } while (0)
-#define PROJ_CASE(G) do { if (full_tiles) PROJ_LAUNCH(G, true); else PROJ_LAUNCH(G, false); } while (0)
-    static const bool no_lds = getenv("DOTS_OCR_PROJ_REG") != nullptr;            // A/B switch: the register-round kernel for long K too
     const size_t lds_x = (size_t)16 * K + 16 * 64 * sizeof(f32x4);
-    if (!no_lds && B <= 8 && need > 4 && need <= PROJ_LDS_G && lds_x <= 160 * 1024) {
-        static uint32_t attr_l[4] = {0, 0, 0, 0};
-        auto go = [&](auto kern, auto wd, uint32_t* done) -> hipError_t {
-            hipError_t e = ensure_lds(kern, lds_x, done);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(kern, grid, dim3(1024), lds_x, s, X, wd, wscale, h, B, N, K);
+    if (!launch_switches().proj_reg && B <= 8 && need > 4 && need <= PROJ_LDS_G && lds_x <= 160 * 1024)          // long K: the X image in LDS
+        return by_weight_type(Wd, fp8, [&](auto wd) {
+            using WT = weight_t<decltype(wd)>;
+            return full_tiles ? launch_dyn_lds<dec_proj_lds_kernel<WT, true>>(grid, dim3(1024), lds_x, s, X, wd, wscale, h, B, N, K)
+                              : launch_dyn_lds<dec_proj_lds_kernel<WT, false>>(grid, dim3(1024), lds_x, s, X, wd, wscale, h, B, N, K);
+        });
+    // register rounds of G k-steps per wave; above four the weight type decides (PROJ_G_FP8 for e4m3, 6 for bf16)
+    auto go1 = [&](auto gv, auto full) {
+        return by_weight_type(Wd, fp8, [&](auto wd) {
+            using WT = weight_t<decltype(wd)>;
+            constexpr int G = decltype(gv)::value <= 4 ? decltype(gv)::value : is_fp8<WT>::value ? PROJ_G_FP8 : 6;
+            hipLaunchKernelGGL((dec_proj_kernel<G, WT, decltype(full)::value>), grid, dim3(1024), 0, s, X, wd, wscale, h, B, N, K, XR);
             return hipGetLastError();
-        };
-        if (wscale) return full_tiles ? go(dec_proj_lds_kernel<u32x2, true>, (const u32x2*)Wd, &attr_l[3]) : go(dec_proj_lds_kernel<u32x2, false>, (const u32x2*)Wd, &attr_l[1]);
-        return full_tiles ? go(dec_proj_lds_kernel<bf16x8, true>, (const bf16x8*)Wd, &attr_l[2]) : go(dec_proj_lds_kernel<bf16x8, false>, (const bf16x8*)Wd, &attr_l[0]);
-    }
-    if (need <= 1) PROJ_CASE(1);
-    else if (need <= 2) PROJ_CASE(2);
-    else if (need <= 3) PROJ_CASE(3);
-    else if (need <= 4) PROJ_CASE(4);
-    else if (wscale) { if (full_tiles) PROJ_LAUNCH(PROJ_G_FP8, true); else PROJ_LAUNCH(PROJ_G_FP8, false); }
-    else PROJ_CASE(6);
-#undef PROJ_CASE
-#undef PROJ_LAUNCH
-    return hipGetLastError();
+        });
+    };
+    auto go = [&](auto gv) { return full_tiles ? go1(gv, std::true_type{}) : go1(gv, std::false_type{}); };
+    return need <= 1 ? go(int_c<1>{}) : need <= 2 ? go(int_c<2>{}) : need <= 3 ? go(int_c<3>{}) : need <= 4 ? go(int_c<4>{}) : go(int_c<5>{});
 }
 
 // part_cus > 0: the stream is CU-masked to that many CUs (the decode partition of the pipelined step): the grid is capped at what those CUs
-// hold at once (occupancy query, cached per kernel) and the kernel walks the remaining pair groups.
-template <typename Kern>
-static int resident_blocks_per_cu(Kern kern, int threads, size_t lds, int* cache) {
-    int v = __atomic_load_n(cache, __ATOMIC_ACQUIRE);
-    if (v > 0) return v;
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(kern), threads, lds) != hipSuccess || n < 1) { (void)hipGetLastError(); n = 1; }
-    __atomic_store_n(cache, n, __ATOMIC_RELEASE);
-    return n;
-}
-
+// hold at once (resident_blocks_per_cu) and the kernel walks the remaining pair groups.
 template <typename WT>
 static hipError_t gateup_launch(hipStream_t s, const bf16_t* h, const bf16_t* ln_w, const WT* W13d, const float* wscale, bf16_t* act,
                                 int B, int H, int I, float eps, int part_cus) {
-    static uint32_t attr[2] = {0, 0};
-    const int XR = B <= 8 ? 8 : 16;
-    const int v = B <= 8 ? 0 : 1;
-    static const int cap_env = [] { const char* e = getenv("DOTS_OCR_GATEUP_WG_CAP"); return e ? atoi(e) : 0; }();     // tests / A-B runs: force the walking path
-    const int tiles = (B + 15) / 16;
-    // 2 pairs per workgroup (8 waves, two rows per wave) for the 16-row image: 14.7 vs 16.4 us at B = 16 (four rows per wave otherwise);
-    // at B <= 8 one pair per workgroup is faster (13.3 vs 13.9 us at B = 8, 11.9 vs 13.6 at B = 1).  DOTS_OCR_GATEUP_PAIRS=1/2 forces either.
-    static const int pairs_env = [] { const char* e = getenv("DOTS_OCR_GATEUP_PAIRS"); return e ? atoi(e) : 0; }();
-    const int pairs = pairs_env ? pairs_env : (B > 8 ? 2 : 1);
-    static const bool per_tile = getenv("DOTS_OCR_GATEUP_PER_TILE") != nullptr;     // A/B switch: one workgroup set per 16-row tile at every batch size
-    // both instantiations (bf16, e4m3) are held to the one-tile kernels bit for bit by tests/test_decode_kernels_gpu.py (round 5: the e4m3 one
-    // too); DOTS_OCR_TWO_TILE_FP8=0 is the A/B switch back to the per-tile kernels for fp8 batches above 16 rows
-    static const bool fp8_ok = !(getenv("DOTS_OCR_TWO_TILE_FP8") && atoi(getenv("DOTS_OCR_TWO_TILE_FP8")) == 0);
-    if (B > 16 && !per_tile && (!wscale || fp8_ok) && (I / 16) % 2 == 0) {          // two batch tiles per workgroup (TT = 2): every weight byte feeds 32 rows
-        static uint32_t attr_t = 0;
-        static int occ_t = 0;
-        const size_t lds_t = (size_t)2 * 16 * H * 2 + 2 * 4 * GU_WAVES * 64 * sizeof(f32x4);
-        if (lds_t <= 160 * 1024) {
-            auto kern_t = dec_gateup_kernel<4, NC_MAX, WT, 2, 2>;
-            hipError_t et = ensure_lds(kern_t, lds_t, &attr_t);
-            if (et != hipSuccess) return et;
-            const int tiles2 = (B + 31) / 32;
-            int gy = I / 32;
-            const int cap = cap_env > 0 ? cap_env : (part_cus > 0 ? part_cus * resident_blocks_per_cu(kern_t, 2 * GU_WAVES * 64, lds_t, &occ_t) : 0);
-            if (cap > 0) gy = std::max(1, std::min(gy, cap / tiles2));
-            hipLaunchKernelGGL(kern_t, dim3(tiles2, gy), dim3(2 * GU_WAVES * 64), lds_t, s, h, ln_w, W13d, wscale, act, B, H, I, eps, 16);
-            return hipGetLastError();
-        }
-    }
-    if (pairs == 2 && (I / 16) % 2 == 0) {
-        static uint32_t attr2[2] = {0, 0};
-        static int occ2[2] = {0, 0};
-        const size_t lds2 = (size_t)XR * H * 2 + 4 * GU_WAVES * 64 * sizeof(f32x4), lds2_max = (size_t)16 * H * 2 + 4 * GU_WAVES * 64 * sizeof(f32x4);
-        auto kern2 = v == 0 ? dec_gateup_kernel<1, NC_MAX, WT, 2> : dec_gateup_kernel<2, NC_MAX, WT, 2>;
-        hipError_t e2 = ensure_lds(kern2, lds2_max, &attr2[v]);
-        if (e2 != hipSuccess) return e2;
-        int gy = I / 32;
-        const int cap = cap_env > 0 ? cap_env : (part_cus > 0 ? part_cus * resident_blocks_per_cu(kern2, 2 * GU_WAVES * 64, lds2, &occ2[v]) : 0);
-        if (cap > 0) gy = std::max(1, std::min(gy, cap / tiles));
-        hipLaunchKernelGGL(kern2, dim3(tiles, gy), dim3(2 * GU_WAVES * 64), lds2, s, h, ln_w, W13d, wscale, act, B, H, I, eps, XR);
+    const LaunchSwitches& lsw = launch_switches();
+    // dec_gateup_kernel<MAXR, NC_MAX, WT, PAIRS, TT> on (tiles_x, gy) workgroups, opted in for lds_max; xr = rows of the X image
+    auto go = [&](auto maxr, auto pairs_c, auto tt, int tiles_x, int gy, size_t lds, size_t lds_max, int xr) {
+        constexpr int threads = decltype(pairs_c)::value * GU_WAVES * 64;
+        constexpr auto kern = dec_gateup_kernel<decltype(maxr)::value, NC_MAX, WT, decltype(pairs_c)::value, decltype(tt)::value>;
+        HIP_CHECK_RET(ensure_dyn_lds<kern>(lds_max));
+        const int cap = lsw.gateup_wg_cap > 0 ? lsw.gateup_wg_cap : (part_cus > 0 ? part_cus * resident_blocks_per_cu<kern>(threads, lds) : 0);
+        if (cap > 0) gy = std::max(1, std::min(gy, cap / tiles_x));
+        hipLaunchKernelGGL(kern, dim3(tiles_x, gy), dim3(threads), lds, s, h, ln_w, W13d, wscale, act, B, H, I, eps, xr);
         return hipGetLastError();
-    }
-    static int occ1[2] = {0, 0};
-    const size_t lds = (size_t)XR * H * 2 + 2 * GU_WAVES * 64 * sizeof(f32x4);
-    const size_t lds_max = (size_t)16 * H * 2 + 2 * GU_WAVES * 64 * sizeof(f32x4);
-    auto kern = v == 0 ? dec_gateup_kernel<2, NC_MAX, WT, 1> : dec_gateup_kernel<4, NC_MAX, WT, 1>;
-    hipError_t e = ensure_lds(kern, lds_max, &attr[v]);
-    if (e != hipSuccess) return e;
-    int gy = I / 16;
-    const int cap = cap_env > 0 ? cap_env : (part_cus > 0 ? part_cus * resident_blocks_per_cu(kern, GU_WAVES * 64, lds, &occ1[v]) : 0);
-    if (cap > 0) gy = std::max(1, std::min(gy, cap / tiles));
-    hipLaunchKernelGGL(kern, dim3(tiles, gy), dim3(GU_WAVES * 64), lds, s, h, ln_w, W13d, wscale, act, B, H, I, eps, XR);
-    return hipGetLastError();
+    };
+    const int XR = B <= 8 ? 8 : 16, tiles = (B + 15) / 16;
+    const size_t x_lds = (size_t)XR * H * 2, x_max = (size_t)16 * H * 2, red = GU_WAVES * 64 * sizeof(f32x4);      // the X image; one split-K reduction buffer
+    const bool even_tiles = (I / 16) % 2 == 0;
+    // both instantiations (bf16, e4m3) are held to the one-tile kernels bit for bit by tests/test_decode_kernels_gpu.py
+    if (B > 16 && !lsw.gateup_per_tile && (!wscale || lsw.two_tile_fp8) && even_tiles && 2 * x_max + 8 * red <= 160 * 1024)      // two batch tiles per workgroup: every weight byte feeds 32 rows
+        return go(int_c<4>{}, int_c<2>{}, int_c<2>{}, (B + 31) / 32, I / 32, 2 * x_max + 8 * red, 2 * x_max + 8 * red, 16);
+    // 2 pairs per workgroup (8 waves, two rows per wave) for the 16-row image: 14.7 vs 16.4 us at B = 16 (four rows per wave otherwise);
+    // at B <= 8 one pair per workgroup is faster (13.3 vs 13.9 us at B = 8, 11.9 vs 13.6 at B = 1)
+    const int pairs = lsw.gateup_pairs ? lsw.gateup_pairs : (B > 8 ? 2 : 1);
+    if (pairs == 2 && even_tiles)
+        return B <= 8 ? go(int_c<1>{}, int_c<2>{}, int_c<1>{}, tiles, I / 32, x_lds + 4 * red, x_max + 4 * red, XR)
+                      : go(int_c<2>{}, int_c<2>{}, int_c<1>{}, tiles, I / 32, x_lds + 4 * red, x_max + 4 * red, XR);
+    return B <= 8 ? go(int_c<2>{}, int_c<1>{}, int_c<1>{}, tiles, I / 16, x_lds + 2 * red, x_max + 2 * red, XR)
+                  : go(int_c<4>{}, int_c<1>{}, int_c<1>{}, tiles, I / 16, x_lds + 2 * red, x_max + 2 * red, XR);
 }
 
 hipError_t launch_dec_gateup(hipStream_t s, const bf16_t* h, const bf16_t* ln_w, const void* W13d, const float* wscale, bf16_t* act,
@@ -1243,20 +1138,13 @@ template <typename WT>
 static hipError_t lmhead_launch(hipStream_t s, const bf16_t* h, const bf16_t* ln_w, const WT* Wd, const float* wscale, float* logits,
                                 int B, int H, int V, float eps) {
     if (H % (32 * LmG<WT>::value)) return hipErrorInvalidValue;
-    static uint32_t attr = 0, attr2 = 0;
-    static const bool per_tile = getenv("DOTS_OCR_LMHEAD_PER_TILE") != nullptr;       // A/B switch: one workgroup set per 16-row tile at every batch size
-    static const bool fp8_ok = !(getenv("DOTS_OCR_TWO_TILE_FP8") && atoi(getenv("DOTS_OCR_TWO_TILE_FP8")) == 0);           // see gateup_launch
-    if (B > 16 && !per_tile && (!wscale || fp8_ok) && (size_t)32 * H * 2 <= 160 * 1024) {   // two batch tiles per workgroup: each weight byte feeds 32 rows
-        hipError_t e2 = ensure_lds(dec_lmhead2_kernel<NC_MAX, WT>, (size_t)32 * H * 2, &attr2);
-        if (e2 != hipSuccess) return e2;
-        hipLaunchKernelGGL((dec_lmhead2_kernel<NC_MAX, WT>), dim3((B + 31) / 32, (V / 16 + 15) / 16), dim3(1024), (size_t)32 * H * 2, s, h, ln_w, Wd, wscale, logits, B, H, V, eps);
-        return hipGetLastError();
-    }
+    const LaunchSwitches& lsw = launch_switches();
+    const size_t x16 = (size_t)16 * H * 2;                  // the X image of one 16-row batch tile
+    if (B > 16 && !lsw.lmhead_per_tile && (!wscale || lsw.two_tile_fp8) && 2 * x16 <= 160 * 1024)      // two batch tiles per workgroup: each weight byte feeds 32 rows (see gateup_launch)
+        return launch_dyn_lds<dec_lmhead2_kernel<NC_MAX, WT>>(dim3((B + 31) / 32, (V / 16 + 15) / 16), dim3(1024), 2 * x16, s, h, ln_w, Wd, wscale, logits, B, H, V, eps);
     const int XR = B <= 8 ? 8 : 16;
-    const size_t lds = (size_t)XR * H * 2;
-    hipError_t e = ensure_lds(dec_lmhead_kernel<NC_MAX, WT>, (size_t)16 * H * 2, &attr);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((dec_lmhead_kernel<NC_MAX, WT>), dim3((B + 15) / 16, (V / 16 + 15) / 16), dim3(1024), lds, s, h, ln_w, Wd, wscale, logits, B, H, V, eps, XR);
+    HIP_CHECK_RET((ensure_dyn_lds<dec_lmhead_kernel<NC_MAX, WT>>(x16)));
+    hipLaunchKernelGGL((dec_lmhead_kernel<NC_MAX, WT>), dim3((B + 15) / 16, (V / 16 + 15) / 16), dim3(1024), (size_t)XR * H * 2, s, h, ln_w, Wd, wscale, logits, B, H, V, eps, XR);
     return hipGetLastError();
 }
 

@@ -22,6 +22,7 @@
 #include "kernels.h"
 #include "prefix_cache.h"
 #include "row_stage.h"
+#include "switches.h"
 
 struct Tensor {
     bf16_t* p = nullptr;

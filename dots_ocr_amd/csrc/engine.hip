@@ -196,10 +196,10 @@ int vit_forward(DotsEngine* e, const float* pix_dev, int64_t N, const int64_t* g
 // bits [0, dec_cus) for the decode loop, [dec_cus, 256) for the tower — each an equal share of every XCD.
 int ensure_overlap_streams(DotsEngine* e) {
     if (e->s_vit) return DOTS_OK;
-    if (const char* v = getenv("DOTS_OCR_OVERLAP_DEC_CUS")) e->dec_cus = std::max(32, std::min(224, atoi(v) / 8 * 8));
+    if (const char* v = sw::read_now(sw::OVERLAP_DEC_CUS)) e->dec_cus = sw::parse_overlap_dec_cus(v);      // per engine, here: bench.py sets it between engines
     uint32_t wd[8] = {0}, wv[8] = {0};
     // DOTS_OCR_OVERLAP_BY_XCD=1 (experiment): whole XCDs instead of an equal share of every XCD — the decode loop gets XCDs 0 .. dec_cus / 32 - 1
-    static const bool by_xcd = getenv("DOTS_OCR_OVERLAP_BY_XCD") != nullptr;
+    const bool by_xcd = launch_switches().overlap_by_xcd;
     for (int b = 0; b < 256; ++b) ((by_xcd ? (b % 8) < e->dec_cus / 32 : b < e->dec_cus) ? wd : wv)[b / 32] |= 1u << (b % 32);
     // A device that refuses CU masks (another compute-partition mode, fewer CUs) still gets correct results: plain streams then
     // time-slice the chip, i.e. the prefetch degenerates to the sequential schedule.
@@ -746,7 +746,7 @@ int decode_layers(DotsEngine* e, const int32_t* tokens, const int32_t* ctx_len, 
     const float scale = 1.0f / sqrtf(128.0f);
     CK(launch_dec_embed(s, tokens, e->embed, e->d_h, B, H));
     if (e->force_part) part = 1;                                                   // dots_set_decode_plan(1): the partition plan on every step (tests, A/B runs)
-    static const bool same_layer = getenv("DOTS_OCR_DEBUG_SAME_LAYER") != nullptr;   // experiment: all weight reads hit the Infinity Cache
+    const bool same_layer = launch_switches().debug_same_layer;   // experiment: all weight reads hit the Infinity Cache
     bool pend = false;                              // down_proj of the previous layer left its K-quarter sums in d_part_h: the next norm launch applies them
     const float* pend_scale = nullptr;
     for (int i = 0; i < c.num_layers; ++i) {
@@ -888,9 +888,9 @@ int dots_create(const DotsConfig* cfg, int device, DotsEngine** out) {
     e->cfg = c;
     e->device = device;
     // DOTS_OCR_CU_RANGE="lo-hi" (experiment, tools/overlap_probe.py): the engine's stream only uses CU-mask bits lo..hi (of 256; bit i = CU i / 8 of XCD i % 8)
-    if (const char* cr = getenv("DOTS_OCR_CU_RANGE")) {
+    if (const char* cr = sw::read_now(sw::CU_RANGE)) {
         int lo = 0, hi = 255;
-        if (sscanf(cr, "%d-%d", &lo, &hi) != 2 || lo < 0 || hi > 255 || lo > hi) { g_create_error = "bad DOTS_OCR_CU_RANGE"; delete e; return DOTS_E_INVALID; }
+        if (!sw::parse_cu_range(cr, &lo, &hi)) { g_create_error = std::string("bad ") + sw::CU_RANGE; delete e; return DOTS_E_INVALID; }
         uint32_t words[8] = {0};
         for (int b = lo; b <= hi; ++b) words[b / 32] |= 1u << (b % 32);
         if (hipExtStreamCreateWithCUMask(&e->stream, 8, words) != hipSuccess) { g_create_error = "hipExtStreamCreateWithCUMask failed"; delete e; return DOTS_E_HIP; }
@@ -1044,7 +1044,7 @@ int dots_generate(DotsEngine* e, const int32_t* input_ids, const int32_t* prompt
     // ---- decode loop: one captured graph replayed max_new_tokens-1 times
     CK(hipEventRecord(e->ev[4], s));
     const int n_splits = splits_for_ctx(e->cfg.max_seq_len);       // engine constant: results do not depend on the batch
-    const bool use_graph = getenv("DOTS_OCR_NO_GRAPH") == nullptr;
+    const bool use_graph = !sw::on_if_set(sw::read_now(sw::NO_GRAPH));           // read per call here, once per process in dots_step_chunk
     hipGraphExec_t exec = nullptr;
     hipGraphExec_t exec_part = nullptr;            // the step captured with the half-chip launch plan, for the masked stream
     if (use_graph && max_new_tokens > 1) {

@@ -24,6 +24,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace {
 
@@ -1146,69 +1147,32 @@ static int raster_group_m(int row_bytes) {
 }
 
 // launch plan of the 256-wide bf16 GEMM (process-wide; results are bit-identical under either plan: the same MFMAs in the same k order
-// per output element): 0 = 8 waves, ping-pong halves (round 2), 1 = 4 waves, one per SIMD, K tiles of 64 through a 5-unit ring (round 5)
+// per output element): 0 = 8 waves, ping-pong halves (round 2), 1 = 4 waves, one per SIMD, K tiles of 64 through a 5-unit ring (round 5:
+// the default, +6-11 % on the A4 shapes, profiles/r05_gemm_*.txt).  -1 = not set by dots_set_gemm_plan: the switch's value.
 static int g_gemm_plan = -1;
 int gemm_get_plan() {
-    int p = __atomic_load_n(&g_gemm_plan, __ATOMIC_RELAXED);
-    if (p < 0) {
-        const char* ev = getenv("DOTS_OCR_GEMM_PLAN");
-        p = ev ? (atoi(ev) != 0) : 1;      // round 5 default: one wave per SIMD (+6-11 % on the A4 shapes, profiles/r05_gemm_*.txt)
-        __atomic_store_n(&g_gemm_plan, p, __ATOMIC_RELAXED);
-    }
-    return p;
+    const int p = __atomic_load_n(&g_gemm_plan, __ATOMIC_RELAXED);
+    return p < 0 ? launch_switches().gemm_plan : p;
 }
 void gemm_set_plan(int plan) { __atomic_store_n(&g_gemm_plan, plan != 0, __ATOMIC_RELAXED); }
 
 template <int E>
 static hipError_t launch_256(hipStream_t s, const bf16_t* A, const bf16_t* W, const bf16_t* bias, const float* colscale, const bf16_t* R, void* C,
                                 int M, int N, int K, int lda, int ldc) {
-    // dynamic LDS > 64 KB is opted into once per (instantiation, DEVICE): engines on several GPUs may live in one process
-    static uint32_t configured = 0;
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    const uint32_t bit = 1u << (dev & 31);
-    if (!(__atomic_load_n(&configured, __ATOMIC_ACQUIRE) & bit)) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_256_kernel<E>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * STAGE2);
-        if (e != hipSuccess) return e;
-        __atomic_fetch_or(&configured, bit, __ATOMIC_RELEASE);
-    }
     const int m_tiles = (M + BM2 - 1) / BM2, n_tiles = N / BN2;
-    static const bool lockstep = getenv("DOTS_OCR_GEMM_LOCKSTEP") != nullptr;       // A/B switch: the one-barrier-per-K-tile schedule
-    if (lockstep || ldc % 8 != 0) {                 // the LDS-staged epilogue stores 16 bytes per lane
-        hipLaunchKernelGGL(gemm_bf16_256_kernel<E>, dim3(m_tiles * n_tiles), dim3(512), 2 * STAGE2, s, A, W, bias, colscale, R, C, M, N, K,
-                           lda, ldc, m_tiles, n_tiles);
-        return hipGetLastError();
-    }
-    if (gemm_get_plan() == 1 && K / BK >= 3) {                  // round 5: one wave per SIMD (dots_set_gemm_plan)
-        static uint32_t configured_w4 = 0;
-        if (!(__atomic_load_n(&configured_w4, __ATOMIC_ACQUIRE) & bit)) {
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_w4_kernel<E>), hipFuncAttributeMaxDynamicSharedMemorySize, W4_RING * W4_UNIT);
-            if (e != hipSuccess) return e;
-            __atomic_fetch_or(&configured_w4, bit, __ATOMIC_RELEASE);
-        }
-        hipLaunchKernelGGL(gemm_bf16_w4_kernel<E>, dim3(m_tiles * n_tiles), dim3(256), W4_RING * W4_UNIT, s, A, W, bias, colscale, R, C, M, N, K,
-                           lda, ldc, m_tiles, n_tiles, raster_group_m(K * 2));
-        return hipGetLastError();
-    }
-    static uint32_t configured_pp = 0;
-    if (!(__atomic_load_n(&configured_pp, __ATOMIC_ACQUIRE) & bit)) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_256pp_kernel<E>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                PP_STAGES * SUB_STAGE);
-        if (e != hipSuccess) return e;
-        __atomic_fetch_or(&configured_pp, bit, __ATOMIC_RELEASE);
-    }
-    hipLaunchKernelGGL(gemm_bf16_256pp_kernel<E>, dim3(m_tiles * n_tiles), dim3(512), PP_STAGES * SUB_STAGE, s, A, W, bias, colscale, R, C, M, N, K,
-                       lda, ldc, m_tiles, n_tiles, raster_group_m(K * 2));
-    return hipGetLastError();
+    const dim3 grid(m_tiles * n_tiles);
+    if (launch_switches().gemm_lockstep || ldc % 8 != 0)                 // the LDS-staged epilogue stores 16 bytes per lane
+        return launch_dyn_lds<gemm_bf16_256_kernel<E>>(grid, dim3(512), 2 * STAGE2, s, A, W, bias, colscale, R, C, M, N, K, lda, ldc, m_tiles, n_tiles);
+    if (gemm_get_plan() == 1 && K / BK >= 3)                    // round 5: one wave per SIMD (dots_set_gemm_plan)
+        return launch_dyn_lds<gemm_bf16_w4_kernel<E>>(grid, dim3(256), W4_RING * W4_UNIT, s, A, W, bias, colscale, R, C, M, N, K, lda, ldc, m_tiles, n_tiles, raster_group_m(K * 2));
+    return launch_dyn_lds<gemm_bf16_256pp_kernel<E>>(grid, dim3(512), PP_STAGES * SUB_STAGE, s, A, W, bias, colscale, R, C, M, N, K, lda, ldc, m_tiles, n_tiles, raster_group_m(K * 2));
 }
 
 hipError_t launch_gemm(hipStream_t s, const bf16_t* A, const bf16_t* W, const bf16_t* bias, const bf16_t* R,
                        void* C, int64_t M, int N, int K, int lda, int ldc, int epi, const float* colscale) {
     if (M <= 0) return hipSuccess;
     if (N % BN != 0 || K % BK != 0 || (lda % 8) != 0 || (ldc % 4) != 0) return hipErrorInvalidValue;
-    static const bool force_small = getenv("DOTS_OCR_GEMM_128") != nullptr;
-    if (N % BN2 == 0 && !force_small) {
+    if (N % BN2 == 0 && !launch_switches().gemm_128) {
         switch (epi) {
             case EPI_NONE: return launch_256<EPI_NONE>(s, A, W, bias, colscale, R, C, (int)M, N, K, lda, ldc);
             case EPI_RESIDUAL: return launch_256<EPI_RESIDUAL>(s, A, W, bias, colscale, R, C, (int)M, N, K, lda, ldc);
@@ -1237,27 +1201,15 @@ hipError_t launch_gemm(hipStream_t s, const bf16_t* A, const bf16_t* W, const bf
 
 hipError_t launch_gemm_qk_rope(hipStream_t s, const bf16_t* A, const bf16_t* W, const bf16_t* bias, bf16_t* qkv, int64_t M, int N, int K, int lda, int ldc,
                                const float2* cs, bf16_t* q, bf16_t* k, int Hq, int Hkv) {
-    static const bool off = getenv("DOTS_OCR_QK_FUSE") && atoi(getenv("DOTS_OCR_QK_FUSE")) == 0;       // A/B switch
-    static const bool lockstep = getenv("DOTS_OCR_GEMM_LOCKSTEP") != nullptr, force_small = getenv("DOTS_OCR_GEMM_128") != nullptr;
-    if (off || lockstep || force_small || gemm_get_plan() != 1 || N != (Hq + 2 * Hkv) * 128 || N % BN2 != 0 || K % BK != 0 || K / BK < 3 || lda % 8 != 0 || ldc % 8 != 0 ||
+    const LaunchSwitches& lsw = launch_switches();
+    if (!lsw.qk_fuse || lsw.gemm_lockstep || lsw.gemm_128 || gemm_get_plan() != 1 || N != (Hq + 2 * Hkv) * 128 || N % BN2 != 0 || K % BK != 0 || K / BK < 3 || lda % 8 != 0 || ldc % 8 != 0 ||
         !cs || !q || !k || M > 0x7fffffff)
         return hipErrorNotSupported;
     if (M <= 0) return hipSuccess;
-    static uint32_t configured = 0;
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    const uint32_t bit = 1u << (dev & 31);
-    if (!(__atomic_load_n(&configured, __ATOMIC_ACQUIRE) & bit)) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_w4_qkrope_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, W4_RING * W4_UNIT);
-        if (e != hipSuccess) return e;
-        __atomic_fetch_or(&configured, bit, __ATOMIC_RELEASE);
-    }
     const int m_tiles = (int)((M + BM2 - 1) / BM2), n_tiles = N / BN2;
     const QkRope rope{cs, q, k, (long long)M, Hq, Hq + Hkv};
-    hipLaunchKernelGGL(gemm_bf16_w4_qkrope_kernel, dim3(m_tiles * n_tiles), dim3(256), W4_RING * W4_UNIT, s, A, W, bias, (const float*)nullptr, (void*)qkv, (int)M, N, K,
-                       lda, ldc, m_tiles, n_tiles, raster_group_m(K * 2), rope);
-    return hipGetLastError();
+    return launch_dyn_lds<gemm_bf16_w4_qkrope_kernel>(dim3(m_tiles * n_tiles), dim3(256), W4_RING * W4_UNIT, s, A, W, bias, (const float*)nullptr, (void*)qkv, (int)M, N, K,
+                                                      lda, ldc, m_tiles, n_tiles, raster_group_m(K * 2), rope);
 }
 
 bool gemm_fp8_supports(int N, int K) { return N % BN2 == 0 && K % 64 == 0; }
@@ -1265,20 +1217,9 @@ bool gemm_fp8_supports(int N, int K) { return N % BN2 == 0 && K % 64 == 0; }
 template <int E>
 static hipError_t launch_fp8_t(hipStream_t s, const uint8_t* Aq, const float* rowscale, const uint8_t* Wq, const float* colscale, const bf16_t* bias,
                                const bf16_t* R, void* C, int M, int N, int K, int ldc) {
-    static uint32_t configured = 0;
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    const uint32_t bit = 1u << (dev & 31);
-    if (!(__atomic_load_n(&configured, __ATOMIC_ACQUIRE) & bit)) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_fp8_256pp_kernel<E>), hipFuncAttributeMaxDynamicSharedMemorySize, PP_STAGES * SUB_STAGE);
-        if (e != hipSuccess) return e;
-        __atomic_fetch_or(&configured, bit, __ATOMIC_RELEASE);
-    }
     const int m_tiles = (M + BM2 - 1) / BM2, n_tiles = N / BN2;
-    hipLaunchKernelGGL(gemm_fp8_256pp_kernel<E>, dim3(m_tiles * n_tiles), dim3(512), PP_STAGES * SUB_STAGE, s, Aq, rowscale, Wq, colscale, bias, R, C, M, N, K,
-                       ldc, m_tiles, n_tiles, raster_group_m(K));
-    return hipGetLastError();
+    return launch_dyn_lds<gemm_fp8_256pp_kernel<E>>(dim3(m_tiles * n_tiles), dim3(512), PP_STAGES * SUB_STAGE, s, Aq, rowscale, Wq, colscale, bias, R, C, M, N, K,
+                                                    ldc, m_tiles, n_tiles, raster_group_m(K));
 }
 
 hipError_t launch_gemm_fp8(hipStream_t s, const uint8_t* Aq, const float* rowscale, const uint8_t* Wq, const float* colscale, const bf16_t* bias,

@@ -659,7 +659,7 @@ int dots_slots_decode(DotsEngine* e, int n_steps) {
     n_steps /= e->spec_k + 1;
     const int n_splits = splits_for_ctx(e->cfg.max_seq_len);
     e->B = rows;
-    static const bool use_graph = getenv("DOTS_OCR_NO_GRAPH") == nullptr;
+    const bool use_graph = !launch_switches().no_graph;
     // beside a prefetched vision tower (the next admission's: dots_vit_prefetch) the chunk is replayed on the decode partition, with the
     // half-chip launch plan when the rows allow it — exactly as dots_generate does
     hipStream_t cur = s;

@@ -338,19 +338,16 @@ int alloc_workspaces(DotsEngine* e) {
     CK(e->alloc(&e->d_logits, (size_t)mb * c.vocab_size));
     CK(e->alloc(&e->d_part_o, (size_t)mb * c.num_heads * 64 * 128));
     CK(e->alloc(&e->d_part_ml, (size_t)mb * c.num_heads * 64 * 2));
-    if (const char* fm = getenv("DOTS_OCR_DECODE_PLAN")) {
-        // the same rule as dots_set_decode_plan: a bit field since round 5 (bit 0 partition plan, + 2 streaming / + 4 per-split attention) — it used to be
-        // "any non-zero = partition plan", so an old setting of 2 or 3 now means the (slower) streaming attention kernel: values outside 0..5 and 6 / 7
-        // (both attention bits) are refused instead of silently re-interpreted
-        const int plan = atoi(fm);
-        if (plan < 0 || plan > 5 || (plan & 6) == 6) {
-            fprintf(stderr, "dots.ocr: DOTS_OCR_DECODE_PLAN=%s ignored: must be 0 / 1 (partition plan on every step), + 2 (streaming attention) or + 4 (per-split attention)\n", fm);
+    if (const char* fm = sw::read_now(sw::DECODE_PLAN)) {          // per engine (refused, not re-interpreted)
+        const sw::DecodePlan plan = sw::parse_decode_plan(fm);
+        if (!plan.ok) {
+            fprintf(stderr, "dots.ocr: %s=%s ignored: must be 0 / 1 (partition plan on every step), + 2 (streaming attention) or + 4 (per-split attention)\n", sw::DECODE_PLAN, fm);
         } else {
-            e->force_part = plan & 1;
-            e->attn_stream = (plan & 2) ? 1 : (plan & 4) ? 0 : -1;
+            e->force_part = plan.force_part;
+            e->attn_stream = plan.attn_stream;
         }
     }
-    if (const char* v = getenv("DOTS_OCR_TOWER_TAIL_LAYERS")) e->tail_fixed = std::max(-1, std::min(atoi(v), c.v_layers));      // dots_tower_tail
+    if (const char* v = sw::read_now(sw::TOWER_TAIL_LAYERS)) e->tail_fixed = sw::parse_tower_tail_layers(v, c.v_layers);      // per engine; dots_tower_tail
     // every slot starts free: its block-table row points at the scratch page (an idle row of the fixed-shape decode graph
     // keeps appending K/V at position 0 of whatever page its row names; it must never be a page a live sequence owns)
     e->hp_table.assign((size_t)mb * e->max_pages, e->n_pool_pages);
