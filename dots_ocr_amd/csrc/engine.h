@@ -220,6 +220,11 @@ struct DotsEngine {
     // three bits up): rows with an n-gram rule, with logit rules, with a penalty in their parameters.  No state of its own: the draft rows
     // use rows [rows, rows * (k + 1)) of ngram_mask and pen_logits, which hold max_batch rows
     int spec_shaped = 0;
+    // may a row with logprobs on verify drafts (dots_set_speculation_logprobs; spec_row_class() asks it), and — allocated by the first call
+    // that switches it on — the accept record of a step (kernels.h SpecState::acc_n / acc_tok).  The draft rows' partials use rows
+    // [rows, rows * (k + 1)) of lp_ms / lp_pv / lp_pi, which hold max_batch rows
+    int spec_logprobs = 0;
+    int32_t *sp_acc_n = nullptr, *sp_acc_tok = nullptr;
     bool row_pen[DOTS_MAX_BATCH] = {false}, row_sampled[DOTS_MAX_BATCH] = {false};
     // of a staged row without ROW_PARAMS: the engine-wide setting its stage entry was written from had a temperature > 0.  Such a row is
     // drawn by the stage whatever dots_set_sampling says later, and its draft rows would be arg maxima: it verifies no draft
@@ -327,11 +332,12 @@ struct DotsEngine {
     // the ban kernel and its bits), the draft count of a speculating step (spec: 0 = the plain step), whether that step draws the draft
     // rows of sampled slots (draw: the two launches of launch_spec_draw), whether some guided row may speculate in it (gspec: the three
     // launches that select the draft rows of guided slots under their guide), which shaped rows may (sspec: the
-    // DOTS_SPEC_SHAPED_* bits that are switched on and held by some row — the draft rows' ban kernel and their shaped selection); engine-wide sampling changes drop
+    // DOTS_SPEC_SHAPED_* bits that are switched on and held by some row — the draft rows' ban kernel and their shaped selection), whether
+    // some row with logprobs may (lpspec: the draft rows' logprob pair and the accept record); engine-wide sampling changes drop
     // the cache (dots_set_sampling), per-row ones live in device memory; beam: the group entries a step's beam kernels run over (0: none).  step_key() builds the key from the engine's state: a feature that
     // changes what a step launches adds a member here and a line there
     struct StepKey {
-        int rows, splits, out_cap, n_eos, part, rowp, lp, rules, guided, ngram, spec, draw, gspec, sspec, beam;
+        int rows, splits, out_cap, n_eos, part, rowp, lp, rules, guided, ngram, spec, draw, gspec, sspec, lpspec, beam;
         bool operator==(const StepKey& o) const { return std::memcmp(this, &o, sizeof(StepKey)) == 0; }
     };
     static_assert(std::has_unique_object_representations_v<StepKey>, "StepKey is compared bytewise: plain ints, no padding");
@@ -457,6 +463,7 @@ void mark_live(DotsEngine* e, const LiveRow* rows, int n, bool occupy = true);
 StepState step_state(const DotsEngine* e, int advance, const int32_t* sel);
 bool spec_draws(const DotsEngine* e);
 bool spec_guides(const DotsEngine* e);
+bool spec_lps(const DotsEngine* e);
 int spec_shapes(const DotsEngine* e);
 RowSel spec_row_sel(const DotsEngine* e);
 GuideSel guide_sel(const DotsEngine* e);

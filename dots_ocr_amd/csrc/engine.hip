@@ -281,6 +281,7 @@ DotsEngine::StepKey step_key(const DotsEngine* e, int rows, int n_splits, int ou
     k.draw = spec_draws(e);
     k.gspec = spec_guides(e);
     k.sspec = spec_shapes(e);
+    k.lpspec = spec_lps(e);
     k.beam = e->slot_mode ? e->n_beam_hi : 0;
     return k;
 }
@@ -807,6 +808,15 @@ int decode_step_launches(DotsEngine* e, int n_splits, int part) {
             CK(launch_ngram_ban_drafts(s, spec_rs.ngram, rows, spec_k, e->out_ids, e->out_lens, c.max_seq_len, e->sp_drafts, e->sp_nlive));
         CK(launch_spec_shape_select(s, sp, spec_rs, step_state(e, 1, e->d_sel), e->d_logits, c.vocab_size, c.vocab_size, rows, e->am_val, e->am_idx));
     }
+    // Slots with logprobs on that speculate (dots_set_speculation_logprobs): the partials of their live draft rows, from the raw logits, into
+    // the rows of the logprob scratch the stage does not use.  With the switch off, or no row with logprobs on, nothing is launched here
+    const bool lpspec = spec_k && spec_lps(e);
+    const LogprobState spec_ls{e->d_row_lp, e->d_sel, e->finished, e->out_lens, e->cur_tokens, e->lp_ms, e->lp_pv, e->lp_pi, e->lp_pos,
+                               e->lp_tok, e->lp_ids, e->lp_top, c.max_seq_len};
+    if (lpspec) {
+        if (B > c.max_batch) return e->fail(DOTS_E_CAPACITY, "%d rows x %d exceed max_batch %d", rows, spec_k + 1, c.max_batch);      // lp_ms / lp_pv / lp_pi hold max_batch rows
+        CK(launch_spec_logprob_partial(s, e->d_logits, c.vocab_size, c.vocab_size, rows, spec_k, e->sp_nlive, spec_ls));
+    }
     // the candidates of the draft rows of sampled slots, before the selection stage moves out_lens: draft row j draws with counter out_lens + j
     if (spec_k && sp.cand)
         CK(launch_spec_draw(s, sp, e->d_logits, c.vocab_size, c.vocab_size, rows, spec_rs, e->out_lens, e->am_val, e->am_idx));
@@ -819,6 +829,8 @@ int decode_step_launches(DotsEngine* e, int n_splits, int part) {
         // the grown output
         const StepState st = step_state(e, 1, e->d_sel);
         CK(launch_spec_accept(s, sp, st, rows, c.vocab_size, e->am_val, e->am_idx, spec_rs));
+        // the entries of the candidates the walk committed, at the positions their commits appended at
+        if (lpspec) CK(launch_spec_logprob_final(s, e->d_logits, c.vocab_size, c.vocab_size, rows, spec_k, sp.acc_n, sp.acc_tok, spec_ls));
         if (e->spec_max_n > 0)
             CK(launch_ngram_draft(s, st.out_ids, st.out_lens, st.out_stride, st.finished, st.sel, sp.cls, sp.engine_greedy, rows, spec_k, e->spec_min_n,
                                   e->spec_max_n, e->sp_drafts, DOTS_MAX_SPEC_DRAFTS, e->sp_ndraft));

@@ -287,6 +287,9 @@ hipError_t launch_stop_fork_rows(hipStream_t s, RowStop* table, int src, const i
 // gstate [DOTS_MAX_BATCH]: while a guided row may speculate (dots_set_speculation_guided), the automaton state every live draft row of a
 // guided slot is selected under, indexed by step row r = j * rows + b (launch_spec_guide_chain); -1 = the row verifies nothing under a
 // guide: dead, idle, or its slot holds none.  nullptr: no step launch asks about guides.
+// acc_n [DOTS_MAX_BATCH], acc_tok [DOTS_MAX_BATCH][DOTS_MAX_SPEC_DRAFTS]: the accept record, while a row with logprobs may speculate
+// (dots_set_speculation_logprobs) — the number of candidates the accept walk of slot b committed in this step and their ids, for
+// launch_spec_logprob_final.  nullptr (both): the walk records nothing.
 #ifndef DOTS_MAX_SPEC_DRAFTS
 #define DOTS_MAX_SPEC_DRAFTS 15
 #endif
@@ -303,6 +306,7 @@ struct SpecState {
     int32_t* cand;
     int32_t* gstate;
     int32_t k, engine_greedy;
+    int32_t *acc_n, *acc_tok;
 };
 // the step's row arrays from the slots' state (st: the StepState of the selection stage; block_table [rows][max_pages]); an idle draft row
 // gets context 0 and a table row of scratch_page, like a released slot
@@ -396,6 +400,14 @@ struct LogprobState {
 // V <= LP_MAX_V, ld >= V; grid (LP_CHUNKS, B) / B
 hipError_t launch_logprob_partial(hipStream_t s, const float* logits, int V, int ld, int B, const LogprobState& st);
 hipError_t launch_logprob_final(hipStream_t s, const float* logits, int V, int ld, int B, const LogprobState& st);
+// The draft rows of a speculating step (dots_set_speculation_logprobs), around the selection stage's own pair:
+// partial: grid (LP_CHUNKS, rows * k), after the lm_head — the partials of every live draft row r = j * rows + b (j <= n_live[b]) of a slot
+//   with top_n[b] >= 0, over logits row r into row r of part_ms / part_v / part_i (which hold rows * (k + 1) rows); takes no snapshot.
+// final: grid (rows, k), after launch_spec_accept — for a < acc_n[b] the entry of candidate acc_tok[b][a] from draft row (a + 1) * rows + b,
+//   at position pos[b] + 1 + a (pos: the snapshot launch_logprob_partial took for row b in this step).
+hipError_t launch_spec_logprob_partial(hipStream_t s, const float* logits, int V, int ld, int rows, int k, const int32_t* n_live, const LogprobState& st);
+hipError_t launch_spec_logprob_final(hipStream_t s, const float* logits, int V, int ld, int rows, int k, const int32_t* acc_n, const int32_t* acc_tok,
+                                     const LogprobState& st);
 // table[row] = top_n, in stream order
 hipError_t launch_set_row_lp(hipStream_t s, int32_t* table, int row, int top_n);
 // ---- beam.hip: beam search over shared KV pages

@@ -6,11 +6,12 @@
 namespace engine {
 namespace {
 // The speculation class of a row (kernels.h SpecRow), from the host's record alone.  THE place that decides it: the stage
-// features and the penalty of the row's parameters through RowStage::speculates, and logprobs (not a stage feature).  The engine-wide
+// features and the penalty of the row's parameters through RowStage::speculates, and logprobs (not a stage feature: a row that has them
+// on speculates only under dots_set_speculation_logprobs).  The engine-wide
 // temperature is not a row's fact: the kernels get it as engine_greedy.
 int spec_row_class(const DotsEngine* e, int row) {
     const int mode = e->spec_rows | (e->spec_guided ? SPEC_ROWS_GUIDED : 0) | e->spec_shaped * SPEC_ROWS_NGRAM;      // DOTS_SPEC_SHAPED_* moved up by three bits
-    if (e->row_lp[row] >= 0 || !e->stage.speculates(row, e->row_pen[row], mode)) return SPEC_ROW_NONE;
+    if ((e->row_lp[row] >= 0 && !e->spec_logprobs) || !e->stage.speculates(row, e->row_pen[row], mode)) return SPEC_ROW_NONE;
     if (e->stage.staged(row) && !e->stage.has(row, ROW_PARAMS) && e->row_entry_sampled[row]) return SPEC_ROW_NONE;
     return e->stage.has(row, ROW_PARAMS) && e->row_sampled[row] ? SPEC_ROW_DRAW : SPEC_ROW_ARGMAX;
 }
@@ -175,6 +176,12 @@ bool spec_guides(const DotsEngine* e) {
     return e->slot_mode && e->spec_k > 0 && e->spec_guided && e->stage.rows(ROW_GUIDE) > 0;
 }
 
+// may some row with logprobs on verify drafts in a speculating step (the launches under StepKey::lpspec)?  A host count: the switch is on
+// and at least one row has logprobs on.  With dots_set_speculation_logprobs off a step launches what it always did
+bool spec_lps(const DotsEngine* e) {
+    return e->slot_mode && e->spec_k > 0 && e->spec_logprobs && e->n_lp > 0;
+}
+
 // Which shaped rows may verify drafts in a speculating step (StepKey::sspec; the DOTS_SPEC_SHAPED_* bits)?  Host counts: a bit is set while
 // dots_set_speculation_shaped has it and at least one row holds the feature — an n-gram rule, logit rules, parameters with a penalty.  0:
 // a step launches what it always did, and the draft-row kernels get no table of these features
@@ -203,7 +210,8 @@ RowSel spec_row_sel(const DotsEngine* e) {
 
 SpecState spec_state(const DotsEngine* e) {
     return SpecState{e->sp_drafts, e->sp_ndraft, e->sp_nlive, e->sp_tokens, e->sp_ctx, e->sp_table, e->sp_stats, e->sp_cls,
-                     spec_draws(e) ? e->sp_cand : nullptr, spec_guides(e) ? e->sp_gstate : nullptr, e->spec_k, e->temperature > 0.f ? 0 : 1};
+                     spec_draws(e) ? e->sp_cand : nullptr, spec_guides(e) ? e->sp_gstate : nullptr, e->spec_k, e->temperature > 0.f ? 0 : 1,
+                     spec_lps(e) ? e->sp_acc_n : nullptr, spec_lps(e) ? e->sp_acc_tok : nullptr};
 }
 
 // what a launch needs to honour the guides (the row table exists once a row has taken one)
@@ -693,6 +701,23 @@ int dots_set_speculation_shaped(DotsEngine* e, int flags) {
     e->spec_shaped = flags;
     drop_step_graphs(e);                                     // a captured step bakes in whether it shapes the draft rows of such slots
     return upload_spec_classes(e);                           // free slots may hold features: every row's class under the new setting
+}
+
+int dots_set_speculation_logprobs(DotsEngine* e, int on) {
+    if (!e) return DOTS_E_INVALID;
+    if (e->slot_mode)
+        for (int b = 0; b < e->cfg.max_batch; ++b)
+            if (e->slot_active[b]) return e->fail(DOTS_E_STATE, "logprob speculation cannot change while slot %d is occupied", b);
+    CK(hipSetDevice(e->device));
+    if (on && !e->sp_acc_tok) {
+        // each piece is allocated once: a call that failed half way is resumed by the next one
+        if (!e->sp_acc_n) CK(e->alloc(&e->sp_acc_n, (size_t)DOTS_MAX_BATCH));
+        CK(e->alloc(&e->sp_acc_tok, (size_t)DOTS_MAX_BATCH * DOTS_MAX_SPEC_DRAFTS));      // set last, it is the guard above
+    }
+    if ((on != 0) == (e->spec_logprobs != 0)) return DOTS_OK;
+    e->spec_logprobs = on != 0;
+    drop_step_graphs(e);                                     // a captured step bakes in whether it reduces the draft rows of logprob slots
+    return upload_spec_classes(e);                           // free slots may have logprobs on: every row's class under the new setting
 }
 
 int dots_set_row_drafts(DotsEngine* e, int row, const int32_t* ids_host, int n) {

@@ -19,6 +19,9 @@
 //   spec_shape_select_kernel   then, while a guided, ruled, n-gram or penalised row may speculate: the arg-max partials (and values, for a
 //                        sampled slot) of the live draft rows of such slots, shaped by the selection stage's own function (select_dev.h)
 //   spec_accept_kernel   after the selection stage: walks a slot's drafts and commits through commit_token while they hold
+//   (spec_logprob_partial_kernel, spec_logprob_final_kernel, logprobs.hip)   only while a row with logprobs may speculate
+//                        (dots_set_speculation_logprobs) and some row has them on: the partials of the live draft rows of such slots beside
+//                        spec_argmax_kernel, and after spec_accept_kernel the entries of the candidates it committed, from its accept record
 //   ngram_draft_kernel   end of the step: the next step's drafts from the row's own output (prompt lookup without the prompt)
 //
 // Draft row (b, j >= 1) is LIVE iff slot b is selected, not finished, a speculating row (sp.cls[b] != SPEC_ROW_NONE: the host's fact,
@@ -244,6 +247,7 @@ __global__ __launch_bounds__(256) void spec_shape_select_kernel(const float* __r
 // no row holds the feature) is one no speculating slot has an entry in.
 // The walk of a guided slot also ends at a draft row the chain marked dead: the draft there is not a token the guide could have
 // committed, so if it equals what was committed that was the all -inf fallback (id 0, the state did not move) and nothing past it is verified.
+// sp.acc_n / sp.acc_tok (both set or both null): the walk also leaves how many candidates it committed and their ids, per slot.
 __global__ __launch_bounds__(64) void spec_accept_kernel(SpecState sp, StepState st, int rows, int V, const float* __restrict__ pval,
                                                          const int32_t* __restrict__ pidx, RowSel rs) {
     __shared__ int32_t s_tok[DOTS_MAX_SPEC_DRAFTS];
@@ -267,13 +271,16 @@ __global__ __launch_bounds__(64) void spec_accept_kernel(SpecState sp, StepState
     __syncthreads();
     if (lane != 0) return;
     sp.n_draft[b] = 0;                                                // the drafts are spent, whatever became of them
+    if (sp.acc_n) sp.acc_n[b] = 0;
     if (nl < 0) return;
     int acc = 0;
     while (acc < nl && !st.finished[b] && sp.drafts[b * DOTS_MAX_SPEC_DRAFTS + acc] == st.cur_tokens[b]) {
         if (guided && sp.gstate[(acc + 1) * rows + b] < 0) break;
         commit_row(st, rs, b, V, pen, s_tok[acc]);
+        if (sp.acc_tok) sp.acc_tok[b * DOTS_MAX_SPEC_DRAFTS + acc] = s_tok[acc];
         ++acc;
     }
+    if (sp.acc_n) sp.acc_n[b] = acc;                                  // the accept record: what the walk committed (launch_spec_logprob_final)
     unsigned long long* mine = sp.stats + (size_t)b * 3;
     mine[0] += 1; mine[1] += (unsigned long long)nl; mine[2] += (unsigned long long)acc;
     unsigned long long* all = sp.stats + (size_t)DOTS_MAX_BATCH * 3;
@@ -412,6 +419,7 @@ hipError_t launch_spec_accept(hipStream_t s, const SpecState& sp, const StepStat
     if (!spec_ok(sp, rows) || !pval || !pidx || V < 1 || !spec_row_sel_ok(sp, rs, V)) return hipErrorInvalidValue;
     if (rs.stop.rows && (!rs.stop.tok_off || !rs.stop.tok_bytes)) return hipErrorInvalidValue;
     if (rs.guide.rows && (!sp.gstate || !rs.guide.tok_off || !rs.guide.tok_bytes)) return hipErrorInvalidValue;
+    if (!sp.acc_n != !sp.acc_tok) return hipErrorInvalidValue;
     hipLaunchKernelGGL(spec_accept_kernel, dim3(rows), dim3(64), 0, s, sp, st, rows, V, pval, pidx, rs);
     return hipGetLastError();
 }

@@ -410,6 +410,7 @@ def _prototypes(lib):
         "dots_set_speculation_rows": (i32, [vp, i32]),
         "dots_set_speculation_guided": (i32, [vp, i32]),
         "dots_set_speculation_shaped": (i32, [vp, i32]),
+        "dots_set_speculation_logprobs": (i32, [vp, i32]),
         "dots_op_spec_guide_masks": (i32, [vp, i32, i32, P(i32), P(i32), P(i32), P(i32), P(i32), P(C.c_uint32)]),
         "dots_set_row_drafts": (i32, [vp, i32, P(i32), i32]),
         "dots_spec_stats": (i32, [vp, i32, P(i64), P(i64), P(i64)]),
@@ -447,7 +448,7 @@ EXPORTED_SYMBOLS = [
     "dots_op_select_tokens_guided", "dots_bench_select_tokens_guided",
     "dots_set_row_ngram", "dots_op_select_tokens_ngram", "dots_bench_select_tokens_ngram",
     "dots_set_speculation", "dots_set_speculation_rows", "dots_set_row_drafts", "dots_spec_stats", "dots_op_ngram_draft",
-    "dots_set_speculation_guided", "dots_op_spec_guide_masks", "dots_set_speculation_shaped",
+    "dots_set_speculation_guided", "dots_op_spec_guide_masks", "dots_set_speculation_shaped", "dots_set_speculation_logprobs",
     "dots_slots_fork", "dots_slots_extend", "dots_slot_logits",
     "dots_slots_beam", "dots_beam_info", "dots_beam_read",
     "dots_stop_create", "dots_stop_destroy", "dots_set_row_stop", "dots_row_stop_hit",
@@ -1059,6 +1060,17 @@ class Engine:
         flags = (SPEC_SHAPED["ngram"] if ngram else 0) | (SPEC_SHAPED["rules"] if rules else 0) | (SPEC_SHAPED["penalties"] if penalties else 0)
         self._ck(self.lib.dots_set_speculation_shaped(self.h, flags), "dots_set_speculation_shaped")
         self.spec_shaped = flags
+
+    spec_logprobs = False                    # Engine.set_speculation_logprobs: off until switched on
+
+    def set_speculation_logprobs(self, on: bool = True):
+        """May a row that returns logprobs (set_row_logprobs) verify drafts?  Off by default.  A row's logprobs are a
+        function of its raw logits row alone and a draft row's logits are those of the sequential step at its position, so the entries of
+        the accepted tokens are bit for bit those of the unspeculated engine, at the same output positions; rejected drafts write
+        nothing.  Every other feature the row carries still needs its own switch.  Only while no slot is occupied; the setting survives
+        set_speculation."""
+        self._ck(self.lib.dots_set_speculation_logprobs(self.h, 1 if on else 0), "dots_set_speculation_logprobs")
+        self.spec_logprobs = bool(on)
 
     def spec_guide_masks_op(self, guides: Sequence[Optional[int]], states: Sequence[int], drafts: Sequence[Sequence[int]], n_live: Sequence[int], k: int):
         """The state chain and the draft-row mask kernels alone (dots_op_spec_guide_masks) for `rows` slots: guide handle (None = an

@@ -137,7 +137,7 @@ class DotsOcrHipForCausalLM:
                  no_repeat_ngram_whitelist=None, speculative_ngram: Optional[int] = None, prompt_lookup_min: int = 2, prompt_lookup_max: int = 4,
                  num_return_sequences: int = 1, stop_strings=None, speculative_rows=None, num_beams: Optional[int] = None,
                  length_penalty: float = 1.0, early_stopping=None, speculative_guided: bool = False, prompt_suffixes=None, speculative_shaped=None,
-                 prefill_chunk: Optional[int] = None, enable_prefix_caching: bool = False, image_keys=None, **_):
+                 prefill_chunk: Optional[int] = None, enable_prefix_caching: bool = False, image_keys=None, speculative_logprobs: bool = False, **_):
         """HF-shaped generate.  do_sample / temperature / top_p default to the checkpoint's generation_config.json (greedy when it
         is absent); with sampling on, tokens are drawn on the GPU from softmax(logits / temperature) restricted to the top_p
         nucleus, reproducibly from `seed`.  Returns LongTensor
@@ -181,6 +181,11 @@ class DotsOcrHipForCausalLM:
         (Engine.set_speculation_guided): every draft row is selected under the state its guide would hold there, so the tokens are
         again exactly those of the call without it.  A sampled guided call also needs speculative_rows "sampled", one with
         stop_strings "stop".  The engine is left with the setting off.
+
+        speculative_logprobs (with speculative_ngram; False = a sequence that returns logprobs runs unspeculated) lets such a sequence
+        verify drafts too (Engine.set_speculation_logprobs): the logprobs of every accepted token are reduced from its draft row's raw
+        logits and land at the token's own position, bit for bit the values of the call without it.  The engine is left with the
+        setting off.
 
         speculative_shaped (with speculative_ngram; None = the above) lets sequences whose logits are shaped verify drafts
         (Engine.set_speculation_shaped): "ngram" (no_repeat_ngram_size), "rules" (logit_bias, allowed_token_ids, min_tokens,
@@ -356,6 +361,8 @@ class DotsOcrHipForCausalLM:
             raise ValueError("speculative_rows needs speculative_ngram")
         if speculative_guided and not spec_k:
             raise ValueError("speculative_guided needs speculative_ngram")
+        if speculative_logprobs and not spec_k:
+            raise ValueError("speculative_logprobs needs speculative_ngram")
         from .engine import SPEC_SHAPED, spec_shaped_flags
         spec_shaped = spec_shaped_flags(speculative_shaped)
         if spec_shaped and not spec_k:
@@ -379,6 +386,8 @@ class DotsOcrHipForCausalLM:
                 self.engine.set_speculation_rows(sampled=bool(spec_rows & SPEC_ROWS["sampled"]), stop=bool(spec_rows & SPEC_ROWS["stop"]))
             if speculative_guided:
                 self.engine.set_speculation_guided(True)
+            if speculative_logprobs:
+                self.engine.set_speculation_logprobs(True)
             if spec_shaped:
                 self.engine.set_speculation_shaped(ngram=bool(spec_shaped & SPEC_SHAPED["ngram"]), rules=bool(spec_shaped & SPEC_SHAPED["rules"]),
                                                    penalties=bool(spec_shaped & SPEC_SHAPED["penalties"]))
@@ -395,6 +404,8 @@ class DotsOcrHipForCausalLM:
                         self.engine.set_speculation_rows()
                     if speculative_guided:
                         self.engine.set_speculation_guided(False)
+                    if speculative_logprobs:
+                        self.engine.set_speculation_logprobs(False)
                     if spec_shaped:
                         self.engine.set_speculation_shaped()
                 except Exception as e:               # the run's own error is the one to raise

@@ -36,7 +36,7 @@ class DotsOCRParser:
                  hf_max_new_tokens=24000, guided=False, no_repeat_ngram_size=None, no_repeat_ngram_window=None,
                  no_repeat_ngram_whitelist=None, speculative_ngram=None, prompt_lookup_min=2, prompt_lookup_max=4, stop=None,
                  speculative_rows=None, num_beams=None, length_penalty=1.0, speculative_guided=False, speculative_shaped=None,
-                 prefill_chunk=None, enable_prefix_caching=False):
+                 prefill_chunk=None, enable_prefix_caching=False, speculative_logprobs=False):
         self.dpi = dpi
         # prefix caching, opt-in over prefill_chunk: the in-process model keeps the full KV pages of the pages it has read and
         # starts a page it meets again — with another prompt, or in a retry — behind them, keyed on the decoded image's bytes and size.  A
@@ -78,6 +78,11 @@ class DotsOCRParser:
         if speculative_guided and not self.speculative_ngram:
             raise ValueError("speculative_guided needs speculative_ngram")
         self.speculative_guided = bool(speculative_guided)
+        # may sequences that return logprobs verify drafts (generate(speculative_logprobs=), Engine.set_speculation_logprobs).  A server
+        # decides by its own --speculative-logprobs flag.
+        if speculative_logprobs and not self.speculative_ngram:
+            raise ValueError("speculative_logprobs needs speculative_ngram")
+        self.speculative_logprobs = bool(speculative_logprobs)
         # which sequences whose logits are shaped verify drafts (generate(speculative_shaped=): "ngram", "rules", "penalties", a comma list,
         # a tuple, "all"; Engine.set_speculation_shaped); None = none.  A server decides by its own --speculative-shaped flag.
         from .engine import spec_shaped_flags
@@ -148,6 +153,8 @@ class DotsOCRParser:
                 kw["speculative_rows"] = self.speculative_rows
             if self.speculative_guided:
                 kw["speculative_guided"] = True
+            if self.speculative_logprobs:
+                kw["speculative_logprobs"] = True
             if self.speculative_shaped is not None:
                 kw["speculative_shaped"] = self.speculative_shaped
         if self._guided_layout(prompts):

@@ -363,7 +363,14 @@ int dots_row_stop_hit(DotsEngine* e, int row, int32_t* out);
  * that shapes the selection is known at the head of the step: the history the n-gram rule reads is the output followed by those drafts,
  * the output counts are the row's counts plus their occurrences, the output index min_tokens is compared with is tokens generated + j.
  * The counts change only when a token is committed, so a rejected draft leaves nothing behind, and the tokens are again EXACTLY those of
- * the unspeculated engine.  Rows with logprobs, and every row under an engine-wide temperature, never speculate.
+ * the unspeculated engine.  Under an engine-wide temperature no row speculates.
+ *
+ * dots_set_speculation_logprobs lets a row that returns logprobs (dots_set_row_logprobs) speculate.  A row's log-probabilities are a
+ * function of its raw logits row alone, and the logits of draft row j are those of the sequential step at that position: the stage
+ * reduces the live draft rows of such slots beside row 0, and after the accept walk the entries of the ACCEPTED candidates are written
+ * at the output positions their commits appended at.  tok_lp, top_ids and top_lp of every position are EXACTLY, bit for bit, those of
+ * the unspeculated engine; rejected and idle draft rows write nothing.  A row speculates iff every other feature it carries is let
+ * through by the switches above.
  *
  * The built-in drafter looks the row's last tokens up in the row's OWN output (the prompt is not searched: image pads and a short
  * instruction).  With out[0 .. L) the tokens generated so far, for n from max_n down to min_n with n + 1 <= L: key = out[L - n .. L);
@@ -386,6 +393,11 @@ int dots_row_stop_hit(DotsEngine* e, int row, int32_t* out);
  *                       never verify a draft, and a step launches exactly what it launched before.  A call of its own, not bits of
  *                       dots_set_speculation_rows.  The setting survives dots_set_speculation calls.  Allowed only while no slot is
  *                       occupied (DOTS_E_STATE); unknown bits: DOTS_E_INVALID; a change drops the captured steps.  Allocates nothing.
+ * dots_set_speculation_logprobs  on != 0: rows with logprobs on may verify drafts; 0 (the default): they never do, and a step launches
+ *                       exactly what it launched before (as it does with the switch on while no row has logprobs on).  A call of its
+ *                       own.  The setting survives dots_set_speculation calls.  Allowed only while no slot is occupied (DOTS_E_STATE); a
+ *                       change drops the captured steps.  The first call that switches it on allocates the accept record (16 int32 per
+ *                       step row).
  * dots_set_row_drafts   the n <= k drafts slot `row` verifies in its NEXT step, replacing what the drafter left (stream ordered; they are
  *                       spent by that step).  DOTS_E_INVALID: n > k or an id outside [0, vocab); DOTS_E_STATE: the slot is not occupied.
  *                       A row that does not speculate ignores them.
@@ -401,6 +413,7 @@ int dots_set_speculation(DotsEngine* e, int k, int min_n, int max_n);
 int dots_set_speculation_rows(DotsEngine* e, int flags);
 int dots_set_speculation_guided(DotsEngine* e, int on);
 int dots_set_speculation_shaped(DotsEngine* e, int flags);
+int dots_set_speculation_logprobs(DotsEngine* e, int on);
 int dots_set_row_drafts(DotsEngine* e, int row, const int32_t* ids_host, int n);
 int dots_spec_stats(DotsEngine* e, int row, int64_t* steps, int64_t* drafted, int64_t* accepted);
 

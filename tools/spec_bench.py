@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """What a speculating decode step costs and what it has to accept to pay (profiles/spec_ngram.txt).
 
-    python tools/spec_bench.py [--slots 1 8] [--k 0 1 3 7] [--steps 64] [--repeats 3] [--prompt 512] [--sampled | --guided | --shaped]
+    python tools/spec_bench.py [--slots 1 8] [--k 0 1 3 7] [--steps 64] [--repeats 3] [--prompt 512] [--sampled | --guided | --shaped | --logprobs N ..]
 
 Full-size language model with seeded random weights (the vision tower, which no text-only prompt touches, is cut to one block so that the
 weights are made quickly), one engine of 64 rows.  Per slot count: the reference tokens come from an unspeculated run; then for every
@@ -37,6 +37,11 @@ legs twice on one build: shaped_off (Engine.set_speculation_shaped(): the rows v
 three bits, with set_speculation_rows(sampled=True) for the parameters).  A live draft row then pays the draft rows' ban kernel and the
 shaped selection.  break_even of a shaped_on row = its cost / the k = 0 cost of shaped_off - 1.
 
+--logprobs N [N ..] (profiles/spec_logprobs.txt; the record there ran --logprobs 0 5 20) switches every row's logprobs on with top_n = N
+and runs the legs twice per N on one build: lpN_off (Engine.set_speculation_logprobs(False): the rows verify nothing, their draft rows
+idle) and lpN_on.  A live draft row then pays the draft rows' partial pass whether or not it is accepted, an accepted one its entry.
+break_even of an lpN_on row = its cost / the k = 0 cost of lpN_off - 1.
+
 One JSON line per measurement on stdout, then a table.
 """
 import argparse
@@ -62,6 +67,8 @@ def main():
     ap.add_argument("--sampled", action="store_true", help="also run sampled speculating rows (2-read and 4-read parameter sets) beside the greedy leg")
     ap.add_argument("--guided", action="store_true", help="every row holds the layout guide: the legs with Engine.set_speculation_guided off and on")
     ap.add_argument("--shaped", action="store_true", help="every row carries an n-gram rule, logit rules and penalties: the legs with Engine.set_speculation_shaped off and on")
+    ap.add_argument("--logprobs", type=int, nargs="+", default=None, metavar="N",
+                    help="every row returns logprobs with top_n = N (0 .. 20): per N the legs with Engine.set_speculation_logprobs off and on")
     ap.add_argument("--tiny", action="store_true", help="the small-dims model instead of the full-size one (a plumbing check, not a measurement)")
     a = ap.parse_args()
     from dots_ocr_amd.config import DotsConfig
@@ -100,6 +107,16 @@ def main():
         if a.sampled or a.guided:
             raise SystemExit("--shaped, --guided and --sampled are separate measurements")
         legs = [("shaped_off", None), ("shaped_on", None)]
+    lp_of = {}                                                       # leg -> top_n (--logprobs)
+    if a.logprobs is not None:
+        if a.sampled or a.guided or a.shaped:
+            raise SystemExit("--logprobs, --shaped, --guided and --sampled are separate measurements")
+        if any(not 0 <= n <= 20 for n in a.logprobs):
+            raise SystemExit("--logprobs takes top_n values in [0, 20]")
+        legs = []
+        for n in a.logprobs:
+            legs += [(f"lp{n}_off", None), (f"lp{n}_on", None)]
+            lp_of[f"lp{n}_off"] = lp_of[f"lp{n}_on"] = n
     alive = [0, 0]                                                   # planted drafts the guide could have committed / all planted (--guided)
 
     def guided_drafts(Tb, pos, k, true_drafts):
@@ -144,6 +161,9 @@ def main():
                       eng.set_row_sampling(b, SamplingParams(temperature=0.0, repetition_penalty=1.05, frequency_penalty=0.1, presence_penalty=0.1))
                       eng.set_row_logit_rules(b, LogitRules(bias={1000 + 7 * i + b: 0.5 for i in range(16)}, min_tokens=n_tok + 1, vocab_size=cfg.vocab_size))
                       eng.set_row_ngram(b, NgramRule(6, 256))
+              if leg in lp_of:
+                  for b in slots:
+                      eng.set_row_logprobs(b, lp_of[leg])
 
           def run(k, true_drafts, T=None):
               """`steps` steps with k drafts per slot of which the first true_drafts are right: (seconds, tokens committed, token lists)"""
@@ -155,6 +175,8 @@ def main():
               if a.shaped:
                   on = leg == "shaped_on"
                   eng.set_speculation_shaped(ngram=on, rules=on, penalties=on)
+              if leg in lp_of:
+                  eng.set_speculation_logprobs(leg.endswith("_on"))
               set_rows()
               eng.slots_prefill(slots, np.concatenate(prompts[:S]), [a.prompt] * S, [n_tok] * S)
               eng.slots_decode(1)                                       # the captured step exists before the clock starts
@@ -162,7 +184,7 @@ def main():
               _, lens = eng.slots_poll()
               start = [int(lens[b]) for b in slots]
               pos = list(start)
-              verifies = leg != "shaped_off"                            # shaped_off rows verify nothing
+              verifies = leg != "shaped_off" and not (leg in lp_of and leg.endswith("_off"))      # shaped_off and lpN_off rows verify nothing
               gain = [[1 + (min(true_drafts, k) if k and verifies else 0)] * S for _ in range(a.steps)]      # tokens a step commits per slot
               plan = None
               if a.guided and k:                                         # the automaton walks stay outside the clock
@@ -224,7 +246,7 @@ def main():
     print()
     print(f"{'leg':>14} {'slots':>5} {'k':>2} {'rows':>4} {'accept':>6} {'ms/step':>9} {'tok/step/slot':>13} {'tokens/s':>10} {'break-even accepted/step':>25}")
     for (leg, S, k, name), r in results.items():
-        base = results.get(("guided_off" if a.guided else "shaped_off" if a.shaped else leg, S, 0, "-"))
+        base = results.get(("guided_off" if a.guided else "shaped_off" if a.shaped else f"lp{lp_of[leg]}_off" if leg in lp_of else leg, S, 0, "-"))
         be = ""
         if k and name == "0" and base:
             be = f"{r['ms_per_step'] / base['ms_per_step'] - 1:.3f}"
