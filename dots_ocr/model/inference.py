@@ -41,3 +41,24 @@ def inference_prompts_with_vllm(image, prompts, protocol="http", ip="localhost",
     except requests.exceptions.RequestException as e:
         print(f"request error: {e}")
         return None
+
+
+def score_with_vllm(image, prompt, candidates, protocol="http", ip="localhost", port=8000, model_name="rednote-hilab/dots.mocr", system_prompt=None,
+                    top_logprobs=0, score_eos=True):
+    """Score given answers to ONE page in one request: the dots_ocr_amd server's own `score_candidates` field.  Nothing is
+    generated; choice i carries candidates[i], its per-token logprobs and their sum.  Returns the choices as dicts in that order, or None on
+    a request error.  No sampling field is sent: the server refuses them beside this one."""
+    import requests
+    from openai import OpenAI        # optional dependency, imported lazily
+    client = OpenAI(api_key=os.environ.get("API_KEY", "0"), base_url=f"{protocol}://{ip}:{port}/v1")
+    messages = [{"role": "system", "content": system_prompt}] if system_prompt else []
+    messages.append({"role": "user", "content": [
+        {"type": "image_url", "image_url": {"url": PILimage_to_base64(image)}},
+        {"type": "text", "text": f"<|img|><|imgpad|><|endofimg|>{prompt}"}]})
+    try:
+        r = client.chat.completions.create(messages=messages, model=model_name,
+                                           extra_body={"score_candidates": list(candidates), "top_logprobs": int(top_logprobs), "score_eos": bool(score_eos)})
+        return [c.model_dump() for c in sorted(r.choices, key=lambda c: c.index)]
+    except requests.exceptions.RequestException as e:
+        print(f"request error: {e}")
+        return None

@@ -294,6 +294,13 @@ struct DotsEngine {
     int32_t *ex_tokens = nullptr, *ex_ctx = nullptr, *ex_table = nullptr, *ex_stage = nullptr;
     size_t ex_stage_cap = 0;
     bf16_t* ex_h = nullptr;
+    // scoring given tokens (dots_slots_score), allocated by the first scoring call: the logits of a chunk's rows
+    // ([max_batch][vocab] fp32 — not d_logits, whose rows are the slots'), the logprob stage's scratch over them and the entries' values
+    // ([max_batch][max_seq_len], rows are slots); the top lists ([..][DOTS_MAX_TOP_LOGPROBS]) by the first call that asks for one.
+    // sc_n[slot]: 1 + the entries the slot's last score recorded, 0 = not scored since it was filled or extended
+    float *sc_logits = nullptr, *sc_ms = nullptr, *sc_pv = nullptr, *sc_tok = nullptr, *sc_top = nullptr;
+    int32_t *sc_pi = nullptr, *sc_ids = nullptr;
+    int sc_n[DOTS_MAX_BATCH] = {0};
     // chunked prefill (dots_slots_prefill_begin / dots_slots_prefill_advance).  fill[slot]: the record of a FILLING slot — not
     // occupied yet (slot_active == 0), so every step treats its row as a free one: context 0, and the DEVICE block-table row stays on the
     // scratch page until the fill completes, while hp_table and fill_table (the table the passes read) name its pages.  src: the prompt as

@@ -410,6 +410,17 @@ hipError_t launch_spec_logprob_final(hipStream_t s, const float* logits, int V, 
                                      const LogprobState& st);
 // table[row] = top_n, in stream order
 hipError_t launch_set_row_lp(hipStream_t s, int32_t* table, int row, int top_n);
+// ---- score.hip: the logprob stage over the fed rows of a scoring extend (dots_slots_score)
+// ScoreRows: per packed row of the call (score_plan.h) — its slot, the entry of that slot it records (-1: none), the token whose value
+// the entry takes and the slot's top_n (0..DOTS_MAX_TOP_LOGPROBS).  The launches serve the chunk of `rows` packed rows from r0 on: logits
+// row r and scratch row r of st (part_ms / part_v / part_i) are packed row r0 + r; the entry goes to tok_lp[slot * stride + entry] and
+// top_ids / top_lp likewise (both nullptr: only tok_lp is written, every top_n then being 0).  Of st only those seven fields and stride
+// are read.  partial: grid (LP_CHUNKS, rows); final: grid rows, one wave.
+struct ScoreRows {
+    const int32_t *slot, *entry, *target, *top_n;
+};
+hipError_t launch_score_logprob_partial(hipStream_t s, const float* logits, int V, int ld, const ScoreRows& sr, int r0, int rows, const LogprobState& st);
+hipError_t launch_score_logprob_final(hipStream_t s, const float* logits, int V, int ld, const ScoreRows& sr, int r0, int rows, const LogprobState& st);
 // ---- beam.hip: beam search over shared KV pages
 // A group of B beams lives in B slots, in group order (beam i = slots[i]).  BeamGroupDev is its device record (B == 0: the entry is free):
 // first = floor(L / 64), the first block-table entry the beams do not share with the prompt; cum the beams' cumulative log-probabilities

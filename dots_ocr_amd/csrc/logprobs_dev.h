@@ -161,8 +161,10 @@ DEVI void lp_final_next(const LpFinalLds& l, int c, int n, int& h, float& gv, in
 
 // One output entry, by the one wave of a final kernel (lane c): the partials of scratch row r — which is also the row of `logits` the
 // values came from — reduced to lse and the sorted top-n, written with the value of the committed token `tok` at output entry o (an index
-// into tok_lp; entries >= n of the top lists become -1 / NaN).  Holds lp_final_load's barriers: every lane calls it.
-DEVI void lp_final_entry(LpFinalLds& l, const float* __restrict__ logits, int V, int ld, const LogprobState& st, int r, int c, int n, size_t o, int tok) {
+// into tok_lp; entries >= n of the top lists become -1 / NaN).  Holds lp_final_load's barriers: every lane calls it.  tops = false (with
+// n == 0): st has no top lists and only tok_lp is written (score.hip, before any call asked for a top list).
+DEVI void lp_final_entry(LpFinalLds& l, const float* __restrict__ logits, int V, int ld, const LogprobState& st, int r, int c, int n, size_t o, int tok,
+                         bool tops = true) {
     const float lse = lp_final_load(l, st.part_ms, st.part_v, st.part_i, r, c, n);
     int h = 0;
     for (int q = 0; q < n; ++q) {
@@ -174,7 +176,7 @@ DEVI void lp_final_entry(LpFinalLds& l, const float* __restrict__ logits, int V,
             st.top_lp[o * DOTS_MAX_TOP_LOGPROBS + q] = gi == LP_NONE ? __builtin_nanf("") : gv - lse;
         }
     }
-    if (c >= n && c < DOTS_MAX_TOP_LOGPROBS) {
+    if (tops && c >= n && c < DOTS_MAX_TOP_LOGPROBS) {
         st.top_ids[o * DOTS_MAX_TOP_LOGPROBS + c] = -1;
         st.top_lp[o * DOTS_MAX_TOP_LOGPROBS + c] = __builtin_nanf("");
     }

@@ -1,6 +1,7 @@
 // Sequence slots of the dots.ocr engine: the host side of the paged KV pool, the steps of admitting a slot and the continuous-batching
 // C ABI (prefill into free slots, fork, decode chunks, poll / read / release).
 #include "engine.h"
+#include "score_plan.h"
 
 namespace engine {
 // ---- KV page allocator (host side; the kernels only ever see the block table)
@@ -224,6 +225,7 @@ void mark_live(DotsEngine* e, const LiveRow* rows, int n, bool occupy) {
         e->slot_prompt[b] = rows[i].ctx;
         e->slot_ctx_ub[b] = rows[i].ctx;
         e->slot_done[b] = 0;
+        e->sc_n[b] = 0;                                     // whatever a score recorded belongs to the sequence before
     }
     e->sel_dirty = true;
 }
@@ -411,15 +413,17 @@ int dots_slots_fork(DotsEngine* e, int src_slot, const int32_t* dst_slots, int n
 // More prompt tokens behind live sequences.  Everything is validated and counted before anything changes; the packed rows
 // then run through the layer loop of a decode step in chunks of at most max_batch rows, and the slots end as slots prefilled with the
 // longer prompt, their first token selected from the logits of their last fed row.
-int dots_slots_extend(DotsEngine* e, const int32_t* slots, int n, const int32_t* ids, const int32_t* lens, const int32_t* keep_pending,
-                      const int32_t* max_new_tokens) {
-    if (!e) return DOTS_E_INVALID;
-    if (!e->finalized) return e->fail(DOTS_E_STATE, "weights not finalized");
-    if (!slots || !ids || !lens || !keep_pending || !max_new_tokens) return e->fail(DOTS_E_INVALID, "null argument");
+//
+// top_n != nullptr: the call scores (dots_slots_score).  The same checks, page arithmetic and launches, and per chunk an
+// lm_head over all its rows into the scoring logits scratch and the logprob stage of score.hip over the rows that record an entry
+// (score_plan.h).  An extend (top_n == nullptr) launches and allocates nothing of that.
+namespace {
+int extend_slots(DotsEngine* e, const char* call, const int32_t* slots, int n, const int32_t* ids, const int32_t* lens, const int32_t* keep_pending,
+                 const int32_t* max_new_tokens, const int32_t* top_n) {
     const DotsConfig& c = e->cfg;
     const int mb = c.max_batch, V = c.vocab_size, H = c.hidden_size;
-    if (n < 1 || n > mb) return e->fail(DOTS_E_INVALID, "dots_slots_extend: n must be in [1, %d]", mb);
-    if (!e->slot_mode) return e->fail(DOTS_E_STATE, "dots_slots_extend: the engine runs a static batch; only a slot sequence can be extended");
+    if (n < 1 || n > mb) return e->fail(DOTS_E_INVALID, "%s: n must be in [1, %d]", call, mb);
+    if (!e->slot_mode) return e->fail(DOTS_E_STATE, "%s: the engine runs a static batch; only a slot sequence can be extended", call);
     if (e->spec_k) return e->fail(DOTS_E_STATE, "a slot cannot be extended while the engine speculates (dots_set_speculation)");
     int64_t n_ids = 0;
     for (int i = 0; i < n; ++i) {
@@ -432,6 +436,8 @@ int dots_slots_extend(DotsEngine* e, const int32_t* slots, int n, const int32_t*
             if (slots[a] == b) return e->fail(DOTS_E_INVALID, "slot %d listed twice", b);
         if (lens[i] < 1) return e->fail(DOTS_E_INVALID, "slot %d: at least one token must be fed, got %d", b, lens[i]);
         if (max_new_tokens[i] < 1) return e->fail(DOTS_E_INVALID, "slot %d: max_new_tokens must be >= 1, got %d", b, max_new_tokens[i]);
+        if (top_n && (top_n[i] < 0 || top_n[i] > DOTS_MAX_TOP_LOGPROBS))
+            return e->fail(DOTS_E_INVALID, "slot %d: top_n must be in [0, %d], got %d", b, DOTS_MAX_TOP_LOGPROBS, top_n[i]);
         if (e->stage.has(b, ROW_PARAMS) && e->row_pen[b])
             return e->fail(DOTS_E_STATE, "slot %d carries a penalty: its prompt-presence image would have to absorb the earlier output, so it cannot be extended", b);
         for (int j = 0; j < lens[i]; ++j) {
@@ -441,6 +447,7 @@ int dots_slots_extend(DotsEngine* e, const int32_t* slots, int n, const int32_t*
         }
         n_ids += lens[i];
     }
+    if (top_n && V > LP_MAX_V) return e->fail(DOTS_E_INVALID, "logprobs support vocabularies up to %d", LP_MAX_V);
     CK(hipSetDevice(e->device));
     hipStream_t s = e->stream;
     // ---- the true contexts (slot_ctx_ub is only a bound once a row has finished early), then the page arithmetic, before anything changes
@@ -477,7 +484,28 @@ int dots_slots_extend(DotsEngine* e, const int32_t* slots, int n, const int32_t*
     if (!e->ex_ctx) CK(e->alloc(&e->ex_ctx, DOTS_MAX_BATCH));
     if (!e->ex_table) CK(e->alloc(&e->ex_table, (size_t)DOTS_MAX_BATCH * e->max_pages));
     if (!e->ex_h) CK(e->alloc(&e->ex_h, (size_t)DOTS_MAX_BATCH * H));
-    const size_t n_stage = 3 * (size_t)n_rows + 5 * (size_t)n;
+    const size_t n_stage = (top_n ? 6 : 3) * (size_t)n_rows + 5 * (size_t)n;
+    bool any_top = false;
+    for (int i = 0; top_n && i < n; ++i) any_top |= top_n[i] > 0;
+    if (top_n) {
+        const size_t K = DOTS_MAX_TOP_LOGPROBS, pos = (size_t)mb * c.max_seq_len;
+        if (!e->sc_logits) CK(e->alloc(&e->sc_logits, (size_t)mb * V));
+        if (!e->sc_ms) CK(e->alloc(&e->sc_ms, (size_t)mb * LP_CHUNKS * 2));
+        if (!e->sc_pv) CK(e->alloc(&e->sc_pv, (size_t)mb * LP_CHUNKS * K));
+        if (!e->sc_pi) CK(e->alloc(&e->sc_pi, (size_t)mb * LP_CHUNKS * K));
+        if (!e->sc_tok) {
+            CK(e->alloc(&e->sc_tok, pos));
+            CK(hipMemsetAsync(e->sc_tok, 0xFF, pos * 4, s));
+        }
+        if (any_top && !e->sc_ids) {
+            CK(e->alloc(&e->sc_ids, pos * K));
+            CK(hipMemsetAsync(e->sc_ids, 0xFF, pos * K * 4, s));
+        }
+        if (any_top && !e->sc_top) {
+            CK(e->alloc(&e->sc_top, pos * K));
+            CK(hipMemsetAsync(e->sc_top, 0xFF, pos * K * 4, s));
+        }
+    }
     if (e->ex_stage_cap < n_stage) {
         CK(hipStreamSynchronize(s));
         e->release(e->ex_stage);
@@ -487,35 +515,36 @@ int dots_slots_extend(DotsEngine* e, const int32_t* slots, int n, const int32_t*
         e->ex_stage_cap = n_stage;
     }
     // packed rows, slot by slot in the caller's order: (slot, offset from the slot's context, token or -1 = its pending token); then the
-    // per-slot lists; then, in chunk order, the step row that holds a slot's last fed token and the slot it belongs to
+    // per-slot lists; then, in chunk order, the step row that holds a slot's last fed token and the slot it belongs to; then, of a score,
+    // per packed row the entry it records, its target and its slot's top_n
     std::vector<int32_t> st(n_stage);
     int32_t *h_slot = st.data(), *h_off = h_slot + n_rows, *h_tok = h_off + n_rows, *h_slots = h_tok + n_rows, *h_fed = h_slots + n, *h_new = h_fed + n,
-            *h_gsrc = h_new + n, *h_gdst = h_gsrc + n;
+            *h_gsrc = h_new + n, *h_gdst = h_gsrc + n, *h_entry = top_n ? h_gdst + n : nullptr, *h_target = top_n ? h_entry + n_rows : nullptr,
+            *h_topn = top_n ? h_target + n_rows : nullptr;
     std::vector<int> chunk_g0((size_t)(n_rows + mb - 1) / mb + 1, 0);
     std::vector<LiveRow> live(n);
     int rows = 0;
     {
-        int64_t r = 0, t = 0;
+        extend_pack_rows(slots, ids, lens, keep_pending, n, h_slot, h_off, h_tok);
+        int64_t r = 0;
         int g = 0;
         for (int i = 0; i < n; ++i) {
-            for (int j = 0; j < fed[i]; ++j, ++r) {
-                h_slot[r] = slots[i];
-                h_off[r] = j;
-                h_tok[r] = keep_pending[i] ? (j == 0 ? -1 : ids[t + j - 1]) : ids[t + j];
-            }
-            t += lens[i];
+            r += fed[i];
+            if (top_n) std::fill(h_topn + (r - fed[i]), h_topn + r, top_n[i]);
             h_slots[i] = slots[i]; h_fed[i] = fed[i]; h_new[i] = max_new_tokens[i];
             h_gsrc[g] = (int32_t)((r - 1) % mb); h_gdst[g] = slots[i];      // slots end in row order, so the lists are in chunk order
             chunk_g0[(size_t)((r - 1) / mb) + 1] = ++g;
             live[i] = LiveRow{slots[i], new_prompt[i], max_new_tokens[i]};
         }
         for (size_t k = 1; k < chunk_g0.size(); ++k) chunk_g0[k] = std::max(chunk_g0[k], chunk_g0[k - 1]);
+        if (top_n) score_plan_rows(h_slot, h_off, h_tok, n_rows, h_entry, h_target);
     }
     CK(hipMemcpyAsync(e->ex_stage, st.data(), n_stage * 4, hipMemcpyHostToDevice, s));
     RET(stage_new_rows(e, live, nullptr, &rows));
     CK(hipStreamSynchronize(s));                             // the staged lists are local variables
     const int32_t *d_slot = e->ex_stage, *d_off = d_slot + n_rows, *d_tok = d_off + n_rows, *d_slots = d_tok + n_rows, *d_fed = d_slots + n,
-                  *d_new = d_fed + n, *d_gsrc = d_new + n, *d_gdst = d_gsrc + n;
+                  *d_new = d_fed + n, *d_gsrc = d_new + n, *d_gdst = d_gsrc + n, *d_entry = top_n ? d_gdst + n : nullptr,
+                  *d_target = top_n ? d_entry + n_rows : nullptr, *d_topn = top_n ? d_target + n_rows : nullptr;
     // ---- from here on the call changes state; a failed launch gives the new pages back
     struct ExtendGuard {
         DotsEngine* e; const int32_t* slots; const int* old_pages; int n; bool armed = true;
@@ -540,6 +569,18 @@ int dots_slots_extend(DotsEngine* e, const int32_t* slots, int n, const int32_t*
     }
     e->fresh_slots.clear();                                  // the call overwrites the logits a fork selects from: a fork comes before an extend
     const ExtendRows ex{d_slot, d_off, d_tok, e->ex_tokens, e->ex_ctx, e->ex_table};
+    const ScoreRows sr{d_slot, d_entry, d_target, d_topn};
+    const LogprobState sc_ls{nullptr, nullptr, nullptr, nullptr, nullptr, e->sc_ms, e->sc_pv, e->sc_pi, nullptr, e->sc_tok, e->sc_ids, e->sc_top, c.max_seq_len};
+    if (top_n) {
+        // the slots' entries of an earlier score are gone whatever happens from here on
+        const size_t L = (size_t)c.max_seq_len, K = DOTS_MAX_TOP_LOGPROBS;
+        for (int i = 0; i < n; ++i) {
+            e->sc_n[slots[i]] = 0;
+            CK(hipMemsetAsync(e->sc_tok + slots[i] * L, 0xFF, L * 4, s));
+            if (e->sc_ids) CK(hipMemsetAsync(e->sc_ids + slots[i] * L * K, 0xFF, L * K * 4, s));
+            if (e->sc_top) CK(hipMemsetAsync(e->sc_top + slots[i] * L * K, 0xFF, L * K * 4, s));
+        }
+    }
     const int n_splits = splits_for_ctx(c.max_seq_len);
     for (int64_t r0 = 0, k = 0; r0 < n_rows; r0 += mb, ++k) {
         const int cn = (int)std::min<int64_t>(mb, n_rows - r0);
@@ -549,10 +590,16 @@ int dots_slots_extend(DotsEngine* e, const int32_t* slots, int n, const int32_t*
         const float* pend_scale = nullptr;
         RET(decode_layers(e, e->ex_tokens, e->ex_ctx, e->ex_table, cn, n_splits, 0, &pend, &pend_scale));
         const int g0 = chunk_g0[k], g1 = chunk_g0[k + 1];
-        if (g1 == g0) continue;                              // no slot's last token is in this chunk: nothing reads its residual rows
+        const bool records = top_n && score_chunk_records(h_entry, r0, cn);
+        if (g1 == g0 && !records) continue;                  // no slot's last token is in this chunk: nothing reads its residual rows
         // the lm_head's prologue would apply the pending K-quarter sums of the last down_proj; the gather needs the finished rows
         if (pend) CK(launch_dec_norm_ximg(s, e->d_h, nullptr, nullptr, cn, H, c.rms_norm_eps, e->d_part_h, pend_scale));
-        CK(launch_gather_rows(s, e->d_h, d_gsrc + g0, d_gdst + g0, e->ex_h, g1 - g0, H));
+        if (g1 > g0) CK(launch_gather_rows(s, e->d_h, d_gsrc + g0, d_gdst + g0, e->ex_h, g1 - g0, H));
+        if (!records) continue;
+        // ---- a score: every row's logits (row r of the scratch = packed row r0 + r), then the entries of the rows that record one
+        CK(launch_dec_lmhead(s, e->d_h, e->final_norm, e->lm_head_d, e->lm_head_s, e->sc_logits, cn, H, V, c.rms_norm_eps, 0, e->d_xn));
+        CK(launch_score_logprob_partial(s, e->sc_logits, V, V, sr, (int)r0, cn, sc_ls));
+        CK(launch_score_logprob_final(s, e->sc_logits, V, V, sr, (int)r0, cn, sc_ls));
     }
     // ---- the slots' state: that of slots prefilled with the longer prompt
     CK(launch_extend_commit(s, d_slots, d_fed, d_new, n, e->ctx_len, e->out_lens, e->finished, e->d_max_len));
@@ -562,7 +609,57 @@ int dots_slots_extend(DotsEngine* e, const int32_t* slots, int n, const int32_t*
     RET(select_first_tokens(e, rows, e->ex_h, e->d_xn));
     CK(hipStreamSynchronize(s));
     mark_live(e, live.data(), n, false);
+    for (int i = 0; top_n && i < n; ++i) e->sc_n[slots[i]] = fed[i];        // 1 + (fed - 1) entries
     guard.armed = false;
+    return DOTS_OK;
+}
+}  // namespace
+
+int dots_slots_extend(DotsEngine* e, const int32_t* slots, int n, const int32_t* ids, const int32_t* lens, const int32_t* keep_pending,
+                      const int32_t* max_new_tokens) {
+    if (!e) return DOTS_E_INVALID;
+    if (!e->finalized) return e->fail(DOTS_E_STATE, "weights not finalized");
+    if (!slots || !ids || !lens || !keep_pending || !max_new_tokens) return e->fail(DOTS_E_INVALID, "null argument");
+    return extend_slots(e, "dots_slots_extend", slots, n, ids, lens, keep_pending, max_new_tokens, nullptr);
+}
+
+// Given tokens scored on live sequences: an extend that records, for every fed row but a slot's last, the logprob entry of
+// the next fed token
+int dots_slots_score(DotsEngine* e, const int32_t* slots, int n, const int32_t* ids, const int32_t* lens, const int32_t* keep_pending,
+                     const int32_t* max_new_tokens, const int32_t* top_n) {
+    if (!e) return DOTS_E_INVALID;
+    if (!e->finalized) return e->fail(DOTS_E_STATE, "weights not finalized");
+    if (!slots || !ids || !lens || !keep_pending || !max_new_tokens || !top_n) return e->fail(DOTS_E_INVALID, "null argument");
+    return extend_slots(e, "dots_slots_score", slots, n, ids, lens, keep_pending, max_new_tokens, top_n);
+}
+
+// Entries [pos0, pos0 + n) of the slot's row of the score record, cut to the row's max_seq_len entries; *n_out = how many the last score
+// of the slot recorded (the entries from there on are 0xFF: NaN / -1)
+int dots_slot_scores(DotsEngine* e, int slot, int pos0, int n, float* tok_lp_host, int32_t* top_ids_host, float* top_lp_host, int32_t* n_out) {
+    if (!e || !n_out || pos0 < 0 || n < 0 || (n > 0 && (!tok_lp_host || !top_ids_host || !top_lp_host)))
+        return e ? e->fail(DOTS_E_INVALID, "bad slot_scores arguments") : DOTS_E_INVALID;
+    if (!slot_occupied(e, slot)) return e->fail(DOTS_E_STATE, "slot %d is not occupied", slot);
+    if (!e->sc_n[slot] || !e->sc_tok) return e->fail(DOTS_E_STATE, "slot %d has not been scored since it was filled (dots_slots_score)", slot);
+    const int take = std::max(0, std::min(n, e->cfg.max_seq_len - pos0));
+    *n_out = e->sc_n[slot] - 1;
+    if (take < n) return e->fail(DOTS_E_INVALID, "slot_scores: entries [%d, %d) exceed max_seq_len %d", pos0, pos0 + n, e->cfg.max_seq_len);
+    if (take <= 0) return DOTS_OK;
+    CK(hipSetDevice(e->device));
+    const size_t K = DOTS_MAX_TOP_LOGPROBS, o = (size_t)slot * e->cfg.max_seq_len + pos0;
+    CK(hipMemcpyAsync(tok_lp_host, e->sc_tok + o, (size_t)take * 4, hipMemcpyDeviceToHost, e->stream));
+    if (e->sc_ids && e->sc_top) {
+        CK(hipMemcpyAsync(top_ids_host, e->sc_ids + o * K, (size_t)take * K * 4, hipMemcpyDeviceToHost, e->stream));
+        CK(hipMemcpyAsync(top_lp_host, e->sc_top + o * K, (size_t)take * K * 4, hipMemcpyDeviceToHost, e->stream));
+    } else {
+        // no call has asked for a top list yet.  What the lists would hold: -1 / NaN beyond top_n = 0 as lp_final_entry writes them in
+        // the recorded entries, 0xFF behind them
+        const size_t rec = (size_t)std::max(0, std::min(take, e->sc_n[slot] - 1 - pos0));
+        std::fill(top_ids_host, top_ids_host + rec * K, -1);
+        std::fill(top_lp_host, top_lp_host + rec * K, __builtin_nanf(""));
+        memset(top_ids_host + rec * K, 0xFF, (take - rec) * K * 4);
+        memset(top_lp_host + rec * K, 0xFF, (take - rec) * K * 4);
+    }
+    CK(hipStreamSynchronize(e->stream));
     return DOTS_OK;
 }
 

@@ -342,6 +342,8 @@ def _prototypes(lib):
         "dots_slots_fork": (i32, [vp, i32, P(i32), i32]),
         "dots_slot_logits": (i32, [vp, i32, P(C.c_float)]),
         "dots_slots_extend": (i32, [vp, P(i32), i32, P(i32), P(i32), P(i32), P(i32)]),
+        "dots_slots_score": (i32, [vp, P(i32), i32, P(i32), P(i32), P(i32), P(i32), P(i32)]),
+        "dots_slot_scores": (i32, [vp, i32, i32, i32, P(f32), P(i32), P(f32), P(i32)]),
         "dots_slots_beam": (i32, [vp, i32, P(i32), i32]),
         "dots_beam_info": (i32, [vp, i32, P(i32), P(i32), P(i32)]),
         "dots_beam_read": (i32, [vp, i32, P(i32), P(i32), P(f32), P(i32), P(i32), i32, P(i32), i32, P(i32)]),
@@ -454,6 +456,7 @@ EXPORTED_SYMBOLS = [
     "dots_stop_create", "dots_stop_destroy", "dots_set_row_stop", "dots_row_stop_hit",
     "dots_op_flash_attn_paged", "dots_slots_prefill_begin", "dots_slots_prefill_advance",
     "dots_prefix_cache_enable", "dots_prefix_cache_lookup", "dots_prefix_cache_release", "dots_slots_prefill_begin_cached", "dots_prefix_cache_info",
+    "dots_slots_score", "dots_slot_scores",
 ]
 
 MAX_SPEC_DRAFTS = 15                         # DOTS_MAX_SPEC_DRAFTS: drafts per slot and step
@@ -1300,6 +1303,40 @@ class Engine:
         cap = np.ascontiguousarray(np.broadcast_to(np.asarray(max_new_tokens, dtype=np.int64), sl.shape), dtype=np.int32)
         self._ck(self.lib.dots_slots_extend(self.h, _i32p(sl) if sl.shape[0] else None, sl.shape[0], _i32p(ids), _i32p(lens), _i32p(keep), _i32p(cap)),
                  "dots_slots_extend")
+
+    def slots_score(self, slots: Sequence[int], ids_list: Sequence[Sequence[int]], top_n=0, keep_pending=False, max_new_tokens=1):
+        """Given tokens scored on live sequences: slots_extend with the same arguments, which also records the
+        log-probability of every fed token but the first under the model: entry j of a slot is log p(F[j + 1] | ..., F[j]) over
+        F = [pending] + ids (keep_pending) or ids, with the top_n (0..20, a scalar or one per slot) largest raw logits beside it, bit
+        for bit what row_logprobs returns for a step forced to that token.  The slots are left as slots_extend leaves them.  Returns
+        one (tok_lp float32 [m], top_ids int32 [m, 20], top_lp float32 [m, 20]) per slot, m = len(F) - 1."""
+        sl = np.ascontiguousarray(slots, dtype=np.int32)
+        assert sl.ndim == 1 and len(ids_list) == sl.shape[0]
+        lens = np.ascontiguousarray([len(x) for x in ids_list], dtype=np.int32)
+        ids = np.ascontiguousarray([t for x in ids_list for t in x] or [0], dtype=np.int32)
+        keep = np.ascontiguousarray(np.broadcast_to(np.asarray(keep_pending, dtype=bool), sl.shape), dtype=np.int32)
+        cap = np.ascontiguousarray(np.broadcast_to(np.asarray(max_new_tokens, dtype=np.int64), sl.shape), dtype=np.int32)
+        top = np.ascontiguousarray(np.broadcast_to(np.asarray(top_n, dtype=np.int64), sl.shape), dtype=np.int32)
+        self._ck(self.lib.dots_slots_score(self.h, _i32p(sl) if sl.shape[0] else None, sl.shape[0], _i32p(ids), _i32p(lens), _i32p(keep), _i32p(cap),
+                                           _i32p(top)), "dots_slots_score")
+        return [self.slot_scores(int(b)) for b in sl]
+
+    def slot_scores(self, slot: int, n: Optional[int] = None, pos0: int = 0):
+        """Entries [pos0, pos0 + n) of the slot's last slots_score (n = None: from pos0 to the last one it recorded), as row_logprobs
+        returns positions.  Entries past the last recorded one read as NaN / -1.  Readable until the slot's next prefill, extend,
+        score or release."""
+        K = MAX_TOP_LOGPROBS
+        m = C.c_int32(0)
+        fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))                          # noqa: E731
+        if n is None:
+            self._ck(self.lib.dots_slot_scores(self.h, int(slot), int(pos0), 0, None, None, None, C.byref(m)), "dots_slot_scores")
+            n = max(0, int(m.value) - int(pos0))
+        n = max(0, int(n))
+        tok = np.empty((max(1, n),), np.float32)
+        ids = np.empty((max(1, n), K), np.int32)
+        top = np.empty((max(1, n), K), np.float32)
+        self._ck(self.lib.dots_slot_scores(self.h, int(slot), int(pos0), n, fp(tok), _i32p(ids), fp(top), C.byref(m)), "dots_slot_scores")
+        return tok[:n].copy(), ids[:n].copy(), top[:n].copy()
 
     def slots_beam(self, src: int, dst_slots: Sequence[int]):
         """Beam search: slot src (just prefilled, no decode step since) and the free slots dst_slots become a group of

@@ -418,6 +418,34 @@ class DotsOcrHipForCausalLM:
                     import warnings                  # raise; the handle stays until the rows are cleared (slots_reset)
                     warnings.warn(f"guide {guide} could not be destroyed: {e}")
 
+    def score(self, input_ids, pixel_values=None, image_grid_thw=None, candidates=None, top_logprobs: int = 0):
+        """Teacher-forced log-probabilities of given continuations (Engine.slots_score; vLLM's prompt_logprobs over a
+        suffix).  input_ids (LongTensor [1, T] or [T]) is the prefix the candidates share — the page's image tokens and the text before
+        them — and candidates 1 .. 8 lists of token ids; candidate i is scored as prefix + candidates[i] from one tower, one prefill of
+        the prefix, one fork and one scoring pass, and nothing is generated.  Returns one (tok_lp float32 [m - 1], top_ids int32
+        [m - 1, 20], top_lp float32 [m - 1, 20]) per candidate of m ids: entry j is log p(candidates[i][j + 1] | prefix,
+        candidates[i][:j + 1]) with the top_logprobs (0 .. 20) largest alternatives beside it, bit for bit what forcing the tokens one
+        decode step at a time returns.  To score a candidate's FIRST token too, move the prefix's last id to the head of every candidate,
+        as the server's `score_candidates` does."""
+        import torch
+        from .scheduler import ContinuousBatcher, Request
+        if candidates is None:
+            raise ValueError("score needs candidates: 1 .. 8 lists of token ids")
+        ids = (input_ids.detach().cpu().numpy() if isinstance(input_ids, torch.Tensor) else np.asarray(input_ids)).astype(np.int32)
+        if ids.ndim == 2 and ids.shape[0] == 1:
+            ids = ids[0]
+        if ids.ndim != 1:
+            raise ValueError("score takes one input row: the prefix the candidates share")
+        pix = grid = None
+        if pixel_values is not None:
+            pix = pixel_values.contiguous().float() if getattr(pixel_values, "is_cuda", False) else \
+                np.ascontiguousarray(pixel_values.detach().cpu().numpy() if isinstance(pixel_values, torch.Tensor) else pixel_values, dtype=np.float32)
+            grid = (image_grid_thw.detach().cpu().numpy() if isinstance(image_grid_thw, torch.Tensor) else np.asarray(image_grid_thw)).astype(np.int64)
+        self.engine.set_sampling(0.0, 1.0, 0)
+        req = Request(ids, pix, grid, 1, score=[[int(t) for t in c] for c in candidates], score_top_logprobs=top_logprobs)
+        ContinuousBatcher(self.engine, eos_ids=self.config.eos_token_ids).run([req])
+        return req.scores_out
+
     def _generate(self, input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens, eos_token_id, pad_token_id, continuous, row_sp, rules,
                   guide, ngram=None, nrs=1, stop=None, stop_min=0, beam=None, suffixes=None, prefill_chunk=None, image_keys=None):
         import torch

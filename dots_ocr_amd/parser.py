@@ -275,6 +275,54 @@ class DotsOCRParser:
             results.append(result)
         return results
 
+    # ------------------------------------------------------------------ score given texts against a page
+    def score_image(self, input_path, candidates, prompt_mode="prompt_layout_all_en", bbox=None, top_logprobs=0):
+        """How probable is each of `candidates` (1 .. 8 texts) as the model's answer to this image under prompt_mode?  Nothing is
+        generated: the page is read once and every candidate's tokens — and the EOS behind them — are scored teacher-forced, through the
+        server's `score_candidates` field or, with use_hf, model.score.  Returns one {text, tokens, token_logprobs, cumulative_logprob,
+        mean_logprob} per candidate, in order; with top_logprobs > 0 also top_logprobs: per token its [(token, logprob), ...]."""
+        candidates = list(candidates)
+        if not 1 <= len(candidates) <= self.MAX_PROMPTS or not all(isinstance(c, str) and c for c in candidates):
+            raise ValueError(f"candidates must be 1 .. {self.MAX_PROMPTS} non-empty strings")
+        origin_image = fetch_image(input_path)
+        image, prompt, _, _ = self._prepare(origin_image, prompt_mode, "image", bbox, False)
+        if not self.use_hf:
+            from dots_ocr.model.inference import score_with_vllm
+            choices = score_with_vllm(image, prompt, candidates, model_name=self.model_name, protocol=self.protocol, ip=self.ip, port=self.port,
+                                      top_logprobs=top_logprobs)
+            if choices is None:
+                return None
+            out = []
+            for cand, ch in zip(candidates, choices):
+                content = ch["logprobs"]["content"]
+                lps = [float(e["logprob"]) for e in content]
+                out.append({"text": cand, "tokens": [e["token"] for e in content], "token_logprobs": lps,
+                            "cumulative_logprob": float(ch["cumulative_logprob"]), "mean_logprob": sum(lps) / max(1, len(lps))})
+                if top_logprobs:
+                    out[-1]["top_logprobs"] = [[(t["token"], float(t["logprob"])) for t in e["top_logprobs"]] for e in content]
+            return out
+        import numpy as np
+        import torch
+        inputs = self._build_inputs([image], [prompt])
+        P = inputs["input_ids"][0][inputs["attention_mask"][0].bool()].tolist()
+        if len(P) < 2 or P[-1] == self.model.config.image_token_id:
+            raise ValueError("the chat template must end in a text token behind at least one other token")
+        tok = self.processor.tokenizer
+        eos = int(self.model.config.eos_token_ids[0])
+        fed = [[P[-1]] + [int(t) for t in tok.encode(c)] + [eos] for c in candidates]      # every candidate token, and the EOS, gets an entry
+        scores = self.model.score(torch.tensor([P[:-1]], dtype=torch.long), inputs["pixel_values"], inputs["image_grid_thw"], candidates=fed,
+                                  top_logprobs=top_logprobs)
+        out = []
+        for cand, ids, (tok_lp, top_ids, top_lp) in zip(candidates, fed, scores):
+            lps = [float(v) for v in tok_lp]
+            out.append({"text": cand, "tokens": [tok.decode([t], skip_special_tokens=False) for t in ids[1:]], "token_logprobs": lps,
+                        "cumulative_logprob": float(np.asarray(tok_lp, np.float32).astype(np.float64).sum()), "mean_logprob": sum(lps) / max(1, len(lps))})
+            if top_logprobs:
+                out[-1]["top_logprobs"] = [[(tok.decode([int(i)], skip_special_tokens=False), float(v)) for i, v in zip(top_ids[j][:top_logprobs],
+                                                                                                                       top_lp[j][:top_logprobs])]
+                                           for j in range(len(lps))]
+        return out
+
     def _inference_with_hf(self, image, prompt) -> str:
         return self._inference_batch_with_hf([image], [prompt])[0]
 

@@ -67,13 +67,24 @@ class Request:
                                                 # suffixes[i] — one tower, one prefill of the prefix, one fork, one Engine.slots_extend.  Sequence i
                                                 # runs under `sampling` with seed + i; the finished request carries outputs, logprobs_out, stop_hit
                                                 # and kv_truncated_each in suffix order, exactly like n > 1
+    score: Optional[Sequence[Sequence[int]]] = None      # score given tokens: 1 .. 8 token lists; input_ids is the prefix they share and
+                                                # candidate i is scored as prefix + score[i] — one tower, one prefill of the prefix, one fork, one
+                                                # Engine.slots_score.  Nothing is generated: the request finishes at admission, its slots released,
+                                                # carrying scores_out[i] = (tok_lp [len - 1], top_ids [len - 1, 20], top_lp [len - 1, 20]) in
+                                                # candidate order — entry j is log p(score[i][j + 1] | prefix, score[i][:j + 1]) — and empty outputs
+    score_top_logprobs: int = 0                 # top_n (0..20) of the top lists beside every scored token
     image_key: Optional[bytes] = None           # prefix caching: 16 bytes, the caller's promise that equal keys mean equal pixels and
                                                 # grid.  An image request without one bypasses the cache.  A finished request carries cached_tokens
 
     @property
     def seqs(self) -> int:
-        """independent sequences of the request: one per suffix, else n"""
-        return len(self.suffixes) if self.suffixes else int(self.n)
+        """independent sequences of the request: one per suffix or scored candidate, else n"""
+        return len(self.tails) if self.tails else int(self.n)
+
+    @property
+    def tails(self):
+        """what is fed behind the shared prefix, one list per sequence: the suffixes, or the candidates of a score; None = nothing"""
+        return self.suffixes if self.suffixes else (self.score if self.score else None)
 
     @property
     def width(self) -> int:
@@ -187,6 +198,7 @@ class ContinuousBatcher:
         self._admit_seq: Dict[int, int] = {}                     # slot -> admission counter (the victim order: most recent first)
         self._admit_count = 0
         self._rejected: List[Tuple[int, Request]] = []           # requests whose own parameters the engine refused (reported by step())
+        self._scored: List[Tuple[int, Request]] = []             # score requests finished at their admission (reported by the step's collect)
         self.eos_ids = tuple(int(t) for t in eos_ids)
         engine.set_eos(list(eos_ids))
         if hasattr(engine, "slots_reset"):           # start from an empty engine: no occupied slot, every KV page in the pool
@@ -214,7 +226,9 @@ class ContinuousBatcher:
             raise ValueError(f"n must be an integer >= 1, got {req.n!r}")
         if req.n > self.n_slots:
             raise ValueError(f"n = {req.n} sequences need more than the {self.n_slots} usable slots")
-        if req.suffixes is not None:
+        if req.score is not None:
+            self._check_score(req)
+        if req.suffixes is not None or req.score is not None:
             self._check_suffixes(req, ids.shape[0])
         if req.num_beams is not None:
             self._check_beam(req)
@@ -245,7 +259,7 @@ class ContinuousBatcher:
                 raise RequestRejected(str(e))
         req.input_ids = ids
         # like HF generate, stop at the context capacity instead of failing
-        longest = max((len(x) for x in req.suffixes), default=0) if req.suffixes else 0
+        longest = max((len(x) for x in req.tails), default=0) if req.tails else 0
         req.max_new_tokens = max(1, min(int(req.max_new_tokens), self.max_seq_len - ids.shape[0] - longest))
         if hasattr(self.engine, "kv_pool_info") and self._group_pages(req) > self.engine.kv_pool_info()[0]:
             raise ValueError(f"prompt of {ids.shape[0]} tokens needs {self._group_pages(req)} KV pages, "
@@ -264,38 +278,60 @@ class ContinuousBatcher:
 
     MAX_SUFFIXES = 8
 
+    def _check_score(self, req: Request):
+        """what only a score request is asked; _check_suffixes then asks what it asks of several prompts.  There is nothing
+        to select, so every selection setting is refused by name rather than dropped"""
+        if req.suffixes is not None:
+            raise RequestRejected("score cannot be combined with suffixes")
+        for name, what in (("sampling", "sampling parameters"), ("guide", "a guide"), ("rules", "logit rules"), ("ngram", "an n-gram rule"),
+                           ("stop", "stop strings"), ("logprobs", "logprobs (score_top_logprobs sets the top lists of the scored tokens)")):
+            if getattr(req, name) is not None:
+                raise RequestRejected(f"a score request selects nothing and takes no {what}")
+        t = req.score_top_logprobs
+        if isinstance(t, bool) or not isinstance(t, (int, np.integer)) or not 0 <= t <= 20:
+            raise RequestRejected(f"score_top_logprobs must be an integer in [0, 20], got {t!r}")
+        if not hasattr(self.engine, "slots_score"):
+            raise RequestRejected("score needs continuous batching on an engine that scores given tokens (Engine.slots_score): not with static batching")
+        req.max_new_tokens = 1                       # the token the extend selects is discarded
+
     def _check_suffixes(self, req: Request, prefix: int):
-        """a request with several prompts is refused whole rather than run with anything dropped"""
-        m = len(req.suffixes)
-        if not 2 <= m <= self.MAX_SUFFIXES:
-            raise RequestRejected(f"suffixes must hold 2 .. {self.MAX_SUFFIXES} token lists, got {m}")
+        """a request with several prompts, or with scored candidates, is refused whole rather than run with anything dropped (DESIGN §6.11,
+        §6.14)"""
+        scoring = req.score is not None
+        what, each, tails = ("score", "candidate", req.score) if scoring else ("suffixes", "suffix", req.suffixes)
+        m = len(tails)
+        if not (1 if scoring else 2) <= m <= self.MAX_SUFFIXES:
+            raise RequestRejected(f"{what} must hold {1 if scoring else 2} .. {self.MAX_SUFFIXES} token lists, got {m}")
         if req.n != 1:
-            raise RequestRejected("suffixes cannot be combined with n > 1: every suffix is one sequence")
+            raise RequestRejected(f"{what} cannot be combined with n > 1: every {each} is one sequence")
         if req.num_beams is not None:
-            raise RequestRejected("suffixes cannot be combined with num_beams")
+            raise RequestRejected(f"{what} cannot be combined with num_beams")
         if not all(hasattr(self.engine, f) for f in ("slots_fork", "slots_extend")):
-            raise RequestRejected("suffixes need continuous batching on an engine that extends a live sequence (Engine.slots_extend): "
+            raise RequestRejected(f"{what} need continuous batching on an engine that extends a live sequence (Engine.slots_extend): "
                                   "not with static batching")
         if getattr(self.engine, "spec_k", 0):
-            raise RequestRejected("suffixes cannot run while the engine speculates")
+            raise RequestRejected(f"{what} cannot run while the engine speculates")
         sp = req.sampling
         if sp is not None and (float(getattr(sp, "repetition_penalty", 1.0)) != 1.0 or float(getattr(sp, "frequency_penalty", 0.0)) != 0.0
                                or float(getattr(sp, "presence_penalty", 0.0)) != 0.0):
             raise RequestRejected("suffixes cannot be combined with a penalty: an extended row's prompt-presence image would be wrong")
         if m > self.n_slots:
-            raise ValueError(f"{m} suffixes need more than the {self.n_slots} usable slots")
+            raise ValueError(f"{m} {what if scoring else 'suffixes'} need more than the {self.n_slots} usable slots")
         vocab = getattr(getattr(self.engine, "cfg", None), "vocab_size", None)
         clean = []
-        for i, x in enumerate(req.suffixes):
+        for i, x in enumerate(tails):
             x = [int(t) for t in x]
             if not x:
-                raise RequestRejected(f"suffix {i} is empty: every suffix keeps at least one token")
+                raise RequestRejected(f"{each} {i} is empty: every {each} keeps at least one token")
             if vocab is not None and not all(0 <= t < vocab for t in x):
-                raise RequestRejected(f"suffix {i} holds a token id outside [0, {vocab})")
+                raise RequestRejected(f"{each} {i} holds a token id outside [0, {vocab})")
             if prefix + len(x) >= self.max_seq_len:
-                raise ValueError(f"prefix + suffix {i} = {prefix} + {len(x)} tokens do not fit max_seq_len={self.max_seq_len}")
+                raise ValueError(f"prefix + {each} {i} = {prefix} + {len(x)} tokens do not fit max_seq_len={self.max_seq_len}")
             clean.append(x)
-        req.suffixes = clean
+        if scoring:
+            req.score = clean
+        else:
+            req.suffixes = clean
 
     def _check_beam(self, req: Request):
         """a beam request is refused whole rather than run with anything dropped"""
@@ -329,7 +365,7 @@ class ContinuousBatcher:
 
     @property
     def idle(self) -> bool:
-        return not self.pending and not self.running and not self._ahead and not self._rejected and not self.filling
+        return not self.pending and not self.running and not self._ahead and not self._rejected and not self.filling and not self._scored
 
     def free_slots(self) -> List[int]:
         held = {s for s, _, _ in self.filling} | {k for ks in self._fill_kids.values() for k in ks}
@@ -347,8 +383,8 @@ class ContinuousBatcher:
         t = int(r.input_ids.shape[0])
         if r.num_beams:
             return self._beam_pages(r)
-        if r.suffixes:                               # after the extend: every sequence holds its own longer prompt + ADMIT_AHEAD
-            return sum(self._admit_pages(t + len(x), r.max_new_tokens) for x in r.suffixes) - (len(r.suffixes) - 1) * (t // 64)
+        if r.tails:                                  # after the extend (or score): every sequence holds its own longer prompt + ADMIT_AHEAD
+            return sum(self._admit_pages(t + len(x), r.max_new_tokens) for x in r.tails) - (len(r.tails) - 1) * (t // 64)
         need = self._admit_pages(t, r.max_new_tokens)
         return need + (int(r.n) - 1) * (need - t // 64)
 
@@ -365,8 +401,8 @@ class ContinuousBatcher:
         if r.num_beams:
             return self._beam_pages(r)               # the whole group holds its pages until it is released together
         t, n = int(r.input_ids.shape[0]), r.seqs if n is None else n
-        if r.suffixes:                               # the n longest of its sequences: conservative for whatever is still running
-            each = sorted(((min(t + len(x) + int(r.max_new_tokens), self.max_seq_len) + 63) // 64 for x in r.suffixes), reverse=True)[:n]
+        if r.tails:                                  # the n longest of its sequences: conservative for whatever is still running
+            each = sorted(((min(t + len(x) + int(r.max_new_tokens), self.max_seq_len) + 63) // 64 for x in r.tails), reverse=True)[:n]
             return sum(each) - (len(each) - 1) * (t // 64)
         worst = (min(t + int(r.max_new_tokens), self.max_seq_len) + 63) // 64
         return worst + (n - 1) * (worst - t // 64)
@@ -576,12 +612,23 @@ class ContinuousBatcher:
             for s, rid, r in group:                  # after every fork (an extend ends the prefill's fork window): one extend per request with suffixes
                 if r.suffixes:
                     self.engine.slots_extend([s] + kids[rid], r.suffixes, keep_pending=False, max_new_tokens=int(r.max_new_tokens))
+            for s, rid, r in group:                  # likewise one score per request with candidates: its entries are read here, nothing decodes
+                if r.score:
+                    r.scores_out = self.engine.slots_score([s] + kids.get(rid, []), r.score, top_n=int(r.score_top_logprobs), keep_pending=False,
+                                                           max_new_tokens=1)
         except Exception:
             for s in slots + forked:                 # the prefill went in: give its slots back, the caller re-queues the group
                 self.engine.slot_release(s)
             self._clear_rows(every)
             raise
         for s, rid, r in group:
+            if r.score:                              # finished at once: the selected token is discarded, the slots go back
+                for k in [s] + kids.get(rid, []):
+                    self.engine.slot_release(k)
+                r.outputs = [np.zeros(0, np.int32) for _ in r.score]
+                r.kv_truncated, r.kv_truncated_each = False, [False] * len(r.score)
+                self._scored.append((rid, r))
+                continue
             for j, k in enumerate([s] + kids.get(rid, [])):
                 self.running[k] = (rid, r)
                 self._admit_count += 1
@@ -729,7 +776,8 @@ class ContinuousBatcher:
     # ------------------------------------------------------------------ main loop
     def _collect(self) -> List[Tuple[int, Request, np.ndarray]]:
         fin, lens = self.engine.slots_poll()
-        done = []
+        done = [(rid, r, r.outputs[0]) for rid, r in self._scored]
+        self._scored = []
         for s in sorted(self.running):
             if s not in self.running:                # a slot of a beam group that has just been reported
                 continue

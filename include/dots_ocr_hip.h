@@ -518,6 +518,33 @@ int dots_slots_prefill(DotsEngine* e, const int32_t* slots_host, int n, const in
  *                    pages (DOTS_E_CAPACITY).  Synchronises. */
 int dots_slots_extend(DotsEngine* e, const int32_t* slots_host, int n, const int32_t* ids_host, const int32_t* lens_host,
                       const int32_t* keep_pending_host, const int32_t* max_new_tokens_host);
+/* ---- Score given tokens on a live sequence: teacher-forced log-probabilities of a text the engine did not generate — vLLM's
+ * prompt_logprobs over a suffix — in passes of max_batch positions instead of one decode step per token.
+ *
+ * dots_slots_score   dots_slots_extend with a record: the same arguments, checks, page arithmetic and launches, and every listed slot is
+ *                    left in exactly the state dots_slots_extend with the same arguments leaves it (KV, context, first token selected from
+ *                    its last fed row, automata restarted), so a scored prefix can be continued by ordinary decoding.  top_n_host[i] in
+ *                    [0, DOTS_MAX_TOP_LOGPROBS] is slot i's top-list length.  Let F = [pending] + ids with keep_pending, else ids, f = |F|.
+ *                    Entry j (0 <= j < f - 1) of the slot holds what the logprob stage (dots_set_row_logprobs) would have written had the
+ *                    row at F[j]'s position selected F[j+1]: tok_lp = l[F[j+1]] - lse over the fp32 lm_head row l at F[j]'s position, and
+ *                    the top_n largest raw logits as (id, l[id] - lse), value descending then id ascending; -1 / NaN beyond top_n.  Bit
+ *                    for bit the entry of a sequential step forced to F[j+1].  The last fed row records nothing (its logits select the
+ *                    slot's first token, as in an extend); f == 1 records zero entries.  The slot's entries are 0xFF-filled when the call
+ *                    starts and stay readable until the next prefill, extend, score, release or reset of that slot.  The logits of the
+ *                    fed rows go to a scratch of the call's own: dots_slot_logits of a slot outside the call is untouched.  The scratch
+ *                    and the entries ([max_batch][max_seq_len]; the top lists once a call asks for top_n > 0) are allocated by the first
+ *                    scoring call: an engine that never scores allocates and launches nothing of this.
+ *                    Refused with nothing changed, as dots_slots_extend: a slot out of range or listed twice, lens < 1, max_new < 1, an id
+ *                    out of range or an image token, top_n outside [0, 20] (DOTS_E_INVALID); a free, filling or suspended slot, a row of a
+ *                    beam group, a row that carries a penalty, a speculating engine, a static batch (DOTS_E_STATE); prompt +
+ *                    max_new_tokens above max_seq_len, or a pool that cannot serve the pages (DOTS_E_CAPACITY).  Synchronises.
+ * dots_slot_scores   entries [pos0, pos0 + n) of the slot's row of the record (pos0 + n <= max_seq_len), in the layout of
+ *                    dots_row_logprobs: tok_lp float [n], top_ids int32 [n][20], top_lp float [n][20].  *n_out = the number of entries the
+ *                    slot's last score recorded; entries from there on read as 0xFF (NaN / -1).  DOTS_E_STATE for a free slot and for a
+ *                    slot that has not been scored since it was filled or extended.  Synchronises. */
+int dots_slots_score(DotsEngine* e, const int32_t* slots_host, int n, const int32_t* ids_host, const int32_t* lens_host,
+                     const int32_t* keep_pending_host, const int32_t* max_new_tokens_host, const int32_t* top_n_host);
+int dots_slot_scores(DotsEngine* e, int slot, int pos0, int n, float* tok_lp_host, int32_t* top_ids_host, float* top_lp_host, int32_t* n_out);
 /* ---- Chunked prefill: the prompts of dots_slots_prefill filled in passes over their own KV pages, so that decode chunks of
  * the running slots can run between the passes and a prompt may be longer than max_prefill_tokens.
  *
