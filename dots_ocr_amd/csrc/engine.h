@@ -200,6 +200,12 @@ struct DotsEngine {
     int32_t *lp_ids = nullptr, *lp_pi = nullptr, *lp_pos = nullptr;
     int row_lp[DOTS_MAX_BATCH];
     int n_lp = 0;                          // rows with logprobs on: > 0 adds the two logprob kernels around the selection stage
+    // streaming (dots_set_row_stream / dots_slots_drain), allocated by the first row switched on: the rows' cursors (output
+    // tokens already delivered) and the mapped pinned block stream_drain_kernel stores into (st_dev: its device address).  row_stream is
+    // host-only: a drain hands the kernel the streaming rows as a bit mask
+    int32_t* stream_pos = nullptr;
+    int32_t *st_host = nullptr, *st_dev = nullptr;
+    int row_stream[DOTS_MAX_BATCH] = {0};
     // n-gram speculative decoding (dots_set_speculation): spec_k drafts per slot and step (0 = off), the drafter's n-gram
     // sizes (spec_max_n == 0: host drafts only), and — allocated by the first call that switches it on — the slots' drafts, the expanded
     // row arrays of a speculating step and the counters (kernels.h SpecState)
@@ -507,6 +513,12 @@ int step_graph(DotsEngine* e, int rows, int n_splits, int out_cap, hipGraphExec_
 // slots.hip: a suspended slot: occupied, its KV parked in host memory (dots_slot_suspend)
 inline bool slot_parked(const DotsEngine* e, int slot) { return slot >= 0 && slot < DOTS_MAX_BATCH && e->parked[slot].on; }
 void swap_free_host(DotsEngine* e);
+// slots.hip: what a poll does to the host record with the device's finished / out_lens (dots_slots_poll, dots_slots_drain)
+void poll_host_state(DotsEngine* e, int32_t* finished, int32_t* out_lens);
+// stream.hip: the rows' stream cursors
+int stream_restart_row(DotsEngine* e, int row);
+int stream_reset(DotsEngine* e);
+void stream_free_host(DotsEngine* e);
 // beam.hip: beam groups
 int beam_step(DotsEngine* e, int rows);
 int beam_before_decode(DotsEngine* e, int n_steps);

@@ -931,6 +931,7 @@ void dots_destroy(DotsEngine* e) {
     for (void* p : e->allocs) hipFree(p);
     if (e->rule_stage_host) hipHostFree(e->rule_stage_host);
     swap_free_host(e);
+    stream_free_host(e);
     if (e->rule_ev) hipEventDestroy(e->rule_ev);
     for (auto& ev : e->ev) if (ev) hipEventDestroy(ev);
     for (auto& ev : e->attn_ev) hipEventDestroy(ev);

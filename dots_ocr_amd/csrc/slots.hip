@@ -173,6 +173,7 @@ int rows_go_live(DotsEngine* e, const std::vector<LiveRow>& rows, bool clear_lp)
         CK(hipMemcpyAsync(e->ctx_len + r.slot, &r.ctx, 4, hipMemcpyHostToDevice, s));
         CK(hipMemcpyAsync(e->d_max_len + r.slot, &r.cap, 4, hipMemcpyHostToDevice, s));
         CK(hipMemsetAsync(e->out_lens + r.slot, 0, 4, s));
+        RET(stream_restart_row(e, r.slot));
         CK(hipMemsetAsync(e->finished + r.slot, 0, 4, s));
         if (e->sp_ndraft) {
             CK(hipMemsetAsync(e->sp_ndraft + r.slot, 0, 4, s));
@@ -228,6 +229,22 @@ void mark_live(DotsEngine* e, const LiveRow* rows, int n, bool occupy) {
         e->sc_n[b] = 0;                                     // whatever a score recorded belongs to the sequence before
     }
     e->sel_dirty = true;
+}
+
+// the device's finished / out_lens as a poll reports them, and what the host record takes from them
+void poll_host_state(DotsEngine* e, int32_t* finished, int32_t* out_lens) {
+    const int mb = e->cfg.max_batch;
+    for (int b = 0; b < mb; ++b) {
+        if (e->slot_mode && e->fill[b].on) { finished[b] = 3; out_lens[b] = 0; }             // filling (dots_slots_prefill_begin): nothing generated yet
+        else if (!e->slot_mode || !e->slot_active[b]) { finished[b] = -1; out_lens[b] = 0; }      // -1: free slot
+        else if (e->parked[b].on) finished[b] = 2;                                           // suspended: out_lens as they stood at suspend
+        else {
+            if (finished[b]) e->slot_done[b] = 1;                                            // takes no more pages
+            // every issued step has run: the context is prompt + generated - 1 exactly.  A speculating step advances a row by 1 .. k + 1
+            // positions, so dots_slots_decode counts k + 1 per step; without this the bound (and the pages taken ahead) would run away
+            if (e->spec_k) e->slot_ctx_ub[b] = std::min(e->slot_ctx_ub[b], e->slot_prompt[b] + out_lens[b] - 1);
+        }
+    }
 }
 }  // namespace engine
 
@@ -603,7 +620,10 @@ int extend_slots(DotsEngine* e, const char* call, const int32_t* slots, int n, c
     }
     // ---- the slots' state: that of slots prefilled with the longer prompt
     CK(launch_extend_commit(s, d_slots, d_fed, d_new, n, e->ctx_len, e->out_lens, e->finished, e->d_max_len));
-    for (int i = 0; i < n; ++i) RET(clear_lp_row(e, slots[i]));
+    for (int i = 0; i < n; ++i) {
+        RET(clear_lp_row(e, slots[i]));
+        RET(stream_restart_row(e, slots[i]));                // extend_commit_kernel zeroed out_lens
+    }
     RET(restart_automata(e, d_slots, n));
     // ---- the first tokens of the new turn: lm_head over the slots' last fed rows, the selection stage over a mask of the extended slots only
     RET(select_first_tokens(e, rows, e->ex_h, e->d_xn));
@@ -692,6 +712,7 @@ int dots_slots_reset(DotsEngine* e) {
     if (e->d_row_lp) CK(hipMemsetAsync(e->d_row_lp, 0xFF, DOTS_MAX_BATCH * 4, s));
     std::fill(e->row_lp, e->row_lp + DOTS_MAX_BATCH, -1);
     e->n_lp = 0;
+    RET(stream_reset(e));
     if (e->sp_ndraft) CK(hipMemsetAsync(e->sp_ndraft, 0, DOTS_MAX_BATCH * 4, s));
     if (e->sp_cls) CK(hipMemsetAsync(e->sp_cls, 0, DOTS_MAX_BATCH * 4, s));         // SPEC_ROW_ARGMAX: no row carries anything
     CK(hipStreamSynchronize(s));
@@ -786,17 +807,7 @@ int dots_slots_poll(DotsEngine* e, int32_t* finished, int32_t* out_lens) {
     CK(hipMemcpyAsync(finished, e->finished, mb * 4, hipMemcpyDeviceToHost, e->stream));
     CK(hipMemcpyAsync(out_lens, e->out_lens, mb * 4, hipMemcpyDeviceToHost, e->stream));
     CK(hipStreamSynchronize(e->stream));
-    for (int b = 0; b < mb; ++b) {
-        if (e->slot_mode && e->fill[b].on) { finished[b] = 3; out_lens[b] = 0; }             // filling (dots_slots_prefill_begin): nothing generated yet
-        else if (!e->slot_mode || !e->slot_active[b]) { finished[b] = -1; out_lens[b] = 0; }      // -1: free slot
-        else if (e->parked[b].on) finished[b] = 2;                                           // suspended: out_lens as they stood at suspend
-        else {
-            if (finished[b]) e->slot_done[b] = 1;                                            // takes no more pages
-            // every issued step has run: the context is prompt + generated - 1 exactly.  A speculating step advances a row by 1 .. k + 1
-            // positions, so dots_slots_decode counts k + 1 per step; without this the bound (and the pages taken ahead) would run away
-            if (e->spec_k) e->slot_ctx_ub[b] = std::min(e->slot_ctx_ub[b], e->slot_prompt[b] + out_lens[b] - 1);
-        }
-    }
+    poll_host_state(e, finished, out_lens);
     return DOTS_OK;
 }
 
@@ -832,6 +843,7 @@ int dots_slot_release(DotsEngine* e, int slot) {
     if (e->beam_of[slot]) return beam_release_group(e, slot);          // the slots of a beam group go together
     for (int f = 0; f < ROW_FEATURES; ++f) RET(clear_row_feature(e, slot, (RowFeature)f));
     RET(set_row_lp(e, slot, -1));
+    e->row_stream[slot] = 0;
     e->slot_active[slot] = 0;
     e->sel_dirty = true;
     CK(hipMemsetAsync(e->ctx_len + slot, 0, 4, e->stream));          // an idle row attends over one key only ...

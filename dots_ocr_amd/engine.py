@@ -348,6 +348,8 @@ def _prototypes(lib):
         "dots_beam_info": (i32, [vp, i32, P(i32), P(i32), P(i32)]),
         "dots_beam_read": (i32, [vp, i32, P(i32), P(i32), P(f32), P(i32), P(i32), i32, P(i32), i32, P(i32)]),
         "dots_slots_poll": (i32, [vp, P(i32), P(i32)]),
+        "dots_set_row_stream": (i32, [vp, i32, i32]),
+        "dots_slots_drain": (i32, [vp, P(i32), P(i32), P(i32), P(i32), P(i32), P(i32), i32, P(f32), P(i32), P(f32), i32, P(i32), P(i32)]),
         "dots_slot_read": (i32, [vp, i32, P(i32), i32, P(i32)]),
         "dots_slot_release": (i32, [vp, i32]),
         "dots_kv_pool_info": (i32, [vp, P(i32), P(i32)]),
@@ -435,7 +437,7 @@ def _prototypes(lib):
 EXPORTED_SYMBOLS = [
     "dots_create", "dots_destroy", "dots_last_error", "dots_stream", "dots_load_weight", "dots_finalize_weights",
     "dots_vit_forward", "dots_vit_prefetch", "dots_vit_take_prefetched", "dots_vit_prefetch_ready", "dots_preprocess_image", "dots_prefill", "dots_decode_step", "dots_generate", "dots_set_sampling", "dots_set_decode_plan", "dots_set_gemm_plan", "dots_tower_tail", "dots_get_logits",
-    "dots_set_eos", "dots_slots_prefill", "dots_slots_decode", "dots_slots_poll", "dots_slot_read", "dots_slot_release", "dots_kv_pool_info", "dots_slot_capacity", "dots_slots_reset",
+    "dots_set_eos", "dots_slots_prefill", "dots_slots_decode", "dots_slots_poll", "dots_set_row_stream", "dots_slots_drain", "dots_slot_read", "dots_slot_release", "dots_kv_pool_info", "dots_slot_capacity", "dots_slots_reset",
     "dots_kv_swap_reserve", "dots_kv_swap_info", "dots_slot_suspend", "dots_slot_resume", "dots_slots_pages_short",
     "dots_set_next_tokens", "dots_get_last_tokens", "dots_get_stats", "dots_synchronize", "dots_debug_capture_hidden",
     "dots_debug_read_hidden", "dots_dev_alloc",
@@ -556,6 +558,7 @@ def draft_row_counts(counts, drafts, j: int) -> dict:
     return c
 
 
+STREAM_ROW_CAP = 256                         # DOTS_STREAM_ROW_CAP: tokens one row delivers per slots_drain at the most
 MAX_TOP_LOGPROBS = 20                        # DOTS_MAX_TOP_LOGPROBS: top entries kept per position
 
 KV_CACHE_DTYPES = {"bf16": 0, "fp8": 1}      # DotsConfig.kv_cache_dtype; "fp8" = OCP e4m3fn (vLLM's --kv-cache-dtype fp8)
@@ -636,6 +639,9 @@ class Engine:
         self.h = h
         self.token_bytes = None                  # guided.TokenBytes once set_token_bytes has run
         self._stops = OrderedDict()              # tuple of stop strings -> handle (create_stop): a small LRU of uploaded automata
+        self._drain_tok = None                   # slots_drain's host buffers, kept between calls: tokens, and — once a row has had logprobs
+        self._drain_lp = None                    # switched on (_drain_wants_lp) — the three logprob arrays
+        self._drain_wants_lp = False
 
     # ------------------------------------------------------------------ plumbing
     def _ck(self, rc: int, what: str):
@@ -1140,6 +1146,8 @@ class Engine:
         if top_n is not None and not 0 <= n <= MAX_TOP_LOGPROBS:
             raise ValueError(f"top_n must be None or in [0, {MAX_TOP_LOGPROBS}], got {top_n!r}")
         self._ck(self.lib.dots_set_row_logprobs(self.h, int(row), n), "dots_set_row_logprobs")
+        if n >= 0:
+            self._drain_wants_lp = True              # slots_drain keeps room for logprob entries from now on
 
     def row_logprobs(self, row: int, n: int, pos0: int = 0):
         """Positions [pos0, pos0 + n) of the row's generated tokens, cut to the positions that exist: (tok_lp float32 [m],
@@ -1382,6 +1390,39 @@ class Engine:
         lens = np.empty((self.max_batch,), dtype=np.int32)
         self._ck(self.lib.dots_slots_poll(self.h, _i32p(fin), _i32p(lens)), "dots_slots_poll")
         return fin, lens
+
+    def set_row_stream(self, row: int, on: bool = True):
+        """Slot `row` streams: slots_drain delivers its new tokens (and logprob entries, with set_row_logprobs).  Set before the slot's
+        prefill or fork; slot release and slots_reset switch it off.  Refused for a row of a beam group."""
+        self._ck(self.lib.dots_set_row_stream(self.h, int(row), 1 if on else 0), "dots_set_row_stream")
+
+    def slots_drain(self):
+        """slots_poll plus what every streaming row committed since the last drain, in one launch and one synchronisation:
+        -> (finished, out_lens, deltas); deltas maps slot -> (tokens int32 [m], None | (tok_lp [m], top_ids [m, 20], top_lp [m, 20])) for
+        the streaming rows with m > 0, the second member in the layout of row_logprobs for rows that return logprobs.  A row delivers
+        at most STREAM_ROW_CAP tokens per call, the oldest first; the rest come with the next call."""
+        mb, K = self.max_batch, MAX_TOP_LOGPROBS
+        n = mb * STREAM_ROW_CAP
+        if self._drain_tok is None:
+            self._drain_tok = np.empty((n,), np.int32)
+        if self._drain_lp is None and self._drain_wants_lp:
+            self._drain_lp = (np.empty((n,), np.float32), np.empty((n, K), np.int32), np.empty((n, K), np.float32))
+        tok, lp = self._drain_tok, self._drain_lp
+        fin, lens = np.empty((mb,), np.int32), np.empty((mb,), np.int32)
+        first, count, lpf = np.empty((mb,), np.int32), np.empty((mb,), np.int32), np.empty((mb,), np.int32)
+        nt, nl = C.c_int32(0), C.c_int32(0)
+        fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))                          # noqa: E731
+        null_f, null_i = C.POINTER(C.c_float)(), C.POINTER(C.c_int32)()
+        self._ck(self.lib.dots_slots_drain(self.h, _i32p(fin), _i32p(lens), _i32p(first), _i32p(count), _i32p(lpf), _i32p(tok),
+                                           tok.shape[0], fp(lp[0]) if lp else null_f, _i32p(lp[1]) if lp else null_i,
+                                           fp(lp[2]) if lp else null_f, lp[0].shape[0] if lp else 0, C.byref(nt), C.byref(nl)),
+                 "dots_slots_drain")
+        deltas = {}
+        for b in np.nonzero(count)[0].tolist():
+            f, m, l = int(first[b]), int(count[b]), int(lpf[b])
+            entries = None if l < 0 else (lp[0][l:l + m].copy(), lp[1][l:l + m].copy(), lp[2][l:l + m].copy())
+            deltas[b] = (tok[f:f + m].copy(), entries)
+        return fin, lens, deltas
 
     def slot_read(self, slot: int, capacity: int) -> np.ndarray:
         out = np.empty((max(1, capacity),), dtype=np.int32)

@@ -137,7 +137,8 @@ class DotsOcrHipForCausalLM:
                  no_repeat_ngram_whitelist=None, speculative_ngram: Optional[int] = None, prompt_lookup_min: int = 2, prompt_lookup_max: int = 4,
                  num_return_sequences: int = 1, stop_strings=None, speculative_rows=None, num_beams: Optional[int] = None,
                  length_penalty: float = 1.0, early_stopping=None, speculative_guided: bool = False, prompt_suffixes=None, speculative_shaped=None,
-                 prefill_chunk: Optional[int] = None, enable_prefix_caching: bool = False, image_keys=None, speculative_logprobs: bool = False, **_):
+                 prefill_chunk: Optional[int] = None, enable_prefix_caching: bool = False, image_keys=None, speculative_logprobs: bool = False, streamer=None,
+                 **_):
         """HF-shaped generate.  do_sample / temperature / top_p default to the checkpoint's generation_config.json (greedy when it
         is absent); with sampling on, tokens are drawn on the GPU from softmax(logits / temperature) restricted to the top_p
         nucleus, reproducibly from `seed`.  Returns LongTensor
@@ -226,7 +227,11 @@ class DotsOcrHipForCausalLM:
         starts a prompt that begins with the same tokens and the same image behind them (ContinuousBatcher(prefix_caching=True), DESIGN
         §6.13): the same tokens as without it.  image_keys: per sequence 16 bytes that name its image (or None) — the caller's promise that
         equal keys mean equal pixels and grid, for instance a digest of the decoded image's bytes and size; a sequence with an image and
-        no key bypasses the cache."""
+        no key bypasses the cache.
+
+        streamer (Hugging Face's protocol, duck-typed: put(ids) and end()) receives the prompt ids, then the new ids of every scheduler
+        chunk as they are generated (Request(stream=)), then end().  It is for one sequence, as in HF: a batch above 1,
+        num_return_sequences > 1 or num_beams with a streamer raise ValueError.  It runs on the continuous path."""
         import dataclasses
         import torch
         t_eff, p_eff = resolve_sampling(self.generation_config, do_sample, temperature, top_p)
@@ -246,6 +251,17 @@ class DotsOcrHipForCausalLM:
             raise ValueError("enable_prefix_caching needs prefill_chunk: only pages written by a chunked fill are cached")
         if image_keys is not None and (not enable_prefix_caching or len(image_keys) != int(input_ids.shape[0])):
             raise ValueError("image_keys needs enable_prefix_caching and one entry (16 bytes or None) per sequence")
+        if streamer is not None:
+            refused = [name for name, on in (("a batch above 1", int(input_ids.shape[0]) != 1), ("num_return_sequences > 1", nrs > 1),
+                                             ("num_beams", num_beams not in (None, 1)), ("prompt_suffixes", prompt_suffixes is not None),
+                                             ("continuous=False", continuous is False)) if on]
+            if refused:
+                raise ValueError(f"a streamer takes one sequence: it cannot be combined with {', '.join(refused)}")
+            if not (hasattr(streamer, "put") and hasattr(streamer, "end")):
+                raise ValueError("streamer needs put(ids) and end()")
+            if not hasattr(self.engine, "slots_drain"):
+                raise ValueError("this engine cannot stream (no slots_drain)")
+            continuous = True
         if early_stopping is not None:
             raise ValueError("early_stopping is not offered: a beam group ends at its cap, or early only where that is exact (DESIGN §6.9)")
         beam = None
@@ -394,7 +410,7 @@ class DotsOcrHipForCausalLM:
         try:
             return self._generate(input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens, eos_token_id, pad_token_id, continuous,
                                   row_sp, rules, guide, ngram, nrs, stop, int(min_tokens or 0), beam, suffixes, prefill_chunk,
-                                  (image_keys or [None] * int(input_ids.shape[0])) if enable_prefix_caching else None)
+                                  (image_keys or [None] * int(input_ids.shape[0])) if enable_prefix_caching else None, streamer)
         finally:
             if spec_k:
                 try:
@@ -447,7 +463,7 @@ class DotsOcrHipForCausalLM:
         return req.scores_out
 
     def _generate(self, input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens, eos_token_id, pad_token_id, continuous, row_sp, rules,
-                  guide, ngram=None, nrs=1, stop=None, stop_min=0, beam=None, suffixes=None, prefill_chunk=None, image_keys=None):
+                  guide, ngram=None, nrs=1, stop=None, stop_min=0, beam=None, suffixes=None, prefill_chunk=None, image_keys=None, streamer=None):
         import torch
         if suffixes:
             nrs = len(suffixes)                      # the rows of the result: one per suffix, laid out as num_return_sequences lays them out
@@ -515,10 +531,15 @@ class DotsOcrHipForCausalLM:
                                         ngram=ngram, n=1 if suffixes else nrs, stop=stop, suffixes=suffixes))
                 if beam is not None:             # a group of beam[0] beams that returns its nrs best hypotheses
                     reqs[-1].n, reqs[-1].num_beams, reqs[-1].num_return, reqs[-1].length_penalty = 1, beam[0], nrs, beam[1]
+            if streamer is not None:             # one sequence (generate() checked): the prompt, then every chunk's new ids, then end()
+                streamer.put(input_ids.detach().cpu())
+                reqs[0].stream = lambda rid, index, toks, lp, fin: len(toks) and streamer.put(torch.as_tensor(np.asarray(toks), dtype=torch.long))
             chunk_kw = {} if prefill_chunk is None else {"prefill_chunk": prefill_chunk}
             if image_keys is not None:           # enable_prefix_caching
                 chunk_kw["prefix_caching"] = True
             outs = ContinuousBatcher(self.engine, eos_ids=eos, **chunk_kw).run(reqs)
+            if streamer is not None:
+                streamer.end()
             if beam is not None:                 # row i * n + j = the j-th best hypothesis of prompt i (a prompt with fewer: pad rows)
                 outs = [r.outputs[j] if j < len(r.outputs) else np.zeros(0, np.int64) for r in reqs for j in range(nrs)]
             elif nrs > 1:                        # row i * n + j = sequence j of prompt i

@@ -73,6 +73,10 @@ class Request:
                                                 # carrying scores_out[i] = (tok_lp [len - 1], top_ids [len - 1, 20], top_lp [len - 1, 20]) in
                                                 # candidate order — entry j is log p(score[i][j + 1] | prefix, score[i][:j + 1]) — and empty outputs
     score_top_logprobs: int = 0                 # top_n (0..20) of the top lists beside every scored token
+    stream: Optional[object] = None             # streaming: callback(rid, index, tokens, logprobs_or_None, finished), called on the
+                                                # scheduler's thread once per sequence that has new tokens or has just finished, before the request is
+                                                # reported; index = 0, the fork index of n > 1, or the prompt index of suffixes.  The tokens of all calls
+                                                # for an index, concatenated, are the request's outputs[index]; logprobs in the layout of row_logprobs
     image_key: Optional[bytes] = None           # prefix caching: 16 bytes, the caller's promise that equal keys mean equal pixels and
                                                 # grid.  An image request without one bypasses the cache.  A finished request carries cached_tokens
 
@@ -187,6 +191,10 @@ class ContinuousBatcher:
         self._row_guide: Dict[int, int] = {}                     # slot -> the guide handle set on it (engine.set_row_guide)
         self._row_ngram: Dict[int, object] = {}                  # slot -> the NgramRule set on it (engine.set_row_ngram)
         self._row_stop: Dict[int, int] = {}                      # slot -> the stop automaton handle set on it (engine.set_row_stop)
+        self._row_stream: Dict[int, bool] = {}                   # slot -> its stream is switched on (engine.set_row_stream)
+        self._streamed: Dict[int, int] = {}                      # streaming slot -> tokens of its sequence handed to the callback so far
+        self._cancel: set = set()                                # request ids cancelled while being admitted: cancelled by the first collect that sees them running
+        self._cancelled: List[Tuple[int, Request, np.ndarray]] = []   # cancelled requests (reported by step())
         self._kids: Dict[int, List[int]] = {}                    # request id -> the slots planned for sequences 1 .. n - 1 of a request with n > 1
         self._seq_index: Dict[int, int] = {}                     # slot -> index of its sequence within a request with n > 1
         self.kv_truncated = 0                                    # sequences ended early by a dry KV pool (finish reason "kv_pool_exhausted")
@@ -226,6 +234,8 @@ class ContinuousBatcher:
             raise ValueError(f"n must be an integer >= 1, got {req.n!r}")
         if req.n > self.n_slots:
             raise ValueError(f"n = {req.n} sequences need more than the {self.n_slots} usable slots")
+        if req.stream is not None:
+            self._check_stream(req)
         if req.score is not None:
             self._check_score(req)
         if req.suffixes is not None or req.score is not None:
@@ -333,6 +343,17 @@ class ContinuousBatcher:
         else:
             req.suffixes = clean
 
+    def _check_stream(self, req: Request):
+        """a streaming request is refused whole rather than run without its callback"""
+        if not callable(req.stream):
+            raise ValueError(f"stream must be a callable (rid, index, tokens, logprobs, finished), got {req.stream!r}")
+        if req.num_beams is not None:
+            raise RequestRejected("a beam request cannot stream: a group's outputs are reordered until it ends")
+        if req.score is not None:
+            raise RequestRejected("a score request generates nothing and cannot stream")
+        if not all(hasattr(self.engine, f) for f in ("slots_drain", "set_row_stream")):
+            raise ValueError("this engine cannot stream (no slots_drain): stream is not available")
+
     def _check_beam(self, req: Request):
         """a beam request is refused whole rather than run with anything dropped"""
         from .beam import MAX_BEAMS
@@ -365,7 +386,8 @@ class ContinuousBatcher:
 
     @property
     def idle(self) -> bool:
-        return not self.pending and not self.running and not self._ahead and not self._rejected and not self.filling and not self._scored
+        return (not self.pending and not self.running and not self._ahead and not self._rejected and not self.filling and not self._scored
+                and not self._cancelled)
 
     def free_slots(self) -> List[int]:
         held = {s for s, _, _ in self.filling} | {k for ks in self._fill_kids.values() for k in ks}
@@ -515,6 +537,8 @@ class ContinuousBatcher:
                 self.engine.set_row_ngram(s, None)
             if self._row_stop.pop(s, None) is not None:
                 self.engine.set_row_stop(s, None)
+            if self._row_stream.pop(s, None) is not None:
+                self.engine.set_row_stream(s, False)
 
     def _set_rows(self, s, r, index: int = 0):
         """per-row parameters of request r on slot s; they apply from the first token the prefill selects.  index: the sequence of a
@@ -552,6 +576,11 @@ class ContinuousBatcher:
             self.engine.set_row_stop(s, h, int(getattr(r.rules, "min_tokens", 0) or 0))
         elif self._row_stop.pop(s, None) is not None:
             self.engine.set_row_stop(s, None)
+        if r.stream is not None:                     # the stream likewise: the first token is delivered by the drain after the prefill
+            self._row_stream[s] = True
+            self.engine.set_row_stream(s, True)
+        elif self._row_stream.pop(s, None) is not None:
+            self.engine.set_row_stream(s, False)
 
     def _prefill(self, group, rows_set: bool = False):
         # image rows are consumed in packed order, so sequences with images keep their relative order: pack the group as is
@@ -633,6 +662,7 @@ class ContinuousBatcher:
                 self.running[k] = (rid, r)
                 self._admit_count += 1
                 self._admit_seq[k] = self._admit_count
+                self._streamed.pop(k, None)
                 self._last_lens[k] = 0               # a reused slot must not inherit its previous occupant's length (_soon_free counted a
                                                      # just-admitted long request as "about to finish" and the look-ahead group was sized for slots that stayed busy)
                 if r.seqs > 1:
@@ -775,12 +805,24 @@ class ContinuousBatcher:
 
     # ------------------------------------------------------------------ main loop
     def _collect(self) -> List[Tuple[int, Request, np.ndarray]]:
-        fin, lens = self.engine.slots_poll()
+        for rid in sorted(self._cancel & {rid for rid, _ in self.running.values()}):      # cancelled while they were being admitted
+            self.cancel(rid)
+        # one drain for every streaming row's new tokens while anything streams, else the plain poll
+        deltas = {}
+        if any(r.stream is not None for _, r in self.running.values()):
+            fin, lens, deltas = self.engine.slots_drain()
+        else:
+            fin, lens = self.engine.slots_poll()
         done = [(rid, r, r.outputs[0]) for rid, r in self._scored]
         self._scored = []
         for s in sorted(self.running):
             if s not in self.running:                # a slot of a beam group that has just been reported
                 continue
+            if self.running[s][1].stream is not None and fin[s] != 1 and s in deltas:
+                rid, req = self.running[s]
+                toks, entries = deltas[s]
+                self._streamed[s] = self._streamed.get(s, 0) + len(toks)
+                req.stream(rid, self._seq_index.get(s, 0), toks, entries, False)
             if self.running[s][1].num_beams:
                 out = self._collect_beam(s, bool(fin[s] == 1))
                 if out is not None:
@@ -803,6 +845,12 @@ class ContinuousBatcher:
                 hit = None
                 if req.stop is not None:             # read before the release clears the row's automaton and its hit record
                     hit = self.engine.row_stop_hit(s)
+                if req.stream is not None:
+                    # its last tokens, before it is reported: what the drain brought, and — a row that held more than one drain
+                    # delivers — the rest of what was just read
+                    sent = self._streamed.pop(s, 0)
+                    entries = None if lp_out is None else tuple(a[sent:] for a in lp_out)
+                    req.stream(rid, self._seq_index.get(s, 0), np.asarray(toks[sent:], np.int32), entries, True)
                 if req.seqs == 1:
                     if req.stop is not None:
                         req.stop_hit = hit
@@ -828,6 +876,7 @@ class ContinuousBatcher:
                 self.engine.slot_release(s)
                 self._row_guide.pop(s, None)         # the release cleared the row's guide: its handle is free to be evicted
                 self._row_stop.pop(s, None)          # and its stop strings
+                self._row_stream.pop(s, None)        # and its stream
         self._last_lens = {s: int(lens[s]) for s in self.running}      # after the finished slots have left: only what is still decoding
         return done
 
@@ -859,7 +908,57 @@ class ContinuousBatcher:
         refused at admission comes back at once with no tokens and `request.error` set (RequestRejected)."""
         out = self._step()
         rejected, self._rejected = self._rejected, []
-        return [(rid, r, np.zeros(0, np.int32)) for rid, r in rejected] + out
+        cancelled, self._cancelled = self._cancelled, []
+        return [(rid, r, np.zeros(0, np.int32)) for rid, r in rejected] + cancelled + out
+
+    # ------------------------------------------------------------------ cancellation (DESIGN §6.15)
+    def cancel(self, rid: int) -> bool:
+        """Stop request `rid` wherever it is.  Pending: it leaves the queue.  Running or suspended: its slots, their pages (parked host
+        pages too) and row handles go back.  Inside a chunked fill or a prefetched group: flagged, and cancelled by the first collect
+        that sees it running.  A member of an n group cancels the group.  The request is reported once by step(), with
+        request.cancelled = True and the tokens it had (outputs in index order for several sequences).  -> whether rid was found"""
+        for i, (pid, r) in enumerate(self.pending):
+            if pid == rid:
+                del self.pending[i]
+                self._unlease([rid])
+                self._cancel.discard(rid)
+                self._report_cancelled(rid, r, [np.zeros(0, np.int32) for _ in range(r.seqs)])
+                return True
+        slots = sorted(s for s, (k, _) in self.running.items() if k == rid)
+        if not slots:
+            if any(k == rid for _, k, _ in self.filling) or any(k == rid for k, _ in self._ahead):
+                self._cancel.add(rid)
+                return True
+            return False
+        self._cancel.discard(rid)
+        req = self.running[slots[0]][1]
+        _, lens = self.engine.slots_poll()
+        parts = dict(getattr(req, "_parts", {}))     # the sequences of an n group that had finished already: (tokens, ...)
+        outs = {j: t[0] for j, t in parts.items()}
+        for s in slots:
+            if not req.num_beams:
+                outs[self._seq_index.get(s, 0)] = self.engine.slot_read(s, int(lens[s]))
+        for s in slots:
+            if not req.num_beams or s == slots[0]:   # one slot of a beam group releases all of them
+                self.engine.slot_release(s)
+            del self.running[s]
+            for d in (self._admit_seq, self._seq_index, self._last_lens, self._streamed, self._parked_pages, self._row_guide, self._row_stop):
+                d.pop(s, None)
+            if s in self.suspended:
+                self.suspended.remove(s)
+        self._clear_rows(slots)                      # the release switched the rows off: the handles' records go too
+        if hasattr(req, "_parts"):
+            del req._parts
+        self._report_cancelled(rid, req, [outs.get(j, np.zeros(0, np.int32)) for j in range(max(1, req.seqs if not req.num_beams else 1))])
+        return True
+
+    def _report_cancelled(self, rid: int, req: Request, outs):
+        req.cancelled = True
+        req.kv_truncated = False
+        if len(outs) > 1:
+            req.outputs = outs
+            req.kv_truncated_each = [False] * len(outs)
+        self._cancelled.append((rid, req, outs[0]))
 
     # ------------------------------------------------------------------ preemption (DESIGN §6.10)
     def _active(self) -> List[int]:

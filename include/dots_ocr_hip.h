@@ -601,6 +601,27 @@ int dots_slots_decode(DotsEngine* e, int n_steps);
 int dots_slots_poll(DotsEngine* e, int32_t* finished_host, int32_t* out_lens_host);
 int dots_slot_read(DotsEngine* e, int slot, int32_t* out_ids_host, int capacity, int32_t* n_out);
 int dots_slot_release(DotsEngine* e, int slot);
+/* ---- Streaming: every streaming row's NEW tokens and logprob entries per scheduler chunk, in one launch and one stream
+ * synchronisation however many rows stream.
+ *
+ * dots_set_row_stream   a row setting like dots_set_row_logprobs: set before the slot's prefill (or fork), switched off by
+ *                       dots_slot_release and dots_slots_reset.  The row's cursor — the number of its output tokens already delivered —
+ *                       starts at 0 wherever the engine starts the slot's output: an admission, a fork child, dots_slots_extend /
+ *                       dots_slots_score.  DOTS_E_STATE for a row of a beam group (a group's outputs are reordered).  The first call
+ *                       allocates the cursors and a pinned staging block; an engine that never streams allocates and launches nothing.
+ * dots_slots_drain      a superset of dots_slots_poll: the same finished / out_lens and the same host-side effects, and for every
+ *                       streaming row b the tokens out_ids[b][cursor, out_len), at most DOTS_STREAM_ROW_CAP of them (the oldest; the rest
+ *                       come with the next drain), packed in slot order: tokens[first[b] .. first[b] + count[b]).  Rows that also return
+ *                       logprobs get the matching entries in the layout of dots_row_logprobs behind lp_first[b] (-1: none).  The cursor
+ *                       advances by what was delivered.  A suspended row delivers what it held at the suspend; a row that does not
+ *                       stream, a free and a filling slot deliver nothing.  tokens_cap / lp_cap (entries) must hold
+ *                       DOTS_STREAM_ROW_CAP per streaming row (per streaming row with logprobs): max_batch x DOTS_STREAM_ROW_CAP always
+ *                       does.  With no streaming row the call IS dots_slots_poll.  Never part of a captured step. */
+#define DOTS_STREAM_ROW_CAP 256
+int dots_set_row_stream(DotsEngine* e, int row, int on);
+int dots_slots_drain(DotsEngine* e, int32_t* finished_host, int32_t* out_lens_host, int32_t* first_host, int32_t* count_host, int32_t* lp_first_host,
+                     int32_t* tokens_host, int tokens_cap, float* tok_lp_host, int32_t* top_ids_host, float* top_lp_host, int lp_cap,
+                     int32_t* n_tokens, int32_t* n_lp);
 /* ---- Beam search: a group of B beams, 2 <= B <= DOTS_MAX_BEAMS, over shared KV pages.  These are vLLM's beam-search
  * semantics with HF's length normalisation applied by the caller; they are not HF's BeamSearchScorer.
  *
