@@ -301,13 +301,11 @@ E_INVALID, E_HIP, E_STATE, E_CAPACITY = -1, -2, -3, -4      # include/dots_ocr_h
 _SIGNATURES_SET = False
 
 
-def _prototypes(lib):
-    global _SIGNATURES_SET
-    if _SIGNATURES_SET:
-        return
+def _signatures() -> dict:
+    """every symbol the library exports -> (result type, argument types): the one list of them (EXPORTED_SYMBOLS are its keys)"""
     vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
     P = C.POINTER
-    sig = {
+    return {
         "dots_create": (i32, [P(CDotsConfig), i32, P(vp)]),
         "dots_destroy": (None, [vp]),
         "dots_last_error": (C.c_char_p, [vp]),
@@ -427,42 +425,22 @@ def _prototypes(lib):
         "dots_probe_grid_barrier": (i32, [i32, i32, i32, i32, i32, P(f32), P(i32)]),
         "dots_probe_cu_mask": (i32, [P(C.c_uint32), i32, i32, i32, i32, P(C.c_uint32)]),
     }
-    for name, (res, args) in sig.items():
+
+
+def _prototypes(lib):
+    global _SIGNATURES_SET
+    if _SIGNATURES_SET:
+        return
+    for name, (res, args) in _signatures().items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
     _SIGNATURES_SET = True
 
 
-EXPORTED_SYMBOLS = [
-    "dots_create", "dots_destroy", "dots_last_error", "dots_stream", "dots_load_weight", "dots_finalize_weights",
-    "dots_vit_forward", "dots_vit_prefetch", "dots_vit_take_prefetched", "dots_vit_prefetch_ready", "dots_preprocess_image", "dots_prefill", "dots_decode_step", "dots_generate", "dots_set_sampling", "dots_set_decode_plan", "dots_set_gemm_plan", "dots_tower_tail", "dots_get_logits",
-    "dots_set_eos", "dots_slots_prefill", "dots_slots_decode", "dots_slots_poll", "dots_set_row_stream", "dots_slots_drain", "dots_slot_read", "dots_slot_release", "dots_kv_pool_info", "dots_slot_capacity", "dots_slots_reset",
-    "dots_kv_swap_reserve", "dots_kv_swap_info", "dots_slot_suspend", "dots_slot_resume", "dots_slots_pages_short",
-    "dots_set_next_tokens", "dots_get_last_tokens", "dots_get_stats", "dots_synchronize", "dots_debug_capture_hidden",
-    "dots_debug_read_hidden", "dots_dev_alloc",
-    "dots_dev_free", "dots_memcpy_h2d", "dots_memcpy_d2h", "dots_op_rmsnorm", "dots_op_layernorm", "dots_op_gemm", "dots_op_quant_fp8", "dots_op_gemm_fp8",
-    "dots_op_flash_attn", "dots_plan_flash_xcd", "dots_op_qkv_rope_split", "dots_op_qkv_proj_rope", "dots_op_dec_qkv", "dots_op_decode_attn", "dots_op_dec_proj", "dots_op_dec_gateup",
-    "dots_op_dec_lmhead", "dots_probe_mfma", "dots_probe_grid_barrier", "dots_probe_cu_mask",
-    "dots_set_kv_scales", "dots_debug_read_kv", "dots_op_dec_qkv_kv8", "dots_op_decode_attn_kv8",
-    "dots_set_row_sampling", "dots_op_select_tokens", "dots_bench_select_tokens",
-    "dots_set_row_logprobs", "dots_row_logprobs", "dots_op_logprobs", "dots_bench_logprobs",
-    "dots_set_row_logit_rules", "dots_op_select_tokens_rules", "dots_bench_select_tokens_rules",
-    "dots_set_token_bytes", "dots_guide_create", "dots_guide_destroy", "dots_set_row_guide", "dots_row_guide_state",
-    "dots_op_select_tokens_guided", "dots_bench_select_tokens_guided",
-    "dots_set_row_ngram", "dots_op_select_tokens_ngram", "dots_bench_select_tokens_ngram",
-    "dots_set_speculation", "dots_set_speculation_rows", "dots_set_row_drafts", "dots_spec_stats", "dots_op_ngram_draft",
-    "dots_set_speculation_guided", "dots_op_spec_guide_masks", "dots_set_speculation_shaped", "dots_set_speculation_logprobs",
-    "dots_slots_fork", "dots_slots_extend", "dots_slot_logits",
-    "dots_slots_beam", "dots_beam_info", "dots_beam_read",
-    "dots_stop_create", "dots_stop_destroy", "dots_set_row_stop", "dots_row_stop_hit",
-    "dots_op_flash_attn_paged", "dots_slots_prefill_begin", "dots_slots_prefill_advance",
-    "dots_prefix_cache_enable", "dots_prefix_cache_lookup", "dots_prefix_cache_release", "dots_slots_prefill_begin_cached", "dots_prefix_cache_info",
-    "dots_slots_score", "dots_slot_scores",
-]
+EXPORTED_SYMBOLS = list(_signatures())
 
-MAX_SPEC_DRAFTS = 15                         # DOTS_MAX_SPEC_DRAFTS: drafts per slot and step
-MAX_NGRAM_SIZE = 64                          # DOTS_MAX_NGRAM_SIZE: longest n-gram the drafter looks up
+MAX_SPEC_DRAFTS = 15                         # DOTS_MAX_SPEC_DRAFTS: drafts per slot and step; the drafter looks up n-grams of up to MAX_NGRAM_SIZE
 
 
 def ngram_draft(history: Sequence[int], k: int, min_n: int = 2, max_n: int = 4) -> list:
@@ -1080,6 +1058,35 @@ class Engine:
         set_speculation."""
         self._ck(self.lib.dots_set_speculation_logprobs(self.h, 1 if on else 0), "dots_set_speculation_logprobs")
         self.spec_logprobs = bool(on)
+
+    @staticmethod
+    def speculation_on(engine, k: int, min_n: int = 2, max_n: int = 4, rows: int = 0, guided: bool = False, logprobs: bool = False, shaped: int = 0):
+        """Speculation and the row classes that may speculate, switched on together while no slot is occupied: set_speculation(k, min_n,
+        max_n), then rows (SPEC_ROWS bits), guided, logprobs and shaped (SPEC_SHAPED bits) — a setter is called only where its setting is
+        not the default, so `engine` may be a stand-in that lacks the others.  speculation_off with the same settings undoes it."""
+        engine.set_speculation(k, int(min_n), int(max_n))
+        if rows:
+            engine.set_speculation_rows(sampled=bool(rows & SPEC_ROWS["sampled"]), stop=bool(rows & SPEC_ROWS["stop"]))
+        if guided:
+            engine.set_speculation_guided(True)
+        if logprobs:
+            engine.set_speculation_logprobs(True)
+        if shaped:
+            engine.set_speculation_shaped(ngram=bool(shaped & SPEC_SHAPED["ngram"]), rules=bool(shaped & SPEC_SHAPED["rules"]),
+                                          penalties=bool(shaped & SPEC_SHAPED["penalties"]))
+
+    @staticmethod
+    def speculation_off(engine, rows: int = 0, guided: bool = False, logprobs: bool = False, shaped: int = 0):
+        """the inverse of speculation_on: every setting it changed goes back to its default"""
+        engine.set_speculation(0)
+        if rows:
+            engine.set_speculation_rows()
+        if guided:
+            engine.set_speculation_guided(False)
+        if logprobs:
+            engine.set_speculation_logprobs(False)
+        if shaped:
+            engine.set_speculation_shaped()
 
     def spec_guide_masks_op(self, guides: Sequence[Optional[int]], states: Sequence[int], drafts: Sequence[Sequence[int]], n_live: Sequence[int], k: int):
         """The state chain and the draft-row mask kernels alone (dots_op_spec_guide_masks) for `rows` slots: guide handle (None = an

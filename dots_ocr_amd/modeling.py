@@ -11,13 +11,15 @@ There is no CPU fallback — constructing the model without the built library or
 from __future__ import annotations
 
 import os
+from dataclasses import dataclass
 from pathlib import Path
 from typing import Optional, Sequence
 
 import numpy as np
 
 from .config import DotsConfig
-from .engine import Engine
+from .engine import SPEC_ROWS, Engine, LogitRules, NgramRule, SamplingParams, spec_rows_flags, spec_shaped_flags
+from .row_features import apply_row, clear_rows
 from .weights import load_state_dict, random_state_dict
 
 
@@ -70,6 +72,21 @@ def split_kv_scales(state_dict, num_layers: int, num_kv_heads: int):
         else:
             rest[n] = t
     return rest, scales
+
+
+@dataclass
+class CallSettings:
+    """What one generate() call gives every sequence besides its SamplingParams, and how the call runs: _generate's one record."""
+    rules: Optional[LogitRules] = None           # the same LogitRules, guide handle, NgramRule and stop strings on every row
+    guide: Optional[int] = None
+    ngram: Optional[NgramRule] = None
+    stop: Optional[tuple] = None
+    nrs: int = 1                                 # num_return_sequences
+    beam: Optional[tuple] = None                 # (num_beams, length_penalty)
+    suffixes: Optional[list] = None              # prompt_suffixes
+    prefill_chunk: Optional[int] = None
+    image_keys: Optional[list] = None            # one entry per sequence when prefix caching is on, else None
+    streamer: object = None
 
 
 class DotsOcrHipForCausalLM:
@@ -298,51 +315,31 @@ class DotsOcrHipForCausalLM:
             if not hasattr(self.engine, "slots_extend"):
                 raise ValueError("this engine cannot extend a live sequence (no slots_extend)")
             continuous = True
-        row_sp = None
-        if (top_k or 0) > 0 or repetition_penalty not in (None, 1.0) or (frequency_penalty or 0.0) != 0.0 or (presence_penalty or 0.0) != 0.0:
-            from .engine import SamplingParams
-            base = SamplingParams(temperature=t_eff, top_p=p_eff, top_k=int(top_k or 0),
+        def call_params():                       # the call's SamplingParams, the seed of sequence 0; built at most once
+            return SamplingParams(temperature=t_eff, top_p=p_eff, top_k=int(top_k or 0),
                                   repetition_penalty=1.0 if repetition_penalty is None else float(repetition_penalty),
                                   frequency_penalty=float(frequency_penalty or 0.0), presence_penalty=float(presence_penalty or 0.0), seed=seed)
-
-            def row_sp(b):
-                return dataclasses.replace(base, seed=int(seed) + b)
+        base = None
+        if (top_k or 0) > 0 or repetition_penalty not in (None, 1.0) or (frequency_penalty or 0.0) != 0.0 or (presence_penalty or 0.0) != 0.0:
+            base = call_params()
         rules = None
         if logit_bias or allowed_token_ids is not None or int(min_tokens or 0) > 0 or stop_token_ids or ignore_eos:
-            from .engine import LogitRules, SamplingParams
             rules = LogitRules(bias={int(k): float(v) for k, v in dict(logit_bias or {}).items()}, allowed=allowed_token_ids,
                                min_tokens=int(min_tokens or 0), stop=tuple(stop_token_ids or ()), ignore_eos=bool(ignore_eos),
                                vocab_size=self.config.vocab_size,
                                eos_ids=self.config.eos_token_ids if eos_token_id is None else
                                ([eos_token_id] if isinstance(eos_token_id, int) else list(eos_token_id)))
-            if row_sp is None:                   # a sampled row with rules draws with seed + b as the penalised rows do
-                base = SamplingParams(temperature=t_eff, top_p=p_eff, seed=seed)
-
-                def row_sp(b):
-                    return dataclasses.replace(base, seed=int(seed) + b)
         from .guided import compile_request
         guide_obj = compile_request(guided_regex, guided_choice, guided_json, whitespace=guided_whitespace_pattern)
         guide = None
         if guide_obj is not None:
             if getattr(self.engine, "token_bytes", None) is None:
                 raise ValueError("guided decoding needs the vocabulary's bytes: call engine.set_token_bytes(...) once (DotsOcrProcessor.token_bytes)")
-            if row_sp is None:                   # a sampled guided row draws with seed + b as the ruled rows do
-                from .engine import SamplingParams
-                base = SamplingParams(temperature=t_eff, top_p=p_eff, seed=seed)
-
-                def row_sp(b):
-                    return dataclasses.replace(base, seed=int(seed) + b)
             guide = self.engine.create_guide(guide_obj)
         ngram = None
         if no_repeat_ngram_size:
-            from .engine import NgramRule, SamplingParams
             ngram = NgramRule(no_repeat_ngram_size, no_repeat_ngram_window or 0, tuple(no_repeat_ngram_whitelist or ()),
                               vocab_size=self.config.vocab_size, max_seq_len=self.max_seq_len)
-            if row_sp is None:                   # a sampled n-gram row draws with seed + b as the ruled rows do
-                base = SamplingParams(temperature=t_eff, top_p=p_eff, seed=seed)
-
-                def row_sp(b):
-                    return dataclasses.replace(base, seed=int(seed) + b)
         elif no_repeat_ngram_window or no_repeat_ngram_whitelist:
             raise ValueError("no_repeat_ngram_window / no_repeat_ngram_whitelist need no_repeat_ngram_size")
         stop = None
@@ -351,27 +348,9 @@ class DotsOcrHipForCausalLM:
             stop = check_stop_strings(stop_strings)
             if getattr(self.engine, "token_bytes", None) is None:
                 raise ValueError("stop strings need the vocabulary's bytes: call engine.set_token_bytes(...) once (DotsOcrProcessor.token_bytes)")
-            if row_sp is None:                   # a sampled row with stop strings draws with seed + b as the ruled rows do
-                from .engine import SamplingParams
-                base = SamplingParams(temperature=t_eff, top_p=p_eff, seed=seed)
-
-                def row_sp(b):
-                    return dataclasses.replace(base, seed=int(seed) + b)
-        if suffixes is not None and t_eff > 0 and row_sp is None:      # sampled: suffix j draws with seed + j (the scheduler adds the index)
-            from .engine import SamplingParams
-            base = SamplingParams(temperature=t_eff, top_p=p_eff, seed=seed)
-
-            def row_sp(b):
-                return base
         if nrs > 1 and beam is None:
             continuous = True
-            from .engine import SamplingParams
-            per_seq = row_sp(0) if row_sp else SamplingParams(temperature=t_eff, top_p=p_eff, seed=seed)
-
-            def row_sp(b):                       # prompt b's sequences take seeds seed + b * n .. + n - 1 (the scheduler adds the index)
-                return dataclasses.replace(per_seq, seed=int(seed) + b * nrs)
         spec_k = int(speculative_ngram or 0)
-        from .engine import SPEC_ROWS, spec_rows_flags
         spec_rows = spec_rows_flags(speculative_rows)
         if spec_rows and not spec_k:
             raise ValueError("speculative_rows needs speculative_ngram")
@@ -379,51 +358,42 @@ class DotsOcrHipForCausalLM:
             raise ValueError("speculative_guided needs speculative_ngram")
         if speculative_logprobs and not spec_k:
             raise ValueError("speculative_logprobs needs speculative_ngram")
-        from .engine import SPEC_SHAPED, spec_shaped_flags
         spec_shaped = spec_shaped_flags(speculative_shaped)
         if spec_shaped and not spec_k:
             raise ValueError("speculative_shaped needs speculative_ngram")
-        if spec_k:
-            if continuous is False:
-                raise ValueError("speculative_ngram runs on the continuous path: continuous=False cannot be combined with it")
-            continuous = True
-            if (spec_rows & SPEC_ROWS["sampled"]) and t_eff > 0:
-                # the engine-wide sampler hashes the slot index and never speculates: the sequences take parameters of their own
-                if row_sp is None:
-                    from .engine import SamplingParams
-                    base = SamplingParams(temperature=t_eff, top_p=p_eff, seed=seed)
+        if spec_k and continuous is False:
+            raise ValueError("speculative_ngram runs on the continuous path: continuous=False cannot be combined with it")
+        # the engine-wide sampler hashes the slot index and never speculates: sampled sequences that may speculate take parameters of their own
+        spec_sampled = bool(spec_k and (spec_rows & SPEC_ROWS["sampled"]) and t_eff > 0)
+        # Does any setting of this call force per-row selection?  Penalties and top_k, every row feature (a sampled row that carries one
+        # draws with a seed of its own, as the penalised rows do), sampled suffixes, several sequences per prompt, sampled speculation.
+        # Sequence b then draws with seed + b; with num_return_sequences prompt b's sequences take seed + b * n .. + n - 1 and with
+        # suffixes the one prompt's take seed .. + m - 1 (the scheduler adds the index within a request to the seed it is given)
+        row_sp = None
+        if (base is not None or rules is not None or guide is not None or ngram is not None or stop is not None
+                or (suffixes is not None and t_eff > 0) or (nrs > 1 and beam is None) or spec_sampled):
+            base = call_params() if base is None else base
+            stride = 0 if suffixes is not None else nrs if nrs > 1 and beam is None else 1
 
-                    def row_sp(b):
-                        return dataclasses.replace(base, seed=int(seed) + b)
+            def row_sp(b):
+                return dataclasses.replace(base, seed=int(seed) + b * stride)
+        spec = dict(rows=spec_rows, guided=bool(speculative_guided), logprobs=bool(speculative_logprobs), shaped=spec_shaped)
+        if spec_k:
+            continuous = True
+            if spec_sampled:
                 self.engine.set_sampling(0.0, 1.0, 0)
             self.engine.slots_reset()            # speculation changes only while no slot is occupied
-            self.engine.set_speculation(spec_k, int(prompt_lookup_min), int(prompt_lookup_max))
-            if spec_rows:
-                self.engine.set_speculation_rows(sampled=bool(spec_rows & SPEC_ROWS["sampled"]), stop=bool(spec_rows & SPEC_ROWS["stop"]))
-            if speculative_guided:
-                self.engine.set_speculation_guided(True)
-            if speculative_logprobs:
-                self.engine.set_speculation_logprobs(True)
-            if spec_shaped:
-                self.engine.set_speculation_shaped(ngram=bool(spec_shaped & SPEC_SHAPED["ngram"]), rules=bool(spec_shaped & SPEC_SHAPED["rules"]),
-                                                   penalties=bool(spec_shaped & SPEC_SHAPED["penalties"]))
+            Engine.speculation_on(self.engine, spec_k, prompt_lookup_min, prompt_lookup_max, **spec)
+        call = CallSettings(rules=rules, guide=guide, ngram=ngram, stop=stop, nrs=nrs, beam=beam, suffixes=suffixes, prefill_chunk=prefill_chunk,
+                            image_keys=(image_keys or [None] * int(input_ids.shape[0])) if enable_prefix_caching else None, streamer=streamer)
         try:
             return self._generate(input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens, eos_token_id, pad_token_id, continuous,
-                                  row_sp, rules, guide, ngram, nrs, stop, int(min_tokens or 0), beam, suffixes, prefill_chunk,
-                                  (image_keys or [None] * int(input_ids.shape[0])) if enable_prefix_caching else None, streamer)
+                                  row_sp, call)
         finally:
             if spec_k:
                 try:
                     self.engine.slots_reset()
-                    self.engine.set_speculation(0)
-                    if spec_rows:
-                        self.engine.set_speculation_rows()
-                    if speculative_guided:
-                        self.engine.set_speculation_guided(False)
-                    if speculative_logprobs:
-                        self.engine.set_speculation_logprobs(False)
-                    if spec_shaped:
-                        self.engine.set_speculation_shaped()
+                    Engine.speculation_off(self.engine, **spec)
                 except Exception as e:               # the run's own error is the one to raise
                     import warnings
                     warnings.warn(f"speculation could not be switched off: {e}")
@@ -462,11 +432,13 @@ class DotsOcrHipForCausalLM:
         ContinuousBatcher(self.engine, eos_ids=self.config.eos_token_ids).run([req])
         return req.scores_out
 
-    def _generate(self, input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens, eos_token_id, pad_token_id, continuous, row_sp, rules,
-                  guide, ngram=None, nrs=1, stop=None, stop_min=0, beam=None, suffixes=None, prefill_chunk=None, image_keys=None, streamer=None):
+    def _generate(self, input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens, eos_token_id, pad_token_id, continuous, row_sp,
+                  call: CallSettings):
+        """row_sp: b -> the SamplingParams of sequence b, or None = the engine-wide setting; call: everything else the rows are given"""
         import torch
-        if suffixes:
-            nrs = len(suffixes)                      # the rows of the result: one per suffix, laid out as num_return_sequences lays them out
+        from .scheduler import ContinuousBatcher, Request
+        suffixes, beam, streamer, image_keys = call.suffixes, call.beam, call.streamer, call.image_keys
+        nrs = len(suffixes) if suffixes else call.nrs    # the rows of the result: one per suffix, laid out as num_return_sequences lays them out
         ids = input_ids.detach().cpu().numpy()
         B, T = ids.shape
         mask = attention_mask.detach().cpu().numpy().astype(bool) if attention_mask is not None else np.ones_like(ids, bool)
@@ -513,28 +485,27 @@ class DotsOcrHipForCausalLM:
         seq_patches = [int(sum(patch_off[g + 1] - patch_off[g] for g in img_of_seq[b])) for b in range(B)]
         if continuous is None:
             continuous = B > self.max_batch
+
+        def request(b, pix=None, g=None):        # sequence b with the call's row settings: what both paths give their rows
+            return Request(prompts[b], pix, g, max_new_tokens, sampling=row_sp(b) if row_sp else None, rules=call.rules, guide=call.guide,
+                           ngram=call.ngram, n=1 if suffixes else nrs, stop=call.stop, suffixes=suffixes)
         if continuous:
-            from .scheduler import ContinuousBatcher, Request
             reqs = []
             for b in range(B):
                 if img_of_seq[b]:
                     lo, hi = int(patch_off[img_of_seq[b][0]]), int(patch_off[img_of_seq[b][-1] + 1])
-                    pix = pv_dev[lo:hi] if pv_dev is not None else pv_host[lo:hi]
-                    reqs.append(Request(prompts[b], pix, grid[img_of_seq[b][0]:img_of_seq[b][-1] + 1], max_new_tokens,
-                                        sampling=row_sp(b) if row_sp else None, rules=rules, guide=guide, ngram=ngram, n=1 if suffixes else nrs,
-                                        stop=stop, suffixes=suffixes))
+                    reqs.append(request(b, pv_dev[lo:hi] if pv_dev is not None else pv_host[lo:hi], grid[img_of_seq[b][0]:img_of_seq[b][-1] + 1]))
                     if image_keys and image_keys[b] is not None:      # the caller names the image; the grid it was resized to is part of what is cached
                         import hashlib
                         reqs[-1].image_key = hashlib.blake2b(bytes(image_keys[b]) + reqs[-1].grid_thw.tobytes(), digest_size=16).digest()
                 else:
-                    reqs.append(Request(prompts[b], None, None, max_new_tokens, sampling=row_sp(b) if row_sp else None, rules=rules, guide=guide,
-                                        ngram=ngram, n=1 if suffixes else nrs, stop=stop, suffixes=suffixes))
+                    reqs.append(request(b))
                 if beam is not None:             # a group of beam[0] beams that returns its nrs best hypotheses
                     reqs[-1].n, reqs[-1].num_beams, reqs[-1].num_return, reqs[-1].length_penalty = 1, beam[0], nrs, beam[1]
             if streamer is not None:             # one sequence (generate() checked): the prompt, then every chunk's new ids, then end()
                 streamer.put(input_ids.detach().cpu())
                 reqs[0].stream = lambda rid, index, toks, lp, fin: len(toks) and streamer.put(torch.as_tensor(np.asarray(toks), dtype=torch.long))
-            chunk_kw = {} if prefill_chunk is None else {"prefill_chunk": prefill_chunk}
+            chunk_kw = {} if call.prefill_chunk is None else {"prefill_chunk": call.prefill_chunk}
             if image_keys is not None:           # enable_prefix_caching
                 chunk_kw["prefix_caching"] = True
             outs = ContinuousBatcher(self.engine, eos_ids=eos, **chunk_kw).run(reqs)
@@ -565,23 +536,13 @@ class DotsOcrHipForCausalLM:
             pix, g, on_dev = pixels_of(plan[0])
             self.engine.vit_prefetch(pix, g, on_device=on_dev)
         prefetched = pipelined                   # a tower is in flight / waiting to be taken
-        rows_set = 0                             # rows given per-row parameters (cleared on the way out)
+        held = {}                                # what the rows of the static batches hold (cleared on the way out)
         try:
             for k, sl in enumerate(plan):
-                if rules is not None:
+                if call.rules is not None:
                     self.engine.set_eos(eos)         # the engine checks a row's rules against the EOS ids of THIS call
-                if row_sp:
-                    for j, b in enumerate(sl):
-                        self.engine.set_row_sampling(j, row_sp(b))
-                        if rules is not None:
-                            self.engine.set_row_logit_rules(j, rules)
-                        if guide is not None:
-                            self.engine.set_row_guide(j, guide)
-                        if ngram is not None:
-                            self.engine.set_row_ngram(j, ngram)
-                        if stop is not None:
-                            self.engine.set_row_stop(j, self.engine.create_stop(stop), stop_min)
-                    rows_set = max(rows_set, len(sl))
+                for j, b in enumerate(sl):
+                    apply_row(self.engine, held, j, request(b))
                 lens = np.array([len(prompts[b]) for b in sl], np.int32)
                 packed = np.concatenate([prompts[b] for b in sl])
                 pix, g, on_dev = pixels_of(sl)
@@ -608,16 +569,7 @@ class DotsOcrHipForCausalLM:
                     pass
             raise
         finally:
-            for j in range(rows_set):
-                self.engine.set_row_sampling(j, None)
-                if rules is not None:
-                    self.engine.set_row_logit_rules(j, None)
-                if guide is not None:
-                    self.engine.set_row_guide(j, None)
-                if ngram is not None:
-                    self.engine.set_row_ngram(j, None)
-                if stop is not None:
-                    self.engine.set_row_stop(j, None)
+            clear_rows(self.engine, held, sorted(held))
         full = np.concatenate([np.repeat(ids.astype(np.int64), nrs, axis=0), new_tokens[:, :n_max]], axis=1)    # HF stops at the longest sequence
         res = torch.from_numpy(full)
         return res.to(input_ids.device) if input_ids.is_cuda else res

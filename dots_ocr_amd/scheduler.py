@@ -17,6 +17,8 @@ from typing import Deque, Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from .row_features import FEATURES, ROW_FEATURES, apply_row, cancel_rows, clear_rows, engine_takes, release_row
+
 
 def split_common_prefix(seqs: Sequence[Sequence[int]]) -> Tuple[List[int], List[List[int]]]:
     """(prefix, suffixes) of several token sequences: their longest common prefix, cut back so that every suffix keeps at least one
@@ -185,13 +187,7 @@ class ContinuousBatcher:
         self.decode_steps = 0
         self.admissions = 0
         self._last_lens: Dict[int, int] = {}                     # slot -> tokens generated as of the last poll
-        self._row_params: Dict[int, object] = {}                 # slot -> the SamplingParams set on it (engine.set_row_sampling)
-        self._row_lp: Dict[int, int] = {}                        # slot -> the logprobs top_n set on it (engine.set_row_logprobs)
-        self._row_rules: Dict[int, object] = {}                  # slot -> the LogitRules set on it (engine.set_row_logit_rules)
-        self._row_guide: Dict[int, int] = {}                     # slot -> the guide handle set on it (engine.set_row_guide)
-        self._row_ngram: Dict[int, object] = {}                  # slot -> the NgramRule set on it (engine.set_row_ngram)
-        self._row_stop: Dict[int, int] = {}                      # slot -> the stop automaton handle set on it (engine.set_row_stop)
-        self._row_stream: Dict[int, bool] = {}                   # slot -> its stream is switched on (engine.set_row_stream)
+        self._rows: Dict[int, Dict[str, object]] = {}            # slot -> feature name -> the value set on it (row_features.ROW_FEATURES)
         self._streamed: Dict[int, int] = {}                      # streaming slot -> tokens of its sequence handed to the callback so far
         self._cancel: set = set()                                # request ids cancelled while being admitted: cancelled by the first collect that sees them running
         self._cancelled: List[Tuple[int, Request, np.ndarray]] = []   # cancelled requests (reported by step())
@@ -244,15 +240,10 @@ class ContinuousBatcher:
             self._check_beam(req)
         if req.n > 1 and not hasattr(self.engine, "slots_fork"):
             raise ValueError("this engine cannot fork a prefilled sequence (no slots_fork): n > 1 is not available")
-        if req.rules is not None and not hasattr(self.engine, "set_row_logit_rules"):
-            raise ValueError("this engine cannot honour logit rules (no set_row_logit_rules)")
-        if req.guide is not None and not hasattr(self.engine, "set_row_guide"):
-            raise ValueError("this engine cannot honour a guide (no set_row_guide)")
-        if req.ngram is not None and not hasattr(self.engine, "set_row_ngram"):
-            raise ValueError("this engine cannot honour an n-gram rule (no set_row_ngram)")
+        for f in ROW_FEATURES:
+            if f.noun and getattr(req, f.name) is not None and not engine_takes(self.engine, f):
+                raise ValueError(f"this engine cannot honour {f.noun} (no {f.setter})")
         if req.stop is not None:
-            if not hasattr(self.engine, "set_row_stop"):
-                raise ValueError("this engine cannot honour stop strings (no set_row_stop)")
             from .stop_strings import check_stop_strings
             try:
                 req.stop = check_stop_strings(req.stop)
@@ -351,7 +342,7 @@ class ContinuousBatcher:
             raise RequestRejected("a beam request cannot stream: a group's outputs are reordered until it ends")
         if req.score is not None:
             raise RequestRejected("a score request generates nothing and cannot stream")
-        if not all(hasattr(self.engine, f) for f in ("slots_drain", "set_row_stream")):
+        if not engine_takes(self.engine, FEATURES["stream"]):
             raise ValueError("this engine cannot stream (no slots_drain): stream is not available")
 
     def _check_beam(self, req: Request):
@@ -524,63 +515,12 @@ class ContinuousBatcher:
 
     def _clear_rows(self, slots):
         """no per-row entry stays on these (free) slots: it would keep the per-row stage on"""
-        for s in slots:
-            if self._row_params.pop(s, None) is not None:
-                self.engine.set_row_sampling(s, None)
-            if self._row_lp.pop(s, None) is not None:
-                self.engine.set_row_logprobs(s, None)
-            if self._row_rules.pop(s, None) is not None:
-                self.engine.set_row_logit_rules(s, None)
-            if self._row_guide.pop(s, None) is not None:
-                self.engine.set_row_guide(s, None)
-            if self._row_ngram.pop(s, None) is not None:
-                self.engine.set_row_ngram(s, None)
-            if self._row_stop.pop(s, None) is not None:
-                self.engine.set_row_stop(s, None)
-            if self._row_stream.pop(s, None) is not None:
-                self.engine.set_row_stream(s, False)
+        clear_rows(self.engine, self._rows, slots)
 
     def _set_rows(self, s, r, index: int = 0):
         """per-row parameters of request r on slot s; they apply from the first token the prefill selects.  index: the sequence of a
         request with n > 1 — its seed is the request's + index (vLLM's rule), everything else is shared"""
-        if r.sampling is not None:
-            import dataclasses
-            sp = r.sampling if index == 0 else dataclasses.replace(r.sampling, seed=int(r.sampling.seed) + index)
-            self._row_params[s] = sp                 # recorded first: a call that raises half way is still cleared
-            self.engine.set_row_sampling(s, sp)
-        elif self._row_params.pop(s, None) is not None:
-            self.engine.set_row_sampling(s, None)
-        if r.logprobs is not None:                   # logprobs likewise, the prefill's token included
-            self._row_lp[s] = r.logprobs
-            self.engine.set_row_logprobs(s, r.logprobs)
-        elif self._row_lp.pop(s, None) is not None:
-            self.engine.set_row_logprobs(s, None)
-        if r.rules is not None:                      # logit rules likewise
-            self._row_rules[s] = r.rules
-            self.engine.set_row_logit_rules(s, r.rules)
-        elif self._row_rules.pop(s, None) is not None:
-            self.engine.set_row_logit_rules(s, None)
-        if r.guide is not None:                      # the guide likewise: the row is set before its prefill, which starts the automaton
-            self._row_guide[s] = r.guide
-            self.engine.set_row_guide(s, r.guide)
-        elif self._row_guide.pop(s, None) is not None:
-            self.engine.set_row_guide(s, None)
-        if r.ngram is not None:                      # the n-gram rule likewise; it needs no reset, the row's output starts empty
-            self._row_ngram[s] = r.ngram
-            self.engine.set_row_ngram(s, r.ngram)
-        elif self._row_ngram.pop(s, None) is not None:
-            self.engine.set_row_ngram(s, None)
-        if r.stop is not None:                       # the stop strings likewise: the prefill starts the automaton over and walks its first token
-            h = self.engine.create_stop(r.stop)      # cached by the engine per tuple of strings
-            self._row_stop[s] = h
-            self.engine.set_row_stop(s, h, int(getattr(r.rules, "min_tokens", 0) or 0))
-        elif self._row_stop.pop(s, None) is not None:
-            self.engine.set_row_stop(s, None)
-        if r.stream is not None:                     # the stream likewise: the first token is delivered by the drain after the prefill
-            self._row_stream[s] = True
-            self.engine.set_row_stream(s, True)
-        elif self._row_stream.pop(s, None) is not None:
-            self.engine.set_row_stream(s, False)
+        apply_row(self.engine, self._rows, s, r, index)
 
     def _prefill(self, group, rows_set: bool = False):
         # image rows are consumed in packed order, so sequences with images keep their relative order: pack the group as is
@@ -871,12 +811,7 @@ class ContinuousBatcher:
                         req.kv_truncated = any(req.kv_truncated_each)
                         del req._parts
                         done.append((rid, req, req.outputs[0]))
-                if self._row_ngram.pop(s, None) is not None:     # the rule leaves with its request (the engine's release clears the row too)
-                    self.engine.set_row_ngram(s, None)
-                self.engine.slot_release(s)
-                self._row_guide.pop(s, None)         # the release cleared the row's guide: its handle is free to be evicted
-                self._row_stop.pop(s, None)          # and its stop strings
-                self._row_stream.pop(s, None)        # and its stream
+                release_row(self.engine, self._rows, s, self.engine.slot_release)    # each feature by its release rule (row_features)
         self._last_lens = {s: int(lens[s]) for s in self.running}      # after the finished slots have left: only what is still decoding
         return done
 
@@ -942,11 +877,11 @@ class ContinuousBatcher:
             if not req.num_beams or s == slots[0]:   # one slot of a beam group releases all of them
                 self.engine.slot_release(s)
             del self.running[s]
-            for d in (self._admit_seq, self._seq_index, self._last_lens, self._streamed, self._parked_pages, self._row_guide, self._row_stop):
+            for d in (self._admit_seq, self._seq_index, self._last_lens, self._streamed, self._parked_pages):
                 d.pop(s, None)
             if s in self.suspended:
                 self.suspended.remove(s)
-        self._clear_rows(slots)                      # the release switched the rows off: the handles' records go too
+        cancel_rows(self.engine, self._rows, slots)  # the release switched the rows off: the handles' records go too
         if hasattr(req, "_parts"):
             del req._parts
         self._report_cancelled(rid, req, [outs.get(j, np.zeros(0, np.int32)) for j in range(max(1, req.seqs if not req.num_beams else 1))])

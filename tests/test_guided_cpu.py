@@ -11,6 +11,7 @@ import pytest
 
 from dots_ocr_amd import guided as G
 from dots_ocr_amd.config import DotsConfig
+from dots_ocr_amd.row_features import rows_holding
 
 GOLDEN = Path(__file__).parent / "golden"
 
@@ -344,7 +345,7 @@ def test_scheduler_sets_the_guide_before_the_prefill_and_clears_it():
     out = cb.run([Request(np.array([1 + i, 2], np.int32), max_new_tokens=3, guide=h if i % 2 == 0 else None) for i in range(4)])
     assert [list(o) for o in out] == [[5, 6, 7]] * 4
     assert order[0] == ("prefill", [h, None])                # rows are set before their prefill
-    assert eng.row_guides == {} and cb._row_guide == {}      # and nothing stays behind
+    assert eng.row_guides == {} and rows_holding(cb._rows, "guide") == []      # and nothing stays behind
     eng.destroy_guide(h)
     with pytest.raises(ValueError):                          # an engine without the call
         ContinuousBatcher(FakeSlotEngine(lambda p: [5], max_batch=2, max_prefill_tokens=64)).submit(Request(np.array([1, 2], np.int32), guide=0))

@@ -9,6 +9,7 @@ import pytest
 
 from dots_ocr_amd.config import DotsConfig
 from dots_ocr_amd.engine import MAX_LOGIT_BIAS, MAX_STOP_IDS, LogitRules
+from dots_ocr_amd.row_features import rows_holding
 
 
 # ---------------------------------------------------------------------------------------------------- LogitRules
@@ -147,7 +148,7 @@ def test_scheduler_clears_rules_when_the_prefill_fails():
     cb.submit(Request(np.array([1, 2], np.int32), max_new_tokens=3, rules=r))
     with pytest.raises(RuntimeError):
         cb.step()
-    assert eng.rules == {} and cb._row_rules == {}
+    assert eng.rules == {} and rows_holding(cb._rows, "rules") == []
     assert eng.rule_calls == [(0, r), (0, None)]
 
 
@@ -191,7 +192,7 @@ def test_a_request_the_engine_refuses_fails_alone():
         assert getattr(done[i][0], "error", None) is None
         assert done[i][1] == ([5, 6, 7] if r.rules is not None else [5, 6, 7, 8])
     # nothing of the refused request stayed on its slot: its sampling entry was taken back, no rules are left anywhere
-    assert eng.rules == {} and cb._row_rules == {} and cb._row_params == {}
+    assert eng.rules == {} and rows_holding(cb._rows, "rules") == [] and rows_holding(cb._rows, "sampling") == []
     assert (1, "sampling", None) in eng.rule_calls
     assert not any(first == 99 for _, first, _ in eng.prefill_rules)          # it never reached the prefill
     with pytest.raises(RequestRejected):                     # run(): the others finish, then the refusal is raised

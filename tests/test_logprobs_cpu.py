@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from dots_ocr_amd.config import DotsConfig
+from dots_ocr_amd.row_features import rows_holding
 
 K = 20
 
@@ -101,7 +102,7 @@ def test_scheduler_clears_the_flag_when_the_prefill_fails():
     cb.submit(Request(np.array([1, 2], np.int32), max_new_tokens=3, logprobs=2))
     with pytest.raises(RuntimeError):
         cb.step()
-    assert eng.lp == {} and cb._row_lp == {}
+    assert eng.lp == {} and rows_holding(cb._rows, "logprobs") == []
     assert eng.lp_calls == [(0, 2), (0, None)]
 
 

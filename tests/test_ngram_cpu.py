@@ -7,6 +7,7 @@ import pytest
 
 from dots_ocr_amd.config import DotsConfig
 from dots_ocr_amd.engine import MAX_NGRAM_SIZE, MAX_NGRAM_WHITELIST, NgramRule, banned_ngram_ids
+from dots_ocr_amd.row_features import rows_holding
 
 
 # ---------------------------------------------------------------------------------------------------- the definition
@@ -124,7 +125,7 @@ def test_scheduler_sets_the_rule_before_the_prefill_and_clears_it_on_release():
     assert [c for c in eng.calls if c[0] == "release" and c[2] is not None] == []
     assert sum(1 for c in eng.calls if c[0] == "release") == len(reqs)
     assert [c[2] for c in eng.calls if c[0] == "set" and c[2] is not None] == [rules[0], rules[2]]
-    assert eng.ngram == {} and cb._row_ngram == {}
+    assert eng.ngram == {} and rows_holding(cb._rows, "ngram") == []
 
 
 def test_scheduler_without_a_rule_makes_no_ngram_calls():
@@ -148,7 +149,7 @@ def test_scheduler_clears_the_rule_when_the_prefill_fails():
     cb.submit(Request(np.array([1, 2], np.int32), max_new_tokens=3, ngram=r))
     with pytest.raises(RuntimeError):
         cb.step()
-    assert eng.ngram == {} and cb._row_ngram == {}
+    assert eng.ngram == {} and rows_holding(cb._rows, "ngram") == []
     assert eng.calls == [("set", 0, r), ("set", 0, None)]
 
 

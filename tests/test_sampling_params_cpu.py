@@ -12,6 +12,7 @@ import torch
 
 from dots_ocr_amd.config import DotsConfig
 from dots_ocr_amd.engine import CDotsSamplingParams, SamplingParams
+from dots_ocr_amd.row_features import rows_holding
 
 ROOT = Path(__file__).resolve().parent.parent
 
@@ -115,7 +116,7 @@ def test_scheduler_clears_row_parameters_when_the_prefill_fails():
     cb.submit(Request(np.array([1, 2], np.int32), max_new_tokens=3, sampling=SamplingParams(temperature=0.4, seed=2)))
     with pytest.raises(RuntimeError):
         cb.step()
-    assert eng.rows == {} and cb._row_params == {}          # no entry left on a slot that was never occupied
+    assert eng.rows == {} and rows_holding(cb._rows, "sampling") == []          # no entry left on a slot that was never occupied
     assert eng.row_calls[-1][1] is None
 
 

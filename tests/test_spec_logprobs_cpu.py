@@ -44,9 +44,15 @@ def test_server_flag_without_speculation_is_an_error():
 
 
 def test_server_main_switches_the_engine_on_only_with_the_flag():
+    """main hands the flag to Engine.speculation_on and touches the switch nowhere else; speculation_on calls the setter only when it is set"""
     src = (ROOT / "dots_ocr_amd" / "server.py").read_text()
-    assert re.search(r"if a\.speculative_logprobs:\n\s+model\.engine\.set_speculation_logprobs\(True\)", src)
-    assert len(re.findall(r"set_speculation_logprobs", src)) == 1
+    assert re.search(r"Engine\.speculation_on\(model\.engine, \*spec,[^\n]*\n[^\n]*\blogprobs=a\.speculative_logprobs\b", src)
+    assert "set_speculation_logprobs" not in src
+    for flag, calls in ((False, []), (True, [(True,)])):
+        e = RecEngine()
+        Engine.speculation_on(e, 3, 2, 4, logprobs=flag)
+        assert [c[1] for c in e.calls if c[0] == "set_speculation_logprobs"] == calls
+        assert [c[1] for c in e.calls if c[0] == "set_speculation"] == [(3, 2, 4)]
 
 
 # ---------------------------------------------------------------------------------------------------- Engine.set_speculation_logprobs

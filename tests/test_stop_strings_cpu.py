@@ -6,6 +6,7 @@ import torch
 
 from dots_ocr_amd.config import DotsConfig
 from dots_ocr_amd.engine import MAX_STOP_BYTES, MAX_STOP_IDS, MAX_STOP_STRINGS
+from dots_ocr_amd.row_features import rows_holding
 from dots_ocr_amd.stop_strings import StopAutomaton, compile_stop, cut_text, first_stop, stopped_text
 from test_parallel_sampling_cpu import ForkEngine
 
@@ -291,7 +292,7 @@ def test_the_batcher_sets_reads_and_clears_the_row():
     outs = cb.run([a, b, plain])
     assert a.stop == ("one",) and a.stop_hit == (6, 1, 3, 0) and proc.tokenizer.decode(outs[0].tolist()) == "row one"
     assert b.stop_hit is None and not hasattr(plain, "stop_hit")                    # "row" lies wholly below min_tokens = 3
-    assert proc.tokenizer.decode(outs[2].tolist()) == TEXTS[0] and eng.stops == {} and cb._row_stop == {}
+    assert proc.tokenizer.decode(outs[2].tolist()) == TEXTS[0] and eng.stops == {} and rows_holding(cb._rows, "stop") == []
     with pytest.raises(RequestRejected):
         cb.submit(Request(ids, stop=[""]))
     from fakes import FakePagedEngine
