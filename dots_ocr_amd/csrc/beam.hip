@@ -325,7 +325,7 @@ int dots_slots_beam(DotsEngine* e, int src_slot, const int32_t* dst_slots, int n
     for (int i = 0; i < B; ++i) {
         const int r = i ? dst_slots[i - 1] : src_slot;
         if (e->stage.staged(r) || e->row_lp[r] >= 0)
-            return e->fail(DOTS_E_INVALID, "slot %d carries row parameters, rules, a guide, an n-gram rule, stop strings or logprobs: a beam row takes none", r);
+            return e->fail(DOTS_E_INVALID, "slot %d carries row parameters, rules, a guide, an n-gram rule, stop strings, a loop guard or logprobs: a beam row takes none", r);
         if (e->row_stream[r]) return e->fail(DOTS_E_STATE, "slot %d streams (dots_set_row_stream): a group's outputs are reordered, its rows cannot", r);
     }
     int gi = 0;

@@ -30,6 +30,7 @@
 #include "decode_layout.h"
 #include "kernels.h"
 #include "launch.h"
+#include "loop_dev.h"
 #include "select_dev.h"
 #include "step_dev.h"
 
@@ -790,6 +791,8 @@ __global__ __launch_bounds__(256) void select_partial_kernel(const float* __rest
     }
 }
 
+static_assert(SEL_THREADS == LOOP_THREADS, "the loop guard's check runs in the stage's workgroup: one thread per period");
+
 // steps 1-2 of a sampled row: rs.thr[b] = the largest key it keeps (the arithmetic: select_dev.h sel_threshold)
 __global__ __launch_bounds__(SEL_THREADS) void select_thresh_kernel(const float* __restrict__ logits, int V, int ld, RowSel rs,
                                                                     const int32_t* __restrict__ sel, const float* __restrict__ pval,
@@ -816,6 +819,7 @@ __global__ __launch_bounds__(SEL_THREADS) void select_rows_kernel(const float* _
     __shared__ float s_best;
     __shared__ int s_bi;
     __shared__ DrawLds D;
+    __shared__ LoopCommitLds LC;
     const int b = blockIdx.x, tid = threadIdx.x;
     if (st.sel && !st.sel[b]) return;                                 // uniform per workgroup
     const bool own = rs.own[b] != 0;
@@ -823,13 +827,20 @@ __global__ __launch_bounds__(SEL_THREADS) void select_rows_kernel(const float* _
     merge_partials(pval, pidx, b, &s_best, &s_bi);
     const RowParams p = own ? rs.params[b] : RowParams{0.f, 1.f, 0, 1.f, 0.f, 0.f, 0};
     const bool pen = own && rs.cnt && row_has_pen(p);
+    // a row with a loop rule does not leave at its commit: the whole workgroup checks the committed token behind it.  n:
+    // the output index the commit writes (thread 0's facts, handed on through LDS)
+    const bool looped = row_looped(rs, b);                            // uniform per workgroup
+    int what = COMMIT_IDLE, n = 0, tok = 0;
     if (!(p.temperature > 0.f)) {
-        if (tid == 0) commit_row(st, rs, b, V, pen, s_bi);
-        return;
+        if (tid == 0) { n = st.out_lens[b]; tok = s_bi; what = commit_row(st, rs, b, V, pen, tok); }
+        if (!looped) return;
+    } else {
+        const float* row = pen || row_ruled(rs, b) || row_guided(rs, b) || row_ngram(rs, b) ? rs.pen + (size_t)b * V : logits + (size_t)b * ld;
+        const int drawn = sel_draw(row, V, p, s_best, rs.thr[b], (uint32_t)st.out_lens[b], D);      // out_lens: nobody commits before the barrier that ends the draw
+        if (tid == 0) { n = st.out_lens[b]; tok = drawn >= 0 ? drawn : s_bi; what = commit_row(st, rs, b, V, pen, tok); }        // no token: a numerical corner, the arg max
+        if (!looped) return;
     }
-    const float* row = pen || row_ruled(rs, b) || row_guided(rs, b) || row_ngram(rs, b) ? rs.pen + (size_t)b * V : logits + (size_t)b * ld;
-    const int tok = sel_draw(row, V, p, s_best, rs.thr[b], (uint32_t)st.out_lens[b], D);      // out_lens: nobody commits before the barrier that ends the draw
-    if (tid == 0) commit_row(st, rs, b, V, pen, tok >= 0 ? tok : s_bi);        // no token: a numerical corner, the arg max
+    loop_after_commit(rs.loop, st, b, what, n, tok, LC);
 }
 
 __global__ __launch_bounds__(256) void pen_prompt_kernel(const int32_t* __restrict__ src, const int32_t* __restrict__ last,

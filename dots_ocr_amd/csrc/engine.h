@@ -193,6 +193,11 @@ struct DotsEngine {
     RowStop* d_stop = nullptr;
     int row_stop[DOTS_MAX_BATCH] = {0};
     int row_stop_min[DOTS_MAX_BATCH] = {0};
+    // loop guard (dots_set_row_loop), allocated by the first row that takes a rule: the row table and the run counters
+    // [DOTS_MAX_BATCH][DOTS_MAX_LOOP_PERIOD].  row_loop[row]: the rule of a row that holds one (what a fork hands its children)
+    RowLoop* d_loop = nullptr;
+    int32_t* loop_run = nullptr;
+    DotsLoopRule row_loop[DOTS_MAX_BATCH] = {};
     // log-probabilities (dots_set_row_logprobs): top_n per row (-1 = off) on the device and its host mirror; the outputs
     // ([max_batch][max_seq_len] positions) and the stage's scratch are allocated by the first row switched on
     int32_t* d_row_lp = nullptr;
@@ -486,6 +491,8 @@ hipError_t launch_row_stage(hipStream_t s, const float* logits, int V, int ld, i
 int select_tokens(DotsEngine* e, int advance);
 int clear_row_feature(DotsEngine* e, int row, RowFeature f);
 int hold_row_stop(DotsEngine* e, int row, int id, int min_tokens);
+int hold_row_loop(DotsEngine* e, int row, const DotsLoopRule& r);
+LoopSel loop_sel(const DotsEngine* e);
 int check_row_params(DotsEngine* e, const DotsSamplingParams& p, RowParams* out);
 int check_logit_rules(DotsEngine* e, const DotsLogitRules& r, int V, const int32_t* eos, int n_eos, RowRules* out);
 int check_ngram_rule(DotsEngine* e, const DotsNgramRule& r, int V, int max_len, RowNgram* out);
@@ -524,7 +531,8 @@ int beam_step(DotsEngine* e, int rows);
 int beam_before_decode(DotsEngine* e, int n_steps);
 int beam_release_group(DotsEngine* e, int slot);
 int beam_clear_all(DotsEngine* e);
-// a group row carries no stage feature and no logprobs: the row setters refuse it
+// a group row carries no stage feature and no logprobs: the row setters refuse it (BEAM_ROW_TAKES_NONE: their common sentence)
+#define BEAM_ROW_TAKES_NONE "slot %d is a row of a beam group: it takes no row parameters, rules, guide, n-gram rule, stop strings, loop guard or logprobs"
 inline bool beam_row(const DotsEngine* e, int row) { return row >= 0 && row < DOTS_MAX_BATCH && e->beam_of[row] != 0; }
 
 }  // namespace engine

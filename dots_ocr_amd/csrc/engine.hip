@@ -1073,7 +1073,7 @@ int dots_generate(DotsEngine* e, const int32_t* input_ids, const int32_t* prompt
         if (exec) CK(hipGraphLaunch(cur != s && exec_part ? exec_part : exec, cur));
         else RET(decode_step_launches(e, n_splits));
         ++steps;
-        if ((n_eos || e->stage.rows(ROW_STOP) > 0) && (step % 16 == 0)) {       // early exit once every sequence hit EOS (or its stop string)
+        if ((n_eos || e->stage.rows(ROW_STOP) > 0 || e->stage.rows(ROW_LOOP) > 0) && (step % 16 == 0)) {       // early exit once every sequence hit EOS (or its stop string, or its loop rule)
             CK(hipMemcpyAsync(fin.data(), e->finished, B * 4, hipMemcpyDeviceToHost, cur));
             CK(hipStreamSynchronize(cur));
             bool all = true;

@@ -203,6 +203,16 @@ struct RowStop {
     int32_t n_states, state, min_tokens, hit_tok, hit_bytes, hit_len, hit_id, _pad;
 };
 struct StopSel { RowStop* rows; const int32_t* tok_off; const uint8_t* tok_bytes; int32_t V, _pad; };
+// Loop guard.  RowLoop: the rule a row holds (max_period == 0: none) and the hit record the commit that fires it leaves
+// (hit_tok == -1: no hit yet).  With out[0 .. n] the row's output, period p in [min_period, max_period] fires after the commit of out[n]
+// iff out[i] == out[i - p] for the last L(p) - p indices i, L(p) = max(repeats * p, min_span) (loop_dev.h).  LoopSel: what a launch of the
+// per-row stage needs — the row table and the run counters run[DOTS_MAX_BATCH][DOTS_MAX_LOOP_PERIOD] (run[b][p - 1] = the consecutive
+// indices up to the last commit with out[i] == out[i - p]).  rows == nullptr = no row of this engine ever held a loop rule.
+#ifndef DOTS_MAX_LOOP_PERIOD
+#define DOTS_MAX_LOOP_PERIOD 1024
+#endif
+struct RowLoop { int32_t min_period, max_period, repeats, min_span, hit_tok, period, span, _pad; };
+struct LoopSel { RowLoop* rows; int32_t* run; };
 struct RowSel {
     const RowParams* params;
     const int32_t* own;
@@ -216,6 +226,7 @@ struct RowSel {
     GuideSel guide;             // guide.rows == nullptr = no row of this launch is guided
     NgramSel ngram;             // ngram.rows == nullptr = no row of this launch carries an n-gram rule
     StopSel stop;               // stop.rows == nullptr = no row of this engine ever held stop strings
+    LoopSel loop;               // loop.rows == nullptr = no row of this engine ever held a loop rule
 };
 // pval / pidx: ARGMAX_CHUNKS (64) partials per row, as launch_argmax_step
 hipError_t launch_select_rows(hipStream_t s, const float* logits, int V, int ld, int B, const RowSel& rs, float* pval, int32_t* pidx, const StepState& st);
@@ -273,6 +284,17 @@ hipError_t launch_set_row_stop(hipStream_t s, RowStop* table, int row, const Row
 hipError_t launch_stop_reset_rows(hipStream_t s, RowStop* table, const int32_t* dst, int n);
 // table[dst[i]] = table[src] at the root with no hit, i < n (dots_slots_fork: the children inherit the source's automaton and min_tokens)
 hipError_t launch_stop_fork_rows(hipStream_t s, RowStop* table, int src, const int32_t* dst, int n);
+// ---- loop.hip: the loop guard, the stream-ordered writers of the row table and the run counters (the check itself is
+// loop_dev.h loop_step, run by select_rows_kernel after the commit)
+// table[row] = r with no hit and the row's counters zeroed (r.max_period == 0: the row holds none)
+hipError_t launch_set_row_loop(hipStream_t s, RowLoop* table, int32_t* run, int row, const RowLoop& r);
+// no hit and zeroed counters for the n rows dst[0 .. n) (dst == nullptr: rows 0 .. n - 1) that hold a rule, in stream order (the row's output starts over)
+hipError_t launch_loop_reset_rows(hipStream_t s, RowLoop* table, int32_t* run, const int32_t* dst, int n);
+// table[dst[i]] = table[src] with no hit and zeroed counters, i < n (dots_slots_fork: what an independent request holds before its first token)
+hipError_t launch_loop_fork_rows(hipStream_t s, RowLoop* table, int32_t* run, int src, const int32_t* dst, int n);
+// One workgroup per case: ids[c * stride + 0 .. lens[c]) go one by one through loop_step under rule r, the counters in registers;
+// hits[c] = {hit_tok, period, span} of the first hit, {-1, 0, 0}: none.  A test entry (dots_loop_probe)
+hipError_t launch_loop_probe(hipStream_t s, const int32_t* ids, const int32_t* lens, int cases, int stride, const RowLoop& r, int32_t* hits);
 // ---- spec.hip: n-gram speculative decoding
 // A speculating step runs over R = rows x (k + 1) rows, draft-major: row j * rows + b carries token j of (last token, draft 1 .. k) of slot
 // b at context ctx + j on the slot's own KV pages.  SpecState: the slots' drafts of the next step (drafts [DOTS_MAX_BATCH]

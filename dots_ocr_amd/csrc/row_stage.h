@@ -9,7 +9,11 @@
 #error "row_stage.h needs DOTS_MAX_BATCH"
 #endif
 
-enum RowFeature { ROW_PARAMS, ROW_RULES, ROW_GUIDE, ROW_NGRAM, ROW_STOP, ROW_FEATURES };
+// ROW_FEATURES counts the features some speculation mode can let through (SpecRows below): what the stand-alone models of `speculates`
+// enumerate.  ROW_LOOP (the loop guard) lies behind them — no mode opens it — and ROW_ALL_FEATURES counts every feature a row
+// can be staged for: what the record's arrays and the engine's "every feature of the row" loops run over.
+enum RowFeature { ROW_PARAMS, ROW_RULES, ROW_GUIDE, ROW_NGRAM, ROW_STOP, ROW_FEATURES, ROW_LOOP = ROW_FEATURES, ROW_ALL_FEATURES };
+static_assert(ROW_ALL_FEATURES <= 8, "RowStage keeps a row's features in one byte");
 // which staged rows may verify drafts: SAMPLED and STOP are the values of DOTS_SPEC_ROWS_* (dots_set_speculation_rows, whose
 // every bit is SPEC_ROWS_ALL); the others are internal: the engine ORs SPEC_ROWS_GUIDED in from dots_set_speculation_guided, and NGRAM /
 // RULES / PENALTY — the DOTS_SPEC_SHAPED_* bits moved up by three — from dots_set_speculation_shaped
@@ -49,6 +53,8 @@ struct RowStage {
     // the guide's state, the history an n-gram rule reads, the output counts and the output index are known at the head of the step;
     // rejected rows leave nothing behind.  The bits are opt-ins because each adds launches to a step, not because a row could go wrong.
     // Logprobs and the engine-wide temperature are not stage features: the caller adds them.
+    // A loop rule (ROW_LOOP) is let through by no bit: its check is workgroup-wide behind every commit, and the accept walk
+    // commits several tokens on one lane.  Such a row runs unspeculated beside speculating neighbours.
     bool speculates(int row, bool has_pen, int mode) const {
         const unsigned open = ((mode & SPEC_ROWS_SAMPLED) ? 1u << ROW_PARAMS : 0u) | ((mode & SPEC_ROWS_STOP) ? 1u << ROW_STOP : 0u) |
                               ((mode & SPEC_ROWS_GUIDED) ? 1u << ROW_GUIDE : 0u) | ((mode & SPEC_ROWS_NGRAM) ? 1u << ROW_NGRAM : 0u) |
@@ -60,6 +66,6 @@ struct RowStage {
 
 private:
     unsigned char bits[DOTS_MAX_BATCH] = {0};
-    int n_rows[ROW_FEATURES] = {0};
+    int n_rows[ROW_ALL_FEATURES] = {0};
     int n_staged = 0;
 };

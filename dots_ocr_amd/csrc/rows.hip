@@ -99,6 +99,15 @@ int ensure_stop_state(DotsEngine* e) {
     return DOTS_OK;
 }
 
+// row table and run counters of the loop guard, allocated by the first row that takes a rule
+int ensure_loop_state(DotsEngine* e) {
+    if (e->d_loop) return DOTS_OK;
+    if (!e->loop_run) CK(e->alloc(&e->loop_run, (size_t)DOTS_MAX_BATCH * DOTS_MAX_LOOP_PERIOD));
+    CK(e->alloc(&e->d_loop, DOTS_MAX_BATCH));              // zeroed by alloc(): no row holds a rule; set last, it is the guard above
+    drop_step_graphs(e);                                   // graphs captured before hold no loop table
+    return DOTS_OK;
+}
+
 // what a row without parameters of its own is selected with once the per-row stage owns it (logit rules): the engine-wide setting as it stands
 RowParams engine_row_params(const DotsEngine* e) { return RowParams{e->temperature, e->top_p, 0, 1.f, 0.f, 0.f, e->seed}; }
 
@@ -205,6 +214,7 @@ RowSel spec_row_sel(const DotsEngine* e) {
     if (on & DOTS_SPEC_SHAPED_NGRAM) rs.ngram = NgramSel{e->d_ngram, e->ngram_mask, ngram_mask_words(V), V};
     if (spec_guides(e)) rs.guide = guide_sel(e);
     if (e->d_stop) rs.stop = StopSel{e->d_stop, e->tok_off, e->tok_bytes, V, 0};
+    rs.loop = loop_sel(e);                                 // a row that holds a rule verifies no draft: the accept walk never asks
     return rs;
 }
 
@@ -213,6 +223,9 @@ SpecState spec_state(const DotsEngine* e) {
                      spec_draws(e) ? e->sp_cand : nullptr, spec_guides(e) ? e->sp_gstate : nullptr, e->spec_k, e->temperature > 0.f ? 0 : 1,
                      spec_lps(e) ? e->sp_acc_n : nullptr, spec_lps(e) ? e->sp_acc_tok : nullptr};
 }
+
+// the loop rows' table and counters, once any row has held a rule (allocating them drops the captured steps, so no cache key changes)
+LoopSel loop_sel(const DotsEngine* e) { return LoopSel{e->d_loop, e->d_loop ? e->loop_run : nullptr}; }
 
 // what a launch needs to honour the guides (the row table exists once a row has taken one)
 GuideSel guide_sel(const DotsEngine* e) {
@@ -245,6 +258,7 @@ int select_tokens(DotsEngine* e, int advance) {
         // the stop-string rows' table, once any row has held one (allocating it drops the captured steps, so no cache key changes): the
         // commit of a row that holds an automaton walks it, no launch is added
         if (e->d_stop) rs.stop = StopSel{e->d_stop, e->tok_off, e->tok_bytes, c.vocab_size, 0};
+        rs.loop = loop_sel(e);                     // as the stop table: the check runs inside the stage's commit kernel, no launch is added
         if (e->stage.rows(ROW_NGRAM) > 0)          // the n-gram rows' banned bits from their own output so far, before the stage reads the logits
             rs.ngram = NgramSel{e->d_ngram, e->ngram_mask, ngram_mask_words(c.vocab_size), c.vocab_size};
         if (e->stage.rows(ROW_GUIDE) > 0)          // the guided rows' allowed bits from their current states, before the stage reads the logits
@@ -280,6 +294,10 @@ int clear_row_feature(DotsEngine* e, int row, RowFeature f) {
         e->stops[e->row_stop[row] - 1].rows -= 1;
         e->row_stop[row] = e->row_stop_min[row] = 0;
         break;
+    case ROW_LOOP:
+        CK(launch_set_row_loop(e->stream, e->d_loop, e->loop_run, row, RowLoop{}));
+        e->row_loop[row] = DotsLoopRule{};
+        break;
     default: break;                                        // own parameters: the stage entry is all there is
     }
     return leave_row_stage(e, row, f);
@@ -293,6 +311,14 @@ int hold_row_stop(DotsEngine* e, int row, int id, int min_tokens) {
     e->row_stop[row] = id + 1;
     e->row_stop_min[row] = min_tokens;
     e->stops[id].rows += 1;
+    return DOTS_OK;
+}
+
+// host side of row `row` taking loop rule r (a checked one): stage membership and the row's payload.  The caller writes the row's table
+// entry (dots_set_row_loop one row, dots_slots_fork all children at once)
+int hold_row_loop(DotsEngine* e, int row, const DotsLoopRule& r) {
+    RET(enter_row_stage(e, row, ROW_LOOP));
+    e->row_loop[row] = r;
     return DOTS_OK;
 }
 
@@ -411,7 +437,7 @@ int dots_set_row_sampling(DotsEngine* e, int row, const DotsSamplingParams* p) {
     if (row < 0 || row >= e->cfg.max_batch) return e->fail(DOTS_E_INVALID, "row %d out of range [0, %d)", row, e->cfg.max_batch);
     CK(hipSetDevice(e->device));
     if (!p) return clear_row_feature(e, row, ROW_PARAMS);
-    if (beam_row(e, row)) return e->fail(DOTS_E_INVALID, "slot %d is a row of a beam group: it takes no row parameters, rules, guide, n-gram rule, stop strings or logprobs", row);
+    if (beam_row(e, row)) return e->fail(DOTS_E_INVALID, BEAM_ROW_TAKES_NONE, row);
     RowParams rp;
     RET(check_row_params(e, *p, &rp));
     RET(ensure_row_table(e));
@@ -427,7 +453,7 @@ int dots_set_row_logit_rules(DotsEngine* e, int row, const DotsLogitRules* r) {
     if (row < 0 || row >= e->cfg.max_batch) return e->fail(DOTS_E_INVALID, "row %d out of range [0, %d)", row, e->cfg.max_batch);
     CK(hipSetDevice(e->device));
     if (!r) return clear_row_feature(e, row, ROW_RULES);
-    if (beam_row(e, row)) return e->fail(DOTS_E_INVALID, "slot %d is a row of a beam group: it takes no row parameters, rules, guide, n-gram rule, stop strings or logprobs", row);
+    if (beam_row(e, row)) return e->fail(DOTS_E_INVALID, BEAM_ROW_TAKES_NONE, row);
     RowRules rr;
     RET(check_logit_rules(e, *r, e->cfg.vocab_size, e->h_eos, e->n_eos, &rr));
     RET(ensure_row_table(e));
@@ -519,7 +545,7 @@ int dots_set_row_guide(DotsEngine* e, int row, int32_t id) {
     if (row < 0 || row >= e->cfg.max_batch) return e->fail(DOTS_E_INVALID, "row %d out of range [0, %d)", row, e->cfg.max_batch);
     CK(hipSetDevice(e->device));
     if (id < 0) return clear_row_feature(e, row, ROW_GUIDE);
-    if (beam_row(e, row)) return e->fail(DOTS_E_INVALID, "slot %d is a row of a beam group: it takes no row parameters, rules, guide, n-gram rule, stop strings or logprobs", row);
+    if (beam_row(e, row)) return e->fail(DOTS_E_INVALID, BEAM_ROW_TAKES_NONE, row);
     if (id >= (int)e->guides.size() || !e->guides[id].table) return e->fail(DOTS_E_INVALID, "no guide %d", id);
     if (!e->tok_off) return e->fail(DOTS_E_STATE, "the token bytes are not set (dots_set_token_bytes): a guide cannot judge any token");
     RET(ensure_row_table(e));
@@ -538,7 +564,7 @@ int dots_set_row_ngram(DotsEngine* e, int row, const DotsNgramRule* r) {
     if (row < 0 || row >= e->cfg.max_batch) return e->fail(DOTS_E_INVALID, "row %d out of range [0, %d)", row, e->cfg.max_batch);
     CK(hipSetDevice(e->device));
     if (!r) return clear_row_feature(e, row, ROW_NGRAM);
-    if (beam_row(e, row)) return e->fail(DOTS_E_INVALID, "slot %d is a row of a beam group: it takes no row parameters, rules, guide, n-gram rule, stop strings or logprobs", row);
+    if (beam_row(e, row)) return e->fail(DOTS_E_INVALID, BEAM_ROW_TAKES_NONE, row);
     RowNgram rn;
     RET(check_ngram_rule(e, *r, e->cfg.vocab_size, e->cfg.max_seq_len, &rn));
     RET(ensure_row_table(e));
@@ -599,7 +625,7 @@ int dots_set_row_stop(DotsEngine* e, int row, int32_t handle, int min_tokens) {
     if (row < 0 || row >= e->cfg.max_batch) return e->fail(DOTS_E_INVALID, "row %d out of range [0, %d)", row, e->cfg.max_batch);
     CK(hipSetDevice(e->device));
     if (handle == 0) return clear_row_feature(e, row, ROW_STOP);
-    if (beam_row(e, row)) return e->fail(DOTS_E_INVALID, "slot %d is a row of a beam group: it takes no row parameters, rules, guide, n-gram rule, stop strings or logprobs", row);
+    if (beam_row(e, row)) return e->fail(DOTS_E_INVALID, BEAM_ROW_TAKES_NONE, row);
     const int id = handle - 1;
     if (id < 0 || id >= (int)e->stops.size() || !e->stops[id].table) return e->fail(DOTS_E_INVALID, "no stop automaton %d", handle);
     if (min_tokens < 0) return e->fail(DOTS_E_INVALID, "stop strings: min_tokens must be >= 0");
@@ -617,6 +643,62 @@ int dots_row_stop_hit(DotsEngine* e, int row, int32_t* out) {
     CK(hipMemcpyAsync(&rs, e->d_stop + row, sizeof(rs), hipMemcpyDeviceToHost, e->stream));
     CK(hipStreamSynchronize(e->stream));
     if (rs.hit_tok >= 0) { out[0] = rs.hit_tok; out[1] = rs.hit_bytes; out[2] = rs.hit_len; out[3] = rs.hit_id; }
+    return DOTS_OK;
+}
+
+// ---------------------------------------------------------------------------------- loop guard
+static int check_loop_rule(DotsEngine* e, const DotsLoopRule& r) {
+    if (r.min_period < 1 || r.max_period < r.min_period || r.max_period > DOTS_MAX_LOOP_PERIOD)
+        return e->fail(DOTS_E_INVALID, "loop guard: periods must satisfy 1 <= min_period <= max_period <= %d, got %d .. %d", DOTS_MAX_LOOP_PERIOD, r.min_period, r.max_period);
+    if (r.repeats < 2 || r.repeats > 64) return e->fail(DOTS_E_INVALID, "loop guard: repeats must be in [2, 64], got %d", r.repeats);
+    if (r.min_span < 0 || r.min_span > 65535) return e->fail(DOTS_E_INVALID, "loop guard: min_span must be in [0, 65535], got %d", r.min_span);
+    return DOTS_OK;
+}
+
+int dots_set_row_loop(DotsEngine* e, int row, const DotsLoopRule* r) {
+    if (!e) return DOTS_E_INVALID;
+    if (row < 0 || row >= e->cfg.max_batch) return e->fail(DOTS_E_INVALID, "row %d out of range [0, %d)", row, e->cfg.max_batch);
+    CK(hipSetDevice(e->device));
+    if (!r) return clear_row_feature(e, row, ROW_LOOP);
+    if (beam_row(e, row)) return e->fail(DOTS_E_INVALID, BEAM_ROW_TAKES_NONE, row);
+    RET(check_loop_rule(e, *r));
+    RET(ensure_row_table(e));
+    RET(ensure_loop_state(e));
+    CK(launch_set_row_loop(e->stream, e->d_loop, e->loop_run, row, RowLoop{r->min_period, r->max_period, r->repeats, r->min_span, -1, 0, 0, 0}));
+    return hold_row_loop(e, row, *r);
+}
+
+int dots_row_loop_hit(DotsEngine* e, int row, int32_t* out) {
+    if (!e || !out) return e ? e->fail(DOTS_E_INVALID, "null argument") : DOTS_E_INVALID;
+    if (row < 0 || row >= e->cfg.max_batch) return e->fail(DOTS_E_INVALID, "row %d out of range [0, %d)", row, e->cfg.max_batch);
+    out[0] = -1; out[1] = 0; out[2] = 0;
+    if (!e->stage.has(row, ROW_LOOP)) return DOTS_OK;
+    CK(hipSetDevice(e->device));
+    RowLoop rl;
+    CK(hipMemcpyAsync(&rl, e->d_loop + row, sizeof(rl), hipMemcpyDeviceToHost, e->stream));
+    CK(hipStreamSynchronize(e->stream));
+    if (rl.hit_tok >= 0) { out[0] = rl.hit_tok; out[1] = rl.period; out[2] = rl.span; }
+    return DOTS_OK;
+}
+
+int dots_loop_probe(DotsEngine* e, const int32_t* ids, const int32_t* lens, int cases, int stride, const DotsLoopRule* rule, int32_t* hits_out) {
+    if (!e || !ids || !lens || !rule || !hits_out) return e ? e->fail(DOTS_E_INVALID, "null argument") : DOTS_E_INVALID;
+    if (cases < 1 || cases > 65535 || stride < 1 || (int64_t)cases * stride > (int64_t)1 << 28)
+        return e->fail(DOTS_E_INVALID, "loop probe: cases must be in [1, 65535], stride >= 1 and cases x stride <= 2^28");
+    for (int c = 0; c < cases; ++c)
+        if (lens[c] < 0 || lens[c] > stride) return e->fail(DOTS_E_INVALID, "loop probe: case %d holds %d ids, the stride is %d", c, lens[c], stride);
+    RET(check_loop_rule(e, *rule));
+    CK(hipSetDevice(e->device));
+    Scratch sc(e);
+    int32_t *d_ids = nullptr, *d_lens = nullptr, *d_hits = nullptr;
+    CK(sc.get(&d_ids, (size_t)cases * stride));
+    CK(sc.get(&d_lens, (size_t)cases));
+    CK(sc.get(&d_hits, (size_t)cases * 3));
+    CK(hipMemcpyAsync(d_ids, ids, (size_t)cases * stride * 4, hipMemcpyHostToDevice, e->stream));
+    CK(hipMemcpyAsync(d_lens, lens, (size_t)cases * 4, hipMemcpyHostToDevice, e->stream));
+    CK(launch_loop_probe(e->stream, d_ids, d_lens, cases, stride, RowLoop{rule->min_period, rule->max_period, rule->repeats, rule->min_span, -1, 0, 0, 0}, d_hits));
+    CK(hipMemcpyAsync(hits_out, d_hits, (size_t)cases * 12, hipMemcpyDeviceToHost, e->stream));
+    CK(hipStreamSynchronize(e->stream));
     return DOTS_OK;
 }
 
@@ -765,7 +847,7 @@ int dots_set_row_logprobs(DotsEngine* e, int row, int top_n) {
     if (row < 0 || row >= e->cfg.max_batch) return e->fail(DOTS_E_INVALID, "row %d out of range [0, %d)", row, e->cfg.max_batch);
     if (top_n < -1 || top_n > DOTS_MAX_TOP_LOGPROBS) return e->fail(DOTS_E_INVALID, "top_n must be -1 (off) or in [0, %d]", DOTS_MAX_TOP_LOGPROBS);
     if (top_n < 0 && !e->d_row_lp) return DOTS_OK;
-    if (top_n >= 0 && beam_row(e, row)) return e->fail(DOTS_E_INVALID, "slot %d is a row of a beam group: it takes no row parameters, rules, guide, n-gram rule, stop strings or logprobs", row);
+    if (top_n >= 0 && beam_row(e, row)) return e->fail(DOTS_E_INVALID, BEAM_ROW_TAKES_NONE, row);
     if (e->cfg.vocab_size > LP_MAX_V) return e->fail(DOTS_E_INVALID, "logprobs support vocabularies up to %d", LP_MAX_V);
     CK(hipSetDevice(e->device));
     if (!e->d_row_lp) {

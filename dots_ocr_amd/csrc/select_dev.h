@@ -33,6 +33,9 @@ DEVI bool row_guided(const RowSel& rs, int b) { return rs.guide.rows && rs.guide
 // does row b carry an n-gram rule in this launch (uniform per workgroup)
 DEVI bool row_ngram(const RowSel& rs, int b) { return rs.ngram.rows && rs.ngram.rows[b].n > 0; }
 
+// does row b hold a loop rule in this launch (uniform per workgroup)
+DEVI bool row_looped(const RowSel& rs, int b) { return rs.loop.rows && rs.loop.rows[b].max_period > 0; }
+
 // is row b penalised in this launch (uniform per workgroup): the counts exist, the stage owns the row (the entry of a row it does not own
 // is not parameters) and its parameters carry a penalty
 DEVI bool row_penalised(const RowSel& rs, int b) { return rs.cnt && rs.own[b] != 0 && row_has_pen(rs.params[b]); }
@@ -80,9 +83,10 @@ DEVI float shape_logit(float l, int i, const RowShape& s, const RowParams& p) {
 // The commit of a row the per-row stage owns: the output count of an unfinished penalised row (pen: the row's parameters carry a penalty and
 // the counts exist), then commit_token with the row's rules, the guides and the stop automata of the launch.  ONE definition:
 // select_rows_kernel commits the rows of a step with it, spec_accept_kernel (spec.hip) every token of its walk.
-DEVI void commit_row(const StepState& st, const RowSel& rs, int b, int V, bool pen, int tok) {
+// Returns commit_token's answer (step_dev.h COMMIT_*).
+DEVI int commit_row(const StepState& st, const RowSel& rs, int b, int V, bool pen, int tok) {
     if (pen && !st.finished[b] && tok >= 0 && tok < V) rs.cnt[(size_t)b * V + tok] += 1;     // output counts of the rows with penalties
-    commit_token(st, b, tok, row_ruled(rs, b) ? rs.rules + b : nullptr, rs.guide.rows ? &rs.guide : nullptr, rs.stop.rows ? &rs.stop : nullptr);
+    return commit_token(st, b, tok, row_ruled(rs, b) ? rs.rules + b : nullptr, rs.guide.rows ? &rs.guide : nullptr, rs.stop.rows ? &rs.stop : nullptr);
 }
 
 DEVI uint32_t sel_key(float t) { return __float_as_uint(0.f - t); }              // 0 - (+-0) = +0: the maximum has key 0

@@ -200,10 +200,12 @@ int stage_new_rows(DotsEngine* e, const std::vector<LiveRow>& rows, int32_t* d_l
 }
 
 // the automata of the rows that hold a guide start over (the first token is selected under the guide), and so do their stop automata,
-// whose hit records are cleared: the first token's bytes are the first ones walked.  d_rows: device list of n rows, nullptr = rows [0, n)
+// whose hit records are cleared: the first token's bytes are the first ones walked; and so do the run counters of the rows with a loop rule.  d_rows: device list of n rows, nullptr = rows [0, n)
 int restart_automata(DotsEngine* e, const int32_t* d_rows, int n, bool stops) {
     if (e->stage.rows(ROW_GUIDE) > 0) CK(launch_guide_reset_rows(e->stream, e->d_guides, d_rows, n));
     if (stops && e->stage.rows(ROW_STOP) > 0) CK(launch_stop_reset_rows(e->stream, e->d_stop, d_rows, n));
+    // the loop guard's window is the output since it last started over: counters zeroed, no hit
+    if (e->stage.rows(ROW_LOOP) > 0) CK(launch_loop_reset_rows(e->stream, e->d_loop, e->loop_run, d_rows, n));
     return DOTS_OK;
 }
 
@@ -419,6 +421,11 @@ int dots_slots_fork(DotsEngine* e, int src_slot, const int32_t* dst_slots, int n
         for (int i = 0; i < n; ++i) RET(hold_row_stop(e, dst_slots[i], e->row_stop[src_slot] - 1, e->row_stop_min[src_slot]));
         CK(launch_stop_fork_rows(s, e->d_stop, src_slot, fk_dst, n));
     }
+    if (e->stage.has(src_slot, ROW_LOOP)) {
+        // ... and its loop rule, with no hit and the counters at zero: what an independent request holds before its first token
+        for (int i = 0; i < n; ++i) RET(hold_row_loop(e, dst_slots[i], e->row_loop[src_slot]));
+        CK(launch_loop_fork_rows(s, e->d_loop, e->loop_run, src_slot, fk_dst, n));
+    }
     CK(hipStreamSynchronize(s));                           // `stage` is a stack array
     // ---- the children's first tokens, from the logits in place
     RET(select_first_tokens(e, rows, nullptr));
@@ -455,6 +462,8 @@ int extend_slots(DotsEngine* e, const char* call, const int32_t* slots, int n, c
         if (max_new_tokens[i] < 1) return e->fail(DOTS_E_INVALID, "slot %d: max_new_tokens must be >= 1, got %d", b, max_new_tokens[i]);
         if (top_n && (top_n[i] < 0 || top_n[i] > DOTS_MAX_TOP_LOGPROBS))
             return e->fail(DOTS_E_INVALID, "slot %d: top_n must be in [0, %d], got %d", b, DOTS_MAX_TOP_LOGPROBS, top_n[i]);
+        if (top_n && e->stage.has(b, ROW_LOOP))
+            return e->fail(DOTS_E_STATE, "slot %d carries a loop guard: a scored row selects nothing it could guard (clear it first: dots_set_row_loop(row, NULL))", b);
         if (e->stage.has(b, ROW_PARAMS) && e->row_pen[b])
             return e->fail(DOTS_E_STATE, "slot %d carries a penalty: its prompt-presence image would have to absorb the earlier output, so it cannot be extended", b);
         for (int j = 0; j < lens[i]; ++j) {
@@ -699,8 +708,9 @@ int dots_slots_reset(DotsEngine* e) {
     CK(hipMemsetAsync(e->out_lens, 0, e->cfg.max_batch * 4, s));
     CK(hipMemsetAsync(e->finished, 0, e->cfg.max_batch * 4, s));
     // no row carries any feature: the features' row tables (in RowFeature order; the own flags stand for the parameters), then the host record
-    const struct { void* table; size_t row_bytes; } feature_tables[ROW_FEATURES] = {
-        {e->d_row_own, 4}, {e->d_rules, sizeof(RowRules)}, {e->d_guides, sizeof(RowGuide)}, {e->d_ngram, sizeof(RowNgram)}, {e->d_stop, sizeof(RowStop)}};
+    const struct { void* table; size_t row_bytes; } feature_tables[ROW_ALL_FEATURES] = {
+        {e->d_row_own, 4}, {e->d_rules, sizeof(RowRules)}, {e->d_guides, sizeof(RowGuide)}, {e->d_ngram, sizeof(RowNgram)}, {e->d_stop, sizeof(RowStop)},
+        {e->d_loop, sizeof(RowLoop)}};
     for (const auto& t : feature_tables)
         if (t.table) CK(hipMemsetAsync(t.table, 0, DOTS_MAX_BATCH * t.row_bytes, s));
     e->stage.reset();
@@ -709,6 +719,7 @@ int dots_slots_reset(DotsEngine* e) {
     std::fill(e->row_stop, e->row_stop + DOTS_MAX_BATCH, 0);
     std::fill(e->row_stop_min, e->row_stop_min + DOTS_MAX_BATCH, 0);
     for (auto& a : e->stops) a.rows = 0;
+    std::fill(e->row_loop, e->row_loop + DOTS_MAX_BATCH, DotsLoopRule{});
     if (e->d_row_lp) CK(hipMemsetAsync(e->d_row_lp, 0xFF, DOTS_MAX_BATCH * 4, s));
     std::fill(e->row_lp, e->row_lp + DOTS_MAX_BATCH, -1);
     e->n_lp = 0;
@@ -841,7 +852,7 @@ int dots_slot_release(DotsEngine* e, int slot) {
     if (!slot_occupied(e, slot) && !(e->slot_mode && slot_filling(e, slot))) return e->fail(DOTS_E_STATE, "slot %d is not occupied", slot);
     CK(hipSetDevice(e->device));
     if (e->beam_of[slot]) return beam_release_group(e, slot);          // the slots of a beam group go together
-    for (int f = 0; f < ROW_FEATURES; ++f) RET(clear_row_feature(e, slot, (RowFeature)f));
+    for (int f = 0; f < ROW_ALL_FEATURES; ++f) RET(clear_row_feature(e, slot, (RowFeature)f));
     RET(set_row_lp(e, slot, -1));
     e->row_stream[slot] = 0;
     e->slot_active[slot] = 0;

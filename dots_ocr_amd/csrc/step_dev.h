@@ -36,9 +36,13 @@ DEVI void stop_walk(const StopSel& ss, const StepState& st, int b, int tok, int 
 // the state is accepting; with nothing else left to allow, a row that ignored it could only repeat it).
 // stop: the engine's stop-string rows (per-row stage only) or nullptr.  A row that holds an automaton and is not finished walks
 // the bytes of the committed token (stop_walk); an EOS or stop id is not walked.
-DEVI void commit_token(const StepState& st, int b, int tok, const RowRules* rules = nullptr, const GuideSel* guide = nullptr,
+// Returns what the commit did, for the loop guard's check behind it (loop_dev.h): COMMIT_IDLE = the row was finished already and nothing
+// was appended, COMMIT_EOS = the token finished the row as an EOS or stop id, COMMIT_TOKEN = anything else.
+enum { COMMIT_IDLE = 0, COMMIT_TOKEN = 1, COMMIT_EOS = 2 };
+DEVI int commit_token(const StepState& st, int b, int tok, const RowRules* rules = nullptr, const GuideSel* guide = nullptr,
                        const StopSel* stop = nullptr) {
     const bool done = st.finished[b] != 0;
+    int what = COMMIT_IDLE;
     if (st.advance_ctx && !done) st.ctx_len[b] += 1;
     if (!done) {
         const int n = st.out_lens[b];
@@ -60,8 +64,10 @@ DEVI void commit_token(const StepState& st, int b, int tok, const RowRules* rule
         }
         if (stop && !eos) stop_walk(*stop, st, b, tok, n);
         if (eos || n + 1 >= cap) st.finished[b] = 1;
+        what = eos ? COMMIT_EOS : COMMIT_TOKEN;
     }
     st.cur_tokens[b] = tok;
+    return what;
 }
 
 DEVI void argmax_merge(float& best, int& bi, float ov, int oi) {

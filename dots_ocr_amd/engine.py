@@ -274,6 +274,10 @@ class NgramRule:
         return c
 
 
+class CDotsLoopRule(C.Structure):
+    _fields_ = [("min_period", C.c_int32), ("max_period", C.c_int32), ("repeats", C.c_int32), ("min_span", C.c_int32)]
+
+
 def banned_ngram_ids(out, n: int, window: int = 0, whitelist=()) -> set:
     """The ids an NgramRule(n, window, whitelist) bans after the generated tokens `out` — the restatement the kernels are
     tested against.  With L = len(out) and P = out[L - n + 1:], every i in [max(0, L - window), L - n] (window 0: from 0) with
@@ -408,6 +412,9 @@ def _signatures() -> dict:
         "dots_stop_destroy": (i32, [vp, i32]),
         "dots_set_row_stop": (i32, [vp, i32, i32, i32]),
         "dots_row_stop_hit": (i32, [vp, i32, P(i32)]),
+        "dots_set_row_loop": (i32, [vp, i32, P(CDotsLoopRule)]),
+        "dots_row_loop_hit": (i32, [vp, i32, P(i32)]),
+        "dots_loop_probe": (i32, [vp, vp, vp, i32, i32, P(CDotsLoopRule), vp]),
         "dots_set_speculation": (i32, [vp, i32, i32, i32]),
         "dots_set_speculation_rows": (i32, [vp, i32]),
         "dots_set_speculation_guided": (i32, [vp, i32]),
@@ -431,8 +438,11 @@ def _prototypes(lib):
     global _SIGNATURES_SET
     if _SIGNATURES_SET:
         return
+    older = bool(os.environ.get("DOTS_OCR_LIB"))     # another build of the library (A/B runs): it may predate a symbol, whose call then fails
     for name, (res, args) in _signatures().items():
-        fn = getattr(lib, name)
+        fn = getattr(lib, name, None) if older else getattr(lib, name)
+        if fn is None:
+            continue
         fn.restype = res
         fn.argtypes = args
     _SIGNATURES_SET = True
@@ -933,6 +943,44 @@ class Engine:
         out = (C.c_int32 * 4)(-1, 0, 0, -1)
         self._ck(self.lib.dots_row_stop_hit(self.h, int(row), out), "dots_row_stop_hit")
         return None if out[0] < 0 else (int(out[0]), int(out[1]), int(out[2]), int(out[3]))
+
+    # ------------------------------------------------------------------ loop guard
+    @staticmethod
+    def _loop_c(rule) -> CDotsLoopRule:
+        from .loop_guard import LoopRule
+        if not isinstance(rule, LoopRule):
+            raise TypeError("rule must be a loop_guard.LoopRule or None")
+        return CDotsLoopRule(rule.min_period, rule.max_period, rule.repeats, rule.min_span)
+
+    def set_row_loop(self, row: int, rule):
+        """Row `row` (a slot, or sequence `row` of a static batch) ends at the token after which its output has repeated with some period
+        for the rule's span (loop_guard.LoopRule; set, then prefill: the window is the output since it last started over); None clears.
+        The first call allocates the counters and drops the captured decode graphs once, later calls keep them; slot release and
+        slots_reset clear the row, slots_fork hands the source's rule to its children.  A row with a rule verifies no draft."""
+        if rule is None:
+            self._ck(self.lib.dots_set_row_loop(self.h, int(row), None), "dots_set_row_loop")
+            return
+        c = self._loop_c(rule)
+        self._ck(self.lib.dots_set_row_loop(self.h, int(row), C.byref(c)), "dots_set_row_loop")
+
+    def row_loop_hit(self, row: int):
+        """(index of the firing token, period, span) of the row's loop hit, or None: no hit (yet)"""
+        out = (C.c_int32 * 3)(-1, 0, 0)
+        self._ck(self.lib.dots_row_loop_hit(self.h, int(row), out), "dots_row_loop_hit")
+        return None if out[0] < 0 else (int(out[0]), int(out[1]), int(out[2]))
+
+    def loop_probe(self, ids, lens, rule):
+        """The device check over explicit histories (a test entry): ids int32 [cases, stride], lens [cases]; returns one
+        (n, period, span) or None per case, as first_loop of loop_guard states it."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        lens = np.ascontiguousarray(lens, dtype=np.int32)
+        if ids.ndim != 2 or lens.shape != (ids.shape[0],):
+            raise ValueError("ids must be [cases, stride] and lens [cases]")
+        c = self._loop_c(rule)
+        hits = np.empty((ids.shape[0], 3), dtype=np.int32)
+        self._ck(self.lib.dots_loop_probe(self.h, ids.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p), int(ids.shape[0]), int(ids.shape[1]),
+                                          C.byref(c), hits.ctypes.data_as(C.c_void_p)), "dots_loop_probe")
+        return [None if h[0] < 0 else (int(h[0]), int(h[1]), int(h[2])) for h in hits]
 
     def _guided_args(self, B, params, rules, n_gen, guides, states):
         if len(params) != B or len(rules) != B or len(guides) != B or len(states) != B:

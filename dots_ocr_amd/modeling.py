@@ -81,6 +81,7 @@ class CallSettings:
     guide: Optional[int] = None
     ngram: Optional[NgramRule] = None
     stop: Optional[tuple] = None
+    loop: Optional[object] = None                # loop_guard.LoopRule
     nrs: int = 1                                 # num_return_sequences
     beam: Optional[tuple] = None                 # (num_beams, length_penalty)
     suffixes: Optional[list] = None              # prompt_suffixes
@@ -155,7 +156,7 @@ class DotsOcrHipForCausalLM:
                  num_return_sequences: int = 1, stop_strings=None, speculative_rows=None, num_beams: Optional[int] = None,
                  length_penalty: float = 1.0, early_stopping=None, speculative_guided: bool = False, prompt_suffixes=None, speculative_shaped=None,
                  prefill_chunk: Optional[int] = None, enable_prefix_caching: bool = False, image_keys=None, speculative_logprobs: bool = False, streamer=None,
-                 **_):
+                 loop_guard=None, **_):
         """HF-shaped generate.  do_sample / temperature / top_p default to the checkpoint's generation_config.json (greedy when it
         is absent); with sampling on, tokens are drawn on the GPU from softmax(logits / temperature) restricted to the top_p
         nucleus, reproducibly from `seed`.  Returns LongTensor
@@ -246,6 +247,11 @@ class DotsOcrHipForCausalLM:
         equal keys mean equal pixels and grid, for instance a digest of the decoded image's bytes and size; a sequence with an image and
         no key bypasses the cache.
 
+        loop_guard (True = loop_guard.LoopRule's defaults, a LoopRule, or a dict of its fields; None / False = off) ends a sequence on the
+        GPU at the token after which its output has cycled for the rule's span (Engine.set_row_loop).  The returned ids end
+        at that token; loop_guard.last_loop finds the hit again and loop_guard.trimmed cuts the ids back to one copy of the cycle.  A
+        sequence with a rule verifies no draft of a speculating call; num_beams refuses it.
+
         streamer (Hugging Face's protocol, duck-typed: put(ids) and end()) receives the prompt ids, then the new ids of every scheduler
         chunk as they are generated (Request(stream=)), then end().  It is for one sequence, as in HF: a batch above 1,
         num_return_sequences > 1 or num_beams with a streamer raise ValueError.  It runs on the continuous path."""
@@ -253,6 +259,10 @@ class DotsOcrHipForCausalLM:
         import torch
         t_eff, p_eff = resolve_sampling(self.generation_config, do_sample, temperature, top_p)
         self.engine.set_sampling(t_eff, p_eff, seed if t_eff > 0 else 0)
+        from .loop_guard import as_rule
+        loop = as_rule(loop_guard)
+        if loop is not None and not hasattr(self.engine, "set_row_loop"):
+            raise ValueError("this engine has no loop guard (no set_row_loop)")
         nrs = num_return_sequences
         if isinstance(nrs, bool) or not isinstance(nrs, int) or nrs < 1:
             raise ValueError(f"num_return_sequences must be an integer >= 1, got {nrs!r}")
@@ -295,7 +305,7 @@ class DotsOcrHipForCausalLM:
                 ("stop_token_ids", bool(stop_token_ids)), ("ignore_eos", bool(ignore_eos)),
                 ("a guide", any(g is not None for g in (guided_regex, guided_choice, guided_json))),
                 ("no_repeat_ngram_size", bool(no_repeat_ngram_size)), ("stop_strings", stop_strings is not None),
-                ("speculative_ngram", bool(speculative_ngram)), ("continuous=False", continuous is False)) if on]
+                ("loop_guard", loop is not None), ("speculative_ngram", bool(speculative_ngram)), ("continuous=False", continuous is False)) if on]
             if refused:
                 raise ValueError(f"num_beams cannot be combined with {', '.join(refused)}")
             if not hasattr(self.engine, "slots_beam"):
@@ -370,7 +380,7 @@ class DotsOcrHipForCausalLM:
         # Sequence b then draws with seed + b; with num_return_sequences prompt b's sequences take seed + b * n .. + n - 1 and with
         # suffixes the one prompt's take seed .. + m - 1 (the scheduler adds the index within a request to the seed it is given)
         row_sp = None
-        if (base is not None or rules is not None or guide is not None or ngram is not None or stop is not None
+        if (base is not None or rules is not None or guide is not None or ngram is not None or stop is not None or loop is not None
                 or (suffixes is not None and t_eff > 0) or (nrs > 1 and beam is None) or spec_sampled):
             base = call_params() if base is None else base
             stride = 0 if suffixes is not None else nrs if nrs > 1 and beam is None else 1
@@ -384,7 +394,7 @@ class DotsOcrHipForCausalLM:
                 self.engine.set_sampling(0.0, 1.0, 0)
             self.engine.slots_reset()            # speculation changes only while no slot is occupied
             Engine.speculation_on(self.engine, spec_k, prompt_lookup_min, prompt_lookup_max, **spec)
-        call = CallSettings(rules=rules, guide=guide, ngram=ngram, stop=stop, nrs=nrs, beam=beam, suffixes=suffixes, prefill_chunk=prefill_chunk,
+        call = CallSettings(rules=rules, guide=guide, ngram=ngram, stop=stop, loop=loop, nrs=nrs, beam=beam, suffixes=suffixes, prefill_chunk=prefill_chunk,
                             image_keys=(image_keys or [None] * int(input_ids.shape[0])) if enable_prefix_caching else None, streamer=streamer)
         try:
             return self._generate(input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens, eos_token_id, pad_token_id, continuous,
@@ -488,7 +498,7 @@ class DotsOcrHipForCausalLM:
 
         def request(b, pix=None, g=None):        # sequence b with the call's row settings: what both paths give their rows
             return Request(prompts[b], pix, g, max_new_tokens, sampling=row_sp(b) if row_sp else None, rules=call.rules, guide=call.guide,
-                           ngram=call.ngram, n=1 if suffixes else nrs, stop=call.stop, suffixes=suffixes)
+                           ngram=call.ngram, n=1 if suffixes else nrs, stop=call.stop, loop=call.loop, suffixes=suffixes)
         if continuous:
             reqs = []
             for b in range(B):

@@ -27,6 +27,12 @@ from .prompts import dict_promptmode_to_prompt
 _LAYOUT_MODES = ("prompt_layout_all_en", "prompt_layout_only_en", "prompt_grounding_ocr")
 
 
+class PageText(str):
+    """A page's response with what the loop guard found in it: repetition = {"period", "span"} when the page was ended
+    because its output cycled (the text then keeps one copy of the cycle), else None."""
+    repetition = None
+
+
 class DotsOCRParser:
     """parse image or pdf file"""
 
@@ -36,8 +42,15 @@ class DotsOCRParser:
                  hf_max_new_tokens=24000, guided=False, no_repeat_ngram_size=None, no_repeat_ngram_window=None,
                  no_repeat_ngram_whitelist=None, speculative_ngram=None, prompt_lookup_min=2, prompt_lookup_max=4, stop=None,
                  speculative_rows=None, num_beams=None, length_penalty=1.0, speculative_guided=False, speculative_shaped=None,
-                 prefill_chunk=None, enable_prefix_caching=False, speculative_logprobs=False):
+                 prefill_chunk=None, enable_prefix_caching=False, speculative_logprobs=False, loop_guard=None):
         self.dpi = dpi
+        # loop guard, opt-in: True (loop_guard.LoopRule's defaults), a LoopRule or a dict of its fields.  The server request
+        # carries `loop_guard`; the in-process model generates with it, the page's ids are cut back to one copy of the cycle
+        # (loop_guard.trimmed) and its result carries "repetition".  With the default None the request and the call are exactly what they were.
+        from .loop_guard import as_rule
+        self.loop_guard = as_rule(loop_guard)
+        if self.loop_guard is not None and num_beams and int(num_beams) != 1:
+            raise ValueError("num_beams cannot be combined with loop_guard")
         # prefix caching, opt-in over prefill_chunk: the in-process model keeps the full KV pages of the pages it has read and
         # starts a page it meets again — with another prompt, or in a retry — behind them, keyed on the decoded image's bytes and size.  A
         # server caches by its own --enable-prefix-caching flag: requests carry nothing.
@@ -139,6 +152,14 @@ class DotsOCRParser:
         layout = {dict_promptmode_to_prompt[m] for m in ("prompt_layout_all_en", "prompt_layout_only_en")}
         return self.guided and all(p in layout for p in prompts)
 
+    def _loop_field(self) -> dict:
+        """the server request's `loop_guard` field, when the guard is on.  The server ends the page at the firing token and says so on the
+        choice; the helpers of the server path hand back the text alone, so such a page is neither cut back nor marked here"""
+        if self.loop_guard is None:
+            return {}
+        import dataclasses
+        return {"loop_guard": dataclasses.asdict(self.loop_guard)}
+
     def _ngram_fields(self) -> dict:
         """the no_repeat_ngram_* settings that are set, under the names generate() and the server share"""
         return {k: v for k, v in (("no_repeat_ngram_size", self.no_repeat_ngram_size), ("no_repeat_ngram_window", self.no_repeat_ngram_window),
@@ -166,6 +187,8 @@ class DotsOCRParser:
             if getattr(self.model.engine, "token_bytes", None) is None:
                 self.model.engine.set_token_bytes(self.processor.guide_token_bytes())
             kw["stop_strings"] = self.stop
+        if self.loop_guard is not None:
+            kw["loop_guard"] = self.loop_guard
         if self.num_beams:
             kw.update(num_beams=self.num_beams, length_penalty=self.length_penalty, do_sample=False)
         if self.prefill_chunk is not None:
@@ -173,9 +196,9 @@ class DotsOCRParser:
         if self.enable_prefix_caching:
             kw.update(enable_prefix_caching=True, image_keys=[self._image_key(im) for im in images])
         generated = self.model.generate(**inputs, max_new_tokens=self.hf_max_new_tokens, **kw)
-        trimmed = [out[len(inp):] for inp, out in zip(inputs.input_ids, generated)]
+        trimmed, loops = self._cut_loops([out[len(inp):] for inp, out in zip(inputs.input_ids, generated)])
         texts = self.processor.batch_decode(trimmed, skip_special_tokens=True, clean_up_tokenization_spaces=False)
-        return self._cut_at_stops(trimmed, texts)
+        return self._mark_loops(self._cut_at_stops(trimmed, texts), loops)
 
     @staticmethod
     def _image_key(image, grid=None) -> Optional[bytes]:
@@ -192,6 +215,32 @@ class DotsOCRParser:
     def _chunk_kw(self) -> dict:
         kw = {} if self.prefill_chunk is None else {"prefill_chunk": self.prefill_chunk}
         return dict(kw, prefix_caching=True) if self.enable_prefix_caching else kw
+
+    def _cut_loops(self, rows):
+        """rows the loop guard ended (their last token is the firing one) cut back to one copy of the cycle -> (rows, the hits or None)"""
+        if self.loop_guard is None:
+            return rows, [None] * len(rows)
+        from .loop_guard import last_loop, trimmed
+        pad, hits = self.processor.tokenizer.pad_token_id, []
+        rows = list(rows)
+        for i, ids in enumerate(rows):
+            toks = [int(t) for t in ids.tolist()]
+            while toks and toks[-1] == pad:
+                toks.pop()
+            hits.append(last_loop(toks, self.loop_guard))
+            if hits[-1] is not None:
+                rows[i] = ids[:len(trimmed(toks, hits[-1]))]
+        return rows, hits
+
+    @staticmethod
+    def _mark_loops(texts, loops) -> List[str]:
+        out = []
+        for text, hit in zip(texts, loops):
+            if hit is not None:
+                text = PageText(text)
+                text.repetition = {"period": int(hit[1]), "span": int(hit[2])}
+            out.append(text)
+        return out
 
     def _cut_at_stops(self, trimmed, texts) -> List[str]:
         if self.stop:                               # the ids end at the token that completed a match: cut the text where the match starts
@@ -228,18 +277,20 @@ class DotsOCRParser:
             if getattr(self.model.engine, "token_bytes", None) is None:
                 self.model.engine.set_token_bytes(self.processor.guide_token_bytes())
             kw["stop_strings"] = self.stop
+        if self.loop_guard is not None:
+            kw["loop_guard"] = self.loop_guard
         dev = inputs["input_ids"].device
         generated = self.model.generate(input_ids=torch.tensor([prefix], dtype=torch.long, device=dev), pixel_values=inputs["pixel_values"],
                                         image_grid_thw=inputs["image_grid_thw"], max_new_tokens=self.hf_max_new_tokens,
                                         prompt_suffixes=suffixes, **kw)
-        trimmed = [out[len(prefix):] for out in generated]
+        trimmed, loops = self._cut_loops([out[len(prefix):] for out in generated])
         texts = self.processor.batch_decode(trimmed, skip_special_tokens=True, clean_up_tokenization_spaces=False)
-        return self._cut_at_stops(trimmed, texts)
+        return self._mark_loops(self._cut_at_stops(trimmed, texts), loops)
 
     def _inference_prompts_with_vllm(self, image, prompts) -> List[str]:
         """one request that carries the server's `prompts` field: choice i answers prompts[i]"""
         from dots_ocr.model.inference import inference_prompts_with_vllm
-        extra = {**self._ngram_fields(), **({"stop": self.stop} if self.stop else {})}
+        extra = {**self._ngram_fields(), **({"stop": self.stop} if self.stop else {}), **self._loop_field()}
         return inference_prompts_with_vllm(image, prompts, model_name=self.model_name, protocol=self.protocol, ip=self.ip, port=self.port,
                                            temperature=self.temperature, top_p=self.top_p, max_completion_tokens=self.max_completion_tokens,
                                            **({"extra_body": extra} if extra else {}))
@@ -329,7 +380,7 @@ class DotsOCRParser:
     def _inference_with_vllm(self, image, prompt):
         from dots_ocr.model.inference import inference_with_vllm
         extra = {**({"guided_layout": True} if self._guided_layout([prompt]) else {}), **self._ngram_fields(),
-                 **({"stop": self.stop} if self.stop else {}),
+                 **({"stop": self.stop} if self.stop else {}), **self._loop_field(),
                  **({"use_beam_search": True, "beam_width": self.num_beams, "length_penalty": self.length_penalty} if self.num_beams else {})}
         return inference_with_vllm(image, prompt, model_name=self.model_name, protocol=self.protocol, ip=self.ip,
                                    port=self.port, temperature=0.0 if self.num_beams else self.temperature,
@@ -363,6 +414,8 @@ class DotsOCRParser:
     def _save(self, response, origin_image, image, prompt_mode, save_dir, save_name, page_idx, min_pixels, max_pixels):
         ih, iw = smart_resize(image.height, image.width)
         result = {"page_no": page_idx, "input_height": ih, "input_width": iw}
+        if getattr(response, "repetition", None):   # the loop guard ended the page
+            result["repetition"] = dict(response.repetition)
         j = os.path.join(save_dir, f"{save_name}.json")
         jpg = os.path.join(save_dir, f"{save_name}.jpg")
         md = os.path.join(save_dir, f"{save_name}.md")

@@ -2,7 +2,7 @@
 settings the selection stage does not own (logprobs, stream).  The scheduler, generate()'s static batches and the server's capability
 probes all walk ROW_FEATURES; a new per-row feature is one entry here (DESIGN §6.1 lists the other places to touch).
 
-Host-only: no torch, no engine import.  A "request" is anything with the seven fields (scheduler.Request); `held` is the caller's record
+Host-only: no torch, no engine import.  A "request" is anything with the eight fields (scheduler.Request); `held` is the caller's record
 of what its rows hold, row -> {feature name -> the value given to the engine}, and has no entry for a row that holds nothing."""
 from __future__ import annotations
 
@@ -51,6 +51,7 @@ ROW_FEATURES = (
     RowFeature("guide", "set_row_guide", _field("guide"), (None,), "a guide", ("set_row_guide",), True, FORGET, True),
     RowFeature("ngram", "set_row_ngram", _field("ngram"), (None,), "an n-gram rule", ("set_row_ngram",), False, CLEAR_FIRST, False),
     RowFeature("stop", "set_row_stop", _stop, (None,), "stop strings", ("set_row_stop",), True, FORGET, True),
+    RowFeature("loop", "set_row_loop", _field("loop"), (None,), "a loop guard", ("set_row_loop", "row_loop_hit"), False, CLEAR_FIRST, False),
     RowFeature("stream", "set_row_stream", lambda engine, r, index: (True,), (False,), None, ("slots_drain", "set_row_stream"), False, FORGET,
                False),
 )

@@ -58,6 +58,9 @@ class Request:
                                                 # match length, match id) or None — as a list in index order when n > 1
     include_stop_str_in_output: bool = False    # vLLM's field: where text built from the tokens is cut (stop_strings.cut_text); the tokens
                                                 # always end at the one that completed the match
+    loop: Optional[object] = None               # loop_guard.LoopRule: the row ends on the device at the token after which its output
+                                                # has cycled for the rule's span.  A finished request carries loop_hit = Engine.row_loop_hit(slot)
+                                                # — (token index, period, span) or None — as a list in index order when n > 1
     num_beams: Optional[int] = None             # beam search: a group of 2 .. 8 beams from one tower and one prefill, in num_beams slots.
                                                 # vLLM's beam-search semantics with HF's length normalisation, not HF's BeamSearchScorer.  A finished
                                                 # request carries outputs (the num_return best hypotheses, best first, a final EOS included),
@@ -285,7 +288,7 @@ class ContinuousBatcher:
         if req.suffixes is not None:
             raise RequestRejected("score cannot be combined with suffixes")
         for name, what in (("sampling", "sampling parameters"), ("guide", "a guide"), ("rules", "logit rules"), ("ngram", "an n-gram rule"),
-                           ("stop", "stop strings"), ("logprobs", "logprobs (score_top_logprobs sets the top lists of the scored tokens)")):
+                           ("stop", "stop strings"), ("loop", "a loop guard"), ("logprobs", "logprobs (score_top_logprobs sets the top lists of the scored tokens)")):
             if getattr(req, name) is not None:
                 raise RequestRejected(f"a score request selects nothing and takes no {what}")
         t = req.score_top_logprobs
@@ -371,7 +374,8 @@ class ContinuousBatcher:
             if not plain:
                 raise RequestRejected("a beam request takes no sampling parameters other than temperature = 0 (no top_k, top_p or penalties)")
             req.sampling = None                      # plain greedy parameters say nothing a beam row could honour or break
-        for name, what in (("rules", "logit rules"), ("guide", "a guide"), ("ngram", "an n-gram rule"), ("stop", "stop strings"), ("logprobs", "logprobs")):
+        for name, what in (("rules", "logit rules"), ("guide", "a guide"), ("ngram", "an n-gram rule"), ("stop", "stop strings"), ("loop", "a loop guard"),
+                           ("logprobs", "logprobs")):
             if getattr(req, name) is not None:
                 raise RequestRejected(f"a beam request takes no {what}")
 
@@ -785,6 +789,9 @@ class ContinuousBatcher:
                 hit = None
                 if req.stop is not None:             # read before the release clears the row's automaton and its hit record
                     hit = self.engine.row_stop_hit(s)
+                loop_hit = None
+                if req.loop is not None:             # likewise: the release clears the row's rule and its hit record
+                    loop_hit = self.engine.row_loop_hit(s)
                 if req.stream is not None:
                     # its last tokens, before it is reported: what the drain brought, and — a row that held more than one drain
                     # delivers — the rest of what was just read
@@ -794,20 +801,24 @@ class ContinuousBatcher:
                 if req.seqs == 1:
                     if req.stop is not None:
                         req.stop_hit = hit
+                    if req.loop is not None:
+                        req.loop_hit = loop_hit
                     if req.logprobs is not None:
                         req.logprobs_out = lp_out
                     done.append((rid, req, toks))
                 else:
                     # one sequence of n: its slot goes back now, the request is reported once, when its last sequence has finished
-                    req._parts[self._seq_index.pop(s)] = (toks, lp_out, req.kv_truncated, hit)
+                    req._parts[self._seq_index.pop(s)] = (toks, lp_out, req.kv_truncated, hit, loop_hit)
                     if len(req._parts) == req.seqs:
                         parts = [req._parts[j] for j in range(req.seqs)]
-                        req.outputs = [t for t, _, _, _ in parts]
+                        req.outputs = [part[0] for part in parts]
                         if req.logprobs is not None:
-                            req.logprobs_out = [l for _, l, _, _ in parts]
+                            req.logprobs_out = [part[1] for part in parts]
                         if req.stop is not None:
-                            req.stop_hit = [h for _, _, _, h in parts]
-                        req.kv_truncated_each = [k for _, _, k, _ in parts]
+                            req.stop_hit = [part[3] for part in parts]
+                        if req.loop is not None:
+                            req.loop_hit = [part[4] for part in parts]
+                        req.kv_truncated_each = [part[2] for part in parts]
                         req.kv_truncated = any(req.kv_truncated_each)
                         del req._parts
                         done.append((rid, req, req.outputs[0]))

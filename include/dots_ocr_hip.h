@@ -329,6 +329,43 @@ int dots_stop_destroy(DotsEngine* e, int32_t handle);
 int dots_set_row_stop(DotsEngine* e, int row, int32_t handle, int min_tokens);
 int dots_row_stop_hit(DotsEngine* e, int row, int32_t* out);
 
+/* ---- Loop guard: a row ends at the token after which its output has started to cycle.  Opt-in per row; the check runs on
+ * the device behind the commit of every token of the row, so the end is exact inside captured decode chunks and in dots_generate, and an
+ * ended row writes no further KV.
+ *
+ * The rule: let out[0 .. n] be the row's output (the prefill's token is index 0) and L(p) = max(repeats * p, min_span).  After the token at
+ * index n is committed, period p in [min_period, max_period] fires iff n + 1 >= L(p) and out[i] == out[i - p] for every i in
+ * [n + 1 - L(p) + p, n].  The row fires at the first n at which any period fires, with the smallest such p: the firing token is appended
+ * whole and is the row's last.  Ids are compared as ids.  A token that finishes the row as an engine EOS id or a stop id of its
+ * DotsLogitRules is not checked; a hit at the token that reaches the generation cap is still recorded; a stop string that matches at the
+ * same token leaves its own record too.  The window is the output since it last started over: a prefill, dots_slots_extend and setting
+ * the rule start it over.
+ *
+ * dots_set_row_loop   row `row` (a slot, or sequence `row` of a static batch) holds the rule with no hit and its counters at zero (NULL:
+ *                     none), written in stream order by one small kernel; the first call allocates the counters (max_batch-independent:
+ *                     256 KiB) and drops the captured decode graphs once, later calls keep them.  dots_slot_release / dots_slots_reset
+ *                     clear the row; dots_slots_fork gives every child the source's rule.  A row with a rule is selected by the per-row
+ *                     stage (with the engine-wide setting as it stands at the call if it has no DotsSamplingParams of its own) and verifies
+ *                     no draft of a speculating step, whatever dots_set_speculation_rows says.  Refused (DOTS_E_INVALID): limits outside
+ *                     1 <= min_period <= max_period <= DOTS_MAX_LOOP_PERIOD, 2 <= repeats <= 64, 0 <= min_span <= 65535; a row of a beam
+ *                     group.  dots_slots_beam refuses a source that holds a rule, dots_slots_score a slot that does (DOTS_E_STATE).
+ * dots_row_loop_hit   out[3] = {index of the firing token, the period, the span L(period)}, or {-1, 0, 0}: no hit (yet), or the row holds
+ *                     no rule.  Synchronises.
+ * dots_loop_probe     a test entry: case c is the history ids_host[c * stride + 0 .. lens_host[c]), fed id by id through the device check
+ *                     under `rule` from zeroed counters; hits_out_host[c * 3 ..] = the first hit as dots_row_loop_hit reports it.  One
+ *                     launch, one workgroup per case.  Synchronises. */
+#define DOTS_MAX_LOOP_PERIOD 1024
+typedef struct DotsLoopRule {
+    int32_t min_period;          /* 1 .. max_period */
+    int32_t max_period;          /* .. DOTS_MAX_LOOP_PERIOD */
+    int32_t repeats;             /* 2 .. 64: the cycle must stand this many times ... */
+    int32_t min_span;            /* 0 .. 65535: ... over at least this many tokens */
+} DotsLoopRule;
+int dots_set_row_loop(DotsEngine* e, int row, const DotsLoopRule* r);
+int dots_row_loop_hit(DotsEngine* e, int row, int32_t* out);
+int dots_loop_probe(DotsEngine* e, const int32_t* ids_host, const int32_t* lens_host, int cases, int stride, const DotsLoopRule* rule,
+                    int32_t* hits_out_host);
+
 /* ---- N-gram speculative decoding: opt-in, engine-wide, slot mode only.  With k drafts a slot occupies up to
  * k + 1 rows of one decode step: row j carries token j of (last committed token, draft 1 .. k) at context ctx + j on the slot's own KV
  * pages, and sees the K/V rows 0 .. j - 1 appended in the step's qkv launch.  Every decode kernel is row-independent and batch-invariant
