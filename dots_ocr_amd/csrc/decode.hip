@@ -32,6 +32,7 @@
 #include "launch.h"
 #include "loop_dev.h"
 #include "select_dev.h"
+#include "share_plan.h"
 #include "step_dev.h"
 
 namespace {
@@ -149,14 +150,20 @@ constexpr int AT_LD = 132;
 
 // KVT = uint8_t: the fp8 pool (layout in the header): a page is 8 + 8 sixteen-byte loads per lane, converted to the bf16 fragments of the bf16 pool
 // in registers; s_K = kv_scales[hkv][0] is folded into scale_log2e, the partial O is multiplied by s_V = kv_scales[hkv][1] as it is written.
-template <int NW, bool ONE, typename KVT = bf16_t>
+// SKIP (a step with a non-empty shared-prefix plan): a workgroup whose (row, split) a shared item covers — bit `split` of
+// skip[row] — returns at once; decode_attn_shared_kernel writes that partial.  Every other workgroup runs the code of SKIP = false.
+template <int NW, bool ONE, typename KVT = bf16_t, bool SKIP = false>
 __global__ __launch_bounds__(NW * 64, ONE && NW <= 4 ? 3 : 2) void decode_attn_kernel(const bf16_t* __restrict__ q, const KVT* __restrict__ pool,
                                                           const int32_t* __restrict__ ctx_len, const int32_t* __restrict__ block_table,
                                                           int max_pages, float* __restrict__ part_o, float* __restrict__ part_ml,
-                                                          int Hq, int Hkv, int n_splits, float scale_log2e, const float* __restrict__ kv_scales) {
+                                                          int Hq, int Hkv, int n_splits, float scale_log2e, const float* __restrict__ kv_scales,
+                                                          const uint64_t* __restrict__ skip) {
     constexpr bool KV8 = sizeof(KVT) == 1;
     extern __shared__ __attribute__((aligned(16))) char at_smem[];
     const int split = blockIdx.x, hkv = blockIdx.y, b = blockIdx.z;
+    if constexpr (SKIP) {
+        if ((skip[b] >> split) & 1) return;
+    }
     const int group = Hq / Hkv;
     float* lds_o = reinterpret_cast<float*>(at_smem);                    // [NW][group][AT_LD]
     float* lds_m = lds_o + NW * group * AT_LD;                           // [NW][16]
@@ -323,6 +330,168 @@ __global__ __launch_bounds__(NW * 64, ONE && NW <= 4 ? 3 : 2) void decode_attn_k
         if (d == 0) { part_ml[base * 2] = m; part_ml[base * 2 + 1] = lsum; }
     }
     TRACE(4);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Shared-prefix decode attention.  grid (item capacity, Hkv), 4 waves; an ITEM of the host's plan (share_plan.h) is a KV
+// split and the rows whose block tables name the same four full prompt pages there.  Wave w fetches page 4 * split + w ONCE — through the
+// first member's block-table row — and keeps it in registers (bf16: K 16 + V 16 fragments; fp8: the raw 8 + 8 loads, converted per pass,
+// exactly); then the members go through in passes of 16 / group rows: MFMA column i carries head i % group of member i / group, the
+// columns past the live ones are zero.  A pass is decode_attn_kernel<4, true> from page_step on, statement for statement: S^T, the
+// column-wise softmax, O^T, the wave partial, the LDS combine of the four waves in the same fixed order and the stores at the member
+// row's own (b, hkv, split, j) index.  No MFMA column, no lane's softmax and no combine entry reads another column, so every partial is
+// the one the per-row kernel writes, bit for bit (tests/test_shared_prefix_gpu.py); the `key < ctx` select is gone because every key of a
+// shared page lies inside every member's context.  Workgroups at or past the live item count exit at once: the grid is the capacity a
+// captured step was keyed on, the count lives in device memory.
+// LDS: combine buffer [4][16 / group * group][AT_LD] | m, l [4][16] each
+template <typename KVT>
+__global__ __launch_bounds__(256, 2) void decode_attn_shared_kernel(const bf16_t* __restrict__ q, const KVT* __restrict__ pool,
+                                                                    const int32_t* __restrict__ block_table, int max_pages, float* __restrict__ part_o,
+                                                                    float* __restrict__ part_ml, int Hq, int Hkv, int n_splits, float scale_log2e,
+                                                                    const float* __restrict__ kv_scales, const int32_t* __restrict__ plan) {
+    constexpr bool KV8 = sizeof(KVT) == 1;
+    constexpr int NW = 4;
+    extern __shared__ __attribute__((aligned(16))) char at_smem[];
+    const int item = blockIdx.x, hkv = blockIdx.y;
+    if (item >= plan[0]) return;
+    const int split = plan[SHARE_ITEMS_OFF + 3 * item], n_mem = plan[SHARE_ITEMS_OFF + 3 * item + 2];
+    const int32_t* mem = plan + SHARE_MEMBERS_OFF + plan[SHARE_ITEMS_OFF + 3 * item + 1];
+    const int group = Hq / Hkv, per = 16 / group, live = per * group;      // rows and live columns of a pass
+    float* lds_o = reinterpret_cast<float*>(at_smem);                    // [NW][live][AT_LD]
+    float* lds_m = lds_o + NW * live * AT_LD;                            // [NW][16]
+    float* lds_l = lds_m + NW * 16;                                      // [NW][16]
+    const int l = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), i = l & 15, g = l >> 4;
+    const int page = block_table[mem[0] * max_pages + min(split * NW + w, max_pages - 1)];
+    float s_v = 1.0f;
+    if constexpr (KV8) {
+        scale_log2e *= kv_scales[hkv * 2];
+        s_v = kv_scales[hkv * 2 + 1];
+    }
+    // the page, once for every member
+    const KVT* kp = pool + ((size_t)(page * Hkv + hkv) * 2) * PAGE_ELEMS;
+    const KVT* vp = kp + PAGE_ELEMS;
+    bf16x8 kf[16], va[8], vb[8];
+    u32x4 k8[8], va8[4], vb8[4];
+    if constexpr (KV8) {
+#pragma unroll
+        for (int c2 = 0; c2 < 8; ++c2) k8[c2] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(kp + (size_t)(c2 * 64 + l) * 16));
+#pragma unroll
+        for (int c2 = 0; c2 < 4; ++c2) va8[c2] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(vp + (size_t)(c2 * 64 + l) * 16));
+#pragma unroll
+        for (int c2 = 0; c2 < 4; ++c2) vb8[c2] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(vp + (size_t)((c2 + 4) * 64 + l) * 16));
+    } else {
+#pragma unroll
+        for (int c = 0; c < 16; ++c) kf[c] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(kp + (size_t)(c * 64 + l) * 8));
+#pragma unroll
+        for (int c = 0; c < 8; ++c) va[c] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(vp + (size_t)(c * 64 + l) * 8));
+#pragma unroll
+        for (int c = 0; c < 8; ++c) vb[c] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(vp + (size_t)((c + 8) * 64 + l) * 8));
+    }
+    const int mi = i / group, head = i - mi * group;          // this lane's column: head `head` of the pass's member mi
+    // Q fragments of a pass (B operand): lane (column i, g) holds Q[member][hkv*group + head][32kk + 8g .. +7]; a pass's are requested one
+    // pass ahead, so that their round trip flies under the softmax, the O^T MFMAs and the combine of the pass before
+    u32x4 qraw[4];
+    auto request_q = [&](int r0) {
+        const int b = mem[min(r0 + mi, n_mem - 1)];
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) qraw[kk] = *reinterpret_cast<const u32x4*>(q + ((size_t)b * Hq + hkv * group + head) * 128 + kk * 32 + g * 8);
+    };
+    request_q(0);
+    for (int r0 = 0; r0 < n_mem; r0 += per) {
+        const bool col_live = i < live && r0 + mi < n_mem;
+        bf16x8 qf[4];
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) {
+            const u32x4 z = {0, 0, 0, 0};
+            qf[kk] = __builtin_bit_cast(bf16x8, col_live ? qraw[kk] : z);
+        }
+        f32x4 o[8];
+#pragma unroll
+        for (int dg = 0; dg < 8; ++dg) o[dg] = f32x4{0, 0, 0, 0};
+        float m_run = -1e30f, l_run = 0.f;
+        // ---- the arithmetic of decode_attn_kernel<4, true>::page_step(first = true), statement for statement
+        // S^T[kg] : rows = keys 16kg + 4g + r, col = q column i
+        f32x4 s[4];
+#pragma unroll
+        for (int kg = 0; kg < 4; ++kg) {
+            s[kg] = f32x4{0, 0, 0, 0};
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk) {
+                if constexpr (KV8) s[kg] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kv8_frag(k8[(kg * 4 + kk) >> 1], (kg * 4 + kk) & 1), qf[kk], s[kg], 0, 0, 0);
+                else s[kg] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[kg * 4 + kk], qf[kk], s[kg], 0, 0, 0);
+            }
+        }
+        if (r0 + per < n_mem) request_q(r0 + per);
+        float mx = -INFINITY;
+#pragma unroll
+        for (int kg = 0; kg < 4; ++kg)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) mx = fmaxf(mx, s[kg][r]);
+        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        const float m_new = fmaxf(m_run, mx * scale_log2e);
+        const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+        m_run = m_new;
+        float psum = 0.f;
+        bf16x8 pf[2];
+#pragma unroll
+        for (int slab = 0; slab < 2; ++slab) {
+            u32x4 pk;
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                float pv[4];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    pv[r] = __builtin_amdgcn_exp2f(fmaf(s[slab * 2 + t][r], scale_log2e, -m_new));
+                    psum += pv[r];
+                }
+                pk[t * 2] = pack_bf2(pv[0], pv[1]);
+                pk[t * 2 + 1] = pack_bf2(pv[2], pv[3]);
+            }
+            pf[slab] = __builtin_bit_cast(bf16x8, pk);
+        }
+        l_run = l_run * alpha + psum;
+        if constexpr (KV8) {
+#pragma unroll
+            for (int dg = 0; dg < 8; ++dg) o[dg] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kv8_frag(va8[dg >> 1], dg & 1), pf[0], o[dg], 0, 0, 0);
+#pragma unroll
+            for (int dg = 0; dg < 8; ++dg) o[dg] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kv8_frag(vb8[dg >> 1], dg & 1), pf[1], o[dg], 0, 0, 0);
+        } else {
+#pragma unroll
+            for (int dg = 0; dg < 8; ++dg) o[dg] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(va[dg], pf[0], o[dg], 0, 0, 0);
+#pragma unroll
+            for (int dg = 0; dg < 8; ++dg) o[dg] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vb[dg], pf[1], o[dg], 0, 0, 0);
+        }
+        // wave partial: l over the 4 lane groups that share a q column
+        l_run += __shfl_xor(l_run, 16, 64);
+        l_run += __shfl_xor(l_run, 32, 64);
+        if (g == 0) { lds_m[w * 16 + i] = m_run; lds_l[w * 16 + i] = l_run; }
+        if (i < live) {
+#pragma unroll
+            for (int dg = 0; dg < 8; ++dg) *reinterpret_cast<f32x4*>(lds_o + (w * live + i) * AT_LD + dg * 16 + 4 * g) = o[dg];     // O^T[d = 16dg+4g+r][column i]
+        }
+        __syncthreads();
+        // combine the NW waves: thread -> (column, d) pairs; column c is head c % group of member c / group
+        for (int it = threadIdx.x; it < live * 128; it += NW * 64) {
+            const int col = it >> 7, d = it & 127, mm = col / group, j = col - mm * group;
+            if (r0 + mm >= n_mem) continue;
+            float m = lds_m[col];
+#pragma unroll
+            for (int ww = 1; ww < NW; ++ww) m = fmaxf(m, lds_m[ww * 16 + col]);
+            float acc = 0.f, lsum = 0.f;
+#pragma unroll
+            for (int ww = 0; ww < NW; ++ww) {
+                const float f = __builtin_amdgcn_exp2f(lds_m[ww * 16 + col] - m);
+                acc += lds_o[(ww * live + col) * AT_LD + d] * f;
+                lsum += lds_l[ww * 16 + col] * f;
+            }
+            const size_t base = (((size_t)mem[r0 + mm] * Hkv + hkv) * n_splits + split) * group + j;
+            if constexpr (KV8) part_o[base * 128 + d] = acc * s_v;
+            else part_o[base * 128 + d] = acc;
+            if (d == 0) { part_ml[base * 2] = m; part_ml[base * 2 + 1] = lsum; }
+        }
+        __syncthreads();                                                 // the next pass overwrites the combine buffer
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -972,10 +1141,31 @@ int decode_attn_stream_wgs(int B, int Hkv, int n_splits, int max_pages, int part
 
 hipError_t launch_decode_attn(hipStream_t s, const bf16_t* q, const void* pool_layer, const int32_t* ctx_len,
                               const int32_t* block_table, int max_pages, float* part_o, float* part_ml,
-                              int B, int Hq, int Hkv, int n_splits, float scale, int part_cus, int stream_mode, const float* kv_scales) {
+                              int B, int Hq, int Hkv, int n_splits, float scale, int part_cus, int stream_mode, const float* kv_scales,
+                              const SharePlanDev* share) {
     if (Hq % Hkv != 0 || Hq / Hkv > 16) return hipErrorInvalidValue;
     const float sl = scale * 1.44269504088896340736f;
     const int nw = decode_attn_waves(), group = Hq / Hkv;
+    if (share && share->cap > 0) {
+        // a non-empty shared-prefix plan (the planner leaves it empty unless waves == 4 and every wave owns one page): the
+        // items' partials from the shared kernel, every other (row, split) from the per-split kernel's SKIP instantiation — also where the
+        // streaming kernel was selected.  One stream, disjoint partial slots
+        if (!share->plan || nw != 4 || (int64_t)n_splits * nw < max_pages || n_splits > SHARE_MAX_SPLITS || B > SHARE_MAX_ROWS) return hipErrorInvalidValue;
+        const size_t lds_sh = ((size_t)4 * (16 / group * group) * AT_LD + 2 * 4 * 16) * sizeof(float), lds = ((size_t)4 * group * AT_LD + 2 * 4 * 16) * sizeof(float);
+        const uint64_t* skip = reinterpret_cast<const uint64_t*>(share->plan + SHARE_MASK_OFF);
+        if (kv_scales) {
+            hipLaunchKernelGGL((decode_attn_shared_kernel<uint8_t>), dim3(share->cap, Hkv), dim3(256), lds_sh, s, q, (const uint8_t*)pool_layer, block_table, max_pages, part_o,
+                               part_ml, Hq, Hkv, n_splits, sl, kv_scales, share->plan);
+            hipLaunchKernelGGL((decode_attn_kernel<4, true, uint8_t, true>), dim3(n_splits, Hkv, B), dim3(256), lds, s, q, (const uint8_t*)pool_layer, ctx_len, block_table,
+                               max_pages, part_o, part_ml, Hq, Hkv, n_splits, sl, kv_scales, skip);
+        } else {
+            hipLaunchKernelGGL((decode_attn_shared_kernel<bf16_t>), dim3(share->cap, Hkv), dim3(256), lds_sh, s, q, (const bf16_t*)pool_layer, block_table, max_pages, part_o,
+                               part_ml, Hq, Hkv, n_splits, sl, nullptr, share->plan);
+            hipLaunchKernelGGL((decode_attn_kernel<4, true, bf16_t, true>), dim3(n_splits, Hkv, B), dim3(256), lds, s, q, (const bf16_t*)pool_layer, ctx_len, block_table,
+                               max_pages, part_o, part_ml, Hq, Hkv, n_splits, sl, nullptr, skip);
+        }
+        return hipGetLastError();
+    }
     if (const int wgs = decode_attn_stream_wgs(B, Hkv, n_splits, max_pages, part_cus, stream_mode, kv_scales != nullptr)) {
         const size_t lds_s = (size_t)ST_NW * ST_PAGE_BYTES + ((size_t)ST_NW * group * AT_LD + 2 * ST_NW * 16) * sizeof(float) + 2 * MAX_DECODE_ROWS * sizeof(int);
         return launch_dyn_lds<decode_attn_stream_kernel>(dim3(wgs), dim3(ST_NW * 64), lds_s, s, q, (const bf16_t*)pool_layer, ctx_len, block_table, max_pages, part_o, part_ml,
@@ -990,10 +1180,10 @@ hipError_t launch_decode_attn(hipStream_t s, const bf16_t* q, const void* pool_l
         constexpr bool ONE = decltype(onev)::value;
         if (kv_scales)
             hipLaunchKernelGGL((decode_attn_kernel<NW, ONE, uint8_t>), grid, dim3(NW * 64), lds, s, q, (const uint8_t*)pool_layer, ctx_len, block_table, max_pages, part_o, part_ml,
-                               Hq, Hkv, n_splits, sl, kv_scales);
+                               Hq, Hkv, n_splits, sl, kv_scales, nullptr);
         else
             hipLaunchKernelGGL((decode_attn_kernel<NW, ONE>), grid, dim3(NW * 64), lds, s, q, (const bf16_t*)pool_layer, ctx_len, block_table, max_pages, part_o, part_ml,
-                               Hq, Hkv, n_splits, sl, nullptr);
+                               Hq, Hkv, n_splits, sl, nullptr, nullptr);
     };
     auto go_nw = [&](auto nwv) { if (one) go(nwv, std::true_type{}); else go(nwv, std::false_type{}); };
     switch (nw) {

@@ -22,6 +22,7 @@
 #include "kernels.h"
 #include "prefix_cache.h"
 #include "row_stage.h"
+#include "share_plan.h"
 #include "switches.h"
 
 struct Tensor {
@@ -275,6 +276,17 @@ struct DotsEngine {
     int slot_ctx_ub[DOTS_MAX_BATCH] = {0}; // host-side upper bound of the slot's context: prompt + decode steps issued (finished rows stop earlier)
     int slot_done[DOTS_MAX_BATCH] = {0};   // seen finished at the last poll: grows no more
     int32_t *d_sel = nullptr, *d_sel_new = nullptr, *d_max_len = nullptr, *p_dst = nullptr;
+    // shared-prefix attention (dots_set_shared_prefix_attention): the switch; share_dirty, raised with sel_dirty (whatever
+    // changes slot_pages, slot_active, parked or slot_prompt) and lowered by the decode chunk that recomputes the plan; the plan's host and
+    // device images (share_plan.h), allocated by the first chunk with the switch on; share_cap: the live item count rounded up to
+    // SHARE_ITEM_QUANTUM (0: an empty plan — the step launches what it launches with the switch off); the last plan's counts and the
+    // KV pages (one page of one kv head of one layer each) the chunks so far did not read
+    bool share_on = false, share_dirty = true;
+    int32_t* d_share = nullptr;
+    std::vector<int32_t> h_share;
+    int share_cap = 0;
+    SharePlanCounts share_last{0, 0, 0, 0};
+    int64_t share_pages_saved = 0;
     const int32_t* sel_now = nullptr;      // selection mask of the next select_tokens() call
     // what an admission uploads asynchronously, staged here so that it outlives the call (as hp_pos / hp_last do): the rows going live
     // (rows_go_live), and the mask [DOTS_MAX_BATCH] and slot list [DOTS_MAX_BATCH] of a first-token selection (stage_new_rows)
@@ -352,10 +364,12 @@ struct DotsEngine {
     // launches that select the draft rows of guided slots under their guide), which shaped rows may (sspec: the
     // DOTS_SPEC_SHAPED_* bits that are switched on and held by some row — the draft rows' ban kernel and their shaped selection), whether
     // some row with logprobs may (lpspec: the draft rows' logprob pair and the accept record); engine-wide sampling changes drop
-    // the cache (dots_set_sampling), per-row ones live in device memory; beam: the group entries a step's beam kernels run over (0: none).  step_key() builds the key from the engine's state: a feature that
+    // the cache (dots_set_sampling), per-row ones live in device memory; beam: the group entries a step's beam kernels run over (0: none);
+    // share: the item capacity of a non-empty shared-prefix plan (the shared kernel's grid and the SKIP instantiation of the per-split
+    // kernel; 0: neither — the live item count itself is device memory).  step_key() builds the key from the engine's state: a feature that
     // changes what a step launches adds a member here and a line there
     struct StepKey {
-        int rows, splits, out_cap, n_eos, part, rowp, lp, rules, guided, ngram, spec, draw, gspec, sspec, lpspec, beam;
+        int rows, splits, out_cap, n_eos, part, rowp, lp, rules, guided, ngram, spec, draw, gspec, sspec, lpspec, beam, share;
         bool operator==(const StepKey& o) const { return std::memcmp(this, &o, sizeof(StepKey)) == 0; }
     };
     static_assert(std::has_unique_object_representations_v<StepKey>, "StepKey is compared bytewise: plain ints, no padding");
@@ -513,7 +527,11 @@ int prefill_advance(DotsEngine* e, int max_tokens, int32_t* remaining);
 inline bool slot_filling(const DotsEngine* e, int slot) { return slot >= 0 && slot < DOTS_MAX_BATCH && e->fill[slot].on; }
 void drop_fill(DotsEngine* e, int slot);      // the record only: the pages go with release_pages
 int decode_layers(DotsEngine* e, const int32_t* tokens, const int32_t* ctx_len, const int32_t* block_table, int B, int n_splits, int part, bool* pend,
-                  const float** pend_scale);
+                  const float** pend_scale, const SharePlanDev* share = nullptr);
+// the shared-prefix plan of the step as the engine stands: the plain slot step with the switch on and a non-empty plan, else {nullptr, 0}
+inline SharePlanDev share_plan_now(const DotsEngine* e) {
+    return e->share_on && e->slot_mode && !e->spec_k && e->share_cap > 0 ? SharePlanDev{e->d_share, e->share_cap} : SharePlanDev{nullptr, 0};
+}
 int decode_step_launches(DotsEngine* e, int n_splits, int part = 0);
 int splits_for_ctx(int max_ctx);
 int step_graph(DotsEngine* e, int rows, int n_splits, int out_cap, hipGraphExec_t* exec, int part = 0);

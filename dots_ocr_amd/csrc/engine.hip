@@ -283,6 +283,7 @@ DotsEngine::StepKey step_key(const DotsEngine* e, int rows, int n_splits, int ou
     k.sspec = spec_shapes(e);
     k.lpspec = spec_lps(e);
     k.beam = e->slot_mode ? e->n_beam_hi : 0;
+    k.share = out_cap == 0 ? share_plan_now(e).cap : 0;
     return k;
 }
 
@@ -740,7 +741,7 @@ void drop_fill(DotsEngine* e, int slot) {
 // are the slots' own arrays in a plain step and step-private ones in a speculating step and in a chunk of dots_slots_extend.  *pend: the
 // last down_proj left its K-quarter sums in d_part_h for the consumer of the residual stream to apply (with *pend_scale)
 int decode_layers(DotsEngine* e, const int32_t* tokens, const int32_t* ctx_len, const int32_t* block_table, int B, int n_splits, int part, bool* pend_out,
-                  const float** pend_scale_out) {
+                  const float** pend_scale_out, const SharePlanDev* share) {
     const DotsConfig& c = e->cfg;
     hipStream_t s = e->stream;
     const int H = c.hidden_size, Hq = c.num_heads, Hkv = c.num_kv_heads, Nq = Hq * 128, I = c.intermediate_size;
@@ -756,7 +757,7 @@ int decode_layers(DotsEngine* e, const int32_t* tokens, const int32_t* ctx_len, 
         CK(launch_dec_qkv(s, e->d_h, L.ln1, L.qkv_wd, L.qkv_s, L.qkv_b, e->lm_inv_freq, ctx_len, block_table, e->max_pages, pool_l, e->d_q, B, H, Hq,
                           Hkv, c.rms_norm_eps, part ? e->dec_cus : 0, e->d_xn, pend ? e->d_part_h : nullptr, pend_scale, layer_kv_scales(e, i)));
         CK(launch_decode_attn(s, e->d_q, pool_l, ctx_len, block_table, e->max_pages, e->d_part_o, e->d_part_ml, B, Hq, Hkv, n_splits, scale, part ? e->dec_cus : 0, e->attn_stream,
-                              layer_kv_scales(e, i)));
+                              layer_kv_scales(e, i), share));
         CK(launch_decode_attn_combine(s, e->d_part_o, e->d_part_ml, ctx_len, e->d_att, B, Hq, Hkv, n_splits));
         bool pend_o = false;
         CK(launch_dec_proj(s, e->d_att, L.o_wd, L.o_s, e->d_h, B, H, Nq, part ? e->dec_cus : 0, e->d_part_h, &pend_o));
@@ -787,7 +788,9 @@ int decode_step_launches(DotsEngine* e, int n_splits, int part) {
     }
     bool pend = false;
     const float* pend_scale = nullptr;
-    RET(decode_layers(e, tokens, ctx_len, block_table, B, n_splits, part, &pend, &pend_scale));
+    // the shared-prefix plan describes the slots' own block table: the plain slot step alone takes it
+    const SharePlanDev share = share_plan_now(e);
+    RET(decode_layers(e, tokens, ctx_len, block_table, B, n_splits, part, &pend, &pend_scale, share.cap ? &share : nullptr));
     if (e->force_part) part = 1;                                                   // as the layers ran (decode_layers)
     CK(launch_dec_lmhead(s, e->d_h, e->final_norm, e->lm_head_d, e->lm_head_s, e->d_logits, B, H, c.vocab_size, c.rms_norm_eps, part ? e->dec_cus : 0, e->d_xn,
                          pend ? e->d_part_h : nullptr, pend_scale));

@@ -122,12 +122,15 @@ hipError_t launch_dec_lmhead64(hipStream_t s, const bf16_t* h, const bf16_t* ln_
 constexpr int DEC_KSPLIT_PARTS = 4;          // K quarters of the K-split projection; part buffers hold DEC_KSPLIT_PARTS x DOTS_MAX_BATCH x N fp32
 bool dec_proj_ksplit_supports(int B, int N, int K);
 hipError_t launch_dec_proj_ksplit(hipStream_t s, const bf16_t* X, const void* Wd, bool fp8, float* part, int B, int N, int K, int cus);
+// Shared-prefix attention: the device image of a plan (share_plan.h) and the item capacity the shared kernel's grid is sized
+// for — workgroups at or past the live item count (plan[0], read on the device) exit at once.  nullptr / cap 0: the step launches nothing of it
+struct SharePlanDev { const int32_t* plan; int cap; };
 int decode_attn_waves();                       // pages in flight per decode-attention workgroup (engine constant)
 int decode_attn_splits(int max_seq_len);       // KV splits for a context capacity: ceil(pages / waves), at most 64
 hipError_t launch_decode_attn(hipStream_t s, const bf16_t* q, const void* pool_layer, const int32_t* ctx_len,
                               const int32_t* block_table, int max_pages, float* part_o, float* part_ml,
                               int B, int Hq, int Hkv, int n_splits, float scale, int part_cus = 0, int stream_mode = -1,
-                              const float* kv_scales = nullptr);
+                              const float* kv_scales = nullptr, const SharePlanDev* share = nullptr);
 // > 0: launch_decode_attn runs the streaming kernel (round 5) with that many resident workgroups; 0: one workgroup per (row, kv head, split).
 // part_cus > 0: the stream is CU-masked to that many CUs; stream_mode 1 / 0 / -1 = always where legal / never / by items per CU; kv8: an fp8 pool (always 0)
 int decode_attn_stream_wgs(int B, int Hkv, int n_splits, int max_pages, int part_cus, int stream_mode = -1, bool kv8 = false);

@@ -70,12 +70,38 @@ int op_dec_qkv(DotsEngine* e, const void* h, const void* ln_w, const void* wqkv,
     return DOTS_OK;
 }
 
+// covered_pairs != nullptr (dots_op_decode_attn_shared): with the shared-prefix plan of the given block table, every row active and
+// static_pages[b] = ctx_len[b] / 64; *covered_pairs = the (row, split) pairs the plan's items cover
 int op_decode_attn(DotsEngine* e, const void* q, const void* pool_layer, const int32_t* ctx_len_dev, const int32_t* block_table_dev,
-                   int max_pages, void* out, int B, int Hq, int Hkv, int max_seq_len, const float* kv_scales) {
+                   int max_pages, void* out, int B, int Hq, int Hkv, int max_seq_len, const float* kv_scales, int32_t* covered_pairs = nullptr) {
     if (!e || !q || !pool_layer || !ctx_len_dev || !block_table_dev || !out || B < 1 || B > DOTS_MAX_BATCH) return e ? e->fail(DOTS_E_INVALID, "bad decode_attn arguments") : DOTS_E_INVALID;
+    if (max_pages < 1 || Hkv < 1 || Hq % Hkv != 0 || Hq / Hkv > 16) return e->fail(DOTS_E_INVALID, "bad decode_attn arguments");
     CK(hipSetDevice(e->device));
     Scratch sc(e);
     const int n_splits = splits_for_ctx(max_seq_len);
+    SharePlanDev share{nullptr, 0};
+    if (covered_pairs) {
+        std::vector<int32_t> ctx(B), table((size_t)B * max_pages), active(B, 1), plan(SHARE_PLAN_WORDS, 0);
+        uint64_t mask[DOTS_MAX_BATCH] = {0};
+        CK(hipMemcpyAsync(ctx.data(), ctx_len_dev, (size_t)B * 4, hipMemcpyDeviceToHost, e->stream));
+        CK(hipMemcpyAsync(table.data(), block_table_dev, table.size() * 4, hipMemcpyDeviceToHost, e->stream));
+        CK(hipStreamSynchronize(e->stream));
+        for (int b = 0; b < B; ++b) ctx[b] = std::min(std::max(ctx[b], 0) / PAGE, max_pages);
+        const int waves = decode_attn_waves();
+        const SharePlanCounts n = waves == 4 ? share_plan(active.data(), table.data(), max_pages, ctx.data(), B, n_splits, waves, max_pages, plan.data() + SHARE_ITEMS_OFF,
+                                                          plan.data() + SHARE_MEMBERS_OFF, mask)
+                                             : SharePlanCounts{0, 0, 0, 0};
+        plan[0] = n.items;
+        std::memcpy(plan.data() + SHARE_MASK_OFF, mask, sizeof(mask));
+        *covered_pairs = n.pairs;
+        if (n.items) {
+            int32_t* d_plan = nullptr;
+            CK(sc.get(&d_plan, (size_t)SHARE_PLAN_WORDS));
+            CK(hipMemcpyAsync(d_plan, plan.data(), (size_t)SHARE_PLAN_WORDS * 4, hipMemcpyHostToDevice, e->stream));
+            CK(hipStreamSynchronize(e->stream));                 // `plan` is a local
+            share = SharePlanDev{d_plan, (int)round_up(n.items, SHARE_ITEM_QUANTUM)};
+        }
+    }
     float *po = nullptr, *pml = nullptr;
     bf16_t* att = nullptr;
     const size_t rb = (size_t)(B + 15) / 16 * 16;
@@ -85,7 +111,7 @@ int op_decode_attn(DotsEngine* e, const void* q, const void* pool_layer, const i
     CK(hipMemsetAsync(po, 0xff, rb * Hq * n_splits * 128 * 4, e->stream));      // NaN: a partial read without having been written shows up
     CK(hipMemsetAsync(pml, 0xff, rb * Hq * n_splits * 2 * 4, e->stream));
     CK(launch_decode_attn(e->stream, (const bf16_t*)q, pool_layer, ctx_len_dev, block_table_dev, max_pages, po, pml, B, Hq, Hkv, n_splits,
-                          1.0f / sqrtf(128.0f), e->force_part ? e->dec_cus : 0, e->attn_stream, kv_scales));      // dots_set_decode_plan: the plan's kernel choice
+                          1.0f / sqrtf(128.0f), e->force_part ? e->dec_cus : 0, e->attn_stream, kv_scales, share.cap ? &share : nullptr));      // dots_set_decode_plan: the plan's kernel choice
     CK(launch_decode_attn_combine(e->stream, po, pml, ctx_len_dev, att, B, Hq, Hkv, n_splits));
     CK(launch_unpack_x(e->stream, att, (bf16_t*)out, B, Hq * 128));
     CK(hipStreamSynchronize(e->stream));
@@ -500,6 +526,21 @@ int dots_op_dec_qkv_kv8(DotsEngine* e, const void* h, const void* ln_w, const vo
 int dots_op_decode_attn(DotsEngine* e, const void* q, const void* pool_layer, const int32_t* ctx_len_dev, const int32_t* block_table_dev,
                         int max_pages, void* out, int B, int Hq, int Hkv, int max_seq_len) {
     return op_decode_attn(e, q, pool_layer, ctx_len_dev, block_table_dev, max_pages, out, B, Hq, Hkv, max_seq_len, nullptr);
+}
+
+int dots_op_decode_attn_shared(DotsEngine* e, const void* q, const void* pool_layer, const int32_t* ctx_len_dev, const int32_t* block_table_dev, int max_pages,
+                               void* out, int B, int Hq, int Hkv, int max_seq_len, const float* kv_scales_dev, int32_t* covered_pairs_out) {
+    if (!covered_pairs_out) return e ? e->fail(DOTS_E_INVALID, "null argument") : DOTS_E_INVALID;
+    return op_decode_attn(e, q, pool_layer, ctx_len_dev, block_table_dev, max_pages, out, B, Hq, Hkv, max_seq_len, kv_scales_dev, covered_pairs_out);
+}
+
+int dots_plan_shared_prefix(const int32_t* active, const int32_t* block_table, int max_pages, const int32_t* static_pages, int rows, int n_splits, int waves,
+                            int32_t* items3, int32_t* members, uint64_t* masks) {
+    if (!active || !block_table || !static_pages || !items3 || !members || !masks || rows < 1 || rows > DOTS_MAX_BATCH || max_pages < 1 || n_splits < 1 || waves < 1)
+        return DOTS_E_INVALID;
+    for (int b = 0; b < rows; ++b)
+        if (static_pages[b] < 0 || static_pages[b] > max_pages) return DOTS_E_INVALID;
+    return share_plan(active, block_table, max_pages, static_pages, rows, n_splits, waves, max_pages, items3, members, masks).items;
 }
 
 int dots_op_decode_attn_kv8(DotsEngine* e, const void* q, const void* pool_layer, const int32_t* ctx_len_dev, const int32_t* block_table_dev,

@@ -731,6 +731,52 @@ int dots_slots_reset(DotsEngine* e) {
     return DOTS_OK;
 }
 
+// Shared-prefix attention: the plan of the next plain steps from the host record as it stands, uploaded in stream order.  A
+// row's static pages are its full prompt pages: nobody writes them, and a beam group's device-side reordering never touches them.  A
+// suspended row idles on the scratch page: it is not active here
+static int share_replan(DotsEngine* e) {
+    if (!e->d_share) {
+        CK(e->alloc(&e->d_share, (size_t)SHARE_PLAN_WORDS));
+        e->h_share.assign(SHARE_PLAN_WORDS, 0);
+    }
+    const int mb = e->cfg.max_batch;
+    int32_t active[DOTS_MAX_BATCH], stat[DOTS_MAX_BATCH];
+    uint64_t mask[DOTS_MAX_BATCH] = {0};
+    for (int b = 0; b < mb; ++b) {
+        active[b] = e->slot_active[b] && !e->parked[b].on;
+        stat[b] = std::min(e->slot_prompt[b] / PAGE, (int)e->slot_pages[b].size());
+    }
+    int32_t* h = e->h_share.data();
+    const int waves = decode_attn_waves();
+    e->share_last = waves == 4 ? share_plan(active, e->hp_table.data(), e->max_pages, stat, mb, splits_for_ctx(e->cfg.max_seq_len), waves, e->max_pages,
+                                            h + SHARE_ITEMS_OFF, h + SHARE_MEMBERS_OFF, mask)
+                               : SharePlanCounts{0, 0, 0, 0};      // the shared kernel is the four-wave arithmetic
+    h[0] = e->share_last.items;
+    std::memcpy(h + SHARE_MASK_OFF, mask, sizeof(mask));
+    CK(hipMemcpyAsync(e->d_share, h, (size_t)SHARE_PLAN_WORDS * 4, hipMemcpyHostToDevice, e->stream));
+    e->share_cap = (int)round_up(e->share_last.items, SHARE_ITEM_QUANTUM);
+    e->share_dirty = false;
+    return DOTS_OK;
+}
+
+int dots_set_shared_prefix_attention(DotsEngine* e, int on) {
+    if (!e) return DOTS_E_INVALID;
+    e->share_on = on != 0;
+    e->share_dirty = true;
+    if (!e->share_on) { e->share_cap = 0; e->share_last = SharePlanCounts{0, 0, 0, 0}; }
+    return DOTS_OK;
+}
+
+int dots_shared_prefix_info(DotsEngine* e, int64_t* out4) {
+    if (!e || !out4) return e ? e->fail(DOTS_E_INVALID, "null argument") : DOTS_E_INVALID;
+    const bool live = share_plan_now(e).cap > 0;
+    out4[0] = live ? e->share_last.items : 0;
+    out4[1] = live ? e->share_last.rows : 0;
+    out4[2] = live ? e->share_last.pairs : 0;
+    out4[3] = e->share_pages_saved;
+    return DOTS_OK;
+}
+
 int dots_slots_decode(DotsEngine* e, int n_steps) {
     if (!e) return DOTS_E_INVALID;
     if (!e->slot_mode) return e->fail(DOTS_E_STATE, "no slot has been prefilled");
@@ -749,7 +795,9 @@ int dots_slots_decode(DotsEngine* e, int n_steps) {
         for (int b = 0; b < DOTS_MAX_BATCH; ++b) sel[b] = e->slot_active[b] && !e->beam_of[b] && !e->parked[b].on;
         CK(hipMemcpyAsync(e->d_sel, sel, DOTS_MAX_BATCH * 4, hipMemcpyHostToDevice, s));
         e->sel_dirty = false;
+        e->share_dirty = true;                              // whatever changes which rows run changes which rows share pages
     }
+    if (e->share_on && e->share_dirty) RET(share_replan(e));
     // ---- paged KV: every running sequence gets the pages the next n_steps positions need, now.  Pool dry: the sequence keeps what it
     // has and its generation cap is lowered to what its pages hold — it finishes there with "length", like HF generate at the
     // context capacity (an admission policy that leaves head-room makes this rare: dots_ocr_amd/scheduler.py).
@@ -806,6 +854,8 @@ int dots_slots_decode(DotsEngine* e, int n_steps) {
     }
     if (r == DOTS_OK && e->ev_dec_end && hipEventRecord(e->ev_dec_end, cur) == hipSuccess) ++e->dec_end_seq;      // pick_tower_tail
     if (r == DOTS_OK) r = chain_streams(e, cur, s);
+    if (r == DOTS_OK && share_plan_now(e).cap)
+        e->share_pages_saved += (int64_t)n_steps * e->share_last.saved * decode_attn_waves() * e->cfg.num_kv_heads * e->cfg.num_layers;
     e->B = 0;
     e->stats.decode_steps += n_steps;
     return r;

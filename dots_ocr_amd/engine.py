@@ -360,6 +360,8 @@ def _signatures() -> dict:
         "dots_slot_suspend": (i32, [vp, i32]),
         "dots_slot_resume": (i32, [vp, i32]),
         "dots_slots_pages_short": (i32, [vp, i32, P(i32)]),
+        "dots_set_shared_prefix_attention": (i32, [vp, i32]),
+        "dots_shared_prefix_info": (i32, [vp, P(i64)]),
         "dots_set_kv_scales": (i32, [vp, P(f32)]),
         "dots_get_logits": (i32, [vp, P(f32)]),
         "dots_set_next_tokens": (i32, [vp, P(i32), i32]),
@@ -387,6 +389,8 @@ def _signatures() -> dict:
         "dots_op_decode_attn": (i32, [vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32]),
         "dots_op_dec_qkv_kv8": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, f32, f32, i32, vp]),
         "dots_op_decode_attn_kv8": (i32, [vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, vp]),
+        "dots_op_decode_attn_shared": (i32, [vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, vp, P(i32)]),
+        "dots_plan_shared_prefix": (i32, [P(i32), P(i32), i32, P(i32), i32, i32, i32, P(i32), P(i32), P(C.c_uint64)]),
         "dots_op_dec_proj": (i32, [vp, vp, vp, vp, i32, i32, i32, i32]),
         "dots_op_dec_gateup": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32]),
         "dots_op_dec_lmhead": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, f32, i32]),
@@ -589,6 +593,28 @@ def plan_flash_xcd(lens: Sequence[int], heads: int):
     if n < 0:
         raise DotsEngineError(f"dots_plan_flash_xcd failed ({n})")
     return base, cnt, cost, int(n)
+
+
+def plan_shared_prefix(active: Sequence[int], block_table, static_pages: Sequence[int], n_splits: int, waves: int = 4):
+    """Host-only: the shared-prefix attention plan (dots_plan_shared_prefix) of a step over the rows of block_table
+    [rows, max_pages] -> (items, masks): items = [(split, [member rows ascending]), ...] split by split, masks[b] = the splits of row b
+    that an item covers, as bits.  Needs the library, not a GPU."""
+    lib = _lib.load()
+    _prototypes(lib)
+    table = np.ascontiguousarray(block_table, dtype=np.int32)
+    act = np.ascontiguousarray(active, dtype=np.int32)
+    stat = np.ascontiguousarray(static_pages, dtype=np.int32)
+    rows, max_pages = table.shape
+    assert act.shape == stat.shape == (rows,)
+    items3 = np.zeros(3 * 32 * max(int(n_splits), 1), np.int32)
+    members = np.zeros(max(rows * int(n_splits), 1), np.int32)
+    masks = np.zeros(rows, np.uint64)
+    n = lib.dots_plan_shared_prefix(_i32p(act), _i32p(table), int(max_pages), _i32p(stat), int(rows), int(n_splits), int(waves), _i32p(items3),
+                                    _i32p(members), masks.ctypes.data_as(C.POINTER(C.c_uint64)))
+    if n < 0:
+        raise DotsEngineError(f"dots_plan_shared_prefix failed ({n})")
+    items = [(int(items3[3 * k]), [int(r) for r in members[items3[3 * k + 1]:items3[3 * k + 1] + items3[3 * k + 2]]]) for k in range(n)]
+    return items, [int(m) for m in masks]
 
 
 def _i32p(a: np.ndarray):
@@ -1343,6 +1369,19 @@ class Engine:
         self._ck(self.lib.dots_prefix_cache_info(self.h, out), "dots_prefix_cache_info")
         return dict(zip(("lookups", "hit_tokens", "inserted", "evicted", "resident", "evictable"), (int(v) for v in out)))
 
+    # shared-prefix decode attention
+    def set_shared_prefix_attention(self, on: bool = True):
+        """Rows that share prompt pages (forks, beams, prompt fan-outs, prefix-cache hits) read each shared KV split once per decode step.
+        The same bits either way; takes effect from the next slots_decode, keeps the captured graphs, and is inert (not refused) while the
+        engine speculates."""
+        self._ck(self.lib.dots_set_shared_prefix_attention(self.h, 1 if on else 0), "dots_set_shared_prefix_attention")
+
+    def shared_prefix_info(self) -> dict:
+        """of the plan in force: items, rows in at least one, (row, split) pairs covered; cumulative: KV pages (one kv head, one layer) not read"""
+        out = (C.c_int64 * 4)()
+        self._ck(self.lib.dots_shared_prefix_info(self.h, out), "dots_shared_prefix_info")
+        return dict(zip(("items", "rows", "pairs", "pages_not_read"), (int(v) for v in out)))
+
     def slots_fork(self, src: int, dst_slots: Sequence[int]):
         """Parallel sampling: every free slot of dst_slots becomes a copy of the sequence slots_prefill just put into slot src (no decode
         step since): the same prompt over the same KV pages, and its own first token under the row parameters already set on it.  From
@@ -1675,6 +1714,14 @@ class Engine:
             raise ValueError("rows must match prefix")
         self._ck(self.lib.dots_op_flash_attn_paged(self.h, q, pool_layer, block_table, max_pages, table_rows, out, None if rw is None else _i32p(rw),
                                                    _i32p(pre), _i32p(new), pre.shape[0], Hq, Hkv, scale, kv_scales), "dots_op_flash_attn_paged")
+
+    def op_decode_attn_shared(self, q, pool_layer, ctx_len, block_table, max_pages, out, B, Hq, Hkv, max_seq_len, kv_scales=None) -> int:
+        """op_decode_attn (kv_scales None) / op_decode_attn_kv8 under the shared-prefix plan of the given block table; -> the (row, split)
+        pairs the plan covers.  The partials are NaN-filled first: a pair neither kernel wrote shows in out."""
+        pairs = C.c_int32(0)
+        self._ck(self.lib.dots_op_decode_attn_shared(self.h, q, pool_layer, ctx_len, block_table, max_pages, out, B, Hq, Hkv, max_seq_len, kv_scales,
+                                                     C.byref(pairs)), "dots_op_decode_attn_shared")
+        return int(pairs.value)
 
     def op_decode_attn_kv8(self, q, pool_layer, ctx_len, block_table, max_pages, out, B, Hq, Hkv, max_seq_len, kv_scales):
         """op_decode_attn on an fp8 (e4m3fn) page pool; kv_scales: device fp32 [Hkv, 2] (K, V)."""

@@ -86,6 +86,7 @@ class CallSettings:
     beam: Optional[tuple] = None                 # (num_beams, length_penalty)
     suffixes: Optional[list] = None              # prompt_suffixes
     prefill_chunk: Optional[int] = None
+    shared_prefix_attention: bool = False        # engine-wide for the call's continuous run
     image_keys: Optional[list] = None            # one entry per sequence when prefix caching is on, else None
     streamer: object = None
 
@@ -156,7 +157,7 @@ class DotsOcrHipForCausalLM:
                  num_return_sequences: int = 1, stop_strings=None, speculative_rows=None, num_beams: Optional[int] = None,
                  length_penalty: float = 1.0, early_stopping=None, speculative_guided: bool = False, prompt_suffixes=None, speculative_shaped=None,
                  prefill_chunk: Optional[int] = None, enable_prefix_caching: bool = False, image_keys=None, speculative_logprobs: bool = False, streamer=None,
-                 loop_guard=None, **_):
+                 loop_guard=None, shared_prefix_attention: bool = False, **_):
         """HF-shaped generate.  do_sample / temperature / top_p default to the checkpoint's generation_config.json (greedy when it
         is absent); with sampling on, tokens are drawn on the GPU from softmax(logits / temperature) restricted to the top_p
         nucleus, reproducibly from `seed`.  Returns LongTensor
@@ -246,6 +247,11 @@ class DotsOcrHipForCausalLM:
         §6.13): the same tokens as without it.  image_keys: per sequence 16 bytes that name its image (or None) — the caller's promise that
         equal keys mean equal pixels and grid, for instance a digest of the decoded image's bytes and size; a sequence with an image and
         no key bypasses the cache.
+
+        shared_prefix_attention=True lets the rows of the call that share prompt KV pages — num_return_sequences > 1, num_beams,
+        prompt_suffixes, prefix-cache hits — read each shared KV split once per decode step (ContinuousBatcher(shared_prefix_attention=True),
+        DESIGN §6.17): the same tokens and logprobs as without it.  Nothing is refused: on the static path and with speculative_ngram it
+        is accepted and has no effect.
 
         loop_guard (True = loop_guard.LoopRule's defaults, a LoopRule, or a dict of its fields; None / False = off) ends a sequence on the
         GPU at the token after which its output has cycled for the rule's span (Engine.set_row_loop).  The returned ids end
@@ -395,6 +401,7 @@ class DotsOcrHipForCausalLM:
             self.engine.slots_reset()            # speculation changes only while no slot is occupied
             Engine.speculation_on(self.engine, spec_k, prompt_lookup_min, prompt_lookup_max, **spec)
         call = CallSettings(rules=rules, guide=guide, ngram=ngram, stop=stop, loop=loop, nrs=nrs, beam=beam, suffixes=suffixes, prefill_chunk=prefill_chunk,
+                            shared_prefix_attention=bool(shared_prefix_attention),
                             image_keys=(image_keys or [None] * int(input_ids.shape[0])) if enable_prefix_caching else None, streamer=streamer)
         try:
             return self._generate(input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens, eos_token_id, pad_token_id, continuous,
@@ -518,7 +525,13 @@ class DotsOcrHipForCausalLM:
             chunk_kw = {} if call.prefill_chunk is None else {"prefill_chunk": call.prefill_chunk}
             if image_keys is not None:           # enable_prefix_caching
                 chunk_kw["prefix_caching"] = True
-            outs = ContinuousBatcher(self.engine, eos_ids=eos, **chunk_kw).run(reqs)
+            if call.shared_prefix_attention:     # for this call's run: the switch goes back off behind it
+                chunk_kw["shared_prefix_attention"] = True
+            try:
+                outs = ContinuousBatcher(self.engine, eos_ids=eos, **chunk_kw).run(reqs)
+            finally:
+                if call.shared_prefix_attention:
+                    self.engine.set_shared_prefix_attention(False)
             if streamer is not None:
                 streamer.end()
             if beam is not None:                 # row i * n + j = the j-th best hypothesis of prompt i (a prompt with fewer: pad rows)

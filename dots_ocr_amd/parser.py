@@ -42,8 +42,12 @@ class DotsOCRParser:
                  hf_max_new_tokens=24000, guided=False, no_repeat_ngram_size=None, no_repeat_ngram_window=None,
                  no_repeat_ngram_whitelist=None, speculative_ngram=None, prompt_lookup_min=2, prompt_lookup_max=4, stop=None,
                  speculative_rows=None, num_beams=None, length_penalty=1.0, speculative_guided=False, speculative_shaped=None,
-                 prefill_chunk=None, enable_prefix_caching=False, speculative_logprobs=False, loop_guard=None):
+                 prefill_chunk=None, enable_prefix_caching=False, speculative_logprobs=False, loop_guard=None, shared_prefix_attention=False):
         self.dpi = dpi
+        # shared-prefix attention, opt-in: the in-process model's rows that share prompt KV pages (beams, the prompts of one
+        # page, prefix-cache hits) read each shared KV split once per decode step; the same tokens.  A server shares by its own
+        # --shared-prefix-attention flag: requests carry nothing.  Accepted and inert with speculative_ngram
+        self.shared_prefix_attention = bool(shared_prefix_attention)
         # loop guard, opt-in: True (loop_guard.LoopRule's defaults), a LoopRule or a dict of its fields.  The server request
         # carries `loop_guard`; the in-process model generates with it, the page's ids are cut back to one copy of the cycle
         # (loop_guard.trimmed) and its result carries "repetition".  With the default None the request and the call are exactly what they were.
@@ -195,6 +199,8 @@ class DotsOCRParser:
             kw["prefill_chunk"] = self.prefill_chunk
         if self.enable_prefix_caching:
             kw.update(enable_prefix_caching=True, image_keys=[self._image_key(im) for im in images])
+        if self.shared_prefix_attention:
+            kw["shared_prefix_attention"] = True
         generated = self.model.generate(**inputs, max_new_tokens=self.hf_max_new_tokens, **kw)
         trimmed, loops = self._cut_loops([out[len(inp):] for inp, out in zip(inputs.input_ids, generated)])
         texts = self.processor.batch_decode(trimmed, skip_special_tokens=True, clean_up_tokenization_spaces=False)
@@ -214,6 +220,8 @@ class DotsOCRParser:
 
     def _chunk_kw(self) -> dict:
         kw = {} if self.prefill_chunk is None else {"prefill_chunk": self.prefill_chunk}
+        if self.shared_prefix_attention:
+            kw["shared_prefix_attention"] = True
         return dict(kw, prefix_caching=True) if self.enable_prefix_caching else kw
 
     def _cut_loops(self, rows):

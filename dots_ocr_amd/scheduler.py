@@ -112,8 +112,19 @@ class ContinuousBatcher:
 
     def __init__(self, engine, eos_ids: Sequence[int] = (), chunk: int = 16, headroom_pages: Optional[int] = 2, prefetch: int = 0,
                  tower_steps_per_page: int = 48, admit_group: Optional[int] = None, preemption: Optional[str] = None,
-                 swap_pages: Optional[int] = None, prefill_chunk: Optional[int] = None, prefix_caching: Optional[bool] = None):
+                 swap_pages: Optional[int] = None, prefill_chunk: Optional[int] = None, prefix_caching: Optional[bool] = None,
+                 shared_prefix_attention: Optional[bool] = None):
         self.engine = engine
+        # shared-prefix attention: an engine-wide switch, not a row feature — rows that share prompt pages (n > 1, beams,
+        # several prompts over one page, prefix-cache hits) read each shared KV split once per decode step; the same bits either way.
+        # Nothing is refused: a speculating engine takes the switch and its steps ignore it.  None leaves the engine as it is
+        if shared_prefix_attention is not None:
+            if shared_prefix_attention and not hasattr(engine, "set_shared_prefix_attention"):
+                raise ValueError("this engine has no shared-prefix attention (no set_shared_prefix_attention)")
+            if hasattr(engine, "set_shared_prefix_attention"):
+                engine.set_shared_prefix_attention(bool(shared_prefix_attention))
+        self.shared_prefix_attention = bool(shared_prefix_attention)
+        self._shared_base = self._shared_pages_now()
         # prefix caching, over the chunked prefill only.  Admission and the look-ahead ask the engine first
         # (Engine.prefix_cache_lookup): a request starts its fill behind the pages it hit, takes that many pages less, and — when the lookup
         # says so — sends no pixels to the tower.  The lease a lookup returns pins those pages until the begin that takes it; every path that
@@ -999,6 +1010,15 @@ class ContinuousBatcher:
         self.engine.slots_decode(self.chunk)
         self.decode_steps += self.chunk
         return self._collect()
+
+    def _shared_pages_now(self) -> int:
+        info = getattr(self.engine, "shared_prefix_info", None)
+        return int(info()["pages_not_read"]) if info is not None else 0
+
+    @property
+    def shared_pages_not_read(self) -> int:
+        """KV pages (one kv head of one layer each) this batcher's decode steps did not read because rows shared them"""
+        return self._shared_pages_now() - self._shared_base
 
     def run_pull(self, pull, low_water: Optional[int] = None) -> Dict[object, np.ndarray]:
         """An open-ended job: `pull(k)` returns up to k (key, Request) pairs from a source shared with other ranks ([] = the source is dry;

@@ -727,6 +727,20 @@ int dots_kv_swap_info(DotsEngine* e, int32_t* total_pages, int32_t* free_pages);
 int dots_slot_suspend(DotsEngine* e, int slot);
 int dots_slot_resume(DotsEngine* e, int slot);
 int dots_slots_pages_short(DotsEngine* e, int n_steps, int32_t* pages);
+/* ---- Shared-prefix decode attention (what vLLM calls cascade attention, here exact): rows that share prompt pages — the
+ * children of a fork, a beam group, a prompts fan-out, two prefix-cache hits on one page image — read each shared KV split once per step
+ * instead of once per row.  Opt-in, default off; tokens, logits, logprobs and KV are the same bits either way, on the bf16 and the fp8 pool.
+ *
+ * dots_set_shared_prefix_attention  on != 0 / 0, in stream order from the next dots_slots_decode; captured step graphs are kept.  The plan
+ *                         (which rows name the same four full prompt pages in which KV split) is recomputed before a decode chunk only
+ *                         after the slots changed, and lives in device arrays allocated by the first chunk with the switch on: an engine
+ *                         that never switches it on allocates and launches nothing new, and a step whose plan is empty launches what
+ *                         it launches with the switch off.  Inert, not refused, while the engine speculates, in dots_slots_extend /
+ *                         dots_slots_score passes, in the static batch, and at max_seq_len above 16 k (n_splits * 4 < pages per row).
+ * dots_shared_prefix_info int64 [4]: of the plan in force — items, rows in at least one item, (row, split) pairs covered — and,
+ *                         cumulative, the KV pages not read: over steps and items, (members - 1) x 4 x kv heads x layers. */
+int dots_set_shared_prefix_attention(DotsEngine* e, int on);
+int dots_shared_prefix_info(DotsEngine* e, int64_t* out4);
 
 /* fp32 logits [B, vocab] of the most recent prefill/decode step (tolerance checks). */
 int dots_get_logits(DotsEngine* e, float* out_host);
@@ -832,6 +846,23 @@ int dots_op_dec_qkv_kv8(DotsEngine* e, const void* h_dev, const void* ln_w_dev, 
 int dots_op_decode_attn_kv8(DotsEngine* e, const void* q_dev, const void* pool_layer_dev, const int32_t* ctx_len_dev,
                             const int32_t* block_table_dev, int max_pages, void* out_dev, int B, int Hq, int Hkv, int max_seq_len,
                             const float* kv_scales_dev);
+/* dots_op_decode_attn (kv_scales_dev_or_null == NULL) or dots_op_decode_attn_kv8 under the shared-prefix plan of the given
+ * block table, every row active and static_pages[b] = ctx_len[b] / 64: the plan's items through the shared kernel, every other (row, split)
+ * through the per-split kernel.  The partial buffers are filled with NaN first, so a (row, split) neither kernel wrote shows in out.
+ * *covered_pairs_out = the (row, split) pairs the items cover (0: the call launched exactly what dots_op_decode_attn launches).  out equals
+ * dots_op_decode_attn's in every bit. */
+int dots_op_decode_attn_shared(DotsEngine* e, const void* q_dev, const void* pool_layer_dev, const int32_t* ctx_len_dev,
+                               const int32_t* block_table_dev, int max_pages, void* out_dev, int B, int Hq, int Hkv, int max_seq_len,
+                               const float* kv_scales_dev_or_null, int32_t* covered_pairs_out);
+/* Host-only (no device, no engine): the shared-prefix plan (csrc/share_plan.h) of a step over rows <= 64 rows.  active / static_pages
+ * int32 [rows], block_table int32 [rows, max_pages] (entries [0, static_pages[b]) of row b are read; 0 <= static_pages[b] <= max_pages).
+ * Split s is pages [waves * s, waves * (s + 1)); row b is eligible for it iff it is active and waves * (s + 1) <= static_pages[b]; the
+ * eligible rows of a split that name the same pages there, two or more, are one item.  items3 int32 [3 * 32 * n_splits] gets {split, first
+ * member, members} per item (split by split, by lowest member within a split), members int32 [rows * n_splits] the member rows (ascending
+ * within an item), masks uint64 [rows] bit s of row b = an item covers (b, s).  Empty when n_splits * waves < max_pages, n_splits > 64 or
+ * waves > 8.  Returns the number of items, or a negative DOTS_E_*. */
+int dots_plan_shared_prefix(const int32_t* active, const int32_t* block_table, int max_pages, const int32_t* static_pages, int rows,
+                            int n_splits, int waves, int32_t* items3, int32_t* members, uint64_t* masks);
 int dots_op_dec_proj(DotsEngine* e, const void* x_dev, const void* w_dev, void* h_inout_dev, int B, int N, int K, int fp8);
 int dots_op_dec_gateup(DotsEngine* e, const void* h_dev, const void* ln_w_dev, const void* gate_w_dev, const void* up_w_dev, void* act_out_dev,
                        int B, int H, int I, float eps, int fp8);
