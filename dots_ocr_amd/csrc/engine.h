@@ -237,6 +237,14 @@ struct DotsEngine {
     // [rows, rows * (k + 1)) of lp_ms / lp_pv / lp_pi, which hold max_batch rows
     int spec_logprobs = 0;
     int32_t *sp_acc_n = nullptr, *sp_acc_tok = nullptr;
+    // predicted outputs (dots_set_row_prediction), allocated by the first call that sets one: the slots' predictions
+    // ([max_batch][max_seq_len]) and per slot their length, the alignment (cur, at), the source flag of the current drafts, the output
+    // length the drafter last saw and the two counters (kernels.h PredictState).  row_pred[row]: the length of the prediction the row holds, n_pred: how many
+    // rows hold one — while it is 0 a step launches what it launched before (StepKey::pred)
+    int32_t *pr_ids = nullptr, *pr_len = nullptr, *pr_cur = nullptr, *pr_at = nullptr, *pr_src = nullptr, *pr_seen = nullptr;
+    unsigned long long* pr_stats = nullptr;
+    int row_pred[DOTS_MAX_BATCH] = {0};
+    int n_pred = 0;
     bool row_pen[DOTS_MAX_BATCH] = {false}, row_sampled[DOTS_MAX_BATCH] = {false};
     // of a staged row without ROW_PARAMS: the engine-wide setting its stage entry was written from had a temperature > 0.  Such a row is
     // drawn by the stage whatever dots_set_sampling says later, and its draft rows would be arg maxima: it verifies no draft
@@ -366,10 +374,11 @@ struct DotsEngine {
     // some row with logprobs may (lpspec: the draft rows' logprob pair and the accept record); engine-wide sampling changes drop
     // the cache (dots_set_sampling), per-row ones live in device memory; beam: the group entries a step's beam kernels run over (0: none);
     // share: the item capacity of a non-empty shared-prefix plan (the shared kernel's grid and the SKIP instantiation of the per-split
-    // kernel; 0: neither — the live item count itself is device memory).  step_key() builds the key from the engine's state: a feature that
-    // changes what a step launches adds a member here and a line there
+    // kernel; 0: neither — the live item count itself is device memory); pred: whether some slot holds a prediction while the built-in
+    // drafter runs (the second drafter launch).  step_key() builds the key from the engine's state: a
+    // feature that changes what a step launches adds a member here and a line there
     struct StepKey {
-        int rows, splits, out_cap, n_eos, part, rowp, lp, rules, guided, ngram, spec, draw, gspec, sspec, lpspec, beam, share;
+        int rows, splits, out_cap, n_eos, part, rowp, lp, rules, guided, ngram, spec, draw, gspec, sspec, lpspec, beam, share, pred;
         bool operator==(const StepKey& o) const { return std::memcmp(this, &o, sizeof(StepKey)) == 0; }
     };
     static_assert(std::has_unique_object_representations_v<StepKey>, "StepKey is compared bytewise: plain ints, no padding");
@@ -500,6 +509,9 @@ int spec_shapes(const DotsEngine* e);
 RowSel spec_row_sel(const DotsEngine* e);
 GuideSel guide_sel(const DotsEngine* e);
 SpecState spec_state(const DotsEngine* e);
+bool spec_predicts(const DotsEngine* e);
+PredictState predict_state(const DotsEngine* e);
+int clear_row_prediction(DotsEngine* e, int row);
 hipError_t launch_row_stage(hipStream_t s, const float* logits, int V, int ld, int B, const RowSel& rs, float* am_val, int32_t* am_idx,
                             const StepState& st, const int32_t* ban_finished);
 int select_tokens(DotsEngine* e, int advance);

@@ -284,6 +284,7 @@ DotsEngine::StepKey step_key(const DotsEngine* e, int rows, int n_splits, int ou
     k.lpspec = spec_lps(e);
     k.beam = e->slot_mode ? e->n_beam_hi : 0;
     k.share = out_cap == 0 ? share_plan_now(e).cap : 0;
+    k.pred = spec_predicts(e);
     return k;
 }
 
@@ -837,6 +838,11 @@ int decode_step_launches(DotsEngine* e, int n_splits, int part) {
         if (e->spec_max_n > 0)
             CK(launch_ngram_draft(s, st.out_ids, st.out_lens, st.out_stride, st.finished, st.sel, sp.cls, sp.engine_greedy, rows, spec_k, e->spec_min_n,
                                   e->spec_max_n, e->sp_drafts, DOTS_MAX_SPEC_DRAFTS, e->sp_ndraft));
+        // the slots that hold a prediction and whose output aligns with it draft from it instead.  While no slot holds
+        // one nothing is launched here
+        if (spec_predicts(e))
+            CK(launch_predict_draft(s, predict_state(e), st.out_ids, st.out_lens, st.out_stride, st.finished, st.sel, sp.cls, sp.engine_greedy, rows, spec_k,
+                                    e->spec_min_n, e->spec_max_n, e->sp_drafts, DOTS_MAX_SPEC_DRAFTS, e->sp_ndraft, e->sp_nlive));
     }
     return DOTS_OK;
 }

@@ -381,6 +381,30 @@ hipError_t launch_ngram_draft(hipStream_t s, const int32_t* out_ids, const int32
 hipError_t launch_spec_set_class(hipStream_t s, int32_t* cls, int row, int value);
 // drafts[row][0 .. n) = ids_host, n_draft[row] = n, in stream order (the ids travel as a kernel argument)
 hipError_t launch_spec_set_drafts(hipStream_t s, int32_t* drafts, int32_t* n_draft, int row, const int32_t* ids_host, int n);
+// ---- predict.hip: predicted outputs, the drafter that proposes a caller-supplied text
+// PredictState: the slots' predictions ids [rows][stride] and, per slot, len (0: the slot holds none), the alignment (cur: the prediction
+// index the next token is expected at, at: the output length at which cur was set), src (did the slot's current drafts come from its
+// prediction) and seen (the output length at the drafter's last run over the slot).  stats [DOTS_MAX_BATCH][2]: the prediction tokens
+// the slot verified / committed, which the drafter accounts at its NEXT run over the slot — the one that finds it finished included —
+// from src, the step's n_live and the growth of the output since `seen`.  seen and stats may be nullptr (both): nothing is counted.
+struct PredictState {
+    const int32_t* ids;
+    int32_t *len, *cur, *at, *src;
+    int32_t stride;
+    int32_t* seen;
+    unsigned long long* stats;
+};
+// After launch_ngram_draft, over the same rows and under the same early-out conditions: for every slot that holds a prediction and whose
+// output the rule (include/dots_ocr_hip.h) aligns with it, drafts[b * draft_stride + 0 .. n_draft[b]) = the prediction from the aligned
+// index on, at most k ids, cur / at = the new alignment, src = 1.  Every other slot keeps its drafts, n_draft, cur and at, and gets src = 0.
+// n_live (SpecState::n_live of the step that just ran; nullptr: nothing is counted): a slot whose src was 1 and that took the step adds
+// n_live[b] to stats[b][0] and out_lens[b] - seen[b] - 1, the tokens its accept walk committed, to stats[b][1].
+hipError_t launch_predict_draft(hipStream_t s, const PredictState& p, const int32_t* out_ids, const int32_t* out_lens, int out_stride, const int32_t* finished,
+                                const int32_t* sel, const int32_t* cls, int engine_greedy, int B, int k, int min_n, int max_n, int32_t* drafts, int draft_stride,
+                                int32_t* n_draft, const int32_t* n_live);
+// len[row] = n and the alignment at the start, in stream order (the ids are copied by the caller); n == 0: the slot holds none any more,
+// src[row] = 0 and — n_draft != nullptr — the drafts it took from the prediction are dropped
+hipError_t launch_predict_set_row(hipStream_t s, const PredictState& p, int32_t* n_draft, int row, int n);
 // ---- extend.hip: more prompt tokens behind a live sequence (dots_slots_extend)
 // ExtendRows: the packed rows of one call — row i feeds token[i] (-1: the slot's pending token, read on the device) to slot slot[i] at
 // context ctx_len[slot] + off[i] — and the step-private arrays of a chunk (tokens / ctx_len [DOTS_MAX_BATCH], block_table [DOTS_MAX_BATCH]

@@ -671,6 +671,21 @@ int dots_op_ngram_draft(DotsEngine* e, const int32_t* hist_dev, const int32_t* h
     return DOTS_OK;
 }
 
+int dots_op_predict_draft(DotsEngine* e, const int32_t* pred_dev, const int32_t* pred_lens_dev, int pred_stride, const int32_t* hist_dev,
+                          const int32_t* hist_lens_dev, int hist_stride, int B, int k, int min_n, int max_n, int32_t* cur_dev, int32_t* at_dev,
+                          int32_t* drafts_dev, int32_t* n_drafts_dev, int32_t* src_dev) {
+    if (!e || !pred_dev || !pred_lens_dev || !hist_dev || !hist_lens_dev || !cur_dev || !at_dev || !drafts_dev || !n_drafts_dev || !src_dev)
+        return e ? e->fail(DOTS_E_INVALID, "null argument") : DOTS_E_INVALID;
+    if (B < 1 || B > DOTS_MAX_BATCH || pred_stride < 1 || hist_stride < 1 || k < 1 || k > DOTS_MAX_SPEC_DRAFTS || min_n < 1 || max_n < min_n ||
+        max_n > DOTS_MAX_NGRAM_SIZE)
+        return e->fail(DOTS_E_INVALID, "predict_draft: B in [1, %d], k in [1, %d], 1 <= min_n <= max_n <= %d", DOTS_MAX_BATCH, DOTS_MAX_SPEC_DRAFTS, DOTS_MAX_NGRAM_SIZE);
+    CK(hipSetDevice(e->device));
+    const PredictState p{pred_dev, const_cast<int32_t*>(pred_lens_dev), cur_dev, at_dev, src_dev, pred_stride, nullptr, nullptr};      // the drafter reads len only
+    CK(launch_predict_draft(e->stream, p, hist_dev, hist_lens_dev, hist_stride, nullptr, nullptr, nullptr, 1, B, k, min_n, max_n, drafts_dev, k, n_drafts_dev, nullptr));
+    CK(hipStreamSynchronize(e->stream));
+    return DOTS_OK;
+}
+
 int dots_op_spec_guide_masks(DotsEngine* e, int rows, int k, const int32_t* guide_ids_host, const int32_t* states_host, const int32_t* drafts_host,
                              const int32_t* n_live_host, int32_t* states_out_host, uint32_t* mask_out_host) {
     if (!e || !guide_ids_host || !states_host || !drafts_host || !n_live_host || !states_out_host || !mask_out_host)

@@ -218,10 +218,27 @@ RowSel spec_row_sel(const DotsEngine* e) {
     return rs;
 }
 
+// does a speculating step run the prediction drafter (StepKey::pred)?  A host count: the built-in drafter runs and at least one slot holds a
+// prediction.  While no slot does, a step launches what it always did
+bool spec_predicts(const DotsEngine* e) { return e->slot_mode && e->spec_k > 0 && e->spec_max_n > 0 && e->n_pred > 0; }
+
+PredictState predict_state(const DotsEngine* e) {
+    return PredictState{e->pr_ids, e->pr_len, e->pr_cur, e->pr_at, e->pr_src, (int32_t)e->cfg.max_seq_len, e->pr_seen, e->pr_stats};
+}
+
 SpecState spec_state(const DotsEngine* e) {
     return SpecState{e->sp_drafts, e->sp_ndraft, e->sp_nlive, e->sp_tokens, e->sp_ctx, e->sp_table, e->sp_stats, e->sp_cls,
                      spec_draws(e) ? e->sp_cand : nullptr, spec_guides(e) ? e->sp_gstate : nullptr, e->spec_k, e->temperature > 0.f ? 0 : 1,
                      spec_lps(e) ? e->sp_acc_n : nullptr, spec_lps(e) ? e->sp_acc_tok : nullptr};
+}
+
+// the row holds no prediction any more (stream ordered): dots_set_row_prediction with n = 0, dots_slot_release
+int clear_row_prediction(DotsEngine* e, int row) {
+    if (!e->pr_ids || !e->row_pred[row]) return DOTS_OK;
+    CK(launch_predict_set_row(e->stream, predict_state(e), e->sp_ndraft, row, 0));
+    e->row_pred[row] = 0;
+    e->n_pred -= 1;
+    return DOTS_OK;
 }
 
 // the loop rows' table and counters, once any row has held a rule (allocating them drops the captured steps, so no cache key changes)
@@ -813,6 +830,7 @@ int dots_set_row_drafts(DotsEngine* e, int row, const int32_t* ids_host, int n) 
     if (!e->spec_k) return DOTS_OK;                          // n == 0 with speculation off: nothing to clear
     CK(hipSetDevice(e->device));
     CK(launch_spec_set_drafts(e->stream, e->sp_drafts, e->sp_ndraft, row, ids_host, n));
+    if (e->pr_src) CK(hipMemsetAsync(e->pr_src + row, 0, 4, e->stream));      // the host's drafts, not the prediction's
     return DOTS_OK;
 }
 
@@ -826,6 +844,50 @@ int dots_spec_stats(DotsEngine* e, int row, int64_t* steps, int64_t* drafted, in
     CK(hipMemcpyAsync(v, e->sp_stats + (size_t)(row < 0 ? DOTS_MAX_BATCH : row) * 3, sizeof(v), hipMemcpyDeviceToHost, e->stream));
     CK(hipStreamSynchronize(e->stream));
     *steps = (int64_t)v[0]; *drafted = (int64_t)v[1]; *accepted = (int64_t)v[2];
+    return DOTS_OK;
+}
+
+// ---------------------------------------------------------------------------------- predicted outputs
+int dots_set_row_prediction(DotsEngine* e, int row, const int32_t* ids_host, int n) {
+    if (!e) return DOTS_E_INVALID;
+    if (row < 0 || row >= e->cfg.max_batch) return e->fail(DOTS_E_INVALID, "row %d out of range [0, %d)", row, e->cfg.max_batch);
+    if (n < 0) return e->fail(DOTS_E_INVALID, "prediction length must be >= 0, got %d", n);
+    if (!ids_host) n = 0;
+    if (n > e->cfg.max_seq_len) return e->fail(DOTS_E_CAPACITY, "a prediction of %d tokens is longer than a sequence can become (max_seq_len %d)", n, e->cfg.max_seq_len);
+    for (int j = 0; j < n; ++j)
+        if (ids_host[j] < 0 || ids_host[j] >= e->cfg.vocab_size)
+            return e->fail(DOTS_E_INVALID, "prediction id %d at %d out of range [0, %d)", ids_host[j], j, e->cfg.vocab_size);
+    CK(hipSetDevice(e->device));
+    if (n == 0) return clear_row_prediction(e, row);
+    hipStream_t s = e->stream;
+    if (!e->pr_stats) {
+        // each piece is allocated once: a call that failed half way is resumed by the next one
+        if (!e->pr_ids) CK(e->alloc(&e->pr_ids, (size_t)e->cfg.max_batch * e->cfg.max_seq_len));
+        if (!e->pr_len) CK(e->alloc(&e->pr_len, (size_t)DOTS_MAX_BATCH));
+        if (!e->pr_cur) CK(e->alloc(&e->pr_cur, (size_t)DOTS_MAX_BATCH));
+        if (!e->pr_at) CK(e->alloc(&e->pr_at, (size_t)DOTS_MAX_BATCH));
+        if (!e->pr_src) CK(e->alloc(&e->pr_src, (size_t)DOTS_MAX_BATCH));
+        if (!e->pr_seen) CK(e->alloc(&e->pr_seen, (size_t)DOTS_MAX_BATCH));
+        CK(e->alloc(&e->pr_stats, (size_t)DOTS_MAX_BATCH * 2));             // set last, it is the guard above
+    }
+    CK(hipMemcpyAsync(e->pr_ids + (size_t)row * e->cfg.max_seq_len, ids_host, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    CK(launch_predict_set_row(s, predict_state(e), e->sp_ndraft, row, n));
+    CK(hipStreamSynchronize(s));                             // ids_host is the caller's
+    if (!e->row_pred[row]) e->n_pred += 1;
+    e->row_pred[row] = n;
+    return DOTS_OK;
+}
+
+int dots_row_prediction_stats(DotsEngine* e, int row, int64_t* drafted, int64_t* accepted) {
+    if (!e || !drafted || !accepted) return e ? e->fail(DOTS_E_INVALID, "null argument") : DOTS_E_INVALID;
+    if (row < 0 || row >= e->cfg.max_batch) return e->fail(DOTS_E_INVALID, "row %d out of range [0, %d)", row, e->cfg.max_batch);
+    *drafted = *accepted = 0;
+    if (!e->pr_stats) return DOTS_OK;
+    CK(hipSetDevice(e->device));
+    unsigned long long v[2] = {0, 0};
+    CK(hipMemcpyAsync(v, e->pr_stats + (size_t)row * 2, sizeof(v), hipMemcpyDeviceToHost, e->stream));
+    CK(hipStreamSynchronize(e->stream));
+    *drafted = (int64_t)v[0]; *accepted = (int64_t)v[1];
     return DOTS_OK;
 }
 

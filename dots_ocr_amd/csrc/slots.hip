@@ -179,6 +179,13 @@ int rows_go_live(DotsEngine* e, const std::vector<LiveRow>& rows, bool clear_lp)
             CK(hipMemsetAsync(e->sp_ndraft + r.slot, 0, 4, s));
             CK(hipMemsetAsync(e->sp_stats + (size_t)r.slot * 3, 0, 3 * sizeof(unsigned long long), s));
         }
+        if (e->pr_stats) {                                  // a prediction the slot holds is aligned with the start of the new output
+            CK(hipMemsetAsync(e->pr_cur + r.slot, 0, 4, s));
+            CK(hipMemsetAsync(e->pr_at + r.slot, 0, 4, s));
+            CK(hipMemsetAsync(e->pr_src + r.slot, 0, 4, s));
+            CK(hipMemsetAsync(e->pr_seen + r.slot, 0, 4, s));
+            CK(hipMemsetAsync(e->pr_stats + (size_t)r.slot * 2, 0, 2 * sizeof(unsigned long long), s));
+        }
         if (clear_lp) RET(clear_lp_row(e, r.slot));
     }
     return DOTS_OK;
@@ -726,6 +733,12 @@ int dots_slots_reset(DotsEngine* e) {
     RET(stream_reset(e));
     if (e->sp_ndraft) CK(hipMemsetAsync(e->sp_ndraft, 0, DOTS_MAX_BATCH * 4, s));
     if (e->sp_cls) CK(hipMemsetAsync(e->sp_cls, 0, DOTS_MAX_BATCH * 4, s));         // SPEC_ROW_ARGMAX: no row carries anything
+    if (e->pr_stats) {                                                              // no slot holds a prediction
+        for (int32_t* a : {e->pr_len, e->pr_cur, e->pr_at, e->pr_src, e->pr_seen}) CK(hipMemsetAsync(a, 0, DOTS_MAX_BATCH * 4, s));
+        CK(hipMemsetAsync(e->pr_stats, 0, (size_t)DOTS_MAX_BATCH * 2 * sizeof(unsigned long long), s));
+    }
+    std::fill(e->row_pred, e->row_pred + DOTS_MAX_BATCH, 0);
+    e->n_pred = 0;
     CK(hipStreamSynchronize(s));
     e->sel_dirty = true;
     return DOTS_OK;
@@ -904,6 +917,7 @@ int dots_slot_release(DotsEngine* e, int slot) {
     if (e->beam_of[slot]) return beam_release_group(e, slot);          // the slots of a beam group go together
     for (int f = 0; f < ROW_ALL_FEATURES; ++f) RET(clear_row_feature(e, slot, (RowFeature)f));
     RET(set_row_lp(e, slot, -1));
+    RET(clear_row_prediction(e, slot));
     e->row_stream[slot] = 0;
     e->slot_active[slot] = 0;
     e->sel_dirty = true;

@@ -23,6 +23,8 @@
 //                        (dots_set_speculation_logprobs) and some row has them on: the partials of the live draft rows of such slots beside
 //                        spec_argmax_kernel, and after spec_accept_kernel the entries of the candidates it committed, from its accept record
 //   ngram_draft_kernel   end of the step: the next step's drafts from the row's own output (prompt lookup without the prompt)
+//   (predict_draft_kernel, predict.hip)   then, only while some slot holds a prediction (dots_set_row_prediction): the drafts of the slots
+//                        whose output aligns with their prediction, from that prediction
 //
 // Draft row (b, j >= 1) is LIVE iff slot b is selected, not finished, a speculating row (sp.cls[b] != SPEC_ROW_NONE: the host's fact,
 // kernels.h SpecRow; engine-wide arg max), holds at least j drafts and j < max_len[b] - out_lens[b]: a live row writes KV position ctx + j, and

@@ -428,6 +428,9 @@ def _signatures() -> dict:
         "dots_set_row_drafts": (i32, [vp, i32, P(i32), i32]),
         "dots_spec_stats": (i32, [vp, i32, P(i64), P(i64), P(i64)]),
         "dots_op_ngram_draft": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]),
+        "dots_set_row_prediction": (i32, [vp, i32, P(i32), i32]),
+        "dots_row_prediction_stats": (i32, [vp, i32, P(i64), P(i64)]),
+        "dots_op_predict_draft": (i32, [vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
         "dots_set_row_logprobs": (i32, [vp, i32, i32]),
         "dots_row_logprobs": (i32, [vp, i32, i32, i32, P(f32), P(i32), P(f32), P(i32)]),
         "dots_op_logprobs": (i32, [vp, vp, i32, i32, i32, P(i32), vp, vp, vp, vp]),
@@ -477,6 +480,76 @@ def ngram_draft(history: Sequence[int], k: int, min_n: int = 2, max_n: int = 4) 
         i = max(full) if full else min(hits)
         return out[i + n:min(i + n + k, L)]
     return []
+
+
+def predicted_draft(out: Sequence[int], pred: Sequence[int], cur: int, at: int, k: int, min_n: int = 2, max_n: int = 4):
+    """The drafting rule of predicted outputs (include/dots_ocr_hip.h), stated on the host: what predict_draft_kernel must
+    produce.  out = the tokens a row has generated, pred = its prediction, (cur, at) its alignment: prediction index cur was where the
+    next token was expected when the output was `at` long, so now it is expected at e* = cur + (L - at).
+      1. anchor: m = min(min_n, L, e*); if m >= 1, e* < P and pred[e* - m .. e*) == out[L - m .. L) then e = e*.
+      2. search: else for n from min(max_n, L) down to min_n, key = out[L - n .. L); candidates e = i + n < P with pred[i .. i + n) == key;
+         the first n with a candidate wins, among them the one nearest to e*, the larger e on a tie.
+    -> (drafts, cur, at): found, drafts = pred[e .. min(e + k, P)) with the new alignment (e, L); else (None, cur, at) — the row keeps
+    the drafts its own output gave it and the alignment stays."""
+    out, pred = [int(t) for t in out], [int(t) for t in pred]
+    L, P, cur, at = len(out), len(pred), int(cur), int(at)
+    if k < 1 or min_n < 1 or max_n < min_n:
+        raise ValueError("predicted_draft needs k >= 1 and 1 <= min_n <= max_n")
+    es = cur + (L - at)
+    e = None
+    m = min(min_n, L, es)
+    if m >= 1 and es < P and pred[es - m:es] == out[L - m:]:
+        e = es
+    if e is None:
+        for n in range(min(max_n, L), min_n - 1, -1):
+            key = out[L - n:]
+            cands = [i + n for i in range(P - n) if pred[i:i + n] == key]
+            if cands:
+                e = min(cands, key=lambda c: (abs(c - es), -c))
+                break
+    if e is None:
+        return None, cur, at
+    return pred[e:min(e + k, P)], e, L
+
+
+def predicted_run(tokens: Sequence[int], pred: Sequence[int], k: int, min_n: int = 2, max_n: int = 4, cap: Optional[int] = None) -> dict:
+    """A row's speculating run replayed on the host.  tokens = everything the row committed in the end (the first token,
+    which the prefill selects, included), pred = its prediction (empty: none), cap = its generation cap (default: len(tokens)).  Every
+    step commits one token, then walks its live drafts while each equals the token committed before it; then the drafters run: the
+    own-output rule (ngram_draft), then predicted_draft, which replaces its drafts where it finds a position.  The drafts a step
+    verifies are cut to the tokens the cap leaves room for.  -> {"steps": [{"drafts", "source" ("prediction" | "own" | None), "live",
+    "accepted"} per step], "n_steps", "drafted", "accepted" (what dots_spec_stats counts), "pred_drafted", "pred_accepted" (what
+    dots_row_prediction_stats counts)}."""
+    T, pred = [int(t) for t in tokens], [int(t) for t in pred]
+    N = len(T)
+    cap = N if cap is None else int(cap)
+    if N < 1 or cap < N:
+        raise ValueError("predicted_run needs at least the first token and cap >= len(tokens)")
+    L, cur, at = 1, 0, 0
+    drafts, source = [], None
+    steps = []
+    tot = {"drafted": 0, "accepted": 0, "pred_drafted": 0, "pred_accepted": 0}
+    while L < N:
+        live = max(0, min(len(drafts), k, cap - L - 1))
+        L += 1                                               # the selection stage commits row 0
+        acc = 0
+        while acc < live and L < N and drafts[acc] == T[L - 1]:
+            L += 1
+            acc += 1
+        steps.append({"drafts": list(drafts), "source": source if drafts else None, "live": live, "accepted": acc})
+        tot["drafted"] += live
+        tot["accepted"] += acc
+        if source == "prediction" and drafts:
+            tot["pred_drafted"] += live
+            tot["pred_accepted"] += acc
+        drafts, source = [], None
+        if L < N:                                            # a finished row drafts nothing
+            drafts, source = ngram_draft(T[:L], k, min_n, max_n), "own"
+            if pred:
+                d, cur, at = predicted_draft(T[:L], pred, cur, at, k, min_n, max_n)
+                if d is not None:
+                    drafts, source = d, "prediction"
+    return {"steps": steps, "n_steps": len(steps), **tot}
 
 
 def spec_usable_slots(max_batch: int, k: int) -> int:
@@ -1218,6 +1291,56 @@ class Engine:
             for ptr in (d_hist, d_lens, d_out, d_n):
                 self.dev_free(ptr)
         return [out[b, :int(n[b])].tolist() for b in range(B)]
+
+    def set_row_prediction(self, row: int, ids: Optional[Sequence[int]]):
+        """Slot `row` holds the prediction `ids` from now on: a text the output is expected to resemble, which the second
+        drafter of a speculating step proposes as drafts where the output aligns with it.  None or empty clears.  Only which tokens are
+        proposed changes: the committed tokens are the unspeculated engine's.  May be called before the slot's prefill; slot release and
+        slots_reset clear it; stored and inert on an engine that does not speculate."""
+        a = np.ascontiguousarray([] if ids is None else list(ids), dtype=np.int32)
+        self._ck(self.lib.dots_set_row_prediction(self.h, int(row), _i32p(a) if a.size else None, int(a.size)), "dots_set_row_prediction")
+
+    def row_prediction_stats(self, row: int) -> dict:
+        """{"drafted", "accepted"}: prediction tokens slot `row` verified as drafts and committed, since its prefill"""
+        dr, ac = C.c_int64(0), C.c_int64(0)
+        self._ck(self.lib.dots_row_prediction_stats(self.h, int(row), C.byref(dr), C.byref(ac)), "dots_row_prediction_stats")
+        return {"drafted": int(dr.value), "accepted": int(ac.value)}
+
+    def predict_draft_op(self, predictions: Sequence[Sequence[int]], histories: Sequence[Sequence[int]], cur: Sequence[int], at: Sequence[int],
+                         k: int, min_n: int = 2, max_n: int = 4) -> list:
+        """predict_draft_kernel alone (dots_op_predict_draft): one launch over the rows, -> one (drafts | None, cur, at) per row, as
+        predicted_draft returns it."""
+        B = len(histories)
+        if not (len(predictions) == len(cur) == len(at) == B):
+            raise ValueError("predict_draft_op: one prediction, cur and at per history")
+
+        def pack(rows):
+            stride = max(1, max(len(r) for r in rows))
+            a = np.zeros((B, stride), np.int32)
+            for b, r in enumerate(rows):
+                a[b, :len(r)] = np.asarray(r, np.int32)
+            return a, np.asarray([len(r) for r in rows], np.int32), stride
+
+        pred, plens, pstride = pack(predictions)
+        hist, hlens, hstride = pack(histories)
+        ptrs = [self.to_device(a) for a in (pred, plens, hist, hlens, np.asarray(cur, np.int32), np.asarray(at, np.int32),
+                                            np.full((B, int(k)), -1, np.int32), np.full((B,), -1, np.int32), np.full((B,), -1, np.int32))]
+        d_pred, d_plens, d_hist, d_hlens, d_cur, d_at, d_out, d_n, d_src = ptrs
+        try:
+            self._ck(self.lib.dots_op_predict_draft(self.h, C.c_void_p(d_pred), C.c_void_p(d_plens), pstride, C.c_void_p(d_hist), C.c_void_p(d_hlens), hstride,
+                                                    B, int(k), int(min_n), int(max_n), C.c_void_p(d_cur), C.c_void_p(d_at), C.c_void_p(d_out),
+                                                    C.c_void_p(d_n), C.c_void_p(d_src)), "dots_op_predict_draft")
+            out, n, src = self.to_host(d_out, (B, int(k)), np.int32), self.to_host(d_n, (B,), np.int32), self.to_host(d_src, (B,), np.int32)
+            c, a = self.to_host(d_cur, (B,), np.int32), self.to_host(d_at, (B,), np.int32)
+        finally:
+            for ptr in ptrs:
+                self.dev_free(ptr)
+        res = []
+        for b in range(B):
+            if int(src[b]) not in (0, 1) or (int(src[b]) == 1) != (int(n[b]) >= 0):
+                raise RuntimeError(f"predict_draft_op: row {b} left src {int(src[b])} with n_drafts {int(n[b])}")
+            res.append((out[b, :int(n[b])].tolist() if src[b] else None, int(c[b]), int(a[b])))
+        return res
 
     def set_row_logprobs(self, row: int, top_n: Optional[int]):
         """Row `row` (a slot, or sequence `row` of a static batch) returns log-probabilities of the raw logits for every token selected

@@ -89,6 +89,7 @@ class CallSettings:
     shared_prefix_attention: bool = False        # engine-wide for the call's continuous run
     image_keys: Optional[list] = None            # one entry per sequence when prefix caching is on, else None
     streamer: object = None
+    predictions: Optional[list] = None           # prediction_ids: one token list or None per sequence
 
 
 class DotsOcrHipForCausalLM:
@@ -157,7 +158,7 @@ class DotsOcrHipForCausalLM:
                  num_return_sequences: int = 1, stop_strings=None, speculative_rows=None, num_beams: Optional[int] = None,
                  length_penalty: float = 1.0, early_stopping=None, speculative_guided: bool = False, prompt_suffixes=None, speculative_shaped=None,
                  prefill_chunk: Optional[int] = None, enable_prefix_caching: bool = False, image_keys=None, speculative_logprobs: bool = False, streamer=None,
-                 loop_guard=None, shared_prefix_attention: bool = False, **_):
+                 loop_guard=None, shared_prefix_attention: bool = False, prediction_ids=None, **_):
         """HF-shaped generate.  do_sample / temperature / top_p default to the checkpoint's generation_config.json (greedy when it
         is absent); with sampling on, tokens are drawn on the GPU from softmax(logits / temperature) restricted to the top_p
         nucleus, reproducibly from `seed`.  Returns LongTensor
@@ -213,6 +214,11 @@ class DotsOcrHipForCausalLM:
         "sampled"), a comma list or a tuple of them, or "all".  Every draft row is selected under the history, the output counts and
         the output index the sequence would have there, so the tokens are again exactly those of the call without it.  The engine is
         left with the setting off.
+
+        prediction_ids (one list of token ids or None per sequence) hands each sequence a PREDICTION, a text its output is expected to
+        resemble (DESIGN §6.18).  With speculative_ngram the engine drafts from it on the GPU and re-aligns after the output diverges;
+        the returned tokens are exactly those of the call without it.  Without speculative_ngram it is carried and inert.  It takes the
+        continuous path and one sequence per prompt: not with num_return_sequences > 1, num_beams, prompt_suffixes or continuous=False.
 
         stop_strings (HF's name: a str or a list of at most 16 str of at most 64 UTF-8 bytes) ends a sequence on the GPU at the token that
         completes one of them in its generated text (Engine.set_row_stop; with min_tokens, no match is taken below it).  The
@@ -294,6 +300,18 @@ class DotsOcrHipForCausalLM:
                 raise ValueError("streamer needs put(ids) and end()")
             if not hasattr(self.engine, "slots_drain"):
                 raise ValueError("this engine cannot stream (no slots_drain)")
+            continuous = True
+        predictions = None
+        if prediction_ids is not None:           # predicted outputs: a hint per sequence, for the continuous path
+            predictions = [None if p is None else [int(t) for t in p] for p in prediction_ids]
+            if len(predictions) != int(input_ids.shape[0]):
+                raise ValueError("prediction_ids takes one token list or None per sequence")
+            refused = [name for name, on in (("num_return_sequences > 1", nrs > 1), ("num_beams", num_beams not in (None, 1)),
+                                             ("prompt_suffixes", prompt_suffixes is not None), ("continuous=False", continuous is False)) if on]
+            if refused:
+                raise ValueError(f"a prediction belongs to one generated sequence: prediction_ids cannot be combined with {', '.join(refused)}")
+            if not hasattr(self.engine, "set_row_prediction"):
+                raise ValueError("this engine takes no prediction (no set_row_prediction)")
             continuous = True
         if early_stopping is not None:
             raise ValueError("early_stopping is not offered: a beam group ends at its cap, or early only where that is exact (DESIGN §6.9)")
@@ -402,7 +420,8 @@ class DotsOcrHipForCausalLM:
             Engine.speculation_on(self.engine, spec_k, prompt_lookup_min, prompt_lookup_max, **spec)
         call = CallSettings(rules=rules, guide=guide, ngram=ngram, stop=stop, loop=loop, nrs=nrs, beam=beam, suffixes=suffixes, prefill_chunk=prefill_chunk,
                             shared_prefix_attention=bool(shared_prefix_attention),
-                            image_keys=(image_keys or [None] * int(input_ids.shape[0])) if enable_prefix_caching else None, streamer=streamer)
+                            image_keys=(image_keys or [None] * int(input_ids.shape[0])) if enable_prefix_caching else None, streamer=streamer,
+                            predictions=predictions)
         try:
             return self._generate(input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens, eos_token_id, pad_token_id, continuous,
                                   row_sp, call)
@@ -505,7 +524,8 @@ class DotsOcrHipForCausalLM:
 
         def request(b, pix=None, g=None):        # sequence b with the call's row settings: what both paths give their rows
             return Request(prompts[b], pix, g, max_new_tokens, sampling=row_sp(b) if row_sp else None, rules=call.rules, guide=call.guide,
-                           ngram=call.ngram, n=1 if suffixes else nrs, stop=call.stop, loop=call.loop, suffixes=suffixes)
+                           ngram=call.ngram, n=1 if suffixes else nrs, stop=call.stop, loop=call.loop, suffixes=suffixes,
+                           prediction=call.predictions[b] if call.predictions else None)
         if continuous:
             reqs = []
             for b in range(B):

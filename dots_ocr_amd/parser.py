@@ -42,8 +42,18 @@ class DotsOCRParser:
                  hf_max_new_tokens=24000, guided=False, no_repeat_ngram_size=None, no_repeat_ngram_window=None,
                  no_repeat_ngram_whitelist=None, speculative_ngram=None, prompt_lookup_min=2, prompt_lookup_max=4, stop=None,
                  speculative_rows=None, num_beams=None, length_penalty=1.0, speculative_guided=False, speculative_shaped=None,
-                 prefill_chunk=None, enable_prefix_caching=False, speculative_logprobs=False, loop_guard=None, shared_prefix_attention=False):
+                 prefill_chunk=None, enable_prefix_caching=False, speculative_logprobs=False, loop_guard=None, shared_prefix_attention=False,
+                 prediction=None):
         self.dpi = dpi
+        # predicted outputs, opt-in: a text the pages' output is expected to resemble — a string for every page, or a
+        # callable (page_index, image) -> str | None.  The in-process model generates with it (generate(prediction_ids=): with
+        # speculative_ngram the engine drafts from it, the tokens are those of a run without it); the server request carries OpenAI's
+        # `prediction` field.  With the default None the request and the call are exactly what they were
+        if prediction is not None and not (isinstance(prediction, str) or callable(prediction)):
+            raise ValueError("prediction must be a string or a callable (page_index, image) -> str | None")
+        if prediction is not None and num_beams and int(num_beams) != 1:
+            raise ValueError("num_beams cannot be combined with prediction")
+        self.prediction = prediction
         # shared-prefix attention, opt-in: the in-process model's rows that share prompt KV pages (beams, the prompts of one
         # page, prefix-cache hits) read each shared KV split once per decode step; the same tokens.  A server shares by its own
         # --shared-prefix-attention flag: requests carry nothing.  Accepted and inert with speculative_ngram
@@ -164,14 +174,33 @@ class DotsOCRParser:
         import dataclasses
         return {"loop_guard": dataclasses.asdict(self.loop_guard)}
 
+    def _prediction_text(self, page_index: int, image) -> Optional[str]:
+        """the prediction of one page as text, or None"""
+        if self.prediction is None:
+            return None
+        text = self.prediction(page_index, image) if callable(self.prediction) else self.prediction
+        if text is not None and not isinstance(text, str):
+            raise ValueError(f"the prediction of page {page_index} must be a string or None, got {type(text).__name__}")
+        return text or None
+
+    def _prediction_ids(self, page_index: int, image) -> Optional[list]:
+        """... tokenised with the processor's tokenizer, without special tokens, and cut to what a sequence can hold"""
+        text = self._prediction_text(page_index, image)
+        if text is None:
+            return None
+        ids = [int(t) for t in self.processor.tokenizer.encode(text)]
+        return ids[:int(getattr(self.model, "max_seq_len", len(ids)))] or None
+
     def _ngram_fields(self) -> dict:
         """the no_repeat_ngram_* settings that are set, under the names generate() and the server share"""
         return {k: v for k, v in (("no_repeat_ngram_size", self.no_repeat_ngram_size), ("no_repeat_ngram_window", self.no_repeat_ngram_window),
                                   ("no_repeat_ngram_whitelist", self.no_repeat_ngram_whitelist)) if v is not None}
 
-    def _inference_batch_with_hf(self, images, prompts) -> List[str]:
+    def _inference_batch_with_hf(self, images, prompts, page0: int = 0) -> List[str]:
         inputs = self._build_inputs(images, prompts)
         kw = self._ngram_fields()
+        if self.prediction is not None:              # page0: the page index of images[0]
+            kw["prediction_ids"] = [self._prediction_ids(page0 + i, im) for i, im in enumerate(images)]
         if self.speculative_ngram:
             kw.update(speculative_ngram=self.speculative_ngram, prompt_lookup_min=self.prompt_lookup_min, prompt_lookup_max=self.prompt_lookup_max)
             if self.speculative_rows is not None:
@@ -382,12 +411,14 @@ class DotsOCRParser:
                                            for j in range(len(lps))]
         return out
 
-    def _inference_with_hf(self, image, prompt) -> str:
-        return self._inference_batch_with_hf([image], [prompt])[0]
+    def _inference_with_hf(self, image, prompt, page_idx: int = 0) -> str:
+        return self._inference_batch_with_hf([image], [prompt], page_idx)[0]
 
-    def _inference_with_vllm(self, image, prompt):
+    def _inference_with_vllm(self, image, prompt, page_idx: int = 0):
         from dots_ocr.model.inference import inference_with_vllm
+        pred = self._prediction_text(page_idx, image)
         extra = {**({"guided_layout": True} if self._guided_layout([prompt]) else {}), **self._ngram_fields(),
+                 **({"prediction": {"type": "content", "content": pred}} if pred else {}),
                  **({"stop": self.stop} if self.stop else {}), **self._loop_field(),
                  **({"use_beam_search": True, "beam_width": self.num_beams, "length_penalty": self.length_penalty} if self.num_beams else {})}
         return inference_with_vllm(image, prompt, model_name=self.model_name, protocol=self.protocol, ip=self.ip,
@@ -462,7 +493,7 @@ class DotsOCRParser:
     def _parse_single_image(self, origin_image, prompt_mode, save_dir, save_name, source="image", page_idx=0, bbox=None,
                             fitz_preprocess=False):
         image, prompt, mn, mx = self._prepare(origin_image, prompt_mode, source, bbox, fitz_preprocess)
-        response = self._inference_with_hf(image, prompt) if self.use_hf else self._inference_with_vllm(image, prompt)
+        response = self._inference_with_hf(image, prompt, page_idx) if self.use_hf else self._inference_with_vllm(image, prompt, page_idx)
         if source == "pdf":
             save_name = f"{save_name}_page_{page_idx}"
         return self._save(response, origin_image, image, prompt_mode, save_dir, save_name, page_idx, mn, mx)
@@ -500,7 +531,8 @@ class DotsOCRParser:
                     ids = ids[inputs["attention_mask"][0].bool()].cpu().numpy()
                     grid = None if "image_grid_thw" not in inputs else inputs["image_grid_thw"].cpu().numpy()
                     cb.submit(Request(ids, inputs.get("pixel_values"), grid, self.hf_max_new_tokens, tag=nxt,
-                                      image_key=self._image_key(image, grid) if self.enable_prefix_caching and grid is not None else None))
+                                      image_key=self._image_key(image, grid) if self.enable_prefix_caching and grid is not None else None,
+                                      prediction=self._prediction_ids(nxt, image)))
                     nxt += 1
                 for _, req, toks in cb.step():
                     i = req.tag
@@ -524,7 +556,7 @@ class DotsOCRParser:
         else:
             from multiprocessing.pool import ThreadPool
             with ThreadPool(max(1, min(len(images), self.num_thread))) as pool:
-                responses = pool.starmap(self._inference_with_vllm, [(p[0], p[1]) for p in prepared])
+                responses = pool.starmap(self._inference_with_vllm, [(p[0], p[1], i) for i, p in enumerate(prepared)])
         results = []
         for i, (im, p, resp) in enumerate(zip(images, prepared, responses)):
             r = self._save(resp, im, p[0], prompt_mode, save_dir, f"{filename}_page_{i}", i, p[2], p[3])

@@ -1,6 +1,8 @@
 """What a request can ask of its decode row, in one table: the host-side mirror of RowFeature in csrc/row_stage.h, plus the two row
 settings the selection stage does not own (logprobs, stream).  The scheduler, generate()'s static batches and the server's capability
-probes all walk ROW_FEATURES; a new per-row feature is one entry here (DESIGN §6.1 lists the other places to touch).
+probes all walk ROW_FEATURES; a new per-row feature is one entry here (DESIGN §6.1 lists the other places to touch).  A request's
+prediction is not in the table: it shapes nothing a row selects, only what a speculating step drafts, and travels beside
+it — the scheduler sets it with the row's features before the prefill and clears it when the slot is admitted without one.
 
 Host-only: no torch, no engine import.  A "request" is anything with the eight fields (scheduler.Request); `held` is the caller's record
 of what its rows hold, row -> {feature name -> the value given to the engine}, and has no entry for a row that holds nothing."""

@@ -82,6 +82,10 @@ class Request:
                                                 # scheduler's thread once per sequence that has new tokens or has just finished, before the request is
                                                 # reported; index = 0, the fork index of n > 1, or the prompt index of suffixes.  The tokens of all calls
                                                 # for an index, concatenated, are the request's outputs[index]; logprobs in the layout of row_logprobs
+    prediction: Optional[Sequence[int]] = None  # predicted outputs: token ids the output is expected to resemble; a speculating engine
+                                                # drafts from them, and the tokens are those of the same request without it.  A hint: stored and inert
+                                                # on an engine that does not speculate.  One sequence only (no n > 1, beams, suffixes or score).  A
+                                                # finished request carries prediction_stats = Engine.row_prediction_stats(slot)
     image_key: Optional[bytes] = None           # prefix caching: 16 bytes, the caller's promise that equal keys mean equal pixels and
                                                 # grid.  An image request without one bypasses the cache.  A finished request carries cached_tokens
 
@@ -202,6 +206,7 @@ class ContinuousBatcher:
         self.admissions = 0
         self._last_lens: Dict[int, int] = {}                     # slot -> tokens generated as of the last poll
         self._rows: Dict[int, Dict[str, object]] = {}            # slot -> feature name -> the value set on it (row_features.ROW_FEATURES)
+        self._predicted: set = set()                             # slots that hold a prediction (beside the table: row_features)
         self._streamed: Dict[int, int] = {}                      # streaming slot -> tokens of its sequence handed to the callback so far
         self._cancel: set = set()                                # request ids cancelled while being admitted: cancelled by the first collect that sees them running
         self._cancelled: List[Tuple[int, Request, np.ndarray]] = []   # cancelled requests (reported by step())
@@ -244,6 +249,8 @@ class ContinuousBatcher:
             raise ValueError(f"n must be an integer >= 1, got {req.n!r}")
         if req.n > self.n_slots:
             raise ValueError(f"n = {req.n} sequences need more than the {self.n_slots} usable slots")
+        if req.prediction is not None:
+            self._check_prediction(req)
         if req.stream is not None:
             self._check_stream(req)
         if req.score is not None:
@@ -292,6 +299,25 @@ class ContinuousBatcher:
         return rid
 
     MAX_SUFFIXES = 8
+
+    def _check_prediction(self, req: Request):
+        """a prediction belongs to one generated sequence: what would need several, or generates nothing, is refused whole"""
+        for bad, what in ((req.n > 1, "n > 1"), (req.num_beams is not None, "num_beams"), (req.score is not None, "score"),
+                          (req.suffixes is not None, "suffixes")):
+            if bad:
+                raise RequestRejected(f"a prediction cannot be combined with {what}: it belongs to one generated sequence")
+        if not hasattr(self.engine, "set_row_prediction"):
+            raise RequestRejected("a prediction needs continuous batching on an engine that takes one (Engine.set_row_prediction): not with static batching")
+        try:
+            ids = [int(t) for t in req.prediction]
+        except (TypeError, ValueError):
+            raise RequestRejected(f"prediction must be a list of token ids, got {req.prediction!r}")
+        vocab = getattr(getattr(self.engine, "cfg", None), "vocab_size", None)
+        if any(t < 0 or (vocab is not None and t >= vocab) for t in ids):
+            raise RequestRejected(f"the prediction holds a token id outside [0, {vocab})")
+        if len(ids) > self.max_seq_len:
+            raise RequestRejected(f"a prediction of {len(ids)} tokens is longer than max_seq_len = {self.max_seq_len}")
+        req.prediction = ids
 
     def _check_score(self, req: Request):
         """what only a score request is asked; _check_suffixes then asks what it asks of several prompts.  There is nothing
@@ -531,11 +557,22 @@ class ContinuousBatcher:
     def _clear_rows(self, slots):
         """no per-row entry stays on these (free) slots: it would keep the per-row stage on"""
         clear_rows(self.engine, self._rows, slots)
+        for s in slots:
+            if s in self._predicted:
+                self._predicted.discard(s)
+                self.engine.set_row_prediction(s, None)
 
     def _set_rows(self, s, r, index: int = 0):
         """per-row parameters of request r on slot s; they apply from the first token the prefill selects.  index: the sequence of a
         request with n > 1 — its seed is the request's + index (vLLM's rule), everything else is shared"""
         apply_row(self.engine, self._rows, s, r, index)
+        # the prediction travels beside the table (row_features): set before the prefill, cleared when the slot is admitted without one
+        if r.prediction:
+            self._predicted.add(s)
+            self.engine.set_row_prediction(s, r.prediction)
+        elif s in self._predicted:
+            self._predicted.discard(s)
+            self.engine.set_row_prediction(s, None)
 
     def _prefill(self, group, rows_set: bool = False):
         # image rows are consumed in packed order, so sequences with images keep their relative order: pack the group as is
@@ -803,6 +840,8 @@ class ContinuousBatcher:
                 loop_hit = None
                 if req.loop is not None:             # likewise: the release clears the row's rule and its hit record
                     loop_hit = self.engine.row_loop_hit(s)
+                if req.prediction:                   # likewise: the release clears the prediction, the next prefill its counters
+                    req.prediction_stats = self.engine.row_prediction_stats(s)
                 if req.stream is not None:
                     # its last tokens, before it is reported: what the drain brought, and — a row that held more than one drain
                     # delivers — the rest of what was just read
@@ -904,6 +943,7 @@ class ContinuousBatcher:
             if s in self.suspended:
                 self.suspended.remove(s)
         cancel_rows(self.engine, self._rows, slots)  # the release switched the rows off: the handles' records go too
+        self._predicted.difference_update(slots)     # ... and cleared their predictions
         if hasattr(req, "_parts"):
             del req._parts
         self._report_cancelled(rid, req, [outs.get(j, np.zeros(0, np.int32)) for j in range(max(1, req.seqs if not req.num_beams else 1))])

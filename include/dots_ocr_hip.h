@@ -454,6 +454,37 @@ int dots_set_speculation_logprobs(DotsEngine* e, int on);
 int dots_set_row_drafts(DotsEngine* e, int row, const int32_t* ids_host, int n);
 int dots_spec_stats(DotsEngine* e, int row, int64_t* steps, int64_t* drafted, int64_t* accepted);
 
+/* Predicted outputs: a slot may hold a PREDICTION, a text the caller expects the output to resemble (a PDF's text layer,
+ * another engine's result, an earlier run).  While the engine speculates with its built-in drafter (k > 0, max_n > 0) a second drafter
+ * runs at the end of every step, on the GPU, and proposes the prediction's tokens as the slot's drafts where it can align the grown output
+ * with it.  A prediction only changes which tokens are PROPOSED: every draft is verified by the step that follows exactly as an n-gram
+ * draft is, so tokens, logprobs and stop hits are those of the unspeculated engine whatever the prediction holds.
+ *
+ * The rule.  out[0 .. L) is the slot's output, pred[0 .. P) its prediction; k, min_n, max_n are dots_set_speculation's.  The slot keeps an
+ * alignment (cur, at): prediction index cur was where the next token was expected when the output was `at` long, so now it is expected
+ * at e* = cur + (L - at).  cur = at = 0 when the prediction is set and when the slot is prefilled.
+ *   1. anchor  m = min(min_n, L, e*).  If m >= 1, e* < P and pred[e* - m .. e*) == out[L - m .. L): e = e*.
+ *   2. search  otherwise, for n from min(max_n, L) down to min_n with key = out[L - n .. L): the candidates are the e = i + n < P with
+ *              pred[i .. i + n) == key.  The first n that has a candidate wins; among its candidates the one nearest to e*, the larger e
+ *              on a tie.
+ *   3. found   the slot's drafts are pred[e .. min(e + k, P)); cur = e, at = L.
+ *   4. else    (or the slot holds no prediction) the slot keeps the drafts the own-output rule above left; cur and at stay, so e* moves on
+ *              with L.
+ * Rows that take no step, finished rows and rows that do not speculate are left alone, as by the built-in drafter.
+ *
+ * dots_set_row_prediction  slot `row` holds ids_host[0 .. n) from now on (copied; stream ordered), aligned with the start of its output.
+ *                       n = 0 or ids_host = NULL: it holds none, and drafts it took from the one it held are dropped.  May be called
+ *                       before the slot's prefill, like the other row setters.  dots_slots_prefill (and the chunked and cached forms)
+ *                       restart the alignment and the counters; dots_slot_release and dots_slots_reset clear the prediction.  A fork's
+ *                       children, beams, extends and scores carry none.  On an engine that does not speculate, or speculates with
+ *                       max_n = 0, it is stored and inert.  While no slot holds one a step launches exactly what it launched before.  The
+ *                       first call that sets one allocates max_batch x max_seq_len int32.  DOTS_E_INVALID: row out of range, n < 0, an id
+ *                       outside [0, vocab); DOTS_E_CAPACITY: n > max_seq_len.
+ * dots_row_prediction_stats  prediction tokens the row verified as drafts (after the generation cap cut them, as dots_spec_stats counts)
+ *                       and prediction tokens it committed, since the row's prefill.  dots_spec_stats counts them too, unchanged. */
+int dots_set_row_prediction(DotsEngine* e, int row, const int32_t* ids_host, int n);
+int dots_row_prediction_stats(DotsEngine* e, int row, int64_t* drafted, int64_t* accepted);
+
 /* Log-probabilities: log_softmax of the raw fp32 logits of the step (before penalties, temperature, top-k and top-p:
  * the values dots_get_logits returns), for every token a row commits, the prefill's first token included.  The top entries are
  * ordered by value descending, then index ascending.  lse comes from per-chunk (max, sum) pairs merged in a fixed chunk order, so a
@@ -916,6 +947,14 @@ int dots_op_spec_guide_masks(DotsEngine* e, int rows, int k, const int32_t* guid
                              const int32_t* n_live_host, int32_t* states_out_host, uint32_t* mask_out_host);
 int dots_op_ngram_draft(DotsEngine* e, const int32_t* hist_dev, const int32_t* hist_lens_dev, int hist_stride, int B, int k, int min_n, int max_n,
                         int32_t* drafts_dev, int32_t* n_drafts_dev);
+/* The prediction drafter alone (predict_draft_kernel, the rule at dots_set_row_prediction) on caller-supplied device arrays: pred int32
+ * [B][pred_stride] with pred_lens [B], hist int32 [B][hist_stride] with hist_lens [B], and the alignments cur / at int32 [B], read and —
+ * for a row the rule finds a position for — written (0 <= cur, at < 2^30).  Such a row gets drafts [B][k], n_drafts [B] and src = 1;
+ * every other row keeps drafts, n_drafts, cur and at as the caller set them and gets src = 0.  Every row drafts: no finished /
+ * selection state is read. */
+int dots_op_predict_draft(DotsEngine* e, const int32_t* pred_dev, const int32_t* pred_lens_dev, int pred_stride, const int32_t* hist_dev,
+                          const int32_t* hist_lens_dev, int hist_stride, int B, int k, int min_n, int max_n, int32_t* cur_dev, int32_t* at_dev,
+                          int32_t* drafts_dev, int32_t* n_drafts_dev, int32_t* src_dev);
 /* The log-probability stage over caller logits: logits_dev fp32 [B, ld] (V <= ld), top_n_host [B] (-1 = row skipped, 0..20),
  * chosen_dev int32 [B] the chosen ids; writes tok_lp_dev float [B], top_ids_dev int32 [B][20], top_lp_dev float [B][20] of every row
  * with top_n >= 0 (entries beyond top_n: -1 / NaN).  The same two kernels the engine runs. */
